@@ -32,7 +32,7 @@ With N ranks (one per GPU) every rank proves and verifies its own 1024 proofs â€
                      (dot_ring_amd/parallel.py, dr_comm_*), `rccl_ranks` = ncclCommCount
 No PyTorch anywhere: a launcher only has to export RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT.
 
-Launch: python bench.py [--gpus N --steps K --warmup W].  For N > 1 either through torch.distributed.run (one rank per GPU) or as
+Launch: python bench.py [--gpus N --steps K --warmup W --dump-outputs DIR].  For N > 1 either through torch.distributed.run (one rank per GPU) or as
 this bare command: with no RANK in the environment the process starts the N rank processes itself (fresh children, before any
 GPU call of its own â€” the shape of the reference's tests/benchmark/bench_ring_proof.py:168-182), relays rank 0's JSON line and
 exits with the worst child's code.  A collective that fails or stalls still prints the line, and the exit code is non-zero.
@@ -382,6 +382,7 @@ class RingWorkload:
         self.ads = [b"bench-batch-ad" + (first_index + i).to_bytes(8, "little") for i in range(batch)]
         self.sks, self.pks = [self.signer_sk] * batch, [self.signer_pk] * batch
         self.prove_s = self.verify_s = 0.0
+        self.last_proofs, self.last_ok = None, None          # what the last step of run() returned (for --dump-outputs)
 
     def distinct_signers(self):
         """every proof signed by another ring member (ring_size >= batch)"""
@@ -410,7 +411,8 @@ class RingWorkload:
         t0 = time.perf_counter()
         all_ok = True
         for _ in range(steps):
-            _, ok = self.step()
+            self.last_proofs, ok = self.step()
+            self.last_ok = ok
             all_ok = all_ok and ok
         barrier()
         return time.perf_counter() - t0, all_ok
@@ -454,6 +456,37 @@ class RingWorkload:
         ok = ok and [p.encode() for p in gpu_proofs] == cpu_proofs
         ok = ok and self.vrf.batch_verify(gpu_proofs, self.alphas[:m], self.ads[:m], tv_ring, tv_root)
         return ok, cpu_proofs, cpu_s
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_step_outputs(out_dir: str, proofs, ok, ped: int) -> dict:
+    """--dump-outputs: what one prove_batch + batch_verify step handed its caller, as float32 .npy files under out_dir.
+
+    pedersen_proof.npy  (n, ped)  the first `ped` (192) bytes of each 784-byte proof: the VRF output point, the blinded key, R, Ok, s, sb.  A
+                                  function of the inputs alone (deterministic nonces), so two builds can be compared byte for byte.
+    batch_verify.npy    (1,)      1.0 if batch_verify accepted the step's proofs.
+    proof_index.npy     (n,)      which proofs of the batch the rows are (all of them, unless a seeded sample had to fit the cap).
+    The ring-proof part of each proof (the remaining 592 bytes) is left out: its hidden rows are drawn from the OS CSPRNG on every call, as in
+    production, so those bytes differ from run to run by design; the batch_verify verdict stands for them."""
+    import random
+
+    import numpy as np
+
+    raw = [p.encode() for p in proofs]
+    index = list(range(len(raw)))
+    if len(raw) * (ped + 1) * 4 > DUMP_MAX_BYTES:                      # a fixed, seeded sample of the batch
+        index = sorted(random.Random(20241015).sample(index, DUMP_MAX_BYTES // ((ped + 1) * 4) - 1))
+    arrays = {
+        "pedersen_proof": np.frombuffer(b"".join(raw[i][:ped] for i in index), dtype=np.uint8).reshape(len(index), ped).astype(np.float32),
+        "batch_verify": np.array([1.0 if ok else 0.0], dtype=np.float32),
+        "proof_index": np.array(index, dtype=np.float32),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": {name: list(a.shape) for name, a in arrays.items()}}
 
 
 def ring_roofline(w: "RingWorkload", steps: int, barrier=lambda: None):
@@ -832,7 +865,11 @@ def main() -> int:
     ap.add_argument("--cpu-workers", type=int, default=-1, help="processes of the all-cores CPU baseline (-1 = min(16, cores), 0 = skip)")
     ap.add_argument("--msm-log2n", type=int, default=20, help="secondary G1 MSM size (0 = skip)")
     ap.add_argument("--extras", type=int, default=1, help="0 = skip the secondary legs (bsn_scalar_mul, other ring sizes, distinct signers)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's batch) to DIR/<name>.npy, float32, at most 64 MB")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "RANK" not in os.environ and args.gpus > 1:
         return launch_ranks(args.gpus, sys.argv[1:])
@@ -884,6 +921,7 @@ def main() -> int:
     # ---- timed region: per-kernel timers off
     elapsed, all_ok = w.run(args.steps, args.warmup, barrier)
     prove_s, verify_s = w.prove_s, w.verify_s
+    dumped = dump_step_outputs(args.dump_outputs, w.last_proofs, w.last_ok, d.PedersenVRF[w.cv].proof_len()) if args.dump_outputs and rank == 0 else None
     if ctl is not None:
         stats = [struct.unpack("<dB", b) for b in ctl.all_gather(struct.pack("<dB", elapsed, 1 if all_ok else 0))]
         elapsed, all_ok = max(s[0] for s in stats), all(s[1] for s in stats)
@@ -1043,6 +1081,7 @@ def main() -> int:
                              "sweep": threads_sweep} ,
             "ring_root_s": w.ring_root_s,
             "setup_s": setup_s,
+            "dumped_outputs": dumped,
         }
         if not parity_ok:
             print("bench.py: PARITY FAILURE â€” GPU result differs from the oracle", file=sys.stderr)

@@ -423,10 +423,14 @@ def test_g1_msm_degenerate_scalars_at_full_size_within_twice_the_random_time(ctx
         assert got == _closed_form_be(col), name
         for _ in range(2):
             ctx.g1_msm_dev(srs, d, n)
-        t0 = time.perf_counter()
-        for _ in range(4):
+        # the fastest of six calls (each returns its point to the host, so each ends in a synchronise): other work on a shared
+        # host or GPU only ever adds time, and a mean carries it into the ratio
+        best = float("inf")
+        for _ in range(6):
+            t0 = time.perf_counter()
             ctx.g1_msm_dev(srs, d, n)
-        times[name] = (time.perf_counter() - t0) / 4
+            best = min(best, time.perf_counter() - t0)
+        times[name] = best
         d.free()
     srs.close()
     for name, t in times.items():
