@@ -99,6 +99,8 @@ _PROTOTYPES.update({
                                         POINTER(ctypes.c_uint64), c_char_p, POINTER(ctypes.c_uint64), c_char_p, POINTER(ctypes.c_uint64),
                                         c_char_p, POINTER(c_int)]),
     "dr_g1_decompress_batch": (c_int, [c_void_p, c_char_p, c_size_t, c_char_p, c_char_p]),
+    "dr_fq_ops_selftest": (c_int, [c_void_p, c_char_p, c_size_t, c_void_p]),
+    "dr_g1_ops_selftest": (c_int, [c_void_p, c_char_p, c_size_t, c_void_p]),
     "dr_bsn_decode_points": (c_int, [c_void_p, c_char_p, c_size_t, c_char_p, c_char_p]),
     "dr_te_scalar_mul_batch": (c_int, [c_void_p, c_int, c_char_p, c_char_p, c_size_t, c_void_p]),
     "dr_te_msm": (c_int, [c_void_p, c_int, c_char_p, c_char_p, c_size_t, c_void_p]),
@@ -521,6 +523,24 @@ class Context:
         out, flags = ctypes.create_string_buffer(max(1, 384 * n)), ctypes.create_string_buffer(max(1, n))
         _check(lib().dr_fr_ops_selftest(self.handle, a, b, n, out, flags))
         return out.raw[: 384 * n], flags.raw[:n]
+
+    def fq_ops_selftest(self, records: bytes) -> bytes:
+        """dr_fq_ops_selftest: n records of 64 little-endian int32 (op, four 14-limb operands) -> n records of 16 int32."""
+        n = len(records) // 256
+        if len(records) != 256 * n:
+            raise ValueError("records are 64 words each")
+        out = ctypes.create_string_buffer(max(1, 64 * n))
+        _check(lib().dr_fq_ops_selftest(self.handle, records, n, out))
+        return out.raw[: 64 * n]
+
+    def g1_ops_selftest(self, records: bytes) -> bytes:
+        """dr_g1_ops_selftest: n records of 192 words (XYZZ images P, Q, affine A) -> n records of 32 x 60 words."""
+        n = len(records) // 768
+        if len(records) != 768 * n:
+            raise ValueError("records are 192 words each")
+        out = ctypes.create_string_buffer(max(1, 7680 * n))
+        _check(lib().dr_g1_ops_selftest(self.handle, records, n, out))
+        return out.raw[: 7680 * n]
 
     # ---- seam A
     # (curve = CURVE_BANDERSNATCH / CURVE_JUBJUB; the default goes through the dr_bsn_* names of the original seam)

@@ -1299,6 +1299,40 @@ int dr_g1_decompress_batch(dr_ctx* ctx, const uint8_t* enc, size_t n, uint8_t* o
     return DR_OK;
 }
 
+int dr_fq_ops_selftest(dr_ctx* ctx, const int32_t* in, size_t n, int32_t* out) {
+    TRY(use_ctx(ctx));
+    if (n == 0) return DR_OK;
+    if (!in || !out) return fail(DR_ERR_INVALID, "null buffer");
+    if (n >= (1ull << 24)) return fail(DR_ERR_INVALID, "batch too large");
+    const size_t in_bytes = n * dr::FQ_SELFTEST_IN_WORDS * 4, out_bytes = n * dr::FQ_SELFTEST_OUT_WORDS * 4;
+    TRY(ctx->io_a.reserve(in_bytes));
+    TRY(ctx->io_b.reserve(out_bytes));
+    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(dr::k_fq_ops_selftest, dim3(div_up(n, 64)), dim3(64), 0, ctx->stream, ctx->io_a.as<int32_t>(), (uint32_t)n,
+                       ctx->io_b.as<int32_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, ctx->io_b.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return DR_OK;
+}
+
+int dr_g1_ops_selftest(dr_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out) {
+    TRY(use_ctx(ctx));
+    if (n == 0) return DR_OK;
+    if (!in || !out) return fail(DR_ERR_INVALID, "null buffer");
+    if (n >= (1ull << 20)) return fail(DR_ERR_INVALID, "batch too large");
+    const size_t in_bytes = n * dr::G1_SELFTEST_IN_WORDS * 4, out_bytes = n * dr::G1_SELFTEST_OUT_WORDS * 4;
+    TRY(ctx->io_a.reserve(in_bytes));
+    TRY(ctx->io_b.reserve(out_bytes));
+    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(dr::k_g1_ops_selftest, dim3(div_up(n, 64)), dim3(64), 0, ctx->stream, ctx->io_a.as<uint32_t>(), (uint32_t)n,
+                       ctx->io_b.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, ctx->io_b.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return DR_OK;
+}
+
 int dr_g1_serialize_check(const uint8_t xy[96]) {
     std::vector<uint8_t> le;
     return g1_be_to_le_limbs(xy, 1, le, true);

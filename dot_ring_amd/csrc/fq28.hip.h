@@ -156,7 +156,7 @@ DR_DEV Fq28 mul_cxx(const Fq28& a, const Fq28& b) {
 }
 
 // a^2: the off-diagonal products once, against the doubled operand (105 + 196 multiply-adds instead of 392).
-// Needs 14 * 2 max|a_i|^2 + 2^60 < 2^63: |a_i| <= 2^29.
+// Needs 14 * 2 max|a_i|^2 + 2^60 < 2^63: |a_i| < 2^29.
 DR_DEV Fq28 sqr_cxx(const Fq28& a) {
     using FP = Fq28Params;
     Fq28 r;

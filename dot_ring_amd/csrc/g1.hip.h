@@ -2,9 +2,13 @@
 // mixed add 8M+2S, full add 12M+2S, doubling 6M+4S (EFD "xyzz": madd-2008-s, add-2008-s, dbl-2008-s-1, a = 0).
 // The reference reaches this arithmetic through blst (dot_ring/ring_proof/pcs/kzg.py:147-175).
 //
-// Register forms (see fq28.hip.h): "N" = normal (a product, carry()'d, or canonical words unpacked: limbs in [0, 2^28)),
+// Register forms (see fq28.hip.h): "N" = limbs 0..12 in [0, 2^28) (a product, carry()'d, or canonical words unpacked),
 // "d" = difference of two N values (|limb| < 2^28).  A point in registers holds x: N, y: d, zz / zzz: N and an explicit
 // infinity flag — testing ZZ == 0 (mod p) on a lazy value would cost a canonicalisation per addition.
+// "N" names the limb form only: a carry()'d x is wider in value than a product's (-p/2, 1.5 p).  Value ranges of the outputs
+// (each is computed fresh from products, so chains do not widen them): x in (-5 p, 3 p) after madd / add, (-3.5 p, 2.5 p) after
+// a doubling; y in (-2 p, 2 p); zz, zzz in (-p/2, 1.5 p).  The consumers need |value| < 32 p for mul and < 8 p for canon28 /
+// is_zero_mod_p; the widest such operand is madd's P = U2 - x in (-3.5 p, 6.5 p).
 // In memory a point is canonical words, Montgomery form with R = 2^392: affine 96 B with (0,0) = infinity, XYZZ 192 B
 // with ZZ = 0 (all four coordinates zero) = infinity.
 #pragma once

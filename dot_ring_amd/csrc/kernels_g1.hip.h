@@ -169,6 +169,97 @@ __global__ __launch_bounds__(256) void k_g1_bases_from_mont(const uint32_t* base
     store_words12(q + 12, w);
 }
 
+// ---- diagnostics (dr_fq_ops_selftest, dr_g1_ops_selftest): the arithmetic of fq28.hip.h / g1.hip.h on raw register images,
+// so that a test can place operands on the edges of each register form and read back exactly what the device produced.
+// Separate kernels: nothing on the hot path calls them or changes for them.
+enum FqSelftestOp : uint32_t {
+    FQ_OP_MUL, FQ_OP_SQR, FQ_OP_MUL2, FQ_OP_ADD, FQ_OP_SUB, FQ_OP_CARRY, FQ_OP_CANON, FQ_OP_IS_ZERO, FQ_OP_MAYBE_ZERO, FQ_OP_INV,
+    FQ_OP_TO_MONT, FQ_OP_FROM_MONT, FQ_OP_UNPACK, FQ_OP_CNEG, FQ_OP_COUNT
+};
+constexpr uint32_t FQ_SELFTEST_IN_WORDS = 64;      // op, then four 14-limb operands a, b, c, d at words 1, 15, 29, 43
+constexpr uint32_t FQ_SELFTEST_OUT_WORDS = 16;     // 14 limbs (or 12 canonical words), flag at word 14
+
+// One lane per record, one operation per lane.  Word operands (to_mont28, unpack28) are the first 12 words of a; the outputs
+// of canon28 / from_mont28 are 12 words; is_zero_mod_p writes only its flag; maybe_zero_normal(mul(a, b)) writes the product
+// and the filter's answer; cneg negates a iff b.l[0] is odd.  An unknown op writes zeros.
+__global__ __launch_bounds__(64) void k_fq_ops_selftest(const int32_t* __restrict__ in, uint32_t n, int32_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t* rec = in + (size_t)i * FQ_SELFTEST_IN_WORDS;
+    Fq28 a, b, c, d;
+#pragma unroll
+    for (int k = 0; k < L28; k++) {
+        a.l[k] = rec[1 + k]; b.l[k] = rec[1 + L28 + k]; c.l[k] = rec[1 + 2 * L28 + k]; d.l[k] = rec[1 + 3 * L28 + k];
+    }
+    uint32_t w[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) w[k] = (uint32_t)a.l[k];
+    Fq28 r = Fq28::zero();
+    uint32_t flag = 0;
+    bool words = false;
+    switch ((uint32_t)rec[0]) {
+        case FQ_OP_MUL: r = mul(a, b); break;
+        case FQ_OP_SQR: r = sqr(a); break;
+        case FQ_OP_MUL2: r = mul2(a, b, c, d); break;
+        case FQ_OP_ADD: r = add(a, b); break;
+        case FQ_OP_SUB: r = sub(a, b); break;
+        case FQ_OP_CARRY: r = carry(a); break;
+        case FQ_OP_CANON: canon28(a, w); words = true; break;
+        case FQ_OP_IS_ZERO: flag = is_zero_mod_p(a) ? 1u : 0u; break;
+        case FQ_OP_MAYBE_ZERO: r = mul(a, b); flag = maybe_zero_normal(r) ? 1u : 0u; break;
+        case FQ_OP_INV: r = inv(a); break;
+        case FQ_OP_TO_MONT: r = to_mont28(w); break;
+        case FQ_OP_FROM_MONT: from_mont28(a, w); words = true; break;
+        case FQ_OP_UNPACK: r = unpack28(w); break;
+        case FQ_OP_CNEG: r = cneg(a, (b.l[0] & 1) != 0); break;
+        default: break;
+    }
+    int32_t* o = out + (size_t)i * FQ_SELFTEST_OUT_WORDS;
+#pragma unroll
+    for (int k = 0; k < L28; k++) o[k] = words ? (k < 12 ? (int32_t)w[k] : 0) : r.l[k];
+    o[L28] = (int32_t)flag;
+    o[L28 + 1] = 0;
+}
+
+// Per lane: P and Q as XYZZ register images (put_raw layout, stride 1) at words 0 and 64, the affine A at word 128 (x limbs,
+// y limbs, inf flag).  Out: G1_SELFTEST_SLOTS register images of G1_SELFTEST_SLOT_WORDS words each — g1_add(P, Q),
+// g1_madd(P, A), g1_dbl(P), g1_dbl_affine(A), g1_to_affine_dev(P) (as g1_from_affine of the result: zz = zzz = R mod p),
+// load_xyzz(store_xyzz(P)), the memory record store_xyzz wrote (48 canonical words), then the chain from P: step k is
+// madd(A), add(Q), dbl for k mod 3 = 0, 1, 2, every intermediate written out.
+constexpr uint32_t G1_SELFTEST_IN_WORDS = 192;
+constexpr uint32_t G1_SELFTEST_SLOT_WORDS = 60;    // XYZZ_RAW_WORDS, padded to 16-byte records (store_xyzz writes uint4)
+constexpr uint32_t G1_SELFTEST_CHAIN = 24;
+constexpr uint32_t G1_SELFTEST_SLOTS = 7 + G1_SELFTEST_CHAIN;
+constexpr uint32_t G1_SELFTEST_OUT_WORDS = (G1_SELFTEST_SLOTS + 1) * G1_SELFTEST_SLOT_WORDS;
+static_assert(XYZZ_RAW_WORDS <= G1_SELFTEST_SLOT_WORDS && G1_SELFTEST_SLOT_WORDS % 4 == 0 && G1_SELFTEST_OUT_WORDS % 4 == 0, "layout");
+
+__global__ __launch_bounds__(64) void k_g1_ops_selftest(const uint32_t* __restrict__ in, uint32_t n, uint32_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t* rec = in + (size_t)i * G1_SELFTEST_IN_WORDS;
+    const G1Xyzz P = get_raw(rec, 1), Q = get_raw(rec + 64, 1);
+    G1Affine A;
+#pragma unroll
+    for (int k = 0; k < L28; k++) { A.x.l[k] = (int32_t)rec[128 + k]; A.y.l[k] = (int32_t)rec[128 + L28 + k]; }
+    A.inf = rec[128 + 2 * L28];
+    uint32_t* o = out + (size_t)i * G1_SELFTEST_OUT_WORDS;
+    put_raw(o + 0 * G1_SELFTEST_SLOT_WORDS, 1, g1_add(P, Q));
+    put_raw(o + 1 * G1_SELFTEST_SLOT_WORDS, 1, g1_madd(P, A));
+    put_raw(o + 2 * G1_SELFTEST_SLOT_WORDS, 1, g1_dbl(P));
+    put_raw(o + 3 * G1_SELFTEST_SLOT_WORDS, 1, g1_dbl_affine(A));
+    put_raw(o + 4 * G1_SELFTEST_SLOT_WORDS, 1, g1_from_affine(g1_to_affine_dev(P)));
+    uint32_t* mem = o + 6 * G1_SELFTEST_SLOT_WORDS;
+    store_xyzz(mem, 0, P);
+    put_raw(o + 5 * G1_SELFTEST_SLOT_WORDS, 1, load_xyzz(mem, 0));
+    G1Xyzz acc = P;
+#pragma unroll 1
+    for (uint32_t k = 0; k < G1_SELFTEST_CHAIN; k++) {
+        const uint32_t step = k % 3;
+        acc = step == 0 ? g1_madd(acc, A) : step == 1 ? g1_add(acc, Q) : g1_dbl(acc);
+        put_raw(o + (7 + k) * G1_SELFTEST_SLOT_WORDS, 1, acc);
+    }
+}
+
 // (WindowTable — how the 256 scalar bits are tiled by windows — lives in dev_types.hpp: the host plans it.)
 
 // ---- 1. signed window digits + bucket histogram.  One lane per scalar.

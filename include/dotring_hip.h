@@ -217,6 +217,21 @@ DR_API int dr_g1_serialize_check(const uint8_t xy[96]);
  * malformed encodings (compression flag missing, x >= p, x not on the curve, non-canonical infinity). */
 DR_API int dr_g1_decompress_batch(dr_ctx *ctx, const uint8_t *enc /* n*48 */, size_t n, uint8_t *out_be_xy /* n*96 */, uint8_t *ok /* n */);                              /* DR_OK iff on curve or infinity */
 
+/* Diagnostic: single operations of the base field the G1 kernels compute in (csrc/fq28.hip.h: 14 signed limbs of 28 bits, lazy
+ * reduction, Montgomery R = 2^392) on RAW limb images, so that tests can place operands on the edges of each register form.
+ * in: n records of 64 int32 — word 0 the op (0 mul a b, 1 sqr a, 2 mul2 a b + c d, 3 add, 4 sub, 5 carry, 6 canon28, 7 is_zero_mod_p,
+ * 8 maybe_zero_normal(mul a b), 9 inv, 10 to_mont28, 11 from_mont28, 12 unpack28, 13 cneg a if b[0] is odd), then the 14 limbs
+ * of a, b, c, d at words 1, 15, 29, 43 (the word operands of to_mont28 / unpack28 are a's first 12 words).  out: n records of 16
+ * int32 — the 14 result limbs (12 canonical words for canon28 / from_mont28), the flag of is_zero_mod_p / maybe_zero_normal
+ * at word 14. */
+DR_API int dr_fq_ops_selftest(dr_ctx *ctx, const int32_t *in /* n*64 */, size_t n, int32_t *out /* n*16 */);
+/* Diagnostic: the XYZZ group law of csrc/g1.hip.h on raw register images.  in: n records of 192 words — P and Q as XYZZ
+ * images (x, y, zz, zzz limbs, then the infinity flag: 57 words) at words 0 and 64, an affine A (x, y limbs, flag) at word
+ * 128.  out: n records of 32 x 60 words — register images (57 words each, 60-word slots) of P + Q, P + A, 2P, 2A,
+ * to_affine(P) (with zz = zzz = R mod p), P stored to memory and loaded back, the 48 canonical words that store wrote, then
+ * 24 chained steps from P: madd A, add Q, dbl, repeated. */
+DR_API int dr_g1_ops_selftest(dr_ctx *ctx, const uint32_t *in /* n*192 */, size_t n, uint32_t *out /* n*1920 */);
+
 /* ---- seam C: NTT over Fr ------------------------------------------------------------------------
  * Replaces BlsScalarNTTPlan.transform / transform_scaled (dot_ring/ring_proof/polynomial/ntt.pyx:104-163,
  * bls_scalar_ntt_round in bls12_381_scalar.c:333): `batch` in-place radix-2 transforms of size 2^log2n with
