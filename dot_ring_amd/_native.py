@@ -187,7 +187,12 @@ def _ragged(items):
     return b"".join(items), (ctypes.c_uint64 * len(off)).from_buffer(off)
 
 
-CURVE_BANDERSNATCH, CURVE_JUBJUB = 0, 1
+CURVE_BANDERSNATCH, CURVE_JUBJUB, CURVE_BANDERSNATCH_SW = 0, 1, 2
+
+
+def suite_point_len(suite: "VrfSuiteStruct") -> int:
+    """bytes of an encoded point of the suite: 33 for the short Weierstrass suite, 32 otherwise"""
+    return 33 if suite.curve == CURVE_BANDERSNATCH_SW else 32
 
 
 def vrf_suite(suite_id: bytes, xof: bool, generator_xy: bytes, blinding_base_xy: bytes, curve: int = CURVE_BANDERSNATCH) -> VrfSuiteStruct:
@@ -642,10 +647,12 @@ class Context:
         return pts, ok.raw[:count]
 
     def bsn_decode_points(self, enc: bytes, curve: int = CURVE_BANDERSNATCH):
-        """dec_point for len(enc)/32 compressed points on the GPU -> (affine x||y bytes, validity flags)."""
-        if len(enc) % 32:
-            raise ValueError("compressed points are 32 bytes each")
-        count = len(enc) // 32
+        """dec_point for len(enc)/32 compressed points on the GPU (33 bytes each, SW affine out, for CURVE_BANDERSNATCH_SW)
+        -> (affine x||y bytes, validity flags)."""
+        width = 33 if curve == CURVE_BANDERSNATCH_SW else 32
+        if len(enc) % width:
+            raise ValueError(f"compressed points are {width} bytes each")
+        count = len(enc) // width
         out, ok = ctypes.create_string_buffer(max(1, 64 * count)), ctypes.create_string_buffer(max(1, count))
         if curve == CURVE_BANDERSNATCH:
             _check(lib().dr_bsn_decode_points(self.handle, enc, count, out, ok))
@@ -654,18 +661,19 @@ class Context:
         return out.raw[: 64 * count], ok.raw[:count]
 
     def pedersen_prove_batch(self, suite: "VrfSuiteStruct", alphas, ads, salts, secret_scalars: bytes):
-        """dr_pedersen_prove_batch -> (batch * 192 proof bytes, batch * 288 auxiliary bytes)."""
-        batch = len(alphas)
+        """dr_pedersen_prove_batch -> (batch * (4 points + 64) proof bytes: 192 / 196 per suite, batch * 288 auxiliary bytes)."""
+        batch, plen = len(alphas), 4 * suite_point_len(suite) + 64
         a_blob, a_off = _ragged(alphas)
         d_blob, d_off = _ragged(ads)
         s_blob, s_off = (None, None) if not salts or not any(salts) else _ragged(salts)
-        out, aux = ctypes.create_string_buffer(max(1, 192 * batch)), ctypes.create_string_buffer(max(1, PEDERSEN_AUX_BYTES * batch))
+        out, aux = ctypes.create_string_buffer(max(1, plen * batch)), ctypes.create_string_buffer(max(1, PEDERSEN_AUX_BYTES * batch))
         _check(lib().dr_pedersen_prove_batch(self.handle, byref(suite), batch, a_blob, a_off, d_blob, d_off, s_blob, s_off, secret_scalars, out, aux))
-        return out.raw[: 192 * batch], aux.raw[: PEDERSEN_AUX_BYTES * batch]
+        return out.raw[: plen * batch], aux.raw[: PEDERSEN_AUX_BYTES * batch]
 
     def ietf_prove_batch(self, suite: "VrfSuiteStruct", thin: bool, alphas, ads, salts, secret_scalars: bytes):
-        """dr_ietf_prove_batch -> (batch * (96 if thin else 80) proof bytes, batch * 128 bytes: O and R affine)."""
-        batch, plen = len(alphas), 96 if thin else 80
+        """dr_ietf_prove_batch -> (batch * (96 if thin else 80) proof bytes — 98 / 81 for the SW suite —, batch * 128 bytes: O and R affine)."""
+        pl = suite_point_len(suite)
+        batch, plen = len(alphas), 2 * pl + 32 if thin else pl + 48
         a_blob, a_off = _ragged(alphas)
         d_blob, d_off = _ragged(ads)
         s_blob, s_off = (None, None) if not salts or not any(salts) else _ragged(salts)
@@ -689,9 +697,9 @@ class Context:
         return verdict.raw[:batch]
 
     def pedersen_verify_batch(self, suite: "VrfSuiteStruct", proofs: bytes, inputs, ads, salts) -> bool:
-        batch = len(inputs)
-        if len(proofs) != 192 * batch:
-            raise ValueError("proofs must be 192 bytes each")
+        batch, plen = len(inputs), 4 * suite_point_len(suite) + 64
+        if len(proofs) != plen * batch:
+            raise ValueError(f"proofs must be {plen} bytes each")
         i_blob, i_off = _ragged(inputs)
         d_blob, d_off = _ragged(ads)
         s_blob, s_off = (None, None) if not salts or not any(salts) else _ragged(salts)

@@ -16,6 +16,7 @@ struct PedersenBatch {
     const drh::VrfSuite& su;
     size_t B;
     std::vector<uint8_t> us, xs, inputs, outs, blind, gb_pts, sc, ybar, ks, kbs, pts3, sc3, third;
+    std::vector<uint8_t> outs_sw;            // SW suite: O in SW coordinates (its encoding and aux record)
     std::vector<drh::Bytes> tr;
     PedersenBatch(const drh::VrfSuite& s, size_t b) : su(s), B(b) {}
     ~PedersenBatch() {          // secret scalars, blinding factors and nonces (and the scalar vectors built from them) do not outlive the call
@@ -37,6 +38,20 @@ struct PedersenBatch {
         inputs.resize(B * 64); outs.resize(B * 64);
         TRY(encode_and_mul(ctx, su, B, alphas, alpha_off, salts, salt_off, xs.data(), inputs.data(), outs.data(), while_waiting));
         tr_.mark("encode+x*I");
+        // the SW suite encodes the SW images: (I_i, O_i) mapped pairwise, one inversion per proof
+        std::vector<uint8_t> io_store;
+        const uint8_t* io_c = nullptr;
+        if (su.cv->sw) {
+            std::vector<uint8_t> io(B * 128);
+            for (size_t i = 0; i < B; i++) {
+                std::memcpy(io.data() + 128 * i, inputs.data() + 64 * i, 64);
+                std::memcpy(io.data() + 128 * i + 64, outs.data() + 64 * i, 64);
+            }
+            TRY(suite_coords(ctx, su, io.data(), 2 * B, 2, io_store, &io_c));
+            outs_sw.resize(B * 64);
+            for (size_t i = 0; i < B; i++) std::memcpy(outs_sw.data() + 64 * i, io_c + 128 * i + 64, 64);
+        }
+        const size_t pl = su.point_len;
         // 3. transcripts, blinding factors
         tr.assign(B, drh::Bytes());
         blind.resize(B * 32); gb_pts.resize(B * 128); sc.resize(B * 64);
@@ -46,9 +61,9 @@ struct PedersenBatch {
             t = su.suite_id;
             drh::put8(t, 0x02);                                    // PEDERSEN_VRF
             drh::put_le64(t, 1);                                   // one (input, output) pair
-            uint8_t enc[32];
-            drh::enc_te_point(inputs.data() + 64 * i, enc); drh::put(t, enc, 32);
-            drh::enc_te_point(outs.data() + 64 * i, enc); drh::put(t, enc, 32);
+            uint8_t enc[33];
+            drh::enc_point(su, io_c ? io_c + 128 * i : inputs.data() + 64 * i, enc); drh::put(t, enc, pl);
+            drh::enc_point(su, io_c ? io_c + 128 * i + 64 : outs.data() + 64 * i, enc); drh::put(t, enc, pl);
             size_t adl = ad_off[i + 1] - ad_off[i];
             drh::put_le64(t, adl);
             drh::put(t, ads + ad_off[i], adl);
@@ -87,11 +102,15 @@ struct PedersenBatch {
         if (fixed) TRY(te_fixed_base_groups(actx, cv, gb, sc.data(), B, 2, ybar.data()));
         else TRY(te_msm_groups(actx, cv, gb_pts.data(), sc.data(), B, 2, ybar.data()));
         // 5. nonces
+        const size_t pl = su.point_len;
+        std::vector<uint8_t> ybar_store;
+        const uint8_t* ybar_c = nullptr;
+        TRY(suite_coords(actx, su, ybar.data(), B, 1, ybar_store, &ybar_c));
         std::vector<int> bad2(B, 0);
         drh::parallel_for(B, [&](size_t i) {
-            uint8_t enc[32];
-            drh::enc_te_point(ybar.data() + 64 * i, enc);
-            drh::put(tr[i], enc, 32);
+            uint8_t enc[33];
+            drh::enc_point(su, ybar_c + 64 * i, enc);
+            drh::put(tr[i], enc, pl);
             uint64_t x[4], b[4], k[4], kb[4];
             drh::load_le32(xs.data() + 32 * i, x);
             drh::load_le32(blind.data() + 32 * i, b);
@@ -116,29 +135,42 @@ struct PedersenBatch {
         } else {
             TRY(te_msm_groups(actx, cv, pts3.data(), sc3.data(), 2 * B, 2, third.data()));
         }
-        // 6. challenge, responses, the 192 encoded bytes
+        // 6. challenge, responses, the encoded proof (4 points, 2 scalars)
+        std::vector<uint8_t> rk_store;
+        const uint8_t* rk_c = nullptr;             // (R_i, O_k,i) pairs in the suite's coordinates
+        if (su.cv->sw) {
+            std::vector<uint8_t> rk(B * 128);
+            for (size_t i = 0; i < B; i++) {
+                std::memcpy(rk.data() + 128 * i, third.data() + 64 * i, 64);
+                std::memcpy(rk.data() + 128 * i + 64, third.data() + 64 * (B + i), 64);
+            }
+            TRY(suite_coords(actx, su, rk.data(), 2 * B, 2, rk_store, &rk_c));
+        }
+        const uint8_t* outs_c = su.cv->sw ? outs_sw.data() : outs.data();
+        auto r_of = [&](size_t i) { return rk_c ? rk_c + 128 * i : third.data() + 64 * i; };
+        auto ok_of = [&](size_t i) { return rk_c ? rk_c + 128 * i + 64 : third.data() + 64 * (B + i); };
         drh::parallel_for(B, [&](size_t i) {
             uint8_t* out = out_proofs + stride * i;
-            drh::enc_te_point(outs.data() + 64 * i, out);
-            drh::enc_te_point(ybar.data() + 64 * i, out + 32);
-            drh::enc_te_point(third.data() + 64 * i, out + 64);
-            drh::enc_te_point(third.data() + 64 * (B + i), out + 96);
+            drh::enc_point(su, outs_c + 64 * i, out);
+            drh::enc_point(su, ybar_c + 64 * i, out + pl);
+            drh::enc_point(su, r_of(i), out + 2 * pl);
+            drh::enc_point(su, ok_of(i), out + 3 * pl);
             uint64_t c[4], x[4], b[4], k[4], kb[4], s[4], sb[4];
-            drh::vrf_challenge(su, tr[i], out + 64, 2, c);
+            drh::vrf_challenge(su, tr[i], out + 2 * pl, 2, c);
             drh::load_le32(xs.data() + 32 * i, x);
             drh::load_le32(blind.data() + 32 * i, b);
             drh::load_le32(ks.data() + 32 * i, k);
             drh::load_le32(kbs.data() + 32 * i, kb);
             mn.mul(c, x, s);  mn.add(s, k, s);
             mn.mul(c, b, sb); mn.add(sb, kb, sb);
-            drh::store_le32(s, out + 128);
-            drh::store_le32(sb, out + 160);
-            if (out_aux) {
+            drh::store_le32(s, out + 4 * pl);
+            drh::store_le32(sb, out + 4 * pl + 32);
+            if (out_aux) {                                   // (in the suite's coordinates)
                 uint8_t* a = out_aux + aux_stride * i;
-                std::memcpy(a, outs.data() + 64 * i, 64);
-                std::memcpy(a + 64, ybar.data() + 64 * i, 64);
-                std::memcpy(a + 128, third.data() + 64 * i, 64);
-                std::memcpy(a + 192, third.data() + 64 * (B + i), 64);
+                std::memcpy(a, outs_c + 64 * i, 64);
+                std::memcpy(a + 64, ybar_c + 64 * i, 64);
+                std::memcpy(a + 128, r_of(i), 64);
+                std::memcpy(a + 192, ok_of(i), 64);
                 std::memcpy(a + 256, blind.data() + 32 * i, 32);
             }
         });
@@ -317,22 +349,26 @@ int pedersen_verify_core(dr_ctx* actx, const drh::VrfSuite& su, size_t B, const 
                                 const std::vector<uint8_t>& te_xy, const std::vector<uint8_t>& in_pts, const uint8_t* ads,
                                 const uint64_t* ad_off, int& ped_ok) {
     const drh::Mod256& mn = su.cv->n;
+    const size_t pl = su.point_len;
+    std::vector<uint8_t> in_store;
+    const uint8_t* in_c = nullptr;
+    TRY(suite_coords(actx, su, in_pts.data(), B, 1, in_store, &in_c));
     std::vector<uint8_t> cs(B * 32);
     drh::parallel_for(B, [&](size_t i) {
         const uint8_t* pr = proofs + stride * i;
         drh::Bytes t = su.suite_id;
         drh::put8(t, 0x02);
         drh::put_le64(t, 1);
-        uint8_t enc[32];
-        drh::enc_te_point(in_pts.data() + 64 * i, enc);
-        drh::put(t, enc, 32);
-        drh::put(t, pr, 32);                                   // output point, as encoded in the proof
+        uint8_t enc[33];
+        drh::enc_point(su, in_c + 64 * i, enc);
+        drh::put(t, enc, pl);
+        drh::put(t, pr, pl);                                   // output point, as encoded in the proof
         size_t adl = ad_off[i + 1] - ad_off[i];
         drh::put_le64(t, adl);
         drh::put(t, ads + ad_off[i], adl);
-        drh::put(t, pr + 32, 32);                              // blinded public key
+        drh::put(t, pr + pl, pl);                              // blinded public key
         uint64_t c[4];
-        drh::vrf_challenge(su, t, pr + 64, 2, c);              // R, O_k
+        drh::vrf_challenge(su, t, pr + 2 * pl, 2, c);          // R, O_k
         drh::store_le32(c, cs.data() + 32 * i);
     });
     {
@@ -340,7 +376,7 @@ int pedersen_verify_core(dr_ctx* actx, const drh::VrfSuite& su, size_t B, const 
         drh::put8(absorbed, 0x50);                             // BATCH_VERIFY
         for (size_t i = 0; i < B; i++) {
             drh::put(absorbed, cs.data() + 32 * i, 32);
-            drh::put(absorbed, proofs + stride * i + 128, 64);    // s, s_b
+            drh::put(absorbed, proofs + stride * i + 4 * pl, 64);   // s, s_b
         }
         std::vector<uint8_t> weights(32 * B);
         drh::vrf_squeeze(su.xof, absorbed.data(), absorbed.size(), weights.data(), weights.size());
@@ -352,8 +388,8 @@ int pedersen_verify_core(dr_ctx* actx, const drh::VrfSuite& su, size_t B, const 
             mn.reduce_bytes(weights.data() + 32 * i, 16, false, w_io);
             mn.reduce_bytes(weights.data() + 32 * i + 16, 16, false, w_cm);
             drh::load_le32(cs.data() + 32 * i, c);
-            drh::load_le32(pr + 128, s);
-            drh::load_le32(pr + 160, sb);
+            drh::load_le32(pr + 4 * pl, s);
+            drh::load_le32(pr + 4 * pl + 32, sb);
             uint8_t* p = pts.data() + 320 * i;
             uint8_t* k = sc.data() + 160 * i;
             std::memcpy(p, te_xy.data() + 64 * (4 * i + 3), 64);       drh::store_le32(w_io, k);                       // O_k
@@ -799,7 +835,7 @@ int dr_pedersen_prove_batch(dr_ctx* ctx, const dr_vrf_suite* suite, size_t batch
         if (batch == 0) return DR_OK;
         if (batch > 65536) return fail(DR_ERR_INVALID, "batch must be at most 65536 per call");
         drh::VrfSuite su;
-        TRY(load_suite(suite, su));
+        TRY(load_suite(suite, su, true));
         for (size_t i = 0; i < batch; i++)
             if (alpha_off[i + 1] < alpha_off[i] || ad_off[i + 1] < ad_off[i] || (salt_off && salt_off[i + 1] < salt_off[i]))
                 return fail(DR_ERR_INVALID, "offsets must be non-decreasing");
@@ -821,7 +857,7 @@ int dr_pedersen_prove_batch(dr_ctx* ctx, const dr_vrf_suite* suite, size_t batch
         }
         PedersenBatch ped(su, batch);
         TRY(ped.head(ctx, alphas, alpha_off, ads, ad_off, salts, salt_off, secret_scalars, tr_));
-        TRY(ped.tail(ctx, out_proofs, 192, out_aux, DR_PEDERSEN_AUX_BYTES));
+        TRY(ped.tail(ctx, out_proofs, 4 * su.point_len + 64, out_aux, DR_PEDERSEN_AUX_BYTES));
         tr_.mark("tail");
         return DR_OK;
     } catch (const std::bad_alloc&) {
@@ -843,8 +879,8 @@ int dr_pedersen_verify_batch(dr_ctx* ctx, const dr_vrf_suite* suite, size_t batc
         if (batch == 0) { *ok = 1; return DR_OK; }
         if (batch > 65536) return fail(DR_ERR_INVALID, "batch must be at most 65536 per call");
         drh::VrfSuite su;
-        TRY(load_suite(suite, su));
-        const size_t B = batch;
+        TRY(load_suite(suite, su, true));
+        const size_t B = batch, pl = su.point_len, plen = 4 * pl + 64;
         const drh::Mod256& mn = su.cv->n;
         for (size_t i = 0; i < B; i++)
             if (in_off[i + 1] < in_off[i] || ad_off[i + 1] < ad_off[i] || (salt_off && salt_off[i + 1] < salt_off[i]))
@@ -863,17 +899,17 @@ int dr_pedersen_verify_batch(dr_ctx* ctx, const dr_vrf_suite* suite, size_t batc
             *ok = all;
             return DR_OK;
         }
-        std::vector<uint8_t> te_enc(B * 128), te_xy(B * 256), flags(B * 4), in_pts(B * 64);
+        std::vector<uint8_t> te_enc(B * 4 * pl), te_xy(B * 256), flags(B * 4), in_pts(B * 64);
         for (size_t i = 0; i < B; i++) {
-            std::memcpy(te_enc.data() + 128 * i, proofs + 192 * i, 128);
+            std::memcpy(te_enc.data() + 4 * pl * i, proofs + plen * i, 4 * pl);
             uint64_t v[4];
-            for (int k = 0; k < 2; k++) { drh::load_le32(proofs + 192 * i + 128 + 32 * k, v); if (drh::Mod256::geq(v, mn.m)) return DR_OK; }   // dec_scalar
+            for (int k = 0; k < 2; k++) { drh::load_le32(proofs + plen * i + 4 * pl + 32 * k, v); if (drh::Mod256::geq(v, mn.m)) return DR_OK; }   // dec_scalar
         }
-        TRY(te_decode_points(ctx, su.cv->id, false, te_enc.data(), 4 * B, te_xy.data(), flags.data()));
+        TRY(te_decode_points(ctx, su.cv->id, false, te_enc.data(), 4 * B, te_xy.data(), flags.data()));     // (TE images for the SW suite)
         for (size_t i = 0; i < 4 * B; i++) if (!flags[i]) return DR_OK;
         TRY(encode_to_curve_msgs(ctx, su, B, inputs, in_off, salts, salt_off, in_pts.data()));
         int ped_ok = 0;
-        TRY(pedersen_verify_core(ctx, su, B, proofs, 192, te_xy, in_pts, ads, ad_off, ped_ok));
+        TRY(pedersen_verify_core(ctx, su, B, proofs, plen, te_xy, in_pts, ads, ad_off, ped_ok));
         *ok = ped_ok;
         return DR_OK;
     } catch (const std::bad_alloc&) {
@@ -895,8 +931,8 @@ int dr_ietf_prove_batch(dr_ctx* ctx, const dr_vrf_suite* suite, int thin, size_t
         if (batch == 0) return DR_OK;
         if (batch > 65536) return fail(DR_ERR_INVALID, "batch must be at most 65536 per call");
         drh::VrfSuite su;
-        TRY(load_suite(suite, su));
-        const size_t B = batch, plen = thin ? 96 : 80;
+        TRY(load_suite(suite, su, true));
+        const size_t B = batch, pl = su.point_len, plen = thin ? 2 * pl + 32 : pl + 48;
         const drh::Mod256& mn = su.cv->n;
         const int cv = su.cv->id;
         for (size_t i = 0; i < B; i++)
@@ -948,22 +984,37 @@ int dr_ietf_prove_batch(dr_ctx* ctx, const dr_vrf_suite* suite, int thin, size_t
         }
         const uint8_t* pks = firsts.data();
         const uint8_t* outs = firsts.data() + 64 * B;
+        // the SW suite encodes the SW images: (pk_i, I_i, O_i) mapped together, one inversion per proof
+        std::vector<uint8_t> pio_store;
+        const uint8_t* pio = nullptr;
+        if (su.cv->sw) {
+            std::vector<uint8_t> t3(B * 192);
+            for (size_t i = 0; i < B; i++) {
+                std::memcpy(t3.data() + 192 * i, pks + 64 * i, 64);
+                std::memcpy(t3.data() + 192 * i + 64, inputs.data() + 64 * i, 64);
+                std::memcpy(t3.data() + 192 * i + 128, outs + 64 * i, 64);
+            }
+            TRY(suite_coords(ctx, su, t3.data(), 3 * B, 3, pio_store, &pio));
+        }
+        auto pk_c = [&](size_t i) { return pio ? pio + 192 * i : pks + 64 * i; };
+        auto in_c = [&](size_t i) { return pio ? pio + 192 * i + 64 : inputs.data() + 64 * i; };
+        auto out_c = [&](size_t i) { return pio ? pio + 192 * i + 128 : outs + 64 * i; };
         // transcripts, delinearisation scalar z, nonces
         std::vector<drh::Bytes> tr(B);
         std::vector<uint8_t> gpts(B * 128), gsc(B * 64);
         std::vector<int> bad(B, 0);
-        uint8_t enc_g[32];
-        drh::enc_te_point(su.generator, enc_g);
+        uint8_t enc_g[33];
+        drh::enc_point(su, su.cv->sw ? su.generator_sw : su.generator, enc_g);
         drh::parallel_for(B, [&](size_t i) {
             drh::Bytes& t = tr[i];
             t = su.suite_id;
             drh::put8(t, thin ? 0x01 : 0x00);                      // THIN_VRF / TINY_VRF
             drh::put_le64(t, 2);
-            uint8_t enc[32];
-            drh::put(t, enc_g, 32);
-            drh::enc_te_point(pks + 64 * i, enc); drh::put(t, enc, 32);
-            drh::enc_te_point(inputs.data() + 64 * i, enc); drh::put(t, enc, 32);
-            drh::enc_te_point(outs + 64 * i, enc); drh::put(t, enc, 32);
+            uint8_t enc[33];
+            drh::put(t, enc_g, pl);
+            drh::enc_point(su, pk_c(i), enc); drh::put(t, enc, pl);
+            drh::enc_point(su, in_c(i), enc); drh::put(t, enc, pl);
+            drh::enc_point(su, out_c(i), enc); drh::put(t, enc, pl);
             size_t adl = ad_off[i + 1] - ad_off[i];
             drh::put_le64(t, adl);
             drh::put(t, ads + ad_off[i], adl);
@@ -985,29 +1036,32 @@ int dr_ietf_prove_batch(dr_ctx* ctx, const dr_vrf_suite* suite, int thin, size_t
         std::vector<uint8_t> merged(B * 64), rs(B * 64);
         TRY(te_msm_groups(ctx, cv, gpts.data(), gsc.data(), B, 2, merged.data()));
         TRY(te_scalar_mul_batch(ctx, cv, merged.data(), ks.data(), B, rs.data()));
+        std::vector<uint8_t> rs_store;
+        const uint8_t* rs_c = nullptr;
+        TRY(suite_coords(ctx, su, rs.data(), B, 1, rs_store, &rs_c));
         drh::parallel_for(B, [&](size_t i) {
             uint8_t* out = out_proofs + plen * i;
-            uint8_t enc_r[32];
-            drh::enc_te_point(outs + 64 * i, out);
-            drh::enc_te_point(rs.data() + 64 * i, enc_r);
+            uint8_t enc_r[33];
+            drh::enc_point(su, out_c(i), out);
+            drh::enc_point(su, rs_c + 64 * i, enc_r);
             uint64_t c[4], x[4], k[4], s[4];
             drh::vrf_challenge(su, tr[i], enc_r, 1, c);
             drh::load_le32(xs.data() + 32 * i, x);
             drh::load_le32(ks.data() + 32 * i, k);
             mn.mul(c, x, s);
             mn.add(s, k, s);
-            if (out_aux) {
-                std::memcpy(out_aux + 128 * i, outs + 64 * i, 64);
-                std::memcpy(out_aux + 128 * i + 64, rs.data() + 64 * i, 64);
+            if (out_aux) {                                   // (in the suite's coordinates)
+                std::memcpy(out_aux + 128 * i, out_c(i), 64);
+                std::memcpy(out_aux + 128 * i + 64, rs_c + 64 * i, 64);
             }
             if (thin) {
-                std::memcpy(out + 32, enc_r, 32);
-                drh::store_le32(s, out + 64);
+                std::memcpy(out + pl, enc_r, pl);
+                drh::store_le32(s, out + 2 * pl);
             } else {
                 uint8_t cb[32];
                 drh::store_le32(c, cb);
-                std::memcpy(out + 32, cb, 16);
-                drh::store_le32(s, out + 48);
+                std::memcpy(out + pl, cb, 16);
+                drh::store_le32(s, out + pl + 16);
             }
         });
         return DR_OK;

@@ -2,7 +2,7 @@
 // Bandersnatch / twisted Edwards kernels of kernels_bsn.hip.h) and hash-to-curve.  See capi_internal.hpp for the layout.
 #include "capi_internal.hpp"
 #include "hostsmall.hpp"
-#include "kernels_bsn.hip.h"
+#include "kernels_sw.hip.h"
 
 namespace dri {
 
@@ -440,13 +440,57 @@ int glv_split_scalars(const uint8_t* scalars, size_t n, std::vector<uint32_t>& o
     return DR_OK;
 }
 
+// ---- the SW suite's boundary (kernels_sw.hip.h): its points cross the ABI in short Weierstrass form and are mapped to and from their
+// TE images on the device; `per` consecutive points share one inversion
+int sw_map_points(dr_ctx* ctx, bool to_te, const uint8_t* in_xy, size_t n, uint8_t* out_xy, unsigned per) {
+    if (n == 0) return DR_OK;
+    if (per < 1 || per > (unsigned)dr::SW_MAP_MAX) return fail(DR_ERR_INVALID, "points per lane out of range");
+    TRY(ctx->io_a.reserve(n * 64));
+    TRY(ctx->io_c.reserve(n * 64));
+    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, in_xy, n * 64, hipMemcpyHostToDevice, ctx->stream));
+    const size_t lanes = (n + per - 1) / per;
+    TRY(launch(ctx, to_te ? "k_sw_to_te" : "k_te_to_sw", [&] {
+        if (to_te)
+            hipLaunchKernelGGL(dr::k_sw_map<true>, dim3(div_up(lanes, 64)), dim3(64), 0, ctx->stream, ctx->io_a.as<uint32_t>(), ctx->io_c.as<uint32_t>(),
+                               (uint32_t)n, (uint32_t)per);
+        else
+            hipLaunchKernelGGL(dr::k_sw_map<false>, dim3(div_up(lanes, 64)), dim3(64), 0, ctx->stream, ctx->io_a.as<uint32_t>(), ctx->io_c.as<uint32_t>(),
+                               (uint32_t)n, (uint32_t)per);
+    }));
+    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_c.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->prof) TRY(prof_collect(ctx));
+    return DR_OK;
+}
+int suite_coords(dr_ctx* ctx, const drh::VrfSuite& su, const uint8_t* te_xy, size_t n, unsigned per, std::vector<uint8_t>& store,
+                 const uint8_t** out) {
+    if (!su.cv->sw) { *out = te_xy; return DR_OK; }
+    store.resize(n * 64);
+    *out = store.data();
+    return sw_map_points(ctx, false, te_xy, n, store.data(), per);
+}
+namespace {
+// f(te_in, te_out) on the TE images of n_in SW points, its n_out results mapped back to SW
+template <class F>
+int sw_boundary(dr_ctx* ctx, const uint8_t* sw_in, size_t n_in, uint8_t* sw_out, size_t n_out, F&& f) {
+    TRY(use_ctx(ctx));
+    if (n_in && !sw_in) return fail(DR_ERR_INVALID, "null buffer");
+    if (n_out && !sw_out) return fail(DR_ERR_INVALID, "null buffer");
+    if (n_in) TRY(check_fr_elems(sw_in, 2 * n_in, "point"));
+    std::vector<uint8_t> te_in(n_in * 64), te_out(n_out * 64);
+    TRY(sw_map_points(ctx, true, sw_in, n_in, te_in.data(), 1));
+    TRY(f(te_in.data(), te_out.data()));
+    return sw_map_points(ctx, false, te_out.data(), n_out, sw_out, 1);
+}
+}  // namespace
+
 int te_scalar_mul_batch(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy) {
     TRY(use_ctx(ctx));
     TRY(check_curve(cv));
     if (n == 0) return DR_OK;
     if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
     TRY(check_fr_elems(pts_xy, 2 * n, "point"));
-    if (n <= drh::small_host_max()) {
+    if (n <= drh::small_host_max() && !drh::te_curve(cv)->sw) {
         // a few multiplications (a key pair, a proof's handful): ~0.09 ms each on a host core against a ~1 ms kernel chain.  The scalars may
         // be secret keys: fixed-schedule multiplication (hostsmall.hpp: te_mul_secret), reduced mod n first as the kernels do
         const drh::TeCurveHost* hc = drh::te_curve(cv);
@@ -494,6 +538,11 @@ int dr_bsn_scalar_mul_batch(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* s
     return te_scalar_mul_batch(ctx, dr::CV_BANDERSNATCH, pts_xy, scalars, n, out_xy);
 }
 int dr_te_scalar_mul_batch(dr_ctx* ctx, int curve, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy) {
+    if (curve == DR_CURVE_BANDERSNATCH_SW) {
+        if (n == 0) return use_ctx(ctx);
+        if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
+        return sw_boundary(ctx, pts_xy, n, out_xy, n, [&](const uint8_t* te, uint8_t* r) { return te_scalar_mul_batch(ctx, curve, te, scalars, n, r); });
+    }
     return te_scalar_mul_batch(ctx, curve, pts_xy, scalars, n, out_xy);
 }
 
@@ -545,6 +594,7 @@ int te_msm_groups(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* sca
 }
 // ---- fixed-base multiplication (kernels_te.hip.h: k_te_fixed_table / k_te_fixed_base_groups)
 static int te_fixed_table(dr_ctx* ctx, int cv, const uint8_t base_xy[64], const uint32_t** out) {
+    if (cv == dr::CV_BANDERSNATCH_SW) cv = dr::CV_BANDERSNATCH;       // (the SW suite's bases arrive here as their TE images: one table each)
     for (auto& fb : ctx->fixed_bases)
         if (fb.cv == cv && std::memcmp(fb.base_xy, base_xy, 64) == 0) { *out = fb.d_table; return DR_OK; }
     TRY(check_fr_elems(base_xy, 2, "base point"));
@@ -577,7 +627,7 @@ int te_fixed_base_groups(dr_ctx* ctx, int cv, const uint8_t* bases_xy, const uin
     if (m == 0 || m > 4) return fail(DR_ERR_INVALID, "1..4 fixed bases per group");
     if (!bases_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
     if (groups * m >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
-    if (groups * m <= drh::small_host_max()) {
+    if (groups * m <= drh::small_host_max() && !drh::te_curve(cv)->sw) {
         // a few groups: 64 table additions per term on a host core (~0.03 ms), entries picked by mask (the scalars are secrets and nonces)
         const drh::TeCurveHost* hc = drh::te_curve(cv);
         const drh::TeHostParams hp = drh::te_host_params(*hc);
@@ -621,6 +671,12 @@ int te_fixed_base_groups(dr_ctx* ctx, int cv, const uint8_t* bases_xy, const uin
     return DR_OK;
 }
 int dr_te_fixed_base_msm_groups(dr_ctx* ctx, int curve, const uint8_t* bases_xy, size_t m, const uint8_t* scalars, size_t groups, uint8_t* out_xy) {
+    if (curve == DR_CURVE_BANDERSNATCH_SW) {
+        if (groups == 0) return use_ctx(ctx);
+        if (m == 0 || m > 4 || groups * m >= (1ull << 31)) return fail(DR_ERR_INVALID, "1..4 fixed bases per group");
+        return sw_boundary(ctx, bases_xy, m, out_xy, groups,
+                           [&](const uint8_t* te, uint8_t* r) { return te_fixed_base_groups(ctx, curve, te, scalars, groups, m, r, true); });
+    }
     return te_fixed_base_groups(ctx, curve, bases_xy, scalars, groups, m, out_xy, true);
 }
 
@@ -628,6 +684,13 @@ int dr_bsn_msm_groups(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars
     return te_msm_groups(ctx, dr::CV_BANDERSNATCH, pts_xy, scalars, groups, m, out_xy);
 }
 int dr_te_msm_groups(dr_ctx* ctx, int curve, const uint8_t* pts_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy) {
+    if (curve == DR_CURVE_BANDERSNATCH_SW) {
+        if (groups == 0) return use_ctx(ctx);
+        if (m == 0 || m > 64) return fail(DR_ERR_INVALID, "group size must be in 1..64");
+        if (groups * m >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
+        return sw_boundary(ctx, pts_xy, groups * m, out_xy, groups,
+                           [&](const uint8_t* te, uint8_t* r) { return te_msm_groups(ctx, curve, te, scalars, groups, m, r); });
+    }
     return te_msm_groups(ctx, curve, pts_xy, scalars, groups, m, out_xy);
 }
 
@@ -648,7 +711,7 @@ int te_msm(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* scalars, s
         TRY(check_fr_elems(pts_xy, 2 * n, "point"));
         return te_msm_pippenger(ctx, cv, pts_xy, scalars, n, out_xy);
     }
-    if (n <= drh::small_host_max() && n <= 64) {
+    if (n <= drh::small_host_max() && n <= 64 && !drh::te_curve(cv)->sw) {
         // a handful of terms (the 7 / 12 points of a one- or two-proof verifier, a sigma protocol's relation): one fixed-schedule multiplication
         // per term on the worker pool (~0.09 ms each, side by side) and their sum — a kernel chain is ~0.8 ms whatever the count
         if (!pts_xy || !scalars) return fail(DR_ERR_INVALID, "null buffer");
@@ -706,11 +769,52 @@ int dr_bsn_msm(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_
     return te_msm(ctx, dr::CV_BANDERSNATCH, pts_xy, scalars, n, out_xy);
 }
 int dr_te_msm(dr_ctx* ctx, int curve, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t out_xy[64]) {
+    if (curve == DR_CURVE_BANDERSNATCH_SW) {
+        if (n >= (1ull << 26)) return fail(DR_ERR_INVALID, "bad MSM size");
+        return sw_boundary(ctx, pts_xy, n, out_xy, 1, [&](const uint8_t* te, uint8_t* r) { return te_msm(ctx, curve, te, scalars, n, r); });
+    }
     return te_msm(ctx, curve, pts_xy, scalars, n, out_xy);
 }
 
 // launch the point decoder for `n` encodings already at d_enc: Bandersnatch = the GLV lane-pair kernel, JubJub = the
 // generic one; tai = candidates of try-and-increment (output hP, no subgroup test)
+// SW suite (kernels_sw.hip.h): n x 33-byte encodings -> SW points (sw_out: public decoding) or their TE images (the batch verifier), or
+// n x 32-byte try-and-increment candidates -> 4P on TE
+static int sw_decode_points(dr_ctx* ctx, bool tai, bool sw_out, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
+    const size_t words = tai ? 8 : 9;
+    std::vector<uint32_t> rec(n * words, 0);
+    for (size_t i = 0; i < n; i++) {
+        if (tai) { std::memcpy(&rec[8 * i], enc + 32 * i, 32); continue; }
+        std::memcpy(&rec[9 * i], enc + 33 * i, 32);
+        rec[9 * i + 8] = enc[33 * i + 32];
+    }
+    TRY(ctx->io_a.reserve(n * words * 4));
+    TRY(ctx->io_b.reserve(n * 64));
+    TRY(ctx->io_c.reserve(n * 4));
+    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, rec.data(), n * words * 4, hipMemcpyHostToDevice, ctx->stream));
+    TRY(launch(ctx, "k_sw_decode_points", [&] {
+        if (tai)
+            hipLaunchKernelGGL((dr::k_sw_decode_points<false, true>), dim3(div_up(n, dr::BSN_BLOCK)), dim3(dr::BSN_BLOCK), 0, ctx->stream,
+                               ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
+        else if (sw_out)
+            hipLaunchKernelGGL((dr::k_sw_decode_points<true, false>), dim3(div_up(n, dr::BSN_BLOCK)), dim3(dr::BSN_BLOCK), 0, ctx->stream,
+                               ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
+        else
+            hipLaunchKernelGGL((dr::k_sw_decode_points<false, false>), dim3(div_up(n, dr::BSN_BLOCK)), dim3(dr::BSN_BLOCK), 0, ctx->stream,
+                               ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
+    }));
+    std::vector<uint32_t> flags(n);
+    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_b.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(flags.data(), ctx->io_c.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->prof) TRY(prof_collect(ctx));
+    for (size_t i = 0; i < n; i++) {
+        ok[i] = flags[i] ? 1 : 0;
+        if (!ok[i] && !tai) std::memset(out_xy + 64 * i, 0, 64);
+    }
+    return DR_OK;
+}
+
 void launch_decode_points(dr_ctx* ctx, hipStream_t st, int cv, bool tai, const uint32_t* d_enc, uint32_t* d_xy, uint32_t* d_ok, size_t n) {
     if (tai) {
         if (cv == dr::CV_JUBJUB)
@@ -725,12 +829,13 @@ void launch_decode_points(dr_ctx* ctx, hipStream_t st, int cv, bool tai, const u
     (void)ctx;
 }
 
-int te_decode_points(dr_ctx* ctx, int cv, bool tai, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
+int te_decode_points(dr_ctx* ctx, int cv, bool tai, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok, bool sw_out) {
     TRY(use_ctx(ctx));
     TRY(check_curve(cv));
     if (n == 0) return DR_OK;
     if (!enc || !out_xy || !ok) return fail(DR_ERR_INVALID, "null buffer");
     if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
+    if (drh::te_curve(cv)->sw) return sw_decode_points(ctx, tai, sw_out, enc, n, out_xy, ok);
     if (!tai && n <= drh::small_host_max()) {
         // a few points (a proof's own, a public key, a small ring): one host core decodes and subgroup-checks a point in ~0.13 ms, the
         // kernel's dependent chain takes ~0.9 ms whatever the count (hostsmall.hpp: te_decode_checked, the same verdicts)
@@ -760,7 +865,7 @@ int dr_bsn_decode_points(dr_ctx* ctx, const uint8_t* enc, size_t n, uint8_t* out
     return te_decode_points(ctx, dr::CV_BANDERSNATCH, false, enc, n, out_xy, ok);
 }
 int dr_te_decode_points(dr_ctx* ctx, int curve, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
-    return te_decode_points(ctx, curve, false, enc, n, out_xy, ok);
+    return te_decode_points(ctx, curve, false, enc, n, out_xy, ok, true);
 }
 
 int dr_bsn_encode_to_curve_batch(dr_ctx* ctx, const uint8_t* u_pairs, size_t n, uint8_t* out_xy) {
@@ -874,7 +979,7 @@ int dr_ringvrf_aux_take_blindings(uint8_t* aux, size_t batch, uint8_t* out_blind
     return DR_OK;
 }
 
-int load_suite(const dr_vrf_suite* s, drh::VrfSuite& out) {
+int load_suite(const dr_vrf_suite* s, drh::VrfSuite& out, bool allow_sw) {
     if (!s || !s->suite_id || s->suite_id_len == 0 || s->suite_id_len > 200) return fail(DR_ERR_INVALID, "bad VRF suite");
     out.suite_id.assign(s->suite_id, s->suite_id + s->suite_id_len);
     out.xof = s->xof != 0;
@@ -882,6 +987,14 @@ int load_suite(const dr_vrf_suite* s, drh::VrfSuite& out) {
     std::memcpy(out.blinding_base, s->blinding_base_xy, 64);
     out.cv = drh::te_curve(s->curve);
     if (!out.cv) return fail(DR_ERR_INVALID, "unknown curve id in VRF suite");
+    if (out.cv->sw) {
+        if (!allow_sw) return fail(DR_ERR_INVALID, "this entry point does not serve the short Weierstrass suite");
+        // the kernels take the suite's constants as their TE images; the SW generator stays for its encoding
+        out.point_len = 33;
+        std::memcpy(out.generator_sw, s->generator_xy, 64);
+        if (!drh::sw_to_te_host(s->generator_xy, out.generator) || !drh::sw_to_te_host(s->blinding_base_xy, out.blinding_base))
+            return fail(DR_ERR_INVALID, "suite base point out of range");
+    }
     return DR_OK;
 }
 
@@ -935,7 +1048,7 @@ int encode_to_curve_msgs(dr_ctx* ctx, const drh::VrfSuite& su, size_t B, const u
 
 int dr_hash_to_field_batch(const dr_vrf_suite* suite, const uint8_t* msgs, const uint64_t* off, size_t count, uint8_t* out_u_pairs) {
     drh::VrfSuite su;
-    TRY(load_suite(suite, su));
+    TRY(load_suite(suite, su, true));
     if (count && (!off || !out_u_pairs || (off[count] && !msgs))) return fail(DR_ERR_INVALID, "null buffer");
     for (size_t i = 0; i < count; i++)
         if (off[i + 1] < off[i]) return fail(DR_ERR_INVALID, "offsets must be non-decreasing");
@@ -948,10 +1061,15 @@ int dr_encode_to_curve_batch(dr_ctx* ctx, const dr_vrf_suite* suite, const uint8
     try {
         TRY(use_ctx(ctx));
         drh::VrfSuite su;
-        TRY(load_suite(suite, su));
+        TRY(load_suite(suite, su, true));
         if (count && (!off || !out_xy || (off[count] && !msgs))) return fail(DR_ERR_INVALID, "null buffer");
         for (size_t i = 0; i < count; i++)
             if (off[i + 1] < off[i] || (salt_off && salt_off[i + 1] < salt_off[i])) return fail(DR_ERR_INVALID, "offsets must be non-decreasing");
+        if (su.cv->sw) {              // the candidates decode to TE images (4P), which go back to SW in one launch
+            std::vector<uint8_t> te(count * 64);
+            TRY(encode_to_curve_msgs(ctx, su, count, msgs, off, salts, salt_off, te.data()));
+            return sw_map_points(ctx, false, te.data(), count, out_xy, 1);
+        }
         return encode_to_curve_msgs(ctx, su, count, msgs, off, salts, salt_off, out_xy);
     } catch (const std::bad_alloc&) {
         return fail(DR_ERR_NOMEM, "out of host memory");

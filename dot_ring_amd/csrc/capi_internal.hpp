@@ -262,9 +262,17 @@ int te_msm_groups(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* sca
 // sum_j k[g*m+j] * Base_j for `groups` groups over m <= 4 CONSTANT bases (fixed-base window tables, cached per context)
 int te_fixed_base_groups(dr_ctx* ctx, int cv, const uint8_t* bases_xy /* m*64 */, const uint8_t* scalars /* groups*m*32 */, size_t groups,
                          size_t m, uint8_t* out_xy /* groups*64 */, bool sync = true);
-int te_decode_points(dr_ctx* ctx, int cv, bool tai, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok);
+// SW suite: enc holds 33-byte encodings (32-byte candidates with tai); sw_out = SW coordinates out, otherwise the TE images
+int te_decode_points(dr_ctx* ctx, int cv, bool tai, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok, bool sw_out = false);
 void launch_decode_points(dr_ctx* ctx, hipStream_t st, int cv, bool tai, const uint32_t* d_enc, uint32_t* d_xy, uint32_t* d_ok, size_t n);
-int load_suite(const dr_vrf_suite* s, drh::VrfSuite& out);
+// allow_sw: the entry point serves the short Weierstrass suite (DR_CURVE_BANDERSNATCH_SW); the others refuse it with DR_ERR_INVALID
+int load_suite(const dr_vrf_suite* s, drh::VrfSuite& out, bool allow_sw = false);
+// n short Weierstrass points <-> their TE images on the device (kernels_sw.hip.h), `per` (1..4) points per lane sharing one inversion
+int sw_map_points(dr_ctx* ctx, bool to_te, const uint8_t* in_xy, size_t n, uint8_t* out_xy, unsigned per);
+// the suite's own coordinates of n TE points (groups of `per` consecutive points share an inversion): the TE points themselves, or for
+// the SW suite their SW images in `store`
+int suite_coords(dr_ctx* ctx, const drh::VrfSuite& su, const uint8_t* te_xy, size_t n, unsigned per, std::vector<uint8_t>& store,
+                 const uint8_t** out);
 int encode_to_curve_msgs(dr_ctx* ctx, const drh::VrfSuite& su, size_t B, const uint8_t* data, const uint64_t* off, const uint8_t* salts,
                          const uint64_t* salt_off, uint8_t* out_xy);
 // while_waiting (optional): host work that needs nothing from these kernels, run on the calling thread after the launches and before the wait

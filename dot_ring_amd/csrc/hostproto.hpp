@@ -307,7 +307,8 @@ inline const Mod256& mod_p() {       // Bandersnatch base field = BLS12-381 scal
 }
 
 // The twisted Edwards curves over that field the library serves (ids as DR_CURVE_* in dotring_hip.h and CV_* in
-// curve.hip.h): Bandersnatch (specs/bandersnatch.py:57-72) and JubJub (specs/jubjub.py:17-29).
+// curve.hip.h): Bandersnatch (specs/bandersnatch.py:57-72) and JubJub (specs/jubjub.py:17-29).  Id 2 is Bandersnatch again, for the
+// suite whose points cross the ABI in short Weierstrass form (specs/bandersnatch_sw.py): the group and every kernel are Bandersnatch's.
 struct TeCurveHost {
     int id;
     Mod256 n;                 // prime-order subgroup
@@ -316,9 +317,10 @@ struct TeCurveHost {
     unsigned scalar_bits;     // bit length of n
     bool glv;                 // has the endomorphism the lane-pair kernels use
     bool tai;                 // hash-to-curve by try-and-increment (otherwise Elligator 2)
+    bool sw = false;          // points cross the ABI as short Weierstrass affine x || y (33-byte encodings); TE inside
 };
 inline const TeCurveHost* te_curve(int id) {
-    static const TeCurveHost curves[2] = {
+    static const TeCurveHost curves[3] = {
         [] { TeCurveHost c{}; c.id = 0; c.n = mod_n();
              const uint64_t d[4] = {0xb369f2f5188d58e7ULL, 0xcb66677177e54f92ULL, 0xc66e3bf86be3b6d8ULL, 0x6389c12633c267cbULL};
              std::memcpy(c.d, d, 32); c.neg_a[0] = 5; c.scalar_bits = 253; c.glv = true; c.tai = false; return c; }(),
@@ -327,8 +329,11 @@ inline const TeCurveHost* te_curve(int id) {
              c.n.init(n);
              const uint64_t d[4] = {0x01065fd6d6343eb1ULL, 0x292d7f6d37579d26ULL, 0xf5fd9207e6bd7fd4ULL, 0x2a9318e74bfa2b48ULL};
              std::memcpy(c.d, d, 32); c.neg_a[0] = 1; c.scalar_bits = 252; c.glv = false; c.tai = true; return c; }(),
+        [] { TeCurveHost c{}; c.id = 2; c.n = mod_n();
+             const uint64_t d[4] = {0xb369f2f5188d58e7ULL, 0xcb66677177e54f92ULL, 0xc66e3bf86be3b6d8ULL, 0x6389c12633c267cbULL};
+             std::memcpy(c.d, d, 32); c.neg_a[0] = 5; c.scalar_bits = 253; c.glv = true; c.tai = true; c.sw = true; return c; }(),
     };
-    return id == 0 || id == 1 ? &curves[id] : nullptr;
+    return id >= 0 && id <= 2 ? &curves[id] : nullptr;
 }
 
 // ---------------------------------------------------------------- GLV decomposition (dot_ring/curve/glv.py:57-160)
@@ -401,6 +406,41 @@ inline void enc_te_point(const uint8_t xy[64], uint8_t out[32]) {
     if (gt) out[31] |= 0x80;
 }
 
+// compressed short Weierstrass point of the SW suite (specs/bandersnatch_sw.py point_to_string): x little-endian, then a flag byte,
+// 0x80 iff y is the larger of (y, p - y); the identity (64 zero bytes) is 32 zero bytes and 0x40
+inline void enc_sw_point(const uint8_t xy[64], uint8_t out[33]) {
+    uint64_t y[4], ny[4], zero[4] = {0, 0, 0, 0};
+    std::memcpy(out, xy, 32);
+    load_le32(xy + 32, y);
+    bool idn = true;
+    for (int i = 0; i < 64; i++) idn = idn && xy[i] == 0;
+    if (idn) { out[32] = 0x40; return; }
+    mod_p().sub(zero, y, ny);
+    bool gt = false;
+    for (int i = 3; i >= 0; i--) { if (y[i] != ny[i]) { gt = y[i] > ny[i]; break; } }
+    out[32] = gt ? 0x80 : 0x00;
+}
+// SW affine -> its TE image (ring_proof/ring_curve.py:14-21) for the suite's constant points; kernels_sw.hip.h maps everything else
+inline bool sw_to_te_host(const uint8_t sw[64], uint8_t te[64]) {
+    static const uint64_t MB[4] = {0x926c66eb6fa86d15ULL, 0xbd025b636bd74122ULL, 0x316b96e5c340cf6aULL, 0x384d1c153c878eeaULL};
+    static const uint64_t A3[4] = {0x614b54769b3c9f88ULL, 0x18b9b65d4c4244c5ULL, 0xe0dbdc89198b28feULL, 0x1617cdda6f6639c1ULL};
+    const Mod256& f = mod_p();
+    uint64_t x[4], y[4], s[4], t[4], one[4], sp1[4], sm1[4], d[4], di[4], v[4], w[4];
+    load_le32(sw, x); load_le32(sw + 32, y);
+    if (Mod256::geq(x, f.m) || Mod256::geq(y, f.m)) return false;
+    f.set_u64(1, one);
+    f.mul(MB, x, s); f.sub(s, A3, s);
+    f.mul(MB, y, t);
+    f.add(s, one, sp1); f.sub(s, one, sm1);
+    f.mul(t, sp1, d);
+    if (f.is_zero(d)) return false;                  // the identity or a point of order 2: not a suite constant
+    f.inv(d, di);
+    f.mul(s, sp1, v); f.mul(v, di, v);
+    f.mul(sm1, t, w); f.mul(w, di, w);
+    store_le32(v, te); store_le32(w, te + 32);
+    return true;
+}
+
 // affine twisted-Edwards addition: the verifier's seed + relation (ring/vrf.py:239-283)
 // in two halves around the one inversion, so that a caller with many additions can invert all denominators together (batch_inv)
 struct TeAddPending { uint64_t e[4], t[4], dx[4], dy[4], den[4]; };
@@ -458,9 +498,16 @@ inline void batch_inv(const Mod256& f, uint64_t (*vals)[4], size_t n) {
 struct VrfSuite {
     Bytes suite_id;
     bool xof;                 // SHAKE128 suite; otherwise SHA-512 counter mode
-    uint8_t generator[64], blinding_base[64];
+    uint8_t generator[64], blinding_base[64];     // TE affine (the kernels' coordinates; the SW suite's are mapped on loading)
     const TeCurveHost* cv = te_curve(0);
+    size_t point_len = 32;                        // bytes of an encoded point: 32 (TE), 33 (SW)
+    uint8_t generator_sw[64] = {0};               // SW suite: the generator as given (its encoding enters the Tiny / Thin transcripts)
 };
+// the suite's point encoding of xy given in the suite's own coordinates (TE, or SW for the SW suite)
+inline void enc_point(const VrfSuite& su, const uint8_t xy[64], uint8_t* out) {
+    if (su.cv->sw) enc_sw_point(xy, out);
+    else enc_te_point(xy, out);
+}
 // squeeze `size` bytes of the stream defined by everything absorbed
 inline void vrf_squeeze(bool xof, const uint8_t* absorbed, size_t len, uint8_t* out, size_t size) {
     if (xof) {
@@ -496,7 +543,7 @@ inline bool vrf_nonce(const VrfSuite& su, const Bytes& transcript, const uint64_
 inline void vrf_challenge(const VrfSuite& su, const Bytes& transcript, const uint8_t* enc_points, size_t count, uint64_t out[4]) {
     Bytes t = transcript;
     put8(t, 0x40);                                   // CHALLENGE
-    put(t, enc_points, 32 * count);
+    put(t, enc_points, su.point_len * count);
     uint8_t raw[16];
     vrf_squeeze(su.xof, t.data(), t.size(), raw, 16);
     su.cv->n.reduce_bytes(raw, 16, false, out);

@@ -438,6 +438,35 @@ __global__ __launch_bounds__(BSN_BLOCK) void k_bsn_decode_points(const uint32_t*
     }
 }
 
+// What follows decompression in a one-lane-per-point decoder (k_te_decode_points below, k_sw_decode_points of kernels_sw.hip.h):
+// Q = hP by log2(h) doublings.  TAI: (ox, oy) = Q, valid &= Q != O.  Otherwise (ox, oy) = P, valid &= Q != O and [h^-1 mod n] Q == P.
+template <int CV, bool TAI>
+DR_DEV void te_cofactor_check(uint32_t* tab, int lane, const Fs& x, const Fs& y, bool& valid, Fs& ox, Fs& oy) {
+    const Fs one = Fs::one();
+    TePoint P;
+    P.x = x; P.y = y; P.z = one; P.t = mul(x, y);
+    constexpr int LOG2_H = CV == CV_JUBJUB ? 3 : 2;
+    TePoint Q = P;
+#pragma unroll 1
+    for (int j = 0; j < LOG2_H; j++) Q = te_dbl<true, CV>(Q);
+    if (is_zero(Q.x)) { valid = false; Q = P; }    // hP = O (x = 0 also covers the order-2 point (0,-1), which h kills anyway)
+    Fs zi = inv(is_zero(Q.z) ? one : Q.z);
+    Fs qx = mul(Q.x, zi), qy = mul(Q.y, zi);
+    if (TAI) {
+        ox = qx; oy = qy;
+        return;
+    }
+    // h^-1 mod n
+    constexpr uint32_t HINV_B[8] = {0xde592de9u, 0x17bdc507u, 0x5712c355u, 0xbfaba540u, 0x81ce5880u, 0x899ad881u, 0x97cd877du, 0x15bc8f5fu};
+    constexpr uint32_t HINV_J[8] = {0xdadee597u, 0x5a12e1cbu, 0x79990210u, 0x14cd0412u, 0x20268760u, 0x20cce760u, 0x4ca675f5u, 0x01cfb69du};
+    uint32_t k[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) k[j] = CV == CV_JUBJUB ? HINV_J[j] : HINV_B[j];
+    TePoint R = bsn_scalar_mul_core<CV>(tab, lane, qx, qy, k);
+    if (!equal(R.x, mul(x, R.z)) || !equal(R.y, mul(y, R.z))) valid = false;
+    ox = x; oy = y;
+}
+
 // The same decoding for a curve without an endomorphism (JubJub, cofactor 8): one lane per point, Q = hP by log2(h)
 // doublings, then [h^-1 mod n] Q through the plain 64-window core.  TAI = true is the device half of try-and-increment
 // hash-to-curve (dot_ring/curve/point.py:252-296): the candidate only has to decompress; the output is hP and ok says
@@ -478,34 +507,11 @@ __global__ __launch_bounds__(BSN_BLOCK) void k_te_decode_points(const uint32_t* 
         }
         if (x_larger != sign) x = neg(x);
     }
-    TePoint P;
-    P.x = x; P.y = y; P.z = one; P.t = mul(x, y);
-    constexpr int LOG2_H = CV == CV_JUBJUB ? 3 : 2;
-    TePoint Q = P;
-#pragma unroll 1
-    for (int j = 0; j < LOG2_H; j++) Q = te_dbl<true, CV>(Q);
-    if (is_zero(Q.x)) { valid = false; Q = P; }    // hP = O (x = 0 also covers the order-2 point (0,-1), which h kills anyway)
-    Fs zi = inv(is_zero(Q.z) ? one : Q.z);
-    Fs qx = mul(Q.x, zi), qy = mul(Q.y, zi);
-    if (TAI) {
-        if (live) {
-            store_fr_std(out_xy + (size_t)i * 16, fs_to_std(qx));
-            store_fr_std(out_xy + (size_t)i * 16 + 8, fs_to_std(qy));
-            ok[i] = valid ? 1u : 0u;
-        }
-        return;
-    }
-    // h^-1 mod n
-    constexpr uint32_t HINV_B[8] = {0xde592de9u, 0x17bdc507u, 0x5712c355u, 0xbfaba540u, 0x81ce5880u, 0x899ad881u, 0x97cd877du, 0x15bc8f5fu};
-    constexpr uint32_t HINV_J[8] = {0xdadee597u, 0x5a12e1cbu, 0x79990210u, 0x14cd0412u, 0x20268760u, 0x20cce760u, 0x4ca675f5u, 0x01cfb69du};
-    uint32_t k[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) k[j] = CV == CV_JUBJUB ? HINV_J[j] : HINV_B[j];
-    TePoint R = bsn_scalar_mul_core<CV>(tab, lane, qx, qy, k);
-    if (!equal(R.x, mul(x, R.z)) || !equal(R.y, mul(y, R.z))) valid = false;
+    Fs ox, oy;
+    te_cofactor_check<CV, TAI>(tab, lane, x, y, valid, ox, oy);
     if (live) {
-        store_fr_std(out_xy + (size_t)i * 16, fs_to_std(x));
-        store_fr_std(out_xy + (size_t)i * 16 + 8, fs_to_std(y));
+        store_fr_std(out_xy + (size_t)i * 16, fs_to_std(ox));
+        store_fr_std(out_xy + (size_t)i * 16 + 8, fs_to_std(oy));
         ok[i] = valid ? 1u : 0u;
     }
 }

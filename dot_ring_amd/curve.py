@@ -3,6 +3,8 @@
 Mirrors (names, argument meaning, error behaviour) the parts of the reference the Ring-VRF path touches:
   dot_ring/curve/specs/bandersnatch.py:57-306   suites, BandersnatchPoint.__mul__/msm, CurveVariant objects
   dot_ring/curve/specs/jubjub.py:17-66          JubJub: same field, a = -1, cofactor 8, try-and-increment
+  dot_ring/curve/specs/bandersnatch_sw.py       Bandersnatch_SW: Bandersnatch's group in short Weierstrass form, 33-byte codec,
+                                                try-and-increment; the kernels compute on its twisted Edwards image
   dot_ring/curve/point.py:150-214               compressed codec
   dot_ring/curve/twisted_edwards/*              affine law, Elligator2 encode_to_curve
   dot_ring/curve/curve.py:56-67,110-237,384-401 valid_point, hash_to_field, key derivation
@@ -290,9 +292,153 @@ class BandersnatchPoint:
         return cls(v, 1 if tv2 == 0 else w)
 
 
+class BandersnatchSWPoint:
+    """Affine short Weierstrass point of Bandersnatch_SW (dot_ring/curve/specs/bandersnatch_sw.py, short_weierstrass/sw_affine_point.py):
+    y^2 = x^3 + a x + b, the identity is (None, None).  Single additions are host big-int code; scalar multiplications, MSMs, decoding
+    and hash-to-curve run on the GPU under DR_CURVE_BANDERSNATCH_SW, whose kernels map to and from the twisted Edwards image."""
+    curve: BandersnatchCurve
+    _N, _H, _CV = _N, 4, _native.CURVE_BANDERSNATCH_SW
+    _SW_A = 10773120815616481058602537765553212789256758185246796157495669123169359657269
+    _SW_B = 29569587568322301171008055308580903175558631321415017492731745847794083609535
+    __slots__ = ("x", "y")
+
+    def __init__(self, x, y):
+        self.x, self.y = x, y
+        if x is None and y is None:
+            return
+        if x is None or y is None or not (0 <= x < _P and 0 <= y < _P):
+            raise ValueError("Invalid point coordinates")
+        if not self._on_curve(x, y):
+            raise ValueError("Point is not on the curve")
+
+    @classmethod
+    def _on_curve(cls, x: int, y: int) -> bool:
+        return (y * y - (x * x * x + cls._SW_A * x + cls._SW_B)) % _P == 0
+
+    @classmethod
+    def _trusted(cls, x: int, y: int):
+        """Kernel outputs: 64 zero bytes are the identity."""
+        pt = object.__new__(cls)
+        pt.x, pt.y = (None, None) if x == 0 and y == 0 else (x, y)
+        return pt
+
+    def __eq__(self, other):
+        return isinstance(other, BandersnatchSWPoint) and self.x == other.x and self.y == other.y
+
+    def __hash__(self):
+        return 0 if self.x is None else (self.x + self.y) % self._N
+
+    def __repr__(self):
+        return f"{type(self).__name__}({self.x}, {self.y})"
+
+    @classmethod
+    def identity(cls):
+        return cls(None, None)
+
+    @classmethod
+    def generator_point(cls):
+        return cls(*cls.curve.params.generator)
+
+    def is_identity(self) -> bool:
+        return self.x is None and self.y is None
+
+    def is_on_curve(self) -> bool:
+        return self.is_identity() or self._on_curve(self.x, self.y)
+
+    # -- group law (sw_affine_point.py)
+    def __add__(self, other):
+        if not isinstance(other, BandersnatchSWPoint):
+            raise TypeError("Can only add SWAffinePoint instances")
+        if self.is_identity():
+            return other
+        if other.is_identity():
+            return self
+        if self.x == other.x:
+            return self.double() if self.y == other.y else self.identity()
+        lam = (other.y - self.y) * pow(other.x - self.x, -1, _P) % _P
+        x3 = (lam * lam - self.x - other.x) % _P
+        return type(self)(x3, (lam * (self.x - x3) - self.y) % _P)
+
+    def double(self):
+        if self.is_identity() or self.y == 0:
+            return self.identity()
+        lam = (3 * self.x * self.x + self._SW_A) * pow(2 * self.y, -1, _P) % _P
+        x3 = (lam * lam - 2 * self.x) % _P
+        return type(self)(x3, (lam * (self.x - x3) - self.y) % _P)
+
+    def __neg__(self):
+        return self if self.is_identity() else type(self)(self.x, -self.y % _P)
+
+    def __sub__(self, other):
+        return self + (-other)
+
+    def __mul__(self, scalar: int):
+        return scalar_mul_batch([self], [scalar])[0]
+
+    __rmul__ = __mul__
+
+    @classmethod
+    def msm(cls, points, scalars):
+        if len(points) != len(scalars):
+            raise ValueError("Points and scalars must have same length")
+        if not points:
+            return cls.identity()
+        raw = runtime.context().bsn_msm(pack_points(points), pack_scalars(scalars, cls._N), cls._CV)
+        return cls._trusted(int.from_bytes(raw[:32], "little"), int.from_bytes(raw[32:], "little"))
+
+    def clear_cofactor(self):
+        return scalar_mul_batch_raw([self], [self._H])[0]
+
+    # -- codec (bandersnatch_sw.py: point_to_string / string_to_point): x little-endian, then a flag byte
+    def point_to_string(self) -> bytes:
+        if self.is_identity():
+            return bytes(32) + b"\x40"
+        return self.x.to_bytes(32, "little") + (b"\x00" if self.y <= -self.y % _P else b"\x80")
+
+    @classmethod
+    def string_to_point(cls, data):
+        if isinstance(data, str):
+            data = bytes.fromhex(data)
+        if len(data) == 0:
+            raise ValueError("Empty octet string")
+        x = int.from_bytes(data[:-1], "little")
+        try:
+            y = cls.curve.mod_sqrt((x * x * x + cls._SW_A * x + cls._SW_B) % _P)
+        except ValueError:
+            y = 0
+        if not y:
+            raise ValueError("Invalid point: no y-coordinate found for x")
+        small, large = sorted((y, -y % _P))
+        flag = data[-1]
+        if flag & 0x3F:
+            raise ValueError("Invalid canonical point flags")
+        if (flag >> 6) & 1:
+            if (flag >> 7) & 1:
+                raise ValueError("Invalid infinity point: negative flag is set")
+            raise ValueError("Invalid infinity point: not supported")
+        try:
+            return cls(x, large if (flag >> 7) & 1 else small)
+        except ValueError:
+            raise ValueError("Invalid point") from None
+
+    # -- hash to curve: try-and-increment (point.py:252-296), candidates hashed natively, decoded and cofactor-cleared on the GPU
+    _suite_struct = BandersnatchPoint.__dict__["_suite_struct"]
+
+    @classmethod
+    def encode_to_curve(cls, alpha_string: bytes, salt: bytes = b""):
+        return cls.encode_to_curve_batch([alpha_string], [salt])[0]
+
+    @classmethod
+    def encode_to_curve_batch(cls, alpha_strings, salts=None):
+        if not alpha_strings:
+            return []
+        return unpack_points(cls, runtime.context().encode_to_curve_batch(cls._suite_struct(), list(alpha_strings), salts))
+
+
 # ------------------------------------------------------------------ batched helpers over the C ABI
 def pack_points(points) -> bytes:
-    return b"".join(p.x.to_bytes(32, "little") + p.y.to_bytes(32, "little") for p in points)
+    """x || y little-endian per point; an SW identity ((None, None)) packs as 64 zero bytes, as the ABI takes it."""
+    return b"".join((p.x or 0).to_bytes(32, "little") + (p.y or 0).to_bytes(32, "little") for p in points)
 
 
 def pack_scalars(scalars, order: int = _N) -> bytes:
@@ -384,7 +530,7 @@ class CurveVariant:
         self.name, self.curve, self.point_type = name, curve, point_type
 
     def point(self, x, y=None):
-        if isinstance(x, BandersnatchPoint):
+        if isinstance(x, (BandersnatchPoint, BandersnatchSWPoint)):
             return x
         if y is None:
             x, y = x
@@ -441,3 +587,27 @@ JubJub = _suite(
     curve_id=_native.CURVE_JUBJUB,
     e2c="tai",
 )
+
+# dot_ring/curve/specs/bandersnatch_sw.py — Bandersnatch's prime-order group in short Weierstrass form (same n, cofactor 4), 33-byte
+# points, try-and-increment hash-to-curve.  Ring proofs refuse it (RingProofParams), as the reference does.
+_SW_PARAMS = SuiteParams(
+    suite_id=b"Bandersnatch-SW-SHA512-TAI-v1", hash_fn=hashlib.sha512, xof=False,
+    auxiliary_points=AuxiliaryPoints(
+        (28115362618644671219696075022370511395136332234538034358311199318506963235315,
+         3900851469868158154936962463930962496000252801946757953905982128670530185313),
+        (13189182432637108534251278524663360416811744717379968387043749958796254980045,
+         14483286006782706188671626508232161325054303360192563232232823772738911894793),
+        (20496180070424734470560955314776462366297546779079302509428101119888111900885,
+         8839106592405352067483360946162273985142890146060814748321063063028225641813)),
+    a=BandersnatchSWPoint._SW_A,
+    d=0,
+    generator=(30900340493481298850216505686589334086208278925799850409469406976849338430199,
+               12663882780877899054958035777720958383845500985908634476792678820121468453298),
+    encoding=Encoding(point_len=33),
+    curve_id=_native.CURVE_BANDERSNATCH_SW,
+    e2c="tai",
+)
+Bandersnatch_SW = CurveVariant(
+    "Bandersnatch_SW", BandersnatchCurve(_SW_PARAMS),
+    type("Bandersnatch_SWPoint", (BandersnatchSWPoint,), {"__slots__": ()}))
+Bandersnatch_SW.point_type.curve = Bandersnatch_SW.curve

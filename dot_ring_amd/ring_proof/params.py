@@ -4,6 +4,7 @@ from __future__ import annotations
 from dataclasses import dataclass, field
 from functools import lru_cache
 
+from .. import _native
 from ..curve import Bandersnatch, CurveVariant
 from .pcs import KZG
 
@@ -79,6 +80,8 @@ class RingProofParams:
     cv: CurveVariant = field(default_factory=lambda: Bandersnatch, compare=False, hash=False)
 
     def __post_init__(self) -> None:
+        if getattr(self.cv.curve.params, "curve_id", None) == _native.CURVE_BANDERSNATCH_SW:     # params.py _validate_curve of the reference
+            raise ValueError(f"{self.cv.name} ring proofs require a Twisted Edwards curve")
         aux = self.cv.curve.params.auxiliary_points
         missing = [n for n in ("blinding_base", "accumulator_base", "padding_point") if getattr(aux, n) is None]
         if missing:

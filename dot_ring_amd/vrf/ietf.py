@@ -46,7 +46,8 @@ class IetfVRF(VRF):
         bb = sp.auxiliary_points.blinding_base or gen                      # unused by these two schemes
         suite = _native.vrf_suite(sp.suite_id, sp.xof, le(gen[0]) + le(gen[1]), le(bb[0]) + le(bb[1]), sp.curve_id)
         sks = b"".join(bytes(sk) if len(sk) == 32 else le(int.from_bytes(sk, "little") % sp.subgroup_order) for sk in secret_keys)
-        plen = 96 if cls.THIN else 80
+        pl = cv.curve.params.encoding.point_len
+        plen = 2 * pl + 32 if cls.THIN else pl + 48
         ctx, make, frm, out = runtime.context(), cv.point_type._trusted, int.from_bytes, []
         for lo in range(0, count, 65536):
             hi = min(count, lo + 65536)
@@ -56,7 +57,7 @@ class IetfVRF(VRF):
                 raw, xy = blob[plen * k : plen * (k + 1)], aux[128 * k : 128 * (k + 1)]
                 o = make(frm(xy[0:32], "little"), frm(xy[32:64], "little"))
                 r = make(frm(xy[64:96], "little"), frm(xy[96:128], "little"))
-                c = 0 if cls.THIN else frm(raw[32:48], "little")
+                c = 0 if cls.THIN else frm(raw[pl : pl + 16], "little")
                 out.append(cls._from_parts(o, r, c, frm(raw[plen - 32 :], "little")))
         return out
 

@@ -129,16 +129,16 @@ class PedersenVRF(VRF):
         ctx = runtime.context()
         suite = cls._suite_struct()
         out, frm, mk = [], int.from_bytes, cv.point_type._trusted
-        step, ab = 65536, _native.PEDERSEN_AUX_BYTES
+        step, ab, plen, sof = 65536, _native.PEDERSEN_AUX_BYTES, cls.proof_len(), 4 * point_len(cv)
         for lo in range(0, count, step):
             hi = min(count, lo + step)
             raw, aux = ctx.pedersen_prove_batch(suite, [bytes(a) for a in alphas[lo:hi]], [bytes(a) for a in additional_data[lo:hi]],
                                                 salts[lo:hi] if salts else None, sks[32 * lo : 32 * hi])
             for i in range(hi - lo):
-                a, r = aux[ab * i : ab * i + ab], raw[192 * i : 192 * i + 192]
+                a, r = aux[ab * i : ab * i + ab], raw[plen * i : plen * i + plen]
                 pts = [mk(frm(a[64 * k : 64 * k + 32], "little"), frm(a[64 * k + 32 : 64 * k + 64], "little")) for k in range(4)]
-                out.append(cls(output_point=pts[0], blinded_pk=pts[1], result_point=pts[2], ok=pts[3], s=frm(r[128:160], "little"),
-                               sb=frm(r[160:192], "little"), _blinding_factor=frm(a[256:288], "little")))
+                out.append(cls(output_point=pts[0], blinded_pk=pts[1], result_point=pts[2], ok=pts[3], s=frm(r[sof : sof + 32], "little"),
+                               sb=frm(r[sof + 32 : sof + 64], "little"), _blinding_factor=frm(a[256:288], "little")))
         return out
 
     @classmethod
@@ -198,7 +198,7 @@ class PedersenVRF(VRF):
                 if not (len(proofs) == len(inputs) == len(additional_data) == len(salts)):
                     return False
                 blobs = [p.encode() for p in proofs]
-                if any(len(b) != 192 for b in blobs):
+                if any(len(b) != cls.proof_len() for b in blobs):
                     return False
                 ins, adl, sl = [bytes(x) for x in inputs], [bytes(x) for x in additional_data], [bytes(x) for x in salts]
             except (AttributeError, TypeError, ValueError):

@@ -102,7 +102,16 @@ DR_API int dr_bsn_decode_points(dr_ctx *ctx, const uint8_t *enc /* n*32 */, size
  * DR_CURVE_BANDERSNATCH (a = -5, cofactor 4; identical to the dr_bsn_* calls) or DR_CURVE_JUBJUB (a = -1, cofactor 8,
  * dot_ring/curve/specs/jubjub.py:17-29 — no endomorphism, so the plain 64-window kernels).  The sigma-protocol and
  * ring entry points below take the curve from dr_vrf_suite.curve. */
-enum { DR_CURVE_BANDERSNATCH = 0, DR_CURVE_JUBJUB = 1 };
+enum { DR_CURVE_BANDERSNATCH = 0, DR_CURVE_JUBJUB = 1, DR_CURVE_BANDERSNATCH_SW = 2 };
+/* DR_CURVE_BANDERSNATCH_SW: Bandersnatch in short Weierstrass form (dot_ring/curve/specs/bandersnatch_sw.py), the same prime-order group;
+ * the kernels compute on its twisted Edwards image (Montgomery-model maps of dot_ring/ring_proof/ring_curve.py:10-23, on the device).
+ * For this curve a raw point is SW affine x(32) || y(32) little-endian, the identity 64 zero bytes; an encoded point is 33 bytes,
+ * x(32) LE then a flag byte (0x80: y is the larger of +-y; dec rejects 0x40 = infinity, any of the low six bits, x >= p, no y, y = 0,
+ * points outside the prime-order subgroup), so dr_te_decode_points reads n*33 bytes.  Accepted by the four calls above and below,
+ * dr_te_fixed_base_msm_groups (curve 2 outside these calls' size limits is refused, never read as TE), dr_encode_to_curve_batch
+ * (try-and-increment, bandersnatch_sw.py + point.py:252-296), dr_ietf_prove_batch, dr_pedersen_prove_batch and dr_pedersen_verify_batch
+ * (proofs 81 / 98 / 196 bytes; inside them points stay TE and are mapped to SW only to be encoded).  The ring prover, the Ring-VRF
+ * calls and dr_ietf_verify_batch refuse it (DR_ERR_INVALID). */
 DR_API int dr_te_scalar_mul_batch(dr_ctx *ctx, int curve, const uint8_t *pts_xy, const uint8_t *scalars, size_t n, uint8_t *out_xy);
 DR_API int dr_te_msm(dr_ctx *ctx, int curve, const uint8_t *pts_xy, const uint8_t *scalars, size_t n, uint8_t out_xy[64]);
 DR_API int dr_te_msm_groups(dr_ctx *ctx, int curve, const uint8_t *pts_xy, const uint8_t *scalars, size_t groups, size_t m, uint8_t *out_xy);
@@ -314,7 +323,8 @@ typedef struct dr_vrf_suite {
     int xof;                        /* 1: SHAKE128 suite, 0: SHA-512 (counter-mode squeeze, expand_message_xmd) */
     uint8_t generator_xy[64];       /* group generator, x||y little-endian */
     uint8_t blinding_base_xy[64];   /* Pedersen blinding base (bandersnatch.py:89-102) */
-    int curve;                      /* DR_CURVE_BANDERSNATCH (Elligator 2 hash-to-curve) or DR_CURVE_JUBJUB (try-and-increment) */
+    int curve;                      /* DR_CURVE_BANDERSNATCH (Elligator 2 hash-to-curve), DR_CURVE_JUBJUB or DR_CURVE_BANDERSNATCH_SW
+                                       (try-and-increment; for the SW suite generator and blinding base are SW affine) */
 } dr_vrf_suite;
 
 /* hash_to_field(msg, 2) for `count` messages msgs[off[i]..off[i+1]): out = count * 2 field elements (32-byte LE),
@@ -345,7 +355,8 @@ DR_API int dr_ringvrf_prove_batch(dr_ring_prover *p, const dr_vrf_suite *suite, 
 
 
 /* PedersenVRF.prove / batch_verify for a batch (dot_ring/vrf/pedersen/vrf.py:86-126, 171-242): the Pedersen halves of the
- * two Ring-VRF calls on their own.  Proofs are 192 bytes (gamma || Y_bar || R || O_k || s || s_b).  out_aux (nullable,
+ * two Ring-VRF calls on their own.  Proofs are 4 points and 2 scalars (gamma || Y_bar || R || O_k || s || s_b): the size per suite, 192
+ * bytes for the TE suites, 196 for DR_CURVE_BANDERSNATCH_SW (whose aux points are SW affine).  out_aux (nullable,
  * batch * DR_PEDERSEN_AUX_BYTES): O, Y_bar, R, O_k affine (4*64) and the blinding factor (32).  The verifier decodes and
  * subgroup-checks the proof points on the GPU; *ok = 1 iff every proof verifies (malformed input: *ok = 0, DR_OK). */
 #define DR_PEDERSEN_AUX_BYTES 288
@@ -356,8 +367,8 @@ DR_API int dr_pedersen_verify_batch(dr_ctx *ctx, const dr_vrf_suite *suite, size
                                     const uint64_t *in_off, const uint8_t *ads, const uint64_t *ad_off, const uint8_t *salts,
                                     const uint64_t *salt_off, int *ok);
 
-/* TinyVRF.prove (thin = 0: 80-byte proofs O || c || s, dot_ring/vrf/ietf/tiny.py:35-70) or ThinVRF.prove (thin = 1: 96-byte
- * proofs O || R || s) for a batch; arguments as for dr_pedersen_prove_batch.  out_aux (nullable, batch * 128): O and R affine. */
+/* TinyVRF.prove (thin = 0: proofs O || c || s, 80 bytes for the TE suites, dot_ring/vrf/ietf/tiny.py:35-70) or ThinVRF.prove (thin = 1:
+ * O || R || s, 96 bytes) for a batch — sizes per suite: 81 / 98 bytes for DR_CURVE_BANDERSNATCH_SW (aux points SW affine); arguments as for dr_pedersen_prove_batch.  out_aux (nullable, batch * 128): O and R affine. */
 DR_API int dr_ietf_prove_batch(dr_ctx *ctx, const dr_vrf_suite *suite, int thin, size_t batch, const uint8_t *alphas,
                                const uint64_t *alpha_off, const uint8_t *ads, const uint64_t *ad_off, const uint8_t *salts,
                                const uint64_t *salt_off, const uint8_t *secret_scalars, uint8_t *out_proofs, uint8_t *out_aux);
