@@ -30,7 +30,6 @@ int prof_collect(dr_ctx* ctx) {
 }
 
 int g_force_c = 0;
-bool window_ok(int c) { return c >= 7 && c <= 16; }
 
 }  // namespace dri
 using namespace dri;
@@ -259,7 +258,7 @@ int dri::ctx_create_role(int device_id, int role, dr_ctx** out) {
     }
     const char* fc = std::getenv("DOTRING_MSM_WINDOW");
     g_force_c = fc ? std::atoi(fc) : 0;
-    if (!window_ok(g_force_c)) g_force_c = 0;
+    if (!dr::forced_window_ok(g_force_c)) g_force_c = 0;
     int rc = bsn_consts_init(ctx->stream);
     if (rc != DR_OK) {
         (void)hipStreamDestroy(ctx->stream);

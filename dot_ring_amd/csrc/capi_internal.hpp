@@ -29,6 +29,7 @@
 #include "hostmath.hpp"
 #include "hostpairing.hpp"
 #include "hostproto.hpp"
+#include "msm_plan.hpp"
 
 namespace dri {
 
@@ -230,7 +231,6 @@ inline void g1_host_to_dev(drh::G1* pts, size_t n) {
 
 // ---- knobs (environment, read in dr_ctx_create; defined in capi_core.hip)
 extern int g_force_c;              // test hook: DOTRING_MSM_WINDOW
-bool window_ok(int c);
 
 }  // namespace dri
 
@@ -303,28 +303,9 @@ struct PhaseTrace {
 };
 
 // ---- capi_msm.hip
-// Fixed-base table descriptor for msm_device (table == nullptr: plain bases, one bucket set per window).
-struct MsmTable {
-    const uint32_t* table = nullptr;
-    dr::WindowTable wt{};
-    uint32_t pt_words = 24;              // words per table record
-    bool bit_rows = false;               // the table has a row per bit: a call may recode the scalars as it likes (non-adjacent form)
-    int naf_delta = -2;                  // see dr_srs::table_naf_delta
-    uint32_t stride = 0, offset = 0;
-    uint32_t short_from = 0xffffffffu, n_short = 0;   // batched MSM: vectors from this index on are zero beyond n_short (sort hint)
-    bool fold_sign = false;              // scalars above r / 2 enter as their negatives (difference columns: r - 1 becomes -1, one digit)
-};
-// exact_streams: internal — the second run of a call whose partition sort overfilled a stream (see msm_device)
 int msm_device(dr_ctx* ctx, const uint32_t* d_bases, const uint32_t* d_scalars, size_t n, size_t batch, std::vector<drh::G1>& results,
-               const MsmTable* tbl = nullptr, bool exact_streams = false);
+               const MsmTable* tbl = nullptr);
 MsmTable srs_table(const dr_srs* srs, size_t offset);
-// the tiling msm_device takes for `batch` MSMs of n points over this table: mode 0 = the table's window rows, 2 = width-c non-adjacent
-// form (bit-row tables, hundreds of MSMs); slots = digit rows per scalar, digits = expected non-zero digits per scalar
-struct Tiling {
-    int mode, c, slots;
-    double digits;
-};
-Tiling tiling_for(const MsmTable& t, size_t n, size_t batch);
 int srs_precompute(dr_ctx* ctx, dr_srs* srs, int window_bits, bool allow_bit_rows);   // dr_srs_precompute with the table shape chosen
 void g1_result_to_bytes(const drh::G1& r, uint8_t* out96, int* is_inf);
 int msm_batch_results_to_bytes(dr_ctx* ctx, size_t batch, uint8_t* out_be_xy, int* is_inf);

@@ -19,7 +19,7 @@ namespace dr {
 // (start[j] = cmax j, row[j] = the table row of the slot's first position, width[j] = cmax).
 struct WindowTable {
     int W, cmax;
-    uint8_t start[40];   // first bit of window w   (W <= 40: widths >= 7 ... see make_plan)
+    uint8_t start[40];   // first bit of window w   (W <= 40: widths >= dr::MIN_WINDOW, msm_plan.hpp)
     uint8_t width[40];
     uint8_t row[40];     // table row of window w (fixed-base table mode)
     int odd;

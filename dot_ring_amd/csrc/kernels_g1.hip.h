@@ -19,6 +19,7 @@
 #pragma once
 #include "dev_types.hpp"
 #include "g1.hip.h"
+#include "msm_plan.hpp"
 #include "msm_recode.hip.h"
 
 namespace dr {
@@ -319,8 +320,6 @@ __global__ void k_g1_digits(const uint32_t* __restrict__ scalars, uint32_t n, ui
 }
 
 // ---- 2. exclusive scan of the histogram (three passes; the array is at most a few million entries)
-constexpr int SCAN_BLOCK = 256, SCAN_ITEMS = 8, SCAN_TILE = SCAN_BLOCK * SCAN_ITEMS;
-
 template <int BLOCK = SCAN_BLOCK>
 DR_DEV uint32_t block_exclusive_scan(uint32_t v, uint32_t* smem, uint32_t& total) {
     // wave scan with shuffles, then scan of the BLOCK / 64 wave totals through LDS
@@ -447,7 +446,6 @@ DR_DEV uint32_t digit_bin(const WindowTable& wt, int w, uint32_t mag, uint32_t& 
 // Each set gets a fixed-capacity segment of `sorted` (capacity = the most digits it can receive), so segment bases
 // need no cross-set scan.  Pass 1 counts, pass 2 recomputes the digits and places them.
 constexpr int SORT_BLOCK = 256;
-constexpr uint32_t SORT_MAX_H = 8192;
 
 struct SortSetParams {
     uint32_t n, batch, H, groups;      // groups: table-mode index groups per MSM (1 otherwise)
@@ -590,10 +588,6 @@ __global__ __launch_bounds__(SORT_BLOCK) void k_g1_sort_sets(const uint32_t* __r
 // One workgroup of 1024 lanes per set (144 KB of LDS: one workgroup per CU, four waves per SIMD).
 // Two instances: up to 2048 buckets per set (the prover's 12-bit SRS windows: 8 KB of bins, 36864 staged entries — four
 // chunks for a dense 135 k-entry set) and up to 8192 (32 KB of bins, 28672 staged entries).
-constexpr int SORT2_BLOCK = 1024;
-constexpr uint32_t SORT2_SLACK = 2048, SORT2_MAX_CHUNKS = 64;
-constexpr uint32_t SORT2_CAP_SMALL_H = 36864, SORT2_CAP_LARGE_H = 28672, SORT2_SMALL_H = 2048;
-
 template <uint32_t MAX_H, uint32_t SORT2_CAP>
 __global__ __launch_bounds__(SORT2_BLOCK) void k_g1_sort_sets_staged(const uint32_t* __restrict__ scalars, WindowTable wt, SortSetParams sp,
                                                                     uint16_t* __restrict__ digits16, uint32_t* __restrict__ counts,
@@ -743,9 +737,6 @@ __global__ __launch_bounds__(SORT2_BLOCK) void k_g1_sort_sets_staged(const uint3
 // whether or not it fitted, so when a stream was overfilled (few distinct scalars) the host knows the exact sizes and runs pass A
 // again with exact stream offsets (exact_base) — no scalar distribution falls back to global atomics unless one partition holds
 // more than 64 stage chunks (2.2 M entries).  Wave-uniform bins (all-equal scalars) cost one LDS atomic per wave, not 64.
-constexpr int PART_BLOCK = 1024;
-constexpr uint32_t PART_TILE_ENTRIES = 32768, PART_MAX_P = 1024, PART_MAX_HP = 1024, PART_STAGE = 36864, PART_SLACK = 2048, PART_MAX_CHUNKS = 64;
-
 struct PartParams {
     uint32_t n, H, groups, tiles_per_set, P, pshift;      // pshift = log2(H / P): bucket >> pshift = partition
     uint32_t tile;                                        // scalars per pass-A workgroup: tile * W <= PART_TILE_ENTRIES, tile <= 2048
@@ -956,7 +947,6 @@ __global__ __launch_bounds__(PART_BLOCK) void k_g1_part_sort(const uint2* __rest
 // A wave otherwise waits for its longest bucket: with ~20 points per bucket (Poisson) a third of the lane-cycles idle.
 // Counting sort over 256 size classes (sizes >= 696 share the first class, see size_class): per-workgroup histograms in LDS, a scan
 // over (class-major, workgroup-minor) cells, then each workgroup places its buckets.  Order inside a class is free.
-constexpr int SZ_BLOCK = 256, SZ_ITEMS = 8, SZ_TILE = SZ_BLOCK * SZ_ITEMS, SZ_CLASSES = 256;
 // class 0 = largest.  One class per size up to 191 entries, then steps of 8 (lanes of a wave differ by < 4 % there) up to 695: lists
 // of G1_LONG_BUCKET entries or more are shared by 16 or 64 lanes (k_g1_accumulate_long), similar lengths side by side.
 DR_DEV uint32_t size_class(uint32_t count) {
@@ -1110,7 +1100,6 @@ __global__ __launch_bounds__(64) void k_g1_accumulate_long(const uint32_t* __res
 // 64 additions per lane, whatever the scalars.  Both kernels find their work by the same scan: the buckets of the largest size class
 // (>= 696 entries) lead `perm`; 64 of them at a time, a wave prefix sum over their segment counts numbers the segments, and segment s
 // belongs to block s mod gridDim.  Fixed small grids; both return at once when the class is empty.
-constexpr uint32_t G1_HEAVY_SLOTS = 2048;                 // grid of k_g1_accumulate_heavy: two waves per SIMD
 // Segment length of a launch: the heavy lists' entries spread over the walk's 2048 waves — total / (2048 - heavy buckets), every
 // bucket's last segment being partial —, a multiple of 64, at least 1024 (a segment ends with a six-addition shuffle tree); 4096 when
 // there are too many heavy buckets for that.  Both kernels compute it the same way (one pass over the leading size class).
@@ -1354,7 +1343,6 @@ __global__ __launch_bounds__(128) void k_g1_reduce_level(const uint32_t* __restr
 // sum of the Y_l.  Per set: T/4 lanes x (8 + 2 log2(T/4) + 11) operations — 930 for T = 128, against the 128 x 17 of the
 // chunk kernel's double-and-add tail plus the fold, and 2 additions per bucket at the first level instead of 3.
 // Sets are packed into 64-lane workgroups; one inlined addition and one inlined doubling, operands muxed per step.
-constexpr int RS_BLOCK = 64, RS_GROUP = 4;
 // (no occupancy cap: three live accumulators need ~390 registers, and with T/4 lanes per set the launch is at most one wave
 // per SIMD anyway)
 // `odd`: bucket j holds the odd multiple 2j + 1 (WindowTable::odd): value = 2 * [sum_j (j + 1) B_j] - sum_j B_j — one more step, on
@@ -1428,7 +1416,6 @@ __global__ __launch_bounds__(RS_BLOCK) void k_g1_reduce_set_scan(const uint32_t*
 // Buckets per lane: 8 fills one wave per SIMD at 2^19 buckets (the kernel's three accumulators take ~390 registers: one resident wave);
 // a smaller MSM has fewer buckets than the chip has such lanes and takes 4, 2 or 1 per lane — the chain is 2 PER_LANE + 17 additions
 // deep (33 at 8, 19 at 1), and the chain is all this launch costs (2^16 pairs: 0.54 -> ~0.3 ms).
-constexpr int WS_BLOCK = 256;
 template <int WS_PER_LANE>
 __global__ __launch_bounds__(WS_BLOCK) void k_g1_reduce_wg_scan(const uint32_t* __restrict__ buckets, uint32_t* __restrict__ out /* [workgroup][2]: V, S */) {
     __shared__ uint32_t sm[WS_BLOCK * XYZZ_RAW_WORDS];

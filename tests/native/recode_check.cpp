@@ -55,7 +55,7 @@ static void fail(const char* what, int w, const uint32_t (&k)[9]) {
     }
 }
 
-static dr::WindowTable naf_table(int w) {         // capi_msm.hip: msm_device, tiling mode 2
+static dr::WindowTable naf_table(int w) {         // msm_plan.hpp: msm_shape, the non-adjacent form
     dr::WindowTable wt{};
     wt.W = (256 + w - 1) / w;
     wt.cmax = w;

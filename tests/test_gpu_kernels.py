@@ -439,8 +439,9 @@ def test_g1_msm_degenerate_scalars_at_full_size_within_twice_the_random_time(ctx
 
 @pytest.mark.parametrize("bits,batch", [(12, 2100), (9, 16500)])
 def test_g1_msm_many_bucket_sets_level_reduction(ctx, srs_bytes, bits, batch):
-    """Thousands of small MSMs over a window table take the level-wise bucket reduction (k_g1_reduce_level/_final:
-    two levels at H = 2048, one at H = 256); sampled results against the oracle, plus all-zero and single-term vectors."""
+    """Thousands of small MSMs over a 24-point table (a row per bit): the non-adjacent form, the per-set LDS sort and the set scan
+    (tests/native/msm_plan_check.cpp pins the path; the level-wise reduction is test_g1_msm_window_rows_take_the_level_reduction);
+    sampled results against the oracle, plus all-zero and single-term vectors."""
     n = 24
     rng = random.Random(bits)
     tabled = ctx.srs_load(srs_bytes[: 96 * n]).precompute(bits)
@@ -455,6 +456,27 @@ def test_g1_msm_many_bucket_sets_level_reduction(ctx, srs_bytes, bits, batch):
     for i in range(batch):
         assert got[i] == want[i % len(vecs)], i
     tabled.close()
+
+
+@pytest.mark.parametrize("bits,batch", [(14, 600), (15, 300)])
+def test_g1_msm_window_rows_take_the_level_reduction(ctx, bits, batch):
+    """Hundreds of MSMs over the 14- and 15-bit window rows of 20000 synthetic bases (too many for a row per bit): 8192 and 16384 buckets
+    per set take the level-wise reduction (k_g1_reduce_level1 / _level / _final; tests/native/msm_plan_check.cpp pins the path), after
+    the LDS sort and the global-atomic sort — every result equals the closed form [sum k_i (1 + i)] G, incl. zero, r - 1 and one term."""
+    import bench
+
+    n = 64
+    srs = ctx.srs_synthetic(bench.G1_BE, 20000, first=1).precompute(bits)
+    assert srs.table_info(n, batch)["rows"] == -(-256 // bits)                  # window rows
+    rng = random.Random(bits)
+    vecs = [[rng.randrange(coracle.FR_P) for _ in range(n)] for _ in range(5)]
+    vecs += [[0] * n, [coracle.FR_P - 1] + [0] * (n - 1), [0] * (n - 1) + [1]]
+    ks = b"".join(b"".join(k.to_bytes(32, "little") for k in vecs[i % len(vecs)]) for i in range(batch))
+    want = [None if not any(v) else _closed_form_be(v) for v in vecs]
+    got = ctx.g1_msm_batch(srs, ks, n)
+    for i in range(batch):
+        assert got[i] == want[i % len(vecs)], i
+    srs.close()
 
 
 @pytest.mark.parametrize("bits,n,batch", [(9, 700, 40), (12, 300, 70), (10, 64, 4100), (8, 1, 33)])
@@ -480,8 +502,9 @@ def test_g1_msm_batched_over_table_matches_plain(ctx, srs_bytes, bits, n, batch)
 @pytest.mark.parametrize("bits,n", [(9, 513), (10, 2048), (12, 6145)])
 def test_g1_msm_a_few_over_a_table_take_the_workgroup_scan(ctx, srs_bytes, bits, n):
     """1 .. 33 MSMs over a window table in one call — RingVRF.prove of ONE proof commits 4, 1 and 2 polynomials this way; up to 32 take the
-    workgroup-scan reduction with a host fold per index group, 33 the chunk kernels: every result equals the oracle's, incl. a zero
-    vector, an all-equal vector, scalars >= r and a vector whose scalars are +-1 (most buckets empty)."""
+    workgroup-scan reduction with a host fold per index group, 33 the chunk kernels (so do 9 .. 32 MSMs of 2048 points over 10-bit
+    windows: their 512 buckets per set are fewer than the scan's span; tests/native/msm_plan_check.cpp pins every path): every result
+    equals the oracle's, incl. a zero vector, an all-equal vector, scalars >= r and a vector whose scalars are +-1 (most buckets empty)."""
     rng = random.Random(bits * 7 + n)
     srs = ctx.srs_load(srs_bytes[: 96 * n]).precompute(bits)
     vecs = [b"".join(rng.randrange(coracle.FR_P).to_bytes(32, "little") for _ in range(n)) for _ in range(5)]
