@@ -10,11 +10,14 @@ RingRoot, the SRS and the per-ring prover tables are resident in HBM before the 
 are 2 short byte strings per proof.  Hidden (ZK) rows are drawn at random as in production (test_vectors=False);
 a parity subset is proved again with test_vectors=True and compared byte-for-byte with the CPU oracle.
 
-The timed region runs with the library's per-kernel timers OFF; the same K steps are then repeated with the timers on
-(HIP events on the streams the kernels are launched on) and that pass supplies `gpu_kernel_ms_per_step` and the
-dominant kernel's average launch duration of `roofline`.
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps (the library's per-kernel timers
+OFF), --dump-outputs if given, and the JSON line.  Its `parity_ok` is batch_verify's verdict on every timed step; the
+figures that take runs of their own are null in its line.
 
-Secondary measurements in the same JSON line (rank 0, one GPU):
+--full adds everything else, after the timed region: the same K steps repeated with the timers on (HIP events on the
+streams the kernels are launched on), which supply `gpu_kernel_ms_per_step` and the dominant kernel's average launch
+duration of `roofline`; the parity subset above and the CPU baselines (`--cpu-proofs`, `--cpu-workers`); and these
+secondary measurements (rank 0, one GPU; `--extras 0` and `--msm-log2n 0` leave them out):
   bsn_scalar_mul     BASELINE configs[1]: 4096 Bandersnatch variable-base scalar multiplications (SURVEY 8(d) config 2 inputs)
   g1_msm             BASELINE configs[2]: one G1 Pippenger MSM over 2^20 (and 2^16) synthetic bases
   other_ring_sizes   the metric's other ring sizes: 256 (N = 1024) and 3000 (N = 4096, known-tau SRS: BASELINE configs[4]'s shape)
@@ -24,7 +27,7 @@ Secondary measurements in the same JSON line (rank 0, one GPU):
   host_threads       the headline step with 4 and 2 host worker threads (what a rank gets when N ranks share a host), phase times by name
   pipelined_prove_verify  the headline's work with batch_verify of batch k on a helper thread beside prove_batch of batch k + 1
   batch_sweep        the headline's step at 512 and 2048 proofs per call
-With N ranks (one per GPU) every rank proves and verifies its own 1024 proofs â€” independent units, no collective.  N > 1 adds
+With N ranks (one per GPU) every rank proves and verifies its own 1024 proofs â€” independent units, no collective.  N > 1 with --full adds
   config5            BASELINE configs[4] through the library call: ONE batch of 1024 x N proofs over ring 3839 (the largest ring of
                      domain 4096, known-tau SRS) sharded by parallel.prove_batch_sharded / batch_verify_sharded, the gather of the
                      784-byte proofs inside the timed region and timed on its own; parity: proofs of different shards vs the oracle
@@ -32,7 +35,7 @@ With N ranks (one per GPU) every rank proves and verifies its own 1024 proofs â€
                      (dot_ring_amd/parallel.py, dr_comm_*), `rccl_ranks` = ncclCommCount
 No PyTorch anywhere: a launcher only has to export RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT.
 
-Launch: python bench.py [--gpus N --steps K --warmup W --dump-outputs DIR].  For N > 1 either through torch.distributed.run (one rank per GPU) or as
+Launch: python bench.py [--gpus N --steps K --warmup W --dump-outputs DIR --full].  For N > 1 either through torch.distributed.run (one rank per GPU) or as
 this bare command: with no RANK in the environment the process starts the N rank processes itself (fresh children, before any
 GPU call of its own â€” the shape of the reference's tests/benchmark/bench_ring_proof.py:168-182), relays rank 0's JSON line and
 exits with the worst child's code.  A collective that fails or stalls still prints the line, and the exit code is non-zero.
@@ -685,9 +688,9 @@ def config5_sharded_leg(d, ring_size: int, batch_per_rank: int, steps: int, pari
 
 def host_threads_sweep(args, counts=(4, 2)):
     """The headline step with fewer host worker threads (DOTRING_HOST_THREADS; the N-rank launcher gives each rank cores // N of them):
-    one child process per setting â€” the pool is sized once per process â€” running this script's timed region only, with the library's
-    phase trace on (DOTRING_TRACE) so that the host phases of the verifier show by name.  Children run one after the other while this
-    process is idle; they share its GPU."""
+    one child process per setting â€” the pool is sized once per process â€” running this script's plain run (the timed region only), with
+    the library's phase trace on (DOTRING_TRACE) so that the host phases of the verifier show by name.  Children run one after the other
+    while this process is idle; they share its GPU."""
     import re
     import subprocess
 
@@ -698,7 +701,7 @@ def host_threads_sweep(args, counts=(4, 2)):
         for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
             env.pop(k, None)
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "3", "--warmup", "1", "--ring-size", str(args.ring_size),
-               "--batch", str(args.batch), "--cpu-proofs", "0", "--msm-log2n", "0", "--extras", "0"]
+               "--batch", str(args.batch)]
         try:
             proc = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
             line = json.loads([ln for ln in proc.stdout.splitlines() if ln.startswith("{")][-1])
@@ -861,15 +864,22 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--ring-size", type=int, default=1024)
     ap.add_argument("--batch", type=int, default=1024, help="proofs per GPU per step")
-    ap.add_argument("--cpu-proofs", type=int, default=16, help="proofs in the CPU baseline sample (0 = skip)")
-    ap.add_argument("--cpu-workers", type=int, default=-1, help="processes of the all-cores CPU baseline (-1 = min(16, cores), 0 = skip)")
-    ap.add_argument("--msm-log2n", type=int, default=20, help="secondary G1 MSM size (0 = skip)")
-    ap.add_argument("--extras", type=int, default=1, help="0 = skip the secondary legs (bsn_scalar_mul, other ring sizes, distinct signers)")
+    ap.add_argument("--cpu-proofs", type=int, default=16, help="with --full: proofs in the oracle parity subset and the CPU baseline sample (0 = skip)")
+    ap.add_argument("--cpu-workers", type=int, default=-1,
+                    help="with --full: processes of the all-cores CPU baseline (-1 = min(16, cores), 0 = skip)")
+    ap.add_argument("--msm-log2n", type=int, default=20, help="with --full: secondary G1 MSM size (0 = skip)")
+    ap.add_argument("--extras", type=int, default=1,
+                    help="with --full: 0 = skip the secondary legs (bsn_scalar_mul, other ring sizes, distinct signers, config5)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed (rank 0's batch) to DIR/<name>.npy, float32, at most 64 MB")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the per-kernel timer pass, the oracle parity subset, the CPU baselines and the "
+                         "secondary legs (a plain run measures the headline alone)")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        args.cpu_proofs = args.cpu_workers = args.msm_log2n = args.extras = 0
 
     if "RANK" not in os.environ and args.gpus > 1:
         return launch_ranks(args.gpus, sys.argv[1:])
@@ -930,9 +940,11 @@ def main() -> int:
     if ctl is not None:
         rank_ms = [s_[0] / args.steps * 1e3 for s_ in stats]           # every rank's own timed region (straggling shows here)
 
-    # ---- the same steps again with the per-kernel timers on (every context of this process: prove_batch's helper threads too)
-    roof, kernel_ms = ring_roofline(w, args.steps, barrier)
-    if ctl is not None:
+    # ---- --full: the same steps again with the per-kernel timers on (every context of this process: prove_batch's helper threads too)
+    roof = kernel_ms = None
+    if args.full:
+        roof, kernel_ms = ring_roofline(w, args.steps, barrier)
+    if roof is not None and ctl is not None:
         # every rank measured its own GPU: the line carries rank 0's roofline in full and the others' figures beside it
         rec = struct.pack("<dddd", roof["frac"], roof["achieved"], roof["avg_kernel_ms"], roof["valu"]["frac"] or 0.0)
         roof["by_rank"] = [dict(zip(("frac", "achieved", "avg_kernel_ms", "valu_frac"), struct.unpack("<dddd", b))) for b in ctl.all_gather(rec)]
@@ -962,41 +974,42 @@ def main() -> int:
 
         total = batch * world * args.steps
         value = total / elapsed
-        traffic = traffic_source = None
-        tpath = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-        if os.path.exists(tpath):
+        if roof is not None:          # --full: the pass with the per-kernel timers ran
+            traffic = traffic_source = None
+            tpath = os.path.join(ROOT, "profiles", "hbm_traffic.json")
+            if os.path.exists(tpath):
+                try:
+                    rec = json.load(open(tpath))
+                    traffic = rec.get(f"ringvrf_ring{args.ring_size}_batch{batch}", {}).get("k_g1_accumulate_bytes_per_launch")
+                    traffic_source = rec.get("_source", "profiles/hbm_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of tools/profile_round.sh, "
+                                                        "NOT measured in this run)") if traffic else None
+                except Exception:
+                    traffic = None
+            roof["traffic"], roof["traffic_source"] = traffic, traffic_source
+            # the clock the chip holds under this kernel, from GRBM_GUI_ACTIVE / duration of its launches in the rocprofv3 --pmc pass
+            # (profiles/hbm_traffic.json: "_clock_ghz"); the nominal 2.4 GHz prices the ceiling too high
+            clock_ghz, clock_source = 2.0, "default (no _clock_ghz in profiles/hbm_traffic.json)"
             try:
                 rec = json.load(open(tpath))
-                traffic = rec.get(f"ringvrf_ring{args.ring_size}_batch{batch}", {}).get("k_g1_accumulate_bytes_per_launch")
-                traffic_source = rec.get("_source", "profiles/hbm_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of tools/profile_round.sh, "
-                                                    "NOT measured in this run)") if traffic else None
+                if rec.get("_clock_ghz"):
+                    clock_ghz, clock_source = float(rec["_clock_ghz"]), rec.get("_clock_source", "profiles/hbm_traffic.json")
             except Exception:
-                traffic = None
-        roof["traffic"], roof["traffic_source"] = traffic, traffic_source
-        # the clock the chip holds under this kernel, from GRBM_GUI_ACTIVE / duration of its launches in the rocprofv3 --pmc pass
-        # (profiles/hbm_traffic.json: "_clock_ghz"); the nominal 2.4 GHz prices the ceiling too high
-        clock_ghz, clock_source = 2.0, "default (no _clock_ghz in profiles/hbm_traffic.json)"
-        try:
-            rec = json.load(open(tpath))
-            if rec.get("_clock_ghz"):
-                clock_ghz, clock_source = float(rec["_clock_ghz"]), rec.get("_clock_source", "profiles/hbm_traffic.json")
-        except Exception:
-            pass
-        v = roof["valu"]
-        v.update({"peak_gadd_s_nominal_clock": VALU_PEAK_GADD_S, "nominal_clock_ghz": 2.4,
-                  # at the measured clock the ceiling is priced at the architectural issue rate â€” one wave-instruction per 4 cycles per SIMD
-                  # (16 lanes per cycle) â€” not at the 4.2 cycles of the v_mad_i64_i32 micro-benchmark; the static instruction count holds
-                  # ~150 cold instructions (the exact zero test of the exceptional cases) that a round of the loop does not execute, so a
-                  # fraction slightly above 1 means "at the issue rate", not faster than it
-                  "peak_gadd_s_at_measured_clock": 1024 * clock_ghz * 1e9 / 4.0 * 64 / MADD_VALU_INSTRUCTIONS / 1e9, "measured_clock_ghz": clock_ghz,
-                  "measured_clock_source": clock_source,
-                  "frac_at_measured_clock": v["achieved_gadd_s"] / (1024 * clock_ghz * 1e9 / 4.0 * 64 / MADD_VALU_INSTRUCTIONS / 1e9) if v["achieved_gadd_s"] else None,
-                  "instructions_source": MADD_SOURCE, "isolated_chain_gadd_s": MEASURED_CHAIN_GADD_S,
-                  "isolated_chain_source": "profiles/r02_ubench_limbs_fused.txt (tools/ubench_limbs.hip on another box; not re-measured in this run)"})
-        # per-proof unique traffic (11N scalars + 14 NTT passes' data + 784 B out), 3.17 KB per
-        # domain point = 6.5 MB per proof at N = 2048, over the whole job
-        roof["whole_proof"] = {"algorithmic_bytes_per_proof": 3174 * n_dom, "achieved": 3174 * n_dom * value / 1e9, "unit": "GB/s",
-                               "frac": 3174 * n_dom * value / 1e9 / (HBM_PEAK_GBS * world)}
+                pass
+            v = roof["valu"]
+            v.update({"peak_gadd_s_nominal_clock": VALU_PEAK_GADD_S, "nominal_clock_ghz": 2.4,
+                      # at the measured clock the ceiling is priced at the architectural issue rate â€” one wave-instruction per 4 cycles per SIMD
+                      # (16 lanes per cycle) â€” not at the 4.2 cycles of the v_mad_i64_i32 micro-benchmark; the static instruction count holds
+                      # ~150 cold instructions (the exact zero test of the exceptional cases) that a round of the loop does not execute, so a
+                      # fraction slightly above 1 means "at the issue rate", not faster than it
+                      "peak_gadd_s_at_measured_clock": 1024 * clock_ghz * 1e9 / 4.0 * 64 / MADD_VALU_INSTRUCTIONS / 1e9, "measured_clock_ghz": clock_ghz,
+                      "measured_clock_source": clock_source,
+                      "frac_at_measured_clock": v["achieved_gadd_s"] / (1024 * clock_ghz * 1e9 / 4.0 * 64 / MADD_VALU_INSTRUCTIONS / 1e9) if v["achieved_gadd_s"] else None,
+                      "instructions_source": MADD_SOURCE, "isolated_chain_gadd_s": MEASURED_CHAIN_GADD_S,
+                      "isolated_chain_source": "profiles/r02_ubench_limbs_fused.txt (tools/ubench_limbs.hip on another box; not re-measured in this run)"})
+            # per-proof unique traffic (11N scalars + 14 NTT passes' data + 784 B out), 3.17 KB per
+            # domain point = 6.5 MB per proof at N = 2048, over the whole job
+            roof["whole_proof"] = {"algorithmic_bytes_per_proof": 3174 * n_dom, "achieved": 3174 * n_dom * value / 1e9, "unit": "GB/s",
+                                   "frac": 3174 * n_dom * value / 1e9 / (HBM_PEAK_GBS * world)}
         g1 = bsn = others = distinct = single = pipelined = sweep = msm_batched = threads_sweep = None
         if world == 1 and args.extras:
             # the second half of BASELINE's metric at this ring size: the batched G1 MSM of `batch` 3N-term commitments
@@ -1067,7 +1080,7 @@ def main() -> int:
             "parity_ok": parity_ok,
             "prove_only_proofs_per_s": batch * args.steps / prove_s if prove_s else None,
             "verify_only_proofs_per_s": batch * args.steps / verify_s if verify_s else None,
-            "gpu_kernel_ms_per_step": {k: round(v, 3) for k, v in kernel_ms.items() if v > 0.0005},
+            "gpu_kernel_ms_per_step": {k: round(v, 3) for k, v in kernel_ms.items() if v > 0.0005} if kernel_ms is not None else None,
             "bsn_scalar_mul": bsn,
             "g1_msm": g1,
             "g1_msm_batched": msm_batched,
@@ -1087,7 +1100,7 @@ def main() -> int:
             print("bench.py: PARITY FAILURE â€” GPU result differs from the oracle", file=sys.stderr)
             rc = 1
 
-    # ---- N > 1: BASELINE configs[4].  (a) its per-GPU shape â€” ring 3839 (domain 4096, known-tau SRS), `batch` proofs per rank,
+    # ---- N > 1 with --full: BASELINE configs[4].  (a) its per-GPU shape â€” ring 3839 (domain 4096, known-tau SRS), `batch` proofs per rank,
     # prove + verify, proofs sharded per rank with no collective, parity subset on rank 0; (b) the base-sharded MSM, the one
     # place with an exchange step: ncclAllGather of one point per rank through dr_comm_* (TCP star when the ranks share a GPU).
     # The collective part is guarded: a collective library that fails or stalls on this node is reported in the line instead

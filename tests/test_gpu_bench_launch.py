@@ -1,8 +1,9 @@
 """GPU: bench.py for N > 1 started as ONE bare command: the process spawns its two ranks itself, both share
 the test box's single GPU (DOTRING_BENCH_SHARE_GPU=1: device 0 for every rank, TCP all-gather since RCCL refuses two ranks per
-device), the line carries n_gpus = 2, a CPU baseline and per-rank rooflines, the config5 leg (ONE batch over ring 3839 / domain 4096 sharded by
+device), and with --full the line carries n_gpus = 2, a CPU baseline and per-rank rooflines, the config5 leg (ONE batch over ring 3839 / domain 4096 sharded by
 parallel.prove_batch_sharded, gathered, verified, proofs of both shards against the oracle) and the base-sharded MSM legs;
-and a collective that cannot come up still prints the line but exits non-zero."""
+and a collective that cannot come up still prints the line but exits non-zero.  A plain run (no --full) on one GPU measures the
+headline alone."""
 import json
 import os
 import subprocess
@@ -23,7 +24,7 @@ def _bench(extra_env, *flags, timeout=900):
 
 
 def test_bare_command_two_ranks_sharing_the_gpu():
-    proc = _bench({"DOTRING_BENCH_SHARE_GPU": "1"}, "--batch", "256", "--cpu-proofs", "2", "--msm-log2n", "16")
+    proc = _bench({"DOTRING_BENCH_SHARE_GPU": "1"}, "--full", "--batch", "256", "--cpu-proofs", "2", "--msm-log2n", "16")
     assert proc.returncode == 0, proc.stderr[-3000:]
     lines = [t for t in proc.stdout.splitlines() if t.startswith("{")]
     assert len(lines) == 1
@@ -48,7 +49,7 @@ def test_failing_collective_prints_the_line_and_exits_nonzero():
     loaded: rank 0's failure travels to its peer as a marker instead of leaving it in recv, the headline survives in the line,
     g1_msm_sharded names the failing call and ranks, and the exit code is non-zero"""
     proc = _bench({"DOTRING_BENCH_SHARE_GPU": "rccl", "DOTRING_BENCH_SHARDED_TIMEOUT": "60", "DOTRING_RCCL_LIB": "/nonexistent/librccl.so"},
-                  "--batch", "64", "--cpu-proofs", "0", "--msm-log2n", "12", "--extras", "0")
+                  "--full", "--batch", "64", "--cpu-proofs", "0", "--msm-log2n", "12", "--extras", "0")
     assert proc.returncode not in (0, 1, 2), proc.stderr[-3000:]
     lines = [t for t in proc.stdout.splitlines() if t.startswith("{")]
     assert len(lines) == 1
@@ -56,3 +57,23 @@ def test_failing_collective_prints_the_line_and_exits_nonzero():
     assert line["n_gpus"] == 2 and line["value"] > 0
     sh = line["g1_msm_sharded"]
     assert "error" in sh and sorted(sh["failed_ranks"]) == [0, 1] and "ncclCommInitRank" in sh["error"]
+
+
+def test_plain_run_measures_the_headline_alone(tmp_path):
+    """without --full one GPU runs set-up, warm-up, the timed steps and --dump-outputs only: the headline fields are there, the
+    figures of the timer pass, the oracle and the secondary legs are null"""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
+    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "64",
+                           "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, env=env)
+    assert proc.returncode == 0, proc.stderr[-3000:]
+    lines = [t for t in proc.stdout.splitlines() if t.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert (line["metric"], line["unit"], line["higher_is_better"], line["dtype"]) == ("ringvrf_proofs_per_sec", "proofs/s", True, "u32")
+    assert line["value"] > 0 and abs(line["value"] - 64 * 2 / (line["ms_per_step"] * 2 / 1e3)) < 1e-6 * line["value"]
+    assert line["parity_ok"] and (line["steps"], line["warmup"], line["n_gpus"]) == (2, 1, 1)
+    for key in ("roofline", "gpu_kernel_ms_per_step", "cpu_baseline", "cpu_baseline_all_cores", "g1_msm", "g1_msm_batched", "bsn_scalar_mul",
+                "other_ring_sizes", "single_call_ms", "pipelined_prove_verify"):
+        assert line[key] is None, key
+    assert line["dumped_outputs"]["files"]["pedersen_proof"] == [64, 192]
+    assert sorted(os.listdir(tmp_path)) == ["batch_verify.npy", "pedersen_proof.npy", "proof_index.npy"]

@@ -6,7 +6,7 @@ reps=${1:-3}
 out=${2:-gpurun_out/ab_commits.txt}
 : > "$out"
 one() {
-  (cd "$1" && python3 bench.py --steps 10 --warmup 2 --cpu-proofs 2 --cpu-workers 0 --msm-log2n 0 --extras 0 2>/dev/null) | python3 -c "
+  (cd "$1" && python3 bench.py --full --steps 10 --warmup 2 --cpu-proofs 2 --cpu-workers 0 --msm-log2n 0 --extras 0 2>/dev/null) | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 k=d['gpu_kernel_ms_per_step']

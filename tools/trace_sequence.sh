@@ -7,7 +7,7 @@ for cfg in "$@"; do
   tag=$(echo "$cfg" | tr ' =' '__')
   out=$root/gpurun_out/trseq/$tag
   mkdir -p "$out"
-  ( export $cfg; cd /tmp; rocprofv3 --kernel-trace --output-format csv -d "$out" -o run -- python "$root/bench.py" --steps 2 --warmup 1 --cpu-proofs 0 --cpu-workers 0 --msm-log2n 0 --extras 0 > "$out/log.txt" 2>&1 )
+  ( export $cfg; cd "$TMPDIR"; rocprofv3 --kernel-trace --output-format csv -d "$out" -o run -- python "$root/bench.py" --full --steps 2 --warmup 1 --cpu-proofs 0 --cpu-workers 0 --msm-log2n 0 --extras 0 > "$out/log.txt" 2>&1 )
   python3 - "$out" "$cfg" <<'PY'
 import csv, sys, re, json
 out, cfg = sys.argv[1], sys.argv[2]
