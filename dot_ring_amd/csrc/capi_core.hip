@@ -3,6 +3,7 @@
 #include "capi_internal.hpp"
 #include "hostsmall.hpp"
 #include "kernels_sw.hip.h"
+#include "kernels_ed25519.hip.h"
 
 namespace dri {
 
@@ -368,6 +369,7 @@ int dr_prof_get(dr_ctx* ctx, const char* name, double* total_ms, int* launches) 
 // ------------------------------------------------------------------------------- seam A
 int te_scalar_mul_batch_dev(dr_ctx* ctx, int cv, const void* d_pts, const void* d_scalars, size_t n, void* d_out) {
     TRY(use_ctx(ctx));
+    if (cv == dr::CV_ED25519) return fail(DR_ERR_INVALID, "device-resident scalar multiplication serves the curves over the BLS12-381 scalar field");
     if (n == 0) return DR_OK;
     if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
     // 4-bit windows (64 KiB of LDS per wave, 2 waves per CU) while the launch is latency-bound; 2-bit windows
@@ -483,9 +485,129 @@ int sw_boundary(dr_ctx* ctx, const uint8_t* sw_in, size_t n_in, uint8_t* sw_out,
 }
 }  // namespace
 
+// ---- Ed25519 (kernels_ed25519.hip.h).  Every call runs on the kernels: there is no host route for this curve, and nothing here
+// touches the BLS12-381 field of the other curves.  Secrets pass through io_a / io_b / io_c only, which ctx_wipe_scratch covers.
+namespace {
+int check_ed_elems(const uint8_t* p, size_t count, const char* what) {
+    for (size_t i = 0; i < count; i++) {
+        uint64_t v[4];
+        drh::load_le32(p + 32 * i, v);
+        if (drh::Mod256::geq(v, drh::mod_p25519().m)) return fail(DR_ERR_INVALID, std::string(what) + " coordinate is not a canonical field element");
+    }
+    return DR_OK;
+}
+int ed_scalar_mul_batch(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy) {
+    if (n == 0) return DR_OK;
+    if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
+    if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
+    TRY(check_ed_elems(pts_xy, 2 * n, "point"));
+    TRY(ctx->io_a.reserve(n * 64));
+    TRY(ctx->io_b.reserve(n * 32));
+    TRY(ctx->io_c.reserve(n * 64));
+    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, pts_xy, n * 64, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->io_b.p, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    TRY(launch(ctx, "k_ed_scalar_mul", [&] {
+        hipLaunchKernelGGL(dr::k_ed_scalar_mul, dim3(div_up(n, dr::ED_BLOCK)), dim3(dr::ED_BLOCK), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
+                           ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
+    }));
+    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_c.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->prof) TRY(prof_collect(ctx));
+    return DR_OK;
+}
+int ed_msm_groups(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy) {
+    if (groups == 0) return DR_OK;
+    if (m == 0 || m > 64) return fail(DR_ERR_INVALID, "group size must be in 1..64");
+    if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
+    const size_t n = groups * m;
+    if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
+    TRY(check_ed_elems(pts_xy, 2 * n, "point"));
+    uint32_t mpad = 1;
+    while (mpad < m) mpad <<= 1;
+    TRY(ctx->io_a.reserve(n * 64));
+    TRY(ctx->io_b.reserve(n * 32));
+    TRY(ctx->io_c.reserve(groups * 64));
+    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, pts_xy, n * 64, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->io_b.p, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    const uint32_t per_block = dr::ED_BLOCK / mpad;
+    TRY(launch(ctx, "k_ed_msm_groups", [&] {
+        hipLaunchKernelGGL(dr::k_ed_msm_groups, dim3(div_up(groups, per_block)), dim3(dr::ED_BLOCK), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
+                           ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)groups, (uint32_t)m, mpad);
+    }));
+    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_c.p, groups * 64, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->prof) TRY(prof_collect(ctx));
+    return DR_OK;
+}
+// fixed bases through the variable-base grouped kernel (each group's terms are the m bases): the same fixed schedule for the secret
+// scalars, no window table
+int ed_fixed_base_groups(dr_ctx* ctx, const uint8_t* bases_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy) {
+    if (groups == 0) return DR_OK;
+    if (m == 0 || m > 4) return fail(DR_ERR_INVALID, "1..4 fixed bases per group");
+    if (!bases_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
+    if (groups * m >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
+    std::vector<uint8_t> pts(groups * m * 64);
+    for (size_t g = 0; g < groups; g++) std::memcpy(pts.data() + 64 * m * g, bases_xy, 64 * m);
+    return ed_msm_groups(ctx, pts.data(), scalars, groups, m, out_xy);
+}
+// one MSM: groups of 64 terms in one launch, then the partial sums with scalar 1, 64 at a time, until one is left
+int ed_msm(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t out_xy[64]) {
+    if (n == 0) {
+        std::memset(out_xy, 0, 64);
+        out_xy[32] = 1;
+        return DR_OK;
+    }
+    if (!pts_xy || !scalars) return fail(DR_ERR_INVALID, "null buffer");
+    std::vector<uint8_t> pts(pts_xy, pts_xy + n * 64), sc(scalars, scalars + n * 32), part;
+    for (;;) {
+        if (n <= 64) return ed_msm_groups(ctx, pts.data(), sc.data(), 1, n, out_xy);
+        const size_t parts = (n + 63) / 64;
+        pts.resize(parts * 64 * 64, 0);
+        sc.resize(parts * 64 * 32, 0);
+        for (size_t i = n; i < parts * 64; i++) pts[64 * i + 32] = 1;         // padding: 0 * (0, 1)
+        part.resize(parts * 64);
+        TRY(ed_msm_groups(ctx, pts.data(), sc.data(), parts, 64, part.data()));
+        explicit_bzero(sc.data(), sc.size());
+        pts.swap(part);
+        n = parts;
+        sc.assign(n * 32, 0);
+        for (size_t i = 0; i < n; i++) sc[32 * i] = 1;
+    }
+}
+int ed_decode_points(dr_ctx* ctx, int mode, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
+    if (n == 0) return DR_OK;
+    if (!enc || !out_xy || !ok) return fail(DR_ERR_INVALID, "null buffer");
+    if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
+    TRY(ctx->io_a.reserve(n * 32));
+    TRY(ctx->io_b.reserve(n * 64));
+    TRY(ctx->io_c.reserve(n * 4));
+    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, enc, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    TRY(launch(ctx, "k_ed_decode_points", [&] {
+        const dim3 grid(div_up(n, dr::ED_BLOCK)), block(dr::ED_BLOCK);
+        if (mode == dr::ED_DEC_TAI)
+            hipLaunchKernelGGL(dr::k_ed_decode_points<dr::ED_DEC_TAI>, grid, block, 0, ctx->stream, ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(),
+                               ctx->io_c.as<uint32_t>(), (uint32_t)n);
+        else if (mode == dr::ED_DEC_CHECK)
+            hipLaunchKernelGGL(dr::k_ed_decode_points<dr::ED_DEC_CHECK>, grid, block, 0, ctx->stream, ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(),
+                               ctx->io_c.as<uint32_t>(), (uint32_t)n);
+        else
+            hipLaunchKernelGGL(dr::k_ed_decode_points<dr::ED_DEC_CODEC>, grid, block, 0, ctx->stream, ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(),
+                               ctx->io_c.as<uint32_t>(), (uint32_t)n);
+    }));
+    std::vector<uint32_t> flags(n);
+    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_b.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(flags.data(), ctx->io_c.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->prof) TRY(prof_collect(ctx));
+    for (size_t i = 0; i < n; i++) ok[i] = flags[i] ? 1 : 0;
+    return DR_OK;
+}
+}  // namespace
+
 int te_scalar_mul_batch(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy) {
     TRY(use_ctx(ctx));
     TRY(check_curve(cv));
+    if (cv == dr::CV_ED25519) return ed_scalar_mul_batch(ctx, pts_xy, scalars, n, out_xy);
     if (n == 0) return DR_OK;
     if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
     TRY(check_fr_elems(pts_xy, 2 * n, "point"));
@@ -548,6 +670,7 @@ int dr_te_scalar_mul_batch(dr_ctx* ctx, int curve, const uint8_t* pts_xy, const 
 int te_msm_groups(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy) {
     TRY(use_ctx(ctx));
     TRY(check_curve(cv));
+    if (cv == dr::CV_ED25519) return ed_msm_groups(ctx, pts_xy, scalars, groups, m, out_xy);
     if (groups == 0) return DR_OK;
     if (m == 0 || m > 64) return fail(DR_ERR_INVALID, "group size must be in 1..64");
     if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
@@ -622,6 +745,7 @@ static int te_fixed_table(dr_ctx* ctx, int cv, const uint8_t base_xy[64], const 
 int te_fixed_base_groups(dr_ctx* ctx, int cv, const uint8_t* bases_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy, bool sync) {
     TRY(use_ctx(ctx));
     TRY(check_curve(cv));
+    if (cv == dr::CV_ED25519) return ed_fixed_base_groups(ctx, bases_xy, scalars, groups, m, out_xy);
     if (groups == 0) return DR_OK;
     if (m == 0 || m > 4) return fail(DR_ERR_INVALID, "1..4 fixed bases per group");
     if (!bases_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
@@ -697,6 +821,7 @@ int te_msm(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* scalars, s
     TRY(use_ctx(ctx));
     TRY(check_curve(cv));
     if (!out_xy) return fail(DR_ERR_INVALID, "null buffer");
+    if (cv == dr::CV_ED25519) return ed_msm(ctx, pts_xy, scalars, n, out_xy);
     if (n == 0) {
         std::memset(out_xy, 0, 64);
         out_xy[32] = 1;
@@ -815,6 +940,7 @@ static int sw_decode_points(dr_ctx* ctx, bool tai, bool sw_out, const uint8_t* e
 }
 
 void launch_decode_points(dr_ctx* ctx, hipStream_t st, int cv, bool tai, const uint32_t* d_enc, uint32_t* d_xy, uint32_t* d_ok, size_t n) {
+    // (the ring verifier's decoder: its suites are over the BLS12-381 scalar field — load_suite refuses Ed25519 there)
     if (tai) {
         if (cv == dr::CV_JUBJUB)
             hipLaunchKernelGGL((dr::k_te_decode_points<dr::CV_JUBJUB, true>), dim3(div_up(n, dr::BSN_BLOCK)), dim3(dr::BSN_BLOCK), 0, st, d_enc, d_xy, d_ok, (uint32_t)n);
@@ -831,6 +957,7 @@ void launch_decode_points(dr_ctx* ctx, hipStream_t st, int cv, bool tai, const u
 int te_decode_points(dr_ctx* ctx, int cv, bool tai, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok, bool sw_out) {
     TRY(use_ctx(ctx));
     TRY(check_curve(cv));
+    if (cv == dr::CV_ED25519) return ed_decode_points(ctx, tai ? dr::ED_DEC_TAI : dr::ED_DEC_CHECK, enc, n, out_xy, ok);
     if (n == 0) return DR_OK;
     if (!enc || !out_xy || !ok) return fail(DR_ERR_INVALID, "null buffer");
     if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
@@ -865,6 +992,32 @@ int dr_bsn_decode_points(dr_ctx* ctx, const uint8_t* enc, size_t n, uint8_t* out
 }
 int dr_te_decode_points(dr_ctx* ctx, int curve, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
     return te_decode_points(ctx, curve, false, enc, n, out_xy, ok, true);
+}
+int dr_ed25519_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
+    TRY(use_ctx(ctx));
+    return ed_decode_points(ctx, check ? dr::ED_DEC_CHECK : dr::ED_DEC_CODEC, enc, n, out_xy, ok);
+}
+
+int dr_fe25519_ops_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
+    TRY(use_ctx(ctx));
+    if (n == 0) return DR_OK;
+    if (!a_limbs || !b_limbs || !out || !flags) return fail(DR_ERR_INVALID, "null buffer");
+    if (n >= (1ull << 24)) return fail(DR_ERR_INVALID, "batch too large");
+    const size_t rec = (size_t)dr::FE_SELFTEST_RECORDS * 32;
+    TRY(ctx->io_a.reserve(n * 72));
+    TRY(ctx->io_b.reserve(n * rec));
+    TRY(ctx->io_c.reserve(n * 4));
+    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, a_limbs, n * 36, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->io_a.as<uint8_t>() + n * 36, b_limbs, n * 36, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(dr::k_fe25519_selftest, dim3(div_up(n, 64)), dim3(64), 0, ctx->stream, ctx->io_a.as<int32_t>(),
+                       (const int32_t*)(ctx->io_a.as<uint8_t>() + n * 36), (uint32_t)n, ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> fl(n);
+    HIP_TRY(hipMemcpyAsync(out, ctx->io_b.p, n * rec, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(fl.data(), ctx->io_c.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < n; i++) flags[i] = (uint8_t)fl[i];
+    return DR_OK;
 }
 
 int dr_bsn_encode_to_curve_batch(dr_ctx* ctx, const uint8_t* u_pairs, size_t n, uint8_t* out_xy) {
@@ -986,6 +1139,7 @@ int load_suite(const dr_vrf_suite* s, drh::VrfSuite& out, bool allow_sw) {
     std::memcpy(out.blinding_base, s->blinding_base_xy, 64);
     out.cv = drh::te_curve(s->curve);
     if (!out.cv) return fail(DR_ERR_INVALID, "unknown curve id in VRF suite");
+    if (out.cv->ed25519 && !allow_sw) return fail(DR_ERR_INVALID, "this entry point does not serve the Ed25519 suite");
     if (out.cv->sw) {
         if (!allow_sw) return fail(DR_ERR_INVALID, "this entry point does not serve the short Weierstrass suite");
         // the kernels take the suite's constants as their TE images; the SW generator stays for its encoding

@@ -318,9 +318,14 @@ struct TeCurveHost {
     bool glv;                 // has the endomorphism the lane-pair kernels use
     bool tai;                 // hash-to-curve by try-and-increment (otherwise Elligator 2)
     bool sw = false;          // points cross the ABI as short Weierstrass affine x || y (33-byte encodings); TE inside
+    bool ed25519 = false;     // over GF(2^255 - 19), not the BLS12-381 scalar field: the kernels of kernels_ed25519.hip.h, no host route
 };
+inline const Mod256& mod_p25519() {   // Ed25519 base field (specs/ed25519.py)
+    static Mod256 s = [] { Mod256 t; const uint64_t p[4] = {0xffffffffffffffedULL, 0xffffffffffffffffULL, 0xffffffffffffffffULL, 0x7fffffffffffffffULL}; t.init(p); return t; }();
+    return s;
+}
 inline const TeCurveHost* te_curve(int id) {
-    static const TeCurveHost curves[3] = {
+    static const TeCurveHost curves[4] = {
         [] { TeCurveHost c{}; c.id = 0; c.n = mod_n();
              const uint64_t d[4] = {0xb369f2f5188d58e7ULL, 0xcb66677177e54f92ULL, 0xc66e3bf86be3b6d8ULL, 0x6389c12633c267cbULL};
              std::memcpy(c.d, d, 32); c.neg_a[0] = 5; c.scalar_bits = 253; c.glv = true; c.tai = false; return c; }(),
@@ -332,9 +337,17 @@ inline const TeCurveHost* te_curve(int id) {
         [] { TeCurveHost c{}; c.id = 2; c.n = mod_n();
              const uint64_t d[4] = {0xb369f2f5188d58e7ULL, 0xcb66677177e54f92ULL, 0xc66e3bf86be3b6d8ULL, 0x6389c12633c267cbULL};
              std::memcpy(c.d, d, 32); c.neg_a[0] = 5; c.scalar_bits = 253; c.glv = true; c.tai = true; c.sw = true; return c; }(),
+        // Ed25519 (specs/ed25519.py, the Ed25519_TAI variant): n = l = 2^252 + 0x14DEF9DEA2F79CD65812631A5CF5D3ED, a = -1, cofactor 8
+        [] { TeCurveHost c{}; c.id = 3;
+             const uint64_t n[4] = {0x5812631a5cf5d3edULL, 0x14def9dea2f79cd6ULL, 0x0000000000000000ULL, 0x1000000000000000ULL};
+             c.n.init(n);
+             const uint64_t d[4] = {0x75eb4dca135978a3ULL, 0x00700a4d4141d8abULL, 0x8cc740797779e898ULL, 0x52036cee2b6ffe73ULL};
+             std::memcpy(c.d, d, 32); c.neg_a[0] = 1; c.scalar_bits = 253; c.glv = false; c.tai = true; c.ed25519 = true; return c; }(),
     };
-    return id >= 0 && id <= 2 ? &curves[id] : nullptr;
+    return id >= 0 && id <= 3 ? &curves[id] : nullptr;
 }
+// the base field of a curve of the table
+inline const Mod256& te_field(const TeCurveHost& c) { return c.ed25519 ? mod_p25519() : mod_p(); }
 
 // ---------------------------------------------------------------- GLV decomposition (dot_ring/curve/glv.py:57-160)
 // k = k1 + k2*lambda (mod n) with |k1|, |k2| < 2^128, from the lattice basis v1 = (a1, b1), v2 = (a2, -a1) the reference
@@ -395,11 +408,12 @@ inline void put(Bytes& b, const void* p, size_t n) { const uint8_t* q = (const u
 inline void put8(Bytes& b, uint8_t v) { b.push_back(v); }
 inline void put_le64(Bytes& b, uint64_t v) { for (int i = 0; i < 8; i++) b.push_back((uint8_t)(v >> (8 * i))); }
 
-// compressed Twisted-Edwards point: y little-endian, bit 255 set iff x > p - x  (point.py:150-214)
-inline void enc_te_point(const uint8_t xy[64], uint8_t out[32]) {
+// compressed Twisted-Edwards point: y little-endian, bit 255 set iff x > p - x  (point.py:150-214; the sign rule of every TE suite,
+// Ed25519's included — not RFC 8032's parity of x)
+inline void enc_te_point(const uint8_t xy[64], uint8_t out[32], const Mod256& field = mod_p()) {
     uint64_t x[4], nx[4], zero[4] = {0, 0, 0, 0};
     load_le32(xy, x);
-    mod_p().sub(zero, x, nx);
+    field.sub(zero, x, nx);
     std::memcpy(out, xy + 32, 32);
     bool gt = false;
     for (int i = 3; i >= 0; i--) { if (x[i] != nx[i]) { gt = x[i] > nx[i]; break; } }
@@ -506,7 +520,7 @@ struct VrfSuite {
 // the suite's point encoding of xy given in the suite's own coordinates (TE, or SW for the SW suite)
 inline void enc_point(const VrfSuite& su, const uint8_t xy[64], uint8_t* out) {
     if (su.cv->sw) enc_sw_point(xy, out);
-    else enc_te_point(xy, out);
+    else enc_te_point(xy, out, te_field(*su.cv));
 }
 // squeeze `size` bytes of the stream defined by everything absorbed
 inline void vrf_squeeze(bool xof, const uint8_t* absorbed, size_t len, uint8_t* out, size_t size) {

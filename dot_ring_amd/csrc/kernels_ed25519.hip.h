@@ -1,0 +1,333 @@
+// Ed25519 kernels (DR_CURVE_ED25519; the reference's specs/ed25519.py, Ed25519_TAI variant): the twisted Edwards group law with
+// a = -1 over GF(2^255 - 19) (fe25519.hip.h) and the kernels that fill, for this curve, the roles kernels_te.hip.h /
+// kernels_bsn.hip.h fill for JubJub: variable-base scalar multiplication on a fixed schedule, grouped MSMs, point decoding and the
+// device half of try-and-increment.  The existing kernels stay as they are; the Bandersnatch / JubJub / SW code does not include
+// this header's field.
+//
+// Points cross the ABI as x || y little-endian (standard form: this field has no Montgomery form).  Extended coordinates
+// (X, Y, Z, T), x = X / Z, y = Y / Z, T = X Y / Z; dbl-2008-hwcd and add-2008-hwcd with a = -1, as curve.hip.h runs them for
+// JubJub.  The comments give the limb bound of every intermediate against fe25519.hip.h's contract ("n" = normal).
+#pragma once
+#include "fe25519.hip.h"
+
+namespace dr {
+
+constexpr int ED_BLOCK = 64;          // one wave per workgroup; 64 KiB of LDS table per wave, as k_bsn_scalar_mul
+constexpr int ED_TABLE = 8;           // entries 1P..8P
+constexpr int ED_PT_WORDS = 32;       // X, Y, Z, T x 8 canonical words
+
+struct EdPoint {
+    F25 x, y, z, t;
+};
+
+DR_DEV EdPoint ed_identity() {
+    EdPoint p;
+    p.x = F25::zero(); p.y = F25::one(); p.z = F25::one(); p.t = F25::zero();
+    return p;
+}
+
+// dbl-2008-hwcd, a = -1.  WITH_T = false skips T3 (the result is only doubled again).
+template <bool WITH_T>
+DR_DEV EdPoint ed_dbl(const EdPoint& p) {
+    const F25 A = sqr(p.x), B = sqr(p.y);                   // n
+    const F25 C = dbl(sqr(p.z));                            // < 2^30.01
+    const F25 E = carry(dbl(mul(p.x, p.y)));                // 2 x y: n
+    const F25 G = sub(B, A);                                // D + B with D = a A = -A: < 2^29.01
+    const F25 F = carry(sub(G, C));                         // n
+    const F25 H = neg(add(A, B));                           // D - B: < 2^30.01
+    EdPoint r;
+    r.x = mul(E, F);
+    r.y = mul(G, H);
+    r.z = mul(F, G);
+    if (WITH_T) r.t = mul(E, H);
+    else r.t = F25::zero();
+    return r;
+}
+
+// add-2008-hwcd, a = -1, unified (also right for doubling and the identity).  dt2 = d T2 (the caller's constant or table value).
+DR_DEV EdPoint ed_add_dt(const EdPoint& p, const EdPoint& q, const F25& dt2) {
+    const F25 A = mul(p.x, q.x), B = mul(p.y, q.y);          // n
+    const F25 C = mul(p.t, dt2);                            // n
+    const F25 D = mul(p.z, q.z);                            // n
+    const F25 E = mul2(p.x, q.y, p.y, q.x);                 // n (operands n or negated n: below 2^29.45)
+    const F25 F = sub(D, C), G = add(D, C);                 // < 2^29.01, < 2^30.01
+    const F25 H = carry(add(B, A));                         // B - a A: n
+    EdPoint r;
+    r.x = mul(E, F);
+    r.y = mul(G, H);
+    r.t = mul(E, H);
+    r.z = mul(F, G);
+    return r;
+}
+DR_DEV EdPoint ed_add(const EdPoint& p, const EdPoint& q) {
+    return ed_add_dt(p, q, mul(F25::constant<Fe25519Consts::D>(), q.t));
+}
+
+DR_DEV EdPoint ed_cneg(const EdPoint& p, bool negate) {
+    EdPoint r = p;
+    r.x = cneg(p.x, negate);
+    r.t = cneg(p.t, negate);
+    return r;
+}
+
+// ---------------------------------------------------------------- memory
+DR_DEV void ed_load8(const uint32_t* p, uint32_t (&w)[8]) {
+    const uint4* q = reinterpret_cast<const uint4*>(p);
+    const uint4 a = q[0], b = q[1];
+    w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
+    w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
+}
+DR_DEV void ed_store8(uint32_t* p, const uint32_t (&w)[8]) {
+    uint4* q = reinterpret_cast<uint4*>(p);
+    q[0] = make_uint4(w[0], w[1], w[2], w[3]);
+    q[1] = make_uint4(w[4], w[5], w[6], w[7]);
+}
+DR_DEV F25 ed_load_fe(const uint32_t* p) {
+    uint32_t w[8];
+    ed_load8(p, w);
+    return fe_unpack(w);
+}
+DR_DEV void ed_store_fe(uint32_t* p, const F25& a) {
+    uint32_t w[8];
+    fe_pack(a, w);
+    ed_store8(p, w);
+}
+DR_DEV void ed_store_affine(uint32_t* out, const EdPoint& acc) {
+    const F25 zi = fe_inv(acc.z);
+    ed_store_fe(out, mul(acc.x, zi));
+    ed_store_fe(out + 8, mul(acc.y, zi));
+}
+// LDS table [entry][word][lane] (bank = lane whatever the entry), canonical words
+DR_DEV void ed_lds_store(uint32_t* tab, int entry, int lane, const EdPoint& p) {
+    uint32_t* base = tab + (size_t)entry * ED_PT_WORDS * ED_BLOCK + lane;
+    uint32_t x[8], y[8], z[8], t[8];
+    fe_pack(p.x, x); fe_pack(p.y, y); fe_pack(p.z, z); fe_pack(p.t, t);
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        base[(0 + i) * ED_BLOCK] = x[i];
+        base[(8 + i) * ED_BLOCK] = y[i];
+        base[(16 + i) * ED_BLOCK] = z[i];
+        base[(24 + i) * ED_BLOCK] = t[i];
+    }
+}
+DR_DEV EdPoint ed_lds_load(const uint32_t* tab, int entry, int lane) {
+    const uint32_t* base = tab + (size_t)entry * ED_PT_WORDS * ED_BLOCK + lane;
+    uint32_t x[8], y[8], z[8], t[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        x[i] = base[(0 + i) * ED_BLOCK];
+        y[i] = base[(8 + i) * ED_BLOCK];
+        z[i] = base[(16 + i) * ED_BLOCK];
+        t[i] = base[(24 + i) * ED_BLOCK];
+    }
+    EdPoint p;
+    p.x = fe_unpack(x); p.y = fe_unpack(y); p.z = fe_unpack(z); p.t = fe_unpack(t);
+    return p;
+}
+DR_DEV EdPoint ed_shfl_down(const EdPoint& p, unsigned delta) {
+    EdPoint o;
+#pragma unroll
+    for (int t = 0; t < FE_L; t++) {
+        o.x.l[t] = __shfl_down(p.x.l[t], delta, 64);
+        o.y.l[t] = __shfl_down(p.y.l[t], delta, 64);
+        o.z.l[t] = __shfl_down(p.z.l[t], delta, 64);
+        o.t.l[t] = __shfl_down(p.t.l[t], delta, 64);
+    }
+    return o;
+}
+
+// k mod l for a 256-bit k: floor((2^256 - 1) / l) = 15, so 16 conditional subtractions (the same count in every lane)
+DR_DEV void ed_reduce_mod_order(uint32_t (&k)[8]) {
+    constexpr uint32_t L[8] = {0x5cf5d3edu, 0x5812631au, 0xa2f79cd6u, 0x14def9deu, 0x00000000u, 0x00000000u, 0x00000000u, 0x10000000u};
+#pragma unroll 1
+    for (int it = 0; it < 16; it++) {
+        uint32_t d[8], borrow = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++) d[i] = subb(k[i], L[i], borrow);
+#pragma unroll
+        for (int i = 0; i < 8; i++) k[i] = borrow ? k[i] : d[i];
+    }
+}
+
+// k P for k < l < 2^253 on the fixed schedule of bsn_scalar_mul_core (kernels_te.hip.h): table 1P..8P in LDS, 64 signed 4-bit
+// windows, 4 doublings and one table addition each whatever the digits — the secret scalars of the provers go through here
+DR_DEV EdPoint ed_scalar_mul_core(uint32_t* tab, int lane, const F25& px, const F25& py, const uint32_t (&k)[8]) {
+    EdPoint P;
+    P.x = px; P.y = py; P.z = F25::one(); P.t = mul(px, py);
+    ed_lds_store(tab, 0, lane, P);
+    EdPoint Q = ed_dbl<true>(P);
+    ed_lds_store(tab, 1, lane, Q);
+#pragma unroll 1
+    for (int e = 2; e < ED_TABLE; e++) {
+        Q = ed_add(Q, P);
+        ed_lds_store(tab, e, lane, Q);
+    }
+    uint32_t dig[8];                 // 64 digits in [-8, 7], stored as d + 8
+    uint32_t carry_in = 0;
+#pragma unroll
+    for (int w = 0; w < 8; w++) {
+        uint32_t packed = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const uint32_t v = ((k[w] >> (4 * j)) & 15u) + carry_in;
+            carry_in = v >= 8u ? 1u : 0u;
+            packed |= ((v + 8u) & 15u) << (4 * j);
+        }
+        dig[w] = packed;
+    }
+    // (k < l < 2^253: the top nibble is <= 1, the final carry is 0)
+    const F25 d = F25::constant<Fe25519Consts::D>();
+    EdPoint acc = ed_identity();
+#pragma unroll 1
+    for (int w = 63; w >= 0; w--) {
+#pragma unroll 1
+        for (int j = 0; j < 3; j++) acc = ed_dbl<false>(acc);
+        acc = ed_dbl<true>(acc);
+        const int dg = (int)((dig[w >> 3] >> (4 * (w & 7))) & 15u) - 8;
+        const int mag = dg < 0 ? -dg : dg;
+        EdPoint T = ed_lds_load(tab, mag == 0 ? 0 : mag - 1, lane);
+        T = ed_cneg(T, dg < 0);
+        if (mag == 0) T = ed_identity();
+        acc = ed_add_dt(acc, T, mul(d, T.t));
+    }
+    return acc;
+}
+
+DR_DEV void ed_load_scalar(const uint32_t* p, uint32_t (&k)[8]) {
+    ed_load8(p, k);
+    ed_reduce_mod_order(k);
+}
+
+// out[i] = k[i] P[i].  pts: n x 16 words (x || y), ks: n x 8, out: n x 16.  One lane per multiplication.
+__global__ __launch_bounds__(ED_BLOCK) void k_ed_scalar_mul(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks,
+                                                            uint32_t* __restrict__ out, uint32_t n) {
+    __shared__ uint32_t tab[ED_TABLE * ED_PT_WORDS * ED_BLOCK];
+    const int lane = threadIdx.x;
+    uint32_t i = blockIdx.x * ED_BLOCK + lane;
+    const bool live = i < n;
+    if (!live) i = n - 1;            // keep the wave converged; the duplicate result is not stored
+    const F25 px = ed_load_fe(pts + (size_t)i * 16), py = ed_load_fe(pts + (size_t)i * 16 + 8);
+    uint32_t k[8];
+    ed_load_scalar(ks + (size_t)i * 8, k);
+    const EdPoint acc = ed_scalar_mul_core(tab, lane, px, py, k);
+    if (live) ed_store_affine(out + (size_t)i * 16, acc);
+}
+
+// out[g] = sum_{j<m} k[g m + j] P[g m + j]: one lane per term (m padded to mpad, a power of two <= 64), folded with shuffles —
+// k_bsn_msm_groups for this curve
+__global__ __launch_bounds__(ED_BLOCK) void k_ed_msm_groups(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks,
+                                                            uint32_t* __restrict__ out, uint32_t groups, uint32_t m, uint32_t mpad) {
+    __shared__ uint32_t tab[ED_TABLE * ED_PT_WORDS * ED_BLOCK];
+    const int lane = threadIdx.x;
+    const uint32_t per_block = ED_BLOCK / mpad;
+    const uint32_t g = blockIdx.x * per_block + lane / mpad;
+    const uint32_t j = lane % mpad;
+    const bool live = g < groups && j < m;
+    const size_t idx = live ? (size_t)g * m + j : 0;          // dead lanes recompute term 0 and are masked out
+    const F25 px = ed_load_fe(pts + idx * 16), py = ed_load_fe(pts + idx * 16 + 8);
+    uint32_t k[8];
+    ed_load_scalar(ks + idx * 8, k);
+    const EdPoint r = ed_scalar_mul_core(tab, lane, px, py, k);
+    EdPoint acc = live ? r : ed_identity();
+#pragma unroll 1
+    for (uint32_t s = mpad >> 1; s > 0; s >>= 1) acc = ed_add(acc, ed_shfl_down(acc, s));
+    if (g < groups && j == 0) ed_store_affine(out + (size_t)g * 16, acc);
+}
+
+// Decoding (the reference's point.py:150-214 with te_affine_point.py:297-316), one lane per 32-byte encoding: the sign is bit 255,
+// y the low 255 bits, y >= p rejected; x^2 = (y^2 - 1) / (d y^2 + 1) (= (1 - y^2) / (a - d y^2) with a = -1), no root rejected;
+// x is the larger of (x, p - x) iff the sign bit is set.  x = 0 (y = +-1) has both candidates 0, so the sign bit is ignored there,
+// and the reference's constructor accepts (0, 1) and (0, -1).  MODE:
+//   ED_DEC_CODEC  the codec alone: ok = decoded, out = (x, y)
+//   ED_DEC_CHECK  also the prime-order check: Q = 8 P is not the identity and [8^-1 mod l] Q = P (a torsion component of P is
+//                 killed by the 8 and does not come back) — the identity and all 8 torsion points are rejected
+//   ED_DEC_TAI    the device half of try-and-increment (point.py:252-296, whose masking leaves the 32 squeezed bytes as they are for
+//                 this curve): ok = decoded and 8 P is not the identity, out = 8 P
+enum { ED_DEC_CODEC = 0, ED_DEC_CHECK = 1, ED_DEC_TAI = 2 };
+template <int MODE>
+__global__ __launch_bounds__(ED_BLOCK) void k_ed_decode_points(const uint32_t* __restrict__ enc /* n*8 */, uint32_t* __restrict__ out_xy /* n*16 */,
+                                                               uint32_t* __restrict__ ok, uint32_t n) {
+    __shared__ uint32_t tab[MODE == ED_DEC_CHECK ? ED_TABLE * ED_PT_WORDS * ED_BLOCK : 1];
+    const int lane = threadIdx.x;
+    uint32_t i = blockIdx.x * ED_BLOCK + lane;
+    const bool live = i < n;
+    if (!live) i = n - 1;
+    uint32_t ys[8];
+    ed_load8(enc + (size_t)i * 8, ys);
+    const bool sign = (ys[7] >> 31) != 0;
+    ys[7] &= 0x7fffffffu;
+    bool valid;
+    {   // y < p: y + 19 does not reach 2^255
+        uint32_t c = 19u;
+#pragma unroll
+        for (int j = 0; j < 7; j++) c = (uint32_t)(((uint64_t)ys[j] + c) >> 32);
+        valid = ys[7] + c < 0x80000000u;
+    }
+    const F25 one = F25::one();
+    const F25 y = fe_unpack(ys);
+    const F25 y2 = sqr(y);
+    const F25 u = carry(sub(y2, one));
+    const F25 v = carry(add(mul(F25::constant<Fe25519Consts::D>(), y2), one));
+    F25 x;
+    if (!fe_sqrt_ratio(u, v, x)) valid = false;       // (v = 0 never happens: -1 / d is not a square; u / 0 has no root here either)
+    if (fe_is_larger(x) != sign) x = neg(x);
+    F25 ox = x, oy = y;
+    if constexpr (MODE != ED_DEC_CODEC) {
+        EdPoint P;
+        P.x = x; P.y = y; P.z = one; P.t = mul(x, y);
+        EdPoint Q = P;
+#pragma unroll 1
+        for (int j = 0; j < 3; j++) Q = ed_dbl<true>(Q);
+        if (fe_is_zero(Q.x)) { valid = false; Q = P; }  // 8 P = O (x = 0: 8 P lies in the prime-order subgroup, where only O has x = 0)
+        const F25 zi = fe_inv(Q.z);
+        const F25 qx = mul(Q.x, zi), qy = mul(Q.y, zi);
+        if constexpr (MODE == ED_DEC_TAI) {
+            ox = qx; oy = qy;
+        } else {
+            constexpr uint32_t HINV[8] = {0xe2dc2f79u, 0x6106e529u, 0x7d1cdad0u, 0x07d39db3u, 0x00000000u, 0x00000000u, 0x00000000u, 0x06000000u};
+            uint32_t k[8];
+#pragma unroll
+            for (int j = 0; j < 8; j++) k[j] = HINV[j];
+            const EdPoint R = ed_scalar_mul_core(tab, lane, qx, qy, k);
+            if (!fe_equal(R.x, mul(x, R.z)) || !fe_equal(R.y, mul(y, R.z))) valid = false;
+        }
+    }
+    if (!valid) { ox = F25::zero(); oy = F25::zero(); }
+    if (live) {
+        ed_store_fe(out_xy + (size_t)i * 16, ox);
+        ed_store_fe(out_xy + (size_t)i * 16 + 8, oy);
+        ok[i] = valid ? 1u : 0u;
+    }
+}
+
+// Diagnostic (dr_fe25519_ops_selftest): fe25519.hip.h's operations on raw limb images, one lane per (a, b) pair of 9 int32 limbs each,
+// so that tests can drive every operation at the limb bounds its contract allows.  out[i] = eleven canonical 32-byte records:
+// a b, a^2, a + b, a - b, -a, carry(a), a b + b a (mul2), a^-1 (0 for 0), sqrt(a) or 0, a itself (pack), sqrt(a / b) or 0;
+// flags[i]: bit 0 a is a square, bit 1 a / b has a root (fe_sqrt_ratio), bit 2 a is the larger of (a, -a).
+constexpr int FE_SELFTEST_RECORDS = 11;
+__global__ __launch_bounds__(64) void k_fe25519_selftest(const int32_t* __restrict__ a_limbs, const int32_t* __restrict__ b_limbs, uint32_t n,
+                                                         uint32_t* __restrict__ out, uint32_t* __restrict__ flags) {
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    F25 a, b;
+#pragma unroll
+    for (int t = 0; t < FE_L; t++) { a.l[t] = a_limbs[(size_t)i * FE_L + t]; b.l[t] = b_limbs[(size_t)i * FE_L + t]; }
+    uint32_t* o = out + (size_t)i * FE_SELFTEST_RECORDS * 8;
+    ed_store_fe(o + 0, mul(a, b));
+    ed_store_fe(o + 8, sqr(a));
+    ed_store_fe(o + 16, add(a, b));
+    ed_store_fe(o + 24, sub(a, b));
+    ed_store_fe(o + 32, neg(a));
+    ed_store_fe(o + 40, carry(a));
+    ed_store_fe(o + 48, mul2(a, b, b, a));
+    ed_store_fe(o + 56, fe_inv(a));
+    F25 r;
+    const bool sq = fe_sqrt_ratio(a, F25::one(), r);
+    ed_store_fe(o + 64, r);
+    ed_store_fe(o + 72, a);
+    const bool rt = fe_sqrt_ratio(a, b, r);
+    ed_store_fe(o + 80, r);
+    flags[i] = (sq ? 1u : 0u) | (rt ? 2u : 0u) | (fe_is_larger(a) ? 4u : 0u);
+}
+
+}  // namespace dr

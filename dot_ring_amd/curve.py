@@ -66,6 +66,18 @@ class SuiteParams:
         return self.suite_id + b"\x60"
 
 
+def _sqrt_5mod8(v: int, p: int) -> int:
+    """a square root mod p = 5 (mod 8) (Ed25519's field), host big-int code as the reference's curve.mod_sqrt"""
+    if v == 0:
+        return 0
+    r = pow(v, (p + 3) // 8, p)
+    if r * r % p != v:
+        r = r * pow(2, (p - 1) // 4, p) % p
+    if r * r % p != v:
+        raise ValueError("No square root exists")
+    return r
+
+
 class BandersnatchCurve:
     def __init__(self, params: SuiteParams):
         self.params = params
@@ -90,11 +102,15 @@ class BandersnatchCurve:
         return [int.from_bytes(raw[48 * i : 48 * i + 48], "big") % _P for i in range(count)]
 
     def mod_sqrt(self, val: int) -> int:
-        return _native.fr_sqrt(val % _P)        # raises ValueError("No square root exists")
+        p = self.params.field_modulus
+        if p == _P:
+            return _native.fr_sqrt(val % _P)    # raises ValueError("No square root exists")
+        return _sqrt_5mod8(val % p, p)
 
     def is_square(self, val: int) -> bool:
-        val %= _P
-        return val == 0 or pow(val, (_P - 1) // 2, _P) == 1
+        p = self.params.field_modulus
+        val %= p
+        return val == 0 or pow(val, (p - 1) // 2, p) == 1
 
     def valid_point(self, point: "BandersnatchPoint") -> bool:
         """Non-identity member of the prime-order subgroup (curve.py:56)."""
@@ -106,19 +122,21 @@ class BandersnatchPoint:
     (the class keeps its Bandersnatch name: that is what the reference's callers import)."""
     curve: BandersnatchCurve
     _A, _D, _N, _H, _CV = _A, _D, _N, 4, _native.CURVE_BANDERSNATCH
+    _P = _P                       # the suite's base field (Ed25519's differs)
     __slots__ = ("x", "y")
 
     def __init__(self, x: int, y: int):
         self.x, self.y = x, y
         if (x, y) != (0, 1):
-            if not (0 <= x < _P and 0 <= y < _P):
+            if not (0 <= x < self._P and 0 <= y < self._P):
                 raise ValueError("Invalid point coordinates")
             if not self._on_curve(x, y):
                 raise ValueError("Point is not on the curve")
 
     @classmethod
     def _on_curve(cls, x: int, y: int) -> bool:
-        return (cls._A * x * x + y * y) % _P == (1 + cls._D * x * x % _P * y * y) % _P
+        p = cls._P
+        return (cls._A * x * x + y * y) % p == (1 + cls._D * x * x % p * y * y) % p
 
     @classmethod
     def _trusted(cls, x: int, y: int):
@@ -163,21 +181,21 @@ class BandersnatchPoint:
         if self == other:
             return self.double()
         x1, y1, x2, y2 = self.x, self.y, other.x, other.y
-        a, d = self._A, self._D
-        t = d * x1 % _P * x2 % _P * y1 % _P * y2 % _P
-        return type(self)((x1 * y2 + x2 * y1) * pow(1 + t, -1, _P) % _P, (y1 * y2 - a * x1 * x2) * pow(1 - t, -1, _P) % _P)
+        a, d, p = self._A, self._D, self._P
+        t = d * x1 % p * x2 % p * y1 % p * y2 % p
+        return type(self)((x1 * y2 + x2 * y1) * pow(1 + t, -1, p) % p, (y1 * y2 - a * x1 * x2) * pow(1 - t, -1, p) % p)
 
     def double(self):
-        x1, y1, a = self.x, self.y, self._A
+        x1, y1, a, p = self.x, self.y, self._A, self._P
         if y1 == 0:
             return self.identity()
-        dx, dy = (a * x1 * x1 + y1 * y1) % _P, (2 - a * x1 * x1 - y1 * y1) % _P
+        dx, dy = (a * x1 * x1 + y1 * y1) % p, (2 - a * x1 * x1 - y1 * y1) % p
         if dx == 0 or dy == 0:
             return self.identity()
-        return type(self)(2 * x1 * y1 * pow(dx, -1, _P) % _P, (y1 * y1 - a * x1 * x1) * pow(dy, -1, _P) % _P)
+        return type(self)(2 * x1 * y1 * pow(dx, -1, p) % p, (y1 * y1 - a * x1 * x1) * pow(dy, -1, p) % p)
 
     def __neg__(self):
-        return type(self)(-self.x % _P, self.y)
+        return type(self)(-self.x % self._P, self.y)
 
     def __sub__(self, other):
         return self + (-other)
@@ -200,7 +218,7 @@ class BandersnatchPoint:
     # -- codec (point.py:150-214)
     def point_to_string(self) -> bytes:
         raw = bytearray(self.y.to_bytes(32, "little"))
-        if self.x > -self.x % _P:
+        if self.x > -self.x % self._P:
             raw[31] |= 0x80
         return bytes(raw)
 
@@ -211,17 +229,17 @@ class BandersnatchPoint:
         sign = (octet_string[-1] >> 7) & 1
         raw = bytearray(octet_string)
         raw[-1] &= 0x7F
-        y = int.from_bytes(raw, "little")
-        if y >= _P:
+        y, p = int.from_bytes(raw, "little"), cls._P
+        if y >= p:
             raise ValueError("Invalid point encoding")
-        den = (cls._A - cls._D * y * y) % _P
+        den = (cls._A - cls._D * y * y) % p
         if den == 0:
             raise ValueError("Invalid point encoding")
         try:
-            x = cls.curve.mod_sqrt((1 - y * y) * pow(den, -1, _P) % _P)
+            x = cls.curve.mod_sqrt((1 - y * y) * pow(den, -1, p) % p)
         except ValueError:
             raise ValueError("Invalid point encoding") from None
-        lo, hi = sorted((x, -x % _P))
+        lo, hi = sorted((x, -x % p))
         return cls(hi if sign else lo, y)
 
     # -- hash to curve (te_affine_point.py:212-295, te_curve.py:48-95)
@@ -519,7 +537,7 @@ def _suite(name: str, suite_id: bytes, xof: bool, bb, ab, pp, **curve_consts):
     curve = BandersnatchCurve(params)
     point_type = type(f"{name}Point", (BandersnatchPoint,), {
         "curve": curve, "__slots__": (), "_A": params.a, "_D": params.d, "_N": params.subgroup_order, "_H": params.cofactor,
-        "_CV": params.curve_id})
+        "_CV": params.curve_id, "_P": params.field_modulus})
     return CurveVariant(name, curve, point_type)
 
 
@@ -611,3 +629,23 @@ Bandersnatch_SW = CurveVariant(
     "Bandersnatch_SW", BandersnatchCurve(_SW_PARAMS),
     type("Bandersnatch_SWPoint", (BandersnatchSWPoint,), {"__slots__": ()}))
 Bandersnatch_SW.point_type.curve = Bandersnatch_SW.curve
+
+# dot_ring/curve/specs/ed25519.py, the Ed25519_TAI variant (the reference exports it as Ed25519): its own field 2^255 - 19, a = -1,
+# cofactor 8, try-and-increment with SHA-512; no accumulator base or padding point, so RingProofParams refuses it.  Every group
+# operation runs on the Ed25519 kernels (DR_CURVE_ED25519).
+Ed25519_TAI = _suite(
+    "Ed25519_TAI", b"Ed25519-SHA512-TAI-v1", False,
+    (45003173884697328536089278691112838614164406922820087464913813433380838325453,
+     31256014272390301975555524011230972931324093235775711248505761870355310252869),
+    None, None,
+    field_modulus=0x7FFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFED,
+    subgroup_order=2**252 + 0x14DEF9DEA2F79CD65812631A5CF5D3ED,
+    cofactor=8,
+    a=-1,
+    d=0x52036CEE2B6FFE738CC740797779E89800700A4D4141D8AB75EB4DCA135978A3,
+    generator=(0x216936D3CD6E53FEC0A4E231FDD6DC5C692CC7609525A7B2C9562D608F25D51A,
+               0x6666666666666666666666666666666666666666666666666666666666666658),
+    curve_id=_native.CURVE_ED25519,
+    e2c="tai",
+)
+Ed25519 = Ed25519_TAI

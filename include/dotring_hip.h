@@ -112,6 +112,15 @@ enum { DR_CURVE_BANDERSNATCH = 0, DR_CURVE_JUBJUB = 1, DR_CURVE_BANDERSNATCH_SW 
  * (try-and-increment, bandersnatch_sw.py + point.py:252-296), dr_ietf_prove_batch, dr_pedersen_prove_batch and dr_pedersen_verify_batch
  * (proofs 81 / 98 / 196 bytes; inside them points stay TE and are mapped to SW only to be encoded).  The ring prover, the Ring-VRF
  * calls and dr_ietf_verify_batch refuse it (DR_ERR_INVALID). */
+/* DR_CURVE_ED25519: Ed25519 (dot_ring/curve/specs/ed25519.py, the Ed25519_TAI variant: a = -1, cofactor 8, n = l, try-and-increment with
+ * SHA-512), over GF(2^255 - 19) — its own kernels (csrc/kernels_ed25519.hip.h, field csrc/fe25519.hip.h).  Raw points are x || y
+ * little-endian, coordinates below 2^255 - 19; encodings are 32 bytes, y with bit 255 = (x > p - x), the reference's sign rule (not
+ * RFC 8032's parity).  Scalars are reduced mod l on the device (sound for points of the prime-order subgroup).  Accepted by
+ * dr_te_scalar_mul_batch, dr_te_msm, dr_te_msm_groups, dr_te_decode_points (canonical y, a root, not the identity, no torsion
+ * component), dr_te_fixed_base_msm_groups (through the variable-base grouped kernel: no window table), dr_encode_to_curve_batch,
+ * dr_ietf_prove_batch, dr_pedersen_prove_batch and dr_pedersen_verify_batch (proofs 80 / 96 / 192 bytes).  Every call runs on the
+ * kernels (no host route).  The ring prover, the Ring-VRF calls, dr_ietf_verify_batch and the dr_bsn_* calls refuse it. */
+enum { DR_CURVE_ED25519 = 3 };
 DR_API int dr_te_scalar_mul_batch(dr_ctx *ctx, int curve, const uint8_t *pts_xy, const uint8_t *scalars, size_t n, uint8_t *out_xy);
 DR_API int dr_te_msm(dr_ctx *ctx, int curve, const uint8_t *pts_xy, const uint8_t *scalars, size_t n, uint8_t out_xy[64]);
 DR_API int dr_te_msm_groups(dr_ctx *ctx, int curve, const uint8_t *pts_xy, const uint8_t *scalars, size_t groups, size_t m, uint8_t *out_xy);
@@ -133,6 +142,17 @@ DR_API int dr_te_fixed_base_msm_groups(dr_ctx *ctx, int curve, const uint8_t *ba
  * (dot_ring/curve/native_field/scalar.pyx); the tests check this entry point against the same integers. */
 DR_API int dr_fr_ops_selftest(dr_ctx *ctx, const uint8_t *a /* n*32 */, const uint8_t *b /* n*32 */, size_t n, uint8_t *out /* n*384 */,
                               uint8_t *is_square /* n */);
+
+/* Ed25519 point decoding with the prime-order check (check = 1: as dr_te_decode_points for DR_CURVE_ED25519) or the codec alone
+ * (check = 0: y < p and a root; (0, 1) and (0, p - 1) decode whatever the sign bit, as the reference's constructor takes them).
+ * ok[i] = 1 when accepted; out_xy[i] is then x || y, otherwise 64 zero bytes. */
+DR_API int dr_ed25519_decode_points(dr_ctx *ctx, int check, const uint8_t *enc /* n*32 */, size_t n, uint8_t *out_xy /* n*64 */, uint8_t *ok /* n */);
+/* Diagnostic: the device's arithmetic in GF(2^255 - 19) (csrc/fe25519.hip.h) on RAW limb images — a and b are 9 signed 32-bit limbs
+ * each (value sum l[i] 2^(29 i)), so that every operation can be driven at the limb bounds of its contract.  out: n x 11 x 32 bytes
+ * of canonical little-endian results: a b, a^2, a + b, a - b, -a, carry(a), a b + b a (fused), a^-1 (0 for 0), sqrt(a) or 0, a,
+ * sqrt(a / b) or 0.  flags[i]: bit 0 a is a square, bit 1 a / b is a square, bit 2 a > p - a. */
+DR_API int dr_fe25519_ops_selftest(dr_ctx *ctx, const int32_t *a_limbs /* n*9 */, const int32_t *b_limbs /* n*9 */, size_t n,
+                                   uint8_t *out /* n*352 */, uint8_t *flags /* n */);
 
 /* square root in the Bandersnatch base field; DR_ERR_NOTSQUARE if none exists. Host-side, no ctx. */
 DR_API int dr_fr_sqrt(const uint8_t in[32], uint8_t out[32]);
@@ -323,8 +343,8 @@ typedef struct dr_vrf_suite {
     int xof;                        /* 1: SHAKE128 suite, 0: SHA-512 (counter-mode squeeze, expand_message_xmd) */
     uint8_t generator_xy[64];       /* group generator, x||y little-endian */
     uint8_t blinding_base_xy[64];   /* Pedersen blinding base (bandersnatch.py:89-102) */
-    int curve;                      /* DR_CURVE_BANDERSNATCH (Elligator 2 hash-to-curve), DR_CURVE_JUBJUB or DR_CURVE_BANDERSNATCH_SW
-                                       (try-and-increment; for the SW suite generator and blinding base are SW affine) */
+    int curve;                      /* DR_CURVE_BANDERSNATCH (Elligator 2 hash-to-curve), DR_CURVE_JUBJUB, DR_CURVE_BANDERSNATCH_SW or
+                                       DR_CURVE_ED25519 (try-and-increment; for the SW suite generator and blinding base are SW affine) */
 } dr_vrf_suite;
 
 /* hash_to_field(msg, 2) for `count` messages msgs[off[i]..off[i+1]): out = count * 2 field elements (32-byte LE),
