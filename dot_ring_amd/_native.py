@@ -108,6 +108,8 @@ _PROTOTYPES.update({
     "dr_te_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
     "dr_ed25519_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
     "dr_fe25519_ops_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p, c_void_p]),
+    "dr_p256_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
+    "dr_p256_field_ops_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p, c_void_p]),
     "dr_encode_to_curve_batch": (c_int, [c_void_p, POINTER(VrfSuiteStruct), c_char_p, POINTER(ctypes.c_uint64), c_char_p,
                                          POINTER(ctypes.c_uint64), c_size_t, c_char_p]),
     "dr_ring_prover_create_te": (c_int, [c_void_p, c_int, c_void_p, c_uint, c_uint, c_char_p, c_char_p, c_char_p, c_char_p, POINTER(c_void_p)]),
@@ -189,18 +191,36 @@ def _ragged(items):
     return b"".join(items), (ctypes.c_uint64 * len(off)).from_buffer(off)
 
 
-CURVE_BANDERSNATCH, CURVE_JUBJUB, CURVE_BANDERSNATCH_SW, CURVE_ED25519 = 0, 1, 2, 3
+CURVE_BANDERSNATCH, CURVE_JUBJUB, CURVE_BANDERSNATCH_SW, CURVE_ED25519, CURVE_P256 = 0, 1, 2, 3, 4
+# dr_vrf_suite.xof: the transcript hash of a suite
+XOF_SHA512, XOF_SHAKE128, XOF_SHA256 = 0, 1, 2
+_XOF_OF_HASH = {"sha512": XOF_SHA512, "shake_128": XOF_SHAKE128, "sha256": XOF_SHA256}
 
 
 def suite_point_len(suite: "VrfSuiteStruct") -> int:
-    """bytes of an encoded point of the suite: 33 for the short Weierstrass suite, 32 otherwise"""
-    return 33 if suite.curve == CURVE_BANDERSNATCH_SW else 32
+    """bytes of an encoded point of the suite: 33 for the short Weierstrass suites (Bandersnatch_SW, P-256), 32 otherwise"""
+    return 33 if suite.curve in (CURVE_BANDERSNATCH_SW, CURVE_P256) else 32
 
 
-def vrf_suite(suite_id: bytes, xof: bool, generator_xy: bytes, blinding_base_xy: bytes, curve: int = CURVE_BANDERSNATCH) -> VrfSuiteStruct:
+def xof_kind(xof) -> int:
+    """dr_vrf_suite.xof of a suite's hash: a hashlib constructor (sha512 -> 0, shake_128 -> 1, sha256 -> 2), the kind itself, or, as
+    before, a bool (True: SHAKE128, False: SHA-512)"""
+    if callable(xof):
+        name = xof().name
+        if name not in _XOF_OF_HASH:
+            raise ValueError(f"no native transcript for hash {name}")
+        return _XOF_OF_HASH[name]
+    if isinstance(xof, bool) or xof is None:
+        return XOF_SHAKE128 if xof else XOF_SHA512
+    if xof not in (XOF_SHA512, XOF_SHAKE128, XOF_SHA256):
+        raise ValueError(f"unknown transcript hash kind {xof}")
+    return int(xof)
+
+
+def vrf_suite(suite_id: bytes, xof, generator_xy: bytes, blinding_base_xy: bytes, curve: int = CURVE_BANDERSNATCH) -> VrfSuiteStruct:
     s = VrfSuiteStruct()
     s._keep = bytes(suite_id)
-    s.suite_id, s.suite_id_len, s.xof, s.curve = s._keep, len(s._keep), 1 if xof else 0, curve
+    s.suite_id, s.suite_id_len, s.xof, s.curve = s._keep, len(s._keep), xof_kind(xof), curve
     ctypes.memmove(s.generator_xy, generator_xy, 64)
     ctypes.memmove(s.blinding_base_xy, blinding_base_xy, 64)
     return s
@@ -221,7 +241,7 @@ def ring_verifier_key(log2n: int, omega_n: int, seed_xy: bytes, fixed_commitment
 
 
 def host_hash(kind: int, data: bytes, out_len: int) -> bytes:
-    """kind: 0 SHA-512, 1 SHAKE128, 2 SHAKE256 (the library's own implementations; checked against hashlib in tests)."""
+    """kind: 0 SHA-512, 1 SHAKE128, 2 SHAKE256, 4 SHA-256 (the library's own implementations; checked against hashlib in tests)."""
     out = ctypes.create_string_buffer(out_len)
     _check(lib().dr_host_hash(kind, data, len(data), out, out_len))
     return out.raw
@@ -540,6 +560,24 @@ class Context:
         _check(lib().dr_fe25519_ops_selftest(self.handle, a_limbs, b_limbs, n, out, flags))
         return out.raw[: 352 * n], flags.raw[:n]
 
+    def p256_field_ops_selftest(self, a_limbs: bytes, b_limbs: bytes):
+        """dr_p256_field_ops_selftest: (n x 12 x 32 result bytes, n flag bytes) for n pairs of raw 9-limb Montgomery images."""
+        n = len(a_limbs) // 36
+        if len(a_limbs) != 36 * n or len(b_limbs) != 36 * n:
+            raise ValueError("operands are 9 int32 limbs each")
+        out, flags = ctypes.create_string_buffer(max(1, 384 * n)), ctypes.create_string_buffer(max(1, n))
+        _check(lib().dr_p256_field_ops_selftest(self.handle, a_limbs, b_limbs, n, out, flags))
+        return out.raw[: 384 * n], flags.raw[:n]
+
+    def p256_decode_points(self, enc: bytes, check: bool = True):
+        """dr_p256_decode_points: (x||y bytes, flags) for len(enc)/33 encodings, with or without the identity check."""
+        if len(enc) % 33:
+            raise ValueError("compressed points are 33 bytes each")
+        count = len(enc) // 33
+        out, ok = ctypes.create_string_buffer(max(1, 64 * count)), ctypes.create_string_buffer(max(1, count))
+        _check(lib().dr_p256_decode_points(self.handle, 1 if check else 0, enc, count, out, ok))
+        return out.raw[: 64 * count], ok.raw[:count]
+
     def ed25519_decode_points(self, enc: bytes, check: bool = True):
         """dr_ed25519_decode_points: (x||y bytes, flags) for len(enc)/32 encodings, with or without the prime-order check."""
         if len(enc) % 32:
@@ -669,7 +707,7 @@ class Context:
     def bsn_decode_points(self, enc: bytes, curve: int = CURVE_BANDERSNATCH):
         """dec_point for len(enc)/32 compressed points on the GPU (33 bytes each, SW affine out, for CURVE_BANDERSNATCH_SW)
         -> (affine x||y bytes, validity flags)."""
-        width = 33 if curve == CURVE_BANDERSNATCH_SW else 32
+        width = 33 if curve in (CURVE_BANDERSNATCH_SW, CURVE_P256) else 32
         if len(enc) % width:
             raise ValueError(f"compressed points are {width} bytes each")
         count = len(enc) // width

@@ -4,6 +4,7 @@
 #include "hostsmall.hpp"
 #include "kernels_sw.hip.h"
 #include "kernels_ed25519.hip.h"
+#include "kernels_p256.hip.h"
 
 namespace dri {
 
@@ -369,7 +370,8 @@ int dr_prof_get(dr_ctx* ctx, const char* name, double* total_ms, int* launches) 
 // ------------------------------------------------------------------------------- seam A
 int te_scalar_mul_batch_dev(dr_ctx* ctx, int cv, const void* d_pts, const void* d_scalars, size_t n, void* d_out) {
     TRY(use_ctx(ctx));
-    if (cv == dr::CV_ED25519) return fail(DR_ERR_INVALID, "device-resident scalar multiplication serves the curves over the BLS12-381 scalar field");
+    if (cv == dr::CV_ED25519 || cv == dr::CV_P256)
+        return fail(DR_ERR_INVALID, "device-resident scalar multiplication serves the curves over the BLS12-381 scalar field");
     if (n == 0) return DR_OK;
     if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
     // 4-bit windows (64 KiB of LDS per wave, 2 waves per CU) while the launch is latency-bound; 2-bit windows
@@ -604,10 +606,130 @@ int ed_decode_points(dr_ctx* ctx, int mode, const uint8_t* enc, size_t n, uint8_
 }
 }  // namespace
 
+// ---- P-256 (kernels_p256.hip.h).  As for Ed25519: every call runs on the kernels, no host route, and secrets pass through io_a /
+// io_b / io_c only, which ctx_wipe_scratch covers.  Points are affine x || y; 64 zero bytes are the identity.
+namespace {
+int check_p256_elems(const uint8_t* p, size_t count, const char* what) {
+    for (size_t i = 0; i < count; i++) {
+        uint64_t v[4];
+        drh::load_le32(p + 32 * i, v);
+        if (drh::Mod256::geq(v, drh::mod_p256().m)) return fail(DR_ERR_INVALID, std::string(what) + " coordinate is not a canonical field element");
+    }
+    return DR_OK;
+}
+int p256_scalar_mul_batch(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy) {
+    if (n == 0) return DR_OK;
+    if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
+    if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
+    TRY(check_p256_elems(pts_xy, 2 * n, "point"));
+    TRY(ctx->io_a.reserve(n * 64));
+    TRY(ctx->io_b.reserve(n * 32));
+    TRY(ctx->io_c.reserve(n * 64));
+    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, pts_xy, n * 64, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->io_b.p, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    TRY(launch(ctx, "k_p256_scalar_mul", [&] {
+        hipLaunchKernelGGL(dr::k_p256_scalar_mul, dim3(div_up(n, dr::P256_BLOCK)), dim3(dr::P256_BLOCK), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
+                           ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
+    }));
+    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_c.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->prof) TRY(prof_collect(ctx));
+    return DR_OK;
+}
+int p256_msm_groups(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy) {
+    if (groups == 0) return DR_OK;
+    if (m == 0 || m > 64) return fail(DR_ERR_INVALID, "group size must be in 1..64");
+    if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
+    const size_t n = groups * m;
+    if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
+    TRY(check_p256_elems(pts_xy, 2 * n, "point"));
+    uint32_t mpad = 1;
+    while (mpad < m) mpad <<= 1;
+    TRY(ctx->io_a.reserve(n * 64));
+    TRY(ctx->io_b.reserve(n * 32));
+    TRY(ctx->io_c.reserve(groups * 64));
+    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, pts_xy, n * 64, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->io_b.p, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    const uint32_t per_block = dr::P256_BLOCK / mpad;
+    TRY(launch(ctx, "k_p256_msm_groups", [&] {
+        hipLaunchKernelGGL(dr::k_p256_msm_groups, dim3(div_up(groups, per_block)), dim3(dr::P256_BLOCK), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
+                           ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)groups, (uint32_t)m, mpad);
+    }));
+    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_c.p, groups * 64, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->prof) TRY(prof_collect(ctx));
+    return DR_OK;
+}
+// fixed bases through the variable-base grouped kernel, as for Ed25519 (no window table)
+int p256_fixed_base_groups(dr_ctx* ctx, const uint8_t* bases_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy) {
+    if (groups == 0) return DR_OK;
+    if (m == 0 || m > 4) return fail(DR_ERR_INVALID, "1..4 fixed bases per group");
+    if (!bases_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
+    if (groups * m >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
+    std::vector<uint8_t> pts(groups * m * 64);
+    for (size_t g = 0; g < groups; g++) std::memcpy(pts.data() + 64 * m * g, bases_xy, 64 * m);
+    return p256_msm_groups(ctx, pts.data(), scalars, groups, m, out_xy);
+}
+// one MSM: groups of 64 terms in one launch, then the partial sums with scalar 1, 64 at a time, until one is left (padding: 0 * O)
+int p256_msm(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t out_xy[64]) {
+    if (n == 0) {
+        std::memset(out_xy, 0, 64);
+        return DR_OK;
+    }
+    if (!pts_xy || !scalars) return fail(DR_ERR_INVALID, "null buffer");
+    std::vector<uint8_t> pts(pts_xy, pts_xy + n * 64), sc(scalars, scalars + n * 32), part;
+    for (;;) {
+        if (n <= 64) return p256_msm_groups(ctx, pts.data(), sc.data(), 1, n, out_xy);
+        const size_t parts = (n + 63) / 64;
+        pts.resize(parts * 64 * 64, 0);
+        sc.resize(parts * 64 * 32, 0);
+        part.resize(parts * 64);
+        TRY(p256_msm_groups(ctx, pts.data(), sc.data(), parts, 64, part.data()));
+        explicit_bzero(sc.data(), sc.size());
+        pts.swap(part);
+        n = parts;
+        sc.assign(n * 32, 0);
+        for (size_t i = 0; i < n; i++) sc[32 * i] = 1;
+    }
+}
+// n x 33-byte encodings, padded to 36 bytes for the kernel
+int p256_decode_points(dr_ctx* ctx, int mode, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
+    if (n == 0) return DR_OK;
+    if (!enc || !out_xy || !ok) return fail(DR_ERR_INVALID, "null buffer");
+    if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
+    std::vector<uint8_t> rec(n * 36, 0);
+    for (size_t i = 0; i < n; i++) std::memcpy(rec.data() + 36 * i, enc + 33 * i, 33);
+    TRY(ctx->io_a.reserve(n * 36));
+    TRY(ctx->io_b.reserve(n * 64));
+    TRY(ctx->io_c.reserve(n * 4));
+    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, rec.data(), n * 36, hipMemcpyHostToDevice, ctx->stream));
+    TRY(launch(ctx, "k_p256_decode_points", [&] {
+        const dim3 grid(div_up(n, dr::P256_BLOCK)), block(dr::P256_BLOCK);
+        if (mode == dr::P256_DEC_TAI)
+            hipLaunchKernelGGL(dr::k_p256_decode_points<dr::P256_DEC_TAI>, grid, block, 0, ctx->stream, ctx->io_a.as<uint32_t>(),
+                               ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
+        else if (mode == dr::P256_DEC_CHECK)
+            hipLaunchKernelGGL(dr::k_p256_decode_points<dr::P256_DEC_CHECK>, grid, block, 0, ctx->stream, ctx->io_a.as<uint32_t>(),
+                               ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
+        else
+            hipLaunchKernelGGL(dr::k_p256_decode_points<dr::P256_DEC_CODEC>, grid, block, 0, ctx->stream, ctx->io_a.as<uint32_t>(),
+                               ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
+    }));
+    std::vector<uint32_t> flags(n);
+    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_b.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(flags.data(), ctx->io_c.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->prof) TRY(prof_collect(ctx));
+    for (size_t i = 0; i < n; i++) ok[i] = flags[i] ? 1 : 0;
+    return DR_OK;
+}
+}  // namespace
+
 int te_scalar_mul_batch(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy) {
     TRY(use_ctx(ctx));
     TRY(check_curve(cv));
     if (cv == dr::CV_ED25519) return ed_scalar_mul_batch(ctx, pts_xy, scalars, n, out_xy);
+    if (cv == dr::CV_P256) return p256_scalar_mul_batch(ctx, pts_xy, scalars, n, out_xy);
     if (n == 0) return DR_OK;
     if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
     TRY(check_fr_elems(pts_xy, 2 * n, "point"));
@@ -671,6 +793,7 @@ int te_msm_groups(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* sca
     TRY(use_ctx(ctx));
     TRY(check_curve(cv));
     if (cv == dr::CV_ED25519) return ed_msm_groups(ctx, pts_xy, scalars, groups, m, out_xy);
+    if (cv == dr::CV_P256) return p256_msm_groups(ctx, pts_xy, scalars, groups, m, out_xy);
     if (groups == 0) return DR_OK;
     if (m == 0 || m > 64) return fail(DR_ERR_INVALID, "group size must be in 1..64");
     if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
@@ -746,6 +869,7 @@ int te_fixed_base_groups(dr_ctx* ctx, int cv, const uint8_t* bases_xy, const uin
     TRY(use_ctx(ctx));
     TRY(check_curve(cv));
     if (cv == dr::CV_ED25519) return ed_fixed_base_groups(ctx, bases_xy, scalars, groups, m, out_xy);
+    if (cv == dr::CV_P256) return p256_fixed_base_groups(ctx, bases_xy, scalars, groups, m, out_xy);
     if (groups == 0) return DR_OK;
     if (m == 0 || m > 4) return fail(DR_ERR_INVALID, "1..4 fixed bases per group");
     if (!bases_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
@@ -822,6 +946,7 @@ int te_msm(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* scalars, s
     TRY(check_curve(cv));
     if (!out_xy) return fail(DR_ERR_INVALID, "null buffer");
     if (cv == dr::CV_ED25519) return ed_msm(ctx, pts_xy, scalars, n, out_xy);
+    if (cv == dr::CV_P256) return p256_msm(ctx, pts_xy, scalars, n, out_xy);
     if (n == 0) {
         std::memset(out_xy, 0, 64);
         out_xy[32] = 1;
@@ -958,6 +1083,7 @@ int te_decode_points(dr_ctx* ctx, int cv, bool tai, const uint8_t* enc, size_t n
     TRY(use_ctx(ctx));
     TRY(check_curve(cv));
     if (cv == dr::CV_ED25519) return ed_decode_points(ctx, tai ? dr::ED_DEC_TAI : dr::ED_DEC_CHECK, enc, n, out_xy, ok);
+    if (cv == dr::CV_P256) return p256_decode_points(ctx, tai ? dr::P256_DEC_TAI : dr::P256_DEC_CHECK, enc, n, out_xy, ok);
     if (n == 0) return DR_OK;
     if (!enc || !out_xy || !ok) return fail(DR_ERR_INVALID, "null buffer");
     if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
@@ -996,6 +1122,32 @@ int dr_te_decode_points(dr_ctx* ctx, int curve, const uint8_t* enc, size_t n, ui
 int dr_ed25519_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
     TRY(use_ctx(ctx));
     return ed_decode_points(ctx, check ? dr::ED_DEC_CHECK : dr::ED_DEC_CODEC, enc, n, out_xy, ok);
+}
+
+int dr_p256_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
+    TRY(use_ctx(ctx));
+    return p256_decode_points(ctx, check ? dr::P256_DEC_CHECK : dr::P256_DEC_CODEC, enc, n, out_xy, ok);
+}
+int dr_p256_field_ops_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
+    TRY(use_ctx(ctx));
+    if (n == 0) return DR_OK;
+    if (!a_limbs || !b_limbs || !out || !flags) return fail(DR_ERR_INVALID, "null buffer");
+    if (n >= (1ull << 24)) return fail(DR_ERR_INVALID, "batch too large");
+    const size_t rec = (size_t)dr::P256_SELFTEST_RECORDS * 32;
+    TRY(ctx->io_a.reserve(n * 72));
+    TRY(ctx->io_b.reserve(n * rec));
+    TRY(ctx->io_c.reserve(n * 4));
+    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, a_limbs, n * 36, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->io_a.as<uint8_t>() + n * 36, b_limbs, n * 36, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(dr::k_p256_field_selftest, dim3(div_up(n, 64)), dim3(64), 0, ctx->stream, ctx->io_a.as<int32_t>(),
+                       (const int32_t*)(ctx->io_a.as<uint8_t>() + n * 36), (uint32_t)n, ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> fl(n);
+    HIP_TRY(hipMemcpyAsync(out, ctx->io_b.p, n * rec, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(fl.data(), ctx->io_c.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < n; i++) flags[i] = (uint8_t)fl[i];
+    return DR_OK;
 }
 
 int dr_fe25519_ops_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
@@ -1084,6 +1236,10 @@ int dr_host_hash(int kind, const uint8_t* data, size_t len, uint8_t* out, size_t
             drh::Sha512::hash(data, len, out);
             return DR_OK;
         case DR_HASH_SHAKE128: { drh::Shake128 s; s.update(data, len); s.digest(out, out_len); return DR_OK; }
+        case DR_HASH_SHA256:
+            if (out_len != 32) return fail(DR_ERR_INVALID, "SHA-256 digests are 32 bytes");
+            drh::Sha256::hash(data, len, out);
+            return DR_OK;
         case DR_HASH_SHAKE256: { drh::Shake256 s; s.update(data, len); s.digest(out, out_len); return DR_OK; }
         case DR_HASH_SHAKE128_X4: {
             if (len % 4 || out_len % 4 || out_len / 4 > 168) return fail(DR_ERR_INVALID, "four equal messages, four digests of at most 168 bytes");
@@ -1134,12 +1290,17 @@ int dr_ringvrf_aux_take_blindings(uint8_t* aux, size_t batch, uint8_t* out_blind
 int load_suite(const dr_vrf_suite* s, drh::VrfSuite& out, bool allow_sw) {
     if (!s || !s->suite_id || s->suite_id_len == 0 || s->suite_id_len > 200) return fail(DR_ERR_INVALID, "bad VRF suite");
     out.suite_id.assign(s->suite_id, s->suite_id + s->suite_id_len);
-    out.xof = s->xof != 0;
+    if (s->xof < 0 || s->xof > 2) return fail(DR_ERR_INVALID, "unknown transcript hash in VRF suite (xof: 0 SHA-512, 1 SHAKE128, 2 SHA-256)");
+    out.xof = s->xof;
     std::memcpy(out.generator, s->generator_xy, 64);
     std::memcpy(out.blinding_base, s->blinding_base_xy, 64);
     out.cv = drh::te_curve(s->curve);
     if (!out.cv) return fail(DR_ERR_INVALID, "unknown curve id in VRF suite");
     if (out.cv->ed25519 && !allow_sw) return fail(DR_ERR_INVALID, "this entry point does not serve the Ed25519 suite");
+    if (out.cv->p256) {
+        if (!allow_sw) return fail(DR_ERR_INVALID, "this entry point does not serve the P-256 suite");
+        out.point_len = 33;
+    }
     if (out.cv->sw) {
         if (!allow_sw) return fail(DR_ERR_INVALID, "this entry point does not serve the short Weierstrass suite");
         // the kernels take the suite's constants as their TE images; the SW generator stays for its encoding
@@ -1176,14 +1337,18 @@ int encode_to_curve_msgs(dr_ctx* ctx, const drh::VrfSuite& su, size_t B, const u
     std::vector<size_t> pending(B);
     for (size_t i = 0; i < B; i++) pending[i] = i;
     std::vector<uint8_t> cand, xy, ok;
+    // P-256 (point.py:275-283 for a short Weierstrass curve with a 256-bit field): the candidate is the 32 squeezed bytes, nothing
+    // shaved, and the flag byte 0x80 appended — 33 bytes, decoded with the codec's rules and its SEC1 fallback
+    const size_t cl = su.cv->p256 ? 33 : 32;
     for (unsigned base = 0; !pending.empty();) {
         if (base >= 256) return fail(DR_ERR_INVALID, "hash_to_curve_tai failed");
         const unsigned K = std::min<unsigned>(base == 0 ? 4 : 8, 256 - base);
         const size_t n = pending.size() * K;
-        cand.resize(n * 32); xy.resize(n * 64); ok.resize(n);
+        cand.resize(n * cl); xy.resize(n * 64); ok.resize(n);
         drh::parallel_for(n, [&](size_t j) {
             const drh::Bytes& m = msgs[pending[j / K]];
-            drh::tai_candidate(su, m.data(), m.size(), base + (unsigned)(j % K), cand.data() + 32 * j);
+            drh::tai_candidate(su, m.data(), m.size(), base + (unsigned)(j % K), cand.data() + cl * j);
+            if (cl == 33) cand[cl * j + 32] = 0x80;
         });
         TRY(te_decode_points(ctx, su.cv->id, true, cand.data(), n, xy.data(), ok.data()));
         std::vector<size_t> still;
@@ -1202,6 +1367,7 @@ int encode_to_curve_msgs(dr_ctx* ctx, const drh::VrfSuite& su, size_t B, const u
 int dr_hash_to_field_batch(const dr_vrf_suite* suite, const uint8_t* msgs, const uint64_t* off, size_t count, uint8_t* out_u_pairs) {
     drh::VrfSuite su;
     TRY(load_suite(suite, su, true));
+    if (su.cv->p256) return fail(DR_ERR_INVALID, "the P-256 suite hashes to the curve by try-and-increment: no hash_to_field");
     if (count && (!off || !out_u_pairs || (off[count] && !msgs))) return fail(DR_ERR_INVALID, "null buffer");
     for (size_t i = 0; i < count; i++)
         if (off[i + 1] < off[i]) return fail(DR_ERR_INVALID, "offsets must be non-decreasing");

@@ -319,13 +319,18 @@ struct TeCurveHost {
     bool tai;                 // hash-to-curve by try-and-increment (otherwise Elligator 2)
     bool sw = false;          // points cross the ABI as short Weierstrass affine x || y (33-byte encodings); TE inside
     bool ed25519 = false;     // over GF(2^255 - 19), not the BLS12-381 scalar field: the kernels of kernels_ed25519.hip.h, no host route
+    bool p256 = false;        // P-256: short Weierstrass over its own field, the kernels of kernels_p256.hip.h, 33-byte encodings, no host route
 };
 inline const Mod256& mod_p25519() {   // Ed25519 base field (specs/ed25519.py)
     static Mod256 s = [] { Mod256 t; const uint64_t p[4] = {0xffffffffffffffedULL, 0xffffffffffffffffULL, 0xffffffffffffffffULL, 0x7fffffffffffffffULL}; t.init(p); return t; }();
     return s;
 }
+inline const Mod256& mod_p256() {      // P-256 base field (specs/p256.py)
+    static Mod256 s = [] { Mod256 t; const uint64_t p[4] = {0xffffffffffffffffULL, 0x00000000ffffffffULL, 0x0000000000000000ULL, 0xffffffff00000001ULL}; t.init(p); return t; }();
+    return s;
+}
 inline const TeCurveHost* te_curve(int id) {
-    static const TeCurveHost curves[4] = {
+    static const TeCurveHost curves[5] = {
         [] { TeCurveHost c{}; c.id = 0; c.n = mod_n();
              const uint64_t d[4] = {0xb369f2f5188d58e7ULL, 0xcb66677177e54f92ULL, 0xc66e3bf86be3b6d8ULL, 0x6389c12633c267cbULL};
              std::memcpy(c.d, d, 32); c.neg_a[0] = 5; c.scalar_bits = 253; c.glv = true; c.tai = false; return c; }(),
@@ -343,11 +348,17 @@ inline const TeCurveHost* te_curve(int id) {
              c.n.init(n);
              const uint64_t d[4] = {0x75eb4dca135978a3ULL, 0x00700a4d4141d8abULL, 0x8cc740797779e898ULL, 0x52036cee2b6ffe73ULL};
              std::memcpy(c.d, d, 32); c.neg_a[0] = 1; c.scalar_bits = 253; c.glv = false; c.tai = true; c.ed25519 = true; return c; }(),
+        // P-256 (specs/p256.py, the P256_TAI variant): y^2 = x^3 - 3 x + b, cofactor 1, n of 256 bits (its top bit set); d and neg_a
+        // do not apply (no twisted Edwards model)
+        [] { TeCurveHost c{}; c.id = 4;
+             const uint64_t n[4] = {0xf3b9cac2fc632551ULL, 0xbce6faada7179e84ULL, 0xffffffffffffffffULL, 0xffffffff00000000ULL};
+             c.n.init(n);
+             c.scalar_bits = 256; c.glv = false; c.tai = true; c.p256 = true; return c; }(),
     };
-    return id >= 0 && id <= 3 ? &curves[id] : nullptr;
+    return id >= 0 && id <= 4 ? &curves[id] : nullptr;
 }
 // the base field of a curve of the table
-inline const Mod256& te_field(const TeCurveHost& c) { return c.ed25519 ? mod_p25519() : mod_p(); }
+inline const Mod256& te_field(const TeCurveHost& c) { return c.ed25519 ? mod_p25519() : c.p256 ? mod_p256() : mod_p(); }
 
 // ---------------------------------------------------------------- GLV decomposition (dot_ring/curve/glv.py:57-160)
 // k = k1 + k2*lambda (mod n) with |k1|, |k2| < 2^128, from the lattice basis v1 = (a1, b1), v2 = (a2, -a1) the reference
@@ -420,16 +431,17 @@ inline void enc_te_point(const uint8_t xy[64], uint8_t out[32], const Mod256& fi
     if (gt) out[31] |= 0x80;
 }
 
-// compressed short Weierstrass point of the SW suite (specs/bandersnatch_sw.py point_to_string): x little-endian, then a flag byte,
-// 0x80 iff y is the larger of (y, p - y); the identity (64 zero bytes) is 32 zero bytes and 0x40
-inline void enc_sw_point(const uint8_t xy[64], uint8_t out[33]) {
+// compressed short Weierstrass point of the SW suite (specs/bandersnatch_sw.py point_to_string) and of P-256 (specs/p256.py, over
+// its own field): x little-endian, then a flag byte, 0x80 iff y is the larger of (y, p - y); the identity (64 zero bytes) is 32 zero
+// bytes and 0x40
+inline void enc_sw_point(const uint8_t xy[64], uint8_t out[33], const Mod256& field = mod_p()) {
     uint64_t y[4], ny[4], zero[4] = {0, 0, 0, 0};
     std::memcpy(out, xy, 32);
     load_le32(xy + 32, y);
     bool idn = true;
     for (int i = 0; i < 64; i++) idn = idn && xy[i] == 0;
     if (idn) { out[32] = 0x40; return; }
-    mod_p().sub(zero, y, ny);
+    field.sub(zero, y, ny);
     bool gt = false;
     for (int i = 3; i >= 0; i--) { if (y[i] != ny[i]) { gt = y[i] > ny[i]; break; } }
     out[32] = gt ? 0x80 : 0x00;
@@ -511,23 +523,34 @@ inline void batch_inv(const Mod256& f, uint64_t (*vals)[4], size_t n) {
 // ---------------------------------------------------------------- VRF transcript (primitives.py:26-55)
 struct VrfSuite {
     Bytes suite_id;
-    bool xof;                 // SHAKE128 suite; otherwise SHA-512 counter mode
+    int xof;                  // the transcript hash (dr_vrf_suite.xof): 0 SHA-512 or 2 SHA-256 in counter mode, 1 SHAKE128
     uint8_t generator[64], blinding_base[64];     // TE affine (the kernels' coordinates; the SW suite's are mapped on loading)
     const TeCurveHost* cv = te_curve(0);
-    size_t point_len = 32;                        // bytes of an encoded point: 32 (TE), 33 (SW)
+    size_t point_len = 32;                        // bytes of an encoded point: 32 (TE), 33 (SW, P-256)
     uint8_t generator_sw[64] = {0};               // SW suite: the generator as given (its encoding enters the Tiny / Thin transcripts)
 };
 // the suite's point encoding of xy given in the suite's own coordinates (TE, or SW for the SW suite)
 inline void enc_point(const VrfSuite& su, const uint8_t xy[64], uint8_t* out) {
     if (su.cv->sw) enc_sw_point(xy, out);
+    else if (su.cv->p256) enc_sw_point(xy, out, mod_p256());
     else enc_te_point(xy, out, te_field(*su.cv));
 }
-// squeeze `size` bytes of the stream defined by everything absorbed
-inline void vrf_squeeze(bool xof, const uint8_t* absorbed, size_t len, uint8_t* out, size_t size) {
-    if (xof) {
+// squeeze `size` bytes of the stream defined by everything absorbed (xof: VrfSuite::xof)
+inline void vrf_squeeze(int xof, const uint8_t* absorbed, size_t len, uint8_t* out, size_t size) {
+    if (xof == 1) {
         Shake128 s;
         s.update(absorbed, len);
         s.digest(out, size);
+        return;
+    }
+    if (xof == 2) {                                  // SHA-256: H(seed || LE64(ctr)), 32 bytes a block
+        uint8_t seed[40], blk[32];
+        Sha256::hash(absorbed, len, seed);
+        for (size_t off = 0, ctr = 0; off < size; off += 32, ctr++) {
+            for (int i = 0; i < 8; i++) seed[32 + i] = (uint8_t)((uint64_t)ctr >> (8 * i));
+            Sha256::hash(seed, 40, blk);
+            std::memcpy(out + off, blk, std::min<size_t>(32, size - off));
+        }
         return;
     }
     uint8_t seed[72], blk[64];
@@ -549,8 +572,8 @@ inline bool vrf_nonce(const VrfSuite& su, const Bytes& transcript, const uint64_
     t = transcript;
     put8(t, 0x11);                                   // NONCE
     put(t, exp, 64);
-    vrf_squeeze(su.xof, t.data(), t.size(), raw, 48);   // ceil((scalar_bits + 128) / 8) = 48 for 253 and for 252 bits
-    su.cv->n.reduce_bytes(raw, 48, false, out);
+    vrf_squeeze(su.xof, t.data(), t.size(), raw, 48);   // ceil((scalar_bits + 128) / 8) = 48 for 252, 253 and 256 bits
+    su.cv->n.reduce_bytes(raw, 48, false, out);         // (Mod256 takes any odd modulus below 2^256, P-256's n with its top bit set too)
     return !su.cv->n.is_zero(out);
 }
 // primitives.py:82-88: 128-bit challenge over the given compressed points
@@ -581,7 +604,7 @@ inline void hash_to_field2(const VrfSuite& su, const uint8_t* msg, size_t len, u
     put8(dst, (uint8_t)dst.size());                  // DST_prime = DST || len(DST)
     const size_t L = 96;
     uint8_t raw[128];
-    if (su.xof) {
+    if (su.xof == 1) {
         Shake128 s;
         s.update(msg, len);
         const uint8_t lb[2] = {0, (uint8_t)L};

@@ -1,0 +1,358 @@
+// P-256 kernels (DR_CURVE_P256; the reference's specs/p256.py, P256_TAI): the short Weierstrass group law with a = -3 over
+// GF(p256) (fp256.hip.h) and the kernels that fill, for this curve, the roles kernels_ed25519.hip.h fills for Ed25519: variable-base
+// scalar multiplication on a fixed schedule, grouped MSMs, point decoding (with the reference's SEC1 fallback) and the device half
+// of try-and-increment.  The existing kernels stay as they are; no other curve includes this header's field.
+//
+// Points cross the ABI as affine x || y little-endian, standard form; 64 zero bytes are the identity ((0, 0) is not on the curve).
+// Inside: homogeneous projective (X : Y : Z), x = X / Z, y = Y / Z, identity (0 : 1 : 0), coordinates in Montgomery form.  The
+// group law is the complete one of Renes, Costello and Batina (2016), algorithms 4 (addition) and 6 (doubling) for a = -3: no
+// exceptional cases (P + P, P + (-P), the identity on either side) and no branches.  The comments give the limb class of every
+// intermediate against fp256.hip.h's contract: n = normal, r = reduced, sK = a sum or difference of K such.
+#pragma once
+#include "fp256.hip.h"
+
+namespace dr {
+
+constexpr int P256_BLOCK = 64;        // one wave per workgroup, as k_ed_scalar_mul
+constexpr int P256_TABLE = 8;         // entries 1P..8P
+constexpr int P256_PT_WORDS = 27;     // X, Y, Z x 9 limbs (the table holds limb images: no packing)
+constexpr int P256_WINDOWS = 65;      // 64 signed 4-bit digits of k < n < 2^256 and the carry out of the top one
+
+struct P256Point {
+    F256 x, y, z;
+};
+
+DR_DEV P256Point p256_identity() {
+    P256Point p;
+    p.x = F256::zero(); p.y = fp_one(); p.z = F256::zero();
+    return p;
+}
+
+// algorithm 6, a = -3 (8M + 3S + 2 products by b, here 7 products, 3 squarings and one fused pair); coordinates n or r in, n out
+DR_DEV P256Point p256_dbl(const P256Point& p) {
+    const F256 b = F256::constant<Fp256Consts::B>();
+    const F256 t0 = sqr(p.x), t1 = sqr(p.y), t2 = sqr(p.z);                    // n
+    const F256 xy = mul(p.x, p.y), xz = mul(p.x, p.z), yz = mul(p.y, p.z);     // n
+    const F256 xz2 = dbl(xz);                                                    // s2
+    F256 y3 = fp_reduce(sub(mul(b, t2), xz2));                                   // b Z^2 - 2 X Z: r
+    y3 = fp_reduce(add(y3, dbl(y3)));                                            // 3 (...): r
+    const F256 xa = fp_reduce(sub(t1, y3)), ya = fp_reduce(add(t1, y3));          // Y^2 -+ y3: r
+    const F256 t2b = add(t2, dbl(t2));                                           // 3 Z^2: s3
+    F256 z3 = fp_reduce(sub(mul(b, xz2), t2b));                                  // 2 b X Z - 3 Z^2: r
+    z3 = fp_reduce(sub(z3, t0));                                                 // r
+    z3 = fp_reduce(add(z3, dbl(z3)));                                            // 3 (...): r
+    const F256 t0b = fp_reduce(sub(add(t0, dbl(t0)), t2b));                      // 3 X^2 - 3 Z^2: r
+    P256Point r;
+    r.x = carry(dbl(mul2(xy, xa, neg(yz), z3)));                                 // 2 X Y xa - 2 Y Z z3: n
+    r.y = mul2(xa, ya, t0b, z3);                                                 // xa ya + t0b z3: n
+    r.z = mul(carry(dbl(carry(dbl(yz)))), dbl(t1));                              // 4 Y Z x 2 Y^2 = 8 Y^3 Z: n
+    return r;
+}
+
+// algorithm 4, a = -3 (12M + 2 products by b; here 8 products and 3 fused pairs); coordinates n or r in, n out
+DR_DEV P256Point p256_add(const P256Point& p, const P256Point& q) {
+    const F256 b = F256::constant<Fp256Consts::B>();
+    const F256 t0 = mul(p.x, q.x), t1 = mul(p.y, q.y), t2 = mul(p.z, q.z);      // n
+    const F256 t3 = fp_reduce(sub(mul(fp_reduce(add(p.x, p.y)), add(q.x, q.y)), add(t0, t1)));   // X1 Y2 + X2 Y1: r
+    const F256 t4 = fp_reduce(sub(mul(fp_reduce(add(p.y, p.z)), add(q.y, q.z)), add(t1, t2)));   // Y1 Z2 + Y2 Z1: r
+    const F256 u = sub(mul(fp_reduce(add(p.x, p.z)), add(q.x, q.z)), add(t0, t2));              // X1 Z2 + X2 Z1: s3
+    const F256 x3a = fp_reduce(sub(u, mul(b, t2)));                              // u - b t2: r
+    const F256 x3b = fp_reduce(add(x3a, dbl(x3a)));                              // 3 (...): r
+    const F256 z3 = fp_reduce(sub(t1, x3b)), x3 = fp_reduce(add(t1, x3b));       // r
+    const F256 t2b = add(t2, dbl(t2));                                           // 3 t2: s3
+    F256 y3 = fp_reduce(sub(mul(b, u), t2b));                                    // b u - 3 t2: r
+    y3 = fp_reduce(sub(y3, t0));                                                 // r
+    y3 = fp_reduce(add(y3, dbl(y3)));                                            // 3 (...): r
+    const F256 t0b = fp_reduce(sub(add(t0, dbl(t0)), t2b));                      // 3 t0 - 3 t2: r
+    P256Point r;
+    r.x = mul2(x3, t3, neg(t4), y3);                                             // n
+    r.y = mul2(x3, z3, t0b, y3);                                                 // n
+    r.z = mul2(t4, z3, t3, t0b);                                                 // n
+    return r;
+}
+
+DR_DEV P256Point p256_cneg(const P256Point& p, bool negate) {
+    P256Point r = p;
+    r.y = cneg(p.y, negate);
+    return r;
+}
+
+// ---------------------------------------------------------------- memory
+DR_DEV void p256_load8(const uint32_t* p, uint32_t (&w)[8]) {
+    const uint4* q = reinterpret_cast<const uint4*>(p);
+    const uint4 a = q[0], b = q[1];
+    w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
+    w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
+}
+DR_DEV void p256_store8(uint32_t* p, const uint32_t (&w)[8]) {
+    uint4* q = reinterpret_cast<uint4*>(p);
+    q[0] = make_uint4(w[0], w[1], w[2], w[3]);
+    q[1] = make_uint4(w[4], w[5], w[6], w[7]);
+}
+// affine x || y (16 words, canonical) -> projective; 64 zero bytes -> the identity
+DR_DEV P256Point p256_load_affine(const uint32_t* p) {
+    uint32_t x[8], y[8];
+    p256_load8(p, x);
+    p256_load8(p + 8, y);
+    uint32_t o = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) o |= x[j] | y[j];
+    P256Point r;
+    r.x = fp_unpack(x);
+    r.y = fp_unpack(y);
+    r.z = fp_one();
+    if (o == 0) r = p256_identity();
+    return r;
+}
+DR_DEV void p256_store_fe(uint32_t* p, const F256& a) {
+    uint32_t w[8];
+    fp_pack(a, w);
+    p256_store8(p, w);
+}
+// x || y of the point; the identity (Z = 0, so x = y = 0 after the multiplication by 0^-1 = 0) stores 64 zero bytes
+DR_DEV void p256_store_affine(uint32_t* out, const P256Point& acc) {
+    const F256 zi = fp_inv(acc.z);
+    p256_store_fe(out, mul(acc.x, zi));
+    p256_store_fe(out + 8, mul(acc.y, zi));
+}
+// LDS table [entry][limb][lane] (bank = lane whatever the entry), limb images of the (normal) coordinates
+DR_DEV void p256_lds_store(uint32_t* tab, int entry, int lane, const P256Point& p) {
+    uint32_t* base = tab + (size_t)entry * P256_PT_WORDS * P256_BLOCK + lane;
+#pragma unroll
+    for (int i = 0; i < FP_L; i++) {
+        base[(0 + i) * P256_BLOCK] = (uint32_t)p.x.l[i];
+        base[(9 + i) * P256_BLOCK] = (uint32_t)p.y.l[i];
+        base[(18 + i) * P256_BLOCK] = (uint32_t)p.z.l[i];
+    }
+}
+DR_DEV P256Point p256_lds_load(const uint32_t* tab, int entry, int lane) {
+    const uint32_t* base = tab + (size_t)entry * P256_PT_WORDS * P256_BLOCK + lane;
+    P256Point p;
+#pragma unroll
+    for (int i = 0; i < FP_L; i++) {
+        p.x.l[i] = (int32_t)base[(0 + i) * P256_BLOCK];
+        p.y.l[i] = (int32_t)base[(9 + i) * P256_BLOCK];
+        p.z.l[i] = (int32_t)base[(18 + i) * P256_BLOCK];
+    }
+    return p;
+}
+DR_DEV P256Point p256_shfl_down(const P256Point& p, unsigned delta) {
+    P256Point o;
+#pragma unroll
+    for (int t = 0; t < FP_L; t++) {
+        o.x.l[t] = __shfl_down(p.x.l[t], delta, 64);
+        o.y.l[t] = __shfl_down(p.y.l[t], delta, 64);
+        o.z.l[t] = __shfl_down(p.z.l[t], delta, 64);
+    }
+    return o;
+}
+
+// k mod n for a 256-bit k: 2 n > 2^256, so one conditional subtraction (in every lane)
+DR_DEV void p256_load_scalar(const uint32_t* p, uint32_t (&k)[8]) {
+    constexpr uint32_t N[8] = {0xfc632551u, 0xf3b9cac2u, 0xa7179e84u, 0xbce6faadu, 0xffffffffu, 0xffffffffu, 0x00000000u, 0xffffffffu};
+    p256_load8(p, k);
+    uint32_t d[8], borrow = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) d[i] = subb(k[i], N[i], borrow);
+#pragma unroll
+    for (int i = 0; i < 8; i++) k[i] = borrow ? k[i] : d[i];
+}
+
+// k P for k < n on the fixed schedule of ed_scalar_mul_core (kernels_ed25519.hip.h): table 1P..8P in LDS, 65 signed 4-bit windows
+// (n has 256 bits: the carry out of the 64th digit is a 65th), four doublings and one table addition each whatever the digits —
+// the secret scalars of the provers go through here
+DR_DEV P256Point p256_scalar_mul_core(uint32_t* tab, int lane, const P256Point& P, const uint32_t (&k)[8]) {
+    p256_lds_store(tab, 0, lane, P);
+    P256Point Q = p256_dbl(P);
+    p256_lds_store(tab, 1, lane, Q);
+#pragma unroll 1
+    for (int e = 2; e < P256_TABLE; e++) {
+        Q = p256_add(Q, P);
+        p256_lds_store(tab, e, lane, Q);
+    }
+    uint32_t dig[8];                 // digits 0..63 in [-8, 7], stored as d + 8; digit 64 = top_carry
+    uint32_t carry_in = 0;
+#pragma unroll
+    for (int w = 0; w < 8; w++) {
+        uint32_t packed = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const uint32_t v = ((k[w] >> (4 * j)) & 15u) + carry_in;
+            carry_in = v >= 8u ? 1u : 0u;
+            packed |= ((v + 8u) & 15u) << (4 * j);
+        }
+        dig[w] = packed;
+    }
+    const uint32_t top_carry = carry_in;
+    P256Point acc = p256_identity();
+#pragma unroll 1
+    for (int w = P256_WINDOWS - 1; w >= 0; w--) {
+#pragma unroll 1
+        for (int j = 0; j < 4; j++) acc = p256_dbl(acc);
+        const int dg = w == P256_WINDOWS - 1 ? (int)top_carry : (int)((dig[w >> 3] >> (4 * (w & 7))) & 15u) - 8;
+        const int mag = dg < 0 ? -dg : dg;
+        P256Point T = p256_lds_load(tab, mag == 0 ? 0 : mag - 1, lane);
+        T = p256_cneg(T, dg < 0);
+        if (mag == 0) T = p256_identity();
+        acc = p256_add(acc, T);
+    }
+    return acc;
+}
+
+// out[i] = k[i] P[i].  pts: n x 16 words (x || y), ks: n x 8, out: n x 16.  One lane per multiplication.
+__global__ __launch_bounds__(P256_BLOCK) void k_p256_scalar_mul(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks,
+                                                                uint32_t* __restrict__ out, uint32_t n) {
+    __shared__ uint32_t tab[P256_TABLE * P256_PT_WORDS * P256_BLOCK];
+    const int lane = threadIdx.x;
+    uint32_t i = blockIdx.x * P256_BLOCK + lane;
+    const bool live = i < n;
+    if (!live) i = n - 1;            // keep the wave converged; the duplicate result is not stored
+    const P256Point P = p256_load_affine(pts + (size_t)i * 16);
+    uint32_t k[8];
+    p256_load_scalar(ks + (size_t)i * 8, k);
+    const P256Point acc = p256_scalar_mul_core(tab, lane, P, k);
+    if (live) p256_store_affine(out + (size_t)i * 16, acc);
+}
+
+// out[g] = sum_{j<m} k[g m + j] P[g m + j]: one lane per term (m padded to mpad, a power of two <= 64), folded with shuffles by the
+// complete addition (terms that coincide or cancel need nothing special) — k_ed_msm_groups for this curve
+__global__ __launch_bounds__(P256_BLOCK) void k_p256_msm_groups(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks,
+                                                                uint32_t* __restrict__ out, uint32_t groups, uint32_t m, uint32_t mpad) {
+    __shared__ uint32_t tab[P256_TABLE * P256_PT_WORDS * P256_BLOCK];
+    const int lane = threadIdx.x;
+    const uint32_t per_block = P256_BLOCK / mpad;
+    const uint32_t g = blockIdx.x * per_block + lane / mpad;
+    const uint32_t j = lane % mpad;
+    const bool live = g < groups && j < m;
+    const size_t idx = live ? (size_t)g * m + j : 0;          // dead lanes recompute term 0 and are masked out
+    const P256Point P = p256_load_affine(pts + idx * 16);
+    uint32_t k[8];
+    p256_load_scalar(ks + idx * 8, k);
+    const P256Point r = p256_scalar_mul_core(tab, lane, P, k);
+    P256Point acc = live ? r : p256_identity();
+#pragma unroll 1
+    for (uint32_t s = mpad >> 1; s > 0; s >>= 1) acc = p256_add(acc, p256_shfl_down(acc, s));
+    if (g < groups && j == 0) p256_store_affine(out + (size_t)g * 16, acc);
+}
+
+// Decoding (the reference's P256Point.string_to_point / _string_to_canonical_point and, for strings that start with 0x02 or 0x03,
+// SWAffinePoint.string_to_point as the fallback), one lane per 33-byte encoding padded to 9 words (bytes 33..35 zero):
+//   canonical: x = bytes 0..31 little-endian, flag = byte 32; flag bits 0..5 set -> rejected; bit 6 (infinity): the identity iff
+//              x = 0 and bit 7 clear, otherwise rejected; else x < p and x^3 - 3 x + b a square, y the larger root iff bit 7;
+//   fallback : when byte 0 is 0x02 or 0x03 and the canonical decoding failed: x = bytes 1..32 BIG-endian (the flag byte included),
+//              x < p and a root, y of the parity byte 0 & 1 (SEC1 compressed).
+// MODE: P256_DEC_CODEC the codec alone (the identity is accepted, out = 64 zero bytes); P256_DEC_CHECK also rejects the identity
+// (the cofactor is 1: a decoded point other than O is a valid point); P256_DEC_TAI the device half of try-and-increment, whose
+// candidates (32 squeezed bytes and the flag 0x80) are accepted on the same terms — no cofactor to clear, so it is CHECK again.
+enum { P256_DEC_CODEC = 0, P256_DEC_CHECK = 1, P256_DEC_TAI = 2 };
+// y^2 = x^3 - 3 x + b for x in Montgomery form; ok and a root (either one) if it exists
+DR_DEV bool p256_y_of_x(const F256& x, F256& y) {
+    const F256 x3 = mul(sqr(x), x);
+    const F256 rhs = fp_reduce(add(sub(x3, add(x, dbl(x))), F256::constant<Fp256Consts::B>()));     // n - s3 + n: r
+    return fp_sqrt(rhs, y);
+}
+// words below p?
+DR_DEV bool p256_below_p(const uint32_t (&w)[8]) {
+    uint32_t borrow = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) (void)subb(w[j], Fp256Consts::PW[j], borrow);
+    return borrow != 0;
+}
+template <int MODE>
+__global__ __launch_bounds__(P256_BLOCK) void k_p256_decode_points(const uint32_t* __restrict__ enc /* n*9 */, uint32_t* __restrict__ out_xy /* n*16 */,
+                                                                   uint32_t* __restrict__ ok, uint32_t n) {
+    const int lane = threadIdx.x;
+    uint32_t i = blockIdx.x * P256_BLOCK + lane;
+    const bool live = i < n;
+    if (!live) i = n - 1;
+    uint32_t w[9];
+#pragma unroll
+    for (int j = 0; j < 9; j++) w[j] = enc[(size_t)i * 9 + j];
+    const uint32_t flag = w[8] & 0xffu, first = w[0] & 0xffu;
+    uint32_t xs[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) xs[j] = w[j];
+    // canonical
+    uint32_t xzero = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) xzero |= xs[j];
+    const bool infinity = (flag & 0x40u) != 0, larger = (flag & 0x80u) != 0;
+    bool valid = (flag & 0x3fu) == 0 && p256_below_p(xs);
+    bool is_identity = false;
+    F256 x = fp_unpack(xs), y;
+    const bool root = p256_y_of_x(x, y);
+    if (infinity) {
+        is_identity = valid && xzero == 0 && !larger;
+        valid = is_identity;
+    } else {
+        valid = valid && root;
+    }
+    uint32_t yw[8];
+    fp_pack(y, yw);
+    bool want_larger = larger, by_parity = false;
+    // the SEC1 fallback: x = BE(bytes 1..32) — little-endian word q is bswap of the (unaligned) word at byte 29 - 4 q
+    if (!valid && (first == 0x02u || first == 0x03u)) {
+        uint32_t xb[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const int k = 7 - q;
+            xb[q] = __builtin_bswap32((w[k] >> 8) | (w[k + 1] << 24));
+        }
+        x = fp_unpack(xb);
+        valid = p256_below_p(xb) && p256_y_of_x(x, y);
+        fp_pack(y, yw);
+        by_parity = true;
+        is_identity = false;
+    }
+    // choose the root: the larger iff the flag's bit 7 (canonical), the parity of byte 0 (SEC1)
+    const bool flip = by_parity ? ((yw[0] & 1u) != (first & 1u)) : (fp_is_larger(yw) != want_larger);
+    if (flip) y = neg(y);
+    if constexpr (MODE != P256_DEC_CODEC) valid = valid && !is_identity;
+    if (live) {
+        if (valid && !is_identity) {
+            p256_store_fe(out_xy + (size_t)i * 16, x);
+            p256_store_fe(out_xy + (size_t)i * 16 + 8, y);
+        } else {
+            const uint32_t z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            p256_store8(out_xy + (size_t)i * 16, z);
+            p256_store8(out_xy + (size_t)i * 16 + 8, z);
+        }
+        ok[i] = valid ? 1u : 0u;
+    }
+}
+
+// Diagnostic (dr_p256_field_ops_selftest): fp256.hip.h's operations on raw limb images, one lane per (a, b) pair of 9 int32 limbs each
+// (Montgomery images: the element of an image is its value times 2^-261 mod p), so that tests can drive every operation at the limb
+// bounds its contract allows.  out[i] = ten canonical 32-byte records: a b, a^2, a + b, a - b, -a, carry(a), a b + b a (mul2),
+// a^-1 (0 for 0), sqrt(a) or 0, a itself (pack); then reduce(a) (record 10) and sqr(reduce(a)) (record 11, the case fp_reduce's
+// note in fp256.hip.h is about).  flags[i]: bit 0 a is a square, bit 1 a > p - a,
+// bit 2 the canonical a is odd.
+constexpr int P256_SELFTEST_RECORDS = 12;
+__global__ __launch_bounds__(64) void k_p256_field_selftest(const int32_t* __restrict__ a_limbs, const int32_t* __restrict__ b_limbs, uint32_t n,
+                                                           uint32_t* __restrict__ out, uint32_t* __restrict__ flags) {
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    F256 a, b;
+#pragma unroll
+    for (int t = 0; t < FP_L; t++) { a.l[t] = a_limbs[(size_t)i * FP_L + t]; b.l[t] = b_limbs[(size_t)i * FP_L + t]; }
+    uint32_t* o = out + (size_t)i * P256_SELFTEST_RECORDS * 8;
+    p256_store_fe(o + 0, mul(a, b));
+    p256_store_fe(o + 8, sqr(a));
+    p256_store_fe(o + 16, add(a, b));
+    p256_store_fe(o + 24, sub(a, b));
+    p256_store_fe(o + 32, neg(a));
+    p256_store_fe(o + 40, carry(a));
+    p256_store_fe(o + 48, mul2(a, b, b, a));
+    p256_store_fe(o + 56, fp_inv(a));
+    F256 r;
+    const bool sq = fp_sqrt(a, r);
+    p256_store_fe(o + 64, r);
+    uint32_t w[8];
+    fp_pack(a, w);
+    p256_store8(o + 72, w);
+    p256_store_fe(o + 80, fp_reduce(a));
+    p256_store_fe(o + 88, sqr(fp_reduce(a)));
+    flags[i] = (sq ? 1u : 0u) | (fp_is_larger(w) ? 2u : 0u) | ((w[0] & 1u) ? 4u : 0u);
+}
+
+}  // namespace dr

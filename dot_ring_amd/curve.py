@@ -5,6 +5,8 @@ Mirrors (names, argument meaning, error behaviour) the parts of the reference th
   dot_ring/curve/specs/jubjub.py:17-66          JubJub: same field, a = -1, cofactor 8, try-and-increment
   dot_ring/curve/specs/bandersnatch_sw.py       Bandersnatch_SW: Bandersnatch's group in short Weierstrass form, 33-byte codec,
                                                 try-and-increment; the kernels compute on its twisted Edwards image
+  dot_ring/curve/specs/p256.py                  P256 (= P256_TAI): NIST P-256, its own field, 33-byte codec with a SEC1 fallback,
+                                                try-and-increment with SHA-256; kernels of their own (DR_CURVE_P256)
   dot_ring/curve/point.py:150-214               compressed codec
   dot_ring/curve/twisted_edwards/*              affine law, Elligator2 encode_to_curve
   dot_ring/curve/curve.py:56-67,110-237,384-401 valid_point, hash_to_field, key derivation
@@ -105,6 +107,11 @@ class BandersnatchCurve:
         p = self.params.field_modulus
         if p == _P:
             return _native.fr_sqrt(val % _P)    # raises ValueError("No square root exists")
+        if p % 4 == 3:                          # P-256's field
+            r = pow(val % p, (p + 1) // 4, p)
+            if r * r % p != val % p:
+                raise ValueError("No square root exists")
+            return r
         return _sqrt_5mod8(val % p, p)
 
     def is_square(self, val: int) -> bool:
@@ -250,7 +257,7 @@ class BandersnatchPoint:
         if st is None:
             sp = cls.curve.params
             le = lambda pt: pt[0].to_bytes(32, "little") + pt[1].to_bytes(32, "little")  # noqa: E731
-            st = _native.vrf_suite(sp.suite_id, sp.xof, le(sp.generator), le(sp.auxiliary_points.blinding_base), sp.curve_id)
+            st = _native.vrf_suite(sp.suite_id, sp.hash_fn, le(sp.generator), le(sp.auxiliary_points.blinding_base), sp.curve_id)
             cls._suite_cache = st
         return st
 
@@ -453,6 +460,182 @@ class BandersnatchSWPoint:
         return unpack_points(cls, runtime.context().encode_to_curve_batch(cls._suite_struct(), list(alpha_strings), salts))
 
 
+class P256Point:
+    """Affine point of P-256 (dot_ring/curve/specs/p256.py, P256_TAI): y^2 = x^3 - 3 x + b over its own field, cofactor 1, the identity
+    is (None, None).  Single additions are host big-int code; scalar multiplications, MSMs, decoding and hash-to-curve run on the GPU
+    under DR_CURVE_P256 (kernels_p256.hip.h)."""
+    curve: BandersnatchCurve
+    _P = 0xFFFFFFFF00000001000000000000000000000000FFFFFFFFFFFFFFFFFFFFFFFF
+    _N = 0xFFFFFFFF00000000FFFFFFFFFFFFFFFFBCE6FAADA7179E84F3B9CAC2FC632551
+    _H, _CV = 1, _native.CURVE_P256
+    _SW_A = -3
+    _SW_B = 0x5AC635D8AA3A93E7B3EBBD55769886BC651D06B0CC53B0F63BCE3C3E27D2604B
+    __slots__ = ("x", "y")
+
+    def __init__(self, x, y):
+        self.x, self.y = x, y
+        if x is None and y is None:
+            return
+        if x is None or y is None or not (0 <= x < self._P and 0 <= y < self._P):
+            raise ValueError("Invalid point coordinates")
+        if not self._on_curve(x, y):
+            raise ValueError("Point is not on the curve")
+
+    @classmethod
+    def _on_curve(cls, x: int, y: int) -> bool:
+        return (y * y - (x * x * x + cls._SW_A * x + cls._SW_B)) % cls._P == 0
+
+    @classmethod
+    def _trusted(cls, x: int, y: int):
+        """Kernel outputs: 64 zero bytes are the identity."""
+        pt = object.__new__(cls)
+        pt.x, pt.y = (None, None) if x == 0 and y == 0 else (x, y)
+        return pt
+
+    def __eq__(self, other):
+        return isinstance(other, P256Point) and self.x == other.x and self.y == other.y
+
+    def __hash__(self):
+        return 0 if self.x is None else (self.x + self.y) % self._N
+
+    def __repr__(self):
+        return f"{type(self).__name__}({self.x}, {self.y})"
+
+    @classmethod
+    def identity(cls):
+        return cls(None, None)
+
+    @classmethod
+    def generator_point(cls):
+        return cls(*cls.curve.params.generator)
+
+    def is_identity(self) -> bool:
+        return self.x is None and self.y is None
+
+    def is_on_curve(self) -> bool:
+        return self.is_identity() or self._on_curve(self.x, self.y)
+
+    # -- group law (sw_affine_point.py)
+    def __add__(self, other):
+        if not isinstance(other, P256Point):
+            raise TypeError("Can only add SWAffinePoint instances")
+        if self.is_identity():
+            return other
+        if other.is_identity():
+            return self
+        p = self._P
+        if self.x == other.x:
+            return self.double() if self.y == other.y else self.identity()
+        lam = (other.y - self.y) * pow(other.x - self.x, -1, p) % p
+        x3 = (lam * lam - self.x - other.x) % p
+        return type(self)(x3, (lam * (self.x - x3) - self.y) % p)
+
+    def double(self):
+        if self.is_identity() or self.y == 0:
+            return self.identity()
+        p = self._P
+        lam = (3 * self.x * self.x + self._SW_A) * pow(2 * self.y, -1, p) % p
+        x3 = (lam * lam - 2 * self.x) % p
+        return type(self)(x3, (lam * (self.x - x3) - self.y) % p)
+
+    def __neg__(self):
+        return self if self.is_identity() else type(self)(self.x, -self.y % self._P)
+
+    def __sub__(self, other):
+        return self + (-other)
+
+    def __mul__(self, scalar: int):
+        return scalar_mul_batch([self], [scalar])[0]
+
+    __rmul__ = __mul__
+
+    @classmethod
+    def msm(cls, points, scalars):
+        if len(points) != len(scalars):
+            raise ValueError("Points and scalars must have same length")
+        if not points:
+            return cls.identity()
+        raw = runtime.context().bsn_msm(pack_points(points), pack_scalars(scalars, cls._N), cls._CV)
+        return cls._trusted(int.from_bytes(raw[:32], "little"), int.from_bytes(raw[32:], "little"))
+
+    def clear_cofactor(self):
+        return self
+
+    # -- codec (p256.py point_to_string / string_to_point / _string_to_canonical_point)
+    def point_to_string(self) -> bytes:
+        if self.is_identity():
+            return bytes(32) + b"\x40"
+        return self.x.to_bytes(32, "little") + (b"\x80" if self.y > -self.y % self._P else b"\x00")
+
+    @classmethod
+    def _y_pair(cls, x: int):
+        """(smaller, larger) root of x^3 - 3 x + b, or None"""
+        p = cls._P
+        try:
+            y = cls.curve.mod_sqrt((x * x * x + cls._SW_A * x + cls._SW_B) % p)
+        except ValueError:
+            return None
+        return tuple(sorted((y, -y % p)))
+
+    @classmethod
+    def _string_to_canonical_point(cls, data: bytes):
+        flag = data[-1]
+        if flag & 0x3F:
+            raise ValueError("Invalid canonical point flags")
+        if (flag >> 6) & 1:
+            if (flag >> 7) & 1 or any(data[:-1]):
+                raise ValueError("Invalid infinity encoding")
+            return cls.identity()
+        x = int.from_bytes(data[:-1], "little")
+        if x >= cls._P:
+            raise ValueError("x-coordinate is not in field")
+        ys = cls._y_pair(x)
+        if ys is None:
+            raise ValueError("Invalid point")
+        return cls(x, ys[1] if (flag >> 7) & 1 else ys[0])
+
+    @classmethod
+    def _string_to_sec1_point(cls, data: bytes):
+        """SWAffinePoint.string_to_point for a 0x02 / 0x03 prefix: x = the big-endian bytes after it, y of that parity"""
+        x = int.from_bytes(data[1:], "big")
+        if x >= cls._P:
+            raise ValueError(f"x-coordinate {x} is not in field Fp (p={cls._P})")
+        ys = cls._y_pair(x)
+        if ys is None:
+            raise ValueError("Invalid point encoding")
+        y = ys[0] if ys[0] % 2 == data[0] % 2 else ys[1]
+        return cls(x, y)
+
+    @classmethod
+    def string_to_point(cls, data):
+        if isinstance(data, str):
+            data = bytes.fromhex(data)
+        data = bytes(data)
+        if len(data) == 33 and data[0] in (0x02, 0x03):
+            # canonical encodings put their flags in the last byte, so they can start with a SEC1 marker byte: the canonical
+            # reading first, SEC1 compressed if that fails (the reference's fallback, which try-and-increment reaches too)
+            try:
+                return cls._string_to_canonical_point(data)
+            except ValueError:
+                return cls._string_to_sec1_point(data)
+        if len(data) != 33:
+            raise ValueError(f"Invalid compressed point length: expected 33, got {len(data)}")
+        return cls._string_to_canonical_point(data)
+
+    # -- hash to curve: try-and-increment (point.py:252-296), candidates hashed natively, decoded on the GPU
+    _suite_struct = BandersnatchPoint.__dict__["_suite_struct"]
+
+    @classmethod
+    def encode_to_curve(cls, alpha_string: bytes, salt: bytes = b""):
+        return cls.encode_to_curve_batch([alpha_string], [salt])[0]
+
+    @classmethod
+    def encode_to_curve_batch(cls, alpha_strings, salts=None):
+        if not alpha_strings:
+            return []
+        return unpack_points(cls, runtime.context().encode_to_curve_batch(cls._suite_struct(), list(alpha_strings), salts))
+
+
 # ------------------------------------------------------------------ batched helpers over the C ABI
 def pack_points(points) -> bytes:
     """x || y little-endian per point; an SW identity ((None, None)) packs as 64 zero bytes, as the ABI takes it."""
@@ -509,6 +692,10 @@ def valid_points(points) -> list[bool]:
     if not live:
         return out
     h, order = type(points[live[0]])._H, type(points[live[0]])._N
+    if h == 1:                               # prime order (P-256): on the curve and not the identity (curve.py:61)
+        for i in live:
+            out[i] = True
+        return out
     cleared = scalar_mul_batch_raw([points[i] for i in live], [h] * len(live))
     back = scalar_mul_batch([c for c in cleared], [pow(h, -1, order)] * len(live))
     for i, c, b in zip(live, cleared, back):
@@ -548,7 +735,7 @@ class CurveVariant:
         self.name, self.curve, self.point_type = name, curve, point_type
 
     def point(self, x, y=None):
-        if isinstance(x, (BandersnatchPoint, BandersnatchSWPoint)):
+        if isinstance(x, (BandersnatchPoint, BandersnatchSWPoint, P256Point)):
             return x
         if y is None:
             x, y = x
@@ -649,3 +836,27 @@ Ed25519_TAI = _suite(
     e2c="tai",
 )
 Ed25519 = Ed25519_TAI
+
+# dot_ring/curve/specs/p256.py, the P256_TAI variant (the reference exports it as P256): NIST P-256 over its own field, a = -3,
+# cofactor 1, 33-byte points, try-and-increment with SHA-256; no accumulator base or padding point, and not twisted Edwards, so
+# RingProofParams refuses it.  Every group operation runs on the P-256 kernels (DR_CURVE_P256).
+_P256_PARAMS = SuiteParams(
+    suite_id=b"Secp256r1-SHA256-TAI-v1", hash_fn=hashlib.sha256, xof=False,
+    auxiliary_points=AuxiliaryPoints(
+        (100063053743935619201936855760019111820847755970243670581468062459849338000,
+         113675507039234898358330549589155441528265243038226986303017485279501143145422),
+        None, None),
+    field_modulus=P256Point._P,
+    subgroup_order=P256Point._N,
+    cofactor=1,
+    a=-3,
+    d=0,
+    generator=(0x6B17D1F2E12C4247F8BCE6E563A440F277037D812DEB33A0F4A13945D898C296,
+               0x4FE342E2FE1A7F9B8EE7EB4A7C0F9E162BCE33576B315ECECBB6406837BF51F5),
+    encoding=Encoding(point_len=33),
+    curve_id=_native.CURVE_P256,
+    e2c="tai",
+)
+P256_TAI = CurveVariant("P256_TAI", BandersnatchCurve(_P256_PARAMS), type("P256_TAIPoint", (P256Point,), {"__slots__": ()}))
+P256_TAI.point_type.curve = P256_TAI.curve
+P256 = P256_TAI

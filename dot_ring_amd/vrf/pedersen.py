@@ -106,7 +106,7 @@ class PedersenVRF(VRF):
         sp = cls.cv.curve.params
         le = lambda v: int(v).to_bytes(32, "little")
         gen, bb = sp.generator, sp.auxiliary_points.blinding_base
-        return _native.vrf_suite(sp.suite_id, sp.xof, le(gen[0]) + le(gen[1]), le(bb[0]) + le(bb[1]), sp.curve_id)
+        return _native.vrf_suite(sp.suite_id, sp.hash_fn, le(gen[0]) + le(gen[1]), le(bb[0]) + le(bb[1]), sp.curve_id)
 
     @classmethod
     def prove_batch(cls, alphas, secret_keys, additional_data, salts=None) -> list:

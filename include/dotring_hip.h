@@ -121,6 +121,16 @@ enum { DR_CURVE_BANDERSNATCH = 0, DR_CURVE_JUBJUB = 1, DR_CURVE_BANDERSNATCH_SW 
  * dr_ietf_prove_batch, dr_pedersen_prove_batch and dr_pedersen_verify_batch (proofs 80 / 96 / 192 bytes).  Every call runs on the
  * kernels (no host route).  The ring prover, the Ring-VRF calls, dr_ietf_verify_batch and the dr_bsn_* calls refuse it. */
 enum { DR_CURVE_ED25519 = 3 };
+/* DR_CURVE_P256: P-256 (dot_ring/curve/specs/p256.py, the P256_TAI variant: y^2 = x^3 - 3 x + b, cofactor 1, n of 256 bits,
+ * try-and-increment with SHA-256) over its own field — its own kernels (csrc/kernels_p256.hip.h, field csrc/fp256.hip.h).  Raw points
+ * are affine x || y little-endian, coordinates below p; 64 zero bytes are the identity ((0, 0) is not on the curve).  Encodings are 33
+ * bytes: x little-endian, then a flag byte (bit 7: y > p - y, bit 6: infinity); a string that starts with 0x02 / 0x03 and does not
+ * decode so is decoded as SEC1 compressed (x = its bytes 1..32 big-endian), as the reference does.  Scalars are reduced mod n on the
+ * device.  Accepted by dr_te_scalar_mul_batch, dr_te_msm, dr_te_msm_groups, dr_te_decode_points (decoded and not the identity),
+ * dr_te_fixed_base_msm_groups (through the variable-base grouped kernel), dr_encode_to_curve_batch, dr_ietf_prove_batch,
+ * dr_pedersen_prove_batch and dr_pedersen_verify_batch (proofs 81 / 98 / 196 bytes; the suite's xof is 2).  Every call runs on the
+ * kernels.  The ring prover, the Ring-VRF calls, dr_ietf_verify_batch, dr_hash_to_field_batch and the dr_bsn_* calls refuse it. */
+enum { DR_CURVE_P256 = 4 };
 DR_API int dr_te_scalar_mul_batch(dr_ctx *ctx, int curve, const uint8_t *pts_xy, const uint8_t *scalars, size_t n, uint8_t *out_xy);
 DR_API int dr_te_msm(dr_ctx *ctx, int curve, const uint8_t *pts_xy, const uint8_t *scalars, size_t n, uint8_t out_xy[64]);
 DR_API int dr_te_msm_groups(dr_ctx *ctx, int curve, const uint8_t *pts_xy, const uint8_t *scalars, size_t groups, size_t m, uint8_t *out_xy);
@@ -153,6 +163,15 @@ DR_API int dr_ed25519_decode_points(dr_ctx *ctx, int check, const uint8_t *enc /
  * sqrt(a / b) or 0.  flags[i]: bit 0 a is a square, bit 1 a / b is a square, bit 2 a > p - a. */
 DR_API int dr_fe25519_ops_selftest(dr_ctx *ctx, const int32_t *a_limbs /* n*9 */, const int32_t *b_limbs /* n*9 */, size_t n,
                                    uint8_t *out /* n*352 */, uint8_t *flags /* n */);
+/* P-256 point decoding: check = 1 as dr_te_decode_points for DR_CURVE_P256, check = 0 the codec alone (the identity's encoding,
+ * 32 zero bytes and 0x40, is then accepted with out_xy = 64 zero bytes).  enc: n x 33 bytes; ok[i] = 1 when accepted. */
+DR_API int dr_p256_decode_points(dr_ctx *ctx, int check, const uint8_t *enc /* n*33 */, size_t n, uint8_t *out_xy /* n*64 */, uint8_t *ok /* n */);
+/* Diagnostic: the device's arithmetic in GF(p256) (csrc/fp256.hip.h) on RAW limb images — 9 signed 32-bit limbs each, value
+ * sum l[i] 2^(29 i), standing for value * 2^-261 mod p (Montgomery form).  out: n x 12 x 32 bytes of canonical little-endian results:
+ * a b, a^2, a + b, a - b, -a, carry(a), a b + b a (fused), a^-1 (0 for 0), sqrt(a) or 0, a, reduce(a), reduce(a)^2.  flags[i]: bit 0 a is a
+ * square, bit 1 a > p - a, bit 2 a is odd. */
+DR_API int dr_p256_field_ops_selftest(dr_ctx *ctx, const int32_t *a_limbs /* n*9 */, const int32_t *b_limbs /* n*9 */, size_t n,
+                                      uint8_t *out /* n*384 */, uint8_t *flags /* n */);
 
 /* square root in the Bandersnatch base field; DR_ERR_NOTSQUARE if none exists. Host-side, no ctx. */
 DR_API int dr_fr_sqrt(const uint8_t in[32], uint8_t out[32]);
@@ -326,7 +345,8 @@ DR_API int dr_ring_prover_residue(dr_ring_prover *p, uint64_t *words);
 enum { DR_HASH_SHA512 = 0, DR_HASH_SHAKE128 = 1, DR_HASH_SHAKE256 = 2,
        /* diagnostic: `data` = four messages of len / 4 bytes each, `out` = their four SHAKE128 digests of out_len / 4 bytes each
         * (at most 168), computed by the four-in-lockstep sponge the batch transcripts use */
-       DR_HASH_SHAKE128_X4 = 3 };
+       DR_HASH_SHAKE128_X4 = 3,
+       DR_HASH_SHA256 = 4 };
 DR_API int dr_host_hash(int kind, const uint8_t *data, size_t len, uint8_t *out, size_t out_len);
 /* out = SHAKE256(seed || LE64(0))[0..576) || SHAKE256(seed || LE64(1))[0..576) || ... (len bytes), hashed on the worker threads.
  * dr_ringvrf_prove_batch's zk_random48 for a batch (12 x 48 bytes per proof: the hidden rows of columns/columns.py:139-146, drawn
@@ -340,11 +360,13 @@ DR_API int dr_ringvrf_aux_take_blindings(uint8_t *aux, size_t batch, uint8_t *ou
 typedef struct dr_vrf_suite {
     const uint8_t *suite_id;        /* e.g. "Bandersnatch-SHA512-ELL2-v1" (bandersnatch.py:74-87) */
     size_t suite_id_len;
-    int xof;                        /* 1: SHAKE128 suite, 0: SHA-512 (counter-mode squeeze, expand_message_xmd) */
+    int xof;                        /* 1: SHAKE128 suite, 0: SHA-512 (counter-mode squeeze, expand_message_xmd), 2: SHA-256 (counter-mode
+                                       squeeze, the P-256 suite); other values are refused */
     uint8_t generator_xy[64];       /* group generator, x||y little-endian */
     uint8_t blinding_base_xy[64];   /* Pedersen blinding base (bandersnatch.py:89-102) */
     int curve;                      /* DR_CURVE_BANDERSNATCH (Elligator 2 hash-to-curve), DR_CURVE_JUBJUB, DR_CURVE_BANDERSNATCH_SW or
-                                       DR_CURVE_ED25519 (try-and-increment; for the SW suite generator and blinding base are SW affine) */
+                                       DR_CURVE_ED25519 or DR_CURVE_P256 (try-and-increment; for the SW suite and P-256 generator and
+                                       blinding base are SW affine) */
 } dr_vrf_suite;
 
 /* hash_to_field(msg, 2) for `count` messages msgs[off[i]..off[i+1]): out = count * 2 field elements (32-byte LE),
