@@ -1,13 +1,14 @@
 """dot_ring_amd — MI355X-native (gfx950) Ring-VRF hot path behind dot-ring's Python API.
 
 The arithmetic lives in libdotring_hip.so (hand-written HIP, see dot_ring_amd/csrc and include/dotring_hip.h);
-this package mirrors the reference's public names (dot_ring/__init__.py:3-19) for the Bandersnatch suites, JubJub, Ed25519 and P-256:
+this package mirrors the reference's public names (dot_ring/__init__.py:3-19) for the Bandersnatch suites, JubJub, Ed25519, P-256 and
+Baby JubJub:
     TinyVRF, ThinVRF, PedersenVRF, RingVRF, Ring, RingRoot, RingProofParams, Bandersnatch, Bandersnatch_SHAKE128, JubJub, Bandersnatch_SW,
-    Ed25519 (= Ed25519_TAI), P256 (= P256_TAI)
+    Ed25519 (= Ed25519_TAI), P256 (= P256_TAI), BabyJubJub
 plus the additive prove_batch() entry points.  There is no CPU fallback for the kernels.
 """
 from . import _native  # noqa: F401
-from .curve import P256, P256_TAI, Bandersnatch, Bandersnatch_SHAKE128, Bandersnatch_SW, Ed25519, Ed25519_TAI, JubJub
+from .curve import P256, P256_TAI, BabyJubJub, Bandersnatch, Bandersnatch_SHAKE128, Bandersnatch_SW, Ed25519, Ed25519_TAI, JubJub
 from .ring_proof.params import RingProofParams
 from .ring_proof.pcs import KZG
 from .vrf.pedersen import PedersenVRF
@@ -16,4 +17,5 @@ from .vrf.thin import ThinVRF
 from .vrf.tiny import TinyVRF
 
 __all__ = ["TinyVRF", "ThinVRF", "PedersenVRF", "RingVRF", "Ring", "RingRoot", "RingProofParams", "KZG",
-           "Bandersnatch", "Bandersnatch_SHAKE128", "JubJub", "Bandersnatch_SW", "Ed25519", "Ed25519_TAI", "P256", "P256_TAI"]
+           "Bandersnatch", "Bandersnatch_SHAKE128", "JubJub", "Bandersnatch_SW", "Ed25519", "Ed25519_TAI", "P256", "P256_TAI",
+           "BabyJubJub"]

@@ -110,6 +110,8 @@ _PROTOTYPES.update({
     "dr_fe25519_ops_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p, c_void_p]),
     "dr_p256_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
     "dr_p256_field_ops_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p, c_void_p]),
+    "dr_bjj_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
+    "dr_bjj_field_ops_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p, c_void_p]),
     "dr_encode_to_curve_batch": (c_int, [c_void_p, POINTER(VrfSuiteStruct), c_char_p, POINTER(ctypes.c_uint64), c_char_p,
                                          POINTER(ctypes.c_uint64), c_size_t, c_char_p]),
     "dr_ring_prover_create_te": (c_int, [c_void_p, c_int, c_void_p, c_uint, c_uint, c_char_p, c_char_p, c_char_p, c_char_p, POINTER(c_void_p)]),
@@ -191,7 +193,7 @@ def _ragged(items):
     return b"".join(items), (ctypes.c_uint64 * len(off)).from_buffer(off)
 
 
-CURVE_BANDERSNATCH, CURVE_JUBJUB, CURVE_BANDERSNATCH_SW, CURVE_ED25519, CURVE_P256 = 0, 1, 2, 3, 4
+CURVE_BANDERSNATCH, CURVE_JUBJUB, CURVE_BANDERSNATCH_SW, CURVE_ED25519, CURVE_P256, CURVE_BABYJUBJUB = 0, 1, 2, 3, 4, 5
 # dr_vrf_suite.xof: the transcript hash of a suite
 XOF_SHA512, XOF_SHAKE128, XOF_SHA256 = 0, 1, 2
 _XOF_OF_HASH = {"sha512": XOF_SHA512, "shake_128": XOF_SHAKE128, "sha256": XOF_SHA256}
@@ -568,6 +570,24 @@ class Context:
         out, flags = ctypes.create_string_buffer(max(1, 384 * n)), ctypes.create_string_buffer(max(1, n))
         _check(lib().dr_p256_field_ops_selftest(self.handle, a_limbs, b_limbs, n, out, flags))
         return out.raw[: 384 * n], flags.raw[:n]
+
+    def bjj_field_ops_selftest(self, a_limbs: bytes, b_limbs: bytes):
+        """dr_bjj_field_ops_selftest: (n x 12 x 32 result bytes, n flag bytes) for n pairs of raw 9-limb Montgomery images."""
+        n = len(a_limbs) // 36
+        if len(a_limbs) != 36 * n or len(b_limbs) != 36 * n:
+            raise ValueError("operands are 9 int32 limbs each")
+        out, flags = ctypes.create_string_buffer(max(1, 384 * n)), ctypes.create_string_buffer(max(1, n))
+        _check(lib().dr_bjj_field_ops_selftest(self.handle, a_limbs, b_limbs, n, out, flags))
+        return out.raw[: 384 * n], flags.raw[:n]
+
+    def bjj_decode_points(self, enc: bytes, check: bool = True):
+        """dr_bjj_decode_points: (x||y bytes, flags) for len(enc)/32 encodings, with or without the prime-order check."""
+        if len(enc) % 32:
+            raise ValueError("compressed points are 32 bytes each")
+        count = len(enc) // 32
+        out, ok = ctypes.create_string_buffer(max(1, 64 * count)), ctypes.create_string_buffer(max(1, count))
+        _check(lib().dr_bjj_decode_points(self.handle, 1 if check else 0, enc, count, out, ok))
+        return out.raw[: 64 * count], ok.raw[:count]
 
     def p256_decode_points(self, enc: bytes, check: bool = True):
         """dr_p256_decode_points: (x||y bytes, flags) for len(enc)/33 encodings, with or without the identity check."""

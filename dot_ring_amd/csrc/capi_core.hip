@@ -5,6 +5,7 @@
 #include "kernels_sw.hip.h"
 #include "kernels_ed25519.hip.h"
 #include "kernels_p256.hip.h"
+#include "kernels_bjj.hip.h"
 
 namespace dri {
 
@@ -370,7 +371,7 @@ int dr_prof_get(dr_ctx* ctx, const char* name, double* total_ms, int* launches) 
 // ------------------------------------------------------------------------------- seam A
 int te_scalar_mul_batch_dev(dr_ctx* ctx, int cv, const void* d_pts, const void* d_scalars, size_t n, void* d_out) {
     TRY(use_ctx(ctx));
-    if (cv == dr::CV_ED25519 || cv == dr::CV_P256)
+    if (cv == dr::CV_ED25519 || cv == dr::CV_P256 || cv == dr::CV_BABYJUBJUB)
         return fail(DR_ERR_INVALID, "device-resident scalar multiplication serves the curves over the BLS12-381 scalar field");
     if (n == 0) return DR_OK;
     if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
@@ -725,11 +726,204 @@ int p256_decode_points(dr_ctx* ctx, int mode, const uint8_t* enc, size_t n, uint
 }
 }  // namespace
 
+// ---- Baby JubJub (kernels_bjj.hip.h).  As for Ed25519: every call runs on the kernels, no host route, nothing here touches the
+// BLS12-381 field, and secrets pass through io_a / io_b / io_c only.  The square-root tables (BjjConsts) are built on the host once
+// per process and copied to the device the first time a context decodes a point.
+namespace {
+int bjj_consts_build(dr::BjjConsts& h) {
+    const drh::Mod256& F = drh::mod_pbn254();
+    static const uint64_t R261[4] = {0x2fd4e1568fffff57ULL, 0x75bba827a494b01aULL, 0x5301fa84819caa80ULL, 0x0dc83629563d4475ULL};   // 2^261 mod p
+    static const uint64_t Q[4] = {0x9b9709143e1f593fULL, 0x181585d2833e8487ULL, 0x131a029b85045b68ULL, 0x000000030644e72eULL};     // (p-1) / 2^28
+    const uint64_t one[4] = {1, 0, 0, 0}, five[4] = {5, 0, 0, 0};
+    uint64_t pm2[4];
+    std::memcpy(pm2, F.m, 32);
+    pm2[0] -= 2;                                               // (p = 1 mod 2^28: no borrow)
+    auto put = [&](uint32_t (&w)[8], const uint64_t v[4]) {    // the device's Montgomery words of v
+        uint64_t t[4];
+        F.mul(v, R261, t);
+        std::memcpy(w, t, 32);
+    };
+    auto mul = [&](const uint64_t a[4], const uint64_t b[4], uint64_t r[4]) { F.mul(a, b, r); };
+    uint64_t c[4], c_inv[4];
+    F.pow(five, Q, c);                                         // order 2^28
+    F.pow(c, pm2, c_inv);
+    for (int j = 0; j < 4; j++) {
+        uint64_t step[4], hstep[4];                            // c^(-2^(7j)), c^(-2^(7j - 1)) (j = 0: c^-1, applied every other k)
+        std::memcpy(step, c_inv, 32);
+        for (int q = 0; q < 7 * j; q++) mul(step, step, step);
+        std::memcpy(hstep, c_inv, 32);
+        for (int q = 0; q < 7 * j - 1; q++) mul(hstep, hstep, hstep);
+        uint64_t m[4], hh[4];
+        std::memcpy(m, one, 32);
+        std::memcpy(hh, one, 32);
+        for (int k = 0; k < 128; k++) {
+            if (j < 3) put(h.dl_mul[j][k], m);
+            put(h.dl_half[j][k], hh);
+            if (j > 0 || (k & 1)) mul(hh, hstep, hh);
+            mul(m, step, m);
+        }
+    }
+    uint64_t g3[4], v[4];
+    std::memcpy(g3, c, 32);
+    for (int q = 0; q < 21; q++) mul(g3, g3, g3);              // order 2^7
+    std::vector<uint32_t> low(128);
+    std::memcpy(v, one, 32);
+    for (int k = 0; k < 128; k++) {
+        low[k] = (uint32_t)v[0];
+        mul(v, g3, v);
+    }
+    if (!(v[0] == 1 && v[1] == 0 && v[2] == 0 && v[3] == 0)) return fail(DR_ERR_DEVICE, "bad discrete-logarithm constants");
+    for (uint32_t a = 0x9e3779b1u; a > 0x9e3779b1u - 2000000u; a -= 2) {
+        std::memset(h.dl_map, 0xff, sizeof h.dl_map);
+        std::vector<uint8_t> used(dr::BJJ_DL_SLOTS, 0);
+        bool ok = true;
+        for (int k = 0; k < 128 && ok; k++) {
+            const uint32_t idx = (low[k] * a) >> 20;
+            if (used[idx]) ok = false;
+            used[idx] = 1;
+            h.dl_map[idx] = (uint8_t)k;
+        }
+        if (ok) { h.dl_hash_mul = a; return DR_OK; }
+    }
+    return fail(DR_ERR_DEVICE, "no perfect hash for the discrete-logarithm table");
+}
+int bjj_consts_ready(dr_ctx* ctx) {
+    if (ctx->bjj_ready) return DR_OK;
+    static std::unique_ptr<dr::BjjConsts> host;                // 33 KB, the same for every context
+    static int host_rc = [] { host = std::make_unique<dr::BjjConsts>(); return bjj_consts_build(*host); }();
+    if (host_rc != DR_OK) return fail(DR_ERR_DEVICE, "bad Baby JubJub square-root constants");
+    HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(dr::g_bjj_consts), host.get(), sizeof(dr::BjjConsts), 0, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->bjj_ready = true;
+    return DR_OK;
+}
+int check_bjj_elems(const uint8_t* p, size_t count, const char* what) {
+    for (size_t i = 0; i < count; i++) {
+        uint64_t v[4];
+        drh::load_le32(p + 32 * i, v);
+        if (drh::Mod256::geq(v, drh::mod_pbn254().m)) return fail(DR_ERR_INVALID, std::string(what) + " coordinate is not a canonical field element");
+    }
+    return DR_OK;
+}
+int bjj_scalar_mul_batch(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy) {
+    if (n == 0) return DR_OK;
+    if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
+    if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
+    TRY(check_bjj_elems(pts_xy, 2 * n, "point"));
+    TRY(ctx->io_a.reserve(n * 64));
+    TRY(ctx->io_b.reserve(n * 32));
+    TRY(ctx->io_c.reserve(n * 64));
+    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, pts_xy, n * 64, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->io_b.p, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    TRY(launch(ctx, "k_bjj_scalar_mul", [&] {
+        hipLaunchKernelGGL(dr::k_bjj_scalar_mul, dim3(div_up(n, dr::BJJ_BLOCK)), dim3(dr::BJJ_BLOCK), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
+                           ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
+    }));
+    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_c.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->prof) TRY(prof_collect(ctx));
+    return DR_OK;
+}
+int bjj_msm_groups(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy) {
+    if (groups == 0) return DR_OK;
+    if (m == 0 || m > 64) return fail(DR_ERR_INVALID, "group size must be in 1..64");
+    if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
+    const size_t n = groups * m;
+    if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
+    TRY(check_bjj_elems(pts_xy, 2 * n, "point"));
+    uint32_t mpad = 1;
+    while (mpad < m) mpad <<= 1;
+    TRY(ctx->io_a.reserve(n * 64));
+    TRY(ctx->io_b.reserve(n * 32));
+    TRY(ctx->io_c.reserve(groups * 64));
+    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, pts_xy, n * 64, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->io_b.p, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    const uint32_t per_block = dr::BJJ_BLOCK / mpad;
+    TRY(launch(ctx, "k_bjj_msm_groups", [&] {
+        hipLaunchKernelGGL(dr::k_bjj_msm_groups, dim3(div_up(groups, per_block)), dim3(dr::BJJ_BLOCK), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
+                           ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)groups, (uint32_t)m, mpad);
+    }));
+    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_c.p, groups * 64, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->prof) TRY(prof_collect(ctx));
+    return DR_OK;
+}
+// fixed bases through the variable-base grouped kernel (each group's terms are the m bases), as for Ed25519
+int bjj_fixed_base_groups(dr_ctx* ctx, const uint8_t* bases_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy) {
+    if (groups == 0) return DR_OK;
+    if (m == 0 || m > 4) return fail(DR_ERR_INVALID, "1..4 fixed bases per group");
+    if (!bases_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
+    if (groups * m >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
+    std::vector<uint8_t> pts(groups * m * 64);
+    for (size_t g = 0; g < groups; g++) std::memcpy(pts.data() + 64 * m * g, bases_xy, 64 * m);
+    return bjj_msm_groups(ctx, pts.data(), scalars, groups, m, out_xy);
+}
+// one MSM: groups of 64 terms in one launch, then the partial sums with scalar 1, 64 at a time, until one is left
+int bjj_msm(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t out_xy[64]) {
+    if (n == 0) {
+        std::memset(out_xy, 0, 64);
+        out_xy[32] = 1;
+        return DR_OK;
+    }
+    if (!pts_xy || !scalars) return fail(DR_ERR_INVALID, "null buffer");
+    std::vector<uint8_t> pts(pts_xy, pts_xy + n * 64), sc(scalars, scalars + n * 32), part;
+    for (;;) {
+        if (n <= 64) {
+            const int rc = bjj_msm_groups(ctx, pts.data(), sc.data(), 1, n, out_xy);
+            explicit_bzero(sc.data(), sc.size());
+            return rc;
+        }
+        const size_t parts = (n + 63) / 64;
+        pts.resize(parts * 64 * 64, 0);
+        sc.resize(parts * 64 * 32, 0);
+        for (size_t i = n; i < parts * 64; i++) pts[64 * i + 32] = 1;         // padding: 0 * (0, 1)
+        part.resize(parts * 64);
+        const int rc = bjj_msm_groups(ctx, pts.data(), sc.data(), parts, 64, part.data());
+        explicit_bzero(sc.data(), sc.size());
+        TRY(rc);
+        pts.swap(part);
+        n = parts;
+        sc.assign(n * 32, 0);
+        for (size_t i = 0; i < n; i++) sc[32 * i] = 1;
+    }
+}
+int bjj_decode_points(dr_ctx* ctx, int mode, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
+    if (n == 0) return DR_OK;
+    if (!enc || !out_xy || !ok) return fail(DR_ERR_INVALID, "null buffer");
+    if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
+    TRY(bjj_consts_ready(ctx));
+    TRY(ctx->io_a.reserve(n * 32));
+    TRY(ctx->io_b.reserve(n * 64));
+    TRY(ctx->io_c.reserve(n * 4));
+    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, enc, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    TRY(launch(ctx, "k_bjj_decode_points", [&] {
+        const dim3 grid(div_up(n, dr::BJJ_BLOCK)), block(dr::BJJ_BLOCK);
+        if (mode == dr::BJJ_DEC_TAI)
+            hipLaunchKernelGGL(dr::k_bjj_decode_points<dr::BJJ_DEC_TAI>, grid, block, 0, ctx->stream, ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(),
+                               ctx->io_c.as<uint32_t>(), (uint32_t)n);
+        else if (mode == dr::BJJ_DEC_CHECK)
+            hipLaunchKernelGGL(dr::k_bjj_decode_points<dr::BJJ_DEC_CHECK>, grid, block, 0, ctx->stream, ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(),
+                               ctx->io_c.as<uint32_t>(), (uint32_t)n);
+        else
+            hipLaunchKernelGGL(dr::k_bjj_decode_points<dr::BJJ_DEC_CODEC>, grid, block, 0, ctx->stream, ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(),
+                               ctx->io_c.as<uint32_t>(), (uint32_t)n);
+    }));
+    std::vector<uint32_t> flags(n);
+    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_b.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(flags.data(), ctx->io_c.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->prof) TRY(prof_collect(ctx));
+    for (size_t i = 0; i < n; i++) ok[i] = flags[i] ? 1 : 0;
+    return DR_OK;
+}
+}  // namespace
+
 int te_scalar_mul_batch(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy) {
     TRY(use_ctx(ctx));
     TRY(check_curve(cv));
     if (cv == dr::CV_ED25519) return ed_scalar_mul_batch(ctx, pts_xy, scalars, n, out_xy);
     if (cv == dr::CV_P256) return p256_scalar_mul_batch(ctx, pts_xy, scalars, n, out_xy);
+    if (cv == dr::CV_BABYJUBJUB) return bjj_scalar_mul_batch(ctx, pts_xy, scalars, n, out_xy);
     if (n == 0) return DR_OK;
     if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
     TRY(check_fr_elems(pts_xy, 2 * n, "point"));
@@ -794,6 +988,7 @@ int te_msm_groups(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* sca
     TRY(check_curve(cv));
     if (cv == dr::CV_ED25519) return ed_msm_groups(ctx, pts_xy, scalars, groups, m, out_xy);
     if (cv == dr::CV_P256) return p256_msm_groups(ctx, pts_xy, scalars, groups, m, out_xy);
+    if (cv == dr::CV_BABYJUBJUB) return bjj_msm_groups(ctx, pts_xy, scalars, groups, m, out_xy);
     if (groups == 0) return DR_OK;
     if (m == 0 || m > 64) return fail(DR_ERR_INVALID, "group size must be in 1..64");
     if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
@@ -870,6 +1065,7 @@ int te_fixed_base_groups(dr_ctx* ctx, int cv, const uint8_t* bases_xy, const uin
     TRY(check_curve(cv));
     if (cv == dr::CV_ED25519) return ed_fixed_base_groups(ctx, bases_xy, scalars, groups, m, out_xy);
     if (cv == dr::CV_P256) return p256_fixed_base_groups(ctx, bases_xy, scalars, groups, m, out_xy);
+    if (cv == dr::CV_BABYJUBJUB) return bjj_fixed_base_groups(ctx, bases_xy, scalars, groups, m, out_xy);
     if (groups == 0) return DR_OK;
     if (m == 0 || m > 4) return fail(DR_ERR_INVALID, "1..4 fixed bases per group");
     if (!bases_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
@@ -947,6 +1143,7 @@ int te_msm(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* scalars, s
     if (!out_xy) return fail(DR_ERR_INVALID, "null buffer");
     if (cv == dr::CV_ED25519) return ed_msm(ctx, pts_xy, scalars, n, out_xy);
     if (cv == dr::CV_P256) return p256_msm(ctx, pts_xy, scalars, n, out_xy);
+    if (cv == dr::CV_BABYJUBJUB) return bjj_msm(ctx, pts_xy, scalars, n, out_xy);
     if (n == 0) {
         std::memset(out_xy, 0, 64);
         out_xy[32] = 1;
@@ -1084,6 +1281,7 @@ int te_decode_points(dr_ctx* ctx, int cv, bool tai, const uint8_t* enc, size_t n
     TRY(check_curve(cv));
     if (cv == dr::CV_ED25519) return ed_decode_points(ctx, tai ? dr::ED_DEC_TAI : dr::ED_DEC_CHECK, enc, n, out_xy, ok);
     if (cv == dr::CV_P256) return p256_decode_points(ctx, tai ? dr::P256_DEC_TAI : dr::P256_DEC_CHECK, enc, n, out_xy, ok);
+    if (cv == dr::CV_BABYJUBJUB) return bjj_decode_points(ctx, tai ? dr::BJJ_DEC_TAI : dr::BJJ_DEC_CHECK, enc, n, out_xy, ok);
     if (n == 0) return DR_OK;
     if (!enc || !out_xy || !ok) return fail(DR_ERR_INVALID, "null buffer");
     if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
@@ -1127,6 +1325,32 @@ int dr_ed25519_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_t 
 int dr_p256_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
     TRY(use_ctx(ctx));
     return p256_decode_points(ctx, check ? dr::P256_DEC_CHECK : dr::P256_DEC_CODEC, enc, n, out_xy, ok);
+}
+int dr_bjj_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
+    TRY(use_ctx(ctx));
+    return bjj_decode_points(ctx, check ? dr::BJJ_DEC_CHECK : dr::BJJ_DEC_CODEC, enc, n, out_xy, ok);
+}
+int dr_bjj_field_ops_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
+    TRY(use_ctx(ctx));
+    if (n == 0) return DR_OK;
+    if (!a_limbs || !b_limbs || !out || !flags) return fail(DR_ERR_INVALID, "null buffer");
+    if (n >= (1ull << 24)) return fail(DR_ERR_INVALID, "batch too large");
+    TRY(bjj_consts_ready(ctx));
+    const size_t rec = (size_t)dr::BJJ_SELFTEST_RECORDS * 32;
+    TRY(ctx->io_a.reserve(n * 72));
+    TRY(ctx->io_b.reserve(n * rec));
+    TRY(ctx->io_c.reserve(n * 4));
+    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, a_limbs, n * 36, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->io_a.as<uint8_t>() + n * 36, b_limbs, n * 36, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(dr::k_bjj_field_selftest, dim3(div_up(n, 64)), dim3(64), 0, ctx->stream, ctx->io_a.as<int32_t>(),
+                       (const int32_t*)(ctx->io_a.as<uint8_t>() + n * 36), (uint32_t)n, ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> fl(n);
+    HIP_TRY(hipMemcpyAsync(out, ctx->io_b.p, n * rec, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(fl.data(), ctx->io_c.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < n; i++) flags[i] = (uint8_t)fl[i];
+    return DR_OK;
 }
 int dr_p256_field_ops_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
     TRY(use_ctx(ctx));
@@ -1297,6 +1521,7 @@ int load_suite(const dr_vrf_suite* s, drh::VrfSuite& out, bool allow_sw) {
     out.cv = drh::te_curve(s->curve);
     if (!out.cv) return fail(DR_ERR_INVALID, "unknown curve id in VRF suite");
     if (out.cv->ed25519 && !allow_sw) return fail(DR_ERR_INVALID, "this entry point does not serve the Ed25519 suite");
+    if (out.cv->bjj && !allow_sw) return fail(DR_ERR_INVALID, "this entry point does not serve the Baby JubJub suite");
     if (out.cv->p256) {
         if (!allow_sw) return fail(DR_ERR_INVALID, "this entry point does not serve the P-256 suite");
         out.point_len = 33;

@@ -102,6 +102,7 @@ struct dr_ctx {
     hipStream_t wipe_stream = nullptr;
     hipEvent_t wipe_from = nullptr, wipe_done = nullptr;
     bool wipe_pending = false;
+    bool bjj_ready = false;                  // the Baby JubJub square-root tables are on this context's device (capi_core.hip)
     dr_ctx* aux = nullptr;                   // second stream for the latency-bound Bandersnatch side of the batch verifier
     dr_ctx* aux2 = nullptr;                  // third stream: the verifier's two G1 MSMs run side by side
     std::vector<dr_ctx*> helpers;            // further streams working for this context (a prover's Pedersen stream): profiling only

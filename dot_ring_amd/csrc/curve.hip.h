@@ -34,6 +34,8 @@ enum { CV_BANDERSNATCH = 0, CV_JUBJUB = 1, CV_BANDERSNATCH_SW = 2 };   // (the S
 enum { CV_ED25519 = 3 };
 // CV_P256 = 4 (DR_CURVE_P256) is a short Weierstrass curve over a third field: kernels_p256.hip.h
 enum { CV_P256 = 4 };
+// CV_BABYJUBJUB = 5 (DR_CURVE_BABYJUBJUB) is a twisted Edwards curve over the BN254 scalar field: kernels_bjj.hip.h
+enum { CV_BABYJUBJUB = 5 };
 
 // d in Montgomery form (2^261): 0x6389C12633C267CBC66E3BF86BE3B6D8CB66677177E54F92B369F2F5188D58E7 (Bandersnatch),
 // 0x2A9318E74BFA2B48F5FD9207E6BD7FD4292D7F6D37579D2601065FD6D6343EB1 (JubJub)

@@ -237,6 +237,11 @@ struct Mod256 {
         std::memcpy(out, acc, 32);
     }
     bool is_zero(const uint64_t* a) const { return (a[0] | a[1] | a[2] | a[3]) == 0; }
+    unsigned bits() const {                                      // bit length of the modulus
+        for (int i = 3; i >= 0; i--)
+            if (m[i]) return 64 * i + 64 - (unsigned)__builtin_clzll(m[i]);
+        return 0;
+    }
     void pow(const uint64_t* a, const uint64_t e[4], uint64_t* r) const {     // standard form
         uint64_t acc[4] = {1, 0, 0, 0}, base[4];
         std::memcpy(base, a, 32);
@@ -320,6 +325,7 @@ struct TeCurveHost {
     bool sw = false;          // points cross the ABI as short Weierstrass affine x || y (33-byte encodings); TE inside
     bool ed25519 = false;     // over GF(2^255 - 19), not the BLS12-381 scalar field: the kernels of kernels_ed25519.hip.h, no host route
     bool p256 = false;        // P-256: short Weierstrass over its own field, the kernels of kernels_p256.hip.h, 33-byte encodings, no host route
+    bool bjj = false;         // Baby JubJub: over the BN254 scalar field, the kernels of kernels_bjj.hip.h, no host route
 };
 inline const Mod256& mod_p25519() {   // Ed25519 base field (specs/ed25519.py)
     static Mod256 s = [] { Mod256 t; const uint64_t p[4] = {0xffffffffffffffedULL, 0xffffffffffffffffULL, 0xffffffffffffffffULL, 0x7fffffffffffffffULL}; t.init(p); return t; }();
@@ -329,8 +335,12 @@ inline const Mod256& mod_p256() {      // P-256 base field (specs/p256.py)
     static Mod256 s = [] { Mod256 t; const uint64_t p[4] = {0xffffffffffffffffULL, 0x00000000ffffffffULL, 0x0000000000000000ULL, 0xffffffff00000001ULL}; t.init(p); return t; }();
     return s;
 }
+inline const Mod256& mod_pbn254() {    // Baby JubJub base field = BN254 scalar field (specs/baby_jubjub.py)
+    static Mod256 s = [] { Mod256 t; const uint64_t p[4] = {0x43e1f593f0000001ULL, 0x2833e84879b97091ULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL}; t.init(p); return t; }();
+    return s;
+}
 inline const TeCurveHost* te_curve(int id) {
-    static const TeCurveHost curves[5] = {
+    static const TeCurveHost curves[6] = {
         [] { TeCurveHost c{}; c.id = 0; c.n = mod_n();
              const uint64_t d[4] = {0xb369f2f5188d58e7ULL, 0xcb66677177e54f92ULL, 0xc66e3bf86be3b6d8ULL, 0x6389c12633c267cbULL};
              std::memcpy(c.d, d, 32); c.neg_a[0] = 5; c.scalar_bits = 253; c.glv = true; c.tai = false; return c; }(),
@@ -354,11 +364,19 @@ inline const TeCurveHost* te_curve(int id) {
              const uint64_t n[4] = {0xf3b9cac2fc632551ULL, 0xbce6faada7179e84ULL, 0xffffffffffffffffULL, 0xffffffff00000000ULL};
              c.n.init(n);
              c.scalar_bits = 256; c.glv = false; c.tai = true; c.p256 = true; return c; }(),
+        // Baby JubJub (specs/baby_jubjub.py): n = l of 251 bits, a = 1, cofactor 8; neg_a is unused (its kernels carry a = 1 themselves)
+        [] { TeCurveHost c{}; c.id = 5;
+             const uint64_t n[4] = {0x677297dc392126f1ULL, 0xab3eedb83920ee0aULL, 0x370a08b6d0302b0bULL, 0x060c89ce5c263405ULL};
+             c.n.init(n);
+             const uint64_t d[4] = {0x736c2b06fb281473ULL, 0x2498beee8e01a829ULL, 0x7a5fd2dee7844661ULL, 0x1575bd81821016c0ULL};
+             std::memcpy(c.d, d, 32); c.scalar_bits = 251; c.glv = false; c.tai = true; c.bjj = true; return c; }(),
     };
-    return id >= 0 && id <= 4 ? &curves[id] : nullptr;
+    return id >= 0 && id <= 5 ? &curves[id] : nullptr;
 }
 // the base field of a curve of the table
-inline const Mod256& te_field(const TeCurveHost& c) { return c.ed25519 ? mod_p25519() : c.p256 ? mod_p256() : mod_p(); }
+inline const Mod256& te_field(const TeCurveHost& c) {
+    return c.ed25519 ? mod_p25519() : c.p256 ? mod_p256() : c.bjj ? mod_pbn254() : mod_p();
+}
 
 // ---------------------------------------------------------------- GLV decomposition (dot_ring/curve/glv.py:57-160)
 // k = k1 + k2*lambda (mod n) with |k1|, |k2| < 2^128, from the lattice basis v1 = (a1, b1), v2 = (a2, -a1) the reference
@@ -587,7 +605,10 @@ inline void vrf_challenge(const VrfSuite& su, const Bytes& transcript, const uin
 }
 
 // try-and-increment hash-to-curve, host half (dot_ring/curve/point.py:252-296): candidate `counter` of a message is the
-// first 32 squeezed bytes of suite_id || 0x60 || LE64(len) || data || counter — read by the device as a compressed point
+// first 32 squeezed bytes of suite_id || 0x60 || LE64(len) || data || counter — read by the device as a compressed point.
+// The reference then shaves the bits of byte 31 above the field's bit length and, on a twisted Edwards curve, puts the sign bit (bit
+// 7) back (point.py:282-287).  For the 255- and 256-bit fields nothing is shaved; Baby JubJub's 254-bit field loses bit 6 (bit 254).
+// (P-256, the short Weierstrass case, shaves nothing either: encode_to_curve_msgs appends its flag byte.)
 inline void tai_candidate(const VrfSuite& su, const uint8_t* data, size_t len, unsigned counter, uint8_t out[32]) {
     Bytes t = su.suite_id;
     put8(t, 0x60);                                   // HASH_TO_CURVE
@@ -595,6 +616,11 @@ inline void tai_candidate(const VrfSuite& su, const uint8_t* data, size_t len, u
     put(t, data, len);
     put8(t, (uint8_t)counter);
     vrf_squeeze(su.xof, t.data(), t.size(), out, 32);
+    const unsigned shave = 256 - te_field(*su.cv).bits();
+    if (shave && !su.cv->p256 && !su.cv->sw) {
+        const uint8_t sign = out[31] & 0x80;
+        out[31] = (uint8_t)((out[31] & ((1u << (8 - shave)) - 1)) | sign);
+    }
 }
 
 // curve.py:110-185 hash_to_field(msg, 2): two field elements, 32-byte little-endian each

@@ -7,6 +7,8 @@ Mirrors (names, argument meaning, error behaviour) the parts of the reference th
                                                 try-and-increment; the kernels compute on its twisted Edwards image
   dot_ring/curve/specs/p256.py                  P256 (= P256_TAI): NIST P-256, its own field, 33-byte codec with a SEC1 fallback,
                                                 try-and-increment with SHA-256; kernels of their own (DR_CURVE_P256)
+  dot_ring/curve/specs/baby_jubjub.py           BabyJubJub: a = 1 over the BN254 scalar field, cofactor 8, try-and-increment with
+                                                SHA-512 (candidates masked to the field's 254 bits); kernels of their own (DR_CURVE_BABYJUBJUB)
   dot_ring/curve/point.py:150-214               compressed codec
   dot_ring/curve/twisted_edwards/*              affine law, Elligator2 encode_to_curve
   dot_ring/curve/curve.py:56-67,110-237,384-401 valid_point, hash_to_field, key derivation
@@ -80,6 +82,29 @@ def _sqrt_5mod8(v: int, p: int) -> int:
     return r
 
 
+def _sqrt_tonelli_shanks(v: int, p: int) -> int:
+    """a square root mod p by Tonelli-Shanks (the reference's curve.mod_sqrt; Baby JubJub's field, p - 1 = Q 2^28), host big-int code"""
+    v %= p
+    if v == 0:
+        return 0
+    if pow(v, (p - 1) // 2, p) != 1:
+        raise ValueError("No square root exists")
+    q, s = p - 1, 0
+    while q % 2 == 0:
+        q, s = q // 2, s + 1
+    z = 2
+    while pow(z, (p - 1) // 2, p) != p - 1:
+        z += 1
+    m, c, t, r = s, pow(z, q, p), pow(v, q, p), pow(v, (q + 1) // 2, p)
+    while t != 1:
+        i, t2 = 1, t * t % p
+        while t2 != 1:
+            i, t2 = i + 1, t2 * t2 % p
+        b = pow(c, 1 << (m - i - 1), p)
+        m, c, t, r = i, b * b % p, t * b * b % p, r * b % p
+    return r
+
+
 class BandersnatchCurve:
     def __init__(self, params: SuiteParams):
         self.params = params
@@ -112,7 +137,9 @@ class BandersnatchCurve:
             if r * r % p != val % p:
                 raise ValueError("No square root exists")
             return r
-        return _sqrt_5mod8(val % p, p)
+        if p % 8 == 5:                          # Ed25519's field
+            return _sqrt_5mod8(val % p, p)
+        return _sqrt_tonelli_shanks(val, p)     # Baby JubJub's
 
     def is_square(self, val: int) -> bool:
         p = self.params.field_modulus
@@ -860,3 +887,26 @@ _P256_PARAMS = SuiteParams(
 P256_TAI = CurveVariant("P256_TAI", BandersnatchCurve(_P256_PARAMS), type("P256_TAIPoint", (P256Point,), {"__slots__": ()}))
 P256_TAI.point_type.curve = P256_TAI.curve
 P256 = P256_TAI
+
+# dot_ring/curve/specs/baby_jubjub.py: a = 1 over the BN254 scalar field, cofactor 8, try-and-increment with SHA-512 (the candidates lose
+# bit 254, as the reference masks them to the field's bit length).  It carries all three auxiliary points, but RingProofParams refuses
+# it as the reference does: the 2048-th root of unity of the ring proofs is not one mod this p.  Every group operation runs on the Baby
+# JubJub kernels (DR_CURVE_BABYJUBJUB).
+BabyJubJub = _suite(
+    "BabyJubJub", b"BabyJubJub-SHA512-TAI-v1", False,
+    (15549380791300914366206471199568039679131690710803662429646809536753521087193,
+     15218614024055502695611547593111691164731001864276292210438920202280814188379),
+    (6402374321243162085389111671722843560682527921646684137786768606010797479351,
+     9735581299071570006712034490635195155689931359428941496570758703259384062170),
+    (11167490195257431015694161063225325511805242064780376648595733691987293447528,
+     18403369502642103292159933062507105566469227524991433735553439433605496057425),
+    field_modulus=21888242871839275222246405745257275088548364400416034343698204186575808495617,
+    subgroup_order=2736030358979909402780800718157159386076813972158567259200215660948447373041,
+    cofactor=8,
+    a=1,
+    d=9706598848417545097372247223557719406784115219466060233080913168975159366771,
+    generator=(19698561148652590122159747500897617769866003486955115824547446575314762165298,
+               19298250018296453272277890825869354524455968081175474282777126169995084727839),
+    curve_id=_native.CURVE_BABYJUBJUB,
+    e2c="tai",
+)

@@ -131,6 +131,16 @@ enum { DR_CURVE_ED25519 = 3 };
  * dr_pedersen_prove_batch and dr_pedersen_verify_batch (proofs 81 / 98 / 196 bytes; the suite's xof is 2).  Every call runs on the
  * kernels.  The ring prover, the Ring-VRF calls, dr_ietf_verify_batch, dr_hash_to_field_batch and the dr_bsn_* calls refuse it. */
 enum { DR_CURVE_P256 = 4 };
+/* DR_CURVE_BABYJUBJUB: Baby JubJub (dot_ring/curve/specs/baby_jubjub.py: a = 1, cofactor 8, n = l of 251 bits, try-and-increment with
+ * SHA-512), over the BN254 scalar field (254 bits) — its own kernels (csrc/kernels_bjj.hip.h, field csrc/fbn254.hip.h).  Raw points are
+ * x || y little-endian, coordinates below p; encodings are 32 bytes, y with bit 255 = (x > p - x); y >= p (so any encoding with bit 254
+ * set) is rejected.  Try-and-increment candidates have bit 254 cleared and the sign bit kept, as the reference masks them.  Scalars are
+ * reduced mod l on the device.  Accepted by dr_te_scalar_mul_batch, dr_te_msm, dr_te_msm_groups, dr_te_decode_points (canonical y, a
+ * root, not the identity, no torsion component), dr_te_fixed_base_msm_groups (through the variable-base grouped kernel),
+ * dr_encode_to_curve_batch, dr_ietf_prove_batch, dr_pedersen_prove_batch and dr_pedersen_verify_batch (proofs 80 / 96 / 192 bytes).
+ * Every call runs on the kernels (no host route).  The ring prover, the Ring-VRF calls, dr_ietf_verify_batch and the dr_bsn_* calls
+ * refuse it. */
+enum { DR_CURVE_BABYJUBJUB = 5 };
 DR_API int dr_te_scalar_mul_batch(dr_ctx *ctx, int curve, const uint8_t *pts_xy, const uint8_t *scalars, size_t n, uint8_t *out_xy);
 DR_API int dr_te_msm(dr_ctx *ctx, int curve, const uint8_t *pts_xy, const uint8_t *scalars, size_t n, uint8_t out_xy[64]);
 DR_API int dr_te_msm_groups(dr_ctx *ctx, int curve, const uint8_t *pts_xy, const uint8_t *scalars, size_t groups, size_t m, uint8_t *out_xy);
@@ -172,6 +182,16 @@ DR_API int dr_p256_decode_points(dr_ctx *ctx, int check, const uint8_t *enc /* n
  * square, bit 1 a > p - a, bit 2 a is odd. */
 DR_API int dr_p256_field_ops_selftest(dr_ctx *ctx, const int32_t *a_limbs /* n*9 */, const int32_t *b_limbs /* n*9 */, size_t n,
                                       uint8_t *out /* n*384 */, uint8_t *flags /* n */);
+/* Baby JubJub point decoding with the prime-order check (check = 1: as dr_te_decode_points for DR_CURVE_BABYJUBJUB) or the codec
+ * alone (check = 0: y < p and a root; (0, 1) and (0, p - 1) decode whatever the sign bit).  ok[i] = 1 when accepted; out_xy[i] is
+ * then x || y, otherwise 64 zero bytes. */
+DR_API int dr_bjj_decode_points(dr_ctx *ctx, int check, const uint8_t *enc /* n*32 */, size_t n, uint8_t *out_xy /* n*64 */, uint8_t *ok /* n */);
+/* Diagnostic: the device's arithmetic in the BN254 scalar field (csrc/fbn254.hip.h) on RAW limb images — 9 signed 32-bit limbs each,
+ * value sum l[i] 2^(29 i), standing for value * 2^-261 mod p (Montgomery form).  out: n x 12 x 32 bytes of canonical little-endian
+ * results: a b, a^2, a + b, a - b, -a, carry(a), a b + b a (fused), a^-1 (0 for 0), sqrt(a) or 0, a, a b through the LDS word form,
+ * a through unpack(pack(a)).  flags[i]: bit 0 a is a square, bit 2 a > p - a. */
+DR_API int dr_bjj_field_ops_selftest(dr_ctx *ctx, const int32_t *a_limbs /* n*9 */, const int32_t *b_limbs /* n*9 */, size_t n,
+                                     uint8_t *out /* n*384 */, uint8_t *flags /* n */);
 
 /* square root in the Bandersnatch base field; DR_ERR_NOTSQUARE if none exists. Host-side, no ctx. */
 DR_API int dr_fr_sqrt(const uint8_t in[32], uint8_t out[32]);
@@ -364,8 +384,8 @@ typedef struct dr_vrf_suite {
                                        squeeze, the P-256 suite); other values are refused */
     uint8_t generator_xy[64];       /* group generator, x||y little-endian */
     uint8_t blinding_base_xy[64];   /* Pedersen blinding base (bandersnatch.py:89-102) */
-    int curve;                      /* DR_CURVE_BANDERSNATCH (Elligator 2 hash-to-curve), DR_CURVE_JUBJUB, DR_CURVE_BANDERSNATCH_SW or
-                                       DR_CURVE_ED25519 or DR_CURVE_P256 (try-and-increment; for the SW suite and P-256 generator and
+    int curve;                      /* DR_CURVE_BANDERSNATCH (Elligator 2 hash-to-curve), DR_CURVE_JUBJUB, DR_CURVE_BANDERSNATCH_SW,
+                                       DR_CURVE_ED25519, DR_CURVE_P256 or DR_CURVE_BABYJUBJUB (try-and-increment; for the SW suite and P-256 generator and
                                        blinding base are SW affine) */
 } dr_vrf_suite;
 
