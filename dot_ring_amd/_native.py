@@ -553,59 +553,48 @@ class Context:
         _check(lib().dr_fr_ops_selftest(self.handle, a, b, n, out, flags))
         return out.raw[: 384 * n], flags.raw[:n]
 
-    def fe25519_ops_selftest(self, a_limbs: bytes, b_limbs: bytes):
-        """dr_fe25519_ops_selftest: (n x 11 x 32 result bytes, n flag bytes) for n pairs of raw 9-limb images (9 little-endian int32 each)."""
+    def _limb_selftest(self, fn, records: int, a_limbs: bytes, b_limbs: bytes):
+        """(n x records x 32 result bytes, n flag bytes) of one native suite's field selftest on n pairs of raw 9-limb images."""
         n = len(a_limbs) // 36
         if len(a_limbs) != 36 * n or len(b_limbs) != 36 * n:
             raise ValueError("operands are 9 int32 limbs each")
-        out, flags = ctypes.create_string_buffer(max(1, 352 * n)), ctypes.create_string_buffer(max(1, n))
-        _check(lib().dr_fe25519_ops_selftest(self.handle, a_limbs, b_limbs, n, out, flags))
-        return out.raw[: 352 * n], flags.raw[:n]
+        rec = 32 * records
+        out, flags = ctypes.create_string_buffer(max(1, rec * n)), ctypes.create_string_buffer(max(1, n))
+        _check(fn(self.handle, a_limbs, b_limbs, n, out, flags))
+        return out.raw[: rec * n], flags.raw[:n]
+
+    def fe25519_ops_selftest(self, a_limbs: bytes, b_limbs: bytes):
+        """dr_fe25519_ops_selftest: (n x 11 x 32 result bytes, n flag bytes) for n pairs of raw 9-limb images (9 little-endian int32 each)."""
+        return self._limb_selftest(lib().dr_fe25519_ops_selftest, 11, a_limbs, b_limbs)
 
     def p256_field_ops_selftest(self, a_limbs: bytes, b_limbs: bytes):
         """dr_p256_field_ops_selftest: (n x 12 x 32 result bytes, n flag bytes) for n pairs of raw 9-limb Montgomery images."""
-        n = len(a_limbs) // 36
-        if len(a_limbs) != 36 * n or len(b_limbs) != 36 * n:
-            raise ValueError("operands are 9 int32 limbs each")
-        out, flags = ctypes.create_string_buffer(max(1, 384 * n)), ctypes.create_string_buffer(max(1, n))
-        _check(lib().dr_p256_field_ops_selftest(self.handle, a_limbs, b_limbs, n, out, flags))
-        return out.raw[: 384 * n], flags.raw[:n]
+        return self._limb_selftest(lib().dr_p256_field_ops_selftest, 12, a_limbs, b_limbs)
 
     def bjj_field_ops_selftest(self, a_limbs: bytes, b_limbs: bytes):
         """dr_bjj_field_ops_selftest: (n x 12 x 32 result bytes, n flag bytes) for n pairs of raw 9-limb Montgomery images."""
-        n = len(a_limbs) // 36
-        if len(a_limbs) != 36 * n or len(b_limbs) != 36 * n:
-            raise ValueError("operands are 9 int32 limbs each")
-        out, flags = ctypes.create_string_buffer(max(1, 384 * n)), ctypes.create_string_buffer(max(1, n))
-        _check(lib().dr_bjj_field_ops_selftest(self.handle, a_limbs, b_limbs, n, out, flags))
-        return out.raw[: 384 * n], flags.raw[:n]
+        return self._limb_selftest(lib().dr_bjj_field_ops_selftest, 12, a_limbs, b_limbs)
+
+    def _decode_points(self, fn, width: int, enc: bytes, check: bool):
+        """(x||y bytes, flags) of one native suite's decoder on len(enc)/width encodings."""
+        if len(enc) % width:
+            raise ValueError(f"compressed points are {width} bytes each")
+        count = len(enc) // width
+        out, ok = ctypes.create_string_buffer(max(1, 64 * count)), ctypes.create_string_buffer(max(1, count))
+        _check(fn(self.handle, 1 if check else 0, enc, count, out, ok))
+        return out.raw[: 64 * count], ok.raw[:count]
 
     def bjj_decode_points(self, enc: bytes, check: bool = True):
         """dr_bjj_decode_points: (x||y bytes, flags) for len(enc)/32 encodings, with or without the prime-order check."""
-        if len(enc) % 32:
-            raise ValueError("compressed points are 32 bytes each")
-        count = len(enc) // 32
-        out, ok = ctypes.create_string_buffer(max(1, 64 * count)), ctypes.create_string_buffer(max(1, count))
-        _check(lib().dr_bjj_decode_points(self.handle, 1 if check else 0, enc, count, out, ok))
-        return out.raw[: 64 * count], ok.raw[:count]
+        return self._decode_points(lib().dr_bjj_decode_points, 32, enc, check)
 
     def p256_decode_points(self, enc: bytes, check: bool = True):
         """dr_p256_decode_points: (x||y bytes, flags) for len(enc)/33 encodings, with or without the identity check."""
-        if len(enc) % 33:
-            raise ValueError("compressed points are 33 bytes each")
-        count = len(enc) // 33
-        out, ok = ctypes.create_string_buffer(max(1, 64 * count)), ctypes.create_string_buffer(max(1, count))
-        _check(lib().dr_p256_decode_points(self.handle, 1 if check else 0, enc, count, out, ok))
-        return out.raw[: 64 * count], ok.raw[:count]
+        return self._decode_points(lib().dr_p256_decode_points, 33, enc, check)
 
     def ed25519_decode_points(self, enc: bytes, check: bool = True):
         """dr_ed25519_decode_points: (x||y bytes, flags) for len(enc)/32 encodings, with or without the prime-order check."""
-        if len(enc) % 32:
-            raise ValueError("compressed points are 32 bytes each")
-        count = len(enc) // 32
-        out, ok = ctypes.create_string_buffer(max(1, 64 * count)), ctypes.create_string_buffer(max(1, count))
-        _check(lib().dr_ed25519_decode_points(self.handle, 1 if check else 0, enc, count, out, ok))
-        return out.raw[: 64 * count], ok.raw[:count]
+        return self._decode_points(lib().dr_ed25519_decode_points, 32, enc, check)
 
     def fq_ops_selftest(self, records: bytes) -> bytes:
         """dr_fq_ops_selftest: n records of 64 little-endian int32 (op, four 14-limb operands) -> n records of 16 int32."""

@@ -371,7 +371,7 @@ int dr_prof_get(dr_ctx* ctx, const char* name, double* total_ms, int* launches) 
 // ------------------------------------------------------------------------------- seam A
 int te_scalar_mul_batch_dev(dr_ctx* ctx, int cv, const void* d_pts, const void* d_scalars, size_t n, void* d_out) {
     TRY(use_ctx(ctx));
-    if (cv == dr::CV_ED25519 || cv == dr::CV_P256 || cv == dr::CV_BABYJUBJUB)
+    if (drh::te_curve(cv) && drh::te_curve(cv)->native != drh::NativeSuite::none)
         return fail(DR_ERR_INVALID, "device-resident scalar multiplication serves the curves over the BLS12-381 scalar field");
     if (n == 0) return DR_OK;
     if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
@@ -488,248 +488,36 @@ int sw_boundary(dr_ctx* ctx, const uint8_t* sw_in, size_t n_in, uint8_t* sw_out,
 }
 }  // namespace
 
-// ---- Ed25519 (kernels_ed25519.hip.h).  Every call runs on the kernels: there is no host route for this curve, and nothing here
-// touches the BLS12-381 field of the other curves.  Secrets pass through io_a / io_b / io_c only, which ctx_wipe_scratch covers.
+// ---- the native suites: Ed25519 (kernels_ed25519.hip.h), P-256 (kernels_p256.hip.h) and Baby JubJub (kernels_bjj.hip.h).  Every call
+// runs on the kernels: there is no host route for these curves, and nothing here touches the BLS12-381 field of the other curves.  Secrets
+// pass through io_a / io_b / io_c only, which ctx_wipe_scratch covers.  Points are affine x || y.  Each suite is one description below (its
+// kernels, launch names, base field, identity and encoding widths); every operation is one template over it.
 namespace {
-int check_ed_elems(const uint8_t* p, size_t count, const char* what) {
-    for (size_t i = 0; i < count; i++) {
-        uint64_t v[4];
-        drh::load_le32(p + 32 * i, v);
-        if (drh::Mod256::geq(v, drh::mod_p25519().m)) return fail(DR_ERR_INVALID, std::string(what) + " coordinate is not a canonical field element");
-    }
-    return DR_OK;
-}
-int ed_scalar_mul_batch(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy) {
-    if (n == 0) return DR_OK;
-    if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
-    if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
-    TRY(check_ed_elems(pts_xy, 2 * n, "point"));
-    TRY(ctx->io_a.reserve(n * 64));
-    TRY(ctx->io_b.reserve(n * 32));
-    TRY(ctx->io_c.reserve(n * 64));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, pts_xy, n * 64, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->io_b.p, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    TRY(launch(ctx, "k_ed_scalar_mul", [&] {
-        hipLaunchKernelGGL(dr::k_ed_scalar_mul, dim3(div_up(n, dr::ED_BLOCK)), dim3(dr::ED_BLOCK), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
-                           ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
-    }));
-    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_c.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->prof) TRY(prof_collect(ctx));
-    return DR_OK;
-}
-int ed_msm_groups(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy) {
-    if (groups == 0) return DR_OK;
-    if (m == 0 || m > 64) return fail(DR_ERR_INVALID, "group size must be in 1..64");
-    if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
-    const size_t n = groups * m;
-    if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
-    TRY(check_ed_elems(pts_xy, 2 * n, "point"));
-    uint32_t mpad = 1;
-    while (mpad < m) mpad <<= 1;
-    TRY(ctx->io_a.reserve(n * 64));
-    TRY(ctx->io_b.reserve(n * 32));
-    TRY(ctx->io_c.reserve(groups * 64));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, pts_xy, n * 64, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->io_b.p, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    const uint32_t per_block = dr::ED_BLOCK / mpad;
-    TRY(launch(ctx, "k_ed_msm_groups", [&] {
-        hipLaunchKernelGGL(dr::k_ed_msm_groups, dim3(div_up(groups, per_block)), dim3(dr::ED_BLOCK), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
-                           ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)groups, (uint32_t)m, mpad);
-    }));
-    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_c.p, groups * 64, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->prof) TRY(prof_collect(ctx));
-    return DR_OK;
-}
-// fixed bases through the variable-base grouped kernel (each group's terms are the m bases): the same fixed schedule for the secret
-// scalars, no window table
-int ed_fixed_base_groups(dr_ctx* ctx, const uint8_t* bases_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy) {
-    if (groups == 0) return DR_OK;
-    if (m == 0 || m > 4) return fail(DR_ERR_INVALID, "1..4 fixed bases per group");
-    if (!bases_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
-    if (groups * m >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
-    std::vector<uint8_t> pts(groups * m * 64);
-    for (size_t g = 0; g < groups; g++) std::memcpy(pts.data() + 64 * m * g, bases_xy, 64 * m);
-    return ed_msm_groups(ctx, pts.data(), scalars, groups, m, out_xy);
-}
-// one MSM: groups of 64 terms in one launch, then the partial sums with scalar 1, 64 at a time, until one is left
-int ed_msm(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t out_xy[64]) {
-    if (n == 0) {
-        std::memset(out_xy, 0, 64);
-        out_xy[32] = 1;
-        return DR_OK;
-    }
-    if (!pts_xy || !scalars) return fail(DR_ERR_INVALID, "null buffer");
-    std::vector<uint8_t> pts(pts_xy, pts_xy + n * 64), sc(scalars, scalars + n * 32), part;
-    for (;;) {
-        if (n <= 64) return ed_msm_groups(ctx, pts.data(), sc.data(), 1, n, out_xy);
-        const size_t parts = (n + 63) / 64;
-        pts.resize(parts * 64 * 64, 0);
-        sc.resize(parts * 64 * 32, 0);
-        for (size_t i = n; i < parts * 64; i++) pts[64 * i + 32] = 1;         // padding: 0 * (0, 1)
-        part.resize(parts * 64);
-        TRY(ed_msm_groups(ctx, pts.data(), sc.data(), parts, 64, part.data()));
-        explicit_bzero(sc.data(), sc.size());
-        pts.swap(part);
-        n = parts;
-        sc.assign(n * 32, 0);
-        for (size_t i = 0; i < n; i++) sc[32 * i] = 1;
-    }
-}
-int ed_decode_points(dr_ctx* ctx, int mode, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
-    if (n == 0) return DR_OK;
-    if (!enc || !out_xy || !ok) return fail(DR_ERR_INVALID, "null buffer");
-    if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
-    TRY(ctx->io_a.reserve(n * 32));
-    TRY(ctx->io_b.reserve(n * 64));
-    TRY(ctx->io_c.reserve(n * 4));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, enc, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    TRY(launch(ctx, "k_ed_decode_points", [&] {
-        const dim3 grid(div_up(n, dr::ED_BLOCK)), block(dr::ED_BLOCK);
-        if (mode == dr::ED_DEC_TAI)
-            hipLaunchKernelGGL(dr::k_ed_decode_points<dr::ED_DEC_TAI>, grid, block, 0, ctx->stream, ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(),
-                               ctx->io_c.as<uint32_t>(), (uint32_t)n);
-        else if (mode == dr::ED_DEC_CHECK)
-            hipLaunchKernelGGL(dr::k_ed_decode_points<dr::ED_DEC_CHECK>, grid, block, 0, ctx->stream, ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(),
-                               ctx->io_c.as<uint32_t>(), (uint32_t)n);
-        else
-            hipLaunchKernelGGL(dr::k_ed_decode_points<dr::ED_DEC_CODEC>, grid, block, 0, ctx->stream, ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(),
-                               ctx->io_c.as<uint32_t>(), (uint32_t)n);
-    }));
-    std::vector<uint32_t> flags(n);
-    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_b.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(flags.data(), ctx->io_c.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->prof) TRY(prof_collect(ctx));
-    for (size_t i = 0; i < n; i++) ok[i] = flags[i] ? 1 : 0;
-    return DR_OK;
-}
-}  // namespace
-
-// ---- P-256 (kernels_p256.hip.h).  As for Ed25519: every call runs on the kernels, no host route, and secrets pass through io_a /
-// io_b / io_c only, which ctx_wipe_scratch covers.  Points are affine x || y; 64 zero bytes are the identity.
-namespace {
-int check_p256_elems(const uint8_t* p, size_t count, const char* what) {
-    for (size_t i = 0; i < count; i++) {
-        uint64_t v[4];
-        drh::load_le32(p + 32 * i, v);
-        if (drh::Mod256::geq(v, drh::mod_p256().m)) return fail(DR_ERR_INVALID, std::string(what) + " coordinate is not a canonical field element");
-    }
-    return DR_OK;
-}
-int p256_scalar_mul_batch(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy) {
-    if (n == 0) return DR_OK;
-    if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
-    if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
-    TRY(check_p256_elems(pts_xy, 2 * n, "point"));
-    TRY(ctx->io_a.reserve(n * 64));
-    TRY(ctx->io_b.reserve(n * 32));
-    TRY(ctx->io_c.reserve(n * 64));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, pts_xy, n * 64, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->io_b.p, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    TRY(launch(ctx, "k_p256_scalar_mul", [&] {
-        hipLaunchKernelGGL(dr::k_p256_scalar_mul, dim3(div_up(n, dr::P256_BLOCK)), dim3(dr::P256_BLOCK), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
-                           ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
-    }));
-    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_c.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->prof) TRY(prof_collect(ctx));
-    return DR_OK;
-}
-int p256_msm_groups(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy) {
-    if (groups == 0) return DR_OK;
-    if (m == 0 || m > 64) return fail(DR_ERR_INVALID, "group size must be in 1..64");
-    if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
-    const size_t n = groups * m;
-    if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
-    TRY(check_p256_elems(pts_xy, 2 * n, "point"));
-    uint32_t mpad = 1;
-    while (mpad < m) mpad <<= 1;
-    TRY(ctx->io_a.reserve(n * 64));
-    TRY(ctx->io_b.reserve(n * 32));
-    TRY(ctx->io_c.reserve(groups * 64));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, pts_xy, n * 64, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->io_b.p, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    const uint32_t per_block = dr::P256_BLOCK / mpad;
-    TRY(launch(ctx, "k_p256_msm_groups", [&] {
-        hipLaunchKernelGGL(dr::k_p256_msm_groups, dim3(div_up(groups, per_block)), dim3(dr::P256_BLOCK), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
-                           ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)groups, (uint32_t)m, mpad);
-    }));
-    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_c.p, groups * 64, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->prof) TRY(prof_collect(ctx));
-    return DR_OK;
-}
-// fixed bases through the variable-base grouped kernel, as for Ed25519 (no window table)
-int p256_fixed_base_groups(dr_ctx* ctx, const uint8_t* bases_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy) {
-    if (groups == 0) return DR_OK;
-    if (m == 0 || m > 4) return fail(DR_ERR_INVALID, "1..4 fixed bases per group");
-    if (!bases_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
-    if (groups * m >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
-    std::vector<uint8_t> pts(groups * m * 64);
-    for (size_t g = 0; g < groups; g++) std::memcpy(pts.data() + 64 * m * g, bases_xy, 64 * m);
-    return p256_msm_groups(ctx, pts.data(), scalars, groups, m, out_xy);
-}
-// one MSM: groups of 64 terms in one launch, then the partial sums with scalar 1, 64 at a time, until one is left (padding: 0 * O)
-int p256_msm(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t out_xy[64]) {
-    if (n == 0) {
-        std::memset(out_xy, 0, 64);
-        return DR_OK;
-    }
-    if (!pts_xy || !scalars) return fail(DR_ERR_INVALID, "null buffer");
-    std::vector<uint8_t> pts(pts_xy, pts_xy + n * 64), sc(scalars, scalars + n * 32), part;
-    for (;;) {
-        if (n <= 64) return p256_msm_groups(ctx, pts.data(), sc.data(), 1, n, out_xy);
-        const size_t parts = (n + 63) / 64;
-        pts.resize(parts * 64 * 64, 0);
-        sc.resize(parts * 64 * 32, 0);
-        part.resize(parts * 64);
-        TRY(p256_msm_groups(ctx, pts.data(), sc.data(), parts, 64, part.data()));
-        explicit_bzero(sc.data(), sc.size());
-        pts.swap(part);
-        n = parts;
-        sc.assign(n * 32, 0);
-        for (size_t i = 0; i < n; i++) sc[32 * i] = 1;
-    }
-}
-// n x 33-byte encodings, padded to 36 bytes for the kernel
-int p256_decode_points(dr_ctx* ctx, int mode, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
-    if (n == 0) return DR_OK;
-    if (!enc || !out_xy || !ok) return fail(DR_ERR_INVALID, "null buffer");
-    if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
-    std::vector<uint8_t> rec(n * 36, 0);
-    for (size_t i = 0; i < n; i++) std::memcpy(rec.data() + 36 * i, enc + 33 * i, 33);
-    TRY(ctx->io_a.reserve(n * 36));
-    TRY(ctx->io_b.reserve(n * 64));
-    TRY(ctx->io_c.reserve(n * 4));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, rec.data(), n * 36, hipMemcpyHostToDevice, ctx->stream));
-    TRY(launch(ctx, "k_p256_decode_points", [&] {
-        const dim3 grid(div_up(n, dr::P256_BLOCK)), block(dr::P256_BLOCK);
-        if (mode == dr::P256_DEC_TAI)
-            hipLaunchKernelGGL(dr::k_p256_decode_points<dr::P256_DEC_TAI>, grid, block, 0, ctx->stream, ctx->io_a.as<uint32_t>(),
-                               ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
-        else if (mode == dr::P256_DEC_CHECK)
-            hipLaunchKernelGGL(dr::k_p256_decode_points<dr::P256_DEC_CHECK>, grid, block, 0, ctx->stream, ctx->io_a.as<uint32_t>(),
-                               ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
-        else
-            hipLaunchKernelGGL(dr::k_p256_decode_points<dr::P256_DEC_CODEC>, grid, block, 0, ctx->stream, ctx->io_a.as<uint32_t>(),
-                               ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
-    }));
-    std::vector<uint32_t> flags(n);
-    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_b.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(flags.data(), ctx->io_c.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->prof) TRY(prof_collect(ctx));
-    for (size_t i = 0; i < n; i++) ok[i] = flags[i] ? 1 : 0;
-    return DR_OK;
-}
-}  // namespace
-
-// ---- Baby JubJub (kernels_bjj.hip.h).  As for Ed25519: every call runs on the kernels, no host route, nothing here touches the
-// BLS12-381 field, and secrets pass through io_a / io_b / io_c only.  The square-root tables (BjjConsts) are built on the host once
-// per process and copied to the device the first time a context decodes a point.
-namespace {
+struct NoConsts { static int consts_ready(dr_ctx*) { return DR_OK; } };   // the suites with no device constants to load first
+struct Ed25519Suite : NoConsts {
+    static constexpr auto scalar_mul = dr::k_ed_scalar_mul;
+    static constexpr auto msm_groups = dr::k_ed_msm_groups;
+    static constexpr auto dec_tai = dr::k_ed_decode_points<dr::ED_DEC_TAI>, dec_check = dr::k_ed_decode_points<dr::ED_DEC_CHECK>,
+                          dec_codec = dr::k_ed_decode_points<dr::ED_DEC_CODEC>;
+    static constexpr auto field_selftest = dr::k_fe25519_selftest;
+    static constexpr int block = dr::ED_BLOCK, selftest_records = dr::FE_SELFTEST_RECORDS;
+    static constexpr const char *name = "Ed25519", *k_scalar_mul = "k_ed_scalar_mul", *k_msm_groups = "k_ed_msm_groups", *k_decode = "k_ed_decode_points";
+    static const drh::Mod256& field() { return drh::mod_p25519(); }
+    static constexpr size_t identity_y = 1, enc_bytes = 32, rec_bytes = 32;   // identity (0, identity_y); encoding, decoder record
+};
+struct P256Suite : NoConsts {
+    static constexpr auto scalar_mul = dr::k_p256_scalar_mul;
+    static constexpr auto msm_groups = dr::k_p256_msm_groups;
+    static constexpr auto dec_tai = dr::k_p256_decode_points<dr::P256_DEC_TAI>, dec_check = dr::k_p256_decode_points<dr::P256_DEC_CHECK>,
+                          dec_codec = dr::k_p256_decode_points<dr::P256_DEC_CODEC>;
+    static constexpr auto field_selftest = dr::k_p256_field_selftest;
+    static constexpr int block = dr::P256_BLOCK, selftest_records = dr::P256_SELFTEST_RECORDS;
+    static constexpr const char *name = "P-256", *k_scalar_mul = "k_p256_scalar_mul", *k_msm_groups = "k_p256_msm_groups", *k_decode = "k_p256_decode_points";
+    static const drh::Mod256& field() { return drh::mod_p256(); }
+    static constexpr size_t identity_y = 0, enc_bytes = 33, rec_bytes = 36;   // 64 zero bytes are the identity
+};
+// Baby JubJub's square-root tables (BjjConsts) are built on the host once per process and copied to the device the first time a context
+// decodes a point or runs the field selftest
 int bjj_consts_build(dr::BjjConsts& h) {
     const drh::Mod256& F = drh::mod_pbn254();
     static const uint64_t R261[4] = {0x2fd4e1568fffff57ULL, 0x75bba827a494b01aULL, 0x5301fa84819caa80ULL, 0x0dc83629563d4475ULL};   // 2^261 mod p
@@ -797,116 +585,124 @@ int bjj_consts_ready(dr_ctx* ctx) {
     ctx->bjj_ready = true;
     return DR_OK;
 }
-int check_bjj_elems(const uint8_t* p, size_t count, const char* what) {
-    for (size_t i = 0; i < count; i++) {
-        uint64_t v[4];
-        drh::load_le32(p + 32 * i, v);
-        if (drh::Mod256::geq(v, drh::mod_pbn254().m)) return fail(DR_ERR_INVALID, std::string(what) + " coordinate is not a canonical field element");
+struct BjjSuite {
+    static constexpr auto scalar_mul = dr::k_bjj_scalar_mul;
+    static constexpr auto msm_groups = dr::k_bjj_msm_groups;
+    static constexpr auto dec_tai = dr::k_bjj_decode_points<dr::BJJ_DEC_TAI>, dec_check = dr::k_bjj_decode_points<dr::BJJ_DEC_CHECK>,
+                          dec_codec = dr::k_bjj_decode_points<dr::BJJ_DEC_CODEC>;
+    static constexpr auto field_selftest = dr::k_bjj_field_selftest;
+    static constexpr int block = dr::BJJ_BLOCK, selftest_records = dr::BJJ_SELFTEST_RECORDS;
+    static constexpr const char *name = "Baby JubJub", *k_scalar_mul = "k_bjj_scalar_mul", *k_msm_groups = "k_bjj_msm_groups", *k_decode = "k_bjj_decode_points";
+    static const drh::Mod256& field() { return drh::mod_pbn254(); }
+    static constexpr size_t identity_y = 1, enc_bytes = 32, rec_bytes = 32;
+    static int consts_ready(dr_ctx* ctx) { return bjj_consts_ready(ctx); }
+};
+// rc = f(S{}) for the description S of curve cv's native suite; false, f not called, for every other curve and an unknown id
+template <class F>
+bool on_native(int cv, int& rc, F&& f) {
+    switch (drh::te_curve(cv) ? drh::te_curve(cv)->native : drh::NativeSuite::none) {
+        case drh::NativeSuite::ed25519: rc = f(Ed25519Suite{}); return true;
+        case drh::NativeSuite::p256: rc = f(P256Suite{}); return true;
+        case drh::NativeSuite::bjj: rc = f(BjjSuite{}); return true;
+        default: return false;
     }
-    return DR_OK;
 }
-int bjj_scalar_mul_batch(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy) {
-    if (n == 0) return DR_OK;
+// n points, their coordinates checked against S's field, and n scalars to io_a / io_b, one launch (`go`, profiled as `name`) into io_c,
+// n_out points back
+template <class S, class F>
+int native_run(S, dr_ctx* ctx, const char* name, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, size_t n_out, uint8_t* out_xy, F&& go) {
     if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
     if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
-    TRY(check_bjj_elems(pts_xy, 2 * n, "point"));
+    for (size_t i = 0; i < 2 * n; i++) {
+        uint64_t v[4];
+        drh::load_le32(pts_xy + 32 * i, v);
+        if (drh::Mod256::geq(v, S::field().m)) return fail(DR_ERR_INVALID, "point coordinate is not a canonical field element");
+    }
     TRY(ctx->io_a.reserve(n * 64));
     TRY(ctx->io_b.reserve(n * 32));
-    TRY(ctx->io_c.reserve(n * 64));
+    TRY(ctx->io_c.reserve(n_out * 64));
     HIP_TRY(hipMemcpyAsync(ctx->io_a.p, pts_xy, n * 64, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(ctx->io_b.p, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    TRY(launch(ctx, "k_bjj_scalar_mul", [&] {
-        hipLaunchKernelGGL(dr::k_bjj_scalar_mul, dim3(div_up(n, dr::BJJ_BLOCK)), dim3(dr::BJJ_BLOCK), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
-                           ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
-    }));
-    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_c.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
+    TRY(launch(ctx, name, go));
+    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_c.p, n_out * 64, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (ctx->prof) TRY(prof_collect(ctx));
     return DR_OK;
 }
-int bjj_msm_groups(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy) {
+template <class S>
+int native_scalar_mul_batch(S, dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy) {
+    if (n == 0) return DR_OK;
+    return native_run(S{}, ctx, S::k_scalar_mul, pts_xy, scalars, n, n, out_xy, [&] {
+        hipLaunchKernelGGL(S::scalar_mul, dim3(div_up(n, S::block)), dim3(S::block), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
+                           ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
+    });
+}
+template <class S>
+int native_msm_groups(S, dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy) {
     if (groups == 0) return DR_OK;
     if (m == 0 || m > 64) return fail(DR_ERR_INVALID, "group size must be in 1..64");
-    if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
-    const size_t n = groups * m;
-    if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
-    TRY(check_bjj_elems(pts_xy, 2 * n, "point"));
     uint32_t mpad = 1;
     while (mpad < m) mpad <<= 1;
-    TRY(ctx->io_a.reserve(n * 64));
-    TRY(ctx->io_b.reserve(n * 32));
-    TRY(ctx->io_c.reserve(groups * 64));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, pts_xy, n * 64, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->io_b.p, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    const uint32_t per_block = dr::BJJ_BLOCK / mpad;
-    TRY(launch(ctx, "k_bjj_msm_groups", [&] {
-        hipLaunchKernelGGL(dr::k_bjj_msm_groups, dim3(div_up(groups, per_block)), dim3(dr::BJJ_BLOCK), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
+    const uint32_t per_block = S::block / mpad;
+    return native_run(S{}, ctx, S::k_msm_groups, pts_xy, scalars, groups * m, groups, out_xy, [&] {
+        hipLaunchKernelGGL(S::msm_groups, dim3(div_up(groups, per_block)), dim3(S::block), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
                            ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)groups, (uint32_t)m, mpad);
-    }));
-    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_c.p, groups * 64, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->prof) TRY(prof_collect(ctx));
-    return DR_OK;
+    });
 }
-// fixed bases through the variable-base grouped kernel (each group's terms are the m bases), as for Ed25519
-int bjj_fixed_base_groups(dr_ctx* ctx, const uint8_t* bases_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy) {
-    if (groups == 0) return DR_OK;
-    if (m == 0 || m > 4) return fail(DR_ERR_INVALID, "1..4 fixed bases per group");
-    if (!bases_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
-    if (groups * m >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
+// fixed bases through the grouped kernel, each group's terms the m bases: no window table.  te_fixed_base_groups checked the arguments.
+template <class S>
+int native_fixed_base_groups(S, dr_ctx* ctx, const uint8_t* bases_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy) {
     std::vector<uint8_t> pts(groups * m * 64);
     for (size_t g = 0; g < groups; g++) std::memcpy(pts.data() + 64 * m * g, bases_xy, 64 * m);
-    return bjj_msm_groups(ctx, pts.data(), scalars, groups, m, out_xy);
+    return native_msm_groups(S{}, ctx, pts.data(), scalars, groups, m, out_xy);
 }
-// one MSM: groups of 64 terms in one launch, then the partial sums with scalar 1, 64 at a time, until one is left
-int bjj_msm(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t out_xy[64]) {
+// one MSM: groups of 64 terms in one launch, then the partial sums with scalar 1, 64 at a time, until one is left.  The host copy of
+// the scalars is wiped after every launch, a failed one included.
+template <class S>
+int native_msm(S, dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t out_xy[64]) {
     if (n == 0) {
         std::memset(out_xy, 0, 64);
-        out_xy[32] = 1;
+        out_xy[32] = (uint8_t)S::identity_y;
         return DR_OK;
     }
     if (!pts_xy || !scalars) return fail(DR_ERR_INVALID, "null buffer");
     std::vector<uint8_t> pts(pts_xy, pts_xy + n * 64), sc(scalars, scalars + n * 32), part;
     for (;;) {
-        if (n <= 64) {
-            const int rc = bjj_msm_groups(ctx, pts.data(), sc.data(), 1, n, out_xy);
-            explicit_bzero(sc.data(), sc.size());
-            return rc;
-        }
-        const size_t parts = (n + 63) / 64;
-        pts.resize(parts * 64 * 64, 0);
-        sc.resize(parts * 64 * 32, 0);
-        for (size_t i = n; i < parts * 64; i++) pts[64 * i + 32] = 1;         // padding: 0 * (0, 1)
+        const size_t parts = (n + 63) / 64, m = parts == 1 ? n : 64;          // the last level: one group of the n <= 64 left
+        pts.resize(parts * m * 64, 0);
+        sc.resize(parts * m * 32, 0);
+        for (size_t i = n; i < parts * m; i++) pts[64 * i + 32] = (uint8_t)S::identity_y;     // padding: 0 * identity
         part.resize(parts * 64);
-        const int rc = bjj_msm_groups(ctx, pts.data(), sc.data(), parts, 64, part.data());
+        const int rc = native_msm_groups(S{}, ctx, pts.data(), sc.data(), parts, m, parts == 1 ? out_xy : part.data());
         explicit_bzero(sc.data(), sc.size());
-        TRY(rc);
+        if (rc != DR_OK || parts == 1) return rc;
         pts.swap(part);
         n = parts;
         sc.assign(n * 32, 0);
         for (size_t i = 0; i < n; i++) sc[32 * i] = 1;
     }
 }
-int bjj_decode_points(dr_ctx* ctx, int mode, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
+// `kernel`: one of the suite's decoder instances, S::dec_codec, S::dec_check or S::dec_tai
+template <class S>
+int native_decode_points(S, dr_ctx* ctx, decltype(S::dec_tai) kernel, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
+    TRY(use_ctx(ctx));
     if (n == 0) return DR_OK;
     if (!enc || !out_xy || !ok) return fail(DR_ERR_INVALID, "null buffer");
     if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
-    TRY(bjj_consts_ready(ctx));
-    TRY(ctx->io_a.reserve(n * 32));
+    TRY(S::consts_ready(ctx));
+    std::vector<uint8_t> rec;
+    if (S::rec_bytes != S::enc_bytes) {                   // each encoding zero-padded to its record
+        rec.assign(n * S::rec_bytes, 0);
+        for (size_t i = 0; i < n; i++) std::memcpy(rec.data() + S::rec_bytes * i, enc + S::enc_bytes * i, S::enc_bytes);
+        enc = rec.data();
+    }
+    TRY(ctx->io_a.reserve(n * S::rec_bytes));
     TRY(ctx->io_b.reserve(n * 64));
     TRY(ctx->io_c.reserve(n * 4));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, enc, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    TRY(launch(ctx, "k_bjj_decode_points", [&] {
-        const dim3 grid(div_up(n, dr::BJJ_BLOCK)), block(dr::BJJ_BLOCK);
-        if (mode == dr::BJJ_DEC_TAI)
-            hipLaunchKernelGGL(dr::k_bjj_decode_points<dr::BJJ_DEC_TAI>, grid, block, 0, ctx->stream, ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(),
-                               ctx->io_c.as<uint32_t>(), (uint32_t)n);
-        else if (mode == dr::BJJ_DEC_CHECK)
-            hipLaunchKernelGGL(dr::k_bjj_decode_points<dr::BJJ_DEC_CHECK>, grid, block, 0, ctx->stream, ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(),
-                               ctx->io_c.as<uint32_t>(), (uint32_t)n);
-        else
-            hipLaunchKernelGGL(dr::k_bjj_decode_points<dr::BJJ_DEC_CODEC>, grid, block, 0, ctx->stream, ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(),
-                               ctx->io_c.as<uint32_t>(), (uint32_t)n);
+    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, enc, n * S::rec_bytes, hipMemcpyHostToDevice, ctx->stream));
+    TRY(launch(ctx, S::k_decode, [&] {
+        hipLaunchKernelGGL(kernel, dim3(div_up(n, S::block)), dim3(S::block), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
+                           ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
     }));
     std::vector<uint32_t> flags(n);
     HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_b.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
@@ -916,14 +712,36 @@ int bjj_decode_points(dr_ctx* ctx, int mode, const uint8_t* enc, size_t n, uint8
     for (size_t i = 0; i < n; i++) ok[i] = flags[i] ? 1 : 0;
     return DR_OK;
 }
+// the field selftests: n pairs of raw 9-limb images in, S::selftest_records results of 32 bytes and one flag byte per pair out
+template <class S>
+int native_field_selftest(S, dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
+    TRY(use_ctx(ctx));
+    if (n == 0) return DR_OK;
+    if (!a_limbs || !b_limbs || !out || !flags) return fail(DR_ERR_INVALID, "null buffer");
+    if (n >= (1ull << 24)) return fail(DR_ERR_INVALID, "batch too large");
+    TRY(S::consts_ready(ctx));
+    const size_t rec = (size_t)S::selftest_records * 32;
+    TRY(ctx->io_a.reserve(n * 72));
+    TRY(ctx->io_b.reserve(n * rec));
+    TRY(ctx->io_c.reserve(n * 4));
+    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, a_limbs, n * 36, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->io_a.as<uint8_t>() + n * 36, b_limbs, n * 36, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(S::field_selftest, dim3(div_up(n, 64)), dim3(64), 0, ctx->stream, ctx->io_a.as<int32_t>(),
+                       (const int32_t*)(ctx->io_a.as<uint8_t>() + n * 36), (uint32_t)n, ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> fl(n);
+    HIP_TRY(hipMemcpyAsync(out, ctx->io_b.p, n * rec, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(fl.data(), ctx->io_c.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < n; i++) flags[i] = (uint8_t)fl[i];
+    return DR_OK;
+}
 }  // namespace
 
 int te_scalar_mul_batch(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy) {
     TRY(use_ctx(ctx));
     TRY(check_curve(cv));
-    if (cv == dr::CV_ED25519) return ed_scalar_mul_batch(ctx, pts_xy, scalars, n, out_xy);
-    if (cv == dr::CV_P256) return p256_scalar_mul_batch(ctx, pts_xy, scalars, n, out_xy);
-    if (cv == dr::CV_BABYJUBJUB) return bjj_scalar_mul_batch(ctx, pts_xy, scalars, n, out_xy);
+    if (int rc; on_native(cv, rc, [&](auto S) { return native_scalar_mul_batch(S, ctx, pts_xy, scalars, n, out_xy); })) return rc;
     if (n == 0) return DR_OK;
     if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
     TRY(check_fr_elems(pts_xy, 2 * n, "point"));
@@ -986,9 +804,7 @@ int dr_te_scalar_mul_batch(dr_ctx* ctx, int curve, const uint8_t* pts_xy, const 
 int te_msm_groups(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy) {
     TRY(use_ctx(ctx));
     TRY(check_curve(cv));
-    if (cv == dr::CV_ED25519) return ed_msm_groups(ctx, pts_xy, scalars, groups, m, out_xy);
-    if (cv == dr::CV_P256) return p256_msm_groups(ctx, pts_xy, scalars, groups, m, out_xy);
-    if (cv == dr::CV_BABYJUBJUB) return bjj_msm_groups(ctx, pts_xy, scalars, groups, m, out_xy);
+    if (int rc; on_native(cv, rc, [&](auto S) { return native_msm_groups(S, ctx, pts_xy, scalars, groups, m, out_xy); })) return rc;
     if (groups == 0) return DR_OK;
     if (m == 0 || m > 64) return fail(DR_ERR_INVALID, "group size must be in 1..64");
     if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
@@ -1063,13 +879,11 @@ static int te_fixed_table(dr_ctx* ctx, int cv, const uint8_t base_xy[64], const 
 int te_fixed_base_groups(dr_ctx* ctx, int cv, const uint8_t* bases_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy, bool sync) {
     TRY(use_ctx(ctx));
     TRY(check_curve(cv));
-    if (cv == dr::CV_ED25519) return ed_fixed_base_groups(ctx, bases_xy, scalars, groups, m, out_xy);
-    if (cv == dr::CV_P256) return p256_fixed_base_groups(ctx, bases_xy, scalars, groups, m, out_xy);
-    if (cv == dr::CV_BABYJUBJUB) return bjj_fixed_base_groups(ctx, bases_xy, scalars, groups, m, out_xy);
     if (groups == 0) return DR_OK;
     if (m == 0 || m > 4) return fail(DR_ERR_INVALID, "1..4 fixed bases per group");
     if (!bases_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
     if (groups * m >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
+    if (int rc; on_native(cv, rc, [&](auto S) { return native_fixed_base_groups(S, ctx, bases_xy, scalars, groups, m, out_xy); })) return rc;
     if (groups * m <= drh::small_host_max() && !drh::te_curve(cv)->sw) {
         // a few groups: 64 table additions per term on a host core (~0.03 ms), entries picked by mask (the scalars are secrets and nonces)
         const drh::TeCurveHost* hc = drh::te_curve(cv);
@@ -1141,9 +955,7 @@ int te_msm(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* scalars, s
     TRY(use_ctx(ctx));
     TRY(check_curve(cv));
     if (!out_xy) return fail(DR_ERR_INVALID, "null buffer");
-    if (cv == dr::CV_ED25519) return ed_msm(ctx, pts_xy, scalars, n, out_xy);
-    if (cv == dr::CV_P256) return p256_msm(ctx, pts_xy, scalars, n, out_xy);
-    if (cv == dr::CV_BABYJUBJUB) return bjj_msm(ctx, pts_xy, scalars, n, out_xy);
+    if (int rc; on_native(cv, rc, [&](auto S) { return native_msm(S, ctx, pts_xy, scalars, n, out_xy); })) return rc;
     if (n == 0) {
         std::memset(out_xy, 0, 64);
         out_xy[32] = 1;
@@ -1277,11 +1089,9 @@ void launch_decode_points(dr_ctx* ctx, hipStream_t st, int cv, bool tai, const u
 }
 
 int te_decode_points(dr_ctx* ctx, int cv, bool tai, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok, bool sw_out) {
+    if (int rc; on_native(cv, rc, [&](auto S) { return native_decode_points(S, ctx, tai ? S.dec_tai : S.dec_check, enc, n, out_xy, ok); })) return rc;
     TRY(use_ctx(ctx));
     TRY(check_curve(cv));
-    if (cv == dr::CV_ED25519) return ed_decode_points(ctx, tai ? dr::ED_DEC_TAI : dr::ED_DEC_CHECK, enc, n, out_xy, ok);
-    if (cv == dr::CV_P256) return p256_decode_points(ctx, tai ? dr::P256_DEC_TAI : dr::P256_DEC_CHECK, enc, n, out_xy, ok);
-    if (cv == dr::CV_BABYJUBJUB) return bjj_decode_points(ctx, tai ? dr::BJJ_DEC_TAI : dr::BJJ_DEC_CHECK, enc, n, out_xy, ok);
     if (n == 0) return DR_OK;
     if (!enc || !out_xy || !ok) return fail(DR_ERR_INVALID, "null buffer");
     if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
@@ -1318,82 +1128,22 @@ int dr_te_decode_points(dr_ctx* ctx, int curve, const uint8_t* enc, size_t n, ui
     return te_decode_points(ctx, curve, false, enc, n, out_xy, ok, true);
 }
 int dr_ed25519_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
-    TRY(use_ctx(ctx));
-    return ed_decode_points(ctx, check ? dr::ED_DEC_CHECK : dr::ED_DEC_CODEC, enc, n, out_xy, ok);
+    return native_decode_points(Ed25519Suite{}, ctx, check ? Ed25519Suite::dec_check : Ed25519Suite::dec_codec, enc, n, out_xy, ok);
 }
-
 int dr_p256_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
-    TRY(use_ctx(ctx));
-    return p256_decode_points(ctx, check ? dr::P256_DEC_CHECK : dr::P256_DEC_CODEC, enc, n, out_xy, ok);
+    return native_decode_points(P256Suite{}, ctx, check ? P256Suite::dec_check : P256Suite::dec_codec, enc, n, out_xy, ok);
 }
 int dr_bjj_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
-    TRY(use_ctx(ctx));
-    return bjj_decode_points(ctx, check ? dr::BJJ_DEC_CHECK : dr::BJJ_DEC_CODEC, enc, n, out_xy, ok);
+    return native_decode_points(BjjSuite{}, ctx, check ? BjjSuite::dec_check : BjjSuite::dec_codec, enc, n, out_xy, ok);
 }
-int dr_bjj_field_ops_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
-    TRY(use_ctx(ctx));
-    if (n == 0) return DR_OK;
-    if (!a_limbs || !b_limbs || !out || !flags) return fail(DR_ERR_INVALID, "null buffer");
-    if (n >= (1ull << 24)) return fail(DR_ERR_INVALID, "batch too large");
-    TRY(bjj_consts_ready(ctx));
-    const size_t rec = (size_t)dr::BJJ_SELFTEST_RECORDS * 32;
-    TRY(ctx->io_a.reserve(n * 72));
-    TRY(ctx->io_b.reserve(n * rec));
-    TRY(ctx->io_c.reserve(n * 4));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, a_limbs, n * 36, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.as<uint8_t>() + n * 36, b_limbs, n * 36, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(dr::k_bjj_field_selftest, dim3(div_up(n, 64)), dim3(64), 0, ctx->stream, ctx->io_a.as<int32_t>(),
-                       (const int32_t*)(ctx->io_a.as<uint8_t>() + n * 36), (uint32_t)n, ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    std::vector<uint32_t> fl(n);
-    HIP_TRY(hipMemcpyAsync(out, ctx->io_b.p, n * rec, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(fl.data(), ctx->io_c.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (size_t i = 0; i < n; i++) flags[i] = (uint8_t)fl[i];
-    return DR_OK;
+int dr_fe25519_ops_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
+    return native_field_selftest(Ed25519Suite{}, ctx, a_limbs, b_limbs, n, out, flags);
 }
 int dr_p256_field_ops_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
-    TRY(use_ctx(ctx));
-    if (n == 0) return DR_OK;
-    if (!a_limbs || !b_limbs || !out || !flags) return fail(DR_ERR_INVALID, "null buffer");
-    if (n >= (1ull << 24)) return fail(DR_ERR_INVALID, "batch too large");
-    const size_t rec = (size_t)dr::P256_SELFTEST_RECORDS * 32;
-    TRY(ctx->io_a.reserve(n * 72));
-    TRY(ctx->io_b.reserve(n * rec));
-    TRY(ctx->io_c.reserve(n * 4));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, a_limbs, n * 36, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.as<uint8_t>() + n * 36, b_limbs, n * 36, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(dr::k_p256_field_selftest, dim3(div_up(n, 64)), dim3(64), 0, ctx->stream, ctx->io_a.as<int32_t>(),
-                       (const int32_t*)(ctx->io_a.as<uint8_t>() + n * 36), (uint32_t)n, ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    std::vector<uint32_t> fl(n);
-    HIP_TRY(hipMemcpyAsync(out, ctx->io_b.p, n * rec, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(fl.data(), ctx->io_c.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (size_t i = 0; i < n; i++) flags[i] = (uint8_t)fl[i];
-    return DR_OK;
+    return native_field_selftest(P256Suite{}, ctx, a_limbs, b_limbs, n, out, flags);
 }
-
-int dr_fe25519_ops_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
-    TRY(use_ctx(ctx));
-    if (n == 0) return DR_OK;
-    if (!a_limbs || !b_limbs || !out || !flags) return fail(DR_ERR_INVALID, "null buffer");
-    if (n >= (1ull << 24)) return fail(DR_ERR_INVALID, "batch too large");
-    const size_t rec = (size_t)dr::FE_SELFTEST_RECORDS * 32;
-    TRY(ctx->io_a.reserve(n * 72));
-    TRY(ctx->io_b.reserve(n * rec));
-    TRY(ctx->io_c.reserve(n * 4));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, a_limbs, n * 36, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.as<uint8_t>() + n * 36, b_limbs, n * 36, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(dr::k_fe25519_selftest, dim3(div_up(n, 64)), dim3(64), 0, ctx->stream, ctx->io_a.as<int32_t>(),
-                       (const int32_t*)(ctx->io_a.as<uint8_t>() + n * 36), (uint32_t)n, ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    std::vector<uint32_t> fl(n);
-    HIP_TRY(hipMemcpyAsync(out, ctx->io_b.p, n * rec, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(fl.data(), ctx->io_c.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (size_t i = 0; i < n; i++) flags[i] = (uint8_t)fl[i];
-    return DR_OK;
+int dr_bjj_field_ops_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
+    return native_field_selftest(BjjSuite{}, ctx, a_limbs, b_limbs, n, out, flags);
 }
 
 int dr_bsn_encode_to_curve_batch(dr_ctx* ctx, const uint8_t* u_pairs, size_t n, uint8_t* out_xy) {
@@ -1520,12 +1270,11 @@ int load_suite(const dr_vrf_suite* s, drh::VrfSuite& out, bool allow_sw) {
     std::memcpy(out.blinding_base, s->blinding_base_xy, 64);
     out.cv = drh::te_curve(s->curve);
     if (!out.cv) return fail(DR_ERR_INVALID, "unknown curve id in VRF suite");
-    if (out.cv->ed25519 && !allow_sw) return fail(DR_ERR_INVALID, "this entry point does not serve the Ed25519 suite");
-    if (out.cv->bjj && !allow_sw) return fail(DR_ERR_INVALID, "this entry point does not serve the Baby JubJub suite");
-    if (out.cv->p256) {
-        if (!allow_sw) return fail(DR_ERR_INVALID, "this entry point does not serve the P-256 suite");
-        out.point_len = 33;
-    }
+    if (int rc; on_native(s->curve, rc, [&](auto S) {
+            out.point_len = S.enc_bytes;
+            return allow_sw ? DR_OK : fail(DR_ERR_INVALID, std::string("this entry point does not serve the ") + S.name + " suite");
+        }) && rc != DR_OK)
+        return rc;
     if (out.cv->sw) {
         if (!allow_sw) return fail(DR_ERR_INVALID, "this entry point does not serve the short Weierstrass suite");
         // the kernels take the suite's constants as their TE images; the SW generator stays for its encoding
@@ -1564,7 +1313,7 @@ int encode_to_curve_msgs(dr_ctx* ctx, const drh::VrfSuite& su, size_t B, const u
     std::vector<uint8_t> cand, xy, ok;
     // P-256 (point.py:275-283 for a short Weierstrass curve with a 256-bit field): the candidate is the 32 squeezed bytes, nothing
     // shaved, and the flag byte 0x80 appended — 33 bytes, decoded with the codec's rules and its SEC1 fallback
-    const size_t cl = su.cv->p256 ? 33 : 32;
+    const size_t cl = su.cv->native == drh::NativeSuite::p256 ? 33 : 32;
     for (unsigned base = 0; !pending.empty();) {
         if (base >= 256) return fail(DR_ERR_INVALID, "hash_to_curve_tai failed");
         const unsigned K = std::min<unsigned>(base == 0 ? 4 : 8, 256 - base);
@@ -1592,7 +1341,7 @@ int encode_to_curve_msgs(dr_ctx* ctx, const drh::VrfSuite& su, size_t B, const u
 int dr_hash_to_field_batch(const dr_vrf_suite* suite, const uint8_t* msgs, const uint64_t* off, size_t count, uint8_t* out_u_pairs) {
     drh::VrfSuite su;
     TRY(load_suite(suite, su, true));
-    if (su.cv->p256) return fail(DR_ERR_INVALID, "the P-256 suite hashes to the curve by try-and-increment: no hash_to_field");
+    if (su.cv->native == drh::NativeSuite::p256) return fail(DR_ERR_INVALID, "the P-256 suite hashes to the curve by try-and-increment: no hash_to_field");
     if (count && (!off || !out_u_pairs || (off[count] && !msgs))) return fail(DR_ERR_INVALID, "null buffer");
     for (size_t i = 0; i < count; i++)
         if (off[i + 1] < off[i]) return fail(DR_ERR_INVALID, "offsets must be non-decreasing");

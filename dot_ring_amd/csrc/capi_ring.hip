@@ -150,7 +150,7 @@ int dr_ring_prover_create_te(dr_ctx* ctx, int curve, const dr_srs* srs, unsigned
     *out = nullptr;
     TRY(check_curve(curve));
     if (drh::te_curve(curve)->sw) return fail(DR_ERR_INVALID, "ring proofs require a Twisted Edwards curve");
-    if (drh::te_curve(curve)->ed25519 || drh::te_curve(curve)->p256 || drh::te_curve(curve)->bjj) return fail(DR_ERR_INVALID, "ring proofs require a curve over the BLS12-381 scalar field");
+    if (drh::te_curve(curve)->native != drh::NativeSuite::none) return fail(DR_ERR_INVALID, "ring proofs require a curve over the BLS12-381 scalar field");
     if (log2n < 9 || log2n > 12) return fail(DR_ERR_INVALID, "domain_size must be between 512 and 4096");
     const uint32_t n = 1u << log2n;
     if (max_ring + drh::te_curve(curve)->scalar_bits + 4 > n) return fail(DR_ERR_INVALID, "max_ring_size exceeds supported size");

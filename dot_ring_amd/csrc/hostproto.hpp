@@ -314,6 +314,10 @@ inline const Mod256& mod_p() {       // Bandersnatch base field = BLS12-381 scal
 // The twisted Edwards curves over that field the library serves (ids as DR_CURVE_* in dotring_hip.h and CV_* in
 // curve.hip.h): Bandersnatch (specs/bandersnatch.py:57-72) and JubJub (specs/jubjub.py:17-29).  Id 2 is Bandersnatch again, for the
 // suite whose points cross the ABI in short Weierstrass form (specs/bandersnatch_sw.py): the group and every kernel are Bandersnatch's.
+// The curves that are not over the BLS12-381 scalar field run only on kernels of their own, with no host route: Ed25519 over
+// GF(2^255 - 19) (kernels_ed25519.hip.h), P-256, short Weierstrass over its own field with 33-byte encodings (kernels_p256.hip.h), and
+// Baby JubJub over the BN254 scalar field (kernels_bjj.hip.h).
+enum class NativeSuite { none, ed25519, p256, bjj };
 struct TeCurveHost {
     int id;
     Mod256 n;                 // prime-order subgroup
@@ -323,9 +327,7 @@ struct TeCurveHost {
     bool glv;                 // has the endomorphism the lane-pair kernels use
     bool tai;                 // hash-to-curve by try-and-increment (otherwise Elligator 2)
     bool sw = false;          // points cross the ABI as short Weierstrass affine x || y (33-byte encodings); TE inside
-    bool ed25519 = false;     // over GF(2^255 - 19), not the BLS12-381 scalar field: the kernels of kernels_ed25519.hip.h, no host route
-    bool p256 = false;        // P-256: short Weierstrass over its own field, the kernels of kernels_p256.hip.h, 33-byte encodings, no host route
-    bool bjj = false;         // Baby JubJub: over the BN254 scalar field, the kernels of kernels_bjj.hip.h, no host route
+    NativeSuite native = NativeSuite::none;
 };
 inline const Mod256& mod_p25519() {   // Ed25519 base field (specs/ed25519.py)
     static Mod256 s = [] { Mod256 t; const uint64_t p[4] = {0xffffffffffffffedULL, 0xffffffffffffffffULL, 0xffffffffffffffffULL, 0x7fffffffffffffffULL}; t.init(p); return t; }();
@@ -357,25 +359,30 @@ inline const TeCurveHost* te_curve(int id) {
              const uint64_t n[4] = {0x5812631a5cf5d3edULL, 0x14def9dea2f79cd6ULL, 0x0000000000000000ULL, 0x1000000000000000ULL};
              c.n.init(n);
              const uint64_t d[4] = {0x75eb4dca135978a3ULL, 0x00700a4d4141d8abULL, 0x8cc740797779e898ULL, 0x52036cee2b6ffe73ULL};
-             std::memcpy(c.d, d, 32); c.neg_a[0] = 1; c.scalar_bits = 253; c.glv = false; c.tai = true; c.ed25519 = true; return c; }(),
+             std::memcpy(c.d, d, 32); c.neg_a[0] = 1; c.scalar_bits = 253; c.glv = false; c.tai = true; c.native = NativeSuite::ed25519; return c; }(),
         // P-256 (specs/p256.py, the P256_TAI variant): y^2 = x^3 - 3 x + b, cofactor 1, n of 256 bits (its top bit set); d and neg_a
         // do not apply (no twisted Edwards model)
         [] { TeCurveHost c{}; c.id = 4;
              const uint64_t n[4] = {0xf3b9cac2fc632551ULL, 0xbce6faada7179e84ULL, 0xffffffffffffffffULL, 0xffffffff00000000ULL};
              c.n.init(n);
-             c.scalar_bits = 256; c.glv = false; c.tai = true; c.p256 = true; return c; }(),
+             c.scalar_bits = 256; c.glv = false; c.tai = true; c.native = NativeSuite::p256; return c; }(),
         // Baby JubJub (specs/baby_jubjub.py): n = l of 251 bits, a = 1, cofactor 8; neg_a is unused (its kernels carry a = 1 themselves)
         [] { TeCurveHost c{}; c.id = 5;
              const uint64_t n[4] = {0x677297dc392126f1ULL, 0xab3eedb83920ee0aULL, 0x370a08b6d0302b0bULL, 0x060c89ce5c263405ULL};
              c.n.init(n);
              const uint64_t d[4] = {0x736c2b06fb281473ULL, 0x2498beee8e01a829ULL, 0x7a5fd2dee7844661ULL, 0x1575bd81821016c0ULL};
-             std::memcpy(c.d, d, 32); c.scalar_bits = 251; c.glv = false; c.tai = true; c.bjj = true; return c; }(),
+             std::memcpy(c.d, d, 32); c.scalar_bits = 251; c.glv = false; c.tai = true; c.native = NativeSuite::bjj; return c; }(),
     };
     return id >= 0 && id <= 5 ? &curves[id] : nullptr;
 }
 // the base field of a curve of the table
 inline const Mod256& te_field(const TeCurveHost& c) {
-    return c.ed25519 ? mod_p25519() : c.p256 ? mod_p256() : c.bjj ? mod_pbn254() : mod_p();
+    switch (c.native) {
+        case NativeSuite::ed25519: return mod_p25519();
+        case NativeSuite::p256: return mod_p256();
+        case NativeSuite::bjj: return mod_pbn254();
+        default: return mod_p();
+    }
 }
 
 // ---------------------------------------------------------------- GLV decomposition (dot_ring/curve/glv.py:57-160)
@@ -550,7 +557,7 @@ struct VrfSuite {
 // the suite's point encoding of xy given in the suite's own coordinates (TE, or SW for the SW suite)
 inline void enc_point(const VrfSuite& su, const uint8_t xy[64], uint8_t* out) {
     if (su.cv->sw) enc_sw_point(xy, out);
-    else if (su.cv->p256) enc_sw_point(xy, out, mod_p256());
+    else if (su.cv->native == NativeSuite::p256) enc_sw_point(xy, out, mod_p256());
     else enc_te_point(xy, out, te_field(*su.cv));
 }
 // squeeze `size` bytes of the stream defined by everything absorbed (xof: VrfSuite::xof)
@@ -617,7 +624,7 @@ inline void tai_candidate(const VrfSuite& su, const uint8_t* data, size_t len, u
     put8(t, (uint8_t)counter);
     vrf_squeeze(su.xof, t.data(), t.size(), out, 32);
     const unsigned shave = 256 - te_field(*su.cv).bits();
-    if (shave && !su.cv->p256 && !su.cv->sw) {
+    if (shave && su.cv->native != NativeSuite::p256 && !su.cv->sw) {
         const uint8_t sign = out[31] & 0x80;
         out[31] = (uint8_t)((out[31] & ((1u << (8 - shave)) - 1)) | sign);
     }
