@@ -110,6 +110,9 @@ _PROTOTYPES.update({
     "dr_fe25519_ops_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p, c_void_p]),
     "dr_p256_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
     "dr_p256_field_ops_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p, c_void_p]),
+    "dr_secp256k1_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
+    "dr_secp256k1_field_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p, c_void_p]),
+    "dr_secp256k1_map_to_curve": (c_int, [c_void_p, c_char_p, c_size_t, c_int, c_char_p, c_char_p]),
     "dr_bjj_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
     "dr_bjj_field_ops_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p, c_void_p]),
     "dr_encode_to_curve_batch": (c_int, [c_void_p, POINTER(VrfSuiteStruct), c_char_p, POINTER(ctypes.c_uint64), c_char_p,
@@ -194,14 +197,21 @@ def _ragged(items):
 
 
 CURVE_BANDERSNATCH, CURVE_JUBJUB, CURVE_BANDERSNATCH_SW, CURVE_ED25519, CURVE_P256, CURVE_BABYJUBJUB = 0, 1, 2, 3, 4, 5
+CURVE_SECP256K1, CURVE_SECP256K1_NU = 6, 7
+# bytes of an encoded point, per curve id (the suites with 33-byte encodings; every other curve's are 32)
+_POINT_LEN = {CURVE_BANDERSNATCH_SW: 33, CURVE_P256: 33, CURVE_SECP256K1: 33, CURVE_SECP256K1_NU: 33}
+
+
+def curve_point_len(curve: int) -> int:
+    return _POINT_LEN.get(curve, 32)
 # dr_vrf_suite.xof: the transcript hash of a suite
 XOF_SHA512, XOF_SHAKE128, XOF_SHA256 = 0, 1, 2
 _XOF_OF_HASH = {"sha512": XOF_SHA512, "shake_128": XOF_SHAKE128, "sha256": XOF_SHA256}
 
 
 def suite_point_len(suite: "VrfSuiteStruct") -> int:
-    """bytes of an encoded point of the suite: 33 for the short Weierstrass suites (Bandersnatch_SW, P-256), 32 otherwise"""
-    return 33 if suite.curve in (CURVE_BANDERSNATCH_SW, CURVE_P256) else 32
+    """bytes of an encoded point of the suite: 33 for the short Weierstrass suites (Bandersnatch_SW, P-256, secp256k1), 32 otherwise"""
+    return curve_point_len(suite.curve)
 
 
 def xof_kind(xof) -> int:
@@ -260,10 +270,11 @@ def random_expand(seed32: bytes, nbytes: int) -> bytes:
 
 
 def hash_to_field_batch(suite: VrfSuiteStruct, msgs) -> bytes:
+    """dr_hash_to_field_batch: two elements (64 bytes) per message; one (32 bytes) for the nonuniform secp256k1 suite"""
     blob, off = _ragged(msgs)
     out = ctypes.create_string_buffer(max(1, 64 * len(msgs)))
     _check(lib().dr_hash_to_field_batch(byref(suite), blob, off, len(msgs), out))
-    return out.raw[: 64 * len(msgs)]
+    return out.raw[: (32 if suite.curve == CURVE_SECP256K1_NU else 64) * len(msgs)]
 
 
 
@@ -592,6 +603,23 @@ class Context:
         """dr_p256_decode_points: (x||y bytes, flags) for len(enc)/33 encodings, with or without the identity check."""
         return self._decode_points(lib().dr_p256_decode_points, 33, enc, check)
 
+    def secp256k1_decode_points(self, enc: bytes, check: bool = True):
+        """dr_secp256k1_decode_points: (x||y bytes, flags) for len(enc)/33 SEC1 encodings."""
+        return self._decode_points(lib().dr_secp256k1_decode_points, 33, enc, check)
+
+    def secp256k1_field_selftest(self, a_limbs: bytes, b_limbs: bytes):
+        """dr_secp256k1_field_selftest: (n x 12 x 32 result bytes, n flag bytes) for n pairs of raw 9-limb images."""
+        return self._limb_selftest(lib().dr_secp256k1_field_selftest, 12, a_limbs, b_limbs)
+
+    def secp256k1_map_to_curve(self, us: bytes, per_item: int):
+        """dr_secp256k1_map_to_curve: (x||y bytes, flags) for len(us) / (32 per_item) items of per_item field elements each."""
+        if per_item not in (1, 2) or len(us) % (32 * per_item):
+            raise ValueError("field elements are 32 bytes each, one or two per item")
+        n = len(us) // (32 * per_item)
+        out, ok = ctypes.create_string_buffer(max(1, 64 * n)), ctypes.create_string_buffer(max(1, n))
+        _check(lib().dr_secp256k1_map_to_curve(self.handle, us, n, per_item, out, ok))
+        return out.raw[: 64 * n], ok.raw[:n]
+
     def ed25519_decode_points(self, enc: bytes, check: bool = True):
         """dr_ed25519_decode_points: (x||y bytes, flags) for len(enc)/32 encodings, with or without the prime-order check."""
         return self._decode_points(lib().dr_ed25519_decode_points, 32, enc, check)
@@ -716,7 +744,7 @@ class Context:
     def bsn_decode_points(self, enc: bytes, curve: int = CURVE_BANDERSNATCH):
         """dec_point for len(enc)/32 compressed points on the GPU (33 bytes each, SW affine out, for CURVE_BANDERSNATCH_SW)
         -> (affine x||y bytes, validity flags)."""
-        width = 33 if curve in (CURVE_BANDERSNATCH_SW, CURVE_P256) else 32
+        width = curve_point_len(curve)
         if len(enc) % width:
             raise ValueError(f"compressed points are {width} bytes each")
         count = len(enc) // width

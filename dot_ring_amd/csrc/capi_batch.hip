@@ -407,7 +407,7 @@ int pedersen_verify_core(dr_ctx* actx, const drh::VrfSuite& su, size_t B, const 
         uint8_t sum[64];
         TRY(te_msm(actx, su.cv->id, pts.data(), sc.data(), 5 * B + 2, sum));
         uint8_t ident[64] = {0};
-        if (su.cv->native != drh::NativeSuite::p256) ident[32] = 1;   // (0, 1) on the twisted Edwards curves; 64 zero bytes on P-256
+        ident[32] = su.identity_y;   // (0, 1) on the twisted Edwards curves; 64 zero bytes on P-256 and secp256k1
         ped_ok = std::memcmp(sum, ident, 64) == 0 ? 1 : 0;
     }
     return DR_OK;

@@ -5,6 +5,7 @@
 #include "kernels_sw.hip.h"
 #include "kernels_ed25519.hip.h"
 #include "kernels_p256.hip.h"
+#include "kernels_secp256k1.hip.h"
 #include "kernels_bjj.hip.h"
 
 namespace dri {
@@ -503,7 +504,7 @@ struct Ed25519Suite : NoConsts {
     static constexpr int block = dr::ED_BLOCK, selftest_records = dr::FE_SELFTEST_RECORDS;
     static constexpr const char *name = "Ed25519", *k_scalar_mul = "k_ed_scalar_mul", *k_msm_groups = "k_ed_msm_groups", *k_decode = "k_ed_decode_points";
     static const drh::Mod256& field() { return drh::mod_p25519(); }
-    static constexpr size_t identity_y = 1, enc_bytes = 32, rec_bytes = 32;   // identity (0, identity_y); encoding, decoder record
+    static constexpr size_t identity_y = 1, enc_bytes = 32, rec_bytes = 32, tai_bytes = 32;   // identity (0, identity_y); encoding, decoder record, try-and-increment candidate
 };
 struct P256Suite : NoConsts {
     static constexpr auto scalar_mul = dr::k_p256_scalar_mul;
@@ -514,7 +515,21 @@ struct P256Suite : NoConsts {
     static constexpr int block = dr::P256_BLOCK, selftest_records = dr::P256_SELFTEST_RECORDS;
     static constexpr const char *name = "P-256", *k_scalar_mul = "k_p256_scalar_mul", *k_msm_groups = "k_p256_msm_groups", *k_decode = "k_p256_decode_points";
     static const drh::Mod256& field() { return drh::mod_p256(); }
-    static constexpr size_t identity_y = 0, enc_bytes = 33, rec_bytes = 36;   // 64 zero bytes are the identity
+    static constexpr size_t identity_y = 0, enc_bytes = 33, rec_bytes = 36, tai_bytes = 33;   // 64 zero bytes are the identity; candidates carry the flag byte
+};
+// secp256k1 (curves 6 and 7): no try-and-increment, so dec_tai is the checking decoder again and encode_to_curve_msgs never takes that
+// branch for these curves (they hash with k_secp256k1_map_to_curve)
+struct Secp256k1Suite : NoConsts {
+    static constexpr auto scalar_mul = dr::k_secp256k1_scalar_mul;
+    static constexpr auto msm_groups = dr::k_secp256k1_msm_groups;
+    static constexpr auto dec_tai = dr::k_secp256k1_decode_points<dr::K1_DEC_CHECK>, dec_check = dr::k_secp256k1_decode_points<dr::K1_DEC_CHECK>,
+                          dec_codec = dr::k_secp256k1_decode_points<dr::K1_DEC_CODEC>;
+    static constexpr auto field_selftest = dr::k_secp256k1_field_selftest;
+    static constexpr int block = dr::K1_BLOCK, selftest_records = dr::K1_SELFTEST_RECORDS;
+    static constexpr const char *name = "secp256k1", *k_scalar_mul = "k_secp256k1_scalar_mul", *k_msm_groups = "k_secp256k1_msm_groups",
+                                *k_decode = "k_secp256k1_decode_points";
+    static const drh::Mod256& field() { return drh::mod_psecp256k1(); }
+    static constexpr size_t identity_y = 0, enc_bytes = 33, rec_bytes = 36, tai_bytes = 33;   // 64 zero bytes are the identity; no candidates are made
 };
 // Baby JubJub's square-root tables (BjjConsts) are built on the host once per process and copied to the device the first time a context
 // decodes a point or runs the field selftest
@@ -594,7 +609,7 @@ struct BjjSuite {
     static constexpr int block = dr::BJJ_BLOCK, selftest_records = dr::BJJ_SELFTEST_RECORDS;
     static constexpr const char *name = "Baby JubJub", *k_scalar_mul = "k_bjj_scalar_mul", *k_msm_groups = "k_bjj_msm_groups", *k_decode = "k_bjj_decode_points";
     static const drh::Mod256& field() { return drh::mod_pbn254(); }
-    static constexpr size_t identity_y = 1, enc_bytes = 32, rec_bytes = 32;
+    static constexpr size_t identity_y = 1, enc_bytes = 32, rec_bytes = 32, tai_bytes = 32;
     static int consts_ready(dr_ctx* ctx) { return bjj_consts_ready(ctx); }
 };
 // rc = f(S{}) for the description S of curve cv's native suite; false, f not called, for every other curve and an unknown id
@@ -604,6 +619,7 @@ bool on_native(int cv, int& rc, F&& f) {
         case drh::NativeSuite::ed25519: rc = f(Ed25519Suite{}); return true;
         case drh::NativeSuite::p256: rc = f(P256Suite{}); return true;
         case drh::NativeSuite::bjj: rc = f(BjjSuite{}); return true;
+        case drh::NativeSuite::secp256k1: rc = f(Secp256k1Suite{}); return true;
         default: return false;
     }
 }
@@ -1142,6 +1158,41 @@ int dr_fe25519_ops_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* 
 int dr_p256_field_ops_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
     return native_field_selftest(P256Suite{}, ctx, a_limbs, b_limbs, n, out, flags);
 }
+int dr_secp256k1_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
+    return native_decode_points(Secp256k1Suite{}, ctx, check ? Secp256k1Suite::dec_check : Secp256k1Suite::dec_codec, enc, n, out_xy, ok);
+}
+int dr_secp256k1_field_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
+    return native_field_selftest(Secp256k1Suite{}, ctx, a_limbs, b_limbs, n, out, flags);
+}
+// the map of RFC 9380 for n items of per_item (1 or 2) field elements each: one launch, the sum of each item's images out
+int dr_secp256k1_map_to_curve(dr_ctx* ctx, const uint8_t* us, size_t n, int per_item, uint8_t* out_xy, uint8_t* ok) {
+    TRY(use_ctx(ctx));
+    if (per_item != 1 && per_item != 2) return fail(DR_ERR_INVALID, "one (nonuniform) or two (uniform, RO) field elements per item");
+    if (n == 0) return DR_OK;
+    if (!us || !out_xy || !ok) return fail(DR_ERR_INVALID, "null buffer");
+    if (n >= (1ull << 30)) return fail(DR_ERR_INVALID, "batch too large");
+    const size_t elems = n * (size_t)per_item;
+    for (size_t i = 0; i < elems; i++) {
+        uint64_t v[4];
+        drh::load_le32(us + 32 * i, v);
+        if (drh::Mod256::geq(v, drh::mod_psecp256k1().m)) return fail(DR_ERR_INVALID, "input is not a canonical field element");
+    }
+    TRY(ctx->io_a.reserve(elems * 32));
+    TRY(ctx->io_b.reserve(n * 64));
+    TRY(ctx->io_c.reserve(n * 4));
+    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, us, elems * 32, hipMemcpyHostToDevice, ctx->stream));
+    TRY(launch(ctx, "k_secp256k1_map_to_curve", [&] {
+        hipLaunchKernelGGL(dr::k_secp256k1_map_to_curve, dim3(div_up(n, dr::K1_BLOCK)), dim3(dr::K1_BLOCK), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
+                           ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n, (uint32_t)per_item);
+    }));
+    std::vector<uint32_t> flags(n);
+    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_b.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(flags.data(), ctx->io_c.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->prof) TRY(prof_collect(ctx));
+    for (size_t i = 0; i < n; i++) ok[i] = flags[i] ? 1 : 0;
+    return DR_OK;
+}
 int dr_bjj_field_ops_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
     return native_field_selftest(BjjSuite{}, ctx, a_limbs, b_limbs, n, out, flags);
 }
@@ -1272,9 +1323,12 @@ int load_suite(const dr_vrf_suite* s, drh::VrfSuite& out, bool allow_sw) {
     if (!out.cv) return fail(DR_ERR_INVALID, "unknown curve id in VRF suite");
     if (int rc; on_native(s->curve, rc, [&](auto S) {
             out.point_len = S.enc_bytes;
+            out.identity_y = (uint8_t)S.identity_y;
+            out.tai_len = S.tai_bytes;
             return allow_sw ? DR_OK : fail(DR_ERR_INVALID, std::string("this entry point does not serve the ") + S.name + " suite");
         }) && rc != DR_OK)
         return rc;
+    if (out.cv->sswu && out.xof != 2) return fail(DR_ERR_INVALID, "the secp256k1 suites hash with SHA-256 (xof = 2)");
     if (out.cv->sw) {
         if (!allow_sw) return fail(DR_ERR_INVALID, "this entry point does not serve the short Weierstrass suite");
         // the kernels take the suite's constants as their TE images; the SW generator stays for its encoding
@@ -1299,6 +1353,18 @@ int encode_to_curve_msgs(dr_ctx* ctx, const drh::VrfSuite& su, size_t B, const u
         if (salt_off) drh::put(m, salts + salt_off[i], salt_off[i + 1] - salt_off[i]);
         drh::put(m, data + off[i], off[i + 1] - off[i]);
     };
+    if (su.cv->sswu) {                // RFC 9380: hash_to_field on the worker threads, the map (and for RO the sum of two images) in one launch
+        const unsigned per = su.cv->nu ? 1 : 2;
+        std::vector<uint8_t> us(B * 32 * per), ok(B);
+        drh::parallel_for(B, [&](size_t i) {
+            build(i);
+            drh::hash_to_field_xmd_sha256(su, msgs[i].data(), msgs[i].size(), per, us.data() + 32 * per * i);
+        });
+        TRY(dr_secp256k1_map_to_curve(ctx, us.data(), B, (int)per, out_xy, ok.data()));
+        for (size_t i = 0; i < B; i++)
+            if (!ok[i]) return fail(DR_ERR_INVALID, "hash to curve: a denominator of the isogeny is zero");
+        return DR_OK;
+    }
     if (!su.cv->tai) {
         std::vector<uint8_t> us(B * 64);
         drh::parallel_for(B, [&](size_t i) {
@@ -1313,7 +1379,7 @@ int encode_to_curve_msgs(dr_ctx* ctx, const drh::VrfSuite& su, size_t B, const u
     std::vector<uint8_t> cand, xy, ok;
     // P-256 (point.py:275-283 for a short Weierstrass curve with a 256-bit field): the candidate is the 32 squeezed bytes, nothing
     // shaved, and the flag byte 0x80 appended — 33 bytes, decoded with the codec's rules and its SEC1 fallback
-    const size_t cl = su.cv->native == drh::NativeSuite::p256 ? 33 : 32;
+    const size_t cl = su.tai_len;
     for (unsigned base = 0; !pending.empty();) {
         if (base >= 256) return fail(DR_ERR_INVALID, "hash_to_curve_tai failed");
         const unsigned K = std::min<unsigned>(base == 0 ? 4 : 8, 256 - base);
@@ -1345,6 +1411,11 @@ int dr_hash_to_field_batch(const dr_vrf_suite* suite, const uint8_t* msgs, const
     if (count && (!off || !out_u_pairs || (off[count] && !msgs))) return fail(DR_ERR_INVALID, "null buffer");
     for (size_t i = 0; i < count; i++)
         if (off[i + 1] < off[i]) return fail(DR_ERR_INVALID, "offsets must be non-decreasing");
+    if (su.cv->sswu) {                // two elements per message for the uniform (RO) variant (64 bytes), one for the nonuniform one (32)
+        const unsigned per = su.cv->nu ? 1 : 2;
+        drh::parallel_for(count, [&](size_t i) { drh::hash_to_field_xmd_sha256(su, msgs + off[i], off[i + 1] - off[i], per, out_u_pairs + 32 * per * i); });
+        return DR_OK;
+    }
     drh::parallel_for(count, [&](size_t i) { drh::hash_to_field2(su, msgs + off[i], off[i + 1] - off[i], out_u_pairs + 64 * i); });
     return DR_OK;
 }

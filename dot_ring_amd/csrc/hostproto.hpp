@@ -316,8 +316,9 @@ inline const Mod256& mod_p() {       // Bandersnatch base field = BLS12-381 scal
 // suite whose points cross the ABI in short Weierstrass form (specs/bandersnatch_sw.py): the group and every kernel are Bandersnatch's.
 // The curves that are not over the BLS12-381 scalar field run only on kernels of their own, with no host route: Ed25519 over
 // GF(2^255 - 19) (kernels_ed25519.hip.h), P-256, short Weierstrass over its own field with 33-byte encodings (kernels_p256.hip.h), and
-// Baby JubJub over the BN254 scalar field (kernels_bjj.hip.h).
-enum class NativeSuite { none, ed25519, p256, bjj };
+// Baby JubJub over the BN254 scalar field (kernels_bjj.hip.h), and secp256k1, short Weierstrass with a = 0 over its own field, SEC1
+// encodings and RFC 9380 hashing to the curve (kernels_secp256k1.hip.h; ids 6 and 7 are its uniform (RO) and nonuniform variants).
+enum class NativeSuite { none, ed25519, p256, bjj, secp256k1 };
 struct TeCurveHost {
     int id;
     Mod256 n;                 // prime-order subgroup
@@ -327,6 +328,8 @@ struct TeCurveHost {
     bool glv;                 // has the endomorphism the lane-pair kernels use
     bool tai;                 // hash-to-curve by try-and-increment (otherwise Elligator 2)
     bool sw = false;          // points cross the ABI as short Weierstrass affine x || y (33-byte encodings); TE inside
+    bool sswu = false;        // hash-to-curve by the simplified SWU map of RFC 9380 (neither try-and-increment nor Elligator 2)
+    bool nu = false;          // ... its nonuniform variant: one field element per message, DST ..._NU_
     NativeSuite native = NativeSuite::none;
 };
 inline const Mod256& mod_p25519() {   // Ed25519 base field (specs/ed25519.py)
@@ -341,8 +344,16 @@ inline const Mod256& mod_pbn254() {    // Baby JubJub base field = BN254 scalar 
     static Mod256 s = [] { Mod256 t; const uint64_t p[4] = {0x43e1f593f0000001ULL, 0x2833e84879b97091ULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL}; t.init(p); return t; }();
     return s;
 }
+inline const Mod256& mod_psecp256k1() {   // secp256k1 base field, 2^256 - 2^32 - 977 (specs/secp256k1.py)
+    static Mod256 s = [] { Mod256 t; const uint64_t p[4] = {0xfffffffefffffc2fULL, 0xffffffffffffffffULL, 0xffffffffffffffffULL, 0xffffffffffffffffULL}; t.init(p); return t; }();
+    return s;
+}
+inline const Mod256& secp256k1_order() {
+    static Mod256 s = [] { Mod256 t; const uint64_t n[4] = {0xbfd25e8cd0364141ULL, 0xbaaedce6af48a03bULL, 0xfffffffffffffffeULL, 0xffffffffffffffffULL}; t.init(n); return t; }();
+    return s;
+}
 inline const TeCurveHost* te_curve(int id) {
-    static const TeCurveHost curves[6] = {
+    static const TeCurveHost curves[8] = {
         [] { TeCurveHost c{}; c.id = 0; c.n = mod_n();
              const uint64_t d[4] = {0xb369f2f5188d58e7ULL, 0xcb66677177e54f92ULL, 0xc66e3bf86be3b6d8ULL, 0x6389c12633c267cbULL};
              std::memcpy(c.d, d, 32); c.neg_a[0] = 5; c.scalar_bits = 253; c.glv = true; c.tai = false; return c; }(),
@@ -372,8 +383,14 @@ inline const TeCurveHost* te_curve(int id) {
              c.n.init(n);
              const uint64_t d[4] = {0x736c2b06fb281473ULL, 0x2498beee8e01a829ULL, 0x7a5fd2dee7844661ULL, 0x1575bd81821016c0ULL};
              std::memcpy(c.d, d, 32); c.scalar_bits = 251; c.glv = false; c.tai = true; c.native = NativeSuite::bjj; return c; }(),
+        // secp256k1 (specs/secp256k1.py): y^2 = x^3 + 7, cofactor 1, n of 256 bits; Secp256k1_RO (6) and Secp256k1_NU (7) share every
+        // constant and the suite id, so the variant travels in the curve id; d and neg_a do not apply
+        [] { TeCurveHost c{}; c.id = 6; c.n = secp256k1_order();
+             c.scalar_bits = 256; c.glv = false; c.tai = false; c.sswu = true; c.native = NativeSuite::secp256k1; return c; }(),
+        [] { TeCurveHost c{}; c.id = 7; c.n = secp256k1_order();
+             c.scalar_bits = 256; c.glv = false; c.tai = false; c.sswu = true; c.nu = true; c.native = NativeSuite::secp256k1; return c; }(),
     };
-    return id >= 0 && id <= 5 ? &curves[id] : nullptr;
+    return id >= 0 && id <= 7 ? &curves[id] : nullptr;
 }
 // the base field of a curve of the table
 inline const Mod256& te_field(const TeCurveHost& c) {
@@ -381,6 +398,7 @@ inline const Mod256& te_field(const TeCurveHost& c) {
         case NativeSuite::ed25519: return mod_p25519();
         case NativeSuite::p256: return mod_p256();
         case NativeSuite::bjj: return mod_pbn254();
+        case NativeSuite::secp256k1: return mod_psecp256k1();
         default: return mod_p();
     }
 }
@@ -471,6 +489,12 @@ inline void enc_sw_point(const uint8_t xy[64], uint8_t out[33], const Mod256& fi
     for (int i = 3; i >= 0; i--) { if (y[i] != ny[i]) { gt = y[i] > ny[i]; break; } }
     out[32] = gt ? 0x80 : 0x00;
 }
+// SEC1 compressed point (sw_affine_point.py point_to_string, the secp256k1 suites): 0x02 / 0x03 by the parity of y, then x big-endian.
+// The identity has no encoding; 64 zero bytes give 0x02 and 32 zero bytes, which no transcript of a valid proof contains.
+inline void enc_sec1_point(const uint8_t xy[64], uint8_t out[33]) {
+    out[0] = (uint8_t)(0x02 | (xy[32] & 1));
+    for (int i = 0; i < 32; i++) out[1 + i] = xy[31 - i];
+}
 // SW affine -> its TE image (ring_proof/ring_curve.py:14-21) for the suite's constant points; kernels_sw.hip.h maps everything else
 inline bool sw_to_te_host(const uint8_t sw[64], uint8_t te[64]) {
     static const uint64_t MB[4] = {0x926c66eb6fa86d15ULL, 0xbd025b636bd74122ULL, 0x316b96e5c340cf6aULL, 0x384d1c153c878eeaULL};
@@ -551,13 +575,16 @@ struct VrfSuite {
     int xof;                  // the transcript hash (dr_vrf_suite.xof): 0 SHA-512 or 2 SHA-256 in counter mode, 1 SHAKE128
     uint8_t generator[64], blinding_base[64];     // TE affine (the kernels' coordinates; the SW suite's are mapped on loading)
     const TeCurveHost* cv = te_curve(0);
-    size_t point_len = 32;                        // bytes of an encoded point: 32 (TE), 33 (SW, P-256)
+    size_t point_len = 32;                        // bytes of an encoded point: 32 (TE), 33 (SW, P-256, secp256k1)
+    size_t tai_len = 32;                          // bytes of a try-and-increment candidate: 33 on P-256 (the flag byte), 32 otherwise
+    uint8_t identity_y = 1;                       // the identity is (0, identity_y): (0, 1) on the twisted Edwards curves, 64 zero bytes otherwise
     uint8_t generator_sw[64] = {0};               // SW suite: the generator as given (its encoding enters the Tiny / Thin transcripts)
 };
 // the suite's point encoding of xy given in the suite's own coordinates (TE, or SW for the SW suite)
 inline void enc_point(const VrfSuite& su, const uint8_t xy[64], uint8_t* out) {
     if (su.cv->sw) enc_sw_point(xy, out);
     else if (su.cv->native == NativeSuite::p256) enc_sw_point(xy, out, mod_p256());
+    else if (su.cv->native == NativeSuite::secp256k1) enc_sec1_point(xy, out);
     else enc_te_point(xy, out, te_field(*su.cv));
 }
 // squeeze `size` bytes of the stream defined by everything absorbed (xof: VrfSuite::xof)
@@ -669,6 +696,43 @@ inline void hash_to_field2(const VrfSuite& su, const uint8_t* msg, size_t len, u
     for (int k = 0; k < 2; k++) {
         uint64_t v[4];
         mod_p().reduce_bytes(raw + 48 * k, 48, true, v);
+        store_le32(v, out + 32 * k);
+    }
+}
+
+// RFC 9380 hash_to_field for the secp256k1 suites (curve.py:110-185 with specs/secp256k1.py): expand_message_xmd over SHA-256 with a
+// Z_pad of 64 bytes and the DST QUUX-V01-CS02-with- || suite_id (its _RO_ replaced by _NU_ for the nonuniform variant), 48 bytes per
+// element, big-endian, mod p.  `count` is 2 (uniform, RO) or 1 (nonuniform); out = count x 32 bytes little-endian.
+inline void hash_to_field_xmd_sha256(const VrfSuite& su, const uint8_t* msg, size_t len, unsigned count, uint8_t* out) {
+    Bytes dst;
+    put(dst, "QUUX-V01-CS02-with-", 19);
+    put(dst, su.suite_id.data(), su.suite_id.size());
+    if (su.cv->nu && dst.size() >= 4 && std::memcmp(&dst[dst.size() - 4], "_RO_", 4) == 0) { dst[dst.size() - 3] = 'N'; dst[dst.size() - 2] = 'U'; }
+    put8(dst, (uint8_t)dst.size());                  // DST_prime = DST || len(DST)
+    const size_t L = 48 * (size_t)count;             // 96 or 48: 3 or 2 blocks of 32
+    uint8_t b0[32], prev[32], raw[96];
+    const uint8_t zpad[64] = {0};
+    Sha256 h;
+    h.update(zpad, 64);
+    if (len) h.update(msg, len);                     // (an empty message has no buffer to read)
+    const uint8_t lb[3] = {0, (uint8_t)L, 0};
+    h.update(lb, 3);
+    h.update(dst.data(), dst.size());
+    h.final(b0);
+    for (size_t i = 1; 32 * (i - 1) < L; i++) {
+        Sha256 g;
+        uint8_t x[32];
+        for (int j = 0; j < 32; j++) x[j] = i == 1 ? b0[j] : (uint8_t)(b0[j] ^ prev[j]);
+        g.update(x, 32);
+        const uint8_t ib = (uint8_t)i;
+        g.update(&ib, 1);
+        g.update(dst.data(), dst.size());
+        g.final(prev);
+        std::memcpy(raw + 32 * (i - 1), prev, 32);
+    }
+    for (unsigned k = 0; k < count; k++) {
+        uint64_t v[4];
+        mod_psecp256k1().reduce_bytes(raw + 48 * k, 48, true, v);
         store_le32(v, out + 32 * k);
     }
 }

@@ -1,0 +1,418 @@
+// secp256k1 kernels (DR_CURVE_SECP256K1 and DR_CURVE_SECP256K1_NU; the reference's specs/secp256k1.py, Secp256k1_RO / Secp256k1_NU): the
+// short Weierstrass group law with a = 0, b = 7 over GF(2^256 - 2^32 - 977) (fsecp256k1.hip.h) and the kernels that fill, for this
+// curve, the roles kernels_p256.hip.h fills for P-256 — variable-base scalar multiplication on a fixed schedule, grouped MSMs, point
+// decoding (plain SEC1 compressed) — and, new with this curve, the map of RFC 9380 hashing to the curve: simplified SWU onto an
+// isogenous curve, the 3-isogeny back, and for the uniform (RO) variant the sum of two images.  The existing kernels stay as they are.
+//
+// Points cross the ABI as affine x || y little-endian; 64 zero bytes are the identity ((0, 0) is not on the curve).  Inside: homogeneous
+// projective (X : Y : Z), identity (0 : 1 : 0).  The group law is the complete one of Renes, Costello and Batina (2016), algorithms 7
+// (addition) and 9 (doubling) for a = 0 with b3 = 3 b = 21: no exceptional cases and no branches.  The comments give the limb class of
+// every intermediate against fsecp256k1.hip.h's contract: n = normal, sK = a sum or difference of K normals.
+#pragma once
+#include "fsecp256k1.hip.h"
+
+namespace dr {
+
+constexpr int K1_BLOCK = 64;          // one wave per workgroup, as k_p256_scalar_mul
+constexpr int K1_TABLE = 8;           // entries 1P..8P
+constexpr int K1_PT_WORDS = 27;       // X, Y, Z x 9 limbs (the table holds limb images: no packing)
+constexpr int K1_WINDOWS = 65;        // 64 signed 4-bit digits of k < n < 2^256 and the carry out of the top one
+constexpr uint32_t K1_B3 = 21;
+
+struct K1Point {
+    FK x, y, z;
+};
+
+DR_DEV K1Point k1_identity() {
+    K1Point p;
+    p.x = FK::zero(); p.y = FK::small(1); p.z = FK::zero();
+    return p;
+}
+
+// algorithm 9, a = 0: 2 squarings, 4 products, one fused pair, two products by 21 / 8; coordinates n in, n out
+DR_DEV K1Point k1_dbl(const K1Point& p) {
+    const FK t0 = sqr(p.y);                                      // n
+    const FK z8 = mul_small(t0, 8);                              // 8 Y^2: n
+    const FK t1 = mul(p.y, p.z);                                 // n
+    const FK t2 = mul_small(sqr(p.z), K1_B3);                    // 21 Z^2: n
+    const FK y3a = carry(add(t0, t2));                           // Y^2 + 21 Z^2: n
+    const FK t0b = carry(sub(t0, add(t2, dbl(t2))));             // Y^2 - 63 Z^2: n - s3 -> n
+    K1Point r;
+    r.x = mul(dbl(t0b), mul(p.x, p.y));                          // 2 (Y^2 - 63 Z^2) X Y: s2 x n
+    r.y = mul2(t0b, y3a, t2, z8);                                // t0b y3a + 8 . 21 Y^2 Z^2: n
+    r.z = mul(t1, z8);                                           // 8 Y^3 Z: n
+    return r;
+}
+
+// algorithm 7, a = 0: 6 products, 3 fused pairs, two products by 21; coordinates n in, n out
+DR_DEV K1Point k1_add(const K1Point& p, const K1Point& q) {
+    const FK t0 = mul(p.x, q.x), t1 = mul(p.y, q.y), t2 = mul(p.z, q.z);                      // n
+    const FK t3 = carry(sub(mul(carry(add(p.x, p.y)), add(q.x, q.y)), add(t0, t1)));          // X1 Y2 + X2 Y1: n x s2 - s2 -> n
+    const FK t4 = carry(sub(mul(carry(add(p.y, p.z)), add(q.y, q.z)), add(t1, t2)));          // Y1 Z2 + Y2 Z1: n
+    const FK y3 = mul_small(carry(sub(mul(carry(add(p.x, p.z)), add(q.x, q.z)), add(t0, t2))), K1_B3);   // 21 (X1 Z2 + X2 Z1): n
+    const FK t0b = carry(add(t0, dbl(t0)));                                                    // 3 X1 X2: n
+    const FK t2b = mul_small(t2, K1_B3);                                                       // 21 Z1 Z2: n
+    const FK z3 = carry(add(t1, t2b)), t1b = carry(sub(t1, t2b));                              // n
+    K1Point r;
+    r.x = mul2(t3, t1b, neg(t4), y3);                                                          // n
+    r.y = mul2(t1b, z3, y3, t0b);                                                              // n
+    r.z = mul2(z3, t4, t0b, t3);                                                               // n
+    return r;
+}
+
+DR_DEV K1Point k1_cneg(const K1Point& p, bool negate) {
+    K1Point r = p;
+    r.y = carry(cneg(p.y, negate));
+    return r;
+}
+
+// ---------------------------------------------------------------- memory
+DR_DEV void k1_load8(const uint32_t* p, uint32_t (&w)[8]) {
+    const uint4* q = reinterpret_cast<const uint4*>(p);
+    const uint4 a = q[0], b = q[1];
+    w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
+    w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
+}
+DR_DEV void k1_store8(uint32_t* p, const uint32_t (&w)[8]) {
+    uint4* q = reinterpret_cast<uint4*>(p);
+    q[0] = make_uint4(w[0], w[1], w[2], w[3]);
+    q[1] = make_uint4(w[4], w[5], w[6], w[7]);
+}
+// affine x || y (16 words, canonical) -> projective; 64 zero bytes -> the identity
+DR_DEV K1Point k1_load_affine(const uint32_t* p) {
+    uint32_t x[8], y[8];
+    k1_load8(p, x);
+    k1_load8(p + 8, y);
+    uint32_t o = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) o |= x[j] | y[j];
+    K1Point r;
+    r.x = fk_unpack(x);
+    r.y = fk_unpack(y);
+    r.z = FK::small(1);
+    if (o == 0) r = k1_identity();
+    return r;
+}
+DR_DEV void k1_store_fe(uint32_t* p, const FK& a) {
+    uint32_t w[8];
+    fk_pack(a, w);
+    k1_store8(p, w);
+}
+// x || y of the point; the identity (Z = 0, so x = y = 0 after the multiplication by 0^-1 = 0) stores 64 zero bytes
+DR_DEV void k1_store_affine(uint32_t* out, const K1Point& acc) {
+    const FK zi = fk_inv(acc.z);
+    k1_store_fe(out, mul(acc.x, zi));
+    k1_store_fe(out + 8, mul(acc.y, zi));
+}
+// LDS table [entry][limb][lane] (bank = lane whatever the entry), limb images of the (normal) coordinates
+DR_DEV void k1_lds_store(uint32_t* tab, int entry, int lane, const K1Point& p) {
+    uint32_t* base = tab + (size_t)entry * K1_PT_WORDS * K1_BLOCK + lane;
+#pragma unroll
+    for (int i = 0; i < FK_L; i++) {
+        base[(0 + i) * K1_BLOCK] = (uint32_t)p.x.l[i];
+        base[(9 + i) * K1_BLOCK] = (uint32_t)p.y.l[i];
+        base[(18 + i) * K1_BLOCK] = (uint32_t)p.z.l[i];
+    }
+}
+DR_DEV K1Point k1_lds_load(const uint32_t* tab, int entry, int lane) {
+    const uint32_t* base = tab + (size_t)entry * K1_PT_WORDS * K1_BLOCK + lane;
+    K1Point p;
+#pragma unroll
+    for (int i = 0; i < FK_L; i++) {
+        p.x.l[i] = (int32_t)base[(0 + i) * K1_BLOCK];
+        p.y.l[i] = (int32_t)base[(9 + i) * K1_BLOCK];
+        p.z.l[i] = (int32_t)base[(18 + i) * K1_BLOCK];
+    }
+    return p;
+}
+DR_DEV K1Point k1_shfl_down(const K1Point& p, unsigned delta) {
+    K1Point o;
+#pragma unroll
+    for (int t = 0; t < FK_L; t++) {
+        o.x.l[t] = __shfl_down(p.x.l[t], delta, 64);
+        o.y.l[t] = __shfl_down(p.y.l[t], delta, 64);
+        o.z.l[t] = __shfl_down(p.z.l[t], delta, 64);
+    }
+    return o;
+}
+
+// k mod n for a 256-bit k: 2 n > 2^256, so one conditional subtraction (in every lane)
+DR_DEV void k1_load_scalar(const uint32_t* p, uint32_t (&k)[8]) {
+    k1_load8(p, k);
+    uint32_t d[8], borrow = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) d[i] = subb(k[i], FsecpConsts::NW[i], borrow);
+#pragma unroll
+    for (int i = 0; i < 8; i++) k[i] = borrow ? k[i] : d[i];
+}
+
+// k P for k < n on the fixed schedule of p256_scalar_mul_core: table 1P..8P in LDS, 65 signed 4-bit windows, four doublings and one
+// table addition each whatever the digits (the table index, always in range, is the only thing a digit decides) — the secret
+// scalars of the provers go through here
+DR_DEV K1Point k1_scalar_mul_core(uint32_t* tab, int lane, const K1Point& P, const uint32_t (&k)[8]) {
+    k1_lds_store(tab, 0, lane, P);
+    K1Point Q = k1_dbl(P);
+    k1_lds_store(tab, 1, lane, Q);
+#pragma unroll 1
+    for (int e = 2; e < K1_TABLE; e++) {
+        Q = k1_add(Q, P);
+        k1_lds_store(tab, e, lane, Q);
+    }
+    uint32_t dig[8];                 // digits 0..63 in [-8, 7], stored as d + 8; digit 64 = top_carry
+    uint32_t carry_in = 0;
+#pragma unroll
+    for (int w = 0; w < 8; w++) {
+        uint32_t packed = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const uint32_t v = ((k[w] >> (4 * j)) & 15u) + carry_in;
+            carry_in = v >= 8u ? 1u : 0u;
+            packed |= ((v + 8u) & 15u) << (4 * j);
+        }
+        dig[w] = packed;
+    }
+    const uint32_t top_carry = carry_in;
+    K1Point acc = k1_identity();
+#pragma unroll 1
+    for (int w = K1_WINDOWS - 1; w >= 0; w--) {
+#pragma unroll 1
+        for (int j = 0; j < 4; j++) acc = k1_dbl(acc);
+        const int dg = w == K1_WINDOWS - 1 ? (int)top_carry : (int)((dig[w >> 3] >> (4 * (w & 7))) & 15u) - 8;
+        const int mag = dg < 0 ? -dg : dg;
+        K1Point T = k1_lds_load(tab, mag == 0 ? 0 : mag - 1, lane);
+        T = k1_cneg(T, dg < 0);
+        if (mag == 0) T = k1_identity();
+        acc = k1_add(acc, T);
+    }
+    return acc;
+}
+
+// out[i] = k[i] P[i].  pts: n x 16 words (x || y), ks: n x 8, out: n x 16.  One lane per multiplication.
+__global__ __launch_bounds__(K1_BLOCK) void k_secp256k1_scalar_mul(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks,
+                                                                   uint32_t* __restrict__ out, uint32_t n) {
+    __shared__ uint32_t tab[K1_TABLE * K1_PT_WORDS * K1_BLOCK];
+    const int lane = threadIdx.x;
+    uint32_t i = blockIdx.x * K1_BLOCK + lane;
+    const bool live = i < n;
+    if (!live) i = n - 1;            // keep the wave converged; the duplicate result is not stored
+    const K1Point P = k1_load_affine(pts + (size_t)i * 16);
+    uint32_t k[8];
+    k1_load_scalar(ks + (size_t)i * 8, k);
+    const K1Point acc = k1_scalar_mul_core(tab, lane, P, k);
+    if (live) k1_store_affine(out + (size_t)i * 16, acc);
+}
+
+// out[g] = sum_{j<m} k[g m + j] P[g m + j]: one lane per term (m padded to mpad, a power of two <= 64), folded with shuffles by the
+// complete addition — k_p256_msm_groups for this curve
+__global__ __launch_bounds__(K1_BLOCK) void k_secp256k1_msm_groups(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks,
+                                                                   uint32_t* __restrict__ out, uint32_t groups, uint32_t m, uint32_t mpad) {
+    __shared__ uint32_t tab[K1_TABLE * K1_PT_WORDS * K1_BLOCK];
+    const int lane = threadIdx.x;
+    const uint32_t per_block = K1_BLOCK / mpad;
+    const uint32_t g = blockIdx.x * per_block + lane / mpad;
+    const uint32_t j = lane % mpad;
+    const bool live = g < groups && j < m;
+    const size_t idx = live ? (size_t)g * m + j : 0;          // dead lanes recompute term 0 and are masked out
+    const K1Point P = k1_load_affine(pts + idx * 16);
+    uint32_t k[8];
+    k1_load_scalar(ks + idx * 8, k);
+    const K1Point r = k1_scalar_mul_core(tab, lane, P, k);
+    K1Point acc = live ? r : k1_identity();
+#pragma unroll 1
+    for (uint32_t s = mpad >> 1; s > 0; s >>= 1) acc = k1_add(acc, k1_shfl_down(acc, s));
+    if (g < groups && j == 0) k1_store_affine(out + (size_t)g * 16, acc);
+}
+
+// Decoding (the reference's SWAffinePoint.string_to_point for a compressed string), one lane per 33-byte SEC1 encoding padded to 9
+// words (bytes 33..35 zero): byte 0 is 0x02 or 0x03, x = bytes 1..32 BIG-endian, x < p, x^3 + 7 a square, y the root of byte 0's
+// parity.  No string encodes the identity, so K1_DEC_CODEC (the codec alone) and K1_DEC_CHECK (also not the identity; the cofactor is
+// 1, so that is all valid_point asks) accept the same strings; both exist because the shared host templates name both.  There is no
+// try-and-increment mode: these suites hash to the curve with k_secp256k1_map_to_curve.
+enum { K1_DEC_CODEC = 0, K1_DEC_CHECK = 1 };
+template <int MODE>
+__global__ __launch_bounds__(K1_BLOCK) void k_secp256k1_decode_points(const uint32_t* __restrict__ enc /* n*9 */, uint32_t* __restrict__ out_xy /* n*16 */,
+                                                                      uint32_t* __restrict__ ok, uint32_t n) {
+    const int lane = threadIdx.x;
+    uint32_t i = blockIdx.x * K1_BLOCK + lane;
+    const bool live = i < n;
+    if (!live) i = n - 1;
+    uint32_t w[9];
+#pragma unroll
+    for (int j = 0; j < 9; j++) w[j] = enc[(size_t)i * 9 + j];
+    const uint32_t first = w[0] & 0xffu;
+    uint32_t xb[8];                  // little-endian word q is the byte swap of the (unaligned) word at byte 29 - 4 q
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+        const int k = 7 - q;
+        xb[q] = __builtin_bswap32((w[k] >> 8) | (w[k + 1] << 24));
+    }
+    uint32_t borrow = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) (void)subb(xb[j], FsecpConsts::PW[j], borrow);
+    const FK x = fk_unpack(xb);
+    FK y;
+    const bool root = fk_sqrt(carry(add(mul(sqr(x), x), FK::small(7))), y);
+    const bool valid = (first == 0x02u || first == 0x03u) && borrow != 0 && root;
+    uint32_t yw[8];
+    fk_pack(y, yw);
+    if ((yw[0] & 1u) != (first & 1u)) y = neg(y);          // (y = 0 cannot happen: -7 is not a cube mod p, the group order is odd)
+    if (live) {
+        if (valid) {
+            k1_store8(out_xy + (size_t)i * 16, xb);
+            k1_store_fe(out_xy + (size_t)i * 16 + 8, y);
+        } else {
+            const uint32_t z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            k1_store8(out_xy + (size_t)i * 16, z);
+            k1_store8(out_xy + (size_t)i * 16 + 8, z);
+        }
+        ok[i] = valid ? 1u : 0u;
+    }
+}
+
+// ---------------------------------------------------------------- hashing to the curve: simplified SWU and an isogeny (RFC 9380)
+// The map's constants, one struct per target curve: E': y^2 = x^3 + A x + B with B and |Z| small (Z negative), sqrt(-Z), and the
+// isogeny E' -> E as four coefficient lists, highest degree first (the leading 1 of the denominators is implied), all as compile-time
+// limbs — nothing is indexed at run time, so nothing goes to scratch.  A curve whose SSWU needs no isogeny (P-256) is a struct with
+// ISOGENY = false and its own A, B, Z.
+struct Secp256k1Sswu {
+    using Fe = FK;
+    static constexpr bool ISOGENY = true;
+    static constexpr uint32_t B = 1771, NEG_Z = 11;
+    static constexpr uint32_t A[9] = {0x1a444533u, 0x02a23e00u, 0x1bc39750u, 0x07a6c796u, 0x1d272e95u, 0x0aac787au, 0x0b728229u, 0x157bacc3u, 0x003f8731u};
+    static constexpr uint32_t SQRT_NEG_Z[9] = {0x103c4a59u, 0x03394e41u, 0x11e2774au, 0x109e014eu, 0x02afeec1u, 0x1fd9c7c2u, 0x0f95eb44u, 0x004e4802u, 0x0031fdf3u};
+    // RFC 9380 appendix E.1: x_num k_(1,3..0), x_den k_(2,1..0), y_num k_(3,3..0), y_den k_(4,2..0)
+    static constexpr uint32_t XN3[9] = {0x0aaaa88cu, 0x11c71c6du, 0x038e38e3u, 0x071c71c7u, 0x0e38e38eu, 0x1c71c71cu, 0x18e38e38u, 0x11c71c71u, 0x008e38e3u};
+    static constexpr uint32_t XN2[9] = {0x1d9dd262u, 0x165e85a9u, 0x1f100c53u, 0x00c28806u, 0x1caece45u, 0x09ef6512u, 0x139b8a90u, 0x11a47e46u, 0x00534c32u};
+    static constexpr uint32_t XN1[9] = {0x117c6581u, 0x1ff88227u, 0x1d8ee4b7u, 0x0ba5f817u, 0x144c5d59u, 0x0ae753feu, 0x0756e7ccu, 0x19017864u, 0x0007d3d4u};
+    static constexpr uint32_t XN0[9] = {0x0aaaa8c7u, 0x11c71c6du, 0x038e38e3u, 0x071c71c7u, 0x0e38e38eu, 0x1c71c71cu, 0x18e38e38u, 0x11c71c71u, 0x008e38e3u};
+    static constexpr uint32_t XD1[9] = {0x0a8c6d14u, 0x0952b309u, 0x17906ef1u, 0x06d6c83eu, 0x0225406du, 0x196a8daau, 0x1077df12u, 0x1ec8707bu, 0x00edadc6u};
+    static constexpr uint32_t XD0[9] = {0x181eb49bu, 0x1f35ba2bu, 0x1e121f67u, 0x1a812a85u, 0x040dd86cu, 0x0665dbdbu, 0x062a728du, 0x0327b292u, 0x00d35771u};
+    static constexpr uint32_t YN3[9] = {0x18e38d84u, 0x05ed0979u, 0x1684bda1u, 0x025ed097u, 0x0f684bdau, 0x1425ed09u, 0x12f684bdu, 0x1b425ed0u, 0x002f684bu};
+    static constexpr uint32_t YN2[9] = {0x1ecee931u, 0x1b2f42d4u, 0x0f880629u, 0x10614403u, 0x0e576722u, 0x04f7b289u, 0x09cdc548u, 0x08d23f23u, 0x0029a619u};
+    static constexpr uint32_t YN1[9] = {0x001d71a3u, 0x1fe487e1u, 0x01b69bf7u, 0x15608dadu, 0x0a6d5647u, 0x12a58950u, 0x103ea742u, 0x065ab96fu, 0x00c75e0cu};
+    static constexpr uint32_t YN0[9] = {0x0e38e23cu, 0x097b425cu, 0x1da12f68u, 0x1097b425u, 0x0bda12f6u, 0x0d097b42u, 0x04bda12fu, 0x1ed097b4u, 0x004bda12u};
+    static constexpr uint32_t YD2[9] = {0x1fd2a76fu, 0x1dfc0c95u, 0x0358a669u, 0x1a422c5eu, 0x0337e0a3u, 0x061fd47fu, 0x08b3ce9cu, 0x0e2ca8b9u, 0x006484aau};
+    static constexpr uint32_t YD1[9] = {0x085c2573u, 0x1da12e93u, 0x1a365e37u, 0x0f837f91u, 0x0c298946u, 0x13319391u, 0x127f57a7u, 0x097717b6u, 0x007a0653u};
+    static constexpr uint32_t YD0[9] = {0x1ffff93bu, 0x1ffffff7u, 0x1fffffffu, 0x1fffffffu, 0x1fffffffu, 0x1fffffffu, 0x1fffffffu, 0x1fffffffu, 0x00ffffffu};
+};
+
+// Simplified SWU in the inversion-free form of RFC 9380 appendix F.2 with the sqrt_ratio of F.2.1.2 (p = 3 mod 4): one exponentiation,
+// selects instead of branches.  In: u (normal, canonical value) and its parity.  Out: the point (xn / xd, y) of E', xd != 0.  The
+// exceptional case tv2 = Z^2 u^4 + Z u^2 = 0 (u = 0 reaches it) takes xd = Z A, that is x1 = B / (Z A).  Every value is carried to
+// normal where it is made, so each product below is normal x normal.
+template <class C>
+DR_DEV void sswu_map(const FK& u, bool u_odd, FK& xn, FK& xd, FK& y) {
+    const FK A = FK::constant<C::A>();
+    const FK tv1 = carry(neg(mul_small(sqr(u), C::NEG_Z)));                  // Z u^2
+    FK tv2 = carry(add(sqr(tv1), tv1));                                      // Z^2 u^4 + Z u^2
+    const FK tv3 = mul_small(add(tv2, FK::small(1)), C::B);                  // B (tv2 + 1): the numerator of x1
+    const FK tv4 = mul(A, carry(select(fk_is_zero(tv2), FK::small(-(int32_t)C::NEG_Z), neg(tv2))));   // A Z or -A tv2: its denominator
+    FK tv6 = sqr(tv4);
+    tv2 = mul(carry(add(sqr(tv3), mul(A, tv6))), tv3);                       // tv3^3 + A tv3 tv4^2
+    tv6 = mul(tv6, tv4);                                                     // tv4^3: the denominator of gx1
+    tv2 = carry(add(tv2, mul_small(tv6, C::B)));                             // ... + B tv4^3: its numerator
+    // sqrt_ratio(tv2, tv6): y1 = sqrt(tv2 / tv6) if that is a square, sqrt(Z tv2 / tv6) otherwise
+    const FK s2 = mul(tv2, tv6);
+    const FK s1 = mul(sqr(tv6), s2);                                         // u v^3
+    const FK y1 = mul(fk_pow_p34(s1), s2);
+    const bool is_square = fk_equal(mul(sqr(y1), tv6), tv2);
+    const FK y2 = mul(y1, FK::constant<C::SQRT_NEG_Z>());
+    const FK yb = mul(mul(tv1, u), y2);                                      // the root for x2 = Z u^2 x1
+    xn = select(is_square, tv3, mul(tv1, tv3));
+    xd = tv4;
+    y = select(is_square, y1, yb);
+    y = carry(cneg(y, fk_is_odd(y) != u_odd));                               // sgn0(y) = sgn0(u)
+}
+
+// The isogeny E' -> E on (xn / xd, y), by Horner in xn with the powers of xd as the homogenising factors, kept projective:
+// (X : Y : Z) = (XN YD : y YN xd XD : xd XD YD) for x = XN / (xd XD), y' = y YN / YD.  ok = false when a denominator vanishes (Z = 0): the
+// kernel of the isogeny, which the reference reports as the failing modular inverse; hashing cannot reach it in practice.
+template <class C>
+DR_DEV K1Point sswu_iso_map(const FK& xn, const FK& xd, const FK& y, bool& ok) {
+    K1Point r;
+    if constexpr (!C::ISOGENY) {
+        r.x = xn; r.y = mul(y, xd); r.z = xd;
+        ok = true;
+        return r;
+    } else {
+        const FK d2 = sqr(xd), d3 = mul(d2, xd);
+        FK XN = mul2(FK::constant<C::XN3>(), xn, FK::constant<C::XN2>(), xd);
+        XN = mul2(XN, xn, FK::constant<C::XN1>(), d2);
+        XN = mul2(XN, xn, FK::constant<C::XN0>(), d3);
+        FK XD = carry(add(xn, mul(FK::constant<C::XD1>(), xd)));
+        XD = mul2(XD, xn, FK::constant<C::XD0>(), d2);
+        FK YN = mul2(FK::constant<C::YN3>(), xn, FK::constant<C::YN2>(), xd);
+        YN = mul2(YN, xn, FK::constant<C::YN1>(), d2);
+        YN = mul2(YN, xn, FK::constant<C::YN0>(), d3);
+        FK YD = carry(add(xn, mul(FK::constant<C::YD2>(), xd)));
+        YD = mul2(YD, xn, FK::constant<C::YD1>(), d2);
+        YD = mul2(YD, xn, FK::constant<C::YD0>(), d3);
+        const FK dx = mul(xd, XD);
+        r.x = mul(XN, YD);
+        r.y = mul(mul(y, YN), dx);
+        r.z = mul(dx, YD);
+        ok = !fk_is_zero(r.z);
+        return r;
+    }
+}
+
+// out[i] = the sum of the images of item i's `per_item` field elements (2: the uniform (RO) encoding, 1: the nonuniform one), u: n x
+// per_item x 8 words (canonical, checked by the host), out: n x 16 words affine x || y, ok[i] = 0 where an isogeny denominator
+// vanished.  One lane per item; one exponentiation per element and one inversion per item.
+__global__ __launch_bounds__(K1_BLOCK) void k_secp256k1_map_to_curve(const uint32_t* __restrict__ us, uint32_t* __restrict__ out_xy,
+                                                                     uint32_t* __restrict__ ok, uint32_t n, uint32_t per_item) {
+    uint32_t i = blockIdx.x * K1_BLOCK + threadIdx.x;
+    const bool live = i < n;
+    if (!live) i = n - 1;
+    K1Point acc = k1_identity();
+    bool good = true;
+#pragma unroll 1
+    for (uint32_t e = 0; e < per_item; e++) {
+        uint32_t w[8];
+        k1_load8(us + ((size_t)i * per_item + e) * 8, w);
+        FK xn, xd, y;
+        sswu_map<Secp256k1Sswu>(fk_unpack(w), (w[0] & 1u) != 0, xn, xd, y);
+        bool ok_e;
+        const K1Point q = sswu_iso_map<Secp256k1Sswu>(xn, xd, y, ok_e);
+        good = good && ok_e;
+        acc = k1_add(acc, q);
+    }
+    if (live) {
+        k1_store_affine(out_xy + (size_t)i * 16, acc);
+        ok[i] = good ? 1u : 0u;
+    }
+}
+
+// Diagnostic (dr_secp256k1_field_selftest): fsecp256k1.hip.h's operations on raw limb images, one lane per (a, b) pair of 9 int32 limbs
+// each, so that tests can drive every operation at the limb bounds its contract allows.  out[i] = twelve canonical 32-byte records:
+// a b, a^2, a + b, a - b, -a, carry(a), a b + b a (mul2), a^-1 (0 for 0), sqrt(a) or 0, a itself (pack), 21 a (mul_small),
+// sqr(carry(a)) (the fused case fk_fold_top's note is about).  flags[i]: bit 0 a is a square, bit 1 the canonical a is odd.
+constexpr int K1_SELFTEST_RECORDS = 12;
+__global__ __launch_bounds__(64) void k_secp256k1_field_selftest(const int32_t* __restrict__ a_limbs, const int32_t* __restrict__ b_limbs, uint32_t n,
+                                                                uint32_t* __restrict__ out, uint32_t* __restrict__ flags) {
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    FK a, b;
+#pragma unroll
+    for (int t = 0; t < FK_L; t++) { a.l[t] = a_limbs[(size_t)i * FK_L + t]; b.l[t] = b_limbs[(size_t)i * FK_L + t]; }
+    uint32_t* o = out + (size_t)i * K1_SELFTEST_RECORDS * 8;
+    k1_store_fe(o + 0, mul(a, b));
+    k1_store_fe(o + 8, sqr(a));
+    k1_store_fe(o + 16, add(a, b));
+    k1_store_fe(o + 24, sub(a, b));
+    k1_store_fe(o + 32, neg(a));
+    k1_store_fe(o + 40, carry(a));
+    k1_store_fe(o + 48, mul2(a, b, b, a));
+    k1_store_fe(o + 56, fk_inv(carry(a)));
+    FK r;
+    const bool sq = fk_sqrt(carry(a), r);
+    k1_store_fe(o + 64, r);
+    uint32_t w[8];
+    fk_pack(a, w);
+    k1_store8(o + 72, w);
+    k1_store_fe(o + 80, mul_small(a, K1_B3));
+    k1_store_fe(o + 88, sqr(carry(a)));
+    flags[i] = (sq ? 1u : 0u) | ((w[0] & 1u) ? 2u : 0u);
+}
+
+}  // namespace dr

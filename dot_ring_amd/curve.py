@@ -7,6 +7,9 @@ Mirrors (names, argument meaning, error behaviour) the parts of the reference th
                                                 try-and-increment; the kernels compute on its twisted Edwards image
   dot_ring/curve/specs/p256.py                  P256 (= P256_TAI): NIST P-256, its own field, 33-byte codec with a SEC1 fallback,
                                                 try-and-increment with SHA-256; kernels of their own (DR_CURVE_P256)
+  dot_ring/curve/specs/secp256k1.py             Secp256k1 (= Secp256k1_RO), Secp256k1_NU: its own field, plain SEC1 33-byte codec, RFC 9380
+                                                hashing to the curve (SHA-256 XMD, simplified SWU, 3-isogeny); kernels of their own
+                                                (DR_CURVE_SECP256K1 / DR_CURVE_SECP256K1_NU)
   dot_ring/curve/specs/baby_jubjub.py           BabyJubJub: a = 1 over the BN254 scalar field, cofactor 8, try-and-increment with
                                                 SHA-512 (candidates masked to the field's 254 bits); kernels of their own (DR_CURVE_BABYJUBJUB)
   dot_ring/curve/point.py:150-214               compressed codec
@@ -63,7 +66,7 @@ class SuiteParams:
     )
     encoding: Encoding = Encoding()
     curve_id: int = _native.CURVE_BANDERSNATCH      # DR_CURVE_* of include/dotring_hip.h
-    e2c: str = "ell2"                               # "ell2" (Elligator 2, RO) or "tai" (try and increment)
+    e2c: str = "ell2"                               # "ell2" (Elligator 2, RO), "tai" (try and increment), "sswu" / "sswu_nu" (RFC 9380)
 
     @property
     def h2c_dst(self) -> bytes:
@@ -663,6 +666,195 @@ class P256Point:
         return unpack_points(cls, runtime.context().encode_to_curve_batch(cls._suite_struct(), list(alpha_strings), salts))
 
 
+class Secp256k1Point:
+    """Affine point of secp256k1 (dot_ring/curve/specs/secp256k1.py): y^2 = x^3 + 7 over its own field, cofactor 1, the identity is
+    (None, None).  Single additions are host big-int code; scalar multiplications, MSMs, decoding and hashing to the curve (RFC 9380:
+    simplified SWU and the 3-isogeny) run on the GPU under the suite's curve id (kernels_secp256k1.hip.h)."""
+    curve: BandersnatchCurve
+    _P = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEFFFFFC2F
+    _N = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141
+    _H, _CV = 1, _native.CURVE_SECP256K1
+    _SW_A, _SW_B = 0, 7
+    __slots__ = ("x", "y")
+
+    def __init__(self, x, y):
+        self.x, self.y = x, y
+        if x is None and y is None:
+            return
+        if x is None or y is None or not (0 <= x < self._P and 0 <= y < self._P):
+            raise ValueError("Invalid point coordinates")
+        if not self._on_curve(x, y):
+            raise ValueError("Point is not on the curve")
+
+    @classmethod
+    def _on_curve(cls, x: int, y: int) -> bool:
+        return (y * y - (x * x * x + cls._SW_B)) % cls._P == 0
+
+    @classmethod
+    def _trusted(cls, x: int, y: int):
+        """Kernel outputs: 64 zero bytes are the identity."""
+        pt = object.__new__(cls)
+        pt.x, pt.y = (None, None) if x == 0 and y == 0 else (x, y)
+        return pt
+
+    def __eq__(self, other):
+        return isinstance(other, Secp256k1Point) and self.x == other.x and self.y == other.y
+
+    def __hash__(self):
+        return 0 if self.x is None else (self.x + self.y) % self._N
+
+    def __repr__(self):
+        return f"{type(self).__name__}({self.x}, {self.y})"
+
+    @classmethod
+    def identity(cls):
+        return cls(None, None)
+
+    @classmethod
+    def generator_point(cls):
+        return cls(*cls.curve.params.generator)
+
+    def is_identity(self) -> bool:
+        return self.x is None and self.y is None
+
+    def is_on_curve(self) -> bool:
+        return self.is_identity() or self._on_curve(self.x, self.y)
+
+    # -- group law (sw_affine_point.py)
+    def __add__(self, other):
+        if not isinstance(other, Secp256k1Point):
+            raise TypeError("Can only add SWAffinePoint instances")
+        if self.is_identity():
+            return other
+        if other.is_identity():
+            return self
+        p = self._P
+        if self.x == other.x:
+            return self.double() if self.y == other.y else self.identity()
+        lam = (other.y - self.y) * pow(other.x - self.x, -1, p) % p
+        x3 = (lam * lam - self.x - other.x) % p
+        return type(self)(x3, (lam * (self.x - x3) - self.y) % p)
+
+    def double(self):
+        if self.is_identity() or self.y == 0:
+            return self.identity()
+        p = self._P
+        lam = 3 * self.x * self.x * pow(2 * self.y, -1, p) % p
+        x3 = (lam * lam - 2 * self.x) % p
+        return type(self)(x3, (lam * (self.x - x3) - self.y) % p)
+
+    def __neg__(self):
+        return self if self.is_identity() else type(self)(self.x, -self.y % self._P)
+
+    def __sub__(self, other):
+        return self + (-other)
+
+    def __mul__(self, scalar: int):
+        """secp256k1.py:85-93: the scalar reduced mod n (a negative one through -P), 0 gives the identity"""
+        return scalar_mul_batch([self], [scalar])[0]
+
+    __rmul__ = __mul__
+
+    @classmethod
+    def msm(cls, points, scalars):
+        if len(points) != len(scalars):
+            raise ValueError("Points and scalars must have same length")
+        if not points:
+            return cls.identity()
+        raw = runtime.context().bsn_msm(pack_points(points), pack_scalars(scalars, cls._N), cls._CV)
+        return cls._trusted(int.from_bytes(raw[:32], "little"), int.from_bytes(raw[32:], "little"))
+
+    def clear_cofactor(self):
+        return self
+
+    # -- codec: SEC1 (sw_affine_point.py point_to_string / string_to_point)
+    def point_to_string(self, compressed: bool = True) -> bytes:
+        if self.is_identity():
+            return b"\x00"
+        x = self.x.to_bytes(32, "big")
+        if compressed:
+            return (b"\x03" if self.y % 2 else b"\x02") + x
+        return b"\x04" + x + self.y.to_bytes(32, "big")
+
+    @classmethod
+    def string_to_point(cls, data):
+        if isinstance(data, str):
+            data = bytes.fromhex(data)
+        data = bytes(data)
+        if len(data) == 0:
+            raise ValueError("Empty octet string")
+        prefix, p = data[0], cls._P
+        if prefix == 0x00:
+            if len(data) != 1:
+                raise ValueError("Point at infinity must be single byte 0x00")
+            return cls.identity()
+        if prefix in (0x02, 0x03):
+            if len(data) != 33:
+                raise ValueError(f"Invalid compressed point length: expected 33, got {len(data)}")
+            x = int.from_bytes(data[1:], "big")
+            if x >= p:
+                raise ValueError(f"x-coordinate {x} is not in field Fp (p={p})")
+            try:
+                y = cls.curve.mod_sqrt((x * x * x + cls._SW_B) % p)
+            except ValueError:
+                raise ValueError("Invalid point encoding") from None
+            if y % 2 != prefix % 2:
+                y = p - y
+            return cls(x, y)
+        if prefix == 0x04:
+            if len(data) != 65:
+                raise ValueError(f"Invalid uncompressed point length: expected 65, got {len(data)}")
+            x, y = int.from_bytes(data[1:33], "big"), int.from_bytes(data[33:], "big")
+            if x >= p:
+                raise ValueError(f"x-coordinate {x} is not in field Fp (p={p})")
+            if y >= p:
+                raise ValueError(f"y-coordinate {y} is not in field Fp (p={p})")
+            if not cls._on_curve(x, y):
+                raise ValueError(f"Point ({x}, {y}) is not on curve")
+            return cls(x, y)
+        raise ValueError(f"Invalid point encoding prefix: 0x{prefix:02x}")
+
+    # -- hash to curve (RFC 9380; sw_affine_point.py:428-562): expand_message_xmd natively on the host, the map on the GPU
+    _suite_struct = BandersnatchPoint.__dict__["_suite_struct"]
+
+    @classmethod
+    def _per_item(cls) -> int:
+        return 1 if cls.curve.params.e2c == "sswu_nu" else 2
+
+    @classmethod
+    def _mapped(cls, us: bytes, per_item: int):
+        raw, ok = runtime.context().secp256k1_map_to_curve(us, per_item)
+        if 0 in ok:
+            raise ValueError("base is not invertible for the given modulus")      # pow(x_den, -1, p) of apply_isogeny
+        return unpack_points(cls, raw)
+
+    @classmethod
+    def map_to_curve_simple_swu(cls, u: int):
+        return cls._mapped((int(u) % cls._P).to_bytes(32, "little"), 1)[0]
+
+    @classmethod
+    def hash_to_field_pairs(cls, alpha_strings, salts=None) -> bytes:
+        """Host half of encode_to_curve for many inputs: two field elements per input (one for the NU variant), packed little-endian."""
+        salts = salts or [b""] * len(alpha_strings)
+        return _native.hash_to_field_batch(cls._suite_struct(), [bytes(s) + bytes(a) for a, s in zip(alpha_strings, salts)])
+
+    @classmethod
+    def encode_to_curve_from_field(cls, us: bytes):
+        """Device half: the maps (and for RO the sum of the two images) for packed field elements."""
+        return cls._mapped(us, cls._per_item()) if us else []
+
+    @classmethod
+    def encode_to_curve(cls, alpha_string: bytes, salt: bytes = b""):
+        return cls.encode_to_curve_batch([alpha_string], [salt])[0]
+
+    @classmethod
+    def encode_to_curve_batch(cls, alpha_strings, salts=None):
+        if not alpha_strings:
+            return []
+        # (a vanishing isogeny denominator comes back as DR_ERR_INVALID: a ValueError, as the reference's failing modular inverse is)
+        return unpack_points(cls, runtime.context().encode_to_curve_batch(cls._suite_struct(), list(alpha_strings), salts))
+
+
 # ------------------------------------------------------------------ batched helpers over the C ABI
 def pack_points(points) -> bytes:
     """x || y little-endian per point; an SW identity ((None, None)) packs as 64 zero bytes, as the ABI takes it."""
@@ -719,7 +911,7 @@ def valid_points(points) -> list[bool]:
     if not live:
         return out
     h, order = type(points[live[0]])._H, type(points[live[0]])._N
-    if h == 1:                               # prime order (P-256): on the curve and not the identity (curve.py:61)
+    if h == 1:                               # prime order (P-256, secp256k1): on the curve and not the identity (curve.py:61)
         for i in live:
             out[i] = True
         return out
@@ -762,7 +954,7 @@ class CurveVariant:
         self.name, self.curve, self.point_type = name, curve, point_type
 
     def point(self, x, y=None):
-        if isinstance(x, (BandersnatchPoint, BandersnatchSWPoint, P256Point)):
+        if isinstance(x, (BandersnatchPoint, BandersnatchSWPoint, P256Point, Secp256k1Point)):
             return x
         if y is None:
             x, y = x
@@ -910,3 +1102,33 @@ BabyJubJub = _suite(
     curve_id=_native.CURVE_BABYJUBJUB,
     e2c="tai",
 )
+
+# dot_ring/curve/specs/secp256k1.py: y^2 = x^3 + 7 over 2^256 - 2^32 - 977, cofactor 1, 33-byte SEC1 points, SHA-256, hashing to the curve by
+# RFC 9380's secp256k1_XMD:SHA-256_SSWU_RO_ (two field elements) or ..._NU_ (one); both variants carry the RO suite id, as in the
+# reference.  No accumulator base or padding point, and not twisted Edwards, so RingProofParams refuses them.  Every group operation and
+# the map run on the secp256k1 kernels (DR_CURVE_SECP256K1 / DR_CURVE_SECP256K1_NU).
+def _secp256k1_variant(name: str, e2c: str, curve_id: int) -> CurveVariant:
+    params = SuiteParams(
+        suite_id=b"secp256k1_XMD:SHA-256_SSWU_RO_", hash_fn=hashlib.sha256, xof=False,
+        auxiliary_points=AuxiliaryPoints(
+            (0x50929B74C1A04954B78B4B6035E97A5E078A5A0F28EC96D547BFEE9ACE803AC0,
+             0x31D3C6863973926E049E637CB1B5F40A36DAC28AF1766968C30C2313F3A38904),
+            None, None),
+        field_modulus=Secp256k1Point._P,
+        subgroup_order=Secp256k1Point._N,
+        cofactor=1,
+        a=0,
+        d=0,
+        generator=(0x79BE667EF9DCBBAC55A06295CE870B07029BFCDB2DCE28D959F2815B16F81798,
+                   0x483ADA7726A3C4655DA4FBFC0E1108A8FD17B448A68554199C47D08FFB10D4B8),
+        encoding=Encoding(point_len=33),
+        curve_id=curve_id,
+        e2c=e2c,
+    )
+    curve = BandersnatchCurve(params)
+    return CurveVariant(name, curve, type(f"{name}Point", (Secp256k1Point,), {"__slots__": (), "curve": curve, "_CV": curve_id}))
+
+
+Secp256k1_RO = _secp256k1_variant("Secp256k1_RO", "sswu", _native.CURVE_SECP256K1)
+Secp256k1_NU = _secp256k1_variant("Secp256k1_NU", "sswu_nu", _native.CURVE_SECP256K1_NU)
+Secp256k1 = Secp256k1_RO

@@ -141,6 +141,16 @@ enum { DR_CURVE_P256 = 4 };
  * Every call runs on the kernels (no host route).  The ring prover, the Ring-VRF calls, dr_ietf_verify_batch and the dr_bsn_* calls
  * refuse it. */
 enum { DR_CURVE_BABYJUBJUB = 5 };
+/* DR_CURVE_SECP256K1 (the reference's Secp256k1 = Secp256k1_RO) and DR_CURVE_SECP256K1_NU (Secp256k1_NU): secp256k1
+ * (dot_ring/curve/specs/secp256k1.py: y^2 = x^3 + 7, cofactor 1, n of 256 bits) over its own field 2^256 - 2^32 - 977 — its own kernels
+ * (csrc/kernels_secp256k1.hip.h, field csrc/fsecp256k1.hip.h).  The two ids differ only in how they hash to the curve (RFC 9380,
+ * secp256k1_XMD:SHA-256_SSWU_RO_: two field elements and the sum of their images; ..._NU_: one), and they share one suite id, which is
+ * why the variant is part of the curve id.  Raw points are affine x || y little-endian, coordinates below p, 64 zero bytes for the
+ * identity; encodings are 33 bytes, plain SEC1 compressed: 0x02 / 0x03 by the parity of y, then x BIG-endian (no string encodes the
+ * identity).  Scalars are reduced mod n on the device.  Accepted by the same entry points as DR_CURVE_P256 (dr_te_decode_points: prefix,
+ * x below p, a root); dr_vrf_suite.xof must be 2.  The ring prover, the Ring-VRF calls, dr_ietf_verify_batch, the GLV and dr_bsn_*
+ * entry points refuse them. */
+enum { DR_CURVE_SECP256K1 = 6, DR_CURVE_SECP256K1_NU = 7 };
 DR_API int dr_te_scalar_mul_batch(dr_ctx *ctx, int curve, const uint8_t *pts_xy, const uint8_t *scalars, size_t n, uint8_t *out_xy);
 DR_API int dr_te_msm(dr_ctx *ctx, int curve, const uint8_t *pts_xy, const uint8_t *scalars, size_t n, uint8_t out_xy[64]);
 DR_API int dr_te_msm_groups(dr_ctx *ctx, int curve, const uint8_t *pts_xy, const uint8_t *scalars, size_t groups, size_t m, uint8_t *out_xy);
@@ -182,6 +192,20 @@ DR_API int dr_p256_decode_points(dr_ctx *ctx, int check, const uint8_t *enc /* n
  * square, bit 1 a > p - a, bit 2 a is odd. */
 DR_API int dr_p256_field_ops_selftest(dr_ctx *ctx, const int32_t *a_limbs /* n*9 */, const int32_t *b_limbs /* n*9 */, size_t n,
                                       uint8_t *out /* n*384 */, uint8_t *flags /* n */);
+/* secp256k1 point decoding (SEC1 compressed, 33 bytes): check = 1 as dr_te_decode_points for DR_CURVE_SECP256K1, check = 0 the codec
+ * alone — the same strings, since none encodes the identity.  ok[i] = 1 when accepted; out_xy[i] is then x || y, otherwise 64 zero bytes. */
+DR_API int dr_secp256k1_decode_points(dr_ctx *ctx, int check, const uint8_t *enc /* n*33 */, size_t n, uint8_t *out_xy /* n*64 */, uint8_t *ok /* n */);
+/* Diagnostic: the device's arithmetic in GF(2^256 - 2^32 - 977) (csrc/fsecp256k1.hip.h) on RAW limb images — 9 signed 32-bit limbs each,
+ * value sum l[i] 2^(29 i), plain (no Montgomery form).  out: n x 12 x 32 bytes of canonical little-endian results: a b, a^2, a + b, a - b,
+ * -a, carry(a), a b + b a (fused), carry(a)^-1 (0 for 0), sqrt(carry(a)) or 0, a, 21 a (mul_small), carry(a)^2.  flags[i]: bit 0 a is a
+ * square, bit 1 a is odd. */
+DR_API int dr_secp256k1_field_selftest(dr_ctx *ctx, const int32_t *a_limbs /* n*9 */, const int32_t *b_limbs /* n*9 */, size_t n,
+                                       uint8_t *out /* n*384 */, uint8_t *flags /* n */);
+/* The map of RFC 9380 onto secp256k1 (simplified SWU onto the isogenous curve, the 3-isogeny back): n items of per_item field elements
+ * (32 bytes little-endian each, below p; 2: the uniform (RO) encoding, 1: the nonuniform one), out_xy[i] = the sum of item i's images,
+ * affine x || y.  ok[i] = 0 where a denominator of the isogeny is zero (the reference raises there; hashing cannot reach it in practice). */
+DR_API int dr_secp256k1_map_to_curve(dr_ctx *ctx, const uint8_t *us /* n*per_item*32 */, size_t n, int per_item, uint8_t *out_xy /* n*64 */,
+                                     uint8_t *ok /* n */);
 /* Baby JubJub point decoding with the prime-order check (check = 1: as dr_te_decode_points for DR_CURVE_BABYJUBJUB) or the codec
  * alone (check = 0: y < p and a root; (0, 1) and (0, p - 1) decode whatever the sign bit).  ok[i] = 1 when accepted; out_xy[i] is
  * then x || y, otherwise 64 zero bytes. */
@@ -381,22 +405,25 @@ typedef struct dr_vrf_suite {
     const uint8_t *suite_id;        /* e.g. "Bandersnatch-SHA512-ELL2-v1" (bandersnatch.py:74-87) */
     size_t suite_id_len;
     int xof;                        /* 1: SHAKE128 suite, 0: SHA-512 (counter-mode squeeze, expand_message_xmd), 2: SHA-256 (counter-mode
-                                       squeeze, the P-256 suite); other values are refused */
+                                       squeeze, the P-256 and secp256k1 suites); other values are refused */
     uint8_t generator_xy[64];       /* group generator, x||y little-endian */
     uint8_t blinding_base_xy[64];   /* Pedersen blinding base (bandersnatch.py:89-102) */
     int curve;                      /* DR_CURVE_BANDERSNATCH (Elligator 2 hash-to-curve), DR_CURVE_JUBJUB, DR_CURVE_BANDERSNATCH_SW,
                                        DR_CURVE_ED25519, DR_CURVE_P256 or DR_CURVE_BABYJUBJUB (try-and-increment; for the SW suite and P-256 generator and
-                                       blinding base are SW affine) */
+                                       blinding base are SW affine), DR_CURVE_SECP256K1 or DR_CURVE_SECP256K1_NU (RFC 9380 simplified SWU) */
 } dr_vrf_suite;
 
 /* hash_to_field(msg, 2) for `count` messages msgs[off[i]..off[i+1]): out = count * 2 field elements (32-byte LE),
- * the input format of dr_bsn_encode_to_curve_batch. */
+ * the input format of dr_bsn_encode_to_curve_batch.  For DR_CURVE_SECP256K1 the two elements are those of RFC 9380's
+ * expand_message_xmd with SHA-256 (the input format of dr_secp256k1_map_to_curve with per_item = 2); for DR_CURVE_SECP256K1_NU it is
+ * hash_to_field(msg, 1): ONE element, 32 bytes, per message.  Host only: no context. */
 DR_API int dr_hash_to_field_batch(const dr_vrf_suite *suite, const uint8_t *msgs, const uint64_t *off /* count+1 */, size_t count,
                                   uint8_t *out_u_pairs);
 
 /* encode_to_curve(salt_i || msg_i) for `count` messages (salts / salt_off nullable), whichever way the suite's curve hashes:
  * Elligator 2 (hash_to_field here + dr_bsn_encode_to_curve_batch) or try-and-increment (dot_ring/curve/point.py:252-296:
- * candidates hashed on worker threads, decompressed and cofactor-cleared on the GPU, several counters per launch). */
+ * candidates hashed on worker threads, decompressed and cofactor-cleared on the GPU, several counters per launch) or, for
+ * the secp256k1 suites, RFC 9380 (hash_to_field on worker threads + one launch of dr_secp256k1_map_to_curve's kernel). */
 DR_API int dr_encode_to_curve_batch(dr_ctx *ctx, const dr_vrf_suite *suite, const uint8_t *msgs, const uint64_t *off /* count+1 */,
                                     const uint8_t *salts, const uint64_t *salt_off, size_t count, uint8_t *out_xy /* count*64 */);
 
