@@ -113,6 +113,8 @@ _PROTOTYPES.update({
     "dr_secp256k1_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
     "dr_secp256k1_field_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p, c_void_p]),
     "dr_secp256k1_map_to_curve": (c_int, [c_void_p, c_char_p, c_size_t, c_int, c_char_p, c_char_p]),
+    "dr_p256_map_to_curve": (c_int, [c_void_p, c_char_p, c_size_t, c_int, c_char_p, c_char_p]),
+    "dr_ed25519_map_to_curve": (c_int, [c_void_p, c_char_p, c_size_t, c_int, c_char_p, c_char_p]),
     "dr_bjj_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
     "dr_bjj_field_ops_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p, c_void_p]),
     "dr_encode_to_curve_batch": (c_int, [c_void_p, POINTER(VrfSuiteStruct), c_char_p, POINTER(ctypes.c_uint64), c_char_p,
@@ -198,8 +200,11 @@ def _ragged(items):
 
 CURVE_BANDERSNATCH, CURVE_JUBJUB, CURVE_BANDERSNATCH_SW, CURVE_ED25519, CURVE_P256, CURVE_BABYJUBJUB = 0, 1, 2, 3, 4, 5
 CURVE_SECP256K1, CURVE_SECP256K1_NU = 6, 7
+CURVE_P256_RO, CURVE_P256_NU, CURVE_ED25519_RO, CURVE_ED25519_NU = 8, 9, 10, 11
 # bytes of an encoded point, per curve id (the suites with 33-byte encodings; every other curve's are 32)
-_POINT_LEN = {CURVE_BANDERSNATCH_SW: 33, CURVE_P256: 33, CURVE_SECP256K1: 33, CURVE_SECP256K1_NU: 33}
+_POINT_LEN = {CURVE_BANDERSNATCH_SW: 33, CURVE_P256: 33, CURVE_SECP256K1: 33, CURVE_SECP256K1_NU: 33, CURVE_P256_RO: 33, CURVE_P256_NU: 33}
+# the nonuniform RFC 9380 suites: one field element per message
+_NU_CURVES = (CURVE_SECP256K1_NU, CURVE_P256_NU, CURVE_ED25519_NU)
 
 
 def curve_point_len(curve: int) -> int:
@@ -270,11 +275,11 @@ def random_expand(seed32: bytes, nbytes: int) -> bytes:
 
 
 def hash_to_field_batch(suite: VrfSuiteStruct, msgs) -> bytes:
-    """dr_hash_to_field_batch: two elements (64 bytes) per message; one (32 bytes) for the nonuniform secp256k1 suite"""
+    """dr_hash_to_field_batch: two elements (64 bytes) per message; one (32 bytes) for the nonuniform RFC 9380 suites"""
     blob, off = _ragged(msgs)
     out = ctypes.create_string_buffer(max(1, 64 * len(msgs)))
     _check(lib().dr_hash_to_field_batch(byref(suite), blob, off, len(msgs), out))
-    return out.raw[: (32 if suite.curve == CURVE_SECP256K1_NU else 64) * len(msgs)]
+    return out.raw[: (32 if suite.curve in _NU_CURVES else 64) * len(msgs)]
 
 
 
@@ -611,14 +616,25 @@ class Context:
         """dr_secp256k1_field_selftest: (n x 12 x 32 result bytes, n flag bytes) for n pairs of raw 9-limb images."""
         return self._limb_selftest(lib().dr_secp256k1_field_selftest, 12, a_limbs, b_limbs)
 
-    def secp256k1_map_to_curve(self, us: bytes, per_item: int):
-        """dr_secp256k1_map_to_curve: (x||y bytes, flags) for len(us) / (32 per_item) items of per_item field elements each."""
+    def _map_to_curve(self, fn, us: bytes, per_item: int):
         if per_item not in (1, 2) or len(us) % (32 * per_item):
             raise ValueError("field elements are 32 bytes each, one or two per item")
         n = len(us) // (32 * per_item)
         out, ok = ctypes.create_string_buffer(max(1, 64 * n)), ctypes.create_string_buffer(max(1, n))
-        _check(lib().dr_secp256k1_map_to_curve(self.handle, us, n, per_item, out, ok))
+        _check(fn(self.handle, us, n, per_item, out, ok))
         return out.raw[: 64 * n], ok.raw[:n]
+
+    def secp256k1_map_to_curve(self, us: bytes, per_item: int):
+        """dr_secp256k1_map_to_curve: (x||y bytes, flags) for len(us) / (32 per_item) items of per_item field elements each."""
+        return self._map_to_curve(lib().dr_secp256k1_map_to_curve, us, per_item)
+
+    def p256_map_to_curve(self, us: bytes, per_item: int):
+        """dr_p256_map_to_curve: as secp256k1_map_to_curve, onto P-256."""
+        return self._map_to_curve(lib().dr_p256_map_to_curve, us, per_item)
+
+    def ed25519_map_to_curve(self, us: bytes, per_item: int):
+        """dr_ed25519_map_to_curve: as secp256k1_map_to_curve, onto Ed25519's prime-order subgroup (flags 0: no image)."""
+        return self._map_to_curve(lib().dr_ed25519_map_to_curve, us, per_item)
 
     def ed25519_decode_points(self, enc: bytes, check: bool = True):
         """dr_ed25519_decode_points: (x||y bytes, flags) for len(enc)/32 encodings, with or without the prime-order check."""

@@ -517,6 +517,15 @@ struct P256Suite : NoConsts {
     static const drh::Mod256& field() { return drh::mod_p256(); }
     static constexpr size_t identity_y = 0, enc_bytes = 33, rec_bytes = 36, tai_bytes = 33;   // 64 zero bytes are the identity; candidates carry the flag byte
 };
+// P256_RO / P256_NU (curves 8 and 9): P-256's kernels with the plain SEC1 modes of its decoder (the reference's generic short
+// Weierstrass encoding, not P256_TAI's; no string encodes the identity, so checking and codec-only decoding coincide and no entry point
+// asks for the latter); no try-and-increment, so dec_tai is the checking decoder and tai_bytes never applies
+struct P256Sec1Suite : P256Suite {
+    static constexpr auto dec_tai = dr::k_p256_decode_points<dr::P256_DEC_SEC1>, dec_check = dr::k_p256_decode_points<dr::P256_DEC_SEC1>,
+                          dec_codec = dr::k_p256_decode_points<dr::P256_DEC_SEC1>;
+    static constexpr const char* name = "P-256 (RFC 9380)";
+};
+static_assert(P256Sec1Suite::dec_codec == P256Sec1Suite::dec_check, "one SEC1 decoder: a caller of either gets this format, never P256_TAI's");
 // secp256k1 (curves 6 and 7): no try-and-increment, so dec_tai is the checking decoder again and encode_to_curve_msgs never takes that
 // branch for these curves (they hash with k_secp256k1_map_to_curve)
 struct Secp256k1Suite : NoConsts {
@@ -617,7 +626,9 @@ template <class F>
 bool on_native(int cv, int& rc, F&& f) {
     switch (drh::te_curve(cv) ? drh::te_curve(cv)->native : drh::NativeSuite::none) {
         case drh::NativeSuite::ed25519: rc = f(Ed25519Suite{}); return true;
-        case drh::NativeSuite::p256: rc = f(P256Suite{}); return true;
+        case drh::NativeSuite::p256:
+            rc = drh::te_curve(cv)->sswu ? f(P256Sec1Suite{}) : f(P256Suite{});      // (ids 8 and 9: the SEC1 codec)
+            return true;
         case drh::NativeSuite::bjj: rc = f(BjjSuite{}); return true;
         case drh::NativeSuite::secp256k1: rc = f(Secp256k1Suite{}); return true;
         default: return false;
@@ -1164,8 +1175,12 @@ int dr_secp256k1_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_
 int dr_secp256k1_field_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
     return native_field_selftest(Secp256k1Suite{}, ctx, a_limbs, b_limbs, n, out, flags);
 }
-// the map of RFC 9380 for n items of per_item (1 or 2) field elements each: one launch, the sum of each item's images out
-int dr_secp256k1_map_to_curve(dr_ctx* ctx, const uint8_t* us, size_t n, int per_item, uint8_t* out_xy, uint8_t* ok) {
+// the maps of RFC 9380 for n items of per_item (1 or 2) field elements each: one launch of the curve's map kernel, the sum of each
+// item's images out (on Ed25519 with the cofactor cleared)
+namespace {
+using MapKernel = void (*)(const uint32_t*, uint32_t*, uint32_t*, uint32_t, uint32_t);
+int native_map_to_curve(dr_ctx* ctx, const char* name, MapKernel kernel, int block, const drh::Mod256& field, const uint8_t* us, size_t n,
+                        int per_item, uint8_t* out_xy, uint8_t* ok) {
     TRY(use_ctx(ctx));
     if (per_item != 1 && per_item != 2) return fail(DR_ERR_INVALID, "one (nonuniform) or two (uniform, RO) field elements per item");
     if (n == 0) return DR_OK;
@@ -1175,15 +1190,15 @@ int dr_secp256k1_map_to_curve(dr_ctx* ctx, const uint8_t* us, size_t n, int per_
     for (size_t i = 0; i < elems; i++) {
         uint64_t v[4];
         drh::load_le32(us + 32 * i, v);
-        if (drh::Mod256::geq(v, drh::mod_psecp256k1().m)) return fail(DR_ERR_INVALID, "input is not a canonical field element");
+        if (drh::Mod256::geq(v, field.m)) return fail(DR_ERR_INVALID, "input is not a canonical field element");
     }
     TRY(ctx->io_a.reserve(elems * 32));
     TRY(ctx->io_b.reserve(n * 64));
     TRY(ctx->io_c.reserve(n * 4));
     HIP_TRY(hipMemcpyAsync(ctx->io_a.p, us, elems * 32, hipMemcpyHostToDevice, ctx->stream));
-    TRY(launch(ctx, "k_secp256k1_map_to_curve", [&] {
-        hipLaunchKernelGGL(dr::k_secp256k1_map_to_curve, dim3(div_up(n, dr::K1_BLOCK)), dim3(dr::K1_BLOCK), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
-                           ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n, (uint32_t)per_item);
+    TRY(launch(ctx, name, [&] {
+        hipLaunchKernelGGL(kernel, dim3(div_up(n, block)), dim3(block), 0, ctx->stream, ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(),
+                           ctx->io_c.as<uint32_t>(), (uint32_t)n, (uint32_t)per_item);
     }));
     std::vector<uint32_t> flags(n);
     HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_b.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
@@ -1192,6 +1207,18 @@ int dr_secp256k1_map_to_curve(dr_ctx* ctx, const uint8_t* us, size_t n, int per_
     if (ctx->prof) TRY(prof_collect(ctx));
     for (size_t i = 0; i < n; i++) ok[i] = flags[i] ? 1 : 0;
     return DR_OK;
+}
+}  // namespace
+int dr_secp256k1_map_to_curve(dr_ctx* ctx, const uint8_t* us, size_t n, int per_item, uint8_t* out_xy, uint8_t* ok) {
+    return native_map_to_curve(ctx, "k_secp256k1_map_to_curve", dr::k_secp256k1_map_to_curve, dr::K1_BLOCK, drh::mod_psecp256k1(), us, n, per_item,
+                               out_xy, ok);
+}
+int dr_p256_map_to_curve(dr_ctx* ctx, const uint8_t* us, size_t n, int per_item, uint8_t* out_xy, uint8_t* ok) {
+    return native_map_to_curve(ctx, "k_p256_map_to_curve", dr::k_p256_map_to_curve, dr::P256_BLOCK, drh::mod_p256(), us, n, per_item, out_xy, ok);
+}
+int dr_ed25519_map_to_curve(dr_ctx* ctx, const uint8_t* us, size_t n, int per_item, uint8_t* out_xy, uint8_t* ok) {
+    return native_map_to_curve(ctx, "k_ed25519_map_to_curve", dr::k_ed25519_map_to_curve, dr::ED_BLOCK, drh::mod_p25519(), us, n, per_item, out_xy,
+                               ok);
 }
 int dr_bjj_field_ops_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
     return native_field_selftest(BjjSuite{}, ctx, a_limbs, b_limbs, n, out, flags);
@@ -1328,7 +1355,8 @@ int load_suite(const dr_vrf_suite* s, drh::VrfSuite& out, bool allow_sw) {
             return allow_sw ? DR_OK : fail(DR_ERR_INVALID, std::string("this entry point does not serve the ") + S.name + " suite");
         }) && rc != DR_OK)
         return rc;
-    if (out.cv->sswu && out.xof != 2) return fail(DR_ERR_INVALID, "the secp256k1 suites hash with SHA-256 (xof = 2)");
+    if (out.cv->sswu && out.xof != 2) return fail(DR_ERR_INVALID, "the secp256k1 and P-256 suites hash with SHA-256 (xof = 2)");
+    if (out.cv->ell2_native && out.xof != 0) return fail(DR_ERR_INVALID, "the Ed25519 suites hash with SHA-512 (xof = 0)");
     if (out.cv->sw) {
         if (!allow_sw) return fail(DR_ERR_INVALID, "this entry point does not serve the short Weierstrass suite");
         // the kernels take the suite's constants as their TE images; the SW generator stays for its encoding
@@ -1353,16 +1381,20 @@ int encode_to_curve_msgs(dr_ctx* ctx, const drh::VrfSuite& su, size_t B, const u
         if (salt_off) drh::put(m, salts + salt_off[i], salt_off[i + 1] - salt_off[i]);
         drh::put(m, data + off[i], off[i + 1] - off[i]);
     };
-    if (su.cv->sswu) {                // RFC 9380: hash_to_field on the worker threads, the map (and for RO the sum of two images) in one launch
+    if (su.cv->sswu || su.cv->ell2_native) {   // RFC 9380: hash_to_field on the worker threads, the map (and for RO the sum of two images) in one launch
         const unsigned per = su.cv->nu ? 1 : 2;
         std::vector<uint8_t> us(B * 32 * per), ok(B);
         drh::parallel_for(B, [&](size_t i) {
             build(i);
-            drh::hash_to_field_xmd_sha256(su, msgs[i].data(), msgs[i].size(), per, us.data() + 32 * per * i);
+            drh::hash_to_field_rfc9380(su, msgs[i].data(), msgs[i].size(), per, us.data() + 32 * per * i);
         });
-        TRY(dr_secp256k1_map_to_curve(ctx, us.data(), B, (int)per, out_xy, ok.data()));
+        switch (su.cv->native) {
+            case drh::NativeSuite::p256: TRY(dr_p256_map_to_curve(ctx, us.data(), B, (int)per, out_xy, ok.data())); break;
+            case drh::NativeSuite::ed25519: TRY(dr_ed25519_map_to_curve(ctx, us.data(), B, (int)per, out_xy, ok.data())); break;
+            default: TRY(dr_secp256k1_map_to_curve(ctx, us.data(), B, (int)per, out_xy, ok.data())); break;
+        }
         for (size_t i = 0; i < B; i++)
-            if (!ok[i]) return fail(DR_ERR_INVALID, "hash to curve: a denominator of the isogeny is zero");
+            if (!ok[i]) return fail(DR_ERR_INVALID, "hash to curve: a denominator of the map is zero");
         return DR_OK;
     }
     if (!su.cv->tai) {
@@ -1407,13 +1439,14 @@ int encode_to_curve_msgs(dr_ctx* ctx, const drh::VrfSuite& su, size_t B, const u
 int dr_hash_to_field_batch(const dr_vrf_suite* suite, const uint8_t* msgs, const uint64_t* off, size_t count, uint8_t* out_u_pairs) {
     drh::VrfSuite su;
     TRY(load_suite(suite, su, true));
-    if (su.cv->native == drh::NativeSuite::p256) return fail(DR_ERR_INVALID, "the P-256 suite hashes to the curve by try-and-increment: no hash_to_field");
+    if (su.cv->native == drh::NativeSuite::p256 && !su.cv->sswu)
+        return fail(DR_ERR_INVALID, "the P-256 suite hashes to the curve by try-and-increment: no hash_to_field");
     if (count && (!off || !out_u_pairs || (off[count] && !msgs))) return fail(DR_ERR_INVALID, "null buffer");
     for (size_t i = 0; i < count; i++)
         if (off[i + 1] < off[i]) return fail(DR_ERR_INVALID, "offsets must be non-decreasing");
-    if (su.cv->sswu) {                // two elements per message for the uniform (RO) variant (64 bytes), one for the nonuniform one (32)
+    if (su.cv->sswu || su.cv->ell2_native) {   // two elements per message for the uniform (RO) variant (64 bytes), one for the nonuniform one (32)
         const unsigned per = su.cv->nu ? 1 : 2;
-        drh::parallel_for(count, [&](size_t i) { drh::hash_to_field_xmd_sha256(su, msgs + off[i], off[i + 1] - off[i], per, out_u_pairs + 32 * per * i); });
+        drh::parallel_for(count, [&](size_t i) { drh::hash_to_field_rfc9380(su, msgs + off[i], off[i + 1] - off[i], per, out_u_pairs + 32 * per * i); });
         return DR_OK;
     }
     drh::parallel_for(count, [&](size_t i) { drh::hash_to_field2(su, msgs + off[i], off[i + 1] - off[i], out_u_pairs + 64 * i); });

@@ -286,4 +286,21 @@ DR_DEV bool fp_sqrt(const F256& v, F256& root) {
     return ok;
 }
 
+// z^((p - 3) / 4), (p - 3) / 4 = 2^254 - 2^222 + 2^190 + 2^94 - 1: the exponent of RFC 9380's sqrt_ratio for p = 3 mod 4.  The head
+// is fp_sqrt's (z^(2^32 - 1), then z^(2^64 - 2^32 + 1)); where the root's chain ends in 2^94 z^... this one appends 94 one bits
+// (32 + 32 + 30).  254 squarings, 13 products.
+DR_DEV F256 fp_pow_p34(const F256& z) {
+    F256 x2, x30;
+    const F256 x32 = fp_pow_2_32_1(z, x2, x30);
+    F256 r = mul(sqr_n(x32, 32), z);
+    r = mul(sqr_n(r, 128), x32);
+    r = mul(sqr_n(r, 32), x32);
+    return mul(sqr_n(r, 30), x30);
+}
+// the canonical value is odd (sgn0 of RFC 9380)
+DR_DEV bool fp_is_odd(const F256& a) {
+    uint32_t w[8];
+    fp_pack(a, w);
+    return (w[0] & 1u) != 0;
+}
 }  // namespace dr

@@ -318,6 +318,8 @@ inline const Mod256& mod_p() {       // Bandersnatch base field = BLS12-381 scal
 // GF(2^255 - 19) (kernels_ed25519.hip.h), P-256, short Weierstrass over its own field with 33-byte encodings (kernels_p256.hip.h), and
 // Baby JubJub over the BN254 scalar field (kernels_bjj.hip.h), and secp256k1, short Weierstrass with a = 0 over its own field, SEC1
 // encodings and RFC 9380 hashing to the curve (kernels_secp256k1.hip.h; ids 6 and 7 are its uniform (RO) and nonuniform variants).
+// Ids 8 - 11 are the RFC 9380 variants of P-256 (8 RO, 9 NU: simplified SWU, SEC1 encodings) and Ed25519 (10 RO, 11 NU: Elligator 2,
+// Ed25519's own codec): the same native suites and kernels as ids 4 and 3, with a map kernel in place of try-and-increment.
 enum class NativeSuite { none, ed25519, p256, bjj, secp256k1 };
 struct TeCurveHost {
     int id;
@@ -329,7 +331,8 @@ struct TeCurveHost {
     bool tai;                 // hash-to-curve by try-and-increment (otherwise Elligator 2)
     bool sw = false;          // points cross the ABI as short Weierstrass affine x || y (33-byte encodings); TE inside
     bool sswu = false;        // hash-to-curve by the simplified SWU map of RFC 9380 (neither try-and-increment nor Elligator 2)
-    bool nu = false;          // ... its nonuniform variant: one field element per message, DST ..._NU_
+    bool ell2_native = false; // hash-to-curve by RFC 9380's Elligator 2 on a native suite's own map kernel (Ed25519), not the Bandersnatch one
+    bool nu = false;          // the nonuniform variant of either: one field element per message, DST ..._NU_
     NativeSuite native = NativeSuite::none;
 };
 inline const Mod256& mod_p25519() {   // Ed25519 base field (specs/ed25519.py)
@@ -352,8 +355,26 @@ inline const Mod256& secp256k1_order() {
     static Mod256 s = [] { Mod256 t; const uint64_t n[4] = {0xbfd25e8cd0364141ULL, 0xbaaedce6af48a03bULL, 0xfffffffffffffffeULL, 0xffffffffffffffffULL}; t.init(n); return t; }();
     return s;
 }
+// the table's entries for Ed25519 (id 3) and P-256 (id 4); their RFC 9380 variants (ids 8 - 11) start from these
+inline TeCurveHost curves_ed25519() {
+    TeCurveHost c{};
+    c.id = 3;
+    const uint64_t n[4] = {0x5812631a5cf5d3edULL, 0x14def9dea2f79cd6ULL, 0x0000000000000000ULL, 0x1000000000000000ULL};
+    c.n.init(n);
+    const uint64_t d[4] = {0x75eb4dca135978a3ULL, 0x00700a4d4141d8abULL, 0x8cc740797779e898ULL, 0x52036cee2b6ffe73ULL};
+    std::memcpy(c.d, d, 32); c.neg_a[0] = 1; c.scalar_bits = 253; c.glv = false; c.tai = true; c.native = NativeSuite::ed25519;
+    return c;
+}
+inline TeCurveHost curves_p256() {
+    TeCurveHost c{};
+    c.id = 4;
+    const uint64_t n[4] = {0xf3b9cac2fc632551ULL, 0xbce6faada7179e84ULL, 0xffffffffffffffffULL, 0xffffffff00000000ULL};
+    c.n.init(n);
+    c.scalar_bits = 256; c.glv = false; c.tai = true; c.native = NativeSuite::p256;
+    return c;
+}
 inline const TeCurveHost* te_curve(int id) {
-    static const TeCurveHost curves[8] = {
+    static const TeCurveHost curves[12] = {
         [] { TeCurveHost c{}; c.id = 0; c.n = mod_n();
              const uint64_t d[4] = {0xb369f2f5188d58e7ULL, 0xcb66677177e54f92ULL, 0xc66e3bf86be3b6d8ULL, 0x6389c12633c267cbULL};
              std::memcpy(c.d, d, 32); c.neg_a[0] = 5; c.scalar_bits = 253; c.glv = true; c.tai = false; return c; }(),
@@ -366,17 +387,10 @@ inline const TeCurveHost* te_curve(int id) {
              const uint64_t d[4] = {0xb369f2f5188d58e7ULL, 0xcb66677177e54f92ULL, 0xc66e3bf86be3b6d8ULL, 0x6389c12633c267cbULL};
              std::memcpy(c.d, d, 32); c.neg_a[0] = 5; c.scalar_bits = 253; c.glv = true; c.tai = true; c.sw = true; return c; }(),
         // Ed25519 (specs/ed25519.py, the Ed25519_TAI variant): n = l = 2^252 + 0x14DEF9DEA2F79CD65812631A5CF5D3ED, a = -1, cofactor 8
-        [] { TeCurveHost c{}; c.id = 3;
-             const uint64_t n[4] = {0x5812631a5cf5d3edULL, 0x14def9dea2f79cd6ULL, 0x0000000000000000ULL, 0x1000000000000000ULL};
-             c.n.init(n);
-             const uint64_t d[4] = {0x75eb4dca135978a3ULL, 0x00700a4d4141d8abULL, 0x8cc740797779e898ULL, 0x52036cee2b6ffe73ULL};
-             std::memcpy(c.d, d, 32); c.neg_a[0] = 1; c.scalar_bits = 253; c.glv = false; c.tai = true; c.native = NativeSuite::ed25519; return c; }(),
+        curves_ed25519(),
         // P-256 (specs/p256.py, the P256_TAI variant): y^2 = x^3 - 3 x + b, cofactor 1, n of 256 bits (its top bit set); d and neg_a
         // do not apply (no twisted Edwards model)
-        [] { TeCurveHost c{}; c.id = 4;
-             const uint64_t n[4] = {0xf3b9cac2fc632551ULL, 0xbce6faada7179e84ULL, 0xffffffffffffffffULL, 0xffffffff00000000ULL};
-             c.n.init(n);
-             c.scalar_bits = 256; c.glv = false; c.tai = true; c.native = NativeSuite::p256; return c; }(),
+        curves_p256(),
         // Baby JubJub (specs/baby_jubjub.py): n = l of 251 bits, a = 1, cofactor 8; neg_a is unused (its kernels carry a = 1 themselves)
         [] { TeCurveHost c{}; c.id = 5;
              const uint64_t n[4] = {0x677297dc392126f1ULL, 0xab3eedb83920ee0aULL, 0x370a08b6d0302b0bULL, 0x060c89ce5c263405ULL};
@@ -389,8 +403,14 @@ inline const TeCurveHost* te_curve(int id) {
              c.scalar_bits = 256; c.glv = false; c.tai = false; c.sswu = true; c.native = NativeSuite::secp256k1; return c; }(),
         [] { TeCurveHost c{}; c.id = 7; c.n = secp256k1_order();
              c.scalar_bits = 256; c.glv = false; c.tai = false; c.sswu = true; c.nu = true; c.native = NativeSuite::secp256k1; return c; }(),
+        // P256_RO (8) and P256_NU (9) (specs/p256.py): P-256's group and kernels, hashing by the simplified SWU map, SEC1 encodings
+        [] { TeCurveHost c = curves_p256(); c.id = 8; c.tai = false; c.sswu = true; return c; }(),
+        [] { TeCurveHost c = curves_p256(); c.id = 9; c.tai = false; c.sswu = true; c.nu = true; return c; }(),
+        // Ed25519_RO (10) and Ed25519_NU (11) (specs/ed25519.py): Ed25519's group, kernels and codec, hashing by Elligator 2
+        [] { TeCurveHost c = curves_ed25519(); c.id = 10; c.tai = false; c.ell2_native = true; return c; }(),
+        [] { TeCurveHost c = curves_ed25519(); c.id = 11; c.tai = false; c.ell2_native = true; c.nu = true; return c; }(),
     };
-    return id >= 0 && id <= 7 ? &curves[id] : nullptr;
+    return id >= 0 && id <= 11 ? &curves[id] : nullptr;
 }
 // the base field of a curve of the table
 inline const Mod256& te_field(const TeCurveHost& c) {
@@ -489,7 +509,7 @@ inline void enc_sw_point(const uint8_t xy[64], uint8_t out[33], const Mod256& fi
     for (int i = 3; i >= 0; i--) { if (y[i] != ny[i]) { gt = y[i] > ny[i]; break; } }
     out[32] = gt ? 0x80 : 0x00;
 }
-// SEC1 compressed point (sw_affine_point.py point_to_string, the secp256k1 suites): 0x02 / 0x03 by the parity of y, then x big-endian.
+// SEC1 compressed point (sw_affine_point.py point_to_string, the secp256k1 suites and P256_RO / P256_NU): 0x02 / 0x03 by the parity of y, then x big-endian.
 // The identity has no encoding; 64 zero bytes give 0x02 and 32 zero bytes, which no transcript of a valid proof contains.
 inline void enc_sec1_point(const uint8_t xy[64], uint8_t out[33]) {
     out[0] = (uint8_t)(0x02 | (xy[32] & 1));
@@ -583,8 +603,8 @@ struct VrfSuite {
 // the suite's point encoding of xy given in the suite's own coordinates (TE, or SW for the SW suite)
 inline void enc_point(const VrfSuite& su, const uint8_t xy[64], uint8_t* out) {
     if (su.cv->sw) enc_sw_point(xy, out);
-    else if (su.cv->native == NativeSuite::p256) enc_sw_point(xy, out, mod_p256());
-    else if (su.cv->native == NativeSuite::secp256k1) enc_sec1_point(xy, out);
+    else if (su.cv->native == NativeSuite::p256 && !su.cv->sswu) enc_sw_point(xy, out, mod_p256());
+    else if (su.cv->native == NativeSuite::secp256k1 || su.cv->native == NativeSuite::p256) enc_sec1_point(xy, out);   // (P256_RO / P256_NU: SEC1)
     else enc_te_point(xy, out, te_field(*su.cv));
 }
 // squeeze `size` bytes of the stream defined by everything absorbed (xof: VrfSuite::xof)
@@ -700,41 +720,62 @@ inline void hash_to_field2(const VrfSuite& su, const uint8_t* msg, size_t len, u
     }
 }
 
-// RFC 9380 hash_to_field for the secp256k1 suites (curve.py:110-185 with specs/secp256k1.py): expand_message_xmd over SHA-256 with a
-// Z_pad of 64 bytes and the DST QUUX-V01-CS02-with- || suite_id (its _RO_ replaced by _NU_ for the nonuniform variant), 48 bytes per
-// element, big-endian, mod p.  `count` is 2 (uniform, RO) or 1 (nonuniform); out = count x 32 bytes little-endian.
-inline void hash_to_field_xmd_sha256(const VrfSuite& su, const uint8_t* msg, size_t len, unsigned count, uint8_t* out) {
+// The DST of a suite that hashes by RFC 9380 (curve.py:41-48 hash_to_curve_dst): secp256k1's is QUUX-V01-CS02-with- || suite_id;
+// P-256's and Ed25519's are the ones of specs/p256.py and specs/ed25519.py, which their suite ids (shared with the try-and-increment
+// variants) do not spell.  The nonuniform variant has the final _RO_ replaced by _NU_.
+inline Bytes h2c_dst(const VrfSuite& su) {
     Bytes dst;
     put(dst, "QUUX-V01-CS02-with-", 19);
-    put(dst, su.suite_id.data(), su.suite_id.size());
+    if (su.cv->native == NativeSuite::p256) put(dst, "P256_XMD:SHA-256_SSWU_RO_", 25);
+    else if (su.cv->native == NativeSuite::ed25519) put(dst, "edwards25519_XMD:SHA-512_ELL2_RO_", 33);
+    else put(dst, su.suite_id.data(), su.suite_id.size());
     if (su.cv->nu && dst.size() >= 4 && std::memcmp(&dst[dst.size() - 4], "_RO_", 4) == 0) { dst[dst.size() - 3] = 'N'; dst[dst.size() - 2] = 'U'; }
+    return dst;
+}
+// RFC 9380 hash_to_field (curve.py:110-185) by expand_message_xmd over the hash H with digests of DIGEST bytes and a Z_pad of BLOCK
+// bytes (the hash's block: specs' expand_len): 48 bytes per element, big-endian, mod `field`.  `count` is 2 (uniform, RO) or 1
+// (nonuniform); out = count x 32 bytes little-endian.  SHA-256 (64 / 32: secp256k1, P-256) needs 3 or 2 blocks for 96 or 48 bytes,
+// SHA-512 (128 / 64: Ed25519_RO / Ed25519_NU) 2 or 1.
+template <class H, size_t BLOCK, size_t DIGEST>
+inline void hash_to_field_xmd(Bytes dst, const Mod256& field, const uint8_t* msg, size_t len, unsigned count, uint8_t* out) {
     put8(dst, (uint8_t)dst.size());                  // DST_prime = DST || len(DST)
-    const size_t L = 48 * (size_t)count;             // 96 or 48: 3 or 2 blocks of 32
-    uint8_t b0[32], prev[32], raw[96];
-    const uint8_t zpad[64] = {0};
-    Sha256 h;
-    h.update(zpad, 64);
+    const size_t L = 48 * (size_t)count;
+    uint8_t b0[DIGEST], prev[DIGEST], raw[2 * DIGEST > 96 ? 2 * DIGEST : 96];
+    const uint8_t zpad[BLOCK] = {0};
+    H h;
+    h.update(zpad, BLOCK);
     if (len) h.update(msg, len);                     // (an empty message has no buffer to read)
     const uint8_t lb[3] = {0, (uint8_t)L, 0};
     h.update(lb, 3);
     h.update(dst.data(), dst.size());
     h.final(b0);
-    for (size_t i = 1; 32 * (i - 1) < L; i++) {
-        Sha256 g;
-        uint8_t x[32];
-        for (int j = 0; j < 32; j++) x[j] = i == 1 ? b0[j] : (uint8_t)(b0[j] ^ prev[j]);
-        g.update(x, 32);
+    for (size_t i = 1; DIGEST * (i - 1) < L; i++) {
+        H g;
+        uint8_t x[DIGEST];
+        for (size_t j = 0; j < DIGEST; j++) x[j] = i == 1 ? b0[j] : (uint8_t)(b0[j] ^ prev[j]);
+        g.update(x, DIGEST);
         const uint8_t ib = (uint8_t)i;
         g.update(&ib, 1);
         g.update(dst.data(), dst.size());
         g.final(prev);
-        std::memcpy(raw + 32 * (i - 1), prev, 32);
+        std::memcpy(raw + DIGEST * (i - 1), prev, DIGEST);
     }
     for (unsigned k = 0; k < count; k++) {
         uint64_t v[4];
-        mod_psecp256k1().reduce_bytes(raw + 48 * k, 48, true, v);
+        field.reduce_bytes(raw + 48 * k, 48, true, v);
         store_le32(v, out + 32 * k);
     }
+}
+inline void hash_to_field_xmd_sha256(const Bytes& dst, const Mod256& field, const uint8_t* msg, size_t len, unsigned count, uint8_t* out) {
+    hash_to_field_xmd<Sha256, 64, 32>(dst, field, msg, len, count, out);
+}
+inline void hash_to_field_xmd_sha512(const Bytes& dst, const Mod256& field, const uint8_t* msg, size_t len, unsigned count, uint8_t* out) {
+    hash_to_field_xmd<Sha512, 128, 64>(dst, field, msg, len, count, out);
+}
+// hash_to_field of a suite that hashes by RFC 9380 (sswu or ell2_native): the hash, DST and modulus of its curve
+inline void hash_to_field_rfc9380(const VrfSuite& su, const uint8_t* msg, size_t len, unsigned count, uint8_t* out) {
+    if (su.cv->ell2_native) hash_to_field_xmd_sha512(h2c_dst(su), te_field(*su.cv), msg, len, count, out);
+    else hash_to_field_xmd_sha256(h2c_dst(su), te_field(*su.cv), msg, len, count, out);
 }
 
 // ---------------------------------------------------------------- ring-proof Fiat-Shamir transcript (transcript.py:21-136)

@@ -300,6 +300,91 @@ __global__ __launch_bounds__(ED_BLOCK) void k_ed_decode_points(const uint32_t* _
     }
 }
 
+// ---------------------------------------------------------------- hashing to the curve (RFC 9380, edwards25519_XMD:SHA-512_ELL2_RO_ / _NU_)
+// Elligator 2 onto curve25519 (v^2 = u^3 + A u^2 + u, A = 486662, Z = 2) as the reference's TECurve.map_to_curve_ell2 runs it, then its
+// mont_to_ed25519, without an inversion per element.  With tv1 = Z u^2 (0 when it is -1; it never is, -1 / 2 is not a square) and
+// d = 1 + tv1:  x1 = -A / d,  gx1 = x1^3 + A x1^2 + x1 = A (A^2 tv1 - d^2) / d^3 =: N / D,  x2 = -x1 - A = -A tv1 / d,  gx2 = tv1 gx1.
+// One exponentiation decides the squareness of gx1 and gives the root of whichever is taken: b = N D^3 (N D^7)^((p - 5) / 8) has
+// D b^2 = w N for a fourth root of unity w.  w = 1, -1: gx1 is a square with root b, b sqrt(-1).  w = i, -i (i = sqrt(-1), not a
+// square, nor is Z = 2): gx2 = Z u^2 gx1 = u^2 b^2 (Z / w), root u b sqrt(-2 i), u b sqrt(2 i).  The sign is the reference's: the root
+// negated when (gx1 is a square) xor (the root is odd).
+struct Ed25519Ell2 {
+    static constexpr uint32_t A[9] = {486662u, 0, 0, 0, 0, 0, 0, 0, 0};
+    static constexpr uint32_t A2[9] = {0x04c21c24u, 0x000001b9u, 0, 0, 0, 0, 0, 0, 0};          // A^2
+    // sqrt(-486664), the root the reference's mod_sqrt (Tonelli-Shanks from the non-residue 2) returns: the factor of mont_to_ed25519
+    static constexpr uint32_t SQRT_NEG_A_MINUS_2[9] = {0x1f457e06u, 0x03702557u, 0x1f46a0b3u, 0x03a7a296u, 0x04f7ec5au, 0x046e01feu, 0x1aef49ecu, 0x1e8c1400u, 0x000f26edu};
+    static constexpr uint32_t SQRT_NEG_2I[9] = {0x15f15f3eu, 0x188f26c5u, 0x1406e1ceu, 0x19cff2a5u, 0x02858d0bu, 0x1fb36102u, 0x03d352cbu, 0x0ff607c4u, 0x00547cdbu};
+    static constexpr uint32_t SQRT_2I[9] = {0x0a0ea0b1u, 0x0770d93au, 0x0bf91e31u, 0x06300d5au, 0x1d7a72f4u, 0x004c9efdu, 0x1c2cad34u, 0x1009f83bu, 0x002b8324u};
+};
+DR_DEV F25 fe_select(bool c, const F25& a, const F25& b) {
+    F25 r;
+#pragma unroll
+    for (int i = 0; i < FE_L; i++) r.l[i] = c ? a.l[i] : b.l[i];
+    return r;
+}
+// the image of u (normal, canonical) on Ed25519 in extended coordinates; ok = false where the reference's modular inverse fails: the
+// Montgomery point has v = 0 (u = 0 reaches it) or u = -1, so that x = sqrt(-486664) u / v or y = (u - 1) / (u + 1) has no value (Z = 0)
+DR_DEV EdPoint ed_ell2_map(const F25& u, bool& ok) {
+    using K = Ed25519Ell2;
+    const F25 one = F25::one(), A = F25::constant<K::A>();
+    F25 tv1 = carry(dbl(sqr(u)));                                            // Z u^2: n
+    tv1 = fe_select(fe_is_zero(add(tv1, one)), F25::zero(), tv1);
+    const F25 d = carry(add(tv1, one));                                      // n
+    const F25 d2 = sqr(d);
+    const F25 N = mul(A, sub(mul(F25::constant<K::A2>(), tv1), d2));         // A (A^2 tv1 - d^2): n x (n - n)
+    const F25 D = mul(d2, d);
+    // b = N D^3 (N D^7)^((p - 5) / 8), as fe_sqrt_ratio
+    const F25 D2 = sqr(D);
+    const F25 nd3 = mul(N, mul(D2, D));
+    const F25 nd7 = mul(nd3, sqr(D2));
+    F25 z11;
+    const F25 b = mul(nd3, mul(sqr_n(fe_pow_2_250_1(nd7, z11), 2), nd7));
+    const F25 vb2 = mul(D, sqr(b));
+    const F25 iN = mul(N, F25::constant<Fe25519Consts::SQRT_M1>());
+    const bool w_one = fe_equal(vb2, N), w_neg = fe_is_zero(add(vb2, N)), w_i = fe_equal(vb2, iN);
+    const bool e2 = w_one || w_neg;                                          // gx1 is a square (N != 0: A^2 - 4 is not a square)
+    const F25 f = fe_select(w_one, one, fe_select(w_neg, F25::constant<Fe25519Consts::SQRT_M1>(),
+                                                  fe_select(w_i, F25::constant<K::SQRT_NEG_2I>(), F25::constant<K::SQRT_2I>())));
+    const F25 y1 = mul(b, f);
+    F25 y = fe_select(e2, y1, mul(y1, u));
+    uint32_t yw[8];
+    fe_pack(y, yw);
+    y = carry(cneg(y, e2 != ((yw[0] & 1u) != 0)));
+    const F25 xn = carry(neg(mul(A, fe_select(e2, one, tv1))));              // -A or -A tv1 over d: n
+    // (u, v) = (xn / d, y) on curve25519 -> Ed25519: x = sqrt(-486664) u / v = a / bb, y = (u - 1) / (u + 1) = c / e
+    const F25 a = mul(F25::constant<K::SQRT_NEG_A_MINUS_2>(), xn), bb = mul(d, y);
+    const F25 c = carry(sub(xn, d)), e = carry(add(xn, d));
+    EdPoint r;
+    r.x = mul(a, e); r.y = mul(c, bb); r.z = mul(bb, e); r.t = mul(a, c);
+    ok = !fe_is_zero(r.z);
+    return r;
+}
+// out[i] = 8 (the sum of the images of item i's `per_item` field elements) (2: the uniform (RO) encoding, 1: the nonuniform one): the
+// reference's _e2c_ell2_ro / _e2c_ell2_nu after hash_to_field.  us: n x per_item x 8 words (canonical, checked by the host), out: n x 16
+// words affine x || y, ok[i] = 0 where an image has no value (the output is then meaningless).  One lane per item; one exponentiation
+// per element and one inversion per item.
+__global__ __launch_bounds__(ED_BLOCK) void k_ed25519_map_to_curve(const uint32_t* __restrict__ us, uint32_t* __restrict__ out_xy,
+                                                                   uint32_t* __restrict__ ok, uint32_t n, uint32_t per_item) {
+    uint32_t i = blockIdx.x * ED_BLOCK + threadIdx.x;
+    const bool live = i < n;
+    if (!live) i = n - 1;
+    EdPoint acc = ed_identity();
+    bool good = true;
+#pragma unroll 1
+    for (uint32_t e = 0; e < per_item; e++) {
+        bool ok_e;
+        const EdPoint q = ed_ell2_map(ed_load_fe(us + ((size_t)i * per_item + e) * 8), ok_e);
+        good = good && ok_e;
+        acc = ed_add(acc, q);
+    }
+#pragma unroll 1
+    for (int j = 0; j < 3; j++) acc = ed_dbl<true>(acc);                     // the cofactor
+    if (live) {
+        ed_store_affine(out_xy + (size_t)i * 16, acc);
+        ok[i] = good ? 1u : 0u;
+    }
+}
+
 // Diagnostic (dr_fe25519_ops_selftest): fe25519.hip.h's operations on raw limb images, one lane per (a, b) pair of 9 int32 limbs each,
 // so that tests can drive every operation at the limb bounds its contract allows.  out[i] = eleven canonical 32-byte records:
 // a b, a^2, a + b, a - b, -a, carry(a), a b + b a (mul2), a^-1 (0 for 0), sqrt(a) or 0, a itself (pack), sqrt(a / b) or 0;

@@ -10,6 +10,7 @@
 // intermediate against fp256.hip.h's contract: n = normal, r = reduced, sK = a sum or difference of K such.
 #pragma once
 #include "fp256.hip.h"
+#include "sswu.hip.h"
 
 namespace dr {
 
@@ -244,7 +245,11 @@ __global__ __launch_bounds__(P256_BLOCK) void k_p256_msm_groups(const uint32_t* 
 // MODE: P256_DEC_CODEC the codec alone (the identity is accepted, out = 64 zero bytes); P256_DEC_CHECK also rejects the identity
 // (the cofactor is 1: a decoded point other than O is a valid point); P256_DEC_TAI the device half of try-and-increment, whose
 // candidates (32 squeezed bytes and the flag 0x80) are accepted on the same terms — no cofactor to clear, so it is CHECK again.
-enum { P256_DEC_CODEC = 0, P256_DEC_CHECK = 1, P256_DEC_TAI = 2 };
+// P256_DEC_SEC1: the codec of the RFC 9380 variants (P256_RO / P256_NU: SWAffinePoint.string_to_point), plain SEC1 compressed as
+// k_secp256k1_decode_points reads it — byte 0 is 0x02 or 0x03, x = bytes 1..32 big-endian, x < p, a root, y of byte 0's parity; nothing
+// else, so a P256_TAI string is read as SEC1 or refused, never by the canonical rules.  No string encodes the identity, so the codec
+// alone and the checking decoder are this one mode.
+enum { P256_DEC_CODEC = 0, P256_DEC_CHECK = 1, P256_DEC_TAI = 2, P256_DEC_SEC1 = 3 };
 // y^2 = x^3 - 3 x + b for x in Montgomery form; ok and a root (either one) if it exists
 DR_DEV bool p256_y_of_x(const F256& x, F256& y) {
     const F256 x3 = mul(sqr(x), x);
@@ -269,6 +274,31 @@ __global__ __launch_bounds__(P256_BLOCK) void k_p256_decode_points(const uint32_
 #pragma unroll
     for (int j = 0; j < 9; j++) w[j] = enc[(size_t)i * 9 + j];
     const uint32_t flag = w[8] & 0xffu, first = w[0] & 0xffu;
+    if constexpr (MODE == P256_DEC_SEC1) {
+        uint32_t xb[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const int k = 7 - q;
+            xb[q] = __builtin_bswap32((w[k] >> 8) | (w[k + 1] << 24));
+        }
+        const F256 x = fp_unpack(xb);
+        F256 y;
+        const bool root = p256_y_of_x(x, y);
+        const bool valid = (first == 0x02u || first == 0x03u) && p256_below_p(xb) && root;
+        if (fp_is_odd(y) != ((first & 1u) != 0)) y = neg(y);     // (y = 0 cannot happen: the group order is odd)
+        if (live) {
+            if (valid) {
+                p256_store8(out_xy + (size_t)i * 16, xb);
+                p256_store_fe(out_xy + (size_t)i * 16 + 8, y);
+            } else {
+                const uint32_t z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+                p256_store8(out_xy + (size_t)i * 16, z);
+                p256_store8(out_xy + (size_t)i * 16 + 8, z);
+            }
+            ok[i] = valid ? 1u : 0u;
+        }
+        return;
+    }
     uint32_t xs[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) xs[j] = w[j];
@@ -319,6 +349,45 @@ __global__ __launch_bounds__(P256_BLOCK) void k_p256_decode_points(const uint32_
         }
         ok[i] = valid ? 1u : 0u;
     }
+}
+
+// ---------------------------------------------------------------- hashing to the curve (RFC 9380, P256_XMD:SHA-256_SSWU_RO_ / _NU_)
+// sswu.hip.h's description of P-256: the simplified SWU map straight onto the curve (A = -3, B = b, Z = -10, no isogeny).  The field is
+// in Montgomery form, so A, Z, |Z| = 10 and sqrt(-Z) = sqrt(10) are compile-time limbs of v 2^261 mod p, B is Fp256Consts::B, and the
+// products by |Z| and B are full products by those constants (neither is small in this form).  sgn0 and equality are taken on the
+// canonical value (fp_pack), the output through p256_store_affine.
+struct P256Sswu {
+    using Fe = F256;
+    using Point = P256Point;
+    static constexpr uint32_t BLOCK = P256_BLOCK;
+    DR_DEV static void load8(const uint32_t* p, uint32_t (&w)[8]) { p256_load8(p, w); }
+    static constexpr bool ISOGENY = false;
+    static constexpr uint32_t A[9] = {0x1fffff9fu, 0x1fffffffu, 0x1fffffffu, 0x0000c1ffu, 0x00000000u, 0x00000000u, 0x01840000u, 0x13e00000u, 0x00ffffffu};
+    static constexpr uint32_t Z[9] = {0x1ffffebfu, 0x1fffffffu, 0x1fffffffu, 0x000281ffu, 0x00000000u, 0x00000000u, 0x05040000u, 0x17e00000u, 0x00fffffeu};
+    static constexpr uint32_t NEG_Z[9] = {0x00000140u, 0x00000000u, 0x00000000u, 0x1ffd8000u, 0x1fffffffu, 0x1fffffffu, 0x1affffffu, 0x07ffffffu, 0x00000001u};
+    static constexpr uint32_t SQRT_NEG_Z[9] = {0x1432bfb2u, 0x1d38ee98u, 0x0e7b850fu, 0x02b5ac8fu, 0x1fdcf080u, 0x08f9ea8du, 0x01ec89e4u, 0x1a8aa3ccu, 0x000a3a4du};
+    DR_DEV static F256 a() { return F256::constant<A>(); }
+    DR_DEV static F256 z() { return F256::constant<Z>(); }
+    DR_DEV static F256 sqrt_neg_z() { return F256::constant<SQRT_NEG_Z>(); }
+    DR_DEV static F256 one() { return fp_one(); }
+    DR_DEV static F256 mul_neg_z(const F256& x) { return mul(F256::constant<NEG_Z>(), x); }            // n x (n or s2): n
+    DR_DEV static F256 mul_b(const F256& x) { return mul(F256::constant<Fp256Consts::B>(), x); }
+    DR_DEV static F256 norm(const F256& x) { return fp_reduce(x); }
+    DR_DEV static bool is_zero(const F256& x) { return fp_is_zero(x); }
+    DR_DEV static bool equal(const F256& x, const F256& y) { return fp_equal(x, y); }
+    DR_DEV static bool is_odd(const F256& x) { return fp_is_odd(x); }
+    DR_DEV static F256 pow_p34(const F256& x) { return fp_pow_p34(x); }
+    DR_DEV static P256Point identity() { return p256_identity(); }
+    DR_DEV static P256Point add(const P256Point& p, const P256Point& q) { return p256_add(p, q); }
+    DR_DEV static F256 unpack(const uint32_t (&w)[8]) { return fp_unpack(w); }
+    DR_DEV static void store_affine(uint32_t* out, const P256Point& p) { p256_store_affine(out, p); }
+};
+// out[i] = the sum of the images of item i's `per_item` (1: NU, 2: RO) field elements, as k_secp256k1_map_to_curve: us n x per_item x 8
+// words (canonical, checked by the host), out n x 16 words affine x || y (64 zero bytes if the two images cancel), ok[i] = 1 always
+// (no isogeny, no denominator that can vanish).  One lane per item.
+__global__ __launch_bounds__(P256_BLOCK) void k_p256_map_to_curve(const uint32_t* __restrict__ us, uint32_t* __restrict__ out_xy,
+                                                                  uint32_t* __restrict__ ok, uint32_t n, uint32_t per_item) {
+    sswu_map_to_curve<P256Sswu>(us, out_xy, ok, n, per_item);
 }
 
 // Diagnostic (dr_p256_field_ops_selftest): fp256.hip.h's operations on raw limb images, one lane per (a, b) pair of 9 int32 limbs each

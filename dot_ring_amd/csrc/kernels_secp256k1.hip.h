@@ -10,6 +10,7 @@
 // every intermediate against fsecp256k1.hip.h's contract: n = normal, sK = a sum or difference of K normals.
 #pragma once
 #include "fsecp256k1.hip.h"
+#include "sswu.hip.h"
 
 namespace dr {
 
@@ -270,12 +271,15 @@ __global__ __launch_bounds__(K1_BLOCK) void k_secp256k1_decode_points(const uint
 }
 
 // ---------------------------------------------------------------- hashing to the curve: simplified SWU and an isogeny (RFC 9380)
-// The map's constants, one struct per target curve: E': y^2 = x^3 + A x + B with B and |Z| small (Z negative), sqrt(-Z), and the
-// isogeny E' -> E as four coefficient lists, highest degree first (the leading 1 of the denominators is implied), all as compile-time
-// limbs — nothing is indexed at run time, so nothing goes to scratch.  A curve whose SSWU needs no isogeny (P-256) is a struct with
-// ISOGENY = false and its own A, B, Z.
+// The map itself is sswu.hip.h, a template over a description of the target curve; this is secp256k1's.  E': y^2 = x^3 + A x + B with
+// B and |Z| small (Z negative), sqrt(-Z), and the isogeny E' -> E as four coefficient lists, highest degree first (the leading 1 of
+// the denominators is implied), all as compile-time limbs — nothing is indexed at run time, so nothing goes to scratch.  P-256, whose
+// SSWU needs no isogeny, has its description (ISOGENY = false) in kernels_p256.hip.h.
 struct Secp256k1Sswu {
     using Fe = FK;
+    using Point = K1Point;
+    static constexpr uint32_t BLOCK = K1_BLOCK;
+    DR_DEV static void load8(const uint32_t* p, uint32_t (&w)[8]) { k1_load8(p, w); }
     static constexpr bool ISOGENY = true;
     static constexpr uint32_t B = 1771, NEG_Z = 11;
     static constexpr uint32_t A[9] = {0x1a444533u, 0x02a23e00u, 0x1bc39750u, 0x07a6c796u, 0x1d272e95u, 0x0aac787au, 0x0b728229u, 0x157bacc3u, 0x003f8731u};
@@ -294,93 +298,28 @@ struct Secp256k1Sswu {
     static constexpr uint32_t YD2[9] = {0x1fd2a76fu, 0x1dfc0c95u, 0x0358a669u, 0x1a422c5eu, 0x0337e0a3u, 0x061fd47fu, 0x08b3ce9cu, 0x0e2ca8b9u, 0x006484aau};
     static constexpr uint32_t YD1[9] = {0x085c2573u, 0x1da12e93u, 0x1a365e37u, 0x0f837f91u, 0x0c298946u, 0x13319391u, 0x127f57a7u, 0x097717b6u, 0x007a0653u};
     static constexpr uint32_t YD0[9] = {0x1ffff93bu, 0x1ffffff7u, 0x1fffffffu, 0x1fffffffu, 0x1fffffffu, 0x1fffffffu, 0x1fffffffu, 0x1fffffffu, 0x00ffffffu};
+    // the field's forms of what sswu.hip.h asks for: B and |Z| are small here, so their products are mul_small
+    DR_DEV static FK a() { return FK::constant<A>(); }
+    DR_DEV static FK z() { return FK::small(-(int32_t)NEG_Z); }
+    DR_DEV static FK sqrt_neg_z() { return FK::constant<SQRT_NEG_Z>(); }
+    DR_DEV static FK one() { return FK::small(1); }
+    DR_DEV static FK mul_neg_z(const FK& x) { return mul_small(x, NEG_Z); }
+    DR_DEV static FK mul_b(const FK& x) { return mul_small(x, B); }
+    DR_DEV static FK norm(const FK& x) { return carry(x); }
+    DR_DEV static bool is_zero(const FK& x) { return fk_is_zero(x); }
+    DR_DEV static bool equal(const FK& x, const FK& y) { return fk_equal(x, y); }
+    DR_DEV static bool is_odd(const FK& x) { return fk_is_odd(x); }
+    DR_DEV static FK pow_p34(const FK& x) { return fk_pow_p34(x); }
+    DR_DEV static K1Point identity() { return k1_identity(); }
+    DR_DEV static K1Point add(const K1Point& p, const K1Point& q) { return k1_add(p, q); }
+    DR_DEV static FK unpack(const uint32_t (&w)[8]) { return fk_unpack(w); }
+    DR_DEV static void store_affine(uint32_t* out, const K1Point& p) { k1_store_affine(out, p); }
 };
 
-// Simplified SWU in the inversion-free form of RFC 9380 appendix F.2 with the sqrt_ratio of F.2.1.2 (p = 3 mod 4): one exponentiation,
-// selects instead of branches.  In: u (normal, canonical value) and its parity.  Out: the point (xn / xd, y) of E', xd != 0.  The
-// exceptional case tv2 = Z^2 u^4 + Z u^2 = 0 (u = 0 reaches it) takes xd = Z A, that is x1 = B / (Z A).  Every value is carried to
-// normal where it is made, so each product below is normal x normal.
-template <class C>
-DR_DEV void sswu_map(const FK& u, bool u_odd, FK& xn, FK& xd, FK& y) {
-    const FK A = FK::constant<C::A>();
-    const FK tv1 = carry(neg(mul_small(sqr(u), C::NEG_Z)));                  // Z u^2
-    FK tv2 = carry(add(sqr(tv1), tv1));                                      // Z^2 u^4 + Z u^2
-    const FK tv3 = mul_small(add(tv2, FK::small(1)), C::B);                  // B (tv2 + 1): the numerator of x1
-    const FK tv4 = mul(A, carry(select(fk_is_zero(tv2), FK::small(-(int32_t)C::NEG_Z), neg(tv2))));   // A Z or -A tv2: its denominator
-    FK tv6 = sqr(tv4);
-    tv2 = mul(carry(add(sqr(tv3), mul(A, tv6))), tv3);                       // tv3^3 + A tv3 tv4^2
-    tv6 = mul(tv6, tv4);                                                     // tv4^3: the denominator of gx1
-    tv2 = carry(add(tv2, mul_small(tv6, C::B)));                             // ... + B tv4^3: its numerator
-    // sqrt_ratio(tv2, tv6): y1 = sqrt(tv2 / tv6) if that is a square, sqrt(Z tv2 / tv6) otherwise
-    const FK s2 = mul(tv2, tv6);
-    const FK s1 = mul(sqr(tv6), s2);                                         // u v^3
-    const FK y1 = mul(fk_pow_p34(s1), s2);
-    const bool is_square = fk_equal(mul(sqr(y1), tv6), tv2);
-    const FK y2 = mul(y1, FK::constant<C::SQRT_NEG_Z>());
-    const FK yb = mul(mul(tv1, u), y2);                                      // the root for x2 = Z u^2 x1
-    xn = select(is_square, tv3, mul(tv1, tv3));
-    xd = tv4;
-    y = select(is_square, y1, yb);
-    y = carry(cneg(y, fk_is_odd(y) != u_odd));                               // sgn0(y) = sgn0(u)
-}
-
-// The isogeny E' -> E on (xn / xd, y), by Horner in xn with the powers of xd as the homogenising factors, kept projective:
-// (X : Y : Z) = (XN YD : y YN xd XD : xd XD YD) for x = XN / (xd XD), y' = y YN / YD.  ok = false when a denominator vanishes (Z = 0): the
-// kernel of the isogeny, which the reference reports as the failing modular inverse; hashing cannot reach it in practice.
-template <class C>
-DR_DEV K1Point sswu_iso_map(const FK& xn, const FK& xd, const FK& y, bool& ok) {
-    K1Point r;
-    if constexpr (!C::ISOGENY) {
-        r.x = xn; r.y = mul(y, xd); r.z = xd;
-        ok = true;
-        return r;
-    } else {
-        const FK d2 = sqr(xd), d3 = mul(d2, xd);
-        FK XN = mul2(FK::constant<C::XN3>(), xn, FK::constant<C::XN2>(), xd);
-        XN = mul2(XN, xn, FK::constant<C::XN1>(), d2);
-        XN = mul2(XN, xn, FK::constant<C::XN0>(), d3);
-        FK XD = carry(add(xn, mul(FK::constant<C::XD1>(), xd)));
-        XD = mul2(XD, xn, FK::constant<C::XD0>(), d2);
-        FK YN = mul2(FK::constant<C::YN3>(), xn, FK::constant<C::YN2>(), xd);
-        YN = mul2(YN, xn, FK::constant<C::YN1>(), d2);
-        YN = mul2(YN, xn, FK::constant<C::YN0>(), d3);
-        FK YD = carry(add(xn, mul(FK::constant<C::YD2>(), xd)));
-        YD = mul2(YD, xn, FK::constant<C::YD1>(), d2);
-        YD = mul2(YD, xn, FK::constant<C::YD0>(), d3);
-        const FK dx = mul(xd, XD);
-        r.x = mul(XN, YD);
-        r.y = mul(mul(y, YN), dx);
-        r.z = mul(dx, YD);
-        ok = !fk_is_zero(r.z);
-        return r;
-    }
-}
-
-// out[i] = the sum of the images of item i's `per_item` field elements (2: the uniform (RO) encoding, 1: the nonuniform one), u: n x
-// per_item x 8 words (canonical, checked by the host), out: n x 16 words affine x || y, ok[i] = 0 where an isogeny denominator
-// vanished.  One lane per item; one exponentiation per element and one inversion per item.
+// out[i] = the sum of the images of item i's `per_item` field elements: sswu.hip.h's map, isogeny and loop for this curve
 __global__ __launch_bounds__(K1_BLOCK) void k_secp256k1_map_to_curve(const uint32_t* __restrict__ us, uint32_t* __restrict__ out_xy,
                                                                      uint32_t* __restrict__ ok, uint32_t n, uint32_t per_item) {
-    uint32_t i = blockIdx.x * K1_BLOCK + threadIdx.x;
-    const bool live = i < n;
-    if (!live) i = n - 1;
-    K1Point acc = k1_identity();
-    bool good = true;
-#pragma unroll 1
-    for (uint32_t e = 0; e < per_item; e++) {
-        uint32_t w[8];
-        k1_load8(us + ((size_t)i * per_item + e) * 8, w);
-        FK xn, xd, y;
-        sswu_map<Secp256k1Sswu>(fk_unpack(w), (w[0] & 1u) != 0, xn, xd, y);
-        bool ok_e;
-        const K1Point q = sswu_iso_map<Secp256k1Sswu>(xn, xd, y, ok_e);
-        good = good && ok_e;
-        acc = k1_add(acc, q);
-    }
-    if (live) {
-        k1_store_affine(out_xy + (size_t)i * 16, acc);
-        ok[i] = good ? 1u : 0u;
-    }
+    sswu_map_to_curve<Secp256k1Sswu>(us, out_xy, ok, n, per_item);
 }
 
 // Diagnostic (dr_secp256k1_field_selftest): fsecp256k1.hip.h's operations on raw limb images, one lane per (a, b) pair of 9 int32 limbs

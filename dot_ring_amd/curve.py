@@ -20,6 +20,7 @@ hashing and the Elligator map stay host-side big-int code exactly as they are in
 """
 from __future__ import annotations
 
+import dataclasses
 import hashlib
 from dataclasses import dataclass
 from typing import Callable
@@ -66,7 +67,7 @@ class SuiteParams:
     )
     encoding: Encoding = Encoding()
     curve_id: int = _native.CURVE_BANDERSNATCH      # DR_CURVE_* of include/dotring_hip.h
-    e2c: str = "ell2"                               # "ell2" (Elligator 2, RO), "tai" (try and increment), "sswu" / "sswu_nu" (RFC 9380)
+    e2c: str = "ell2"                               # "ell2" / "ell2_nu" (Elligator 2), "tai" (try and increment), "sswu" / "sswu_nu" (RFC 9380)
 
     @property
     def h2c_dst(self) -> bytes:
@@ -855,6 +856,118 @@ class Secp256k1Point:
         return unpack_points(cls, runtime.context().encode_to_curve_batch(cls._suite_struct(), list(alpha_strings), salts))
 
 
+class P256SswuPoint(P256Point):
+    """Affine point of P256_RO / P256_NU (dot_ring/curve/specs/p256.py with E2C_Variant.SSWU / SSWU_NU): P-256's group and kernels under
+    the variant's curve id, the reference's generic SEC1 codec in place of P256_TAI's (P256Point.point_to_string defers to
+    SWAffinePoint's for these variants), and hashing to the curve by RFC 9380's simplified SWU map (k_p256_map_to_curve)."""
+    __slots__ = ()
+
+    # -- codec: SEC1 (sw_affine_point.py point_to_string / string_to_point)
+    def point_to_string(self, compressed: bool = True) -> bytes:
+        if self.is_identity():
+            return b"\x00"
+        x = self.x.to_bytes(32, "big")
+        if compressed:
+            return (b"\x03" if self.y % 2 else b"\x02") + x
+        return b"\x04" + x + self.y.to_bytes(32, "big")
+
+    @classmethod
+    def string_to_point(cls, data):
+        if isinstance(data, str):
+            data = bytes.fromhex(data)
+        data = bytes(data)
+        if len(data) == 0:
+            raise ValueError("Empty octet string")
+        prefix, p = data[0], cls._P
+        if prefix == 0x00:
+            if len(data) != 1:
+                raise ValueError("Point at infinity must be single byte 0x00")
+            return cls.identity()
+        if prefix in (0x02, 0x03):
+            if len(data) != 33:
+                raise ValueError(f"Invalid compressed point length: expected 33, got {len(data)}")
+            return cls._string_to_sec1_point(data)
+        if prefix == 0x04:
+            if len(data) != 65:
+                raise ValueError(f"Invalid uncompressed point length: expected 65, got {len(data)}")
+            x, y = int.from_bytes(data[1:33], "big"), int.from_bytes(data[33:], "big")
+            if x >= p:
+                raise ValueError(f"x-coordinate {x} is not in field Fp (p={p})")
+            if y >= p:
+                raise ValueError(f"y-coordinate {y} is not in field Fp (p={p})")
+            if not cls._on_curve(x, y):
+                raise ValueError(f"Point ({x}, {y}) is not on curve")
+            return cls(x, y)
+        raise ValueError(f"Invalid point encoding prefix: 0x{prefix:02x}")
+
+    # -- hash to curve (RFC 9380; sw_affine_point.py:428-533): expand_message_xmd natively on the host, the map on the GPU
+    @classmethod
+    def _per_item(cls) -> int:
+        return 1 if cls.curve.params.e2c.endswith("_nu") else 2
+
+    @classmethod
+    def _mapped(cls, us: bytes, per_item: int):
+        raw, _ = runtime.context().p256_map_to_curve(us, per_item)          # (no denominator of this map can vanish)
+        return unpack_points(cls, raw)
+
+    @classmethod
+    def map_to_curve_simple_swu(cls, u: int):
+        return cls._mapped((int(u) % cls._P).to_bytes(32, "little"), 1)[0]
+
+    hash_to_field_pairs = Secp256k1Point.__dict__["hash_to_field_pairs"]
+    encode_to_curve_from_field = Secp256k1Point.__dict__["encode_to_curve_from_field"]
+
+
+class Ed25519Ell2Point(BandersnatchPoint):
+    """Affine point of Ed25519_RO / Ed25519_NU (dot_ring/curve/specs/ed25519.py with E2C_Variant.ELL2 / ELL2_NU): Ed25519's group, kernels
+    and codec under the variant's curve id, hashing to the curve by RFC 9380's Elligator 2 (k_ed25519_map_to_curve: the map onto
+    curve25519, the reference's mont_to_ed25519, the sum of two images for RO, the cofactor cleared)."""
+    __slots__ = ()
+
+    @classmethod
+    def _per_item(cls) -> int:
+        return 1 if cls.curve.params.e2c.endswith("_nu") else 2
+
+    @classmethod
+    def _mapped(cls, us: bytes, per_item: int):
+        raw, ok = runtime.context().ed25519_map_to_curve(us, per_item)
+        if 0 in ok:
+            raise ValueError("base is not invertible for the given modulus")      # pow(v, -1, p) / pow(u + 1, -1, p) of mont_to_ed25519
+        return unpack_points(cls, raw)
+
+    @classmethod
+    def map_to_curve(cls, u: int):
+        """Ed25519Point.map_to_curve (te_curve.py:48-95, then mont_to_ed25519): ONE image with its cofactor not cleared, host big-int code
+        as BandersnatchPoint.map_to_curve is; the batched path (encode_to_curve_from_field) runs the same steps in the kernel"""
+        p, a = cls._P, 486662
+        tv1 = 2 * u * u % p
+        if tv1 == p - 1:
+            tv1 = 0
+        x1 = -a * pow(tv1 + 1, -1, p) % p
+        gx1 = ((x1 + a) * x1 + 1) * x1 % p
+        e2 = cls.curve.is_square(gx1)
+        x, y2 = (x1, gx1) if e2 else ((-x1 - a) % p, tv1 * gx1 % p)
+        y = cls.curve.mod_sqrt(y2)
+        if e2 ^ (y % 2 == 1):
+            y = -y % p
+        # pow raises ValueError where y = 0 or x = -1, as the reference does
+        return cls(_sqrt_tonelli_shanks(-486664, p) * x % p * pow(y, -1, p) % p, (x - 1) * pow(x + 1, -1, p) % p)
+
+    hash_to_field_pairs = Secp256k1Point.__dict__["hash_to_field_pairs"]
+    encode_to_curve_from_field = Secp256k1Point.__dict__["encode_to_curve_from_field"]
+
+    @classmethod
+    def encode_to_curve(cls, alpha_string: bytes, salt: bytes = b""):
+        return cls.encode_to_curve_batch([alpha_string], [salt])[0]
+
+    @classmethod
+    def encode_to_curve_batch(cls, alpha_strings, salts=None):
+        if not alpha_strings:
+            return []
+        # (a message whose image has no value comes back as DR_ERR_INVALID: a ValueError, as the reference's failing modular inverse is)
+        return unpack_points(cls, runtime.context().encode_to_curve_batch(cls._suite_struct(), list(alpha_strings), salts))
+
+
 # ------------------------------------------------------------------ batched helpers over the C ABI
 def pack_points(points) -> bytes:
     """x || y little-endian per point; an SW identity ((None, None)) packs as 64 zero bytes, as the ABI takes it."""
@@ -1056,6 +1169,21 @@ Ed25519_TAI = _suite(
 )
 Ed25519 = Ed25519_TAI
 
+
+# Ed25519_RO / Ed25519_NU (specs/ed25519.py: the same params, E2C_Variant.ELL2 / ELL2_NU): hashing to the curve by RFC 9380's
+# edwards25519_XMD:SHA-512_ELL2_RO_ (two field elements) or ..._NU_ (one); the suite id is the TAI variant's, as in the reference, so the
+# variant travels in the curve id (DR_CURVE_ED25519_RO / DR_CURVE_ED25519_NU).
+def _ed25519_variant(name: str, e2c: str, curve_id: int) -> CurveVariant:
+    params = dataclasses.replace(Ed25519_TAI.curve.params, curve_id=curve_id, e2c=e2c)
+    curve = BandersnatchCurve(params)
+    return CurveVariant(name, curve, type(f"{name}Point", (Ed25519Ell2Point,), {
+        "curve": curve, "__slots__": (), "_A": params.a, "_D": params.d, "_N": params.subgroup_order, "_H": params.cofactor,
+        "_CV": curve_id, "_P": params.field_modulus}))
+
+
+Ed25519_RO = _ed25519_variant("Ed25519_RO", "ell2", _native.CURVE_ED25519_RO)
+Ed25519_NU = _ed25519_variant("Ed25519_NU", "ell2_nu", _native.CURVE_ED25519_NU)
+
 # dot_ring/curve/specs/p256.py, the P256_TAI variant (the reference exports it as P256): NIST P-256 over its own field, a = -3,
 # cofactor 1, 33-byte points, try-and-increment with SHA-256; no accumulator base or padding point, and not twisted Edwards, so
 # RingProofParams refuses it.  Every group operation runs on the P-256 kernels (DR_CURVE_P256).
@@ -1079,6 +1207,18 @@ _P256_PARAMS = SuiteParams(
 P256_TAI = CurveVariant("P256_TAI", BandersnatchCurve(_P256_PARAMS), type("P256_TAIPoint", (P256Point,), {"__slots__": ()}))
 P256_TAI.point_type.curve = P256_TAI.curve
 P256 = P256_TAI
+
+
+# P256_RO / P256_NU (specs/p256.py: the same params, E2C_Variant.SSWU / SSWU_NU): hashing to the curve by RFC 9380's
+# P256_XMD:SHA-256_SSWU_RO_ (two field elements) or ..._NU_ (one), points in SEC1 form; the suite id is the TAI variant's, as in the
+# reference, so the variant travels in the curve id (DR_CURVE_P256_RO / DR_CURVE_P256_NU).  Not twisted Edwards: RingProofParams refuses them.
+def _p256_variant(name: str, e2c: str, curve_id: int) -> CurveVariant:
+    curve = BandersnatchCurve(dataclasses.replace(_P256_PARAMS, curve_id=curve_id, e2c=e2c))
+    return CurveVariant(name, curve, type(f"{name}Point", (P256SswuPoint,), {"__slots__": (), "curve": curve, "_CV": curve_id}))
+
+
+P256_RO = _p256_variant("P256_RO", "sswu", _native.CURVE_P256_RO)
+P256_NU = _p256_variant("P256_NU", "sswu_nu", _native.CURVE_P256_NU)
 
 # dot_ring/curve/specs/baby_jubjub.py: a = 1 over the BN254 scalar field, cofactor 8, try-and-increment with SHA-512 (the candidates lose
 # bit 254, as the reference masks them to the field's bit length).  It carries all three auxiliary points, but RingProofParams refuses

@@ -151,6 +151,18 @@ enum { DR_CURVE_BABYJUBJUB = 5 };
  * x below p, a root); dr_vrf_suite.xof must be 2.  The ring prover, the Ring-VRF calls, dr_ietf_verify_batch, the GLV and dr_bsn_*
  * entry points refuse them. */
 enum { DR_CURVE_SECP256K1 = 6, DR_CURVE_SECP256K1_NU = 7 };
+/* The RFC 9380 variants of P-256 and Ed25519 (the reference's P256_RO / P256_NU and Ed25519_RO / Ed25519_NU): the groups, kernels,
+ * raw point form and scalar handling of DR_CURVE_P256 and DR_CURVE_ED25519, hashing to the curve by a map kernel in place of
+ * try-and-increment (RO: two field elements and the sum of their images; NU: one).  Each shares its suite id with the
+ * try-and-increment variant, which is why the variant is part of the curve id.
+ *   DR_CURVE_P256_RO / _NU     P256_XMD:SHA-256_SSWU_RO_ / _NU_: the simplified SWU map straight onto the curve (csrc/sswu.hip.h, the
+ *                              template k_secp256k1_map_to_curve is the other instance of); dr_vrf_suite.xof must be 2.  Encodings are
+ *                              33 bytes, plain SEC1 compressed as DR_CURVE_SECP256K1's — NOT DR_CURVE_P256's little-endian x and flag
+ *                              byte: dr_te_decode_points reads 0x02 / 0x03, x big-endian below p, a root, and nothing else.
+ *   DR_CURVE_ED25519_RO / _NU  edwards25519_XMD:SHA-512_ELL2_RO_ / _NU_: Elligator 2 onto curve25519, the reference's mont_to_ed25519,
+ *                              the cofactor cleared; dr_vrf_suite.xof must be 0.  Encodings are DR_CURVE_ED25519's.
+ * The ring prover, the Ring-VRF calls, dr_ietf_verify_batch, the GLV and dr_bsn_* entry points refuse them, as they refuse ids 3, 4, 6, 7. */
+enum { DR_CURVE_P256_RO = 8, DR_CURVE_P256_NU = 9, DR_CURVE_ED25519_RO = 10, DR_CURVE_ED25519_NU = 11 };
 DR_API int dr_te_scalar_mul_batch(dr_ctx *ctx, int curve, const uint8_t *pts_xy, const uint8_t *scalars, size_t n, uint8_t *out_xy);
 DR_API int dr_te_msm(dr_ctx *ctx, int curve, const uint8_t *pts_xy, const uint8_t *scalars, size_t n, uint8_t out_xy[64]);
 DR_API int dr_te_msm_groups(dr_ctx *ctx, int curve, const uint8_t *pts_xy, const uint8_t *scalars, size_t groups, size_t m, uint8_t *out_xy);
@@ -206,6 +218,17 @@ DR_API int dr_secp256k1_field_selftest(dr_ctx *ctx, const int32_t *a_limbs /* n*
  * affine x || y.  ok[i] = 0 where a denominator of the isogeny is zero (the reference raises there; hashing cannot reach it in practice). */
 DR_API int dr_secp256k1_map_to_curve(dr_ctx *ctx, const uint8_t *us /* n*per_item*32 */, size_t n, int per_item, uint8_t *out_xy /* n*64 */,
                                      uint8_t *ok /* n */);
+/* The map of RFC 9380 onto P-256 (simplified SWU, A = -3, Z = -10, no isogeny), same arguments: out_xy[i] = the sum of item i's images,
+ * affine x || y (64 zero bytes if two images cancel); ok[i] is always 1 (no denominator of this map can vanish).  Inputs at or above p
+ * are refused with DR_ERR_INVALID. */
+DR_API int dr_p256_map_to_curve(dr_ctx *ctx, const uint8_t *us /* n*per_item*32 */, size_t n, int per_item, uint8_t *out_xy /* n*64 */,
+                                uint8_t *ok /* n */);
+/* The map of RFC 9380 onto Ed25519 (Elligator 2 onto curve25519 with Z = 2, then x = sqrt(-486664) u / v, y = (u - 1) / (u + 1) with the
+ * root the reference takes), same arguments: out_xy[i] = 8 times the sum of item i's images, a point of the prime-order subgroup.
+ * ok[i] = 0 where an image has no value (v = 0 or u = -1 on curve25519; the element 0 maps there): the reference's modular inverse
+ * fails there and out_xy[i] is meaningless.  Inputs at or above p are refused with DR_ERR_INVALID. */
+DR_API int dr_ed25519_map_to_curve(dr_ctx *ctx, const uint8_t *us /* n*per_item*32 */, size_t n, int per_item, uint8_t *out_xy /* n*64 */,
+                                   uint8_t *ok /* n */);
 /* Baby JubJub point decoding with the prime-order check (check = 1: as dr_te_decode_points for DR_CURVE_BABYJUBJUB) or the codec
  * alone (check = 0: y < p and a root; (0, 1) and (0, p - 1) decode whatever the sign bit).  ok[i] = 1 when accepted; out_xy[i] is
  * then x || y, otherwise 64 zero bytes. */
@@ -405,25 +428,31 @@ typedef struct dr_vrf_suite {
     const uint8_t *suite_id;        /* e.g. "Bandersnatch-SHA512-ELL2-v1" (bandersnatch.py:74-87) */
     size_t suite_id_len;
     int xof;                        /* 1: SHAKE128 suite, 0: SHA-512 (counter-mode squeeze, expand_message_xmd), 2: SHA-256 (counter-mode
-                                       squeeze, the P-256 and secp256k1 suites); other values are refused */
+                                       squeeze, the P-256 and secp256k1 suites); other values are refused.  The RFC 9380 suites hash to the
+                                       field with the same hash: ids 6 - 9 want 2, ids 10 and 11 want 0 */
     uint8_t generator_xy[64];       /* group generator, x||y little-endian */
     uint8_t blinding_base_xy[64];   /* Pedersen blinding base (bandersnatch.py:89-102) */
     int curve;                      /* DR_CURVE_BANDERSNATCH (Elligator 2 hash-to-curve), DR_CURVE_JUBJUB, DR_CURVE_BANDERSNATCH_SW,
                                        DR_CURVE_ED25519, DR_CURVE_P256 or DR_CURVE_BABYJUBJUB (try-and-increment; for the SW suite and P-256 generator and
-                                       blinding base are SW affine), DR_CURVE_SECP256K1 or DR_CURVE_SECP256K1_NU (RFC 9380 simplified SWU) */
+                                       blinding base are SW affine), DR_CURVE_SECP256K1 or DR_CURVE_SECP256K1_NU, DR_CURVE_P256_RO or
+                                       DR_CURVE_P256_NU (RFC 9380 simplified SWU), DR_CURVE_ED25519_RO or DR_CURVE_ED25519_NU (RFC 9380
+                                       Elligator 2) */
 } dr_vrf_suite;
 
 /* hash_to_field(msg, 2) for `count` messages msgs[off[i]..off[i+1]): out = count * 2 field elements (32-byte LE),
  * the input format of dr_bsn_encode_to_curve_batch.  For DR_CURVE_SECP256K1 the two elements are those of RFC 9380's
  * expand_message_xmd with SHA-256 (the input format of dr_secp256k1_map_to_curve with per_item = 2); for DR_CURVE_SECP256K1_NU it is
- * hash_to_field(msg, 1): ONE element, 32 bytes, per message.  Host only: no context. */
+ * hash_to_field(msg, 1): ONE element, 32 bytes, per message.  DR_CURVE_P256_RO / DR_CURVE_ED25519_RO give the two elements of their
+ * suites (SHA-256 with P-256's DST and modulus; SHA-512 with a 128-byte Z_pad, edwards25519's DST and 2^255 - 19), the input formats of
+ * dr_p256_map_to_curve / dr_ed25519_map_to_curve; DR_CURVE_P256_NU / DR_CURVE_ED25519_NU one element.  Host only: no context. */
 DR_API int dr_hash_to_field_batch(const dr_vrf_suite *suite, const uint8_t *msgs, const uint64_t *off /* count+1 */, size_t count,
                                   uint8_t *out_u_pairs);
 
 /* encode_to_curve(salt_i || msg_i) for `count` messages (salts / salt_off nullable), whichever way the suite's curve hashes:
  * Elligator 2 (hash_to_field here + dr_bsn_encode_to_curve_batch) or try-and-increment (dot_ring/curve/point.py:252-296:
  * candidates hashed on worker threads, decompressed and cofactor-cleared on the GPU, several counters per launch) or, for
- * the secp256k1 suites, RFC 9380 (hash_to_field on worker threads + one launch of dr_secp256k1_map_to_curve's kernel). */
+ * curve ids 6 - 11, RFC 9380 (hash_to_field on worker threads + one launch of the kernel of dr_secp256k1_map_to_curve,
+ * dr_p256_map_to_curve or dr_ed25519_map_to_curve; DR_ERR_INVALID if a map has no value for a message). */
 DR_API int dr_encode_to_curve_batch(dr_ctx *ctx, const dr_vrf_suite *suite, const uint8_t *msgs, const uint64_t *off /* count+1 */,
                                     const uint8_t *salts, const uint64_t *salt_off, size_t count, uint8_t *out_xy /* count*64 */);
 
