@@ -9,12 +9,11 @@
 // the Montgomery limbs: a table entry is bn_to_words of each coordinate (8 words, value below 2^256, not canonical).
 #pragma once
 #include "fbn254.hip.h"
+#include "wave_curve.hip.h"
 
 namespace dr {
 
-constexpr int BJJ_BLOCK = 64;         // one wave per workgroup; 64 KiB of LDS table per wave, as k_ed_scalar_mul
-constexpr int BJJ_TABLE = 8;          // entries 1P..8P
-constexpr int BJJ_PT_WORDS = 32;      // X, Y, Z, T x 8 words
+constexpr int BJJ_BLOCK = 64;         // one wave per workgroup; 64 KiB of LDS table per wave (X, Y, Z, T x 8 words), as k_ed_scalar_mul
 
 // Square roots, p - 1 = Q 2^28 (Q odd).  With w = x^((Q-1)/2), R = w x, t = R w = x^Q, t lies in the cyclic group <c> of order
 // 2^28, c = 5^Q (5 is the smallest non-residue).  Its logarithm e (t = c^e) is read off in four 7-bit windows, as fr_sqrt_core
@@ -119,33 +118,6 @@ DR_DEV BjjPoint bjj_cneg(const BjjPoint& p, bool negate) {
 }
 
 // ---------------------------------------------------------------- memory
-DR_DEV void bjj_load8(const uint32_t* p, uint32_t (&w)[8]) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    const uint4 a = q[0], b = q[1];
-    w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
-    w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
-}
-DR_DEV void bjj_store8(uint32_t* p, const uint32_t (&w)[8]) {
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(w[0], w[1], w[2], w[3]);
-    q[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
-// standard-form words in memory <-> Montgomery limbs
-DR_DEV Fbn bjj_load_fe(const uint32_t* p) {
-    uint32_t w[8];
-    bjj_load8(p, w);
-    return bn_unpack(w);
-}
-DR_DEV void bjj_store_fe(uint32_t* p, const Fbn& a) {
-    uint32_t w[8];
-    bn_pack(a, w);
-    bjj_store8(p, w);
-}
-DR_DEV void bjj_store_affine(uint32_t* out, const BjjPoint& acc) {
-    const Fbn zi = bn_inv(acc.z);
-    bjj_store_fe(out, mul(acc.x, zi));
-    bjj_store_fe(out + 8, mul(acc.y, zi));
-}
 // a normal (value in (-2^253, p + 2^253)) as the 8 words of its Montgomery value, moved into [0, 2^256): carried, p added when it
 // is negative — bn_unpack_raw reads it back as a normal of the same value mod p
 DR_DEV void bn_to_words(const Fbn& a, uint32_t (&w)[8]) {
@@ -160,44 +132,6 @@ DR_DEV void bn_to_words(const Fbn& a, uint32_t (&w)[8]) {
         w[j] |= u << sh;
         if (sh > 3 && j + 1 < 8) w[j + 1] |= u >> (32 - sh);
     }
-}
-// LDS table [entry][word][lane] (bank = lane whatever the entry)
-DR_DEV void bjj_lds_store(uint32_t* tab, int entry, int lane, const BjjPoint& p) {
-    uint32_t* base = tab + (size_t)entry * BJJ_PT_WORDS * BJJ_BLOCK + lane;
-    uint32_t x[8], y[8], z[8], t[8];
-    bn_to_words(p.x, x); bn_to_words(p.y, y); bn_to_words(p.z, z); bn_to_words(p.t, t);
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        base[(0 + i) * BJJ_BLOCK] = x[i];
-        base[(8 + i) * BJJ_BLOCK] = y[i];
-        base[(16 + i) * BJJ_BLOCK] = z[i];
-        base[(24 + i) * BJJ_BLOCK] = t[i];
-    }
-}
-DR_DEV BjjPoint bjj_lds_load(const uint32_t* tab, int entry, int lane) {
-    const uint32_t* base = tab + (size_t)entry * BJJ_PT_WORDS * BJJ_BLOCK + lane;
-    uint32_t x[8], y[8], z[8], t[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        x[i] = base[(0 + i) * BJJ_BLOCK];
-        y[i] = base[(8 + i) * BJJ_BLOCK];
-        z[i] = base[(16 + i) * BJJ_BLOCK];
-        t[i] = base[(24 + i) * BJJ_BLOCK];
-    }
-    BjjPoint p;
-    p.x = bn_unpack_raw(x); p.y = bn_unpack_raw(y); p.z = bn_unpack_raw(z); p.t = bn_unpack_raw(t);
-    return p;
-}
-DR_DEV BjjPoint bjj_shfl_down(const BjjPoint& p, unsigned delta) {
-    BjjPoint o;
-#pragma unroll
-    for (int t = 0; t < BN_L; t++) {
-        o.x.l[t] = __shfl_down(p.x.l[t], delta, 64);
-        o.y.l[t] = __shfl_down(p.y.l[t], delta, 64);
-        o.z.l[t] = __shfl_down(p.z.l[t], delta, 64);
-        o.t.l[t] = __shfl_down(p.t.l[t], delta, 64);
-    }
-    return o;
 }
 
 // k mod l for a 256-bit k: floor((2^256 - 1) / l) = 42 < 64, so conditional subtractions of 32 l, 16 l, 8 l, 4 l, 2 l and l (the
@@ -218,89 +152,43 @@ DR_DEV void bjj_reduce_mod_order(uint32_t (&k)[8]) {
     }
 }
 
-// k P for k < l < 2^251 on the fixed schedule of ed_scalar_mul_core: table 1P..8P in LDS, 64 signed 4-bit windows, 4 doublings and
-// one table addition each whatever the digits — the secret scalars of the provers go through here
-DR_DEV BjjPoint bjj_scalar_mul_core(uint32_t* tab, int lane, const Fbn& px, const Fbn& py, const uint32_t (&k)[8]) {
-    BjjPoint P;
-    P.x = px; P.y = py; P.z = bn_one(); P.t = mul(px, py);
-    bjj_lds_store(tab, 0, lane, P);
-    BjjPoint Q = bjj_dbl<true>(P);
-    bjj_lds_store(tab, 1, lane, Q);
-#pragma unroll 1
-    for (int e = 2; e < BJJ_TABLE; e++) {
-        Q = bjj_add(Q, P);
-        bjj_lds_store(tab, e, lane, Q);
+// wave_curve.hip.h's description of Baby JubJub: standard-form words at the ABI, Montgomery limbs inside and Montgomery words
+// (bn_to_words / bn_unpack_raw) in the LDS table, 64 windows (l < 2^251)
+struct BjjCurve {
+    using Fe = Fbn;
+    using Point = BjjPoint;
+    static constexpr int BLOCK = BJJ_BLOCK, WINDOWS = 64, LDS_WORDS = 8;
+    static constexpr bool EXTENDED = true, ZERO_IS_IDENTITY = false;
+    DR_DEV static Fbn unpack(const uint32_t (&w)[8]) { return bn_unpack(w); }
+    DR_DEV static void pack(const Fbn& a, uint32_t (&w)[8]) { bn_pack(a, w); }
+    DR_DEV static Fbn inv(const Fbn& a) { return bn_inv(a); }
+    DR_DEV static void to_lds(const Fbn& a, uint32_t (&w)[8]) { bn_to_words(a, w); }
+    DR_DEV static Fbn from_lds(const uint32_t (&w)[8]) { return bn_unpack_raw(w); }
+    DR_DEV static BjjPoint identity() { return bjj_identity(); }
+    DR_DEV static BjjPoint from_affine(const Fbn& x, const Fbn& y) {
+        BjjPoint P;
+        P.x = x; P.y = y; P.z = bn_one(); P.t = mul(x, y);
+        return P;
     }
-    uint32_t dig[8];                 // 64 digits in [-8, 7], stored as d + 8
-    uint32_t carry_in = 0;
-#pragma unroll
-    for (int w = 0; w < 8; w++) {
-        uint32_t packed = 0;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const uint32_t v = ((k[w] >> (4 * j)) & 15u) + carry_in;
-            carry_in = v >= 8u ? 1u : 0u;
-            packed |= ((v + 8u) & 15u) << (4 * j);
-        }
-        dig[w] = packed;
+    DR_DEV static BjjPoint add(const BjjPoint& p, const BjjPoint& q) { return bjj_add(p, q); }
+    DR_DEV static BjjPoint dbl(const BjjPoint& p) { return bjj_dbl<true>(p); }
+    DR_DEV static BjjPoint dbl_no_t(const BjjPoint& p) { return bjj_dbl<false>(p); }
+    DR_DEV static BjjPoint cneg(const BjjPoint& p, bool negate) { return bjj_cneg(p, negate); }
+    DR_DEV static void load_scalar(const uint32_t* p, uint32_t (&k)[8]) {
+        wave_load8(p, k);
+        bjj_reduce_mod_order(k);
     }
-    // (k < l < 2^251: the top nibble is 0, the final carry is 0)
-    const Fbn d = Fbn::constant<FbnConsts::D>();
-    BjjPoint acc = bjj_identity();
-#pragma unroll 1
-    for (int w = 63; w >= 0; w--) {
-#pragma unroll 1
-        for (int j = 0; j < 3; j++) acc = bjj_dbl<false>(acc);
-        acc = bjj_dbl<true>(acc);
-        const int dg = (int)((dig[w >> 3] >> (4 * (w & 7))) & 15u) - 8;
-        const int mag = dg < 0 ? -dg : dg;
-        BjjPoint T = bjj_lds_load(tab, mag == 0 ? 0 : mag - 1, lane);
-        T = bjj_cneg(T, dg < 0);
-        if (mag == 0) T = bjj_identity();
-        acc = bjj_add_dt(acc, T, mul(d, T.t));
-    }
-    return acc;
-}
+};
 
-DR_DEV void bjj_load_scalar(const uint32_t* p, uint32_t (&k)[8]) {
-    bjj_load8(p, k);
-    bjj_reduce_mod_order(k);
-}
-
-// out[i] = k[i] P[i].  pts: n x 16 words (x || y), ks: n x 8, out: n x 16.  One lane per multiplication.
+// out[i] = k[i] P[i]: wave_curve.hip.h's kernel bodies for this curve
 __global__ __launch_bounds__(BJJ_BLOCK) void k_bjj_scalar_mul(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks,
                                                               uint32_t* __restrict__ out, uint32_t n) {
-    __shared__ uint32_t tab[BJJ_TABLE * BJJ_PT_WORDS * BJJ_BLOCK];
-    const int lane = threadIdx.x;
-    uint32_t i = blockIdx.x * BJJ_BLOCK + lane;
-    const bool live = i < n;
-    if (!live) i = n - 1;            // keep the wave converged; the duplicate result is not stored
-    const Fbn px = bjj_load_fe(pts + (size_t)i * 16), py = bjj_load_fe(pts + (size_t)i * 16 + 8);
-    uint32_t k[8];
-    bjj_load_scalar(ks + (size_t)i * 8, k);
-    const BjjPoint acc = bjj_scalar_mul_core(tab, lane, px, py, k);
-    if (live) bjj_store_affine(out + (size_t)i * 16, acc);
+    wave_scalar_mul<BjjCurve>(pts, ks, out, n);
 }
-
-// out[g] = sum_{j<m} k[g m + j] P[g m + j]: one lane per term (m padded to mpad, a power of two <= 64), folded with shuffles —
-// k_ed_msm_groups for this curve
+// out[g] = sum_{j<m} k[g m + j] P[g m + j]
 __global__ __launch_bounds__(BJJ_BLOCK) void k_bjj_msm_groups(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks,
                                                               uint32_t* __restrict__ out, uint32_t groups, uint32_t m, uint32_t mpad) {
-    __shared__ uint32_t tab[BJJ_TABLE * BJJ_PT_WORDS * BJJ_BLOCK];
-    const int lane = threadIdx.x;
-    const uint32_t per_block = BJJ_BLOCK / mpad;
-    const uint32_t g = blockIdx.x * per_block + lane / mpad;
-    const uint32_t j = lane % mpad;
-    const bool live = g < groups && j < m;
-    const size_t idx = live ? (size_t)g * m + j : 0;          // dead lanes recompute term 0 and are masked out
-    const Fbn px = bjj_load_fe(pts + idx * 16), py = bjj_load_fe(pts + idx * 16 + 8);
-    uint32_t k[8];
-    bjj_load_scalar(ks + idx * 8, k);
-    const BjjPoint r = bjj_scalar_mul_core(tab, lane, px, py, k);
-    BjjPoint acc = live ? r : bjj_identity();
-#pragma unroll 1
-    for (uint32_t s = mpad >> 1; s > 0; s >>= 1) acc = bjj_add(acc, bjj_shfl_down(acc, s));
-    if (g < groups && j == 0) bjj_store_affine(out + (size_t)g * 16, acc);
+    wave_msm_groups<BjjCurve>(pts, ks, out, groups, m, mpad);
 }
 
 // Decoding (the reference's point.py:150-214 with te_affine_point.py:297-316), one lane per 32-byte encoding: the sign is bit 255,
@@ -316,13 +204,13 @@ enum { BJJ_DEC_CODEC = 0, BJJ_DEC_CHECK = 1, BJJ_DEC_TAI = 2 };
 template <int MODE>
 __global__ __launch_bounds__(BJJ_BLOCK) void k_bjj_decode_points(const uint32_t* __restrict__ enc /* n*8 */, uint32_t* __restrict__ out_xy /* n*16 */,
                                                                  uint32_t* __restrict__ ok, uint32_t n) {
-    __shared__ uint32_t tab[MODE == BJJ_DEC_CHECK ? BJJ_TABLE * BJJ_PT_WORDS * BJJ_BLOCK : 1];
+    __shared__ uint32_t tab[MODE == BJJ_DEC_CHECK ? wave_table_words<BjjCurve>() : 1];
     const int lane = threadIdx.x;
     uint32_t i = blockIdx.x * BJJ_BLOCK + lane;
     const bool live = i < n;
     if (!live) i = n - 1;
     uint32_t ys[8];
-    bjj_load8(enc + (size_t)i * 8, ys);
+    wave_load8(enc + (size_t)i * 8, ys);
     const bool sign = (ys[7] >> 31) != 0;
     ys[7] &= 0x7fffffffu;
     bool valid;
@@ -342,8 +230,7 @@ __global__ __launch_bounds__(BJJ_BLOCK) void k_bjj_decode_points(const uint32_t*
     if (bn_is_larger(x) != sign) x = neg(x);
     Fbn ox = x, oy = yy;
     if constexpr (MODE != BJJ_DEC_CODEC) {
-        BjjPoint P;
-        P.x = x; P.y = yy; P.z = one; P.t = mul(x, yy);
+        const BjjPoint P = BjjCurve::from_affine(x, yy);
         BjjPoint Q = P;
 #pragma unroll 1
         for (int j = 0; j < 3; j++) Q = bjj_dbl<true>(Q);
@@ -357,14 +244,14 @@ __global__ __launch_bounds__(BJJ_BLOCK) void k_bjj_decode_points(const uint32_t*
             uint32_t k[8];
 #pragma unroll
             for (int j = 0; j < 8; j++) k[j] = HINV[j];
-            const BjjPoint R = bjj_scalar_mul_core(tab, lane, qx, qy, k);
+            const BjjPoint R = wave_scalar_mul_core<BjjCurve>(tab, lane, BjjCurve::from_affine(qx, qy), k);
             if (!bn_equal(R.x, mul(x, R.z)) || !bn_equal(R.y, mul(yy, R.z))) valid = false;
         }
     }
     if (!valid) { ox = Fbn::zero(); oy = Fbn::zero(); }
     if (live) {
-        bjj_store_fe(out_xy + (size_t)i * 16, ox);
-        bjj_store_fe(out_xy + (size_t)i * 16 + 8, oy);
+        wave_store_fe<BjjCurve>(out_xy + (size_t)i * 16, ox);
+        wave_store_fe<BjjCurve>(out_xy + (size_t)i * 16 + 8, oy);
         ok[i] = valid ? 1u : 0u;
     }
 }
@@ -383,23 +270,23 @@ __global__ __launch_bounds__(64) void k_bjj_field_selftest(const int32_t* __rest
 #pragma unroll
     for (int t = 0; t < BN_L; t++) { a.l[t] = a_limbs[(size_t)i * BN_L + t]; b.l[t] = b_limbs[(size_t)i * BN_L + t]; }
     uint32_t* o = out + (size_t)i * BJJ_SELFTEST_RECORDS * 8;
-    bjj_store_fe(o + 0, mul(a, b));
-    bjj_store_fe(o + 8, sqr(a));
-    bjj_store_fe(o + 16, add(a, b));
-    bjj_store_fe(o + 24, sub(a, b));
-    bjj_store_fe(o + 32, neg(a));
-    bjj_store_fe(o + 40, carry(a));
-    bjj_store_fe(o + 48, mul2(a, b, b, a));
-    bjj_store_fe(o + 56, bn_inv(a));
+    wave_store_fe<BjjCurve>(o + 0, mul(a, b));
+    wave_store_fe<BjjCurve>(o + 8, sqr(a));
+    wave_store_fe<BjjCurve>(o + 16, add(a, b));
+    wave_store_fe<BjjCurve>(o + 24, sub(a, b));
+    wave_store_fe<BjjCurve>(o + 32, neg(a));
+    wave_store_fe<BjjCurve>(o + 40, carry(a));
+    wave_store_fe<BjjCurve>(o + 48, mul2(a, b, b, a));
+    wave_store_fe<BjjCurve>(o + 56, bn_inv(a));
     Fbn r;
     const bool sq = bjj_sqrt(a, r);
-    bjj_store_fe(o + 64, r);
-    bjj_store_fe(o + 72, a);
+    wave_store_fe<BjjCurve>(o + 64, r);
+    wave_store_fe<BjjCurve>(o + 72, a);
     uint32_t w[8];
     bn_to_words(mul(a, b), w);
-    bjj_store_fe(o + 80, bn_unpack_raw(w));
+    wave_store_fe<BjjCurve>(o + 80, bn_unpack_raw(w));
     bn_pack(a, w);
-    bjj_store_fe(o + 88, bn_unpack(w));
+    wave_store_fe<BjjCurve>(o + 88, bn_unpack(w));
     flags[i] = (sq ? 1u : 0u) | (bn_is_larger(a) ? 4u : 0u);
 }
 

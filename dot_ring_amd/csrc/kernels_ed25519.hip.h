@@ -9,12 +9,11 @@
 // JubJub.  The comments give the limb bound of every intermediate against fe25519.hip.h's contract ("n" = normal).
 #pragma once
 #include "fe25519.hip.h"
+#include "wave_curve.hip.h"
 
 namespace dr {
 
-constexpr int ED_BLOCK = 64;          // one wave per workgroup; 64 KiB of LDS table per wave, as k_bsn_scalar_mul
-constexpr int ED_TABLE = 8;           // entries 1P..8P
-constexpr int ED_PT_WORDS = 32;       // X, Y, Z, T x 8 canonical words
+constexpr int ED_BLOCK = 64;          // one wave per workgroup; 64 KiB of LDS table per wave (X, Y, Z, T x 8 words), as k_bsn_scalar_mul
 
 struct EdPoint {
     F25 x, y, z, t;
@@ -70,72 +69,6 @@ DR_DEV EdPoint ed_cneg(const EdPoint& p, bool negate) {
     return r;
 }
 
-// ---------------------------------------------------------------- memory
-DR_DEV void ed_load8(const uint32_t* p, uint32_t (&w)[8]) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    const uint4 a = q[0], b = q[1];
-    w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
-    w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
-}
-DR_DEV void ed_store8(uint32_t* p, const uint32_t (&w)[8]) {
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(w[0], w[1], w[2], w[3]);
-    q[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
-DR_DEV F25 ed_load_fe(const uint32_t* p) {
-    uint32_t w[8];
-    ed_load8(p, w);
-    return fe_unpack(w);
-}
-DR_DEV void ed_store_fe(uint32_t* p, const F25& a) {
-    uint32_t w[8];
-    fe_pack(a, w);
-    ed_store8(p, w);
-}
-DR_DEV void ed_store_affine(uint32_t* out, const EdPoint& acc) {
-    const F25 zi = fe_inv(acc.z);
-    ed_store_fe(out, mul(acc.x, zi));
-    ed_store_fe(out + 8, mul(acc.y, zi));
-}
-// LDS table [entry][word][lane] (bank = lane whatever the entry), canonical words
-DR_DEV void ed_lds_store(uint32_t* tab, int entry, int lane, const EdPoint& p) {
-    uint32_t* base = tab + (size_t)entry * ED_PT_WORDS * ED_BLOCK + lane;
-    uint32_t x[8], y[8], z[8], t[8];
-    fe_pack(p.x, x); fe_pack(p.y, y); fe_pack(p.z, z); fe_pack(p.t, t);
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        base[(0 + i) * ED_BLOCK] = x[i];
-        base[(8 + i) * ED_BLOCK] = y[i];
-        base[(16 + i) * ED_BLOCK] = z[i];
-        base[(24 + i) * ED_BLOCK] = t[i];
-    }
-}
-DR_DEV EdPoint ed_lds_load(const uint32_t* tab, int entry, int lane) {
-    const uint32_t* base = tab + (size_t)entry * ED_PT_WORDS * ED_BLOCK + lane;
-    uint32_t x[8], y[8], z[8], t[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        x[i] = base[(0 + i) * ED_BLOCK];
-        y[i] = base[(8 + i) * ED_BLOCK];
-        z[i] = base[(16 + i) * ED_BLOCK];
-        t[i] = base[(24 + i) * ED_BLOCK];
-    }
-    EdPoint p;
-    p.x = fe_unpack(x); p.y = fe_unpack(y); p.z = fe_unpack(z); p.t = fe_unpack(t);
-    return p;
-}
-DR_DEV EdPoint ed_shfl_down(const EdPoint& p, unsigned delta) {
-    EdPoint o;
-#pragma unroll
-    for (int t = 0; t < FE_L; t++) {
-        o.x.l[t] = __shfl_down(p.x.l[t], delta, 64);
-        o.y.l[t] = __shfl_down(p.y.l[t], delta, 64);
-        o.z.l[t] = __shfl_down(p.z.l[t], delta, 64);
-        o.t.l[t] = __shfl_down(p.t.l[t], delta, 64);
-    }
-    return o;
-}
-
 // k mod l for a 256-bit k: floor((2^256 - 1) / l) = 15, so 16 conditional subtractions (the same count in every lane)
 DR_DEV void ed_reduce_mod_order(uint32_t (&k)[8]) {
     constexpr uint32_t L[8] = {0x5cf5d3edu, 0x5812631au, 0xa2f79cd6u, 0x14def9deu, 0x00000000u, 0x00000000u, 0x00000000u, 0x10000000u};
@@ -149,89 +82,42 @@ DR_DEV void ed_reduce_mod_order(uint32_t (&k)[8]) {
     }
 }
 
-// k P for k < l < 2^253 on the fixed schedule of bsn_scalar_mul_core (kernels_te.hip.h): table 1P..8P in LDS, 64 signed 4-bit
-// windows, 4 doublings and one table addition each whatever the digits — the secret scalars of the provers go through here
-DR_DEV EdPoint ed_scalar_mul_core(uint32_t* tab, int lane, const F25& px, const F25& py, const uint32_t (&k)[8]) {
-    EdPoint P;
-    P.x = px; P.y = py; P.z = F25::one(); P.t = mul(px, py);
-    ed_lds_store(tab, 0, lane, P);
-    EdPoint Q = ed_dbl<true>(P);
-    ed_lds_store(tab, 1, lane, Q);
-#pragma unroll 1
-    for (int e = 2; e < ED_TABLE; e++) {
-        Q = ed_add(Q, P);
-        ed_lds_store(tab, e, lane, Q);
+// wave_curve.hip.h's description of Ed25519: canonical words at the ABI and in the LDS table, 64 windows (l < 2^253)
+struct Ed25519Curve {
+    using Fe = F25;
+    using Point = EdPoint;
+    static constexpr int BLOCK = ED_BLOCK, WINDOWS = 64, LDS_WORDS = 8;
+    static constexpr bool EXTENDED = true, ZERO_IS_IDENTITY = false;
+    DR_DEV static F25 unpack(const uint32_t (&w)[8]) { return fe_unpack(w); }
+    DR_DEV static void pack(const F25& a, uint32_t (&w)[8]) { fe_pack(a, w); }
+    DR_DEV static F25 inv(const F25& a) { return fe_inv(a); }
+    DR_DEV static void to_lds(const F25& a, uint32_t (&w)[8]) { fe_pack(a, w); }
+    DR_DEV static F25 from_lds(const uint32_t (&w)[8]) { return fe_unpack(w); }
+    DR_DEV static EdPoint identity() { return ed_identity(); }
+    DR_DEV static EdPoint from_affine(const F25& x, const F25& y) {
+        EdPoint P;
+        P.x = x; P.y = y; P.z = F25::one(); P.t = mul(x, y);
+        return P;
     }
-    uint32_t dig[8];                 // 64 digits in [-8, 7], stored as d + 8
-    uint32_t carry_in = 0;
-#pragma unroll
-    for (int w = 0; w < 8; w++) {
-        uint32_t packed = 0;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const uint32_t v = ((k[w] >> (4 * j)) & 15u) + carry_in;
-            carry_in = v >= 8u ? 1u : 0u;
-            packed |= ((v + 8u) & 15u) << (4 * j);
-        }
-        dig[w] = packed;
+    DR_DEV static EdPoint add(const EdPoint& p, const EdPoint& q) { return ed_add(p, q); }
+    DR_DEV static EdPoint dbl(const EdPoint& p) { return ed_dbl<true>(p); }
+    DR_DEV static EdPoint dbl_no_t(const EdPoint& p) { return ed_dbl<false>(p); }
+    DR_DEV static EdPoint cneg(const EdPoint& p, bool negate) { return ed_cneg(p, negate); }
+    DR_DEV static void load_scalar(const uint32_t* p, uint32_t (&k)[8]) {
+        wave_load8(p, k);
+        ed_reduce_mod_order(k);
     }
-    // (k < l < 2^253: the top nibble is <= 1, the final carry is 0)
-    const F25 d = F25::constant<Fe25519Consts::D>();
-    EdPoint acc = ed_identity();
-#pragma unroll 1
-    for (int w = 63; w >= 0; w--) {
-#pragma unroll 1
-        for (int j = 0; j < 3; j++) acc = ed_dbl<false>(acc);
-        acc = ed_dbl<true>(acc);
-        const int dg = (int)((dig[w >> 3] >> (4 * (w & 7))) & 15u) - 8;
-        const int mag = dg < 0 ? -dg : dg;
-        EdPoint T = ed_lds_load(tab, mag == 0 ? 0 : mag - 1, lane);
-        T = ed_cneg(T, dg < 0);
-        if (mag == 0) T = ed_identity();
-        acc = ed_add_dt(acc, T, mul(d, T.t));
-    }
-    return acc;
-}
+};
 
-DR_DEV void ed_load_scalar(const uint32_t* p, uint32_t (&k)[8]) {
-    ed_load8(p, k);
-    ed_reduce_mod_order(k);
-}
-
-// out[i] = k[i] P[i].  pts: n x 16 words (x || y), ks: n x 8, out: n x 16.  One lane per multiplication.
+// out[i] = k[i] P[i]: wave_curve.hip.h's kernel bodies for this curve
 __global__ __launch_bounds__(ED_BLOCK) void k_ed_scalar_mul(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks,
                                                             uint32_t* __restrict__ out, uint32_t n) {
-    __shared__ uint32_t tab[ED_TABLE * ED_PT_WORDS * ED_BLOCK];
-    const int lane = threadIdx.x;
-    uint32_t i = blockIdx.x * ED_BLOCK + lane;
-    const bool live = i < n;
-    if (!live) i = n - 1;            // keep the wave converged; the duplicate result is not stored
-    const F25 px = ed_load_fe(pts + (size_t)i * 16), py = ed_load_fe(pts + (size_t)i * 16 + 8);
-    uint32_t k[8];
-    ed_load_scalar(ks + (size_t)i * 8, k);
-    const EdPoint acc = ed_scalar_mul_core(tab, lane, px, py, k);
-    if (live) ed_store_affine(out + (size_t)i * 16, acc);
+    wave_scalar_mul<Ed25519Curve>(pts, ks, out, n);
 }
-
-// out[g] = sum_{j<m} k[g m + j] P[g m + j]: one lane per term (m padded to mpad, a power of two <= 64), folded with shuffles —
-// k_bsn_msm_groups for this curve
+// out[g] = sum_{j<m} k[g m + j] P[g m + j]
 __global__ __launch_bounds__(ED_BLOCK) void k_ed_msm_groups(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks,
                                                             uint32_t* __restrict__ out, uint32_t groups, uint32_t m, uint32_t mpad) {
-    __shared__ uint32_t tab[ED_TABLE * ED_PT_WORDS * ED_BLOCK];
-    const int lane = threadIdx.x;
-    const uint32_t per_block = ED_BLOCK / mpad;
-    const uint32_t g = blockIdx.x * per_block + lane / mpad;
-    const uint32_t j = lane % mpad;
-    const bool live = g < groups && j < m;
-    const size_t idx = live ? (size_t)g * m + j : 0;          // dead lanes recompute term 0 and are masked out
-    const F25 px = ed_load_fe(pts + idx * 16), py = ed_load_fe(pts + idx * 16 + 8);
-    uint32_t k[8];
-    ed_load_scalar(ks + idx * 8, k);
-    const EdPoint r = ed_scalar_mul_core(tab, lane, px, py, k);
-    EdPoint acc = live ? r : ed_identity();
-#pragma unroll 1
-    for (uint32_t s = mpad >> 1; s > 0; s >>= 1) acc = ed_add(acc, ed_shfl_down(acc, s));
-    if (g < groups && j == 0) ed_store_affine(out + (size_t)g * 16, acc);
+    wave_msm_groups<Ed25519Curve>(pts, ks, out, groups, m, mpad);
 }
 
 // Decoding (the reference's point.py:150-214 with te_affine_point.py:297-316), one lane per 32-byte encoding: the sign is bit 255,
@@ -247,13 +133,13 @@ enum { ED_DEC_CODEC = 0, ED_DEC_CHECK = 1, ED_DEC_TAI = 2 };
 template <int MODE>
 __global__ __launch_bounds__(ED_BLOCK) void k_ed_decode_points(const uint32_t* __restrict__ enc /* n*8 */, uint32_t* __restrict__ out_xy /* n*16 */,
                                                                uint32_t* __restrict__ ok, uint32_t n) {
-    __shared__ uint32_t tab[MODE == ED_DEC_CHECK ? ED_TABLE * ED_PT_WORDS * ED_BLOCK : 1];
+    __shared__ uint32_t tab[MODE == ED_DEC_CHECK ? wave_table_words<Ed25519Curve>() : 1];
     const int lane = threadIdx.x;
     uint32_t i = blockIdx.x * ED_BLOCK + lane;
     const bool live = i < n;
     if (!live) i = n - 1;
     uint32_t ys[8];
-    ed_load8(enc + (size_t)i * 8, ys);
+    wave_load8(enc + (size_t)i * 8, ys);
     const bool sign = (ys[7] >> 31) != 0;
     ys[7] &= 0x7fffffffu;
     bool valid;
@@ -273,8 +159,7 @@ __global__ __launch_bounds__(ED_BLOCK) void k_ed_decode_points(const uint32_t* _
     if (fe_is_larger(x) != sign) x = neg(x);
     F25 ox = x, oy = y;
     if constexpr (MODE != ED_DEC_CODEC) {
-        EdPoint P;
-        P.x = x; P.y = y; P.z = one; P.t = mul(x, y);
+        const EdPoint P = Ed25519Curve::from_affine(x, y);
         EdPoint Q = P;
 #pragma unroll 1
         for (int j = 0; j < 3; j++) Q = ed_dbl<true>(Q);
@@ -288,14 +173,14 @@ __global__ __launch_bounds__(ED_BLOCK) void k_ed_decode_points(const uint32_t* _
             uint32_t k[8];
 #pragma unroll
             for (int j = 0; j < 8; j++) k[j] = HINV[j];
-            const EdPoint R = ed_scalar_mul_core(tab, lane, qx, qy, k);
+            const EdPoint R = wave_scalar_mul_core<Ed25519Curve>(tab, lane, Ed25519Curve::from_affine(qx, qy), k);
             if (!fe_equal(R.x, mul(x, R.z)) || !fe_equal(R.y, mul(y, R.z))) valid = false;
         }
     }
     if (!valid) { ox = F25::zero(); oy = F25::zero(); }
     if (live) {
-        ed_store_fe(out_xy + (size_t)i * 16, ox);
-        ed_store_fe(out_xy + (size_t)i * 16 + 8, oy);
+        wave_store_fe<Ed25519Curve>(out_xy + (size_t)i * 16, ox);
+        wave_store_fe<Ed25519Curve>(out_xy + (size_t)i * 16 + 8, oy);
         ok[i] = valid ? 1u : 0u;
     }
 }
@@ -373,14 +258,14 @@ __global__ __launch_bounds__(ED_BLOCK) void k_ed25519_map_to_curve(const uint32_
 #pragma unroll 1
     for (uint32_t e = 0; e < per_item; e++) {
         bool ok_e;
-        const EdPoint q = ed_ell2_map(ed_load_fe(us + ((size_t)i * per_item + e) * 8), ok_e);
+        const EdPoint q = ed_ell2_map(wave_load_fe<Ed25519Curve>(us + ((size_t)i * per_item + e) * 8), ok_e);
         good = good && ok_e;
         acc = ed_add(acc, q);
     }
 #pragma unroll 1
     for (int j = 0; j < 3; j++) acc = ed_dbl<true>(acc);                     // the cofactor
     if (live) {
-        ed_store_affine(out_xy + (size_t)i * 16, acc);
+        wave_store_affine<Ed25519Curve>(out_xy + (size_t)i * 16, acc);
         ok[i] = good ? 1u : 0u;
     }
 }
@@ -398,20 +283,20 @@ __global__ __launch_bounds__(64) void k_fe25519_selftest(const int32_t* __restri
 #pragma unroll
     for (int t = 0; t < FE_L; t++) { a.l[t] = a_limbs[(size_t)i * FE_L + t]; b.l[t] = b_limbs[(size_t)i * FE_L + t]; }
     uint32_t* o = out + (size_t)i * FE_SELFTEST_RECORDS * 8;
-    ed_store_fe(o + 0, mul(a, b));
-    ed_store_fe(o + 8, sqr(a));
-    ed_store_fe(o + 16, add(a, b));
-    ed_store_fe(o + 24, sub(a, b));
-    ed_store_fe(o + 32, neg(a));
-    ed_store_fe(o + 40, carry(a));
-    ed_store_fe(o + 48, mul2(a, b, b, a));
-    ed_store_fe(o + 56, fe_inv(a));
+    wave_store_fe<Ed25519Curve>(o + 0, mul(a, b));
+    wave_store_fe<Ed25519Curve>(o + 8, sqr(a));
+    wave_store_fe<Ed25519Curve>(o + 16, add(a, b));
+    wave_store_fe<Ed25519Curve>(o + 24, sub(a, b));
+    wave_store_fe<Ed25519Curve>(o + 32, neg(a));
+    wave_store_fe<Ed25519Curve>(o + 40, carry(a));
+    wave_store_fe<Ed25519Curve>(o + 48, mul2(a, b, b, a));
+    wave_store_fe<Ed25519Curve>(o + 56, fe_inv(a));
     F25 r;
     const bool sq = fe_sqrt_ratio(a, F25::one(), r);
-    ed_store_fe(o + 64, r);
-    ed_store_fe(o + 72, a);
+    wave_store_fe<Ed25519Curve>(o + 64, r);
+    wave_store_fe<Ed25519Curve>(o + 72, a);
     const bool rt = fe_sqrt_ratio(a, b, r);
-    ed_store_fe(o + 80, r);
+    wave_store_fe<Ed25519Curve>(o + 80, r);
     flags[i] = (sq ? 1u : 0u) | (rt ? 2u : 0u) | (fe_is_larger(a) ? 4u : 0u);
 }
 

@@ -11,13 +11,11 @@
 #pragma once
 #include "fp256.hip.h"
 #include "sswu.hip.h"
+#include "wave_curve.hip.h"
 
 namespace dr {
 
 constexpr int P256_BLOCK = 64;        // one wave per workgroup, as k_ed_scalar_mul
-constexpr int P256_TABLE = 8;         // entries 1P..8P
-constexpr int P256_PT_WORDS = 27;     // X, Y, Z x 9 limbs (the table holds limb images: no packing)
-constexpr int P256_WINDOWS = 65;      // 64 signed 4-bit digits of k < n < 2^256 and the carry out of the top one
 
 struct P256Point {
     F256 x, y, z;
@@ -78,162 +76,66 @@ DR_DEV P256Point p256_cneg(const P256Point& p, bool negate) {
     return r;
 }
 
-// ---------------------------------------------------------------- memory
-DR_DEV void p256_load8(const uint32_t* p, uint32_t (&w)[8]) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    const uint4 a = q[0], b = q[1];
-    w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
-    w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
-}
-DR_DEV void p256_store8(uint32_t* p, const uint32_t (&w)[8]) {
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(w[0], w[1], w[2], w[3]);
-    q[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
-// affine x || y (16 words, canonical) -> projective; 64 zero bytes -> the identity
-DR_DEV P256Point p256_load_affine(const uint32_t* p) {
-    uint32_t x[8], y[8];
-    p256_load8(p, x);
-    p256_load8(p + 8, y);
-    uint32_t o = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) o |= x[j] | y[j];
-    P256Point r;
-    r.x = fp_unpack(x);
-    r.y = fp_unpack(y);
-    r.z = fp_one();
-    if (o == 0) r = p256_identity();
-    return r;
-}
-DR_DEV void p256_store_fe(uint32_t* p, const F256& a) {
-    uint32_t w[8];
-    fp_pack(a, w);
-    p256_store8(p, w);
-}
-// x || y of the point; the identity (Z = 0, so x = y = 0 after the multiplication by 0^-1 = 0) stores 64 zero bytes
-DR_DEV void p256_store_affine(uint32_t* out, const P256Point& acc) {
-    const F256 zi = fp_inv(acc.z);
-    p256_store_fe(out, mul(acc.x, zi));
-    p256_store_fe(out + 8, mul(acc.y, zi));
-}
-// LDS table [entry][limb][lane] (bank = lane whatever the entry), limb images of the (normal) coordinates
-DR_DEV void p256_lds_store(uint32_t* tab, int entry, int lane, const P256Point& p) {
-    uint32_t* base = tab + (size_t)entry * P256_PT_WORDS * P256_BLOCK + lane;
-#pragma unroll
-    for (int i = 0; i < FP_L; i++) {
-        base[(0 + i) * P256_BLOCK] = (uint32_t)p.x.l[i];
-        base[(9 + i) * P256_BLOCK] = (uint32_t)p.y.l[i];
-        base[(18 + i) * P256_BLOCK] = (uint32_t)p.z.l[i];
-    }
-}
-DR_DEV P256Point p256_lds_load(const uint32_t* tab, int entry, int lane) {
-    const uint32_t* base = tab + (size_t)entry * P256_PT_WORDS * P256_BLOCK + lane;
-    P256Point p;
-#pragma unroll
-    for (int i = 0; i < FP_L; i++) {
-        p.x.l[i] = (int32_t)base[(0 + i) * P256_BLOCK];
-        p.y.l[i] = (int32_t)base[(9 + i) * P256_BLOCK];
-        p.z.l[i] = (int32_t)base[(18 + i) * P256_BLOCK];
-    }
-    return p;
-}
-DR_DEV P256Point p256_shfl_down(const P256Point& p, unsigned delta) {
-    P256Point o;
-#pragma unroll
-    for (int t = 0; t < FP_L; t++) {
-        o.x.l[t] = __shfl_down(p.x.l[t], delta, 64);
-        o.y.l[t] = __shfl_down(p.y.l[t], delta, 64);
-        o.z.l[t] = __shfl_down(p.z.l[t], delta, 64);
-    }
-    return o;
-}
-
 // k mod n for a 256-bit k: 2 n > 2^256, so one conditional subtraction (in every lane)
 DR_DEV void p256_load_scalar(const uint32_t* p, uint32_t (&k)[8]) {
     constexpr uint32_t N[8] = {0xfc632551u, 0xf3b9cac2u, 0xa7179e84u, 0xbce6faadu, 0xffffffffu, 0xffffffffu, 0x00000000u, 0xffffffffu};
-    p256_load8(p, k);
+    wave_load8(p, k);
     uint32_t d[8], borrow = 0;
 #pragma unroll
     for (int i = 0; i < 8; i++) d[i] = subb(k[i], N[i], borrow);
 #pragma unroll
     for (int i = 0; i < 8; i++) k[i] = borrow ? k[i] : d[i];
 }
-
-// k P for k < n on the fixed schedule of ed_scalar_mul_core (kernels_ed25519.hip.h): table 1P..8P in LDS, 65 signed 4-bit windows
-// (n has 256 bits: the carry out of the 64th digit is a 65th), four doublings and one table addition each whatever the digits —
-// the secret scalars of the provers go through here
-DR_DEV P256Point p256_scalar_mul_core(uint32_t* tab, int lane, const P256Point& P, const uint32_t (&k)[8]) {
-    p256_lds_store(tab, 0, lane, P);
-    P256Point Q = p256_dbl(P);
-    p256_lds_store(tab, 1, lane, Q);
-#pragma unroll 1
-    for (int e = 2; e < P256_TABLE; e++) {
-        Q = p256_add(Q, P);
-        p256_lds_store(tab, e, lane, Q);
-    }
-    uint32_t dig[8];                 // digits 0..63 in [-8, 7], stored as d + 8; digit 64 = top_carry
-    uint32_t carry_in = 0;
+// y^2 = x^3 - 3 x + b for x in Montgomery form; ok and a root (either one) if it exists
+DR_DEV bool p256_y_of_x(const F256& x, F256& y) {
+    const F256 x3 = mul(sqr(x), x);
+    const F256 rhs = fp_reduce(add(sub(x3, add(x, dbl(x))), F256::constant<Fp256Consts::B>()));     // n - s3 + n: r
+    return fp_sqrt(rhs, y);
+}
+// words below p?
+DR_DEV bool p256_below_p(const uint32_t (&w)[8]) {
+    uint32_t borrow = 0;
 #pragma unroll
-    for (int w = 0; w < 8; w++) {
-        uint32_t packed = 0;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const uint32_t v = ((k[w] >> (4 * j)) & 15u) + carry_in;
-            carry_in = v >= 8u ? 1u : 0u;
-            packed |= ((v + 8u) & 15u) << (4 * j);
-        }
-        dig[w] = packed;
-    }
-    const uint32_t top_carry = carry_in;
-    P256Point acc = p256_identity();
-#pragma unroll 1
-    for (int w = P256_WINDOWS - 1; w >= 0; w--) {
-#pragma unroll 1
-        for (int j = 0; j < 4; j++) acc = p256_dbl(acc);
-        const int dg = w == P256_WINDOWS - 1 ? (int)top_carry : (int)((dig[w >> 3] >> (4 * (w & 7))) & 15u) - 8;
-        const int mag = dg < 0 ? -dg : dg;
-        P256Point T = p256_lds_load(tab, mag == 0 ? 0 : mag - 1, lane);
-        T = p256_cneg(T, dg < 0);
-        if (mag == 0) T = p256_identity();
-        acc = p256_add(acc, T);
-    }
-    return acc;
+    for (int j = 0; j < 8; j++) (void)subb(w[j], Fp256Consts::PW[j], borrow);
+    return borrow != 0;
 }
 
-// out[i] = k[i] P[i].  pts: n x 16 words (x || y), ks: n x 8, out: n x 16.  One lane per multiplication.
+// wave_curve.hip.h's description of P-256: standard-form words at the ABI (64 zero bytes: the identity), Montgomery limbs inside, the
+// limb images of the (normal) coordinates in the LDS table (27 words a point: no packing), 65 windows (n has 256 bits)
+struct P256Curve {
+    using Fe = F256;
+    using Point = P256Point;
+    static constexpr int BLOCK = P256_BLOCK, WINDOWS = 65, LDS_WORDS = 9;
+    static constexpr bool EXTENDED = false, ZERO_IS_IDENTITY = true;
+    DR_DEV static F256 unpack(const uint32_t (&w)[8]) { return fp_unpack(w); }
+    DR_DEV static void pack(const F256& a, uint32_t (&w)[8]) { fp_pack(a, w); }
+    DR_DEV static F256 inv(const F256& a) { return fp_inv(a); }
+    DR_DEV static void to_lds(const F256& a, uint32_t (&w)[9]) { wave_limbs_to_words(a, w); }
+    DR_DEV static F256 from_lds(const uint32_t (&w)[9]) { return wave_words_to_limbs<F256>(w); }
+    DR_DEV static P256Point identity() { return p256_identity(); }
+    DR_DEV static P256Point from_affine(const F256& x, const F256& y) {
+        P256Point P;
+        P.x = x; P.y = y; P.z = fp_one();
+        return P;
+    }
+    DR_DEV static P256Point add(const P256Point& p, const P256Point& q) { return p256_add(p, q); }
+    DR_DEV static P256Point dbl(const P256Point& p) { return p256_dbl(p); }
+    DR_DEV static P256Point cneg(const P256Point& p, bool negate) { return p256_cneg(p, negate); }
+    DR_DEV static void load_scalar(const uint32_t* p, uint32_t (&k)[8]) { p256_load_scalar(p, k); }
+    DR_DEV static bool below_p(const uint32_t (&w)[8]) { return p256_below_p(w); }
+    DR_DEV static bool y_of_x(const F256& x, F256& y) { return p256_y_of_x(x, y); }
+    DR_DEV static bool is_odd(const F256& x) { return fp_is_odd(x); }
+};
+
+// out[i] = k[i] P[i]: wave_curve.hip.h's kernel bodies for this curve
 __global__ __launch_bounds__(P256_BLOCK) void k_p256_scalar_mul(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks,
                                                                 uint32_t* __restrict__ out, uint32_t n) {
-    __shared__ uint32_t tab[P256_TABLE * P256_PT_WORDS * P256_BLOCK];
-    const int lane = threadIdx.x;
-    uint32_t i = blockIdx.x * P256_BLOCK + lane;
-    const bool live = i < n;
-    if (!live) i = n - 1;            // keep the wave converged; the duplicate result is not stored
-    const P256Point P = p256_load_affine(pts + (size_t)i * 16);
-    uint32_t k[8];
-    p256_load_scalar(ks + (size_t)i * 8, k);
-    const P256Point acc = p256_scalar_mul_core(tab, lane, P, k);
-    if (live) p256_store_affine(out + (size_t)i * 16, acc);
+    wave_scalar_mul<P256Curve>(pts, ks, out, n);
 }
-
-// out[g] = sum_{j<m} k[g m + j] P[g m + j]: one lane per term (m padded to mpad, a power of two <= 64), folded with shuffles by the
-// complete addition (terms that coincide or cancel need nothing special) — k_ed_msm_groups for this curve
+// out[g] = sum_{j<m} k[g m + j] P[g m + j]
 __global__ __launch_bounds__(P256_BLOCK) void k_p256_msm_groups(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks,
                                                                 uint32_t* __restrict__ out, uint32_t groups, uint32_t m, uint32_t mpad) {
-    __shared__ uint32_t tab[P256_TABLE * P256_PT_WORDS * P256_BLOCK];
-    const int lane = threadIdx.x;
-    const uint32_t per_block = P256_BLOCK / mpad;
-    const uint32_t g = blockIdx.x * per_block + lane / mpad;
-    const uint32_t j = lane % mpad;
-    const bool live = g < groups && j < m;
-    const size_t idx = live ? (size_t)g * m + j : 0;          // dead lanes recompute term 0 and are masked out
-    const P256Point P = p256_load_affine(pts + idx * 16);
-    uint32_t k[8];
-    p256_load_scalar(ks + idx * 8, k);
-    const P256Point r = p256_scalar_mul_core(tab, lane, P, k);
-    P256Point acc = live ? r : p256_identity();
-#pragma unroll 1
-    for (uint32_t s = mpad >> 1; s > 0; s >>= 1) acc = p256_add(acc, p256_shfl_down(acc, s));
-    if (g < groups && j == 0) p256_store_affine(out + (size_t)g * 16, acc);
+    wave_msm_groups<P256Curve>(pts, ks, out, groups, m, mpad);
 }
 
 // Decoding (the reference's P256Point.string_to_point / _string_to_canonical_point and, for strings that start with 0x02 or 0x03,
@@ -250,55 +152,20 @@ __global__ __launch_bounds__(P256_BLOCK) void k_p256_msm_groups(const uint32_t* 
 // else, so a P256_TAI string is read as SEC1 or refused, never by the canonical rules.  No string encodes the identity, so the codec
 // alone and the checking decoder are this one mode.
 enum { P256_DEC_CODEC = 0, P256_DEC_CHECK = 1, P256_DEC_TAI = 2, P256_DEC_SEC1 = 3 };
-// y^2 = x^3 - 3 x + b for x in Montgomery form; ok and a root (either one) if it exists
-DR_DEV bool p256_y_of_x(const F256& x, F256& y) {
-    const F256 x3 = mul(sqr(x), x);
-    const F256 rhs = fp_reduce(add(sub(x3, add(x, dbl(x))), F256::constant<Fp256Consts::B>()));     // n - s3 + n: r
-    return fp_sqrt(rhs, y);
-}
-// words below p?
-DR_DEV bool p256_below_p(const uint32_t (&w)[8]) {
-    uint32_t borrow = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) (void)subb(w[j], Fp256Consts::PW[j], borrow);
-    return borrow != 0;
-}
 template <int MODE>
 __global__ __launch_bounds__(P256_BLOCK) void k_p256_decode_points(const uint32_t* __restrict__ enc /* n*9 */, uint32_t* __restrict__ out_xy /* n*16 */,
                                                                    uint32_t* __restrict__ ok, uint32_t n) {
-    const int lane = threadIdx.x;
-    uint32_t i = blockIdx.x * P256_BLOCK + lane;
+    if constexpr (MODE == P256_DEC_SEC1) {
+        sec1_decode<P256Curve>(enc, out_xy, ok, n);
+        return;
+    }
+    uint32_t i = blockIdx.x * P256_BLOCK + threadIdx.x;
     const bool live = i < n;
     if (!live) i = n - 1;
     uint32_t w[9];
 #pragma unroll
     for (int j = 0; j < 9; j++) w[j] = enc[(size_t)i * 9 + j];
     const uint32_t flag = w[8] & 0xffu, first = w[0] & 0xffu;
-    if constexpr (MODE == P256_DEC_SEC1) {
-        uint32_t xb[8];
-#pragma unroll
-        for (int q = 0; q < 8; q++) {
-            const int k = 7 - q;
-            xb[q] = __builtin_bswap32((w[k] >> 8) | (w[k + 1] << 24));
-        }
-        const F256 x = fp_unpack(xb);
-        F256 y;
-        const bool root = p256_y_of_x(x, y);
-        const bool valid = (first == 0x02u || first == 0x03u) && p256_below_p(xb) && root;
-        if (fp_is_odd(y) != ((first & 1u) != 0)) y = neg(y);     // (y = 0 cannot happen: the group order is odd)
-        if (live) {
-            if (valid) {
-                p256_store8(out_xy + (size_t)i * 16, xb);
-                p256_store_fe(out_xy + (size_t)i * 16 + 8, y);
-            } else {
-                const uint32_t z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                p256_store8(out_xy + (size_t)i * 16, z);
-                p256_store8(out_xy + (size_t)i * 16 + 8, z);
-            }
-            ok[i] = valid ? 1u : 0u;
-        }
-        return;
-    }
     uint32_t xs[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) xs[j] = w[j];
@@ -320,14 +187,10 @@ __global__ __launch_bounds__(P256_BLOCK) void k_p256_decode_points(const uint32_
     uint32_t yw[8];
     fp_pack(y, yw);
     bool want_larger = larger, by_parity = false;
-    // the SEC1 fallback: x = BE(bytes 1..32) — little-endian word q is bswap of the (unaligned) word at byte 29 - 4 q
+    // the SEC1 fallback: x = BE(bytes 1..32)
     if (!valid && (first == 0x02u || first == 0x03u)) {
         uint32_t xb[8];
-#pragma unroll
-        for (int q = 0; q < 8; q++) {
-            const int k = 7 - q;
-            xb[q] = __builtin_bswap32((w[k] >> 8) | (w[k + 1] << 24));
-        }
+        sec1_x_words(w, xb);
         x = fp_unpack(xb);
         valid = p256_below_p(xb) && p256_y_of_x(x, y);
         fp_pack(y, yw);
@@ -340,12 +203,11 @@ __global__ __launch_bounds__(P256_BLOCK) void k_p256_decode_points(const uint32_
     if constexpr (MODE != P256_DEC_CODEC) valid = valid && !is_identity;
     if (live) {
         if (valid && !is_identity) {
-            p256_store_fe(out_xy + (size_t)i * 16, x);
-            p256_store_fe(out_xy + (size_t)i * 16 + 8, y);
+            wave_store_fe<P256Curve>(out_xy + (size_t)i * 16, x);
+            wave_store_fe<P256Curve>(out_xy + (size_t)i * 16 + 8, y);
         } else {
-            const uint32_t z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            p256_store8(out_xy + (size_t)i * 16, z);
-            p256_store8(out_xy + (size_t)i * 16 + 8, z);
+            wave_store_zero8(out_xy + (size_t)i * 16);
+            wave_store_zero8(out_xy + (size_t)i * 16 + 8);
         }
         ok[i] = valid ? 1u : 0u;
     }
@@ -355,12 +217,8 @@ __global__ __launch_bounds__(P256_BLOCK) void k_p256_decode_points(const uint32_
 // sswu.hip.h's description of P-256: the simplified SWU map straight onto the curve (A = -3, B = b, Z = -10, no isogeny).  The field is
 // in Montgomery form, so A, Z, |Z| = 10 and sqrt(-Z) = sqrt(10) are compile-time limbs of v 2^261 mod p, B is Fp256Consts::B, and the
 // products by |Z| and B are full products by those constants (neither is small in this form).  sgn0 and equality are taken on the
-// canonical value (fp_pack), the output through p256_store_affine.
-struct P256Sswu {
-    using Fe = F256;
-    using Point = P256Point;
-    static constexpr uint32_t BLOCK = P256_BLOCK;
-    DR_DEV static void load8(const uint32_t* p, uint32_t (&w)[8]) { p256_load8(p, w); }
+// canonical value (fp_pack).  The field, the point, its addition and the ABI forms are P256Curve's.
+struct P256Sswu : P256Curve {
     static constexpr bool ISOGENY = false;
     static constexpr uint32_t A[9] = {0x1fffff9fu, 0x1fffffffu, 0x1fffffffu, 0x0000c1ffu, 0x00000000u, 0x00000000u, 0x01840000u, 0x13e00000u, 0x00ffffffu};
     static constexpr uint32_t Z[9] = {0x1ffffebfu, 0x1fffffffu, 0x1fffffffu, 0x000281ffu, 0x00000000u, 0x00000000u, 0x05040000u, 0x17e00000u, 0x00fffffeu};
@@ -375,12 +233,7 @@ struct P256Sswu {
     DR_DEV static F256 norm(const F256& x) { return fp_reduce(x); }
     DR_DEV static bool is_zero(const F256& x) { return fp_is_zero(x); }
     DR_DEV static bool equal(const F256& x, const F256& y) { return fp_equal(x, y); }
-    DR_DEV static bool is_odd(const F256& x) { return fp_is_odd(x); }
     DR_DEV static F256 pow_p34(const F256& x) { return fp_pow_p34(x); }
-    DR_DEV static P256Point identity() { return p256_identity(); }
-    DR_DEV static P256Point add(const P256Point& p, const P256Point& q) { return p256_add(p, q); }
-    DR_DEV static F256 unpack(const uint32_t (&w)[8]) { return fp_unpack(w); }
-    DR_DEV static void store_affine(uint32_t* out, const P256Point& p) { p256_store_affine(out, p); }
 };
 // out[i] = the sum of the images of item i's `per_item` (1: NU, 2: RO) field elements, as k_secp256k1_map_to_curve: us n x per_item x 8
 // words (canonical, checked by the host), out n x 16 words affine x || y (64 zero bytes if the two images cancel), ok[i] = 1 always
@@ -405,22 +258,22 @@ __global__ __launch_bounds__(64) void k_p256_field_selftest(const int32_t* __res
 #pragma unroll
     for (int t = 0; t < FP_L; t++) { a.l[t] = a_limbs[(size_t)i * FP_L + t]; b.l[t] = b_limbs[(size_t)i * FP_L + t]; }
     uint32_t* o = out + (size_t)i * P256_SELFTEST_RECORDS * 8;
-    p256_store_fe(o + 0, mul(a, b));
-    p256_store_fe(o + 8, sqr(a));
-    p256_store_fe(o + 16, add(a, b));
-    p256_store_fe(o + 24, sub(a, b));
-    p256_store_fe(o + 32, neg(a));
-    p256_store_fe(o + 40, carry(a));
-    p256_store_fe(o + 48, mul2(a, b, b, a));
-    p256_store_fe(o + 56, fp_inv(a));
+    wave_store_fe<P256Curve>(o + 0, mul(a, b));
+    wave_store_fe<P256Curve>(o + 8, sqr(a));
+    wave_store_fe<P256Curve>(o + 16, add(a, b));
+    wave_store_fe<P256Curve>(o + 24, sub(a, b));
+    wave_store_fe<P256Curve>(o + 32, neg(a));
+    wave_store_fe<P256Curve>(o + 40, carry(a));
+    wave_store_fe<P256Curve>(o + 48, mul2(a, b, b, a));
+    wave_store_fe<P256Curve>(o + 56, fp_inv(a));
     F256 r;
     const bool sq = fp_sqrt(a, r);
-    p256_store_fe(o + 64, r);
+    wave_store_fe<P256Curve>(o + 64, r);
     uint32_t w[8];
     fp_pack(a, w);
-    p256_store8(o + 72, w);
-    p256_store_fe(o + 80, fp_reduce(a));
-    p256_store_fe(o + 88, sqr(fp_reduce(a)));
+    wave_store8(o + 72, w);
+    wave_store_fe<P256Curve>(o + 80, fp_reduce(a));
+    wave_store_fe<P256Curve>(o + 88, sqr(fp_reduce(a)));
     flags[i] = (sq ? 1u : 0u) | (fp_is_larger(w) ? 2u : 0u) | ((w[0] & 1u) ? 4u : 0u);
 }
 

@@ -11,13 +11,11 @@
 #pragma once
 #include "fsecp256k1.hip.h"
 #include "sswu.hip.h"
+#include "wave_curve.hip.h"
 
 namespace dr {
 
 constexpr int K1_BLOCK = 64;          // one wave per workgroup, as k_p256_scalar_mul
-constexpr int K1_TABLE = 8;           // entries 1P..8P
-constexpr int K1_PT_WORDS = 27;       // X, Y, Z x 9 limbs (the table holds limb images: no packing)
-constexpr int K1_WINDOWS = 65;        // 64 signed 4-bit digits of k < n < 2^256 and the carry out of the top one
 constexpr uint32_t K1_B3 = 21;
 
 struct K1Point {
@@ -67,161 +65,61 @@ DR_DEV K1Point k1_cneg(const K1Point& p, bool negate) {
     return r;
 }
 
-// ---------------------------------------------------------------- memory
-DR_DEV void k1_load8(const uint32_t* p, uint32_t (&w)[8]) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    const uint4 a = q[0], b = q[1];
-    w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
-    w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
-}
-DR_DEV void k1_store8(uint32_t* p, const uint32_t (&w)[8]) {
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(w[0], w[1], w[2], w[3]);
-    q[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
-// affine x || y (16 words, canonical) -> projective; 64 zero bytes -> the identity
-DR_DEV K1Point k1_load_affine(const uint32_t* p) {
-    uint32_t x[8], y[8];
-    k1_load8(p, x);
-    k1_load8(p + 8, y);
-    uint32_t o = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) o |= x[j] | y[j];
-    K1Point r;
-    r.x = fk_unpack(x);
-    r.y = fk_unpack(y);
-    r.z = FK::small(1);
-    if (o == 0) r = k1_identity();
-    return r;
-}
-DR_DEV void k1_store_fe(uint32_t* p, const FK& a) {
-    uint32_t w[8];
-    fk_pack(a, w);
-    k1_store8(p, w);
-}
-// x || y of the point; the identity (Z = 0, so x = y = 0 after the multiplication by 0^-1 = 0) stores 64 zero bytes
-DR_DEV void k1_store_affine(uint32_t* out, const K1Point& acc) {
-    const FK zi = fk_inv(acc.z);
-    k1_store_fe(out, mul(acc.x, zi));
-    k1_store_fe(out + 8, mul(acc.y, zi));
-}
-// LDS table [entry][limb][lane] (bank = lane whatever the entry), limb images of the (normal) coordinates
-DR_DEV void k1_lds_store(uint32_t* tab, int entry, int lane, const K1Point& p) {
-    uint32_t* base = tab + (size_t)entry * K1_PT_WORDS * K1_BLOCK + lane;
-#pragma unroll
-    for (int i = 0; i < FK_L; i++) {
-        base[(0 + i) * K1_BLOCK] = (uint32_t)p.x.l[i];
-        base[(9 + i) * K1_BLOCK] = (uint32_t)p.y.l[i];
-        base[(18 + i) * K1_BLOCK] = (uint32_t)p.z.l[i];
-    }
-}
-DR_DEV K1Point k1_lds_load(const uint32_t* tab, int entry, int lane) {
-    const uint32_t* base = tab + (size_t)entry * K1_PT_WORDS * K1_BLOCK + lane;
-    K1Point p;
-#pragma unroll
-    for (int i = 0; i < FK_L; i++) {
-        p.x.l[i] = (int32_t)base[(0 + i) * K1_BLOCK];
-        p.y.l[i] = (int32_t)base[(9 + i) * K1_BLOCK];
-        p.z.l[i] = (int32_t)base[(18 + i) * K1_BLOCK];
-    }
-    return p;
-}
-DR_DEV K1Point k1_shfl_down(const K1Point& p, unsigned delta) {
-    K1Point o;
-#pragma unroll
-    for (int t = 0; t < FK_L; t++) {
-        o.x.l[t] = __shfl_down(p.x.l[t], delta, 64);
-        o.y.l[t] = __shfl_down(p.y.l[t], delta, 64);
-        o.z.l[t] = __shfl_down(p.z.l[t], delta, 64);
-    }
-    return o;
-}
-
 // k mod n for a 256-bit k: 2 n > 2^256, so one conditional subtraction (in every lane)
 DR_DEV void k1_load_scalar(const uint32_t* p, uint32_t (&k)[8]) {
-    k1_load8(p, k);
+    wave_load8(p, k);
     uint32_t d[8], borrow = 0;
 #pragma unroll
     for (int i = 0; i < 8; i++) d[i] = subb(k[i], FsecpConsts::NW[i], borrow);
 #pragma unroll
     for (int i = 0; i < 8; i++) k[i] = borrow ? k[i] : d[i];
 }
-
-// k P for k < n on the fixed schedule of p256_scalar_mul_core: table 1P..8P in LDS, 65 signed 4-bit windows, four doublings and one
-// table addition each whatever the digits (the table index, always in range, is the only thing a digit decides) — the secret
-// scalars of the provers go through here
-DR_DEV K1Point k1_scalar_mul_core(uint32_t* tab, int lane, const K1Point& P, const uint32_t (&k)[8]) {
-    k1_lds_store(tab, 0, lane, P);
-    K1Point Q = k1_dbl(P);
-    k1_lds_store(tab, 1, lane, Q);
-#pragma unroll 1
-    for (int e = 2; e < K1_TABLE; e++) {
-        Q = k1_add(Q, P);
-        k1_lds_store(tab, e, lane, Q);
-    }
-    uint32_t dig[8];                 // digits 0..63 in [-8, 7], stored as d + 8; digit 64 = top_carry
-    uint32_t carry_in = 0;
+// words below p?
+DR_DEV bool k1_below_p(const uint32_t (&w)[8]) {
+    uint32_t borrow = 0;
 #pragma unroll
-    for (int w = 0; w < 8; w++) {
-        uint32_t packed = 0;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const uint32_t v = ((k[w] >> (4 * j)) & 15u) + carry_in;
-            carry_in = v >= 8u ? 1u : 0u;
-            packed |= ((v + 8u) & 15u) << (4 * j);
-        }
-        dig[w] = packed;
-    }
-    const uint32_t top_carry = carry_in;
-    K1Point acc = k1_identity();
-#pragma unroll 1
-    for (int w = K1_WINDOWS - 1; w >= 0; w--) {
-#pragma unroll 1
-        for (int j = 0; j < 4; j++) acc = k1_dbl(acc);
-        const int dg = w == K1_WINDOWS - 1 ? (int)top_carry : (int)((dig[w >> 3] >> (4 * (w & 7))) & 15u) - 8;
-        const int mag = dg < 0 ? -dg : dg;
-        K1Point T = k1_lds_load(tab, mag == 0 ? 0 : mag - 1, lane);
-        T = k1_cneg(T, dg < 0);
-        if (mag == 0) T = k1_identity();
-        acc = k1_add(acc, T);
-    }
-    return acc;
+    for (int j = 0; j < 8; j++) (void)subb(w[j], FsecpConsts::PW[j], borrow);
+    return borrow != 0;
 }
+// y^2 = x^3 + 7: ok and a root (either one) if it exists (y = 0 cannot happen: -7 is not a cube mod p)
+DR_DEV bool k1_y_of_x(const FK& x, FK& y) { return fk_sqrt(carry(add(mul(sqr(x), x), FK::small(7))), y); }
 
-// out[i] = k[i] P[i].  pts: n x 16 words (x || y), ks: n x 8, out: n x 16.  One lane per multiplication.
+// wave_curve.hip.h's description of secp256k1: canonical words at the ABI (64 zero bytes: the identity), the limb images of the
+// (normal) coordinates in the LDS table (27 words a point: no packing), 65 windows (n has 256 bits)
+struct Secp256k1Curve {
+    using Fe = FK;
+    using Point = K1Point;
+    static constexpr int BLOCK = K1_BLOCK, WINDOWS = 65, LDS_WORDS = 9;
+    static constexpr bool EXTENDED = false, ZERO_IS_IDENTITY = true;
+    DR_DEV static FK unpack(const uint32_t (&w)[8]) { return fk_unpack(w); }
+    DR_DEV static void pack(const FK& a, uint32_t (&w)[8]) { fk_pack(a, w); }
+    DR_DEV static FK inv(const FK& a) { return fk_inv(a); }
+    DR_DEV static void to_lds(const FK& a, uint32_t (&w)[9]) { wave_limbs_to_words(a, w); }
+    DR_DEV static FK from_lds(const uint32_t (&w)[9]) { return wave_words_to_limbs<FK>(w); }
+    DR_DEV static K1Point identity() { return k1_identity(); }
+    DR_DEV static K1Point from_affine(const FK& x, const FK& y) {
+        K1Point P;
+        P.x = x; P.y = y; P.z = FK::small(1);
+        return P;
+    }
+    DR_DEV static K1Point add(const K1Point& p, const K1Point& q) { return k1_add(p, q); }
+    DR_DEV static K1Point dbl(const K1Point& p) { return k1_dbl(p); }
+    DR_DEV static K1Point cneg(const K1Point& p, bool negate) { return k1_cneg(p, negate); }
+    DR_DEV static void load_scalar(const uint32_t* p, uint32_t (&k)[8]) { k1_load_scalar(p, k); }
+    DR_DEV static bool below_p(const uint32_t (&w)[8]) { return k1_below_p(w); }
+    DR_DEV static bool y_of_x(const FK& x, FK& y) { return k1_y_of_x(x, y); }
+    DR_DEV static bool is_odd(const FK& x) { return fk_is_odd(x); }
+};
+
+// out[i] = k[i] P[i]: wave_curve.hip.h's kernel bodies for this curve
 __global__ __launch_bounds__(K1_BLOCK) void k_secp256k1_scalar_mul(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks,
                                                                    uint32_t* __restrict__ out, uint32_t n) {
-    __shared__ uint32_t tab[K1_TABLE * K1_PT_WORDS * K1_BLOCK];
-    const int lane = threadIdx.x;
-    uint32_t i = blockIdx.x * K1_BLOCK + lane;
-    const bool live = i < n;
-    if (!live) i = n - 1;            // keep the wave converged; the duplicate result is not stored
-    const K1Point P = k1_load_affine(pts + (size_t)i * 16);
-    uint32_t k[8];
-    k1_load_scalar(ks + (size_t)i * 8, k);
-    const K1Point acc = k1_scalar_mul_core(tab, lane, P, k);
-    if (live) k1_store_affine(out + (size_t)i * 16, acc);
+    wave_scalar_mul<Secp256k1Curve>(pts, ks, out, n);
 }
-
-// out[g] = sum_{j<m} k[g m + j] P[g m + j]: one lane per term (m padded to mpad, a power of two <= 64), folded with shuffles by the
-// complete addition — k_p256_msm_groups for this curve
+// out[g] = sum_{j<m} k[g m + j] P[g m + j]
 __global__ __launch_bounds__(K1_BLOCK) void k_secp256k1_msm_groups(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks,
                                                                    uint32_t* __restrict__ out, uint32_t groups, uint32_t m, uint32_t mpad) {
-    __shared__ uint32_t tab[K1_TABLE * K1_PT_WORDS * K1_BLOCK];
-    const int lane = threadIdx.x;
-    const uint32_t per_block = K1_BLOCK / mpad;
-    const uint32_t g = blockIdx.x * per_block + lane / mpad;
-    const uint32_t j = lane % mpad;
-    const bool live = g < groups && j < m;
-    const size_t idx = live ? (size_t)g * m + j : 0;          // dead lanes recompute term 0 and are masked out
-    const K1Point P = k1_load_affine(pts + idx * 16);
-    uint32_t k[8];
-    k1_load_scalar(ks + idx * 8, k);
-    const K1Point r = k1_scalar_mul_core(tab, lane, P, k);
-    K1Point acc = live ? r : k1_identity();
-#pragma unroll 1
-    for (uint32_t s = mpad >> 1; s > 0; s >>= 1) acc = k1_add(acc, k1_shfl_down(acc, s));
-    if (g < groups && j == 0) k1_store_affine(out + (size_t)g * 16, acc);
+    wave_msm_groups<Secp256k1Curve>(pts, ks, out, groups, m, mpad);
 }
 
 // Decoding (the reference's SWAffinePoint.string_to_point for a compressed string), one lane per 33-byte SEC1 encoding padded to 9
@@ -233,41 +131,7 @@ enum { K1_DEC_CODEC = 0, K1_DEC_CHECK = 1 };
 template <int MODE>
 __global__ __launch_bounds__(K1_BLOCK) void k_secp256k1_decode_points(const uint32_t* __restrict__ enc /* n*9 */, uint32_t* __restrict__ out_xy /* n*16 */,
                                                                       uint32_t* __restrict__ ok, uint32_t n) {
-    const int lane = threadIdx.x;
-    uint32_t i = blockIdx.x * K1_BLOCK + lane;
-    const bool live = i < n;
-    if (!live) i = n - 1;
-    uint32_t w[9];
-#pragma unroll
-    for (int j = 0; j < 9; j++) w[j] = enc[(size_t)i * 9 + j];
-    const uint32_t first = w[0] & 0xffu;
-    uint32_t xb[8];                  // little-endian word q is the byte swap of the (unaligned) word at byte 29 - 4 q
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-        const int k = 7 - q;
-        xb[q] = __builtin_bswap32((w[k] >> 8) | (w[k + 1] << 24));
-    }
-    uint32_t borrow = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) (void)subb(xb[j], FsecpConsts::PW[j], borrow);
-    const FK x = fk_unpack(xb);
-    FK y;
-    const bool root = fk_sqrt(carry(add(mul(sqr(x), x), FK::small(7))), y);
-    const bool valid = (first == 0x02u || first == 0x03u) && borrow != 0 && root;
-    uint32_t yw[8];
-    fk_pack(y, yw);
-    if ((yw[0] & 1u) != (first & 1u)) y = neg(y);          // (y = 0 cannot happen: -7 is not a cube mod p, the group order is odd)
-    if (live) {
-        if (valid) {
-            k1_store8(out_xy + (size_t)i * 16, xb);
-            k1_store_fe(out_xy + (size_t)i * 16 + 8, y);
-        } else {
-            const uint32_t z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            k1_store8(out_xy + (size_t)i * 16, z);
-            k1_store8(out_xy + (size_t)i * 16 + 8, z);
-        }
-        ok[i] = valid ? 1u : 0u;
-    }
+    sec1_decode<Secp256k1Curve>(enc, out_xy, ok, n);
 }
 
 // ---------------------------------------------------------------- hashing to the curve: simplified SWU and an isogeny (RFC 9380)
@@ -275,11 +139,7 @@ __global__ __launch_bounds__(K1_BLOCK) void k_secp256k1_decode_points(const uint
 // B and |Z| small (Z negative), sqrt(-Z), and the isogeny E' -> E as four coefficient lists, highest degree first (the leading 1 of
 // the denominators is implied), all as compile-time limbs — nothing is indexed at run time, so nothing goes to scratch.  P-256, whose
 // SSWU needs no isogeny, has its description (ISOGENY = false) in kernels_p256.hip.h.
-struct Secp256k1Sswu {
-    using Fe = FK;
-    using Point = K1Point;
-    static constexpr uint32_t BLOCK = K1_BLOCK;
-    DR_DEV static void load8(const uint32_t* p, uint32_t (&w)[8]) { k1_load8(p, w); }
+struct Secp256k1Sswu : Secp256k1Curve {
     static constexpr bool ISOGENY = true;
     static constexpr uint32_t B = 1771, NEG_Z = 11;
     static constexpr uint32_t A[9] = {0x1a444533u, 0x02a23e00u, 0x1bc39750u, 0x07a6c796u, 0x1d272e95u, 0x0aac787au, 0x0b728229u, 0x157bacc3u, 0x003f8731u};
@@ -298,7 +158,7 @@ struct Secp256k1Sswu {
     static constexpr uint32_t YD2[9] = {0x1fd2a76fu, 0x1dfc0c95u, 0x0358a669u, 0x1a422c5eu, 0x0337e0a3u, 0x061fd47fu, 0x08b3ce9cu, 0x0e2ca8b9u, 0x006484aau};
     static constexpr uint32_t YD1[9] = {0x085c2573u, 0x1da12e93u, 0x1a365e37u, 0x0f837f91u, 0x0c298946u, 0x13319391u, 0x127f57a7u, 0x097717b6u, 0x007a0653u};
     static constexpr uint32_t YD0[9] = {0x1ffff93bu, 0x1ffffff7u, 0x1fffffffu, 0x1fffffffu, 0x1fffffffu, 0x1fffffffu, 0x1fffffffu, 0x1fffffffu, 0x00ffffffu};
-    // the field's forms of what sswu.hip.h asks for: B and |Z| are small here, so their products are mul_small
+    // the field's forms of what sswu.hip.h asks for beyond Secp256k1Curve: B and |Z| are small here, so their products are mul_small
     DR_DEV static FK a() { return FK::constant<A>(); }
     DR_DEV static FK z() { return FK::small(-(int32_t)NEG_Z); }
     DR_DEV static FK sqrt_neg_z() { return FK::constant<SQRT_NEG_Z>(); }
@@ -308,12 +168,7 @@ struct Secp256k1Sswu {
     DR_DEV static FK norm(const FK& x) { return carry(x); }
     DR_DEV static bool is_zero(const FK& x) { return fk_is_zero(x); }
     DR_DEV static bool equal(const FK& x, const FK& y) { return fk_equal(x, y); }
-    DR_DEV static bool is_odd(const FK& x) { return fk_is_odd(x); }
     DR_DEV static FK pow_p34(const FK& x) { return fk_pow_p34(x); }
-    DR_DEV static K1Point identity() { return k1_identity(); }
-    DR_DEV static K1Point add(const K1Point& p, const K1Point& q) { return k1_add(p, q); }
-    DR_DEV static FK unpack(const uint32_t (&w)[8]) { return fk_unpack(w); }
-    DR_DEV static void store_affine(uint32_t* out, const K1Point& p) { k1_store_affine(out, p); }
 };
 
 // out[i] = the sum of the images of item i's `per_item` field elements: sswu.hip.h's map, isogeny and loop for this curve
@@ -335,22 +190,22 @@ __global__ __launch_bounds__(64) void k_secp256k1_field_selftest(const int32_t* 
 #pragma unroll
     for (int t = 0; t < FK_L; t++) { a.l[t] = a_limbs[(size_t)i * FK_L + t]; b.l[t] = b_limbs[(size_t)i * FK_L + t]; }
     uint32_t* o = out + (size_t)i * K1_SELFTEST_RECORDS * 8;
-    k1_store_fe(o + 0, mul(a, b));
-    k1_store_fe(o + 8, sqr(a));
-    k1_store_fe(o + 16, add(a, b));
-    k1_store_fe(o + 24, sub(a, b));
-    k1_store_fe(o + 32, neg(a));
-    k1_store_fe(o + 40, carry(a));
-    k1_store_fe(o + 48, mul2(a, b, b, a));
-    k1_store_fe(o + 56, fk_inv(carry(a)));
+    wave_store_fe<Secp256k1Curve>(o + 0, mul(a, b));
+    wave_store_fe<Secp256k1Curve>(o + 8, sqr(a));
+    wave_store_fe<Secp256k1Curve>(o + 16, add(a, b));
+    wave_store_fe<Secp256k1Curve>(o + 24, sub(a, b));
+    wave_store_fe<Secp256k1Curve>(o + 32, neg(a));
+    wave_store_fe<Secp256k1Curve>(o + 40, carry(a));
+    wave_store_fe<Secp256k1Curve>(o + 48, mul2(a, b, b, a));
+    wave_store_fe<Secp256k1Curve>(o + 56, fk_inv(carry(a)));
     FK r;
     const bool sq = fk_sqrt(carry(a), r);
-    k1_store_fe(o + 64, r);
+    wave_store_fe<Secp256k1Curve>(o + 64, r);
     uint32_t w[8];
     fk_pack(a, w);
-    k1_store8(o + 72, w);
-    k1_store_fe(o + 80, mul_small(a, K1_B3));
-    k1_store_fe(o + 88, sqr(carry(a)));
+    wave_store8(o + 72, w);
+    wave_store_fe<Secp256k1Curve>(o + 80, mul_small(a, K1_B3));
+    wave_store_fe<Secp256k1Curve>(o + 88, sqr(carry(a)));
     flags[i] = (sq ? 1u : 0u) | ((w[0] & 1u) ? 2u : 0u);
 }
 

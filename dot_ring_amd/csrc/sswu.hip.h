@@ -10,10 +10,11 @@
 //   norm(x)                        a sum, difference or negation of normals back to what mul / sqr accept on both sides
 //   is_zero, equal, is_odd         on the canonical value (is_odd is sgn0)
 //   pow_p34(x)                     x^((p - 3) / 4), p = 3 mod 4
-//   BLOCK, load8(p, w)             the workgroup size of the curve's kernels and its 32-byte load
-//   identity(), add(P, Q), unpack(w), store_affine(out, P)      the group's neutral element, complete addition, and the ABI's forms
+//   BLOCK, identity(), add(P, Q), unpack(w), pack(a, w), inv(a)    as wave_curve.hip.h asks them of its description: a curve's SSWU
+//                                  description derives from that one
 #pragma once
 #include "field.hip.h"
+#include "wave_curve.hip.h"
 
 namespace dr {
 
@@ -95,7 +96,7 @@ DR_DEV void sswu_map_to_curve(const uint32_t* __restrict__ us, uint32_t* __restr
 #pragma unroll 1
     for (uint32_t e = 0; e < per_item; e++) {
         uint32_t w[8];
-        C::load8(us + ((size_t)i * per_item + e) * 8, w);
+        wave_load8(us + ((size_t)i * per_item + e) * 8, w);
         Fe xn, xd, y;
         sswu_map<C>(C::unpack(w), (w[0] & 1u) != 0, xn, xd, y);
         bool ok_e;
@@ -104,7 +105,7 @@ DR_DEV void sswu_map_to_curve(const uint32_t* __restrict__ us, uint32_t* __restr
         acc = C::add(acc, pt);
     }
     if (live) {
-        C::store_affine(out_xy + (size_t)i * 16, acc);
+        wave_store_affine<C>(out_xy + (size_t)i * 16, acc);
         ok[i] = good ? 1u : 0u;
     }
 }

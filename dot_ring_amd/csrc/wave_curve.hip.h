@@ -1,0 +1,273 @@
+// The wave-per-workgroup scalar-multiplication family of the four native curves (Ed25519, Baby JubJub, P-256, secp256k1) as one set of
+// templates over a description C of the curve: the memory forms, the fixed-schedule scalar multiplication the provers' secret scalars go
+// through, the two kernel bodies built on it, and the SEC1-compressed decoder.  kernels_ed25519.hip.h (Ed25519Curve), kernels_bjj.hip.h
+// (BjjCurve), kernels_p256.hip.h (P256Curve) and kernels_secp256k1.hip.h (Secp256k1Curve) each give a field, a group law, one
+// description and one thin named __global__ per kernel; the schedule below exists once.  C provides
+//   Fe, Point                      the field element (int32_t limbs l[]) and the point: members x, y, z and, when EXTENDED, t
+//   BLOCK, WINDOWS                 the workgroup size (64: one wave) and the number of signed 4-bit windows of a reduced scalar: 64 when
+//                                  the order is below 2^255 (no carry leaves the top digit), 65 otherwise
+//   EXTENDED, LDS_WORDS            whether the point has a fourth coordinate t; the words of one coordinate in the LDS table
+//   ZERO_IS_IDENTITY               whether 64 zero bytes stand for the identity at the ABI (the Weierstrass curves: (0, 0) is no point)
+//   unpack(w), pack(a, w), inv(a)  the ABI's canonical 8 words <-> an element (in the field's own form); a^-1 with 0^-1 = 0
+//   to_lds(a, w), from_lds(w)      a normal coordinate <-> its LDS_WORDS table words (canonical or Montgomery words, or the limb image)
+//   identity(), from_affine(x, y)  the neutral element; the point of affine coordinates
+//   add(P, Q), dbl(P)              the unified / complete addition and the doubling (all coordinates)
+//   dbl_no_t(P)                    when EXTENDED: the doubling without t (three of a window's four doublings are only doubled again)
+//   cneg(P, b)                     -P if b
+//   load_scalar(p, k)              8 words at p reduced mod the group order
+// and, for sec1_decode:  below_p(w), y_of_x(x, y) (a root of the curve equation, false if none), is_odd(y) (of the canonical value).
+#pragma once
+#include "field.hip.h"
+
+namespace dr {
+
+constexpr int WAVE_TABLE = 8;         // entries 1P..8P: what a signed 4-bit digit can select
+
+DR_DEV void wave_load8(const uint32_t* p, uint32_t (&w)[8]) {
+    const uint4* q = reinterpret_cast<const uint4*>(p);
+    const uint4 a = q[0], b = q[1];
+    w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
+    w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
+}
+DR_DEV void wave_store8(uint32_t* p, const uint32_t (&w)[8]) {
+    uint4* q = reinterpret_cast<uint4*>(p);
+    q[0] = make_uint4(w[0], w[1], w[2], w[3]);
+    q[1] = make_uint4(w[4], w[5], w[6], w[7]);
+}
+DR_DEV void wave_store_zero8(uint32_t* p) {
+    const uint32_t z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    wave_store8(p, z);
+}
+
+// ---------------------------------------------------------------- memory
+template <class C>
+DR_DEV typename C::Fe wave_load_fe(const uint32_t* p) {
+    uint32_t w[8];
+    wave_load8(p, w);
+    return C::unpack(w);
+}
+template <class C>
+DR_DEV void wave_store_fe(uint32_t* p, const typename C::Fe& a) {
+    uint32_t w[8];
+    C::pack(a, w);
+    wave_store8(p, w);
+}
+// x || y of the point; where the identity has Z = 0, x = y = 0 after the multiplication by 0^-1 = 0: it stores 64 zero bytes
+template <class C>
+DR_DEV void wave_store_affine(uint32_t* out, const typename C::Point& acc) {
+    const typename C::Fe zi = C::inv(acc.z);
+    wave_store_fe<C>(out, mul(acc.x, zi));
+    wave_store_fe<C>(out + 8, mul(acc.y, zi));
+}
+// One term of a batch: the point of affine x || y (16 words, canonical) at pt and the scalar at kp, reduced into k.  The scalar is
+// reduced before the point is built from its coordinates (an extended point costs a product that nothing needs across that loop).
+template <class C>
+DR_DEV typename C::Point wave_load_term(const uint32_t* pt, const uint32_t* kp, uint32_t (&k)[8]) {
+    uint32_t x[8], y[8];
+    wave_load8(pt, x);
+    wave_load8(pt + 8, y);
+    [[maybe_unused]] uint32_t o = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) o |= x[j] | y[j];
+    const typename C::Fe px = C::unpack(x), py = C::unpack(y);
+    C::load_scalar(kp, k);
+    typename C::Point r = C::from_affine(px, py);
+    if constexpr (C::ZERO_IS_IDENTITY) {
+        if (o == 0) r = C::identity();
+    }
+    return r;
+}
+// the limb image of a coordinate as table words: what to_lds / from_lds are where the table keeps limbs (no packing)
+template <class Fe, int N>
+DR_DEV void wave_limbs_to_words(const Fe& a, uint32_t (&w)[N]) {
+    static_assert(N == sizeof(a.l) / sizeof(a.l[0]), "LDS_WORDS of a limb-image table is the field's limb count");
+#pragma unroll
+    for (int i = 0; i < N; i++) w[i] = (uint32_t)a.l[i];
+}
+template <class Fe, int N>
+DR_DEV Fe wave_words_to_limbs(const uint32_t (&w)[N]) {
+    Fe a;
+    static_assert(N == sizeof(a.l) / sizeof(a.l[0]), "LDS_WORDS of a limb-image table is the field's limb count");
+#pragma unroll
+    for (int i = 0; i < N; i++) a.l[i] = (int32_t)w[i];
+    return a;
+}
+// LDS table [entry][word][lane] (bank = lane whatever the entry)
+template <class C>
+constexpr int wave_table_words() { return WAVE_TABLE * (C::EXTENDED ? 4 : 3) * C::LDS_WORDS * C::BLOCK; }
+template <class C>
+DR_DEV void wave_lds_store(uint32_t* tab, int entry, int lane, const typename C::Point& p) {
+    constexpr int W = C::LDS_WORDS, B = C::BLOCK;
+    uint32_t* base = tab + (size_t)entry * (wave_table_words<C>() / WAVE_TABLE) + lane;
+    [[maybe_unused]] uint32_t x[W], y[W], z[W], t[W];
+    C::to_lds(p.x, x); C::to_lds(p.y, y); C::to_lds(p.z, z);
+    if constexpr (C::EXTENDED) C::to_lds(p.t, t);
+#pragma unroll
+    for (int i = 0; i < W; i++) {
+        base[(0 + i) * B] = x[i];
+        base[(W + i) * B] = y[i];
+        base[(2 * W + i) * B] = z[i];
+        if constexpr (C::EXTENDED) base[(3 * W + i) * B] = t[i];
+    }
+}
+template <class C>
+DR_DEV typename C::Point wave_lds_load(const uint32_t* tab, int entry, int lane) {
+    constexpr int W = C::LDS_WORDS, B = C::BLOCK;
+    const uint32_t* base = tab + (size_t)entry * (wave_table_words<C>() / WAVE_TABLE) + lane;
+    [[maybe_unused]] uint32_t x[W], y[W], z[W], t[W];
+#pragma unroll
+    for (int i = 0; i < W; i++) {
+        x[i] = base[(0 + i) * B];
+        y[i] = base[(W + i) * B];
+        z[i] = base[(2 * W + i) * B];
+        if constexpr (C::EXTENDED) t[i] = base[(3 * W + i) * B];
+    }
+    typename C::Point p;
+    p.x = C::from_lds(x); p.y = C::from_lds(y); p.z = C::from_lds(z);
+    if constexpr (C::EXTENDED) p.t = C::from_lds(t);
+    return p;
+}
+template <class C>
+DR_DEV typename C::Point wave_shfl_down(const typename C::Point& p, unsigned delta) {
+    typename C::Point o;
+#pragma unroll
+    for (int t = 0; t < (int)(sizeof(p.x.l) / sizeof(p.x.l[0])); t++) {
+        o.x.l[t] = __shfl_down(p.x.l[t], delta, 64);
+        o.y.l[t] = __shfl_down(p.y.l[t], delta, 64);
+        o.z.l[t] = __shfl_down(p.z.l[t], delta, 64);
+        if constexpr (C::EXTENDED) o.t.l[t] = __shfl_down(p.t.l[t], delta, 64);
+    }
+    return o;
+}
+
+// ---------------------------------------------------------------- scalar multiplication
+// k P for k below the group order on a fixed schedule: table 1P..8P in LDS, 64 signed 4-bit windows (and, where the order has 256 bits,
+// the carry out of the 64th digit as a 65th), four doublings and one table addition each whatever the digits (the table index, always in
+// range, is the only thing a digit decides: no branch and no loop bound depends on one) — the secret scalars of the provers go through
+// here
+template <class C>
+DR_DEV typename C::Point wave_scalar_mul_core(uint32_t* tab, int lane, const typename C::Point& P, const uint32_t (&k)[8]) {
+    using Point = typename C::Point;
+    wave_lds_store<C>(tab, 0, lane, P);
+    Point Q = C::dbl(P);
+    wave_lds_store<C>(tab, 1, lane, Q);
+#pragma unroll 1
+    for (int e = 2; e < WAVE_TABLE; e++) {
+        Q = C::add(Q, P);
+        wave_lds_store<C>(tab, e, lane, Q);
+    }
+    uint32_t dig[8];                 // digits 0..63 in [-8, 7], stored as d + 8; digit 64 = top_carry
+    uint32_t carry_in = 0;
+#pragma unroll
+    for (int w = 0; w < 8; w++) {
+        uint32_t packed = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const uint32_t v = ((k[w] >> (4 * j)) & 15u) + carry_in;
+            carry_in = v >= 8u ? 1u : 0u;
+            packed |= ((v + 8u) & 15u) << (4 * j);
+        }
+        dig[w] = packed;
+    }
+    [[maybe_unused]] const uint32_t top_carry = carry_in;      // (0 when the order is below 2^255: the top nibble is then at most 1)
+    Point acc = C::identity();
+#pragma unroll 1
+    for (int w = C::WINDOWS - 1; w >= 0; w--) {
+        if constexpr (C::EXTENDED) {             // three doublings whose T nothing reads, then one with T
+#pragma unroll 1
+            for (int j = 0; j < 3; j++) acc = C::dbl_no_t(acc);
+            acc = C::dbl(acc);
+        } else {
+#pragma unroll 1
+            for (int j = 0; j < 4; j++) acc = C::dbl(acc);
+        }
+        int dg;
+        if constexpr (C::WINDOWS == 65) dg = w == 64 ? (int)top_carry : (int)((dig[w >> 3] >> (4 * (w & 7))) & 15u) - 8;
+        else dg = (int)((dig[w >> 3] >> (4 * (w & 7))) & 15u) - 8;
+        const int mag = dg < 0 ? -dg : dg;
+        Point T = wave_lds_load<C>(tab, mag == 0 ? 0 : mag - 1, lane);
+        T = C::cneg(T, dg < 0);
+        if (mag == 0) T = C::identity();
+        acc = C::add(acc, T);
+    }
+    return acc;
+}
+
+// out[i] = k[i] P[i].  pts: n x 16 words (x || y), ks: n x 8, out: n x 16.  One lane per multiplication.
+template <class C>
+DR_DEV void wave_scalar_mul(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks, uint32_t* __restrict__ out, uint32_t n) {
+    __shared__ uint32_t tab[wave_table_words<C>()];
+    const int lane = threadIdx.x;
+    uint32_t i = blockIdx.x * C::BLOCK + lane;
+    const bool live = i < n;
+    if (!live) i = n - 1;            // keep the wave converged; the duplicate result is not stored
+    uint32_t k[8];
+    const typename C::Point P = wave_load_term<C>(pts + (size_t)i * 16, ks + (size_t)i * 8, k);
+    const typename C::Point acc = wave_scalar_mul_core<C>(tab, lane, P, k);
+    if (live) wave_store_affine<C>(out + (size_t)i * 16, acc);
+}
+
+// out[g] = sum_{j<m} k[g m + j] P[g m + j]: one lane per term (m padded to mpad, a power of two <= 64), folded with shuffles by the
+// unified / complete addition (terms that coincide or cancel need nothing special)
+template <class C>
+DR_DEV void wave_msm_groups(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks, uint32_t* __restrict__ out,
+                            uint32_t groups, uint32_t m, uint32_t mpad) {
+    using Point = typename C::Point;
+    __shared__ uint32_t tab[wave_table_words<C>()];
+    const int lane = threadIdx.x;
+    const uint32_t per_block = C::BLOCK / mpad;
+    const uint32_t g = blockIdx.x * per_block + lane / mpad;
+    const uint32_t j = lane % mpad;
+    const bool live = g < groups && j < m;
+    const size_t idx = live ? (size_t)g * m + j : 0;          // dead lanes recompute term 0 and are masked out
+    uint32_t k[8];
+    const Point P = wave_load_term<C>(pts + idx * 16, ks + idx * 8, k);
+    const Point r = wave_scalar_mul_core<C>(tab, lane, P, k);
+    Point acc = live ? r : C::identity();
+#pragma unroll 1
+    for (uint32_t s = mpad >> 1; s > 0; s >>= 1) acc = C::add(acc, wave_shfl_down<C>(acc, s));
+    if (g < groups && j == 0) wave_store_affine<C>(out + (size_t)g * 16, acc);
+}
+
+// ---------------------------------------------------------------- SEC1 compressed points
+// x = bytes 1..32 of a 33-byte string (9 words, bytes 33..35 zero) read BIG-endian: little-endian word q is the byte swap of the
+// (unaligned) word at byte 29 - 4 q
+DR_DEV void sec1_x_words(const uint32_t (&w)[9], uint32_t (&xb)[8]) {
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+        const int k = 7 - q;
+        xb[q] = __builtin_bswap32((w[k] >> 8) | (w[k + 1] << 24));
+    }
+}
+// One lane per 33-byte SEC1 compressed encoding padded to 9 words: byte 0 is 0x02 or 0x03, x < p, the curve equation has a root, y the
+// root of byte 0's parity (y = 0 cannot happen: the group orders are odd).  out = x || y and ok = 1, or 64 zero bytes and ok = 0.
+template <class C>
+DR_DEV void sec1_decode(const uint32_t* __restrict__ enc /* n*9 */, uint32_t* __restrict__ out_xy /* n*16 */, uint32_t* __restrict__ ok,
+                        uint32_t n) {
+    uint32_t i = blockIdx.x * C::BLOCK + threadIdx.x;
+    const bool live = i < n;
+    if (!live) i = n - 1;
+    uint32_t w[9];
+#pragma unroll
+    for (int j = 0; j < 9; j++) w[j] = enc[(size_t)i * 9 + j];
+    const uint32_t first = w[0] & 0xffu;
+    uint32_t xb[8];
+    sec1_x_words(w, xb);
+    const typename C::Fe x = C::unpack(xb);
+    typename C::Fe y;
+    const bool root = C::y_of_x(x, y);
+    const bool valid = (first == 0x02u || first == 0x03u) && C::below_p(xb) && root;
+    if (C::is_odd(y) != ((first & 1u) != 0)) y = neg(y);
+    if (live) {
+        if (valid) {
+            wave_store8(out_xy + (size_t)i * 16, xb);
+            wave_store_fe<C>(out_xy + (size_t)i * 16 + 8, y);
+        } else {
+            wave_store_zero8(out_xy + (size_t)i * 16);
+            wave_store_zero8(out_xy + (size_t)i * 16 + 8);
+        }
+        ok[i] = valid ? 1u : 0u;
+    }
+}
+
+}  // namespace dr

@@ -118,6 +118,41 @@ def test_msm_groups_and_single_msm(ctx):
         assert fixed[64 * g : 64 * g + 64] == r.raw(r.add(r.mul(ks[2 * g], r.G), r.mul(ks[2 * g + 1], r.BLINDING)))
 
 
+@pytest.mark.parametrize("m", [1, 2, 63, 64, 65])
+def test_msm_groups(ctx, m):
+    """the grouped MSM over the group sizes at which its fold changes shape (mpad = 1, 2, 64 with and without a dead lane), a number of
+    groups that does not fill the last workgroup, and terms that coincide, cancel or are the identity inside a group"""
+    rng = random.Random(50 + m)
+    base = _points(rng, 16)
+    sc = lambda ks: b"".join(k.to_bytes(32, "little") for k in ks)  # noqa: E731
+    if m == 65:                                   # the grouped call takes at most 64 terms: the single MSM serves 65
+        pts = [base[i % 16] for i in range(65)]
+        ks = [rng.randrange(2**256) for _ in pts]
+        with pytest.raises(ValueError, match="group size must be in 1..64"):
+            ctx.bsn_msm_groups(b"".join(map(r.raw, pts)), sc(ks), 65, CV5)
+        assert ctx.bsn_msm(b"".join(map(r.raw, pts)), sc(ks), CV5) == r.raw(r.msm(pts, ks))
+        return
+    groups = 3 if m >= 63 else 13
+    pts, ks = [], []
+    for g in range(groups):
+        gp = [base[rng.randrange(16)] for _ in range(m)]
+        gk = [rng.randrange(2**256) for _ in gp]
+        if g == 0:
+            gp[0] = r.O                            # an identity term (the whole group when m = 1)
+        if m >= 2 and g == 1:
+            gp[1], gk[1] = gp[0], gk[0]            # P + P inside one group
+        if m >= 2 and g == 2:
+            gp[m - 1], gk[m - 1] = r.neg(gp[0]), gk[0]     # k P + k (-P) inside one group, at the two ends of the fold
+        pts += gp
+        ks += gk
+    raw = ctx.bsn_msm_groups(b"".join(map(r.raw, pts)), sc(ks), m, CV5)
+    assert len(raw) == 64 * groups
+    for g in range(groups):
+        assert raw[64 * g : 64 * g + 64] == r.raw(r.msm(pts[g * m : g * m + m], ks[g * m : g * m + m])), g
+    if m == 2:                                     # a group that cancels to the identity
+        assert ctx.bsn_msm_groups(r.raw(base[0]) + r.raw(r.neg(base[0])), sc([7, 7]), 2, CV5) == r.raw(r.O)
+
+
 def _decode_cases(rng):
     cases = []
     for _ in range(150):

@@ -28,11 +28,14 @@ _INSN = re.compile(r"^\s+(\S+)\s.*//\s*([0-9A-F]+):")
 _TARGET = re.compile(r"<\S+\+0x([0-9a-f]+)>")
 
 
-def device_objects():
+def device_objects(build=BUILD):
     """extract the gfx950 bundle of every .o (llvm-objdump --offloading writes <obj>.0.hipv4-...gfx950 next to it)"""
     outs = []
-    for obj in sorted(glob.glob(os.path.join(BUILD, "*.o"))):
-        subprocess.run([OBJDUMP, "--offloading", obj], cwd=BUILD, capture_output=True, check=False)
+    build = os.path.abspath(build)
+    for obj in sorted(glob.glob(os.path.join(build, "*.o"))):
+        for stale in glob.glob(obj + ".*.hipv4-*") + glob.glob(obj + ".*.host-*"):      # an earlier extraction is not overwritten
+            os.remove(stale)
+        subprocess.run([OBJDUMP, "--offloading", obj], cwd=build, capture_output=True, check=False)
         outs += glob.glob(obj + ".*gfx950")
     return sorted(set(outs))
 
