@@ -116,6 +116,10 @@ _PROTOTYPES.update({
     "dr_p256_map_to_curve": (c_int, [c_void_p, c_char_p, c_size_t, c_int, c_char_p, c_char_p]),
     "dr_ed25519_map_to_curve": (c_int, [c_void_p, c_char_p, c_size_t, c_int, c_char_p, c_char_p]),
     "dr_bjj_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
+    "dr_curve25519_scalar_mul_batch": (c_int, [c_void_p, c_char_p, c_char_p, c_char_p, c_size_t, c_char_p, c_char_p]),
+    "dr_curve25519_msm_groups": (c_int, [c_void_p, c_char_p, c_char_p, c_char_p, c_size_t, c_size_t, c_char_p, c_char_p]),
+    "dr_curve25519_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
+    "dr_curve25519_map_to_curve": (c_int, [c_void_p, c_char_p, c_size_t, c_int, c_int, c_char_p, c_char_p]),
     "dr_bjj_field_ops_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p, c_void_p]),
     "dr_encode_to_curve_batch": (c_int, [c_void_p, POINTER(VrfSuiteStruct), c_char_p, POINTER(ctypes.c_uint64), c_char_p,
                                          POINTER(ctypes.c_uint64), c_size_t, c_char_p]),
@@ -201,10 +205,12 @@ def _ragged(items):
 CURVE_BANDERSNATCH, CURVE_JUBJUB, CURVE_BANDERSNATCH_SW, CURVE_ED25519, CURVE_P256, CURVE_BABYJUBJUB = 0, 1, 2, 3, 4, 5
 CURVE_SECP256K1, CURVE_SECP256K1_NU = 6, 7
 CURVE_P256_RO, CURVE_P256_NU, CURVE_ED25519_RO, CURVE_ED25519_NU = 8, 9, 10, 11
-# bytes of an encoded point, per curve id (the suites with 33-byte encodings; every other curve's are 32)
-_POINT_LEN = {CURVE_BANDERSNATCH_SW: 33, CURVE_P256: 33, CURVE_SECP256K1: 33, CURVE_SECP256K1_NU: 33, CURVE_P256_RO: 33, CURVE_P256_NU: 33}
+CURVE_CURVE25519_RO, CURVE_CURVE25519_NU = 13, 14       # (12 is not assigned)
+# bytes of an encoded point, per curve id (the suites with 33-byte encodings and Curve25519's 64-byte u || v; every other curve's are 32)
+_POINT_LEN = {CURVE_BANDERSNATCH_SW: 33, CURVE_P256: 33, CURVE_SECP256K1: 33, CURVE_SECP256K1_NU: 33, CURVE_P256_RO: 33, CURVE_P256_NU: 33,
+              CURVE_CURVE25519_RO: 64, CURVE_CURVE25519_NU: 64}
 # the nonuniform RFC 9380 suites: one field element per message
-_NU_CURVES = (CURVE_SECP256K1_NU, CURVE_P256_NU, CURVE_ED25519_NU)
+_NU_CURVES = (CURVE_SECP256K1_NU, CURVE_P256_NU, CURVE_ED25519_NU, CURVE_CURVE25519_NU)
 
 
 def curve_point_len(curve: int) -> int:
@@ -635,6 +641,39 @@ class Context:
     def ed25519_map_to_curve(self, us: bytes, per_item: int):
         """dr_ed25519_map_to_curve: as secp256k1_map_to_curve, onto Ed25519's prime-order subgroup (flags 0: no image)."""
         return self._map_to_curve(lib().dr_ed25519_map_to_curve, us, per_item)
+
+    # ---- Curve25519: Montgomery points u || v with an identity flag byte per point (include/dotring_hip.h)
+    def curve25519_scalar_mul_batch(self, pts_uv: bytes, id_in: bytes, scalars: bytes):
+        """dr_curve25519_scalar_mul_batch: (u||v bytes, identity flags) of k_i P_i; id_in: one flag byte per point (1: the identity)."""
+        n = len(scalars) // 32
+        if len(scalars) != 32 * n or len(pts_uv) != 64 * n or len(id_in) != n:
+            raise ValueError("Points, flags and scalars must have same length")
+        out, flags = ctypes.create_string_buffer(max(1, 64 * n)), ctypes.create_string_buffer(max(1, n))
+        _check(lib().dr_curve25519_scalar_mul_batch(self.handle, pts_uv, id_in, scalars, n, out, flags))
+        return out.raw[: 64 * n], flags.raw[:n]
+
+    def curve25519_msm_groups(self, pts_uv: bytes, id_in: bytes, scalars: bytes, m: int):
+        """dr_curve25519_msm_groups: (u||v bytes, identity flags) of the sums of consecutive groups of m terms."""
+        n = len(scalars) // 32
+        if m <= 0 or n % m or len(scalars) != 32 * n or len(pts_uv) != 64 * n or len(id_in) != n:
+            raise ValueError("Points, flags and scalars must have same length (a multiple of the group size)")
+        groups = n // m
+        out, flags = ctypes.create_string_buffer(max(1, 64 * groups)), ctypes.create_string_buffer(max(1, groups))
+        _check(lib().dr_curve25519_msm_groups(self.handle, pts_uv, id_in, scalars, groups, m, out, flags))
+        return out.raw[: 64 * groups], flags.raw[:groups]
+
+    def curve25519_decode_points(self, enc: bytes, check: bool = True):
+        """dr_curve25519_decode_points: (u||v bytes, flags) for len(enc)/64 encodings, with or without the prime-order check."""
+        return self._decode_points(lib().dr_curve25519_decode_points, 64, enc, check)
+
+    def curve25519_map_to_curve(self, us: bytes, per_item: int, clear_cofactor: bool = True):
+        """dr_curve25519_map_to_curve: (u||v bytes, identity flags) for len(us) / (32 per_item) items; every element has an image."""
+        if per_item not in (1, 2) or len(us) % (32 * per_item):
+            raise ValueError("field elements are 32 bytes each, one or two per item")
+        n = len(us) // (32 * per_item)
+        out, flags = ctypes.create_string_buffer(max(1, 64 * n)), ctypes.create_string_buffer(max(1, n))
+        _check(lib().dr_curve25519_map_to_curve(self.handle, us, n, per_item, 1 if clear_cofactor else 0, out, flags))
+        return out.raw[: 64 * n], flags.raw[:n]
 
     def ed25519_decode_points(self, enc: bytes, check: bool = True):
         """dr_ed25519_decode_points: (x||y bytes, flags) for len(enc)/32 encodings, with or without the prime-order check."""

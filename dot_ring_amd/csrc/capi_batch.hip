@@ -61,7 +61,7 @@ struct PedersenBatch {
             t = su.suite_id;
             drh::put8(t, 0x02);                                    // PEDERSEN_VRF
             drh::put_le64(t, 1);                                   // one (input, output) pair
-            uint8_t enc[33];
+            uint8_t enc[drh::POINT_MAX];
             drh::enc_point(su, io_c ? io_c + 128 * i : inputs.data() + 64 * i, enc); drh::put(t, enc, pl);
             drh::enc_point(su, io_c ? io_c + 128 * i + 64 : outs.data() + 64 * i, enc); drh::put(t, enc, pl);
             size_t adl = ad_off[i + 1] - ad_off[i];
@@ -108,7 +108,7 @@ struct PedersenBatch {
         TRY(suite_coords(actx, su, ybar.data(), B, 1, ybar_store, &ybar_c));
         std::vector<int> bad2(B, 0);
         drh::parallel_for(B, [&](size_t i) {
-            uint8_t enc[33];
+            uint8_t enc[drh::POINT_MAX];
             drh::enc_point(su, ybar_c + 64 * i, enc);
             drh::put(tr[i], enc, pl);
             uint64_t x[4], b[4], k[4], kb[4];
@@ -147,6 +147,10 @@ struct PedersenBatch {
             TRY(suite_coords(actx, su, rk.data(), 2 * B, 2, rk_store, &rk_c));
         }
         const uint8_t* outs_c = su.cv->sw ? outs_sw.data() : outs.data();
+        // Curve25519: the identity has no encoding (the reference's point_to_string raises)
+        if (drh::any_mont_identity(su, inputs.data(), B) || drh::any_mont_identity(su, outs.data(), B) || drh::any_mont_identity(su, ybar.data(), B) ||
+            drh::any_mont_identity(su, third.data(), 2 * B))
+            return fail(DR_ERR_INVALID, "cannot serialize the point at infinity");
         auto r_of = [&](size_t i) { return rk_c ? rk_c + 128 * i : third.data() + 64 * i; };
         auto ok_of = [&](size_t i) { return rk_c ? rk_c + 128 * i + 64 : third.data() + 64 * (B + i); };
         drh::parallel_for(B, [&](size_t i) {
@@ -359,7 +363,7 @@ int pedersen_verify_core(dr_ctx* actx, const drh::VrfSuite& su, size_t B, const 
         drh::Bytes t = su.suite_id;
         drh::put8(t, 0x02);
         drh::put_le64(t, 1);
-        uint8_t enc[33];
+        uint8_t enc[drh::POINT_MAX];
         drh::enc_point(su, in_c + 64 * i, enc);
         drh::put(t, enc, pl);
         drh::put(t, pr, pl);                                   // output point, as encoded in the proof
@@ -406,8 +410,9 @@ int pedersen_verify_core(dr_ctx* actx, const drh::VrfSuite& su, size_t B, const 
         std::memcpy(pts.data() + 320 * B + 64, su.blinding_base, 64);  drh::store_le32(bs, sc.data() + 160 * B + 32);
         uint8_t sum[64];
         TRY(te_msm(actx, su.cv->id, pts.data(), sc.data(), 5 * B + 2, sum));
-        uint8_t ident[64] = {0};
-        ident[32] = su.identity_y;   // (0, 1) on the twisted Edwards curves; 64 zero bytes on P-256 and secp256k1
+        uint8_t ident[64];
+        std::memset(ident, su.identity_fill, 64);
+        if (!su.identity_fill) ident[32] = su.identity_y;   // (0, 1) on the twisted Edwards curves; 64 zero bytes on P-256 and secp256k1; 0xff bytes on Curve25519
         ped_ok = std::memcmp(sum, ident, 64) == 0 ? 1 : 0;
     }
     return DR_OK;
@@ -984,6 +989,9 @@ int dr_ietf_prove_batch(dr_ctx* ctx, const dr_vrf_suite* suite, int thin, size_t
         }
         const uint8_t* pks = firsts.data();
         const uint8_t* outs = firsts.data() + 64 * B;
+        // Curve25519: the identity has no encoding (the reference's point_to_string raises)
+        if (drh::any_mont_identity(su, inputs.data(), B) || drh::any_mont_identity(su, firsts.data(), 2 * B))
+            return fail(DR_ERR_INVALID, "cannot serialize the point at infinity");
         // the SW suite encodes the SW images: (pk_i, I_i, O_i) mapped together, one inversion per proof
         std::vector<uint8_t> pio_store;
         const uint8_t* pio = nullptr;
@@ -1003,14 +1011,14 @@ int dr_ietf_prove_batch(dr_ctx* ctx, const dr_vrf_suite* suite, int thin, size_t
         std::vector<drh::Bytes> tr(B);
         std::vector<uint8_t> gpts(B * 128), gsc(B * 64);
         std::vector<int> bad(B, 0);
-        uint8_t enc_g[33];
+        uint8_t enc_g[drh::POINT_MAX];
         drh::enc_point(su, su.cv->sw ? su.generator_sw : su.generator, enc_g);
         drh::parallel_for(B, [&](size_t i) {
             drh::Bytes& t = tr[i];
             t = su.suite_id;
             drh::put8(t, thin ? 0x01 : 0x00);                      // THIN_VRF / TINY_VRF
             drh::put_le64(t, 2);
-            uint8_t enc[33];
+            uint8_t enc[drh::POINT_MAX];
             drh::put(t, enc_g, pl);
             drh::enc_point(su, pk_c(i), enc); drh::put(t, enc, pl);
             drh::enc_point(su, in_c(i), enc); drh::put(t, enc, pl);
@@ -1039,9 +1047,10 @@ int dr_ietf_prove_batch(dr_ctx* ctx, const dr_vrf_suite* suite, int thin, size_t
         std::vector<uint8_t> rs_store;
         const uint8_t* rs_c = nullptr;
         TRY(suite_coords(ctx, su, rs.data(), B, 1, rs_store, &rs_c));
+        if (drh::any_mont_identity(su, rs.data(), B)) return fail(DR_ERR_INVALID, "cannot serialize the point at infinity");
         drh::parallel_for(B, [&](size_t i) {
             uint8_t* out = out_proofs + plen * i;
-            uint8_t enc_r[33];
+            uint8_t enc_r[drh::POINT_MAX];
             drh::enc_point(su, out_c(i), out);
             drh::enc_point(su, rs_c + 64 * i, enc_r);
             uint64_t c[4], x[4], k[4], s[4];

@@ -4,6 +4,7 @@
 #include "hostsmall.hpp"
 #include "kernels_sw.hip.h"
 #include "kernels_ed25519.hip.h"
+#include "kernels_curve25519.hip.h"
 #include "kernels_p256.hip.h"
 #include "kernels_secp256k1.hip.h"
 #include "kernels_bjj.hip.h"
@@ -494,7 +495,10 @@ int sw_boundary(dr_ctx* ctx, const uint8_t* sw_in, size_t n_in, uint8_t* sw_out,
 // pass through io_a / io_b / io_c only, which ctx_wipe_scratch covers.  Points are affine x || y.  Each suite is one description below (its
 // kernels, launch names, base field, identity and encoding widths); every operation is one template over it.
 namespace {
-struct NoConsts { static int consts_ready(dr_ctx*) { return DR_OK; } };   // the suites with no device constants to load first
+struct NoConsts {                      // the suites with no device constants to load first
+    static int consts_ready(dr_ctx*) { return DR_OK; }
+    static constexpr bool flagged = false;     // whether the kernels carry an identity flag word beside each point (Curve25519 alone)
+};
 struct Ed25519Suite : NoConsts {
     static constexpr auto scalar_mul = dr::k_ed_scalar_mul;
     static constexpr auto msm_groups = dr::k_ed_msm_groups;
@@ -610,6 +614,7 @@ int bjj_consts_ready(dr_ctx* ctx) {
     return DR_OK;
 }
 struct BjjSuite {
+    static constexpr bool flagged = false;
     static constexpr auto scalar_mul = dr::k_bjj_scalar_mul;
     static constexpr auto msm_groups = dr::k_bjj_msm_groups;
     static constexpr auto dec_tai = dr::k_bjj_decode_points<dr::BJJ_DEC_TAI>, dec_check = dr::k_bjj_decode_points<dr::BJJ_DEC_CHECK>,
@@ -621,6 +626,31 @@ struct BjjSuite {
     static constexpr size_t identity_y = 1, enc_bytes = 32, rec_bytes = 32, tai_bytes = 32;
     static int consts_ready(dr_ctx* ctx) { return bjj_consts_ready(ctx); }
 };
+// Curve25519_RO / Curve25519_NU (curves 13 and 14, kernels_curve25519.hip.h): Ed25519's group under Montgomery coordinates u || v, 64 bytes
+// encoded as they are.  The kernels take and give an identity flag word per point (`flagged`); between the launches, where a point is 64
+// bytes and nothing else, the identity is drh::mont_is_identity's 64 bytes of 0xff.  No try-and-increment: dec_tai is the checking decoder.
+struct Curve25519Suite : NoConsts {
+    static constexpr bool flagged = true;
+    static constexpr auto scalar_mul = dr::k_c25519_scalar_mul;
+    static constexpr auto msm_groups = dr::k_c25519_msm_groups;
+    static constexpr auto dec_tai = dr::k_c25519_decode_points<dr::C25519_DEC_CHECK>, dec_check = dr::k_c25519_decode_points<dr::C25519_DEC_CHECK>,
+                          dec_codec = dr::k_c25519_decode_points<dr::C25519_DEC_CODEC>;
+    static constexpr int block = dr::ED_BLOCK;
+    static constexpr const char *name = "Curve25519", *k_scalar_mul = "k_c25519_scalar_mul", *k_msm_groups = "k_c25519_msm_groups",
+                                *k_decode = "k_c25519_decode_points";
+    static const drh::Mod256& field() { return drh::mod_p25519(); }
+    static constexpr size_t identity_y = 0, enc_bytes = 64, rec_bytes = 64, tai_bytes = 64;   // (identity_y does not apply: native_identity)
+};
+// the identity as the 64 bytes the host path carries: (0, identity_y), 64 zero bytes on the Weierstrass curves, 64 bytes of 0xff on Curve25519
+template <class S>
+void native_identity(uint8_t* xy) {
+    if constexpr (S::flagged) {
+        std::memset(xy, 0xff, 64);
+    } else {
+        std::memset(xy, 0, 64);
+        xy[32] = (uint8_t)S::identity_y;
+    }
+}
 // rc = f(S{}) for the description S of curve cv's native suite; false, f not called, for every other curve and an unknown id
 template <class F>
 bool on_native(int cv, int& rc, F&& f) {
@@ -631,50 +661,99 @@ bool on_native(int cv, int& rc, F&& f) {
             return true;
         case drh::NativeSuite::bjj: rc = f(BjjSuite{}); return true;
         case drh::NativeSuite::secp256k1: rc = f(Secp256k1Suite{}); return true;
+        case drh::NativeSuite::curve25519: rc = f(Curve25519Suite{}); return true;
         default: return false;
     }
 }
 // n points, their coordinates checked against S's field, and n scalars to io_a / io_b, one launch (`go`, profiled as `name`) into io_c,
 // n_out points back
+// The identity flags of a flagged suite's call when the caller spells them out (the dr_curve25519_* entry points): one byte per point in
+// (null: none is the identity) and out.  Without them the identity travels inside the 64 bytes (drh::mont_is_identity).
+struct NativeFlags {
+    const uint8_t* in = nullptr;
+    uint8_t* out = nullptr;
+};
 template <class S, class F>
-int native_run(S, dr_ctx* ctx, const char* name, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, size_t n_out, uint8_t* out_xy, F&& go) {
+int native_run(S, dr_ctx* ctx, const char* name, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, size_t n_out, uint8_t* out_xy, F&& go,
+               const NativeFlags* fl = nullptr) {
     if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
     if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
+    // a flagged suite: the identities among the points become flag words behind the points in io_a (their 64 bytes zeros), and the flag
+    // words the kernel leaves behind its results in io_c become identities again; with the caller's own flags (fl) the points go as they
+    // are, so that 64 bytes of 0xff are refused below like every other coordinate at or above p
+    std::vector<uint8_t> clean;
+    std::vector<uint32_t> flags_in, flags_out;
+    if constexpr (S::flagged) {
+        flags_in.assign(n, 0);
+        for (size_t i = 0; fl && fl->in && i < n; i++) {
+            if (!fl->in[i]) continue;
+            if (clean.empty()) clean.assign(pts_xy, pts_xy + n * 64);      // (a flagged point's 64 bytes are ignored)
+            std::memset(clean.data() + 64 * i, 0, 64);
+            flags_in[i] = 1;
+        }
+        for (size_t i = 0; !fl && i < n; i++) {
+            if (!drh::mont_is_identity(pts_xy + 64 * i)) continue;
+            if (clean.empty()) clean.assign(pts_xy, pts_xy + n * 64);
+            std::memset(clean.data() + 64 * i, 0, 64);
+            flags_in[i] = 1;
+        }
+        if (!clean.empty()) pts_xy = clean.data();
+    }
     for (size_t i = 0; i < 2 * n; i++) {
         uint64_t v[4];
         drh::load_le32(pts_xy + 32 * i, v);
         if (drh::Mod256::geq(v, S::field().m)) return fail(DR_ERR_INVALID, "point coordinate is not a canonical field element");
     }
-    TRY(ctx->io_a.reserve(n * 64));
+    TRY(ctx->io_a.reserve(n * (S::flagged ? 68 : 64)));
     TRY(ctx->io_b.reserve(n * 32));
-    TRY(ctx->io_c.reserve(n_out * 64));
+    TRY(ctx->io_c.reserve(n_out * (S::flagged ? 68 : 64)));
     HIP_TRY(hipMemcpyAsync(ctx->io_a.p, pts_xy, n * 64, hipMemcpyHostToDevice, ctx->stream));
+    if constexpr (S::flagged) HIP_TRY(hipMemcpyAsync(ctx->io_a.as<uint8_t>() + n * 64, flags_in.data(), n * 4, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(ctx->io_b.p, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
     TRY(launch(ctx, name, go));
     HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_c.p, n_out * 64, hipMemcpyDeviceToHost, ctx->stream));
+    if constexpr (S::flagged) {
+        flags_out.resize(n_out);
+        HIP_TRY(hipMemcpyAsync(flags_out.data(), ctx->io_c.as<uint8_t>() + n_out * 64, n_out * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (ctx->prof) TRY(prof_collect(ctx));
+    for (size_t i = 0; i < flags_out.size(); i++) {
+        if (fl) fl->out[i] = flags_out[i] ? 1 : 0;                         // (the kernel stored 64 zero bytes)
+        else if (flags_out[i]) native_identity<S>(out_xy + 64 * i);
+    }
     return DR_OK;
 }
 template <class S>
-int native_scalar_mul_batch(S, dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy) {
+int native_scalar_mul_batch(S, dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy, const NativeFlags* fl = nullptr) {
     if (n == 0) return DR_OK;
     return native_run(S{}, ctx, S::k_scalar_mul, pts_xy, scalars, n, n, out_xy, [&] {
-        hipLaunchKernelGGL(S::scalar_mul, dim3(div_up(n, S::block)), dim3(S::block), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
-                           ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
-    });
+        if constexpr (S::flagged)
+            hipLaunchKernelGGL(S::scalar_mul, dim3(div_up(n, S::block)), dim3(S::block), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
+                               ctx->io_b.as<uint32_t>(), ctx->io_a.as<uint32_t>() + n * 16, ctx->io_c.as<uint32_t>(),
+                               ctx->io_c.as<uint32_t>() + n * 16, (uint32_t)n);
+        else
+            hipLaunchKernelGGL(S::scalar_mul, dim3(div_up(n, S::block)), dim3(S::block), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
+                               ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
+    }, fl);
 }
 template <class S>
-int native_msm_groups(S, dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy) {
+int native_msm_groups(S, dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy,
+                      const NativeFlags* fl = nullptr) {
     if (groups == 0) return DR_OK;
     if (m == 0 || m > 64) return fail(DR_ERR_INVALID, "group size must be in 1..64");
     uint32_t mpad = 1;
     while (mpad < m) mpad <<= 1;
     const uint32_t per_block = S::block / mpad;
     return native_run(S{}, ctx, S::k_msm_groups, pts_xy, scalars, groups * m, groups, out_xy, [&] {
-        hipLaunchKernelGGL(S::msm_groups, dim3(div_up(groups, per_block)), dim3(S::block), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
-                           ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)groups, (uint32_t)m, mpad);
-    });
+        if constexpr (S::flagged)
+            hipLaunchKernelGGL(S::msm_groups, dim3(div_up(groups, per_block)), dim3(S::block), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
+                               ctx->io_b.as<uint32_t>(), ctx->io_a.as<uint32_t>() + groups * m * 16, ctx->io_c.as<uint32_t>(),
+                               ctx->io_c.as<uint32_t>() + groups * 16, (uint32_t)groups, (uint32_t)m, mpad);
+        else
+            hipLaunchKernelGGL(S::msm_groups, dim3(div_up(groups, per_block)), dim3(S::block), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
+                               ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)groups, (uint32_t)m, mpad);
+    }, fl);
 }
 // fixed bases through the grouped kernel, each group's terms the m bases: no window table.  te_fixed_base_groups checked the arguments.
 template <class S>
@@ -688,8 +767,7 @@ int native_fixed_base_groups(S, dr_ctx* ctx, const uint8_t* bases_xy, const uint
 template <class S>
 int native_msm(S, dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t out_xy[64]) {
     if (n == 0) {
-        std::memset(out_xy, 0, 64);
-        out_xy[32] = (uint8_t)S::identity_y;
+        native_identity<S>(out_xy);
         return DR_OK;
     }
     if (!pts_xy || !scalars) return fail(DR_ERR_INVALID, "null buffer");
@@ -698,7 +776,7 @@ int native_msm(S, dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, si
         const size_t parts = (n + 63) / 64, m = parts == 1 ? n : 64;          // the last level: one group of the n <= 64 left
         pts.resize(parts * m * 64, 0);
         sc.resize(parts * m * 32, 0);
-        for (size_t i = n; i < parts * m; i++) pts[64 * i + 32] = (uint8_t)S::identity_y;     // padding: 0 * identity
+        for (size_t i = n; i < parts * m; i++) native_identity<S>(pts.data() + 64 * i);       // padding: 0 * identity
         part.resize(parts * 64);
         const int rc = native_msm_groups(S{}, ctx, pts.data(), sc.data(), parts, m, parts == 1 ? out_xy : part.data());
         explicit_bzero(sc.data(), sc.size());
@@ -1220,6 +1298,57 @@ int dr_ed25519_map_to_curve(dr_ctx* ctx, const uint8_t* us, size_t n, int per_it
     return native_map_to_curve(ctx, "k_ed25519_map_to_curve", dr::k_ed25519_map_to_curve, dr::ED_BLOCK, drh::mod_p25519(), us, n, per_item, out_xy,
                                ok);
 }
+// ---- Curve25519 (kernels_curve25519.hip.h): the entry points with the identity flags spelled out.  The flag bytes go straight to the
+// kernels' flag words (NativeFlags); a point whose flag is 0 must have canonical coordinates, 64 bytes of 0xff included.
+int dr_curve25519_scalar_mul_batch(dr_ctx* ctx, const uint8_t* pts_uv, const uint8_t* id_in, const uint8_t* scalars, size_t n, uint8_t* out_uv,
+                                   uint8_t* id_out) {
+    TRY(use_ctx(ctx));
+    if (n && !id_out) return fail(DR_ERR_INVALID, "null buffer");
+    const NativeFlags fl{id_in, id_out};
+    return native_scalar_mul_batch(Curve25519Suite{}, ctx, pts_uv, scalars, n, out_uv, &fl);
+}
+int dr_curve25519_msm_groups(dr_ctx* ctx, const uint8_t* pts_uv, const uint8_t* id_in, const uint8_t* scalars, size_t groups, size_t m,
+                             uint8_t* out_uv, uint8_t* id_out) {
+    TRY(use_ctx(ctx));
+    if (m == 0 || m > 64) return fail(DR_ERR_INVALID, "group size must be in 1..64");
+    if (groups >= (1ull << 31) || groups * m >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
+    if (groups && !id_out) return fail(DR_ERR_INVALID, "null buffer");
+    const NativeFlags fl{id_in, id_out};
+    return native_msm_groups(Curve25519Suite{}, ctx, pts_uv, scalars, groups, m, out_uv, &fl);
+}
+int dr_curve25519_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_t n, uint8_t* out_uv, uint8_t* ok) {
+    return native_decode_points(Curve25519Suite{}, ctx, check ? Curve25519Suite::dec_check : Curve25519Suite::dec_codec, enc, n, out_uv, ok);
+}
+// n items of per_item (1 or 2) field elements: the sum of their Elligator 2 images, times the cofactor 8 unless clear_cofactor = 0; every
+// canonical input has a value (id_out[i] = 1 where it is the identity, its 64 bytes then zeros)
+int dr_curve25519_map_to_curve(dr_ctx* ctx, const uint8_t* us, size_t n, int per_item, int clear_cofactor, uint8_t* out_uv, uint8_t* id_out) {
+    TRY(use_ctx(ctx));
+    if (per_item != 1 && per_item != 2) return fail(DR_ERR_INVALID, "one (nonuniform) or two (uniform, RO) field elements per item");
+    if (n == 0) return DR_OK;
+    if (!us || !out_uv || !id_out) return fail(DR_ERR_INVALID, "null buffer");
+    if (n >= (1ull << 30)) return fail(DR_ERR_INVALID, "batch too large");
+    const size_t elems = n * (size_t)per_item;
+    for (size_t i = 0; i < elems; i++) {
+        uint64_t v[4];
+        drh::load_le32(us + 32 * i, v);
+        if (drh::Mod256::geq(v, drh::mod_p25519().m)) return fail(DR_ERR_INVALID, "input is not a canonical field element");
+    }
+    TRY(ctx->io_a.reserve(elems * 32));
+    TRY(ctx->io_b.reserve(n * 64));
+    TRY(ctx->io_c.reserve(n * 4));
+    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, us, elems * 32, hipMemcpyHostToDevice, ctx->stream));
+    TRY(launch(ctx, "k_curve25519_map_to_curve", [&] {
+        hipLaunchKernelGGL(dr::k_curve25519_map_to_curve, dim3(div_up(n, dr::ED_BLOCK)), dim3(dr::ED_BLOCK), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
+                           ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n, (uint32_t)per_item, clear_cofactor ? 1u : 0u);
+    }));
+    std::vector<uint32_t> flags(n);
+    HIP_TRY(hipMemcpyAsync(out_uv, ctx->io_b.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(flags.data(), ctx->io_c.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->prof) TRY(prof_collect(ctx));
+    for (size_t i = 0; i < n; i++) id_out[i] = flags[i] ? 1 : 0;
+    return DR_OK;
+}
 int dr_bjj_field_ops_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
     return native_field_selftest(BjjSuite{}, ctx, a_limbs, b_limbs, n, out, flags);
 }
@@ -1352,11 +1481,12 @@ int load_suite(const dr_vrf_suite* s, drh::VrfSuite& out, bool allow_sw) {
             out.point_len = S.enc_bytes;
             out.identity_y = (uint8_t)S.identity_y;
             out.tai_len = S.tai_bytes;
+            out.identity_fill = S.flagged ? 0xff : 0;
             return allow_sw ? DR_OK : fail(DR_ERR_INVALID, std::string("this entry point does not serve the ") + S.name + " suite");
         }) && rc != DR_OK)
         return rc;
     if (out.cv->sswu && out.xof != 2) return fail(DR_ERR_INVALID, "the secp256k1 and P-256 suites hash with SHA-256 (xof = 2)");
-    if (out.cv->ell2_native && out.xof != 0) return fail(DR_ERR_INVALID, "the Ed25519 suites hash with SHA-512 (xof = 0)");
+    if (out.cv->ell2_native && out.xof != 0) return fail(DR_ERR_INVALID, "the Ed25519 and Curve25519 suites hash with SHA-512 (xof = 0)");
     if (out.cv->sw) {
         if (!allow_sw) return fail(DR_ERR_INVALID, "this entry point does not serve the short Weierstrass suite");
         // the kernels take the suite's constants as their TE images; the SW generator stays for its encoding
@@ -1391,6 +1521,13 @@ int encode_to_curve_msgs(dr_ctx* ctx, const drh::VrfSuite& su, size_t B, const u
         switch (su.cv->native) {
             case drh::NativeSuite::p256: TRY(dr_p256_map_to_curve(ctx, us.data(), B, (int)per, out_xy, ok.data())); break;
             case drh::NativeSuite::ed25519: TRY(dr_ed25519_map_to_curve(ctx, us.data(), B, (int)per, out_xy, ok.data())); break;
+            case drh::NativeSuite::curve25519:        // (every input has an image; one that is the identity travels as 64 bytes of 0xff)
+                TRY(dr_curve25519_map_to_curve(ctx, us.data(), B, (int)per, 1, out_xy, ok.data()));
+                for (size_t i = 0; i < B; i++) {
+                    if (ok[i]) std::memset(out_xy + 64 * i, 0xff, 64);
+                    ok[i] = 1;
+                }
+                break;
             default: TRY(dr_secp256k1_map_to_curve(ctx, us.data(), B, (int)per, out_xy, ok.data())); break;
         }
         for (size_t i = 0; i < B; i++)

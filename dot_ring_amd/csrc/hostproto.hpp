@@ -320,7 +320,10 @@ inline const Mod256& mod_p() {       // Bandersnatch base field = BLS12-381 scal
 // encodings and RFC 9380 hashing to the curve (kernels_secp256k1.hip.h; ids 6 and 7 are its uniform (RO) and nonuniform variants).
 // Ids 8 - 11 are the RFC 9380 variants of P-256 (8 RO, 9 NU: simplified SWU, SEC1 encodings) and Ed25519 (10 RO, 11 NU: Elligator 2,
 // Ed25519's own codec): the same native suites and kernels as ids 4 and 3, with a map kernel in place of try-and-increment.
-enum class NativeSuite { none, ed25519, p256, bjj, secp256k1 };
+// Ids 13 and 14 are Curve25519_RO / Curve25519_NU (specs/curve25519.py): Ed25519's group and field with points in Montgomery form
+// (u, v), 64 bytes on the wire, on kernels_curve25519.hip.h, which converts at both ends of each kernel.  Id 12 stays unassigned: it is
+// the id the tests of the earlier suites use as the unknown one.
+enum class NativeSuite { none, ed25519, p256, bjj, secp256k1, curve25519 };
 struct TeCurveHost {
     int id;
     Mod256 n;                 // prime-order subgroup
@@ -374,7 +377,7 @@ inline TeCurveHost curves_p256() {
     return c;
 }
 inline const TeCurveHost* te_curve(int id) {
-    static const TeCurveHost curves[12] = {
+    static const TeCurveHost curves[14] = {
         [] { TeCurveHost c{}; c.id = 0; c.n = mod_n();
              const uint64_t d[4] = {0xb369f2f5188d58e7ULL, 0xcb66677177e54f92ULL, 0xc66e3bf86be3b6d8ULL, 0x6389c12633c267cbULL};
              std::memcpy(c.d, d, 32); c.neg_a[0] = 5; c.scalar_bits = 253; c.glv = true; c.tai = false; return c; }(),
@@ -409,13 +412,17 @@ inline const TeCurveHost* te_curve(int id) {
         // Ed25519_RO (10) and Ed25519_NU (11) (specs/ed25519.py): Ed25519's group, kernels and codec, hashing by Elligator 2
         [] { TeCurveHost c = curves_ed25519(); c.id = 10; c.tai = false; c.ell2_native = true; return c; }(),
         [] { TeCurveHost c = curves_ed25519(); c.id = 11; c.tai = false; c.ell2_native = true; c.nu = true; return c; }(),
+        // Curve25519_RO (13) and Curve25519_NU (14) (specs/curve25519.py): the same order and field, Montgomery points; d and neg_a do not apply
+        [] { TeCurveHost c = curves_ed25519(); c.id = 13; c.tai = false; c.ell2_native = true; c.native = NativeSuite::curve25519; return c; }(),
+        [] { TeCurveHost c = curves_ed25519(); c.id = 14; c.tai = false; c.ell2_native = true; c.nu = true; c.native = NativeSuite::curve25519; return c; }(),
     };
+    if (id >= 13 && id <= 14) return &curves[id - 1];      // (12 is no curve)
     return id >= 0 && id <= 11 ? &curves[id] : nullptr;
 }
 // the base field of a curve of the table
 inline const Mod256& te_field(const TeCurveHost& c) {
     switch (c.native) {
-        case NativeSuite::ed25519: return mod_p25519();
+        case NativeSuite::ed25519: case NativeSuite::curve25519: return mod_p25519();
         case NativeSuite::p256: return mod_p256();
         case NativeSuite::bjj: return mod_pbn254();
         case NativeSuite::secp256k1: return mod_psecp256k1();
@@ -595,16 +602,32 @@ struct VrfSuite {
     int xof;                  // the transcript hash (dr_vrf_suite.xof): 0 SHA-512 or 2 SHA-256 in counter mode, 1 SHAKE128
     uint8_t generator[64], blinding_base[64];     // TE affine (the kernels' coordinates; the SW suite's are mapped on loading)
     const TeCurveHost* cv = te_curve(0);
-    size_t point_len = 32;                        // bytes of an encoded point: 32 (TE), 33 (SW, P-256, secp256k1)
+    size_t point_len = 32;                        // bytes of an encoded point: 32 (TE), 33 (SW, P-256, secp256k1), 64 (Curve25519)
     size_t tai_len = 32;                          // bytes of a try-and-increment candidate: 33 on P-256 (the flag byte), 32 otherwise
     uint8_t identity_y = 1;                       // the identity is (0, identity_y): (0, 1) on the twisted Edwards curves, 64 zero bytes otherwise
     uint8_t generator_sw[64] = {0};               // SW suite: the generator as given (its encoding enters the Tiny / Thin transcripts)
+    uint8_t identity_fill = 0;                    // 0xff on Curve25519: its identity inside the library is 64 bytes of 0xff (mont_identity)
 };
+// Curve25519's identity where a point is 64 bytes and nothing else (the host path between the launches and the generic dr_te_* entry
+// points): u = v = 2^256 - 1, which is no field element, so no point of the curve — (0, 0) is one.  The launches turn it into the kernels'
+// identity flag and back (capi_core.hip: native_run).
+constexpr size_t POINT_MAX = 64;                  // the longest encoded point of any suite
+inline bool mont_is_identity(const uint8_t xy[64]) {
+    for (int i = 0; i < 64; i++) if (xy[i] != 0xff) return false;
+    return true;
+}
+// whether any of n points of a Curve25519 suite is the identity (false for every other suite)
+inline bool any_mont_identity(const VrfSuite& su, const uint8_t* xy, size_t n) {
+    if (!su.identity_fill) return false;
+    for (size_t i = 0; i < n; i++) if (mont_is_identity(xy + 64 * i)) return true;
+    return false;
+}
 // the suite's point encoding of xy given in the suite's own coordinates (TE, or SW for the SW suite)
 inline void enc_point(const VrfSuite& su, const uint8_t xy[64], uint8_t* out) {
     if (su.cv->sw) enc_sw_point(xy, out);
     else if (su.cv->native == NativeSuite::p256 && !su.cv->sswu) enc_sw_point(xy, out, mod_p256());
     else if (su.cv->native == NativeSuite::secp256k1 || su.cv->native == NativeSuite::p256) enc_sec1_point(xy, out);   // (P256_RO / P256_NU: SEC1)
+    else if (su.cv->native == NativeSuite::curve25519) std::memcpy(out, xy, 64);   // u || v as they are (the identity has no encoding: the provers refuse it)
     else enc_te_point(xy, out, te_field(*su.cv));
 }
 // squeeze `size` bytes of the stream defined by everything absorbed (xof: VrfSuite::xof)

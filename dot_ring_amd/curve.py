@@ -12,6 +12,9 @@ Mirrors (names, argument meaning, error behaviour) the parts of the reference th
                                                 (DR_CURVE_SECP256K1 / DR_CURVE_SECP256K1_NU)
   dot_ring/curve/specs/baby_jubjub.py           BabyJubJub: a = 1 over the BN254 scalar field, cofactor 8, try-and-increment with
                                                 SHA-512 (candidates masked to the field's 254 bits); kernels of their own (DR_CURVE_BABYJUBJUB)
+  dot_ring/curve/specs/curve25519.py            Curve25519 (= Curve25519_RO), Curve25519_NU: Montgomery affine points over Ed25519's field,
+                                                64-byte u || v codec, RFC 9380 Elligator 2 with SHA-512; kernels of their own over the
+                                                Ed25519 group law (DR_CURVE_CURVE25519_RO / _NU)
   dot_ring/curve/point.py:150-214               compressed codec
   dot_ring/curve/twisted_edwards/*              affine law, Elligator2 encode_to_curve
   dot_ring/curve/curve.py:56-67,110-237,384-401 valid_point, hash_to_field, key derivation
@@ -968,10 +971,192 @@ class Ed25519Ell2Point(BandersnatchPoint):
         return unpack_points(cls, runtime.context().encode_to_curve_batch(cls._suite_struct(), list(alpha_strings), salts))
 
 
+class Curve25519Point:
+    """Affine point of Curve25519_RO / Curve25519_NU (dot_ring/curve/specs/curve25519.py, montgomery/mg_affine_point.py):
+    y^2 = x^3 + 486662 x^2 + x over 2^255 - 19 (x, y are the reference's names for u, v), cofactor 8, the identity is (None, None).
+    (0, 0) is a point of the curve (order 2), so the identity cannot travel as 64 zero bytes: it packs as 64 bytes of 0xff for the generic
+    entry points and as a flag byte for the dr_curve25519_* ones (pack_points_flagged).  Single additions are host big-int code with the
+    reference's affine formulas; scalar multiplications, MSMs, decoding and hashing to the curve run on the GPU (kernels_curve25519.hip.h,
+    which computes on the Ed25519 group law through the birational map)."""
+    curve: BandersnatchCurve
+    _P = 2**255 - 19
+    _N = 2**252 + 0x14DEF9DEA2F79CD65812631A5CF5D3ED
+    _H, _CV = 8, _native.CURVE_CURVE25519_RO
+    _MG_A = 486662
+    _IDENTITY_BYTES = b"\xff" * 64
+    __slots__ = ("x", "y")
+
+    def __init__(self, x, y):
+        self.x, self.y = x, y
+        if x is None and y is None:
+            return
+        if x is None or y is None or not (0 <= x < self._P and 0 <= y < self._P):
+            raise ValueError("Invalid point coordinates")
+        if not self._on_curve(x, y):
+            raise ValueError("Point is not on the curve")
+
+    @classmethod
+    def _on_curve(cls, x: int, y: int) -> bool:
+        return (y * y - ((x + cls._MG_A) * x + 1) * x) % cls._P == 0
+
+    @classmethod
+    def _trusted(cls, x: int, y: int):
+        """Kernel outputs: 64 bytes of 0xff are the identity."""
+        pt = object.__new__(cls)
+        pt.x, pt.y = (None, None) if x == y == (1 << 256) - 1 else (x, y)
+        return pt
+
+    def __eq__(self, other):
+        return isinstance(other, Curve25519Point) and self.x == other.x and self.y == other.y
+
+    def __hash__(self):
+        return 0 if self.x is None else (self.x + self.y) % self._N
+
+    def __repr__(self):
+        return f"{type(self).__name__}({self.x}, {self.y})"
+
+    @classmethod
+    def identity(cls):
+        return cls(None, None)
+
+    @classmethod
+    def generator_point(cls):
+        return cls(*cls.curve.params.generator)
+
+    def is_identity(self) -> bool:
+        return self.x is None or self.y is None
+
+    def is_on_curve(self) -> bool:
+        return self.is_identity() or self._on_curve(self.x, self.y)
+
+    # -- group law (mg_affine_point.py:38-116, B = 1)
+    def __add__(self, other):
+        if not isinstance(other, Curve25519Point):
+            return NotImplemented
+        if self.is_identity():
+            return other
+        if other.is_identity():
+            return self
+        p, a = self._P, self._MG_A
+        x1, y1, x2, y2 = self.x, self.y, other.x, other.y
+        if x1 == x2:
+            if y1 != y2 or y1 == 0:
+                return self.identity()
+            lam = (3 * x1 * x1 + 2 * a * x1 + 1) * pow(2 * y1, -1, p) % p
+        else:
+            lam = (y2 - y1) * pow(x2 - x1, -1, p) % p
+        x3 = (lam * lam - a - x1 - x2) % p
+        return type(self)(x3, (lam * (x1 - x3) - y1) % p)
+
+    def double(self):
+        return self + self
+
+    def __neg__(self):
+        return self if self.is_identity() else type(self)(self.x, -self.y % self._P)
+
+    def __sub__(self, other):
+        return self + (-other)
+
+    def __mul__(self, scalar: int):
+        return scalar_mul_batch([self], [scalar])[0]
+
+    __rmul__ = __mul__
+
+    @classmethod
+    def msm(cls, points, scalars):
+        if len(points) != len(scalars):
+            raise ValueError("Points and scalars must have same length")
+        if not points:
+            return cls.identity()
+        raw = runtime.context().bsn_msm(pack_points(points), pack_scalars(scalars, cls._N), cls._CV)
+        return cls._trusted(int.from_bytes(raw[:32], "little"), int.from_bytes(raw[32:], "little"))
+
+    def clear_cofactor(self):
+        return scalar_mul_batch_raw([self], [self._H])[0]
+
+    # -- codec (mg_affine_point.py:348-389): u || v, 32 little-endian bytes each; no compressed form, no encoding of the identity
+    def point_to_string(self) -> bytes:
+        if self.is_identity():
+            raise ValueError("Cannot serialize point at infinity")
+        if not self.curve.params.encoding.uncompressed:
+            raise NotImplementedError("Compressed encoding not implemented")
+        return self.x.to_bytes(32, "little") + self.y.to_bytes(32, "little")
+
+    @classmethod
+    def string_to_point(cls, data):
+        if isinstance(data, str):
+            data = bytes.fromhex(data)
+        data = bytes(data)
+        if not cls.curve.params.encoding.uncompressed:
+            raise NotImplementedError("Compressed encoding not implemented")
+        if len(data) != 64:
+            raise ValueError(f"Invalid point length: expected 64, got {len(data)}")
+        return cls(int.from_bytes(data[:32], "little"), int.from_bytes(data[32:], "little"))
+
+    # -- hash to curve (RFC 9380 curve25519_XMD:SHA-512_ELL2_RO_ / _NU_): expand_message_xmd natively on the host, the map on the GPU
+    _suite_struct = BandersnatchPoint.__dict__["_suite_struct"]
+
+    @classmethod
+    def _per_item(cls) -> int:
+        return 1 if cls.curve.params.e2c.endswith("_nu") else 2
+
+    @classmethod
+    def map_to_curve(cls, u: int):
+        """MGAffinePoint.map_to_curve (mg_affine_point.py:289-346): ONE image with its cofactor not cleared, host big-int code as the
+        other suites' map_to_curve is; the batched path (encode_to_curve_from_field) runs the same steps in the kernel"""
+        p, a = cls._P, cls._MG_A
+        tv1 = 2 * u * u % p
+        if tv1 == p - 1:
+            tv1 = 0
+        x1 = -a * pow(tv1 + 1, -1, p) % p
+        gx1 = ((x1 + a) * x1 + 1) * x1 % p
+        e2 = cls.curve.is_square(gx1)
+        x, y2 = (x1, gx1) if e2 else ((-x1 - a) % p, tv1 * gx1 % p)
+        y = _sqrt_tonelli_shanks(y2, p)
+        if e2 ^ (y % 2 == 1):
+            y = -y % p
+        return cls(x, y)
+
+    hash_to_field_pairs = Secp256k1Point.__dict__["hash_to_field_pairs"]
+
+    @classmethod
+    def encode_to_curve_from_field(cls, us: bytes):
+        """Device half: the maps, for RO the sum of the two images, and the cofactor, for packed canonical field elements."""
+        if not us:
+            return []
+        return unpack_points_flagged(cls, *runtime.context().curve25519_map_to_curve(us, cls._per_item()))
+
+    @classmethod
+    def encode_to_curve(cls, alpha_string: bytes, salt: bytes = b""):
+        return cls.encode_to_curve_batch([alpha_string], [salt])[0]
+
+    @classmethod
+    def encode_to_curve_batch(cls, alpha_strings, salts=None):
+        if not alpha_strings:
+            return []
+        return unpack_points(cls, runtime.context().encode_to_curve_batch(cls._suite_struct(), list(alpha_strings), salts))
+
+
 # ------------------------------------------------------------------ batched helpers over the C ABI
 def pack_points(points) -> bytes:
-    """x || y little-endian per point; an SW identity ((None, None)) packs as 64 zero bytes, as the ABI takes it."""
-    return b"".join((p.x or 0).to_bytes(32, "little") + (p.y or 0).to_bytes(32, "little") for p in points)
+    """x || y little-endian per point; an SW identity ((None, None)) packs as 64 zero bytes, as the ABI takes it, Curve25519's — where
+    (0, 0) is a point — as 64 bytes of 0xff."""
+    return b"".join(p._IDENTITY_BYTES if p.x is None and hasattr(p, "_IDENTITY_BYTES")
+                    else (p.x or 0).to_bytes(32, "little") + (p.y or 0).to_bytes(32, "little") for p in points)
+
+
+def pack_points_flagged(points):
+    """(u || v bytes, identity flag bytes) of Curve25519 points as the dr_curve25519_* entry points take them: the identity is 64 zero
+    bytes with its flag byte 1."""
+    return (b"".join((p.x or 0).to_bytes(32, "little") + (p.y or 0).to_bytes(32, "little") for p in points),
+            bytes(1 if p.is_identity() else 0 for p in points))
+
+
+def unpack_points_flagged(cls, raw: bytes, flags: bytes):
+    """Curve25519 kernel outputs with their identity flags: group elements by construction, no per-point curve check."""
+    frm = int.from_bytes
+    return [cls.identity() if flags[i] else cls._trusted(frm(raw[64 * i : 64 * i + 32], "little"), frm(raw[64 * i + 32 : 64 * i + 64], "little"))
+            for i in range(len(flags))]
 
 
 def pack_scalars(scalars, order: int = _N) -> bytes:
@@ -1067,7 +1252,7 @@ class CurveVariant:
         self.name, self.curve, self.point_type = name, curve, point_type
 
     def point(self, x, y=None):
-        if isinstance(x, (BandersnatchPoint, BandersnatchSWPoint, P256Point, Secp256k1Point)):
+        if isinstance(x, (BandersnatchPoint, BandersnatchSWPoint, P256Point, Secp256k1Point, Curve25519Point)):
             return x
         if y is None:
             x, y = x
@@ -1268,6 +1453,35 @@ def _secp256k1_variant(name: str, e2c: str, curve_id: int) -> CurveVariant:
     curve = BandersnatchCurve(params)
     return CurveVariant(name, curve, type(f"{name}Point", (Secp256k1Point,), {"__slots__": (), "curve": curve, "_CV": curve_id}))
 
+
+# dot_ring/curve/specs/curve25519.py: v^2 = u^3 + 486662 u^2 + u over 2^255 - 19, Ed25519's group (cofactor 8) in Montgomery form, points
+# 64 bytes u || v (point_len 32, uncompressed), SHA-512, hashing to the curve by RFC 9380's curve25519_XMD:SHA-512_ELL2_RO_ (two field
+# elements) or ..._NU_ (one); both variants share the RO suite id and the generator as Pedersen blinding base, as in the reference.  No
+# accumulator base or padding point, and not twisted Edwards, so RingProofParams refuses them.
+_CURVE25519_G = (9, 14781619447589544791020593568409986887264606134616475288964881837755586237401)
+
+
+def _curve25519_variant(name: str, e2c: str, curve_id: int) -> CurveVariant:
+    params = SuiteParams(
+        suite_id=b"curve25519_XMD:SHA-512_ELL2_RO_", hash_fn=hashlib.sha512, xof=False,
+        auxiliary_points=AuxiliaryPoints(_CURVE25519_G, None, None),
+        field_modulus=Curve25519Point._P,
+        subgroup_order=Curve25519Point._N,
+        cofactor=8,
+        a=Curve25519Point._MG_A,
+        d=1,                                       # (the Montgomery B)
+        generator=_CURVE25519_G,
+        encoding=Encoding(point_len=32, uncompressed=True),
+        curve_id=curve_id,
+        e2c=e2c,
+    )
+    curve = BandersnatchCurve(params)
+    return CurveVariant(name, curve, type(f"{name}Point", (Curve25519Point,), {"__slots__": (), "curve": curve, "_CV": curve_id}))
+
+
+Curve25519_RO = _curve25519_variant("Curve25519_RO", "ell2", _native.CURVE_CURVE25519_RO)
+Curve25519_NU = _curve25519_variant("Curve25519_NU", "ell2_nu", _native.CURVE_CURVE25519_NU)
+Curve25519 = Curve25519_RO
 
 Secp256k1_RO = _secp256k1_variant("Secp256k1_RO", "sswu", _native.CURVE_SECP256K1)
 Secp256k1_NU = _secp256k1_variant("Secp256k1_NU", "sswu_nu", _native.CURVE_SECP256K1_NU)

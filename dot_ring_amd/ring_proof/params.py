@@ -80,9 +80,9 @@ class RingProofParams:
     cv: CurveVariant = field(default_factory=lambda: Bandersnatch, compare=False, hash=False)
 
     def __post_init__(self) -> None:
-        short_weierstrass = (_native.CURVE_BANDERSNATCH_SW, _native.CURVE_P256, _native.CURVE_SECP256K1, _native.CURVE_SECP256K1_NU,
-                             _native.CURVE_P256_RO, _native.CURVE_P256_NU)
-        if getattr(self.cv.curve.params, "curve_id", None) in short_weierstrass:   # params.py _validate_curve
+        not_twisted_edwards = (_native.CURVE_BANDERSNATCH_SW, _native.CURVE_P256, _native.CURVE_SECP256K1, _native.CURVE_SECP256K1_NU,
+                               _native.CURVE_P256_RO, _native.CURVE_P256_NU, _native.CURVE_CURVE25519_RO, _native.CURVE_CURVE25519_NU)
+        if getattr(self.cv.curve.params, "curve_id", None) in not_twisted_edwards:   # params.py _validate_curve
             raise ValueError(f"{self.cv.name} ring proofs require a Twisted Edwards curve")
         aux = self.cv.curve.params.auxiliary_points
         missing = [n for n in ("blinding_base", "accumulator_base", "padding_point") if getattr(aux, n) is None]

@@ -16,7 +16,8 @@ def scalar_len(cv) -> int:
 
 
 def point_len(cv) -> int:
-    return cv.curve.params.encoding.point_len
+    encoding = cv.curve.params.encoding
+    return encoding.point_len * (2 if encoding.uncompressed else 1)        # (Curve25519: u || v, 2 x 32 bytes)
 
 
 def enc_64(value: int) -> bytes:

@@ -11,7 +11,7 @@ import os
 from .. import _native, runtime
 from ..curve import msm_groups, scalar_mul_batch
 from .base import VRF
-from .codec import dec_point, dec_scalar_mod
+from .codec import dec_point, dec_scalar_mod, point_len
 from .primitives import VrfIo, challenge, nonce, point_to_hash, vrf_transcript, vrf_transcript_scalars
 
 
@@ -46,7 +46,7 @@ class IetfVRF(VRF):
         bb = sp.auxiliary_points.blinding_base or gen                      # unused by these two schemes
         suite = _native.vrf_suite(sp.suite_id, sp.hash_fn, le(gen[0]) + le(gen[1]), le(bb[0]) + le(bb[1]), sp.curve_id)
         sks = b"".join(bytes(sk) if len(sk) == 32 else le(int.from_bytes(sk, "little") % sp.subgroup_order) for sk in secret_keys)
-        pl = cv.curve.params.encoding.point_len
+        pl = point_len(cv)
         plen = 2 * pl + 32 if cls.THIN else pl + 48
         ctx, make, frm, out = runtime.context(), cv.point_type._trusted, int.from_bytes, []
         for lo in range(0, count, 65536):

@@ -163,6 +163,22 @@ enum { DR_CURVE_SECP256K1 = 6, DR_CURVE_SECP256K1_NU = 7 };
  *                              the cofactor cleared; dr_vrf_suite.xof must be 0.  Encodings are DR_CURVE_ED25519's.
  * The ring prover, the Ring-VRF calls, dr_ietf_verify_batch, the GLV and dr_bsn_* entry points refuse them, as they refuse ids 3, 4, 6, 7. */
 enum { DR_CURVE_P256_RO = 8, DR_CURVE_P256_NU = 9, DR_CURVE_ED25519_RO = 10, DR_CURVE_ED25519_NU = 11 };
+/* Curve25519_RO / Curve25519_NU (the reference's specs/curve25519.py): v^2 = u^3 + 486662 u^2 + u over GF(2^255 - 19), the group of
+ * DR_CURVE_ED25519 in Montgomery form.  Raw points are u || v, 32 little-endian bytes each, and the ENCODING of a point is those same 64
+ * bytes (dr_vrf_suite: point length 64, challenge length 16, xof 0; suite id curve25519_XMD:SHA-512_ELL2_RO_ for both variants, the DST
+ * of the maps QUUX-V01-CS02-with- || suite id with _RO_ replaced by _NU_ for the nonuniform one).  The kernels (csrc/kernels_curve25519.hip.h)
+ * compute on the Ed25519 group law through x = c u / v, y = (u - 1) / (u + 1), c = sqrt(-486664), converting at both ends of each launch.
+ *
+ * THE IDENTITY.  (0, 0) is a point of this curve (the one of order 2), so 64 zero bytes do NOT stand for the identity here, as they do
+ * on the Weierstrass curves.  The identity is carried beside the point:
+ *   - the dr_curve25519_* entry points below take and give one FLAG BYTE per point: 0 = the 64 bytes are the point, 1 = the point is the
+ *     identity (its 64 bytes are ignored on input and zero on output).  The kernels' form of the same flag is one 32-bit word per point.
+ *   - the generic dr_te_* entry points and the dr_*_prove_batch / verify calls, whose points are 64 bytes and nothing else, write the
+ *     identity of these two curve ids as 64 bytes of 0xff: u = v = 2^256 - 1 is no field element, so it is no point.
+ * A proof whose point would be the identity has no encoding (the reference's point_to_string raises): the provers return DR_ERR_INVALID.
+ * The ring prover, the Ring-VRF calls, dr_ietf_verify_batch, the GLV and dr_bsn_* entry points refuse these ids, as they refuse 3 - 11.
+ * Id 12 is not assigned (every entry point answers DR_ERR_INVALID to it). */
+enum { DR_CURVE_CURVE25519_RO = 13, DR_CURVE_CURVE25519_NU = 14 };
 DR_API int dr_te_scalar_mul_batch(dr_ctx *ctx, int curve, const uint8_t *pts_xy, const uint8_t *scalars, size_t n, uint8_t *out_xy);
 DR_API int dr_te_msm(dr_ctx *ctx, int curve, const uint8_t *pts_xy, const uint8_t *scalars, size_t n, uint8_t out_xy[64]);
 DR_API int dr_te_msm_groups(dr_ctx *ctx, int curve, const uint8_t *pts_xy, const uint8_t *scalars, size_t groups, size_t m, uint8_t *out_xy);
@@ -229,6 +245,27 @@ DR_API int dr_p256_map_to_curve(dr_ctx *ctx, const uint8_t *us /* n*per_item*32 
  * fails there and out_xy[i] is meaningless.  Inputs at or above p are refused with DR_ERR_INVALID. */
 DR_API int dr_ed25519_map_to_curve(dr_ctx *ctx, const uint8_t *us /* n*per_item*32 */, size_t n, int per_item, uint8_t *out_xy /* n*64 */,
                                    uint8_t *ok /* n */);
+/* Curve25519 (DR_CURVE_CURVE25519_RO / _NU) with the identity flags spelled out (see the curve ids for their meaning; id_in may be NULL:
+ * no input is the identity).  The flag is the only form of the identity here: a point whose flag is 0 must have both coordinates below
+ * p, so 64 bytes of 0xff — the identity of the generic dr_te_* entry points — are refused with DR_ERR_INVALID like any other
+ * non-canonical coordinate.  Scalars are reduced mod l on the device and go through the fixed schedule of the other native suites.
+ *   dr_curve25519_scalar_mul_batch  out[i] = k[i] P[i]
+ *   dr_curve25519_msm_groups        out[g] = sum_{j<m} k[g m + j] P[g m + j], m <= 64
+ *   dr_curve25519_decode_points     one 64-byte u || v per point: ok[i] = 1 iff u < p, v < p and the curve equation holds (check = 0: all
+ *                                   the reference's string_to_point asks, so (0, 0) and the other small-order points pass) and, with
+ *                                   check = 1, the point is also a non-identity point of the prime-order subgroup (the VRF layer's
+ *                                   dec_point; dr_te_decode_points for these ids).  out_uv[i] = the point, or 64 zero bytes.
+ *   dr_curve25519_map_to_curve      RFC 9380 curve25519_XMD:SHA-512_ELL2_RO_ / _NU_ after hash_to_field: the sum of the Elligator 2 images
+ *                                   of item i's per_item (2 or 1) elements, times the cofactor 8 unless clear_cofactor = 0.  Every element
+ *                                   below p has an image (0 maps to (0, 0)): there is no error flag; elements at or above p are refused. */
+DR_API int dr_curve25519_scalar_mul_batch(dr_ctx *ctx, const uint8_t *pts_uv /* n*64 */, const uint8_t *id_in /* n or NULL */,
+                                          const uint8_t *scalars /* n*32 */, size_t n, uint8_t *out_uv /* n*64 */, uint8_t *id_out /* n */);
+DR_API int dr_curve25519_msm_groups(dr_ctx *ctx, const uint8_t *pts_uv /* groups*m*64 */, const uint8_t *id_in /* groups*m or NULL */,
+                                    const uint8_t *scalars /* groups*m*32 */, size_t groups, size_t m, uint8_t *out_uv /* groups*64 */,
+                                    uint8_t *id_out /* groups */);
+DR_API int dr_curve25519_decode_points(dr_ctx *ctx, int check, const uint8_t *enc /* n*64 */, size_t n, uint8_t *out_uv /* n*64 */, uint8_t *ok /* n */);
+DR_API int dr_curve25519_map_to_curve(dr_ctx *ctx, const uint8_t *us /* n*per_item*32 */, size_t n, int per_item, int clear_cofactor,
+                                      uint8_t *out_uv /* n*64 */, uint8_t *id_out /* n */);
 /* Baby JubJub point decoding with the prime-order check (check = 1: as dr_te_decode_points for DR_CURVE_BABYJUBJUB) or the codec
  * alone (check = 0: y < p and a root; (0, 1) and (0, p - 1) decode whatever the sign bit).  ok[i] = 1 when accepted; out_xy[i] is
  * then x || y, otherwise 64 zero bytes. */
