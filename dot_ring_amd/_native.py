@@ -78,6 +78,8 @@ _PROTOTYPES = {
     "dr_ring_prover_residue": (c_int, [c_void_p, POINTER(ctypes.c_uint64)]),
     "dr_ntt": (c_int, [c_void_p, c_void_p, c_uint, c_size_t, c_char_p, c_char_p]),
     "dr_ntt_dev": (c_int, [c_void_p, c_void_p, c_uint, c_size_t, c_char_p, c_char_p]),
+    "dr_ntt_formats_selftest": (c_int, [c_void_p, c_char_p, c_size_t, c_char_p, c_size_t, c_char_p, c_size_t, c_uint, c_size_t, c_char_p,
+                                        c_char_p, c_int, c_int, c_int, ctypes.c_uint32, c_void_p]),
 }
 
 
@@ -202,6 +204,8 @@ def _ragged(items):
     return b"".join(items), (ctypes.c_uint64 * len(off)).from_buffer(off)
 
 
+# element formats of dr_ntt_formats_selftest (csrc/kernels_ntt.hip.h)
+NTT_FMT_STD8, NTT_FMT_FS9, NTT_FMT_STD8_SCALED, NTT_FMT_FS9_COSETS = 0, 1, 2, 3
 CURVE_BANDERSNATCH, CURVE_JUBJUB, CURVE_BANDERSNATCH_SW, CURVE_ED25519, CURVE_P256, CURVE_BABYJUBJUB = 0, 1, 2, 3, 4, 5
 CURVE_SECP256K1, CURVE_SECP256K1_NU = 6, 7
 CURVE_P256_RO, CURVE_P256_NU, CURVE_ED25519_RO, CURVE_ED25519_NU = 8, 9, 10, 11
@@ -910,6 +914,20 @@ class Context:
     def ntt_dev(self, d_data: DeviceBuffer, log2n: int, batch: int, omega: int, scale: int | None = None) -> None:
         sc = scale.to_bytes(32, "little") if scale is not None else None
         _check(lib().dr_ntt_dev(self.handle, d_data.ptr, log2n, batch, omega.to_bytes(32, "little"), sc))
+
+    def ntt_formats_selftest(self, src: bytes, log2n: int, batch: int, omega: int, scale: int | None = None, fmt_in: int = NTT_FMT_STD8,
+                             fmt_out: int = NTT_FMT_STD8, pad: int = 0, src_div: int = 1, in_scale: bytes | None = None,
+                             special: bytes | None = None) -> bytes:
+        """dr_ntt_formats_selftest: `batch` transforms of raw records in the ring prover's element formats (NTT_FMT_*; words are
+        little-endian 32-bit) -> batch * 2^log2n raw records of fmt_out (8 words STD8, 9 limbs FS9)."""
+        if len(src) % 4 or (in_scale is not None and len(in_scale) % 4) or (special is not None and len(special) % 4):
+            raise ValueError("records are whole 32-bit words")
+        sc = scale.to_bytes(32, "little") if scale is not None else None
+        out = ctypes.create_string_buffer(max(1, (batch << log2n) * (36 if fmt_out == NTT_FMT_FS9 else 32)))
+        _check(lib().dr_ntt_formats_selftest(self.handle, src, len(src) // 4, in_scale, len(in_scale) // 4 if in_scale is not None else 0,
+                                             special, len(special) // 4 if special is not None else 0, log2n, batch,
+                                             omega.to_bytes(32, "little"), sc, fmt_in, fmt_out, pad, src_div, out))
+        return out.raw[: (batch << log2n) * (36 if fmt_out == NTT_FMT_FS9 else 32)]
 
 
 # ---- host-only helpers (no GPU needed)

@@ -35,6 +35,65 @@ int dr_ntt(dr_ctx* ctx, uint8_t* data, unsigned log2n, size_t batch, const uint8
     return DR_OK;
 }
 
+// Diagnostic: dr::ntt_run in the prover's element formats on caller-supplied raw buffers (the call ring_ntt makes: same launch
+// wrapper, same scratch, always a separate source).  The buffer sizes are checked against what the kernels will read; which
+// combinations of format, size and padding are admitted is ntt_run's own decision, taken before anything is launched.
+int dr_ntt_formats_selftest(dr_ctx* ctx, const uint32_t* src, size_t src_words, const uint32_t* in_scale, size_t in_scale_words,
+                            const uint32_t* special, size_t special_words, unsigned log2n, size_t batch, const uint8_t omega[32],
+                            const uint8_t* scale, int fmt_in, int fmt_out, int pad, uint32_t src_div, uint32_t* out) {
+    TRY(use_ctx(ctx));
+    if (!src || !out || !omega) return fail(DR_ERR_INVALID, "null buffer");
+    if (log2n < 1 || log2n > 24) return fail(DR_ERR_INVALID, "native NTT plan size must be a power of two >= 2");
+    if (batch == 0 || batch > 65535) return fail(DR_ERR_INVALID, "1 to 65535 transforms per call");
+    if (fmt_in < dr::NTT_FMT_STD8 || fmt_in > dr::NTT_FMT_FS9_COSETS || (fmt_out != dr::NTT_FMT_STD8 && fmt_out != dr::NTT_FMT_FS9))
+        return fail(DR_ERR_INVALID, "unknown element format");
+    if (pad < 0 || pad > dr::NTT_LOG_TILE || (unsigned)pad >= log2n) return fail(DR_ERR_INVALID, "padding exceeds the first pass");
+    const size_t n = (size_t)1 << log2n, n_src = n >> pad, div = src_div ? src_div : 1;
+    size_t want_src = 0, want_scale = 0, want_special = 0;
+    if (fmt_in == dr::NTT_FMT_STD8) want_src = batch * n_src * 8;
+    if (fmt_in == dr::NTT_FMT_FS9) want_src = batch * n_src * dr::L29;
+    if (fmt_in == dr::NTT_FMT_STD8_SCALED) {
+        if (batch % div) return fail(DR_ERR_INVALID, "transforms must be a multiple of src_div");
+        want_src = batch / div * n_src * 8;
+        want_scale = div * n_src * dr::L29;
+    }
+    if (fmt_in == dr::NTT_FMT_FS9_COSETS) {
+        want_src = batch * 3 * (n_src >> 2) * dr::L29;
+        want_special = batch * 3 * dr::L29;
+    }
+    if (src_words != want_src || (in_scale && in_scale_words != want_scale) || (special && special_words != want_special))
+        return fail(DR_ERR_INVALID, "buffer size does not match the format");
+    drh::Fr w, sc;
+    if (!drh::Fr::load_le(w, omega)) return fail(DR_ERR_INVALID, "omega is not a canonical field element");
+    if (scale && !drh::Fr::load_le(sc, scale)) return fail(DR_ERR_INVALID, "scale is not a canonical field element");
+    struct Owned {
+        Scratch s;
+        ~Owned() { s.release(); }
+    } d_scale, d_special;
+    const size_t out_bytes = batch * n * (fmt_out == dr::NTT_FMT_FS9 ? dr::L29 : 8) * 4;
+    TRY(ctx->io_a.reserve(src_words * 4));
+    TRY(ctx->io_c.reserve(out_bytes));
+    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, src, src_words * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (in_scale) {
+        TRY(d_scale.s.reserve(in_scale_words * 4));
+        HIP_TRY(hipMemcpyAsync(d_scale.s.p, in_scale, in_scale_words * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (special) {
+        TRY(d_special.s.reserve(special_words * 4));
+        HIP_TRY(hipMemcpyAsync(d_special.s.p, special, special_words * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    int rc = dr::ntt_run(ctx->stream, [&](const char* name, auto&& f) { return launch(ctx, name, f); }, ctx->twiddles, ctx->io_b,
+                         ctx->io_c.as<uint32_t>(), log2n, batch, w, scale ? &sc : nullptr,
+                         [&]() -> int { HIP_TRY(hipStreamSynchronize(ctx->stream)); if (ctx->prof) TRY(prof_collect(ctx)); return DR_OK; },
+                         fmt_in, fmt_out, ctx->io_a.as<uint32_t>(), pad, src_div, in_scale ? d_scale.s.as<uint32_t>() : nullptr,
+                         special ? d_special.s.as<uint32_t>() : nullptr);
+    HIP_TRY(hipStreamSynchronize(ctx->stream));       // the uploads, whatever ntt_run decided
+    if (rc == DR_ERR_INVALID) return fail(rc, "NTT refused: format, size or padding outside what the kernels cover");
+    if (rc != DR_OK) return rc;
+    HIP_TRY(hipMemcpy(out, ctx->io_c.p, out_bytes, hipMemcpyDeviceToHost));
+    return DR_OK;
+}
+
 // ------------------------------------------------------------------------------- batched ring prover
 struct dr_ring_prover {
     dr_ctx* ctx = nullptr;

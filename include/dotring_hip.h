@@ -392,6 +392,23 @@ DR_API int dr_g1_ops_selftest(dr_ctx *ctx, const uint32_t *in /* n*192 */, size_
  */
 DR_API int dr_ntt(dr_ctx *ctx, uint8_t *data, unsigned log2n, size_t batch, const uint8_t omega[32], const uint8_t *scale);
 DR_API int dr_ntt_dev(dr_ctx *ctx, void *d_data, unsigned log2n, size_t batch, const uint8_t omega[32], const uint8_t *scale);
+/* Diagnostic: the same transform in the ring prover's internal element formats, on RAW caller-supplied records, so that tests can
+ * place operands on the edges of what each format admits.  Formats (fmt_in 0..3, fmt_out 0 or 1):
+ *   0 STD8         8 little-endian words of the canonical value
+ *   1 FS9          9 signed 32-bit limbs l_i, v = sum l_i 2^(29 i), standing for v 2^-261 mod p; as input: limbs 0..7 within
+ *                  (-2^30, 2^30 + 2^29) and |v| < 3.3 p; as output: v = x 2^261 scale mod p in normal form with a scale, without
+ *                  one limbs 0..7 in [0, 2^29) and |v| < 0.51 p
+ *   2 STD8_SCALED  input only: transform x reads STD8 vector x / src_div of `src` and multiplies element i by record i of table
+ *                  x % src_div of `in_scale` (src_div tables of FS9 records holding s R^2, R = 2^261)
+ *   3 FS9_COSETS   input only: point idx of the vector is coset idx % 4, row idx / 4; `src` holds cosets 1..3 coset-major
+ *                  ([transform][coset - 1][row], FS9), coset 0 is zero except its last three rows, `special` ([transform][3], FS9)
+ * src holds 2^(log2n - pad) elements per source vector (zero-padded to 2^log2n in effect) and is never overwritten; out receives
+ * batch * 2^log2n records of fmt_out.  omega and scale (NULL: none) as for dr_ntt.  The word counts must match the format exactly.
+ * DR_ERR_INVALID, with nothing launched, for what the kernels do not cover: FS9 / FS9_COSETS input or FS9 output without a scale
+ * above log2n = 16, FS9_COSETS below log2n = 4 or without `special`, STD8_SCALED without `in_scale` or with pad != 0. */
+DR_API int dr_ntt_formats_selftest(dr_ctx *ctx, const uint32_t *src, size_t src_words, const uint32_t *in_scale, size_t in_scale_words,
+                                   const uint32_t *special, size_t special_words, unsigned log2n, size_t batch, const uint8_t omega[32],
+                                   const uint8_t *scale, int fmt_in, int fmt_out, int pad, uint32_t src_div, uint32_t *out);
 
 /* ---- batched ring prover ---------------------------------------------------------------------------
  * Device-resident prover for MANY proofs over ONE ring (additive API): replaces the interpreted loops of
