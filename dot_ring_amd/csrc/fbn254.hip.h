@@ -8,6 +8,10 @@
 // so a product is 81 column products plus 81 reduction products — the count fr29.hip.h's Montgomery product has.  This header is
 // separate from fr29.hip.h (not a template parameter of it) so that no existing kernel's code changes.
 //
+// The element type, the limb-wise operations, the column products over reduce() below, the word layout and the predicates on the
+// canonical words are limb29.hip.h's (shared with the other 9 x 29 fields, not with fr29.hip.h); this header holds the constants, the
+// Montgomery step, carry, the canonicalisation of pack and the exponentiation.
+//
 // Value of an element: sum l[i] 2^(29 i), limbs SIGNED; the element it stands for is that value times R^-1 mod p.
 // Reduction of a product (columns c_0..c_16, int64): nine steps k = 0..8 take m from c_k, add m P_j to c_(k+j) (j = 0..8), and carry
 // c_k >> 29 (exact) into c_(k+1); the result is c_9..c_16 carried into 9 limbs.  Its value is T = (a b + M p) / 2^261 with
@@ -25,29 +29,9 @@
 //   pack(a)   : limbs below 2^30 in magnitude, |value| < 2^263 -> the canonical element in [0, p) as 8 little-endian words
 //   unpack(w) : 8 words (any value below 2^256) -> the element w in Montgomery form, normal
 #pragma once
-#include "field.hip.h"
+#include "limb29.hip.h"
 
 namespace dr {
-
-constexpr int BN_L = 9;
-constexpr uint32_t BN_M29 = 0x1fffffffu;
-
-struct Fbn {                          // an element of the BN254 scalar field in Montgomery form, signed 29-bit limbs
-    int32_t l[BN_L];
-    DR_DEV static Fbn zero() {
-        Fbn r;
-#pragma unroll
-        for (int i = 0; i < BN_L; i++) r.l[i] = 0;
-        return r;
-    }
-    template <const uint32_t (&C)[9]>
-    DR_DEV static Fbn constant() {
-        Fbn r;
-#pragma unroll
-        for (int i = 0; i < BN_L; i++) r.l[i] = (int32_t)C[i];
-        return r;
-    }
-};
 
 struct FbnConsts {
     // p, R mod p (the Montgomery one), R^2 mod p and the curve's d R mod p, in 29-bit limbs
@@ -59,175 +43,75 @@ struct FbnConsts {
     static constexpr uint32_t PW[8] = {0xf0000001u, 0x43e1f593u, 0x79b97091u, 0x2833e848u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
     static constexpr uint32_t HALF_P[8] = {0xf8000000u, 0xa1f0fac9u, 0x3cdcb848u, 0x9419f424u, 0x40c0ac2eu, 0xdc2822dbu, 0x7098d014u, 0x18322739u};
     static constexpr uint32_t PM2[8] = {0xefffffffu, 0x43e1f593u, 0x79b97091u, 0x2833e848u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
+    DR_DEV static Limb29<FbnConsts> reduce(int64_t (&c)[17]);
+    DR_DEV static void pack(const Limb29<FbnConsts>& a, uint32_t (&w)[8]);
 };
+using Fbn = Limb29<FbnConsts>;         // an element of the BN254 scalar field in Montgomery form, signed 29-bit limbs
 
 DR_DEV Fbn bn_one() { return Fbn::constant<FbnConsts::ONE>(); }
-
-DR_DEV Fbn add(const Fbn& a, const Fbn& b) {
-    Fbn r;
-#pragma unroll
-    for (int i = 0; i < BN_L; i++) r.l[i] = a.l[i] + b.l[i];
-    return r;
-}
-DR_DEV Fbn sub(const Fbn& a, const Fbn& b) {
-    Fbn r;
-#pragma unroll
-    for (int i = 0; i < BN_L; i++) r.l[i] = a.l[i] - b.l[i];
-    return r;
-}
-DR_DEV Fbn dbl(const Fbn& a) { return add(a, a); }
-DR_DEV Fbn neg(const Fbn& a) {
-    Fbn r;
-#pragma unroll
-    for (int i = 0; i < BN_L; i++) r.l[i] = -a.l[i];
-    return r;
-}
-DR_DEV Fbn cneg(const Fbn& a, bool negate) {
-    const int32_t s = negate ? -1 : 0;
-    Fbn r;
-#pragma unroll
-    for (int i = 0; i < BN_L; i++) r.l[i] = (a.l[i] ^ s) - s;
-    return r;
-}
-DR_DEV Fbn select(bool c, const Fbn& a, const Fbn& b) {
-    Fbn r;
-#pragma unroll
-    for (int i = 0; i < BN_L; i++) r.l[i] = c ? a.l[i] : b.l[i];
-    return r;
-}
 
 // limbs 0..7 into [0, 2^29), the rest into limb 8 (signed)
 DR_DEV Fbn carry(const Fbn& a) {
     Fbn r;
     int32_t c = 0;
 #pragma unroll
-    for (int i = 0; i < BN_L - 1; i++) {
+    for (int i = 0; i < LIMBS29 - 1; i++) {
         const int32_t t = a.l[i] + c;
-        r.l[i] = t & (int32_t)BN_M29;
+        r.l[i] = t & (int32_t)MASK29;
         c = t >> 29;
     }
-    r.l[BN_L - 1] = a.l[BN_L - 1] + c;
+    r.l[LIMBS29 - 1] = a.l[LIMBS29 - 1] + c;
     return r;
 }
 
 // columns c_0..c_16 -> (sum c_k 2^(29 k)) / 2^261 mod p, carried (the Montgomery reduction of the header)
-DR_DEV Fbn bn_redc(int64_t (&c)[17]) {
+DR_DEV Fbn FbnConsts::reduce(int64_t (&c)[17]) {
 #pragma unroll
-    for (int k = 0; k < BN_L; k++) {
+    for (int k = 0; k < LIMBS29; k++) {
         const uint32_t t = (uint32_t)c[k];
-        const int64_t m = (int64_t)((0u - t - (t << 28)) & BN_M29);      // -c_k p^-1 mod 2^29
+        const int64_t m = (int64_t)((0u - t - (t << 28)) & MASK29);      // -c_k p^-1 mod 2^29
 #pragma unroll
-        for (int j = 0; j < BN_L; j++) c[k + j] += m * (int64_t)FbnConsts::P[j];
+        for (int j = 0; j < LIMBS29; j++) c[k + j] += m * (int64_t)FbnConsts::P[j];
         c[k + 1] += c[k] >> 29;                                          // c_k is now a multiple of 2^29
     }
     Fbn r;
     int64_t u = c[9];
 #pragma unroll
-    for (int k = 0; k < BN_L - 2; k++) {
-        r.l[k] = (int32_t)((uint32_t)u & BN_M29);
+    for (int k = 0; k < LIMBS29 - 2; k++) {
+        r.l[k] = (int32_t)((uint32_t)u & MASK29);
         u = c[10 + k] + (u >> 29);
     }
-    r.l[BN_L - 2] = (int32_t)((uint32_t)u & BN_M29);
-    r.l[BN_L - 1] = (int32_t)(u >> 29);
+    r.l[LIMBS29 - 2] = (int32_t)((uint32_t)u & MASK29);
+    r.l[LIMBS29 - 1] = (int32_t)(u >> 29);
     return r;
-}
-
-DR_DEV Fbn mul(const Fbn& a, const Fbn& b) {
-    int64_t c[17];
-#pragma unroll
-    for (int k = 0; k < 17; k++) c[k] = 0;
-#pragma unroll
-    for (int i = 0; i < BN_L; i++)
-#pragma unroll
-        for (int j = 0; j < BN_L; j++) c[i + j] += (int64_t)a.l[i] * (int64_t)b.l[j];
-    return bn_redc(c);
-}
-DR_DEV Fbn sqr(const Fbn& a) {
-    int32_t d[BN_L];
-#pragma unroll
-    for (int i = 0; i < BN_L; i++) d[i] = 2 * a.l[i];
-    int64_t c[17];
-#pragma unroll
-    for (int k = 0; k < 17; k++) c[k] = 0;
-#pragma unroll
-    for (int i = 0; i < BN_L; i++) {
-        c[2 * i] += (int64_t)a.l[i] * (int64_t)a.l[i];
-#pragma unroll
-        for (int j = i + 1; j < BN_L; j++) c[i + j] += (int64_t)d[i] * (int64_t)a.l[j];
-    }
-    return bn_redc(c);
-}
-DR_DEV Fbn mul2(const Fbn& a, const Fbn& b, const Fbn& x, const Fbn& y) {     // a b + x y, one reduction
-    int64_t c[17];
-#pragma unroll
-    for (int k = 0; k < 17; k++) c[k] = 0;
-#pragma unroll
-    for (int i = 0; i < BN_L; i++)
-#pragma unroll
-        for (int j = 0; j < BN_L; j++) {
-            c[i + j] += (int64_t)a.l[i] * (int64_t)b.l[j];
-            c[i + j] += (int64_t)x.l[i] * (int64_t)y.l[j];
-        }
-    return bn_redc(c);
 }
 
 // ---------------------------------------------------------------- 8 x u32 words <-> limbs
 // the limbs of w as they are (w already in Montgomery form, as the per-context tables are)
-DR_DEV Fbn bn_unpack_raw(const uint32_t (&w)[8]) {
-    Fbn r;
-#pragma unroll
-    for (int i = 0; i < BN_L; i++) {
-        const int bit = 29 * i, j = bit >> 5, sh = bit & 31;
-        uint32_t v = w[j] >> sh;
-        if (sh > 3 && j + 1 < 8) v |= w[j + 1] << (32 - sh);
-        r.l[i] = (int32_t)(i < BN_L - 1 ? v & BN_M29 : v);
-    }
-    return r;
-}
+DR_DEV Fbn bn_unpack_raw(const uint32_t (&w)[8]) { return limbs_of_words<FbnConsts>(w); }
 DR_DEV Fbn bn_unpack(const uint32_t (&w)[8]) { return mul(bn_unpack_raw(w), Fbn::constant<FbnConsts::R2>()); }   // w R mod p
-// canonical little-endian words of the element a stands for (a R^-1 mod p)
-DR_DEV void bn_pack(const Fbn& a, uint32_t (&w)[8]) {
+// canonical little-endian words of the element a stands for (a R^-1 mod p); the layout loop is limb29.hip.h's words_of_limbs, kept in
+// place as in fp256.hip.h
+DR_DEV void FbnConsts::pack(const Fbn& a, uint32_t (&w)[8]) {
     int64_t c[17];
 #pragma unroll
-    for (int k = 0; k < 17; k++) c[k] = k < BN_L ? (int64_t)a.l[k] : 0;
+    for (int k = 0; k < 17; k++) c[k] = k < LIMBS29 ? (int64_t)a.l[k] : 0;
     // |value| < 2^263: T = (value + M p) / 2^261 lies in (-4, p + 4) — one conditional addition and one subtraction of p
-    Fbn t = bn_redc(c);
-    const bool negative = t.l[BN_L - 1] < 0;
+    Fbn t = reduce(c);
+    const bool negative = t.l[LIMBS29 - 1] < 0;
     t = carry(select(negative, add(t, Fbn::constant<FbnConsts::P>()), t));
 #pragma unroll
     for (int j = 0; j < 8; j++) w[j] = 0;
 #pragma unroll
-    for (int i = 0; i < BN_L; i++) {
+    for (int i = 0; i < LIMBS29; i++) {
         const uint32_t u = (uint32_t)t.l[i];
         const int bit = 29 * i, j = bit >> 5, sh = bit & 31;
         w[j] |= u << sh;
         if (sh > 3 && j + 1 < 8) w[j + 1] |= u >> (32 - sh);
     }
-    uint32_t d[8], borrow = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) d[j] = subb(w[j], FbnConsts::PW[j], borrow);
-    const bool ge = borrow == 0;                       // w >= p
-#pragma unroll
-    for (int j = 0; j < 8; j++) w[j] = ge ? d[j] : w[j];
+    sub_p_if_ge<FbnConsts>(w);
 }
-DR_DEV bool bn_is_zero(const Fbn& a) {
-    uint32_t w[8];
-    bn_pack(a, w);
-    uint32_t o = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) o |= w[j];
-    return o == 0;
-}
-DR_DEV bool bn_equal(const Fbn& a, const Fbn& b) { return bn_is_zero(sub(a, b)); }
-// x > p - x for the canonical x: the reference's sign rule (x > -x % p)
-DR_DEV bool bn_is_larger(const Fbn& a) {
-    uint32_t w[8];
-    bn_pack(a, w);
-    uint32_t borrow = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) (void)subb(FbnConsts::HALF_P[j], w[j], borrow);
-    return borrow != 0;                              // (p - 1) / 2 - x < 0
-}
+DR_DEV void bn_pack(const Fbn& a, uint32_t (&w)[8]) { FbnConsts::pack(a, w); }
 
 // ---------------------------------------------------------------- exponentiations: a fixed schedule, the same in every lane
 // a^e for an exponent the same in every lane (a constant): left to right with 3-bit sliding windows over a, a^3, a^5, a^7 —
@@ -253,7 +137,7 @@ DR_DEV Fbn bn_pow(const Fbn& a, const uint32_t (&e)[8]) {
         }
         Fbn m;
 #pragma unroll
-        for (int t = 0; t < BN_L; t++) m.l[t] = v == 1 ? a.l[t] : v == 3 ? a3.l[t] : v == 5 ? a5.l[t] : a7.l[t];
+        for (int t = 0; t < LIMBS29; t++) m.l[t] = v == 1 ? a.l[t] : v == 3 ? a3.l[t] : v == 5 ? a5.l[t] : a7.l[t];
         r = started ? mul(r, m) : m;
         started = true;
         i -= l;

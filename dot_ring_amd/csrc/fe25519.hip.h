@@ -8,6 +8,9 @@
 // v_mad_u64_u32 for the fold), sqr 115 (45 + 10), mul2 (a b + c d, one reduction) 245, carry 33.  fr29.hip.h's Montgomery
 // product is 206 / 178 / 287: the fold by 1216 replaces the 81 multiply-adds of a Montgomery reduction.
 //
+// The element type, the limb-wise operations, the column products over reduce() below, the word layout and the predicates on the
+// canonical words are limb29.hip.h's; this header holds the constants, the fold, carry, the canonicalisation of pack and the chains.
+//
 // Value of an element: sum l[i] 2^(29 i), limbs SIGNED.  Reduction of a product: columns c_0..c_16 (int64), the high columns
 // carried into 29-bit digits h_0..h_7 and a top carry t; c_k += 1216 h_k (2^261 = 2^6 19 = 1216 mod p), c_8 += 1216 t; one carry
 // chain over c_0..c_8; the bits of c_8 from 23 up (>= 2^255) come back into limb 0 times 19, and that limb's carry into limb 1.
@@ -25,35 +28,11 @@
 //               [p, 2^255) — the 19 values just below 2^255 — and negative values are reduced)
 //   unpack(w) : 8 words (any value below 2^256) -> limbs 0..7 in [0, 2^29), limb 8 < 2^24: a valid operand of every operation
 #pragma once
-#include "field.hip.h"
+#include "limb29.hip.h"
 
 namespace dr {
 
-constexpr int FE_L = 9;
-constexpr uint32_t FE_M29 = 0x1fffffffu;
 constexpr uint32_t FE_M23 = 0x007fffffu;
-
-struct F25 {                          // an element of GF(2^255 - 19) in signed 29-bit limbs
-    int32_t l[FE_L];
-    DR_DEV static F25 zero() {
-        F25 r;
-#pragma unroll
-        for (int i = 0; i < FE_L; i++) r.l[i] = 0;
-        return r;
-    }
-    DR_DEV static F25 one() {
-        F25 r = zero();
-        r.l[0] = 1;
-        return r;
-    }
-    template <const uint32_t (&C)[9]>
-    DR_DEV static F25 constant() {
-        F25 r;
-#pragma unroll
-        for (int i = 0; i < FE_L; i++) r.l[i] = (int32_t)C[i];
-        return r;
-    }
-};
 
 struct Fe25519Consts {
     // d = -121665 / 121666 and sqrt(-1) = 2^((p-1)/4), in 29-bit limbs
@@ -61,59 +40,35 @@ struct Fe25519Consts {
     static constexpr uint32_t SQRT_M1[9] = {0x0a0ea0b0u, 0x0770d93au, 0x0bf91e31u, 0x06300d5au, 0x1d7a72f4u, 0x004c9efdu, 0x1c2cad34u, 0x1009f83bu, 0x002b8324u};
     // (p - 1) / 2 = 2^254 - 10, little-endian words: x is "the larger root" iff x > (p - 1) / 2
     static constexpr uint32_t HALF_P[8] = {0xfffffff6u, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0x3fffffffu};
+    DR_DEV static Limb29<Fe25519Consts> reduce(int64_t (&c)[17]);
+    DR_DEV static void pack(const Limb29<Fe25519Consts>& a, uint32_t (&w)[8]);
 };
-
-DR_DEV F25 add(const F25& a, const F25& b) {
-    F25 r;
-#pragma unroll
-    for (int i = 0; i < FE_L; i++) r.l[i] = a.l[i] + b.l[i];
-    return r;
-}
-DR_DEV F25 sub(const F25& a, const F25& b) {
-    F25 r;
-#pragma unroll
-    for (int i = 0; i < FE_L; i++) r.l[i] = a.l[i] - b.l[i];
-    return r;
-}
-DR_DEV F25 dbl(const F25& a) { return add(a, a); }
-DR_DEV F25 neg(const F25& a) {
-    F25 r;
-#pragma unroll
-    for (int i = 0; i < FE_L; i++) r.l[i] = -a.l[i];
-    return r;
-}
-DR_DEV F25 cneg(const F25& a, bool negate) {
-    const int32_t s = negate ? -1 : 0;
-    F25 r;
-#pragma unroll
-    for (int i = 0; i < FE_L; i++) r.l[i] = (a.l[i] ^ s) - s;
-    return r;
-}
+using F25 = Limb29<Fe25519Consts>;     // an element of GF(2^255 - 19) in signed 29-bit limbs
 
 // limbs 0..7 into [0, 2^29); bits 255 and up of limb 8 folded into limb 0 times 19, its carry into limb 1
 DR_DEV F25 carry(const F25& a) {
     F25 r;
     int32_t c = 0;
 #pragma unroll
-    for (int i = 0; i < FE_L - 1; i++) {
+    for (int i = 0; i < LIMBS29 - 1; i++) {
         const int32_t t = a.l[i] + c;
-        r.l[i] = t & (int32_t)FE_M29;
+        r.l[i] = t & (int32_t)MASK29;
         c = t >> 29;
     }
-    const int32_t top = a.l[FE_L - 1] + c;
-    r.l[FE_L - 1] = top & (int32_t)FE_M23;
+    const int32_t top = a.l[LIMBS29 - 1] + c;
+    r.l[LIMBS29 - 1] = top & (int32_t)FE_M23;
     const int32_t v = r.l[0] + 19 * (top >> 23);
-    r.l[0] = v & (int32_t)FE_M29;
+    r.l[0] = v & (int32_t)MASK29;
     r.l[1] += v >> 29;
     return r;
 }
 
 // columns c_0..c_16 of a product (|c_k| < 2^63 - 2^41) -> a normal element
-DR_DEV F25 fe_reduce(int64_t (&c)[17]) {
+DR_DEV F25 Fe25519Consts::reduce(int64_t (&c)[17]) {
     int64_t t = c[9];
 #pragma unroll
     for (int k = 0; k < 8; k++) {                    // high columns -> 29-bit digits; digit k has weight 2^(29 (k + 9)) = 1216 2^(29 k)
-        const uint32_t h = (uint32_t)t & FE_M29;
+        const uint32_t h = (uint32_t)t & MASK29;
         t = (t >> 29) + (k < 7 ? c[10 + k] : 0);
         c[k] += (int64_t)((uint64_t)h * 1216u);
     }
@@ -122,132 +77,54 @@ DR_DEV F25 fe_reduce(int64_t (&c)[17]) {
     int64_t u = c[0];
 #pragma unroll
     for (int k = 0; k < 8; k++) {
-        r.l[k] = (int32_t)((uint32_t)u & FE_M29);
+        r.l[k] = (int32_t)((uint32_t)u & MASK29);
         u = c[k + 1] + (u >> 29);
     }
     r.l[8] = (int32_t)((uint32_t)u & FE_M23);
     const int64_t v = (int64_t)r.l[0] + (u >> 23) * 19;
-    r.l[0] = (int32_t)((uint32_t)v & FE_M29);
+    r.l[0] = (int32_t)((uint32_t)v & MASK29);
     r.l[1] += (int32_t)(v >> 29);
     return r;
 }
 
-DR_DEV F25 mul(const F25& a, const F25& b) {
-    int64_t c[17];
-#pragma unroll
-    for (int k = 0; k < 17; k++) c[k] = 0;
-#pragma unroll
-    for (int i = 0; i < FE_L; i++)
-#pragma unroll
-        for (int j = 0; j < FE_L; j++) c[i + j] += (int64_t)a.l[i] * (int64_t)b.l[j];
-    return fe_reduce(c);
-}
-DR_DEV F25 sqr(const F25& a) {
-    int32_t d[FE_L];
-#pragma unroll
-    for (int i = 0; i < FE_L; i++) d[i] = 2 * a.l[i];
-    int64_t c[17];
-#pragma unroll
-    for (int k = 0; k < 17; k++) c[k] = 0;
-#pragma unroll
-    for (int i = 0; i < FE_L; i++) {
-        c[2 * i] += (int64_t)a.l[i] * (int64_t)a.l[i];
-#pragma unroll
-        for (int j = i + 1; j < FE_L; j++) c[i + j] += (int64_t)d[i] * (int64_t)a.l[j];
-    }
-    return fe_reduce(c);
-}
-DR_DEV F25 mul2(const F25& a, const F25& b, const F25& x, const F25& y) {      // a b + x y, one reduction
-    int64_t c[17];
-#pragma unroll
-    for (int k = 0; k < 17; k++) c[k] = 0;
-#pragma unroll
-    for (int i = 0; i < FE_L; i++)
-#pragma unroll
-        for (int j = 0; j < FE_L; j++) {
-            c[i + j] += (int64_t)a.l[i] * (int64_t)b.l[j];
-            c[i + j] += (int64_t)x.l[i] * (int64_t)y.l[j];
-        }
-    return fe_reduce(c);
-}
-DR_DEV F25 sqr_n(F25 a, int n) {                       // a^(2^n)
-#pragma unroll 1
-    for (int i = 0; i < n; i++) a = sqr(a);
-    return a;
-}
-
 // ---------------------------------------------------------------- 8 x u32 words <-> limbs
-DR_DEV F25 fe_unpack(const uint32_t (&w)[8]) {
-    F25 r;
-#pragma unroll
-    for (int i = 0; i < FE_L; i++) {
-        const int bit = 29 * i, j = bit >> 5, sh = bit & 31;
-        uint32_t v = w[j] >> sh;
-        if (sh > 3 && j + 1 < 8) v |= w[j + 1] << (32 - sh);
-        r.l[i] = (int32_t)(v & FE_M29);
-    }
-    return r;
-}
+DR_DEV F25 fe_unpack(const uint32_t (&w)[8]) { return limbs_of_words<Fe25519Consts>(w); }
 // canonical little-endian words of a (limbs below 2^30 in magnitude)
-DR_DEV void fe_pack(const F25& a, uint32_t (&w)[8]) {
+DR_DEV void Fe25519Consts::pack(const F25& a, uint32_t (&w)[8]) {
     // carried: value in [-2^232, 2^255 + 2^232); + 2p (limbs 2^29 - 38, 2^29 - 1 (x 7), 2^24 - 1) makes it positive
     const F25 c = carry(a);
-    uint32_t u[FE_L];
+    uint32_t u[LIMBS29];
     uint32_t cy = 0;
 #pragma unroll
-    for (int i = 0; i < FE_L; i++) {
-        const uint32_t p2 = i == 0 ? FE_M29 - 37u : i == FE_L - 1 ? 0x00ffffffu : FE_M29;
+    for (int i = 0; i < LIMBS29; i++) {
+        const uint32_t p2 = i == 0 ? MASK29 - 37u : i == LIMBS29 - 1 ? 0x00ffffffu : MASK29;
         u[i] = (uint32_t)c.l[i] + p2 + cy;
-        if (i < FE_L - 1) { cy = u[i] >> 29; u[i] &= FE_M29; }
+        if (i < LIMBS29 - 1) { cy = u[i] >> 29; u[i] &= MASK29; }
     }
     // fold bits 255.. (value < 2^257): value in [0, 2^255 + 57]
-    uint32_t q = u[FE_L - 1] >> 23;
-    u[FE_L - 1] &= FE_M23;
+    uint32_t q = u[LIMBS29 - 1] >> 23;
+    u[LIMBS29 - 1] &= FE_M23;
     cy = 19u * q;
 #pragma unroll
-    for (int i = 0; i < FE_L; i++) {
+    for (int i = 0; i < LIMBS29; i++) {
         u[i] += cy;
-        if (i < FE_L - 1) { cy = u[i] >> 29; u[i] &= FE_M29; }
+        if (i < LIMBS29 - 1) { cy = u[i] >> 29; u[i] &= MASK29; }
     }
     // value >= p iff value + 19 >= 2^255: then subtract p = add 19, drop bit 255
     cy = 19u;
 #pragma unroll
-    for (int i = 0; i < FE_L - 1; i++) cy = (u[i] + cy) >> 29;
-    q = (u[FE_L - 1] + cy) >> 23;
+    for (int i = 0; i < LIMBS29 - 1; i++) cy = (u[i] + cy) >> 29;
+    q = (u[LIMBS29 - 1] + cy) >> 23;
     cy = 19u * q;
 #pragma unroll
-    for (int i = 0; i < FE_L; i++) {
+    for (int i = 0; i < LIMBS29; i++) {
         u[i] += cy;
-        if (i < FE_L - 1) { cy = u[i] >> 29; u[i] &= FE_M29; }
+        if (i < LIMBS29 - 1) { cy = u[i] >> 29; u[i] &= MASK29; }
     }
-    u[FE_L - 1] &= FE_M23;
-#pragma unroll
-    for (int j = 0; j < 8; j++) w[j] = 0;
-#pragma unroll
-    for (int i = 0; i < FE_L; i++) {
-        const int bit = 29 * i, j = bit >> 5, sh = bit & 31;
-        w[j] |= u[i] << sh;
-        if (sh > 3 && j + 1 < 8) w[j + 1] |= u[i] >> (32 - sh);
-    }
+    u[LIMBS29 - 1] &= FE_M23;
+    words_of_limbs(u, w);
 }
-DR_DEV bool fe_is_zero(const F25& a) {
-    uint32_t w[8];
-    fe_pack(a, w);
-    uint32_t o = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) o |= w[j];
-    return o == 0;
-}
-DR_DEV bool fe_equal(const F25& a, const F25& b) { return fe_is_zero(sub(a, b)); }
-// x > p - x for the canonical x: the reference's sign rule (point.py: x > -x % p), not the parity of x
-DR_DEV bool fe_is_larger(const F25& a) {
-    uint32_t w[8];
-    fe_pack(a, w);
-    uint32_t borrow = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) (void)subb(Fe25519Consts::HALF_P[j], w[j], borrow);
-    return borrow != 0;                              // (p - 1) / 2 - x < 0
-}
+DR_DEV void fe_pack(const F25& a, uint32_t (&w)[8]) { Fe25519Consts::pack(a, w); }
 
 // ---------------------------------------------------------------- exponentiations (the fixed chains of ref10)
 // z^(2^250 - 1), and z^11 on the side
@@ -280,8 +157,8 @@ DR_DEV bool fe_sqrt_ratio(const F25& u, const F25& v, F25& root) {
     const F25 p58 = mul(sqr_n(fe_pow_2_250_1(uv7, z11), 2), uv7);     // (u v^7)^(2^252 - 3)
     F25 b = mul(uv3, p58);
     const F25 vb2 = mul(v, sqr(b));
-    if (fe_equal(vb2, u)) { root = b; return true; }
-    if (fe_is_zero(add(vb2, u))) { root = mul(b, F25::constant<Fe25519Consts::SQRT_M1>()); return true; }
+    if (equal(vb2, u)) { root = b; return true; }
+    if (is_zero(add(vb2, u))) { root = mul(b, F25::constant<Fe25519Consts::SQRT_M1>()); return true; }
     root = F25::zero();
     return false;
 }

@@ -8,6 +8,10 @@
 // limb layouts of the Ed25519 kernels (LDS tables, shuffles) carry over.  Counted in the gfx950 code object (one operation
 // between loads and stores, minus the same kernel without it): see DESIGN.md section 8c.
 //
+// The element type, the limb-wise operations, the column products over reduce() below, the word layout and the predicates on the
+// canonical words are limb29.hip.h's; this header holds the constants, the Montgomery step, carry / fp_reduce, the canonicalisation
+// of pack and the chains.
+//
 // Value of an element: sum l[i] 2^(29 i), limbs SIGNED; the element it stands for is that value times R^-1 mod p.
 // Reduction of a product (columns c_0..c_16, int64): nine steps k = 0..8 take m = c_k mod 2^29, carry c_k >> 29 into c_(k+1) and
 // add m 2^9, m 2^18, -m 2^21, m 2^24 to c_(k+3), c_(k+6), c_(k+7), c_(k+8); the result is c_9..c_16 carried into 9 limbs.
@@ -26,29 +30,9 @@
 //   pack(a)   : limbs below 2^30 in magnitude, |value| < 2^263 -> the canonical element in [0, p) as 8 little-endian words
 //   unpack(w) : 8 words (any value below 2^256) -> the element w in Montgomery form, normal
 #pragma once
-#include "field.hip.h"
+#include "limb29.hip.h"
 
 namespace dr {
-
-constexpr int FP_L = 9;
-constexpr uint32_t FP_M29 = 0x1fffffffu;
-
-struct F256 {                         // an element of GF(p256) in Montgomery form, signed 29-bit limbs
-    int32_t l[FP_L];
-    DR_DEV static F256 zero() {
-        F256 r;
-#pragma unroll
-        for (int i = 0; i < FP_L; i++) r.l[i] = 0;
-        return r;
-    }
-    template <const uint32_t (&C)[9]>
-    DR_DEV static F256 constant() {
-        F256 r;
-#pragma unroll
-        for (int i = 0; i < FP_L; i++) r.l[i] = (int32_t)C[i];
-        return r;
-    }
-};
 
 struct Fp256Consts {
     // p, R mod p (the Montgomery one), R^2 mod p and b R mod p (b of y^2 = x^3 - 3 x + b), in 29-bit limbs
@@ -59,54 +43,24 @@ struct Fp256Consts {
     // p and (p - 1) / 2 as little-endian words
     static constexpr uint32_t PW[8] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0x00000000u, 0x00000000u, 0x00000000u, 0x00000001u, 0xffffffffu};
     static constexpr uint32_t HALF_P[8] = {0xffffffffu, 0xffffffffu, 0x7fffffffu, 0x00000000u, 0x00000000u, 0x80000000u, 0x80000000u, 0x7fffffffu};
+    DR_DEV static Limb29<Fp256Consts> reduce(int64_t (&c)[17]);
+    DR_DEV static void pack(const Limb29<Fp256Consts>& a, uint32_t (&w)[8]);
 };
+using F256 = Limb29<Fp256Consts>;      // an element of GF(p256) in Montgomery form, signed 29-bit limbs
 
 DR_DEV F256 fp_one() { return F256::constant<Fp256Consts::ONE>(); }
-
-DR_DEV F256 add(const F256& a, const F256& b) {
-    F256 r;
-#pragma unroll
-    for (int i = 0; i < FP_L; i++) r.l[i] = a.l[i] + b.l[i];
-    return r;
-}
-DR_DEV F256 sub(const F256& a, const F256& b) {
-    F256 r;
-#pragma unroll
-    for (int i = 0; i < FP_L; i++) r.l[i] = a.l[i] - b.l[i];
-    return r;
-}
-DR_DEV F256 dbl(const F256& a) { return add(a, a); }
-DR_DEV F256 neg(const F256& a) {
-    F256 r;
-#pragma unroll
-    for (int i = 0; i < FP_L; i++) r.l[i] = -a.l[i];
-    return r;
-}
-DR_DEV F256 cneg(const F256& a, bool negate) {
-    const int32_t s = negate ? -1 : 0;
-    F256 r;
-#pragma unroll
-    for (int i = 0; i < FP_L; i++) r.l[i] = (a.l[i] ^ s) - s;
-    return r;
-}
-DR_DEV F256 select(bool c, const F256& a, const F256& b) {
-    F256 r;
-#pragma unroll
-    for (int i = 0; i < FP_L; i++) r.l[i] = c ? a.l[i] : b.l[i];
-    return r;
-}
 
 // limbs 0..7 into [0, 2^29), the rest into limb 8 (signed)
 DR_DEV F256 carry(const F256& a) {
     F256 r;
     int32_t c = 0;
 #pragma unroll
-    for (int i = 0; i < FP_L - 1; i++) {
+    for (int i = 0; i < LIMBS29 - 1; i++) {
         const int32_t t = a.l[i] + c;
-        r.l[i] = t & (int32_t)FP_M29;
+        r.l[i] = t & (int32_t)MASK29;
         c = t >> 29;
     }
-    r.l[FP_L - 1] = a.l[FP_L - 1] + c;
+    r.l[LIMBS29 - 1] = a.l[LIMBS29 - 1] + c;
     return r;
 }
 // carry, then the bits of limb 8 from 2^256 up (h, signed) folded back with 2^256 = 2^224 - 2^192 - 2^96 + 1 (mod p):
@@ -119,23 +73,23 @@ DR_DEV F256 carry(const F256& a) {
 // k_p256_field_selftest's record 11, sqr(reduce(a)), drives exactly that case (tests/test_gpu_p256.py).
 DR_DEV F256 fp_reduce(const F256& a) {
     F256 r = carry(a);
-    const uint32_t h = (uint32_t)(r.l[FP_L - 1] >> 24);          // (two's complement: the fold below wraps as signed arithmetic would)
-    r.l[FP_L - 1] = (int32_t)((uint32_t)r.l[FP_L - 1] & 0x00ffffffu);
+    const uint32_t h = (uint32_t)(r.l[LIMBS29 - 1] >> 24);          // (two's complement: the fold below wraps as signed arithmetic would)
+    r.l[LIMBS29 - 1] = (int32_t)((uint32_t)r.l[LIMBS29 - 1] & 0x00ffffffu);
     r.l[0] = (int32_t)((uint32_t)r.l[0] + h);
     r.l[3] = (int32_t)((uint32_t)r.l[3] - (h << 9));
     r.l[6] = (int32_t)((uint32_t)r.l[6] - (h << 18));
     r.l[7] = (int32_t)((uint32_t)r.l[7] + (h << 21));
 #pragma unroll
-    for (int i = 0; i < FP_L; i++) asm volatile("" : "+v"(r.l[i]));
+    for (int i = 0; i < LIMBS29; i++) asm volatile("" : "+v"(r.l[i]));
     return r;
 }
 
 // columns c_0..c_16 -> (sum c_k 2^(29 k)) / 2^261 mod p, carried (the Montgomery reduction of the header)
-DR_DEV F256 fp_redc(int64_t (&c)[17]) {
+DR_DEV F256 Fp256Consts::reduce(int64_t (&c)[17]) {
 #pragma unroll
-    for (int k = 0; k < FP_L; k++) {
+    for (int k = 0; k < LIMBS29; k++) {
         const int64_t v = c[k];
-        const uint32_t m = (uint32_t)v & FP_M29;
+        const uint32_t m = (uint32_t)v & MASK29;
         c[k + 1] += v >> 29;                                   // (v - m) / 2^29: the column itself cancels against -m
         c[k + 3] += (int64_t)((uint64_t)m << 9);
         c[k + 6] += (int64_t)((uint64_t)m << 18);
@@ -145,112 +99,50 @@ DR_DEV F256 fp_redc(int64_t (&c)[17]) {
     F256 r;
     int64_t u = c[9];
 #pragma unroll
-    for (int k = 0; k < FP_L - 2; k++) {
-        r.l[k] = (int32_t)((uint32_t)u & FP_M29);
+    for (int k = 0; k < LIMBS29 - 2; k++) {
+        r.l[k] = (int32_t)((uint32_t)u & MASK29);
         u = c[10 + k] + (u >> 29);
     }
-    r.l[FP_L - 2] = (int32_t)((uint32_t)u & FP_M29);
-    r.l[FP_L - 1] = (int32_t)(u >> 29);
+    r.l[LIMBS29 - 2] = (int32_t)((uint32_t)u & MASK29);
+    r.l[LIMBS29 - 1] = (int32_t)(u >> 29);
     return r;
 }
 
-DR_DEV F256 mul(const F256& a, const F256& b) {
-    int64_t c[17];
-#pragma unroll
-    for (int k = 0; k < 17; k++) c[k] = 0;
-#pragma unroll
-    for (int i = 0; i < FP_L; i++)
-#pragma unroll
-        for (int j = 0; j < FP_L; j++) c[i + j] += (int64_t)a.l[i] * (int64_t)b.l[j];
-    return fp_redc(c);
-}
-DR_DEV F256 sqr(const F256& a) {
-    int32_t d[FP_L];
-#pragma unroll
-    for (int i = 0; i < FP_L; i++) d[i] = 2 * a.l[i];
-    int64_t c[17];
-#pragma unroll
-    for (int k = 0; k < 17; k++) c[k] = 0;
-#pragma unroll
-    for (int i = 0; i < FP_L; i++) {
-        c[2 * i] += (int64_t)a.l[i] * (int64_t)a.l[i];
-#pragma unroll
-        for (int j = i + 1; j < FP_L; j++) c[i + j] += (int64_t)d[i] * (int64_t)a.l[j];
-    }
-    return fp_redc(c);
-}
-DR_DEV F256 mul2(const F256& a, const F256& b, const F256& x, const F256& y) {     // a b + x y, one reduction
-    int64_t c[17];
-#pragma unroll
-    for (int k = 0; k < 17; k++) c[k] = 0;
-#pragma unroll
-    for (int i = 0; i < FP_L; i++)
-#pragma unroll
-        for (int j = 0; j < FP_L; j++) {
-            c[i + j] += (int64_t)a.l[i] * (int64_t)b.l[j];
-            c[i + j] += (int64_t)x.l[i] * (int64_t)y.l[j];
-        }
-    return fp_redc(c);
-}
-DR_DEV F256 sqr_n(F256 a, int n) {                     // a^(2^n)
-#pragma unroll 1
-    for (int i = 0; i < n; i++) a = sqr(a);
-    return a;
-}
-
 // ---------------------------------------------------------------- 8 x u32 words <-> limbs
+// (the layout loops of fp_unpack and fp_pack are limb29.hip.h's limbs_of_words / words_of_limbs, kept in place: through the shared
+// routines the compiler orders the code of P-256 and Baby JubJub kernels differently — same counts; DESIGN.md section 8j lists them)
 DR_DEV F256 fp_unpack(const uint32_t (&w)[8]) {
     F256 r;
 #pragma unroll
-    for (int i = 0; i < FP_L; i++) {
+    for (int i = 0; i < LIMBS29; i++) {
         const int bit = 29 * i, j = bit >> 5, sh = bit & 31;
         uint32_t v = w[j] >> sh;
         if (sh > 3 && j + 1 < 8) v |= w[j + 1] << (32 - sh);
-        r.l[i] = (int32_t)(i < FP_L - 1 ? v & FP_M29 : v);
+        r.l[i] = (int32_t)(i < LIMBS29 - 1 ? v & MASK29 : v);
     }
     return mul(r, F256::constant<Fp256Consts::R2>());   // w R mod p
 }
 // canonical little-endian words of the element a stands for (a R^-1 mod p)
-DR_DEV void fp_pack(const F256& a, uint32_t (&w)[8]) {
+DR_DEV void Fp256Consts::pack(const F256& a, uint32_t (&w)[8]) {
     int64_t c[17];
 #pragma unroll
-    for (int k = 0; k < 17; k++) c[k] = k < FP_L ? (int64_t)a.l[k] : 0;
+    for (int k = 0; k < 17; k++) c[k] = k < LIMBS29 ? (int64_t)a.l[k] : 0;
     // |value| < 2^263: T = (value + M p) / 2^261 lies in (-4, p + 4) — one conditional addition and one subtraction of p
-    F256 t = fp_redc(c);
-    const bool negative = t.l[FP_L - 1] < 0;
+    F256 t = reduce(c);
+    const bool negative = t.l[LIMBS29 - 1] < 0;
     t = carry(select(negative, add(t, F256::constant<Fp256Consts::P>()), t));
 #pragma unroll
     for (int j = 0; j < 8; j++) w[j] = 0;
 #pragma unroll
-    for (int i = 0; i < FP_L; i++) {
+    for (int i = 0; i < LIMBS29; i++) {
         const uint32_t u = (uint32_t)t.l[i];
         const int bit = 29 * i, j = bit >> 5, sh = bit & 31;
         w[j] |= u << sh;
         if (sh > 3 && j + 1 < 8) w[j + 1] |= u >> (32 - sh);
     }
-    uint32_t d[8], borrow = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) d[j] = subb(w[j], Fp256Consts::PW[j], borrow);
-    const bool ge = borrow == 0;                       // w >= p
-#pragma unroll
-    for (int j = 0; j < 8; j++) w[j] = ge ? d[j] : w[j];
+    sub_p_if_ge<Fp256Consts>(w);
 }
-DR_DEV bool fp_is_zero(const F256& a) {
-    uint32_t w[8];
-    fp_pack(a, w);
-    uint32_t o = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) o |= w[j];
-    return o == 0;
-}
-DR_DEV bool fp_equal(const F256& a, const F256& b) { return fp_is_zero(sub(a, b)); }
-// y > p - y for the canonical y: the flag bit of the reference's P-256 codec (y > -y % p)
-DR_DEV bool fp_is_larger(const uint32_t (&w)[8]) {
-    uint32_t borrow = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) (void)subb(Fp256Consts::HALF_P[j], w[j], borrow);
-    return borrow != 0;                              // (p - 1) / 2 - y < 0
-}
+DR_DEV void fp_pack(const F256& a, uint32_t (&w)[8]) { Fp256Consts::pack(a, w); }
 
 // ---------------------------------------------------------------- exponentiations: fixed chains, the same in every lane
 // z^(2^32 - 1), and z^(2^2 - 1), z^(2^30 - 1) on the side
@@ -281,7 +173,7 @@ DR_DEV bool fp_sqrt(const F256& v, F256& root) {
     F256 r = mul(sqr_n(x32, 32), v);
     r = mul(sqr_n(r, 96), v);
     r = sqr_n(r, 94);
-    const bool ok = fp_equal(sqr(r), v);
+    const bool ok = equal(sqr(r), v);
     root = ok ? r : F256::zero();
     return ok;
 }
@@ -297,10 +189,5 @@ DR_DEV F256 fp_pow_p34(const F256& z) {
     r = mul(sqr_n(r, 32), x32);
     return mul(sqr_n(r, 30), x30);
 }
-// the canonical value is odd (sgn0 of RFC 9380)
-DR_DEV bool fp_is_odd(const F256& a) {
-    uint32_t w[8];
-    fp_pack(a, w);
-    return (w[0] & 1u) != 0;
-}
+
 }  // namespace dr

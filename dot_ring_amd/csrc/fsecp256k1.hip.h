@@ -11,6 +11,10 @@
 // 182 / 162 / 289; the figures recorded with the older harness are 150 / 115 for Ed25519 and 206 / 178 for fr29.  The fold is thus
 // no cheaper than P-256's shift-only step (each digit's 64-bit shift-add is two instructions); it saves the conversions.
 //
+// The element type, the limb-wise operations, the column products over reduce() below, the word layout and the predicates on the
+// canonical words are limb29.hip.h's; this header holds the constants, the fold, fk_fold_top / carry / mul_small, the canonicalisation
+// of pack and the chains.
+//
 // Value of an element: sum l[i] 2^(29 i), limbs SIGNED.  Reduction of a product: columns c_0..c_16 (int64), the high columns carried
 // into 29-bit digits h_0..h_7 and a top carry t (weight B^17 = B^8 B^9); c_k += 31264 h_k, c_(k+1) += h_k 2^8; c_8 += 31264 t, and t's
 // second limb, t 2^8 B^9, folds once more: c_1 += t 2^16, c_0 += 31264 2^8 t.  One carry chain over c_0..c_8; the bits of c_8 from 24 up
@@ -29,76 +33,22 @@
 //   pack(a)   : limbs as for carry -> the canonical representative in [0, p) as 8 little-endian words
 //   unpack(w) : 8 words (any value below 2^256) -> limbs 0..7 in [0, 2^29), limb 8 < 2^24: normal
 #pragma once
-#include "field.hip.h"
+#include "limb29.hip.h"
 
 namespace dr {
 
-constexpr int FK_L = 9;
-constexpr uint32_t FK_M29 = 0x1fffffffu;
 constexpr uint32_t FK_M24 = 0x00ffffffu;
 constexpr uint32_t FK_FOLD = 31264u;               // 2^5 977: 2^261 = 2^8 B + FK_FOLD (mod p)
-
-struct FK {                           // an element of GF(2^256 - 2^32 - 977) in signed 29-bit limbs
-    int32_t l[FK_L];
-    DR_DEV static FK zero() {
-        FK r;
-#pragma unroll
-        for (int i = 0; i < FK_L; i++) r.l[i] = 0;
-        return r;
-    }
-    DR_DEV static FK small(int32_t v) {             // |v| < 2^29
-        FK r = zero();
-        r.l[0] = v;
-        return r;
-    }
-    template <const uint32_t (&C)[9]>
-    DR_DEV static FK constant() {
-        FK r;
-#pragma unroll
-        for (int i = 0; i < FK_L; i++) r.l[i] = (int32_t)C[i];
-        return r;
-    }
-};
 
 struct FsecpConsts {
     // p in 29-bit limbs; p and the group order n as little-endian words
     static constexpr uint32_t P[9] = {0x1ffffc2fu, 0x1ffffff7u, 0x1fffffffu, 0x1fffffffu, 0x1fffffffu, 0x1fffffffu, 0x1fffffffu, 0x1fffffffu, 0x00ffffffu};
     static constexpr uint32_t PW[8] = {0xfffffc2fu, 0xfffffffeu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
     static constexpr uint32_t NW[8] = {0xd0364141u, 0xbfd25e8cu, 0xaf48a03bu, 0xbaaedce6u, 0xfffffffeu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
+    DR_DEV static Limb29<FsecpConsts> reduce(int64_t (&c)[17]);
+    DR_DEV static void pack(const Limb29<FsecpConsts>& a, uint32_t (&w)[8]);
 };
-
-DR_DEV FK add(const FK& a, const FK& b) {
-    FK r;
-#pragma unroll
-    for (int i = 0; i < FK_L; i++) r.l[i] = a.l[i] + b.l[i];
-    return r;
-}
-DR_DEV FK sub(const FK& a, const FK& b) {
-    FK r;
-#pragma unroll
-    for (int i = 0; i < FK_L; i++) r.l[i] = a.l[i] - b.l[i];
-    return r;
-}
-DR_DEV FK dbl(const FK& a) { return add(a, a); }
-DR_DEV FK neg(const FK& a) {
-    FK r;
-#pragma unroll
-    for (int i = 0; i < FK_L; i++) r.l[i] = -a.l[i];
-    return r;
-}
-DR_DEV FK cneg(const FK& a, bool negate) {
-    const int32_t s = negate ? -1 : 0;
-    FK r;
-#pragma unroll
-    for (int i = 0; i < FK_L; i++) r.l[i] = (a.l[i] ^ s) - s;
-    return r;
-}
-DR_DEV FK select(bool c, const FK& a, const FK& b) {
-    FK r;
-#pragma unroll
-    for (int i = 0; i < FK_L; i++) r.l[i] = c ? a.l[i] : b.l[i];
-    return r;
-}
+using FK = Limb29<FsecpConsts>;        // an element of GF(2^256 - 2^32 - 977) in signed 29-bit limbs
 
 // the end of every reduction: limbs 0..7 in [0, 2^29) and u = limb 8 with everything above it (|u| < 2^63); the bits of u from 24 up
 // fold into limbs 0 and 1 (2^256 = 8 B + 977), their carry into limb 2.  The masked limb 8 leaves through an empty asm statement, as
@@ -109,21 +59,21 @@ DR_DEV void fk_fold_top(FK& r, int64_t u) {
     asm volatile("" : "+v"(r.l[8]));
     const int64_t q = u >> 24;
     const int64_t v0 = (int64_t)r.l[0] + q * 977;
-    r.l[0] = (int32_t)((uint32_t)v0 & FK_M29);
+    r.l[0] = (int32_t)((uint32_t)v0 & MASK29);
     const int64_t v1 = (int64_t)r.l[1] + q * 8 + (v0 >> 29);
-    r.l[1] = (int32_t)((uint32_t)v1 & FK_M29);
+    r.l[1] = (int32_t)((uint32_t)v1 & MASK29);
     r.l[2] += (int32_t)(v1 >> 29);
 }
 DR_DEV FK carry(const FK& a) {
     FK r;
     int32_t c = 0;
 #pragma unroll
-    for (int i = 0; i < FK_L - 1; i++) {
+    for (int i = 0; i < LIMBS29 - 1; i++) {
         const int32_t t = a.l[i] + c;
-        r.l[i] = t & (int32_t)FK_M29;
+        r.l[i] = t & (int32_t)MASK29;
         c = t >> 29;
     }
-    fk_fold_top(r, (int64_t)(a.l[FK_L - 1] + c));
+    fk_fold_top(r, (int64_t)(a.l[LIMBS29 - 1] + c));
     return r;
 }
 // a k for a small non-negative k (the curve's 21 = 3 b, the map's B' = 1771 and |Z| = 11)
@@ -131,21 +81,21 @@ DR_DEV FK mul_small(const FK& a, uint32_t k) {
     FK r;
     int64_t u = 0;
 #pragma unroll
-    for (int i = 0; i < FK_L - 1; i++) {
+    for (int i = 0; i < LIMBS29 - 1; i++) {
         u += (int64_t)a.l[i] * (int64_t)k;
-        r.l[i] = (int32_t)((uint32_t)u & FK_M29);
+        r.l[i] = (int32_t)((uint32_t)u & MASK29);
         u >>= 29;
     }
-    fk_fold_top(r, u + (int64_t)a.l[FK_L - 1] * (int64_t)k);
+    fk_fold_top(r, u + (int64_t)a.l[LIMBS29 - 1] * (int64_t)k);
     return r;
 }
 
 // columns c_0..c_16 of a product (|c_k| < 2^63 - 2^47) -> a normal element
-DR_DEV FK fk_reduce(int64_t (&c)[17]) {
+DR_DEV FK FsecpConsts::reduce(int64_t (&c)[17]) {
     int64_t t = c[9];
 #pragma unroll
     for (int k = 0; k < 8; k++) {                    // high columns -> 29-bit digits; digit k has weight B^(k + 9) = (2^8 B + 31264) B^k
-        const uint32_t h = (uint32_t)t & FK_M29;
+        const uint32_t h = (uint32_t)t & MASK29;
         t = (t >> 29) + (k < 7 ? c[10 + k] : 0);
         c[k] += (int64_t)((uint64_t)h * FK_FOLD);
         c[k + 1] += (int64_t)((uint64_t)h << 8);
@@ -157,125 +107,45 @@ DR_DEV FK fk_reduce(int64_t (&c)[17]) {
     int64_t u = c[0];
 #pragma unroll
     for (int k = 0; k < 8; k++) {
-        r.l[k] = (int32_t)((uint32_t)u & FK_M29);
+        r.l[k] = (int32_t)((uint32_t)u & MASK29);
         u = c[k + 1] + (u >> 29);
     }
     fk_fold_top(r, u);
     return r;
 }
 
-DR_DEV FK mul(const FK& a, const FK& b) {
-    int64_t c[17];
-#pragma unroll
-    for (int k = 0; k < 17; k++) c[k] = 0;
-#pragma unroll
-    for (int i = 0; i < FK_L; i++)
-#pragma unroll
-        for (int j = 0; j < FK_L; j++) c[i + j] += (int64_t)a.l[i] * (int64_t)b.l[j];
-    return fk_reduce(c);
-}
-DR_DEV FK sqr(const FK& a) {
-    int32_t d[FK_L];
-#pragma unroll
-    for (int i = 0; i < FK_L; i++) d[i] = 2 * a.l[i];
-    int64_t c[17];
-#pragma unroll
-    for (int k = 0; k < 17; k++) c[k] = 0;
-#pragma unroll
-    for (int i = 0; i < FK_L; i++) {
-        c[2 * i] += (int64_t)a.l[i] * (int64_t)a.l[i];
-#pragma unroll
-        for (int j = i + 1; j < FK_L; j++) c[i + j] += (int64_t)d[i] * (int64_t)a.l[j];
-    }
-    return fk_reduce(c);
-}
-DR_DEV FK mul2(const FK& a, const FK& b, const FK& x, const FK& y) {      // a b + x y, one reduction
-    int64_t c[17];
-#pragma unroll
-    for (int k = 0; k < 17; k++) c[k] = 0;
-#pragma unroll
-    for (int i = 0; i < FK_L; i++)
-#pragma unroll
-        for (int j = 0; j < FK_L; j++) {
-            c[i + j] += (int64_t)a.l[i] * (int64_t)b.l[j];
-            c[i + j] += (int64_t)x.l[i] * (int64_t)y.l[j];
-        }
-    return fk_reduce(c);
-}
-DR_DEV FK sqr_n(FK a, int n) {                       // a^(2^n)
-#pragma unroll 1
-    for (int i = 0; i < n; i++) a = sqr(a);
-    return a;
-}
-
 // ---------------------------------------------------------------- 8 x u32 words <-> limbs
-DR_DEV FK fk_unpack(const uint32_t (&w)[8]) {
-    FK r;
-#pragma unroll
-    for (int i = 0; i < FK_L; i++) {
-        const int bit = 29 * i, j = bit >> 5, sh = bit & 31;
-        uint32_t v = w[j] >> sh;
-        if (sh > 3 && j + 1 < 8) v |= w[j + 1] << (32 - sh);
-        r.l[i] = (int32_t)(v & FK_M29);
-    }
-    return r;
-}
+DR_DEV FK fk_unpack(const uint32_t (&w)[8]) { return limbs_of_words<FsecpConsts>(w); }
 // canonical little-endian words of a (limbs below 2^31 - 8 in magnitude)
-DR_DEV void fk_pack(const FK& a, uint32_t (&w)[8]) {
+DR_DEV void FsecpConsts::pack(const FK& a, uint32_t (&w)[8]) {
     // carried: value in (-2^73, 2^256 + 2^73); + p makes it positive and below 2^257
     const FK c = carry(a);
-    uint32_t u[FK_L];
+    uint32_t u[LIMBS29];
     uint32_t cy = 0;
 #pragma unroll
-    for (int i = 0; i < FK_L; i++) {
+    for (int i = 0; i < LIMBS29; i++) {
         u[i] = (uint32_t)c.l[i] + FsecpConsts::P[i] + cy;           // (two's complement: a negative limb 2 borrows through cy below)
-        if (i < FK_L - 1) { cy = (uint32_t)((int32_t)u[i] >> 29); u[i] &= FK_M29; }
+        if (i < LIMBS29 - 1) { cy = (uint32_t)((int32_t)u[i] >> 29); u[i] &= MASK29; }
     }
     // fold bit 256, twice: the first fold takes p away again, and a carried value of 2^256 or more (limb 2 can exceed 2^29) then
     // still has the bit; after the second the value is in [0, 2^256)
 #pragma unroll
     for (int pass = 0; pass < 2; pass++) {
-        const uint32_t q = u[FK_L - 1] >> 24;
-        u[FK_L - 1] &= FK_M24;
+        const uint32_t q = u[LIMBS29 - 1] >> 24;
+        u[LIMBS29 - 1] &= FK_M24;
         u[0] += 977u * q;
         u[1] += 8u * q;
         cy = 0;
 #pragma unroll
-        for (int i = 0; i < FK_L; i++) {
+        for (int i = 0; i < LIMBS29; i++) {
             u[i] += cy;
-            if (i < FK_L - 1) { cy = u[i] >> 29; u[i] &= FK_M29; }
+            if (i < LIMBS29 - 1) { cy = u[i] >> 29; u[i] &= MASK29; }
         }
     }
-#pragma unroll
-    for (int j = 0; j < 8; j++) w[j] = 0;
-#pragma unroll
-    for (int i = 0; i < FK_L; i++) {
-        const int bit = 29 * i, j = bit >> 5, sh = bit & 31;
-        w[j] |= u[i] << sh;
-        if (sh > 3 && j + 1 < 8) w[j + 1] |= u[i] >> (32 - sh);
-    }
-    uint32_t d[8], borrow = 0;                          // below 2^256 < 2 p: one conditional subtraction
-#pragma unroll
-    for (int j = 0; j < 8; j++) d[j] = subb(w[j], FsecpConsts::PW[j], borrow);
-    const bool ge = borrow == 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) w[j] = ge ? d[j] : w[j];
+    words_of_limbs(u, w);
+    sub_p_if_ge<FsecpConsts>(w);                        // below 2^256 < 2 p: one conditional subtraction
 }
-DR_DEV bool fk_is_zero(const FK& a) {
-    uint32_t w[8];
-    fk_pack(a, w);
-    uint32_t o = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) o |= w[j];
-    return o == 0;
-}
-DR_DEV bool fk_equal(const FK& a, const FK& b) { return fk_is_zero(sub(a, b)); }
-// the canonical a is odd: sgn0 of RFC 9380 and the prefix bit of the SEC1 codec
-DR_DEV bool fk_is_odd(const FK& a) {
-    uint32_t w[8];
-    fk_pack(a, w);
-    return (w[0] & 1u) != 0;
-}
+DR_DEV void fk_pack(const FK& a, uint32_t (&w)[8]) { FsecpConsts::pack(a, w); }
 
 // ---------------------------------------------------------------- exponentiations: fixed chains, the same in every lane
 // p = [223 ones] 0 [22 ones] 0000101111 in binary.  z^(2^223 - 1) shifted by 23 bits times z^(2^22 - 1) is the head every exponent
@@ -315,7 +185,7 @@ DR_DEV bool fk_sqrt(const FK& v, FK& root) {
     FK x2;
     FK r = fk_pow_head(v, x2);
     r = sqr_n(mul(sqr_n(r, 6), x2), 2);
-    const bool ok = fk_equal(sqr(r), v);
+    const bool ok = equal(sqr(r), v);
     root = ok ? r : FK::zero();
     return ok;
 }

@@ -40,7 +40,7 @@ DR_DEV uint32_t bjj_dlog_window(const Fbn& v) {
 // a square root of x (which of the two is unspecified: callers fix the sign); false, root = 0, when x is not a square
 DR_DEV bool bjj_sqrt(const Fbn& x, Fbn& root) {
     root = Fbn::zero();
-    if (bn_is_zero(x)) return true;
+    if (is_zero(x)) return true;
     constexpr uint32_t QM1H[8] = {0x1f0fac9fu, 0xcdcb848au, 0x419f4243u, 0x0c0ac2e9u, 0xc2822db4u, 0x098d014du, 0x83227397u, 0x00000001u};   // (Q-1)/2
     uint32_t e[8];
 #pragma unroll
@@ -118,15 +118,15 @@ DR_DEV BjjPoint bjj_cneg(const BjjPoint& p, bool negate) {
 }
 
 // ---------------------------------------------------------------- memory
-// a normal (value in (-2^253, p + 2^253)) as the 8 words of its Montgomery value, moved into [0, 2^256): carried, p added when it
-// is negative — bn_unpack_raw reads it back as a normal of the same value mod p
+// a normal (value in (-2^253, p + 2^253)) as the 8 words of its Montgomery value, moved into [0, 2^256): carried, p added when it is
+// negative — bn_unpack_raw reads it back as a normal of the same value mod p (the loop is bn_pack's, in place for the same reason)
 DR_DEV void bn_to_words(const Fbn& a, uint32_t (&w)[8]) {
     Fbn c = carry(a);
-    c = carry(select(c.l[BN_L - 1] < 0, add(c, Fbn::constant<FbnConsts::P>()), c));
+    c = carry(select(c.l[LIMBS29 - 1] < 0, add(c, Fbn::constant<FbnConsts::P>()), c));
 #pragma unroll
     for (int j = 0; j < 8; j++) w[j] = 0;
 #pragma unroll
-    for (int i = 0; i < BN_L; i++) {
+    for (int i = 0; i < LIMBS29; i++) {
         const uint32_t u = (uint32_t)c.l[i];
         const int bit = 29 * i, j = bit >> 5, sh = bit & 31;
         w[j] |= u << sh;
@@ -227,14 +227,14 @@ __global__ __launch_bounds__(BJJ_BLOCK) void k_bjj_decode_points(const uint32_t*
     const Fbn v = sub(one, mul(Fbn::constant<FbnConsts::D>(), y2));
     Fbn x;
     if (!bjj_sqrt(mul(u, bn_inv(v)), x)) valid = false;
-    if (bn_is_larger(x) != sign) x = neg(x);
+    if (is_larger(x) != sign) x = neg(x);
     Fbn ox = x, oy = yy;
     if constexpr (MODE != BJJ_DEC_CODEC) {
         const BjjPoint P = BjjCurve::from_affine(x, yy);
         BjjPoint Q = P;
 #pragma unroll 1
         for (int j = 0; j < 3; j++) Q = bjj_dbl<true>(Q);
-        if (bn_is_zero(Q.x)) { valid = false; Q = P; }  // 8 P = O (x = 0: 8 P lies in the prime-order subgroup, where only O has x = 0)
+        if (is_zero(Q.x)) { valid = false; Q = P; }  // 8 P = O (x = 0: 8 P lies in the prime-order subgroup, where only O has x = 0)
         const Fbn zi = bn_inv(Q.z);
         const Fbn qx = mul(Q.x, zi), qy = mul(Q.y, zi);
         if constexpr (MODE == BJJ_DEC_TAI) {
@@ -245,7 +245,7 @@ __global__ __launch_bounds__(BJJ_BLOCK) void k_bjj_decode_points(const uint32_t*
 #pragma unroll
             for (int j = 0; j < 8; j++) k[j] = HINV[j];
             const BjjPoint R = wave_scalar_mul_core<BjjCurve>(tab, lane, BjjCurve::from_affine(qx, qy), k);
-            if (!bn_equal(R.x, mul(x, R.z)) || !bn_equal(R.y, mul(yy, R.z))) valid = false;
+            if (!equal(R.x, mul(x, R.z)) || !equal(R.y, mul(yy, R.z))) valid = false;
         }
     }
     if (!valid) { ox = Fbn::zero(); oy = Fbn::zero(); }
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(64) void k_bjj_field_selftest(const int32_t* __rest
     if (i >= n) return;
     Fbn a, b;
 #pragma unroll
-    for (int t = 0; t < BN_L; t++) { a.l[t] = a_limbs[(size_t)i * BN_L + t]; b.l[t] = b_limbs[(size_t)i * BN_L + t]; }
+    for (int t = 0; t < LIMBS29; t++) { a.l[t] = a_limbs[(size_t)i * LIMBS29 + t]; b.l[t] = b_limbs[(size_t)i * LIMBS29 + t]; }
     uint32_t* o = out + (size_t)i * BJJ_SELFTEST_RECORDS * 8;
     wave_store_fe<BjjCurve>(o + 0, mul(a, b));
     wave_store_fe<BjjCurve>(o + 8, sqr(a));
@@ -287,7 +287,7 @@ __global__ __launch_bounds__(64) void k_bjj_field_selftest(const int32_t* __rest
     wave_store_fe<BjjCurve>(o + 80, bn_unpack_raw(w));
     bn_pack(a, w);
     wave_store_fe<BjjCurve>(o + 88, bn_unpack(w));
-    flags[i] = (sq ? 1u : 0u) | (bn_is_larger(a) ? 4u : 0u);
+    flags[i] = (sq ? 1u : 0u) | (is_larger(a) ? 4u : 0u);
 }
 
 }  // namespace dr

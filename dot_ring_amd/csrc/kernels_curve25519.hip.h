@@ -26,17 +26,17 @@ namespace dr {
 
 // the Edwards image of (u, v) in extended coordinates; `ident`: the identity flag of the input
 DR_DEV EdPoint c25519_to_edwards(const F25& u, const F25& v, bool ident) {
-    const F25 one = F25::one();
+    const F25 one = F25::small(1);
     const F25 cu = mul(F25::constant<Ed25519Ell2::SQRT_NEG_A_MINUS_2>(), u);     // n
     const F25 up = carry(add(u, one)), um = carry(sub(u, one));                  // n
     EdPoint r;
     r.x = mul(cu, up); r.y = mul(um, v); r.z = mul(v, up); r.t = mul(cu, um);
-    const bool two = fe_is_zero(v);                                              // (0, 0) -> (0, -1)
+    const bool two = is_zero(v);                                                 // (0, 0) -> (0, -1)
     const F25 ey = cneg(one, two && !ident);
-    r.x = fe_select(two || ident, F25::zero(), r.x);
-    r.t = fe_select(two || ident, F25::zero(), r.t);
-    r.y = fe_select(two || ident, ey, r.y);
-    r.z = fe_select(two || ident, one, r.z);
+    r.x = select(two || ident, F25::zero(), r.x);
+    r.t = select(two || ident, F25::zero(), r.t);
+    r.y = select(two || ident, ey, r.y);
+    r.z = select(two || ident, one, r.z);
     return r;
 }
 // u || v of an Edwards point (16 words) and its identity flag; (0, -1) stores (0, 0) through 0^-1 = 0, the identity zeros and flag 1
@@ -44,7 +44,7 @@ DR_DEV void c25519_store(uint32_t* out, uint32_t* flag, const EdPoint& p) {
     const F25 zmy = carry(sub(p.z, p.y)), zpy = carry(add(p.z, p.y));            // n
     const F25 inv = fe_inv(mul(p.x, zmy));
     const F25 zi = mul(zpy, inv);
-    const bool ident = fe_is_zero(p.x) && fe_is_zero(zmy);
+    const bool ident = is_zero(p.x) && is_zero(zmy);
     wave_store_fe<Ed25519Curve>(out, mul(zi, p.x));
     wave_store_fe<Ed25519Curve>(out + 8, mul(mul(F25::constant<Ed25519Ell2::SQRT_NEG_A_MINUS_2>(), zi), p.z));
     *flag = ident ? 1u : 0u;
@@ -118,20 +118,20 @@ __global__ __launch_bounds__(ED_BLOCK) void k_c25519_decode_points(const uint32_
     wave_load8(enc + (size_t)i * 16 + 8, vw);
     bool valid = c25519_below_p(uw) && c25519_below_p(vw);
     const F25 u = fe_unpack(uw), v = fe_unpack(vw);
-    const F25 rhs = mul(u, add(mul(u, add(u, F25::constant<Ed25519Ell2::A>())), F25::one()));     // u (u (u + A) + 1): n x (n + n)
-    if (!fe_equal(sqr(v), rhs)) valid = false;
+    const F25 rhs = mul(u, add(mul(u, add(u, F25::constant<Ed25519Ell2::A>())), F25::small(1)));     // u (u (u + A) + 1): n x (n + n)
+    if (!equal(sqr(v), rhs)) valid = false;
     if constexpr (MODE == C25519_DEC_CHECK) {
         const EdPoint P = c25519_to_edwards(u, v, false);
         EdPoint Q = P;
 #pragma unroll 1
         for (int j = 0; j < 3; j++) Q = ed_dbl<true>(Q);
-        if (fe_is_zero(Q.x)) { valid = false; Q = P; }   // 8 P = O (x = 0: 8 P lies in the prime-order subgroup, where only O has x = 0)
+        if (is_zero(Q.x)) { valid = false; Q = P; }   // 8 P = O (x = 0: 8 P lies in the prime-order subgroup, where only O has x = 0)
         constexpr uint32_t HINV[8] = {0xe2dc2f79u, 0x6106e529u, 0x7d1cdad0u, 0x07d39db3u, 0x00000000u, 0x00000000u, 0x00000000u, 0x06000000u};
         uint32_t k[8];
 #pragma unroll
         for (int j = 0; j < 8; j++) k[j] = HINV[j];
         const EdPoint R = wave_scalar_mul_core<Ed25519Curve>(tab, lane, Q, k);
-        if (!fe_equal(mul(R.x, P.z), mul(P.x, R.z)) || !fe_equal(mul(R.y, P.z), mul(P.y, R.z))) valid = false;
+        if (!equal(mul(R.x, P.z), mul(P.x, R.z)) || !equal(mul(R.y, P.z), mul(P.y, R.z))) valid = false;
     }
     if (live) {
         if (valid) {
@@ -154,11 +154,11 @@ __global__ __launch_bounds__(ED_BLOCK) void k_c25519_decode_points(const uint32_
 DR_DEV EdPoint c25519_ell2_edwards(const F25& u) {
     bool ok;
     EdPoint q = ed_ell2_map(u, ok);
-    const F25 one = F25::one(), zero = F25::zero();
-    q.x = fe_select(ok, q.x, zero);
-    q.y = fe_select(ok, q.y, neg(one));
-    q.z = fe_select(ok, q.z, one);
-    q.t = fe_select(ok, q.t, zero);
+    const F25 one = F25::small(1), zero = F25::zero();
+    q.x = select(ok, q.x, zero);
+    q.y = select(ok, q.y, neg(one));
+    q.z = select(ok, q.z, one);
+    q.t = select(ok, q.t, zero);
     return q;
 }
 // out[i] = [8] (the sum of the images of item i's `per_item` field elements) (2: the uniform (RO) encoding, 1: the nonuniform one), or

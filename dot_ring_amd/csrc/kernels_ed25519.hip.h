@@ -21,7 +21,7 @@ struct EdPoint {
 
 DR_DEV EdPoint ed_identity() {
     EdPoint p;
-    p.x = F25::zero(); p.y = F25::one(); p.z = F25::one(); p.t = F25::zero();
+    p.x = F25::zero(); p.y = F25::small(1); p.z = F25::small(1); p.t = F25::zero();
     return p;
 }
 
@@ -96,7 +96,7 @@ struct Ed25519Curve {
     DR_DEV static EdPoint identity() { return ed_identity(); }
     DR_DEV static EdPoint from_affine(const F25& x, const F25& y) {
         EdPoint P;
-        P.x = x; P.y = y; P.z = F25::one(); P.t = mul(x, y);
+        P.x = x; P.y = y; P.z = F25::small(1); P.t = mul(x, y);
         return P;
     }
     DR_DEV static EdPoint add(const EdPoint& p, const EdPoint& q) { return ed_add(p, q); }
@@ -149,21 +149,21 @@ __global__ __launch_bounds__(ED_BLOCK) void k_ed_decode_points(const uint32_t* _
         for (int j = 0; j < 7; j++) c = (uint32_t)(((uint64_t)ys[j] + c) >> 32);
         valid = ys[7] + c < 0x80000000u;
     }
-    const F25 one = F25::one();
+    const F25 one = F25::small(1);
     const F25 y = fe_unpack(ys);
     const F25 y2 = sqr(y);
     const F25 u = carry(sub(y2, one));
     const F25 v = carry(add(mul(F25::constant<Fe25519Consts::D>(), y2), one));
     F25 x;
     if (!fe_sqrt_ratio(u, v, x)) valid = false;       // (v = 0 never happens: -1 / d is not a square; u / 0 has no root here either)
-    if (fe_is_larger(x) != sign) x = neg(x);
+    if (is_larger(x) != sign) x = neg(x);
     F25 ox = x, oy = y;
     if constexpr (MODE != ED_DEC_CODEC) {
         const EdPoint P = Ed25519Curve::from_affine(x, y);
         EdPoint Q = P;
 #pragma unroll 1
         for (int j = 0; j < 3; j++) Q = ed_dbl<true>(Q);
-        if (fe_is_zero(Q.x)) { valid = false; Q = P; }  // 8 P = O (x = 0: 8 P lies in the prime-order subgroup, where only O has x = 0)
+        if (is_zero(Q.x)) { valid = false; Q = P; }  // 8 P = O (x = 0: 8 P lies in the prime-order subgroup, where only O has x = 0)
         const F25 zi = fe_inv(Q.z);
         const F25 qx = mul(Q.x, zi), qy = mul(Q.y, zi);
         if constexpr (MODE == ED_DEC_TAI) {
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(ED_BLOCK) void k_ed_decode_points(const uint32_t* _
 #pragma unroll
             for (int j = 0; j < 8; j++) k[j] = HINV[j];
             const EdPoint R = wave_scalar_mul_core<Ed25519Curve>(tab, lane, Ed25519Curve::from_affine(qx, qy), k);
-            if (!fe_equal(R.x, mul(x, R.z)) || !fe_equal(R.y, mul(y, R.z))) valid = false;
+            if (!equal(R.x, mul(x, R.z)) || !equal(R.y, mul(y, R.z))) valid = false;
         }
     }
     if (!valid) { ox = F25::zero(); oy = F25::zero(); }
@@ -201,19 +201,13 @@ struct Ed25519Ell2 {
     static constexpr uint32_t SQRT_NEG_2I[9] = {0x15f15f3eu, 0x188f26c5u, 0x1406e1ceu, 0x19cff2a5u, 0x02858d0bu, 0x1fb36102u, 0x03d352cbu, 0x0ff607c4u, 0x00547cdbu};
     static constexpr uint32_t SQRT_2I[9] = {0x0a0ea0b1u, 0x0770d93au, 0x0bf91e31u, 0x06300d5au, 0x1d7a72f4u, 0x004c9efdu, 0x1c2cad34u, 0x1009f83bu, 0x002b8324u};
 };
-DR_DEV F25 fe_select(bool c, const F25& a, const F25& b) {
-    F25 r;
-#pragma unroll
-    for (int i = 0; i < FE_L; i++) r.l[i] = c ? a.l[i] : b.l[i];
-    return r;
-}
 // the image of u (normal, canonical) on Ed25519 in extended coordinates; ok = false where the reference's modular inverse fails: the
 // Montgomery point has v = 0 (u = 0 reaches it) or u = -1, so that x = sqrt(-486664) u / v or y = (u - 1) / (u + 1) has no value (Z = 0)
 DR_DEV EdPoint ed_ell2_map(const F25& u, bool& ok) {
     using K = Ed25519Ell2;
-    const F25 one = F25::one(), A = F25::constant<K::A>();
+    const F25 one = F25::small(1), A = F25::constant<K::A>();
     F25 tv1 = carry(dbl(sqr(u)));                                            // Z u^2: n
-    tv1 = fe_select(fe_is_zero(add(tv1, one)), F25::zero(), tv1);
+    tv1 = select(is_zero(add(tv1, one)), F25::zero(), tv1);
     const F25 d = carry(add(tv1, one));                                      // n
     const F25 d2 = sqr(d);
     const F25 N = mul(A, sub(mul(F25::constant<K::A2>(), tv1), d2));         // A (A^2 tv1 - d^2): n x (n - n)
@@ -226,22 +220,22 @@ DR_DEV EdPoint ed_ell2_map(const F25& u, bool& ok) {
     const F25 b = mul(nd3, mul(sqr_n(fe_pow_2_250_1(nd7, z11), 2), nd7));
     const F25 vb2 = mul(D, sqr(b));
     const F25 iN = mul(N, F25::constant<Fe25519Consts::SQRT_M1>());
-    const bool w_one = fe_equal(vb2, N), w_neg = fe_is_zero(add(vb2, N)), w_i = fe_equal(vb2, iN);
+    const bool w_one = equal(vb2, N), w_neg = is_zero(add(vb2, N)), w_i = equal(vb2, iN);
     const bool e2 = w_one || w_neg;                                          // gx1 is a square (N != 0: A^2 - 4 is not a square)
-    const F25 f = fe_select(w_one, one, fe_select(w_neg, F25::constant<Fe25519Consts::SQRT_M1>(),
-                                                  fe_select(w_i, F25::constant<K::SQRT_NEG_2I>(), F25::constant<K::SQRT_2I>())));
+    const F25 f = select(w_one, one, select(w_neg, F25::constant<Fe25519Consts::SQRT_M1>(),
+                                            select(w_i, F25::constant<K::SQRT_NEG_2I>(), F25::constant<K::SQRT_2I>())));
     const F25 y1 = mul(b, f);
-    F25 y = fe_select(e2, y1, mul(y1, u));
+    F25 y = select(e2, y1, mul(y1, u));
     uint32_t yw[8];
     fe_pack(y, yw);
     y = carry(cneg(y, e2 != ((yw[0] & 1u) != 0)));
-    const F25 xn = carry(neg(mul(A, fe_select(e2, one, tv1))));              // -A or -A tv1 over d: n
+    const F25 xn = carry(neg(mul(A, select(e2, one, tv1))));                 // -A or -A tv1 over d: n
     // (u, v) = (xn / d, y) on curve25519 -> Ed25519: x = sqrt(-486664) u / v = a / bb, y = (u - 1) / (u + 1) = c / e
     const F25 a = mul(F25::constant<K::SQRT_NEG_A_MINUS_2>(), xn), bb = mul(d, y);
     const F25 c = carry(sub(xn, d)), e = carry(add(xn, d));
     EdPoint r;
     r.x = mul(a, e); r.y = mul(c, bb); r.z = mul(bb, e); r.t = mul(a, c);
-    ok = !fe_is_zero(r.z);
+    ok = !is_zero(r.z);
     return r;
 }
 // out[i] = 8 (the sum of the images of item i's `per_item` field elements) (2: the uniform (RO) encoding, 1: the nonuniform one): the
@@ -281,7 +275,7 @@ __global__ __launch_bounds__(64) void k_fe25519_selftest(const int32_t* __restri
     if (i >= n) return;
     F25 a, b;
 #pragma unroll
-    for (int t = 0; t < FE_L; t++) { a.l[t] = a_limbs[(size_t)i * FE_L + t]; b.l[t] = b_limbs[(size_t)i * FE_L + t]; }
+    for (int t = 0; t < LIMBS29; t++) { a.l[t] = a_limbs[(size_t)i * LIMBS29 + t]; b.l[t] = b_limbs[(size_t)i * LIMBS29 + t]; }
     uint32_t* o = out + (size_t)i * FE_SELFTEST_RECORDS * 8;
     wave_store_fe<Ed25519Curve>(o + 0, mul(a, b));
     wave_store_fe<Ed25519Curve>(o + 8, sqr(a));
@@ -292,12 +286,12 @@ __global__ __launch_bounds__(64) void k_fe25519_selftest(const int32_t* __restri
     wave_store_fe<Ed25519Curve>(o + 48, mul2(a, b, b, a));
     wave_store_fe<Ed25519Curve>(o + 56, fe_inv(a));
     F25 r;
-    const bool sq = fe_sqrt_ratio(a, F25::one(), r);
+    const bool sq = fe_sqrt_ratio(a, F25::small(1), r);
     wave_store_fe<Ed25519Curve>(o + 64, r);
     wave_store_fe<Ed25519Curve>(o + 72, a);
     const bool rt = fe_sqrt_ratio(a, b, r);
     wave_store_fe<Ed25519Curve>(o + 80, r);
-    flags[i] = (sq ? 1u : 0u) | (rt ? 2u : 0u) | (fe_is_larger(a) ? 4u : 0u);
+    flags[i] = (sq ? 1u : 0u) | (rt ? 2u : 0u) | (is_larger(a) ? 4u : 0u);
 }
 
 }  // namespace dr

@@ -124,7 +124,7 @@ struct P256Curve {
     DR_DEV static void load_scalar(const uint32_t* p, uint32_t (&k)[8]) { p256_load_scalar(p, k); }
     DR_DEV static bool below_p(const uint32_t (&w)[8]) { return p256_below_p(w); }
     DR_DEV static bool y_of_x(const F256& x, F256& y) { return p256_y_of_x(x, y); }
-    DR_DEV static bool is_odd(const F256& x) { return fp_is_odd(x); }
+    DR_DEV static bool is_odd(const F256& x) { return dr::is_odd(x); }
 };
 
 // out[i] = k[i] P[i]: wave_curve.hip.h's kernel bodies for this curve
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(P256_BLOCK) void k_p256_decode_points(const uint32_
         is_identity = false;
     }
     // choose the root: the larger iff the flag's bit 7 (canonical), the parity of byte 0 (SEC1)
-    const bool flip = by_parity ? ((yw[0] & 1u) != (first & 1u)) : (fp_is_larger(yw) != want_larger);
+    const bool flip = by_parity ? ((yw[0] & 1u) != (first & 1u)) : (is_larger_words<Fp256Consts>(yw) != want_larger);
     if (flip) y = neg(y);
     if constexpr (MODE != P256_DEC_CODEC) valid = valid && !is_identity;
     if (live) {
@@ -231,8 +231,8 @@ struct P256Sswu : P256Curve {
     DR_DEV static F256 mul_neg_z(const F256& x) { return mul(F256::constant<NEG_Z>(), x); }            // n x (n or s2): n
     DR_DEV static F256 mul_b(const F256& x) { return mul(F256::constant<Fp256Consts::B>(), x); }
     DR_DEV static F256 norm(const F256& x) { return fp_reduce(x); }
-    DR_DEV static bool is_zero(const F256& x) { return fp_is_zero(x); }
-    DR_DEV static bool equal(const F256& x, const F256& y) { return fp_equal(x, y); }
+    DR_DEV static bool is_zero(const F256& x) { return dr::is_zero(x); }
+    DR_DEV static bool equal(const F256& x, const F256& y) { return dr::equal(x, y); }
     DR_DEV static F256 pow_p34(const F256& x) { return fp_pow_p34(x); }
 };
 // out[i] = the sum of the images of item i's `per_item` (1: NU, 2: RO) field elements, as k_secp256k1_map_to_curve: us n x per_item x 8
@@ -256,7 +256,7 @@ __global__ __launch_bounds__(64) void k_p256_field_selftest(const int32_t* __res
     if (i >= n) return;
     F256 a, b;
 #pragma unroll
-    for (int t = 0; t < FP_L; t++) { a.l[t] = a_limbs[(size_t)i * FP_L + t]; b.l[t] = b_limbs[(size_t)i * FP_L + t]; }
+    for (int t = 0; t < LIMBS29; t++) { a.l[t] = a_limbs[(size_t)i * LIMBS29 + t]; b.l[t] = b_limbs[(size_t)i * LIMBS29 + t]; }
     uint32_t* o = out + (size_t)i * P256_SELFTEST_RECORDS * 8;
     wave_store_fe<P256Curve>(o + 0, mul(a, b));
     wave_store_fe<P256Curve>(o + 8, sqr(a));
@@ -274,7 +274,7 @@ __global__ __launch_bounds__(64) void k_p256_field_selftest(const int32_t* __res
     wave_store8(o + 72, w);
     wave_store_fe<P256Curve>(o + 80, fp_reduce(a));
     wave_store_fe<P256Curve>(o + 88, sqr(fp_reduce(a)));
-    flags[i] = (sq ? 1u : 0u) | (fp_is_larger(w) ? 2u : 0u) | ((w[0] & 1u) ? 4u : 0u);
+    flags[i] = (sq ? 1u : 0u) | (is_larger_words<Fp256Consts>(w) ? 2u : 0u) | ((w[0] & 1u) ? 4u : 0u);
 }
 
 }  // namespace dr

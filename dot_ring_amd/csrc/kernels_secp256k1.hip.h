@@ -108,7 +108,7 @@ struct Secp256k1Curve {
     DR_DEV static void load_scalar(const uint32_t* p, uint32_t (&k)[8]) { k1_load_scalar(p, k); }
     DR_DEV static bool below_p(const uint32_t (&w)[8]) { return k1_below_p(w); }
     DR_DEV static bool y_of_x(const FK& x, FK& y) { return k1_y_of_x(x, y); }
-    DR_DEV static bool is_odd(const FK& x) { return fk_is_odd(x); }
+    DR_DEV static bool is_odd(const FK& x) { return dr::is_odd(x); }
 };
 
 // out[i] = k[i] P[i]: wave_curve.hip.h's kernel bodies for this curve
@@ -166,8 +166,8 @@ struct Secp256k1Sswu : Secp256k1Curve {
     DR_DEV static FK mul_neg_z(const FK& x) { return mul_small(x, NEG_Z); }
     DR_DEV static FK mul_b(const FK& x) { return mul_small(x, B); }
     DR_DEV static FK norm(const FK& x) { return carry(x); }
-    DR_DEV static bool is_zero(const FK& x) { return fk_is_zero(x); }
-    DR_DEV static bool equal(const FK& x, const FK& y) { return fk_equal(x, y); }
+    DR_DEV static bool is_zero(const FK& x) { return dr::is_zero(x); }
+    DR_DEV static bool equal(const FK& x, const FK& y) { return dr::equal(x, y); }
     DR_DEV static FK pow_p34(const FK& x) { return fk_pow_p34(x); }
 };
 
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(64) void k_secp256k1_field_selftest(const int32_t* 
     if (i >= n) return;
     FK a, b;
 #pragma unroll
-    for (int t = 0; t < FK_L; t++) { a.l[t] = a_limbs[(size_t)i * FK_L + t]; b.l[t] = b_limbs[(size_t)i * FK_L + t]; }
+    for (int t = 0; t < LIMBS29; t++) { a.l[t] = a_limbs[(size_t)i * LIMBS29 + t]; b.l[t] = b_limbs[(size_t)i * LIMBS29 + t]; }
     uint32_t* o = out + (size_t)i * K1_SELFTEST_RECORDS * 8;
     wave_store_fe<Secp256k1Curve>(o + 0, mul(a, b));
     wave_store_fe<Secp256k1Curve>(o + 8, sqr(a));
