@@ -118,6 +118,14 @@ _PROTOTYPES.update({
     "dr_p256_map_to_curve": (c_int, [c_void_p, c_char_p, c_size_t, c_int, c_char_p, c_char_p]),
     "dr_ed25519_map_to_curve": (c_int, [c_void_p, c_char_p, c_size_t, c_int, c_char_p, c_char_p]),
     "dr_bjj_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
+    "dr_blsg1_hash_to_field_batch": (c_int, [c_int, c_char_p, POINTER(ctypes.c_uint64), c_size_t, c_char_p]),
+    "dr_blsg1_map_to_curve": (c_int, [c_void_p, c_char_p, c_size_t, c_int, c_int, c_char_p, c_char_p]),
+    "dr_blsg1_encode_to_curve_batch": (c_int, [c_void_p, c_int, c_char_p, POINTER(ctypes.c_uint64), c_char_p, POINTER(ctypes.c_uint64), c_size_t,
+                                               c_char_p]),
+    "dr_blsg1_scalar_mul_batch": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_char_p]),
+    "dr_blsg1_msm_groups": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_size_t, c_char_p]),
+    "dr_blsg1_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
+    "dr_blsg1_field_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p, c_void_p]),
     "dr_curve25519_scalar_mul_batch": (c_int, [c_void_p, c_char_p, c_char_p, c_char_p, c_size_t, c_char_p, c_char_p]),
     "dr_curve25519_msm_groups": (c_int, [c_void_p, c_char_p, c_char_p, c_char_p, c_size_t, c_size_t, c_char_p, c_char_p]),
     "dr_curve25519_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
@@ -210,6 +218,8 @@ CURVE_BANDERSNATCH, CURVE_JUBJUB, CURVE_BANDERSNATCH_SW, CURVE_ED25519, CURVE_P2
 CURVE_SECP256K1, CURVE_SECP256K1_NU = 6, 7
 CURVE_P256_RO, CURVE_P256_NU, CURVE_ED25519_RO, CURVE_ED25519_NU = 8, 9, 10, 11
 CURVE_CURVE25519_RO, CURVE_CURVE25519_NU = 13, 14       # (12 is not assigned)
+# BLS12-381 G1 by RFC 9380: 48-byte coordinates, entry points of their own (dr_blsg1_*); every 64-byte entry point refuses these ids
+CURVE_BLS12_381_G1, CURVE_BLS12_381_G1_NU = 15, 16
 # bytes of an encoded point, per curve id (the suites with 33-byte encodings and Curve25519's 64-byte u || v; every other curve's are 32)
 _POINT_LEN = {CURVE_BANDERSNATCH_SW: 33, CURVE_P256: 33, CURVE_SECP256K1: 33, CURVE_SECP256K1_NU: 33, CURVE_P256_RO: 33, CURVE_P256_NU: 33,
               CURVE_CURVE25519_RO: 64, CURVE_CURVE25519_NU: 64}
@@ -291,6 +301,13 @@ def hash_to_field_batch(suite: VrfSuiteStruct, msgs) -> bytes:
     _check(lib().dr_hash_to_field_batch(byref(suite), blob, off, len(msgs), out))
     return out.raw[: (32 if suite.curve in _NU_CURVES else 64) * len(msgs)]
 
+
+def blsg1_hash_to_field_batch(variant: int, msgs) -> bytes:
+    """dr_blsg1_hash_to_field_batch (host only): two elements (96 bytes) per message for CURVE_BLS12_381_G1, one (48) for ..._NU"""
+    blob, off = _ragged([bytes(m) for m in msgs])
+    out = ctypes.create_string_buffer(max(1, 96 * len(msgs)))
+    _check(lib().dr_blsg1_hash_to_field_batch(variant, blob, off, len(msgs), out))
+    return out.raw[: (48 if variant == CURVE_BLS12_381_G1_NU else 96) * len(msgs)]
 
 
 def lib() -> ctypes.CDLL:
@@ -625,6 +642,62 @@ class Context:
     def secp256k1_field_selftest(self, a_limbs: bytes, b_limbs: bytes):
         """dr_secp256k1_field_selftest: (n x 12 x 32 result bytes, n flag bytes) for n pairs of raw 9-limb images."""
         return self._limb_selftest(lib().dr_secp256k1_field_selftest, 12, a_limbs, b_limbs)
+
+    # ---- BLS12-381 G1 (include/dotring_hip.h: points 96 bytes x || y little-endian, 96 zero bytes the identity; scalars as they are)
+    def blsg1_map_to_curve(self, us: bytes, per_item: int, clear: bool = True):
+        """dr_blsg1_map_to_curve: (x||y bytes, flags) for len(us) / (48 per_item) items; clear = False: before the cofactor clearing."""
+        if per_item not in (1, 2) or len(us) % (48 * per_item):
+            raise ValueError("field elements are 48 bytes each, one or two per item")
+        n = len(us) // (48 * per_item)
+        out, ok = ctypes.create_string_buffer(max(1, 96 * n)), ctypes.create_string_buffer(max(1, n))
+        _check(lib().dr_blsg1_map_to_curve(self.handle, us, n, per_item, 1 if clear else 0, out, ok))
+        return out.raw[: 96 * n], ok.raw[:n]
+
+    def blsg1_encode_to_curve_batch(self, variant: int, msgs, salts=None) -> bytes:
+        """dr_blsg1_encode_to_curve_batch: encode_to_curve(salt_i || msg_i) -> count * 96 bytes x||y."""
+        count = len(msgs)
+        m_blob, m_off = _ragged([bytes(m) for m in msgs])
+        s_blob, s_off = (None, None) if not salts or not any(salts) else _ragged([bytes(x) for x in salts])
+        out = ctypes.create_string_buffer(max(96 * count, 1))
+        _check(lib().dr_blsg1_encode_to_curve_batch(self.handle, variant, m_blob, m_off, s_blob, s_off, count, out))
+        return out.raw[: 96 * count]
+
+    def blsg1_scalar_mul_batch(self, pts_xy: bytes, scalars: bytes) -> bytes:
+        """dr_blsg1_scalar_mul_batch: k_i P_i for n points of E(Fq) and n 32-byte scalars used as they are."""
+        n = len(scalars) // 32
+        if len(scalars) != 32 * n or len(pts_xy) != 96 * n:
+            raise ValueError("Points and scalars must have same length")
+        out = ctypes.create_string_buffer(max(1, 96 * n))
+        _check(lib().dr_blsg1_scalar_mul_batch(self.handle, pts_xy, scalars, n, out))
+        return out.raw[: 96 * n]
+
+    def blsg1_msm_groups(self, pts_xy: bytes, scalars: bytes, m: int) -> bytes:
+        """dr_blsg1_msm_groups: the sums of consecutive groups of m (1..64) terms."""
+        n = len(scalars) // 32
+        if m < 1 or len(scalars) != 32 * n or len(pts_xy) != 96 * n or n % m:
+            raise ValueError("Points and scalars must have same length, a multiple of the group size")
+        groups = n // m
+        out = ctypes.create_string_buffer(max(1, 96 * groups))
+        _check(lib().dr_blsg1_msm_groups(self.handle, pts_xy, scalars, groups, m, out))
+        return out.raw[: 96 * groups]
+
+    def blsg1_decode_points(self, enc: bytes, check: bool = True):
+        """dr_blsg1_decode_points: (x||y bytes, flags) for len(enc)/49 SEC1 encodings; check: also r P = O."""
+        if len(enc) % 49:
+            raise ValueError("compressed points are 49 bytes each")
+        count = len(enc) // 49
+        out, ok = ctypes.create_string_buffer(max(1, 96 * count)), ctypes.create_string_buffer(max(1, count))
+        _check(lib().dr_blsg1_decode_points(self.handle, 1 if check else 0, enc, count, out, ok))
+        return out.raw[: 96 * count], ok.raw[:count]
+
+    def blsg1_field_selftest(self, a_limbs: bytes, b_limbs: bytes):
+        """dr_blsg1_field_selftest: (n x 5 x 48 result bytes, n flag bytes) for n pairs of raw 14-limb images (little-endian int32 each)."""
+        n = len(a_limbs) // 56
+        if len(a_limbs) != 56 * n or len(b_limbs) != 56 * n:
+            raise ValueError("operands are 14 int32 limbs each")
+        out, flags = ctypes.create_string_buffer(max(1, 240 * n)), ctypes.create_string_buffer(max(1, n))
+        _check(lib().dr_blsg1_field_selftest(self.handle, a_limbs, b_limbs, n, out, flags))
+        return out.raw[: 240 * n], flags.raw[:n]
 
     def _map_to_curve(self, fn, us: bytes, per_item: int):
         if per_item not in (1, 2) or len(us) % (32 * per_item):

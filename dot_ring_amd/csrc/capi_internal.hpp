@@ -4,6 +4,7 @@
 //   capi_ring.hip   seam C (NTT) and the batched ring prover's phases
 //   capi_batch.hip  native batch orchestration: Pedersen / IETF / Ring-VRF prove and verify
 //   capi_comm.hip   RCCL communicator for the base-sharded MSM
+//   capi_blsg1.hip  the BLS12_381_G1 suites: 48-byte coordinates, hashing to G1 and the group of E(Fq)
 // Each kernel header is included by exactly one of them; the others reach its kernels through the launch wrappers below.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -2,12 +2,14 @@
 // field and point types, the map's constants as compile-time limbs, and the handful of field operations whose names or forms differ
 // between the fields.  kernels_secp256k1.hip.h (Secp256k1Sswu: a map onto an isogenous curve, then the 3-isogeny) and
 // kernels_p256.hip.h (P256Sswu: the map straight onto the curve, ISOGENY = false) each give one description and one kernel; the
-// arithmetic below exists once.  C provides
+// arithmetic below exists once.  kernels_g1_h2c.hip.h (G1hSswu, BLS12-381 G1) takes sswu_map alone: its 11-isogeny, 48-byte coordinates and
+// cofactor clearing have an evaluation and a kernel body of their own there.  C provides
 //   Fe, Point                      the field element and the projective point
 //   ISOGENY                        whether the image lies on an isogenous curve E' (then XN3..YD0, the isogeny's coefficient lists)
 //   a(), z(), sqrt_neg_z(), one()  A of the SWU curve, Z, sqrt(-Z) and 1 as elements (in the field's own form)
-//   mul_neg_z(x), mul_b(x)         |Z| x and B x, normal, for x a normal or a sum of two
-//   norm(x)                        a sum, difference or negation of normals back to what mul / sqr accept on both sides
+//   mul_neg_z(x), mul_b(x)         -Z x and B x for x a normal or a sum of two, in a form mul / sqr accept on both sides (normal where the
+//                                  field reduces small multiples; G1hSswu's -Z x is carried, |value| < 11.2 p, within its mul's 32 p)
+//   norm(x)                        a sum, difference or negation of such values back to what mul / sqr accept on both sides
 //   is_zero, equal, is_odd         on the canonical value (is_odd is sgn0)
 //   pow_p34(x)                     x^((p - 3) / 4), p = 3 mod 4
 //   BLOCK, identity(), add(P, Q), unpack(w), pack(a, w), inv(a)    as wave_curve.hip.h asks them of its description: a curve's SSWU
@@ -21,7 +23,7 @@ namespace dr {
 // Simplified SWU in the inversion-free form of RFC 9380 appendix F.2 with the sqrt_ratio of F.2.1.2 (p = 3 mod 4): one exponentiation,
 // selects instead of branches.  In: u (normal, canonical value) and its parity.  Out: the point (xn / xd, y) of E', xd != 0.  The
 // exceptional case tv2 = Z^2 u^4 + Z u^2 = 0 (u = 0 reaches it) takes xd = Z A, that is x1 = B / (Z A).  Every value is normalised
-// where it is made, so each product below is normal x normal.
+// where it is made, so each operand of a product below is what the field's mul / sqr accept (normal x normal for the 9 x 29-bit fields).
 template <class C>
 DR_DEV void sswu_map(const typename C::Fe& u, bool u_odd, typename C::Fe& xn, typename C::Fe& xd, typename C::Fe& y) {
     using Fe = typename C::Fe;

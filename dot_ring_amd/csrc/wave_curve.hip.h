@@ -1,21 +1,25 @@
-// The wave-per-workgroup scalar-multiplication family of the four native curves (Ed25519, Baby JubJub, P-256, secp256k1) as one set of
-// templates over a description C of the curve: the memory forms, the fixed-schedule scalar multiplication the provers' secret scalars go
+// The wave-per-workgroup scalar-multiplication family of the four native 256-bit curves (Ed25519, Baby JubJub, P-256, secp256k1) and of
+// BLS12-381's E(Fq) (48-byte coordinates) as one set of templates over a description C of the curve: the memory forms, the fixed-schedule scalar multiplication the provers' secret scalars go
 // through, the two kernel bodies built on it, and the SEC1-compressed decoder.  kernels_ed25519.hip.h (Ed25519Curve), kernels_bjj.hip.h
-// (BjjCurve), kernels_p256.hip.h (P256Curve) and kernels_secp256k1.hip.h (Secp256k1Curve) each give a field, a group law, one
-// description and one thin named __global__ per kernel; the schedule below exists once.  C provides
+// (BjjCurve), kernels_p256.hip.h (P256Curve), kernels_secp256k1.hip.h (Secp256k1Curve) and kernels_g1_h2c.hip.h (G1hCurve) each give a
+// field, a group law, one description and one thin named __global__ per kernel; the schedule below exists once.  C provides
 //   Fe, Point                      the field element (int32_t limbs l[]) and the point: members x, y, z and, when EXTENDED, t
+//   WORDS                          the 32-bit words of a coordinate at the ABI: 8, or 12 (a multiple of 4: they move as uint4).  A point is
+//                                  2 WORDS words (x || y); scalars are 8 words whatever the curve
 //   BLOCK, WINDOWS                 the workgroup size (64: one wave) and the number of signed 4-bit windows of a reduced scalar: 64 when
 //                                  the order is below 2^255 (no carry leaves the top digit), 65 otherwise
 //   EXTENDED, LDS_WORDS            whether the point has a fourth coordinate t; the words of one coordinate in the LDS table
-//   ZERO_IS_IDENTITY               whether 64 zero bytes stand for the identity at the ABI (the Weierstrass curves: (0, 0) is no point)
-//   unpack(w), pack(a, w), inv(a)  the ABI's canonical 8 words <-> an element (in the field's own form); a^-1 with 0^-1 = 0
+//   ZERO_IS_IDENTITY               whether zero bytes (64, or 96) stand for the identity at the ABI (the Weierstrass curves: (0, 0) is no point)
+//   unpack(w), pack(a, w), inv(a)  the ABI's canonical WORDS words <-> an element (in the field's own form); a^-1 with 0^-1 = 0
 //   to_lds(a, w), from_lds(w)      a normal coordinate <-> its LDS_WORDS table words (canonical or Montgomery words, or the limb image)
 //   identity(), from_affine(x, y)  the neutral element; the point of affine coordinates
 //   add(P, Q), dbl(P)              the unified / complete addition and the doubling (all coordinates)
 //   dbl_no_t(P)                    when EXTENDED: the doubling without t (three of a window's four doublings are only doubled again)
 //   cneg(P, b)                     -P if b
-//   load_scalar(p, k)              8 words at p reduced mod the group order
-// and, for sec1_decode:  below_p(w), y_of_x(x, y) (a root of the curve equation, false if none), is_odd(y) (of the canonical value).
+//   load_scalar(p, k)              8 words at p reduced mod the group order (G1hCurve: as they are — E(Fq) is not of prime order, and
+//                                  the 65 windows take any 256-bit scalar)
+// and, for sec1_decode:  below_p(w), y_of_x(x, y) (a root of the curve equation, false if none), is_odd(y) (of the canonical value),
+// and with CHECK in_subgroup(x, y).
 #pragma once
 #include "field.hip.h"
 
@@ -38,37 +42,73 @@ DR_DEV void wave_store_zero8(uint32_t* p) {
     const uint32_t z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     wave_store8(p, z);
 }
+// the same for a coordinate of W words (W = 8: the three above)
+template <int W>
+DR_DEV void wave_load_words(const uint32_t* p, uint32_t (&w)[W]) {
+    static_assert(W % 4 == 0, "coordinates move as uint4");
+    if constexpr (W == 8) {
+        wave_load8(p, w);
+    } else {
+        const uint4* q = reinterpret_cast<const uint4*>(p);
+#pragma unroll
+        for (int j = 0; j < W / 4; j++) {
+            const uint4 a = q[j];
+            w[4 * j] = a.x; w[4 * j + 1] = a.y; w[4 * j + 2] = a.z; w[4 * j + 3] = a.w;
+        }
+    }
+}
+template <int W>
+DR_DEV void wave_store_words(uint32_t* p, const uint32_t (&w)[W]) {
+    static_assert(W % 4 == 0, "coordinates move as uint4");
+    if constexpr (W == 8) {
+        wave_store8(p, w);
+    } else {
+        uint4* q = reinterpret_cast<uint4*>(p);
+#pragma unroll
+        for (int j = 0; j < W / 4; j++) q[j] = make_uint4(w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]);
+    }
+}
+template <int W>
+DR_DEV void wave_store_zero_words(uint32_t* p) {
+    if constexpr (W == 8) {
+        wave_store_zero8(p);
+    } else {
+        uint4* q = reinterpret_cast<uint4*>(p);
+#pragma unroll
+        for (int j = 0; j < W / 4; j++) q[j] = make_uint4(0, 0, 0, 0);
+    }
+}
 
 // ---------------------------------------------------------------- memory
 template <class C>
 DR_DEV typename C::Fe wave_load_fe(const uint32_t* p) {
-    uint32_t w[8];
-    wave_load8(p, w);
+    uint32_t w[C::WORDS];
+    wave_load_words(p, w);
     return C::unpack(w);
 }
 template <class C>
 DR_DEV void wave_store_fe(uint32_t* p, const typename C::Fe& a) {
-    uint32_t w[8];
+    uint32_t w[C::WORDS];
     C::pack(a, w);
-    wave_store8(p, w);
+    wave_store_words(p, w);
 }
-// x || y of the point; where the identity has Z = 0, x = y = 0 after the multiplication by 0^-1 = 0: it stores 64 zero bytes
+// x || y of the point; where the identity has Z = 0, x = y = 0 after the multiplication by 0^-1 = 0: it stores zero bytes
 template <class C>
 DR_DEV void wave_store_affine(uint32_t* out, const typename C::Point& acc) {
     const typename C::Fe zi = C::inv(acc.z);
     wave_store_fe<C>(out, mul(acc.x, zi));
-    wave_store_fe<C>(out + 8, mul(acc.y, zi));
+    wave_store_fe<C>(out + C::WORDS, mul(acc.y, zi));
 }
-// One term of a batch: the point of affine x || y (16 words, canonical) at pt and the scalar at kp, reduced into k.  The scalar is
+// One term of a batch: the point of affine x || y (2 WORDS words, canonical) at pt and the scalar at kp, reduced into k.  The scalar is
 // reduced before the point is built from its coordinates (an extended point costs a product that nothing needs across that loop).
 template <class C>
 DR_DEV typename C::Point wave_load_term(const uint32_t* pt, const uint32_t* kp, uint32_t (&k)[8]) {
-    uint32_t x[8], y[8];
-    wave_load8(pt, x);
-    wave_load8(pt + 8, y);
+    uint32_t x[C::WORDS], y[C::WORDS];
+    wave_load_words(pt, x);
+    wave_load_words(pt + C::WORDS, y);
     [[maybe_unused]] uint32_t o = 0;
 #pragma unroll
-    for (int j = 0; j < 8; j++) o |= x[j] | y[j];
+    for (int j = 0; j < C::WORDS; j++) o |= x[j] | y[j];
     const typename C::Fe px = C::unpack(x), py = C::unpack(y);
     C::load_scalar(kp, k);
     typename C::Point r = C::from_affine(px, py);
@@ -193,7 +233,7 @@ DR_DEV typename C::Point wave_scalar_mul_core(uint32_t* tab, int lane, const typ
     return acc;
 }
 
-// out[i] = k[i] P[i].  pts: n x 16 words (x || y), ks: n x 8, out: n x 16.  One lane per multiplication.
+// out[i] = k[i] P[i].  pts: n x 2 WORDS words (x || y), ks: n x 8, out: n x 2 WORDS.  One lane per multiplication.
 template <class C>
 DR_DEV void wave_scalar_mul(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks, uint32_t* __restrict__ out, uint32_t n) {
     __shared__ uint32_t tab[wave_table_words<C>()];
@@ -202,9 +242,9 @@ DR_DEV void wave_scalar_mul(const uint32_t* __restrict__ pts, const uint32_t* __
     const bool live = i < n;
     if (!live) i = n - 1;            // keep the wave converged; the duplicate result is not stored
     uint32_t k[8];
-    const typename C::Point P = wave_load_term<C>(pts + (size_t)i * 16, ks + (size_t)i * 8, k);
+    const typename C::Point P = wave_load_term<C>(pts + (size_t)i * (2 * C::WORDS), ks + (size_t)i * 8, k);
     const typename C::Point acc = wave_scalar_mul_core<C>(tab, lane, P, k);
-    if (live) wave_store_affine<C>(out + (size_t)i * 16, acc);
+    if (live) wave_store_affine<C>(out + (size_t)i * (2 * C::WORDS), acc);
 }
 
 // out[g] = sum_{j<m} k[g m + j] P[g m + j]: one lane per term (m padded to mpad, a power of two <= 64), folded with shuffles by the
@@ -221,50 +261,55 @@ DR_DEV void wave_msm_groups(const uint32_t* __restrict__ pts, const uint32_t* __
     const bool live = g < groups && j < m;
     const size_t idx = live ? (size_t)g * m + j : 0;          // dead lanes recompute term 0 and are masked out
     uint32_t k[8];
-    const Point P = wave_load_term<C>(pts + idx * 16, ks + idx * 8, k);
+    const Point P = wave_load_term<C>(pts + idx * (2 * C::WORDS), ks + idx * 8, k);
     const Point r = wave_scalar_mul_core<C>(tab, lane, P, k);
     Point acc = live ? r : C::identity();
 #pragma unroll 1
     for (uint32_t s = mpad >> 1; s > 0; s >>= 1) acc = C::add(acc, wave_shfl_down<C>(acc, s));
-    if (g < groups && j == 0) wave_store_affine<C>(out + (size_t)g * 16, acc);
+    if (g < groups && j == 0) wave_store_affine<C>(out + (size_t)g * (2 * C::WORDS), acc);
 }
 
 // ---------------------------------------------------------------- SEC1 compressed points
-// x = bytes 1..32 of a 33-byte string (9 words, bytes 33..35 zero) read BIG-endian: little-endian word q is the byte swap of the
-// (unaligned) word at byte 29 - 4 q
-DR_DEV void sec1_x_words(const uint32_t (&w)[9], uint32_t (&xb)[8]) {
+// x = bytes 1..4 W of a (4 W + 1)-byte string (W + 1 words, the last three bytes zero; W = 8: 33 bytes, W = 12: 49) read BIG-endian:
+// little-endian word q is the byte swap of the (unaligned) word at byte 4 W - 3 - 4 q
+template <int W>
+DR_DEV void sec1_x_words(const uint32_t (&w)[W + 1], uint32_t (&xb)[W]) {
 #pragma unroll
-    for (int q = 0; q < 8; q++) {
-        const int k = 7 - q;
+    for (int q = 0; q < W; q++) {
+        const int k = W - 1 - q;
         xb[q] = __builtin_bswap32((w[k] >> 8) | (w[k + 1] << 24));
     }
 }
-// One lane per 33-byte SEC1 compressed encoding padded to 9 words: byte 0 is 0x02 or 0x03, x < p, the curve equation has a root, y the
-// root of byte 0's parity (y = 0 cannot happen: the group orders are odd).  out = x || y and ok = 1, or 64 zero bytes and ok = 0.
-template <class C>
-DR_DEV void sec1_decode(const uint32_t* __restrict__ enc /* n*9 */, uint32_t* __restrict__ out_xy /* n*16 */, uint32_t* __restrict__ ok,
-                        uint32_t n) {
+// One lane per SEC1 compressed encoding (33 or 49 bytes) padded to WORDS + 1 words: byte 0 is 0x02 or 0x03, x < p, the curve equation
+// has a root, y the root of byte 0's parity (y = 0 cannot happen: the group orders are odd).  With CHECK the point must also pass the
+// description's in_subgroup (curves with a cofactor; the point is computed either way, so the wave stays converged).  out = x || y and
+// ok = 1, or zero bytes and ok = 0.
+template <class C, bool CHECK = false>
+DR_DEV void sec1_decode(const uint32_t* __restrict__ enc /* n*(WORDS+1) */, uint32_t* __restrict__ out_xy /* n*2*WORDS */,
+                        uint32_t* __restrict__ ok, uint32_t n) {
+    constexpr int W = C::WORDS;
     uint32_t i = blockIdx.x * C::BLOCK + threadIdx.x;
     const bool live = i < n;
     if (!live) i = n - 1;
-    uint32_t w[9];
+    uint32_t w[W + 1];
 #pragma unroll
-    for (int j = 0; j < 9; j++) w[j] = enc[(size_t)i * 9 + j];
+    for (int j = 0; j < W + 1; j++) w[j] = enc[(size_t)i * (W + 1) + j];
     const uint32_t first = w[0] & 0xffu;
-    uint32_t xb[8];
-    sec1_x_words(w, xb);
+    uint32_t xb[W];
+    sec1_x_words<W>(w, xb);
     const typename C::Fe x = C::unpack(xb);
     typename C::Fe y;
     const bool root = C::y_of_x(x, y);
-    const bool valid = (first == 0x02u || first == 0x03u) && C::below_p(xb) && root;
+    bool valid = (first == 0x02u || first == 0x03u) && C::below_p(xb) && root;
     if (C::is_odd(y) != ((first & 1u) != 0)) y = neg(y);
+    if constexpr (CHECK) valid = C::in_subgroup(x, y) && valid;
     if (live) {
         if (valid) {
-            wave_store8(out_xy + (size_t)i * 16, xb);
-            wave_store_fe<C>(out_xy + (size_t)i * 16 + 8, y);
+            wave_store_words(out_xy + (size_t)i * (2 * W), xb);
+            wave_store_fe<C>(out_xy + (size_t)i * (2 * W) + W, y);
         } else {
-            wave_store_zero8(out_xy + (size_t)i * 16);
-            wave_store_zero8(out_xy + (size_t)i * 16 + 8);
+            wave_store_zero_words<W>(out_xy + (size_t)i * (2 * W));
+            wave_store_zero_words<W>(out_xy + (size_t)i * (2 * W) + W);
         }
         ok[i] = valid ? 1u : 0u;
     }

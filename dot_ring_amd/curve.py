@@ -670,15 +670,12 @@ class P256Point:
         return unpack_points(cls, runtime.context().encode_to_curve_batch(cls._suite_struct(), list(alpha_strings), salts))
 
 
-class Secp256k1Point:
-    """Affine point of secp256k1 (dot_ring/curve/specs/secp256k1.py): y^2 = x^3 + 7 over its own field, cofactor 1, the identity is
-    (None, None).  Single additions are host big-int code; scalar multiplications, MSMs, decoding and hashing to the curve (RFC 9380:
-    simplified SWU and the 3-isogeny) run on the GPU under the suite's curve id (kernels_secp256k1.hip.h)."""
+class ShortWeierstrassA0Point:
+    """Affine point of a curve y^2 = x^3 + b (a = 0) over a prime field, the identity (None, None): the coordinates, equality and the
+    host big-int group law (sw_affine_point.py) that secp256k1 and BLS12-381's E(Fq) share.  A subclass gives _P, _N, _SW_B and
+    everything that runs on its own kernels.  Points of different curves neither compare equal nor add."""
     curve: BandersnatchCurve
-    _P = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEFFFFFC2F
-    _N = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141
-    _H, _CV = 1, _native.CURVE_SECP256K1
-    _SW_A, _SW_B = 0, 7
+    _SW_A = 0
     __slots__ = ("x", "y")
 
     def __init__(self, x, y):
@@ -702,7 +699,7 @@ class Secp256k1Point:
         return pt
 
     def __eq__(self, other):
-        return isinstance(other, Secp256k1Point) and self.x == other.x and self.y == other.y
+        return isinstance(other, ShortWeierstrassA0Point) and self._P == other._P and self.x == other.x and self.y == other.y
 
     def __hash__(self):
         return 0 if self.x is None else (self.x + self.y) % self._N
@@ -726,7 +723,7 @@ class Secp256k1Point:
 
     # -- group law (sw_affine_point.py)
     def __add__(self, other):
-        if not isinstance(other, Secp256k1Point):
+        if not isinstance(other, ShortWeierstrassA0Point) or other._P != self._P:
             raise TypeError("Can only add SWAffinePoint instances")
         if self.is_identity():
             return other
@@ -752,6 +749,17 @@ class Secp256k1Point:
 
     def __sub__(self, other):
         return self + (-other)
+
+
+class Secp256k1Point(ShortWeierstrassA0Point):
+    """Affine point of secp256k1 (dot_ring/curve/specs/secp256k1.py): y^2 = x^3 + 7 over its own field, cofactor 1, the identity is
+    (None, None).  Single additions are host big-int code; scalar multiplications, MSMs, decoding and hashing to the curve (RFC 9380:
+    simplified SWU and the 3-isogeny) run on the GPU under the suite's curve id (kernels_secp256k1.hip.h)."""
+    _P = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEFFFFFC2F
+    _N = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141
+    _H, _CV = 1, _native.CURVE_SECP256K1
+    _SW_B = 7
+    __slots__ = ()
 
     def __mul__(self, scalar: int):
         """secp256k1.py:85-93: the scalar reduced mod n (a negative one through -P), 0 gives the identity"""
@@ -857,6 +865,187 @@ class Secp256k1Point:
             return []
         # (a vanishing isogeny denominator comes back as DR_ERR_INVALID: a ValueError, as the reference's failing modular inverse is)
         return unpack_points(cls, runtime.context().encode_to_curve_batch(cls._suite_struct(), list(alpha_strings), salts))
+
+
+class Bls12381G1Point(ShortWeierstrassA0Point):
+    """Affine point of E(Fq): y^2 = x^3 + 4 over BLS12-381's 381-bit base field (dot_ring/curve/specs/bls12_381_G1.py), the identity is
+    (None, None).  It has Secp256k1Point's surface (the host big-int additions are the shared a = 0 base class's) with 48-byte
+    coordinates.  E(Fq) has order h r: a point need not lie in G1, so scalars are NEVER reduced mod r — `P * k` is exact for every
+    integer k and every point.  Scalar multiplications, MSMs, decoding of compressed strings and hashing to the curve (RFC 9380:
+    simplified SWU, the 11-isogeny, h_eff) run on the GPU (kernels_g1_h2c.hip.h, the dr_blsg1_* entry points)."""
+    _P = 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB
+    _N = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
+    _H = 0xD201000000010001                              # h_eff of RFC 9380 8.8.1: the reference's `cofactor`, what clear_cofactor multiplies by
+    _COFACTOR = 0x396C8C005555E1568C00AAAB0000AAAB       # #E(Fq) = _COFACTOR * _N
+    _CV = _native.CURVE_BLS12_381_G1
+    _SW_B = 4
+    __slots__ = ()
+
+    # -- kernels: points cross as x || y, 48 + 48 bytes little-endian, 96 zero bytes the identity; scalars as they are
+    @staticmethod
+    def _pack(points) -> bytes:
+        return b"".join((p.x or 0).to_bytes(48, "little") + (p.y or 0).to_bytes(48, "little") for p in points)
+
+    @classmethod
+    def _unpack(cls, raw: bytes):
+        frm, mk = int.from_bytes, cls._trusted
+        return [mk(frm(raw[i : i + 48], "little"), frm(raw[i + 48 : i + 96], "little")) for i in range(0, len(raw), 96)]
+
+    @classmethod
+    def _terms(cls, points, scalars):
+        """(points, scalars below 2^256) with the same sum of products: a scalar outside [0, 2^256) is reduced mod #E(Fq) = h r (381
+        bits, the exponent of every point) and, if still 2^256 or more, split as k_lo + 2^192 k_hi over P and 2^192 P"""
+        pts, ks, wide = [], [], []
+        for pt, k in zip(points, scalars):
+            k = int(k)
+            if not 0 <= k < 1 << 256:
+                k %= cls._COFACTOR * cls._N
+            if k < 1 << 256:
+                pts.append(pt)
+                ks.append(k)
+            else:
+                wide.append((pt, k))
+        if wide:
+            shifted = cls._unpack(runtime.context().blsg1_scalar_mul_batch(cls._pack([pt for pt, _ in wide]),
+                                                                           (1 << 192).to_bytes(32, "little") * len(wide)))
+            for (pt, k), hi in zip(wide, shifted):
+                pts += [pt, hi]
+                ks += [k & ((1 << 192) - 1), k >> 192]
+        return pts, ks
+
+    def __mul__(self, scalar: int):
+        """exact for every integer: negative k negates, 0 <= k < 2^256 is one kernel entry, larger k goes mod h r through two terms"""
+        k = int(scalar)
+        if k < 0:
+            return (-self) * (-k)
+        pts, ks = self._terms([self], [k])
+        if len(pts) == 1:
+            raw = runtime.context().blsg1_scalar_mul_batch(self._pack(pts), ks[0].to_bytes(32, "little"))
+        else:
+            raw = runtime.context().blsg1_msm_groups(self._pack(pts), b"".join(v.to_bytes(32, "little") for v in ks), 2)
+        return self._unpack(raw)[0]
+
+    __rmul__ = __mul__
+
+    @classmethod
+    def msm(cls, points, scalars):
+        """sum k_i P_i for any integers k_i: groups of up to 64 terms in one launch, then their partial sums the same way"""
+        if len(points) != len(scalars):
+            raise ValueError("Points and scalars must have same length")
+        pts, ks = cls._terms(points, scalars)
+        if not pts:
+            return cls.identity()
+        while True:
+            parts = -(-len(pts) // 64)
+            m = len(pts) if parts == 1 else 64
+            pad = parts * m - len(pts)                                     # padding: 0 * identity
+            raw = runtime.context().blsg1_msm_groups(cls._pack(pts) + bytes(96 * pad),
+                                                     b"".join(v.to_bytes(32, "little") for v in ks) + bytes(32 * pad), m)
+            pts = cls._unpack(raw)
+            if parts == 1:
+                return pts[0]
+            ks = [1] * parts
+
+    def clear_cofactor(self):
+        return self * self._H
+
+    # -- codec: SEC1 (sw_affine_point.py point_to_string / string_to_point), 48-byte coordinates
+    def point_to_string(self, compressed: bool = True) -> bytes:
+        if self.is_identity():
+            return b"\x00"
+        x = self.x.to_bytes(48, "big")
+        if compressed:
+            return (b"\x03" if self.y % 2 else b"\x02") + x
+        return b"\x04" + x + self.y.to_bytes(48, "big")
+
+    @classmethod
+    def string_to_point(cls, data):
+        """the forms the reference accepts: 0x00 (identity), 0x02 / 0x03 (compressed: the decode kernel), 0x04 (uncompressed), 0x06 / 0x07
+        (hybrid: both coordinates and the parity of y); any point of E(Fq) decodes, in G1 or not (curve.valid_point asks that)"""
+        if isinstance(data, str):
+            data = bytes.fromhex(data)
+        data = bytes(data)
+        if len(data) == 0:
+            raise ValueError("Empty octet string")
+        prefix, p = data[0], cls._P
+        if prefix == 0x00:
+            if len(data) != 1:
+                raise ValueError("Point at infinity must be single byte 0x00")
+            return cls.identity()
+        if prefix in (0x02, 0x03):
+            if len(data) != 49:
+                raise ValueError(f"Invalid compressed point length: expected 49, got {len(data)}")
+            x = int.from_bytes(data[1:], "big")
+            if x >= p:
+                raise ValueError(f"x-coordinate {x} is not in field Fp (p={p})")
+            raw, ok = runtime.context().blsg1_decode_points(data, check=False)
+            if not ok[0]:
+                raise ValueError("Invalid point encoding")
+            return cls._unpack(raw)[0]
+        if prefix in (0x04, 0x06, 0x07):
+            if len(data) != 97:
+                kind = "uncompressed" if prefix == 0x04 else "hybrid"
+                raise ValueError(f"Invalid {kind} point length: expected 97, got {len(data)}")
+            x, y = int.from_bytes(data[1:49], "big"), int.from_bytes(data[49:], "big")
+            if x >= p:
+                raise ValueError(f"x-coordinate {x} is not in field Fp (p={p})")
+            if y >= p:
+                raise ValueError(f"y-coordinate {y} is not in field Fp (p={p})")
+            if prefix != 0x04 and y % 2 != prefix % 2:
+                raise ValueError("Hybrid format: y parity doesn't match prefix")
+            if not cls._on_curve(x, y):
+                raise ValueError(f"Point ({x}, {y}) is not on curve")
+            return cls(x, y)
+        raise ValueError(f"Invalid point encoding prefix: 0x{prefix:02x}")
+
+    # -- hash to curve (RFC 9380 BLS12381G1_XMD:SHA-256_SSWU_RO_ / _NU_): expand_message_xmd natively on the host, the map on the GPU
+    @classmethod
+    def _per_item(cls) -> int:
+        return 1 if cls.curve.params.e2c == "sswu_nu" else 2
+
+    @classmethod
+    def encode_to_curve(cls, alpha_string: bytes, salt: bytes = b""):
+        return cls.encode_to_curve_batch([alpha_string], [salt])[0]
+
+    @classmethod
+    def _mapped(cls, us: bytes, per_item: int, clear: bool = True):
+        raw, ok = runtime.context().blsg1_map_to_curve(us, per_item, clear)
+        if 0 in ok:
+            raise ValueError("base is not invertible for the given modulus")      # pow(x_den, -1, p) of apply_isogeny
+        return cls._unpack(raw)
+
+    @classmethod
+    def map_to_curve_simple_swu(cls, u: int):
+        """one image on E, before the cofactor clearing (a point of E(Fq), in general outside G1)"""
+        return cls._mapped((int(u) % cls._P).to_bytes(48, "little"), 1, clear=False)[0]
+
+    @classmethod
+    def hash_to_field_pairs(cls, alpha_strings, salts=None) -> bytes:
+        """Host half of encode_to_curve for many inputs: two 48-byte field elements per input (one for the NU variant), little-endian."""
+        salts = salts or [b""] * len(alpha_strings)
+        return _native.blsg1_hash_to_field_batch(cls._CV, [bytes(s) + bytes(a) for a, s in zip(alpha_strings, salts)])
+
+    @classmethod
+    def encode_to_curve_from_field(cls, us: bytes):
+        """Device half: the maps, for RO the sum of the two images, and the multiplication by h_eff."""
+        return cls._mapped(us, cls._per_item()) if us else []
+
+    @classmethod
+    def encode_to_curve_batch(cls, alpha_strings, salts=None):
+        if not alpha_strings:
+            return []
+        return cls._unpack(runtime.context().blsg1_encode_to_curve_batch(cls._CV, list(alpha_strings), salts))
+
+    @classmethod
+    def _valid_points(cls, points) -> list[bool]:
+        """the reference's valid_point for a batch: on the curve, not the identity and r P = O — the CHECK mode of the decoder"""
+        live = [i for i, pt in enumerate(points) if not pt.is_identity() and pt.is_on_curve()]
+        out = [False] * len(points)
+        if live:
+            _, ok = runtime.context().blsg1_decode_points(b"".join(points[i].point_to_string() for i in live), check=True)
+            for i, flag in zip(live, ok):
+                out[i] = bool(flag)
+        return out
 
 
 class P256SswuPoint(P256Point):
@@ -1176,6 +1365,11 @@ def scalar_mul_batch(points, scalars):
     if not points:
         return []
     cls = type(points[0])
+    if issubclass(cls, Bls12381G1Point):         # 48-byte coordinates and unreduced scalars: its own entry point
+        pts, ks = cls._terms(points, scalars)
+        if len(pts) != len(points):              # a scalar of 2^256 or more became two terms: point by point
+            return [p * k for p, k in zip(points, scalars)]
+        return cls._unpack(runtime.context().blsg1_scalar_mul_batch(cls._pack(pts), b"".join(k.to_bytes(32, "little") for k in ks)))
     first = points[0]
     if all(p is first for p in points) and (first.x, first.y) in _fixed_bases(cls):
         # k_i * G (key derivation, curve.py:384) or k_i * B: the constant's fixed-base window table — 64 table additions
@@ -1198,12 +1392,16 @@ def msm_groups(points, scalars, m: int):
     if not points:
         return []
     cls = type(points[0])
+    if issubclass(cls, Bls12381G1Point):
+        return [cls.msm(points[i : i + m], scalars[i : i + m]) for i in range(0, len(points), m)]
     raw = runtime.context().bsn_msm_groups(pack_points(points), pack_scalars(scalars, cls._N), m, cls._CV)
     return unpack_points(cls, raw)
 
 
 def valid_points(points) -> list[bool]:
     """curve.py:56 for a whole batch: [h]P != O and [h^-1 mod n][h]P == P (h the cofactor), one launch for all points."""
+    if points and isinstance(points[0], Bls12381G1Point):      # E(Fq) is not h x (prime) for a small h: the decoder's r P = O
+        return type(points[0])._valid_points(points)
     live = [i for i, p in enumerate(points) if not p.is_identity() and p.is_on_curve()]
     out = [False] * len(points)
     if not live:
@@ -1252,7 +1450,7 @@ class CurveVariant:
         self.name, self.curve, self.point_type = name, curve, point_type
 
     def point(self, x, y=None):
-        if isinstance(x, (BandersnatchPoint, BandersnatchSWPoint, P256Point, Secp256k1Point, Curve25519Point)):
+        if isinstance(x, (BandersnatchPoint, BandersnatchSWPoint, P256Point, ShortWeierstrassA0Point, Curve25519Point)):
             return x
         if y is None:
             x, y = x
@@ -1486,3 +1684,32 @@ Curve25519 = Curve25519_RO
 Secp256k1_RO = _secp256k1_variant("Secp256k1_RO", "sswu", _native.CURVE_SECP256K1)
 Secp256k1_NU = _secp256k1_variant("Secp256k1_NU", "sswu_nu", _native.CURVE_SECP256K1_NU)
 Secp256k1 = Secp256k1_RO
+
+
+# dot_ring/curve/specs/bls12_381_G1.py: E: y^2 = x^3 + 4 over the 381-bit Fq, #E(Fq) = h r, hashing by RFC 9380's
+# BLS12381G1_XMD:SHA-256_SSWU_RO_ (two field elements) or ..._NU_ (one), `cofactor` = h_eff; both variants carry the RO suite id, as in the
+# reference.  Encoding(point_len=32, challenge_len=48) are the reference's own figures; its points encode to 49 bytes, which point_len =
+# 32 contradicts, so the reference can decode no key or proof of this curve — the VRF classes refuse these two suites (vrf/base.py) and
+# what is served is the point type and curve.valid_point.  No auxiliary points, not twisted Edwards: RingProofParams refuses them too.
+def _bls12_381_g1_variant(name: str, e2c: str, curve_id: int) -> CurveVariant:
+    params = SuiteParams(
+        suite_id=b"BLS12381G1_XMD:SHA-256_SSWU_RO_", hash_fn=hashlib.sha256, xof=False,
+        auxiliary_points=AuxiliaryPoints(None, None, None),
+        field_modulus=Bls12381G1Point._P,
+        subgroup_order=Bls12381G1Point._N,
+        cofactor=Bls12381G1Point._H,
+        a=0,
+        d=0,
+        generator=(0x17F1D3A73197D7942695638C4FA9AC0FC3688C4F9774B905A14E3A3F171BAC586C55E83FF97A1AEFFB3AF00ADB22C6BB,
+                   0x08B3F481E3AAA0F1A09E30ED741D8AE4FCF5E095D5D00AF600DB18CB2C04B3EDD03CC744A2888AE40CAA232946C5E7E1),
+        encoding=Encoding(point_len=32, challenge_len=48),
+        curve_id=curve_id,
+        e2c=e2c,
+    )
+    curve = BandersnatchCurve(params)
+    return CurveVariant(name, curve, type(f"{name}Point", (Bls12381G1Point,), {"__slots__": (), "curve": curve, "_CV": curve_id}))
+
+
+BLS12_381_G1_RO = _bls12_381_g1_variant("BLS12_381_G1_RO", "sswu", _native.CURVE_BLS12_381_G1)
+BLS12_381_G1_NU = _bls12_381_g1_variant("BLS12_381_G1_NU", "sswu_nu", _native.CURVE_BLS12_381_G1_NU)
+BLS12_381_G1 = BLS12_381_G1_RO

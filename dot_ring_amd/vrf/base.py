@@ -3,6 +3,7 @@
 dataclass equality between proofs works and per-class memos survive."""
 from __future__ import annotations
 
+from .. import _native
 from ..curve import CurveVariant
 
 _BOUND: dict = {}
@@ -19,6 +20,10 @@ class VRF:
     def __class_getitem__(cls, variant):
         if not isinstance(variant, CurveVariant):
             return cls
+        if variant.curve.params.curve_id in (_native.CURVE_BLS12_381_G1, _native.CURVE_BLS12_381_G1_NU):
+            # a deliberate deviation: the reference binds the class and can then decode nothing
+            raise ValueError(f"{cls.__name__} has no {variant.name} suite: the reference's point length for this curve is 32 while its points "
+                             "encode to 49 bytes, so no key or proof of it can be decoded")
         bound = _BOUND.get((cls, variant.name))
         if bound is None or bound.cv is not variant:
             bound = _BOUND[(cls, variant.name)] = type(f"{cls.__name__}[{variant.name}]", (cls,), {"cv": variant})

@@ -277,6 +277,50 @@ DR_API int dr_bjj_decode_points(dr_ctx *ctx, int check, const uint8_t *enc /* n*
 DR_API int dr_bjj_field_ops_selftest(dr_ctx *ctx, const int32_t *a_limbs /* n*9 */, const int32_t *b_limbs /* n*9 */, size_t n,
                                      uint8_t *out /* n*384 */, uint8_t *flags /* n */);
 
+/* DR_CURVE_BLS12_381_G1 (the reference's BLS12_381_G1 = BLS12_381_G1_RO) and DR_CURVE_BLS12_381_G1_NU (BLS12_381_G1_NU): hashing to
+ * BLS12-381's G1 by RFC 9380 (dot_ring/curve/specs/bls12_381_G1.py: E: y^2 = x^3 + 4 over the 381-bit Fq, #E(Fq) = h r,
+ * BLS12381G1_XMD:SHA-256_SSWU_RO_ / _NU_: simplified SWU onto the 11-isogenous curve with Z = 11, the isogeny back, the sum of two images
+ * for RO and one for NU, then times h_eff = 0xd201000000010001) and the group of E(Fq) — csrc/kernels_g1_h2c.hip.h over the device's Fq
+ * (csrc/fq28.hip.h).  The FIRST curve here whose coordinates are 48 bytes, so it has entry points of its own (dr_blsg1_*) and EVERY
+ * 64-byte entry point refuses these two ids with DR_ERR_INVALID: dr_te_*, dr_encode_to_curve_batch, dr_hash_to_field_batch, the provers
+ * and verifiers, the ring calls, GLV and dr_bsn_*.  There is no VRF over these suites: the reference's point length for this curve (32)
+ * contradicts the 49 bytes its points encode to, so no key or proof of it can be decoded.
+ *
+ * POINTS are affine x || y, 48 + 48 bytes LITTLE-endian, canonical standard form; 96 zero bytes are the identity ((0, 0) is not on the
+ * curve).  This is NOT the big-endian record of dr_g1_msm* / dr_srs_* below (seam B), which stays as it is.  A point may be ANY point of
+ * E(Fq), in G1 or not: SCALARS are 32 bytes little-endian used AS THEY ARE (0 <= k < 2^256, never reduced mod r).
+ *   dr_blsg1_hash_to_field_batch    host only: expand_message_xmd over SHA-256 (Z_pad 64 bytes), L = 64 bytes per element, big-endian, mod
+ *                                   p, with the DST of `variant` (one of the two curve ids): two elements per message for RO, one for
+ *                                   NU, 48 bytes little-endian each.  msgs / off as dr_hash_to_field_batch (off: count + 1 offsets).
+ *   dr_blsg1_map_to_curve           n items of per_item (2 or 1) elements below p: out_xy[i] = the sum of their images, times h_eff if
+ *                                   clear (clear = 0: the reference's map_to_curve_simple_swu, the Q0 / Q1 / Q of RFC 9380's vectors).
+ *                                   ok[i] = 0 where a denominator of the isogeny vanishes (the reference's modular inverse raises).
+ *                                   Elements at or above p and other per_item are refused with DR_ERR_INVALID.
+ *   dr_blsg1_encode_to_curve_batch  encode_to_curve(salt_i || msg_i) (salts nullable): hash_to_field on the worker threads and one map
+ *                                   launch; DR_ERR_INVALID if a map has no value.
+ *   dr_blsg1_scalar_mul_batch       out[i] = k[i] P[i];  dr_blsg1_msm_groups  out[g] = sum_{j<m} k[g m + j] P[g m + j], m <= 64
+ *   dr_blsg1_decode_points          49-byte SEC1 compressed strings (0x02 / 0x03 by the parity of y, then x BIG-endian, x < p, x^3 + 4 a
+ *                                   square).  check = 0 accepts every point of E(Fq), as the reference's string_to_point; check = 1
+ *                                   also demands r P = O (the reference's valid_point).  out_xy[i] = the point, or 96 zero bytes.
+ *   dr_blsg1_field_selftest         diagnostic: what kernels_g1_h2c.hip.h adds to the field, on RAW limb images (14 signed 32-bit limbs
+ *                                   each, value sum l[i] 2^(28 i), standing for value 2^-392 mod p).  out: n x 5 x 48 bytes, each the
+ *                                   canonical little-endian value r 2^-392 mod p of: a^((p - 3) / 4); its product with a if that is a
+ *                                   root of a, else 0; select(i odd, a, b); 12 a (lazy additions and carries); a b + b a (fused).
+ *                                   flags[i]: bit 0 a is a square, bit 1 the canonical a 2^-392 mod p is odd (sgn0), bit 2 a is zero. */
+enum { DR_CURVE_BLS12_381_G1 = 15, DR_CURVE_BLS12_381_G1_NU = 16 };
+DR_API int dr_blsg1_hash_to_field_batch(int variant, const uint8_t *msgs, const uint64_t *off, size_t count, uint8_t *out /* count*(96|48) */);
+DR_API int dr_blsg1_map_to_curve(dr_ctx *ctx, const uint8_t *us /* n*per_item*48 */, size_t n, int per_item, int clear,
+                                 uint8_t *out_xy /* n*96 */, uint8_t *ok /* n */);
+DR_API int dr_blsg1_encode_to_curve_batch(dr_ctx *ctx, int variant, const uint8_t *msgs, const uint64_t *off, const uint8_t *salts,
+                                          const uint64_t *salt_off, size_t count, uint8_t *out_xy /* count*96 */);
+DR_API int dr_blsg1_scalar_mul_batch(dr_ctx *ctx, const uint8_t *pts_xy /* n*96 */, const uint8_t *scalars /* n*32 */, size_t n,
+                                     uint8_t *out_xy /* n*96 */);
+DR_API int dr_blsg1_msm_groups(dr_ctx *ctx, const uint8_t *pts_xy /* groups*m*96 */, const uint8_t *scalars /* groups*m*32 */, size_t groups,
+                               size_t m, uint8_t *out_xy /* groups*96 */);
+DR_API int dr_blsg1_decode_points(dr_ctx *ctx, int check, const uint8_t *enc /* n*49 */, size_t n, uint8_t *out_xy /* n*96 */, uint8_t *ok /* n */);
+DR_API int dr_blsg1_field_selftest(dr_ctx *ctx, const int32_t *a_limbs /* n*14 */, const int32_t *b_limbs /* n*14 */, size_t n,
+                                   uint8_t *out /* n*240 */, uint8_t *flags /* n */);
+
 /* square root in the Bandersnatch base field; DR_ERR_NOTSQUARE if none exists. Host-side, no ctx. */
 DR_API int dr_fr_sqrt(const uint8_t in[32], uint8_t out[32]);
 
