@@ -126,6 +126,13 @@ _PROTOTYPES.update({
     "dr_blsg1_msm_groups": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_size_t, c_char_p]),
     "dr_blsg1_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
     "dr_blsg1_field_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p, c_void_p]),
+    "dr_blsg2_hash_to_field_batch": (c_int, [c_int, c_char_p, POINTER(ctypes.c_uint64), c_size_t, c_char_p]),
+    "dr_blsg2_map_to_curve": (c_int, [c_void_p, c_char_p, c_size_t, c_int, c_int, c_char_p, c_char_p]),
+    "dr_blsg2_encode_to_curve_batch": (c_int, [c_void_p, c_int, c_char_p, POINTER(ctypes.c_uint64), c_char_p, POINTER(ctypes.c_uint64), c_size_t,
+                                               c_char_p]),
+    "dr_blsg2_scalar_mul_batch": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_char_p]),
+    "dr_blsg2_check_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p]),
+    "dr_blsg2_field_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p, c_void_p]),
     "dr_curve25519_scalar_mul_batch": (c_int, [c_void_p, c_char_p, c_char_p, c_char_p, c_size_t, c_char_p, c_char_p]),
     "dr_curve25519_msm_groups": (c_int, [c_void_p, c_char_p, c_char_p, c_char_p, c_size_t, c_size_t, c_char_p, c_char_p]),
     "dr_curve25519_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
@@ -220,6 +227,8 @@ CURVE_P256_RO, CURVE_P256_NU, CURVE_ED25519_RO, CURVE_ED25519_NU = 8, 9, 10, 11
 CURVE_CURVE25519_RO, CURVE_CURVE25519_NU = 13, 14       # (12 is not assigned)
 # BLS12-381 G1 by RFC 9380: 48-byte coordinates, entry points of their own (dr_blsg1_*); every 64-byte entry point refuses these ids
 CURVE_BLS12_381_G1, CURVE_BLS12_381_G1_NU = 15, 16
+# BLS12-381 G2 by RFC 9380: Fq2 coordinates (96 bytes), entry points of their own (dr_blsg2_*); refused everywhere else
+CURVE_BLS12_381_G2, CURVE_BLS12_381_G2_NU = 17, 18
 # bytes of an encoded point, per curve id (the suites with 33-byte encodings and Curve25519's 64-byte u || v; every other curve's are 32)
 _POINT_LEN = {CURVE_BANDERSNATCH_SW: 33, CURVE_P256: 33, CURVE_SECP256K1: 33, CURVE_SECP256K1_NU: 33, CURVE_P256_RO: 33, CURVE_P256_NU: 33,
               CURVE_CURVE25519_RO: 64, CURVE_CURVE25519_NU: 64}
@@ -308,6 +317,14 @@ def blsg1_hash_to_field_batch(variant: int, msgs) -> bytes:
     out = ctypes.create_string_buffer(max(1, 96 * len(msgs)))
     _check(lib().dr_blsg1_hash_to_field_batch(variant, blob, off, len(msgs), out))
     return out.raw[: (48 if variant == CURVE_BLS12_381_G1_NU else 96) * len(msgs)]
+
+
+def blsg2_hash_to_field_batch(variant: int, msgs) -> bytes:
+    """dr_blsg2_hash_to_field_batch (host only): two Fq2 elements (192 bytes) per message for CURVE_BLS12_381_G2, one (96) for ..._NU"""
+    blob, off = _ragged([bytes(m) for m in msgs])
+    out = ctypes.create_string_buffer(max(1, 192 * len(msgs)))
+    _check(lib().dr_blsg2_hash_to_field_batch(variant, blob, off, len(msgs), out))
+    return out.raw[: (96 if variant == CURVE_BLS12_381_G2_NU else 192) * len(msgs)]
 
 
 def lib() -> ctypes.CDLL:
@@ -698,6 +715,54 @@ class Context:
         out, flags = ctypes.create_string_buffer(max(1, 240 * n)), ctypes.create_string_buffer(max(1, n))
         _check(lib().dr_blsg1_field_selftest(self.handle, a_limbs, b_limbs, n, out, flags))
         return out.raw[: 240 * n], flags.raw[:n]
+
+    # ---- BLS12-381 G2 (include/dotring_hip.h: Fq2 elements c0 || c1, 96 bytes; points 192 bytes x || y, 192 zero bytes the identity;
+    # scalars 96 bytes as they are)
+    def blsg2_map_to_curve(self, us: bytes, per_item: int, clear: bool = True):
+        """dr_blsg2_map_to_curve: (x||y bytes, flags) for len(us) / (96 per_item) items; clear = False: before the cofactor clearing.
+        per_item other than 1 or 2 is the library's to refuse."""
+        if len(us) % 96 or (per_item in (1, 2) and len(us) % (96 * per_item)):
+            raise ValueError("field elements are 96 bytes each, one or two per item")
+        n = len(us) // (96 * per_item) if per_item in (1, 2) else len(us) // 96
+        out, ok = ctypes.create_string_buffer(max(1, 192 * n)), ctypes.create_string_buffer(max(1, n))
+        _check(lib().dr_blsg2_map_to_curve(self.handle, us, n, per_item, 1 if clear else 0, out, ok))
+        return out.raw[: 192 * n], ok.raw[:n]
+
+    def blsg2_encode_to_curve_batch(self, variant: int, msgs, salts=None) -> bytes:
+        """dr_blsg2_encode_to_curve_batch: encode_to_curve(salt_i || msg_i) -> count * 192 bytes x||y."""
+        count = len(msgs)
+        m_blob, m_off = _ragged([bytes(m) for m in msgs])
+        s_blob, s_off = (None, None) if not salts or not any(salts) else _ragged([bytes(x) for x in salts])
+        out = ctypes.create_string_buffer(max(192 * count, 1))
+        _check(lib().dr_blsg2_encode_to_curve_batch(self.handle, variant, m_blob, m_off, s_blob, s_off, count, out))
+        return out.raw[: 192 * count]
+
+    def blsg2_scalar_mul_batch(self, pts_xy: bytes, scalars: bytes) -> bytes:
+        """dr_blsg2_scalar_mul_batch: k_i P_i for n points of E(Fq2) and n 96-byte scalars used as they are."""
+        n = len(scalars) // 96
+        if len(scalars) != 96 * n or len(pts_xy) != 192 * n:
+            raise ValueError("Points and scalars must have same length")
+        out = ctypes.create_string_buffer(max(1, 192 * n))
+        _check(lib().dr_blsg2_scalar_mul_batch(self.handle, pts_xy, scalars, n, out))
+        return out.raw[: 192 * n]
+
+    def blsg2_check_points(self, pts_xy: bytes, subgroup: bool = True) -> bytes:
+        """dr_blsg2_check_points: one flag byte per 192-byte point: on the curve, and with `subgroup` also r P = O."""
+        if len(pts_xy) % 192:
+            raise ValueError("points are 192 bytes each")
+        n = len(pts_xy) // 192
+        ok = ctypes.create_string_buffer(max(1, n))
+        _check(lib().dr_blsg2_check_points(self.handle, 1 if subgroup else 0, pts_xy, n, ok))
+        return ok.raw[:n]
+
+    def blsg2_field_selftest(self, a_limbs: bytes, b_limbs: bytes):
+        """dr_blsg2_field_selftest: (n x 5 x 96 result bytes, n flag bytes) for n pairs of raw 2 x 14-limb images (little-endian int32)."""
+        n = len(a_limbs) // 112
+        if len(a_limbs) != 112 * n or len(b_limbs) != 112 * n:
+            raise ValueError("operands are 2 x 14 int32 limbs each")
+        out, flags = ctypes.create_string_buffer(max(1, 480 * n)), ctypes.create_string_buffer(max(1, n))
+        _check(lib().dr_blsg2_field_selftest(self.handle, a_limbs, b_limbs, n, out, flags))
+        return out.raw[: 480 * n], flags.raw[:n]
 
     def _map_to_curve(self, fn, us: bytes, per_item: int):
         if per_item not in (1, 2) or len(us) % (32 * per_item):

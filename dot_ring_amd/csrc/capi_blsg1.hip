@@ -1,11 +1,11 @@
-// libdotring_hip.so — C ABI, part 6 of 6: the BLS12_381_G1 suites (DR_CURVE_BLS12_381_G1 / DR_CURVE_BLS12_381_G1_NU; the reference's
+// libdotring_hip.so — C ABI, part 6 of 7: the BLS12_381_G1 suites (DR_CURVE_BLS12_381_G1 / DR_CURVE_BLS12_381_G1_NU; the reference's
 // specs/bls12_381_G1.py).  The first curve here whose coordinates are 48 bytes: none of it goes through the 64-byte paths of
 // capi_core.hip — points are affine x || y, 48 + 48 bytes little-endian, canonical standard form, 96 zero bytes the identity.  The
-// kernels are kernels_g1_h2c.hip.h (the complete projective law over fq28.hip.h, wave_curve.hip.h's and sswu.hip.h's templates); the
+// kernels are kernels_g1_h2c_entry.hip.h over kernels_g1_h2c.hip.h (the complete projective law over fq28.hip.h, wave_curve.hip.h's and sswu.hip.h's templates); the
 // host does hash_to_field (expand_message_xmd over SHA-256, L = 64) on the worker threads and checks that inputs are canonical.
 // Scalars are 32 bytes used AS THEY ARE: E(Fq) has order h r, and its points need not lie in G1.
 #include "capi_internal.hpp"
-#include "kernels_g1_h2c.hip.h"
+#include "kernels_g1_h2c_entry.hip.h"
 
 using namespace dri;
 

@@ -1048,6 +1048,296 @@ class Bls12381G1Point(ShortWeierstrassA0Point):
         return out
 
 
+class Fp2:
+    """An element re + im i of Fp2 = Fp[i] / (i^2 + 1) with the surface of the reference's dot_ring/curve/fp2.py: re, im, p, the
+    arithmetic operators (integers act as elements of Fp), inv, is_square, sqrt, sgn0, to_tuple.  Host big-integer code."""
+    __slots__ = ("re", "im", "p")
+
+    def __init__(self, re: int, im: int, p: int):
+        self.p = int(p)
+        self.re, self.im = int(re) % self.p, int(im) % self.p
+
+    def _coerce(self, other):
+        if isinstance(other, Fp2):
+            if other.p != self.p:
+                raise ValueError("Fp2 operands use different fields")
+            return other
+        if isinstance(other, int):
+            return Fp2(other, 0, self.p)
+        return None
+
+    def __eq__(self, other):
+        if isinstance(other, Fp2):
+            return self.p == other.p and self.re == other.re and self.im == other.im
+        if isinstance(other, int):
+            return self.im == 0 and self.re == other % self.p
+        return NotImplemented
+
+    def __hash__(self):
+        return hash((self.re, self.im, self.p))
+
+    def __repr__(self):
+        return f"Fp2({self.re}, {self.im})"
+
+    def __add__(self, other):
+        other = self._coerce(other)
+        return NotImplemented if other is None else Fp2(self.re + other.re, self.im + other.im, self.p)
+
+    __radd__ = __add__
+
+    def __neg__(self):
+        return Fp2(-self.re, -self.im, self.p)
+
+    def __sub__(self, other):
+        other = self._coerce(other)
+        return NotImplemented if other is None else Fp2(self.re - other.re, self.im - other.im, self.p)
+
+    def __rsub__(self, other):
+        other = self._coerce(other)
+        return NotImplemented if other is None else other - self
+
+    def __mul__(self, other):
+        other = self._coerce(other)
+        if other is None:
+            return NotImplemented
+        return Fp2(self.re * other.re - self.im * other.im, self.re * other.im + self.im * other.re, self.p)
+
+    __rmul__ = __mul__
+
+    def __pow__(self, e: int):
+        if e < 0:
+            return self.inv() ** -e
+        acc, base = Fp2(1, 0, self.p), self
+        while e:
+            if e & 1:
+                acc = acc * base
+            base = base * base
+            e >>= 1
+        return acc
+
+    def conj(self):
+        return Fp2(self.re, -self.im, self.p)
+
+    def norm(self) -> int:
+        return (self.re * self.re + self.im * self.im) % self.p
+
+    def is_zero(self) -> bool:
+        return self.re == 0 and self.im == 0
+
+    def inv(self):
+        n = self.norm()
+        if n == 0:
+            raise ZeroDivisionError("Fp2 zero has no inverse")
+        ni = pow(n, -1, self.p)
+        return Fp2(self.re * ni, -self.im * ni, self.p)
+
+    def __truediv__(self, other):
+        other = self._coerce(other)
+        return NotImplemented if other is None else self * other.inv()
+
+    def __rtruediv__(self, other):
+        other = self._coerce(other)
+        return NotImplemented if other is None else other * self.inv()
+
+    def is_square(self) -> bool:
+        """through the norm (p = 3 mod 4): a^((p^2 - 1) / 2) = norm(a)^((p - 1) / 2); zero is a square"""
+        return pow(self.norm(), (self.p - 1) // 2, self.p) != self.p - 1
+
+    def sqrt(self):
+        """a root, or None: the norm route the device takes (csrc/fq2_28.hip.h) — roots in Fp of the norm and of (re +- s) / 2, one
+        division; an element of Fp has the root (r, 0) or (0, r)"""
+        p = self.p
+        if p % 4 != 3:
+            raise NotImplementedError("Fp2.sqrt needs p = 3 mod 4")
+        root = lambda v: pow(v, (p + 1) // 4, p)  # noqa: E731
+        if self.im == 0:
+            r = root(self.re)                      # r^2 = +-re: (0, r)^2 = -r^2
+            return Fp2(r, 0, p) if r * r % p == self.re else Fp2(0, r, p)
+        s = root(self.norm())
+        if s * s % p != self.norm():
+            return None
+        d = (self.re + s) * pow(2, -1, p) % p
+        r = root(d)
+        t = self.im * pow(2 * r, -1, p) % p
+        return Fp2(r, t, p) if r * r % p == d else Fp2(t, r, p)
+
+    def sgn0(self) -> int:
+        return (self.re & 1) | ((self.re == 0) & (self.im & 1))
+
+    def to_tuple(self):
+        return self.re, self.im
+
+
+class Bls12381G2Point:
+    """Affine point of E(Fq2): y^2 = x^3 + 4 (1 + i) over BLS12-381's quadratic extension (dot_ring/curve/specs/bls12_381_G2.py), the
+    identity is (None, None); coordinates are Fp2 values ((re, im) tuples are accepted).  E(Fq2) has order h2 r (762 bits): a point need
+    not lie in G2, so scalars are never reduced mod r.  Single additions are host big-integer code; scalar multiplications and hashing to
+    the curve (RFC 9380: simplified SWU, the 3-isogeny, the clearing by psi) run on the GPU (kernels_g2_h2c.hip.h, the dr_blsg2_* entry
+    points).  There is no point codec, as in the reference."""
+    curve: BandersnatchCurve
+    _P = 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB
+    _N = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
+    # h_eff of RFC 9380 8.8.2: the reference's `cofactor`, what clear_cofactor multiplies by (636 bits)
+    _H = 0xBC69F08F2EE75B3584C6A0EA91B352888E2A8E9145AD7689986FF031508FFE1329C2F178731DB956D82BF015D1212B02EC0EC69D7477C1AE954CBC06689F6A359894C0ADEBBF6B4E8020005AAA95551
+    # #E(Fq2) = _COFACTOR * _N
+    _COFACTOR = 0x5D543A95414E7F1091D50792876A202CD91DE4547085ABAA68A205B2E5A7DDFA628F1CB4D9E82EF21537E293A6691AE1616EC6E786F0C70CF1C38E31C7238E5
+    _CV = _native.CURVE_BLS12_381_G2
+    __slots__ = ("x", "y")
+
+    def __init__(self, x, y):
+        self.x, self.y = self._coord(x), self._coord(y)
+        if self.x is None and self.y is None:
+            return
+        if self.x is None or self.y is None:
+            raise ValueError("Invalid point coordinates")
+        if not self._on_curve(self.x, self.y):
+            raise ValueError("Point is not on the curve")
+
+    @classmethod
+    def _coord(cls, value):
+        if value is None:
+            return None
+        if isinstance(value, Fp2):
+            if value.p != cls._P:
+                raise ValueError("Fp2 coordinate uses the wrong field")
+            return value
+        if isinstance(value, tuple) and len(value) == 2:
+            return Fp2(value[0], value[1], cls._P)
+        raise TypeError("BLS12-381 G2 coordinates must be Fp2 values")
+
+    @classmethod
+    def _on_curve(cls, x: Fp2, y: Fp2) -> bool:
+        return y * y == x * x * x + Fp2(4, 4, cls._P)
+
+    @classmethod
+    def _trusted(cls, x: Fp2, y: Fp2):
+        """Kernel outputs: 192 zero bytes are the identity."""
+        pt = object.__new__(cls)
+        pt.x, pt.y = (None, None) if x.is_zero() and y.is_zero() else (x, y)
+        return pt
+
+    def __eq__(self, other):
+        return isinstance(other, Bls12381G2Point) and self.x == other.x and self.y == other.y
+
+    def __hash__(self):
+        return 0 if self.x is None else hash((self.x.to_tuple(), self.y.to_tuple()))
+
+    def __repr__(self):
+        return f"{type(self).__name__}({self.x}, {self.y})"
+
+    @classmethod
+    def identity(cls):
+        return cls(None, None)
+
+    @classmethod
+    def generator_point(cls):
+        return cls(*cls.curve.params.generator)
+
+    def is_identity(self) -> bool:
+        return self.x is None and self.y is None
+
+    def is_on_curve(self) -> bool:
+        return self.is_identity() or self._on_curve(self.x, self.y)
+
+    # -- group law on the host
+    def __add__(self, other):
+        if not isinstance(other, Bls12381G2Point):
+            raise TypeError("Can only add BLS12_381_G2Point instances")
+        if self.is_identity():
+            return other
+        if other.is_identity():
+            return self
+        if self.x == other.x:
+            if (self.y + other.y).is_zero():
+                return self.identity()
+            lam = 3 * self.x * self.x / (2 * self.y)
+        else:
+            lam = (other.y - self.y) / (other.x - self.x)
+        x3 = lam * lam - self.x - other.x
+        return self._trusted(x3, lam * (self.x - x3) - self.y)
+
+    def __neg__(self):
+        return self if self.is_identity() else self._trusted(self.x, -self.y)
+
+    def __sub__(self, other):
+        if not isinstance(other, Bls12381G2Point):
+            raise TypeError("Can only subtract BLS12_381_G2Point instances")
+        return self + (-other)
+
+    # -- kernels: Fq2 elements cross as c0 || c1, points as x || y, 4 x 48 bytes little-endian, 192 zero bytes the identity
+    @staticmethod
+    def _pack_fp2(a: Fp2) -> bytes:
+        return a.re.to_bytes(48, "little") + a.im.to_bytes(48, "little")
+
+    @classmethod
+    def _pack(cls, points) -> bytes:
+        return b"".join(bytes(192) if p.is_identity() else cls._pack_fp2(p.x) + cls._pack_fp2(p.y) for p in points)
+
+    @classmethod
+    def _unpack(cls, raw: bytes):
+        frm = lambda i: Fp2(int.from_bytes(raw[i : i + 48], "little"), int.from_bytes(raw[i + 48 : i + 96], "little"), cls._P)  # noqa: E731
+        return [cls._trusted(frm(i), frm(i + 96)) for i in range(0, len(raw), 192)]
+
+    def __mul__(self, scalar: int):
+        """exact for every integer: negative k negates, 0 <= k < 2^768 is one kernel entry with k as it is, larger k goes mod h2 r"""
+        k = int(scalar)
+        if k < 0:
+            return (-self) * (-k)
+        if k >> 768:
+            k %= self._COFACTOR * self._N
+        return self._unpack(runtime.context().blsg2_scalar_mul_batch(self._pack([self]), k.to_bytes(96, "little")))[0]
+
+    __rmul__ = __mul__
+
+    def clear_cofactor(self):
+        return self * self._H
+
+    def point_to_string(self) -> bytes:
+        raise NotImplementedError("BLS12-381 G2 point serialization is not implemented")
+
+    @classmethod
+    def string_to_point(cls, data):
+        raise NotImplementedError("BLS12-381 G2 point deserialization is not implemented")
+
+    # -- hash to curve (RFC 9380 BLS12381G2_XMD:SHA-256_SSWU_RO_ / _NU_): expand_message_xmd natively on the host, the map on the GPU
+    @classmethod
+    def _per_item(cls) -> int:
+        return 1 if cls.curve.params.e2c == "sswu_nu" else 2
+
+    @classmethod
+    def _mapped(cls, us: bytes, per_item: int, clear: bool = True):
+        raw, ok = runtime.context().blsg2_map_to_curve(us, per_item, clear)
+        if 0 in ok:                                # (no input reaches it: the isogeny's kernel has no point of E'(Fq2))
+            raise ValueError("base is not invertible for the given modulus")
+        return cls._unpack(raw)
+
+    @classmethod
+    def map_to_curve_simple_swu(cls, u):
+        """one image on E, before the cofactor clearing (a point of E(Fq2), in general outside G2)"""
+        return cls._mapped(cls._pack_fp2(cls._coord(u)), 1, clear=False)[0]
+
+    @classmethod
+    def hash_to_field_pairs(cls, alpha_strings, salts=None) -> bytes:
+        """Host half of encode_to_curve for many inputs: two 96-byte Fq2 elements per input (one for the NU variant), little-endian."""
+        salts = salts or [b""] * len(alpha_strings)
+        return _native.blsg2_hash_to_field_batch(cls._CV, [bytes(s) + bytes(a) for a, s in zip(alpha_strings, salts)])
+
+    @classmethod
+    def encode_to_curve_from_field(cls, us: bytes):
+        """Device half: the maps, for RO the sum of the two images, and the clearing."""
+        return cls._mapped(us, cls._per_item()) if us else []
+
+    @classmethod
+    def encode_to_curve(cls, alpha_string: bytes, salt: bytes = b""):
+        return cls.encode_to_curve_batch([alpha_string], [salt])[0]
+
+    @classmethod
+    def encode_to_curve_batch(cls, alpha_strings, salts=None):
+        if not alpha_strings:
+            return []
+        return cls._unpack(runtime.context().blsg2_encode_to_curve_batch(cls._CV, list(alpha_strings), salts))
+
+
 class P256SswuPoint(P256Point):
     """Affine point of P256_RO / P256_NU (dot_ring/curve/specs/p256.py with E2C_Variant.SSWU / SSWU_NU): P-256's group and kernels under
     the variant's curve id, the reference's generic SEC1 codec in place of P256_TAI's (P256Point.point_to_string defers to
@@ -1450,7 +1740,7 @@ class CurveVariant:
         self.name, self.curve, self.point_type = name, curve, point_type
 
     def point(self, x, y=None):
-        if isinstance(x, (BandersnatchPoint, BandersnatchSWPoint, P256Point, ShortWeierstrassA0Point, Curve25519Point)):
+        if isinstance(x, (BandersnatchPoint, BandersnatchSWPoint, P256Point, ShortWeierstrassA0Point, Curve25519Point, Bls12381G2Point)):
             return x
         if y is None:
             x, y = x
@@ -1713,3 +2003,35 @@ def _bls12_381_g1_variant(name: str, e2c: str, curve_id: int) -> CurveVariant:
 BLS12_381_G1_RO = _bls12_381_g1_variant("BLS12_381_G1_RO", "sswu", _native.CURVE_BLS12_381_G1)
 BLS12_381_G1_NU = _bls12_381_g1_variant("BLS12_381_G1_NU", "sswu_nu", _native.CURVE_BLS12_381_G1_NU)
 BLS12_381_G1 = BLS12_381_G1_RO
+
+
+# dot_ring/curve/specs/bls12_381_G2.py: E: y^2 = x^3 + 4 (1 + i) over Fq2, #E(Fq2) = h2 r, hashing by RFC 9380's
+# BLS12381G2_XMD:SHA-256_SSWU_RO_ (two field elements) or ..._NU_ (one), `cofactor` = the 636-bit h_eff; both variants carry the RO suite
+# id, as in the reference.  Encoding(point_len=32, challenge_len=32) are the reference's own figures; it has NO point codec for this curve
+# (point_to_string / string_to_point raise), so no key or proof can be encoded — the VRF classes refuse these two suites (vrf/base.py)
+# and what is served is the point type.  No auxiliary points, not twisted Edwards: RingProofParams refuses them too.
+def _bls12_381_g2_variant(name: str, e2c: str, curve_id: int) -> CurveVariant:
+    fp2 = lambda re, im: Fp2(re, im, Bls12381G2Point._P)  # noqa: E731
+    params = SuiteParams(
+        suite_id=b"BLS12381G2_XMD:SHA-256_SSWU_RO_", hash_fn=hashlib.sha256, xof=False,
+        auxiliary_points=AuxiliaryPoints(None, None, None),
+        field_modulus=Bls12381G2Point._P,
+        subgroup_order=Bls12381G2Point._N,
+        cofactor=Bls12381G2Point._H,
+        a=0,
+        d=0,
+        generator=(fp2(0x024AA2B2F08F0A91260805272DC51051C6E47AD4FA403B02B4510B647AE3D1770BAC0326A805BBEFD48056C8C121BDB8,
+                       0x13E02B6052719F607DACD3A088274F65596BD0D09920B61AB5DA61BBDC7F5049334CF11213945D57E5AC7D055D042B7E),
+                   fp2(0x0CE5D527727D6E118CC9CDC6DA2E351AADFD9BAA8CBDD3A76D429A695160D12C923AC9CC3BACA289E193548608B82801,
+                       0x0606C4A02EA734CC32ACD2B02BC28B99CB3E287E85A763AF267492AB572E99AB3F370D275CEC1DA1AAA9075FF05F79BE)),
+        encoding=Encoding(point_len=32, challenge_len=32),
+        curve_id=curve_id,
+        e2c=e2c,
+    )
+    curve = BandersnatchCurve(params)
+    return CurveVariant(name, curve, type(f"{name}Point", (Bls12381G2Point,), {"__slots__": (), "curve": curve, "_CV": curve_id}))
+
+
+BLS12_381_G2_RO = _bls12_381_g2_variant("BLS12_381_G2_RO", "sswu", _native.CURVE_BLS12_381_G2)
+BLS12_381_G2_NU = _bls12_381_g2_variant("BLS12_381_G2_NU", "sswu_nu", _native.CURVE_BLS12_381_G2_NU)
+BLS12_381_G2 = BLS12_381_G2_RO

@@ -24,6 +24,10 @@ class VRF:
             # a deliberate deviation: the reference binds the class and can then decode nothing
             raise ValueError(f"{cls.__name__} has no {variant.name} suite: the reference's point length for this curve is 32 while its points "
                              "encode to 49 bytes, so no key or proof of it can be decoded")
+        if variant.curve.params.curve_id in (_native.CURVE_BLS12_381_G2, _native.CURVE_BLS12_381_G2_NU):
+            #  the reference binds the class and then fails at its first point_to_string
+            raise ValueError(f"{cls.__name__} has no {variant.name} suite: the curve has no point codec (point_to_string and "
+                             "string_to_point are not implemented), so no key or proof of it can be encoded")
         bound = _BOUND.get((cls, variant.name))
         if bound is None or bound.cv is not variant:
             bound = _BOUND[(cls, variant.name)] = type(f"{cls.__name__}[{variant.name}]", (cls,), {"cv": variant})

@@ -321,6 +321,47 @@ DR_API int dr_blsg1_decode_points(dr_ctx *ctx, int check, const uint8_t *enc /* 
 DR_API int dr_blsg1_field_selftest(dr_ctx *ctx, const int32_t *a_limbs /* n*14 */, const int32_t *b_limbs /* n*14 */, size_t n,
                                    uint8_t *out /* n*240 */, uint8_t *flags /* n */);
 
+/* DR_CURVE_BLS12_381_G2 (the reference's BLS12_381_G2 = BLS12_381_G2_RO) and DR_CURVE_BLS12_381_G2_NU (BLS12_381_G2_NU): hashing to
+ * BLS12-381's G2 by RFC 9380 (dot_ring/curve/specs/bls12_381_G2.py: E: y^2 = x^3 + 4 (1 + i) over Fq2 = Fq[i] / (i^2 + 1), #E(Fq2) = h2 r,
+ * BLS12381G2_XMD:SHA-256_SSWU_RO_ / _NU_: simplified SWU onto the 3-isogenous curve with Z = -(2 + i), the isogeny back, the sum of two
+ * images for RO and one for NU, then the cofactor clearing of appendix G.3, which equals the multiplication by the 636-bit h_eff) and the
+ * group of E(Fq2) — csrc/kernels_g2_h2c.hip.h over csrc/fq2_28.hip.h.  Entry points of their own (dr_blsg2_*); EVERY 64-byte entry point
+ * refuses these two ids with DR_ERR_INVALID, as it refuses 15 and 16, and so does every dr_blsg1_* call that takes a variant.  There is no
+ * VRF over these suites: the reference has no point codec for this curve.
+ *
+ * FIELD ELEMENTS are c0 || c1 (c0 + c1 i), 48 + 48 bytes LITTLE-endian, canonical standard form; a component at or above p is refused
+ * with DR_ERR_INVALID.  POINTS are affine x || y, 192 bytes; 192 zero bytes are the identity ((0, 0) is not on the curve).  A point may be
+ * ANY point of E(Fq2), in G2 or not: SCALARS are 96 bytes little-endian used AS THEY ARE (0 <= k < 2^768, never reduced).
+ *   dr_blsg2_hash_to_field_batch    host only: expand_message_xmd over SHA-256 (Z_pad 64 bytes), m = 2, L = 64 bytes per component,
+ *                                   big-endian, mod p, with the DST of `variant` (one of the two curve ids): two elements (192 bytes, from
+ *                                   256 uniform bytes) per message for RO, one (96, from 128) for NU.  msgs / off as
+ *                                   dr_hash_to_field_batch (off: count + 1 offsets).
+ *   dr_blsg2_map_to_curve           n items of per_item (2 or 1) elements: out_xy[i] = the sum of their images, cleared if clear (clear = 0:
+ *                                   the reference's map_to_curve_simple_swu, the Q0 / Q1 of RFC 9380's vectors).  ok[i] = 0 where a
+ *                                   denominator of the isogeny vanishes; no input reaches that (the isogeny's kernel has no point over
+ *                                   Fq2 with a rational x on E'), the flag is kept for the shape of the G1 call.  Other per_item are refused.
+ *   dr_blsg2_encode_to_curve_batch  encode_to_curve(salt_i || msg_i) (salts nullable): hash_to_field on the worker threads, then the map.
+ *   dr_blsg2_scalar_mul_batch       out[i] = k[i] P[i]: a bit-by-bit walk from the top set bit of each wave's largest scalar.  Scalars
+ *                                   are treated as PUBLIC (the walk's length and its skipped additions depend on them).
+ *   dr_blsg2_check_points           ok[i] = 1 iff point i satisfies the curve equation (the identity does); subgroup = 1 also demands
+ *                                   r P = O.
+ *   dr_blsg2_field_selftest         diagnostic of csrc/fq2_28.hip.h on RAW limb images (2 x 14 signed 32-bit limbs an element, c0 then c1,
+ *                                   value sum l[i] 2^(28 i), standing for value 2^-392 mod p).  out: n x 5 x 96 bytes, each the canonical
+ *                                   c0 || c1 of: a b; a^2; a^-1 (0 for 0); 12 (1 + i) a as the group law computes it (folds, additions,
+ *                                   carries; a's components in (-2.1 p, 1.1 p)); a root of a, or 0 if a is no square.  flags[i]: bit 0 a
+ *                                   is a square, bit 1 sgn0(a) (RFC 9380 4.1, m = 2), bit 2 a is zero. */
+enum { DR_CURVE_BLS12_381_G2 = 17, DR_CURVE_BLS12_381_G2_NU = 18 };
+DR_API int dr_blsg2_hash_to_field_batch(int variant, const uint8_t *msgs, const uint64_t *off, size_t count, uint8_t *out /* count*(192|96) */);
+DR_API int dr_blsg2_map_to_curve(dr_ctx *ctx, const uint8_t *us /* n*per_item*96 */, size_t n, int per_item, int clear,
+                                 uint8_t *out_xy /* n*192 */, uint8_t *ok /* n */);
+DR_API int dr_blsg2_encode_to_curve_batch(dr_ctx *ctx, int variant, const uint8_t *msgs, const uint64_t *off, const uint8_t *salts,
+                                          const uint64_t *salt_off, size_t count, uint8_t *out_xy /* count*192 */);
+DR_API int dr_blsg2_scalar_mul_batch(dr_ctx *ctx, const uint8_t *pts_xy /* n*192 */, const uint8_t *scalars /* n*96 */, size_t n,
+                                     uint8_t *out_xy /* n*192 */);
+DR_API int dr_blsg2_check_points(dr_ctx *ctx, int subgroup, const uint8_t *pts_xy /* n*192 */, size_t n, uint8_t *ok /* n */);
+DR_API int dr_blsg2_field_selftest(dr_ctx *ctx, const int32_t *a_limbs /* n*28 */, const int32_t *b_limbs /* n*28 */, size_t n,
+                                   uint8_t *out /* n*480 */, uint8_t *flags /* n */);
+
 /* square root in the Bandersnatch base field; DR_ERR_NOTSQUARE if none exists. Host-side, no ctx. */
 DR_API int dr_fr_sqrt(const uint8_t in[32], uint8_t out[32]);
 
