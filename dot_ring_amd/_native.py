@@ -133,6 +133,14 @@ _PROTOTYPES.update({
     "dr_blsg2_scalar_mul_batch": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_char_p]),
     "dr_blsg2_check_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p]),
     "dr_blsg2_field_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p, c_void_p]),
+    "dr_ed448_hash_to_field_batch": (c_int, [c_int, c_char_p, POINTER(ctypes.c_uint64), c_size_t, c_char_p]),
+    "dr_ed448_map_to_curve": (c_int, [c_void_p, c_char_p, c_size_t, c_int, c_int, c_char_p, c_char_p]),
+    "dr_ed448_encode_to_curve_batch": (c_int, [c_void_p, c_int, c_char_p, POINTER(ctypes.c_uint64), c_char_p, POINTER(ctypes.c_uint64), c_size_t,
+                                               c_char_p]),
+    "dr_ed448_scalar_mul_batch": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_char_p]),
+    "dr_ed448_msm_groups": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_size_t, c_char_p]),
+    "dr_ed448_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
+    "dr_ed448_field_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p, c_void_p]),
     "dr_curve25519_scalar_mul_batch": (c_int, [c_void_p, c_char_p, c_char_p, c_char_p, c_size_t, c_char_p, c_char_p]),
     "dr_curve25519_msm_groups": (c_int, [c_void_p, c_char_p, c_char_p, c_char_p, c_size_t, c_size_t, c_char_p, c_char_p]),
     "dr_curve25519_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
@@ -229,6 +237,8 @@ CURVE_CURVE25519_RO, CURVE_CURVE25519_NU = 13, 14       # (12 is not assigned)
 CURVE_BLS12_381_G1, CURVE_BLS12_381_G1_NU = 15, 16
 # BLS12-381 G2 by RFC 9380: Fq2 coordinates (96 bytes), entry points of their own (dr_blsg2_*); refused everywhere else
 CURVE_BLS12_381_G2, CURVE_BLS12_381_G2_NU = 17, 18
+# Ed448 by RFC 9380: 56-byte coordinates AND 56-byte scalars, entry points of their own (dr_ed448_*); refused everywhere else
+CURVE_ED448_RO, CURVE_ED448_NU = 19, 20
 # bytes of an encoded point, per curve id (the suites with 33-byte encodings and Curve25519's 64-byte u || v; every other curve's are 32)
 _POINT_LEN = {CURVE_BANDERSNATCH_SW: 33, CURVE_P256: 33, CURVE_SECP256K1: 33, CURVE_SECP256K1_NU: 33, CURVE_P256_RO: 33, CURVE_P256_NU: 33,
               CURVE_CURVE25519_RO: 64, CURVE_CURVE25519_NU: 64}
@@ -325,6 +335,14 @@ def blsg2_hash_to_field_batch(variant: int, msgs) -> bytes:
     out = ctypes.create_string_buffer(max(1, 192 * len(msgs)))
     _check(lib().dr_blsg2_hash_to_field_batch(variant, blob, off, len(msgs), out))
     return out.raw[: (96 if variant == CURVE_BLS12_381_G2_NU else 192) * len(msgs)]
+
+
+def ed448_hash_to_field_batch(variant: int, msgs) -> bytes:
+    """dr_ed448_hash_to_field_batch (host only): two elements (112 bytes) per message for CURVE_ED448_RO, one (56) for CURVE_ED448_NU"""
+    blob, off = _ragged([bytes(m) for m in msgs])
+    out = ctypes.create_string_buffer(max(1, 112 * len(msgs)))
+    _check(lib().dr_ed448_hash_to_field_batch(variant, blob, off, len(msgs), out))
+    return out.raw[: (56 if variant == CURVE_ED448_NU else 112) * len(msgs)]
 
 
 def lib() -> ctypes.CDLL:
@@ -763,6 +781,65 @@ class Context:
         out, flags = ctypes.create_string_buffer(max(1, 480 * n)), ctypes.create_string_buffer(max(1, n))
         _check(lib().dr_blsg2_field_selftest(self.handle, a_limbs, b_limbs, n, out, flags))
         return out.raw[: 480 * n], flags.raw[:n]
+
+    # ---- Ed448 (include/dotring_hip.h: field elements 56 bytes; points 112 bytes x || y, the identity (0, 1) as itself; scalars 56 bytes as
+    # they are)
+    def ed448_map_to_curve(self, us: bytes, per_item: int, clear: bool = True):
+        """dr_ed448_map_to_curve: (x||y bytes, flags) for len(us) / (56 per_item) items; clear = False: before the cofactor clearing.
+        per_item other than 1 or 2 is the library's to refuse."""
+        if len(us) % 56 or (per_item in (1, 2) and len(us) % (56 * per_item)):
+            raise ValueError("field elements are 56 bytes each, one or two per item")
+        n = len(us) // (56 * per_item) if per_item in (1, 2) else len(us) // 56
+        out, ok = ctypes.create_string_buffer(max(1, 112 * n)), ctypes.create_string_buffer(max(1, n))
+        _check(lib().dr_ed448_map_to_curve(self.handle, us, n, per_item, 1 if clear else 0, out, ok))
+        return out.raw[: 112 * n], ok.raw[:n]
+
+    def ed448_encode_to_curve_batch(self, variant: int, msgs, salts=None) -> bytes:
+        """dr_ed448_encode_to_curve_batch: encode_to_curve(salt_i || msg_i) -> count * 112 bytes x||y."""
+        count = len(msgs)
+        m_blob, m_off = _ragged([bytes(m) for m in msgs])
+        s_blob, s_off = (None, None) if not salts or not any(salts) else _ragged([bytes(x) for x in salts])
+        out = ctypes.create_string_buffer(max(112 * count, 1))
+        _check(lib().dr_ed448_encode_to_curve_batch(self.handle, variant, m_blob, m_off, s_blob, s_off, count, out))
+        return out.raw[: 112 * count]
+
+    def ed448_scalar_mul_batch(self, pts_xy: bytes, scalars: bytes) -> bytes:
+        """dr_ed448_scalar_mul_batch: k_i P_i for n points and n 56-byte scalars used as they are."""
+        n = len(scalars) // 56
+        if len(scalars) != 56 * n or len(pts_xy) != 112 * n:
+            raise ValueError("Points and scalars must have same length")
+        out = ctypes.create_string_buffer(max(1, 112 * n))
+        _check(lib().dr_ed448_scalar_mul_batch(self.handle, pts_xy, scalars, n, out))
+        return out.raw[: 112 * n]
+
+    def ed448_msm_groups(self, pts_xy: bytes, scalars: bytes, m: int) -> bytes:
+        """dr_ed448_msm_groups: the sums of consecutive groups of m (<= 64) terms k_j P_j -> groups * 112 bytes."""
+        n = len(scalars) // 56
+        if len(scalars) != 56 * n or len(pts_xy) != 112 * n or m <= 0 or n % m:
+            raise ValueError("Points and scalars must have same length, a multiple of the group size")
+        groups = n // m
+        out = ctypes.create_string_buffer(max(1, 112 * groups))
+        _check(lib().dr_ed448_msm_groups(self.handle, pts_xy, scalars, groups, m, out))
+        return out.raw[: 112 * groups]
+
+    def ed448_decode_points(self, enc: bytes, check: bool = True):
+        """dr_ed448_decode_points: (x||y bytes, flags) for 112-byte points: coordinates below p and on the curve; with `check` also not the
+        identity and n P = O."""
+        if len(enc) % 112:
+            raise ValueError("points are 112 bytes each")
+        n = len(enc) // 112
+        out, ok = ctypes.create_string_buffer(max(1, 112 * n)), ctypes.create_string_buffer(max(1, n))
+        _check(lib().dr_ed448_decode_points(self.handle, 1 if check else 0, enc, n, out, ok))
+        return out.raw[: 112 * n], ok.raw[:n]
+
+    def ed448_field_selftest(self, a_limbs: bytes, b_limbs: bytes):
+        """dr_ed448_field_selftest: (n x 11 x 56 result bytes, n flag bytes) for n pairs of raw 16-limb images (little-endian int32)."""
+        n = len(a_limbs) // 64
+        if len(a_limbs) != 64 * n or len(b_limbs) != 64 * n:
+            raise ValueError("operands are 16 int32 limbs each")
+        out, flags = ctypes.create_string_buffer(max(1, 616 * n)), ctypes.create_string_buffer(max(1, n))
+        _check(lib().dr_ed448_field_selftest(self.handle, a_limbs, b_limbs, n, out, flags))
+        return out.raw[: 616 * n], flags.raw[:n]
 
     def _map_to_curve(self, fn, us: bytes, per_item: int):
         if per_item not in (1, 2) or len(us) % (32 * per_item):

@@ -6,6 +6,7 @@
 //   capi_comm.hip   RCCL communicator for the base-sharded MSM
 //   capi_blsg1.hip  the BLS12_381_G1 suites: 48-byte coordinates, hashing to G1 and the group of E(Fq)
 //   capi_blsg2.hip  the BLS12_381_G2 suites: Fq2 coordinates, hashing to G2 and the group of E(Fq2)
+//   capi_ed448.hip  the Ed448 suites: 56-byte coordinates and scalars, hashing to the curve and the group of E(F_p)
 // Each header that defines kernels is included by exactly one of them; the others reach its kernels through the launch wrappers below.
 // (kernels_g1_h2c.hip.h defines none: the two BLS12-381 hashing units share its device functions.)
 #pragma once

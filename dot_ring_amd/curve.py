@@ -15,6 +15,9 @@ Mirrors (names, argument meaning, error behaviour) the parts of the reference th
   dot_ring/curve/specs/curve25519.py            Curve25519 (= Curve25519_RO), Curve25519_NU: Montgomery affine points over Ed25519's field,
                                                 64-byte u || v codec, RFC 9380 Elligator 2 with SHA-512; kernels of their own over the
                                                 Ed25519 group law (DR_CURVE_CURVE25519_RO / _NU)
+  dot_ring/curve/specs/ed448.py                 Ed448 (= Ed448_RO), Ed448_NU: a = 1, d = -39081 over 2^448 - 2^224 - 1, cofactor 4, 112-byte
+                                                x || y codec, 56-byte scalars, RFC 9380 Elligator 2 with SHAKE256; kernels of their own
+                                                (DR_CURVE_ED448_RO / _NU), the first suite wider than 256 bits in both
   dot_ring/curve/point.py:150-214               compressed codec
   dot_ring/curve/twisted_edwards/*              affine law, Elligator2 encode_to_curve
   dot_ring/curve/curve.py:56-67,110-237,384-401 valid_point, hash_to_field, key derivation
@@ -1450,6 +1453,112 @@ class Ed25519Ell2Point(BandersnatchPoint):
         return unpack_points(cls, runtime.context().encode_to_curve_batch(cls._suite_struct(), list(alpha_strings), salts))
 
 
+class Ed448Point(BandersnatchPoint):
+    """Affine point of Ed448_RO / Ed448_NU (dot_ring/curve/specs/ed448.py): x^2 + y^2 = 1 - 39081 x^2 y^2 over p = 2^448 - 2^224 - 1,
+    cofactor 4, the identity (0, 1).  Coordinates and scalars are 56 bytes, so nothing here goes through the 64-byte entry points: scalar
+    multiplications, MSMs, the subgroup check and hashing to the curve run on the dr_ed448_* kernels (kernels_ed448.hip.h), whose scalars
+    are used as they are — the reduction mod n of the reference's __mul__ happens here.  Single additions are host big-int code
+    (BandersnatchPoint's affine formulas with this curve's a and d)."""
+    _P = 2**448 - 2**224 - 1
+    _N = 2**446 - 0x8335DC163BB124B65129C96FDE933D8D723A70AADC873D6D54A7BB0D
+    _A, _D, _H, _CV = 1, -39081, 4, _native.CURVE_ED448_RO
+    _MG_A = 156326
+    _WIDE = True                  # the VRF classes keep their Python orchestration: the native batch provers carry 32-byte scalars
+    __slots__ = ()
+
+    # -- the C ABI's forms
+    @staticmethod
+    def _pack(points) -> bytes:
+        return b"".join(p.x.to_bytes(56, "little") + p.y.to_bytes(56, "little") for p in points)
+
+    @classmethod
+    def _unpack(cls, raw: bytes):
+        """Kernel outputs are group elements by construction: no per-point curve check."""
+        frm, mk = int.from_bytes, cls._trusted
+        return [mk(frm(raw[i : i + 56], "little"), frm(raw[i + 56 : i + 112], "little")) for i in range(0, len(raw), 112)]
+
+    @classmethod
+    def _scalars(cls, scalars) -> bytes:
+        return b"".join((int(k) % cls._N).to_bytes(56, "little") for k in scalars)
+
+    # -- scalar multiplication / MSM on the GPU (te_affine_point.py:163: the scalar reduced mod n)
+    def __mul__(self, scalar: int):
+        return scalar_mul_batch([self], [scalar])[0]
+
+    __rmul__ = __mul__
+
+    @classmethod
+    def msm(cls, points, scalars):
+        if len(points) != len(scalars):
+            raise ValueError("Points and scalars must have same length")
+        acc = cls.identity()
+        for lo in range(0, len(points), 64):          # groups of up to 64 terms on the device, their sums added on the host
+            part = points[lo : lo + 64]
+            acc = acc + msm_groups(part, scalars[lo : lo + 64], len(part))[0]
+        return acc
+
+    def clear_cofactor(self):
+        return scalar_mul_batch_raw([self], [self._H])[0]
+
+    # -- codec (point.py: uncompressed_p2s / uncompressed_s2p): x || y, 56 little-endian bytes each
+    def point_to_string(self) -> bytes:
+        return self.x.to_bytes(56, "little") + self.y.to_bytes(56, "little")
+
+    @classmethod
+    def string_to_point(cls, octet_string):
+        if isinstance(octet_string, str):
+            octet_string = bytes.fromhex(octet_string)
+        octet_string = bytes(octet_string)
+        return cls(int.from_bytes(octet_string[:56], "little"), int.from_bytes(octet_string[56:], "little"))
+
+    # -- hash to curve (RFC 9380 edwards448_XOF:SHAKE256_ELL2_RO_ / _NU_): expand_message_xof natively on the host, the map on the GPU
+    @classmethod
+    def _per_item(cls) -> int:
+        return 1 if cls.curve.params.e2c.endswith("_nu") else 2
+
+    @classmethod
+    def _mapped(cls, us: bytes, per_item: int, clear: bool = True):
+        raw, ok = runtime.context().ed448_map_to_curve(us, per_item, clear)
+        if 0 in ok:
+            raise ValueError("Point is not on the curve")        # mont_to_ed448 with inv(0) = 0 gives (0, 0): u in {0, 1, p - 1}
+        return cls._unpack(raw)
+
+    @classmethod
+    def map_to_curve(cls, u: int):
+        """Ed448Point.map_to_curve (te_curve.py map_to_curve_ell2, then mont_to_ed448): ONE image with its cofactor not cleared"""
+        return cls._mapped((int(u) % cls._P).to_bytes(56, "little"), 1, clear=False)[0]
+
+    @classmethod
+    def hash_to_field_pairs(cls, alpha_strings, salts=None) -> bytes:
+        """Host half of encode_to_curve for many inputs: _per_item() field elements per input, 56 little-endian bytes each."""
+        salts = salts or [b""] * len(alpha_strings)
+        return _native.ed448_hash_to_field_batch(cls.curve.params.curve_id, [bytes(s) + bytes(a) for a, s in zip(alpha_strings, salts)])
+
+    @classmethod
+    def encode_to_curve_from_field(cls, us: bytes):
+        """Device half: the maps, for RO the sum of the two images, and the cofactor, for packed canonical field elements."""
+        if not us:
+            return []
+        return cls._mapped(us, cls._per_item())
+
+    @classmethod
+    def encode_to_curve(cls, alpha_string: bytes, salt: bytes = b""):
+        return cls.encode_to_curve_batch([alpha_string], [salt])[0]
+
+    @classmethod
+    def encode_to_curve_batch(cls, alpha_strings, salts=None):
+        if not alpha_strings:
+            return []
+        # (a message whose image has no value comes back as DR_ERR_INVALID: a ValueError, as the reference's point constructor raises)
+        return cls._unpack(runtime.context().ed448_encode_to_curve_batch(cls.curve.params.curve_id, list(alpha_strings), salts))
+
+    @classmethod
+    def _valid_points(cls, points) -> list[bool]:
+        """curve.py:56 for a batch: on the curve, not the identity and n P = O (dr_ed448_decode_points with check = 1)"""
+        _, ok = runtime.context().ed448_decode_points(cls._pack(points), True)
+        return [bool(f) for f in ok]
+
+
 class Curve25519Point:
     """Affine point of Curve25519_RO / Curve25519_NU (dot_ring/curve/specs/curve25519.py, montgomery/mg_affine_point.py):
     y^2 = x^3 + 486662 x^2 + x over 2^255 - 19 (x, y are the reference's names for u, v), cofactor 8, the identity is (None, None).
@@ -1660,6 +1769,8 @@ def scalar_mul_batch(points, scalars):
         if len(pts) != len(points):              # a scalar of 2^256 or more became two terms: point by point
             return [p * k for p, k in zip(points, scalars)]
         return cls._unpack(runtime.context().blsg1_scalar_mul_batch(cls._pack(pts), b"".join(k.to_bytes(32, "little") for k in ks)))
+    if issubclass(cls, Ed448Point):              # 56-byte coordinates and scalars: its own entry point
+        return cls._unpack(runtime.context().ed448_scalar_mul_batch(cls._pack(points), cls._scalars(scalars)))
     first = points[0]
     if all(p is first for p in points) and (first.x, first.y) in _fixed_bases(cls):
         # k_i * G (key derivation, curve.py:384) or k_i * B: the constant's fixed-base window table — 64 table additions
@@ -1684,6 +1795,10 @@ def msm_groups(points, scalars, m: int):
     cls = type(points[0])
     if issubclass(cls, Bls12381G1Point):
         return [cls.msm(points[i : i + m], scalars[i : i + m]) for i in range(0, len(points), m)]
+    if issubclass(cls, Ed448Point):
+        if m > 64:                               # the kernel folds up to 64 terms in a wave: longer groups fold on the host (msm)
+            return [cls.msm(points[i : i + m], scalars[i : i + m]) for i in range(0, len(points), m)]
+        return cls._unpack(runtime.context().ed448_msm_groups(cls._pack(points), cls._scalars(scalars), m))
     raw = runtime.context().bsn_msm_groups(pack_points(points), pack_scalars(scalars, cls._N), m, cls._CV)
     return unpack_points(cls, raw)
 
@@ -1691,6 +1806,8 @@ def msm_groups(points, scalars, m: int):
 def valid_points(points) -> list[bool]:
     """curve.py:56 for a whole batch: [h]P != O and [h^-1 mod n][h]P == P (h the cofactor), one launch for all points."""
     if points and isinstance(points[0], Bls12381G1Point):      # E(Fq) is not h x (prime) for a small h: the decoder's r P = O
+        return type(points[0])._valid_points(points)
+    if points and isinstance(points[0], Ed448Point):           # one launch: the decoder's n P = O
         return type(points[0])._valid_points(points)
     live = [i for i, p in enumerate(points) if not p.is_identity() and p.is_on_curve()]
     out = [False] * len(points)
@@ -2035,3 +2152,32 @@ def _bls12_381_g2_variant(name: str, e2c: str, curve_id: int) -> CurveVariant:
 BLS12_381_G2_RO = _bls12_381_g2_variant("BLS12_381_G2_RO", "sswu", _native.CURVE_BLS12_381_G2)
 BLS12_381_G2_NU = _bls12_381_g2_variant("BLS12_381_G2_NU", "sswu_nu", _native.CURVE_BLS12_381_G2_NU)
 BLS12_381_G2 = BLS12_381_G2_RO
+
+
+# dot_ring/curve/specs/ed448.py: x^2 + y^2 = 1 - 39081 x^2 y^2 over 2^448 - 2^224 - 1, cofactor 4, points 112 bytes x || y (point_len 56,
+# uncompressed), 56-byte scalars, SHAKE256 as transcript XOF, hashing to the curve by RFC 9380's edwards448_XOF:SHAKE256_ELL2_RO_ (two
+# field elements) or ..._NU_ (one); both variants share the RO suite id and the generator as Pedersen blinding base, as in the reference.
+# No accumulator base or padding point, so RingProofParams refuses them.
+def _ed448_variant(name: str, e2c: str, curve_id: int) -> CurveVariant:
+    g = (117812161263436946737282484343310064665180535357016373416879082147939404277809514858788439644911793978499419995990477371552926308078495,
+         19)
+    params = SuiteParams(
+        suite_id=b"edwards448_XOF:SHAKE256_ELL2_RO_", hash_fn=hashlib.shake_256, xof=True,
+        auxiliary_points=AuxiliaryPoints(g, None, None),
+        field_modulus=Ed448Point._P,
+        subgroup_order=Ed448Point._N,
+        cofactor=4,
+        a=1,
+        d=-39081,
+        generator=g,
+        encoding=Encoding(point_len=56, challenge_len=64, uncompressed=True),
+        curve_id=curve_id,
+        e2c=e2c,
+    )
+    curve = BandersnatchCurve(params)
+    return CurveVariant(name, curve, type(f"{name}Point", (Ed448Point,), {"__slots__": (), "curve": curve, "_CV": curve_id}))
+
+
+Ed448_RO = _ed448_variant("Ed448_RO", "ell2", _native.CURVE_ED448_RO)
+Ed448_NU = _ed448_variant("Ed448_NU", "ell2_nu", _native.CURVE_ED448_NU)
+Ed448 = Ed448_RO

@@ -16,6 +16,7 @@ def _unsupported(owner, what: str):
 
 class VRF:
     cv = None
+    RING = False                  # RingVRF alone: the scheme carries a ring proof
 
     def __class_getitem__(cls, variant):
         if not isinstance(variant, CurveVariant):
@@ -28,6 +29,10 @@ class VRF:
             #  the reference binds the class and then fails at its first point_to_string
             raise ValueError(f"{cls.__name__} has no {variant.name} suite: the curve has no point codec (point_to_string and "
                              "string_to_point are not implemented), so no key or proof of it can be encoded")
+        if cls.RING and variant.curve.params.curve_id in (_native.CURVE_ED448_RO, _native.CURVE_ED448_NU):
+            #  no accumulator base or padding point, as RingProofParams says, and the ring proof's columns are 32-byte scalars
+            raise ValueError(f"{cls.__name__} has no {variant.name} suite: the curve has no accumulator base and no padding point, and its "
+                             "56-byte coordinates do not fit the ring proof's columns")
         bound = _BOUND.get((cls, variant.name))
         if bound is None or bound.cv is not variant:
             bound = _BOUND[(cls, variant.name)] = type(f"{cls.__name__}[{variant.name}]", (cls,), {"cv": variant})

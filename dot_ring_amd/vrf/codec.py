@@ -1,4 +1,4 @@
-"""Byte codecs of the VRF layer: little-endian scalars of the group order's width, compressed points
+"""Byte codecs of the VRF layer: little-endian scalars of the group order's width (32 bytes, 56 for Ed448), compressed points
 (reference behaviour: dot_ring/vrf/codec.py:9-51 — same function names, lengths and error texts, because the
 reference's tests match on them).  Point decoding is a batch operation here: decompression and the subgroup check of
 any number of points are one kernel launch (dr_bsn_decode_points)."""
@@ -64,12 +64,18 @@ def dec_points(cv, values) -> list:
         blobs.append(v)
     if not blobs:
         return []
-    xy, flags = runtime.context().bsn_decode_points(b"".join(blobs), cv.curve.params.curve_id)
+    wide = getattr(cv.point_type, "_WIDE", False)       # Ed448: 112-byte x || y, checked by dr_ed448_decode_points(check = 1)
+    if wide:
+        xy, flags = runtime.context().ed448_decode_points(b"".join(blobs), True)
+    else:
+        xy, flags = runtime.context().bsn_decode_points(b"".join(blobs), cv.curve.params.curve_id)
     if 0 in flags:
         # the reference reports the first bad point: "Invalid point encoding" when it does not decompress
         # (point.py:176-205), otherwise the subgroup message of dec_point
         cv.point_type.string_to_point(blobs[bytes(flags).index(0)])
         raise ValueError("point is not a valid nonidentity subgroup point")
+    if wide:
+        return cv.point_type._unpack(xy)
     make, le = cv.point_type._trusted, int.from_bytes
     return [make(le(xy[o : o + 32], "little"), le(xy[o + 32 : o + 64], "little")) for o in range(0, 64 * len(blobs), 64)]
 

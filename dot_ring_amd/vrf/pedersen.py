@@ -118,7 +118,8 @@ class PedersenVRF(VRF):
             raise ValueError("batch arguments must have equal lengths")
         if count == 0:
             return []
-        if os.environ.get("DOTRING_NATIVE_HOST", "1") == "0" or not cls.cv.curve.params.auxiliary_points.blinding_base:
+        if (os.environ.get("DOTRING_NATIVE_HOST", "1") == "0" or not cls.cv.curve.params.auxiliary_points.blinding_base
+                or getattr(cls.cv.point_type, "_WIDE", False)):          # (Ed448: dr_pedersen_prove_batch carries 32-byte scalars)
             from ..pipeline import drive
 
             return drive(cls._prove_gen(alphas, secret_keys, additional_data, salts))
@@ -193,7 +194,8 @@ class PedersenVRF(VRF):
         cv = cls.cv
         if salts is None:
             salts = [b""] * len(proofs)
-        if os.environ.get("DOTRING_NATIVE_HOST", "1") != "0" and cv.curve.params.auxiliary_points.blinding_base:
+        if (os.environ.get("DOTRING_NATIVE_HOST", "1") != "0" and cv.curve.params.auxiliary_points.blinding_base
+                and not getattr(cv.point_type, "_WIDE", False)):
             try:
                 if not (len(proofs) == len(inputs) == len(additional_data) == len(salts)):
                     return False

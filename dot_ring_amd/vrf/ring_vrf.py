@@ -207,6 +207,8 @@ def _public_keys_column_data(nm_points, domain_size, omega, prime, pcs):
 # ------------------------------------------------------------------ RingVRF (vrf.py:30-305, proof_payload.py)
 @dataclass
 class RingVRF(VRF):
+    RING = True                   # (VRF.__class_getitem__: the suites whose points the ring proof's 32-byte columns cannot hold are refused)
+
     pedersen_proof: PedersenVRF
     c_b: Column
     c_accip: Column

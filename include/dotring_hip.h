@@ -362,6 +362,45 @@ DR_API int dr_blsg2_check_points(dr_ctx *ctx, int subgroup, const uint8_t *pts_x
 DR_API int dr_blsg2_field_selftest(dr_ctx *ctx, const int32_t *a_limbs /* n*28 */, const int32_t *b_limbs /* n*28 */, size_t n,
                                    uint8_t *out /* n*480 */, uint8_t *flags /* n */);
 
+/* DR_CURVE_ED448_RO (the reference's Ed448 = Ed448_RO) and DR_CURVE_ED448_NU (Ed448_NU): the Edwards curve x^2 + y^2 = 1 - 39081 x^2 y^2
+ * over p = 2^448 - 2^224 - 1 (dot_ring/curve/specs/ed448.py), cofactor 4, hashing by RFC 9380's edwards448_XOF:SHAKE256_ELL2_RO_ (two field
+ * elements) or ..._NU_ (one) — csrc/kernels_ed448.hip.h over csrc/fe448.hip.h.  Entry points of their own (dr_ed448_*); EVERY 64-byte
+ * entry point (dr_te_*, dr_bsn_*, the dr_vrf_suite calls, the ring calls) refuses these two ids with DR_ERR_INVALID, and so do the
+ * dr_blsg1_* / dr_blsg2_* calls as variants.  Formats: field elements and coordinates are 56 bytes little-endian, canonical (< p); points
+ * are affine x || y, 112 bytes, the identity (0, 1) as itself (a point of the curve: no flag byte, no zero-bytes convention); scalars are
+ * 56 bytes used AS THEY ARE (any k < 2^448, no reduction mod the group order: small-order points and images before the cofactor is
+ * cleared are multiplied exactly).  Coordinates or elements at or above p and other per_item values give DR_ERR_INVALID.
+ *   dr_ed448_hash_to_field_batch    host only: expand_message_xof over SHAKE256, L = 84 bytes per element, the variant's DST
+ *                                   (QUUX-V01-CS02-with-edwards448_XOF:SHAKE256_ELL2_RO_ / ..._NU_); two elements (112 bytes) per message
+ *                                   for RO, one (56) for NU.
+ *   dr_ed448_map_to_curve           n items of per_item (2 or 1) elements: out_xy[i] = the sum of their Elligator 2 images (through the
+ *                                   reference's mont_to_ed448), times 4 if clear (clear = 0, per_item = 1: the reference's map_to_curve).
+ *                                   ok[i] = 0 and 112 zero bytes where an image has no value: an element in {0, 1, p - 1}, and no other.
+ *   dr_ed448_encode_to_curve_batch  encode_to_curve(salt_i || msg_i) (salts nullable): hash_to_field on the worker threads, then the map;
+ *                                   DR_ERR_INVALID if a map has no value.
+ *   dr_ed448_scalar_mul_batch       out[i] = k[i] P[i], the window loop on a fixed schedule (113 signed 4-bit windows) as for the other native
+ *                                   suites; the final inversion of Z (division steps) is not fixed-time.
+ *   dr_ed448_msm_groups             out[g] = sum_{j<m} k[g m + j] P[g m + j], m <= 64.
+ *   dr_ed448_decode_points          ok[i] = 1 and out_xy[i] = enc[i] iff both coordinates are below p and the curve equation holds, and
+ *                                   with check = 1 also P is not the identity and n P = O; otherwise ok[i] = 0 and 112 zero bytes.
+ *   dr_ed448_field_selftest         diagnostic of csrc/fe448.hip.h on RAW limb images (16 signed 32-bit limbs an element): out[i] = eleven
+ *                                   56-byte canonical records (a b, a^2, a + b, a - b, -a, carry(a), 39081 a, a^-1, a^((p + 1) / 4), a,
+ *                                   156326 a), flags[i]: bit 0 a is a square, bit 1 a is odd, bit 2 a is zero, bit 3 a = b. */
+enum { DR_CURVE_ED448_RO = 19, DR_CURVE_ED448_NU = 20 };
+DR_API int dr_ed448_hash_to_field_batch(int variant, const uint8_t *msgs, const uint64_t *off, size_t count, uint8_t *out /* count*(112|56) */);
+DR_API int dr_ed448_map_to_curve(dr_ctx *ctx, const uint8_t *us /* n*per_item*56 */, size_t n, int per_item, int clear,
+                                 uint8_t *out_xy /* n*112 */, uint8_t *ok /* n */);
+DR_API int dr_ed448_encode_to_curve_batch(dr_ctx *ctx, int variant, const uint8_t *msgs, const uint64_t *off, const uint8_t *salts,
+                                          const uint64_t *salt_off, size_t count, uint8_t *out_xy /* count*112 */);
+DR_API int dr_ed448_scalar_mul_batch(dr_ctx *ctx, const uint8_t *pts_xy /* n*112 */, const uint8_t *scalars /* n*56 */, size_t n,
+                                     uint8_t *out_xy /* n*112 */);
+DR_API int dr_ed448_msm_groups(dr_ctx *ctx, const uint8_t *pts_xy, const uint8_t *scalars, size_t groups, size_t m,
+                               uint8_t *out_xy /* groups*112 */);
+DR_API int dr_ed448_decode_points(dr_ctx *ctx, int check, const uint8_t *enc /* n*112 */, size_t n, uint8_t *out_xy /* n*112 */,
+                                  uint8_t *ok /* n */);
+DR_API int dr_ed448_field_selftest(dr_ctx *ctx, const int32_t *a_limbs /* n*16 */, const int32_t *b_limbs /* n*16 */, size_t n,
+                                   uint8_t *out /* n*11*56 */, uint8_t *flags /* n */);
+
 /* square root in the Bandersnatch base field; DR_ERR_NOTSQUARE if none exists. Host-side, no ctx. */
 DR_API int dr_fr_sqrt(const uint8_t in[32], uint8_t out[32]);
 
