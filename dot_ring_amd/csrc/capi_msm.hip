@@ -454,16 +454,11 @@ int te_msm_pippenger(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* 
     };
     if (n >= 4096) drh::parallel_for(n, red);
     else for (size_t i = 0; i < n; i++) red(i);
-    // window width by size (the reference's rule grows the same way, bandersnatch.py:23-36); index groups until a bucket
-    // holds ~8 points or 64 groups
-    const int c = n < 4096 ? 7 : n < 16384 ? 8 : n < 65536 ? 9 : 10;
-    // tile scalar_bits + 1 bits, not 256: a top window holding one or two live bits would put half of all points into one bucket
-    const dr::WindowTable wt = dr::make_window_table(c, (int)cu->scalar_bits + 1);
-    const uint32_t H = 1u << (wt.cmax - 1), L = 8, T = H / L;
-    uint32_t groups = 1;
-    while (groups < 64 && n / ((size_t)groups * 2 * H) >= 8) groups *= 2;
-    const size_t sets = (size_t)wt.W * groups, nbuckets = sets * H;
-    const size_t per_set = (n + groups - 1) / groups;
+    // window width, tiling, index groups and capacities: the plan (msm_plan.hpp, checked on the host by tests/native/te_msm_plan_check.cpp)
+    const dr::TeMsmPlan plan = dr::plan_te_msm(n, (int)cu->scalar_bits);
+    const dr::WindowTable& wt = plan.wt;
+    const uint32_t H = plan.H, L = plan.L, T = plan.T, groups = plan.groups;
+    const size_t sets = plan.sets, nbuckets = plan.nbuckets, per_set = plan.per_set;
     hipStream_t st = ctx->stream;
     TRY(ctx->io_a.reserve(n * 64));
     TRY(ctx->io_b.reserve(n * 96));

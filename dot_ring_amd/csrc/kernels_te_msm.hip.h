@@ -14,6 +14,7 @@
 // core is ~50x faster at that than one GPU lane).  Data: points 64 B in, table 96 B, buckets / partials 128 B (X, Y, Z, T).
 #pragma once
 #include "kernels_te.hip.h"
+#include "msm_plan.hpp"
 
 namespace dr {
 
@@ -40,10 +41,7 @@ __global__ void k_te_msm_prepare(const uint32_t* __restrict__ pts /* n*16 std */
     store_fr_std(o + 16, pack(mul(te_d_mont<CV>(), mul(x, y))));
 }
 
-// A bucket longer than this is not walked by one lane but by a whole wave (k_te_msm_accumulate_heavy): skewed scalars — many
-// equal ones, or values much shorter than the windows cover — put thousands of points into one bucket, and a single lane
-// adding them one after the other would be the whole kernel's run time.
-constexpr uint32_t TE_HEAVY_BUCKET = 64;
+// (TE_HEAVY_BUCKET, the list length from which a whole wave walks a bucket, is in msm_plan.hpp with the rest of the call's plan)
 
 template <int CV>
 DR_DEV TePoint te_msm_walk(const uint32_t* __restrict__ table, const uint32_t* __restrict__ sorted, uint32_t beg, uint32_t len, uint32_t first,

@@ -1,5 +1,6 @@
 // The plan of a G1 Pippenger call (msm_device, capi_msm.hip) and the kernel-geometry constants it depends on (kernels_g1.hip.h uses
-// them from here).  Plain host C++ (no HIP): g++ builds it for tests/native/msm_plan_check.cpp.
+// them from here), and the plan of a twisted Edwards Pippenger call (te_msm_pippenger: plan_te_msm).  Plain host C++ (no HIP): g++ builds
+// it for tests/native/msm_plan_check.cpp and tests/native/te_msm_plan_check.cpp.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -77,6 +78,35 @@ inline WindowTable make_window_table(int c, int bits = 256) {      // `bits` sca
     }
     wt.odd = 0;
     return wt;
+}
+
+// ---- the twisted Edwards Pippenger (te_msm_pippenger, capi_msm.hip; kernels_te_msm.hip.h): ONE variable-base MSM of n terms
+// A bucket list longer than this is not walked by one lane but by a whole wave (k_te_msm_accumulate_heavy): skewed scalars — many
+// equal ones, or values much shorter than the windows cover — put thousands of points into one bucket, and a single lane
+// adding them one after the other would be the whole kernel's run time.
+constexpr uint32_t TE_HEAVY_BUCKET = 64;
+constexpr uint32_t TE_REDUCE_CHUNK = 8;                    // buckets per lane of k_te_msm_reduce
+
+struct TeMsmPlan {
+    int c = 0;                           // window width asked for; wt.cmax is the widest one of the tiling
+    WindowTable wt{};
+    uint32_t H = 0, L = 0, T = 0, groups = 1;   // buckets per set, per reduction chunk, chunks per set, index groups
+    size_t sets = 0, nbuckets = 0, per_set = 0; // (window, group) bucket sets, all buckets, entries reserved per set in `sorted`
+};
+
+// scalar_bits: bits of the group order (253 on Bandersnatch, 252 on JubJub); scalars arrive reduced below it
+inline TeMsmPlan plan_te_msm(size_t n, int scalar_bits) {
+    TeMsmPlan p;
+    // window width by size (the reference's rule grows the same way, bandersnatch.py:23-36)
+    p.c = n < 4096 ? 7 : n < 16384 ? 8 : n < 65536 ? 9 : 10;
+    // tile scalar_bits + 1 bits, not 256: a top window holding one or two live bits would put half of all points into one bucket
+    p.wt = make_window_table(p.c, scalar_bits + 1);
+    p.H = 1u << (p.wt.cmax - 1), p.L = TE_REDUCE_CHUNK, p.T = p.H / p.L;
+    // index groups until a bucket holds ~8 points or 64 groups
+    while (p.groups < 64 && n / ((size_t)p.groups * 2 * p.H) >= 8) p.groups *= 2;
+    p.sets = (size_t)p.wt.W * p.groups, p.nbuckets = p.sets * p.H;
+    p.per_set = (n + p.groups - 1) / p.groups;
+    return p;
 }
 
 }  // namespace dr
