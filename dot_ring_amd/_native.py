@@ -7,10 +7,12 @@ from __future__ import annotations
 
 import array
 import ctypes
+import functools
 import itertools
 import threading
 import os
 from ctypes import POINTER, byref, c_char_p, c_double, c_int, c_size_t, c_uint, c_void_p
+from typing import NamedTuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdotring_hip.so")
@@ -321,28 +323,37 @@ def hash_to_field_batch(suite: VrfSuiteStruct, msgs) -> bytes:
     return out.raw[: (32 if suite.curve in _NU_CURVES else 64) * len(msgs)]
 
 
-def blsg1_hash_to_field_batch(variant: int, msgs) -> bytes:
-    """dr_blsg1_hash_to_field_batch (host only): two elements (96 bytes) per message for CURVE_BLS12_381_G1, one (48) for ..._NU"""
+class _Wide(NamedTuple):
+    """One wide suite (csrc/capi_wide.hpp) as its dr_<suite>_* entry points see it: byte widths, selftest record count, the NU variant."""
+    elem: int           # a hashed field element
+    point: int          # x || y
+    scalar: int
+    enc: int            # one input of the flag-returning call
+    limbs: int          # a raw limb image of the field selftest
+    records: int        # results per operand pair of the field selftest
+    nu: int             # the variant id with one element per message
+    flagged: str        # the flag-returning call: "decode_points" (points and flags back) or "check_points" (flags alone)
+
+
+_WIDE = {
+    "blsg1": _Wide(48, 96, 32, 49, 56, 5, CURVE_BLS12_381_G1_NU, "decode_points"),
+    "blsg2": _Wide(96, 192, 96, 192, 112, 5, CURVE_BLS12_381_G2_NU, "check_points"),
+    "ed448": _Wide(56, 112, 56, 112, 64, 11, CURVE_ED448_NU, "decode_points"),
+}
+
+
+def _wide_hash_to_field_batch(suite: str, variant: int, msgs) -> bytes:
+    """dr_<suite>_hash_to_field_batch (host only): two elements per message, one for the suite's NU variant"""
+    w = _WIDE[suite]
     blob, off = _ragged([bytes(m) for m in msgs])
-    out = ctypes.create_string_buffer(max(1, 96 * len(msgs)))
-    _check(lib().dr_blsg1_hash_to_field_batch(variant, blob, off, len(msgs), out))
-    return out.raw[: (48 if variant == CURVE_BLS12_381_G1_NU else 96) * len(msgs)]
+    out = ctypes.create_string_buffer(max(1, 2 * w.elem * len(msgs)))
+    _check(getattr(lib(), f"dr_{suite}_hash_to_field_batch")(variant, blob, off, len(msgs), out))
+    return out.raw[: (1 if variant == w.nu else 2) * w.elem * len(msgs)]
 
 
-def blsg2_hash_to_field_batch(variant: int, msgs) -> bytes:
-    """dr_blsg2_hash_to_field_batch (host only): two Fq2 elements (192 bytes) per message for CURVE_BLS12_381_G2, one (96) for ..._NU"""
-    blob, off = _ragged([bytes(m) for m in msgs])
-    out = ctypes.create_string_buffer(max(1, 192 * len(msgs)))
-    _check(lib().dr_blsg2_hash_to_field_batch(variant, blob, off, len(msgs), out))
-    return out.raw[: (96 if variant == CURVE_BLS12_381_G2_NU else 192) * len(msgs)]
-
-
-def ed448_hash_to_field_batch(variant: int, msgs) -> bytes:
-    """dr_ed448_hash_to_field_batch (host only): two elements (112 bytes) per message for CURVE_ED448_RO, one (56) for CURVE_ED448_NU"""
-    blob, off = _ragged([bytes(m) for m in msgs])
-    out = ctypes.create_string_buffer(max(1, 112 * len(msgs)))
-    _check(lib().dr_ed448_hash_to_field_batch(variant, blob, off, len(msgs), out))
-    return out.raw[: (56 if variant == CURVE_ED448_NU else 112) * len(msgs)]
+blsg1_hash_to_field_batch = functools.partial(_wide_hash_to_field_batch, "blsg1")
+blsg2_hash_to_field_batch = functools.partial(_wide_hash_to_field_batch, "blsg2")
+ed448_hash_to_field_batch = functools.partial(_wide_hash_to_field_batch, "ed448")
 
 
 def lib() -> ctypes.CDLL:
@@ -631,12 +642,13 @@ class Context:
         _check(lib().dr_fr_ops_selftest(self.handle, a, b, n, out, flags))
         return out.raw[: 384 * n], flags.raw[:n]
 
-    def _limb_selftest(self, fn, records: int, a_limbs: bytes, b_limbs: bytes):
-        """(n x records x 32 result bytes, n flag bytes) of one native suite's field selftest on n pairs of raw 9-limb images."""
-        n = len(a_limbs) // 36
-        if len(a_limbs) != 36 * n or len(b_limbs) != 36 * n:
-            raise ValueError("operands are 9 int32 limbs each")
-        rec = 32 * records
+    def _limb_selftest(self, fn, records: int, a_limbs: bytes, b_limbs: bytes, limb_bytes: int = 36, elem: int = 32):
+        """(n x records x elem result bytes, n flag bytes) of one native suite's field selftest on n pairs of raw limb images (nine limbs
+        and 32-byte results on the 256-bit suites)."""
+        n = len(a_limbs) // limb_bytes
+        if len(a_limbs) != limb_bytes * n or len(b_limbs) != limb_bytes * n:
+            raise ValueError(f"operands are {limb_bytes // 4} int32 limbs each")
+        rec = elem * records
         out, flags = ctypes.create_string_buffer(max(1, rec * n)), ctypes.create_string_buffer(max(1, n))
         _check(fn(self.handle, a_limbs, b_limbs, n, out, flags))
         return out.raw[: rec * n], flags.raw[:n]
@@ -678,168 +690,92 @@ class Context:
         """dr_secp256k1_field_selftest: (n x 12 x 32 result bytes, n flag bytes) for n pairs of raw 9-limb images."""
         return self._limb_selftest(lib().dr_secp256k1_field_selftest, 12, a_limbs, b_limbs)
 
-    # ---- BLS12-381 G1 (include/dotring_hip.h: points 96 bytes x || y little-endian, 96 zero bytes the identity; scalars as they are)
-    def blsg1_map_to_curve(self, us: bytes, per_item: int, clear: bool = True):
-        """dr_blsg1_map_to_curve: (x||y bytes, flags) for len(us) / (48 per_item) items; clear = False: before the cofactor clearing."""
-        if per_item not in (1, 2) or len(us) % (48 * per_item):
-            raise ValueError("field elements are 48 bytes each, one or two per item")
-        n = len(us) // (48 * per_item)
-        out, ok = ctypes.create_string_buffer(max(1, 96 * n)), ctypes.create_string_buffer(max(1, n))
-        _check(lib().dr_blsg1_map_to_curve(self.handle, us, n, per_item, 1 if clear else 0, out, ok))
-        return out.raw[: 96 * n], ok.raw[:n]
+    # ---- the wide suites (include/dotring_hip.h; widths in _WIDE): BLS12-381 G1 (points 96 bytes x || y little-endian, 96 zero bytes the
+    # identity), G2 (Fq2 elements c0 || c1; 192 zero bytes the identity) and Ed448 (the identity (0, 1) as itself); scalars as they are
+    def _wide_map_to_curve(self, suite: str, us: bytes, per_item: int, clear: bool = True):
+        """dr_<suite>_map_to_curve: (x||y bytes, flags) for len(us) / (elem per_item) items; clear = False: before the cofactor clearing.
+        per_item other than 1 or 2 is the library's to refuse."""
+        w = _WIDE[suite]
+        if len(us) % w.elem or (per_item in (1, 2) and len(us) % (w.elem * per_item)):
+            raise ValueError(f"field elements are {w.elem} bytes each, one or two per item")
+        n = len(us) // (w.elem * per_item) if per_item in (1, 2) else len(us) // w.elem
+        out, ok = ctypes.create_string_buffer(max(1, w.point * n)), ctypes.create_string_buffer(max(1, n))
+        _check(getattr(lib(), f"dr_{suite}_map_to_curve")(self.handle, us, n, per_item, 1 if clear else 0, out, ok))
+        return out.raw[: w.point * n], ok.raw[:n]
 
-    def blsg1_encode_to_curve_batch(self, variant: int, msgs, salts=None) -> bytes:
-        """dr_blsg1_encode_to_curve_batch: encode_to_curve(salt_i || msg_i) -> count * 96 bytes x||y."""
-        count = len(msgs)
+    def _wide_encode_to_curve_batch(self, suite: str, variant: int, msgs, salts=None) -> bytes:
+        """dr_<suite>_encode_to_curve_batch: encode_to_curve(salt_i || msg_i) -> count points x||y."""
+        w, count = _WIDE[suite], len(msgs)
         m_blob, m_off = _ragged([bytes(m) for m in msgs])
         s_blob, s_off = (None, None) if not salts or not any(salts) else _ragged([bytes(x) for x in salts])
-        out = ctypes.create_string_buffer(max(96 * count, 1))
-        _check(lib().dr_blsg1_encode_to_curve_batch(self.handle, variant, m_blob, m_off, s_blob, s_off, count, out))
-        return out.raw[: 96 * count]
+        out = ctypes.create_string_buffer(max(w.point * count, 1))
+        _check(getattr(lib(), f"dr_{suite}_encode_to_curve_batch")(self.handle, variant, m_blob, m_off, s_blob, s_off, count, out))
+        return out.raw[: w.point * count]
 
-    def blsg1_scalar_mul_batch(self, pts_xy: bytes, scalars: bytes) -> bytes:
-        """dr_blsg1_scalar_mul_batch: k_i P_i for n points of E(Fq) and n 32-byte scalars used as they are."""
-        n = len(scalars) // 32
-        if len(scalars) != 32 * n or len(pts_xy) != 96 * n:
+    def _wide_scalar_mul_batch(self, suite: str, pts_xy: bytes, scalars: bytes) -> bytes:
+        """dr_<suite>_scalar_mul_batch: k_i P_i for n points and n scalars used as they are."""
+        w = _WIDE[suite]
+        n = len(scalars) // w.scalar
+        if len(scalars) != w.scalar * n or len(pts_xy) != w.point * n:
             raise ValueError("Points and scalars must have same length")
-        out = ctypes.create_string_buffer(max(1, 96 * n))
-        _check(lib().dr_blsg1_scalar_mul_batch(self.handle, pts_xy, scalars, n, out))
-        return out.raw[: 96 * n]
+        out = ctypes.create_string_buffer(max(1, w.point * n))
+        _check(getattr(lib(), f"dr_{suite}_scalar_mul_batch")(self.handle, pts_xy, scalars, n, out))
+        return out.raw[: w.point * n]
 
-    def blsg1_msm_groups(self, pts_xy: bytes, scalars: bytes, m: int) -> bytes:
-        """dr_blsg1_msm_groups: the sums of consecutive groups of m (1..64) terms."""
-        n = len(scalars) // 32
-        if m < 1 or len(scalars) != 32 * n or len(pts_xy) != 96 * n or n % m:
+    def _wide_msm_groups(self, suite: str, pts_xy: bytes, scalars: bytes, m: int) -> bytes:
+        """dr_<suite>_msm_groups: the sums of consecutive groups of m (1..64) terms k_j P_j."""
+        w = _WIDE[suite]
+        n = len(scalars) // w.scalar
+        if m < 1 or len(scalars) != w.scalar * n or len(pts_xy) != w.point * n or n % m:
             raise ValueError("Points and scalars must have same length, a multiple of the group size")
         groups = n // m
-        out = ctypes.create_string_buffer(max(1, 96 * groups))
-        _check(lib().dr_blsg1_msm_groups(self.handle, pts_xy, scalars, groups, m, out))
-        return out.raw[: 96 * groups]
+        out = ctypes.create_string_buffer(max(1, w.point * groups))
+        _check(getattr(lib(), f"dr_{suite}_msm_groups")(self.handle, pts_xy, scalars, groups, m, out))
+        return out.raw[: w.point * groups]
 
-    def blsg1_decode_points(self, enc: bytes, check: bool = True):
-        """dr_blsg1_decode_points: (x||y bytes, flags) for len(enc)/49 SEC1 encodings; check: also r P = O."""
-        if len(enc) % 49:
-            raise ValueError("compressed points are 49 bytes each")
-        count = len(enc) // 49
-        out, ok = ctypes.create_string_buffer(max(1, 96 * count)), ctypes.create_string_buffer(max(1, count))
-        _check(lib().dr_blsg1_decode_points(self.handle, 1 if check else 0, enc, count, out, ok))
-        return out.raw[: 96 * count], ok.raw[:count]
+    def _wide_flagged(self, suite: str, enc: bytes, check: bool = True):
+        """dr_<suite>_decode_points: (x||y bytes, flags) for G1's 49-byte SEC1 encodings (check: also r P = O) and Ed448's 112-byte points
+        (coordinates below p and on the curve; check: also not the identity and n P = O).  dr_blsg2_check_points: the flags alone, one per
+        192-byte point: on the curve, and with `check` also r P = O."""
+        w = _WIDE[suite]
+        if len(enc) % w.enc:
+            raise ValueError(f"points are {w.enc} bytes each")
+        n = len(enc) // w.enc
+        ok = ctypes.create_string_buffer(max(1, n))
+        fn = getattr(lib(), f"dr_{suite}_{w.flagged}")
+        if w.flagged == "check_points":
+            _check(fn(self.handle, 1 if check else 0, enc, n, ok))
+            return ok.raw[:n]
+        out = ctypes.create_string_buffer(max(1, w.point * n))
+        _check(fn(self.handle, 1 if check else 0, enc, n, out, ok))
+        return out.raw[: w.point * n], ok.raw[:n]
 
-    def blsg1_field_selftest(self, a_limbs: bytes, b_limbs: bytes):
-        """dr_blsg1_field_selftest: (n x 5 x 48 result bytes, n flag bytes) for n pairs of raw 14-limb images (little-endian int32 each)."""
-        n = len(a_limbs) // 56
-        if len(a_limbs) != 56 * n or len(b_limbs) != 56 * n:
-            raise ValueError("operands are 14 int32 limbs each")
-        out, flags = ctypes.create_string_buffer(max(1, 240 * n)), ctypes.create_string_buffer(max(1, n))
-        _check(lib().dr_blsg1_field_selftest(self.handle, a_limbs, b_limbs, n, out, flags))
-        return out.raw[: 240 * n], flags.raw[:n]
+    def _wide_field_selftest(self, suite: str, a_limbs: bytes, b_limbs: bytes):
+        """dr_<suite>_field_selftest: (n x records x elem result bytes, n flag bytes) for n pairs of raw limb images (little-endian int32:
+        14 limbs for G1, 2 x 14 for G2, 16 for Ed448)."""
+        w = _WIDE[suite]
+        return self._limb_selftest(getattr(lib(), f"dr_{suite}_field_selftest"), w.records, a_limbs, b_limbs, w.limbs, w.elem)
 
-    # ---- BLS12-381 G2 (include/dotring_hip.h: Fq2 elements c0 || c1, 96 bytes; points 192 bytes x || y, 192 zero bytes the identity;
-    # scalars 96 bytes as they are)
-    def blsg2_map_to_curve(self, us: bytes, per_item: int, clear: bool = True):
-        """dr_blsg2_map_to_curve: (x||y bytes, flags) for len(us) / (96 per_item) items; clear = False: before the cofactor clearing.
-        per_item other than 1 or 2 is the library's to refuse."""
-        if len(us) % 96 or (per_item in (1, 2) and len(us) % (96 * per_item)):
-            raise ValueError("field elements are 96 bytes each, one or two per item")
-        n = len(us) // (96 * per_item) if per_item in (1, 2) else len(us) // 96
-        out, ok = ctypes.create_string_buffer(max(1, 192 * n)), ctypes.create_string_buffer(max(1, n))
-        _check(lib().dr_blsg2_map_to_curve(self.handle, us, n, per_item, 1 if clear else 0, out, ok))
-        return out.raw[: 192 * n], ok.raw[:n]
-
-    def blsg2_encode_to_curve_batch(self, variant: int, msgs, salts=None) -> bytes:
-        """dr_blsg2_encode_to_curve_batch: encode_to_curve(salt_i || msg_i) -> count * 192 bytes x||y."""
-        count = len(msgs)
-        m_blob, m_off = _ragged([bytes(m) for m in msgs])
-        s_blob, s_off = (None, None) if not salts or not any(salts) else _ragged([bytes(x) for x in salts])
-        out = ctypes.create_string_buffer(max(192 * count, 1))
-        _check(lib().dr_blsg2_encode_to_curve_batch(self.handle, variant, m_blob, m_off, s_blob, s_off, count, out))
-        return out.raw[: 192 * count]
-
-    def blsg2_scalar_mul_batch(self, pts_xy: bytes, scalars: bytes) -> bytes:
-        """dr_blsg2_scalar_mul_batch: k_i P_i for n points of E(Fq2) and n 96-byte scalars used as they are."""
-        n = len(scalars) // 96
-        if len(scalars) != 96 * n or len(pts_xy) != 192 * n:
-            raise ValueError("Points and scalars must have same length")
-        out = ctypes.create_string_buffer(max(1, 192 * n))
-        _check(lib().dr_blsg2_scalar_mul_batch(self.handle, pts_xy, scalars, n, out))
-        return out.raw[: 192 * n]
+    blsg1_map_to_curve = functools.partialmethod(_wide_map_to_curve, "blsg1")
+    blsg1_encode_to_curve_batch = functools.partialmethod(_wide_encode_to_curve_batch, "blsg1")
+    blsg1_scalar_mul_batch = functools.partialmethod(_wide_scalar_mul_batch, "blsg1")
+    blsg1_msm_groups = functools.partialmethod(_wide_msm_groups, "blsg1")
+    blsg1_decode_points = functools.partialmethod(_wide_flagged, "blsg1")
+    blsg1_field_selftest = functools.partialmethod(_wide_field_selftest, "blsg1")
+    blsg2_map_to_curve = functools.partialmethod(_wide_map_to_curve, "blsg2")
+    blsg2_encode_to_curve_batch = functools.partialmethod(_wide_encode_to_curve_batch, "blsg2")
+    blsg2_scalar_mul_batch = functools.partialmethod(_wide_scalar_mul_batch, "blsg2")
+    blsg2_field_selftest = functools.partialmethod(_wide_field_selftest, "blsg2")
+    ed448_map_to_curve = functools.partialmethod(_wide_map_to_curve, "ed448")
+    ed448_encode_to_curve_batch = functools.partialmethod(_wide_encode_to_curve_batch, "ed448")
+    ed448_scalar_mul_batch = functools.partialmethod(_wide_scalar_mul_batch, "ed448")
+    ed448_msm_groups = functools.partialmethod(_wide_msm_groups, "ed448")
+    ed448_decode_points = functools.partialmethod(_wide_flagged, "ed448")
+    ed448_field_selftest = functools.partialmethod(_wide_field_selftest, "ed448")
 
     def blsg2_check_points(self, pts_xy: bytes, subgroup: bool = True) -> bytes:
         """dr_blsg2_check_points: one flag byte per 192-byte point: on the curve, and with `subgroup` also r P = O."""
-        if len(pts_xy) % 192:
-            raise ValueError("points are 192 bytes each")
-        n = len(pts_xy) // 192
-        ok = ctypes.create_string_buffer(max(1, n))
-        _check(lib().dr_blsg2_check_points(self.handle, 1 if subgroup else 0, pts_xy, n, ok))
-        return ok.raw[:n]
-
-    def blsg2_field_selftest(self, a_limbs: bytes, b_limbs: bytes):
-        """dr_blsg2_field_selftest: (n x 5 x 96 result bytes, n flag bytes) for n pairs of raw 2 x 14-limb images (little-endian int32)."""
-        n = len(a_limbs) // 112
-        if len(a_limbs) != 112 * n or len(b_limbs) != 112 * n:
-            raise ValueError("operands are 2 x 14 int32 limbs each")
-        out, flags = ctypes.create_string_buffer(max(1, 480 * n)), ctypes.create_string_buffer(max(1, n))
-        _check(lib().dr_blsg2_field_selftest(self.handle, a_limbs, b_limbs, n, out, flags))
-        return out.raw[: 480 * n], flags.raw[:n]
-
-    # ---- Ed448 (include/dotring_hip.h: field elements 56 bytes; points 112 bytes x || y, the identity (0, 1) as itself; scalars 56 bytes as
-    # they are)
-    def ed448_map_to_curve(self, us: bytes, per_item: int, clear: bool = True):
-        """dr_ed448_map_to_curve: (x||y bytes, flags) for len(us) / (56 per_item) items; clear = False: before the cofactor clearing.
-        per_item other than 1 or 2 is the library's to refuse."""
-        if len(us) % 56 or (per_item in (1, 2) and len(us) % (56 * per_item)):
-            raise ValueError("field elements are 56 bytes each, one or two per item")
-        n = len(us) // (56 * per_item) if per_item in (1, 2) else len(us) // 56
-        out, ok = ctypes.create_string_buffer(max(1, 112 * n)), ctypes.create_string_buffer(max(1, n))
-        _check(lib().dr_ed448_map_to_curve(self.handle, us, n, per_item, 1 if clear else 0, out, ok))
-        return out.raw[: 112 * n], ok.raw[:n]
-
-    def ed448_encode_to_curve_batch(self, variant: int, msgs, salts=None) -> bytes:
-        """dr_ed448_encode_to_curve_batch: encode_to_curve(salt_i || msg_i) -> count * 112 bytes x||y."""
-        count = len(msgs)
-        m_blob, m_off = _ragged([bytes(m) for m in msgs])
-        s_blob, s_off = (None, None) if not salts or not any(salts) else _ragged([bytes(x) for x in salts])
-        out = ctypes.create_string_buffer(max(112 * count, 1))
-        _check(lib().dr_ed448_encode_to_curve_batch(self.handle, variant, m_blob, m_off, s_blob, s_off, count, out))
-        return out.raw[: 112 * count]
-
-    def ed448_scalar_mul_batch(self, pts_xy: bytes, scalars: bytes) -> bytes:
-        """dr_ed448_scalar_mul_batch: k_i P_i for n points and n 56-byte scalars used as they are."""
-        n = len(scalars) // 56
-        if len(scalars) != 56 * n or len(pts_xy) != 112 * n:
-            raise ValueError("Points and scalars must have same length")
-        out = ctypes.create_string_buffer(max(1, 112 * n))
-        _check(lib().dr_ed448_scalar_mul_batch(self.handle, pts_xy, scalars, n, out))
-        return out.raw[: 112 * n]
-
-    def ed448_msm_groups(self, pts_xy: bytes, scalars: bytes, m: int) -> bytes:
-        """dr_ed448_msm_groups: the sums of consecutive groups of m (<= 64) terms k_j P_j -> groups * 112 bytes."""
-        n = len(scalars) // 56
-        if len(scalars) != 56 * n or len(pts_xy) != 112 * n or m <= 0 or n % m:
-            raise ValueError("Points and scalars must have same length, a multiple of the group size")
-        groups = n // m
-        out = ctypes.create_string_buffer(max(1, 112 * groups))
-        _check(lib().dr_ed448_msm_groups(self.handle, pts_xy, scalars, groups, m, out))
-        return out.raw[: 112 * groups]
-
-    def ed448_decode_points(self, enc: bytes, check: bool = True):
-        """dr_ed448_decode_points: (x||y bytes, flags) for 112-byte points: coordinates below p and on the curve; with `check` also not the
-        identity and n P = O."""
-        if len(enc) % 112:
-            raise ValueError("points are 112 bytes each")
-        n = len(enc) // 112
-        out, ok = ctypes.create_string_buffer(max(1, 112 * n)), ctypes.create_string_buffer(max(1, n))
-        _check(lib().dr_ed448_decode_points(self.handle, 1 if check else 0, enc, n, out, ok))
-        return out.raw[: 112 * n], ok.raw[:n]
-
-    def ed448_field_selftest(self, a_limbs: bytes, b_limbs: bytes):
-        """dr_ed448_field_selftest: (n x 11 x 56 result bytes, n flag bytes) for n pairs of raw 16-limb images (little-endian int32)."""
-        n = len(a_limbs) // 64
-        if len(a_limbs) != 64 * n or len(b_limbs) != 64 * n:
-            raise ValueError("operands are 16 int32 limbs each")
-        out, flags = ctypes.create_string_buffer(max(1, 616 * n)), ctypes.create_string_buffer(max(1, n))
-        _check(lib().dr_ed448_field_selftest(self.handle, a_limbs, b_limbs, n, out, flags))
-        return out.raw[: 616 * n], flags.raw[:n]
+        return self._wide_flagged("blsg2", pts_xy, subgroup)
 
     def _map_to_curve(self, fn, us: bytes, per_item: int):
         if per_item not in (1, 2) or len(us) % (32 * per_item):

@@ -809,13 +809,7 @@ int native_decode_points(S, dr_ctx* ctx, decltype(S::dec_tai) kernel, const uint
         hipLaunchKernelGGL(kernel, dim3(div_up(n, S::block)), dim3(S::block), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
                            ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
     }));
-    std::vector<uint32_t> flags(n);
-    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_b.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(flags.data(), ctx->io_c.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->prof) TRY(prof_collect(ctx));
-    for (size_t i = 0; i < n; i++) ok[i] = flags[i] ? 1 : 0;
-    return DR_OK;
+    return finish_flagged(ctx, out_xy, ctx->io_b.p, n * 64, ctx->io_c.p, n, ok);
 }
 // the field selftests: n pairs of raw 9-limb images in, S::selftest_records results of 32 bytes and one flag byte per pair out
 template <class S>
@@ -835,9 +829,7 @@ int native_field_selftest(S, dr_ctx* ctx, const int32_t* a_limbs, const int32_t*
                        (const int32_t*)(ctx->io_a.as<uint8_t>() + n * 36), (uint32_t)n, ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>());
     HIP_TRY(hipGetLastError());
     std::vector<uint32_t> fl(n);
-    HIP_TRY(hipMemcpyAsync(out, ctx->io_b.p, n * rec, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(fl.data(), ctx->io_c.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    TRY(download_flagged(ctx, out, ctx->io_b.p, n * rec, ctx->io_c.p, fl));
     for (size_t i = 0; i < n; i++) flags[i] = (uint8_t)fl[i];
     return DR_OK;
 }
@@ -1278,13 +1270,7 @@ int native_map_to_curve(dr_ctx* ctx, const char* name, MapKernel kernel, int blo
         hipLaunchKernelGGL(kernel, dim3(div_up(n, block)), dim3(block), 0, ctx->stream, ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(),
                            ctx->io_c.as<uint32_t>(), (uint32_t)n, (uint32_t)per_item);
     }));
-    std::vector<uint32_t> flags(n);
-    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_b.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(flags.data(), ctx->io_c.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->prof) TRY(prof_collect(ctx));
-    for (size_t i = 0; i < n; i++) ok[i] = flags[i] ? 1 : 0;
-    return DR_OK;
+    return finish_flagged(ctx, out_xy, ctx->io_b.p, n * 64, ctx->io_c.p, n, ok);
 }
 }  // namespace
 int dr_secp256k1_map_to_curve(dr_ctx* ctx, const uint8_t* us, size_t n, int per_item, uint8_t* out_xy, uint8_t* ok) {

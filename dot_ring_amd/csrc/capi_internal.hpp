@@ -7,6 +7,8 @@
 //   capi_blsg1.hip  the BLS12_381_G1 suites: 48-byte coordinates, hashing to G1 and the group of E(Fq)
 //   capi_blsg2.hip  the BLS12_381_G2 suites: Fq2 coordinates, hashing to G2 and the group of E(Fq2)
 //   capi_ed448.hip  the Ed448 suites: 56-byte coordinates and scalars, hashing to the curve and the group of E(F_p)
+// The last three are one description of their suite each (widths, limits, kernels, hashing parameters) and their entry points as calls
+// of capi_wide.hpp's templates, the one host path of the suites whose coordinates do not fit the 64-byte paths of capi_core.hip.
 // Each header that defines kernels is included by exactly one of them; the others reach its kernels through the launch wrappers below.
 // (kernels_g1_h2c.hip.h defines none: the two BLS12-381 hashing units share its device functions.)
 #pragma once
@@ -197,6 +199,23 @@ int launch(dr_ctx* ctx, const char* name, F&& f) {
     } while (0)
 
 inline unsigned div_up(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
+
+// The tail of a call whose kernel leaves one flag word per item in d_flags beside its results: `bytes` of results (d_out to out; none
+// where out is null) and the n flag words to the host, then wait for the stream.
+inline int download_flagged(dr_ctx* ctx, void* out, const void* d_out, size_t bytes, const void* d_flags, std::vector<uint32_t>& flags) {
+    if (out) HIP_TRY(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(flags.data(), d_flags, flags.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return DR_OK;
+}
+// ... of a profiled launch: the kernel timers collected, and each flag word as one byte, 1 or 0
+inline int finish_flagged(dr_ctx* ctx, void* out, const void* d_out, size_t bytes, const void* d_flags, size_t n, uint8_t* ok) {
+    std::vector<uint32_t> flags(n);
+    TRY(download_flagged(ctx, out, d_out, bytes, d_flags, flags));
+    if (ctx->prof) TRY(prof_collect(ctx));
+    for (size_t i = 0; i < n; i++) ok[i] = flags[i] ? 1 : 0;
+    return DR_OK;
+}
 
 // The device keeps Fq in Montgomery form with R = 2^392 (14 x 28-bit limbs, fq28.hip.h), the host with R = 2^384
 // (6 x 64-bit limbs, hostmath.hpp); both store canonical little-endian words, so crossing the boundary is one Montgomery

@@ -21,6 +21,7 @@
 #include <thread>
 #include <vector>
 
+#include "hosth2c.hpp"
 #include "hosthash.hpp"
 #include "hostmath.hpp"
 
@@ -755,34 +756,14 @@ inline Bytes h2c_dst(const VrfSuite& su) {
     if (su.cv->nu && dst.size() >= 4 && std::memcmp(&dst[dst.size() - 4], "_RO_", 4) == 0) { dst[dst.size() - 3] = 'N'; dst[dst.size() - 2] = 'U'; }
     return dst;
 }
-// RFC 9380 hash_to_field (curve.py:110-185) by expand_message_xmd over the hash H with digests of DIGEST bytes and a Z_pad of BLOCK
-// bytes (the hash's block: specs' expand_len): 48 bytes per element, big-endian, mod `field`.  `count` is 2 (uniform, RO) or 1
+// RFC 9380 hash_to_field (curve.py:110-185) by hosth2c.hpp's expand_message_xmd over the hash H with digests of DIGEST bytes and a Z_pad
+// of BLOCK bytes (the hash's block: specs' expand_len): 48 bytes per element, big-endian, mod `field`.  `count` is 2 (uniform, RO) or 1
 // (nonuniform); out = count x 32 bytes little-endian.  SHA-256 (64 / 32: secp256k1, P-256) needs 3 or 2 blocks for 96 or 48 bytes,
 // SHA-512 (128 / 64: Ed25519_RO / Ed25519_NU) 2 or 1.
 template <class H, size_t BLOCK, size_t DIGEST>
-inline void hash_to_field_xmd(Bytes dst, const Mod256& field, const uint8_t* msg, size_t len, unsigned count, uint8_t* out) {
-    put8(dst, (uint8_t)dst.size());                  // DST_prime = DST || len(DST)
-    const size_t L = 48 * (size_t)count;
-    uint8_t b0[DIGEST], prev[DIGEST], raw[2 * DIGEST > 96 ? 2 * DIGEST : 96];
-    const uint8_t zpad[BLOCK] = {0};
-    H h;
-    h.update(zpad, BLOCK);
-    if (len) h.update(msg, len);                     // (an empty message has no buffer to read)
-    const uint8_t lb[3] = {0, (uint8_t)L, 0};
-    h.update(lb, 3);
-    h.update(dst.data(), dst.size());
-    h.final(b0);
-    for (size_t i = 1; DIGEST * (i - 1) < L; i++) {
-        H g;
-        uint8_t x[DIGEST];
-        for (size_t j = 0; j < DIGEST; j++) x[j] = i == 1 ? b0[j] : (uint8_t)(b0[j] ^ prev[j]);
-        g.update(x, DIGEST);
-        const uint8_t ib = (uint8_t)i;
-        g.update(&ib, 1);
-        g.update(dst.data(), dst.size());
-        g.final(prev);
-        std::memcpy(raw + DIGEST * (i - 1), prev, DIGEST);
-    }
+inline void hash_to_field_xmd(const Bytes& dst, const Mod256& field, const uint8_t* msg, size_t len, unsigned count, uint8_t* out) {
+    uint8_t raw[96];
+    expand_message_xmd<H, BLOCK, DIGEST>(dst.data(), dst.size(), nullptr, 0, msg, len, 48 * (size_t)count, raw);
     for (unsigned k = 0; k < count; k++) {
         uint64_t v[4];
         field.reduce_bytes(raw + 48 * k, 48, true, v);

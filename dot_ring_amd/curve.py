@@ -115,6 +115,68 @@ def _sqrt_tonelli_shanks(v: int, p: int) -> int:
     return r
 
 
+class _Rfc9380:
+    """Hashing to the curve by RFC 9380 as every suite here does it: hash_to_field natively on the host, the map on the GPU.  The default
+    hooks are the 256-bit suites' (the library's dr_vrf_suite entry points); a class supplies what differs:
+      _mapped(us, per_item)       the device half: points for packed field elements, per_item of them each
+      _hash_to_field(msgs)        the library's hash_to_field for many messages, packed little-endian
+      _encoded(msgs, salts)       the library's encode_to_curve for many messages, unpacked"""
+    __slots__ = ()
+
+    @classmethod
+    def _per_item(cls) -> int:
+        return 1 if cls.curve.params.e2c.endswith("_nu") else 2
+
+    @classmethod
+    def _hash_to_field(cls, msgs) -> bytes:
+        return _native.hash_to_field_batch(cls._suite_struct(), msgs)
+
+    @classmethod
+    def _encoded(cls, msgs, salts):
+        # (a message whose image has no value comes back as DR_ERR_INVALID: a ValueError, as the reference's failing step is)
+        return unpack_points(cls, runtime.context().encode_to_curve_batch(cls._suite_struct(), msgs, salts))
+
+    @classmethod
+    def hash_to_field_pairs(cls, alpha_strings, salts=None) -> bytes:
+        """Host half of encode_to_curve for many inputs: two field elements per input (one for the NU variant), packed little-endian."""
+        salts = salts or [b""] * len(alpha_strings)
+        return cls._hash_to_field([bytes(s) + bytes(a) for a, s in zip(alpha_strings, salts)])
+
+    @classmethod
+    def encode_to_curve_from_field(cls, us: bytes):
+        """Device half: the maps, for RO the sum of the two images, and the cofactor, for packed canonical field elements."""
+        return cls._mapped(us, cls._per_item()) if us else []
+
+    @classmethod
+    def encode_to_curve(cls, alpha_string: bytes, salt: bytes = b""):
+        return cls.encode_to_curve_batch([alpha_string], [salt])[0]
+
+    @classmethod
+    def encode_to_curve_batch(cls, alpha_strings, salts=None):
+        return cls._encoded(list(alpha_strings), salts) if alpha_strings else []
+
+
+class _WideRfc9380(_Rfc9380):
+    """... over a wide suite's own entry points (_native._WIDE): the class names its suite (_SUITE), unpacks the points (_unpack) and words
+    the refusal of a field element without an image as the reference's failing step does (_NO_IMAGE)."""
+    __slots__ = ()
+
+    @classmethod
+    def _mapped(cls, us: bytes, per_item: int, clear: bool = True):
+        raw, ok = runtime.context()._wide_map_to_curve(cls._SUITE, us, per_item, clear)
+        if 0 in ok:
+            raise ValueError(cls._NO_IMAGE)
+        return cls._unpack(raw)
+
+    @classmethod
+    def _hash_to_field(cls, msgs) -> bytes:
+        return _native._wide_hash_to_field_batch(cls._SUITE, cls.curve.params.curve_id, msgs)
+
+    @classmethod
+    def _encoded(cls, msgs, salts):
+        return cls._unpack(runtime.context()._wide_encode_to_curve_batch(cls._SUITE, cls.curve.params.curve_id, msgs, salts))
+
+
 class BandersnatchCurve:
     def __init__(self, params: SuiteParams):
         self.params = params
@@ -754,7 +816,7 @@ class ShortWeierstrassA0Point:
         return self + (-other)
 
 
-class Secp256k1Point(ShortWeierstrassA0Point):
+class Secp256k1Point(_Rfc9380, ShortWeierstrassA0Point):
     """Affine point of secp256k1 (dot_ring/curve/specs/secp256k1.py): y^2 = x^3 + 7 over its own field, cofactor 1, the identity is
     (None, None).  Single additions are host big-int code; scalar multiplications, MSMs, decoding and hashing to the curve (RFC 9380:
     simplified SWU and the 3-isogeny) run on the GPU under the suite's curve id (kernels_secp256k1.hip.h)."""
@@ -833,10 +895,6 @@ class Secp256k1Point(ShortWeierstrassA0Point):
     _suite_struct = BandersnatchPoint.__dict__["_suite_struct"]
 
     @classmethod
-    def _per_item(cls) -> int:
-        return 1 if cls.curve.params.e2c == "sswu_nu" else 2
-
-    @classmethod
     def _mapped(cls, us: bytes, per_item: int):
         raw, ok = runtime.context().secp256k1_map_to_curve(us, per_item)
         if 0 in ok:
@@ -847,30 +905,8 @@ class Secp256k1Point(ShortWeierstrassA0Point):
     def map_to_curve_simple_swu(cls, u: int):
         return cls._mapped((int(u) % cls._P).to_bytes(32, "little"), 1)[0]
 
-    @classmethod
-    def hash_to_field_pairs(cls, alpha_strings, salts=None) -> bytes:
-        """Host half of encode_to_curve for many inputs: two field elements per input (one for the NU variant), packed little-endian."""
-        salts = salts or [b""] * len(alpha_strings)
-        return _native.hash_to_field_batch(cls._suite_struct(), [bytes(s) + bytes(a) for a, s in zip(alpha_strings, salts)])
 
-    @classmethod
-    def encode_to_curve_from_field(cls, us: bytes):
-        """Device half: the maps (and for RO the sum of the two images) for packed field elements."""
-        return cls._mapped(us, cls._per_item()) if us else []
-
-    @classmethod
-    def encode_to_curve(cls, alpha_string: bytes, salt: bytes = b""):
-        return cls.encode_to_curve_batch([alpha_string], [salt])[0]
-
-    @classmethod
-    def encode_to_curve_batch(cls, alpha_strings, salts=None):
-        if not alpha_strings:
-            return []
-        # (a vanishing isogeny denominator comes back as DR_ERR_INVALID: a ValueError, as the reference's failing modular inverse is)
-        return unpack_points(cls, runtime.context().encode_to_curve_batch(cls._suite_struct(), list(alpha_strings), salts))
-
-
-class Bls12381G1Point(ShortWeierstrassA0Point):
+class Bls12381G1Point(_WideRfc9380, ShortWeierstrassA0Point):
     """Affine point of E(Fq): y^2 = x^3 + 4 over BLS12-381's 381-bit base field (dot_ring/curve/specs/bls12_381_G1.py), the identity is
     (None, None).  It has Secp256k1Point's surface (the host big-int additions are the shared a = 0 base class's) with 48-byte
     coordinates.  E(Fq) has order h r: a point need not lie in G1, so scalars are NEVER reduced mod r — `P * k` is exact for every
@@ -882,6 +918,7 @@ class Bls12381G1Point(ShortWeierstrassA0Point):
     _COFACTOR = 0x396C8C005555E1568C00AAAB0000AAAB       # #E(Fq) = _COFACTOR * _N
     _CV = _native.CURVE_BLS12_381_G1
     _SW_B = 4
+    _SUITE, _NO_IMAGE = "blsg1", "base is not invertible for the given modulus"     # pow(x_den, -1, p) of apply_isogeny
     __slots__ = ()
 
     # -- kernels: points cross as x || y, 48 + 48 bytes little-endian, 96 zero bytes the identity; scalars as they are
@@ -1003,41 +1040,21 @@ class Bls12381G1Point(ShortWeierstrassA0Point):
 
     # -- hash to curve (RFC 9380 BLS12381G1_XMD:SHA-256_SSWU_RO_ / _NU_): expand_message_xmd natively on the host, the map on the GPU
     @classmethod
-    def _per_item(cls) -> int:
-        return 1 if cls.curve.params.e2c == "sswu_nu" else 2
-
-    @classmethod
-    def encode_to_curve(cls, alpha_string: bytes, salt: bytes = b""):
-        return cls.encode_to_curve_batch([alpha_string], [salt])[0]
-
-    @classmethod
-    def _mapped(cls, us: bytes, per_item: int, clear: bool = True):
-        raw, ok = runtime.context().blsg1_map_to_curve(us, per_item, clear)
-        if 0 in ok:
-            raise ValueError("base is not invertible for the given modulus")      # pow(x_den, -1, p) of apply_isogeny
-        return cls._unpack(raw)
-
-    @classmethod
     def map_to_curve_simple_swu(cls, u: int):
         """one image on E, before the cofactor clearing (a point of E(Fq), in general outside G1)"""
         return cls._mapped((int(u) % cls._P).to_bytes(48, "little"), 1, clear=False)[0]
 
+    # -- what the module-level batch helpers ask a wide point type
     @classmethod
-    def hash_to_field_pairs(cls, alpha_strings, salts=None) -> bytes:
-        """Host half of encode_to_curve for many inputs: two 48-byte field elements per input (one for the NU variant), little-endian."""
-        salts = salts or [b""] * len(alpha_strings)
-        return _native.blsg1_hash_to_field_batch(cls._CV, [bytes(s) + bytes(a) for a, s in zip(alpha_strings, salts)])
+    def _scalar_mul_batch(cls, points, scalars):
+        pts, ks = cls._terms(points, scalars)
+        if len(pts) != len(points):              # a scalar of 2^256 or more became two terms: point by point
+            return [p * k for p, k in zip(points, scalars)]
+        return cls._unpack(runtime.context().blsg1_scalar_mul_batch(cls._pack(pts), b"".join(k.to_bytes(32, "little") for k in ks)))
 
     @classmethod
-    def encode_to_curve_from_field(cls, us: bytes):
-        """Device half: the maps, for RO the sum of the two images, and the multiplication by h_eff."""
-        return cls._mapped(us, cls._per_item()) if us else []
-
-    @classmethod
-    def encode_to_curve_batch(cls, alpha_strings, salts=None):
-        if not alpha_strings:
-            return []
-        return cls._unpack(runtime.context().blsg1_encode_to_curve_batch(cls._CV, list(alpha_strings), salts))
+    def _msm_groups(cls, points, scalars, m: int):
+        return [cls.msm(points[i : i + m], scalars[i : i + m]) for i in range(0, len(points), m)]
 
     @classmethod
     def _valid_points(cls, points) -> list[bool]:
@@ -1171,7 +1188,7 @@ class Fp2:
         return self.re, self.im
 
 
-class Bls12381G2Point:
+class Bls12381G2Point(_WideRfc9380):
     """Affine point of E(Fq2): y^2 = x^3 + 4 (1 + i) over BLS12-381's quadratic extension (dot_ring/curve/specs/bls12_381_G2.py), the
     identity is (None, None); coordinates are Fp2 values ((re, im) tuples are accepted).  E(Fq2) has order h2 r (762 bits): a point need
     not lie in G2, so scalars are never reduced mod r.  Single additions are host big-integer code; scalar multiplications and hashing to
@@ -1303,45 +1320,16 @@ class Bls12381G2Point:
         raise NotImplementedError("BLS12-381 G2 point deserialization is not implemented")
 
     # -- hash to curve (RFC 9380 BLS12381G2_XMD:SHA-256_SSWU_RO_ / _NU_): expand_message_xmd natively on the host, the map on the GPU
-    @classmethod
-    def _per_item(cls) -> int:
-        return 1 if cls.curve.params.e2c == "sswu_nu" else 2
-
-    @classmethod
-    def _mapped(cls, us: bytes, per_item: int, clear: bool = True):
-        raw, ok = runtime.context().blsg2_map_to_curve(us, per_item, clear)
-        if 0 in ok:                                # (no input reaches it: the isogeny's kernel has no point of E'(Fq2))
-            raise ValueError("base is not invertible for the given modulus")
-        return cls._unpack(raw)
+    # (no input reaches _NO_IMAGE: the isogeny's kernel has no point of E'(Fq2))
+    _SUITE, _NO_IMAGE = "blsg2", "base is not invertible for the given modulus"
 
     @classmethod
     def map_to_curve_simple_swu(cls, u):
         """one image on E, before the cofactor clearing (a point of E(Fq2), in general outside G2)"""
         return cls._mapped(cls._pack_fp2(cls._coord(u)), 1, clear=False)[0]
 
-    @classmethod
-    def hash_to_field_pairs(cls, alpha_strings, salts=None) -> bytes:
-        """Host half of encode_to_curve for many inputs: two 96-byte Fq2 elements per input (one for the NU variant), little-endian."""
-        salts = salts or [b""] * len(alpha_strings)
-        return _native.blsg2_hash_to_field_batch(cls._CV, [bytes(s) + bytes(a) for a, s in zip(alpha_strings, salts)])
 
-    @classmethod
-    def encode_to_curve_from_field(cls, us: bytes):
-        """Device half: the maps, for RO the sum of the two images, and the clearing."""
-        return cls._mapped(us, cls._per_item()) if us else []
-
-    @classmethod
-    def encode_to_curve(cls, alpha_string: bytes, salt: bytes = b""):
-        return cls.encode_to_curve_batch([alpha_string], [salt])[0]
-
-    @classmethod
-    def encode_to_curve_batch(cls, alpha_strings, salts=None):
-        if not alpha_strings:
-            return []
-        return cls._unpack(runtime.context().blsg2_encode_to_curve_batch(cls._CV, list(alpha_strings), salts))
-
-
-class P256SswuPoint(P256Point):
+class P256SswuPoint(_Rfc9380, P256Point):
     """Affine point of P256_RO / P256_NU (dot_ring/curve/specs/p256.py with E2C_Variant.SSWU / SSWU_NU): P-256's group and kernels under
     the variant's curve id, the reference's generic SEC1 codec in place of P256_TAI's (P256Point.point_to_string defers to
     SWAffinePoint's for these variants), and hashing to the curve by RFC 9380's simplified SWU map (k_p256_map_to_curve)."""
@@ -1387,10 +1375,6 @@ class P256SswuPoint(P256Point):
 
     # -- hash to curve (RFC 9380; sw_affine_point.py:428-533): expand_message_xmd natively on the host, the map on the GPU
     @classmethod
-    def _per_item(cls) -> int:
-        return 1 if cls.curve.params.e2c.endswith("_nu") else 2
-
-    @classmethod
     def _mapped(cls, us: bytes, per_item: int):
         raw, _ = runtime.context().p256_map_to_curve(us, per_item)          # (no denominator of this map can vanish)
         return unpack_points(cls, raw)
@@ -1399,19 +1383,12 @@ class P256SswuPoint(P256Point):
     def map_to_curve_simple_swu(cls, u: int):
         return cls._mapped((int(u) % cls._P).to_bytes(32, "little"), 1)[0]
 
-    hash_to_field_pairs = Secp256k1Point.__dict__["hash_to_field_pairs"]
-    encode_to_curve_from_field = Secp256k1Point.__dict__["encode_to_curve_from_field"]
 
-
-class Ed25519Ell2Point(BandersnatchPoint):
+class Ed25519Ell2Point(_Rfc9380, BandersnatchPoint):
     """Affine point of Ed25519_RO / Ed25519_NU (dot_ring/curve/specs/ed25519.py with E2C_Variant.ELL2 / ELL2_NU): Ed25519's group, kernels
     and codec under the variant's curve id, hashing to the curve by RFC 9380's Elligator 2 (k_ed25519_map_to_curve: the map onto
     curve25519, the reference's mont_to_ed25519, the sum of two images for RO, the cofactor cleared)."""
     __slots__ = ()
-
-    @classmethod
-    def _per_item(cls) -> int:
-        return 1 if cls.curve.params.e2c.endswith("_nu") else 2
 
     @classmethod
     def _mapped(cls, us: bytes, per_item: int):
@@ -1438,22 +1415,8 @@ class Ed25519Ell2Point(BandersnatchPoint):
         # pow raises ValueError where y = 0 or x = -1, as the reference does
         return cls(_sqrt_tonelli_shanks(-486664, p) * x % p * pow(y, -1, p) % p, (x - 1) * pow(x + 1, -1, p) % p)
 
-    hash_to_field_pairs = Secp256k1Point.__dict__["hash_to_field_pairs"]
-    encode_to_curve_from_field = Secp256k1Point.__dict__["encode_to_curve_from_field"]
 
-    @classmethod
-    def encode_to_curve(cls, alpha_string: bytes, salt: bytes = b""):
-        return cls.encode_to_curve_batch([alpha_string], [salt])[0]
-
-    @classmethod
-    def encode_to_curve_batch(cls, alpha_strings, salts=None):
-        if not alpha_strings:
-            return []
-        # (a message whose image has no value comes back as DR_ERR_INVALID: a ValueError, as the reference's failing modular inverse is)
-        return unpack_points(cls, runtime.context().encode_to_curve_batch(cls._suite_struct(), list(alpha_strings), salts))
-
-
-class Ed448Point(BandersnatchPoint):
+class Ed448Point(_WideRfc9380, BandersnatchPoint):
     """Affine point of Ed448_RO / Ed448_NU (dot_ring/curve/specs/ed448.py): x^2 + y^2 = 1 - 39081 x^2 y^2 over p = 2^448 - 2^224 - 1,
     cofactor 4, the identity (0, 1).  Coordinates and scalars are 56 bytes, so nothing here goes through the 64-byte entry points: scalar
     multiplications, MSMs, the subgroup check and hashing to the curve run on the dr_ed448_* kernels (kernels_ed448.hip.h), whose scalars
@@ -1464,6 +1427,7 @@ class Ed448Point(BandersnatchPoint):
     _A, _D, _H, _CV = 1, -39081, 4, _native.CURVE_ED448_RO
     _MG_A = 156326
     _WIDE = True                  # the VRF classes keep their Python orchestration: the native batch provers carry 32-byte scalars
+    _SUITE, _NO_IMAGE = "ed448", "Point is not on the curve"      # mont_to_ed448 with inv(0) = 0 gives (0, 0): u in {0, 1, p - 1}
     __slots__ = ()
 
     # -- the C ABI's forms
@@ -1513,44 +1477,20 @@ class Ed448Point(BandersnatchPoint):
 
     # -- hash to curve (RFC 9380 edwards448_XOF:SHAKE256_ELL2_RO_ / _NU_): expand_message_xof natively on the host, the map on the GPU
     @classmethod
-    def _per_item(cls) -> int:
-        return 1 if cls.curve.params.e2c.endswith("_nu") else 2
-
-    @classmethod
-    def _mapped(cls, us: bytes, per_item: int, clear: bool = True):
-        raw, ok = runtime.context().ed448_map_to_curve(us, per_item, clear)
-        if 0 in ok:
-            raise ValueError("Point is not on the curve")        # mont_to_ed448 with inv(0) = 0 gives (0, 0): u in {0, 1, p - 1}
-        return cls._unpack(raw)
-
-    @classmethod
     def map_to_curve(cls, u: int):
         """Ed448Point.map_to_curve (te_curve.py map_to_curve_ell2, then mont_to_ed448): ONE image with its cofactor not cleared"""
         return cls._mapped((int(u) % cls._P).to_bytes(56, "little"), 1, clear=False)[0]
 
+    # -- what the module-level batch helpers ask a wide point type
     @classmethod
-    def hash_to_field_pairs(cls, alpha_strings, salts=None) -> bytes:
-        """Host half of encode_to_curve for many inputs: _per_item() field elements per input, 56 little-endian bytes each."""
-        salts = salts or [b""] * len(alpha_strings)
-        return _native.ed448_hash_to_field_batch(cls.curve.params.curve_id, [bytes(s) + bytes(a) for a, s in zip(alpha_strings, salts)])
+    def _scalar_mul_batch(cls, points, scalars):
+        return cls._unpack(runtime.context().ed448_scalar_mul_batch(cls._pack(points), cls._scalars(scalars)))
 
     @classmethod
-    def encode_to_curve_from_field(cls, us: bytes):
-        """Device half: the maps, for RO the sum of the two images, and the cofactor, for packed canonical field elements."""
-        if not us:
-            return []
-        return cls._mapped(us, cls._per_item())
-
-    @classmethod
-    def encode_to_curve(cls, alpha_string: bytes, salt: bytes = b""):
-        return cls.encode_to_curve_batch([alpha_string], [salt])[0]
-
-    @classmethod
-    def encode_to_curve_batch(cls, alpha_strings, salts=None):
-        if not alpha_strings:
-            return []
-        # (a message whose image has no value comes back as DR_ERR_INVALID: a ValueError, as the reference's point constructor raises)
-        return cls._unpack(runtime.context().ed448_encode_to_curve_batch(cls.curve.params.curve_id, list(alpha_strings), salts))
+    def _msm_groups(cls, points, scalars, m: int):
+        if m > 64:                               # the kernel folds up to 64 terms in a wave: longer groups fold on the host (msm)
+            return [cls.msm(points[i : i + m], scalars[i : i + m]) for i in range(0, len(points), m)]
+        return cls._unpack(runtime.context().ed448_msm_groups(cls._pack(points), cls._scalars(scalars), m))
 
     @classmethod
     def _valid_points(cls, points) -> list[bool]:
@@ -1559,7 +1499,7 @@ class Ed448Point(BandersnatchPoint):
         return [bool(f) for f in ok]
 
 
-class Curve25519Point:
+class Curve25519Point(_Rfc9380):
     """Affine point of Curve25519_RO / Curve25519_NU (dot_ring/curve/specs/curve25519.py, montgomery/mg_affine_point.py):
     y^2 = x^3 + 486662 x^2 + x over 2^255 - 19 (x, y are the reference's names for u, v), cofactor 8, the identity is (None, None).
     (0, 0) is a point of the curve (order 2), so the identity cannot travel as 64 zero bytes: it packs as 64 bytes of 0xff for the generic
@@ -1685,10 +1625,6 @@ class Curve25519Point:
     _suite_struct = BandersnatchPoint.__dict__["_suite_struct"]
 
     @classmethod
-    def _per_item(cls) -> int:
-        return 1 if cls.curve.params.e2c.endswith("_nu") else 2
-
-    @classmethod
     def map_to_curve(cls, u: int):
         """MGAffinePoint.map_to_curve (mg_affine_point.py:289-346): ONE image with its cofactor not cleared, host big-int code as the
         other suites' map_to_curve is; the batched path (encode_to_curve_from_field) runs the same steps in the kernel"""
@@ -1705,24 +1641,9 @@ class Curve25519Point:
             y = -y % p
         return cls(x, y)
 
-    hash_to_field_pairs = Secp256k1Point.__dict__["hash_to_field_pairs"]
-
     @classmethod
-    def encode_to_curve_from_field(cls, us: bytes):
-        """Device half: the maps, for RO the sum of the two images, and the cofactor, for packed canonical field elements."""
-        if not us:
-            return []
-        return unpack_points_flagged(cls, *runtime.context().curve25519_map_to_curve(us, cls._per_item()))
-
-    @classmethod
-    def encode_to_curve(cls, alpha_string: bytes, salt: bytes = b""):
-        return cls.encode_to_curve_batch([alpha_string], [salt])[0]
-
-    @classmethod
-    def encode_to_curve_batch(cls, alpha_strings, salts=None):
-        if not alpha_strings:
-            return []
-        return unpack_points(cls, runtime.context().encode_to_curve_batch(cls._suite_struct(), list(alpha_strings), salts))
+    def _mapped(cls, us: bytes, per_item: int):
+        return unpack_points_flagged(cls, *runtime.context().curve25519_map_to_curve(us, per_item))
 
 
 # ------------------------------------------------------------------ batched helpers over the C ABI
@@ -1764,13 +1685,8 @@ def scalar_mul_batch(points, scalars):
     if not points:
         return []
     cls = type(points[0])
-    if issubclass(cls, Bls12381G1Point):         # 48-byte coordinates and unreduced scalars: its own entry point
-        pts, ks = cls._terms(points, scalars)
-        if len(pts) != len(points):              # a scalar of 2^256 or more became two terms: point by point
-            return [p * k for p, k in zip(points, scalars)]
-        return cls._unpack(runtime.context().blsg1_scalar_mul_batch(cls._pack(pts), b"".join(k.to_bytes(32, "little") for k in ks)))
-    if issubclass(cls, Ed448Point):              # 56-byte coordinates and scalars: its own entry point
-        return cls._unpack(runtime.context().ed448_scalar_mul_batch(cls._pack(points), cls._scalars(scalars)))
+    if hasattr(cls, "_scalar_mul_batch"):        # a wide point type (other coordinate and scalar widths): its own entry point
+        return cls._scalar_mul_batch(points, scalars)
     first = points[0]
     if all(p is first for p in points) and (first.x, first.y) in _fixed_bases(cls):
         # k_i * G (key derivation, curve.py:384) or k_i * B: the constant's fixed-base window table — 64 table additions
@@ -1793,22 +1709,16 @@ def msm_groups(points, scalars, m: int):
     if not points:
         return []
     cls = type(points[0])
-    if issubclass(cls, Bls12381G1Point):
-        return [cls.msm(points[i : i + m], scalars[i : i + m]) for i in range(0, len(points), m)]
-    if issubclass(cls, Ed448Point):
-        if m > 64:                               # the kernel folds up to 64 terms in a wave: longer groups fold on the host (msm)
-            return [cls.msm(points[i : i + m], scalars[i : i + m]) for i in range(0, len(points), m)]
-        return cls._unpack(runtime.context().ed448_msm_groups(cls._pack(points), cls._scalars(scalars), m))
+    if hasattr(cls, "_msm_groups"):
+        return cls._msm_groups(points, scalars, m)
     raw = runtime.context().bsn_msm_groups(pack_points(points), pack_scalars(scalars, cls._N), m, cls._CV)
     return unpack_points(cls, raw)
 
 
 def valid_points(points) -> list[bool]:
     """curve.py:56 for a whole batch: [h]P != O and [h^-1 mod n][h]P == P (h the cofactor), one launch for all points."""
-    if points and isinstance(points[0], Bls12381G1Point):      # E(Fq) is not h x (prime) for a small h: the decoder's r P = O
-        return type(points[0])._valid_points(points)
-    if points and isinstance(points[0], Ed448Point):           # one launch: the decoder's n P = O
-        return type(points[0])._valid_points(points)
+    if points and hasattr(type(points[0]), "_valid_points"):   # a wide point type: one launch of its decoder's subgroup check (on G1,
+        return type(points[0])._valid_points(points)            # where E(Fq) is not h x (prime) for a small h, the only sound one)
     live = [i for i, p in enumerate(points) if not p.is_identity() and p.is_on_curve()]
     out = [False] * len(points)
     if not live:

@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
-"""Wall time of one `encode_to_curve_batch` call at 4096 messages for Ed448_RO and, in the same process, for Ed25519_RO (the same map
-one field down: the yardstick DESIGN.md 8m quotes).  `python3 tools/ed448_encode_timing.py [count]`.
+"""Wall time of one `encode_to_curve_batch` call at 4096 messages for a suite and, in the same process, for its yardstick: the suite
+DESIGN.md compares it with.  `python3 tools/encode_timing.py SUITE YARDSTICK [count]`, the names as dot_ring_amd exports them:
+  BLS12_381_G1_RO Secp256k1_RO      the only other SSWU-with-isogeny suite
+  BLS12_381_G2_RO BLS12_381_G1_RO   the same field, chain and law one level down
+  Ed448_RO Ed25519_RO               the same map one field down
 Each figure is ONE call after one warm-up call of the same size — unrepeated, to be quoted as such."""
 import os
 import sys
@@ -11,9 +14,11 @@ import dot_ring_amd as d  # noqa: E402
 
 
 def main():
-    count = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
+    if len(sys.argv) < 3:
+        sys.exit(__doc__)
+    count = int(sys.argv[3]) if len(sys.argv) > 3 else 4096
     msgs = [b"message %d" % i for i in range(count)]
-    for cv in (d.Ed448_RO, d.Ed25519_RO):
+    for cv in (getattr(d, sys.argv[1]), getattr(d, sys.argv[2])):
         cv.point_type.encode_to_curve_batch(msgs)                      # warm-up: buffers, code object
         t0 = time.perf_counter()
         out = cv.point_type.encode_to_curve_batch(msgs)
