@@ -223,13 +223,104 @@ class BandersnatchCurve:
         return bool(valid_points([point])[0])
 
 
-class BandersnatchPoint:
-    """Affine twisted Edwards point; `curve` and the coefficient shortcuts are bound per suite by the subclasses below
-    (the class keeps its Bandersnatch name: that is what the reference's callers import)."""
+class _AffinePoint:
+    """Root of every point type: two coordinates and what no curve form changes.  A family below it (twisted Edwards, short
+    Weierstrass, Montgomery, E(Fq2)) gives __init__, _on_curve, _trusted, __eq__ with __hash__, __add__ and __neg__; a concrete class
+    gives `curve`, _N, _H, _CV, its codec and whatever runs on kernels of its own.  The identity is (None, None) unless a family says
+    otherwise."""
     curve: BandersnatchCurve
+    _WIDE = False                     # coordinates or scalars wider than the 64-byte entry points': the class brings its own hooks
+    _IDENTITY_BYTES = bytes(64)       # how pack_points sends an identity whose coordinates are None
+    __slots__ = ("x", "y")
+
+    def __repr__(self):
+        return f"{type(self).__name__}({self.x}, {self.y})"
+
+    @classmethod
+    def identity(cls):
+        return cls(None, None)
+
+    @classmethod
+    def generator_point(cls):
+        return cls(*cls.curve.params.generator)
+
+    def is_identity(self) -> bool:
+        return self.x is None and self.y is None
+
+    def is_on_curve(self) -> bool:
+        return self.is_identity() or self._on_curve(self.x, self.y)
+
+    def __sub__(self, other):
+        return self + (-other)
+
+    # -- scalar multiplication / MSM on the GPU
+    def __mul__(self, scalar: int):
+        return scalar_mul_batch([self], [scalar])[0]
+
+    __rmul__ = __mul__
+
+    @classmethod
+    def msm(cls, points, scalars):
+        if len(points) != len(scalars):
+            raise ValueError("Points and scalars must have same length")
+        if not points:
+            return cls.identity()
+        raw = runtime.context().bsn_msm(pack_points(points), pack_scalars(scalars, cls._N), cls._CV)
+        return cls._trusted(int.from_bytes(raw[:32], "little"), int.from_bytes(raw[32:], "little"))
+
+    @classmethod
+    def _suite_struct(cls):
+        """dr_vrf_suite of this point type's suite (cached on the class)."""
+        st = cls.__dict__.get("_suite_cache")
+        if st is None:
+            sp = cls.curve.params
+            le = lambda pt: pt[0].to_bytes(32, "little") + pt[1].to_bytes(32, "little")  # noqa: E731
+            st = _native.vrf_suite(sp.suite_id, sp.hash_fn, le(sp.generator), le(sp.auxiliary_points.blinding_base), sp.curve_id)
+            cls._suite_cache = st
+        return st
+
+    # -- what the module-level batch helpers ask a point type: here over the 64-byte entry points, a wide type has its own
+    @classmethod
+    def _scalar_mul_batch(cls, points, scalars):
+        first = points[0]
+        if all(p is first for p in points) and (first.x, first.y) in _fixed_bases(cls):
+            # k_i * G (key derivation, curve.py:384) or k_i * B: the constant's fixed-base window table — 64 table additions
+            # over four lanes instead of ~250 dependent doublings (dr_te_fixed_base_msm_groups)
+            raw = runtime.context().te_fixed_base_msm_groups(pack_points([first]), pack_scalars(scalars, cls._N), cls._CV)
+            return unpack_points(cls, raw)
+        raw = runtime.context().bsn_scalar_mul_batch(pack_points(points), pack_scalars(scalars, cls._N), cls._CV)
+        return unpack_points(cls, raw)
+
+    @classmethod
+    def _msm_groups(cls, points, scalars, m: int):
+        raw = runtime.context().bsn_msm_groups(pack_points(points), pack_scalars(scalars, cls._N), m, cls._CV)
+        return unpack_points(cls, raw)
+
+    @classmethod
+    def _valid_points(cls, points) -> list[bool]:
+        """[h]P != O and [h^-1 mod n][h]P == P (h the cofactor), one launch for all points"""
+        live = [i for i, p in enumerate(points) if not p.is_identity() and p.is_on_curve()]
+        out = [False] * len(points)
+        if not live:
+            return out
+        h, order = type(points[live[0]])._H, type(points[live[0]])._N
+        if h == 1:                               # prime order (P-256, secp256k1): on the curve and not the identity (curve.py:61)
+            for i in live:
+                out[i] = True
+            return out
+        cleared = scalar_mul_batch_raw([points[i] for i in live], [h] * len(live))
+        back = scalar_mul_batch([c for c in cleared], [pow(h, -1, order)] * len(live))
+        for i, c, b in zip(live, cleared, back):
+            out[i] = (not c.is_identity()) and b == points[i]
+        return out
+
+
+class BandersnatchPoint(_AffinePoint):
+    """Affine twisted Edwards point, the identity (0, 1); `curve` and the coefficient shortcuts are bound per suite by the subclasses
+    below (the class keeps its Bandersnatch name: that is what the reference's callers import)."""
     _A, _D, _N, _H, _CV = _A, _D, _N, 4, _native.CURVE_BANDERSNATCH
     _P = _P                       # the suite's base field (Ed25519's differs)
-    __slots__ = ("x", "y")
+    __slots__ = ()
 
     def __init__(self, x: int, y: int):
         self.x, self.y = x, y
@@ -259,22 +350,12 @@ class BandersnatchPoint:
     def __hash__(self):
         return (self.x + self.y) % self._N
 
-    def __repr__(self):
-        return f"{type(self).__name__}({self.x}, {self.y})"
-
     @classmethod
     def identity(cls):
         return cls(0, 1)
 
-    @classmethod
-    def generator_point(cls):
-        return cls(*cls.curve.params.generator)
-
     def is_identity(self) -> bool:
         return self.x == 0 and self.y == 1
-
-    def is_on_curve(self) -> bool:
-        return self._on_curve(self.x, self.y)
 
     # -- group law: single additions are host big-int code, as in te_affine_point.py:69-167
     def __add__(self, other):
@@ -303,23 +384,10 @@ class BandersnatchPoint:
     def __neg__(self):
         return type(self)(-self.x % self._P, self.y)
 
-    def __sub__(self, other):
-        return self + (-other)
-
-    # -- scalar multiplication / MSM on the GPU
-    def __mul__(self, scalar: int):
-        return scalar_mul_batch([self], [scalar])[0]
-
-    __rmul__ = __mul__
-
     @classmethod
     def msm(cls, points, scalars):
-        if len(points) != len(scalars):
-            raise ValueError("Points and scalars must have same length")
-        if not points:
-            return cls.identity()
-        raw = runtime.context().bsn_msm(pack_points(points), pack_scalars(scalars, cls._N), cls._CV)
-        return cls(int.from_bytes(raw[:32], "little"), int.from_bytes(raw[32:], "little"))
+        s = super().msm(points, scalars)
+        return cls(s.x, s.y)             # (through the checking constructor, as the reference's)
 
     # -- codec (point.py:150-214)
     def point_to_string(self) -> bytes:
@@ -349,17 +417,6 @@ class BandersnatchPoint:
         return cls(hi if sign else lo, y)
 
     # -- hash to curve (te_affine_point.py:212-295, te_curve.py:48-95)
-    @classmethod
-    def _suite_struct(cls):
-        """dr_vrf_suite of this point type's suite (cached on the class)."""
-        st = cls.__dict__.get("_suite_cache")
-        if st is None:
-            sp = cls.curve.params
-            le = lambda pt: pt[0].to_bytes(32, "little") + pt[1].to_bytes(32, "little")  # noqa: E731
-            st = _native.vrf_suite(sp.suite_id, sp.hash_fn, le(sp.generator), le(sp.auxiliary_points.blinding_base), sp.curve_id)
-            cls._suite_cache = st
-        return st
-
     @classmethod
     def encode_to_curve(cls, alpha_string: bytes, salt: bytes = b""):
         if cls.curve.params.e2c == "tai":          # point.py:252-296, through the batch entry point (hashing native, sqrt on the GPU)
@@ -416,28 +473,25 @@ class BandersnatchPoint:
         return cls(v, 1 if tv2 == 0 else w)
 
 
-class BandersnatchSWPoint:
-    """Affine short Weierstrass point of Bandersnatch_SW (dot_ring/curve/specs/bandersnatch_sw.py, short_weierstrass/sw_affine_point.py):
-    y^2 = x^3 + a x + b, the identity is (None, None).  Single additions are host big-int code; scalar multiplications, MSMs, decoding
-    and hash-to-curve run on the GPU under DR_CURVE_BANDERSNATCH_SW, whose kernels map to and from the twisted Edwards image."""
-    curve: BandersnatchCurve
-    _N, _H, _CV = _N, 4, _native.CURVE_BANDERSNATCH_SW
-    _SW_A = 10773120815616481058602537765553212789256758185246796157495669123169359657269
-    _SW_B = 29569587568322301171008055308580903175558631321415017492731745847794083609535
-    __slots__ = ("x", "y")
+class _ShortWeierstrassPoint(_AffinePoint):
+    """Affine point of y^2 = x^3 + a x + b over the integers mod _P (short_weierstrass/sw_affine_point.py), the identity (None, None):
+    the constructor's checks, equality and the host big-int group law.  A subclass gives _P, _SW_A, _SW_B, _N, _H, its codec and
+    whatever runs on its own kernels.  Points of different curves — different (p, a, b) — neither compare equal nor add; the
+    variants of one curve do both."""
+    __slots__ = ()
 
     def __init__(self, x, y):
         self.x, self.y = x, y
         if x is None and y is None:
             return
-        if x is None or y is None or not (0 <= x < _P and 0 <= y < _P):
+        if x is None or y is None or not (0 <= x < self._P and 0 <= y < self._P):
             raise ValueError("Invalid point coordinates")
         if not self._on_curve(x, y):
             raise ValueError("Point is not on the curve")
 
     @classmethod
     def _on_curve(cls, x: int, y: int) -> bool:
-        return (y * y - (x * x * x + cls._SW_A * x + cls._SW_B)) % _P == 0
+        return (y * y - (x * x * x + cls._SW_A * x + cls._SW_B)) % cls._P == 0
 
     @classmethod
     def _trusted(cls, x: int, y: int):
@@ -446,72 +500,129 @@ class BandersnatchSWPoint:
         pt.x, pt.y = (None, None) if x == 0 and y == 0 else (x, y)
         return pt
 
+    def _same_curve(self, other) -> bool:
+        return type(other) is type(self) or (isinstance(other, _ShortWeierstrassPoint) and self._P == other._P
+                                             and self._SW_A == other._SW_A and self._SW_B == other._SW_B)
+
     def __eq__(self, other):
-        return isinstance(other, BandersnatchSWPoint) and self.x == other.x and self.y == other.y
+        return self._same_curve(other) and self.x == other.x and self.y == other.y
 
     def __hash__(self):
         return 0 if self.x is None else (self.x + self.y) % self._N
 
-    def __repr__(self):
-        return f"{type(self).__name__}({self.x}, {self.y})"
-
-    @classmethod
-    def identity(cls):
-        return cls(None, None)
-
-    @classmethod
-    def generator_point(cls):
-        return cls(*cls.curve.params.generator)
-
-    def is_identity(self) -> bool:
-        return self.x is None and self.y is None
-
-    def is_on_curve(self) -> bool:
-        return self.is_identity() or self._on_curve(self.x, self.y)
-
     # -- group law (sw_affine_point.py)
     def __add__(self, other):
-        if not isinstance(other, BandersnatchSWPoint):
+        if not self._same_curve(other):
             raise TypeError("Can only add SWAffinePoint instances")
         if self.is_identity():
             return other
         if other.is_identity():
             return self
+        p = self._P
         if self.x == other.x:
             return self.double() if self.y == other.y else self.identity()
-        lam = (other.y - self.y) * pow(other.x - self.x, -1, _P) % _P
-        x3 = (lam * lam - self.x - other.x) % _P
-        return type(self)(x3, (lam * (self.x - x3) - self.y) % _P)
+        lam = (other.y - self.y) * pow(other.x - self.x, -1, p) % p
+        x3 = (lam * lam - self.x - other.x) % p
+        return type(self)(x3, (lam * (self.x - x3) - self.y) % p)
 
     def double(self):
         if self.is_identity() or self.y == 0:
             return self.identity()
-        lam = (3 * self.x * self.x + self._SW_A) * pow(2 * self.y, -1, _P) % _P
-        x3 = (lam * lam - 2 * self.x) % _P
-        return type(self)(x3, (lam * (self.x - x3) - self.y) % _P)
+        p = self._P
+        lam = (3 * self.x * self.x + self._SW_A) * pow(2 * self.y, -1, p) % p
+        x3 = (lam * lam - 2 * self.x) % p
+        return type(self)(x3, (lam * (self.x - x3) - self.y) % p)
 
     def __neg__(self):
-        return self if self.is_identity() else type(self)(self.x, -self.y % _P)
-
-    def __sub__(self, other):
-        return self + (-other)
-
-    def __mul__(self, scalar: int):
-        return scalar_mul_batch([self], [scalar])[0]
-
-    __rmul__ = __mul__
-
-    @classmethod
-    def msm(cls, points, scalars):
-        if len(points) != len(scalars):
-            raise ValueError("Points and scalars must have same length")
-        if not points:
-            return cls.identity()
-        raw = runtime.context().bsn_msm(pack_points(points), pack_scalars(scalars, cls._N), cls._CV)
-        return cls._trusted(int.from_bytes(raw[:32], "little"), int.from_bytes(raw[32:], "little"))
+        return self if self.is_identity() else type(self)(self.x, -self.y % self._P)
 
     def clear_cofactor(self):
-        return scalar_mul_batch_raw([self], [self._H])[0]
+        return scalar_mul_batch_raw([self], [self._H])[0]          # host doublings: none, and self, where the cofactor is 1
+
+    # -- hash to curve: try-and-increment (point.py:252-296), candidates hashed natively, decoded and cofactor-cleared on the GPU; an
+    # RFC 9380 suite puts its mixin in front
+    @classmethod
+    def encode_to_curve(cls, alpha_string: bytes, salt: bytes = b""):
+        return cls.encode_to_curve_batch([alpha_string], [salt])[0]
+
+    @classmethod
+    def encode_to_curve_batch(cls, alpha_strings, salts=None):
+        if not alpha_strings:
+            return []
+        return unpack_points(cls, runtime.context().encode_to_curve_batch(cls._suite_struct(), list(alpha_strings), salts))
+
+
+class _Sec1Codec:
+    """The SEC1 strings of a short Weierstrass point type (sw_affine_point.py point_to_string / string_to_point): 0x00 the identity,
+    0x02 / 0x03 compressed, 0x04 uncompressed and, where the class sets _SEC1_HYBRID, 0x06 / 0x07 (both coordinates and the parity of
+    y).  Coordinates are _SEC1_LEN big-endian bytes; _sec1_decompress turns a compressed (prefix, x < p) into a point."""
+    __slots__ = ()
+    _SEC1_LEN = 32
+    _SEC1_HYBRID = False
+
+    def point_to_string(self, compressed: bool = True) -> bytes:
+        if self.is_identity():
+            return b"\x00"
+        x = self.x.to_bytes(self._SEC1_LEN, "big")
+        if compressed:
+            return (b"\x03" if self.y % 2 else b"\x02") + x
+        return b"\x04" + x + self.y.to_bytes(self._SEC1_LEN, "big")
+
+    @classmethod
+    def _sec1_decompress(cls, prefix: int, x: int):
+        """a host square root, the root of the prefix's parity"""
+        p = cls._P
+        try:
+            y = cls.curve.mod_sqrt((x * x * x + cls._SW_A * x + cls._SW_B) % p)
+        except ValueError:
+            raise ValueError("Invalid point encoding") from None
+        return cls(x, y if y % 2 == prefix % 2 else p - y)
+
+    @classmethod
+    def string_to_point(cls, data):
+        if isinstance(data, str):
+            data = bytes.fromhex(data)
+        data = bytes(data)
+        if len(data) == 0:
+            raise ValueError("Empty octet string")
+        prefix, p, n = data[0], cls._P, cls._SEC1_LEN
+        if prefix == 0x00:
+            if len(data) != 1:
+                raise ValueError("Point at infinity must be single byte 0x00")
+            return cls.identity()
+        if prefix in (0x02, 0x03):
+            if len(data) != n + 1:
+                raise ValueError(f"Invalid compressed point length: expected {n + 1}, got {len(data)}")
+            x = int.from_bytes(data[1:], "big")
+            if x >= p:
+                raise ValueError(f"x-coordinate {x} is not in field Fp (p={p})")
+            return cls._sec1_decompress(prefix, x)
+        if prefix == 0x04 or (cls._SEC1_HYBRID and prefix in (0x06, 0x07)):
+            if len(data) != 2 * n + 1:
+                kind = "uncompressed" if prefix == 0x04 else "hybrid"
+                raise ValueError(f"Invalid {kind} point length: expected {2 * n + 1}, got {len(data)}")
+            x, y = int.from_bytes(data[1 : n + 1], "big"), int.from_bytes(data[n + 1 :], "big")
+            if x >= p:
+                raise ValueError(f"x-coordinate {x} is not in field Fp (p={p})")
+            if y >= p:
+                raise ValueError(f"y-coordinate {y} is not in field Fp (p={p})")
+            if prefix != 0x04 and y % 2 != prefix % 2:
+                raise ValueError("Hybrid format: y parity doesn't match prefix")
+            if not cls._on_curve(x, y):
+                raise ValueError(f"Point ({x}, {y}) is not on curve")
+            return cls(x, y)
+        raise ValueError(f"Invalid point encoding prefix: 0x{prefix:02x}")
+
+
+class BandersnatchSWPoint(_ShortWeierstrassPoint):
+    """Affine short Weierstrass point of Bandersnatch_SW (dot_ring/curve/specs/bandersnatch_sw.py) over the module's field.  Scalar
+    multiplications, MSMs, decoding and hash-to-curve run on the GPU under DR_CURVE_BANDERSNATCH_SW, whose kernels map to and from the
+    twisted Edwards image."""
+    _P = _P
+    _N, _H, _CV = _N, 4, _native.CURVE_BANDERSNATCH_SW
+    _SW_A = 10773120815616481058602537765553212789256758185246796157495669123169359657269
+    _SW_B = 29569587568322301171008055308580903175558631321415017492731745847794083609535
+    __slots__ = ()
 
     # -- codec (bandersnatch_sw.py: point_to_string / string_to_point): x little-endian, then a flag byte
     def point_to_string(self) -> bytes:
@@ -545,120 +656,16 @@ class BandersnatchSWPoint:
         except ValueError:
             raise ValueError("Invalid point") from None
 
-    # -- hash to curve: try-and-increment (point.py:252-296), candidates hashed natively, decoded and cofactor-cleared on the GPU
-    _suite_struct = BandersnatchPoint.__dict__["_suite_struct"]
 
-    @classmethod
-    def encode_to_curve(cls, alpha_string: bytes, salt: bytes = b""):
-        return cls.encode_to_curve_batch([alpha_string], [salt])[0]
-
-    @classmethod
-    def encode_to_curve_batch(cls, alpha_strings, salts=None):
-        if not alpha_strings:
-            return []
-        return unpack_points(cls, runtime.context().encode_to_curve_batch(cls._suite_struct(), list(alpha_strings), salts))
-
-
-class P256Point:
-    """Affine point of P-256 (dot_ring/curve/specs/p256.py, P256_TAI): y^2 = x^3 - 3 x + b over its own field, cofactor 1, the identity
-    is (None, None).  Single additions are host big-int code; scalar multiplications, MSMs, decoding and hash-to-curve run on the GPU
-    under DR_CURVE_P256 (kernels_p256.hip.h)."""
-    curve: BandersnatchCurve
+class P256Point(_ShortWeierstrassPoint):
+    """Affine point of P-256 (dot_ring/curve/specs/p256.py, P256_TAI): y^2 = x^3 - 3 x + b over its own field, cofactor 1.  Scalar
+    multiplications, MSMs, decoding and hash-to-curve run on the GPU under DR_CURVE_P256 (kernels_p256.hip.h)."""
     _P = 0xFFFFFFFF00000001000000000000000000000000FFFFFFFFFFFFFFFFFFFFFFFF
     _N = 0xFFFFFFFF00000000FFFFFFFFFFFFFFFFBCE6FAADA7179E84F3B9CAC2FC632551
     _H, _CV = 1, _native.CURVE_P256
     _SW_A = -3
     _SW_B = 0x5AC635D8AA3A93E7B3EBBD55769886BC651D06B0CC53B0F63BCE3C3E27D2604B
-    __slots__ = ("x", "y")
-
-    def __init__(self, x, y):
-        self.x, self.y = x, y
-        if x is None and y is None:
-            return
-        if x is None or y is None or not (0 <= x < self._P and 0 <= y < self._P):
-            raise ValueError("Invalid point coordinates")
-        if not self._on_curve(x, y):
-            raise ValueError("Point is not on the curve")
-
-    @classmethod
-    def _on_curve(cls, x: int, y: int) -> bool:
-        return (y * y - (x * x * x + cls._SW_A * x + cls._SW_B)) % cls._P == 0
-
-    @classmethod
-    def _trusted(cls, x: int, y: int):
-        """Kernel outputs: 64 zero bytes are the identity."""
-        pt = object.__new__(cls)
-        pt.x, pt.y = (None, None) if x == 0 and y == 0 else (x, y)
-        return pt
-
-    def __eq__(self, other):
-        return isinstance(other, P256Point) and self.x == other.x and self.y == other.y
-
-    def __hash__(self):
-        return 0 if self.x is None else (self.x + self.y) % self._N
-
-    def __repr__(self):
-        return f"{type(self).__name__}({self.x}, {self.y})"
-
-    @classmethod
-    def identity(cls):
-        return cls(None, None)
-
-    @classmethod
-    def generator_point(cls):
-        return cls(*cls.curve.params.generator)
-
-    def is_identity(self) -> bool:
-        return self.x is None and self.y is None
-
-    def is_on_curve(self) -> bool:
-        return self.is_identity() or self._on_curve(self.x, self.y)
-
-    # -- group law (sw_affine_point.py)
-    def __add__(self, other):
-        if not isinstance(other, P256Point):
-            raise TypeError("Can only add SWAffinePoint instances")
-        if self.is_identity():
-            return other
-        if other.is_identity():
-            return self
-        p = self._P
-        if self.x == other.x:
-            return self.double() if self.y == other.y else self.identity()
-        lam = (other.y - self.y) * pow(other.x - self.x, -1, p) % p
-        x3 = (lam * lam - self.x - other.x) % p
-        return type(self)(x3, (lam * (self.x - x3) - self.y) % p)
-
-    def double(self):
-        if self.is_identity() or self.y == 0:
-            return self.identity()
-        p = self._P
-        lam = (3 * self.x * self.x + self._SW_A) * pow(2 * self.y, -1, p) % p
-        x3 = (lam * lam - 2 * self.x) % p
-        return type(self)(x3, (lam * (self.x - x3) - self.y) % p)
-
-    def __neg__(self):
-        return self if self.is_identity() else type(self)(self.x, -self.y % self._P)
-
-    def __sub__(self, other):
-        return self + (-other)
-
-    def __mul__(self, scalar: int):
-        return scalar_mul_batch([self], [scalar])[0]
-
-    __rmul__ = __mul__
-
-    @classmethod
-    def msm(cls, points, scalars):
-        if len(points) != len(scalars):
-            raise ValueError("Points and scalars must have same length")
-        if not points:
-            return cls.identity()
-        raw = runtime.context().bsn_msm(pack_points(points), pack_scalars(scalars, cls._N), cls._CV)
-        return cls._trusted(int.from_bytes(raw[:32], "little"), int.from_bytes(raw[32:], "little"))
-
-    def clear_cofactor(self):
-        return self
+    __slots__ = ()
 
     # -- codec (p256.py point_to_string / string_to_point / _string_to_canonical_point)
     def point_to_string(self) -> bytes:
@@ -721,179 +728,25 @@ class P256Point:
             raise ValueError(f"Invalid compressed point length: expected 33, got {len(data)}")
         return cls._string_to_canonical_point(data)
 
-    # -- hash to curve: try-and-increment (point.py:252-296), candidates hashed natively, decoded on the GPU
-    _suite_struct = BandersnatchPoint.__dict__["_suite_struct"]
 
-    @classmethod
-    def encode_to_curve(cls, alpha_string: bytes, salt: bytes = b""):
-        return cls.encode_to_curve_batch([alpha_string], [salt])[0]
-
-    @classmethod
-    def encode_to_curve_batch(cls, alpha_strings, salts=None):
-        if not alpha_strings:
-            return []
-        return unpack_points(cls, runtime.context().encode_to_curve_batch(cls._suite_struct(), list(alpha_strings), salts))
-
-
-class ShortWeierstrassA0Point:
-    """Affine point of a curve y^2 = x^3 + b (a = 0) over a prime field, the identity (None, None): the coordinates, equality and the
-    host big-int group law (sw_affine_point.py) that secp256k1 and BLS12-381's E(Fq) share.  A subclass gives _P, _N, _SW_B and
-    everything that runs on its own kernels.  Points of different curves neither compare equal nor add."""
-    curve: BandersnatchCurve
+class ShortWeierstrassA0Point(_ShortWeierstrassPoint):
+    """y^2 = x^3 + b: secp256k1 and BLS12-381's E(Fq)"""
     _SW_A = 0
-    __slots__ = ("x", "y")
-
-    def __init__(self, x, y):
-        self.x, self.y = x, y
-        if x is None and y is None:
-            return
-        if x is None or y is None or not (0 <= x < self._P and 0 <= y < self._P):
-            raise ValueError("Invalid point coordinates")
-        if not self._on_curve(x, y):
-            raise ValueError("Point is not on the curve")
-
-    @classmethod
-    def _on_curve(cls, x: int, y: int) -> bool:
-        return (y * y - (x * x * x + cls._SW_B)) % cls._P == 0
-
-    @classmethod
-    def _trusted(cls, x: int, y: int):
-        """Kernel outputs: 64 zero bytes are the identity."""
-        pt = object.__new__(cls)
-        pt.x, pt.y = (None, None) if x == 0 and y == 0 else (x, y)
-        return pt
-
-    def __eq__(self, other):
-        return isinstance(other, ShortWeierstrassA0Point) and self._P == other._P and self.x == other.x and self.y == other.y
-
-    def __hash__(self):
-        return 0 if self.x is None else (self.x + self.y) % self._N
-
-    def __repr__(self):
-        return f"{type(self).__name__}({self.x}, {self.y})"
-
-    @classmethod
-    def identity(cls):
-        return cls(None, None)
-
-    @classmethod
-    def generator_point(cls):
-        return cls(*cls.curve.params.generator)
-
-    def is_identity(self) -> bool:
-        return self.x is None and self.y is None
-
-    def is_on_curve(self) -> bool:
-        return self.is_identity() or self._on_curve(self.x, self.y)
-
-    # -- group law (sw_affine_point.py)
-    def __add__(self, other):
-        if not isinstance(other, ShortWeierstrassA0Point) or other._P != self._P:
-            raise TypeError("Can only add SWAffinePoint instances")
-        if self.is_identity():
-            return other
-        if other.is_identity():
-            return self
-        p = self._P
-        if self.x == other.x:
-            return self.double() if self.y == other.y else self.identity()
-        lam = (other.y - self.y) * pow(other.x - self.x, -1, p) % p
-        x3 = (lam * lam - self.x - other.x) % p
-        return type(self)(x3, (lam * (self.x - x3) - self.y) % p)
-
-    def double(self):
-        if self.is_identity() or self.y == 0:
-            return self.identity()
-        p = self._P
-        lam = 3 * self.x * self.x * pow(2 * self.y, -1, p) % p
-        x3 = (lam * lam - 2 * self.x) % p
-        return type(self)(x3, (lam * (self.x - x3) - self.y) % p)
-
-    def __neg__(self):
-        return self if self.is_identity() else type(self)(self.x, -self.y % self._P)
-
-    def __sub__(self, other):
-        return self + (-other)
+    __slots__ = ()
 
 
-class Secp256k1Point(_Rfc9380, ShortWeierstrassA0Point):
-    """Affine point of secp256k1 (dot_ring/curve/specs/secp256k1.py): y^2 = x^3 + 7 over its own field, cofactor 1, the identity is
-    (None, None).  Single additions are host big-int code; scalar multiplications, MSMs, decoding and hashing to the curve (RFC 9380:
-    simplified SWU and the 3-isogeny) run on the GPU under the suite's curve id (kernels_secp256k1.hip.h)."""
+class Secp256k1Point(_Rfc9380, _Sec1Codec, ShortWeierstrassA0Point):
+    """Affine point of secp256k1 (dot_ring/curve/specs/secp256k1.py): y^2 = x^3 + 7 over its own field, cofactor 1, SEC1 strings.
+    Scalar multiplications (secp256k1.py:85-93: the scalar reduced mod n, a negative one through -P, 0 gives the identity), MSMs,
+    decoding and hashing to the curve (RFC 9380: simplified SWU and the 3-isogeny) run on the GPU under the suite's curve id
+    (kernels_secp256k1.hip.h)."""
     _P = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEFFFFFC2F
     _N = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141
     _H, _CV = 1, _native.CURVE_SECP256K1
     _SW_B = 7
     __slots__ = ()
 
-    def __mul__(self, scalar: int):
-        """secp256k1.py:85-93: the scalar reduced mod n (a negative one through -P), 0 gives the identity"""
-        return scalar_mul_batch([self], [scalar])[0]
-
-    __rmul__ = __mul__
-
-    @classmethod
-    def msm(cls, points, scalars):
-        if len(points) != len(scalars):
-            raise ValueError("Points and scalars must have same length")
-        if not points:
-            return cls.identity()
-        raw = runtime.context().bsn_msm(pack_points(points), pack_scalars(scalars, cls._N), cls._CV)
-        return cls._trusted(int.from_bytes(raw[:32], "little"), int.from_bytes(raw[32:], "little"))
-
-    def clear_cofactor(self):
-        return self
-
-    # -- codec: SEC1 (sw_affine_point.py point_to_string / string_to_point)
-    def point_to_string(self, compressed: bool = True) -> bytes:
-        if self.is_identity():
-            return b"\x00"
-        x = self.x.to_bytes(32, "big")
-        if compressed:
-            return (b"\x03" if self.y % 2 else b"\x02") + x
-        return b"\x04" + x + self.y.to_bytes(32, "big")
-
-    @classmethod
-    def string_to_point(cls, data):
-        if isinstance(data, str):
-            data = bytes.fromhex(data)
-        data = bytes(data)
-        if len(data) == 0:
-            raise ValueError("Empty octet string")
-        prefix, p = data[0], cls._P
-        if prefix == 0x00:
-            if len(data) != 1:
-                raise ValueError("Point at infinity must be single byte 0x00")
-            return cls.identity()
-        if prefix in (0x02, 0x03):
-            if len(data) != 33:
-                raise ValueError(f"Invalid compressed point length: expected 33, got {len(data)}")
-            x = int.from_bytes(data[1:], "big")
-            if x >= p:
-                raise ValueError(f"x-coordinate {x} is not in field Fp (p={p})")
-            try:
-                y = cls.curve.mod_sqrt((x * x * x + cls._SW_B) % p)
-            except ValueError:
-                raise ValueError("Invalid point encoding") from None
-            if y % 2 != prefix % 2:
-                y = p - y
-            return cls(x, y)
-        if prefix == 0x04:
-            if len(data) != 65:
-                raise ValueError(f"Invalid uncompressed point length: expected 65, got {len(data)}")
-            x, y = int.from_bytes(data[1:33], "big"), int.from_bytes(data[33:], "big")
-            if x >= p:
-                raise ValueError(f"x-coordinate {x} is not in field Fp (p={p})")
-            if y >= p:
-                raise ValueError(f"y-coordinate {y} is not in field Fp (p={p})")
-            if not cls._on_curve(x, y):
-                raise ValueError(f"Point ({x}, {y}) is not on curve")
-            return cls(x, y)
-        raise ValueError(f"Invalid point encoding prefix: 0x{prefix:02x}")
-
     # -- hash to curve (RFC 9380; sw_affine_point.py:428-562): expand_message_xmd natively on the host, the map on the GPU
-    _suite_struct = BandersnatchPoint.__dict__["_suite_struct"]
-
     @classmethod
     def _mapped(cls, us: bytes, per_item: int):
         raw, ok = runtime.context().secp256k1_map_to_curve(us, per_item)
@@ -906,7 +759,7 @@ class Secp256k1Point(_Rfc9380, ShortWeierstrassA0Point):
         return cls._mapped((int(u) % cls._P).to_bytes(32, "little"), 1)[0]
 
 
-class Bls12381G1Point(_WideRfc9380, ShortWeierstrassA0Point):
+class Bls12381G1Point(_WideRfc9380, _Sec1Codec, ShortWeierstrassA0Point):
     """Affine point of E(Fq): y^2 = x^3 + 4 over BLS12-381's 381-bit base field (dot_ring/curve/specs/bls12_381_G1.py), the identity is
     (None, None).  It has Secp256k1Point's surface (the host big-int additions are the shared a = 0 base class's) with 48-byte
     coordinates.  E(Fq) has order h r: a point need not lie in G1, so scalars are NEVER reduced mod r — `P * k` is exact for every
@@ -918,6 +771,7 @@ class Bls12381G1Point(_WideRfc9380, ShortWeierstrassA0Point):
     _COFACTOR = 0x396C8C005555E1568C00AAAB0000AAAB       # #E(Fq) = _COFACTOR * _N
     _CV = _native.CURVE_BLS12_381_G1
     _SW_B = 4
+    _SEC1_LEN, _SEC1_HYBRID = 48, True
     _SUITE, _NO_IMAGE = "blsg1", "base is not invertible for the given modulus"     # pow(x_den, -1, p) of apply_isogeny
     __slots__ = ()
 
@@ -989,54 +843,14 @@ class Bls12381G1Point(_WideRfc9380, ShortWeierstrassA0Point):
     def clear_cofactor(self):
         return self * self._H
 
-    # -- codec: SEC1 (sw_affine_point.py point_to_string / string_to_point), 48-byte coordinates
-    def point_to_string(self, compressed: bool = True) -> bytes:
-        if self.is_identity():
-            return b"\x00"
-        x = self.x.to_bytes(48, "big")
-        if compressed:
-            return (b"\x03" if self.y % 2 else b"\x02") + x
-        return b"\x04" + x + self.y.to_bytes(48, "big")
-
+    # -- codec: SEC1 with 48-byte coordinates and the hybrid forms; any point of E(Fq) decodes, in G1 or not (curve.valid_point asks that)
     @classmethod
-    def string_to_point(cls, data):
-        """the forms the reference accepts: 0x00 (identity), 0x02 / 0x03 (compressed: the decode kernel), 0x04 (uncompressed), 0x06 / 0x07
-        (hybrid: both coordinates and the parity of y); any point of E(Fq) decodes, in G1 or not (curve.valid_point asks that)"""
-        if isinstance(data, str):
-            data = bytes.fromhex(data)
-        data = bytes(data)
-        if len(data) == 0:
-            raise ValueError("Empty octet string")
-        prefix, p = data[0], cls._P
-        if prefix == 0x00:
-            if len(data) != 1:
-                raise ValueError("Point at infinity must be single byte 0x00")
-            return cls.identity()
-        if prefix in (0x02, 0x03):
-            if len(data) != 49:
-                raise ValueError(f"Invalid compressed point length: expected 49, got {len(data)}")
-            x = int.from_bytes(data[1:], "big")
-            if x >= p:
-                raise ValueError(f"x-coordinate {x} is not in field Fp (p={p})")
-            raw, ok = runtime.context().blsg1_decode_points(data, check=False)
-            if not ok[0]:
-                raise ValueError("Invalid point encoding")
-            return cls._unpack(raw)[0]
-        if prefix in (0x04, 0x06, 0x07):
-            if len(data) != 97:
-                kind = "uncompressed" if prefix == 0x04 else "hybrid"
-                raise ValueError(f"Invalid {kind} point length: expected 97, got {len(data)}")
-            x, y = int.from_bytes(data[1:49], "big"), int.from_bytes(data[49:], "big")
-            if x >= p:
-                raise ValueError(f"x-coordinate {x} is not in field Fp (p={p})")
-            if y >= p:
-                raise ValueError(f"y-coordinate {y} is not in field Fp (p={p})")
-            if prefix != 0x04 and y % 2 != prefix % 2:
-                raise ValueError("Hybrid format: y parity doesn't match prefix")
-            if not cls._on_curve(x, y):
-                raise ValueError(f"Point ({x}, {y}) is not on curve")
-            return cls(x, y)
-        raise ValueError(f"Invalid point encoding prefix: 0x{prefix:02x}")
+    def _sec1_decompress(cls, prefix: int, x: int):
+        """the decode kernel"""
+        raw, ok = runtime.context().blsg1_decode_points(bytes([prefix]) + x.to_bytes(48, "big"), check=False)
+        if not ok[0]:
+            raise ValueError("Invalid point encoding")
+        return cls._unpack(raw)[0]
 
     # -- hash to curve (RFC 9380 BLS12381G1_XMD:SHA-256_SSWU_RO_ / _NU_): expand_message_xmd natively on the host, the map on the GPU
     @classmethod
@@ -1188,13 +1002,12 @@ class Fp2:
         return self.re, self.im
 
 
-class Bls12381G2Point(_WideRfc9380):
+class Bls12381G2Point(_WideRfc9380, _AffinePoint):
     """Affine point of E(Fq2): y^2 = x^3 + 4 (1 + i) over BLS12-381's quadratic extension (dot_ring/curve/specs/bls12_381_G2.py), the
     identity is (None, None); coordinates are Fp2 values ((re, im) tuples are accepted).  E(Fq2) has order h2 r (762 bits): a point need
     not lie in G2, so scalars are never reduced mod r.  Single additions are host big-integer code; scalar multiplications and hashing to
     the curve (RFC 9380: simplified SWU, the 3-isogeny, the clearing by psi) run on the GPU (kernels_g2_h2c.hip.h, the dr_blsg2_* entry
     points).  There is no point codec, as in the reference."""
-    curve: BandersnatchCurve
     _P = 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB
     _N = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
     # h_eff of RFC 9380 8.8.2: the reference's `cofactor`, what clear_cofactor multiplies by (636 bits)
@@ -1202,7 +1015,7 @@ class Bls12381G2Point(_WideRfc9380):
     # #E(Fq2) = _COFACTOR * _N
     _COFACTOR = 0x5D543A95414E7F1091D50792876A202CD91DE4547085ABAA68A205B2E5A7DDFA628F1CB4D9E82EF21537E293A6691AE1616EC6E786F0C70CF1C38E31C7238E5
     _CV = _native.CURVE_BLS12_381_G2
-    __slots__ = ("x", "y")
+    __slots__ = ()
 
     def __init__(self, x, y):
         self.x, self.y = self._coord(x), self._coord(y)
@@ -1241,23 +1054,6 @@ class Bls12381G2Point(_WideRfc9380):
 
     def __hash__(self):
         return 0 if self.x is None else hash((self.x.to_tuple(), self.y.to_tuple()))
-
-    def __repr__(self):
-        return f"{type(self).__name__}({self.x}, {self.y})"
-
-    @classmethod
-    def identity(cls):
-        return cls(None, None)
-
-    @classmethod
-    def generator_point(cls):
-        return cls(*cls.curve.params.generator)
-
-    def is_identity(self) -> bool:
-        return self.x is None and self.y is None
-
-    def is_on_curve(self) -> bool:
-        return self.is_identity() or self._on_curve(self.x, self.y)
 
     # -- group law on the host
     def __add__(self, other):
@@ -1329,49 +1125,11 @@ class Bls12381G2Point(_WideRfc9380):
         return cls._mapped(cls._pack_fp2(cls._coord(u)), 1, clear=False)[0]
 
 
-class P256SswuPoint(_Rfc9380, P256Point):
+class P256SswuPoint(_Rfc9380, _Sec1Codec, P256Point):
     """Affine point of P256_RO / P256_NU (dot_ring/curve/specs/p256.py with E2C_Variant.SSWU / SSWU_NU): P-256's group and kernels under
     the variant's curve id, the reference's generic SEC1 codec in place of P256_TAI's (P256Point.point_to_string defers to
     SWAffinePoint's for these variants), and hashing to the curve by RFC 9380's simplified SWU map (k_p256_map_to_curve)."""
     __slots__ = ()
-
-    # -- codec: SEC1 (sw_affine_point.py point_to_string / string_to_point)
-    def point_to_string(self, compressed: bool = True) -> bytes:
-        if self.is_identity():
-            return b"\x00"
-        x = self.x.to_bytes(32, "big")
-        if compressed:
-            return (b"\x03" if self.y % 2 else b"\x02") + x
-        return b"\x04" + x + self.y.to_bytes(32, "big")
-
-    @classmethod
-    def string_to_point(cls, data):
-        if isinstance(data, str):
-            data = bytes.fromhex(data)
-        data = bytes(data)
-        if len(data) == 0:
-            raise ValueError("Empty octet string")
-        prefix, p = data[0], cls._P
-        if prefix == 0x00:
-            if len(data) != 1:
-                raise ValueError("Point at infinity must be single byte 0x00")
-            return cls.identity()
-        if prefix in (0x02, 0x03):
-            if len(data) != 33:
-                raise ValueError(f"Invalid compressed point length: expected 33, got {len(data)}")
-            return cls._string_to_sec1_point(data)
-        if prefix == 0x04:
-            if len(data) != 65:
-                raise ValueError(f"Invalid uncompressed point length: expected 65, got {len(data)}")
-            x, y = int.from_bytes(data[1:33], "big"), int.from_bytes(data[33:], "big")
-            if x >= p:
-                raise ValueError(f"x-coordinate {x} is not in field Fp (p={p})")
-            if y >= p:
-                raise ValueError(f"y-coordinate {y} is not in field Fp (p={p})")
-            if not cls._on_curve(x, y):
-                raise ValueError(f"Point ({x}, {y}) is not on curve")
-            return cls(x, y)
-        raise ValueError(f"Invalid point encoding prefix: 0x{prefix:02x}")
 
     # -- hash to curve (RFC 9380; sw_affine_point.py:428-533): expand_message_xmd natively on the host, the map on the GPU
     @classmethod
@@ -1382,6 +1140,23 @@ class P256SswuPoint(_Rfc9380, P256Point):
     @classmethod
     def map_to_curve_simple_swu(cls, u: int):
         return cls._mapped((int(u) % cls._P).to_bytes(32, "little"), 1)[0]
+
+
+def _ell2_curve25519(u: int):
+    """RFC 9380's Elligator 2 onto curve25519, v^2 = u^3 + 486662 u^2 + u (te_curve.py:48-95, mg_affine_point.py:289-346): the
+    Montgomery coordinates of ONE image, host big-int code"""
+    p, a = 2**255 - 19, 486662
+    tv1 = 2 * u * u % p
+    if tv1 == p - 1:
+        tv1 = 0
+    x1 = -a * pow(tv1 + 1, -1, p) % p
+    gx1 = ((x1 + a) * x1 + 1) * x1 % p
+    e2 = gx1 == 0 or pow(gx1, (p - 1) // 2, p) == 1
+    x, y2 = (x1, gx1) if e2 else ((-x1 - a) % p, tv1 * gx1 % p)
+    y = _sqrt_5mod8(y2, p)
+    if e2 ^ (y % 2 == 1):                     # (the parity picks the root: whichever the square-root routine returned)
+        y = -y % p
+    return x, y
 
 
 class Ed25519Ell2Point(_Rfc9380, BandersnatchPoint):
@@ -1401,17 +1176,8 @@ class Ed25519Ell2Point(_Rfc9380, BandersnatchPoint):
     def map_to_curve(cls, u: int):
         """Ed25519Point.map_to_curve (te_curve.py:48-95, then mont_to_ed25519): ONE image with its cofactor not cleared, host big-int code
         as BandersnatchPoint.map_to_curve is; the batched path (encode_to_curve_from_field) runs the same steps in the kernel"""
-        p, a = cls._P, 486662
-        tv1 = 2 * u * u % p
-        if tv1 == p - 1:
-            tv1 = 0
-        x1 = -a * pow(tv1 + 1, -1, p) % p
-        gx1 = ((x1 + a) * x1 + 1) * x1 % p
-        e2 = cls.curve.is_square(gx1)
-        x, y2 = (x1, gx1) if e2 else ((-x1 - a) % p, tv1 * gx1 % p)
-        y = cls.curve.mod_sqrt(y2)
-        if e2 ^ (y % 2 == 1):
-            y = -y % p
+        p = cls._P
+        x, y = _ell2_curve25519(u)
         # pow raises ValueError where y = 0 or x = -1, as the reference does
         return cls(_sqrt_tonelli_shanks(-486664, p) * x % p * pow(y, -1, p) % p, (x - 1) * pow(x + 1, -1, p) % p)
 
@@ -1445,12 +1211,7 @@ class Ed448Point(_WideRfc9380, BandersnatchPoint):
     def _scalars(cls, scalars) -> bytes:
         return b"".join((int(k) % cls._N).to_bytes(56, "little") for k in scalars)
 
-    # -- scalar multiplication / MSM on the GPU (te_affine_point.py:163: the scalar reduced mod n)
-    def __mul__(self, scalar: int):
-        return scalar_mul_batch([self], [scalar])[0]
-
-    __rmul__ = __mul__
-
+    # -- MSM on the GPU (te_affine_point.py:163: the scalars reduced mod n)
     @classmethod
     def msm(cls, points, scalars):
         if len(points) != len(scalars):
@@ -1499,20 +1260,19 @@ class Ed448Point(_WideRfc9380, BandersnatchPoint):
         return [bool(f) for f in ok]
 
 
-class Curve25519Point(_Rfc9380):
+class Curve25519Point(_Rfc9380, _AffinePoint):
     """Affine point of Curve25519_RO / Curve25519_NU (dot_ring/curve/specs/curve25519.py, montgomery/mg_affine_point.py):
     y^2 = x^3 + 486662 x^2 + x over 2^255 - 19 (x, y are the reference's names for u, v), cofactor 8, the identity is (None, None).
     (0, 0) is a point of the curve (order 2), so the identity cannot travel as 64 zero bytes: it packs as 64 bytes of 0xff for the generic
     entry points and as a flag byte for the dr_curve25519_* ones (pack_points_flagged).  Single additions are host big-int code with the
     reference's affine formulas; scalar multiplications, MSMs, decoding and hashing to the curve run on the GPU (kernels_curve25519.hip.h,
     which computes on the Ed25519 group law through the birational map)."""
-    curve: BandersnatchCurve
     _P = 2**255 - 19
     _N = 2**252 + 0x14DEF9DEA2F79CD65812631A5CF5D3ED
     _H, _CV = 8, _native.CURVE_CURVE25519_RO
     _MG_A = 486662
     _IDENTITY_BYTES = b"\xff" * 64
-    __slots__ = ("x", "y")
+    __slots__ = ()
 
     def __init__(self, x, y):
         self.x, self.y = x, y
@@ -1540,22 +1300,8 @@ class Curve25519Point(_Rfc9380):
     def __hash__(self):
         return 0 if self.x is None else (self.x + self.y) % self._N
 
-    def __repr__(self):
-        return f"{type(self).__name__}({self.x}, {self.y})"
-
-    @classmethod
-    def identity(cls):
-        return cls(None, None)
-
-    @classmethod
-    def generator_point(cls):
-        return cls(*cls.curve.params.generator)
-
     def is_identity(self) -> bool:
         return self.x is None or self.y is None
-
-    def is_on_curve(self) -> bool:
-        return self.is_identity() or self._on_curve(self.x, self.y)
 
     # -- group law (mg_affine_point.py:38-116, B = 1)
     def __add__(self, other):
@@ -1582,23 +1328,6 @@ class Curve25519Point(_Rfc9380):
     def __neg__(self):
         return self if self.is_identity() else type(self)(self.x, -self.y % self._P)
 
-    def __sub__(self, other):
-        return self + (-other)
-
-    def __mul__(self, scalar: int):
-        return scalar_mul_batch([self], [scalar])[0]
-
-    __rmul__ = __mul__
-
-    @classmethod
-    def msm(cls, points, scalars):
-        if len(points) != len(scalars):
-            raise ValueError("Points and scalars must have same length")
-        if not points:
-            return cls.identity()
-        raw = runtime.context().bsn_msm(pack_points(points), pack_scalars(scalars, cls._N), cls._CV)
-        return cls._trusted(int.from_bytes(raw[:32], "little"), int.from_bytes(raw[32:], "little"))
-
     def clear_cofactor(self):
         return scalar_mul_batch_raw([self], [self._H])[0]
 
@@ -1622,24 +1351,11 @@ class Curve25519Point(_Rfc9380):
         return cls(int.from_bytes(data[:32], "little"), int.from_bytes(data[32:], "little"))
 
     # -- hash to curve (RFC 9380 curve25519_XMD:SHA-512_ELL2_RO_ / _NU_): expand_message_xmd natively on the host, the map on the GPU
-    _suite_struct = BandersnatchPoint.__dict__["_suite_struct"]
-
     @classmethod
     def map_to_curve(cls, u: int):
         """MGAffinePoint.map_to_curve (mg_affine_point.py:289-346): ONE image with its cofactor not cleared, host big-int code as the
         other suites' map_to_curve is; the batched path (encode_to_curve_from_field) runs the same steps in the kernel"""
-        p, a = cls._P, cls._MG_A
-        tv1 = 2 * u * u % p
-        if tv1 == p - 1:
-            tv1 = 0
-        x1 = -a * pow(tv1 + 1, -1, p) % p
-        gx1 = ((x1 + a) * x1 + 1) * x1 % p
-        e2 = cls.curve.is_square(gx1)
-        x, y2 = (x1, gx1) if e2 else ((-x1 - a) % p, tv1 * gx1 % p)
-        y = _sqrt_tonelli_shanks(y2, p)
-        if e2 ^ (y % 2 == 1):
-            y = -y % p
-        return cls(x, y)
+        return cls(*_ell2_curve25519(u))
 
     @classmethod
     def _mapped(cls, us: bytes, per_item: int):
@@ -1650,7 +1366,7 @@ class Curve25519Point(_Rfc9380):
 def pack_points(points) -> bytes:
     """x || y little-endian per point; an SW identity ((None, None)) packs as 64 zero bytes, as the ABI takes it, Curve25519's — where
     (0, 0) is a point — as 64 bytes of 0xff."""
-    return b"".join(p._IDENTITY_BYTES if p.x is None and hasattr(p, "_IDENTITY_BYTES")
+    return b"".join(p._IDENTITY_BYTES if p.x is None
                     else (p.x or 0).to_bytes(32, "little") + (p.y or 0).to_bytes(32, "little") for p in points)
 
 
@@ -1682,19 +1398,7 @@ def scalar_mul_batch(points, scalars):
     """[k_i * P_i] in one kernel launch."""
     if len(points) != len(scalars):
         raise ValueError("Points and scalars must have same length")
-    if not points:
-        return []
-    cls = type(points[0])
-    if hasattr(cls, "_scalar_mul_batch"):        # a wide point type (other coordinate and scalar widths): its own entry point
-        return cls._scalar_mul_batch(points, scalars)
-    first = points[0]
-    if all(p is first for p in points) and (first.x, first.y) in _fixed_bases(cls):
-        # k_i * G (key derivation, curve.py:384) or k_i * B: the constant's fixed-base window table — 64 table additions
-        # over four lanes instead of ~250 dependent doublings (dr_te_fixed_base_msm_groups)
-        raw = runtime.context().te_fixed_base_msm_groups(pack_points([first]), pack_scalars(scalars, cls._N), cls._CV)
-        return unpack_points(cls, raw)
-    raw = runtime.context().bsn_scalar_mul_batch(pack_points(points), pack_scalars(scalars, cls._N), cls._CV)
-    return unpack_points(cls, raw)
+    return type(points[0])._scalar_mul_batch(points, scalars) if points else []
 
 
 def _fixed_bases(cls):
@@ -1706,33 +1410,13 @@ def _fixed_bases(cls):
 
 def msm_groups(points, scalars, m: int):
     """[sum_{j<m} k_{g*m+j} * P_{g*m+j}] for consecutive groups of m terms, one launch."""
-    if not points:
-        return []
-    cls = type(points[0])
-    if hasattr(cls, "_msm_groups"):
-        return cls._msm_groups(points, scalars, m)
-    raw = runtime.context().bsn_msm_groups(pack_points(points), pack_scalars(scalars, cls._N), m, cls._CV)
-    return unpack_points(cls, raw)
+    return type(points[0])._msm_groups(points, scalars, m) if points else []
 
 
 def valid_points(points) -> list[bool]:
-    """curve.py:56 for a whole batch: [h]P != O and [h^-1 mod n][h]P == P (h the cofactor), one launch for all points."""
-    if points and hasattr(type(points[0]), "_valid_points"):   # a wide point type: one launch of its decoder's subgroup check (on G1,
-        return type(points[0])._valid_points(points)            # where E(Fq) is not h x (prime) for a small h, the only sound one)
-    live = [i for i, p in enumerate(points) if not p.is_identity() and p.is_on_curve()]
-    out = [False] * len(points)
-    if not live:
-        return out
-    h, order = type(points[live[0]])._H, type(points[live[0]])._N
-    if h == 1:                               # prime order (P-256, secp256k1): on the curve and not the identity (curve.py:61)
-        for i in live:
-            out[i] = True
-        return out
-    cleared = scalar_mul_batch_raw([points[i] for i in live], [h] * len(live))
-    back = scalar_mul_batch([c for c in cleared], [pow(h, -1, order)] * len(live))
-    for i, c, b in zip(live, cleared, back):
-        out[i] = (not c.is_identity()) and b == points[i]
-    return out
+    """curve.py:56 for a whole batch: non-identity members of the prime-order subgroup, one launch for all points (on G1, where E(Fq)
+    is not h x (prime) for a small h, the decoder's subgroup check is the only sound one)."""
+    return type(points[0])._valid_points(points) if points else []
 
 
 def scalar_mul_batch_raw(points, small_scalars):
@@ -1750,14 +1434,26 @@ def scalar_mul_batch_raw(points, small_scalars):
 
 
 # ------------------------------------------------------------------ suites / curve variants
-def _suite(name: str, suite_id: bytes, xof: bool, bb, ab, pp, **curve_consts):
-    params = SuiteParams(suite_id=suite_id, hash_fn=hashlib.shake_128 if xof else hashlib.sha512,
-                         auxiliary_points=AuxiliaryPoints(bb, ab, pp), xof=xof, **curve_consts)
+def _variant(base, name: str, params: SuiteParams, **class_attrs):
+    """the variant `name`: a curve object over params and the point type f"{name}Point" below base, bound to it"""
     curve = BandersnatchCurve(params)
-    point_type = type(f"{name}Point", (BandersnatchPoint,), {
-        "curve": curve, "__slots__": (), "_A": params.a, "_D": params.d, "_N": params.subgroup_order, "_H": params.cofactor,
-        "_CV": params.curve_id, "_P": params.field_modulus})
-    return CurveVariant(name, curve, point_type)
+    return CurveVariant(name, curve, type(f"{name}Point", (base,), {"__slots__": (), "curve": curve, "_CV": params.curve_id, **class_attrs}))
+
+
+def _te_variant(base, name: str, params: SuiteParams):
+    """... of a 256-bit twisted Edwards suite: the class takes its coefficients, order, cofactor and field from params"""
+    return _variant(base, name, params, _A=params.a, _D=params.d, _N=params.subgroup_order, _H=params.cofactor, _P=params.field_modulus)
+
+
+def _suite(name: str, suite_id: bytes, xof: bool, bb, ab, pp, **curve_consts):
+    return _te_variant(BandersnatchPoint, name, SuiteParams(
+        suite_id=suite_id, hash_fn=hashlib.shake_128 if xof else hashlib.sha512, auxiliary_points=AuxiliaryPoints(bb, ab, pp), xof=xof,
+        **curve_consts))
+
+
+def _nu(params: SuiteParams, curve_id: int) -> SuiteParams:
+    """the suite's non-uniform (one field element) variant: it travels in the curve id"""
+    return dataclasses.replace(params, curve_id=curve_id, e2c=params.e2c + "_nu")
 
 
 class CurveVariant:
@@ -1767,7 +1463,7 @@ class CurveVariant:
         self.name, self.curve, self.point_type = name, curve, point_type
 
     def point(self, x, y=None):
-        if isinstance(x, (BandersnatchPoint, BandersnatchSWPoint, P256Point, ShortWeierstrassA0Point, Curve25519Point, Bls12381G2Point)):
+        if isinstance(x, _AffinePoint):
             return x
         if y is None:
             x, y = x
@@ -1844,10 +1540,7 @@ _SW_PARAMS = SuiteParams(
     curve_id=_native.CURVE_BANDERSNATCH_SW,
     e2c="tai",
 )
-Bandersnatch_SW = CurveVariant(
-    "Bandersnatch_SW", BandersnatchCurve(_SW_PARAMS),
-    type("Bandersnatch_SWPoint", (BandersnatchSWPoint,), {"__slots__": ()}))
-Bandersnatch_SW.point_type.curve = Bandersnatch_SW.curve
+Bandersnatch_SW = _variant(BandersnatchSWPoint, "Bandersnatch_SW", _SW_PARAMS)
 
 # dot_ring/curve/specs/ed25519.py, the Ed25519_TAI variant (the reference exports it as Ed25519): its own field 2^255 - 19, a = -1,
 # cofactor 8, try-and-increment with SHA-512; no accumulator base or padding point, so RingProofParams refuses it.  Every group
@@ -1873,16 +1566,9 @@ Ed25519 = Ed25519_TAI
 # Ed25519_RO / Ed25519_NU (specs/ed25519.py: the same params, E2C_Variant.ELL2 / ELL2_NU): hashing to the curve by RFC 9380's
 # edwards25519_XMD:SHA-512_ELL2_RO_ (two field elements) or ..._NU_ (one); the suite id is the TAI variant's, as in the reference, so the
 # variant travels in the curve id (DR_CURVE_ED25519_RO / DR_CURVE_ED25519_NU).
-def _ed25519_variant(name: str, e2c: str, curve_id: int) -> CurveVariant:
-    params = dataclasses.replace(Ed25519_TAI.curve.params, curve_id=curve_id, e2c=e2c)
-    curve = BandersnatchCurve(params)
-    return CurveVariant(name, curve, type(f"{name}Point", (Ed25519Ell2Point,), {
-        "curve": curve, "__slots__": (), "_A": params.a, "_D": params.d, "_N": params.subgroup_order, "_H": params.cofactor,
-        "_CV": curve_id, "_P": params.field_modulus}))
-
-
-Ed25519_RO = _ed25519_variant("Ed25519_RO", "ell2", _native.CURVE_ED25519_RO)
-Ed25519_NU = _ed25519_variant("Ed25519_NU", "ell2_nu", _native.CURVE_ED25519_NU)
+_ED25519_RO_PARAMS = dataclasses.replace(Ed25519_TAI.curve.params, curve_id=_native.CURVE_ED25519_RO, e2c="ell2")
+Ed25519_RO = _te_variant(Ed25519Ell2Point, "Ed25519_RO", _ED25519_RO_PARAMS)
+Ed25519_NU = _te_variant(Ed25519Ell2Point, "Ed25519_NU", _nu(_ED25519_RO_PARAMS, _native.CURVE_ED25519_NU))
 
 # dot_ring/curve/specs/p256.py, the P256_TAI variant (the reference exports it as P256): NIST P-256 over its own field, a = -3,
 # cofactor 1, 33-byte points, try-and-increment with SHA-256; no accumulator base or padding point, and not twisted Edwards, so
@@ -1904,21 +1590,16 @@ _P256_PARAMS = SuiteParams(
     curve_id=_native.CURVE_P256,
     e2c="tai",
 )
-P256_TAI = CurveVariant("P256_TAI", BandersnatchCurve(_P256_PARAMS), type("P256_TAIPoint", (P256Point,), {"__slots__": ()}))
-P256_TAI.point_type.curve = P256_TAI.curve
+P256_TAI = _variant(P256Point, "P256_TAI", _P256_PARAMS)
 P256 = P256_TAI
 
 
 # P256_RO / P256_NU (specs/p256.py: the same params, E2C_Variant.SSWU / SSWU_NU): hashing to the curve by RFC 9380's
 # P256_XMD:SHA-256_SSWU_RO_ (two field elements) or ..._NU_ (one), points in SEC1 form; the suite id is the TAI variant's, as in the
 # reference, so the variant travels in the curve id (DR_CURVE_P256_RO / DR_CURVE_P256_NU).  Not twisted Edwards: RingProofParams refuses them.
-def _p256_variant(name: str, e2c: str, curve_id: int) -> CurveVariant:
-    curve = BandersnatchCurve(dataclasses.replace(_P256_PARAMS, curve_id=curve_id, e2c=e2c))
-    return CurveVariant(name, curve, type(f"{name}Point", (P256SswuPoint,), {"__slots__": (), "curve": curve, "_CV": curve_id}))
-
-
-P256_RO = _p256_variant("P256_RO", "sswu", _native.CURVE_P256_RO)
-P256_NU = _p256_variant("P256_NU", "sswu_nu", _native.CURVE_P256_NU)
+_P256_RO_PARAMS = dataclasses.replace(_P256_PARAMS, curve_id=_native.CURVE_P256_RO, e2c="sswu")
+P256_RO = _variant(P256SswuPoint, "P256_RO", _P256_RO_PARAMS)
+P256_NU = _variant(P256SswuPoint, "P256_NU", _nu(_P256_RO_PARAMS, _native.CURVE_P256_NU))
 
 # dot_ring/curve/specs/baby_jubjub.py: a = 1 over the BN254 scalar field, cofactor 8, try-and-increment with SHA-512 (the candidates lose
 # bit 254, as the reference masks them to the field's bit length).  It carries all three auxiliary points, but RingProofParams refuses
@@ -1947,60 +1628,48 @@ BabyJubJub = _suite(
 # RFC 9380's secp256k1_XMD:SHA-256_SSWU_RO_ (two field elements) or ..._NU_ (one); both variants carry the RO suite id, as in the
 # reference.  No accumulator base or padding point, and not twisted Edwards, so RingProofParams refuses them.  Every group operation and
 # the map run on the secp256k1 kernels (DR_CURVE_SECP256K1 / DR_CURVE_SECP256K1_NU).
-def _secp256k1_variant(name: str, e2c: str, curve_id: int) -> CurveVariant:
-    params = SuiteParams(
-        suite_id=b"secp256k1_XMD:SHA-256_SSWU_RO_", hash_fn=hashlib.sha256, xof=False,
-        auxiliary_points=AuxiliaryPoints(
-            (0x50929B74C1A04954B78B4B6035E97A5E078A5A0F28EC96D547BFEE9ACE803AC0,
-             0x31D3C6863973926E049E637CB1B5F40A36DAC28AF1766968C30C2313F3A38904),
-            None, None),
-        field_modulus=Secp256k1Point._P,
-        subgroup_order=Secp256k1Point._N,
-        cofactor=1,
-        a=0,
-        d=0,
-        generator=(0x79BE667EF9DCBBAC55A06295CE870B07029BFCDB2DCE28D959F2815B16F81798,
-                   0x483ADA7726A3C4655DA4FBFC0E1108A8FD17B448A68554199C47D08FFB10D4B8),
-        encoding=Encoding(point_len=33),
-        curve_id=curve_id,
-        e2c=e2c,
-    )
-    curve = BandersnatchCurve(params)
-    return CurveVariant(name, curve, type(f"{name}Point", (Secp256k1Point,), {"__slots__": (), "curve": curve, "_CV": curve_id}))
-
+_SECP256K1_PARAMS = SuiteParams(
+    suite_id=b"secp256k1_XMD:SHA-256_SSWU_RO_", hash_fn=hashlib.sha256, xof=False,
+    auxiliary_points=AuxiliaryPoints(
+        (0x50929B74C1A04954B78B4B6035E97A5E078A5A0F28EC96D547BFEE9ACE803AC0,
+         0x31D3C6863973926E049E637CB1B5F40A36DAC28AF1766968C30C2313F3A38904),
+        None, None),
+    field_modulus=Secp256k1Point._P,
+    subgroup_order=Secp256k1Point._N,
+    cofactor=1,
+    a=0,
+    d=0,
+    generator=(0x79BE667EF9DCBBAC55A06295CE870B07029BFCDB2DCE28D959F2815B16F81798,
+               0x483ADA7726A3C4655DA4FBFC0E1108A8FD17B448A68554199C47D08FFB10D4B8),
+    encoding=Encoding(point_len=33),
+    curve_id=_native.CURVE_SECP256K1,
+    e2c="sswu",
+)
+Secp256k1_RO = _variant(Secp256k1Point, "Secp256k1_RO", _SECP256K1_PARAMS)
+Secp256k1_NU = _variant(Secp256k1Point, "Secp256k1_NU", _nu(_SECP256K1_PARAMS, _native.CURVE_SECP256K1_NU))
+Secp256k1 = Secp256k1_RO
 
 # dot_ring/curve/specs/curve25519.py: v^2 = u^3 + 486662 u^2 + u over 2^255 - 19, Ed25519's group (cofactor 8) in Montgomery form, points
 # 64 bytes u || v (point_len 32, uncompressed), SHA-512, hashing to the curve by RFC 9380's curve25519_XMD:SHA-512_ELL2_RO_ (two field
 # elements) or ..._NU_ (one); both variants share the RO suite id and the generator as Pedersen blinding base, as in the reference.  No
 # accumulator base or padding point, and not twisted Edwards, so RingProofParams refuses them.
 _CURVE25519_G = (9, 14781619447589544791020593568409986887264606134616475288964881837755586237401)
-
-
-def _curve25519_variant(name: str, e2c: str, curve_id: int) -> CurveVariant:
-    params = SuiteParams(
-        suite_id=b"curve25519_XMD:SHA-512_ELL2_RO_", hash_fn=hashlib.sha512, xof=False,
-        auxiliary_points=AuxiliaryPoints(_CURVE25519_G, None, None),
-        field_modulus=Curve25519Point._P,
-        subgroup_order=Curve25519Point._N,
-        cofactor=8,
-        a=Curve25519Point._MG_A,
-        d=1,                                       # (the Montgomery B)
-        generator=_CURVE25519_G,
-        encoding=Encoding(point_len=32, uncompressed=True),
-        curve_id=curve_id,
-        e2c=e2c,
-    )
-    curve = BandersnatchCurve(params)
-    return CurveVariant(name, curve, type(f"{name}Point", (Curve25519Point,), {"__slots__": (), "curve": curve, "_CV": curve_id}))
-
-
-Curve25519_RO = _curve25519_variant("Curve25519_RO", "ell2", _native.CURVE_CURVE25519_RO)
-Curve25519_NU = _curve25519_variant("Curve25519_NU", "ell2_nu", _native.CURVE_CURVE25519_NU)
+_CURVE25519_PARAMS = SuiteParams(
+    suite_id=b"curve25519_XMD:SHA-512_ELL2_RO_", hash_fn=hashlib.sha512, xof=False,
+    auxiliary_points=AuxiliaryPoints(_CURVE25519_G, None, None),
+    field_modulus=Curve25519Point._P,
+    subgroup_order=Curve25519Point._N,
+    cofactor=8,
+    a=Curve25519Point._MG_A,
+    d=1,                                       # (the Montgomery B)
+    generator=_CURVE25519_G,
+    encoding=Encoding(point_len=32, uncompressed=True),
+    curve_id=_native.CURVE_CURVE25519_RO,
+    e2c="ell2",
+)
+Curve25519_RO = _variant(Curve25519Point, "Curve25519_RO", _CURVE25519_PARAMS)
+Curve25519_NU = _variant(Curve25519Point, "Curve25519_NU", _nu(_CURVE25519_PARAMS, _native.CURVE_CURVE25519_NU))
 Curve25519 = Curve25519_RO
-
-Secp256k1_RO = _secp256k1_variant("Secp256k1_RO", "sswu", _native.CURVE_SECP256K1)
-Secp256k1_NU = _secp256k1_variant("Secp256k1_NU", "sswu_nu", _native.CURVE_SECP256K1_NU)
-Secp256k1 = Secp256k1_RO
 
 
 # dot_ring/curve/specs/bls12_381_G1.py: E: y^2 = x^3 + 4 over the 381-bit Fq, #E(Fq) = h r, hashing by RFC 9380's
@@ -2008,27 +1677,22 @@ Secp256k1 = Secp256k1_RO
 # reference.  Encoding(point_len=32, challenge_len=48) are the reference's own figures; its points encode to 49 bytes, which point_len =
 # 32 contradicts, so the reference can decode no key or proof of this curve — the VRF classes refuse these two suites (vrf/base.py) and
 # what is served is the point type and curve.valid_point.  No auxiliary points, not twisted Edwards: RingProofParams refuses them too.
-def _bls12_381_g1_variant(name: str, e2c: str, curve_id: int) -> CurveVariant:
-    params = SuiteParams(
-        suite_id=b"BLS12381G1_XMD:SHA-256_SSWU_RO_", hash_fn=hashlib.sha256, xof=False,
-        auxiliary_points=AuxiliaryPoints(None, None, None),
-        field_modulus=Bls12381G1Point._P,
-        subgroup_order=Bls12381G1Point._N,
-        cofactor=Bls12381G1Point._H,
-        a=0,
-        d=0,
-        generator=(0x17F1D3A73197D7942695638C4FA9AC0FC3688C4F9774B905A14E3A3F171BAC586C55E83FF97A1AEFFB3AF00ADB22C6BB,
-                   0x08B3F481E3AAA0F1A09E30ED741D8AE4FCF5E095D5D00AF600DB18CB2C04B3EDD03CC744A2888AE40CAA232946C5E7E1),
-        encoding=Encoding(point_len=32, challenge_len=48),
-        curve_id=curve_id,
-        e2c=e2c,
-    )
-    curve = BandersnatchCurve(params)
-    return CurveVariant(name, curve, type(f"{name}Point", (Bls12381G1Point,), {"__slots__": (), "curve": curve, "_CV": curve_id}))
-
-
-BLS12_381_G1_RO = _bls12_381_g1_variant("BLS12_381_G1_RO", "sswu", _native.CURVE_BLS12_381_G1)
-BLS12_381_G1_NU = _bls12_381_g1_variant("BLS12_381_G1_NU", "sswu_nu", _native.CURVE_BLS12_381_G1_NU)
+_BLS12_381_G1_PARAMS = SuiteParams(
+    suite_id=b"BLS12381G1_XMD:SHA-256_SSWU_RO_", hash_fn=hashlib.sha256, xof=False,
+    auxiliary_points=AuxiliaryPoints(None, None, None),
+    field_modulus=Bls12381G1Point._P,
+    subgroup_order=Bls12381G1Point._N,
+    cofactor=Bls12381G1Point._H,
+    a=0,
+    d=0,
+    generator=(0x17F1D3A73197D7942695638C4FA9AC0FC3688C4F9774B905A14E3A3F171BAC586C55E83FF97A1AEFFB3AF00ADB22C6BB,
+               0x08B3F481E3AAA0F1A09E30ED741D8AE4FCF5E095D5D00AF600DB18CB2C04B3EDD03CC744A2888AE40CAA232946C5E7E1),
+    encoding=Encoding(point_len=32, challenge_len=48),
+    curve_id=_native.CURVE_BLS12_381_G1,
+    e2c="sswu",
+)
+BLS12_381_G1_RO = _variant(Bls12381G1Point, "BLS12_381_G1_RO", _BLS12_381_G1_PARAMS)
+BLS12_381_G1_NU = _variant(Bls12381G1Point, "BLS12_381_G1_NU", _nu(_BLS12_381_G1_PARAMS, _native.CURVE_BLS12_381_G1_NU))
 BLS12_381_G1 = BLS12_381_G1_RO
 
 
@@ -2037,30 +1701,25 @@ BLS12_381_G1 = BLS12_381_G1_RO
 # id, as in the reference.  Encoding(point_len=32, challenge_len=32) are the reference's own figures; it has NO point codec for this curve
 # (point_to_string / string_to_point raise), so no key or proof can be encoded — the VRF classes refuse these two suites (vrf/base.py)
 # and what is served is the point type.  No auxiliary points, not twisted Edwards: RingProofParams refuses them too.
-def _bls12_381_g2_variant(name: str, e2c: str, curve_id: int) -> CurveVariant:
-    fp2 = lambda re, im: Fp2(re, im, Bls12381G2Point._P)  # noqa: E731
-    params = SuiteParams(
-        suite_id=b"BLS12381G2_XMD:SHA-256_SSWU_RO_", hash_fn=hashlib.sha256, xof=False,
-        auxiliary_points=AuxiliaryPoints(None, None, None),
-        field_modulus=Bls12381G2Point._P,
-        subgroup_order=Bls12381G2Point._N,
-        cofactor=Bls12381G2Point._H,
-        a=0,
-        d=0,
-        generator=(fp2(0x024AA2B2F08F0A91260805272DC51051C6E47AD4FA403B02B4510B647AE3D1770BAC0326A805BBEFD48056C8C121BDB8,
-                       0x13E02B6052719F607DACD3A088274F65596BD0D09920B61AB5DA61BBDC7F5049334CF11213945D57E5AC7D055D042B7E),
-                   fp2(0x0CE5D527727D6E118CC9CDC6DA2E351AADFD9BAA8CBDD3A76D429A695160D12C923AC9CC3BACA289E193548608B82801,
-                       0x0606C4A02EA734CC32ACD2B02BC28B99CB3E287E85A763AF267492AB572E99AB3F370D275CEC1DA1AAA9075FF05F79BE)),
-        encoding=Encoding(point_len=32, challenge_len=32),
-        curve_id=curve_id,
-        e2c=e2c,
-    )
-    curve = BandersnatchCurve(params)
-    return CurveVariant(name, curve, type(f"{name}Point", (Bls12381G2Point,), {"__slots__": (), "curve": curve, "_CV": curve_id}))
-
-
-BLS12_381_G2_RO = _bls12_381_g2_variant("BLS12_381_G2_RO", "sswu", _native.CURVE_BLS12_381_G2)
-BLS12_381_G2_NU = _bls12_381_g2_variant("BLS12_381_G2_NU", "sswu_nu", _native.CURVE_BLS12_381_G2_NU)
+_fp2 = lambda re, im: Fp2(re, im, Bls12381G2Point._P)  # noqa: E731
+_BLS12_381_G2_PARAMS = SuiteParams(
+    suite_id=b"BLS12381G2_XMD:SHA-256_SSWU_RO_", hash_fn=hashlib.sha256, xof=False,
+    auxiliary_points=AuxiliaryPoints(None, None, None),
+    field_modulus=Bls12381G2Point._P,
+    subgroup_order=Bls12381G2Point._N,
+    cofactor=Bls12381G2Point._H,
+    a=0,
+    d=0,
+    generator=(_fp2(0x024AA2B2F08F0A91260805272DC51051C6E47AD4FA403B02B4510B647AE3D1770BAC0326A805BBEFD48056C8C121BDB8,
+                    0x13E02B6052719F607DACD3A088274F65596BD0D09920B61AB5DA61BBDC7F5049334CF11213945D57E5AC7D055D042B7E),
+               _fp2(0x0CE5D527727D6E118CC9CDC6DA2E351AADFD9BAA8CBDD3A76D429A695160D12C923AC9CC3BACA289E193548608B82801,
+                    0x0606C4A02EA734CC32ACD2B02BC28B99CB3E287E85A763AF267492AB572E99AB3F370D275CEC1DA1AAA9075FF05F79BE)),
+    encoding=Encoding(point_len=32, challenge_len=32),
+    curve_id=_native.CURVE_BLS12_381_G2,
+    e2c="sswu",
+)
+BLS12_381_G2_RO = _variant(Bls12381G2Point, "BLS12_381_G2_RO", _BLS12_381_G2_PARAMS)
+BLS12_381_G2_NU = _variant(Bls12381G2Point, "BLS12_381_G2_NU", _nu(_BLS12_381_G2_PARAMS, _native.CURVE_BLS12_381_G2_NU))
 BLS12_381_G2 = BLS12_381_G2_RO
 
 
@@ -2068,26 +1727,21 @@ BLS12_381_G2 = BLS12_381_G2_RO
 # uncompressed), 56-byte scalars, SHAKE256 as transcript XOF, hashing to the curve by RFC 9380's edwards448_XOF:SHAKE256_ELL2_RO_ (two
 # field elements) or ..._NU_ (one); both variants share the RO suite id and the generator as Pedersen blinding base, as in the reference.
 # No accumulator base or padding point, so RingProofParams refuses them.
-def _ed448_variant(name: str, e2c: str, curve_id: int) -> CurveVariant:
-    g = (117812161263436946737282484343310064665180535357016373416879082147939404277809514858788439644911793978499419995990477371552926308078495,
-         19)
-    params = SuiteParams(
-        suite_id=b"edwards448_XOF:SHAKE256_ELL2_RO_", hash_fn=hashlib.shake_256, xof=True,
-        auxiliary_points=AuxiliaryPoints(g, None, None),
-        field_modulus=Ed448Point._P,
-        subgroup_order=Ed448Point._N,
-        cofactor=4,
-        a=1,
-        d=-39081,
-        generator=g,
-        encoding=Encoding(point_len=56, challenge_len=64, uncompressed=True),
-        curve_id=curve_id,
-        e2c=e2c,
-    )
-    curve = BandersnatchCurve(params)
-    return CurveVariant(name, curve, type(f"{name}Point", (Ed448Point,), {"__slots__": (), "curve": curve, "_CV": curve_id}))
-
-
-Ed448_RO = _ed448_variant("Ed448_RO", "ell2", _native.CURVE_ED448_RO)
-Ed448_NU = _ed448_variant("Ed448_NU", "ell2_nu", _native.CURVE_ED448_NU)
+_ED448_G = (117812161263436946737282484343310064665180535357016373416879082147939404277809514858788439644911793978499419995990477371552926308078495,
+            19)
+_ED448_PARAMS = SuiteParams(
+    suite_id=b"edwards448_XOF:SHAKE256_ELL2_RO_", hash_fn=hashlib.shake_256, xof=True,
+    auxiliary_points=AuxiliaryPoints(_ED448_G, None, None),
+    field_modulus=Ed448Point._P,
+    subgroup_order=Ed448Point._N,
+    cofactor=4,
+    a=1,
+    d=-39081,
+    generator=_ED448_G,
+    encoding=Encoding(point_len=56, challenge_len=64, uncompressed=True),
+    curve_id=_native.CURVE_ED448_RO,
+    e2c="ell2",
+)
+Ed448_RO = _variant(Ed448Point, "Ed448_RO", _ED448_PARAMS)
+Ed448_NU = _variant(Ed448Point, "Ed448_NU", _nu(_ED448_PARAMS, _native.CURVE_ED448_NU))
 Ed448 = Ed448_RO

@@ -64,7 +64,7 @@ def dec_points(cv, values) -> list:
         blobs.append(v)
     if not blobs:
         return []
-    wide = getattr(cv.point_type, "_WIDE", False)       # Ed448: 112-byte x || y, checked by dr_ed448_decode_points(check = 1)
+    wide = cv.point_type._WIDE       # Ed448: 112-byte x || y, checked by dr_ed448_decode_points(check = 1)
     if wide:
         xy, flags = runtime.context().ed448_decode_points(b"".join(blobs), True)
     else:

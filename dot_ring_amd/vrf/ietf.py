@@ -37,7 +37,7 @@ class IetfVRF(VRF):
             raise ValueError("batch arguments must have equal lengths")
         if count == 0:
             return []
-        if os.environ.get("DOTRING_NATIVE_HOST", "1") == "0" or getattr(cls.cv.point_type, "_WIDE", False):
+        if os.environ.get("DOTRING_NATIVE_HOST", "1") == "0" or cls.cv.point_type._WIDE:
             # (Ed448: 56-byte scalars and 112-byte points, which dr_ietf_prove_batch does not carry)
             return cls._prove_batch_python(alphas, secret_keys, additional_data, salts)
         cv = cls.cv

@@ -119,7 +119,7 @@ class PedersenVRF(VRF):
         if count == 0:
             return []
         if (os.environ.get("DOTRING_NATIVE_HOST", "1") == "0" or not cls.cv.curve.params.auxiliary_points.blinding_base
-                or getattr(cls.cv.point_type, "_WIDE", False)):          # (Ed448: dr_pedersen_prove_batch carries 32-byte scalars)
+                or cls.cv.point_type._WIDE):          # (Ed448: dr_pedersen_prove_batch carries 32-byte scalars)
             from ..pipeline import drive
 
             return drive(cls._prove_gen(alphas, secret_keys, additional_data, salts))
@@ -195,7 +195,7 @@ class PedersenVRF(VRF):
         if salts is None:
             salts = [b""] * len(proofs)
         if (os.environ.get("DOTRING_NATIVE_HOST", "1") != "0" and cv.curve.params.auxiliary_points.blinding_base
-                and not getattr(cv.point_type, "_WIDE", False)):
+                and not cv.point_type._WIDE):
             try:
                 if not (len(proofs) == len(inputs) == len(additional_data) == len(salts)):
                     return False

@@ -1,7 +1,9 @@
-"""Baby JubJub against JubJub (same hash, cofactor 8, try-and-increment and protocols; another field and a = 1 instead of -1): Tiny /
-Thin / Pedersen prove_batch, Thin / Pedersen batch_verify at 1024 and 4096 proofs, one fresh process, a warm-up of every call first,
-the two suites alternating, host clock around the (synchronous) calls; prints both rates and their ratio
-(python tools/babyjubjub_suite_timing.py [reps]).  Under rocprofv3 --kernel-trace --stats, BJJ_ONLY=1 times Baby JubJub alone."""
+"""One suite against a yardstick suite with the same protocols: Tiny / Thin / Pedersen prove_batch, Thin / Pedersen batch_verify and
+encode_to_curve_batch at 1024 and 4096 proofs, one fresh process, a warm-up of every call first, the two suites alternating, host clock
+around the (synchronous) calls; prints both rates and their ratio:
+    python tools/suite_timing.py SUITE [YARDSTICK] [reps]
+The pairs the design notes quote: Bandersnatch_SW Bandersnatch, Ed25519 JubJub, P256 Ed25519, BabyJubJub JubJub, Secp256k1 P256.
+Without a yardstick (under rocprofv3 --kernel-trace --stats, say) the suite is timed alone."""
 import os
 import sys
 import time
@@ -9,8 +11,11 @@ import time
 sys.path.insert(0, os.getcwd())
 import dot_ring_amd as d  # noqa: E402
 
-REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 3
-SUITES = [d.BabyJubJub] if os.environ.get("BJJ_ONLY") else [d.JubJub, d.BabyJubJub]
+NAMES = [a for a in sys.argv[1:] if not a.isdigit()]
+REPS = next((int(a) for a in sys.argv[1:] if a.isdigit()), 3)
+if not 1 <= len(NAMES) <= 2:
+    raise SystemExit(__doc__)
+SUITES = [getattr(d, n) for n in reversed(NAMES)]           # the yardstick first, as the per-suite tools had it
 
 
 def work(cv, B):
@@ -28,6 +33,7 @@ def work(cv, B):
         "Pedersen.prove_batch": lambda: ped.prove_batch(als, sks, ads),
         "Thin.batch_verify": lambda: thin.batch_verify(thin_proofs, pks, als, ads),
         "Pedersen.batch_verify": lambda: ped.batch_verify(ped_proofs, als, ads),
+        "encode_to_curve_batch": lambda: cv.point_type.encode_to_curve_batch(als),
     }
 
 
@@ -48,7 +54,8 @@ def main():
             rates = {k: B / v for k, v in best.items()}
             line = " | ".join(f"{k} {rates[k]:9.0f} /s ({best[k] * 1e3:7.1f} ms)" for k in rates)
             if len(rates) == 2:
-                line += f" | BabyJubJub/JubJub {rates['BabyJubJub'] / rates['JubJub']:.3f}"
+                base, suite = (cv.name for cv in SUITES)
+                line += f" | {suite}/{base} {rates[suite] / rates[base]:.3f}"
             print(f"B={B:5d} {op:22s} {line}", flush=True)
 
 
