@@ -324,7 +324,7 @@ def hash_to_field_batch(suite: VrfSuiteStruct, msgs) -> bytes:
 
 
 class _Wide(NamedTuple):
-    """One wide suite (csrc/capi_wide.hpp) as its dr_<suite>_* entry points see it: byte widths, selftest record count, the NU variant."""
+    """One wide suite (csrc/capi_suite.hpp) as its dr_<suite>_* entry points see it: byte widths, selftest record count, the NU variant."""
     elem: int           # a hashed field element
     point: int          # x || y
     scalar: int

@@ -1,17 +1,17 @@
 // libdotring_hip.so — C ABI, part 7 of 8: the BLS12_381_G2 suites (DR_CURVE_BLS12_381_G2 / DR_CURVE_BLS12_381_G2_NU; the reference's
 // specs/bls12_381_G2.py).  Coordinates are elements of Fq2, c0 || c1, 48 + 48 bytes little-endian, canonical standard form; points are
 // affine x || y, 192 bytes, 192 zero bytes the identity.  None of it goes through the 64-byte paths of capi_core.hip but through
-// capi_wide.hpp.  The kernels are kernels_g2_h2c.hip.h (the complete projective law over fq2_28.hip.h); the host does hash_to_field
+// capi_suite.hpp.  The kernels are kernels_g2_h2c.hip.h (the complete projective law over fq2_28.hip.h); the host does hash_to_field
 // (expand_message_xmd over SHA-256, m = 2, L = 64) on the worker threads and checks that inputs are canonical.  Scalars are 96 bytes used
 // AS THEY ARE: E(Fq2) has order h2 r (762 bits), and its points need not lie in G2.
-#include "capi_wide.hpp"
+#include "capi_suite.hpp"
 #include "kernels_g2_h2c.hip.h"
 
 using namespace dri;
 
 namespace {
 
-struct Blsg2Suite {                     // (no msm_groups; the flag-returning launch is check_points, which gives no points back)
+struct Blsg2Suite : SuiteDefaults {                     // (no msm_groups; the flag-returning launch is check_points, which gives no points back)
     static constexpr size_t fe_bytes = 48, elem_bytes = 96, pt_bytes = 192, scalar_bytes = 96, limb_bytes = 4 * 2 * dr::L28;
     static constexpr int variant_ro = DR_CURVE_BLS12_381_G2, variant_nu = DR_CURVE_BLS12_381_G2_NU;
     static constexpr const char* variant_names = "DR_CURVE_BLS12_381_G2 or DR_CURVE_BLS12_381_G2_NU";
@@ -53,25 +53,26 @@ struct Blsg2Suite {                     // (no msm_groups; the flag-returning la
 }  // namespace
 
 int dr_blsg2_hash_to_field_batch(int variant, const uint8_t* msgs, const uint64_t* off, size_t count, uint8_t* out) {
-    return wide_hash_to_field_batch<Blsg2Suite>(variant, msgs, off, count, out);
+    return hash_to_field_batch<Blsg2Suite>(variant, msgs, off, count, out);
 }
 int dr_blsg2_map_to_curve(dr_ctx* ctx, const uint8_t* us, size_t n, int per_item, int clear, uint8_t* out_xy, uint8_t* ok) {
-    return wide_map_to_curve<Blsg2Suite>(ctx, us, n, per_item, clear, out_xy, ok);
+    return map_to_curve<Blsg2Suite>(ctx, us, n, per_item, clear, out_xy, ok);
 }
 int dr_blsg2_encode_to_curve_batch(dr_ctx* ctx, int variant, const uint8_t* msgs, const uint64_t* off, const uint8_t* salts,
                                    const uint64_t* salt_off, size_t count, uint8_t* out_xy) {
-    return wide_encode_to_curve_batch<Blsg2Suite>(ctx, variant, msgs, off, salts, salt_off, count, out_xy);
+    return encode_to_curve_batch<Blsg2Suite>(ctx, variant, msgs, off, salts, salt_off, count, out_xy);
 }
 int dr_blsg2_scalar_mul_batch(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy) {
-    return wide_scalar_mul_batch<Blsg2Suite>(ctx, pts_xy, scalars, n, out_xy);
+    TRY(use_ctx(ctx));
+    return scalar_mul_batch<Blsg2Suite>(ctx, pts_xy, scalars, n, out_xy);
 }
 int dr_blsg2_check_points(dr_ctx* ctx, int subgroup, const uint8_t* pts_xy, size_t n, uint8_t* ok) {
-    return wide_flagged<Blsg2Suite>(ctx, pts_xy, n, nullptr, ok, [&] {
+    return flagged_round<Blsg2Suite>(ctx, pts_xy, n, nullptr, ok, [&] {
         const auto kernel = subgroup ? dr::k_blsg2_check_points<dr::G2H_CHECK_SUBGROUP> : dr::k_blsg2_check_points<dr::G2H_CHECK_CURVE>;
         hipLaunchKernelGGL(kernel, dim3(div_up(n, dr::G2H_BLOCK)), dim3(dr::G2H_BLOCK), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
                            ctx->io_c.as<uint32_t>(), (uint32_t)n);
     });
 }
 int dr_blsg2_field_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
-    return wide_field_selftest<Blsg2Suite>(ctx, a_limbs, b_limbs, n, out, flags);
+    return field_selftest<Blsg2Suite>(ctx, a_limbs, b_limbs, n, out, flags);
 }

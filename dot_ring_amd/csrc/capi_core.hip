@@ -1,6 +1,6 @@
 // libdotring_hip.so — C ABI (include/dotring_hip.h), part 1 of 8: contexts, device memory, profiling, seam A (the
 // Bandersnatch / twisted Edwards kernels of kernels_bsn.hip.h) and hash-to-curve.  See capi_internal.hpp for the layout.
-#include "capi_internal.hpp"
+#include "capi_suite.hpp"
 #include "hostsmall.hpp"
 #include "kernels_sw.hip.h"
 #include "kernels_ed25519.hip.h"
@@ -451,22 +451,15 @@ int glv_split_scalars(const uint8_t* scalars, size_t n, std::vector<uint32_t>& o
 int sw_map_points(dr_ctx* ctx, bool to_te, const uint8_t* in_xy, size_t n, uint8_t* out_xy, unsigned per) {
     if (n == 0) return DR_OK;
     if (per < 1 || per > (unsigned)dr::SW_MAP_MAX) return fail(DR_ERR_INVALID, "points per lane out of range");
-    TRY(ctx->io_a.reserve(n * 64));
-    TRY(ctx->io_c.reserve(n * 64));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, in_xy, n * 64, hipMemcpyHostToDevice, ctx->stream));
     const size_t lanes = (n + per - 1) / per;
-    TRY(launch(ctx, to_te ? "k_sw_to_te" : "k_te_to_sw", [&] {
+    return io_round(ctx, {n * 64, 0, n * 64}, {{&ctx->io_a, 0, in_xy, n * 64}}, to_te ? "k_sw_to_te" : "k_te_to_sw", [&] {
         if (to_te)
             hipLaunchKernelGGL(dr::k_sw_map<true>, dim3(div_up(lanes, 64)), dim3(64), 0, ctx->stream, ctx->io_a.as<uint32_t>(), ctx->io_c.as<uint32_t>(),
                                (uint32_t)n, (uint32_t)per);
         else
             hipLaunchKernelGGL(dr::k_sw_map<false>, dim3(div_up(lanes, 64)), dim3(64), 0, ctx->stream, ctx->io_a.as<uint32_t>(), ctx->io_c.as<uint32_t>(),
                                (uint32_t)n, (uint32_t)per);
-    }));
-    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_c.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->prof) TRY(prof_collect(ctx));
-    return DR_OK;
+    }, {{out_xy, &ctx->io_c, 0, n * 64}});
 }
 int suite_coords(dr_ctx* ctx, const drh::VrfSuite& su, const uint8_t* te_xy, size_t n, unsigned per, std::vector<uint8_t>& store,
                  const uint8_t** out) {
@@ -490,16 +483,36 @@ int sw_boundary(dr_ctx* ctx, const uint8_t* sw_in, size_t n_in, uint8_t* sw_out,
 }
 }  // namespace
 
-// ---- the native suites: Ed25519 (kernels_ed25519.hip.h), P-256 (kernels_p256.hip.h) and Baby JubJub (kernels_bjj.hip.h).  Every call
-// runs on the kernels: there is no host route for these curves, and nothing here touches the BLS12-381 field of the other curves.  Secrets
-// pass through io_a / io_b / io_c only, which ctx_wipe_scratch covers.  Points are affine x || y.  Each suite is one description below (its
-// kernels, launch names, base field, identity and encoding widths); every operation is one template over it.
+// ---- the native suites: Ed25519 (kernels_ed25519.hip.h), P-256 (kernels_p256.hip.h), Baby JubJub (kernels_bjj.hip.h), secp256k1
+// (kernels_secp256k1.hip.h) and Curve25519 (kernels_curve25519.hip.h).  Every call runs on the kernels: there is no host route for these
+// curves, and nothing here touches the BLS12-381 field of the other curves.  Secrets pass through io_a / io_b / io_c only, which
+// ctx_wipe_scratch covers.  Points are affine x || y.  Each suite is one description below (its kernels, launch names, base field, identity
+// and encoding widths) of the shape capi_suite.hpp lists; every operation is one of that header's templates over it.
 namespace {
-struct NoConsts {                      // the suites with no device constants to load first
-    static int consts_ready(dr_ctx*) { return DR_OK; }
-    static constexpr bool flagged = false;     // whether the kernels carry an identity flag word beside each point (Curve25519 alone)
+// what the five descriptions share: 64-byte points, 32-byte scalars and field elements, nine-limb selftest images, the kernels' limits
+template <class S>
+struct Native256 : SuiteDefaults {
+    static constexpr size_t fe_bytes = 32, elem_bytes = 32, pt_bytes = 64, scalar_bytes = 32, limb_bytes = 36;
+    static constexpr size_t max_map = 1ull << 30, max_points = 1ull << 31, max_decode = 1ull << 31;
+    static constexpr bool limit_first = false, decode_gives_points = true, decode_checks_canonical = false;
+    static bool canonical(const uint8_t* p) {
+        uint64_t v[4];
+        drh::load_le32(p, v);
+        return !drh::Mod256::geq(v, S::field().m);
+    }
+    // the maps of RFC 9380 for n items of per_item (1 or 2) field elements each: one launch of the suite's map kernel (S::map, profiled as
+    // S::k_map), the sum of each item's images out (on Ed25519 with the cofactor cleared)
+    static size_t map_flag_words(size_t n, size_t) { return n; }
+    static int map_launch(dr_ctx* ctx, size_t n, size_t, int per_item, int) {
+        return launch(ctx, S::k_map, [&] {
+            hipLaunchKernelGGL(S::map, dim3(div_up(n, S::block)), dim3(S::block), 0, ctx->stream, ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(),
+                               ctx->io_c.as<uint32_t>(), (uint32_t)n, (uint32_t)per_item);
+        });
+    }
 };
-struct Ed25519Suite : NoConsts {
+struct Ed25519Suite : Native256<Ed25519Suite> {
+    static constexpr auto map = dr::k_ed25519_map_to_curve;
+    static constexpr const char* k_map = "k_ed25519_map_to_curve";
     static constexpr auto scalar_mul = dr::k_ed_scalar_mul;
     static constexpr auto msm_groups = dr::k_ed_msm_groups;
     static constexpr auto dec_tai = dr::k_ed_decode_points<dr::ED_DEC_TAI>, dec_check = dr::k_ed_decode_points<dr::ED_DEC_CHECK>,
@@ -510,7 +523,9 @@ struct Ed25519Suite : NoConsts {
     static const drh::Mod256& field() { return drh::mod_p25519(); }
     static constexpr size_t identity_y = 1, enc_bytes = 32, rec_bytes = 32, tai_bytes = 32;   // identity (0, identity_y); encoding, decoder record, try-and-increment candidate
 };
-struct P256Suite : NoConsts {
+struct P256Suite : Native256<P256Suite> {
+    static constexpr auto map = dr::k_p256_map_to_curve;
+    static constexpr const char* k_map = "k_p256_map_to_curve";
     static constexpr auto scalar_mul = dr::k_p256_scalar_mul;
     static constexpr auto msm_groups = dr::k_p256_msm_groups;
     static constexpr auto dec_tai = dr::k_p256_decode_points<dr::P256_DEC_TAI>, dec_check = dr::k_p256_decode_points<dr::P256_DEC_CHECK>,
@@ -532,7 +547,9 @@ struct P256Sec1Suite : P256Suite {
 static_assert(P256Sec1Suite::dec_codec == P256Sec1Suite::dec_check, "one SEC1 decoder: a caller of either gets this format, never P256_TAI's");
 // secp256k1 (curves 6 and 7): no try-and-increment, so dec_tai is the checking decoder again and encode_to_curve_msgs never takes that
 // branch for these curves (they hash with k_secp256k1_map_to_curve)
-struct Secp256k1Suite : NoConsts {
+struct Secp256k1Suite : Native256<Secp256k1Suite> {
+    static constexpr auto map = dr::k_secp256k1_map_to_curve;
+    static constexpr const char* k_map = "k_secp256k1_map_to_curve";
     static constexpr auto scalar_mul = dr::k_secp256k1_scalar_mul;
     static constexpr auto msm_groups = dr::k_secp256k1_msm_groups;
     static constexpr auto dec_tai = dr::k_secp256k1_decode_points<dr::K1_DEC_CHECK>, dec_check = dr::k_secp256k1_decode_points<dr::K1_DEC_CHECK>,
@@ -613,8 +630,7 @@ int bjj_consts_ready(dr_ctx* ctx) {
     ctx->bjj_ready = true;
     return DR_OK;
 }
-struct BjjSuite {
-    static constexpr bool flagged = false;
+struct BjjSuite : Native256<BjjSuite> {
     static constexpr auto scalar_mul = dr::k_bjj_scalar_mul;
     static constexpr auto msm_groups = dr::k_bjj_msm_groups;
     static constexpr auto dec_tai = dr::k_bjj_decode_points<dr::BJJ_DEC_TAI>, dec_check = dr::k_bjj_decode_points<dr::BJJ_DEC_CHECK>,
@@ -629,7 +645,7 @@ struct BjjSuite {
 // Curve25519_RO / Curve25519_NU (curves 13 and 14, kernels_curve25519.hip.h): Ed25519's group under Montgomery coordinates u || v, 64 bytes
 // encoded as they are.  The kernels take and give an identity flag word per point (`flagged`); between the launches, where a point is 64
 // bytes and nothing else, the identity is drh::mont_is_identity's 64 bytes of 0xff.  No try-and-increment: dec_tai is the checking decoder.
-struct Curve25519Suite : NoConsts {
+struct Curve25519Suite : Native256<Curve25519Suite> {
     static constexpr bool flagged = true;
     static constexpr auto scalar_mul = dr::k_c25519_scalar_mul;
     static constexpr auto msm_groups = dr::k_c25519_msm_groups;
@@ -640,6 +656,13 @@ struct Curve25519Suite : NoConsts {
                                 *k_decode = "k_c25519_decode_points";
     static const drh::Mod256& field() { return drh::mod_p25519(); }
     static constexpr size_t identity_y = 0, enc_bytes = 64, rec_bytes = 64, tai_bytes = 64;   // (identity_y does not apply: native_identity)
+    // Elligator 2, times the cofactor 8 unless `clear` is 0; every canonical input has a value, and the flag says that it is the identity
+    static int map_launch(dr_ctx* ctx, size_t n, size_t, int per_item, int clear) {
+        return launch(ctx, "k_curve25519_map_to_curve", [&] {
+            hipLaunchKernelGGL(dr::k_curve25519_map_to_curve, dim3(div_up(n, block)), dim3(block), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
+                               ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n, (uint32_t)per_item, clear ? 1u : 0u);
+        });
+    }
 };
 // the identity as the 64 bytes the host path carries: (0, identity_y), 64 zero bytes on the Weierstrass curves, 64 bytes of 0xff on Curve25519
 template <class S>
@@ -665,102 +688,12 @@ bool on_native(int cv, int& rc, F&& f) {
         default: return false;
     }
 }
-// n points, their coordinates checked against S's field, and n scalars to io_a / io_b, one launch (`go`, profiled as `name`) into io_c,
-// n_out points back
-// The identity flags of a flagged suite's call when the caller spells them out (the dr_curve25519_* entry points): one byte per point in
-// (null: none is the identity) and out.  Without them the identity travels inside the 64 bytes (drh::mont_is_identity).
-struct NativeFlags {
-    const uint8_t* in = nullptr;
-    uint8_t* out = nullptr;
-};
-template <class S, class F>
-int native_run(S, dr_ctx* ctx, const char* name, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, size_t n_out, uint8_t* out_xy, F&& go,
-               const NativeFlags* fl = nullptr) {
-    if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
-    if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
-    // a flagged suite: the identities among the points become flag words behind the points in io_a (their 64 bytes zeros), and the flag
-    // words the kernel leaves behind its results in io_c become identities again; with the caller's own flags (fl) the points go as they
-    // are, so that 64 bytes of 0xff are refused below like every other coordinate at or above p
-    std::vector<uint8_t> clean;
-    std::vector<uint32_t> flags_in, flags_out;
-    if constexpr (S::flagged) {
-        flags_in.assign(n, 0);
-        for (size_t i = 0; fl && fl->in && i < n; i++) {
-            if (!fl->in[i]) continue;
-            if (clean.empty()) clean.assign(pts_xy, pts_xy + n * 64);      // (a flagged point's 64 bytes are ignored)
-            std::memset(clean.data() + 64 * i, 0, 64);
-            flags_in[i] = 1;
-        }
-        for (size_t i = 0; !fl && i < n; i++) {
-            if (!drh::mont_is_identity(pts_xy + 64 * i)) continue;
-            if (clean.empty()) clean.assign(pts_xy, pts_xy + n * 64);
-            std::memset(clean.data() + 64 * i, 0, 64);
-            flags_in[i] = 1;
-        }
-        if (!clean.empty()) pts_xy = clean.data();
-    }
-    for (size_t i = 0; i < 2 * n; i++) {
-        uint64_t v[4];
-        drh::load_le32(pts_xy + 32 * i, v);
-        if (drh::Mod256::geq(v, S::field().m)) return fail(DR_ERR_INVALID, "point coordinate is not a canonical field element");
-    }
-    TRY(ctx->io_a.reserve(n * (S::flagged ? 68 : 64)));
-    TRY(ctx->io_b.reserve(n * 32));
-    TRY(ctx->io_c.reserve(n_out * (S::flagged ? 68 : 64)));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, pts_xy, n * 64, hipMemcpyHostToDevice, ctx->stream));
-    if constexpr (S::flagged) HIP_TRY(hipMemcpyAsync(ctx->io_a.as<uint8_t>() + n * 64, flags_in.data(), n * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->io_b.p, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    TRY(launch(ctx, name, go));
-    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_c.p, n_out * 64, hipMemcpyDeviceToHost, ctx->stream));
-    if constexpr (S::flagged) {
-        flags_out.resize(n_out);
-        HIP_TRY(hipMemcpyAsync(flags_out.data(), ctx->io_c.as<uint8_t>() + n_out * 64, n_out * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->prof) TRY(prof_collect(ctx));
-    for (size_t i = 0; i < flags_out.size(); i++) {
-        if (fl) fl->out[i] = flags_out[i] ? 1 : 0;                         // (the kernel stored 64 zero bytes)
-        else if (flags_out[i]) native_identity<S>(out_xy + 64 * i);
-    }
-    return DR_OK;
-}
-template <class S>
-int native_scalar_mul_batch(S, dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy, const NativeFlags* fl = nullptr) {
-    if (n == 0) return DR_OK;
-    return native_run(S{}, ctx, S::k_scalar_mul, pts_xy, scalars, n, n, out_xy, [&] {
-        if constexpr (S::flagged)
-            hipLaunchKernelGGL(S::scalar_mul, dim3(div_up(n, S::block)), dim3(S::block), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
-                               ctx->io_b.as<uint32_t>(), ctx->io_a.as<uint32_t>() + n * 16, ctx->io_c.as<uint32_t>(),
-                               ctx->io_c.as<uint32_t>() + n * 16, (uint32_t)n);
-        else
-            hipLaunchKernelGGL(S::scalar_mul, dim3(div_up(n, S::block)), dim3(S::block), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
-                               ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
-    }, fl);
-}
-template <class S>
-int native_msm_groups(S, dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy,
-                      const NativeFlags* fl = nullptr) {
-    if (groups == 0) return DR_OK;
-    if (m == 0 || m > 64) return fail(DR_ERR_INVALID, "group size must be in 1..64");
-    uint32_t mpad = 1;
-    while (mpad < m) mpad <<= 1;
-    const uint32_t per_block = S::block / mpad;
-    return native_run(S{}, ctx, S::k_msm_groups, pts_xy, scalars, groups * m, groups, out_xy, [&] {
-        if constexpr (S::flagged)
-            hipLaunchKernelGGL(S::msm_groups, dim3(div_up(groups, per_block)), dim3(S::block), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
-                               ctx->io_b.as<uint32_t>(), ctx->io_a.as<uint32_t>() + groups * m * 16, ctx->io_c.as<uint32_t>(),
-                               ctx->io_c.as<uint32_t>() + groups * 16, (uint32_t)groups, (uint32_t)m, mpad);
-        else
-            hipLaunchKernelGGL(S::msm_groups, dim3(div_up(groups, per_block)), dim3(S::block), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
-                               ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)groups, (uint32_t)m, mpad);
-    }, fl);
-}
 // fixed bases through the grouped kernel, each group's terms the m bases: no window table.  te_fixed_base_groups checked the arguments.
 template <class S>
 int native_fixed_base_groups(S, dr_ctx* ctx, const uint8_t* bases_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy) {
     std::vector<uint8_t> pts(groups * m * 64);
     for (size_t g = 0; g < groups; g++) std::memcpy(pts.data() + 64 * m * g, bases_xy, 64 * m);
-    return native_msm_groups(S{}, ctx, pts.data(), scalars, groups, m, out_xy);
+    return msm_groups<S>(ctx, pts.data(), scalars, groups, m, out_xy);
 }
 // one MSM: groups of 64 terms in one launch, then the partial sums with scalar 1, 64 at a time, until one is left.  The host copy of
 // the scalars is wiped after every launch, a failed one included.
@@ -778,7 +711,7 @@ int native_msm(S, dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, si
         sc.resize(parts * m * 32, 0);
         for (size_t i = n; i < parts * m; i++) native_identity<S>(pts.data() + 64 * i);       // padding: 0 * identity
         part.resize(parts * 64);
-        const int rc = native_msm_groups(S{}, ctx, pts.data(), sc.data(), parts, m, parts == 1 ? out_xy : part.data());
+        const int rc = msm_groups<S>(ctx, pts.data(), sc.data(), parts, m, parts == 1 ? out_xy : part.data());
         explicit_bzero(sc.data(), sc.size());
         if (rc != DR_OK || parts == 1) return rc;
         pts.swap(part);
@@ -787,74 +720,35 @@ int native_msm(S, dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, si
         for (size_t i = 0; i < n; i++) sc[32 * i] = 1;
     }
 }
-// `kernel`: one of the suite's decoder instances, S::dec_codec, S::dec_check or S::dec_tai
-template <class S>
-int native_decode_points(S, dr_ctx* ctx, decltype(S::dec_tai) kernel, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
-    TRY(use_ctx(ctx));
-    if (n == 0) return DR_OK;
-    if (!enc || !out_xy || !ok) return fail(DR_ERR_INVALID, "null buffer");
-    if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
-    TRY(S::consts_ready(ctx));
-    std::vector<uint8_t> rec;
-    if (S::rec_bytes != S::enc_bytes) {                   // each encoding zero-padded to its record
-        rec.assign(n * S::rec_bytes, 0);
-        for (size_t i = 0; i < n; i++) std::memcpy(rec.data() + S::rec_bytes * i, enc + S::enc_bytes * i, S::enc_bytes);
-        enc = rec.data();
-    }
-    TRY(ctx->io_a.reserve(n * S::rec_bytes));
-    TRY(ctx->io_b.reserve(n * 64));
-    TRY(ctx->io_c.reserve(n * 4));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, enc, n * S::rec_bytes, hipMemcpyHostToDevice, ctx->stream));
-    TRY(launch(ctx, S::k_decode, [&] {
-        hipLaunchKernelGGL(kernel, dim3(div_up(n, S::block)), dim3(S::block), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
-                           ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
-    }));
-    return finish_flagged(ctx, out_xy, ctx->io_b.p, n * 64, ctx->io_c.p, n, ok);
-}
-// the field selftests: n pairs of raw 9-limb images in, S::selftest_records results of 32 bytes and one flag byte per pair out
-template <class S>
-int native_field_selftest(S, dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
-    TRY(use_ctx(ctx));
-    if (n == 0) return DR_OK;
-    if (!a_limbs || !b_limbs || !out || !flags) return fail(DR_ERR_INVALID, "null buffer");
-    if (n >= (1ull << 24)) return fail(DR_ERR_INVALID, "batch too large");
-    TRY(S::consts_ready(ctx));
-    const size_t rec = (size_t)S::selftest_records * 32;
-    TRY(ctx->io_a.reserve(n * 72));
-    TRY(ctx->io_b.reserve(n * rec));
-    TRY(ctx->io_c.reserve(n * 4));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, a_limbs, n * 36, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.as<uint8_t>() + n * 36, b_limbs, n * 36, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(S::field_selftest, dim3(div_up(n, 64)), dim3(64), 0, ctx->stream, ctx->io_a.as<int32_t>(),
-                       (const int32_t*)(ctx->io_a.as<uint8_t>() + n * 36), (uint32_t)n, ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    std::vector<uint32_t> fl(n);
-    TRY(download_flagged(ctx, out, ctx->io_b.p, n * rec, ctx->io_c.p, fl));
-    for (size_t i = 0; i < n; i++) flags[i] = (uint8_t)fl[i];
-    return DR_OK;
-}
 }  // namespace
+
+// k P for one term of a small batch on a host core: the affine point (canonical: checked by the caller), the scalar reduced mod n as the
+// kernels do, then the fixed-schedule multiplication (hostsmall.hpp: te_mul_secret; the scalars may be secret keys) and the wipe of the
+// reduced scalar.  The caller wipes the product once it has used it.
+static drh::TeExt te_mul_term_host(const drh::TeCurveHost& hc, const drh::TeHostParams& hp, const uint8_t* xy, const uint8_t* scalar) {
+    drh::TeExt P;
+    uint64_t k[4];
+    (void)drh::te_load_affine(xy, P);
+    hc.n.reduce_bytes(scalar, 32, false, k);
+    drh::TeExt r = drh::te_mul_secret(P, k, hp);
+    explicit_bzero(k, sizeof k);
+    return r;
+}
 
 int te_scalar_mul_batch(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy) {
     TRY(use_ctx(ctx));
     TRY(check_curve(cv));
-    if (int rc; on_native(cv, rc, [&](auto S) { return native_scalar_mul_batch(S, ctx, pts_xy, scalars, n, out_xy); })) return rc;
+    if (int rc; on_native(cv, rc, [&](auto S) { return scalar_mul_batch<decltype(S)>(ctx, pts_xy, scalars, n, out_xy); })) return rc;
     if (n == 0) return DR_OK;
     if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
     TRY(check_fr_elems(pts_xy, 2 * n, "point"));
     if (n <= drh::small_host_max() && !drh::te_curve(cv)->sw) {
-        // a few multiplications (a key pair, a proof's handful): ~0.09 ms each on a host core against a ~1 ms kernel chain.  The scalars may
-        // be secret keys: fixed-schedule multiplication (hostsmall.hpp: te_mul_secret), reduced mod n first as the kernels do
+        // a few multiplications (a key pair, a proof's handful): ~0.09 ms each on a host core against a ~1 ms kernel chain
         const drh::TeCurveHost* hc = drh::te_curve(cv);
         const drh::TeHostParams hp = drh::te_host_params(*hc);
         drh::parallel_for(n, [&](size_t i) {
-            drh::TeExt P;
-            uint64_t k[4];
-            (void)drh::te_load_affine(pts_xy + 64 * i, P);                    // (canonical: checked above)
-            hc->n.reduce_bytes(scalars + 32 * i, 32, false, k);
-            drh::TeExt r = drh::te_mul_secret(P, k, hp);
+            drh::TeExt r = te_mul_term_host(*hc, hp, pts_xy + 64 * i, scalars + 32 * i);
             drh::te_store_affine(r, out_xy + 64 * i);
-            explicit_bzero(k, sizeof k);
             explicit_bzero(&r, sizeof r);
         }, 1);
         return DR_OK;
@@ -862,29 +756,14 @@ int te_scalar_mul_batch(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_
     if (drh::te_curve(cv)->glv && n < 16384) {       // latency-bound launch: halve the chain with GLV on lane pairs
         std::vector<uint32_t> split;
         TRY(glv_split_scalars(scalars, n, split));
-        TRY(ctx->io_a.reserve(n * 64));
-        TRY(ctx->io_b.reserve(n * 48));
-        TRY(ctx->io_c.reserve(n * 64));
-        HIP_TRY(hipMemcpyAsync(ctx->io_a.p, pts_xy, n * 64, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(ctx->io_b.p, split.data(), n * 48, hipMemcpyHostToDevice, ctx->stream));
-        TRY(launch(ctx, "k_bsn_scalar_mul", [&] {
+        return io_round(ctx, {n * 64, n * 48, n * 64}, {{&ctx->io_a, 0, pts_xy, n * 64}, {&ctx->io_b, 0, split.data(), n * 48}}, "k_bsn_scalar_mul", [&] {
             hipLaunchKernelGGL(dr::k_bsn_scalar_mul_glv<false>, dim3(div_up(2 * n, dr::BSN_BLOCK)), dim3(dr::BSN_BLOCK), 0, ctx->stream,
                                ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
-        }));
-        HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_c.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->prof) TRY(prof_collect(ctx));
-        return DR_OK;
+        }, {{out_xy, &ctx->io_c, 0, n * 64}});
     }
-    TRY(ctx->io_a.reserve(n * 64));
-    TRY(ctx->io_b.reserve(n * 32));
-    TRY(ctx->io_c.reserve(n * 64));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, pts_xy, n * 64, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->io_b.p, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    TRY(te_scalar_mul_batch_dev(ctx, cv, ctx->io_a.p, ctx->io_b.p, n, ctx->io_c.p));
-    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_c.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return DR_OK;
+    // the device-resident call on the context's own buffers: it launches, waits and collects the timers itself
+    return io_round(ctx, {n * 64, n * 32, n * 64}, {{&ctx->io_a, 0, pts_xy, n * 64}, {&ctx->io_b, 0, scalars, n * 32}}, nullptr,
+                    [&] { return te_scalar_mul_batch_dev(ctx, cv, ctx->io_a.p, ctx->io_b.p, n, ctx->io_c.p); }, {{out_xy, &ctx->io_c, 0, n * 64}});
 }
 int dr_bsn_scalar_mul_batch(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy) {
     return te_scalar_mul_batch(ctx, dr::CV_BANDERSNATCH, pts_xy, scalars, n, out_xy);
@@ -901,49 +780,30 @@ int dr_te_scalar_mul_batch(dr_ctx* ctx, int curve, const uint8_t* pts_xy, const 
 int te_msm_groups(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy) {
     TRY(use_ctx(ctx));
     TRY(check_curve(cv));
-    if (int rc; on_native(cv, rc, [&](auto S) { return native_msm_groups(S, ctx, pts_xy, scalars, groups, m, out_xy); })) return rc;
+    if (int rc; on_native(cv, rc, [&](auto S) { return msm_groups<decltype(S)>(ctx, pts_xy, scalars, groups, m, out_xy); })) return rc;
     if (groups == 0) return DR_OK;
     if (m == 0 || m > 64) return fail(DR_ERR_INVALID, "group size must be in 1..64");
     if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
     size_t n = groups * m;
     if (n >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
     TRY(check_fr_elems(pts_xy, 2 * n, "point"));
-    if (drh::te_curve(cv)->glv && m <= 32 && n < 16384) {
-        std::vector<uint32_t> split;
-        TRY(glv_split_scalars(scalars, n, split));
-        uint32_t mpad2 = 2;
-        while (mpad2 < 2 * m) mpad2 <<= 1;
-        TRY(ctx->io_a.reserve(n * 64));
-        TRY(ctx->io_b.reserve(n * 48));
-        TRY(ctx->io_c.reserve(groups * 64));
-        HIP_TRY(hipMemcpyAsync(ctx->io_a.p, pts_xy, n * 64, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(ctx->io_b.p, split.data(), n * 48, hipMemcpyHostToDevice, ctx->stream));
-        const uint32_t per_block2 = dr::BSN_BLOCK / mpad2;
-        TRY(launch(ctx, "k_bsn_msm_groups", [&] {
-            hipLaunchKernelGGL(dr::k_bsn_msm_groups_glv, dim3(div_up(groups, per_block2)), dim3(dr::BSN_BLOCK), 0, ctx->stream,
-                               ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)groups, (uint32_t)m, mpad2);
-        }));
-        HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_c.p, groups * 64, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->prof) TRY(prof_collect(ctx));
-        return DR_OK;
-    }
-    uint32_t mpad = 1;
-    while (mpad < m) mpad <<= 1;
-    TRY(ctx->io_a.reserve(n * 64));
-    TRY(ctx->io_b.reserve(n * 32));
-    TRY(ctx->io_c.reserve(groups * 64));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, pts_xy, n * 64, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->io_b.p, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    // latency-bound launch: GLV on lane pairs (two lanes per term), the scalars split on the host
+    const bool glv = drh::te_curve(cv)->glv && m <= 32 && n < 16384;
+    std::vector<uint32_t> split;
+    if (glv) TRY(glv_split_scalars(scalars, n, split));
+    const size_t lanes = glv ? 2 * m : m, scalar_bytes = glv ? 48 : 32;
+    uint32_t mpad = glv ? 2 : 1;
+    while (mpad < lanes) mpad <<= 1;
     const uint32_t per_block = dr::BSN_BLOCK / mpad;
-    TRY(launch(ctx, "k_bsn_msm_groups", [&] {
-        LAUNCH_CV(cv, dr::k_bsn_msm_groups, dim3(div_up(groups, per_block)), dim3(dr::BSN_BLOCK), 0, ctx->stream,
-                  ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)groups, (uint32_t)m, mpad);
-    }));
-    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_c.p, groups * 64, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->prof) TRY(prof_collect(ctx));
-    return DR_OK;
+    return io_round(ctx, {n * 64, n * scalar_bytes, groups * 64},
+                    {{&ctx->io_a, 0, pts_xy, n * 64}, {&ctx->io_b, 0, glv ? (const void*)split.data() : scalars, n * scalar_bytes}}, "k_bsn_msm_groups", [&] {
+        if (glv)
+            hipLaunchKernelGGL(dr::k_bsn_msm_groups_glv, dim3(div_up(groups, per_block)), dim3(dr::BSN_BLOCK), 0, ctx->stream,
+                               ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)groups, (uint32_t)m, mpad);
+        else
+            LAUNCH_CV(cv, dr::k_bsn_msm_groups, dim3(div_up(groups, per_block)), dim3(dr::BSN_BLOCK), 0, ctx->stream,
+                      ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)groups, (uint32_t)m, mpad);
+    }, {{out_xy, &ctx->io_c, 0, groups * 64}});
 }
 // ---- fixed-base multiplication (kernels_te.hip.h: k_te_fixed_table / k_te_fixed_base_groups)
 static int te_fixed_table(dr_ctx* ctx, int cv, const uint8_t base_xy[64], const uint32_t** out) {
@@ -1010,19 +870,10 @@ int te_fixed_base_groups(dr_ctx* ctx, int cv, const uint8_t* bases_xy, const uin
     uint32_t mpad = 1;
     while (mpad < m) mpad <<= 1;
     const uint32_t per_block = 64 / (mpad * dr::TE_FIXED_LANES);
-    TRY(ctx->io_b.reserve(groups * m * 32));
-    TRY(ctx->io_c.reserve(groups * 64));
-    HIP_TRY(hipMemcpyAsync(ctx->io_b.p, scalars, groups * m * 32, hipMemcpyHostToDevice, ctx->stream));
-    TRY(launch(ctx, "k_bsn_fixed_base", [&] {
+    return io_round(ctx, {0, groups * m * 32, groups * 64}, {{&ctx->io_b, 0, scalars, groups * m * 32}}, "k_bsn_fixed_base", [&] {
         LAUNCH_CV(cv, dr::k_te_fixed_base_groups, dim3(div_up(groups, per_block)), dim3(64), 0, ctx->stream, tabs, ctx->io_b.as<uint32_t>(),
                   ctx->io_c.as<uint32_t>(), (uint32_t)groups, (uint32_t)m, mpad);
-    }));
-    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_c.p, groups * 64, hipMemcpyDeviceToHost, ctx->stream));
-    if (sync) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->prof) TRY(prof_collect(ctx));
-    }
-    return DR_OK;
+    }, {{out_xy, &ctx->io_c, 0, groups * 64}}, sync);
 }
 int dr_te_fixed_base_msm_groups(dr_ctx* ctx, int curve, const uint8_t* bases_xy, size_t m, const uint8_t* scalars, size_t groups, uint8_t* out_xy) {
     if (curve == DR_CURVE_BANDERSNATCH_SW) {
@@ -1074,14 +925,7 @@ int te_msm(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* scalars, s
         const drh::TeCurveHost* hc = drh::te_curve(cv);
         const drh::TeHostParams hp = drh::te_host_params(*hc);
         std::vector<drh::TeExt> terms(n);
-        drh::parallel_for(n, [&](size_t i) {
-            drh::TeExt P;
-            uint64_t k[4];
-            (void)drh::te_load_affine(pts_xy + 64 * i, P);
-            hc->n.reduce_bytes(scalars + 32 * i, 32, false, k);
-            terms[i] = drh::te_mul_secret(P, k, hp);
-            explicit_bzero(k, sizeof k);
-        }, 1);
+        drh::parallel_for(n, [&](size_t i) { terms[i] = te_mul_term_host(*hc, hp, pts_xy + 64 * i, scalars + 32 * i); }, 1);
         drh::TeExt acc = terms[0];
         for (size_t i = 1; i < n; i++) acc = drh::te_add(acc, terms[i], hp);
         drh::te_store_affine(acc, out_xy);
@@ -1102,22 +946,14 @@ int te_msm(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* scalars, s
         for (size_t i = n; i < parts * 64; i++) pp[64 * i + 32] = 1;
         TRY(te_msm_groups(ctx, cv, pp.data(), kk.data(), parts, 64, part.data()));
     }
-    using drh::Fr;
-    uint8_t D_LE[32];
-    drh::store_le32(drh::te_curve(cv)->d, D_LE);
-    Fr d, five = Fr::from_u64(drh::te_curve(cv)->neg_a[0]);        // -a
-    if (!Fr::load_le(d, D_LE)) return fail(DR_ERR_DEVICE, "bad curve constant");
-    Fr X = Fr::zero(), Y = Fr::one(), Z = Fr::one(), T = Fr::zero();          // identity
-    for (size_t i = 0; i < parts; i++) {                                      // add-2008-hwcd with Z2 = 1
-        Fr x2, y2;
-        if (!Fr::load_le(x2, part.data() + 64 * i) || !Fr::load_le(y2, part.data() + 64 * i + 32)) return fail(DR_ERR_DEVICE, "kernel result out of range");
-        Fr A = X * x2, B = Y * y2, C = T * d * (x2 * y2), D = Z;
-        Fr E = (X + Y) * (x2 + y2) - A - B, F = D - C, G = D + C, H = B + A * five;      // H = B - a*A
-        X = E * F; Y = G * H; T = E * H; Z = F * G;
+    const drh::TeHostParams hp = drh::te_host_params(*drh::te_curve(cv));       // (the SW id carries the constants of its TE image)
+    drh::TeExt acc = drh::te_identity();
+    for (size_t i = 0; i < parts; i++) {
+        drh::TeExt p;
+        if (!drh::te_load_affine(part.data() + 64 * i, p)) return fail(DR_ERR_DEVICE, "kernel result out of range");
+        acc = drh::te_add(acc, p, hp);
     }
-    Fr zi = Z.inv();
-    (X * zi).store_le(out_xy);
-    (Y * zi).store_le(out_xy + 32);
+    drh::te_store_affine(acc, out_xy);
     return DR_OK;
 }
 int dr_bsn_msm(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t out_xy[64]) {
@@ -1143,11 +979,7 @@ static int sw_decode_points(dr_ctx* ctx, bool tai, bool sw_out, const uint8_t* e
         std::memcpy(&rec[9 * i], enc + 33 * i, 32);
         rec[9 * i + 8] = enc[33 * i + 32];
     }
-    TRY(ctx->io_a.reserve(n * words * 4));
-    TRY(ctx->io_b.reserve(n * 64));
-    TRY(ctx->io_c.reserve(n * 4));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, rec.data(), n * words * 4, hipMemcpyHostToDevice, ctx->stream));
-    TRY(launch(ctx, "k_sw_decode_points", [&] {
+    TRY(io_round_flagged(ctx, {n * words * 4, n * 64, n * 4}, {{&ctx->io_a, 0, rec.data(), n * words * 4}}, "k_sw_decode_points", [&] {
         if (tai)
             hipLaunchKernelGGL((dr::k_sw_decode_points<false, true>), dim3(div_up(n, dr::BSN_BLOCK)), dim3(dr::BSN_BLOCK), 0, ctx->stream,
                                ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
@@ -1157,16 +989,9 @@ static int sw_decode_points(dr_ctx* ctx, bool tai, bool sw_out, const uint8_t* e
         else
             hipLaunchKernelGGL((dr::k_sw_decode_points<false, false>), dim3(div_up(n, dr::BSN_BLOCK)), dim3(dr::BSN_BLOCK), 0, ctx->stream,
                                ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
-    }));
-    std::vector<uint32_t> flags(n);
-    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_b.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(flags.data(), ctx->io_c.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->prof) TRY(prof_collect(ctx));
-    for (size_t i = 0; i < n; i++) {
-        ok[i] = flags[i] ? 1 : 0;
-        if (!ok[i] && !tai) std::memset(out_xy + 64 * i, 0, 64);
-    }
+    }, {out_xy, &ctx->io_b, 0, n * 64}, n, ok));
+    for (size_t i = 0; i < n && !tai; i++)
+        if (!ok[i]) std::memset(out_xy + 64 * i, 0, 64);          // (a refused string leaves no point; a refused candidate's is never read)
     return DR_OK;
 }
 
@@ -1186,7 +1011,7 @@ void launch_decode_points(dr_ctx* ctx, hipStream_t st, int cv, bool tai, const u
 }
 
 int te_decode_points(dr_ctx* ctx, int cv, bool tai, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok, bool sw_out) {
-    if (int rc; on_native(cv, rc, [&](auto S) { return native_decode_points(S, ctx, tai ? S.dec_tai : S.dec_check, enc, n, out_xy, ok); })) return rc;
+    if (int rc; on_native(cv, rc, [&](auto S) { return decode_points<decltype(S)>(ctx, tai ? S.dec_tai : S.dec_check, enc, n, out_xy, ok); })) return rc;
     TRY(use_ctx(ctx));
     TRY(check_curve(cv));
     if (n == 0) return DR_OK;
@@ -1203,20 +1028,9 @@ int te_decode_points(dr_ctx* ctx, int cv, bool tai, const uint8_t* enc, size_t n
         }, 1);
         return DR_OK;
     }
-    TRY(ctx->io_a.reserve(n * 32));
-    TRY(ctx->io_b.reserve(n * 64));
-    TRY(ctx->io_c.reserve(n * 4));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, enc, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    TRY(launch(ctx, "k_bsn_decode_points", [&] {
+    return io_round_flagged(ctx, {n * 32, n * 64, n * 4}, {{&ctx->io_a, 0, enc, n * 32}}, "k_bsn_decode_points", [&] {
         launch_decode_points(ctx, ctx->stream, cv, tai, ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), n);
-    }));
-    std::vector<uint32_t> flags(n);
-    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_b.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(flags.data(), ctx->io_c.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->prof) TRY(prof_collect(ctx));
-    for (size_t i = 0; i < n; i++) ok[i] = flags[i] ? 1 : 0;
-    return DR_OK;
+    }, {out_xy, &ctx->io_b, 0, n * 64}, n, ok);
 }
 int dr_bsn_decode_points(dr_ctx* ctx, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
     return te_decode_points(ctx, dr::CV_BANDERSNATCH, false, enc, n, out_xy, ok);
@@ -1225,73 +1039,43 @@ int dr_te_decode_points(dr_ctx* ctx, int curve, const uint8_t* enc, size_t n, ui
     return te_decode_points(ctx, curve, false, enc, n, out_xy, ok, true);
 }
 int dr_ed25519_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
-    return native_decode_points(Ed25519Suite{}, ctx, check ? Ed25519Suite::dec_check : Ed25519Suite::dec_codec, enc, n, out_xy, ok);
+    return decode_points<Ed25519Suite>(ctx, check ? Ed25519Suite::dec_check : Ed25519Suite::dec_codec, enc, n, out_xy, ok);
 }
 int dr_p256_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
-    return native_decode_points(P256Suite{}, ctx, check ? P256Suite::dec_check : P256Suite::dec_codec, enc, n, out_xy, ok);
+    return decode_points<P256Suite>(ctx, check ? P256Suite::dec_check : P256Suite::dec_codec, enc, n, out_xy, ok);
 }
 int dr_bjj_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
-    return native_decode_points(BjjSuite{}, ctx, check ? BjjSuite::dec_check : BjjSuite::dec_codec, enc, n, out_xy, ok);
+    return decode_points<BjjSuite>(ctx, check ? BjjSuite::dec_check : BjjSuite::dec_codec, enc, n, out_xy, ok);
 }
 int dr_fe25519_ops_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
-    return native_field_selftest(Ed25519Suite{}, ctx, a_limbs, b_limbs, n, out, flags);
+    return field_selftest<Ed25519Suite>(ctx, a_limbs, b_limbs, n, out, flags);
 }
 int dr_p256_field_ops_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
-    return native_field_selftest(P256Suite{}, ctx, a_limbs, b_limbs, n, out, flags);
+    return field_selftest<P256Suite>(ctx, a_limbs, b_limbs, n, out, flags);
 }
 int dr_secp256k1_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
-    return native_decode_points(Secp256k1Suite{}, ctx, check ? Secp256k1Suite::dec_check : Secp256k1Suite::dec_codec, enc, n, out_xy, ok);
+    return decode_points<Secp256k1Suite>(ctx, check ? Secp256k1Suite::dec_check : Secp256k1Suite::dec_codec, enc, n, out_xy, ok);
 }
 int dr_secp256k1_field_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
-    return native_field_selftest(Secp256k1Suite{}, ctx, a_limbs, b_limbs, n, out, flags);
+    return field_selftest<Secp256k1Suite>(ctx, a_limbs, b_limbs, n, out, flags);
 }
-// the maps of RFC 9380 for n items of per_item (1 or 2) field elements each: one launch of the curve's map kernel, the sum of each
-// item's images out (on Ed25519 with the cofactor cleared)
-namespace {
-using MapKernel = void (*)(const uint32_t*, uint32_t*, uint32_t*, uint32_t, uint32_t);
-int native_map_to_curve(dr_ctx* ctx, const char* name, MapKernel kernel, int block, const drh::Mod256& field, const uint8_t* us, size_t n,
-                        int per_item, uint8_t* out_xy, uint8_t* ok) {
-    TRY(use_ctx(ctx));
-    if (per_item != 1 && per_item != 2) return fail(DR_ERR_INVALID, "one (nonuniform) or two (uniform, RO) field elements per item");
-    if (n == 0) return DR_OK;
-    if (!us || !out_xy || !ok) return fail(DR_ERR_INVALID, "null buffer");
-    if (n >= (1ull << 30)) return fail(DR_ERR_INVALID, "batch too large");
-    const size_t elems = n * (size_t)per_item;
-    for (size_t i = 0; i < elems; i++) {
-        uint64_t v[4];
-        drh::load_le32(us + 32 * i, v);
-        if (drh::Mod256::geq(v, field.m)) return fail(DR_ERR_INVALID, "input is not a canonical field element");
-    }
-    TRY(ctx->io_a.reserve(elems * 32));
-    TRY(ctx->io_b.reserve(n * 64));
-    TRY(ctx->io_c.reserve(n * 4));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, us, elems * 32, hipMemcpyHostToDevice, ctx->stream));
-    TRY(launch(ctx, name, [&] {
-        hipLaunchKernelGGL(kernel, dim3(div_up(n, block)), dim3(block), 0, ctx->stream, ctx->io_a.as<uint32_t>(), ctx->io_b.as<uint32_t>(),
-                           ctx->io_c.as<uint32_t>(), (uint32_t)n, (uint32_t)per_item);
-    }));
-    return finish_flagged(ctx, out_xy, ctx->io_b.p, n * 64, ctx->io_c.p, n, ok);
-}
-}  // namespace
 int dr_secp256k1_map_to_curve(dr_ctx* ctx, const uint8_t* us, size_t n, int per_item, uint8_t* out_xy, uint8_t* ok) {
-    return native_map_to_curve(ctx, "k_secp256k1_map_to_curve", dr::k_secp256k1_map_to_curve, dr::K1_BLOCK, drh::mod_psecp256k1(), us, n, per_item,
-                               out_xy, ok);
+    return map_to_curve<Secp256k1Suite>(ctx, us, n, per_item, 1, out_xy, ok);
 }
 int dr_p256_map_to_curve(dr_ctx* ctx, const uint8_t* us, size_t n, int per_item, uint8_t* out_xy, uint8_t* ok) {
-    return native_map_to_curve(ctx, "k_p256_map_to_curve", dr::k_p256_map_to_curve, dr::P256_BLOCK, drh::mod_p256(), us, n, per_item, out_xy, ok);
+    return map_to_curve<P256Suite>(ctx, us, n, per_item, 1, out_xy, ok);
 }
 int dr_ed25519_map_to_curve(dr_ctx* ctx, const uint8_t* us, size_t n, int per_item, uint8_t* out_xy, uint8_t* ok) {
-    return native_map_to_curve(ctx, "k_ed25519_map_to_curve", dr::k_ed25519_map_to_curve, dr::ED_BLOCK, drh::mod_p25519(), us, n, per_item, out_xy,
-                               ok);
+    return map_to_curve<Ed25519Suite>(ctx, us, n, per_item, 1, out_xy, ok);
 }
 // ---- Curve25519 (kernels_curve25519.hip.h): the entry points with the identity flags spelled out.  The flag bytes go straight to the
-// kernels' flag words (NativeFlags); a point whose flag is 0 must have canonical coordinates, 64 bytes of 0xff included.
+// kernels' flag words (IdentityFlags); a point whose flag is 0 must have canonical coordinates, 64 bytes of 0xff included.
 int dr_curve25519_scalar_mul_batch(dr_ctx* ctx, const uint8_t* pts_uv, const uint8_t* id_in, const uint8_t* scalars, size_t n, uint8_t* out_uv,
                                    uint8_t* id_out) {
     TRY(use_ctx(ctx));
     if (n && !id_out) return fail(DR_ERR_INVALID, "null buffer");
-    const NativeFlags fl{id_in, id_out};
-    return native_scalar_mul_batch(Curve25519Suite{}, ctx, pts_uv, scalars, n, out_uv, &fl);
+    const IdentityFlags fl{id_in, id_out};
+    return scalar_mul_batch<Curve25519Suite>(ctx, pts_uv, scalars, n, out_uv, &fl);
 }
 int dr_curve25519_msm_groups(dr_ctx* ctx, const uint8_t* pts_uv, const uint8_t* id_in, const uint8_t* scalars, size_t groups, size_t m,
                              uint8_t* out_uv, uint8_t* id_out) {
@@ -1299,44 +1083,19 @@ int dr_curve25519_msm_groups(dr_ctx* ctx, const uint8_t* pts_uv, const uint8_t* 
     if (m == 0 || m > 64) return fail(DR_ERR_INVALID, "group size must be in 1..64");
     if (groups >= (1ull << 31) || groups * m >= (1ull << 31)) return fail(DR_ERR_INVALID, "batch too large");
     if (groups && !id_out) return fail(DR_ERR_INVALID, "null buffer");
-    const NativeFlags fl{id_in, id_out};
-    return native_msm_groups(Curve25519Suite{}, ctx, pts_uv, scalars, groups, m, out_uv, &fl);
+    const IdentityFlags fl{id_in, id_out};
+    return msm_groups<Curve25519Suite>(ctx, pts_uv, scalars, groups, m, out_uv, &fl);
 }
 int dr_curve25519_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_t n, uint8_t* out_uv, uint8_t* ok) {
-    return native_decode_points(Curve25519Suite{}, ctx, check ? Curve25519Suite::dec_check : Curve25519Suite::dec_codec, enc, n, out_uv, ok);
+    return decode_points<Curve25519Suite>(ctx, check ? Curve25519Suite::dec_check : Curve25519Suite::dec_codec, enc, n, out_uv, ok);
 }
 // n items of per_item (1 or 2) field elements: the sum of their Elligator 2 images, times the cofactor 8 unless clear_cofactor = 0; every
 // canonical input has a value (id_out[i] = 1 where it is the identity, its 64 bytes then zeros)
 int dr_curve25519_map_to_curve(dr_ctx* ctx, const uint8_t* us, size_t n, int per_item, int clear_cofactor, uint8_t* out_uv, uint8_t* id_out) {
-    TRY(use_ctx(ctx));
-    if (per_item != 1 && per_item != 2) return fail(DR_ERR_INVALID, "one (nonuniform) or two (uniform, RO) field elements per item");
-    if (n == 0) return DR_OK;
-    if (!us || !out_uv || !id_out) return fail(DR_ERR_INVALID, "null buffer");
-    if (n >= (1ull << 30)) return fail(DR_ERR_INVALID, "batch too large");
-    const size_t elems = n * (size_t)per_item;
-    for (size_t i = 0; i < elems; i++) {
-        uint64_t v[4];
-        drh::load_le32(us + 32 * i, v);
-        if (drh::Mod256::geq(v, drh::mod_p25519().m)) return fail(DR_ERR_INVALID, "input is not a canonical field element");
-    }
-    TRY(ctx->io_a.reserve(elems * 32));
-    TRY(ctx->io_b.reserve(n * 64));
-    TRY(ctx->io_c.reserve(n * 4));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, us, elems * 32, hipMemcpyHostToDevice, ctx->stream));
-    TRY(launch(ctx, "k_curve25519_map_to_curve", [&] {
-        hipLaunchKernelGGL(dr::k_curve25519_map_to_curve, dim3(div_up(n, dr::ED_BLOCK)), dim3(dr::ED_BLOCK), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
-                           ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n, (uint32_t)per_item, clear_cofactor ? 1u : 0u);
-    }));
-    std::vector<uint32_t> flags(n);
-    HIP_TRY(hipMemcpyAsync(out_uv, ctx->io_b.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(flags.data(), ctx->io_c.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->prof) TRY(prof_collect(ctx));
-    for (size_t i = 0; i < n; i++) id_out[i] = flags[i] ? 1 : 0;
-    return DR_OK;
+    return map_to_curve<Curve25519Suite>(ctx, us, n, per_item, clear_cofactor, out_uv, id_out);
 }
 int dr_bjj_field_ops_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
-    return native_field_selftest(BjjSuite{}, ctx, a_limbs, b_limbs, n, out, flags);
+    return field_selftest<BjjSuite>(ctx, a_limbs, b_limbs, n, out, flags);
 }
 
 int dr_bsn_encode_to_curve_batch(dr_ctx* ctx, const uint8_t* u_pairs, size_t n, uint8_t* out_xy) {
@@ -1349,17 +1108,10 @@ int dr_bsn_encode_to_curve_batch(dr_ctx* ctx, const uint8_t* u_pairs, size_t n, 
         drh::parallel_for(n, [&](size_t i) { (void)drh::te_encode_to_curve_host(u_pairs + 64 * i, out_xy + 64 * i); }, 1);
         return DR_OK;
     }
-    TRY(ctx->io_a.reserve(n * 64));
-    TRY(ctx->io_c.reserve(n * 64));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, u_pairs, n * 64, hipMemcpyHostToDevice, ctx->stream));
-    TRY(launch(ctx, "k_bsn_encode_to_curve", [&] {
+    return io_round(ctx, {n * 64, 0, n * 64}, {{&ctx->io_a, 0, u_pairs, n * 64}}, "k_bsn_encode_to_curve", [&] {
         hipLaunchKernelGGL(dr::k_bsn_encode_to_curve, dim3(div_up(2 * n, 64)), dim3(64), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
                            ctx->io_c.as<uint32_t>(), (uint32_t)n);
-    }));
-    HIP_TRY(hipMemcpyAsync(out_xy, ctx->io_c.p, n * 64, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->prof) TRY(prof_collect(ctx));
-    return DR_OK;
+    }, {{out_xy, &ctx->io_c, 0, n * 64}});
 }
 
 int dr_fr_ops_selftest(dr_ctx* ctx, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out, uint8_t* is_square) {
@@ -1369,20 +1121,10 @@ int dr_fr_ops_selftest(dr_ctx* ctx, const uint8_t* a, const uint8_t* b, size_t n
     if (n >= (1ull << 24)) return fail(DR_ERR_INVALID, "batch too large");
     TRY(check_fr_elems(a, n, "field element"));
     TRY(check_fr_elems(b, n, "field element"));
-    TRY(ctx->io_a.reserve(n * 64));
-    TRY(ctx->io_b.reserve(n * 384));
-    TRY(ctx->io_c.reserve(n * 4));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.p, a, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->io_a.as<uint8_t>() + n * 32, b, n * 32, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(dr::k_fr_ops_selftest, dim3(div_up(n, 64)), dim3(64), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
-                       ctx->io_a.as<uint32_t>() + n * 8, (uint32_t)n, ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    std::vector<uint32_t> flags(n);
-    HIP_TRY(hipMemcpyAsync(out, ctx->io_b.p, n * 384, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(flags.data(), ctx->io_c.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (size_t i = 0; i < n; i++) is_square[i] = flags[i] ? 1 : 0;
-    return DR_OK;
+    return io_round_flagged(ctx, {n * 64, n * 384, n * 4}, {{&ctx->io_a, 0, a, n * 32}, {&ctx->io_a, n * 32, b, n * 32}}, nullptr, [&] {
+        hipLaunchKernelGGL(dr::k_fr_ops_selftest, dim3(div_up(n, 64)), dim3(64), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
+                           ctx->io_a.as<uint32_t>() + n * 8, (uint32_t)n, ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>());
+    }, {out, &ctx->io_b, 0, n * 384}, n, is_square);
 }
 
 int dr_fr_sqrt(const uint8_t in[32], uint8_t out[32]) {

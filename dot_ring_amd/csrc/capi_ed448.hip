@@ -1,20 +1,21 @@
 // libdotring_hip.so — C ABI, part 8 of 8: the Ed448 suites (DR_CURVE_ED448_RO / DR_CURVE_ED448_NU; the reference's specs/ed448.py).
 // Field elements and coordinates are 56 bytes little-endian, canonical; points are affine x || y, 112 bytes, the identity (0, 1) as itself;
-// scalars are 56 bytes used AS THEY ARE.  None of it goes through the 64-byte paths of capi_core.hip but through capi_wide.hpp.  The
+// scalars are 56 bytes used AS THEY ARE.  None of it goes through the 64-byte paths of capi_core.hip but through capi_suite.hpp.  The
 // kernels are kernels_ed448.hip.h over fe448.hip.h; the host does hash_to_field (expand_message_xof over SHAKE256, L = 84) on the worker
 // threads and checks that inputs are canonical.  Scalars may be secret: they pass through io_a / io_b / io_c only, which ctx_wipe_scratch
 // covers.
-#include "capi_wide.hpp"
+#include "capi_suite.hpp"
 #include "kernels_ed448.hip.h"
 
 using namespace dri;
 
 namespace {
 
-struct Ed448Suite {
+struct Ed448Suite : SuiteDefaults {
     static constexpr size_t fe_bytes = 56, elem_bytes = 56, pt_bytes = 112, scalar_bytes = 56, limb_bytes = 4 * dr::L448;
     static constexpr int variant_ro = DR_CURVE_ED448_RO, variant_nu = DR_CURVE_ED448_NU;
     static constexpr const char* variant_names = "DR_CURVE_ED448_RO or DR_CURVE_ED448_NU";
+    static constexpr bool limit_first = true;
     static constexpr size_t max_map = 1ull << 28, max_points = 1ull << 29, max_decode = 1ull << 29;
     static constexpr auto scalar_mul = dr::k_ed448_scalar_mul;
     static constexpr auto msm_groups = dr::k_ed448_msm_groups;
@@ -50,28 +51,30 @@ struct Ed448Suite {
 }  // namespace
 
 int dr_ed448_hash_to_field_batch(int variant, const uint8_t* msgs, const uint64_t* off, size_t count, uint8_t* out) {
-    return wide_hash_to_field_batch<Ed448Suite>(variant, msgs, off, count, out);
+    return hash_to_field_batch<Ed448Suite>(variant, msgs, off, count, out);
 }
 int dr_ed448_map_to_curve(dr_ctx* ctx, const uint8_t* us, size_t n, int per_item, int clear, uint8_t* out_xy, uint8_t* ok) {
-    return wide_map_to_curve<Ed448Suite>(ctx, us, n, per_item, clear, out_xy, ok);
+    return map_to_curve<Ed448Suite>(ctx, us, n, per_item, clear, out_xy, ok);
 }
 int dr_ed448_encode_to_curve_batch(dr_ctx* ctx, int variant, const uint8_t* msgs, const uint64_t* off, const uint8_t* salts,
                                    const uint64_t* salt_off, size_t count, uint8_t* out_xy) {
-    return wide_encode_to_curve_batch<Ed448Suite>(ctx, variant, msgs, off, salts, salt_off, count, out_xy);
+    return encode_to_curve_batch<Ed448Suite>(ctx, variant, msgs, off, salts, salt_off, count, out_xy);
 }
 int dr_ed448_scalar_mul_batch(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy) {
-    return wide_scalar_mul_batch<Ed448Suite>(ctx, pts_xy, scalars, n, out_xy);
+    TRY(use_ctx(ctx));
+    return scalar_mul_batch<Ed448Suite>(ctx, pts_xy, scalars, n, out_xy);
 }
 int dr_ed448_msm_groups(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy) {
-    return wide_msm_groups<Ed448Suite>(ctx, pts_xy, scalars, groups, m, out_xy);
+    TRY(use_ctx(ctx));
+    return msm_groups<Ed448Suite>(ctx, pts_xy, scalars, groups, m, out_xy);
 }
 int dr_ed448_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
-    return wide_flagged<Ed448Suite>(ctx, enc, n, out_xy, ok, [&] {
+    return flagged_round<Ed448Suite>(ctx, enc, n, out_xy, ok, [&] {
         const auto kernel = check ? dr::k_ed448_check_points<1> : dr::k_ed448_check_points<0>;
         hipLaunchKernelGGL(kernel, dim3(div_up(n, dr::E448_BLOCK)), dim3(dr::E448_BLOCK), 0, ctx->stream, ctx->io_a.as<uint32_t>(),
                            ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>(), (uint32_t)n);
     });
 }
 int dr_ed448_field_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
-    return wide_field_selftest<Ed448Suite>(ctx, a_limbs, b_limbs, n, out, flags);
+    return field_selftest<Ed448Suite>(ctx, a_limbs, b_limbs, n, out, flags);
 }

@@ -8,7 +8,8 @@
 //   capi_blsg2.hip  the BLS12_381_G2 suites: Fq2 coordinates, hashing to G2 and the group of E(Fq2)
 //   capi_ed448.hip  the Ed448 suites: 56-byte coordinates and scalars, hashing to the curve and the group of E(F_p)
 // The last three are one description of their suite each (widths, limits, kernels, hashing parameters) and their entry points as calls
-// of capi_wide.hpp's templates, the one host path of the suites whose coordinates do not fit the 64-byte paths of capi_core.hip.
+// of capi_suite.hpp's templates, the one host path they share with the five 256-bit suites described in capi_core.hip; every host
+// round trip of a single-launch entry point is io_round below.
 // Each header that defines kernels is included by exactly one of them; the others reach its kernels through the launch wrappers below.
 // (kernels_g1_h2c.hip.h defines none: the two BLS12-381 hashing units share its device functions.)
 #pragma once
@@ -21,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <map>
 #include <array>
 #include <memory>
@@ -28,6 +30,7 @@
 #include <set>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/dotring_hip.h"
@@ -200,20 +203,58 @@ int launch(dr_ctx* ctx, const char* name, F&& f) {
 
 inline unsigned div_up(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 
-// The tail of a call whose kernel leaves one flag word per item in d_flags beside its results: `bytes` of results (d_out to out; none
-// where out is null) and the n flag words to the host, then wait for the stream.
-inline int download_flagged(dr_ctx* ctx, void* out, const void* d_out, size_t bytes, const void* d_flags, std::vector<uint32_t>& flags) {
-    if (out) HIP_TRY(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(flags.data(), d_flags, flags.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+// One host round trip of a single-launch entry point, the only place that spells the sequence out: reserve io_a / io_b / io_c (`need`; 0:
+// not used), the uploads in order, the launch, the downloads in order (one without a destination is skipped), and with `sync` the wait
+// for the stream and the kernel timers.  Without `sync` the caller waits later (the prover's fixed-base commitments).  `go` is one kernel
+// launch, profiled as `name` (null: not profiled, the field selftests), or a step that returns a status and launches under names of its
+// own (G2's two-kernel map); these three forms are all it takes.  Buffers are named by their Scratch, since the reserve here is what gives
+// them their address.  The timers are collected after every synchronised round, also after an unprofiled one and after a step that has
+// collected them itself (te_scalar_mul_batch_dev), where the calls written out by hand did not: with nothing pending that does nothing.
+struct IoBytes {
+    size_t a, b, c;
+};
+struct IoUp {
+    Scratch* to;
+    size_t at;
+    const void* from;
+    size_t bytes;
+};
+struct IoDown {
+    void* to;
+    const Scratch* from;
+    size_t at, bytes;
+};
+template <class F>
+int io_round(dr_ctx* ctx, IoBytes need, std::initializer_list<IoUp> ups, const char* name, F&& go, std::initializer_list<IoDown> downs, bool sync = true) {
+    if (need.a) TRY(ctx->io_a.reserve(need.a));
+    if (need.b) TRY(ctx->io_b.reserve(need.b));
+    if (need.c) TRY(ctx->io_c.reserve(need.c));
+    for (const IoUp& u : ups) HIP_TRY(hipMemcpyAsync(u.to->as<uint8_t>() + u.at, u.from, u.bytes, hipMemcpyHostToDevice, ctx->stream));
+    if constexpr (std::is_void_v<decltype(go())>) {
+        if (name) {
+            TRY(launch(ctx, name, go));
+        } else {
+            go();
+            HIP_TRY(hipGetLastError());
+        }
+    } else {
+        TRY(go());
+    }
+    for (const IoDown& d : downs)
+        if (d.to) HIP_TRY(hipMemcpyAsync(d.to, (const uint8_t*)d.from->p + d.at, d.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (!sync) return DR_OK;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->prof) TRY(prof_collect(ctx));
     return DR_OK;
 }
-// ... of a profiled launch: the kernel timers collected, and each flag word as one byte, 1 or 0
-inline int finish_flagged(dr_ctx* ctx, void* out, const void* d_out, size_t bytes, const void* d_flags, size_t n, uint8_t* ok) {
+// ... of a kernel that leaves one flag word per item at the start of io_c beside its results (`out`): each word as one byte, 1 or 0, or
+// with `truth` false the word cut to a byte
+template <class F>
+int io_round_flagged(dr_ctx* ctx, IoBytes need, std::initializer_list<IoUp> ups, const char* name, F&& go, IoDown out, size_t n, uint8_t* ok,
+                     bool truth = true) {
     std::vector<uint32_t> flags(n);
-    TRY(download_flagged(ctx, out, d_out, bytes, d_flags, flags));
-    if (ctx->prof) TRY(prof_collect(ctx));
-    for (size_t i = 0; i < n; i++) ok[i] = flags[i] ? 1 : 0;
+    TRY(io_round(ctx, need, ups, name, go, {out, {flags.data(), &ctx->io_c, 0, n * 4}}));
+    for (size_t i = 0; i < n; i++) ok[i] = truth ? (flags[i] ? 1 : 0) : (uint8_t)flags[i];
     return DR_OK;
 }
 

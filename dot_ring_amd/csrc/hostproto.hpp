@@ -24,6 +24,7 @@
 #include "hosth2c.hpp"
 #include "hosthash.hpp"
 #include "hostmath.hpp"
+#include "hostrecords.hpp"
 
 namespace drh {
 
@@ -611,11 +612,10 @@ struct VrfSuite {
 };
 // Curve25519's identity where a point is 64 bytes and nothing else (the host path between the launches and the generic dr_te_* entry
 // points): u = v = 2^256 - 1, which is no field element, so no point of the curve — (0, 0) is one.  The launches turn it into the kernels'
-// identity flag and back (capi_core.hip: native_run).
+// identity flag and back (capi_suite.hpp: run_points, hostrecords.hpp: split_identities).
 constexpr size_t POINT_MAX = 64;                  // the longest encoded point of any suite
 inline bool mont_is_identity(const uint8_t xy[64]) {
-    for (int i = 0; i < 64; i++) if (xy[i] != 0xff) return false;
-    return true;
+    return all_ff(xy, 64);
 }
 // whether any of n points of a Curve25519 suite is the identity (false for every other suite)
 inline bool any_mont_identity(const VrfSuite& su, const uint8_t* xy, size_t n) {

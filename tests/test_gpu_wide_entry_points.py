@@ -1,4 +1,4 @@
-"""The host path the three wide suites share (csrc/capi_wide.hpp under the dr_blsg1_*, dr_blsg2_* and dr_ed448_* entry points), on the
+"""The host path the three wide suites share (csrc/capi_suite.hpp under the dr_blsg1_*, dr_blsg2_* and dr_ed448_* entry points), on the
 GPU: every profiled entry point launches under its own name and no other suite's; a batch returns what its items return one by one,
 flags included, across the edge of a 64-thread block (n = 1, 64, 65: G1H_BLOCK = G2H_BLOCK = E448_BLOCK = 64); and a small batch on a
 context that has just run a large one returns what a fresh context returns (no stale flag word, and for G2 the per-element flags at
