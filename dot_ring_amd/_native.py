@@ -143,6 +143,13 @@ _PROTOTYPES.update({
     "dr_ed448_msm_groups": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_size_t, c_char_p]),
     "dr_ed448_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
     "dr_ed448_field_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p, c_void_p]),
+    "dr_curve448_hash_to_field_batch": (c_int, [c_int, c_char_p, POINTER(ctypes.c_uint64), c_size_t, c_char_p]),
+    "dr_curve448_map_to_curve": (c_int, [c_void_p, c_char_p, c_size_t, c_int, c_int, c_char_p, c_char_p]),
+    "dr_curve448_encode_to_curve_batch": (c_int, [c_void_p, c_int, c_char_p, POINTER(ctypes.c_uint64), c_char_p, POINTER(ctypes.c_uint64), c_size_t,
+                                                  c_char_p]),
+    "dr_curve448_scalar_mul_batch": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_char_p]),
+    "dr_curve448_msm_groups": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_size_t, c_char_p]),
+    "dr_curve448_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
     "dr_curve25519_scalar_mul_batch": (c_int, [c_void_p, c_char_p, c_char_p, c_char_p, c_size_t, c_char_p, c_char_p]),
     "dr_curve25519_msm_groups": (c_int, [c_void_p, c_char_p, c_char_p, c_char_p, c_size_t, c_size_t, c_char_p, c_char_p]),
     "dr_curve25519_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
@@ -241,6 +248,8 @@ CURVE_BLS12_381_G1, CURVE_BLS12_381_G1_NU = 15, 16
 CURVE_BLS12_381_G2, CURVE_BLS12_381_G2_NU = 17, 18
 # Ed448 by RFC 9380: 56-byte coordinates AND 56-byte scalars, entry points of their own (dr_ed448_*); refused everywhere else
 CURVE_ED448_RO, CURVE_ED448_NU = 19, 20
+# Curve448 by RFC 9380: Montgomery u || v over Ed448's field, entry points of their own (dr_curve448_*), the identity 112 bytes of 0xff
+CURVE_CURVE448_RO, CURVE_CURVE448_NU = 21, 22
 # bytes of an encoded point, per curve id (the suites with 33-byte encodings and Curve25519's 64-byte u || v; every other curve's are 32)
 _POINT_LEN = {CURVE_BANDERSNATCH_SW: 33, CURVE_P256: 33, CURVE_SECP256K1: 33, CURVE_SECP256K1_NU: 33, CURVE_P256_RO: 33, CURVE_P256_NU: 33,
               CURVE_CURVE25519_RO: 64, CURVE_CURVE25519_NU: 64}
@@ -339,6 +348,7 @@ _WIDE = {
     "blsg1": _Wide(48, 96, 32, 49, 56, 5, CURVE_BLS12_381_G1_NU, "decode_points"),
     "blsg2": _Wide(96, 192, 96, 192, 112, 5, CURVE_BLS12_381_G2_NU, "check_points"),
     "ed448": _Wide(56, 112, 56, 112, 64, 11, CURVE_ED448_NU, "decode_points"),
+    "curve448": _Wide(56, 112, 56, 112, 64, 0, CURVE_CURVE448_NU, "decode_points"),       # (no field selftest: the field is Ed448's)
 }
 
 
@@ -354,6 +364,7 @@ def _wide_hash_to_field_batch(suite: str, variant: int, msgs) -> bytes:
 blsg1_hash_to_field_batch = functools.partial(_wide_hash_to_field_batch, "blsg1")
 blsg2_hash_to_field_batch = functools.partial(_wide_hash_to_field_batch, "blsg2")
 ed448_hash_to_field_batch = functools.partial(_wide_hash_to_field_batch, "ed448")
+curve448_hash_to_field_batch = functools.partial(_wide_hash_to_field_batch, "curve448")
 
 
 def lib() -> ctypes.CDLL:
@@ -691,7 +702,8 @@ class Context:
         return self._limb_selftest(lib().dr_secp256k1_field_selftest, 12, a_limbs, b_limbs)
 
     # ---- the wide suites (include/dotring_hip.h; widths in _WIDE): BLS12-381 G1 (points 96 bytes x || y little-endian, 96 zero bytes the
-    # identity), G2 (Fq2 elements c0 || c1; 192 zero bytes the identity) and Ed448 (the identity (0, 1) as itself); scalars as they are
+    # identity), G2 (Fq2 elements c0 || c1; 192 zero bytes the identity), Ed448 (the identity (0, 1) as itself) and Curve448 (u || v, the
+    # identity 112 bytes of 0xff in and out); scalars as they are
     def _wide_map_to_curve(self, suite: str, us: bytes, per_item: int, clear: bool = True):
         """dr_<suite>_map_to_curve: (x||y bytes, flags) for len(us) / (elem per_item) items; clear = False: before the cofactor clearing.
         per_item other than 1 or 2 is the library's to refuse."""
@@ -772,6 +784,11 @@ class Context:
     ed448_msm_groups = functools.partialmethod(_wide_msm_groups, "ed448")
     ed448_decode_points = functools.partialmethod(_wide_flagged, "ed448")
     ed448_field_selftest = functools.partialmethod(_wide_field_selftest, "ed448")
+    curve448_map_to_curve = functools.partialmethod(_wide_map_to_curve, "curve448")
+    curve448_encode_to_curve_batch = functools.partialmethod(_wide_encode_to_curve_batch, "curve448")
+    curve448_scalar_mul_batch = functools.partialmethod(_wide_scalar_mul_batch, "curve448")
+    curve448_msm_groups = functools.partialmethod(_wide_msm_groups, "curve448")
+    curve448_decode_points = functools.partialmethod(_wide_flagged, "curve448")
 
     def blsg2_check_points(self, pts_xy: bytes, subgroup: bool = True) -> bytes:
         """dr_blsg2_check_points: one flag byte per 192-byte point: on the curve, and with `subgroup` also r P = O."""

@@ -11,7 +11,7 @@
 //                                                              the device, whether points come back, whether inputs are field elements
 //   canonical(p)                                               whether the fe_bytes at p are below the modulus
 //   consts_ready(ctx)                                          device constants a decoder or the selftest needs (SuiteDefaults: none)
-//   flagged                                                    the kernels carry an identity flag word beside each point (Curve25519 alone)
+//   flagged                                                    the kernels carry an identity flag word beside each point (Curve25519, Curve448)
 //   map_flag_words(n, elems), map_launch(ctx, n, elems, per_item, clear)   the flag words of the map in io_c (the first n the items') and
 //                                                              its launches, elements in io_a, points to io_b
 // and a wide suite, for its hashing,
@@ -109,7 +109,7 @@ int encode_to_curve_batch(dr_ctx* ctx, int variant, const uint8_t* msgs, const u
     return DR_OK;
 }
 
-// The identity flags of a flagged suite's call when the caller spells them out (the dr_curve25519_* entry points): one byte per point in
+// The identity flags of a flagged suite's call when the caller spells them out (the dr_curve25519_* entry points; the dr_curve448_* ones do not): one byte per point in
 // (null: none is the identity) and out.  Without them the identity travels inside the point, as pt_bytes of 0xff (drh::mont_is_identity).
 struct IdentityFlags {
     const uint8_t* in = nullptr;

@@ -1,5 +1,5 @@
 // Host-only shaping of what the single-launch entry points upload (capi_suite.hpp): zero-padded decoder records, and the identities of a
-// flagged suite (Curve25519) as flag words beside cleaned points.  No HIP include: tests/native/io_records_check.cpp builds this header
+// flagged suite (Curve25519, Curve448) as flag words beside cleaned points.  No HIP include: tests/native/io_records_check.cpp builds this header
 // stand-alone under the address and undefined-behaviour sanitizers.
 #pragma once
 #include <cstddef>

@@ -18,6 +18,9 @@ Mirrors (names, argument meaning, error behaviour) the parts of the reference th
   dot_ring/curve/specs/ed448.py                 Ed448 (= Ed448_RO), Ed448_NU: a = 1, d = -39081 over 2^448 - 2^224 - 1, cofactor 4, 112-byte
                                                 x || y codec, 56-byte scalars, RFC 9380 Elligator 2 with SHAKE256; kernels of their own
                                                 (DR_CURVE_ED448_RO / _NU), the first suite wider than 256 bits in both
+  dot_ring/curve/specs/curve448.py              Curve448 (= Curve448_RO), Curve448_NU: Montgomery affine points over Ed448's field, 112-byte
+                                                u || v codec, 56-byte scalars, RFC 9380 Elligator 2 with SHAKE256; kernels of their own on
+                                                the Edwards curve birational to it (DR_CURVE_CURVE448_RO / _NU)
   dot_ring/curve/point.py:150-214               compressed codec
   dot_ring/curve/twisted_edwards/*              affine law, Elligator2 encode_to_curve
   dot_ring/curve/curve.py:56-67,110-237,384-401 valid_point, hash_to_field, key derivation
@@ -1260,18 +1263,11 @@ class Ed448Point(_WideRfc9380, BandersnatchPoint):
         return [bool(f) for f in ok]
 
 
-class Curve25519Point(_Rfc9380, _AffinePoint):
-    """Affine point of Curve25519_RO / Curve25519_NU (dot_ring/curve/specs/curve25519.py, montgomery/mg_affine_point.py):
-    y^2 = x^3 + 486662 x^2 + x over 2^255 - 19 (x, y are the reference's names for u, v), cofactor 8, the identity is (None, None).
-    (0, 0) is a point of the curve (order 2), so the identity cannot travel as 64 zero bytes: it packs as 64 bytes of 0xff for the generic
-    entry points and as a flag byte for the dr_curve25519_* ones (pack_points_flagged).  Single additions are host big-int code with the
-    reference's affine formulas; scalar multiplications, MSMs, decoding and hashing to the curve run on the GPU (kernels_curve25519.hip.h,
-    which computes on the Ed25519 group law through the birational map)."""
-    _P = 2**255 - 19
-    _N = 2**252 + 0x14DEF9DEA2F79CD65812631A5CF5D3ED
-    _H, _CV = 8, _native.CURVE_CURVE25519_RO
-    _MG_A = 486662
-    _IDENTITY_BYTES = b"\xff" * 64
+class _MontgomeryPoint(_AffinePoint):
+    """Affine point of a Montgomery curve y^2 = x^3 + A x^2 + x (montgomery/mg_affine_point.py with B = 1; x, y are the reference's names
+    for u, v): the constructor's checks, the affine chord-and-tangent law and the uncompressed codec u || v, by the field's byte width.
+    The identity is (None, None) and has no encoding; (0, 0) is a point (order 2), so inside the library the identity travels as bytes of
+    0xff.  A concrete class gives _P, _N, _H, _CV, _MG_A, _FE_BYTES and its hashing."""
     __slots__ = ()
 
     def __init__(self, x, y):
@@ -1289,13 +1285,14 @@ class Curve25519Point(_Rfc9380, _AffinePoint):
 
     @classmethod
     def _trusted(cls, x: int, y: int):
-        """Kernel outputs: 64 bytes of 0xff are the identity."""
+        """Kernel outputs: coordinates of 0xff bytes are the identity."""
+        ones = (1 << (8 * cls._FE_BYTES)) - 1
         pt = object.__new__(cls)
-        pt.x, pt.y = (None, None) if x == y == (1 << 256) - 1 else (x, y)
+        pt.x, pt.y = (None, None) if x == y == ones else (x, y)
         return pt
 
     def __eq__(self, other):
-        return isinstance(other, Curve25519Point) and self.x == other.x and self.y == other.y
+        return isinstance(other, _MontgomeryPoint) and self._P == other._P and self.x == other.x and self.y == other.y
 
     def __hash__(self):
         return 0 if self.x is None else (self.x + self.y) % self._N
@@ -1305,7 +1302,7 @@ class Curve25519Point(_Rfc9380, _AffinePoint):
 
     # -- group law (mg_affine_point.py:38-116, B = 1)
     def __add__(self, other):
-        if not isinstance(other, Curve25519Point):
+        if not isinstance(other, _MontgomeryPoint) or self._P != other._P:
             return NotImplemented
         if self.is_identity():
             return other
@@ -1331,13 +1328,13 @@ class Curve25519Point(_Rfc9380, _AffinePoint):
     def clear_cofactor(self):
         return scalar_mul_batch_raw([self], [self._H])[0]
 
-    # -- codec (mg_affine_point.py:348-389): u || v, 32 little-endian bytes each; no compressed form, no encoding of the identity
+    # -- codec (mg_affine_point.py:348-389): u || v, little-endian; no compressed form, no encoding of the identity
     def point_to_string(self) -> bytes:
         if self.is_identity():
             raise ValueError("Cannot serialize point at infinity")
         if not self.curve.params.encoding.uncompressed:
             raise NotImplementedError("Compressed encoding not implemented")
-        return self.x.to_bytes(32, "little") + self.y.to_bytes(32, "little")
+        return self.x.to_bytes(self._FE_BYTES, "little") + self.y.to_bytes(self._FE_BYTES, "little")
 
     @classmethod
     def string_to_point(cls, data):
@@ -1346,9 +1343,25 @@ class Curve25519Point(_Rfc9380, _AffinePoint):
         data = bytes(data)
         if not cls.curve.params.encoding.uncompressed:
             raise NotImplementedError("Compressed encoding not implemented")
-        if len(data) != 64:
-            raise ValueError(f"Invalid point length: expected 64, got {len(data)}")
-        return cls(int.from_bytes(data[:32], "little"), int.from_bytes(data[32:], "little"))
+        w = cls._FE_BYTES
+        if len(data) != 2 * w:
+            raise ValueError(f"Invalid point length: expected {2 * w}, got {len(data)}")
+        return cls(int.from_bytes(data[:w], "little"), int.from_bytes(data[w:], "little"))
+
+
+class Curve25519Point(_Rfc9380, _MontgomeryPoint):
+    """Affine point of Curve25519_RO / Curve25519_NU (dot_ring/curve/specs/curve25519.py, montgomery/mg_affine_point.py):
+    y^2 = x^3 + 486662 x^2 + x over 2^255 - 19 (x, y are the reference's names for u, v), cofactor 8, the identity is (None, None).
+    (0, 0) is a point of the curve (order 2), so the identity cannot travel as 64 zero bytes: it packs as 64 bytes of 0xff for the generic
+    entry points and as a flag byte for the dr_curve25519_* ones (pack_points_flagged).  Single additions are host big-int code with the
+    reference's affine formulas; scalar multiplications, MSMs, decoding and hashing to the curve run on the GPU (kernels_curve25519.hip.h,
+    which computes on the Ed25519 group law through the birational map)."""
+    _P = 2**255 - 19
+    _N = 2**252 + 0x14DEF9DEA2F79CD65812631A5CF5D3ED
+    _H, _CV = 8, _native.CURVE_CURVE25519_RO
+    _MG_A, _FE_BYTES = 486662, 32
+    _IDENTITY_BYTES = b"\xff" * 64
+    __slots__ = ()
 
     # -- hash to curve (RFC 9380 curve25519_XMD:SHA-512_ELL2_RO_ / _NU_): expand_message_xmd natively on the host, the map on the GPU
     @classmethod
@@ -1360,6 +1373,71 @@ class Curve25519Point(_Rfc9380, _AffinePoint):
     @classmethod
     def _mapped(cls, us: bytes, per_item: int):
         return unpack_points_flagged(cls, *runtime.context().curve25519_map_to_curve(us, per_item))
+
+
+class Curve448Point(_WideRfc9380, _MontgomeryPoint):
+    """Affine point of Curve448_RO / Curve448_NU (dot_ring/curve/specs/curve448.py): y^2 = x^3 + 156326 x^2 + x over
+    p = 2^448 - 2^224 - 1, cofactor 4.  Coordinates and scalars are 56 bytes, so nothing goes through the 64-byte entry points: scalar
+    multiplications, MSMs, the subgroup check and hashing to the curve run on the dr_curve448_* kernels (kernels_curve448.hip.h, on the
+    complete Edwards law birational to this curve), where the identity is 112 bytes of 0xff in and out.  The kernels use scalars as
+    they are; MGAffinePoint.__mul__ does not reduce its scalar (P * k is exact for every integer, a negative k negating the point), so
+    scalars go out reduced mod 4 n, the order of the whole group."""
+    _P = 2**448 - 2**224 - 1
+    _N = 2**446 - 0x8335DC163BB124B65129C96FDE933D8D723A70AADC873D6D54A7BB0D
+    _H, _CV = 4, _native.CURVE_CURVE448_RO
+    _MG_A, _FE_BYTES = 156326, 56
+    _WIDE = True                  # the VRF classes keep their Python orchestration: the native batch provers carry 32-byte scalars
+    _SUITE, _NO_IMAGE = "curve448", "No inverse exists"           # mod_inverse(0) of map_to_curve: u in {1, p - 1}
+    _IDENTITY_BYTES = b"\xff" * 112
+    __slots__ = ()
+
+    # -- the C ABI's forms
+    @classmethod
+    def _pack(cls, points) -> bytes:
+        return b"".join(cls._IDENTITY_BYTES if p.is_identity() else p.x.to_bytes(56, "little") + p.y.to_bytes(56, "little") for p in points)
+
+    @classmethod
+    def _unpack(cls, raw: bytes):
+        """Kernel outputs are group elements by construction: no per-point curve check."""
+        frm, mk = int.from_bytes, cls._trusted
+        return [mk(frm(raw[i : i + 56], "little"), frm(raw[i + 56 : i + 112], "little")) for i in range(0, len(raw), 112)]
+
+    @classmethod
+    def _scalars(cls, scalars) -> bytes:
+        return b"".join((int(k) % (cls._H * cls._N)).to_bytes(56, "little") for k in scalars)
+
+    @classmethod
+    def msm(cls, points, scalars):
+        if len(points) != len(scalars):
+            raise ValueError("Points and scalars must have same length")
+        acc = cls.identity()
+        for lo in range(0, len(points), 64):          # groups of up to 64 terms on the device, their sums added on the host
+            part = points[lo : lo + 64]
+            acc = acc + msm_groups(part, scalars[lo : lo + 64], len(part))[0]
+        return acc
+
+    # -- hash to curve (RFC 9380 curve448_XOF:SHAKE256_ELL2_RO_ / _NU_): expand_message_xof natively on the host, the map on the GPU
+    @classmethod
+    def map_to_curve(cls, u: int):
+        """MGAffinePoint.map_to_curve: ONE image with its cofactor not cleared; ValueError("No inverse exists") for u in {1, p - 1}"""
+        return cls._mapped((int(u) % cls._P).to_bytes(56, "little"), 1, clear=False)[0]
+
+    # -- what the module-level batch helpers ask a wide point type
+    @classmethod
+    def _scalar_mul_batch(cls, points, scalars):
+        return cls._unpack(runtime.context().curve448_scalar_mul_batch(cls._pack(points), cls._scalars(scalars)))
+
+    @classmethod
+    def _msm_groups(cls, points, scalars, m: int):
+        if m > 64:                               # the kernel folds up to 64 terms in a wave: longer groups fold on the host (msm)
+            return [cls.msm(points[i : i + m], scalars[i : i + m]) for i in range(0, len(points), m)]
+        return cls._unpack(runtime.context().curve448_msm_groups(cls._pack(points), cls._scalars(scalars), m))
+
+    @classmethod
+    def _valid_points(cls, points) -> list[bool]:
+        """curve.py:56 for a batch: on the curve, not the identity and n P = O (dr_curve448_decode_points with check = 1)"""
+        _, ok = runtime.context().curve448_decode_points(cls._pack(points), True)
+        return [bool(f) for f in ok]
 
 
 # ------------------------------------------------------------------ batched helpers over the C ABI
@@ -1745,3 +1823,25 @@ _ED448_PARAMS = SuiteParams(
 Ed448_RO = _variant(Ed448Point, "Ed448_RO", _ED448_PARAMS)
 Ed448_NU = _variant(Ed448Point, "Ed448_NU", _nu(_ED448_PARAMS, _native.CURVE_ED448_NU))
 Ed448 = Ed448_RO
+
+
+# dot_ring/curve/specs/curve448.py: v^2 = u^3 + 156326 u^2 + u over 2^448 - 2^224 - 1, cofactor 4, points 112 bytes u || v (point_len 56,
+# uncompressed), SHAKE256 transcript; no accumulator base and no padding point (no ring proofs).  Both variants share the suite id, as in
+# the reference.  challenge_len = 28 is the reference's own figure; its VRF layer squeezes 16 bytes whatever this says, and so does this one.
+_CURVE448_G = (5, 355293926785568175264127502063783334808976399387714271831880898435169088786967410002932673765864550910142774147268105838985595290606362)
+_CURVE448_PARAMS = SuiteParams(
+    suite_id=b"curve448_XOF:SHAKE256_ELL2_RO_", hash_fn=hashlib.shake_256, xof=True,
+    auxiliary_points=AuxiliaryPoints(_CURVE448_G, None, None),
+    field_modulus=Curve448Point._P,
+    subgroup_order=Curve448Point._N,
+    cofactor=4,
+    a=156326,
+    d=1,                          # (the reference's b)
+    generator=_CURVE448_G,
+    encoding=Encoding(point_len=56, challenge_len=28, uncompressed=True),
+    curve_id=_native.CURVE_CURVE448_RO,
+    e2c="ell2",
+)
+Curve448_RO = _variant(Curve448Point, "Curve448_RO", _CURVE448_PARAMS)
+Curve448_NU = _variant(Curve448Point, "Curve448_NU", _nu(_CURVE448_PARAMS, _native.CURVE_CURVE448_NU))
+Curve448 = Curve448_RO

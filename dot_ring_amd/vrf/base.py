@@ -33,6 +33,10 @@ class VRF:
             #  no accumulator base or padding point, as RingProofParams says, and the ring proof's columns are 32-byte scalars
             raise ValueError(f"{cls.__name__} has no {variant.name} suite: the curve has no accumulator base and no padding point, and its "
                              "56-byte coordinates do not fit the ring proof's columns")
+        if cls.RING and variant.curve.params.curve_id in (_native.CURVE_CURVE448_RO, _native.CURVE_CURVE448_NU):
+            # a Montgomery curve, as RingProofParams says, and the ring proof's columns are 32-byte scalars
+            raise ValueError(f"{cls.__name__} has no {variant.name} suite: ring proofs require a Twisted Edwards curve, and its 56-byte "
+                             "coordinates do not fit the ring proof's columns")
         bound = _BOUND.get((cls, variant.name))
         if bound is None or bound.cv is not variant:
             bound = _BOUND[(cls, variant.name)] = type(f"{cls.__name__}[{variant.name}]", (cls,), {"cv": variant})

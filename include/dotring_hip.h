@@ -401,6 +401,41 @@ DR_API int dr_ed448_decode_points(dr_ctx *ctx, int check, const uint8_t *enc /* 
 DR_API int dr_ed448_field_selftest(dr_ctx *ctx, const int32_t *a_limbs /* n*16 */, const int32_t *b_limbs /* n*16 */, size_t n,
                                    uint8_t *out /* n*11*56 */, uint8_t *flags /* n */);
 
+/* DR_CURVE_CURVE448_RO (the reference's Curve448 = Curve448_RO) and DR_CURVE_CURVE448_NU (Curve448_NU): the Montgomery curve
+ * v^2 = u^3 + 156326 u^2 + u over p = 2^448 - 2^224 - 1 (dot_ring/curve/specs/curve448.py over montgomery/mg_affine_point.py), cofactor 4,
+ * hashing by RFC 9380's curve448_XOF:SHAKE256_ELL2_RO_ (two field elements) or ..._NU_ (one) — csrc/kernels_curve448.hip.h, which computes
+ * on the complete Edwards law of csrc/c448_law.hip.h (the curve birational to curve448) over csrc/fe448.hip.h.  Entry points of their own
+ * (dr_curve448_*); every 64-byte entry point refuses these two ids with DR_ERR_INVALID, and so do the dr_blsg1_* / dr_blsg2_* /
+ * dr_ed448_* calls as variants.  Formats: field elements and coordinates are 56 bytes little-endian, canonical (< p); points are affine
+ * u || v, 112 bytes; scalars are 56 bytes used AS THEY ARE (any k < 2^448).  THE IDENTITY has no affine coordinates and (0, 0) is a point
+ * of the curve (order 2): at every entry point below the identity is 112 bytes of 0xff, in and out, and there are no flag-byte
+ * parameters.  Other coordinates or elements at or above p and other per_item values give DR_ERR_INVALID.
+ *   dr_curve448_hash_to_field_batch    host only: expand_message_xof over SHAKE256, L = 84, the variant's DST
+ *                                      (QUUX-V01-CS02-with-curve448_XOF:SHAKE256_ELL2_RO_ / ..._NU_); 112 bytes per message for RO, 56 for NU.
+ *   dr_curve448_map_to_curve           n items of per_item (2 or 1) elements: out_uv[i] = the sum of their Elligator 2 images, times 4 if
+ *                                      clear (clear = 0, per_item = 1: the reference's map_to_curve).  ok[i] = 0 and 112 zero bytes where an
+ *                                      image has no value: an element in {1, p - 1}, and no other (0 maps to (0, 0)).
+ *   dr_curve448_encode_to_curve_batch  encode_to_curve(salt_i || msg_i) (salts nullable); DR_ERR_INVALID if a map has no value.
+ *   dr_curve448_scalar_mul_batch       out[i] = k[i] P[i], the window loop on a fixed schedule (113 signed 4-bit windows); the final
+ *                                      inversion (division steps) is not fixed-time.
+ *   dr_curve448_msm_groups             out[g] = sum_{j<m} k[g m + j] P[g m + j], m <= 64.
+ *   dr_curve448_decode_points          ok[i] = 1 and out_uv[i] = enc[i] iff both coordinates are below p and the curve equation holds
+ *                                      ((0, 0) passes; 112 bytes of 0xff do not), and with check = 1 also n P = O; otherwise ok[i] = 0
+ *                                      and 112 zero bytes.
+ * The diagnostic of the field is dr_ed448_field_selftest. */
+enum { DR_CURVE_CURVE448_RO = 21, DR_CURVE_CURVE448_NU = 22 };
+DR_API int dr_curve448_hash_to_field_batch(int variant, const uint8_t *msgs, const uint64_t *off, size_t count, uint8_t *out /* count*(112|56) */);
+DR_API int dr_curve448_map_to_curve(dr_ctx *ctx, const uint8_t *us /* n*per_item*56 */, size_t n, int per_item, int clear,
+                                    uint8_t *out_uv /* n*112 */, uint8_t *ok /* n */);
+DR_API int dr_curve448_encode_to_curve_batch(dr_ctx *ctx, int variant, const uint8_t *msgs, const uint64_t *off, const uint8_t *salts,
+                                             const uint64_t *salt_off, size_t count, uint8_t *out_uv /* count*112 */);
+DR_API int dr_curve448_scalar_mul_batch(dr_ctx *ctx, const uint8_t *pts_uv /* n*112 */, const uint8_t *scalars /* n*56 */, size_t n,
+                                        uint8_t *out_uv /* n*112 */);
+DR_API int dr_curve448_msm_groups(dr_ctx *ctx, const uint8_t *pts_uv, const uint8_t *scalars, size_t groups, size_t m,
+                                  uint8_t *out_uv /* groups*112 */);
+DR_API int dr_curve448_decode_points(dr_ctx *ctx, int check, const uint8_t *enc /* n*112 */, size_t n, uint8_t *out_uv /* n*112 */,
+                                     uint8_t *ok /* n */);
+
 /* square root in the Bandersnatch base field; DR_ERR_NOTSQUARE if none exists. Host-side, no ctx. */
 DR_API int dr_fr_sqrt(const uint8_t in[32], uint8_t out[32]);
 

@@ -4,6 +4,7 @@ DESIGN.md compares it with.  `python3 tools/encode_timing.py SUITE YARDSTICK [co
   BLS12_381_G1_RO Secp256k1_RO      the only other SSWU-with-isogeny suite
   BLS12_381_G2_RO BLS12_381_G1_RO   the same field, chain and law one level down
   Ed448_RO Ed25519_RO               the same map one field down
+  Curve448_RO Ed448_RO              the same field and the same Elligator 2; another law and no isogeny after the map
 Each figure is ONE call after one warm-up call of the same size — unrepeated, to be quoted as such."""
 import os
 import sys

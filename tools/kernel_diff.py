@@ -5,7 +5,8 @@
 `make`) disassembles the gfx950 code objects of both (extracted as tools/count_kernel_insts.py does) and, for every kernel symbol
 present in both, compares opcode and operands of the whole instruction stream.  The one thing blanked is the literal of each
 s_add_u32 / s_addc_u32 that follows an s_getpc_b64: the PC-relative address of a constant, which moves with the layout of the code
-object.  Per symbol it prints `identical` or `different`; for a different one both instruction counts, both v_mad_i64_i32 counts
+object; and the run of s_nop at the very end of a listing is dropped (the alignment padding behind the LAST kernel of a code object,
+which belongs to another kernel once a unit gains one).  Per symbol it prints `identical` or `different`; for a different one both instruction counts, both v_mad_i64_i32 counts
 (the field products executed) and VGPR / AGPR / SGPR / LDS / scratch of both sides (tools/kernel_resources.py).  Symbols on one
 side only are listed.  Exit status 1 if a symbol differs or is missing.  Needs no GPU.
 """
@@ -45,6 +46,9 @@ def streams(build):
             elif after_getpc and op in ("s_add_u32", "s_addc_u32"):
                 args, after_getpc = _PCREL.sub("LIT", args), after_getpc - 1
             out[name].append(op + " " + args)
+    for ins in out.values():                   # the s_nop padding behind a code object's last kernel is listed under it: not executed
+        while ins and ins[-1].startswith("s_nop") and any(i.startswith("s_endpgm") for i in ins):
+            ins.pop()
     return kernels, out
 
 
