@@ -150,6 +150,14 @@ _PROTOTYPES.update({
     "dr_curve448_scalar_mul_batch": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_char_p]),
     "dr_curve448_msm_groups": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_size_t, c_char_p]),
     "dr_curve448_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
+    "dr_p521_hash_to_field_batch": (c_int, [c_int, c_char_p, POINTER(ctypes.c_uint64), c_size_t, c_char_p]),
+    "dr_p521_map_to_curve": (c_int, [c_void_p, c_char_p, c_size_t, c_int, c_int, c_char_p, c_char_p]),
+    "dr_p521_encode_to_curve_batch": (c_int, [c_void_p, c_int, c_char_p, POINTER(ctypes.c_uint64), c_char_p, POINTER(ctypes.c_uint64), c_size_t,
+                                      c_char_p]),
+    "dr_p521_scalar_mul_batch": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_char_p]),
+    "dr_p521_msm_groups": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_size_t, c_char_p]),
+    "dr_p521_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
+    "dr_p521_field_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p, c_void_p]),
     "dr_curve25519_scalar_mul_batch": (c_int, [c_void_p, c_char_p, c_char_p, c_char_p, c_size_t, c_char_p, c_char_p]),
     "dr_curve25519_msm_groups": (c_int, [c_void_p, c_char_p, c_char_p, c_char_p, c_size_t, c_size_t, c_char_p, c_char_p]),
     "dr_curve25519_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
@@ -250,6 +258,8 @@ CURVE_BLS12_381_G2, CURVE_BLS12_381_G2_NU = 17, 18
 CURVE_ED448_RO, CURVE_ED448_NU = 19, 20
 # Curve448 by RFC 9380: Montgomery u || v over Ed448's field, entry points of their own (dr_curve448_*), the identity 112 bytes of 0xff
 CURVE_CURVE448_RO, CURVE_CURVE448_NU = 21, 22
+# P-521 by RFC 9380: 68-byte coordinates and scalars (below 2^521), entry points of their own (dr_p521_*), the identity 136 zero bytes
+CURVE_P521_RO, CURVE_P521_NU = 23, 24
 # bytes of an encoded point, per curve id (the suites with 33-byte encodings and Curve25519's 64-byte u || v; every other curve's are 32)
 _POINT_LEN = {CURVE_BANDERSNATCH_SW: 33, CURVE_P256: 33, CURVE_SECP256K1: 33, CURVE_SECP256K1_NU: 33, CURVE_P256_RO: 33, CURVE_P256_NU: 33,
               CURVE_CURVE25519_RO: 64, CURVE_CURVE25519_NU: 64}
@@ -349,6 +359,7 @@ _WIDE = {
     "blsg2": _Wide(96, 192, 96, 192, 112, 5, CURVE_BLS12_381_G2_NU, "check_points"),
     "ed448": _Wide(56, 112, 56, 112, 64, 11, CURVE_ED448_NU, "decode_points"),
     "curve448": _Wide(56, 112, 56, 112, 64, 0, CURVE_CURVE448_NU, "decode_points"),       # (no field selftest: the field is Ed448's)
+    "p521": _Wide(68, 136, 68, 67, 76, 11, CURVE_P521_NU, "decode_points"),               # (decodes 67-byte SEC1 strings)
 }
 
 
@@ -365,6 +376,7 @@ blsg1_hash_to_field_batch = functools.partial(_wide_hash_to_field_batch, "blsg1"
 blsg2_hash_to_field_batch = functools.partial(_wide_hash_to_field_batch, "blsg2")
 ed448_hash_to_field_batch = functools.partial(_wide_hash_to_field_batch, "ed448")
 curve448_hash_to_field_batch = functools.partial(_wide_hash_to_field_batch, "curve448")
+p521_hash_to_field_batch = functools.partial(_wide_hash_to_field_batch, "p521")
 
 
 def lib() -> ctypes.CDLL:
@@ -703,7 +715,7 @@ class Context:
 
     # ---- the wide suites (include/dotring_hip.h; widths in _WIDE): BLS12-381 G1 (points 96 bytes x || y little-endian, 96 zero bytes the
     # identity), G2 (Fq2 elements c0 || c1; 192 zero bytes the identity), Ed448 (the identity (0, 1) as itself) and Curve448 (u || v, the
-    # identity 112 bytes of 0xff in and out); scalars as they are
+    # identity 112 bytes of 0xff in and out) and P-521 (136 zero bytes the identity; scalars below 2^521); scalars as they are
     def _wide_map_to_curve(self, suite: str, us: bytes, per_item: int, clear: bool = True):
         """dr_<suite>_map_to_curve: (x||y bytes, flags) for len(us) / (elem per_item) items; clear = False: before the cofactor clearing.
         per_item other than 1 or 2 is the library's to refuse."""
@@ -764,7 +776,7 @@ class Context:
 
     def _wide_field_selftest(self, suite: str, a_limbs: bytes, b_limbs: bytes):
         """dr_<suite>_field_selftest: (n x records x elem result bytes, n flag bytes) for n pairs of raw limb images (little-endian int32:
-        14 limbs for G1, 2 x 14 for G2, 16 for Ed448)."""
+        14 limbs for G1, 2 x 14 for G2, 16 for Ed448, 19 for P-521)."""
         w = _WIDE[suite]
         return self._limb_selftest(getattr(lib(), f"dr_{suite}_field_selftest"), w.records, a_limbs, b_limbs, w.limbs, w.elem)
 
@@ -789,6 +801,12 @@ class Context:
     curve448_scalar_mul_batch = functools.partialmethod(_wide_scalar_mul_batch, "curve448")
     curve448_msm_groups = functools.partialmethod(_wide_msm_groups, "curve448")
     curve448_decode_points = functools.partialmethod(_wide_flagged, "curve448")
+    p521_map_to_curve = functools.partialmethod(_wide_map_to_curve, "p521")
+    p521_encode_to_curve_batch = functools.partialmethod(_wide_encode_to_curve_batch, "p521")
+    p521_scalar_mul_batch = functools.partialmethod(_wide_scalar_mul_batch, "p521")
+    p521_msm_groups = functools.partialmethod(_wide_msm_groups, "p521")
+    p521_decode_points = functools.partialmethod(_wide_flagged, "p521")
+    p521_field_selftest = functools.partialmethod(_wide_field_selftest, "p521")
 
     def blsg2_check_points(self, pts_xy: bytes, subgroup: bool = True) -> bytes:
         """dr_blsg2_check_points: one flag byte per 192-byte point: on the curve, and with `subgroup` also r P = O."""

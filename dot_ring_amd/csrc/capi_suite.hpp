@@ -1,5 +1,5 @@
 // The one host path of every suite's single-launch entry points: the five 256-bit suites of capi_core.hip (Ed25519, P-256, Baby JubJub,
-// secp256k1, Curve25519) and the wide ones (capi_blsg1.hip, capi_blsg2.hip, capi_ed448.hip), whose coordinates do not fit 64-byte points.
+// secp256k1, Curve25519) and the wide ones (capi_blsg1.hip, capi_blsg2.hip, capi_ed448.hip, capi_p521.hip), whose coordinates do not fit 64-byte points.
 // No kernel is defined here.  A unit describes its suite in one struct S and its entry points are calls of the templates below; every one
 // of them is one io_round (capi_internal.hpp).  S has
 //   fe_bytes, elem_bytes, pt_bytes, scalar_bytes, limb_bytes   a base-field element, a hashed element (elem_bytes / fe_bytes components),
@@ -12,6 +12,7 @@
 //   canonical(p)                                               whether the fe_bytes at p are below the modulus
 //   consts_ready(ctx)                                          device constants a decoder or the selftest needs (SuiteDefaults: none)
 //   flagged                                                    the kernels carry an identity flag word beside each point (Curve25519, Curve448)
+//   checks_scalars; scalars_ok(scalars, n), scalar_refusal     whether the suite bounds its scalars (P-521: below 2^521), the check and its text
 //   map_flag_words(n, elems), map_launch(ctx, n, elems, per_item, clear)   the flag words of the map in io_c (the first n the items') and
 //                                                              its launches, elements in io_a, points to io_b
 // and a wide suite, for its hashing,
@@ -32,6 +33,7 @@ constexpr size_t MAX_SELFTEST = 1ull << 24;            // the field selftests' b
 struct SuiteDefaults {
     static int consts_ready(dr_ctx*) { return DR_OK; }
     static constexpr bool flagged = false;
+    static constexpr bool checks_scalars = false;      // true: run_points asks S::scalars_ok(scalars, n) before anything is uploaded
 };
 
 // BLS12-381's base field element (48 bytes little-endian) below p: shared by the G1 and G2 suites
@@ -121,6 +123,9 @@ int run_points(dr_ctx* ctx, const char* name, const uint8_t* pts_xy, const uint8
                const IdentityFlags* fl = nullptr) {
     if (!pts_xy || !scalars || !out_xy) return fail(DR_ERR_INVALID, "null buffer");
     if (n >= S::max_points) return fail(DR_ERR_INVALID, "batch too large");
+    if constexpr (S::checks_scalars) {
+        if (!S::scalars_ok(scalars, n)) return fail(DR_ERR_INVALID, S::scalar_refusal);
+    }
     if constexpr (S::flagged) {
         // the identities among the points become flag words behind the points in io_a (their bytes zeros), and the flag words the kernel
         // leaves behind its results in io_c become identities again; with the caller's own flags (fl) the points go as they are, so that

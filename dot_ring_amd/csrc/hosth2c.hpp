@@ -92,6 +92,33 @@ inline void fe_reduce_be84(const uint8_t* in, uint8_t* out) {
     std::memcpy(out, v, 56);
 }
 
+// 98 big-endian bytes (784 bits) mod P-521's p = 2^521 - 1 -> 68 bytes little-endian.  2^521 = 1: the value is lo + hi with lo its low
+// 521 bits and hi the 263 above; the sum is below 2^521 + 2^263, so folding its bit 521 once more leaves a value <= p, and p itself is 0
+inline void fp521_reduce_be98(const uint8_t* in, uint8_t* out) {
+    uint8_t le[112] = {0};
+    for (size_t i = 0; i < 98; i++) le[i] = in[97 - i];
+    uint64_t v[14], s[9];
+    std::memcpy(v, le, sizeof v);
+    unsigned __int128 c = 0;
+    for (int i = 0; i < 9; i++) {
+        const uint64_t lo = i < 8 ? v[i] : v[8] & 0x1ffull;
+        const uint64_t hi = i + 9 < 14 ? (v[i + 8] >> 9) | (v[i + 9] << 55) : 0;      // (v >> 521), words 0..4 non-zero
+        c += (unsigned __int128)lo + hi;
+        s[i] = (uint64_t)c;
+        c >>= 64;
+    }
+    uint64_t carry = s[8] >> 9;                          // bit 521
+    s[8] &= 0x1ffull;
+    for (int i = 0; i < 9 && carry; i++) {
+        s[i] += carry;
+        carry = s[i] == 0 ? 1 : 0;
+    }
+    bool is_p = s[8] == 0x1ffull;
+    for (int i = 0; i < 8; i++) is_p = is_p && s[i] == ~0ull;
+    if (is_p) std::memset(s, 0, sizeof s);
+    std::memcpy(out, s, 68);
+}
+
 // hash_to_field of the BLS12-381 suites: expand_message_xmd over SHA-256 to `chunks` x 64 bytes (at most 4), each big-endian mod p;
 // out = chunks x 48 bytes little-endian.  G1 asks for one chunk per element, G2 for two (c0 || c1).
 inline void hash_to_field_fq(const void* dst, size_t dst_len, unsigned chunks, const uint8_t* salt, size_t salt_len, const uint8_t* msg, size_t len,
@@ -106,6 +133,13 @@ inline void hash_to_field_fe448(const void* dst, size_t dst_len, unsigned count,
     uint8_t raw[168];
     expand_message_xof(dst, dst_len, salt, salt_len, msg, len, 84 * (size_t)count, raw);
     for (unsigned k = 0; k < count; k++) fe_reduce_be84(raw + 84 * k, out + 56 * k);
+}
+// hash_to_field of the P-521 suites: expand_message_xmd over SHA-512 to count x 98 bytes (at most 2); out = count x 68 bytes little-endian
+inline void hash_to_field_fp521(const void* dst, size_t dst_len, unsigned count, const uint8_t* salt, size_t salt_len, const uint8_t* msg, size_t len,
+                                uint8_t* out) {
+    uint8_t raw[196];
+    expand_message_xmd<Sha512, 128, 64>(dst, dst_len, salt, salt_len, msg, len, 98 * (size_t)count, raw);
+    for (unsigned k = 0; k < count; k++) fp521_reduce_be98(raw + 98 * k, out + 68 * k);
 }
 
 }  // namespace drh

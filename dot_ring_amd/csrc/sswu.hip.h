@@ -15,8 +15,12 @@
 //   BLOCK, identity(), add(P, Q), unpack(w), pack(a, w), inv(a)    as wave_curve.hip.h asks them of its description: a curve's SSWU
 //                                  description derives from that one
 #pragma once
+#if defined(__HIPCC__)
 #include "field.hip.h"
 #include "wave_curve.hip.h"
+#else                                  // a host build of sswu_map and sswu_iso_map alone (tests/native/p521_host_check.cpp)
+#define DR_DEV static inline
+#endif
 
 namespace dr {
 
@@ -83,6 +87,7 @@ DR_DEV typename C::Point sswu_iso_map(const typename C::Fe& xn, const typename C
     }
 }
 
+#if defined(__HIPCC__)
 // out[i] = the sum of the images of item i's `per_item` field elements (2: the uniform (RO) encoding, 1: the nonuniform one), u: n x
 // per_item x 8 words (canonical, checked by the host), out: n x 16 words affine x || y, ok[i] = 0 where an isogeny denominator
 // vanished.  One lane per item; one exponentiation per element and one inversion per item.  The body of both map kernels.
@@ -111,5 +116,6 @@ DR_DEV void sswu_map_to_curve(const uint32_t* __restrict__ us, uint32_t* __restr
         ok[i] = good ? 1u : 0u;
     }
 }
+#endif
 
 }  // namespace dr

@@ -1441,6 +1441,87 @@ class Curve448Point(_WideRfc9380, _MontgomeryPoint):
 
 
 # ------------------------------------------------------------------ batched helpers over the C ABI
+class P521Point(_WideRfc9380, _Sec1Codec, _ShortWeierstrassPoint):
+    """Affine point of P521_RO / P521_NU (dot_ring/curve/specs/p521.py): y^2 = x^3 - 3 x + b over p = 2^521 - 1, prime order, cofactor 1,
+    the identity (None, None).  Coordinates and scalars are 66 bytes (68 at the C ABI), so nothing here goes through the 64-byte entry
+    points: scalar multiplications, MSMs, decoding and hashing to the curve run on the dr_p521_* kernels (kernels_p521.hip.h), whose
+    scalars are used as they are below 2^521 — the reduction mod n happens here and is exact for every point, the group having prime
+    order n.  Single additions are the shared host big-int law; SEC1 strings carry 66-byte coordinates."""
+    _P = 2**521 - 1
+    _N = 0x01FFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFA51868783BF2F966B7FCC0148F709A5D03BB5C9B8899C47AEBB6FB71E91386409
+    _H, _CV = 1, _native.CURVE_P521_RO
+    _SW_A = -3
+    _SW_B = 0x0051953EB9618E1C9A1F929A21A0B68540EEA2DA725B99B315F3B8B489918EF109E156193951EC7E937B1652C0BD3BB1BF073573DF883D2C34F1EF451FD46B503F00
+    _SEC1_LEN = 66
+    _WIDE = True                  # the VRF classes keep their Python orchestration: the native batch provers carry 32-byte scalars
+    _SUITE, _NO_IMAGE = "p521", "the map to the curve has no value"       # (never raised: every field element has an image)
+    __slots__ = ()
+
+    # -- the C ABI's forms: x || y, 68 + 68 bytes little-endian, 136 zero bytes the identity
+    @staticmethod
+    def _pack(points) -> bytes:
+        return b"".join((p.x or 0).to_bytes(68, "little") + (p.y or 0).to_bytes(68, "little") for p in points)
+
+    @classmethod
+    def _unpack(cls, raw: bytes):
+        """Kernel outputs are group elements by construction: no per-point curve check."""
+        frm, mk = int.from_bytes, cls._trusted
+        return [mk(frm(raw[i : i + 68], "little"), frm(raw[i + 68 : i + 136], "little")) for i in range(0, len(raw), 136)]
+
+    @classmethod
+    def _scalars(cls, scalars) -> bytes:
+        return b"".join((int(k) % cls._N).to_bytes(68, "little") for k in scalars)
+
+    def __mul__(self, scalar: int):
+        return self._scalar_mul_batch([self], [scalar])[0]
+
+    __rmul__ = __mul__
+
+    @classmethod
+    def msm(cls, points, scalars):
+        if len(points) != len(scalars):
+            raise ValueError("Points and scalars must have same length")
+        acc = cls.identity()
+        for lo in range(0, len(points), 64):          # groups of up to 64 terms on the device, their sums added on the host
+            part = points[lo : lo + 64]
+            acc = acc + msm_groups(part, scalars[lo : lo + 64], len(part))[0]
+        return acc
+
+    def clear_cofactor(self):
+        return self                                   # the cofactor is 1
+
+    # -- codec: SEC1 with 66-byte coordinates; a compressed string's root is p = 3 mod 4's, on the host
+    @classmethod
+    def _sec1_decompress(cls, prefix: int, x: int):
+        p = cls._P
+        v = (x * x * x + cls._SW_A * x + cls._SW_B) % p
+        y = pow(v, (p + 1) // 4, p)
+        if y * y % p != v:
+            raise ValueError("Invalid point encoding")
+        return cls(x, y if y % 2 == prefix % 2 else p - y)
+
+    # -- hash to curve (RFC 9380 P521_XMD:SHA-512_SSWU_RO_ / _NU_): expand_message_xmd natively on the host, the map on the GPU
+    @classmethod
+    def map_to_curve_simple_swu(cls, u: int):
+        return cls._mapped((int(u) % cls._P).to_bytes(68, "little"), 1, clear=False)[0]
+
+    # -- what the module-level batch helpers ask a wide point type
+    @classmethod
+    def _scalar_mul_batch(cls, points, scalars):
+        return cls._unpack(runtime.context().p521_scalar_mul_batch(cls._pack(points), cls._scalars(scalars)))
+
+    @classmethod
+    def _msm_groups(cls, points, scalars, m: int):
+        if m > 64:                               # the kernel folds up to 64 terms in a wave: longer groups fold on the host (msm)
+            return [cls.msm(points[i : i + m], scalars[i : i + m]) for i in range(0, len(points), m)]
+        return cls._unpack(runtime.context().p521_msm_groups(cls._pack(points), cls._scalars(scalars), m))
+
+    @classmethod
+    def _valid_points(cls, points) -> list[bool]:
+        """curve.py:56 for a batch: on the curve and not the identity (prime order: nothing else to ask)"""
+        return [not pt.is_identity() and pt.is_on_curve() for pt in points]
+
+
 def pack_points(points) -> bytes:
     """x || y little-endian per point; an SW identity ((None, None)) packs as 64 zero bytes, as the ABI takes it, Curve25519's — where
     (0, 0) is a point — as 64 bytes of 0xff."""
@@ -1845,3 +1926,28 @@ _CURVE448_PARAMS = SuiteParams(
 Curve448_RO = _variant(Curve448Point, "Curve448_RO", _CURVE448_PARAMS)
 Curve448_NU = _variant(Curve448Point, "Curve448_NU", _nu(_CURVE448_PARAMS, _native.CURVE_CURVE448_NU))
 Curve448 = Curve448_RO
+
+
+# dot_ring/curve/specs/p521.py: y^2 = x^3 - 3 x + b over 2^521 - 1, prime order, cofactor 1, SEC1 compressed points of 67 bytes, 66-byte
+# scalars, SHA-512 transcripts, hashing to the curve by RFC 9380's P521_XMD:SHA-512_SSWU_RO_ (two field elements, L = 98, Z = -4) or
+# ..._NU_ (one); both variants share the RO suite id, and the Pedersen blinding base IS the generator, as in the reference.  No accumulator
+# base or padding point and not twisted Edwards: RingProofParams refuses them.  challenge_len = 32 is the reference's own figure; its VRF
+# layer squeezes 16 bytes whatever this says, and so does this one.
+_P521_G = (0x00C6858E06B70404E9CD9E3ECB662395B4429C648139053FB521F828AF606B4D3DBAA14B5E77EFE75928FE1DC127A2FFA8DE3348B3C1856A429BF97E7E31C2E5BD66,
+           0x011839296A789A3BC0045C8A5FB42C7D1BD998F54449579B446817AFBD17273E662C97EE72995EF42640C550B9013FAD0761353C7086A272C24088BE94769FD16650)
+_P521_PARAMS = SuiteParams(
+    suite_id=b"P521_XMD:SHA-512_SSWU_RO_", hash_fn=hashlib.sha512, xof=False,
+    auxiliary_points=AuxiliaryPoints(_P521_G, None, None),
+    field_modulus=P521Point._P,
+    subgroup_order=P521Point._N,
+    cofactor=1,
+    a=-3,
+    d=P521Point._SW_B,            # (the reference's b)
+    generator=_P521_G,
+    encoding=Encoding(point_len=67, challenge_len=32),
+    curve_id=_native.CURVE_P521_RO,
+    e2c="sswu",
+)
+P521_RO = _variant(P521Point, "P521_RO", _P521_PARAMS)
+P521_NU = _variant(P521Point, "P521_NU", _nu(_P521_PARAMS, _native.CURVE_P521_NU))
+P521 = P521_RO

@@ -436,6 +436,45 @@ DR_API int dr_curve448_msm_groups(dr_ctx *ctx, const uint8_t *pts_uv, const uint
 DR_API int dr_curve448_decode_points(dr_ctx *ctx, int check, const uint8_t *enc /* n*112 */, size_t n, uint8_t *out_uv /* n*112 */,
                                      uint8_t *ok /* n */);
 
+/* DR_CURVE_P521_RO (the reference's P521 = P521_RO) and DR_CURVE_P521_NU (P521_NU): P-521, y^2 = x^3 - 3 x + b over p = 2^521 - 1
+ * (dot_ring/curve/specs/p521.py), prime order, cofactor 1, hashing by RFC 9380's P521_XMD:SHA-512_SSWU_RO_ (two field elements) or
+ * ..._NU_ (one) — csrc/kernels_p521.hip.h on the complete law of csrc/p521_law.hip.h over csrc/fp521.hip.h.  Entry points of their own
+ * (dr_p521_*); every 64-byte entry point refuses these two ids with DR_ERR_INVALID, and so do the dr_blsg1_* / dr_blsg2_* / dr_ed448_* /
+ * dr_curve448_* calls as variants.  Formats: field elements and coordinates are 68 bytes little-endian, canonical (< p); points are
+ * affine x || y, 136 bytes, and 136 ZERO BYTES ARE THE IDENTITY, in and out ((0, 0) is not on the curve); scalars are 68 bytes
+ * little-endian below 2^521, used AS THEY ARE (a scalar at or above 2^521 gives DR_ERR_INVALID before anything is uploaded).  Coordinates
+ * or elements at or above p and other per_item values give DR_ERR_INVALID.
+ *   dr_p521_hash_to_field_batch    host only: expand_message_xmd over SHA-512, L = 98 bytes per element, the variant's DST
+ *                                  (QUUX-V01-CS02-with-P521_XMD:SHA-512_SSWU_RO_ / ..._NU_); two elements (136 bytes) per message for RO,
+ *                                  one (68) for NU.
+ *   dr_p521_map_to_curve           n items of per_item (2 or 1) elements: out_xy[i] = the sum of their simplified SWU images (Z = -4, no
+ *                                  isogeny).  ok[i] = 1 always: every element has an image.  The cofactor is 1: `clear` changes nothing.
+ *   dr_p521_encode_to_curve_batch  encode_to_curve(salt_i || msg_i) (salts nullable): hash_to_field on the worker threads, then the map.
+ *   dr_p521_scalar_mul_batch       out[i] = k[i] P[i], the window loop on a fixed schedule (131 signed 4-bit windows) as for the other
+ *                                  native suites; the final inversion of Z (division steps) is not fixed-time.
+ *   dr_p521_msm_groups             out[g] = sum_{j<m} k[g m + j] P[g m + j], m <= 64.
+ *   dr_p521_decode_points          SEC1 compressed, 67 bytes: ok[i] = 1 and out_xy[i] = x || y iff byte 0 is 0x02 or 0x03, x (bytes 1..66
+ *                                  big-endian) is below p and x^3 - 3 x + b is a square, y of byte 0's parity; otherwise ok[i] = 0 and
+ *                                  136 zero bytes.  No string encodes the identity and the cofactor is 1, so check = 0 and check = 1 are
+ *                                  the same kernel; the parameter is the suites' common signature.
+ *   dr_p521_field_selftest         diagnostic of csrc/fp521.hip.h on RAW limb images (19 signed 32-bit limbs an element): out[i] = eleven
+ *                                  68-byte canonical records (a b, a^2, a + b, a - b, -a, carry(a), 4 a, a^-1, carry(a)^((p + 1) / 4), a,
+ *                                  -(2^28 - 1) a), flags[i]: bit 0 a is a square, bit 1 a is odd, bit 2 a is zero, bit 3 a = b. */
+enum { DR_CURVE_P521_RO = 23, DR_CURVE_P521_NU = 24 };
+DR_API int dr_p521_hash_to_field_batch(int variant, const uint8_t *msgs, const uint64_t *off, size_t count, uint8_t *out /* count*(136|68) */);
+DR_API int dr_p521_map_to_curve(dr_ctx *ctx, const uint8_t *us /* n*per_item*68 */, size_t n, int per_item, int clear,
+                                uint8_t *out_xy /* n*136 */, uint8_t *ok /* n */);
+DR_API int dr_p521_encode_to_curve_batch(dr_ctx *ctx, int variant, const uint8_t *msgs, const uint64_t *off, const uint8_t *salts,
+                                         const uint64_t *salt_off, size_t count, uint8_t *out_xy /* count*136 */);
+DR_API int dr_p521_scalar_mul_batch(dr_ctx *ctx, const uint8_t *pts_xy /* n*136 */, const uint8_t *scalars /* n*68 */, size_t n,
+                                    uint8_t *out_xy /* n*136 */);
+DR_API int dr_p521_msm_groups(dr_ctx *ctx, const uint8_t *pts_xy, const uint8_t *scalars, size_t groups, size_t m,
+                              uint8_t *out_xy /* groups*136 */);
+DR_API int dr_p521_decode_points(dr_ctx *ctx, int check, const uint8_t *enc /* n*67 */, size_t n, uint8_t *out_xy /* n*136 */,
+                                 uint8_t *ok /* n */);
+DR_API int dr_p521_field_selftest(dr_ctx *ctx, const int32_t *a_limbs /* n*19 */, const int32_t *b_limbs /* n*19 */, size_t n,
+                                  uint8_t *out /* n*11*68 */, uint8_t *flags /* n */);
+
 /* square root in the Bandersnatch base field; DR_ERR_NOTSQUARE if none exists. Host-side, no ctx. */
 DR_API int dr_fr_sqrt(const uint8_t in[32], uint8_t out[32]);
 
