@@ -157,7 +157,7 @@ DR_DEV void bjj_reduce_mod_order(uint32_t (&k)[8]) {
 struct BjjCurve {
     using Fe = Fbn;
     using Point = BjjPoint;
-    static constexpr int WORDS = 8, BLOCK = BJJ_BLOCK, WINDOWS = 64, LDS_WORDS = 8;
+    static constexpr int WORDS = 8, SCALAR_WORDS = 8, BLOCK = BJJ_BLOCK, WINDOWS = 64, LDS_WORDS = 8;
     static constexpr bool EXTENDED = true, ZERO_IS_IDENTITY = false;
     DR_DEV static Fbn unpack(const uint32_t (&w)[8]) { return bn_unpack(w); }
     DR_DEV static void pack(const Fbn& a, uint32_t (&w)[8]) { bn_pack(a, w); }

@@ -8,8 +8,8 @@
 // on output); the host turns 112 bytes of 0xff into that flag and back (capi_suite.hpp, run_points).  The map writes the 0xff bytes
 // itself, because its flag word says whether the item has a value at all.
 //
-// The schedule is kernels_ed448.hip.h's e448_scalar_mul_core restated over a curve description (that header stays byte-identical, and
-// with it every Ed448 symbol); the memory forms (seven uint4 a point, seven uint2 a scalar) and the LDS helpers are used as they are.
+// The schedule is wave_curve.hip.h's over Curve448Curve, which gives the law and the table forms; the memory forms (seven uint4 a point,
+// seven uint2 a scalar) are that header's too.  The kernel bodies stay here: they carry the flag words.
 // Included by capi_ed448.hip after kernels_ed448.hip.h: one unit per kernel header, and no second copy of the Ed448 kernels.
 #pragma once
 #include "c448_law.hip.h"
@@ -20,7 +20,7 @@ namespace dr {
 struct Curve448Curve {
     using Fe = F448;
     using Point = M448Point;
-    static constexpr int BLOCK = E448_BLOCK, LDS_WORDS = L448;
+    static constexpr int SCALAR_WORDS = W448, BLOCK = E448_BLOCK, WINDOWS = E448_WINDOWS, LDS_WORDS = L448;   // any k < 2^448
     static constexpr bool EXTENDED = false;
     DR_DEV static void to_lds(const F448& a, uint32_t (&w)[L448]) { wave_limbs_to_words(a, w); }
     DR_DEV static F448 from_lds(const uint32_t (&w)[L448]) { return wave_words_to_limbs<F448>(w); }
@@ -30,53 +30,10 @@ struct Curve448Curve {
     DR_DEV static M448Point identity() { return m448_identity(); }
 };
 
-// k P for ANY k < 2^448 on the fixed schedule of e448_scalar_mul_core: table 1P..8P in LDS (8 x 3 x 16 words x 64 lanes x 4 = 98 304
-// bytes, one workgroup per CU), 112 signed 4-bit windows and the carry out of the last digit as a 113th, four doublings and one table
-// addition each whatever the digits.  What "fixed schedule" covers is said there: the window loop alone, not the store's inversion.
-template <class C>
-DR_DEV typename C::Point w448_scalar_mul_core(uint32_t* tab, int lane, const typename C::Point& P, const uint32_t (&k)[W448]) {
-    using Point = typename C::Point;
-    wave_lds_store<C>(tab, 0, lane, P);
-    Point Q = C::dbl(P);
-    wave_lds_store<C>(tab, 1, lane, Q);
-#pragma unroll 1
-    for (int e = 2; e < WAVE_TABLE; e++) {
-        Q = C::add(Q, P);
-        wave_lds_store<C>(tab, e, lane, Q);
-    }
-    uint32_t dig[W448];              // digits 0..111 in [-8, 7], stored as d + 8; digit 112 = top_carry
-    uint32_t carry_in = 0;
-#pragma unroll
-    for (int w = 0; w < W448; w++) {
-        uint32_t packed = 0;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const uint32_t v = ((k[w] >> (4 * j)) & 15u) + carry_in;
-            carry_in = v >= 8u ? 1u : 0u;
-            packed |= ((v + 8u) & 15u) << (4 * j);
-        }
-        dig[w] = packed;
-    }
-    const uint32_t top_carry = carry_in;
-    Point acc = C::identity();
-#pragma unroll 1
-    for (int w = E448_WINDOWS - 1; w >= 0; w--) {
-#pragma unroll 1
-        for (int j = 0; j < 4; j++) acc = C::dbl(acc);
-        const int dg = w == E448_WINDOWS - 1 ? (int)top_carry : (int)((dig[w >> 3] >> (4 * (w & 7))) & 15u) - 8;
-        const int mag = dg < 0 ? -dg : dg;
-        Point T = wave_lds_load<C>(tab, mag == 0 ? 0 : mag - 1, lane);
-        T = C::cneg(T, dg < 0);
-        if (mag == 0) T = C::identity();
-        acc = C::add(acc, T);
-    }
-    return acc;
-}
-
 // ---------------------------------------------------------------- memory forms
 DR_DEV M448Point c448_load_term(const uint32_t* pt, uint32_t flag) {
     uint32_t u[W448], v[W448];
-    e448_load_point_words(pt, u, v);
+    wave_load_point_words(pt, u, v);
     return m448_load(unpack(u), unpack(v), flag != 0);
 }
 // u || v of a point (28 words); true for the identity, which stores zeros.  (0 : -1 : 1) stores (0, 0)
@@ -86,7 +43,7 @@ DR_DEV bool c448_store(uint32_t* out, const M448Point& p) {
     uint32_t uw[W448], vw[W448];
     pack(u, uw);
     pack(v, vw);
-    e448_store_point_words(out, uw, vw);
+    wave_store_point_words(out, uw, vw);
     return ident;
 }
 DR_DEV void c448_store_fill(uint32_t* p, uint32_t word) {
@@ -96,7 +53,9 @@ DR_DEV void c448_store_fill(uint32_t* p, uint32_t word) {
 }
 
 // out[i] = k[i] P[i].  pts: n x 28 words u || v canonical, ks: n x 14, id_in / id_out: n flag words, out: n x 28.  One lane per
-// multiplication; the operand order is capi_suite.hpp's launch_points for a flagged suite.
+// multiplication; the operand order is capi_suite.hpp's launch_points for a flagged suite.  The schedule of the (secret) scalar is
+// wave_curve.hip.h's: 8 x 3 x 16 table words x 64 lanes x 4 = 98 304 bytes of LDS, one workgroup per CU.  (The body is wave_scalar_mul's
+// with this file's load and store forms: a change to that template's lane handling belongs here too.)
 __global__ __launch_bounds__(E448_BLOCK) void k_c448_scalar_mul(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks,
                                                                 const uint32_t* __restrict__ id_in, uint32_t* __restrict__ out,
                                                                 uint32_t* __restrict__ id_out, uint32_t n) {
@@ -106,14 +65,15 @@ __global__ __launch_bounds__(E448_BLOCK) void k_c448_scalar_mul(const uint32_t* 
     const bool live = i < n;
     if (!live) i = n - 1;            // keep the wave converged; the duplicate result is not stored
     uint32_t k[W448];
-    e448_load_elem_words(ks + (size_t)i * W448, k);
+    wave_load_words(ks + (size_t)i * W448, k);
     const M448Point P = c448_load_term(pts + (size_t)i * E448_PT_WORDS, id_in[i]);
-    const M448Point acc = w448_scalar_mul_core<Curve448Curve>(tab, lane, P, k);
+    const M448Point acc = wave_scalar_mul_core<Curve448Curve>(tab, lane, P, k);
     if (live) id_out[i] = c448_store(out + (size_t)i * E448_PT_WORDS, acc) ? 1u : 0u;
 }
 
 // out[g] = sum_{j<m} k[g m + j] P[g m + j]: one lane per term (m padded to mpad, a power of two <= 64), folded with shuffles by the
-// complete addition (terms that coincide or cancel need nothing special)
+// complete addition (terms that coincide or cancel need nothing special).  (The body is wave_msm_groups' with this file's load and store
+// forms: a change to that template's lane handling or fold belongs here too.)
 __global__ __launch_bounds__(E448_BLOCK) void k_c448_msm_groups(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks,
                                                                 const uint32_t* __restrict__ id_in, uint32_t* __restrict__ out,
                                                                 uint32_t* __restrict__ id_out, uint32_t groups, uint32_t m, uint32_t mpad) {
@@ -125,9 +85,9 @@ __global__ __launch_bounds__(E448_BLOCK) void k_c448_msm_groups(const uint32_t* 
     const bool live = g < groups && j < m;
     const size_t idx = live ? (size_t)g * m + j : 0;          // dead lanes recompute term 0 and are masked out
     uint32_t k[W448];
-    e448_load_elem_words(ks + idx * W448, k);
+    wave_load_words(ks + idx * W448, k);
     const M448Point P = c448_load_term(pts + idx * E448_PT_WORDS, id_in[idx]);
-    const M448Point r = w448_scalar_mul_core<Curve448Curve>(tab, lane, P, k);
+    const M448Point r = wave_scalar_mul_core<Curve448Curve>(tab, lane, P, k);
     M448Point acc = live ? r : m448_identity();
 #pragma unroll 1
     for (uint32_t s = mpad >> 1; s > 0; s >>= 1) acc = m448_add(acc, wave_shfl_down<Curve448Curve>(acc, s));
@@ -149,7 +109,7 @@ __global__ __launch_bounds__(E448_BLOCK) void k_curve448_map_to_curve(const uint
 #pragma unroll 1
     for (uint32_t e = 0; e < per_item; e++) {
         uint32_t w[W448];
-        e448_load_elem_words(us + ((size_t)i * per_item + e) * W448, w);
+        wave_load_words(us + ((size_t)i * per_item + e) * W448, w);
         F448 N, D, v;
         bool has_value;
         m448_ell2(unpack(w), N, D, v, has_value);
@@ -171,7 +131,7 @@ __global__ __launch_bounds__(E448_BLOCK) void k_curve448_map_to_curve(const uint
 
 // Decoding (the reference's MGAffinePoint.string_to_point), one lane per 112-byte u || v.  CHECK = 0: both coordinates below p and
 // v^2 = u^3 + A u^2 + u ((0, 0) and the points of order 4 pass; a record of 0xff bytes does not).  CHECK = 1: additionally n P = O by
-// the schedule above over the public words of n (a decoded point is never the identity; (0, 0) has order 2 and fails).  out = the input
+// the fixed schedule over the public words of n (a decoded point is never the identity; (0, 0) has order 2 and fails).  out = the input
 // and ok = 1, or 112 zero bytes and ok = 0.
 template <int CHECK>
 __global__ __launch_bounds__(E448_BLOCK) void k_c448_decode_points(const uint32_t* __restrict__ enc, uint32_t* __restrict__ out_uv,
@@ -182,7 +142,7 @@ __global__ __launch_bounds__(E448_BLOCK) void k_c448_decode_points(const uint32_
     const bool live = i < n;
     if (!live) i = n - 1;
     uint32_t uw[W448], vw[W448];
-    e448_load_point_words(enc + (size_t)i * E448_PT_WORDS, uw, vw);
+    wave_load_point_words(enc + (size_t)i * E448_PT_WORDS, uw, vw);
     bool valid = below_p(uw) && below_p(vw);
     const F448 u = unpack(uw), v = unpack(vw);
     valid = valid && m448_on_curve(u, v);
@@ -191,11 +151,11 @@ __global__ __launch_bounds__(E448_BLOCK) void k_c448_decode_points(const uint32_
         uint32_t k[W448];
 #pragma unroll
         for (int j = 0; j < W448; j++) k[j] = E448_ORDER[j];
-        valid = m448_is_identity(w448_scalar_mul_core<Curve448Curve>(tab, lane, P, k)) && valid;
+        valid = m448_is_identity(wave_scalar_mul_core<Curve448Curve>(tab, lane, P, k)) && valid;
     }
     if (live) {
-        if (valid) e448_store_point_words(out_uv + (size_t)i * E448_PT_WORDS, uw, vw);
-        else e448_store_zero_point(out_uv + (size_t)i * E448_PT_WORDS);
+        if (valid) wave_store_point_words(out_uv + (size_t)i * E448_PT_WORDS, uw, vw);
+        else wave_store_zero_words<E448_PT_WORDS>(out_uv + (size_t)i * E448_PT_WORDS);
         ok[i] = valid ? 1u : 0u;
     }
 }

@@ -86,7 +86,7 @@ DR_DEV void ed_reduce_mod_order(uint32_t (&k)[8]) {
 struct Ed25519Curve {
     using Fe = F25;
     using Point = EdPoint;
-    static constexpr int WORDS = 8, BLOCK = ED_BLOCK, WINDOWS = 64, LDS_WORDS = 8;
+    static constexpr int WORDS = 8, SCALAR_WORDS = 8, BLOCK = ED_BLOCK, WINDOWS = 64, LDS_WORDS = 8;
     static constexpr bool EXTENDED = true, ZERO_IS_IDENTITY = false;
     DR_DEV static F25 unpack(const uint32_t (&w)[8]) { return fe_unpack(w); }
     DR_DEV static void pack(const F25& a, uint32_t (&w)[8]) { fe_pack(a, w); }

@@ -12,9 +12,7 @@
 // instead of 64 and three quarters of the LDS table.  The comments give the limb class of every intermediate against fe448.hip.h's
 // contract ("n" = normal, "k n" = |limb| <= k normal; mul needs ka kb <= 3, sqr 1 n).
 //
-// The schedule is wave_curve.hip.h's (LDS table 1P..8P, signed 4-bit windows, four doublings and one table addition whatever the digits),
-// restated here for 14 scalar words and 113 windows: that header fixes scalars at 8 words and coordinates at a multiple of 4, and it
-// stays byte-identical.  Its table, shuffle and limb-image helpers, which depend on neither, are used as they are.
+// The schedule, the memory forms and the two kernel bodies are wave_curve.hip.h's over Ed448Curve: 14 scalar words, 113 windows.
 #pragma once
 #include "fe448.hip.h"
 #include "wave_curve.hip.h"
@@ -68,143 +66,36 @@ DR_DEV E448Point e448_add(const E448Point& p, const E448Point& q) {
 }
 DR_DEV E448Point e448_cneg(const E448Point& p, bool negate) { return {cneg(p.x, negate), p.y, p.z}; }
 
-// what wave_curve.hip.h's table and shuffle helpers need of a curve description: the table keeps the limb images (no packing)
+// wave_curve.hip.h's description of Ed448: canonical words at the ABI (14 per coordinate; the identity is (0, 1) as itself), the limb
+// images in the LDS table (no packing), and 113 windows over the scalar AS IT IS: 112 nibbles of any k < 2^448 and the carry out of the
+// last digit.  Z is never 0 (the law is complete), so the affine store needs nothing special.
 struct Ed448Curve {
     using Fe = F448;
     using Point = E448Point;
-    static constexpr int BLOCK = E448_BLOCK, LDS_WORDS = L448;
-    static constexpr bool EXTENDED = false;
+    static constexpr int WORDS = W448, SCALAR_WORDS = W448, BLOCK = E448_BLOCK, WINDOWS = E448_WINDOWS, LDS_WORDS = L448;
+    static constexpr bool EXTENDED = false, ZERO_IS_IDENTITY = false;
+    DR_DEV static F448 unpack(const uint32_t (&w)[W448]) { return dr::unpack(w); }
+    DR_DEV static void pack(const F448& a, uint32_t (&w)[W448]) { dr::pack(a, w); }
+    DR_DEV static F448 inv(const F448& a) { return dr::inv(a); }                                  // 1 n
     DR_DEV static void to_lds(const F448& a, uint32_t (&w)[L448]) { wave_limbs_to_words(a, w); }
     DR_DEV static F448 from_lds(const uint32_t (&w)[L448]) { return wave_words_to_limbs<F448>(w); }
+    DR_DEV static E448Point identity() { return e448_identity(); }
+    DR_DEV static E448Point from_affine(const F448& x, const F448& y) { return e448_from_affine(x, y); }
     DR_DEV static E448Point add(const E448Point& p, const E448Point& q) { return e448_add(p, q); }
+    DR_DEV static E448Point dbl(const E448Point& p) { return e448_dbl(p); }
+    DR_DEV static E448Point cneg(const E448Point& p, bool negate) { return e448_cneg(p, negate); }
+    DR_DEV static void load_scalar(const uint32_t* p, uint32_t (&k)[W448]) { wave_load_words(p, k); }    // no reduction (head of the file)
 };
-
-// ---------------------------------------------------------------- memory forms
-DR_DEV void e448_load_elem_words(const uint32_t* p, uint32_t (&w)[W448]) {           // 56 bytes: 8-byte aligned
-    const uint2* q = reinterpret_cast<const uint2*>(p);
-#pragma unroll
-    for (int j = 0; j < W448 / 2; j++) {
-        const uint2 a = q[j];
-        w[2 * j] = a.x; w[2 * j + 1] = a.y;
-    }
-}
-DR_DEV void e448_load_point_words(const uint32_t* p, uint32_t (&x)[W448], uint32_t (&y)[W448]) {   // 112 bytes: 16-byte aligned
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    uint32_t w[E448_PT_WORDS];
-#pragma unroll
-    for (int j = 0; j < E448_PT_WORDS / 4; j++) {
-        const uint4 a = q[j];
-        w[4 * j] = a.x; w[4 * j + 1] = a.y; w[4 * j + 2] = a.z; w[4 * j + 3] = a.w;
-    }
-#pragma unroll
-    for (int j = 0; j < W448; j++) { x[j] = w[j]; y[j] = w[W448 + j]; }
-}
-DR_DEV void e448_store_point_words(uint32_t* p, const uint32_t (&x)[W448], const uint32_t (&y)[W448]) {
-    uint4* q = reinterpret_cast<uint4*>(p);
-    uint32_t w[E448_PT_WORDS];
-#pragma unroll
-    for (int j = 0; j < W448; j++) { w[j] = x[j]; w[W448 + j] = y[j]; }
-#pragma unroll
-    for (int j = 0; j < E448_PT_WORDS / 4; j++) q[j] = make_uint4(w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]);
-}
-DR_DEV void e448_store_zero_point(uint32_t* p) {
-    uint4* q = reinterpret_cast<uint4*>(p);
-#pragma unroll
-    for (int j = 0; j < E448_PT_WORDS / 4; j++) q[j] = make_uint4(0, 0, 0, 0);
-}
-// x || y of the point, one inversion (Z is never 0: the law is complete)
-DR_DEV void e448_store_affine(uint32_t* out, const E448Point& acc) {
-    const F448 zi = inv(acc.z);                              // 1 n
-    uint32_t x[W448], y[W448];
-    pack(mul(acc.x, zi), x);
-    pack(mul(acc.y, zi), y);
-    e448_store_point_words(out, x, y);
-}
-DR_DEV E448Point e448_load_affine(const uint32_t* p) {
-    uint32_t x[W448], y[W448];
-    e448_load_point_words(p, x, y);
-    return e448_from_affine(unpack(x), unpack(y));
-}
-
-// ---------------------------------------------------------------- scalar multiplication
-// k P for ANY k < 2^448 on a fixed schedule: table 1P..8P in LDS, 112 signed 4-bit windows and the carry out of the last digit as a
-// 113th, four doublings and one table addition each whatever the digits (the table index, always in range, is the only thing a digit
-// decides: no branch and no loop bound depends on one) — secret keys and nonces go through here.  The fixed schedule is this window
-// loop ALONE: the affine store that follows inverts Z by division steps, whose batch loop ends when g reaches 0 (divstep28.hip.h), so its
-// batch count depends on Z, a value derived from the scalar — as on every other curve of this library.  The kernels are not fixed-time
-// as a whole.
-DR_DEV E448Point e448_scalar_mul_core(uint32_t* tab, int lane, const E448Point& P, const uint32_t (&k)[W448]) {
-    wave_lds_store<Ed448Curve>(tab, 0, lane, P);
-    E448Point Q = e448_dbl(P);
-    wave_lds_store<Ed448Curve>(tab, 1, lane, Q);
-#pragma unroll 1
-    for (int e = 2; e < WAVE_TABLE; e++) {
-        Q = e448_add(Q, P);
-        wave_lds_store<Ed448Curve>(tab, e, lane, Q);
-    }
-    uint32_t dig[W448];              // digits 0..111 in [-8, 7], stored as d + 8; digit 112 = top_carry
-    uint32_t carry_in = 0;
-#pragma unroll
-    for (int w = 0; w < W448; w++) {
-        uint32_t packed = 0;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const uint32_t v = ((k[w] >> (4 * j)) & 15u) + carry_in;
-            carry_in = v >= 8u ? 1u : 0u;
-            packed |= ((v + 8u) & 15u) << (4 * j);
-        }
-        dig[w] = packed;
-    }
-    const uint32_t top_carry = carry_in;
-    E448Point acc = e448_identity();
-#pragma unroll 1
-    for (int w = E448_WINDOWS - 1; w >= 0; w--) {
-#pragma unroll 1
-        for (int j = 0; j < 4; j++) acc = e448_dbl(acc);
-        const int dg = w == E448_WINDOWS - 1 ? (int)top_carry : (int)((dig[w >> 3] >> (4 * (w & 7))) & 15u) - 8;
-        const int mag = dg < 0 ? -dg : dg;
-        E448Point T = wave_lds_load<Ed448Curve>(tab, mag == 0 ? 0 : mag - 1, lane);
-        T = e448_cneg(T, dg < 0);
-        if (mag == 0) T = e448_identity();
-        acc = e448_add(acc, T);
-    }
-    return acc;
-}
 
 // out[i] = k[i] P[i].  pts: n x 28 words (x || y), ks: n x 14, out: n x 28.  One lane per multiplication.
 __global__ __launch_bounds__(E448_BLOCK) void k_ed448_scalar_mul(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks,
                                                                  uint32_t* __restrict__ out, uint32_t n) {
-    __shared__ uint32_t tab[wave_table_words<Ed448Curve>()];
-    const int lane = threadIdx.x;
-    uint32_t i = blockIdx.x * E448_BLOCK + lane;
-    const bool live = i < n;
-    if (!live) i = n - 1;            // keep the wave converged; the duplicate result is not stored
-    uint32_t k[W448];
-    e448_load_elem_words(ks + (size_t)i * W448, k);
-    const E448Point P = e448_load_affine(pts + (size_t)i * E448_PT_WORDS);
-    const E448Point acc = e448_scalar_mul_core(tab, lane, P, k);
-    if (live) e448_store_affine(out + (size_t)i * E448_PT_WORDS, acc);
+    wave_scalar_mul<Ed448Curve>(pts, ks, out, n);
 }
-
-// out[g] = sum_{j<m} k[g m + j] P[g m + j]: one lane per term (m padded to mpad, a power of two <= 64), folded with shuffles by the
-// complete addition (terms that coincide or cancel need nothing special)
+// out[g] = sum_{j<m} k[g m + j] P[g m + j], m <= 64 padded to mpad: one lane per term, folded with shuffles by the complete addition
 __global__ __launch_bounds__(E448_BLOCK) void k_ed448_msm_groups(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks,
                                                                  uint32_t* __restrict__ out, uint32_t groups, uint32_t m, uint32_t mpad) {
-    __shared__ uint32_t tab[wave_table_words<Ed448Curve>()];
-    const int lane = threadIdx.x;
-    const uint32_t per_block = E448_BLOCK / mpad;
-    const uint32_t g = blockIdx.x * per_block + lane / mpad;
-    const uint32_t j = lane % mpad;
-    const bool live = g < groups && j < m;
-    const size_t idx = live ? (size_t)g * m + j : 0;          // dead lanes recompute term 0 and are masked out
-    uint32_t k[W448];
-    e448_load_elem_words(ks + idx * W448, k);
-    const E448Point P = e448_load_affine(pts + idx * E448_PT_WORDS);
-    const E448Point r = e448_scalar_mul_core(tab, lane, P, k);
-    E448Point acc = live ? r : e448_identity();
-#pragma unroll 1
-    for (uint32_t s = mpad >> 1; s > 0; s >>= 1) acc = e448_add(acc, wave_shfl_down<Ed448Curve>(acc, s));
-    if (g < groups && j == 0) e448_store_affine(out + (size_t)g * E448_PT_WORDS, acc);
+    wave_msm_groups<Ed448Curve>(pts, ks, out, groups, m, mpad);
 }
 
 // ---------------------------------------------------------------- hashing to the curve (RFC 9380, edwards448_XOF:SHAKE256_ELL2_RO_ / _NU_)
@@ -271,7 +162,7 @@ __global__ __launch_bounds__(E448_BLOCK) void k_ed448_map_to_curve(const uint32_
 #pragma unroll 1
     for (uint32_t e = 0; e < per_item; e++) {
         uint32_t w[W448];
-        e448_load_elem_words(us + ((size_t)i * per_item + e) * W448, w);
+        wave_load_words(us + ((size_t)i * per_item + e) * W448, w);
         bool ok_e;
         const E448Point q = e448_ell2_map(unpack(w), ok_e);
         good = good && ok_e;
@@ -282,14 +173,14 @@ __global__ __launch_bounds__(E448_BLOCK) void k_ed448_map_to_curve(const uint32_
         for (int j = 0; j < 2; j++) acc = e448_dbl(acc);                     // the cofactor
     }
     if (live) {
-        if (good) e448_store_affine(out_xy + (size_t)i * E448_PT_WORDS, acc);
-        else e448_store_zero_point(out_xy + (size_t)i * E448_PT_WORDS);
+        if (good) wave_store_affine<Ed448Curve>(out_xy + (size_t)i * E448_PT_WORDS, acc);
+        else wave_store_zero_words<E448_PT_WORDS>(out_xy + (size_t)i * E448_PT_WORDS);
         ok[i] = good ? 1u : 0u;
     }
 }
 
 // One lane per 112-byte x || y.  CHECK = 0: both coordinates below p and the curve equation holds (the identity (0, 1) passes).
-// CHECK = 1: additionally not the identity, and n P = O by the schedule above over the public words of n.  out = the input and ok = 1,
+// CHECK = 1: additionally not the identity, and n P = O by the fixed schedule over the public words of n.  out = the input and ok = 1,
 // or 112 zero bytes and ok = 0.
 template <int CHECK>
 __global__ __launch_bounds__(E448_BLOCK) void k_ed448_check_points(const uint32_t* __restrict__ enc, uint32_t* __restrict__ out_xy,
@@ -300,7 +191,7 @@ __global__ __launch_bounds__(E448_BLOCK) void k_ed448_check_points(const uint32_
     const bool live = i < n;
     if (!live) i = n - 1;
     uint32_t xw[W448], yw[W448];
-    e448_load_point_words(enc + (size_t)i * E448_PT_WORDS, xw, yw);
+    wave_load_point_words(enc + (size_t)i * E448_PT_WORDS, xw, yw);
     bool valid = below_p(xw) && below_p(yw);
     const F448 x = unpack(xw), y = unpack(yw);
     const F448 x2 = sqr(x), y2 = sqr(y);
@@ -312,11 +203,11 @@ __global__ __launch_bounds__(E448_BLOCK) void k_ed448_check_points(const uint32_
         uint32_t k[W448];
 #pragma unroll
         for (int j = 0; j < W448; j++) k[j] = E448_ORDER[j];
-        valid = e448_is_identity(e448_scalar_mul_core(tab, lane, P, k)) && valid;
+        valid = e448_is_identity(wave_scalar_mul_core<Ed448Curve>(tab, lane, P, k)) && valid;
     }
     if (live) {
-        if (valid) e448_store_point_words(out_xy + (size_t)i * E448_PT_WORDS, xw, yw);
-        else e448_store_zero_point(out_xy + (size_t)i * E448_PT_WORDS);
+        if (valid) wave_store_point_words(out_xy + (size_t)i * E448_PT_WORDS, xw, yw);
+        else wave_store_zero_words<E448_PT_WORDS>(out_xy + (size_t)i * E448_PT_WORDS);
         ok[i] = valid ? 1u : 0u;
     }
 }

@@ -158,7 +158,7 @@ __device__ const uint32_t G1H_R[8] = {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x5
 struct G1hCurve {
     using Fe = Fq28;
     using Point = G1hPoint;
-    static constexpr int WORDS = 12, BLOCK = G1H_BLOCK, WINDOWS = 65, LDS_WORDS = 14;
+    static constexpr int WORDS = 12, SCALAR_WORDS = 8, BLOCK = G1H_BLOCK, WINDOWS = 65, LDS_WORDS = 14;
     static constexpr bool EXTENDED = false, ZERO_IS_IDENTITY = true;
     DR_DEV static Fq28 unpack(const uint32_t (&w)[12]) { return to_mont28(w); }
     DR_DEV static void pack(const Fq28& a, uint32_t (&w)[12]) { from_mont28(a, w); }

@@ -105,7 +105,7 @@ DR_DEV bool p256_below_p(const uint32_t (&w)[8]) {
 struct P256Curve {
     using Fe = F256;
     using Point = P256Point;
-    static constexpr int WORDS = 8, BLOCK = P256_BLOCK, WINDOWS = 65, LDS_WORDS = 9;
+    static constexpr int WORDS = 8, SCALAR_WORDS = 8, BLOCK = P256_BLOCK, WINDOWS = 65, LDS_WORDS = 9;
     static constexpr bool EXTENDED = false, ZERO_IS_IDENTITY = true;
     DR_DEV static F256 unpack(const uint32_t (&w)[8]) { return fp_unpack(w); }
     DR_DEV static void pack(const F256& a, uint32_t (&w)[8]) { fp_pack(a, w); }

@@ -6,11 +6,9 @@
 // not on the curve: b != 0).  A point is 136 bytes, a multiple of 8, so it moves as seventeen uint2; a 68-byte element or scalar moves
 // as words.  Scalars are 68 bytes below 2^521 (the host refuses others) used AS THEY ARE.
 //
-// The schedule is wave_curve.hip.h's (LDS table 1P..8P, signed 4-bit windows, four doublings and one table addition whatever the
-// digits), restated for 17 scalar words and 131 windows as kernels_curve448.hip.h restates it for 14 and 113: that header fixes scalars
-// at 8 words and coordinates at a multiple of 4, and it stays byte-identical.  Its table, shuffle and limb-image helpers, which depend on
-// neither, are used as they are.  The table keeps limb images: 8 x 3 x 19 words x 64 lanes x 4 = 116 736 bytes of the CU's 160 KiB, one
-// workgroup (one wave) per CU.
+// The schedule, the memory forms and the two kernel bodies are wave_curve.hip.h's over P521Curve: 17 scalar words, 131 windows
+// (p521_law.hip.h: why 131 and no window for a carry out).  The table keeps limb images: 8 x 3 x 19 words x 64 lanes x 4 = 116 736
+// bytes of the CU's 160 KiB, one workgroup (one wave) per CU.
 #pragma once
 #include "p521_law.hip.h"
 #include "sswu.hip.h"
@@ -21,137 +19,35 @@ namespace dr {
 constexpr int P521_BLOCK = 64;        // one wave per workgroup
 constexpr int P521_PT_WORDS = 2 * W521;
 
-// what wave_curve.hip.h's table and shuffle helpers and the schedule below need of a curve description
+// wave_curve.hip.h's description of P-521: canonical words at the ABI (17 per coordinate; 136 zero bytes: the identity, which has Z = 0
+// and so stores them by 0^-1 = 0), the limb images in the LDS table, and 131 windows over the scalar AS IT IS (k < 2^521)
 struct P521Curve {
     using Fe = F521;
     using Point = P521Point;
-    static constexpr int BLOCK = P521_BLOCK, LDS_WORDS = L521;
-    static constexpr bool EXTENDED = false;
+    static constexpr int WORDS = W521, SCALAR_WORDS = W521, BLOCK = P521_BLOCK, WINDOWS = P521_WINDOWS, LDS_WORDS = L521;
+    static constexpr bool EXTENDED = false, ZERO_IS_IDENTITY = true;
+    DR_DEV static F521 unpack(const uint32_t (&w)[W521]) { return dr::unpack(w); }
+    DR_DEV static void pack(const F521& a, uint32_t (&w)[W521]) { dr::pack(a, w); }
+    DR_DEV static F521 inv(const F521& a) { return dr::inv(a); }                                  // 1 n
     DR_DEV static void to_lds(const F521& a, uint32_t (&w)[L521]) { wave_limbs_to_words(a, w); }
     DR_DEV static F521 from_lds(const uint32_t (&w)[L521]) { return wave_words_to_limbs<F521>(w); }
+    DR_DEV static P521Point identity() { return p521_identity(); }
+    DR_DEV static P521Point from_affine(const F521& x, const F521& y) { return p521_from_affine(x, y); }
     DR_DEV static P521Point add(const P521Point& p, const P521Point& q) { return p521_add(p, q); }
     DR_DEV static P521Point dbl(const P521Point& p) { return p521_dbl(p); }
     DR_DEV static P521Point cneg(const P521Point& p, bool negate) { return p521_cneg(p, negate); }
-    DR_DEV static P521Point identity() { return p521_identity(); }
+    DR_DEV static void load_scalar(const uint32_t* p, uint32_t (&k)[W521]) { wave_load_words(p, k); }    // no reduction
 };
-
-// ---------------------------------------------------------------- memory forms
-DR_DEV void p521_load_elem_words(const uint32_t* p, uint32_t (&w)[W521]) {           // 68 bytes: 4-byte aligned
-#pragma unroll
-    for (int j = 0; j < W521; j++) w[j] = p[j];
-}
-DR_DEV void p521_load_point_words(const uint32_t* p, uint32_t (&x)[W521], uint32_t (&y)[W521]) {   // 136 bytes: 8-byte aligned
-    const uint2* q = reinterpret_cast<const uint2*>(p);
-    uint32_t w[P521_PT_WORDS];
-#pragma unroll
-    for (int j = 0; j < P521_PT_WORDS / 2; j++) {
-        const uint2 a = q[j];
-        w[2 * j] = a.x; w[2 * j + 1] = a.y;
-    }
-#pragma unroll
-    for (int j = 0; j < W521; j++) { x[j] = w[j]; y[j] = w[W521 + j]; }
-}
-DR_DEV void p521_store_point_words(uint32_t* p, const uint32_t (&x)[W521], const uint32_t (&y)[W521]) {
-    uint2* q = reinterpret_cast<uint2*>(p);
-    uint32_t w[P521_PT_WORDS];
-#pragma unroll
-    for (int j = 0; j < W521; j++) { w[j] = x[j]; w[W521 + j] = y[j]; }
-#pragma unroll
-    for (int j = 0; j < P521_PT_WORDS / 2; j++) q[j] = make_uint2(w[2 * j], w[2 * j + 1]);
-}
-DR_DEV void p521_store_zero_point(uint32_t* p) {
-    uint2* q = reinterpret_cast<uint2*>(p);
-#pragma unroll
-    for (int j = 0; j < P521_PT_WORDS / 2; j++) q[j] = make_uint2(0, 0);
-}
-// x || y of the point, one inversion; the identity has Z = 0, so x = y = 0 after the multiplication by 0^-1 = 0: it stores zero bytes
-DR_DEV void p521_store_affine(uint32_t* out, const P521Point& acc) {
-    const F521 zi = inv(acc.z);                              // 1 n
-    uint32_t x[W521], y[W521];
-    pack(mul(acc.x, zi), x);
-    pack(mul(acc.y, zi), y);
-    p521_store_point_words(out, x, y);
-}
-// the point of 34 canonical words; 136 zero bytes are the identity
-DR_DEV P521Point p521_load_affine(const uint32_t* p) {
-    uint32_t x[W521], y[W521];
-    p521_load_point_words(p, x, y);
-    uint32_t o = 0;
-#pragma unroll
-    for (int j = 0; j < W521; j++) o |= x[j] | y[j];
-    P521Point r = p521_from_affine(unpack(x), unpack(y));
-    if (o == 0) r = p521_identity();
-    return r;
-}
-
-// ---------------------------------------------------------------- scalar multiplication
-// k P for ANY k < 2^521 on a fixed schedule: table 1P..8P in LDS, 131 signed 4-bit windows (p521_law.hip.h, p521_recode: why 131 and
-// no window for a carry out), four doublings and one table addition each whatever the digits (the table index, always in range, is the
-// only thing a digit decides: no branch and no loop bound depends on one) — secret keys and nonces go through here.  As on every other
-// curve of this library the fixed schedule is this window loop ALONE: the affine store that follows inverts Z by division steps, whose
-// batch loop ends when g reaches 0.
-template <class C>
-DR_DEV typename C::Point w521_scalar_mul_core(uint32_t* tab, int lane, const typename C::Point& P, const uint32_t (&k)[W521]) {
-    using Point = typename C::Point;
-    wave_lds_store<C>(tab, 0, lane, P);
-    Point Q = C::dbl(P);
-    wave_lds_store<C>(tab, 1, lane, Q);
-#pragma unroll 1
-    for (int e = 2; e < WAVE_TABLE; e++) {
-        Q = C::add(Q, P);
-        wave_lds_store<C>(tab, e, lane, Q);
-    }
-    uint32_t dig[W521];
-    p521_recode(k, dig);
-    Point acc = C::identity();
-#pragma unroll 1
-    for (int w = P521_WINDOWS - 1; w >= 0; w--) {
-#pragma unroll 1
-        for (int j = 0; j < 4; j++) acc = C::dbl(acc);
-        const int dg = p521_digit(dig, w);
-        const int mag = dg < 0 ? -dg : dg;
-        Point T = wave_lds_load<C>(tab, mag == 0 ? 0 : mag - 1, lane);
-        T = C::cneg(T, dg < 0);
-        if (mag == 0) T = C::identity();
-        acc = C::add(acc, T);
-    }
-    return acc;
-}
 
 // out[i] = k[i] P[i].  pts: n x 34 words (x || y), ks: n x 17, out: n x 34.  One lane per multiplication.
 __global__ __launch_bounds__(P521_BLOCK) void k_p521_scalar_mul(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks,
                                                                 uint32_t* __restrict__ out, uint32_t n) {
-    __shared__ uint32_t tab[wave_table_words<P521Curve>()];
-    const int lane = threadIdx.x;
-    uint32_t i = blockIdx.x * P521_BLOCK + lane;
-    const bool live = i < n;
-    if (!live) i = n - 1;            // keep the wave converged; the duplicate result is not stored
-    uint32_t k[W521];
-    p521_load_elem_words(ks + (size_t)i * W521, k);
-    const P521Point P = p521_load_affine(pts + (size_t)i * P521_PT_WORDS);
-    const P521Point acc = w521_scalar_mul_core<P521Curve>(tab, lane, P, k);
-    if (live) p521_store_affine(out + (size_t)i * P521_PT_WORDS, acc);
+    wave_scalar_mul<P521Curve>(pts, ks, out, n);
 }
-
-// out[g] = sum_{j<m} k[g m + j] P[g m + j]: one lane per term (m padded to mpad, a power of two <= 64), folded with shuffles by the
-// complete addition (terms that coincide or cancel need nothing special)
+// out[g] = sum_{j<m} k[g m + j] P[g m + j], m <= 64 padded to mpad: one lane per term, folded with shuffles by the complete addition
 __global__ __launch_bounds__(P521_BLOCK) void k_p521_msm_groups(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks,
                                                                 uint32_t* __restrict__ out, uint32_t groups, uint32_t m, uint32_t mpad) {
-    __shared__ uint32_t tab[wave_table_words<P521Curve>()];
-    const int lane = threadIdx.x;
-    const uint32_t per_block = P521_BLOCK / mpad;
-    const uint32_t g = blockIdx.x * per_block + lane / mpad;
-    const uint32_t j = lane % mpad;
-    const bool live = g < groups && j < m;
-    const size_t idx = live ? (size_t)g * m + j : 0;          // dead lanes recompute term 0 and are masked out
-    uint32_t k[W521];
-    p521_load_elem_words(ks + idx * W521, k);
-    const P521Point P = p521_load_affine(pts + idx * P521_PT_WORDS);
-    const P521Point r = w521_scalar_mul_core<P521Curve>(tab, lane, P, k);
-    P521Point acc = live ? r : p521_identity();
-#pragma unroll 1
-    for (uint32_t s = mpad >> 1; s > 0; s >>= 1) acc = p521_add(acc, wave_shfl_down<P521Curve>(acc, s));
-    if (g < groups && j == 0) p521_store_affine(out + (size_t)g * P521_PT_WORDS, acc);
+    wave_msm_groups<P521Curve>(pts, ks, out, groups, m, mpad);
 }
 
 // ---------------------------------------------------------------- hashing to the curve (RFC 9380, P521_XMD:SHA-512_SSWU_RO_ / _NU_)
@@ -172,7 +68,7 @@ __global__ __launch_bounds__(P521_BLOCK) void k_p521_map_to_curve(const uint32_t
 #pragma unroll 1
     for (uint32_t e = 0; e < per_item; e++) {
         uint32_t w[W521];
-        p521_load_elem_words(us + ((size_t)i * per_item + e) * W521, w);
+        wave_load_words(us + ((size_t)i * per_item + e) * W521, w);
         F521 xn, xd, y;
         sswu_map<P521Sswu>(unpack(w), (w[0] & 1u) != 0, xn, xd, y);
         bool ok_e;
@@ -181,7 +77,7 @@ __global__ __launch_bounds__(P521_BLOCK) void k_p521_map_to_curve(const uint32_t
         acc = p521_add(acc, pt);
     }
     if (live) {
-        p521_store_affine(out_xy + (size_t)i * P521_PT_WORDS, acc);
+        wave_store_affine<P521Curve>(out_xy + (size_t)i * P521_PT_WORDS, acc);
         ok[i] = good ? 1u : 0u;
     }
 }
@@ -207,7 +103,7 @@ __global__ __launch_bounds__(P521_BLOCK) void k_p521_decode_points(const uint32_
     const bool live = i < n;
     if (!live) i = n - 1;
     uint32_t w[W521];
-    p521_load_elem_words(enc + (size_t)i * W521, w);
+    wave_load_words(enc + (size_t)i * W521, w);
     const uint32_t first = w[0] & 0xffu;
     uint32_t xb[W521];
     p521_sec1_x_words(w, xb);
@@ -222,9 +118,9 @@ __global__ __launch_bounds__(P521_BLOCK) void k_p521_decode_points(const uint32_
         if (valid) {
             uint32_t yw[W521];
             pack(y, yw);
-            p521_store_point_words(out_xy + (size_t)i * P521_PT_WORDS, xb, yw);
+            wave_store_point_words(out_xy + (size_t)i * P521_PT_WORDS, xb, yw);
         } else {
-            p521_store_zero_point(out_xy + (size_t)i * P521_PT_WORDS);
+            wave_store_zero_words<P521_PT_WORDS>(out_xy + (size_t)i * P521_PT_WORDS);
         }
         ok[i] = valid ? 1u : 0u;
     }

@@ -89,7 +89,7 @@ DR_DEV bool k1_y_of_x(const FK& x, FK& y) { return fk_sqrt(carry(add(mul(sqr(x),
 struct Secp256k1Curve {
     using Fe = FK;
     using Point = K1Point;
-    static constexpr int WORDS = 8, BLOCK = K1_BLOCK, WINDOWS = 65, LDS_WORDS = 9;
+    static constexpr int WORDS = 8, SCALAR_WORDS = 8, BLOCK = K1_BLOCK, WINDOWS = 65, LDS_WORDS = 9;
     static constexpr bool EXTENDED = false, ZERO_IS_IDENTITY = true;
     DR_DEV static FK unpack(const uint32_t (&w)[8]) { return fk_unpack(w); }
     DR_DEV static void pack(const FK& a, uint32_t (&w)[8]) { fk_pack(a, w); }

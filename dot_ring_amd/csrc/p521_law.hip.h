@@ -7,8 +7,7 @@
 // The comments give the limb class of every intermediate against fp521.hip.h's contract ("n" = normal, "k n" = |limb| <= k normal; mul
 // needs ka kb <= 6, sqr 2 n).  A point's coordinates are x: 1 n, y: n (1 n once negated), z: n, in and out.
 //
-// The map's description for sswu.hip.h and the scalar recoding of the fixed schedule (kernels_p521.hip.h) are here as well, so that
-// the host can check them.
+// The map's description for sswu.hip.h is here as well, so that the host can check it, and the window count of the fixed schedule.
 // Plain integer C++ like fp521.hip.h: compiles for the device and, with g++, for the host (tests/native/p521_host_check.cpp, where
 // -fsanitize=undefined turns a signed 64-bit column overflow into an abort).
 #pragma once
@@ -99,25 +98,10 @@ struct P521Sswu {
     DR_F521_MEMBER static F521 pow_p34(const F521& x) { return f521_pow_p34(x); }
 };
 
-// ---------------------------------------------------------------- the scalar recoding of the fixed schedule
-// Signed 4-bit digits of a scalar k < 2^521 given as 17 words: k = sum d_w 16^w, d_w in [-8, 7], w = 0..130.  131 nibbles cover 524
-// bits; nibble 130 holds bit 520 alone, so with the carry into it d_130 <= 2 and nothing leaves it: 131 windows, and no window for a
-// carry out as the 448-bit schedules need.  dig[w / 8] holds d_w + 8 in its nibble w % 8; the nibbles from 131 up come out as 8 (zero).
+// ---------------------------------------------------------------- the windows of the fixed schedule
+// Signed 4-bit digits (wave_recode.hip.h) of a scalar k < 2^521 given as 17 words: k = sum d_w 16^w, d_w in [-8, 7], w = 0..130.  131
+// nibbles cover 524 bits; nibble 130 holds bit 520 alone, so with the carry into it d_130 <= 2 and nothing leaves it: 131 windows, and
+// no window for a carry out as the 448-bit schedules need.  The nibbles from 131 up come out as 8 (zero).
 constexpr int P521_WINDOWS = 131;
-DR_F521_FN void p521_recode(const uint32_t (&k)[W521], uint32_t (&dig)[W521]) {
-    uint32_t carry_in = 0;
-#pragma unroll
-    for (int w = 0; w < W521; w++) {
-        uint32_t packed = 0;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const uint32_t v = ((k[w] >> (4 * j)) & 15u) + carry_in;
-            carry_in = v >= 8u ? 1u : 0u;
-            packed |= ((v + 8u) & 15u) << (4 * j);
-        }
-        dig[w] = packed;
-    }
-}
-DR_F521_FN int p521_digit(const uint32_t (&dig)[W521], int w) { return (int)((dig[w >> 3] >> (4 * (w & 7))) & 15u) - 8; }
 
 }  // namespace dr

@@ -1,27 +1,35 @@
-// The wave-per-workgroup scalar-multiplication family of the four native 256-bit curves (Ed25519, Baby JubJub, P-256, secp256k1) and of
-// BLS12-381's E(Fq) (48-byte coordinates) as one set of templates over a description C of the curve: the memory forms, the fixed-schedule scalar multiplication the provers' secret scalars go
-// through, the two kernel bodies built on it, and the SEC1-compressed decoder.  kernels_ed25519.hip.h (Ed25519Curve), kernels_bjj.hip.h
-// (BjjCurve), kernels_p256.hip.h (P256Curve), kernels_secp256k1.hip.h (Secp256k1Curve) and kernels_g1_h2c.hip.h (G1hCurve) each give a
-// field, a group law, one description and one thin named __global__ per kernel; the schedule below exists once.  C provides
+// The wave-per-workgroup scalar-multiplication family of every curve with kernels of its own — the four native 256-bit curves (Ed25519,
+// Baby JubJub, P-256, secp256k1), BLS12-381's E(Fq) (48-byte coordinates), Ed448, Curve448 (56-byte coordinates and scalars) and P-521
+// (68-byte) — as one set of templates over a description C of the curve: the memory forms, the fixed-schedule scalar multiplication the
+// provers' secret scalars go through, the two kernel bodies built on it, and the SEC1-compressed decoder.  kernels_ed25519.hip.h
+// (Ed25519Curve), kernels_bjj.hip.h (BjjCurve), kernels_p256.hip.h (P256Curve), kernels_secp256k1.hip.h (Secp256k1Curve),
+// kernels_g1_h2c.hip.h (G1hCurve), kernels_ed448.hip.h (Ed448Curve), kernels_curve448.hip.h (Curve448Curve) and kernels_p521.hip.h
+// (P521Curve) each give a field, a group law, one description and one thin named __global__ per kernel; the schedule below exists once.
+// C provides
 //   Fe, Point                      the field element (int32_t limbs l[]) and the point: members x, y, z and, when EXTENDED, t
-//   WORDS                          the 32-bit words of a coordinate at the ABI: 8, or 12 (a multiple of 4: they move as uint4).  A point is
-//                                  2 WORDS words (x || y); scalars are 8 words whatever the curve
-//   BLOCK, WINDOWS                 the workgroup size (64: one wave) and the number of signed 4-bit windows of a reduced scalar: 64 when
-//                                  the order is below 2^255 (no carry leaves the top digit), 65 otherwise
+//   WORDS                          the 32-bit words of a coordinate at the ABI: 8, 12, 14 or 17 (any count).  A point is 2 WORDS words
+//                                  (x || y) and moves as the widest of uint4 / uint2 / words that divides its byte length
+//   SCALAR_WORDS                   the 32-bit words of a scalar at the ABI: 8, 14 or 17; it moves the same way
+//   BLOCK, WINDOWS                 the workgroup size (64: one wave) and the number of signed 4-bit windows of a scalar: 8 SCALAR_WORDS + 1
+//                                  where a carry can leave the top digit (65: an order of 256 bits; 113: any k < 2^448), otherwise the
+//                                  digits that can be non-zero (64: an order below 2^255; 131: k < 2^521, p521_law.hip.h)
 //   EXTENDED, LDS_WORDS            whether the point has a fourth coordinate t; the words of one coordinate in the LDS table
-//   ZERO_IS_IDENTITY               whether zero bytes (64, or 96) stand for the identity at the ABI (the Weierstrass curves: (0, 0) is no point)
+//   ZERO_IS_IDENTITY               whether zero bytes stand for the identity at the ABI (the Weierstrass curves: (0, 0) is no point)
 //   unpack(w), pack(a, w), inv(a)  the ABI's canonical WORDS words <-> an element (in the field's own form); a^-1 with 0^-1 = 0
 //   to_lds(a, w), from_lds(w)      a normal coordinate <-> its LDS_WORDS table words (canonical or Montgomery words, or the limb image)
 //   identity(), from_affine(x, y)  the neutral element; the point of affine coordinates
 //   add(P, Q), dbl(P)              the unified / complete addition and the doubling (all coordinates)
 //   dbl_no_t(P)                    when EXTENDED: the doubling without t (three of a window's four doublings are only doubled again)
 //   cneg(P, b)                     -P if b
-//   load_scalar(p, k)              8 words at p reduced mod the group order (G1hCurve: as they are — E(Fq) is not of prime order, and
-//                                  the 65 windows take any 256-bit scalar)
+//   load_scalar(p, k)              SCALAR_WORDS words at p reduced mod the group order, or (G1hCurve, Ed448Curve, P521Curve) as they
+//                                  are: E(Fq) and E448 are not of prime order, and the windows take every scalar of the width (P-521:
+//                                  every k < 2^521; the host refuses others)
 // and, for sec1_decode:  below_p(w), y_of_x(x, y) (a root of the curve equation, false if none), is_odd(y) (of the canonical value),
-// and with CHECK in_subgroup(x, y).
+// and with CHECK in_subgroup(x, y).  Curve448Curve, whose points cross the ABI as Montgomery (u, v) with a flag word, gives the law and
+// the table forms only: its kernels (and kernels_curve25519.hip.h's over Ed25519Curve) call the core from bodies of their own.
 #pragma once
 #include "field.hip.h"
+#include "wave_recode.hip.h"
 
 namespace dr {
 
@@ -42,40 +50,77 @@ DR_DEV void wave_store_zero8(uint32_t* p) {
     const uint32_t z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     wave_store8(p, z);
 }
-// the same for a coordinate of W words (W = 8: the three above)
-template <int W>
-DR_DEV void wave_load_words(const uint32_t* p, uint32_t (&w)[W]) {
-    static_assert(W % 4 == 0, "coordinates move as uint4");
-    if constexpr (W == 8) {
+// the same for N words of any count: they move as the widest of uint4 / uint2 / words that divides their byte length (N = 8: the three
+// above; seven uint4 for a point of 2 x 14 words, seven uint2 for a scalar of 14, seventeen uint2 for a point of 2 x 17)
+template <int N>
+DR_DEV void wave_load_words(const uint32_t* p, uint32_t (&w)[N]) {
+    if constexpr (N == 8) {
         wave_load8(p, w);
-    } else {
+    } else if constexpr (N % 4 == 0) {
         const uint4* q = reinterpret_cast<const uint4*>(p);
 #pragma unroll
-        for (int j = 0; j < W / 4; j++) {
+        for (int j = 0; j < N / 4; j++) {
             const uint4 a = q[j];
             w[4 * j] = a.x; w[4 * j + 1] = a.y; w[4 * j + 2] = a.z; w[4 * j + 3] = a.w;
         }
+    } else if constexpr (N % 2 == 0) {
+        const uint2* q = reinterpret_cast<const uint2*>(p);
+#pragma unroll
+        for (int j = 0; j < N / 2; j++) {
+            const uint2 a = q[j];
+            w[2 * j] = a.x; w[2 * j + 1] = a.y;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; j++) w[j] = p[j];
     }
 }
-template <int W>
-DR_DEV void wave_store_words(uint32_t* p, const uint32_t (&w)[W]) {
-    static_assert(W % 4 == 0, "coordinates move as uint4");
-    if constexpr (W == 8) {
+template <int N>
+DR_DEV void wave_store_words(uint32_t* p, const uint32_t (&w)[N]) {
+    if constexpr (N == 8) {
         wave_store8(p, w);
-    } else {
+    } else if constexpr (N % 4 == 0) {
         uint4* q = reinterpret_cast<uint4*>(p);
 #pragma unroll
-        for (int j = 0; j < W / 4; j++) q[j] = make_uint4(w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]);
+        for (int j = 0; j < N / 4; j++) q[j] = make_uint4(w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]);
+    } else if constexpr (N % 2 == 0) {
+        uint2* q = reinterpret_cast<uint2*>(p);
+#pragma unroll
+        for (int j = 0; j < N / 2; j++) q[j] = make_uint2(w[2 * j], w[2 * j + 1]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; j++) p[j] = w[j];
+    }
+}
+template <int N>
+DR_DEV void wave_store_zero_words(uint32_t* p) {
+    const uint32_t z[N] = {};
+    wave_store_words(p, z);
+}
+// a point, x || y of W words each: coordinate by coordinate where a coordinate is a whole number of uint4 (W = 8, 12), otherwise as one
+// run of 2 W words (a coordinate of 14 or 17 words alone is not aligned to the vector its point moves as)
+template <int W>
+DR_DEV void wave_load_point_words(const uint32_t* p, uint32_t (&x)[W], uint32_t (&y)[W]) {
+    if constexpr (W % 4 == 0) {
+        wave_load_words(p, x);
+        wave_load_words(p + W, y);
+    } else {
+        uint32_t w[2 * W];
+        wave_load_words(p, w);
+#pragma unroll
+        for (int j = 0; j < W; j++) { x[j] = w[j]; y[j] = w[W + j]; }
     }
 }
 template <int W>
-DR_DEV void wave_store_zero_words(uint32_t* p) {
-    if constexpr (W == 8) {
-        wave_store_zero8(p);
+DR_DEV void wave_store_point_words(uint32_t* p, const uint32_t (&x)[W], const uint32_t (&y)[W]) {
+    if constexpr (W % 4 == 0) {
+        wave_store_words(p, x);
+        wave_store_words(p + W, y);
     } else {
-        uint4* q = reinterpret_cast<uint4*>(p);
+        uint32_t w[2 * W];
 #pragma unroll
-        for (int j = 0; j < W / 4; j++) q[j] = make_uint4(0, 0, 0, 0);
+        for (int j = 0; j < W; j++) { w[j] = x[j]; w[W + j] = y[j]; }
+        wave_store_words(p, w);
     }
 }
 
@@ -96,16 +141,22 @@ DR_DEV void wave_store_fe(uint32_t* p, const typename C::Fe& a) {
 template <class C>
 DR_DEV void wave_store_affine(uint32_t* out, const typename C::Point& acc) {
     const typename C::Fe zi = C::inv(acc.z);
-    wave_store_fe<C>(out, mul(acc.x, zi));
-    wave_store_fe<C>(out + C::WORDS, mul(acc.y, zi));
+    if constexpr (C::WORDS % 4 == 0) {
+        wave_store_fe<C>(out, mul(acc.x, zi));
+        wave_store_fe<C>(out + C::WORDS, mul(acc.y, zi));
+    } else {
+        uint32_t x[C::WORDS], y[C::WORDS];
+        C::pack(mul(acc.x, zi), x);
+        C::pack(mul(acc.y, zi), y);
+        wave_store_point_words(out, x, y);
+    }
 }
 // One term of a batch: the point of affine x || y (2 WORDS words, canonical) at pt and the scalar at kp, reduced into k.  The scalar is
 // reduced before the point is built from its coordinates (an extended point costs a product that nothing needs across that loop).
 template <class C>
-DR_DEV typename C::Point wave_load_term(const uint32_t* pt, const uint32_t* kp, uint32_t (&k)[8]) {
+DR_DEV typename C::Point wave_load_term(const uint32_t* pt, const uint32_t* kp, uint32_t (&k)[C::SCALAR_WORDS]) {
     uint32_t x[C::WORDS], y[C::WORDS];
-    wave_load_words(pt, x);
-    wave_load_words(pt + C::WORDS, y);
+    wave_load_point_words(pt, x, y);
     [[maybe_unused]] uint32_t o = 0;
 #pragma unroll
     for (int j = 0; j < C::WORDS; j++) o |= x[j] | y[j];
@@ -181,13 +232,18 @@ DR_DEV typename C::Point wave_shfl_down(const typename C::Point& p, unsigned del
 }
 
 // ---------------------------------------------------------------- scalar multiplication
-// k P for k below the group order on a fixed schedule: table 1P..8P in LDS, 64 signed 4-bit windows (and, where the order has 256 bits,
-// the carry out of the 64th digit as a 65th), four doublings and one table addition each whatever the digits (the table index, always in
-// range, is the only thing a digit decides: no branch and no loop bound depends on one) — the secret scalars of the provers go through
-// here
+// k P on a fixed schedule: table 1P..8P in LDS, WINDOWS signed 4-bit windows (wave_recode.hip.h) of a scalar of SCALAR_WORDS words —
+// its 8 SCALAR_WORDS digits and, where WINDOWS is one more (an order of 256 bits; any k < 2^448), the carry out of the top digit as the
+// last window; where it is fewer (64 for an order below 2^255, 131 for k < 2^521) the digits above are zero and no carry leaves —
+// four doublings and one table addition each whatever the digits (the table index, always in range, is the only thing a digit decides:
+// no branch and no loop bound depends on one) — the secret scalars of the provers go through here.  The fixed schedule is this window
+// loop ALONE: the affine store that follows inverts Z by division steps, whose batch loop ends when g reaches 0 (divstep28.hip.h), so
+// its batch count depends on Z, a value derived from the scalar.  The kernels are not fixed-time as a whole.
 template <class C>
-DR_DEV typename C::Point wave_scalar_mul_core(uint32_t* tab, int lane, const typename C::Point& P, const uint32_t (&k)[8]) {
+DR_DEV typename C::Point wave_scalar_mul_core(uint32_t* tab, int lane, const typename C::Point& P, const uint32_t (&k)[C::SCALAR_WORDS]) {
     using Point = typename C::Point;
+    constexpr int DIGITS = 8 * C::SCALAR_WORDS;
+    static_assert(C::WINDOWS <= DIGITS + 1, "a window is a digit of the recoding or the carry out of its top digit");
     wave_lds_store<C>(tab, 0, lane, P);
     Point Q = C::dbl(P);
     wave_lds_store<C>(tab, 1, lane, Q);
@@ -196,20 +252,13 @@ DR_DEV typename C::Point wave_scalar_mul_core(uint32_t* tab, int lane, const typ
         Q = C::add(Q, P);
         wave_lds_store<C>(tab, e, lane, Q);
     }
-    uint32_t dig[8];                 // digits 0..63 in [-8, 7], stored as d + 8; digit 64 = top_carry
-    uint32_t carry_in = 0;
+    // wave_recode(k, dig), its loop over the words spelled here, and below wave_digit(dig, w) with its 8 taken off here: with either
+    // behind a call of its own the compiler orders the kernels of the 256-bit curves another way
+    uint32_t dig[C::SCALAR_WORDS];
+    uint32_t carry = 0;
 #pragma unroll
-    for (int w = 0; w < 8; w++) {
-        uint32_t packed = 0;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const uint32_t v = ((k[w] >> (4 * j)) & 15u) + carry_in;
-            carry_in = v >= 8u ? 1u : 0u;
-            packed |= ((v + 8u) & 15u) << (4 * j);
-        }
-        dig[w] = packed;
-    }
-    [[maybe_unused]] const uint32_t top_carry = carry_in;      // (0 when the order is below 2^255: the top nibble is then at most 1)
+    for (int w = 0; w < C::SCALAR_WORDS; w++) dig[w] = wave_recode_word(k[w], carry);
+    [[maybe_unused]] const uint32_t top_carry = carry;
     Point acc = C::identity();
 #pragma unroll 1
     for (int w = C::WINDOWS - 1; w >= 0; w--) {
@@ -222,8 +271,8 @@ DR_DEV typename C::Point wave_scalar_mul_core(uint32_t* tab, int lane, const typ
             for (int j = 0; j < 4; j++) acc = C::dbl(acc);
         }
         int dg;
-        if constexpr (C::WINDOWS == 65) dg = w == 64 ? (int)top_carry : (int)((dig[w >> 3] >> (4 * (w & 7))) & 15u) - 8;
-        else dg = (int)((dig[w >> 3] >> (4 * (w & 7))) & 15u) - 8;
+        if constexpr (C::WINDOWS == DIGITS + 1) dg = w == DIGITS ? (int)top_carry : (int)wave_nibble(dig, w) - 8;
+        else dg = (int)wave_nibble(dig, w) - 8;
         const int mag = dg < 0 ? -dg : dg;
         Point T = wave_lds_load<C>(tab, mag == 0 ? 0 : mag - 1, lane);
         T = C::cneg(T, dg < 0);
@@ -233,7 +282,7 @@ DR_DEV typename C::Point wave_scalar_mul_core(uint32_t* tab, int lane, const typ
     return acc;
 }
 
-// out[i] = k[i] P[i].  pts: n x 2 WORDS words (x || y), ks: n x 8, out: n x 2 WORDS.  One lane per multiplication.
+// out[i] = k[i] P[i].  pts: n x 2 WORDS words (x || y), ks: n x SCALAR_WORDS, out: n x 2 WORDS.  One lane per multiplication.
 template <class C>
 DR_DEV void wave_scalar_mul(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks, uint32_t* __restrict__ out, uint32_t n) {
     __shared__ uint32_t tab[wave_table_words<C>()];
@@ -241,8 +290,8 @@ DR_DEV void wave_scalar_mul(const uint32_t* __restrict__ pts, const uint32_t* __
     uint32_t i = blockIdx.x * C::BLOCK + lane;
     const bool live = i < n;
     if (!live) i = n - 1;            // keep the wave converged; the duplicate result is not stored
-    uint32_t k[8];
-    const typename C::Point P = wave_load_term<C>(pts + (size_t)i * (2 * C::WORDS), ks + (size_t)i * 8, k);
+    uint32_t k[C::SCALAR_WORDS];
+    const typename C::Point P = wave_load_term<C>(pts + (size_t)i * (2 * C::WORDS), ks + (size_t)i * C::SCALAR_WORDS, k);
     const typename C::Point acc = wave_scalar_mul_core<C>(tab, lane, P, k);
     if (live) wave_store_affine<C>(out + (size_t)i * (2 * C::WORDS), acc);
 }
@@ -260,8 +309,8 @@ DR_DEV void wave_msm_groups(const uint32_t* __restrict__ pts, const uint32_t* __
     const uint32_t j = lane % mpad;
     const bool live = g < groups && j < m;
     const size_t idx = live ? (size_t)g * m + j : 0;          // dead lanes recompute term 0 and are masked out
-    uint32_t k[8];
-    const Point P = wave_load_term<C>(pts + idx * (2 * C::WORDS), ks + idx * 8, k);
+    uint32_t k[C::SCALAR_WORDS];
+    const Point P = wave_load_term<C>(pts + idx * (2 * C::WORDS), ks + idx * C::SCALAR_WORDS, k);
     const Point r = wave_scalar_mul_core<C>(tab, lane, P, k);
     Point acc = live ? r : C::identity();
 #pragma unroll 1

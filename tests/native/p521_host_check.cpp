@@ -7,7 +7,7 @@
 //   sub x1 y1 x2 y2             ... the second point negated by p521_cneg first
 //   dbl x y                     p521_dbl
 //   map u                       sswu_map<P521Sswu> and sswu_iso_map, stored affine
-//   recode k                    the 131 digits of p521_recode, least significant first, then the nibbles above them (all 0)
+//   recode k                    the 131 digits of wave_recode<17>, least significant first, then the nibbles above them (all 0)
 //   words v                     unpack then pack (the canonical value of any 17 words below 2^532), then below_p
 // Output: canonical values as 136 hexadecimal digits; points as `x y` (the identity as zeros); flags 0 / 1; digits as decimal integers.
 // Built with -fsanitize=undefined -fno-sanitize-recover, a signed overflow of a 64-bit column (or of a 32-bit limb) aborts the program:
@@ -19,6 +19,7 @@
 
 #include "p521_law.hip.h"
 #include "sswu.hip.h"
+#include "wave_recode.hip.h"
 
 static bool read_words(std::istringstream& in, uint32_t (&w)[dr::W521]) {
     std::string s;
@@ -102,8 +103,8 @@ int main() {
         } else if (op == "recode") {
             uint32_t k[dr::W521], dig[dr::W521];
             if (!read_words(in, k)) return 2;
-            dr::p521_recode(k, dig);
-            for (int w = 0; w < 8 * dr::W521; w++) std::printf("%d ", dr::p521_digit(dig, w));
+            dr::wave_recode(k, dig);
+            for (int w = 0; w < 8 * dr::W521; w++) std::printf("%d ", dr::wave_digit(dig, w));
         } else if (op == "words") {
             uint32_t w[dr::W521];
             if (!read_words(in, w)) return 2;

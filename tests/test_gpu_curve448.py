@@ -192,13 +192,14 @@ def test_encode_to_curve_batch(ctx, variant, cid):
 
 
 # ---------------------------------------------------------------- scalar multiplication
-SCALARS = [0, 1, 2, 4, N - 1, N, N + 1, 2 * N, 4 * N - 1, 4 * N, 2**447, 2**448 - 1]
+# the last two: every nibble 7 (the largest digit everywhere, no carry) and every nibble 8 (a carry out of every digit, up into window 113)
+SCALARS = [0, 1, 2, 4, N - 1, N, N + 1, 2 * N, 4 * N - 1, 4 * N, 2**447, 2**448 - 1, int("7" * 112, 16), int("8" * 112, 16)]
 
 
 def test_scalar_mul_takes_scalars_as_they_are(ctx, hashed):
     bases = [c.G, hashed, G_PLUS_TWO, OUTSIDE, c.TWO_TORSION, c.T4, None]
     pts = [b for b in bases for _ in SCALARS]
-    got = pts_of(ctx.curve448_scalar_mul_batch(b"".join(raw(p) for p in pts), _sc(SCALARS * len(bases))))   # 84 items
+    got = pts_of(ctx.curve448_scalar_mul_batch(b"".join(raw(p) for p in pts), _sc(SCALARS * len(bases))))   # 98 items
     for j, base in enumerate(bases):
         assert got[len(SCALARS) * j : len(SCALARS) * (j + 1)] == [c.mul(k, base) for k in SCALARS], j
     at = lambda j, k: got[len(SCALARS) * j + SCALARS.index(k)]  # noqa: E731

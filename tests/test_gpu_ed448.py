@@ -201,7 +201,8 @@ def test_encode_to_curve_batch(ctx, variant, cid):
 
 
 # ---------------------------------------------------------------- scalar multiplication
-SCALARS = [0, 1, 2, 4, N - 1, N, N + 1, 4 * N - 1, 4 * N, 2**447, 2**448 - 1]
+# the last two: every nibble 7 (the largest digit everywhere, no carry) and every nibble 8 (a carry out of every digit, up into window 113)
+SCALARS = [0, 1, 2, 4, N - 1, N, N + 1, 4 * N - 1, 4 * N, 2**447, 2**448 - 1, int("7" * 112, 16), int("8" * 112, 16)]
 
 
 @pytest.mark.parametrize("base", ["generator", "hashed", "outside"])
