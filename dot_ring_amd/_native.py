@@ -158,6 +158,14 @@ _PROTOTYPES.update({
     "dr_p521_msm_groups": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_size_t, c_char_p]),
     "dr_p521_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
     "dr_p521_field_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p, c_void_p]),
+    "dr_p384_hash_to_field_batch": (c_int, [c_int, c_char_p, POINTER(ctypes.c_uint64), c_size_t, c_char_p]),
+    "dr_p384_map_to_curve": (c_int, [c_void_p, c_char_p, c_size_t, c_int, c_int, c_char_p, c_char_p]),
+    "dr_p384_encode_to_curve_batch": (c_int, [c_void_p, c_int, c_char_p, POINTER(ctypes.c_uint64), c_char_p, POINTER(ctypes.c_uint64), c_size_t,
+                                      c_char_p]),
+    "dr_p384_scalar_mul_batch": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_char_p]),
+    "dr_p384_msm_groups": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_size_t, c_char_p]),
+    "dr_p384_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
+    "dr_p384_field_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p, c_void_p]),
     "dr_curve25519_scalar_mul_batch": (c_int, [c_void_p, c_char_p, c_char_p, c_char_p, c_size_t, c_char_p, c_char_p]),
     "dr_curve25519_msm_groups": (c_int, [c_void_p, c_char_p, c_char_p, c_char_p, c_size_t, c_size_t, c_char_p, c_char_p]),
     "dr_curve25519_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
@@ -260,6 +268,8 @@ CURVE_ED448_RO, CURVE_ED448_NU = 19, 20
 CURVE_CURVE448_RO, CURVE_CURVE448_NU = 21, 22
 # P-521 by RFC 9380: 68-byte coordinates and scalars (below 2^521), entry points of their own (dr_p521_*), the identity 136 zero bytes
 CURVE_P521_RO, CURVE_P521_NU = 23, 24
+# P-384 by RFC 9380: 48-byte coordinates and scalars (every 384-bit value), entry points of their own (dr_p384_*), the identity 96 zero bytes
+CURVE_P384_RO, CURVE_P384_NU = 25, 26
 # bytes of an encoded point, per curve id (the suites with 33-byte encodings and Curve25519's 64-byte u || v; every other curve's are 32)
 _POINT_LEN = {CURVE_BANDERSNATCH_SW: 33, CURVE_P256: 33, CURVE_SECP256K1: 33, CURVE_SECP256K1_NU: 33, CURVE_P256_RO: 33, CURVE_P256_NU: 33,
               CURVE_CURVE25519_RO: 64, CURVE_CURVE25519_NU: 64}
@@ -360,6 +370,7 @@ _WIDE = {
     "ed448": _Wide(56, 112, 56, 112, 64, 11, CURVE_ED448_NU, "decode_points"),
     "curve448": _Wide(56, 112, 56, 112, 64, 0, CURVE_CURVE448_NU, "decode_points"),       # (no field selftest: the field is Ed448's)
     "p521": _Wide(68, 136, 68, 67, 76, 11, CURVE_P521_NU, "decode_points"),               # (decodes 67-byte SEC1 strings)
+    "p384": _Wide(48, 96, 48, 49, 56, 13, CURVE_P384_NU, "decode_points"),                # (decodes 49-byte SEC1 strings)
 }
 
 
@@ -377,6 +388,7 @@ blsg2_hash_to_field_batch = functools.partial(_wide_hash_to_field_batch, "blsg2"
 ed448_hash_to_field_batch = functools.partial(_wide_hash_to_field_batch, "ed448")
 curve448_hash_to_field_batch = functools.partial(_wide_hash_to_field_batch, "curve448")
 p521_hash_to_field_batch = functools.partial(_wide_hash_to_field_batch, "p521")
+p384_hash_to_field_batch = functools.partial(_wide_hash_to_field_batch, "p384")
 
 
 def lib() -> ctypes.CDLL:
@@ -715,7 +727,8 @@ class Context:
 
     # ---- the wide suites (include/dotring_hip.h; widths in _WIDE): BLS12-381 G1 (points 96 bytes x || y little-endian, 96 zero bytes the
     # identity), G2 (Fq2 elements c0 || c1; 192 zero bytes the identity), Ed448 (the identity (0, 1) as itself) and Curve448 (u || v, the
-    # identity 112 bytes of 0xff in and out) and P-521 (136 zero bytes the identity; scalars below 2^521); scalars as they are
+    # identity 112 bytes of 0xff in and out) and P-521 (136 zero bytes the identity; scalars below 2^521) and P-384 (96 zero bytes the
+    # identity); scalars as they are
     def _wide_map_to_curve(self, suite: str, us: bytes, per_item: int, clear: bool = True):
         """dr_<suite>_map_to_curve: (x||y bytes, flags) for len(us) / (elem per_item) items; clear = False: before the cofactor clearing.
         per_item other than 1 or 2 is the library's to refuse."""
@@ -776,7 +789,7 @@ class Context:
 
     def _wide_field_selftest(self, suite: str, a_limbs: bytes, b_limbs: bytes):
         """dr_<suite>_field_selftest: (n x records x elem result bytes, n flag bytes) for n pairs of raw limb images (little-endian int32:
-        14 limbs for G1, 2 x 14 for G2, 16 for Ed448, 19 for P-521)."""
+        14 limbs for G1, 2 x 14 for G2, 16 for Ed448, 19 for P-521, 14 for P-384)."""
         w = _WIDE[suite]
         return self._limb_selftest(getattr(lib(), f"dr_{suite}_field_selftest"), w.records, a_limbs, b_limbs, w.limbs, w.elem)
 
@@ -807,6 +820,12 @@ class Context:
     p521_msm_groups = functools.partialmethod(_wide_msm_groups, "p521")
     p521_decode_points = functools.partialmethod(_wide_flagged, "p521")
     p521_field_selftest = functools.partialmethod(_wide_field_selftest, "p521")
+    p384_map_to_curve = functools.partialmethod(_wide_map_to_curve, "p384")
+    p384_encode_to_curve_batch = functools.partialmethod(_wide_encode_to_curve_batch, "p384")
+    p384_scalar_mul_batch = functools.partialmethod(_wide_scalar_mul_batch, "p384")
+    p384_msm_groups = functools.partialmethod(_wide_msm_groups, "p384")
+    p384_decode_points = functools.partialmethod(_wide_flagged, "p384")
+    p384_field_selftest = functools.partialmethod(_wide_field_selftest, "p384")
 
     def blsg2_check_points(self, pts_xy: bytes, subgroup: bool = True) -> bytes:
         """dr_blsg2_check_points: one flag byte per 192-byte point: on the curve, and with `subgroup` also r P = O."""

@@ -1,4 +1,4 @@
-// libdotring_hip.so — C ABI, part 4 of 9: native batch orchestration.  Pedersen / IETF / Ring-VRF prove_batch and
+// libdotring_hip.so — C ABI, part 4 of 10: native batch orchestration.  Pedersen / IETF / Ring-VRF prove_batch and
 // batch_verify run the whole protocol in the library: GPU phases through the entry points of the other parts, the hashing
 // between them on worker threads (hosthash.hpp, hostproto.hpp).
 #include "capi_internal.hpp"

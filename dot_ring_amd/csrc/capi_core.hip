@@ -1,4 +1,4 @@
-// libdotring_hip.so — C ABI (include/dotring_hip.h), part 1 of 9: contexts, device memory, profiling, seam A (the
+// libdotring_hip.so — C ABI (include/dotring_hip.h), part 1 of 10: contexts, device memory, profiling, seam A (the
 // Bandersnatch / twisted Edwards kernels of kernels_bsn.hip.h) and hash-to-curve.  See capi_internal.hpp for the layout.
 #include "capi_suite.hpp"
 #include "hostsmall.hpp"

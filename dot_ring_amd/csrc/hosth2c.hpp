@@ -1,5 +1,5 @@
 // RFC 9380 section 5 on the host, once for every suite: expand_message_xmd, expand_message_xof, and the reductions of the wide fields
-// (BLS12-381's Fq from 64 bytes, Ed448's field from 84).  Plain C++: tests/native/h2c_hash_check.cpp builds it without the HIP toolchain.
+// (BLS12-381's Fq from 64 bytes, Ed448's field from 84, P-521's from 98, P-384's from 72).  Plain C++: tests/native/h2c_hash_check.cpp builds it without the HIP toolchain.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -119,6 +119,42 @@ inline void fp521_reduce_be98(const uint8_t* in, uint8_t* out) {
     std::memcpy(out, s, 68);
 }
 
+// 72 big-endian bytes (576 bits) mod P-384's p = 2^384 - 2^128 - 2^96 + 2^32 - 1 -> 48 bytes little-endian.  2^384 = 2^128 + 2^96 - 2^32 + 1:
+// with hi the 192 bits above lo's 384, the value is lo + hi + (hi << 96) + (hi << 128) - (hi << 32), every shift a whole number of 32-bit
+// words; the sum is not negative and below 2^384 + 2^321 < 2 p, so p comes off at most once (the loop allows twice)
+inline void fp384_reduce_be72(const uint8_t* in, uint8_t* out) {
+    static const uint32_t PW[12] = {0xffffffffu, 0, 0, 0xffffffffu, 0xfffffffeu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu,
+                                    0xffffffffu, 0xffffffffu};
+    uint32_t w[18];
+    for (int j = 0; j < 18; j++) {
+        const uint8_t* q = in + 68 - 4 * j;
+        w[j] = (uint32_t)q[3] | (uint32_t)q[2] << 8 | (uint32_t)q[1] << 16 | (uint32_t)q[0] << 24;
+    }
+    const uint32_t* hi = w + 12;
+    uint32_t v[13];
+    int64_t c = 0;
+    for (int j = 0; j < 13; j++) {
+        int64_t t = c + (j < 12 ? w[j] : 0);
+        if (j < 6) t += hi[j];
+        if (j >= 3 && j < 9) t += hi[j - 3];
+        if (j >= 4 && j < 10) t += hi[j - 4];
+        if (j >= 1 && j < 7) t -= hi[j - 1];
+        v[j] = (uint32_t)t;
+        c = t >> 32;
+    }
+    for (int pass = 0; pass < 2; pass++) {
+        uint32_t d[13];
+        int64_t borrow = 0;
+        for (int j = 0; j < 13; j++) {
+            const int64_t t = (int64_t)v[j] - (j < 12 ? PW[j] : 0) + borrow;
+            d[j] = (uint32_t)t;
+            borrow = t >> 32;
+        }
+        if (borrow == 0) std::memcpy(v, d, sizeof d);
+    }
+    std::memcpy(out, v, 48);
+}
+
 // hash_to_field of the BLS12-381 suites: expand_message_xmd over SHA-256 to `chunks` x 64 bytes (at most 4), each big-endian mod p;
 // out = chunks x 48 bytes little-endian.  G1 asks for one chunk per element, G2 for two (c0 || c1).
 inline void hash_to_field_fq(const void* dst, size_t dst_len, unsigned chunks, const uint8_t* salt, size_t salt_len, const uint8_t* msg, size_t len,
@@ -140,6 +176,14 @@ inline void hash_to_field_fp521(const void* dst, size_t dst_len, unsigned count,
     uint8_t raw[196];
     expand_message_xmd<Sha512, 128, 64>(dst, dst_len, salt, salt_len, msg, len, 98 * (size_t)count, raw);
     for (unsigned k = 0; k < count; k++) fp521_reduce_be98(raw + 98 * k, out + 68 * k);
+}
+
+// hash_to_field of the P-384 suites: expand_message_xmd over SHA-384 to count x 72 bytes (at most 2); out = count x 48 bytes little-endian
+inline void hash_to_field_fp384(const void* dst, size_t dst_len, unsigned count, const uint8_t* salt, size_t salt_len, const uint8_t* msg, size_t len,
+                                uint8_t* out) {
+    uint8_t raw[144];
+    expand_message_xmd<Sha384, 128, 48>(dst, dst_len, salt, salt_len, msg, len, 72 * (size_t)count, raw);
+    for (unsigned k = 0; k < count; k++) fp384_reduce_be72(raw + 72 * k, out + 48 * k);
 }
 
 }  // namespace drh

@@ -1,5 +1,5 @@
 // Host-side hash functions for the Fiat-Shamir / VRF transcripts that sit between GPU phases:
-// SHA-512 and SHA-256 (FIPS 180-4) and the Keccak sponge behind SHAKE128 / SHAKE256 (FIPS 202).
+// SHA-512, SHA-384 and SHA-256 (FIPS 180-4) and the Keccak sponge behind SHAKE128 / SHAKE256 (FIPS 202).
 // The reference hashes with hashlib (dot_ring/vrf/primitives.py:26-55, ring_proof/transcript/transcript.py:21-136,
 // curve/curve.py:145-185); a batch of proofs needs ~40 small hashes per proof, which the native prover runs on
 // worker threads instead of one interpreter call each.  Checked against hashlib in tests/test_native_host.py.
@@ -94,6 +94,29 @@ struct Sha512 {
     }
     static void hash(const void* data, size_t len, uint8_t out[64]) {
         Sha512 s;
+        s.update(data, len);
+        s.final(out);
+    }
+};
+
+// ---------------------------------------------------------------- SHA-384 (the P-384 suites' hash_to_field)
+// SHA-512's compression and padding with initial values of its own and the first 48 bytes of the state as the digest (FIPS 180-4, 5.3.4)
+struct Sha384 : Sha512 {
+    Sha384() { reset(); }
+    void reset() {
+        static const uint64_t iv[8] = {0xcbbb9d5dc1059ed8ULL, 0x629a292a367cd507ULL, 0x9159015a3070dd17ULL, 0x152fecd8f70e5939ULL,
+                                       0x67332667ffc00b31ULL, 0x8eb44a8768581511ULL, 0xdb0c2e0d64f98fa7ULL, 0x47b5481dbefa4fa4ULL};
+        std::memcpy(h, iv, sizeof h);
+        fill = 0;
+        total = 0;
+    }
+    void final(uint8_t out[48]) {
+        uint8_t full[64];
+        Sha512::final(full);
+        std::memcpy(out, full, 48);
+    }
+    static void hash(const void* data, size_t len, uint8_t out[48]) {
+        Sha384 s;
         s.update(data, len);
         s.final(out);
     }

@@ -1,17 +1,17 @@
 // The wave-per-workgroup scalar-multiplication family of every curve with kernels of its own — the four native 256-bit curves (Ed25519,
-// Baby JubJub, P-256, secp256k1), BLS12-381's E(Fq) (48-byte coordinates), Ed448, Curve448 (56-byte coordinates and scalars) and P-521
-// (68-byte) — as one set of templates over a description C of the curve: the memory forms, the fixed-schedule scalar multiplication the
+// Baby JubJub, P-256, secp256k1), BLS12-381's E(Fq) (48-byte coordinates), Ed448, Curve448 (56-byte coordinates and scalars), P-521
+// (68-byte) and P-384 (48-byte coordinates and scalars) — as one set of templates over a description C of the curve: the memory forms, the fixed-schedule scalar multiplication the
 // provers' secret scalars go through, the two kernel bodies built on it, and the SEC1-compressed decoder.  kernels_ed25519.hip.h
 // (Ed25519Curve), kernels_bjj.hip.h (BjjCurve), kernels_p256.hip.h (P256Curve), kernels_secp256k1.hip.h (Secp256k1Curve),
-// kernels_g1_h2c.hip.h (G1hCurve), kernels_ed448.hip.h (Ed448Curve), kernels_curve448.hip.h (Curve448Curve) and kernels_p521.hip.h
-// (P521Curve) each give a field, a group law, one description and one thin named __global__ per kernel; the schedule below exists once.
+// kernels_g1_h2c.hip.h (G1hCurve), kernels_ed448.hip.h (Ed448Curve), kernels_curve448.hip.h (Curve448Curve), kernels_p521.hip.h
+// (P521Curve) and kernels_p384.hip.h (P384Curve) each give a field, a group law, one description and one thin named __global__ per kernel; the schedule below exists once.
 // C provides
 //   Fe, Point                      the field element (int32_t limbs l[]) and the point: members x, y, z and, when EXTENDED, t
 //   WORDS                          the 32-bit words of a coordinate at the ABI: 8, 12, 14 or 17 (any count).  A point is 2 WORDS words
 //                                  (x || y) and moves as the widest of uint4 / uint2 / words that divides its byte length
-//   SCALAR_WORDS                   the 32-bit words of a scalar at the ABI: 8, 14 or 17; it moves the same way
+//   SCALAR_WORDS                   the 32-bit words of a scalar at the ABI: 8, 12, 14 or 17; it moves the same way
 //   BLOCK, WINDOWS                 the workgroup size (64: one wave) and the number of signed 4-bit windows of a scalar: 8 SCALAR_WORDS + 1
-//                                  where a carry can leave the top digit (65: an order of 256 bits; 113: any k < 2^448), otherwise the
+//                                  where a carry can leave the top digit (65: an order of 256 bits; 97: any k < 2^384; 113: any k < 2^448), otherwise the
 //                                  digits that can be non-zero (64: an order below 2^255; 131: k < 2^521, p521_law.hip.h)
 //   EXTENDED, LDS_WORDS            whether the point has a fourth coordinate t; the words of one coordinate in the LDS table
 //   ZERO_IS_IDENTITY               whether zero bytes stand for the identity at the ABI (the Weierstrass curves: (0, 0) is no point)

@@ -1441,36 +1441,33 @@ class Curve448Point(_WideRfc9380, _MontgomeryPoint):
 
 
 # ------------------------------------------------------------------ batched helpers over the C ABI
-class P521Point(_WideRfc9380, _Sec1Codec, _ShortWeierstrassPoint):
-    """Affine point of P521_RO / P521_NU (dot_ring/curve/specs/p521.py): y^2 = x^3 - 3 x + b over p = 2^521 - 1, prime order, cofactor 1,
-    the identity (None, None).  Coordinates and scalars are 66 bytes (68 at the C ABI), so nothing here goes through the 64-byte entry
-    points: scalar multiplications, MSMs, decoding and hashing to the curve run on the dr_p521_* kernels (kernels_p521.hip.h), whose
-    scalars are used as they are below 2^521 — the reduction mod n happens here and is exact for every point, the group having prime
-    order n.  Single additions are the shared host big-int law; SEC1 strings carry 66-byte coordinates."""
-    _P = 2**521 - 1
-    _N = 0x01FFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFA51868783BF2F966B7FCC0148F709A5D03BB5C9B8899C47AEBB6FB71E91386409
-    _H, _CV = 1, _native.CURVE_P521_RO
-    _SW_A = -3
-    _SW_B = 0x0051953EB9618E1C9A1F929A21A0B68540EEA2DA725B99B315F3B8B489918EF109E156193951EC7E937B1652C0BD3BB1BF073573DF883D2C34F1EF451FD46B503F00
-    _SEC1_LEN = 66
+class _WidePrimeSwPoint(_WideRfc9380, _Sec1Codec, _ShortWeierstrassPoint):
+    """What P-521 and P-384 share: a short Weierstrass curve of prime order (cofactor 1) over p = 3 mod 4 whose coordinates and scalars do
+    not fit the 64-byte entry points, so scalar multiplications, MSMs, decoding and hashing to the curve run on the dr_<_SUITE>_* kernels.
+    Coordinates and scalars are _ABI_LEN bytes little-endian at the C ABI, 2 _ABI_LEN zero bytes the identity; the kernels use scalars as
+    they are — the reduction mod n happens here and is exact for every point, the group having prime order n.  Single additions are the
+    shared host big-int law; SEC1 strings carry _SEC1_LEN-byte coordinates.  A concrete class gives _P, _N, _SW_B, _CV, _SEC1_LEN,
+    _ABI_LEN and _SUITE."""
+    _H, _SW_A = 1, -3
     _WIDE = True                  # the VRF classes keep their Python orchestration: the native batch provers carry 32-byte scalars
-    _SUITE, _NO_IMAGE = "p521", "the map to the curve has no value"       # (never raised: every field element has an image)
+    _NO_IMAGE = "the map to the curve has no value"       # (never raised: every field element has an image)
     __slots__ = ()
 
-    # -- the C ABI's forms: x || y, 68 + 68 bytes little-endian, 136 zero bytes the identity
-    @staticmethod
-    def _pack(points) -> bytes:
-        return b"".join((p.x or 0).to_bytes(68, "little") + (p.y or 0).to_bytes(68, "little") for p in points)
+    # -- the C ABI's forms: x || y little-endian, zero bytes the identity
+    @classmethod
+    def _pack(cls, points) -> bytes:
+        n = cls._ABI_LEN
+        return b"".join((p.x or 0).to_bytes(n, "little") + (p.y or 0).to_bytes(n, "little") for p in points)
 
     @classmethod
     def _unpack(cls, raw: bytes):
         """Kernel outputs are group elements by construction: no per-point curve check."""
-        frm, mk = int.from_bytes, cls._trusted
-        return [mk(frm(raw[i : i + 68], "little"), frm(raw[i + 68 : i + 136], "little")) for i in range(0, len(raw), 136)]
+        frm, mk, n = int.from_bytes, cls._trusted, cls._ABI_LEN
+        return [mk(frm(raw[i : i + n], "little"), frm(raw[i + n : i + 2 * n], "little")) for i in range(0, len(raw), 2 * n)]
 
     @classmethod
     def _scalars(cls, scalars) -> bytes:
-        return b"".join((int(k) % cls._N).to_bytes(68, "little") for k in scalars)
+        return b"".join((int(k) % cls._N).to_bytes(cls._ABI_LEN, "little") for k in scalars)
 
     def __mul__(self, scalar: int):
         return self._scalar_mul_batch([self], [scalar])[0]
@@ -1490,7 +1487,7 @@ class P521Point(_WideRfc9380, _Sec1Codec, _ShortWeierstrassPoint):
     def clear_cofactor(self):
         return self                                   # the cofactor is 1
 
-    # -- codec: SEC1 with 66-byte coordinates; a compressed string's root is p = 3 mod 4's, on the host
+    # -- codec: a compressed string's root is p = 3 mod 4's, on the host
     @classmethod
     def _sec1_decompress(cls, prefix: int, x: int):
         p = cls._P
@@ -1500,26 +1497,49 @@ class P521Point(_WideRfc9380, _Sec1Codec, _ShortWeierstrassPoint):
             raise ValueError("Invalid point encoding")
         return cls(x, y if y % 2 == prefix % 2 else p - y)
 
-    # -- hash to curve (RFC 9380 P521_XMD:SHA-512_SSWU_RO_ / _NU_): expand_message_xmd natively on the host, the map on the GPU
+    # -- hash to curve (RFC 9380 ..._XMD:SHA-..._SSWU_RO_ / _NU_): expand_message_xmd natively on the host, the map on the GPU
     @classmethod
     def map_to_curve_simple_swu(cls, u: int):
-        return cls._mapped((int(u) % cls._P).to_bytes(68, "little"), 1, clear=False)[0]
+        return cls._mapped((int(u) % cls._P).to_bytes(cls._ABI_LEN, "little"), 1, clear=False)[0]
 
     # -- what the module-level batch helpers ask a wide point type
     @classmethod
     def _scalar_mul_batch(cls, points, scalars):
-        return cls._unpack(runtime.context().p521_scalar_mul_batch(cls._pack(points), cls._scalars(scalars)))
+        return cls._unpack(runtime.context()._wide_scalar_mul_batch(cls._SUITE, cls._pack(points), cls._scalars(scalars)))
 
     @classmethod
     def _msm_groups(cls, points, scalars, m: int):
         if m > 64:                               # the kernel folds up to 64 terms in a wave: longer groups fold on the host (msm)
             return [cls.msm(points[i : i + m], scalars[i : i + m]) for i in range(0, len(points), m)]
-        return cls._unpack(runtime.context().p521_msm_groups(cls._pack(points), cls._scalars(scalars), m))
+        return cls._unpack(runtime.context()._wide_msm_groups(cls._SUITE, cls._pack(points), cls._scalars(scalars), m))
 
     @classmethod
     def _valid_points(cls, points) -> list[bool]:
         """curve.py:56 for a batch: on the curve and not the identity (prime order: nothing else to ask)"""
         return [not pt.is_identity() and pt.is_on_curve() for pt in points]
+
+
+class P521Point(_WidePrimeSwPoint):
+    """Affine point of P521_RO / P521_NU (dot_ring/curve/specs/p521.py): y^2 = x^3 - 3 x + b over p = 2^521 - 1, the identity (None, None).
+    Coordinates and scalars are 66 bytes (68 at the C ABI, scalars below 2^521); the kernels are kernels_p521.hip.h's."""
+    _P = 2**521 - 1
+    _N = 0x01FFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFA51868783BF2F966B7FCC0148F709A5D03BB5C9B8899C47AEBB6FB71E91386409
+    _CV = _native.CURVE_P521_RO
+    _SW_B = 0x0051953EB9618E1C9A1F929A21A0B68540EEA2DA725B99B315F3B8B489918EF109E156193951EC7E937B1652C0BD3BB1BF073573DF883D2C34F1EF451FD46B503F00
+    _SEC1_LEN, _ABI_LEN, _SUITE = 66, 68, "p521"
+    __slots__ = ()
+
+
+class P384Point(_WidePrimeSwPoint):
+    """Affine point of P384_RO / P384_NU (dot_ring/curve/specs/p384.py): y^2 = x^3 - 3 x + b over p = 2^384 - 2^128 - 2^96 + 2^32 - 1, the
+    identity (None, None).  Coordinates and scalars are 48 bytes, at the C ABI too; the kernels are kernels_p384.hip.h's, whose 97 windows
+    take every 384-bit value."""
+    _P = 2**384 - 2**128 - 2**96 + 2**32 - 1
+    _N = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFC7634D81F4372DDF581A0DB248B0A77AECEC196ACCC52973
+    _CV = _native.CURVE_P384_RO
+    _SW_B = 0xB3312FA7E23EE7E4988E056BE3F82D19181D9C6EFE8141120314088F5013875AC656398D8A2ED19D2A85C8EDD3EC2AEF
+    _SEC1_LEN, _ABI_LEN, _SUITE = 48, 48, "p384"
+    __slots__ = ()
 
 
 def pack_points(points) -> bytes:
@@ -1951,3 +1971,28 @@ _P521_PARAMS = SuiteParams(
 P521_RO = _variant(P521Point, "P521_RO", _P521_PARAMS)
 P521_NU = _variant(P521Point, "P521_NU", _nu(_P521_PARAMS, _native.CURVE_P521_NU))
 P521 = P521_RO
+
+
+# dot_ring/curve/specs/p384.py: y^2 = x^3 - 3 x + b over 2^384 - 2^128 - 2^96 + 2^32 - 1, prime order, cofactor 1, SEC1 compressed points
+# of 49 bytes, 48-byte scalars, SHA-384 transcripts (the first suite with a 48-byte digest), hashing to the curve by RFC 9380's
+# P384_XMD:SHA-384_SSWU_RO_ (two field elements, L = 72, Z = -12) or ..._NU_ (one); both variants share the RO suite id, and the Pedersen
+# blinding base IS the generator, as in the reference.  Not twisted Edwards: RingProofParams refuses them.  challenge_len = 24 is the
+# reference's own figure; its VRF layer squeezes 16 bytes whatever this says, and so does this one.
+_P384_G = (0xAA87CA22BE8B05378EB1C71EF320AD746E1D3B628BA79B9859F741E082542A385502F25DBF55296C3A545E3872760AB7,
+           0x3617DE4A96262C6F5D9E98BF9292DC29F8F41DBD289A147CE9DA3113B5F0B8C00A60B1CE1D7E819D7A431D7C90EA0E5F)
+_P384_PARAMS = SuiteParams(
+    suite_id=b"P384_XMD:SHA-384_SSWU_RO_", hash_fn=hashlib.sha384, xof=False,
+    auxiliary_points=AuxiliaryPoints(_P384_G, None, None),
+    field_modulus=P384Point._P,
+    subgroup_order=P384Point._N,
+    cofactor=1,
+    a=-3,
+    d=P384Point._SW_B,            # (the reference's b)
+    generator=_P384_G,
+    encoding=Encoding(point_len=49, challenge_len=24),
+    curve_id=_native.CURVE_P384_RO,
+    e2c="sswu",
+)
+P384_RO = _variant(P384Point, "P384_RO", _P384_PARAMS)
+P384_NU = _variant(P384Point, "P384_NU", _nu(_P384_PARAMS, _native.CURVE_P384_NU))
+P384 = P384_RO

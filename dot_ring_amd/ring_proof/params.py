@@ -84,7 +84,7 @@ class RingProofParams:
                                _native.CURVE_P256_RO, _native.CURVE_P256_NU, _native.CURVE_CURVE25519_RO, _native.CURVE_CURVE25519_NU,
                                _native.CURVE_BLS12_381_G1, _native.CURVE_BLS12_381_G1_NU, _native.CURVE_BLS12_381_G2,
                                _native.CURVE_BLS12_381_G2_NU, _native.CURVE_CURVE448_RO, _native.CURVE_CURVE448_NU, _native.CURVE_P521_RO,
-                               _native.CURVE_P521_NU)
+                               _native.CURVE_P521_NU, _native.CURVE_P384_RO, _native.CURVE_P384_NU)
         if getattr(self.cv.curve.params, "curve_id", None) in not_twisted_edwards:   # params.py _validate_curve
             raise ValueError(f"{self.cv.name} ring proofs require a Twisted Edwards curve")
         aux = self.cv.curve.params.auxiliary_points

@@ -37,10 +37,10 @@ class VRF:
             # a Montgomery curve, as RingProofParams says, and the ring proof's columns are 32-byte scalars
             raise ValueError(f"{cls.__name__} has no {variant.name} suite: ring proofs require a Twisted Edwards curve, and its 56-byte "
                              "coordinates do not fit the ring proof's columns")
-        if cls.RING and variant.curve.params.curve_id in (_native.CURVE_P521_RO, _native.CURVE_P521_NU):
+        if cls.RING and variant.curve.params.curve_id in (_native.CURVE_P521_RO, _native.CURVE_P521_NU, _native.CURVE_P384_RO, _native.CURVE_P384_NU):
             # a short Weierstrass curve, as RingProofParams says, and the ring proof's columns are 32-byte scalars
-            raise ValueError(f"{cls.__name__} has no {variant.name} suite: ring proofs require a Twisted Edwards curve, and its 66-byte "
-                             "coordinates do not fit the ring proof's columns")
+            raise ValueError(f"{cls.__name__} has no {variant.name} suite: ring proofs require a Twisted Edwards curve, and its "
+                             f"{variant.point_type._SEC1_LEN}-byte coordinates do not fit the ring proof's columns")
         bound = _BOUND.get((cls, variant.name))
         if bound is None or bound.cv is not variant:
             bound = _BOUND[(cls, variant.name)] = type(f"{cls.__name__}[{variant.name}]", (cls,), {"cv": variant})

@@ -1,4 +1,4 @@
-"""Byte codecs of the VRF layer: little-endian scalars of the group order's width (32 bytes, 56 for Ed448 and Curve448, 66 for P-521), compressed points
+"""Byte codecs of the VRF layer: little-endian scalars of the group order's width (32 bytes, 56 for Ed448 and Curve448, 66 for P-521, 48 for P-384), compressed points
 (reference behaviour: dot_ring/vrf/codec.py:9-51 — same function names, lengths and error texts, because the
 reference's tests match on them).  Point decoding is a batch operation here: decompression and the subgroup check of
 any number of points are one kernel launch (dr_bsn_decode_points)."""
@@ -64,7 +64,7 @@ def dec_points(cv, values) -> list:
         blobs.append(v)
     if not blobs:
         return []
-    wide = cv.point_type._WIDE       # Ed448, Curve448 (112-byte points), P-521 (67-byte SEC1 strings): checked by the suite's dr_<suite>_decode_points(check = 1)
+    wide = cv.point_type._WIDE       # Ed448, Curve448 (112-byte points), P-521 and P-384 (67- and 49-byte SEC1 strings): checked by the suite's dr_<suite>_decode_points(check = 1)
     if wide:
         xy, flags = runtime.context()._wide_flagged(cv.point_type._SUITE, b"".join(blobs), True)
     else:

@@ -475,6 +475,47 @@ DR_API int dr_p521_decode_points(dr_ctx *ctx, int check, const uint8_t *enc /* n
 DR_API int dr_p521_field_selftest(dr_ctx *ctx, const int32_t *a_limbs /* n*19 */, const int32_t *b_limbs /* n*19 */, size_t n,
                                   uint8_t *out /* n*11*68 */, uint8_t *flags /* n */);
 
+/* DR_CURVE_P384_RO (the reference's P384 = P384_RO) and DR_CURVE_P384_NU (P384_NU): P-384, y^2 = x^3 - 3 x + b over
+ * p = 2^384 - 2^128 - 2^96 + 2^32 - 1 (dot_ring/curve/specs/p384.py), prime order, cofactor 1, hashing by RFC 9380's
+ * P384_XMD:SHA-384_SSWU_RO_ (two field elements) or ..._NU_ (one) — csrc/kernels_p384.hip.h on the complete law of csrc/p384_law.hip.h
+ * over csrc/fp384.hip.h (Montgomery form inside the kernels only).  Entry points of their own (dr_p384_*); every 64-byte entry point
+ * refuses these two ids with DR_ERR_INVALID, and so do the dr_blsg1_* / dr_blsg2_* / dr_ed448_* / dr_curve448_* / dr_p521_* calls as
+ * variants; the dr_p384_* calls refuse every other id.  Formats: field elements and coordinates are 48 bytes little-endian, canonical
+ * (< p); points are affine x || y, 96 bytes, and 96 ZERO BYTES ARE THE IDENTITY, in and out ((0, 0) is not on the curve); scalars are
+ * 48 bytes little-endian used AS THEY ARE, every 384-bit value (none is refused).  Coordinates or elements at or above p and other
+ * per_item values give DR_ERR_INVALID.
+ *   dr_p384_hash_to_field_batch    host only: expand_message_xmd over SHA-384, L = 72 bytes per element, the variant's DST
+ *                                  (QUUX-V01-CS02-with-P384_XMD:SHA-384_SSWU_RO_ / ..._NU_); two elements (96 bytes) per message for RO,
+ *                                  one (48) for NU.
+ *   dr_p384_map_to_curve           n items of per_item (2 or 1) elements: out_xy[i] = the sum of their simplified SWU images (Z = -12, no
+ *                                  isogeny).  ok[i] = 1 always: every element has an image.  The cofactor is 1: `clear` changes nothing.
+ *   dr_p384_encode_to_curve_batch  encode_to_curve(salt_i || msg_i) (salts nullable): hash_to_field on the worker threads, then the map.
+ *   dr_p384_scalar_mul_batch       out[i] = k[i] P[i], the window loop on a fixed schedule (97 signed 4-bit windows) as for the other
+ *                                  native suites; the final inversion of Z (division steps) is not fixed-time.
+ *   dr_p384_msm_groups             out[g] = sum_{j<m} k[g m + j] P[g m + j], m <= 64.
+ *   dr_p384_decode_points          SEC1 compressed, 49 bytes: ok[i] = 1 and out_xy[i] = x || y iff byte 0 is 0x02 or 0x03, x (bytes 1..48
+ *                                  big-endian) is below p and x^3 - 3 x + b is a square, y of byte 0's parity; otherwise ok[i] = 0 and
+ *                                  96 zero bytes.  No string encodes the identity and the cofactor is 1, so check = 0 and check = 1 are
+ *                                  the same kernel; the parameter is the suites' common signature.
+ *   dr_p384_field_selftest         diagnostic of csrc/fp384.hip.h on RAW limb images (14 signed 32-bit limbs; an image stands for its
+ *                                  value times 2^-392 mod p): out[i] = thirteen 48-byte canonical records (a b, a^2, a + b, a - b, -a,
+ *                                  carry(a), 4 a, a^-1, carry(a)^((p + 1) / 4), a, -(2^28 - 1) a, carry(a)^2, the fused 2 a b), flags[i]:
+ *                                  bit 0 a is a square, bit 1 a is odd, bit 2 a is zero, bit 3 a = b. */
+enum { DR_CURVE_P384_RO = 25, DR_CURVE_P384_NU = 26 };
+DR_API int dr_p384_hash_to_field_batch(int variant, const uint8_t *msgs, const uint64_t *off, size_t count, uint8_t *out /* count*(96|48) */);
+DR_API int dr_p384_map_to_curve(dr_ctx *ctx, const uint8_t *us /* n*per_item*48 */, size_t n, int per_item, int clear,
+                                uint8_t *out_xy /* n*96 */, uint8_t *ok /* n */);
+DR_API int dr_p384_encode_to_curve_batch(dr_ctx *ctx, int variant, const uint8_t *msgs, const uint64_t *off, const uint8_t *salts,
+                                         const uint64_t *salt_off, size_t count, uint8_t *out_xy /* count*96 */);
+DR_API int dr_p384_scalar_mul_batch(dr_ctx *ctx, const uint8_t *pts_xy /* n*96 */, const uint8_t *scalars /* n*48 */, size_t n,
+                                    uint8_t *out_xy /* n*96 */);
+DR_API int dr_p384_msm_groups(dr_ctx *ctx, const uint8_t *pts_xy, const uint8_t *scalars, size_t groups, size_t m,
+                              uint8_t *out_xy /* groups*96 */);
+DR_API int dr_p384_decode_points(dr_ctx *ctx, int check, const uint8_t *enc /* n*49 */, size_t n, uint8_t *out_xy /* n*96 */,
+                                 uint8_t *ok /* n */);
+DR_API int dr_p384_field_selftest(dr_ctx *ctx, const int32_t *a_limbs /* n*14 */, const int32_t *b_limbs /* n*14 */, size_t n,
+                                  uint8_t *out /* n*13*48 */, uint8_t *flags /* n */);
+
 /* square root in the Bandersnatch base field; DR_ERR_NOTSQUARE if none exists. Host-side, no ctx. */
 DR_API int dr_fr_sqrt(const uint8_t in[32], uint8_t out[32]);
 

@@ -6,6 +6,7 @@ DESIGN.md compares it with.  `python3 tools/encode_timing.py SUITE YARDSTICK [co
   Ed448_RO Ed25519_RO               the same map one field down
   Curve448_RO Ed448_RO              the same field and the same Elligator 2; another law and no isogeny after the map
   P521_RO Ed448_RO                  the other wide suite with VRFs: 19 limbs against 16, SSWU against Elligator 2
+  P384_RO P521_RO                   the same map and law on 14 Montgomery limbs against 19 with a fold, SHA-384 against SHA-512
 Each figure is ONE call after one warm-up call of the same size — unrepeated, to be quoted as such."""
 import os
 import sys
