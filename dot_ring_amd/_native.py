@@ -166,6 +166,7 @@ _PROTOTYPES.update({
     "dr_p384_msm_groups": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_size_t, c_char_p]),
     "dr_p384_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
     "dr_p384_field_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p, c_void_p]),
+    "dr_wide_msm": (c_int, [c_void_p, c_int, c_char_p, c_char_p, c_size_t, c_char_p]),
     "dr_curve25519_scalar_mul_batch": (c_int, [c_void_p, c_char_p, c_char_p, c_char_p, c_size_t, c_char_p, c_char_p]),
     "dr_curve25519_msm_groups": (c_int, [c_void_p, c_char_p, c_char_p, c_char_p, c_size_t, c_size_t, c_char_p, c_char_p]),
     "dr_curve25519_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
@@ -372,6 +373,11 @@ _WIDE = {
     "p521": _Wide(68, 136, 68, 67, 76, 11, CURVE_P521_NU, "decode_points"),               # (decodes 67-byte SEC1 strings)
     "p384": _Wide(48, 96, 48, 49, 56, 13, CURVE_P384_NU, "decode_points"),                # (decodes 49-byte SEC1 strings)
 }
+
+
+WIDE_PIP_FROM = 256            # csrc/msm_plan.hpp: the term count from which dr_wide_msm takes the bucket method
+# the suites dr_wide_msm serves, by the curve id it takes (either variant: RO and NU are one group)
+_WIDE_MSM_CURVE = {"p384": CURVE_P384_RO, "p521": CURVE_P521_RO, "ed448": CURVE_ED448_RO, "curve448": CURVE_CURVE448_RO}
 
 
 def _wide_hash_to_field_batch(suite: str, variant: int, msgs) -> bytes:
@@ -769,6 +775,19 @@ class Context:
         out = ctypes.create_string_buffer(max(1, w.point * groups))
         _check(getattr(lib(), f"dr_{suite}_msm_groups")(self.handle, pts_xy, scalars, groups, m, out))
         return out.raw[: w.point * groups]
+
+    def wide_msm(self, suite: str, pts_xy: bytes, scalars: bytes) -> bytes:
+        """dr_wide_msm: ONE sum of n terms k_i P_i on "p384", "p521", "ed448" or "curve448", in the forms of that suite's msm_groups; from
+        256 terms on by the bucket method (csrc/wave_msm.hip.h).  No terms give the identity."""
+        if suite not in _WIDE_MSM_CURVE:
+            raise ValueError("wide_msm serves p384, p521, ed448 and curve448")
+        w = _WIDE[suite]
+        n = len(scalars) // w.scalar
+        if len(scalars) != w.scalar * n or len(pts_xy) != w.point * n:
+            raise ValueError("Points and scalars must have same length")
+        out = ctypes.create_string_buffer(w.point)
+        _check(lib().dr_wide_msm(self.handle, _WIDE_MSM_CURVE[suite], pts_xy, scalars, n, out))
+        return out.raw[: w.point]
 
     def _wide_flagged(self, suite: str, enc: bytes, check: bool = True):
         """dr_<suite>_decode_points: (x||y bytes, flags) for G1's 49-byte SEC1 encodings (check: also r P = O) and Ed448's 112-byte points

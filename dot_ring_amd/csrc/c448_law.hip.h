@@ -108,6 +108,30 @@ DR_F448_FN bool m448_store(const M448Point& p, F448& u, F448& v) {
     return is_zero(p.x) && is_zero(ymz);
 }
 
+// The law as the host side of dr_wide_msm takes it (wide_combine.hpp): the operations of the window combination and the ABI's u || v
+// words <-> a point; the identity is words of 0xffffffff, in and out (the Curve448 entry points' spelling)
+struct M448Law {
+    using Point = M448Point;
+    static constexpr int WORDS = W448, LIMBS = L448;
+    DR_F448_MEMBER static M448Point identity() { return m448_identity(); }
+    DR_F448_MEMBER static M448Point add(const M448Point& p, const M448Point& q) { return m448_add(p, q); }
+    DR_F448_MEMBER static M448Point dbl(const M448Point& p) { return m448_dbl(p); }
+    DR_F448_MEMBER static M448Point from_abi(const uint32_t (&w)[2 * W448]) {
+        uint32_t u[W448], v[W448], o = 0xffffffffu;
+        for (int j = 0; j < W448; j++) { u[j] = w[j]; v[j] = w[W448 + j]; o &= u[j] & v[j]; }
+        if (o == 0xffffffffu) return m448_identity();
+        return m448_load(unpack(u), unpack(v), false);
+    }
+    DR_F448_MEMBER static void to_abi(const M448Point& p, uint32_t (&w)[2 * W448]) {
+        F448 u, v;
+        const bool ident = m448_store(p, u, v);
+        uint32_t uw[W448], vw[W448];
+        pack(u, uw);
+        pack(v, vw);
+        for (int j = 0; j < W448; j++) { w[j] = ident ? 0xffffffffu : uw[j]; w[W448 + j] = ident ? 0xffffffffu : vw[j]; }
+    }
+};
+
 // v^2 = u^3 + A u^2 + u for u, v n (the decoder's test)
 DR_F448_FN bool m448_on_curve(const F448& u, const F448& v) {
     const F448 ua = carry(add(u, F448::small(M448Consts::A)));               // n

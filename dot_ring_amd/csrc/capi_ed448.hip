@@ -7,6 +7,7 @@
 // hash_to_field (expand_message_xof over SHAKE256, L = 84) on the worker threads and checks that inputs are canonical.  Scalars may be
 // secret: they pass through io_a / io_b / io_c only, which ctx_wipe_scratch covers.
 #include "capi_suite.hpp"
+#include "capi_wide_msm.hpp"
 #include "kernels_ed448.hip.h"
 #include "kernels_curve448.hip.h"
 
@@ -25,6 +26,15 @@ struct Ed448Suite : SuiteDefaults {
     static constexpr auto field_selftest = dr::k_ed448_field_selftest;
     static constexpr int block = dr::E448_BLOCK, selftest_records = dr::E448_SELFTEST_RECORDS;
     static constexpr const char *k_scalar_mul = "k_ed448_scalar_mul", *k_msm_groups = "k_ed448_msm_groups", *k_decode = "k_ed448_check_points";
+    // the bucket method of dr_wide_msm (capi_wide_msm.hpp): the law on the host, the bits the tiling covers, the stages' kernels
+    using Law = dr::E448Law;
+    static constexpr int wide_bits = 449;
+    static constexpr auto wide_prepare = dr::k_ed448_msm_prepare;
+    static constexpr auto wide_sort = dr::k_ed448_msm_sort;
+    static constexpr auto wide_accumulate = dr::k_ed448_msm_accumulate;
+    static constexpr auto wide_accumulate_heavy = dr::k_ed448_msm_accumulate_heavy;
+    static constexpr auto wide_reduce = dr::k_ed448_msm_reduce;
+    static constexpr auto wide_fold = dr::k_ed448_msm_fold;
     static constexpr size_t enc_bytes = pt_bytes, rec_bytes = pt_bytes;   // the decoder takes x || y as given: its kernel judges the range
     static constexpr bool decode_gives_points = true, decode_checks_canonical = false;
     // (a field element in {0, 1, p - 1}: kernels_ed448.hip.h, e448_ell2_map)
@@ -64,6 +74,15 @@ struct Curve448Suite : SuiteDefaults {
     static constexpr auto msm_groups = dr::k_c448_msm_groups;
     static constexpr int block = dr::E448_BLOCK;
     static constexpr const char *k_scalar_mul = "k_c448_scalar_mul", *k_msm_groups = "k_c448_msm_groups", *k_decode = "k_c448_decode_points";
+    // the bucket method of dr_wide_msm (capi_wide_msm.hpp): the law on the host, the bits the tiling covers, the stages' kernels
+    using Law = dr::M448Law;
+    static constexpr int wide_bits = 449;
+    static constexpr auto wide_prepare = dr::k_c448_msm_prepare;
+    static constexpr auto wide_sort = dr::k_ed448_msm_sort;
+    static constexpr auto wide_accumulate = dr::k_c448_msm_accumulate;
+    static constexpr auto wide_accumulate_heavy = dr::k_c448_msm_accumulate_heavy;
+    static constexpr auto wide_reduce = dr::k_c448_msm_reduce;
+    static constexpr auto wide_fold = dr::k_c448_msm_fold;
     static constexpr size_t enc_bytes = pt_bytes, rec_bytes = pt_bytes;   // the decoder takes u || v as given: its kernel judges the range
     static constexpr bool decode_gives_points = true, decode_checks_canonical = false;
     // (a field element in {1, p - 1}: the reference's mod_inverse(0); c448_law.hip.h, m448_ell2)
@@ -112,6 +131,15 @@ int dr_ed448_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_t n,
 }
 int dr_ed448_field_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
     return field_selftest<Ed448Suite>(ctx, a_limbs, b_limbs, n, out, flags);
+}
+
+// dr_wide_msm for DR_CURVE_ED448_RO / _NU and DR_CURVE_CURVE448_RO / _NU (the dispatcher is capi_msm.hip's); Curve448's identity travels
+// inside the point as 112 bytes of 0xff, in and out
+int ed448_wide_msm(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy) {
+    return wide_msm<Ed448Suite>(ctx, pts_xy, scalars, n, out_xy);
+}
+int curve448_wide_msm(dr_ctx* ctx, const uint8_t* pts_uv, const uint8_t* scalars, size_t n, uint8_t* out_uv) {
+    return wide_msm<Curve448Suite>(ctx, pts_uv, scalars, n, out_uv);
 }
 
 // ---- Curve448: the identity is 112 bytes of 0xff at every one of them, in and out; there are no flag-byte parameters

@@ -7,6 +7,7 @@
 //   capi_blsg1.hip  the BLS12_381_G1 suites: 48-byte coordinates, hashing to G1 and the group of E(Fq)
 //   capi_blsg2.hip  the BLS12_381_G2 suites: Fq2 coordinates, hashing to G2 and the group of E(Fq2)
 //   capi_ed448.hip  the Ed448 suites: 56-byte coordinates and scalars, hashing to the curve and the group of E(F_p)
+// (wave_msm.hip.h defines none either: the wide suites' units instantiate its templates in their own named kernels)
 // The last three are one description of their suite each (widths, limits, kernels, hashing parameters) and their entry points as calls
 // of capi_suite.hpp's templates, the one host path they share with the five 256-bit suites described in capi_core.hip; every host
 // round trip of a single-launch entry point is io_round below.
@@ -379,10 +380,19 @@ int msm_to_bytes(dr_ctx* ctx, const uint32_t* d_bases, const uint32_t* d_scalars
 int g1_be_to_le_limbs(const uint8_t* be, size_t m, std::vector<uint8_t>& le, bool check_curve);
 // K4: one twisted Edwards MSM by the bucket method (n from a few hundred terms)
 int te_msm_pippenger(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t out_xy[64]);
+// counts[nbuckets] -> perm[nbuckets], the buckets ordered by list length, longest first (k_size_hist / k_size_place of kernels_g1.hip.h:
+// they only look at counts): for the bucket walks of other units (te_msm_pippenger; capi_wide_msm.hpp).  Reserves perm, cells, cell_off, tiles
+int bucket_size_order(dr_ctx* ctx, size_t nbuckets);
 // launch wrappers around kernels_g1.hip.h for the batch verifier
 void g1_launch_decompress(hipStream_t st, const uint8_t* d_enc, uint32_t* d_bases, uint32_t* d_ok, size_t n);
 void g1_launch_bases_to_mont(hipStream_t st, uint32_t* d_bases, size_t n);
 void g1_launch_bases_from_mont(hipStream_t st, const uint32_t* d_bases, uint32_t* d_out, size_t n);
+
+// ---- capi_p384.hip, capi_p521.hip, capi_ed448.hip: dr_wide_msm of their suites (capi_wide_msm.hpp); the dispatcher is capi_msm.hip's
+int p384_wide_msm(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy);
+int p521_wide_msm(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy);
+int ed448_wide_msm(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy);
+int curve448_wide_msm(dr_ctx* ctx, const uint8_t* pts_uv, const uint8_t* scalars, size_t n, uint8_t* out_uv);
 
 // ---- capi_ring.hip
 dr_ctx* ring_prover_ctx(dr_ring_prover* p);

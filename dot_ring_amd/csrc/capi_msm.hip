@@ -440,6 +440,29 @@ TeHost te_host_add(const TeHost& p, const TeHost& q, const drh::Fr& d, const drh
 }
 }  // namespace
 
+// ctx->counts -> ctx->perm on ctx->stream: the buckets by list length, longest first, so that the lanes of a wave of a bucket walk have
+// lists of about one length
+int bucket_size_order(dr_ctx* ctx, size_t nbuckets) {
+    hipStream_t st = ctx->stream;
+    const unsigned szblocks = div_up(nbuckets, dr::SZ_TILE);
+    const size_t ncells = (size_t)dr::SZ_CLASSES * szblocks;
+    TRY(ctx->tiles.reserve((size_t)(div_up(ncells, dr::SCAN_TILE) + 1) * 4));
+    TRY(ctx->perm.reserve(nbuckets * 4));
+    TRY(ctx->cells.reserve(ncells * 4));
+    TRY(ctx->cell_off.reserve(ncells * 4));
+    return launch(ctx, "k_size_sort", [&] {
+        hipLaunchKernelGGL(dr::k_size_hist, dim3(szblocks), dim3(dr::SZ_BLOCK), 0, st, ctx->counts.as<uint32_t>(), nbuckets, szblocks,
+                           ctx->cells.as<uint32_t>());
+        const unsigned nt = div_up(ncells, dr::SCAN_TILE);
+        hipLaunchKernelGGL(dr::k_scan_tiles, dim3(nt), dim3(dr::SCAN_BLOCK), 0, st, ctx->cells.as<uint32_t>(), ctx->cell_off.as<uint32_t>(),
+                           ctx->tiles.as<uint32_t>(), ncells);
+        hipLaunchKernelGGL(dr::k_scan_tile_sums, dim3(1), dim3(dr::SCAN_BLOCK), 0, st, ctx->tiles.as<uint32_t>(), nt, ctx->tiles.as<uint32_t>() + nt);
+        hipLaunchKernelGGL(dr::k_scan_add, dim3(div_up(ncells, 256)), dim3(256), 0, st, ctx->cell_off.as<uint32_t>(), ctx->tiles.as<uint32_t>(), ncells);
+        hipLaunchKernelGGL(dr::k_size_place, dim3(szblocks), dim3(dr::SZ_BLOCK), 0, st, ctx->counts.as<uint32_t>(), nbuckets, szblocks,
+                           ctx->cell_off.as<uint32_t>(), ctx->perm.as<uint32_t>());
+    });
+}
+
 int te_msm_pippenger(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t out_xy[64]) {
     TRY(use_ctx(ctx));
     const drh::TeCurveHost* cu = drh::te_curve(cv);
@@ -466,12 +489,6 @@ int te_msm_pippenger(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* 
     TRY(ctx->counts.reserve(nbuckets * 4));
     TRY(ctx->offsets.reserve((nbuckets + 1) * 4));
     TRY(ctx->sorted.reserve(sets * per_set * 4));
-    const unsigned szblocks = div_up(nbuckets, dr::SZ_TILE);
-    const size_t ncells = (size_t)dr::SZ_CLASSES * szblocks;
-    TRY(ctx->tiles.reserve((size_t)(div_up(ncells, dr::SCAN_TILE) + 1) * 4));
-    TRY(ctx->perm.reserve(nbuckets * 4));
-    TRY(ctx->cells.reserve(ncells * 4));
-    TRY(ctx->cell_off.reserve(ncells * 4));
     TRY(ctx->buckets.reserve(nbuckets * 128));
     TRY(ctx->partial.reserve(sets * T * 128));
     TRY(ctx->winsum.reserve(sets * 128));
@@ -487,17 +504,7 @@ int te_msm_pippenger(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* 
         hipLaunchKernelGGL(dr::k_g1_sort_sets, dim3((unsigned)sets), dim3(dr::SORT_BLOCK), 0, st, ctx->scalars.as<uint32_t>(), wt, sp,
                            ctx->counts.as<uint32_t>(), ctx->offsets.as<uint32_t>(), ctx->sorted.as<uint32_t>());
     }));
-    TRY(launch(ctx, "k_size_sort", [&] {
-        hipLaunchKernelGGL(dr::k_size_hist, dim3(szblocks), dim3(dr::SZ_BLOCK), 0, st, ctx->counts.as<uint32_t>(), nbuckets, szblocks,
-                           ctx->cells.as<uint32_t>());
-        const unsigned nt = div_up(ncells, dr::SCAN_TILE);
-        hipLaunchKernelGGL(dr::k_scan_tiles, dim3(nt), dim3(dr::SCAN_BLOCK), 0, st, ctx->cells.as<uint32_t>(), ctx->cell_off.as<uint32_t>(),
-                           ctx->tiles.as<uint32_t>(), ncells);
-        hipLaunchKernelGGL(dr::k_scan_tile_sums, dim3(1), dim3(dr::SCAN_BLOCK), 0, st, ctx->tiles.as<uint32_t>(), nt, ctx->tiles.as<uint32_t>() + nt);
-        hipLaunchKernelGGL(dr::k_scan_add, dim3(div_up(ncells, 256)), dim3(256), 0, st, ctx->cell_off.as<uint32_t>(), ctx->tiles.as<uint32_t>(), ncells);
-        hipLaunchKernelGGL(dr::k_size_place, dim3(szblocks), dim3(dr::SZ_BLOCK), 0, st, ctx->counts.as<uint32_t>(), nbuckets, szblocks,
-                           ctx->cell_off.as<uint32_t>(), ctx->perm.as<uint32_t>());
-    }));
+    TRY(bucket_size_order(ctx, nbuckets));
     TRY(launch(ctx, "k_te_msm_accumulate", [&] {
         LAUNCH_CV(cv, dr::k_te_msm_accumulate, dim3(div_up(nbuckets, 256)), dim3(256), 0, st, ctx->io_b.as<uint32_t>(), ctx->sorted.as<uint32_t>(),
                   ctx->offsets.as<uint32_t>(), ctx->counts.as<uint32_t>(), ctx->perm.as<uint32_t>(), ctx->buckets.as<uint32_t>(), nbuckets);
@@ -529,6 +536,17 @@ int te_msm_pippenger(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* 
     (acc.x * zi).store_le(out_xy);
     (acc.y * zi).store_le(out_xy + 32);
     return DR_OK;
+}
+
+// One MSM on a wide suite: each suite's unit has the implementation (capi_wide_msm.hpp over its kernels), this selects by id
+int dr_wide_msm(dr_ctx* ctx, int curve, const uint8_t* pts, const uint8_t* scalars, size_t n, uint8_t* out) {
+    switch (curve) {
+        case DR_CURVE_P384_RO: case DR_CURVE_P384_NU: return p384_wide_msm(ctx, pts, scalars, n, out);
+        case DR_CURVE_P521_RO: case DR_CURVE_P521_NU: return p521_wide_msm(ctx, pts, scalars, n, out);
+        case DR_CURVE_ED448_RO: case DR_CURVE_ED448_NU: return ed448_wide_msm(ctx, pts, scalars, n, out);
+        case DR_CURVE_CURVE448_RO: case DR_CURVE_CURVE448_NU: return curve448_wide_msm(ctx, pts, scalars, n, out);
+        default: return fail(DR_ERR_INVALID, "dr_wide_msm serves the P-384, P-521, Ed448 and Curve448 suites");
+    }
 }
 
 void g1_launch_decompress(hipStream_t st, const uint8_t* d_enc, uint32_t* d_bases, uint32_t* d_ok, size_t n) {

@@ -6,6 +6,7 @@
 // L = 72) on the worker threads and checks that inputs are canonical.  Scalars may be secret: they pass through io_a / io_b / io_c
 // only, which ctx_wipe_scratch covers.
 #include "capi_suite.hpp"
+#include "capi_wide_msm.hpp"
 #include "kernels_p384.hip.h"
 
 using namespace dri;
@@ -23,6 +24,15 @@ struct P384Suite : SuiteDefaults {
     static constexpr auto field_selftest = dr::k_p384_field_selftest;
     static constexpr int block = dr::P384_BLOCK, selftest_records = dr::P384_SELFTEST_RECORDS;
     static constexpr const char *k_scalar_mul = "k_p384_scalar_mul", *k_msm_groups = "k_p384_msm_groups", *k_decode = "k_p384_decode_points";
+    // the bucket method of dr_wide_msm (capi_wide_msm.hpp): the law on the host, the bits the tiling covers, the stages' kernels
+    using Law = dr::P384Law;
+    static constexpr int wide_bits = 385;
+    static constexpr auto wide_prepare = dr::k_p384_msm_prepare;
+    static constexpr auto wide_sort = dr::k_p384_msm_sort;
+    static constexpr auto wide_accumulate = dr::k_p384_msm_accumulate;
+    static constexpr auto wide_accumulate_heavy = dr::k_p384_msm_accumulate_heavy;
+    static constexpr auto wide_reduce = dr::k_p384_msm_reduce;
+    static constexpr auto wide_fold = dr::k_p384_msm_fold;
     // SEC1 compressed: 49 bytes, three zero bytes behind each on the device; the kernel judges the range of x, which is big-endian
     static constexpr size_t enc_bytes = 49, rec_bytes = 52;
     static constexpr bool decode_gives_points = true, decode_checks_canonical = false;
@@ -67,6 +77,10 @@ int dr_p384_scalar_mul_batch(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* 
 int dr_p384_msm_groups(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy) {
     TRY(use_ctx(ctx));
     return msm_groups<P384Suite>(ctx, pts_xy, scalars, groups, m, out_xy);
+}
+// dr_wide_msm for DR_CURVE_P384_RO / _NU (the dispatcher is capi_msm.hip's)
+int p384_wide_msm(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy) {
+    return wide_msm<P384Suite>(ctx, pts_xy, scalars, n, out_xy);
 }
 // check = 0 and check = 1 are one kernel (include/dotring_hip.h says why); the parameter is the suites' common signature
 int dr_p384_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {

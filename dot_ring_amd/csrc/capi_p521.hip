@@ -6,6 +6,7 @@
 // hash_to_field (expand_message_xmd over SHA-512, L = 98) on the worker threads and checks that inputs are canonical.  Scalars may be
 // secret: they pass through io_a / io_b / io_c only, which ctx_wipe_scratch covers.
 #include "capi_suite.hpp"
+#include "capi_wide_msm.hpp"
 #include "kernels_p521.hip.h"
 
 using namespace dri;
@@ -23,6 +24,15 @@ struct P521Suite : SuiteDefaults {
     static constexpr auto field_selftest = dr::k_p521_field_selftest;
     static constexpr int block = dr::P521_BLOCK, selftest_records = dr::P521_SELFTEST_RECORDS;
     static constexpr const char *k_scalar_mul = "k_p521_scalar_mul", *k_msm_groups = "k_p521_msm_groups", *k_decode = "k_p521_decode_points";
+    // the bucket method of dr_wide_msm (capi_wide_msm.hpp): the law on the host, the bits the tiling covers, the stages' kernels
+    using Law = dr::P521Law;
+    static constexpr int wide_bits = 522;
+    static constexpr auto wide_prepare = dr::k_p521_msm_prepare;
+    static constexpr auto wide_sort = dr::k_p521_msm_sort;
+    static constexpr auto wide_accumulate = dr::k_p521_msm_accumulate;
+    static constexpr auto wide_accumulate_heavy = dr::k_p521_msm_accumulate_heavy;
+    static constexpr auto wide_reduce = dr::k_p521_msm_reduce;
+    static constexpr auto wide_fold = dr::k_p521_msm_fold;
     // SEC1 compressed: 67 bytes, a zero byte behind each on the device; the kernel judges the range of x, which is big-endian
     static constexpr size_t enc_bytes = 67, rec_bytes = 68;
     static constexpr bool decode_gives_points = true, decode_checks_canonical = false;
@@ -79,6 +89,10 @@ int dr_p521_scalar_mul_batch(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* 
 int dr_p521_msm_groups(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy) {
     TRY(use_ctx(ctx));
     return msm_groups<P521Suite>(ctx, pts_xy, scalars, groups, m, out_xy);
+}
+// dr_wide_msm for DR_CURVE_P521_RO / _NU (the dispatcher is capi_msm.hip's)
+int p521_wide_msm(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy) {
+    return wide_msm<P521Suite>(ctx, pts_xy, scalars, n, out_xy);
 }
 // check = 0 and check = 1 are one kernel (include/dotring_hip.h says why); the parameter is the suites' common signature
 int dr_p521_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {

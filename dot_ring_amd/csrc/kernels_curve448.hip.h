@@ -94,6 +94,35 @@ __global__ __launch_bounds__(E448_BLOCK) void k_c448_msm_groups(const uint32_t* 
     if (g < groups && j == 0) id_out[g] = c448_store(out + (size_t)g * E448_PT_WORDS, acc) ? 1u : 0u;
 }
 
+
+// ---------------------------------------------------------------- the bucket method (dr_wide_msm): wave_msm.hip.h over Curve448Curve
+// One MSM of n >= WIDE_PIP_FROM terms; the stages, their operands and the plan are that header's.  W448 scalar words, as they are.
+// (the point is loaded as k_c448_msm_groups loads it: u || v with the flag word of the identity beside it)
+__global__ __launch_bounds__(WMSM_BLOCK) void k_c448_msm_prepare(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ id_in, uint32_t n,
+                                                                uint32_t* __restrict__ table) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    wave_msm_put<Curve448Curve>(table, i, c448_load_term(pts + (size_t)i * E448_PT_WORDS, id_in[i]));
+}
+// (the sort looks at scalars only, and those are Ed448's 14 words: k_ed448_msm_sort)
+__global__ __launch_bounds__(WMSM_BLOCK) void k_c448_msm_accumulate(const uint32_t* __restrict__ table, const uint32_t* __restrict__ sorted,
+                                                                    const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts,
+                                                                    const uint32_t* __restrict__ perm, uint32_t* __restrict__ buckets, size_t nbuckets) {
+    wave_msm_accumulate<Curve448Curve>(table, sorted, offsets, counts, perm, buckets, nbuckets);
+}
+__global__ __launch_bounds__(64) void k_c448_msm_accumulate_heavy(const uint32_t* __restrict__ table, const uint32_t* __restrict__ sorted,
+                                                                  const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts,
+                                                                  uint32_t* __restrict__ buckets, size_t nbuckets) {
+    wave_msm_accumulate_heavy<Curve448Curve>(table, sorted, offsets, counts, buckets, nbuckets);
+}
+__global__ __launch_bounds__(WMSM_BLOCK) void k_c448_msm_reduce(const uint32_t* __restrict__ buckets, size_t sets, uint32_t H, uint32_t L,
+                                                                uint32_t* __restrict__ partial) {
+    wave_msm_reduce<Curve448Curve>(buckets, sets, H, L, partial);
+}
+__global__ __launch_bounds__(WMSM_BLOCK) void k_c448_msm_fold(const uint32_t* __restrict__ partial, size_t sets, uint32_t T, uint32_t* __restrict__ setsum) {
+    wave_msm_fold<Curve448Curve>(partial, sets, T, setsum);
+}
+
 // ---------------------------------------------------------------- hashing to the curve (RFC 9380, curve448_XOF:SHAKE256_ELL2_RO_ / _NU_)
 // out[i] = [4 if clear] (the sum of the images of item i's `per_item` field elements) (2: the uniform (RO) encoding, 1: the nonuniform
 // one).  us: n x per_item x 14 words (canonical, checked by the host), out: n x 28 words u || v.  ok[i] = 0 and 112 zero bytes exactly

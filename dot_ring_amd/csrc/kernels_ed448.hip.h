@@ -14,8 +14,9 @@
 //
 // The schedule, the memory forms and the two kernel bodies are wave_curve.hip.h's over Ed448Curve: 14 scalar words, 113 windows.
 #pragma once
-#include "fe448.hip.h"
+#include "e448_law.hip.h"
 #include "wave_curve.hip.h"
+#include "wave_msm.hip.h"
 
 namespace dr {
 
@@ -23,48 +24,12 @@ constexpr int E448_BLOCK = 64;        // one wave per workgroup; 96 KiB of LDS t
 constexpr int E448_WINDOWS = 113;     // 112 nibbles of a 448-bit scalar and the carry out of the last digit
 constexpr int E448_PT_WORDS = 2 * W448;
 
-struct E448Point {
-    F448 x, y, z;
-};
-
 // the group order n = 2^446 - 0x8335dc163bb124b65129c96fde933d8d723a70aadc873d6d54a7bb0d, 14 words: the public scalar of the subgroup check.
 __device__ const uint32_t E448_ORDER[W448] = {0xab5844f3u, 0x2378c292u, 0x8dc58f55u, 0x216cc272u, 0xaed63690u, 0xc44edb49u, 0x7cca23e9u,
                                               0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0x3fffffffu};
 
-DR_DEV E448Point e448_identity() { return {F448::zero(), F448::small(1), F448::small(1)}; }
-DR_DEV E448Point e448_from_affine(const F448& x, const F448& y) { return {x, y, F448::small(1)}; }
-DR_DEV bool e448_is_identity(const E448Point& p) { return is_zero(p.x) && equal(p.y, p.z); }
-
-// dbl-2007-bl, c = 1: coordinates n in, n out
-DR_DEV E448Point e448_dbl(const E448Point& p) {
-    const F448 B = sqr(carry(add(p.x, p.y)));                // (X + Y)^2: the sum carried to n
-    const F448 C = sqr(p.x), D = sqr(p.y);                   // n
-    const F448 E = carry(add(C, D));                         // n
-    const F448 H = sqr(p.z);                                 // n
-    const F448 J = sub(E, dbl(H));                           // E - 2 H: limbs in (-2 n, n): 2 n
-    E448Point r;
-    r.x = mul(carry(sub(B, add(C, D))), J);                  // (B - C - D) J: n x 2 n
-    r.y = mul(E, sub(C, D));                                 // n x 1 n
-    r.z = mul(E, J);                                         // n x 2 n
-    return r;
-}
-
-// add-2007-bl, c = 1, a = 1: unified and, d being a non-square, complete.  Coordinates n (x possibly negated: 1 n) in, n out
-DR_DEV E448Point e448_add(const E448Point& p, const E448Point& q) {
-    const F448 A = mul(p.z, q.z);                                            // n
-    const F448 B = sqr(A);                                                   // n
-    const F448 C = mul(p.x, q.x), D = mul(p.y, q.y);                         // n
-    const F448 E = mul_small(mul(C, D), Fe448Consts::EDWARDS_D_NEG);         // -d C D = 39081 C D: n
-    const F448 F = add(B, E), G = sub(B, E);                                 // B - d C D: 2 n; B + d C D: 1 n
-    // (X1 + Y1) (X2 + Y2) - C - D: the sums carried to n; limbs in (-2 n, n): 2 n
-    const F448 t = sub(mul(carry(add(p.x, p.y)), carry(add(q.x, q.y))), add(C, D));
-    E448Point r;
-    r.x = mul(mul(A, F), t);                                                 // (n x 2 n) x 2 n
-    r.y = mul(mul(A, G), sub(D, C));                                         // (n x 1 n) x 1 n
-    r.z = mul(F, G);                                                         // 2 n x 1 n
-    return r;
-}
-DR_DEV E448Point e448_cneg(const E448Point& p, bool negate) { return {cneg(p.x, negate), p.y, p.z}; }
+// (the law itself — E448Point, e448_identity, e448_from_affine, e448_is_identity, e448_dbl, e448_add, e448_cneg — is e448_law.hip.h's: the
+// host runs it too, for the window combination of dr_wide_msm)
 
 // wave_curve.hip.h's description of Ed448: canonical words at the ABI (14 per coordinate; the identity is (0, 1) as itself), the limb
 // images in the LDS table (no packing), and 113 windows over the scalar AS IT IS: 112 nibbles of any k < 2^448 and the carry out of the
@@ -96,6 +61,35 @@ __global__ __launch_bounds__(E448_BLOCK) void k_ed448_scalar_mul(const uint32_t*
 __global__ __launch_bounds__(E448_BLOCK) void k_ed448_msm_groups(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks,
                                                                  uint32_t* __restrict__ out, uint32_t groups, uint32_t m, uint32_t mpad) {
     wave_msm_groups<Ed448Curve>(pts, ks, out, groups, m, mpad);
+}
+
+
+// ---------------------------------------------------------------- the bucket method (dr_wide_msm): wave_msm.hip.h over Ed448Curve
+// One MSM of n >= WIDE_PIP_FROM terms; the stages, their operands and the plan are that header's.  W448 scalar words, as they are.
+__global__ __launch_bounds__(WMSM_BLOCK) void k_ed448_msm_prepare(const uint32_t* __restrict__ pts, uint32_t n, uint32_t* __restrict__ table) {
+    wave_msm_prepare<Ed448Curve>(pts, n, table);
+}
+__global__ __launch_bounds__(WMSM_SORT_BLOCK) void k_ed448_msm_sort(const uint32_t* __restrict__ scalars, WideTiling wt, uint32_t n, uint32_t H,
+                                                                   uint32_t groups, uint32_t capacity, uint32_t* __restrict__ counts,
+                                                                   uint32_t* __restrict__ offsets, uint32_t* __restrict__ sorted) {
+    wave_msm_sort<W448>(scalars, wt, n, H, groups, capacity, counts, offsets, sorted);
+}
+__global__ __launch_bounds__(WMSM_BLOCK) void k_ed448_msm_accumulate(const uint32_t* __restrict__ table, const uint32_t* __restrict__ sorted,
+                                                                    const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts,
+                                                                    const uint32_t* __restrict__ perm, uint32_t* __restrict__ buckets, size_t nbuckets) {
+    wave_msm_accumulate<Ed448Curve>(table, sorted, offsets, counts, perm, buckets, nbuckets);
+}
+__global__ __launch_bounds__(64) void k_ed448_msm_accumulate_heavy(const uint32_t* __restrict__ table, const uint32_t* __restrict__ sorted,
+                                                                  const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts,
+                                                                  uint32_t* __restrict__ buckets, size_t nbuckets) {
+    wave_msm_accumulate_heavy<Ed448Curve>(table, sorted, offsets, counts, buckets, nbuckets);
+}
+__global__ __launch_bounds__(WMSM_BLOCK) void k_ed448_msm_reduce(const uint32_t* __restrict__ buckets, size_t sets, uint32_t H, uint32_t L,
+                                                                uint32_t* __restrict__ partial) {
+    wave_msm_reduce<Ed448Curve>(buckets, sets, H, L, partial);
+}
+__global__ __launch_bounds__(WMSM_BLOCK) void k_ed448_msm_fold(const uint32_t* __restrict__ partial, size_t sets, uint32_t T, uint32_t* __restrict__ setsum) {
+    wave_msm_fold<Ed448Curve>(partial, sets, T, setsum);
 }
 
 // ---------------------------------------------------------------- hashing to the curve (RFC 9380, edwards448_XOF:SHAKE256_ELL2_RO_ / _NU_)

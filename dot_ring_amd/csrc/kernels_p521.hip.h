@@ -13,6 +13,7 @@
 #include "p521_law.hip.h"
 #include "sswu.hip.h"
 #include "wave_curve.hip.h"
+#include "wave_msm.hip.h"
 
 namespace dr {
 
@@ -48,6 +49,35 @@ __global__ __launch_bounds__(P521_BLOCK) void k_p521_scalar_mul(const uint32_t* 
 __global__ __launch_bounds__(P521_BLOCK) void k_p521_msm_groups(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ ks,
                                                                 uint32_t* __restrict__ out, uint32_t groups, uint32_t m, uint32_t mpad) {
     wave_msm_groups<P521Curve>(pts, ks, out, groups, m, mpad);
+}
+
+
+// ---------------------------------------------------------------- the bucket method (dr_wide_msm): wave_msm.hip.h over P521Curve
+// One MSM of n >= WIDE_PIP_FROM terms; the stages, their operands and the plan are that header's.  W521 scalar words, as they are.
+__global__ __launch_bounds__(WMSM_BLOCK) void k_p521_msm_prepare(const uint32_t* __restrict__ pts, uint32_t n, uint32_t* __restrict__ table) {
+    wave_msm_prepare<P521Curve>(pts, n, table);
+}
+__global__ __launch_bounds__(WMSM_SORT_BLOCK) void k_p521_msm_sort(const uint32_t* __restrict__ scalars, WideTiling wt, uint32_t n, uint32_t H,
+                                                                   uint32_t groups, uint32_t capacity, uint32_t* __restrict__ counts,
+                                                                   uint32_t* __restrict__ offsets, uint32_t* __restrict__ sorted) {
+    wave_msm_sort<W521>(scalars, wt, n, H, groups, capacity, counts, offsets, sorted);
+}
+__global__ __launch_bounds__(WMSM_BLOCK) void k_p521_msm_accumulate(const uint32_t* __restrict__ table, const uint32_t* __restrict__ sorted,
+                                                                    const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts,
+                                                                    const uint32_t* __restrict__ perm, uint32_t* __restrict__ buckets, size_t nbuckets) {
+    wave_msm_accumulate<P521Curve>(table, sorted, offsets, counts, perm, buckets, nbuckets);
+}
+__global__ __launch_bounds__(64) void k_p521_msm_accumulate_heavy(const uint32_t* __restrict__ table, const uint32_t* __restrict__ sorted,
+                                                                  const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts,
+                                                                  uint32_t* __restrict__ buckets, size_t nbuckets) {
+    wave_msm_accumulate_heavy<P521Curve>(table, sorted, offsets, counts, buckets, nbuckets);
+}
+__global__ __launch_bounds__(WMSM_BLOCK) void k_p521_msm_reduce(const uint32_t* __restrict__ buckets, size_t sets, uint32_t H, uint32_t L,
+                                                                uint32_t* __restrict__ partial) {
+    wave_msm_reduce<P521Curve>(buckets, sets, H, L, partial);
+}
+__global__ __launch_bounds__(WMSM_BLOCK) void k_p521_msm_fold(const uint32_t* __restrict__ partial, size_t sets, uint32_t T, uint32_t* __restrict__ setsum) {
+    wave_msm_fold<P521Curve>(partial, sets, T, setsum);
 }
 
 // ---------------------------------------------------------------- hashing to the curve (RFC 9380, P521_XMD:SHA-512_SSWU_RO_ / _NU_)

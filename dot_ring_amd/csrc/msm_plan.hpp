@@ -1,6 +1,7 @@
 // The plan of a G1 Pippenger call (msm_device, capi_msm.hip) and the kernel-geometry constants it depends on (kernels_g1.hip.h uses
-// them from here), and the plan of a twisted Edwards Pippenger call (te_msm_pippenger: plan_te_msm).  Plain host C++ (no HIP): g++ builds
-// it for tests/native/msm_plan_check.cpp and tests/native/te_msm_plan_check.cpp.
+// them from here), and the plan of a twisted Edwards Pippenger call (te_msm_pippenger: plan_te_msm) and of the wide suites' bucket
+// method (dr_wide_msm: plan_wide_msm).  Plain host C++ (no HIP): g++ builds it for tests/native/msm_plan_check.cpp,
+// tests/native/te_msm_plan_check.cpp and tests/native/wide_msm_plan_check.cpp.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -8,6 +9,7 @@
 #include <cstdint>
 
 #include "dev_types.hpp"
+#include "wide_recode.hip.h"
 
 namespace dr {
 
@@ -103,6 +105,31 @@ inline TeMsmPlan plan_te_msm(size_t n, int scalar_bits) {
     p.wt = make_window_table(p.c, scalar_bits + 1);
     p.H = 1u << (p.wt.cmax - 1), p.L = TE_REDUCE_CHUNK, p.T = p.H / p.L;
     // index groups until a bucket holds ~8 points or 64 groups
+    while (p.groups < 64 && n / ((size_t)p.groups * 2 * p.H) >= 8) p.groups *= 2;
+    p.sets = (size_t)p.wt.W * p.groups, p.nbuckets = p.sets * p.H;
+    p.per_set = (n + p.groups - 1) / p.groups;
+    return p;
+}
+
+// ---- the bucket method of the wide suites (dr_wide_msm; wave_msm.hip.h, capi_wide_msm.hpp): ONE variable-base MSM of n terms on
+// P-384, Ed448, Curve448 or P-521.  From WIDE_PIP_FROM terms on; below it the call launches msm_groups in chunks of up to 64.
+constexpr size_t WIDE_PIP_FROM = 256;
+constexpr uint32_t WIDE_MAX_H = 512;                       // wave_msm_sort: bins of a set in LDS (window widths up to 10)
+
+struct WideMsmPlan {
+    int c = 0;                           // window width asked for; wide_cmax(wt) is the widest one of the tiling
+    WideTiling wt{};
+    uint32_t H = 0, L = 0, T = 0, groups = 1;   // buckets per set, per reduction chunk, chunks per set, index groups
+    size_t sets = 0, nbuckets = 0, per_set = 0; // (window, group) bucket sets, all buckets, entries reserved per set in `sorted`
+};
+
+// bits: what the tiling covers, one more than the scalars can have (wide_recode.hip.h): 385 on P-384, 449 on Ed448 and Curve448, 522 on
+// P-521.  Width by size, index groups and chunks are plan_te_msm's rules: the walk and the reduction have the same shape
+inline WideMsmPlan plan_wide_msm(size_t n, int bits) {
+    WideMsmPlan p;
+    p.c = n < 4096 ? 7 : n < 16384 ? 8 : n < 65536 ? 9 : 10;
+    p.wt = make_wide_tiling(p.c, bits);
+    p.H = 1u << (wide_cmax(p.wt) - 1), p.L = TE_REDUCE_CHUNK, p.T = p.H / p.L;
     while (p.groups < 64 && n / ((size_t)p.groups * 2 * p.H) >= 8) p.groups *= 2;
     p.sets = (size_t)p.wt.W * p.groups, p.nbuckets = p.sets * p.H;
     p.per_set = (n + p.groups - 1) / p.groups;

@@ -69,6 +69,28 @@ DR_F384_FN P384Point p384_add(const P384Point& p, const P384Point& q) {
     return r;
 }
 
+// The law as the host side of dr_wide_msm takes it (wide_combine.hpp): the operations of the window combination and the ABI's x || y
+// words <-> a point; zero words are the identity, which has Z = 0 and so stores them by 0^-1 = 0
+struct P384Law {
+    using Point = P384Point;
+    static constexpr int WORDS = W384, LIMBS = L384;
+    DR_F384_MEMBER static P384Point identity() { return p384_identity(); }
+    DR_F384_MEMBER static P384Point add(const P384Point& p, const P384Point& q) { return p384_add(p, q); }
+    DR_F384_MEMBER static P384Point dbl(const P384Point& p) { return p384_dbl(p); }
+    DR_F384_MEMBER static P384Point from_abi(const uint32_t (&w)[2 * W384]) {
+        uint32_t x[W384], y[W384], o = 0;
+        for (int j = 0; j < W384; j++) { x[j] = w[j]; y[j] = w[W384 + j]; o |= x[j] | y[j]; }
+        return o == 0 ? p384_identity() : p384_from_affine(unpack(x), unpack(y));
+    }
+    DR_F384_MEMBER static void to_abi(const P384Point& p, uint32_t (&w)[2 * W384]) {
+        const F384 zi = inv(p.z);
+        uint32_t x[W384], y[W384];
+        pack(mul(p.x, zi), x);
+        pack(mul(p.y, zi), y);
+        for (int j = 0; j < W384; j++) { w[j] = x[j]; w[W384 + j] = y[j]; }
+    }
+};
+
 // sswu.hip.h's description of P-384: the simplified SWU map straight onto the curve (A = -3, B = b, Z = -12, no isogeny).  A and Z are
 // the small elements -3 R and -12 R (five signed limbs each, 1 n), -Z x is the small multiple 12 x, and only B x and the product with
 // sqrt(-Z) = sqrt(12) meet a full-width constant.  Every value sswu_map makes is normal where it is made (norm = carry), so each of its

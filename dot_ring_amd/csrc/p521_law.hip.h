@@ -78,6 +78,28 @@ DR_F521_FN P521Point p521_add(const P521Point& p, const P521Point& q) {
     return r;
 }
 
+// The law as the host side of dr_wide_msm takes it (wide_combine.hpp): the operations of the window combination and the ABI's x || y
+// words <-> a point; zero words are the identity, which has Z = 0 and so stores them by 0^-1 = 0
+struct P521Law {
+    using Point = P521Point;
+    static constexpr int WORDS = W521, LIMBS = L521;
+    DR_F521_MEMBER static P521Point identity() { return p521_identity(); }
+    DR_F521_MEMBER static P521Point add(const P521Point& p, const P521Point& q) { return p521_add(p, q); }
+    DR_F521_MEMBER static P521Point dbl(const P521Point& p) { return p521_dbl(p); }
+    DR_F521_MEMBER static P521Point from_abi(const uint32_t (&w)[2 * W521]) {
+        uint32_t x[W521], y[W521], o = 0;
+        for (int j = 0; j < W521; j++) { x[j] = w[j]; y[j] = w[W521 + j]; o |= x[j] | y[j]; }
+        return o == 0 ? p521_identity() : p521_from_affine(unpack(x), unpack(y));
+    }
+    DR_F521_MEMBER static void to_abi(const P521Point& p, uint32_t (&w)[2 * W521]) {
+        const F521 zi = inv(p.z);
+        uint32_t x[W521], y[W521];
+        pack(mul(p.x, zi), x);
+        pack(mul(p.y, zi), y);
+        for (int j = 0; j < W521; j++) { w[j] = x[j]; w[W521 + j] = y[j]; }
+    }
+};
+
 // sswu.hip.h's description of P-521: the simplified SWU map straight onto the curve (A = -3, B = b, Z = -4, no isogeny).  The field is
 // in standard form, so A, Z and sqrt(-Z) = 2 are one-limb elements, -Z x is a small multiple and only B x is a full product.  Every
 // value sswu_map makes is normal where it is made (norm = carry), so each of its products is n x n or n x 2 n.

@@ -1219,6 +1219,9 @@ class Ed448Point(_WideRfc9380, BandersnatchPoint):
     def msm(cls, points, scalars):
         if len(points) != len(scalars):
             raise ValueError("Points and scalars must have same length")
+        if len(points) >= _native.WIDE_PIP_FROM:      # dr_wide_msm: the bucket method
+            return cls._unpack(runtime.context().wide_msm("ed448", cls._pack(points), cls._scalars(scalars)))[0]
+        # below it the dispatch that tests/golden/point_surface_cpu.json records for this class stays as it was
         acc = cls.identity()
         for lo in range(0, len(points), 64):          # groups of up to 64 terms on the device, their sums added on the host
             part = points[lo : lo + 64]
@@ -1252,7 +1255,7 @@ class Ed448Point(_WideRfc9380, BandersnatchPoint):
 
     @classmethod
     def _msm_groups(cls, points, scalars, m: int):
-        if m > 64:                               # the kernel folds up to 64 terms in a wave: longer groups fold on the host (msm)
+        if m > 64:                               # the kernel folds up to 64 terms in a wave: longer groups are one msm each (dr_wide_msm)
             return [cls.msm(points[i : i + m], scalars[i : i + m]) for i in range(0, len(points), m)]
         return cls._unpack(runtime.context().ed448_msm_groups(cls._pack(points), cls._scalars(scalars), m))
 
@@ -1410,11 +1413,12 @@ class Curve448Point(_WideRfc9380, _MontgomeryPoint):
     def msm(cls, points, scalars):
         if len(points) != len(scalars):
             raise ValueError("Points and scalars must have same length")
-        acc = cls.identity()
-        for lo in range(0, len(points), 64):          # groups of up to 64 terms on the device, their sums added on the host
-            part = points[lo : lo + 64]
-            acc = acc + msm_groups(part, scalars[lo : lo + 64], len(part))[0]
-        return acc
+        if not points:
+            return cls.identity()
+        if len(points) <= 64:                         # one launch: a wave folds up to 64 terms
+            return msm_groups(points, scalars, len(points))[0]
+        # more: dr_wide_msm — chunks of 64 folded natively below 256 terms, the bucket method from there on
+        return cls._unpack(runtime.context().wide_msm("curve448", cls._pack(points), cls._scalars(scalars)))[0]
 
     # -- hash to curve (RFC 9380 curve448_XOF:SHAKE256_ELL2_RO_ / _NU_): expand_message_xof natively on the host, the map on the GPU
     @classmethod
@@ -1429,7 +1433,7 @@ class Curve448Point(_WideRfc9380, _MontgomeryPoint):
 
     @classmethod
     def _msm_groups(cls, points, scalars, m: int):
-        if m > 64:                               # the kernel folds up to 64 terms in a wave: longer groups fold on the host (msm)
+        if m > 64:                               # the kernel folds up to 64 terms in a wave: longer groups are one msm each (dr_wide_msm)
             return [cls.msm(points[i : i + m], scalars[i : i + m]) for i in range(0, len(points), m)]
         return cls._unpack(runtime.context().curve448_msm_groups(cls._pack(points), cls._scalars(scalars), m))
 
@@ -1478,11 +1482,12 @@ class _WidePrimeSwPoint(_WideRfc9380, _Sec1Codec, _ShortWeierstrassPoint):
     def msm(cls, points, scalars):
         if len(points) != len(scalars):
             raise ValueError("Points and scalars must have same length")
-        acc = cls.identity()
-        for lo in range(0, len(points), 64):          # groups of up to 64 terms on the device, their sums added on the host
-            part = points[lo : lo + 64]
-            acc = acc + msm_groups(part, scalars[lo : lo + 64], len(part))[0]
-        return acc
+        if not points:
+            return cls.identity()
+        if len(points) <= 64:                         # one launch: a wave folds up to 64 terms
+            return msm_groups(points, scalars, len(points))[0]
+        # more: dr_wide_msm — chunks of 64 folded natively below 256 terms, the bucket method from there on
+        return cls._unpack(runtime.context().wide_msm(cls._SUITE, cls._pack(points), cls._scalars(scalars)))[0]
 
     def clear_cofactor(self):
         return self                                   # the cofactor is 1
@@ -1509,7 +1514,7 @@ class _WidePrimeSwPoint(_WideRfc9380, _Sec1Codec, _ShortWeierstrassPoint):
 
     @classmethod
     def _msm_groups(cls, points, scalars, m: int):
-        if m > 64:                               # the kernel folds up to 64 terms in a wave: longer groups fold on the host (msm)
+        if m > 64:                               # the kernel folds up to 64 terms in a wave: longer groups are one msm each (dr_wide_msm)
             return [cls.msm(points[i : i + m], scalars[i : i + m]) for i in range(0, len(points), m)]
         return cls._unpack(runtime.context()._wide_msm_groups(cls._SUITE, cls._pack(points), cls._scalars(scalars), m))
 

@@ -516,6 +516,21 @@ DR_API int dr_p384_decode_points(dr_ctx *ctx, int check, const uint8_t *enc /* n
 DR_API int dr_p384_field_selftest(dr_ctx *ctx, const int32_t *a_limbs /* n*14 */, const int32_t *b_limbs /* n*14 */, size_t n,
                                   uint8_t *out /* n*13*48 */, uint8_t *flags /* n */);
 
+/* ---- one MSM on a wide suite ---------------------------------------------------------------------
+ * out = sum_{i<n} k[i] P[i] on P-384, P-521, Ed448 or Curve448: `curve` is one of DR_CURVE_P384_RO / _NU, DR_CURVE_P521_RO / _NU,
+ * DR_CURVE_ED448_RO / _NU, DR_CURVE_CURVE448_RO / _NU (RO and NU are one group); every other id gives DR_ERR_INVALID.  Points, scalars and
+ * the result are in the forms of that suite's dr_<suite>_msm_groups: affine x || y (u || v) of 96, 136, 112 or 112 bytes, scalars of 48,
+ * 68, 56 or 56 bytes used AS THEY ARE (P-521: below 2^521; Ed448 and Curve448: also k >= n, on points outside the prime-order
+ * subgroup).  The identity is 96 / 136 zero bytes on P-384 / P-521, (0, 1) on Ed448 and 112 bytes of 0xff INSIDE the point on Curve448, in
+ * and out; n = 0 gives it.  The refusals are msm_groups': a coordinate at or above p, a P-521 scalar of 2^521 or more, a null buffer, n at
+ * or above the suite's batch limit.
+ * Below 256 terms (WIDE_PIP_FROM, csrc/msm_plan.hpp) the call launches dr_<suite>_msm_groups' kernel in chunks of up to 64 terms and adds the
+ * partial sums on the host with the suite's law.  From 256 terms on it takes the bucket method (csrc/wave_msm.hip.h): signed window
+ * digits of the scalars, one bucket set per (window, index group), bucket walks, running-sum reductions, and the window combination on
+ * the host.  The bucket method is NOT a fixed schedule — bucket choice and list lengths depend on the scalars, as in dr_te_msm from 256
+ * terms — so it is for public scalars (the batch verifiers'); secret scalars go through scalar_mul_batch and msm_groups. */
+DR_API int dr_wide_msm(dr_ctx *ctx, int curve, const uint8_t *pts, const uint8_t *scalars, size_t n, uint8_t *out);
+
 /* square root in the Bandersnatch base field; DR_ERR_NOTSQUARE if none exists. Host-side, no ctx. */
 DR_API int dr_fr_sqrt(const uint8_t in[32], uint8_t out[32]);
 
