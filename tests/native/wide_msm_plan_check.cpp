@@ -4,7 +4,8 @@
 //   wide_msm_plan_check                   plan invariants over a sweep of sizes from WIDE_PIP_FROM to 2^20 for 385, 449 and 522 tiled bits,
 //                                         and the pinned (c, W, H, groups) of the sizes the GPU tests use
 //   wide_msm_plan_check hist <file>       <file>: blocks "case <name> <bits> <scalar words> <n of the plan> <count>" + count scalars (hex,
-//                                         big-endian, the terms 0 .. count - 1 of an MSM of n).  Per case: the plan, the scalars whose
+//                                         big-endian, the terms 0 .. count - 1 of an MSM of n; "<hex>*<times>" stands for that many
+//                                         equal scalars in a row; <file> "-" is the standard input).  Per case: the plan, the scalars whose
 //                                         digits do not sum back to them, and the bucket histogram of every (window, index group) set
 //                                         walked as wave_msm_sort walks it: the longest list, every list of TE_HEAVY_BUCKET entries or
 //                                         more (window, group, bucket, length, negative entries), entries in bucket H - 1 per window.
@@ -93,6 +94,16 @@ static int plan_checks() {
     pin(300, 385, 7, 55, 64, 1);  pin(320, 449, 7, 65, 64, 1);   pin(320, 522, 7, 75, 64, 1);      // point_type.msm, batch_verify of 64 proofs
     pin(1023, 522, 7, 75, 64, 1); pin(1024, 522, 7, 75, 64, 2);  pin(4095, 385, 7, 55, 64, 4);     // the thresholds themselves
     pin(16384, 449, 9, 50, 256, 8); pin(65536, 522, 10, 53, 512, 16);
+    // the sizes of tests/test_gpu_wide_msm_plans.py: widths 9 and 10, 8 to 64 index groups, and no size a multiple of its group count
+    struct Upper { size_t n; int c, w385, w449, w522; uint32_t H, groups; };
+    for (const Upper& u : {Upper{1031, 7, 55, 65, 75, 64, 2}, Upper{4103, 8, 49, 57, 66, 128, 4}, Upper{16383, 8, 49, 57, 66, 128, 8},
+                           Upper{16387, 9, 43, 50, 58, 256, 8}, Upper{65535, 9, 43, 50, 58, 256, 16}, Upper{65539, 10, 39, 45, 53, 512, 16},
+                           Upper{131075, 10, 39, 45, 53, 512, 32}, Upper{262147, 10, 39, 45, 53, 512, 64}}) {
+        pin(u.n, 385, u.c, u.w385, u.H, u.groups); pin(u.n, 449, u.c, u.w449, u.H, u.groups); pin(u.n, 522, u.c, u.w522, u.H, u.groups);
+        CHECK(u.n % u.groups != 0, "n=%zu: the group bounds are to be ceilings that differ from the floors", u.n);
+    }
+    CHECK(dr::plan_wide_msm(16387, 522).wt.rem == 0 && dr::plan_wide_msm(65535, 522).wt.rem == 0, "522 = 58 x 9: every window of full width");
+    CHECK(dr::plan_wide_msm(65539, 522).H == dr::WIDE_MAX_H && dr::plan_wide_msm(262147, 385).groups == 64, "the largest set and the group cap");
     if (failures == 0) std::printf("wide msm plan ok: %zu sizes, heavy from %u\n", ns.size(), dr::TE_HEAVY_BUCKET + 1);
     return failures ? 1 : 0;
 }
@@ -129,7 +140,7 @@ static bool reconstructs(const std::vector<uint32_t>& k, int kw, const dr::WideT
 }
 
 static int histograms(const char* path) {
-    FILE* f = std::fopen(path, "r");
+    FILE* f = std::strcmp(path, "-") == 0 ? stdin : std::fopen(path, "r");
     if (!f) { std::fprintf(stderr, "cannot open %s\n", path); return 2; }
     char name[128];
     int bits, kw;
@@ -137,11 +148,19 @@ static int histograms(const char* path) {
     std::vector<char> line(4096);
     while (std::fscanf(f, " case %127s %d %d %zu %zu", name, &bits, &kw, &n, &count) == 5) {
         std::vector<std::vector<uint32_t>> ks(count);
-        for (size_t i = 0; i < count; i++) {
-            if (std::fscanf(f, " %4095s", line.data()) != 1 || !hex_words(line.data(), kw, ks[i])) {
+        for (size_t i = 0; i < count;) {
+            if (std::fscanf(f, " %4095s", line.data()) != 1) { std::fprintf(stderr, "%s: scalar %zu is missing\n", name, i); return 2; }
+            size_t times = 1;
+            if (char* star = std::strchr(line.data(), '*')) {
+                *star = 0;
+                times = std::strtoull(star + 1, nullptr, 10);
+            }
+            if (times == 0 || times > count - i || !hex_words(line.data(), kw, ks[i])) {
                 std::fprintf(stderr, "%s: bad scalar %zu\n", name, i);
                 return 2;
             }
+            for (size_t j = 1; j < times; j++) ks[i + j] = ks[i];
+            i += times;
         }
         if (count > n) { std::fprintf(stderr, "%s: more scalars than terms\n", name); return 2; }
         const dr::WideMsmPlan p = dr::plan_wide_msm(n, bits);

@@ -7,11 +7,14 @@ The program checks the plan's invariants over a sweep of sizes and pins (c, W, H
 wide_digit per (window, index group) over the scalars of every family of wide_msm_cases.py, as wave_msm_sort walks them, and prints the
 bucket histograms; the tests below assert on them what the families claim — so what test_gpu_wide_msm.py runs on the GPU is proved here
 to enter the wave walk, to sit on both sides of the hand-over between the two accumulate kernels, to reach the last bucket of a
-full-width window, and to have two index groups at 1030 terms.  Last, the program combines set sums with each of the four laws and the
+full-width window, and to have two index groups at 1030 terms.  The same for the upper half of the plan (wide_msm_cases.PLANS, run by
+test_gpu_wide_msm_plans.py): widths 9 and 10, 8 to 64 index groups, group bounds with a remainder, a tiling of full-width windows only;
+those cases go to the program through a pipe, one at a time.  Last, the program combines set sums with each of the four laws and the
 result is checked against the big-integer restatements."""
 import os
 import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
@@ -29,16 +32,35 @@ def exe(tmp_path_factory):
     return str(out)
 
 
-def _histograms(exe, path, rows):
-    """rows: (name, bits, scalar words, n of the plan, scalars) -> {name: dict}"""
-    with open(path, "w") as f:
-        for name, bits, words, n, ks in rows:
-            f.write(f"case {name} {bits} {words} {n} {len(ks)}\n")
-            f.write("\n".join("%x" % k for k in ks) + "\n")
-    proc = subprocess.run([exe, "hist", str(path)], capture_output=True, text=True)
-    assert proc.returncode == 0, proc.stderr
+def _histograms(exe, path, rows, piped=False):
+    """rows: (name, bits, scalar words, n of the plan, scalars) -> {name: dict}.  piped: rows may be an iterator and go through the
+    program's standard input, a case of one scalar as one line (the large cases would make a file of hundreds of megabytes), and path
+    takes what the program prints"""
+    if piped:
+        names = []
+        with open(path, "w") as printed:
+            proc = subprocess.Popen([exe, "hist", "-"], stdin=subprocess.PIPE, stdout=printed, stderr=printed, text=True)
+            for name, bits, words, n, ks in rows:
+                names.append(name)
+                proc.stdin.write(f"case {name} {bits} {words} {n} {len(ks)}\n")
+                proc.stdin.write(f"{ks[0]:x}*{len(ks)}\n" if len(set(ks)) == 1 else "\n".join(map("%x".__mod__, ks)) + "\n")
+            proc.stdin.close()
+            code = proc.wait()
+        with open(path) as printed:
+            stdout = printed.read()
+        assert code == 0, stdout[-2000:]
+    else:
+        rows = list(rows)
+        names = [row[0] for row in rows]
+        with open(path, "w") as f:
+            for name, bits, words, n, ks in rows:
+                f.write(f"case {name} {bits} {words} {n} {len(ks)}\n")
+                f.write("\n".join("%x" % k for k in ks) + "\n")
+        proc = subprocess.run([exe, "hist", str(path)], capture_output=True, text=True)
+        assert proc.returncode == 0, proc.stderr
+        stdout = proc.stdout
     out, cur = {}, None
-    for line in proc.stdout.splitlines():
+    for line in stdout.splitlines():
         word = line.split()
         if word[0] == "case":
             cur = {k: int(v) for k, v in (item.split("=") for item in word[2:])}
@@ -48,7 +70,7 @@ def _histograms(exe, path, rows):
             cur["top"] = [int(x) for x in word[1:]]
         elif word[0] == "list":
             cur["lists"].append(tuple(int(x) for x in word[1:]))                # (window, group, bucket, length, negative entries)
-    assert list(out) == [row[0] for row in rows]
+    assert list(out) == names
     return out
 
 
@@ -168,16 +190,100 @@ def test_cancel_and_edges_claims(hist, name, n):
         assert not small
 
 
+# ---------------------------------------------------------------- the upper half of the plan (test_gpu_wide_msm_plans.py)
+EQUAL_LENGTHS = {1031: [515, 516], 4103: [1025, 1026], 16383: [2047, 2048], 16387: [2048, 2049], 65535: [4095, 4096], 65539: [4096, 4097],
+                 131075: [4096, 4097], 262147: [4096, 4097]}
+
+
+@pytest.fixture(scope="module")
+def plan_hist(exe, tmp_path_factory):
+    """name -> the histograms of every case of cases.PLANS on that suite, made at the first call for all four suites, one program each at
+    the same time; the cases are built one at a time and dropped (all of a suite's together are 1.4 million scalars)"""
+    done = {}
+    printed = tmp_path_factory.mktemp("wide_msm_plans")
+
+    def one(name):
+        s = cases.SUITES[name]
+        built = (cases.build(name, family, n) for n in cases.PLANS for family in cases.plan_families(n))
+        rows = ((c.name, s.bits, s.words, c.n, c.scalars) for c in built)
+        return _histograms(exe, printed / f"{name}.txt", rows, piped=True)
+
+    def of(name):
+        if not done:
+            with ThreadPoolExecutor(len(cases.NAMES)) as pool:
+                done.update(zip(cases.NAMES, pool.map(one, cases.NAMES)))
+        return done[name]
+
+    return of
+
+
+@pytest.mark.parametrize("n", tuple(cases.PLANS))
+@pytest.mark.parametrize("name", cases.NAMES)
+def test_upper_plans_and_their_ladder_lists(plan_hist, name, n):
+    """the pinned plan, in which no group bound is a whole multiple; every family's digits sum back; the ladder scalars make no list of 64
+    (a condition on the inputs: their GPU runs then are the per-lane walk alone) and reach the last bucket of full-width windows"""
+    s = cases.SUITES[name]
+    t = cases.Tiling(n, s.bits)
+    c, widths, H, groups, _ = cases.PLANS[n]
+    W = widths[(385, 449, 522).index(s.bits)]
+    assert (t.c, t.W, t.H, t.groups, t.cmax) == (c, W, H, groups, c) and n % groups != 0 and groups <= 64
+    assert [-(-g * n // groups) for g in range(groups + 1)] != [g * n // groups for g in range(groups + 1)]
+    for family in cases.plan_families(n):
+        h = plan_hist(name)[f"{name}-{family}-{n}"]
+        assert (h["n"], h["c"], h["W"], h["H"], h["groups"], h["cmax"]) == (n, c, W, H, groups, c) and h["reconstruct_bad"] == 0
+        assert h["heavy"] == sum(1 for x in h["lists"] if x[3] > cases.HEAVY)
+        assert (h["rem"] == 0) == (len(set(t.widths)) == 1)
+    if (n, s.bits) in ((16387, 522), (65535, 522)):
+        assert h["rem"] == 0 and set(t.widths) == {9}                       # 522 = 58 x 9: no window of width 8
+    lad = plan_hist(name)[f"{name}-ladder-{n}"]
+    assert lad["heavy"] == 0 and lad["longest"] < cases.HEAVY
+    full = [w for w in range(t.W) if t.widths[w] == t.cmax]
+    assert full and sum(lad["top"][w] for w in full) >= 1 and sum(lad["top"][w] for w in range(t.W) if w not in full) == 0
+
+
+@pytest.mark.parametrize("n", tuple(cases.PLANS))
+@pytest.mark.parametrize("name", cases.NAMES)
+def test_upper_equal_has_one_long_list_per_window_and_group(plan_hist, name, n):
+    """one heavy list per non-zero digit and index group, of all the group's terms: two lengths, since n is no multiple of the groups"""
+    case, h = cases.build(name, "equal", n), plan_hist(name)[f"{name}-equal-{n}"]
+    t = cases.Tiling(n, cases.SUITES[name].bits)
+    ds = cases.digits(case.scalars[0], t)
+    nonzero = sum(1 for d in ds if d)
+    assert len(set(case.scalars)) == 1 and h["heavy"] == nonzero * t.groups == len(h["lists"]) and nonzero >= t.W - 8
+    assert sorted((x[0], x[1]) for x in h["lists"]) == [(w, g) for w in range(t.W) if ds[w] for g in range(t.groups)]
+    assert all(x[2] == abs(ds[x[0]]) - 1 and x[4] == (x[3] if ds[x[0]] < 0 else 0) for x in h["lists"])
+    assert sorted({x[3] for x in h["lists"]}) == case.claims["lengths"] == EQUAL_LENGTHS[n] and min(EQUAL_LENGTHS[n]) > cases.HEAVY
+    assert h["longest"] == EQUAL_LENGTHS[n][1]
+
+
+@pytest.mark.parametrize("n", tuple(n for n in cases.PLANS if "lengths" in cases.plan_families(n)))
+@pytest.mark.parametrize("name", cases.NAMES)
+def test_upper_lengths_and_cancelling_pairs(plan_hist, name, n):
+    """lists of exactly 64 and 65 in window 0 of index group 0, and an odd number of terms that still sum to the identity"""
+    h = plan_hist(name)[f"{name}-lengths-{n}"]
+    assert [x for x in h["lists"] if x[0] == 0 and x[2] < 2] == [(0, 0, 0, 64, 0), (0, 0, 1, 65, 0)]
+    assert h["heavy"] >= h["W"]
+    s = cases.SUITES[name]
+    ident = cases.build(name, "cancel-identity", n)
+    assert n % 2 == 1 and ident.terms[-1][:2] == ("id", 0) and ident.terms[-1][2] >> (s.bits // 2)        # a long scalar on the identity
+    assert all(a[0] == "m" and b[0] == "neg" and a[1:] == b[1:] for a, b in zip(ident.terms[:-1:2], ident.terms[1:-1:2]))
+    assert ident.expected() == s.identity and any(x[3] >= 80 for x in plan_hist(name)[ident.name]["lists"])
+    mixed = plan_hist(name)[f"{name}-cancel-mixed-{n}"]
+    assert any(x[3] >= 130 for x in mixed["lists"]) and any(100 <= x[3] < 130 for x in mixed["lists"])
+
+
 # ---------------------------------------------------------------- the host's window combination
 @pytest.mark.parametrize("name", cases.NAMES)
 def test_host_combine_equals_the_restatement(exe, tmp_path, name):
-    """set sums m G (ladder points, some negated, some the identity) for the plans of 256, 1030 and 4100 terms: the program's combination
-    is (sum_w 2^start_w sum_g m_wg mod n) G"""
+    """set sums m G (ladder points, some negated, some the identity) for the plans of 256, 1030 and 4100 terms, and of 16387, 65539 and
+    262147 (widths 9 and 10; 8, 16 and 64 index groups: up to 3392 set sums): the program's combination is
+    (sum_w 2^start_w sum_g m_wg mod n) G"""
     s = cases.SUITES[name]
     ref, lad = s.ref, cases.ladder(name)
     rng = cases._rng(name, "combine")
     blocks, want = [], []
-    for n in cases.SIZES + ("identity",):
+    assert [cases.PLANS[n][3] for n in (16387, 65539, 262147)] == [8, 16, 64]
+    for n in cases.SIZES + (16387, 65539, 262147, "identity"):
         t = cases.Tiling(256 if n == "identity" else n, s.bits)
         total, lines = 0, []
         for w in range(t.W):

@@ -1,5 +1,5 @@
 """The input families of the wide suites' bucket method (dr_wide_msm: csrc/wave_msm.hip.h), shared by test_wide_msm_plan_cpu.py, which
-proves on the host what bucket lists they make, and test_gpu_wide_msm.py, which runs them on the GPU.
+proves on the host what bucket lists they make, and test_gpu_wide_msm.py and test_gpu_wide_msm_plans.py, which run them on the GPU.
 
 Every point is a known multiple m G of the suite's generator (a ladder a G, (a + 1) G, ... built by affine additions), the identity, or
 a small-order point Q, so the expected value of a case is the closed form (sum k_i m_i mod n) G + (sum of Q's scalars mod ord Q) Q: one
@@ -22,6 +22,20 @@ with open(os.path.join(ROOT, "dot_ring_amd", "csrc", "msm_plan.hpp")) as _f:
 FROM = int(re.search(r"WIDE_PIP_FROM = (\d+)", _plan).group(1))
 HEAVY = int(re.search(r"TE_HEAVY_BUCKET = (\d+)", _plan).group(1))
 SIZES = (FROM, 1030, 4100)            # one index group, two, and the second window width
+# The upper half of the plan (test_gpu_wide_msm_plans.py): n -> (c, (W at 385, 449, 522 bits), H, index groups, families).  No size is a
+# multiple of its group count, so every group bound is a ceiling that differs from the floor.  1031 and 4103: the plans of 1030 and 4100
+# with a remainder; 16383 and 65535: the densest windows of widths 8 and 9 (one below a threshold); 16387 and 65539: widths 9 and 10, the
+# second with two bins per lane of the sort; 131075: 32 index groups; 262147: the cap of 64
+PLANS = {
+    1031: (7, (55, 65, 75), 64, 2, ("ladder", "equal", "edges")),
+    4103: (8, (49, 57, 66), 128, 4, ("ladder", "equal", "edges")),
+    16383: (8, (49, 57, 66), 128, 8, None),
+    16387: (9, (43, 50, 58), 256, 8, None),
+    65535: (9, (43, 50, 58), 256, 16, ("ladder", "equal")),
+    65539: (10, (39, 45, 53), 512, 16, None),
+    131075: (10, (39, 45, 53), 512, 32, ("ladder", "equal")),
+    262147: (10, (39, 45, 53), 512, 64, ("ladder", "equal")),
+}
 
 
 class Suite:
@@ -78,12 +92,17 @@ LADDER_A = 0x5EED0123456789ABCDEF
 
 @lru_cache(maxsize=None)
 def ladder(name):
-    """(a + i) G for i < 4100, by affine additions"""
+    """(a + i) G for i < 4100, by affine additions; term i of a larger case takes point i % 4100"""
     ref = SUITES[name].ref
     pts = [ref.mul(LADDER_A, ref.G)]
     for _ in range(max(SIZES) - 1):
         pts.append(ref.add(pts[-1], ref.G))
     return pts
+
+
+@lru_cache(maxsize=None)
+def _raw_ladder(name):
+    return [SUITES[name].raw(pt) for pt in ladder(name)]
 
 
 class Case:
@@ -101,10 +120,10 @@ class Case:
 
     def packed(self):
         s = SUITES[self.suite]
-        lad, ref = ladder(self.suite), s.ref
+        lad, raws, ref = ladder(self.suite), _raw_ladder(self.suite), s.ref
         pts = []
         for kind, v, _ in self.terms:
-            pts.append(s.raw(lad[v]) if kind == "m" else s.raw(ref.neg(lad[v])) if kind == "neg" else s.identity if kind == "id" else s.raw(s.small))
+            pts.append(raws[v] if kind == "m" else s.raw(ref.neg(lad[v])) if kind == "neg" else s.identity if kind == "id" else s.raw(s.small))
         return b"".join(pts), b"".join(k.to_bytes(s.nbytes, "little") for k in self.scalars)
 
     def expected(self):
@@ -118,6 +137,9 @@ class Case:
         return s.raw(out)
 
 
+LADDER = max(SIZES)
+
+
 def _rng(*key):
     return random.Random("wide-msm/" + "/".join(str(x) for x in key))
 
@@ -128,7 +150,7 @@ def _full(rng, s):
 
 def ladder_case(name, n, tag="ladder"):
     s, rng = SUITES[name], _rng(name, tag, n)
-    return Case(name, tag, n, [("m", i, _full(rng, s)) for i in range(n)])
+    return Case(name, tag, n, [("m", i % LADDER, _full(rng, s)) for i in range(n)])
 
 
 def equal_case(name, n):
@@ -148,26 +170,29 @@ def lengths_case(name, n):
     low = lambda k, d: (k >> (w0 + 1) << (w0 + 1)) | d                      # window 0 = d, the bit above it clear
     k1, k2 = low(_full(rng, s), 1), low(_full(rng, s), 2)
     terms = [("m", i, k1) for i in range(64)] + [("m", i, k2) for i in range(64, 129)]
-    terms += [("m", i, low(_full(rng, s), rng.randrange(3, 1 << (w0 - 1)))) for i in range(129, n)]
+    terms += [("m", i % LADDER, low(_full(rng, s), rng.randrange(3, 1 << (w0 - 1)))) for i in range(129, n)]
     assert n // t.groups >= 129
     return Case(name, "lengths", n, terms)
 
 
 def cancel_case(name, n, identity_total):
-    """(P, -P) pairs under one scalar and (P, P) repeats; identity_total: nothing but such pairs, whose sum is the identity"""
+    """(P, -P) pairs under one scalar and (P, P) repeats; identity_total: nothing but such pairs (and, where n is odd, one identity point
+    under a full-width scalar), whose sum is the identity"""
     s, rng = SUITES[name], _rng(name, "cancel", n, identity_total)
     if identity_total:
         terms = []
         for j in range(n // 2):
             k = _full(rng, s) if j >= 40 else 0x1234567 + (1 << (s.bits - 3))     # 40 pairs share one scalar: lists of 80
-            terms += [("m", j, k), ("neg", j, k)]
+            terms += [("m", j % LADDER, k), ("neg", j % LADDER, k)]
+        if n % 2:
+            terms.append(("id", 0, _full(rng, s)))
         return Case(name, "cancel-identity", n, terms)
     u, v = _full(rng, s), _full(rng, s)
     terms = []
     for j in range(65):
         terms += [("m", j, u), ("neg", j, u)]                  # 130 terms of one scalar that sum to the identity
     terms += [("m", 7, v)] * 100                               # one point a hundred times
-    terms += [("m", i, _full(rng, s)) for i in range(len(terms), n)]
+    terms += [("m", i % LADDER, _full(rng, s)) for i in range(len(terms), n)]
     return Case(name, "cancel-mixed", n, terms)
 
 
@@ -190,18 +215,30 @@ def edges_case(name, n):
         ks.append(next(q * s.order + r for q in (1, 2, 3) for r in (2, 3) if good(ks + [q * s.order + r])))
         assert all(k >= s.order for k in ks) and sum(ks) % s.small_order and sum(k % s.order for k in ks) % s.small_order != sum(ks) % s.small_order
         terms += [("small", 0, k) for k in ks]
-    terms += [("m", i, _full(rng, s)) for i in range(len(terms), n - 2)]
-    terms += [("id", 0, _full(rng, s)), ("m", n - 1, s.top - 1)]
+    terms += [("m", i % LADDER, _full(rng, s)) for i in range(len(terms), n - 2)]
+    terms += [("id", 0, _full(rng, s)), ("m", (n - 1) % LADDER, s.top - 1)]
     return Case(name, "edges", n, terms)
 
 
 FAMILIES = ("ladder", "equal", "lengths", "cancel-mixed", "cancel-identity", "edges")
 
 
-@lru_cache(maxsize=None)
-def case(name, family, n):
+def build(name, family, n):
+    """a case that nobody keeps: the large ones are tens of megabytes of terms"""
     return {"ladder": ladder_case, "equal": equal_case, "lengths": lengths_case, "edges": edges_case,
             "cancel-mixed": lambda a, b: cancel_case(a, b, False), "cancel-identity": lambda a, b: cancel_case(a, b, True)}[family](name, n)
+
+
+case = lru_cache(maxsize=None)(build)
+
+
+def plan_families(n):
+    return PLANS[n][4] or FAMILIES
+
+
+def plan_keys():
+    """(suite, family, n) of every case of PLANS"""
+    return [(name, family, n) for name in NAMES for n in PLANS for family in plan_families(n)]
 
 
 def all_cases():
