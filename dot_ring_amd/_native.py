@@ -209,6 +209,11 @@ _PROTOTYPES.update({
     "dr_comm_all_gather": (c_int, [c_void_p, c_char_p, c_size_t, c_char_p]),
     "dr_g1_msm_sharded_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, POINTER(c_int)]),
 })
+# the group laws on raw limb images (csrc/wave_curve.hip.h, wave_law_selftest): suite -> (limbs of a coordinate, coordinates of a point)
+LAW_SELFTEST_SHAPES = {"ed25519": (9, 4), "bjj": (9, 4), "p256": (9, 3), "secp256k1": (9, 3), "blsg1": (14, 3), "ed448": (16, 3),
+                       "curve448": (16, 3), "p521": (19, 3), "p384": (14, 3)}
+LAW_SELFTEST_SLOTS = 13
+_PROTOTYPES.update({f"dr_{suite}_law_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p]) for suite in LAW_SELFTEST_SHAPES})
 COMM_ID_BYTES = 128
 RINGVRF_AUX_BYTES = 960
 PEDERSEN_AUX_BYTES = 288
@@ -845,6 +850,28 @@ class Context:
     p384_msm_groups = functools.partialmethod(_wide_msm_groups, "p384")
     p384_decode_points = functools.partialmethod(_wide_flagged, "p384")
     p384_field_selftest = functools.partialmethod(_wide_field_selftest, "p384")
+
+    def _law_selftest(self, suite: str, points: bytes, controls: bytes) -> bytes:
+        """dr_<suite>_law_selftest: n x 13 points of raw limbs (little-endian int32) for n records of P then Q in the same form and n
+        little-endian control words (include/dotring_hip.h lists the slots)."""
+        limbs, coords = LAW_SELFTEST_SHAPES[suite]
+        rec = 2 * coords * limbs * 4
+        n = len(controls) // 4
+        if len(controls) != 4 * n or len(points) != rec * n:
+            raise ValueError(f"{suite}: a record is {rec} bytes of limbs and one 4-byte control word")
+        out = ctypes.create_string_buffer(max(1, n * LAW_SELFTEST_SLOTS * coords * limbs * 4))
+        _check(getattr(lib(), f"dr_{suite}_law_selftest")(self.handle, points, controls, n, out))
+        return out.raw[: n * LAW_SELFTEST_SLOTS * coords * limbs * 4]
+
+    ed25519_law_selftest = functools.partialmethod(_law_selftest, "ed25519")
+    bjj_law_selftest = functools.partialmethod(_law_selftest, "bjj")
+    p256_law_selftest = functools.partialmethod(_law_selftest, "p256")
+    secp256k1_law_selftest = functools.partialmethod(_law_selftest, "secp256k1")
+    blsg1_law_selftest = functools.partialmethod(_law_selftest, "blsg1")
+    ed448_law_selftest = functools.partialmethod(_law_selftest, "ed448")
+    curve448_law_selftest = functools.partialmethod(_law_selftest, "curve448")
+    p521_law_selftest = functools.partialmethod(_law_selftest, "p521")
+    p384_law_selftest = functools.partialmethod(_law_selftest, "p384")
 
     def blsg2_check_points(self, pts_xy: bytes, subgroup: bool = True) -> bytes:
         """dr_blsg2_check_points: one flag byte per 192-byte point: on the curve, and with `subgroup` also r P = O."""

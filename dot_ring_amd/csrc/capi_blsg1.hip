@@ -21,6 +21,8 @@ struct Blsg1Suite : SuiteDefaults {
     static constexpr auto scalar_mul = dr::k_blsg1_scalar_mul;
     static constexpr auto msm_groups = dr::k_blsg1_msm_groups;
     static constexpr auto field_selftest = dr::k_blsg1_field_selftest;
+    static constexpr auto law_selftest = dr::k_blsg1_law_selftest;
+    static constexpr int law_coords = 3, law_slots = dr::WAVE_LAW_SLOTS;
     static constexpr int block = dr::G1H_BLOCK, selftest_records = dr::G1H_SELFTEST_RECORDS;
     static constexpr const char *k_scalar_mul = "k_blsg1_scalar_mul", *k_msm_groups = "k_blsg1_msm_groups", *k_decode = "k_blsg1_decode_points";
     static constexpr size_t enc_bytes = 49, rec_bytes = 52;               // each encoding zero-padded to 13 words
@@ -71,4 +73,7 @@ int dr_blsg1_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_t n,
 }
 int dr_blsg1_field_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
     return field_selftest<Blsg1Suite>(ctx, a_limbs, b_limbs, n, out, flags);
+}
+int dr_blsg1_law_selftest(dr_ctx* ctx, const int32_t* points, const uint32_t* controls, size_t n, int32_t* out) {
+    return law_selftest<Blsg1Suite>(ctx, points, controls, n, out);
 }

@@ -493,6 +493,7 @@ namespace {
 template <class S>
 struct Native256 : SuiteDefaults {
     static constexpr size_t fe_bytes = 32, elem_bytes = 32, pt_bytes = 64, scalar_bytes = 32, limb_bytes = 36;
+    static constexpr int law_slots = dr::WAVE_LAW_SLOTS;
     static constexpr size_t max_map = 1ull << 30, max_points = 1ull << 31, max_decode = 1ull << 31;
     static constexpr bool limit_first = false, decode_gives_points = true, decode_checks_canonical = false;
     static bool canonical(const uint8_t* p) {
@@ -518,6 +519,8 @@ struct Ed25519Suite : Native256<Ed25519Suite> {
     static constexpr auto dec_tai = dr::k_ed_decode_points<dr::ED_DEC_TAI>, dec_check = dr::k_ed_decode_points<dr::ED_DEC_CHECK>,
                           dec_codec = dr::k_ed_decode_points<dr::ED_DEC_CODEC>;
     static constexpr auto field_selftest = dr::k_fe25519_selftest;
+    static constexpr auto law_selftest = dr::k_ed_law_selftest;
+    static constexpr int law_coords = 4;
     static constexpr int block = dr::ED_BLOCK, selftest_records = dr::FE_SELFTEST_RECORDS;
     static constexpr const char *name = "Ed25519", *k_scalar_mul = "k_ed_scalar_mul", *k_msm_groups = "k_ed_msm_groups", *k_decode = "k_ed_decode_points";
     static const drh::Mod256& field() { return drh::mod_p25519(); }
@@ -531,6 +534,8 @@ struct P256Suite : Native256<P256Suite> {
     static constexpr auto dec_tai = dr::k_p256_decode_points<dr::P256_DEC_TAI>, dec_check = dr::k_p256_decode_points<dr::P256_DEC_CHECK>,
                           dec_codec = dr::k_p256_decode_points<dr::P256_DEC_CODEC>;
     static constexpr auto field_selftest = dr::k_p256_field_selftest;
+    static constexpr auto law_selftest = dr::k_p256_law_selftest;
+    static constexpr int law_coords = 3;
     static constexpr int block = dr::P256_BLOCK, selftest_records = dr::P256_SELFTEST_RECORDS;
     static constexpr const char *name = "P-256", *k_scalar_mul = "k_p256_scalar_mul", *k_msm_groups = "k_p256_msm_groups", *k_decode = "k_p256_decode_points";
     static const drh::Mod256& field() { return drh::mod_p256(); }
@@ -555,6 +560,8 @@ struct Secp256k1Suite : Native256<Secp256k1Suite> {
     static constexpr auto dec_tai = dr::k_secp256k1_decode_points<dr::K1_DEC_CHECK>, dec_check = dr::k_secp256k1_decode_points<dr::K1_DEC_CHECK>,
                           dec_codec = dr::k_secp256k1_decode_points<dr::K1_DEC_CODEC>;
     static constexpr auto field_selftest = dr::k_secp256k1_field_selftest;
+    static constexpr auto law_selftest = dr::k_secp256k1_law_selftest;
+    static constexpr int law_coords = 3;
     static constexpr int block = dr::K1_BLOCK, selftest_records = dr::K1_SELFTEST_RECORDS;
     static constexpr const char *name = "secp256k1", *k_scalar_mul = "k_secp256k1_scalar_mul", *k_msm_groups = "k_secp256k1_msm_groups",
                                 *k_decode = "k_secp256k1_decode_points";
@@ -636,6 +643,8 @@ struct BjjSuite : Native256<BjjSuite> {
     static constexpr auto dec_tai = dr::k_bjj_decode_points<dr::BJJ_DEC_TAI>, dec_check = dr::k_bjj_decode_points<dr::BJJ_DEC_CHECK>,
                           dec_codec = dr::k_bjj_decode_points<dr::BJJ_DEC_CODEC>;
     static constexpr auto field_selftest = dr::k_bjj_field_selftest;
+    static constexpr auto law_selftest = dr::k_bjj_law_selftest;
+    static constexpr int law_coords = 4;
     static constexpr int block = dr::BJJ_BLOCK, selftest_records = dr::BJJ_SELFTEST_RECORDS;
     static constexpr const char *name = "Baby JubJub", *k_scalar_mul = "k_bjj_scalar_mul", *k_msm_groups = "k_bjj_msm_groups", *k_decode = "k_bjj_decode_points";
     static const drh::Mod256& field() { return drh::mod_pbn254(); }
@@ -1096,6 +1105,19 @@ int dr_curve25519_map_to_curve(dr_ctx* ctx, const uint8_t* us, size_t n, int per
 }
 int dr_bjj_field_ops_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
     return field_selftest<BjjSuite>(ctx, a_limbs, b_limbs, n, out, flags);
+}
+// the group laws on raw limb images (wave_curve.hip.h's wave_law_selftest; include/dotring_hip.h describes the records)
+int dr_ed25519_law_selftest(dr_ctx* ctx, const int32_t* points, const uint32_t* controls, size_t n, int32_t* out) {
+    return law_selftest<Ed25519Suite>(ctx, points, controls, n, out);
+}
+int dr_bjj_law_selftest(dr_ctx* ctx, const int32_t* points, const uint32_t* controls, size_t n, int32_t* out) {
+    return law_selftest<BjjSuite>(ctx, points, controls, n, out);
+}
+int dr_p256_law_selftest(dr_ctx* ctx, const int32_t* points, const uint32_t* controls, size_t n, int32_t* out) {
+    return law_selftest<P256Suite>(ctx, points, controls, n, out);
+}
+int dr_secp256k1_law_selftest(dr_ctx* ctx, const int32_t* points, const uint32_t* controls, size_t n, int32_t* out) {
+    return law_selftest<Secp256k1Suite>(ctx, points, controls, n, out);
 }
 
 int dr_bsn_encode_to_curve_batch(dr_ctx* ctx, const uint8_t* u_pairs, size_t n, uint8_t* out_xy) {

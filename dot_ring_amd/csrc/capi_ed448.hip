@@ -24,6 +24,8 @@ struct Ed448Suite : SuiteDefaults {
     static constexpr auto scalar_mul = dr::k_ed448_scalar_mul;
     static constexpr auto msm_groups = dr::k_ed448_msm_groups;
     static constexpr auto field_selftest = dr::k_ed448_field_selftest;
+    static constexpr auto law_selftest = dr::k_ed448_law_selftest;
+    static constexpr int law_coords = 3, law_slots = dr::WAVE_LAW_SLOTS;
     static constexpr int block = dr::E448_BLOCK, selftest_records = dr::E448_SELFTEST_RECORDS;
     static constexpr const char *k_scalar_mul = "k_ed448_scalar_mul", *k_msm_groups = "k_ed448_msm_groups", *k_decode = "k_ed448_check_points";
     // the bucket method of dr_wide_msm (capi_wide_msm.hpp): the law on the host, the bits the tiling covers, the stages' kernels
@@ -62,9 +64,11 @@ struct Ed448Suite : SuiteDefaults {
 };
 
 // Curve448: the field, the widths and the limits are Ed448's; the kernels carry an identity flag word beside each point (flagged), which
-// run_points makes of 112 bytes of 0xff and back.  The field selftest is Ed448's: there is none here.
+// run_points makes of 112 bytes of 0xff and back.  The field selftest is Ed448's: there is none here; the law (c448_law.hip.h) has its own.
 struct Curve448Suite : SuiteDefaults {
-    static constexpr size_t fe_bytes = 56, elem_bytes = 56, pt_bytes = 112, scalar_bytes = 56;
+    static constexpr size_t fe_bytes = 56, elem_bytes = 56, pt_bytes = 112, scalar_bytes = 56, limb_bytes = 4 * dr::L448;
+    static constexpr auto law_selftest = dr::k_c448_law_selftest;
+    static constexpr int law_coords = 3, law_slots = dr::WAVE_LAW_SLOTS;
     static constexpr bool flagged = true;
     static constexpr int variant_ro = DR_CURVE_CURVE448_RO, variant_nu = DR_CURVE_CURVE448_NU;
     static constexpr const char* variant_names = "DR_CURVE_CURVE448_RO or DR_CURVE_CURVE448_NU";
@@ -132,6 +136,9 @@ int dr_ed448_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_t n,
 int dr_ed448_field_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
     return field_selftest<Ed448Suite>(ctx, a_limbs, b_limbs, n, out, flags);
 }
+int dr_ed448_law_selftest(dr_ctx* ctx, const int32_t* points, const uint32_t* controls, size_t n, int32_t* out) {
+    return law_selftest<Ed448Suite>(ctx, points, controls, n, out);
+}
 
 // dr_wide_msm for DR_CURVE_ED448_RO / _NU and DR_CURVE_CURVE448_RO / _NU (the dispatcher is capi_msm.hip's); Curve448's identity travels
 // inside the point as 112 bytes of 0xff, in and out
@@ -163,4 +170,7 @@ int dr_curve448_msm_groups(dr_ctx* ctx, const uint8_t* pts_uv, const uint8_t* sc
 }
 int dr_curve448_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_t n, uint8_t* out_uv, uint8_t* ok) {
     return decode_points<Curve448Suite>(ctx, check ? dr::k_c448_decode_points<1> : dr::k_c448_decode_points<0>, enc, n, out_uv, ok);
+}
+int dr_curve448_law_selftest(dr_ctx* ctx, const int32_t* points, const uint32_t* controls, size_t n, int32_t* out) {
+    return law_selftest<Curve448Suite>(ctx, points, controls, n, out);
 }

@@ -22,6 +22,8 @@ struct P384Suite : SuiteDefaults {
     static constexpr auto scalar_mul = dr::k_p384_scalar_mul;
     static constexpr auto msm_groups = dr::k_p384_msm_groups;
     static constexpr auto field_selftest = dr::k_p384_field_selftest;
+    static constexpr auto law_selftest = dr::k_p384_law_selftest;
+    static constexpr int law_coords = 3, law_slots = dr::WAVE_LAW_SLOTS;
     static constexpr int block = dr::P384_BLOCK, selftest_records = dr::P384_SELFTEST_RECORDS;
     static constexpr const char *k_scalar_mul = "k_p384_scalar_mul", *k_msm_groups = "k_p384_msm_groups", *k_decode = "k_p384_decode_points";
     // the bucket method of dr_wide_msm (capi_wide_msm.hpp): the law on the host, the bits the tiling covers, the stages' kernels
@@ -89,4 +91,7 @@ int dr_p384_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_t n, 
 }
 int dr_p384_field_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, size_t n, uint8_t* out, uint8_t* flags) {
     return field_selftest<P384Suite>(ctx, a_limbs, b_limbs, n, out, flags);
+}
+int dr_p384_law_selftest(dr_ctx* ctx, const int32_t* points, const uint32_t* controls, size_t n, int32_t* out) {
+    return law_selftest<P384Suite>(ctx, points, controls, n, out);
 }

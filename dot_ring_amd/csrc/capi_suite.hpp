@@ -7,6 +7,8 @@
 //   max_map, max_points, max_decode                            batch limits (exclusive): map / encode, scalar_mul / msm_groups, decode / check
 //   limit_first                                                msm_groups compares its sizes with max_points before it looks for null buffers
 //   block, selftest_records; scalar_mul, msm_groups, field_selftest (kernels); k_scalar_mul, k_msm_groups, k_decode (launch names)
+//   law_selftest (kernel), law_coords, law_slots               the diagnostic of the group law on raw limb images: the coordinates of a
+//                                                              point (3, or 4 with t) and wave_curve.hip.h's WAVE_LAW_SLOTS
 //   enc_bytes, rec_bytes, decode_gives_points, decode_checks_canonical   the flag-returning launch: an input, its zero-padded record on
 //                                                              the device, whether points come back, whether inputs are field elements
 //   canonical(p)                                               whether the fe_bytes at p are below the modulus
@@ -222,6 +224,23 @@ int field_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, 
         hipLaunchKernelGGL(S::field_selftest, dim3(div_up(n, 64)), dim3(64), 0, ctx->stream, ctx->io_a.as<int32_t>(),
                            (const int32_t*)(ctx->io_a.as<uint8_t>() + n * S::limb_bytes), (uint32_t)n, ctx->io_b.as<uint32_t>(), ctx->io_c.as<uint32_t>());
     }, {out, &ctx->io_b, 0, n * rec}, n, flags, false);
+}
+
+// wave_curve.hip.h's wave_law_selftest over the suite's curve: n records of S::law_coords coordinates for P and as many for Q, raw limb
+// images of S::limb_bytes each, and n control words in; n x S::law_slots (wave_curve.hip.h's WAVE_LAW_SLOTS) points in the same form out; not profiled
+template <class S>
+int law_selftest(dr_ctx* ctx, const int32_t* points, const uint32_t* controls, size_t n, int32_t* out) {
+    TRY(use_ctx(ctx));
+    if (n == 0) return DR_OK;
+    if (!points || !controls || !out) return fail(DR_ERR_INVALID, "null buffer");
+    if (n >= MAX_SELFTEST) return fail(DR_ERR_INVALID, "batch too large");
+    TRY(S::consts_ready(ctx));
+    constexpr size_t pt = (size_t)S::law_coords * S::limb_bytes;
+    return io_round(ctx, {n * (2 * pt + 4), n * S::law_slots * pt, 0},
+                    {{&ctx->io_a, 0, points, n * 2 * pt}, {&ctx->io_a, n * 2 * pt, controls, n * 4}}, nullptr, [&] {
+        hipLaunchKernelGGL(S::law_selftest, dim3(div_up(n, 64)), dim3(64), 0, ctx->stream, ctx->io_a.as<int32_t>(),
+                           (const uint32_t*)(ctx->io_a.as<uint8_t>() + n * 2 * pt), (uint32_t)n, ctx->io_b.as<int32_t>());
+    }, {{out, &ctx->io_b, 0, n * S::law_slots * pt}});
 }
 
 }  // namespace dri

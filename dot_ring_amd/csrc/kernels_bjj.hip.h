@@ -73,7 +73,9 @@ DR_DEV BjjPoint bjj_identity() {
     return p;
 }
 
-// dbl-2008-hwcd, a = 1.  WITH_T = false skips T3 (the result is only doubled again).
+// dbl-2008-hwcd, a = 1.  WITH_T = false skips T3 (the result is only doubled again).  Coordinates n (x and t possibly negated by
+// bjj_cneg: every operand below is a square or a product, which take a negated normal as they take a normal) in, n out: every
+// coordinate is a product (T = 0 without it)
 template <bool WITH_T>
 DR_DEV BjjPoint bjj_dbl(const BjjPoint& p) {
     const Fbn A = sqr(p.x), B = sqr(p.y);                   // n
@@ -91,7 +93,8 @@ DR_DEV BjjPoint bjj_dbl(const BjjPoint& p) {
     return r;
 }
 
-// add-2008-hwcd, a = 1, unified (also right for doubling and the identity: d is not a square, a = 1 is).  dt2 = d T2.
+// add-2008-hwcd, a = 1, unified (also right for doubling and the identity: d is not a square, a = 1 is).  dt2 = d T2.  Coordinates n
+// (x and t possibly negated by bjj_cneg, in either point) in, n out: every coordinate is a product
 DR_DEV BjjPoint bjj_add_dt(const BjjPoint& p, const BjjPoint& q, const Fbn& dt2) {
     const Fbn A = mul(p.x, q.x), B = mul(p.y, q.y);          // n
     const Fbn C = mul(p.t, dt2);                            // n
@@ -288,6 +291,11 @@ __global__ __launch_bounds__(64) void k_bjj_field_selftest(const int32_t* __rest
     bn_pack(a, w);
     wave_store_fe<BjjCurve>(o + 88, bn_unpack(w));
     flags[i] = (sq ? 1u : 0u) | (is_larger(a) ? 4u : 0u);
+}
+
+// Diagnostic (dr_bjj_law_selftest): wave_curve.hip.h's wave_law_selftest over BjjCurve, the law on raw limb images
+__global__ __launch_bounds__(64) void k_bjj_law_selftest(const int32_t* __restrict__ pts, const uint32_t* __restrict__ ctl, uint32_t n, int32_t* __restrict__ out) {
+    wave_law_selftest<BjjCurve>(pts, ctl, n, out);
 }
 
 }  // namespace dr

@@ -189,4 +189,9 @@ __global__ __launch_bounds__(E448_BLOCK) void k_c448_decode_points(const uint32_
     }
 }
 
+// Diagnostic (dr_curve448_law_selftest): wave_curve.hip.h's wave_law_selftest over Curve448Curve, the law on raw limb images
+__global__ __launch_bounds__(64) void k_c448_law_selftest(const int32_t* __restrict__ pts, const uint32_t* __restrict__ ctl, uint32_t n, int32_t* __restrict__ out) {
+    wave_law_selftest<Curve448Curve>(pts, ctl, n, out);
+}
+
 }  // namespace dr

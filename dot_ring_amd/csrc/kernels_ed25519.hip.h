@@ -25,7 +25,9 @@ DR_DEV EdPoint ed_identity() {
     return p;
 }
 
-// dbl-2008-hwcd, a = -1.  WITH_T = false skips T3 (the result is only doubled again).
+// dbl-2008-hwcd, a = -1.  WITH_T = false skips T3 (the result is only doubled again).  Coordinates n (x and t possibly negated by
+// ed_cneg: every operand below is a square or a product, which take a negated normal as they take a normal) in, n out: every coordinate
+// is a product (T = 0 without it)
 template <bool WITH_T>
 DR_DEV EdPoint ed_dbl(const EdPoint& p) {
     const F25 A = sqr(p.x), B = sqr(p.y);                   // n
@@ -44,6 +46,7 @@ DR_DEV EdPoint ed_dbl(const EdPoint& p) {
 }
 
 // add-2008-hwcd, a = -1, unified (also right for doubling and the identity).  dt2 = d T2 (the caller's constant or table value).
+// Coordinates n (x and t possibly negated by ed_cneg, in either point) in, n out: every coordinate is a product
 DR_DEV EdPoint ed_add_dt(const EdPoint& p, const EdPoint& q, const F25& dt2) {
     const F25 A = mul(p.x, q.x), B = mul(p.y, q.y);          // n
     const F25 C = mul(p.t, dt2);                            // n
@@ -292,6 +295,11 @@ __global__ __launch_bounds__(64) void k_fe25519_selftest(const int32_t* __restri
     const bool rt = fe_sqrt_ratio(a, b, r);
     wave_store_fe<Ed25519Curve>(o + 80, r);
     flags[i] = (sq ? 1u : 0u) | (rt ? 2u : 0u) | (is_larger(a) ? 4u : 0u);
+}
+
+// Diagnostic (dr_ed25519_law_selftest): wave_curve.hip.h's wave_law_selftest over Ed25519Curve, the law on raw limb images
+__global__ __launch_bounds__(64) void k_ed_law_selftest(const int32_t* __restrict__ pts, const uint32_t* __restrict__ ctl, uint32_t n, int32_t* __restrict__ out) {
+    wave_law_selftest<Ed25519Curve>(pts, ctl, n, out);
 }
 
 }  // namespace dr

@@ -241,4 +241,9 @@ __global__ __launch_bounds__(64) void k_ed448_field_selftest(const int32_t* __re
     flags[i] = (sq ? 1u : 0u) | (is_odd(a) ? 2u : 0u) | (is_zero(a) ? 4u : 0u) | (equal(a, b) ? 8u : 0u);
 }
 
+// Diagnostic (dr_ed448_law_selftest): wave_curve.hip.h's wave_law_selftest over Ed448Curve, the law on raw limb images
+__global__ __launch_bounds__(64) void k_ed448_law_selftest(const int32_t* __restrict__ pts, const uint32_t* __restrict__ ctl, uint32_t n, int32_t* __restrict__ out) {
+    wave_law_selftest<Ed448Curve>(pts, ctl, n, out);
+}
+
 }  // namespace dr

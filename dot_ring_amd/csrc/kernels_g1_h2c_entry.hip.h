@@ -80,4 +80,9 @@ __global__ __launch_bounds__(64) void k_blsg1_field_selftest(const int32_t* __re
     flags[i] = (sq ? 1u : 0u) | (g1h_is_odd(a) ? 2u : 0u) | (g1h_is_zero(a) ? 4u : 0u);
 }
 
+// Diagnostic (dr_blsg1_law_selftest): wave_curve.hip.h's wave_law_selftest over G1hCurve, the law on raw limb images
+__global__ __launch_bounds__(64) void k_blsg1_law_selftest(const int32_t* __restrict__ pts, const uint32_t* __restrict__ ctl, uint32_t n, int32_t* __restrict__ out) {
+    wave_law_selftest<G1hCurve>(pts, ctl, n, out);
+}
+
 }  // namespace dr

@@ -27,7 +27,8 @@ DR_DEV P256Point p256_identity() {
     return p;
 }
 
-// algorithm 6, a = -3 (8M + 3S + 2 products by b, here 7 products, 3 squarings and one fused pair); coordinates n or r in, n out
+// algorithm 6, a = -3 (8M + 3S + 2 products by b, here 7 products, 3 squarings and one fused pair); coordinates n or r (y possibly
+// negated by p256_cneg: it meets products, squares and sums of two only) in, n out
 DR_DEV P256Point p256_dbl(const P256Point& p) {
     const F256 b = F256::constant<Fp256Consts::B>();
     const F256 t0 = sqr(p.x), t1 = sqr(p.y), t2 = sqr(p.z);                    // n
@@ -48,7 +49,8 @@ DR_DEV P256Point p256_dbl(const P256Point& p) {
     return r;
 }
 
-// algorithm 4, a = -3 (12M + 2 products by b; here 8 products and 3 fused pairs); coordinates n or r in, n out
+// algorithm 4, a = -3 (12M + 2 products by b; here 8 products and 3 fused pairs); coordinates n or r (y possibly negated by
+// p256_cneg, in either point) in, n out
 DR_DEV P256Point p256_add(const P256Point& p, const P256Point& q) {
     const F256 b = F256::constant<Fp256Consts::B>();
     const F256 t0 = mul(p.x, q.x), t1 = mul(p.y, q.y), t2 = mul(p.z, q.z);      // n
@@ -275,6 +277,11 @@ __global__ __launch_bounds__(64) void k_p256_field_selftest(const int32_t* __res
     wave_store_fe<P256Curve>(o + 80, fp_reduce(a));
     wave_store_fe<P256Curve>(o + 88, sqr(fp_reduce(a)));
     flags[i] = (sq ? 1u : 0u) | (is_larger_words<Fp256Consts>(w) ? 2u : 0u) | ((w[0] & 1u) ? 4u : 0u);
+}
+
+// Diagnostic (dr_p256_law_selftest): wave_curve.hip.h's wave_law_selftest over P256Curve, the law on raw limb images
+__global__ __launch_bounds__(64) void k_p256_law_selftest(const int32_t* __restrict__ pts, const uint32_t* __restrict__ ctl, uint32_t n, int32_t* __restrict__ out) {
+    wave_law_selftest<P256Curve>(pts, ctl, n, out);
 }
 
 }  // namespace dr

@@ -209,4 +209,9 @@ __global__ __launch_bounds__(64) void k_secp256k1_field_selftest(const int32_t* 
     flags[i] = (sq ? 1u : 0u) | ((w[0] & 1u) ? 2u : 0u);
 }
 
+// Diagnostic (dr_secp256k1_law_selftest): wave_curve.hip.h's wave_law_selftest over Secp256k1Curve, the law on raw limb images
+__global__ __launch_bounds__(64) void k_secp256k1_law_selftest(const int32_t* __restrict__ pts, const uint32_t* __restrict__ ctl, uint32_t n, int32_t* __restrict__ out) {
+    wave_law_selftest<Secp256k1Curve>(pts, ctl, n, out);
+}
+
 }  // namespace dr

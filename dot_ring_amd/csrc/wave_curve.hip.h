@@ -1,7 +1,7 @@
 // The wave-per-workgroup scalar-multiplication family of every curve with kernels of its own — the four native 256-bit curves (Ed25519,
 // Baby JubJub, P-256, secp256k1), BLS12-381's E(Fq) (48-byte coordinates), Ed448, Curve448 (56-byte coordinates and scalars), P-521
 // (68-byte) and P-384 (48-byte coordinates and scalars) — as one set of templates over a description C of the curve: the memory forms, the fixed-schedule scalar multiplication the
-// provers' secret scalars go through, the two kernel bodies built on it, and the SEC1-compressed decoder.  kernels_ed25519.hip.h
+// provers' secret scalars go through, the two kernel bodies built on it, a diagnostic of the law on raw limb images, and the SEC1-compressed decoder.  kernels_ed25519.hip.h
 // (Ed25519Curve), kernels_bjj.hip.h (BjjCurve), kernels_p256.hip.h (P256Curve), kernels_secp256k1.hip.h (Secp256k1Curve),
 // kernels_g1_h2c.hip.h (G1hCurve), kernels_ed448.hip.h (Ed448Curve), kernels_curve448.hip.h (Curve448Curve), kernels_p521.hip.h
 // (P521Curve) and kernels_p384.hip.h (P384Curve) each give a field, a group law, one description and one thin named __global__ per kernel; the schedule below exists once.
@@ -316,6 +316,80 @@ DR_DEV void wave_msm_groups(const uint32_t* __restrict__ pts, const uint32_t* __
 #pragma unroll 1
     for (uint32_t s = mpad >> 1; s > 0; s >>= 1) acc = C::add(acc, wave_shfl_down<C>(acc, s));
     if (g < groups && j == 0) wave_store_affine<C>(out + (size_t)g * (2 * C::WORDS), acc);
+}
+
+// ---------------------------------------------------------------- diagnostic of the law (dr_*_law_selftest)
+// The description's law on RAW limb images, one lane per record: no packing, no inversion and no ABI conversion on either side, so a test
+// sees the congruence AND the register form of everything the law returns, and can put every coordinate at the edge of the class the
+// law documents.  pts: n records of P then Q, each x, y, z (and t when EXTENDED) of sizeof(Fe::l) / 4 int32 limbs; ctl: n control words;
+// out: n x WAVE_LAW_SLOTS points in the same form.  The slots:
+//   0  add(P, Q)                1  add(P, cneg(Q, true))       2  dbl(P)          3  dbl_no_t(P) (EXTENDED only; otherwise not written)
+//   4  cneg(P, true)            5  slot 0 after wave_lds_store to entry WAVE_LAW_ENTRY and wave_lds_load back     6  cneg(P, false)
+//   7 + w, w = 0..5             acc after window w of a chain run exactly as wave_scalar_mul_core runs one: four doublings (the first
+//                               three dbl_no_t when EXTENDED), then add of the table term loaded from LDS entry WAVE_LAW_ENTRY (slot 0's
+//                               point, stored once), negated when bit w of the control word is set and replaced by identity() when bit
+//                               8 + w is; the chain starts at acc = P
+// The table is the scalar multiplication's own (wave_table_words<C>()).  A lane past n recomputes record n - 1 and stores nothing.
+constexpr int WAVE_LAW_SLOTS = 13, WAVE_LAW_WINDOWS = 6, WAVE_LAW_ENTRY = 3;
+template <class C>
+DR_DEV void wave_law_selftest(const int32_t* __restrict__ pts, const uint32_t* __restrict__ ctl, uint32_t n, int32_t* __restrict__ out) {
+    using Point = typename C::Point;
+    using Fe = typename C::Fe;
+    constexpr int L = (int)(sizeof(Fe::l) / sizeof(int32_t)), NC = C::EXTENDED ? 4 : 3;
+    __shared__ uint32_t tab[wave_table_words<C>()];
+    const int lane = threadIdx.x;
+    uint32_t i = blockIdx.x * C::BLOCK + lane;
+    const bool live = i < n;
+    if (!live) i = n - 1;            // keep the wave converged; the duplicate results are not stored
+    auto load = [&](const int32_t* p) {
+        Point r;
+#pragma unroll
+        for (int t = 0; t < L; t++) {
+            r.x.l[t] = p[t]; r.y.l[t] = p[L + t]; r.z.l[t] = p[2 * L + t];
+            if constexpr (C::EXTENDED) r.t.l[t] = p[3 * L + t];
+        }
+        return r;
+    };
+    int32_t* const o = out + (size_t)i * (WAVE_LAW_SLOTS * NC * L);
+    auto put = [&](int slot, const Point& r) {
+        if (!live) return;
+        int32_t* q = o + slot * (NC * L);
+#pragma unroll
+        for (int t = 0; t < L; t++) {
+            q[t] = r.x.l[t]; q[L + t] = r.y.l[t]; q[2 * L + t] = r.z.l[t];
+            if constexpr (C::EXTENDED) q[3 * L + t] = r.t.l[t];
+        }
+    };
+    const Point P = load(pts + (size_t)i * (2 * NC * L)), Q = load(pts + (size_t)i * (2 * NC * L) + NC * L);
+    const uint32_t cw = ctl[i];
+#pragma unroll 1
+    for (int s = 0; s < 2; s++) {
+        const Point R = C::add(P, C::cneg(Q, s != 0));
+        put(s, R);
+        if (s == 0) wave_lds_store<C>(tab, WAVE_LAW_ENTRY, lane, R);
+    }
+    put(2, C::dbl(P));
+    if constexpr (C::EXTENDED) put(3, C::dbl_no_t(P));
+#pragma unroll 1
+    for (int s = 0; s < 2; s++) put(s == 0 ? 4 : 6, C::cneg(P, s == 0));
+    put(5, wave_lds_load<C>(tab, WAVE_LAW_ENTRY, lane));
+    Point acc = P;
+#pragma unroll 1
+    for (int w = 0; w < WAVE_LAW_WINDOWS; w++) {
+        if constexpr (C::EXTENDED) {
+#pragma unroll 1
+            for (int j = 0; j < 3; j++) acc = C::dbl_no_t(acc);
+            acc = C::dbl(acc);
+        } else {
+#pragma unroll 1
+            for (int j = 0; j < 4; j++) acc = C::dbl(acc);
+        }
+        Point T = wave_lds_load<C>(tab, WAVE_LAW_ENTRY, lane);
+        T = C::cneg(T, ((cw >> w) & 1u) != 0);
+        if (((cw >> (8 + w)) & 1u) != 0) T = C::identity();
+        acc = C::add(acc, T);
+        put(7 + w, acc);
+    }
 }
 
 // ---------------------------------------------------------------- SEC1 compressed points

@@ -531,6 +531,34 @@ DR_API int dr_p384_field_selftest(dr_ctx *ctx, const int32_t *a_limbs /* n*14 */
  * terms — so it is for public scalars (the batch verifiers'); secret scalars go through scalar_mul_batch and msm_groups. */
 DR_API int dr_wide_msm(dr_ctx *ctx, int curve, const uint8_t *pts, const uint8_t *scalars, size_t n, uint8_t *out);
 
+/* ---- diagnostics of the nine group laws on RAW limb images ---------------------------------------
+ * csrc/wave_curve.hip.h's wave_law_selftest over the curve's description: no packing, no inversion and no conversion on either side, so a
+ * test can put every coordinate at the edge of the limb class its law documents and read the class of what the law returns.  A
+ * coordinate is L signed 32-bit limbs (9: Ed25519, Baby JubJub, P-256, secp256k1; 14: BLS12-381 E(Fq), P-384; 16: Ed448, Curve448; 19:
+ * P-521) in the field's own form; a point is its C coordinates x, y, z (C = 3) or x, y, z, t (C = 4: Ed25519, Baby JubJub).
+ * points[i] = P then Q (2 C L limbs), controls[i] = one word, out[i] = 13 points (13 C L limbs):
+ *   0 add(P, Q)   1 add(P, -Q)   2 dbl(P)   3 dbl_no_t(P) (C = 4 only; not written otherwise)   4 cneg(P, true)   6 cneg(P, false)
+ *   5 slot 0 through the LDS table of the scalar multiplication (to_lds, from_lds) and back
+ *   7 + w, w < 6: the accumulator after window w of the fixed schedule started at P: four doublings, then the table term (slot 0's point,
+ *   from LDS) added, negated if bit w of the control word is set, the identity if bit 8 + w is.
+ * n = 0 returns at once; a null buffer and n >= 2^24 are refused.  The calls launch under no profiled name. */
+DR_API int dr_ed25519_law_selftest(dr_ctx *ctx, const int32_t *points /* n*2*4*9 */, const uint32_t *controls /* n */, size_t n,
+                                   int32_t *out /* n*13*4*9 */);
+DR_API int dr_bjj_law_selftest(dr_ctx *ctx, const int32_t *points /* n*2*4*9 */, const uint32_t *controls, size_t n, int32_t *out /* n*13*4*9 */);
+DR_API int dr_p256_law_selftest(dr_ctx *ctx, const int32_t *points /* n*2*3*9 */, const uint32_t *controls, size_t n, int32_t *out /* n*13*3*9 */);
+DR_API int dr_secp256k1_law_selftest(dr_ctx *ctx, const int32_t *points /* n*2*3*9 */, const uint32_t *controls, size_t n,
+                                     int32_t *out /* n*13*3*9 */);
+DR_API int dr_blsg1_law_selftest(dr_ctx *ctx, const int32_t *points /* n*2*3*14 */, const uint32_t *controls, size_t n,
+                                 int32_t *out /* n*13*3*14 */);
+DR_API int dr_ed448_law_selftest(dr_ctx *ctx, const int32_t *points /* n*2*3*16 */, const uint32_t *controls, size_t n,
+                                 int32_t *out /* n*13*3*16 */);
+DR_API int dr_curve448_law_selftest(dr_ctx *ctx, const int32_t *points /* n*2*3*16 */, const uint32_t *controls, size_t n,
+                                    int32_t *out /* n*13*3*16 */);
+DR_API int dr_p521_law_selftest(dr_ctx *ctx, const int32_t *points /* n*2*3*19 */, const uint32_t *controls, size_t n,
+                                int32_t *out /* n*13*3*19 */);
+DR_API int dr_p384_law_selftest(dr_ctx *ctx, const int32_t *points /* n*2*3*14 */, const uint32_t *controls, size_t n,
+                                int32_t *out /* n*13*3*14 */);
+
 /* square root in the Bandersnatch base field; DR_ERR_NOTSQUARE if none exists. Host-side, no ctx. */
 DR_API int dr_fr_sqrt(const uint8_t in[32], uint8_t out[32]);
 

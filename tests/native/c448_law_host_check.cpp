@@ -7,6 +7,7 @@
 //   oncurve u v             m448_on_curve
 //   rawadd x1 y1 z1 x2 y2 z2 (limb images)   m448_add on them as they are
 //   rawdbl x y z (limb images)               m448_dbl
+//   lane P Q control                         law_lane.hpp: the same and the chain of six windows, raw limbs out
 // Output: `flag u v` (flag 1 = the identity; u, v 112 hexadecimal digits) for add / sub / dbl; `has_value flag u v` for ell2; `0` / `1`
 // for oncurve; `X Y Z` (canonical, 112 digits each) for the raw forms.  Built with -fsanitize=undefined -fno-sanitize-recover, a signed
 // overflow of a 64-bit column (or of a 32-bit limb) aborts the program: that is how the limb classes annotated in the header are
@@ -17,6 +18,11 @@
 #include <string>
 
 #include "c448_law.hip.h"
+#include "law_lane.hpp"
+
+struct LaneLaw : dr::M448Law {
+    static dr::M448Point cneg(const dr::M448Point& p, bool negate) { return dr::m448_cneg(p, negate); }
+};
 
 static bool read_hex(std::istringstream& in, dr::F448& a) {
     std::string s;
@@ -101,6 +107,8 @@ int main() {
         } else if (op == "rawdbl") {
             if (!read_limbs(in, p.x) || !read_limbs(in, p.y) || !read_limbs(in, p.z)) return 2;
             print_projective(dr::m448_dbl(p));
+        } else if (op == "lane") {
+            if (!law_lane<LaneLaw>(in)) return 2;
         } else {
             return 3;
         }

@@ -11,6 +11,7 @@
 //   map u                       sswu_map<P384Sswu> and sswu_iso_map, stored affine
 //   recode k                    the 96 digits of wave_recode<12>, least significant first, then the carry out of the top one
 //   words v                     unpack then pack (the canonical value of any 12 words), then below_p
+//   lane P Q control            law_lane.hpp: rawadd, rawdbl, both cneg and the chain of six windows on raw limb images, raw limbs out
 // Output: canonical values as 96 hexadecimal digits; points as `x y` (the identity as zeros); flags 0 / 1; digits as decimal integers.
 // Built with -fsanitize=undefined -fno-sanitize-recover, a signed overflow of a 64-bit column (or of a 32-bit limb) aborts the program:
 // that is how the contract of the field and the limb classes annotated in the law are checked without a GPU.
@@ -22,6 +23,12 @@
 #include "p384_law.hip.h"
 #include "sswu.hip.h"
 #include "wave_recode.hip.h"
+
+#include "law_lane.hpp"
+
+struct LaneLaw : dr::P384Law {
+    static dr::P384Point cneg(const dr::P384Point& p, bool negate) { return dr::p384_cneg(p, negate); }
+};
 
 static bool read_words(std::istringstream& in, uint32_t (&w)[dr::W384]) {
     std::string s;
@@ -118,6 +125,8 @@ int main() {
             if (!read_words(in, w)) return 2;
             print_fe(dr::unpack(w));
             std::printf(" %d", dr::below_p(w) ? 1 : 0);
+        } else if (op == "lane") {
+            if (!law_lane<LaneLaw>(in)) return 2;
         } else {
             return 3;
         }

@@ -336,7 +336,7 @@ def test_names_ids_exports_and_lengths():
     w = _native._WIDE["p384"]
     assert (w.elem, w.point, w.scalar, w.enc, w.limbs, w.records, w.nu, w.flagged) == (48, 96, 48, 49, 56, 13, 26, "decode_points")
     names = ["dr_p384_hash_to_field_batch", "dr_p384_map_to_curve", "dr_p384_encode_to_curve_batch", "dr_p384_scalar_mul_batch",
-             "dr_p384_msm_groups", "dr_p384_decode_points", "dr_p384_field_selftest"]
+             "dr_p384_msm_groups", "dr_p384_decode_points", "dr_p384_field_selftest", "dr_p384_law_selftest"]
     lib = _native.lib()
     for name in names:
         assert name in _native.EXPORTED_SYMBOLS and hasattr(lib, name)

@@ -321,7 +321,7 @@ def test_names_ids_exports_and_lengths():
     w = _native._WIDE["p521"]
     assert (w.elem, w.point, w.scalar, w.enc, w.limbs, w.records, w.nu, w.flagged) == (68, 136, 68, 67, 76, 11, 24, "decode_points")
     names = ["dr_p521_hash_to_field_batch", "dr_p521_map_to_curve", "dr_p521_encode_to_curve_batch", "dr_p521_scalar_mul_batch",
-             "dr_p521_msm_groups", "dr_p521_decode_points", "dr_p521_field_selftest"]
+             "dr_p521_msm_groups", "dr_p521_decode_points", "dr_p521_field_selftest", "dr_p521_law_selftest"]
     lib = _native.lib()
     for name in names:
         assert name in _native.EXPORTED_SYMBOLS and hasattr(lib, name)
