@@ -33,12 +33,12 @@ struct M448Point {
     F448 x, y, z;
 };
 
-DR_F448_FN M448Point m448_identity() { return {F448::zero(), F448::small(1), F448::small(1)}; }
-DR_F448_FN bool m448_is_identity(const M448Point& p) { return is_zero(p.x) && equal(p.y, p.z); }
-DR_F448_FN M448Point m448_cneg(const M448Point& p, bool negate) { return {cneg(p.x, negate), p.y, p.z}; }
+DR_L28_FN M448Point m448_identity() { return {F448::zero(), F448::small(1), F448::small(1)}; }
+DR_L28_FN bool m448_is_identity(const M448Point& p) { return is_zero(p.x) && equal(p.y, p.z); }
+DR_L28_FN M448Point m448_cneg(const M448Point& p, bool negate) { return {cneg(p.x, negate), p.y, p.z}; }
 
 // dbl-2008-bbjlp: coordinates n (x possibly negated: 1 n) in, n out
-DR_F448_FN M448Point m448_dbl(const M448Point& p) {
+DR_L28_FN M448Point m448_dbl(const M448Point& p) {
     const F448 B = sqr(carry(add(p.x, p.y)));                // (X + Y)^2: the sum carried to n
     const F448 C = sqr(p.x), D = sqr(p.y);                   // n
     const F448 E = mul_small(C, M448Consts::EDWARDS_A);      // a C: n
@@ -53,7 +53,7 @@ DR_F448_FN M448Point m448_dbl(const M448Point& p) {
 }
 
 // add-2008-bbjlp: unified and, d being a non-square and a a square, complete.  Coordinates n (x possibly negated: 1 n) in, n out
-DR_F448_FN M448Point m448_add(const M448Point& p, const M448Point& q) {
+DR_L28_FN M448Point m448_add(const M448Point& p, const M448Point& q) {
     const F448 A = mul(p.z, q.z);                                            // n
     const F448 B = sqr(A);                                                   // n
     const F448 C = mul(p.x, q.x), D = mul(p.y, q.y);                         // 1 n x 1 n, n x n: n
@@ -70,7 +70,7 @@ DR_F448_FN M448Point m448_add(const M448Point& p, const M448Point& q) {
 
 // the point of E_M for Montgomery (u, v), both n; `ident`: the identity flag of the input (u, v ignored).  No inversion:
 // (X : Y : Z) = (u (u - 1) : (u + 1) v : v (u - 1)); v = 0 is (0, 0) alone, (0 : -1 : 1)
-DR_F448_FN M448Point m448_load(const F448& u, const F448& v, bool ident) {
+DR_L28_FN M448Point m448_load(const F448& u, const F448& v, bool ident) {
     const F448 one = F448::small(1);
     const F448 um = carry(sub(u, one)), up = carry(add(u, one));             // n
     M448Point r;
@@ -84,7 +84,7 @@ DR_F448_FN M448Point m448_load(const F448& u, const F448& v, bool ident) {
 }
 // ... for u = N / D with D != 0 (the Elligator 2 map's fraction; N 1 n, D n, v 1 n): the same three products times D^2,
 // (N (N - D) : (N + D) v D : v (N - D) D)
-DR_F448_FN M448Point m448_load_fraction(const F448& N, const F448& D, const F448& v) {
+DR_L28_FN M448Point m448_load_fraction(const F448& N, const F448& D, const F448& v) {
     const F448 one = F448::small(1);
     const F448 nm = carry(sub(N, D)), np = carry(add(N, D));                 // n
     M448Point r;
@@ -99,7 +99,7 @@ DR_F448_FN M448Point m448_load_fraction(const F448& N, const F448& D, const F448
 }
 // Montgomery (u, v) of a point, one inversion: i = 1 / (X (Y - Z)), u = (Y + Z) X i, v = (Y + Z) Z i.  The identity (X = 0 and
 // Y = Z) returns true and u = v = 0; (0 : -1 : 1) gives (0, 0) through inv(0) = 0, as it must.  u, v: n
-DR_F448_FN bool m448_store(const M448Point& p, F448& u, F448& v) {
+DR_L28_FN bool m448_store(const M448Point& p, F448& u, F448& v) {
     const F448 ymz = carry(sub(p.y, p.z)), ypz = carry(add(p.y, p.z));       // n
     const F448 i = inv(mul(p.x, ymz));                                       // 1 n
     const F448 t = mul(ypz, i);                                              // n
@@ -110,19 +110,17 @@ DR_F448_FN bool m448_store(const M448Point& p, F448& u, F448& v) {
 
 // The law as the host side of dr_wide_msm takes it (wide_combine.hpp): the operations of the window combination and the ABI's u || v
 // words <-> a point; the identity is words of 0xffffffff, in and out (the Curve448 entry points' spelling)
-struct M448Law {
-    using Point = M448Point;
-    static constexpr int WORDS = W448, LIMBS = L448;
-    DR_F448_MEMBER static M448Point identity() { return m448_identity(); }
-    DR_F448_MEMBER static M448Point add(const M448Point& p, const M448Point& q) { return m448_add(p, q); }
-    DR_F448_MEMBER static M448Point dbl(const M448Point& p) { return m448_dbl(p); }
-    DR_F448_MEMBER static M448Point from_abi(const uint32_t (&w)[2 * W448]) {
+struct M448Law : Limb28Law<M448Law, M448Point> {
+    DR_L28_MEMBER static M448Point identity() { return m448_identity(); }
+    DR_L28_MEMBER static M448Point add(const M448Point& p, const M448Point& q) { return m448_add(p, q); }
+    DR_L28_MEMBER static M448Point dbl(const M448Point& p) { return m448_dbl(p); }
+    DR_L28_MEMBER static M448Point from_abi(const uint32_t (&w)[2 * W448]) {
         uint32_t u[W448], v[W448], o = 0xffffffffu;
         for (int j = 0; j < W448; j++) { u[j] = w[j]; v[j] = w[W448 + j]; o &= u[j] & v[j]; }
         if (o == 0xffffffffu) return m448_identity();
         return m448_load(unpack(u), unpack(v), false);
     }
-    DR_F448_MEMBER static void to_abi(const M448Point& p, uint32_t (&w)[2 * W448]) {
+    DR_L28_MEMBER static void to_abi(const M448Point& p, uint32_t (&w)[2 * W448]) {
         F448 u, v;
         const bool ident = m448_store(p, u, v);
         uint32_t uw[W448], vw[W448];
@@ -133,7 +131,7 @@ struct M448Law {
 };
 
 // v^2 = u^3 + A u^2 + u for u, v n (the decoder's test)
-DR_F448_FN bool m448_on_curve(const F448& u, const F448& v) {
+DR_L28_FN bool m448_on_curve(const F448& u, const F448& v) {
     const F448 ua = carry(add(u, F448::small(M448Consts::A)));               // n
     const F448 q = carry(add(mul(u, ua), F448::small(1)));                   // u (u + A) + 1: n
     return equal(sqr(v), mul(u, q));
@@ -143,7 +141,7 @@ DR_F448_FN bool m448_on_curve(const F448& u, const F448& v) {
 // inversion-free shape of appendix G.2.2 (p = 3 mod 4): the first half of kernels_ed448.hip.h's e448_ell2_map, whose comment derives
 // it.  The image is (N / D, v), D = 1 - u^2.  has_value = false exactly where u^2 = 1: the reference's comparison of a reduced value
 // with -1 never holds there, so it inverts 0 and raises.  u = 0 has the value (0, 0) (N = v = 0: gx1 = -A is a non-square).
-DR_F448_FN void m448_ell2(const F448& u /* n, canonical */, F448& N, F448& D, F448& v, bool& has_value) {
+DR_L28_FN void m448_ell2(const F448& u /* n, canonical */, F448& N, F448& D, F448& v, bool& has_value) {
     constexpr int32_t A = M448Consts::A;
     const F448 one = F448::small(1);
     F448 u2 = sqr(u);                                                        // -tv1: n

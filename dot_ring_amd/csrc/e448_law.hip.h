@@ -13,12 +13,12 @@ struct E448Point {
     F448 x, y, z;
 };
 
-DR_F448_FN E448Point e448_identity() { return {F448::zero(), F448::small(1), F448::small(1)}; }
-DR_F448_FN E448Point e448_from_affine(const F448& x, const F448& y) { return {x, y, F448::small(1)}; }
-DR_F448_FN bool e448_is_identity(const E448Point& p) { return is_zero(p.x) && equal(p.y, p.z); }
+DR_L28_FN E448Point e448_identity() { return {F448::zero(), F448::small(1), F448::small(1)}; }
+DR_L28_FN E448Point e448_from_affine(const F448& x, const F448& y) { return {x, y, F448::small(1)}; }
+DR_L28_FN bool e448_is_identity(const E448Point& p) { return is_zero(p.x) && equal(p.y, p.z); }
 
 // dbl-2007-bl, c = 1: coordinates n in, n out
-DR_F448_FN E448Point e448_dbl(const E448Point& p) {
+DR_L28_FN E448Point e448_dbl(const E448Point& p) {
     const F448 B = sqr(carry(add(p.x, p.y)));                // (X + Y)^2: the sum carried to n
     const F448 C = sqr(p.x), D = sqr(p.y);                   // n
     const F448 E = carry(add(C, D));                         // n
@@ -32,7 +32,7 @@ DR_F448_FN E448Point e448_dbl(const E448Point& p) {
 }
 
 // add-2007-bl, c = 1, a = 1: unified and, d being a non-square, complete.  Coordinates n (x possibly negated: 1 n) in, n out
-DR_F448_FN E448Point e448_add(const E448Point& p, const E448Point& q) {
+DR_L28_FN E448Point e448_add(const E448Point& p, const E448Point& q) {
     const F448 A = mul(p.z, q.z);                                            // n
     const F448 B = sqr(A);                                                   // n
     const F448 C = mul(p.x, q.x), D = mul(p.y, q.y);                         // n
@@ -46,28 +46,16 @@ DR_F448_FN E448Point e448_add(const E448Point& p, const E448Point& q) {
     r.z = mul(F, G);                                                         // 2 n x 1 n
     return r;
 }
-DR_F448_FN E448Point e448_cneg(const E448Point& p, bool negate) { return {cneg(p.x, negate), p.y, p.z}; }
+DR_L28_FN E448Point e448_cneg(const E448Point& p, bool negate) { return {cneg(p.x, negate), p.y, p.z}; }
 
 // The law as the host side of dr_wide_msm takes it (wide_combine.hpp): the operations of the window combination and the ABI's x || y
 // words <-> a point; the identity is (0, 1) as itself and Z is never 0
-struct E448Law {
-    using Point = E448Point;
-    static constexpr int WORDS = W448, LIMBS = L448;
-    DR_F448_MEMBER static E448Point identity() { return e448_identity(); }
-    DR_F448_MEMBER static E448Point add(const E448Point& p, const E448Point& q) { return e448_add(p, q); }
-    DR_F448_MEMBER static E448Point dbl(const E448Point& p) { return e448_dbl(p); }
-    DR_F448_MEMBER static E448Point from_abi(const uint32_t (&w)[2 * W448]) {
-        uint32_t x[W448], y[W448];
-        for (int j = 0; j < W448; j++) { x[j] = w[j]; y[j] = w[W448 + j]; }
-        return e448_from_affine(unpack(x), unpack(y));
-    }
-    DR_F448_MEMBER static void to_abi(const E448Point& p, uint32_t (&w)[2 * W448]) {
-        const F448 zi = inv(p.z);
-        uint32_t x[W448], y[W448];
-        pack(mul(p.x, zi), x);
-        pack(mul(p.y, zi), y);
-        for (int j = 0; j < W448; j++) { w[j] = x[j]; w[W448 + j] = y[j]; }
-    }
+struct E448Law : Limb28Law<E448Law, E448Point> {
+    static constexpr bool ZERO_IS_IDENTITY = false;
+    DR_L28_MEMBER static E448Point identity() { return e448_identity(); }
+    DR_L28_MEMBER static E448Point from_affine(const F448& x, const F448& y) { return e448_from_affine(x, y); }
+    DR_L28_MEMBER static E448Point add(const E448Point& p, const E448Point& q) { return e448_add(p, q); }
+    DR_L28_MEMBER static E448Point dbl(const E448Point& p) { return e448_dbl(p); }
 };
 
 }  // namespace dr

@@ -28,85 +28,39 @@
 // Plain integer C++: compiles for the device (hipcc) and for the host (g++, tests/native/ed448_field_host_check.cpp, where
 // -fsanitize=undefined turns a signed 64-bit column overflow into an abort).
 #pragma once
-#include <stdint.h>
-
 #include "divstep28.hip.h"
-
-#if defined(__HIPCC__)
-#define DR_F448_FN __host__ __device__ __forceinline__
-#define DR_F448_MEMBER __host__ __device__ __forceinline__
-#else
-#define DR_F448_FN static inline
-#define DR_F448_MEMBER inline
-#endif
+#include "limb28.hip.h"
 
 namespace dr {
 
 constexpr int L448 = 16;              // limbs
 constexpr int W448 = 14;              // 32-bit words of a canonical element
-constexpr int32_t M448 = 0x0fffffff;
+constexpr int32_t M448 = MASK28;
 constexpr int F448_DIVSTEP_BATCHES = 47;
 
+// the field's description for limb28.hip.h (its constants AND the members that header calls back: p_limb, small, unpack), which gives
+// the element type, the limb-wise operations, sqr_n, pack, is_zero, is_odd and equal
 struct Fe448Consts {
+    static constexpr int LIMBS = L448, WORDS = W448, TOP_BITS = 28;
     // p with a seventeenth (zero) limb, for the division steps
     static constexpr uint32_t P17[17] = {0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu, 0xffffffeu,
                                          0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu, 0};
     static constexpr int32_t EDWARDS_D_NEG = 39081;      // d = -39081
     static constexpr int32_t MONT_A = 156326;            // curve448: v^2 = u^3 + A u^2 + u
+    DR_L28_MEMBER static int32_t p_limb(int i) { return i == 8 ? M448 - 1 : M448; }
+    DR_L28_MEMBER static Limb28<Fe448Consts> small(int32_t v);
+    DR_L28_MEMBER static Limb28<Fe448Consts> unpack(const uint32_t (&w)[WORDS]);
 };
+using F448 = Limb28<Fe448Consts>;
 
-struct F448 {
-    int32_t l[L448];
-    DR_F448_MEMBER static F448 zero() {
-        F448 r;
-#pragma unroll
-        for (int i = 0; i < L448; i++) r.l[i] = 0;
-        return r;
-    }
-    DR_F448_MEMBER static F448 small(int32_t v) {            // |v| < 2^28
-        F448 r = zero();
-        r.l[0] = v;
-        return r;
-    }
-};
-
-DR_F448_FN int32_t f448_p_limb(int i) { return i == 8 ? M448 - 1 : M448; }
-
-DR_F448_FN F448 add(const F448& a, const F448& b) {
-    F448 r;
-#pragma unroll
-    for (int i = 0; i < L448; i++) r.l[i] = a.l[i] + b.l[i];
-    return r;
-}
-DR_F448_FN F448 sub(const F448& a, const F448& b) {
-    F448 r;
-#pragma unroll
-    for (int i = 0; i < L448; i++) r.l[i] = a.l[i] - b.l[i];
-    return r;
-}
-DR_F448_FN F448 dbl(const F448& a) { return add(a, a); }
-DR_F448_FN F448 neg(const F448& a) {
-    F448 r;
-#pragma unroll
-    for (int i = 0; i < L448; i++) r.l[i] = -a.l[i];
-    return r;
-}
-DR_F448_FN F448 cneg(const F448& a, bool negate) {      // negate ? -a : a
-    const int32_t s = negate ? -1 : 0;
-    F448 r;
-#pragma unroll
-    for (int i = 0; i < L448; i++) r.l[i] = (a.l[i] ^ s) - s;
-    return r;
-}
-DR_F448_FN F448 select(bool c, const F448& a, const F448& b) {   // c ? a : b
-    F448 r;
-#pragma unroll
-    for (int i = 0; i < L448; i++) r.l[i] = c ? a.l[i] : b.l[i];
+DR_L28_MEMBER F448 Fe448Consts::small(int32_t v) {           // |v| < 2^28
+    F448 r = F448::zero();
+    r.l[0] = v;
     return r;
 }
 
 // any limbs with |l_i| < 2^31 - 2^5 -> normal: one ripple, the carry out of limb 15 (|c| <= 8) folded onto limbs 0 and 8
-DR_F448_FN F448 carry(const F448& a) {
+DR_L28_FN F448 carry(const F448& a) {
     F448 r;
     int32_t c = 0;
 #pragma unroll
@@ -122,7 +76,7 @@ DR_F448_FN F448 carry(const F448& a) {
 
 // sixteen signed 64-bit columns (|r_i| < 2^63 - 2^40) -> normal.  The carry out of column 15 (|c| < 2^36) goes onto limbs 0 and 8, whose
 // own carries (|c| <= 2^8 + 1) are left on limbs 1 and 9.
-DR_F448_FN F448 f448_carry64(const int64_t (&r)[L448]) {
+DR_L28_FN F448 f448_carry64(const int64_t (&r)[L448]) {
     F448 o;
     int64_t c = 0;
 #pragma unroll
@@ -140,7 +94,7 @@ DR_F448_FN F448 f448_carry64(const int64_t (&r)[L448]) {
 }
 
 // a b: 256 multiply-adds.  Contract at the head of the file.
-DR_F448_FN F448 mul(const F448& a, const F448& b) {
+DR_L28_FN F448 mul(const F448& a, const F448& b) {
     int64_t r[L448];
 #pragma unroll
     for (int j = 0; j < 8; j++) {
@@ -159,7 +113,7 @@ DR_F448_FN F448 mul(const F448& a, const F448& b) {
 }
 
 // a^2: the off-diagonal products once, against the doubled operand (136 multiply-adds)
-DR_F448_FN F448 sqr(const F448& a) {
+DR_L28_FN F448 sqr(const F448& a) {
     int32_t a2[L448];
 #pragma unroll
     for (int i = 0; i < L448; i++) a2[i] = 2 * a.l[i];
@@ -182,14 +136,9 @@ DR_F448_FN F448 sqr(const F448& a) {
     }
     return f448_carry64(r);
 }
-DR_F448_FN F448 sqr_n(F448 a, int n) {
-#pragma unroll 1
-    for (int i = 0; i < n; i++) a = sqr(a);
-    return a;
-}
 
 // k a for a small constant k (39081, 156326): |a_i| k < 2^62
-DR_F448_FN F448 mul_small(const F448& a, int32_t k) {
+DR_L28_FN F448 mul_small(const F448& a, int32_t k) {
     int64_t r[L448];
 #pragma unroll
     for (int i = 0; i < L448; i++) r[i] = (int64_t)a.l[i] * k;
@@ -197,62 +146,13 @@ DR_F448_FN F448 mul_small(const F448& a, int32_t k) {
 }
 
 // ---------------------------------------------------------------- canonical form: 14 x u32 words, value in [0, p)
-// the limbs of the representative in [0, p), each in [0, 2^28).  carry() leaves a value in (-2^229, 2^448 + 2^229); + p is positive and
-// below 3 p, so p is taken off twice where it fits.
-DR_F448_FN void f448_canon_limbs(const F448& a, int32_t (&u)[L448]) {
-    const F448 x = carry(a);
-    int32_t c = 0;
-#pragma unroll
-    for (int i = 0; i < L448; i++) {
-        const int32_t t = x.l[i] + f448_p_limb(i) + c;
-        u[i] = t & M448;
-        c = t >> 28;
-    }
-    int32_t top = c;                                    // 0, 1 or 2
-#pragma unroll
-    for (int pass = 0; pass < 2; pass++) {
-        int32_t d[L448];
-        c = 0;
-#pragma unroll
-        for (int i = 0; i < L448; i++) {
-            const int32_t t = u[i] - f448_p_limb(i) + c;
-            d[i] = t & M448;
-            c = t >> 28;
-        }
-        const int32_t dt = top + c;
-        const bool take = dt >= 0;
-#pragma unroll
-        for (int i = 0; i < L448; i++) u[i] = take ? d[i] : u[i];
-        top = take ? dt : top;
-    }
-}
-DR_F448_FN void pack(const F448& a, uint32_t (&w)[W448]) {
-    int32_t u[L448];
-    f448_canon_limbs(a, u);
-#pragma unroll
-    for (int j = 0; j < W448; j++) w[j] = 0;
-#pragma unroll
-    for (int i = 0; i < L448; i++) {
-        const int bit = 28 * i, j = bit >> 5, sh = bit & 31;
-        const uint32_t v = (uint32_t)u[i];
-        w[j] |= v << sh;
-        if (sh > 4 && j + 1 < W448) w[j + 1] |= v >> (32 - sh);
-    }
-}
+// (canon_limbs, the limbs of the representative in [0, p), each in [0, 2^28), is limb28.hip.h's: carry() leaves a value in
+// (-2^229, 2^448 + 2^229); + p is positive and below 3 p.  pack is that header's over it.)
 // words -> limbs (no arithmetic: the value is reinterpreted in radix 2^28); any 448-bit value, normal out
-DR_F448_FN F448 unpack(const uint32_t (&w)[W448]) {
-    F448 r;
-#pragma unroll
-    for (int i = 0; i < L448; i++) {
-        const int bit = 28 * i, j = bit >> 5, sh = bit & 31;
-        uint32_t v = w[j] >> sh;
-        if (sh > 4 && j + 1 < W448) v |= w[j + 1] << (32 - sh);
-        r.l[i] = (int32_t)(v & (uint32_t)M448);
-    }
-    return r;
-}
+DR_L28_MEMBER F448 Fe448Consts::unpack(const uint32_t (&w)[W448]) { return limbs_of_words<Fe448Consts>(w); }
+DR_L28_FN F448 unpack(const uint32_t (&w)[W448]) { return Fe448Consts::unpack(w); }
 // whether 14 words are below p = ff..ff fffffffe ff..ff (word 7 is the odd one)
-DR_F448_FN bool below_p(const uint32_t (&w)[W448]) {
+DR_L28_FN bool below_p(const uint32_t (&w)[W448]) {
     uint32_t hi = 0xffffffffu, lo = 0xffffffffu;
 #pragma unroll
     for (int j = 8; j < W448; j++) hi &= w[j];
@@ -261,25 +161,12 @@ DR_F448_FN bool below_p(const uint32_t (&w)[W448]) {
     const bool geq = hi == 0xffffffffu && (w[7] == 0xffffffffu || (w[7] == 0xfffffffeu && lo == 0xffffffffu));
     return !geq;
 }
-DR_F448_FN bool is_zero(const F448& a) {
-    int32_t u[L448], acc = 0;
-    f448_canon_limbs(a, u);
-#pragma unroll
-    for (int i = 0; i < L448; i++) acc |= u[i];
-    return acc == 0;
-}
-DR_F448_FN bool is_odd(const F448& a) {                 // of the canonical value
-    int32_t u[L448];
-    f448_canon_limbs(a, u);
-    return (u[0] & 1) != 0;
-}
-DR_F448_FN bool equal(const F448& a, const F448& b) { return is_zero(sub(a, b)); }
 
 // ---------------------------------------------------------------- inversion and roots
 // a^-1 (0 -> 0): a lazy value with |limb| < 2^28 + 2^5 (1 n), |value| < 24.5 p
-DR_F448_FN F448 inv(const F448& a) {
+DR_L28_FN F448 inv(const F448& a) {
     int32_t u[L448], x[17], out[17];
-    f448_canon_limbs(a, u);
+    canon_limbs(a, u);
 #pragma unroll
     for (int i = 0; i < L448; i++) x[i] = u[i];
     x[16] = 0;
@@ -292,7 +179,7 @@ DR_F448_FN F448 inv(const F448& a) {
     return r;
 }
 // a^((p - 3) / 4) = a^(2^446 - 2^222 - 1): with x_k = a^(2^k - 1), x_223^(2^223) x_222.  445 squarings and 12 products; a: 1 n
-DR_F448_FN F448 f448_pow_p34(const F448& a) {
+DR_L28_FN F448 f448_pow_p34(const F448& a) {
     const F448 x2 = mul(sqr(a), a);
     const F448 x3 = mul(sqr(x2), a);
     const F448 x6 = mul(sqr_n(x3, 3), x3);
@@ -307,7 +194,7 @@ DR_F448_FN F448 f448_pow_p34(const F448& a) {
     return mul(sqr_n(x223, 223), x222);
 }
 // r = a^((p + 1) / 4); true iff r^2 = a (a is a square, 0 included).  a: 1 n
-DR_F448_FN bool f448_sqrt(const F448& a, F448& r) {
+DR_L28_FN bool f448_sqrt(const F448& a, F448& r) {
     r = mul(f448_pow_p34(a), a);
     return equal(sqr(r), a);
 }

@@ -33,7 +33,7 @@
 // up (h, signed, |h| <= 64 for 32 n) with 2^384 = 2^128 + 2^96 - 2^32 + 1 (mod p): h, -h 2^4, h 2^12, h 2^16 onto limbs 0, 1, 3, 4.  One
 // class then describes limbs and value together, as in fp521.hip.h.
 //
-// CANONICAL VALUES.  pack, is_zero, is_odd and equal work on the element itself, a R^-1 mod p: f384_canon_limbs runs the fourteen steps
+// CANONICAL VALUES.  pack, is_zero, is_odd and equal work on the element itself, a R^-1 mod p: canon_limbs runs the fourteen steps
 // on the limbs alone (T in (-9, p + 9) for limbs below 2^31), adds p and takes p off twice where it fits.  Limbs that spell p, p + 1 or
 // 2^384 therefore come out as the elements 0, R^-1 and 2^384 R^-1.
 //
@@ -47,26 +47,20 @@
 // Plain integer C++: compiles for the device (hipcc) and for the host (g++, tests/native/p384_host_check.cpp, where
 // -fsanitize=undefined turns a signed 64-bit column overflow into an abort).
 #pragma once
-#include <stdint.h>
-
 #include "divstep28.hip.h"
-
-#if defined(__HIPCC__)
-#define DR_F384_FN __host__ __device__ __forceinline__
-#define DR_F384_MEMBER __host__ __device__ __forceinline__
-#else
-#define DR_F384_FN static inline
-#define DR_F384_MEMBER inline
-#endif
+#include "limb28.hip.h"
 
 namespace dr {
 
 constexpr int L384 = 14;              // limbs
 constexpr int W384 = 12;              // 32-bit words of a canonical element
-constexpr int32_t M384 = 0x0fffffff;  // a 28-bit limb
+constexpr int32_t M384 = MASK28;      // a 28-bit limb
 constexpr int F384_DIVSTEP_BATCHES = 40;
 
+// the field's description for limb28.hip.h (its constants AND the members that header calls back: small, unpack, reduce), which gives
+// the element type, the limb-wise operations, the column products mul, mul2 and sqr over reduce, sqr_n, pack, is_zero, is_odd and equal
 struct Fp384Consts {
+    static constexpr int LIMBS = L384, WORDS = W384;
     // p, R^2 mod p, b R mod p (b of y^2 = x^3 - 3 x + b) and sqrt(12) R mod p in canonical 28-bit limbs
     static constexpr uint32_t P14[14] = {0xfffffffu, 0x000000fu, 0x0000000u, 0xffff000u, 0xffeffffu, 0xfffffffu, 0xfffffffu,
                                          0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu, 0x00fffffu};
@@ -79,69 +73,24 @@ struct Fp384Consts {
     // p as little-endian words
     static constexpr uint32_t PW[12] = {0xffffffffu, 0x00000000u, 0x00000000u, 0xffffffffu, 0xfffffffeu, 0xffffffffu,
                                         0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
+    DR_L28_MEMBER static Limb28<Fp384Consts> small(int32_t v);
+    DR_L28_MEMBER static Limb28<Fp384Consts> reduce(int64_t (&c)[2 * LIMBS - 1]);
+    DR_L28_MEMBER static Limb28<Fp384Consts> unpack(const uint32_t (&w)[WORDS]);
 };
+using F384 = Limb28<Fp384Consts>;
 
-struct F384 {
-    int32_t l[L384];
-    DR_F384_MEMBER static F384 zero() {
-        F384 r;
-#pragma unroll
-        for (int i = 0; i < L384; i++) r.l[i] = 0;
-        return r;
-    }
-    // the element v for |v| <= 15: v R mod p with R = 2^392 = 2^8 - 2^12 B + 2^20 B^3 + 2^24 B^4 (mod p) in signed limbs; 1 n
-    DR_F384_MEMBER static F384 small(int32_t v) {
-        F384 r = zero();
-        r.l[0] = v * (1 << 8);
-        r.l[1] = -v * (1 << 12);
-        r.l[3] = v * (1 << 20);
-        r.l[4] = v * (1 << 24);
-        return r;
-    }
-    template <const int32_t (&C)[L384]>
-    DR_F384_MEMBER static F384 constant() {
-        F384 r;
-#pragma unroll
-        for (int i = 0; i < L384; i++) r.l[i] = C[i];
-        return r;
-    }
-};
-
-DR_F384_FN F384 add(const F384& a, const F384& b) {
-    F384 r;
-#pragma unroll
-    for (int i = 0; i < L384; i++) r.l[i] = a.l[i] + b.l[i];
-    return r;
-}
-DR_F384_FN F384 sub(const F384& a, const F384& b) {
-    F384 r;
-#pragma unroll
-    for (int i = 0; i < L384; i++) r.l[i] = a.l[i] - b.l[i];
-    return r;
-}
-DR_F384_FN F384 dbl(const F384& a) { return add(a, a); }
-DR_F384_FN F384 neg(const F384& a) {
-    F384 r;
-#pragma unroll
-    for (int i = 0; i < L384; i++) r.l[i] = -a.l[i];
-    return r;
-}
-DR_F384_FN F384 cneg(const F384& a, bool negate) {      // negate ? -a : a
-    const int32_t s = negate ? -1 : 0;
-    F384 r;
-#pragma unroll
-    for (int i = 0; i < L384; i++) r.l[i] = (a.l[i] ^ s) - s;
-    return r;
-}
-DR_F384_FN F384 select(bool c, const F384& a, const F384& b) {   // c ? a : b
-    F384 r;
-#pragma unroll
-    for (int i = 0; i < L384; i++) r.l[i] = c ? a.l[i] : b.l[i];
+// the element v for |v| <= 15: v R mod p with R = 2^392 = 2^8 - 2^12 B + 2^20 B^3 + 2^24 B^4 (mod p) in signed limbs; 1 n
+DR_L28_MEMBER F384 Fp384Consts::small(int32_t v) {
+    F384 r = F384::zero();
+    r.l[0] = v * (1 << 8);
+    r.l[1] = -v * (1 << 12);
+    r.l[3] = v * (1 << 20);
+    r.l[4] = v * (1 << 24);
     return r;
 }
 
 // any limbs with |l_i| < 2^31 - 2^5: one ripple, then the bits of limb 13 from 2^384 up folded onto limbs 0, 1, 3, 4 (head of the file)
-DR_F384_FN F384 carry(const F384& a) {
+DR_L28_FN F384 carry(const F384& a) {
     F384 r;
     int32_t c = 0;
 #pragma unroll
@@ -161,7 +110,7 @@ DR_F384_FN F384 carry(const F384& a) {
 }
 
 // columns c_0..c_26 -> (sum c_k 2^(28 k)) / 2^392 mod p: the fourteen steps, then c_14..c_26 carried.  n out under mul's contract.
-DR_F384_FN F384 f384_redc(int64_t (&c)[2 * L384 - 1]) {
+DR_L28_MEMBER F384 Fp384Consts::reduce(int64_t (&c)[2 * L384 - 1]) {
 #pragma unroll
     for (int k = 0; k < L384; k++) {
         const int64_t v = c[k];
@@ -182,59 +131,12 @@ DR_F384_FN F384 f384_redc(int64_t (&c)[2 * L384 - 1]) {
     return r;
 }
 
-// a b R^-1: 196 multiply-adds.  Contract and step at the head of the file.
-DR_F384_FN F384 mul(const F384& a, const F384& b) {
-    int64_t c[2 * L384 - 1];
-#pragma unroll
-    for (int j = 0; j < 2 * L384 - 1; j++) {
-        int64_t s = 0;
-#pragma unroll
-        for (int i = 0; i < L384; i++)
-            if (j - i >= 0 && j - i < L384) s += (int64_t)a.l[i] * b.l[j - i];
-        c[j] = s;
-    }
-    return f384_redc(c);
-}
-// (a b + c d) R^-1 with one reduction: 392 multiply-adds; ka kb + kc kd <= 8
-DR_F384_FN F384 mul2(const F384& a, const F384& b, const F384& c, const F384& d) {
-    int64_t col[2 * L384 - 1];
-#pragma unroll
-    for (int j = 0; j < 2 * L384 - 1; j++) {
-        int64_t s = 0;
-#pragma unroll
-        for (int i = 0; i < L384; i++)
-            if (j - i >= 0 && j - i < L384) s += (int64_t)a.l[i] * b.l[j - i] + (int64_t)c.l[i] * d.l[j - i];
-        col[j] = s;
-    }
-    return f384_redc(col);
-}
-// a^2 R^-1: the off-diagonal products once, against the doubled operand (105 multiply-adds); a <= 2 n
-DR_F384_FN F384 sqr(const F384& a) {
-    int32_t a2[L384];
-#pragma unroll
-    for (int i = 0; i < L384; i++) a2[i] = 2 * a.l[i];
-    int64_t c[2 * L384 - 1];
-#pragma unroll
-    for (int j = 0; j < 2 * L384 - 1; j++) {
-        int64_t s = 0;
-#pragma unroll
-        for (int i = 0; i < L384; i++) {
-            const int m = j - i;
-            if (m >= i && m < L384) s += i == m ? (int64_t)a.l[i] * a.l[i] : (int64_t)a2[i] * a.l[m];
-        }
-        c[j] = s;
-    }
-    return f384_redc(c);
-}
-DR_F384_FN F384 sqr_n(F384 a, int n) {
-#pragma unroll 1
-    for (int i = 0; i < n; i++) a = sqr(a);
-    return a;
-}
+// The products are limb28.hip.h's over reduce: mul(a, b) = a b R^-1 (196 multiply-adds; contract and step at the head of the file),
+// mul2(a, b, c, d) = (a b + c d) R^-1 with one reduction (392; ka kb + kc kd <= 8) and sqr(a) = a^2 R^-1 (105; a <= 2 n).
 
 // k a for a small constant k: |a_i| k < 2^62.  The columns ripple in 64 bits, the bits from 2^384 up (|h| < 2^43) fold as in carry, the
 // limbs ripple again and what is left above 2^384 (|h| <= 2) folds without a ripple: n out
-DR_F384_FN F384 mul_small(const F384& a, int32_t k) {
+DR_L28_FN F384 mul_small(const F384& a, int32_t k) {
     int64_t t[L384];
     int64_t c = 0;
 #pragma unroll
@@ -271,11 +173,11 @@ DR_F384_FN F384 mul_small(const F384& a, int32_t k) {
 // ---------------------------------------------------------------- canonical form: 12 x u32 words, value in [0, p)
 // the limbs of the ELEMENT a stands for, a R^-1 mod p, in [0, p): limbs 0..12 in [0, 2^28), limb 13 in [0, 2^20).  The fourteen steps on
 // the limbs alone give T in (-9, p + 9); T + p is positive and below 3 p, so p is taken off twice where it fits.
-DR_F384_FN void f384_canon_limbs(const F384& a, int32_t (&u)[L384]) {
+DR_L28_FN void canon_limbs(const F384& a, int32_t (&u)[L384]) {
     int64_t col[2 * L384 - 1];
 #pragma unroll
     for (int k = 0; k < 2 * L384 - 1; k++) col[k] = k < L384 ? (int64_t)a.l[k] : 0;
-    const F384 t = f384_redc(col);
+    const F384 t = Fp384Consts::reduce(col);
     int32_t c = 0;
 #pragma unroll
     for (int i = 0; i < L384 - 1; i++) {
@@ -300,21 +202,11 @@ DR_F384_FN void f384_canon_limbs(const F384& a, int32_t (&u)[L384]) {
         for (int i = 0; i < L384; i++) u[i] = take ? d[i] : u[i];
     }
 }
-DR_F384_FN void pack(const F384& a, uint32_t (&w)[W384]) {
-    int32_t u[L384];
-    f384_canon_limbs(a, u);
-#pragma unroll
-    for (int j = 0; j < W384; j++) w[j] = 0;
-#pragma unroll
-    for (int i = 0; i < L384; i++) {
-        const int bit = 28 * i, j = bit >> 5, sh = bit & 31;
-        const uint32_t v = (uint32_t)u[i];
-        w[j] |= v << sh;
-        if (sh > 4 && j + 1 < W384) w[j + 1] |= v >> (32 - sh);
-    }
-}
+// (pack is limb28.hip.h's over canon_limbs)
 // words (any value below 2^384) -> the element in Montgomery form: the value reinterpreted in radix 2^28 (limb 13 below 2^20) times R^2
-DR_F384_FN F384 unpack(const uint32_t (&w)[W384]) {
+// (the loop is limb28.hip.h's limbs_of_words, kept in place: through the shared routine the compiler orders the product that follows
+// differently in four P-384 kernels — same counts)
+DR_L28_MEMBER F384 Fp384Consts::unpack(const uint32_t (&w)[W384]) {
     F384 r;
 #pragma unroll
     for (int i = 0; i < L384; i++) {
@@ -323,10 +215,11 @@ DR_F384_FN F384 unpack(const uint32_t (&w)[W384]) {
         if (sh > 4 && j + 1 < W384) v |= w[j + 1] << (32 - sh);
         r.l[i] = (int32_t)(v & (uint32_t)M384);
     }
-    return mul(r, F384::constant<Fp384Consts::R2>());
+    return mul(r, F384::constant<R2>());
 }
+DR_L28_FN F384 unpack(const uint32_t (&w)[W384]) { return Fp384Consts::unpack(w); }
 // whether 12 words are below p
-DR_F384_FN bool below_p(const uint32_t (&w)[W384]) {
+DR_L28_FN bool below_p(const uint32_t (&w)[W384]) {
     bool lt = false, eq = true;
 #pragma unroll
     for (int j = W384 - 1; j >= 0; j--) {
@@ -335,24 +228,11 @@ DR_F384_FN bool below_p(const uint32_t (&w)[W384]) {
     }
     return lt;
 }
-DR_F384_FN bool is_zero(const F384& a) {
-    int32_t u[L384], acc = 0;
-    f384_canon_limbs(a, u);
-#pragma unroll
-    for (int i = 0; i < L384; i++) acc |= u[i];
-    return acc == 0;
-}
-DR_F384_FN bool is_odd(const F384& a) {                 // of the canonical element (sgn0)
-    int32_t u[L384];
-    f384_canon_limbs(a, u);
-    return (u[0] & 1) != 0;
-}
-DR_F384_FN bool equal(const F384& a, const F384& b) { return is_zero(sub(a, b)); }
 
 // ---------------------------------------------------------------- inversion and roots
 // a^((p - 3) / 4): with x_k = a^(2^k - 1), x255 from x2, x3, x6, x12, x15, x30, x60, x120, x240, then a zero bit, x32, 64 zero bits
 // and x30.  381 squarings and 13 products; a: 1 n
-DR_F384_FN F384 f384_pow_p34(const F384& a) {
+DR_L28_FN F384 f384_pow_p34(const F384& a) {
     const F384 x2 = mul(sqr(a), a);
     const F384 x3 = mul(sqr(x2), a);
     const F384 x6 = mul(sqr_n(x3, 3), x3);
@@ -369,9 +249,9 @@ DR_F384_FN F384 f384_pow_p34(const F384& a) {
 }
 // a^-1 (0 -> 0) by division steps on the canonical element, back into Montgomery form by the product with R^2 (1 n of value class 16
 // times n); n out
-DR_F384_FN F384 inv(const F384& a) {
+DR_L28_FN F384 inv(const F384& a) {
     int32_t x[L384], out[L384];
-    f384_canon_limbs(a, x);
+    canon_limbs(a, x);
     inv_divsteps<L384, 28, F384_DIVSTEP_BATCHES>(Fp384Consts::P14, 1u, x, out);
     F384 r;
 #pragma unroll
@@ -379,9 +259,9 @@ DR_F384_FN F384 inv(const F384& a) {
     return mul(r, F384::constant<Fp384Consts::R2>());
 }
 // a^-1 (0 -> 0) as a^(p - 2) = (a^((p - 3) / 4))^4 a; a: 1 n, n out
-DR_F384_FN F384 f384_inv_chain(const F384& a) { return mul(sqr_n(f384_pow_p34(a), 2), a); }
+DR_L28_FN F384 f384_inv_chain(const F384& a) { return mul(sqr_n(f384_pow_p34(a), 2), a); }
 // r = a^((p + 1) / 4); true iff r^2 = a (a is a square, 0 included).  a: 1 n
-DR_F384_FN bool f384_sqrt(const F384& a, F384& r) {
+DR_L28_FN bool f384_sqrt(const F384& a, F384& r) {
     r = mul(f384_pow_p34(a), a);
     return equal(sqr(r), a);
 }

@@ -20,7 +20,7 @@
 // out of limb 18 is taken at bit 17 (2^521 = 1) and rippled through limbs 0 and 1, its last bit left on limb 2.
 // The product is schoolbook, 361 multiply-adds (sqr: 190).
 //
-// ZERO HAS TWO IMAGES, 0 and p (all limbs full).  pack, is_zero, is_odd and equal work on the canonical value: f521_canon_limbs carries,
+// ZERO HAS TWO IMAGES, 0 and p (all limbs full).  pack, is_zero, is_odd and equal work on the canonical value: canon_limbs carries,
 // adds p (the sum is positive and below 3 p) and takes p off twice where it fits, so limbs that spell p, p + 1 or 2^521 come out as 0, 1
 // and 1.
 //
@@ -35,83 +35,37 @@
 // Plain integer C++: compiles for the device (hipcc) and for the host (g++, tests/native/p521_host_check.cpp, where
 // -fsanitize=undefined turns a signed 64-bit column overflow into an abort).
 #pragma once
-#include <stdint.h>
-
 #include "divstep28.hip.h"
-
-#if defined(__HIPCC__)
-#define DR_F521_FN __host__ __device__ __forceinline__
-#define DR_F521_MEMBER __host__ __device__ __forceinline__
-#else
-#define DR_F521_FN static inline
-#define DR_F521_MEMBER inline
-#endif
+#include "limb28.hip.h"
 
 namespace dr {
 
 constexpr int L521 = 19;              // limbs
 constexpr int W521 = 17;              // 32-bit words of a canonical element
-constexpr int32_t M521 = 0x0fffffff;  // a 28-bit limb
+constexpr int32_t M521 = MASK28;      // a 28-bit limb
 constexpr int32_t T521 = 0x0001ffff;  // the 17 bits of limb 18
 constexpr int F521_DIVSTEP_BATCHES = 54;
 
+// the field's description for limb28.hip.h (its constants AND the members that header calls back: p_limb, small, unpack), which gives
+// the element type, the limb-wise operations, sqr_n, pack, is_zero, is_odd and equal
 struct Fp521Consts {
+    static constexpr int LIMBS = L521, WORDS = W521, TOP_BITS = 17;
     static constexpr uint32_t P19[19] = {0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu,
                                          0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu, 0xfffffffu, 0x1ffffu};
+    DR_L28_MEMBER static int32_t p_limb(int i) { return i == LIMBS - 1 ? T521 : M521; }
+    DR_L28_MEMBER static Limb28<Fp521Consts> small(int32_t v);
+    DR_L28_MEMBER static Limb28<Fp521Consts> unpack(const uint32_t (&w)[WORDS]);
 };
+using F521 = Limb28<Fp521Consts>;
 
-struct F521 {
-    int32_t l[L521];
-    DR_F521_MEMBER static F521 zero() {
-        F521 r;
-#pragma unroll
-        for (int i = 0; i < L521; i++) r.l[i] = 0;
-        return r;
-    }
-    DR_F521_MEMBER static F521 small(int32_t v) {            // |v| < 2^28
-        F521 r = zero();
-        r.l[0] = v;
-        return r;
-    }
-};
-
-DR_F521_FN int32_t f521_p_limb(int i) { return i == L521 - 1 ? T521 : M521; }
-
-DR_F521_FN F521 add(const F521& a, const F521& b) {
-    F521 r;
-#pragma unroll
-    for (int i = 0; i < L521; i++) r.l[i] = a.l[i] + b.l[i];
-    return r;
-}
-DR_F521_FN F521 sub(const F521& a, const F521& b) {
-    F521 r;
-#pragma unroll
-    for (int i = 0; i < L521; i++) r.l[i] = a.l[i] - b.l[i];
-    return r;
-}
-DR_F521_FN F521 dbl(const F521& a) { return add(a, a); }
-DR_F521_FN F521 neg(const F521& a) {
-    F521 r;
-#pragma unroll
-    for (int i = 0; i < L521; i++) r.l[i] = -a.l[i];
-    return r;
-}
-DR_F521_FN F521 cneg(const F521& a, bool negate) {      // negate ? -a : a
-    const int32_t s = negate ? -1 : 0;
-    F521 r;
-#pragma unroll
-    for (int i = 0; i < L521; i++) r.l[i] = (a.l[i] ^ s) - s;
-    return r;
-}
-DR_F521_FN F521 select(bool c, const F521& a, const F521& b) {   // c ? a : b
-    F521 r;
-#pragma unroll
-    for (int i = 0; i < L521; i++) r.l[i] = c ? a.l[i] : b.l[i];
+DR_L28_MEMBER F521 Fp521Consts::small(int32_t v) {           // |v| < 2^28
+    F521 r = F521::zero();
+    r.l[0] = v;
     return r;
 }
 
 // any limbs with |l_i| < 2^31 - 2^5 -> normal: one ripple, the carry out of limb 18 taken at bit 17 (|c| < 2^14 + 1) onto limb 0
-DR_F521_FN F521 carry(const F521& a) {
+DR_L28_FN F521 carry(const F521& a) {
     F521 r;
     int32_t c = 0;
 #pragma unroll
@@ -128,7 +82,7 @@ DR_F521_FN F521 carry(const F521& a) {
 
 // nineteen signed 64-bit columns (|r_i| < 2^63 - 2^37) -> normal.  The carry out of column 18 (bit 17 up, |c| < 2^46) goes onto limb 0,
 // whose carry (|c| < 2^19) goes onto limb 1, whose carry (-1, 0 or 1) is left on limb 2.
-DR_F521_FN F521 f521_carry64(const int64_t (&r)[L521]) {
+DR_L28_FN F521 f521_carry64(const int64_t (&r)[L521]) {
     F521 o;
     int64_t c = 0;
 #pragma unroll
@@ -148,7 +102,7 @@ DR_F521_FN F521 f521_carry64(const int64_t (&r)[L521]) {
 }
 
 // a b: 361 multiply-adds.  Contract and fold at the head of the file.
-DR_F521_FN F521 mul(const F521& a, const F521& b) {
+DR_L28_FN F521 mul(const F521& a, const F521& b) {
     int64_t r[L521];
     int64_t up = 0;                                     // floor(c / 2^17) of the high column before
 #pragma unroll
@@ -166,7 +120,7 @@ DR_F521_FN F521 mul(const F521& a, const F521& b) {
 }
 
 // a^2: the off-diagonal products once, against the doubled operand (190 multiply-adds); a <= 2 n
-DR_F521_FN F521 sqr(const F521& a) {
+DR_L28_FN F521 sqr(const F521& a) {
     int32_t a2[L521];
 #pragma unroll
     for (int i = 0; i < L521; i++) a2[i] = 2 * a.l[i];
@@ -186,14 +140,9 @@ DR_F521_FN F521 sqr(const F521& a) {
     }
     return f521_carry64(r);
 }
-DR_F521_FN F521 sqr_n(F521 a, int n) {
-#pragma unroll 1
-    for (int i = 0; i < n; i++) a = sqr(a);
-    return a;
-}
 
 // k a for a small constant k: |a_i| k < 2^62
-DR_F521_FN F521 mul_small(const F521& a, int32_t k) {
+DR_L28_FN F521 mul_small(const F521& a, int32_t k) {
     int64_t r[L521];
 #pragma unroll
     for (int i = 0; i < L521; i++) r[i] = (int64_t)a.l[i] * k;
@@ -201,86 +150,24 @@ DR_F521_FN F521 mul_small(const F521& a, int32_t k) {
 }
 
 // ---------------------------------------------------------------- canonical form: 17 x u32 words, value in [0, p)
-// the limbs of the representative in [0, p), limbs 0..17 in [0, 2^28), limb 18 in [0, 2^17).  carry() leaves a value in
-// (-2^14, 2^521 + 2^14); + p is positive and below 3 p, so p is taken off twice where it fits.
-DR_F521_FN void f521_canon_limbs(const F521& a, int32_t (&u)[L521]) {
-    const F521 x = carry(a);
-    int32_t c = 0;
-#pragma unroll
-    for (int i = 0; i < L521; i++) {
-        const int32_t t = x.l[i] + f521_p_limb(i) + c;
-        u[i] = t & f521_p_limb(i);
-        c = t >> (i == L521 - 1 ? 17 : 28);
-    }
-    int32_t top = c;                                    // 0, 1 or 2
-#pragma unroll
-    for (int pass = 0; pass < 2; pass++) {
-        int32_t d[L521];
-        c = 0;
-#pragma unroll
-        for (int i = 0; i < L521; i++) {
-            const int32_t t = u[i] - f521_p_limb(i) + c;
-            d[i] = t & f521_p_limb(i);
-            c = t >> (i == L521 - 1 ? 17 : 28);
-        }
-        const int32_t dt = top + c;
-        const bool take = dt >= 0;
-#pragma unroll
-        for (int i = 0; i < L521; i++) u[i] = take ? d[i] : u[i];
-        top = take ? dt : top;
-    }
-}
-DR_F521_FN void pack(const F521& a, uint32_t (&w)[W521]) {
-    int32_t u[L521];
-    f521_canon_limbs(a, u);
-#pragma unroll
-    for (int j = 0; j < W521; j++) w[j] = 0;
-#pragma unroll
-    for (int i = 0; i < L521; i++) {
-        const int bit = 28 * i, j = bit >> 5, sh = bit & 31;
-        const uint32_t v = (uint32_t)u[i];
-        w[j] |= v << sh;
-        if (sh > 4 && j + 1 < W521) w[j + 1] |= v >> (32 - sh);
-    }
-}
+// (canon_limbs, the limbs of the representative in [0, p), limbs 0..17 in [0, 2^28), limb 18 in [0, 2^17), is limb28.hip.h's: carry()
+// leaves a value in (-2^14, 2^521 + 2^14); + p is positive and below 3 p.  pack is that header's over it.)
 // words -> limbs (no arithmetic: the value is reinterpreted in radix 2^28); any value below 2^532 (bits 532..543 are not read: the
 // callers' values are below p, or 528 bits of an encoding that below_p judges); 1 n out
-DR_F521_FN F521 unpack(const uint32_t (&w)[W521]) {
-    F521 r;
-#pragma unroll
-    for (int i = 0; i < L521; i++) {
-        const int bit = 28 * i, j = bit >> 5, sh = bit & 31;
-        uint32_t v = w[j] >> sh;
-        if (sh > 4 && j + 1 < W521) v |= w[j + 1] << (32 - sh);
-        r.l[i] = (int32_t)(v & (uint32_t)M521);
-    }
-    return r;
-}
+DR_L28_MEMBER F521 Fp521Consts::unpack(const uint32_t (&w)[W521]) { return limbs_of_words<Fp521Consts>(w); }
+DR_L28_FN F521 unpack(const uint32_t (&w)[W521]) { return Fp521Consts::unpack(w); }
 // whether 17 words are below p = 0x1ff ffffffff ... ffffffff
-DR_F521_FN bool below_p(const uint32_t (&w)[W521]) {
+DR_L28_FN bool below_p(const uint32_t (&w)[W521]) {
     uint32_t lo = 0xffffffffu;
 #pragma unroll
     for (int j = 0; j < W521 - 1; j++) lo &= w[j];
     return w[W521 - 1] < 0x1ffu || (w[W521 - 1] == 0x1ffu && lo != 0xffffffffu);
 }
-DR_F521_FN bool is_zero(const F521& a) {
-    int32_t u[L521], acc = 0;
-    f521_canon_limbs(a, u);
-#pragma unroll
-    for (int i = 0; i < L521; i++) acc |= u[i];
-    return acc == 0;
-}
-DR_F521_FN bool is_odd(const F521& a) {                 // of the canonical value (sgn0)
-    int32_t u[L521];
-    f521_canon_limbs(a, u);
-    return (u[0] & 1) != 0;
-}
-DR_F521_FN bool equal(const F521& a, const F521& b) { return is_zero(sub(a, b)); }
 
 // ---------------------------------------------------------------- inversion and roots
 // a^((p - 3) / 4) = a^(2^519 - 1): with x_k = a^(2^k - 1), x_2k = x_k^(2^k) x_k up to x_512, then 519 = 512 + 4 + 2 + 1.
 // 518 squarings and 12 products; a: 1 n
-DR_F521_FN F521 f521_pow_p34(const F521& a) {
+DR_L28_FN F521 f521_pow_p34(const F521& a) {
     const F521 x2 = mul(sqr(a), a);
     const F521 x4 = mul(sqr_n(x2, 2), x2);
     const F521 x8 = mul(sqr_n(x4, 4), x4);
@@ -295,9 +182,9 @@ DR_F521_FN F521 f521_pow_p34(const F521& a) {
     return mul(sqr(x518), a);
 }
 // a^-1 (0 -> 0) by division steps: a lazy value with |limb| < 2^28 (1 n), |value| < 28 p
-DR_F521_FN F521 inv(const F521& a) {
+DR_L28_FN F521 inv(const F521& a) {
     int32_t x[L521], out[L521];
-    f521_canon_limbs(a, x);
+    canon_limbs(a, x);
     inv_divsteps<L521, 28, F521_DIVSTEP_BATCHES>(Fp521Consts::P19, 1u, x, out);
     F521 r;
 #pragma unroll
@@ -305,9 +192,9 @@ DR_F521_FN F521 inv(const F521& a) {
     return r;
 }
 // a^-1 (0 -> 0) as a^(p - 2) = a^(2^521 - 3) = (a^(2^519 - 1))^4 a; a: 1 n, n out
-DR_F521_FN F521 f521_inv_chain(const F521& a) { return mul(sqr_n(f521_pow_p34(a), 2), a); }
+DR_L28_FN F521 f521_inv_chain(const F521& a) { return mul(sqr_n(f521_pow_p34(a), 2), a); }
 // r = a^((p + 1) / 4); true iff r^2 = a (a is a square, 0 included).  a: 1 n
-DR_F521_FN bool f521_sqrt(const F521& a, F521& r) {
+DR_L28_FN bool f521_sqrt(const F521& a, F521& r) {
     r = mul(f521_pow_p34(a), a);
     return equal(sqr(r), a);
 }

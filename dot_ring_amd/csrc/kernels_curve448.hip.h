@@ -17,13 +17,10 @@
 
 namespace dr {
 
-struct Curve448Curve {
-    using Fe = F448;
+struct Curve448Curve : Limb28Curve<Fe448Consts> {
     using Point = M448Point;
-    static constexpr int SCALAR_WORDS = W448, BLOCK = E448_BLOCK, WINDOWS = E448_WINDOWS, LDS_WORDS = L448;   // any k < 2^448
+    static constexpr int SCALAR_WORDS = W448, BLOCK = E448_BLOCK, WINDOWS = E448_WINDOWS;   // any k < 2^448
     static constexpr bool EXTENDED = false;
-    DR_DEV static void to_lds(const F448& a, uint32_t (&w)[L448]) { wave_limbs_to_words(a, w); }
-    DR_DEV static F448 from_lds(const uint32_t (&w)[L448]) { return wave_words_to_limbs<F448>(w); }
     DR_DEV static M448Point add(const M448Point& p, const M448Point& q) { return m448_add(p, q); }
     DR_DEV static M448Point dbl(const M448Point& p) { return m448_dbl(p); }
     DR_DEV static M448Point cneg(const M448Point& p, bool negate) { return m448_cneg(p, negate); }

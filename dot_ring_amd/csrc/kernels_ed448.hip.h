@@ -34,16 +34,11 @@ __device__ const uint32_t E448_ORDER[W448] = {0xab5844f3u, 0x2378c292u, 0x8dc58f
 // wave_curve.hip.h's description of Ed448: canonical words at the ABI (14 per coordinate; the identity is (0, 1) as itself), the limb
 // images in the LDS table (no packing), and 113 windows over the scalar AS IT IS: 112 nibbles of any k < 2^448 and the carry out of the
 // last digit.  Z is never 0 (the law is complete), so the affine store needs nothing special.
-struct Ed448Curve {
-    using Fe = F448;
+struct Ed448Curve : Limb28Curve<Fe448Consts> {
     using Point = E448Point;
-    static constexpr int WORDS = W448, SCALAR_WORDS = W448, BLOCK = E448_BLOCK, WINDOWS = E448_WINDOWS, LDS_WORDS = L448;
+    static constexpr int SCALAR_WORDS = W448, BLOCK = E448_BLOCK, WINDOWS = E448_WINDOWS;
     static constexpr bool EXTENDED = false, ZERO_IS_IDENTITY = false;
-    DR_DEV static F448 unpack(const uint32_t (&w)[W448]) { return dr::unpack(w); }
-    DR_DEV static void pack(const F448& a, uint32_t (&w)[W448]) { dr::pack(a, w); }
-    DR_DEV static F448 inv(const F448& a) { return dr::inv(a); }                                  // 1 n
-    DR_DEV static void to_lds(const F448& a, uint32_t (&w)[L448]) { wave_limbs_to_words(a, w); }
-    DR_DEV static F448 from_lds(const uint32_t (&w)[L448]) { return wave_words_to_limbs<F448>(w); }
+    DR_DEV static F448 inv(const F448& a) { return dr::inv(a); }     // 1 n; stays here: Limb28Curve supplies no inv
     DR_DEV static E448Point identity() { return e448_identity(); }
     DR_DEV static E448Point from_affine(const F448& x, const F448& y) { return e448_from_affine(x, y); }
     DR_DEV static E448Point add(const E448Point& p, const E448Point& q) { return e448_add(p, q); }
@@ -217,14 +212,9 @@ __global__ __launch_bounds__(64) void k_ed448_field_selftest(const int32_t* __re
     if (i >= n) return;
     F448 a, b;
 #pragma unroll
-    for (int t = 0; t < L448; t++) { a.l[t] = a_limbs[(size_t)i * L448 + t]; b.l[t] = b_limbs[(size_t)i * L448 + t]; }
+    for (int t = 0; t < L448; t++) { a.l[t] = a_limbs[(size_t)i * L448 + t]; b.l[t] = b_limbs[(size_t)i * L448 + t]; }   // (in place: DESIGN.md section 8x)
     uint32_t* o = out + (size_t)i * E448_SELFTEST_RECORDS * W448;
-    auto put = [&](int r, const F448& v) {
-        uint32_t w[W448];
-        pack(v, w);
-#pragma unroll
-        for (int j = 0; j < W448; j++) o[r * W448 + j] = w[j];
-    };
+    auto put = [&](int r, const F448& v) { field_selftest_put(o, r, v); };
     put(0, mul(a, b));
     put(1, sqr(a));
     put(2, add(a, b));

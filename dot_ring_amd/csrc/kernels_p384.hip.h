@@ -24,16 +24,11 @@ constexpr int P384_PT_WORDS = 2 * W384;
 
 // wave_curve.hip.h's description of P-384: canonical words at the ABI (12 per coordinate; 96 zero bytes: the identity, which has Z = 0
 // and so stores them by 0^-1 = 0), the limb images (Montgomery form) in the LDS table, and 97 windows over the scalar AS IT IS
-struct P384Curve {
-    using Fe = F384;
+struct P384Curve : Limb28Curve<Fp384Consts> {
     using Point = P384Point;
-    static constexpr int WORDS = W384, SCALAR_WORDS = W384, BLOCK = P384_BLOCK, WINDOWS = P384_WINDOWS, LDS_WORDS = L384;
+    static constexpr int SCALAR_WORDS = W384, BLOCK = P384_BLOCK, WINDOWS = P384_WINDOWS;
     static constexpr bool EXTENDED = false, ZERO_IS_IDENTITY = true;
-    DR_DEV static F384 unpack(const uint32_t (&w)[W384]) { return dr::unpack(w); }
-    DR_DEV static void pack(const F384& a, uint32_t (&w)[W384]) { dr::pack(a, w); }
-    DR_DEV static F384 inv(const F384& a) { return dr::inv(a); }                                  // n
-    DR_DEV static void to_lds(const F384& a, uint32_t (&w)[L384]) { wave_limbs_to_words(a, w); }
-    DR_DEV static F384 from_lds(const uint32_t (&w)[L384]) { return wave_words_to_limbs<F384>(w); }
+    DR_DEV static F384 inv(const F384& a) { return dr::inv(a); }     // n; stays here: Limb28Curve supplies no inv
     DR_DEV static P384Point identity() { return p384_identity(); }
     DR_DEV static P384Point from_affine(const F384& x, const F384& y) { return p384_from_affine(x, y); }
     DR_DEV static P384Point add(const P384Point& p, const P384Point& q) { return p384_add(p, q); }
@@ -144,14 +139,9 @@ __global__ __launch_bounds__(64) void k_p384_field_selftest(const int32_t* __res
     if (i >= n) return;
     F384 a, b;
 #pragma unroll
-    for (int t = 0; t < L384; t++) { a.l[t] = a_limbs[(size_t)i * L384 + t]; b.l[t] = b_limbs[(size_t)i * L384 + t]; }
+    for (int t = 0; t < L384; t++) { a.l[t] = a_limbs[(size_t)i * L384 + t]; b.l[t] = b_limbs[(size_t)i * L384 + t]; }   // (in place: DESIGN.md section 8x)
     uint32_t* o = out + (size_t)i * P384_SELFTEST_RECORDS * W384;
-    auto put = [&](int r, const F384& v) {
-        uint32_t w[W384];
-        pack(v, w);
-#pragma unroll
-        for (int j = 0; j < W384; j++) o[r * W384 + j] = w[j];
-    };
+    auto put = [&](int r, const F384& v) { field_selftest_put(o, r, v); };
     const F384 ca = carry(a);
     put(0, mul(a, b));
     put(1, sqr(a));

@@ -22,16 +22,11 @@ constexpr int P521_PT_WORDS = 2 * W521;
 
 // wave_curve.hip.h's description of P-521: canonical words at the ABI (17 per coordinate; 136 zero bytes: the identity, which has Z = 0
 // and so stores them by 0^-1 = 0), the limb images in the LDS table, and 131 windows over the scalar AS IT IS (k < 2^521)
-struct P521Curve {
-    using Fe = F521;
+struct P521Curve : Limb28Curve<Fp521Consts> {
     using Point = P521Point;
-    static constexpr int WORDS = W521, SCALAR_WORDS = W521, BLOCK = P521_BLOCK, WINDOWS = P521_WINDOWS, LDS_WORDS = L521;
+    static constexpr int SCALAR_WORDS = W521, BLOCK = P521_BLOCK, WINDOWS = P521_WINDOWS;
     static constexpr bool EXTENDED = false, ZERO_IS_IDENTITY = true;
-    DR_DEV static F521 unpack(const uint32_t (&w)[W521]) { return dr::unpack(w); }
-    DR_DEV static void pack(const F521& a, uint32_t (&w)[W521]) { dr::pack(a, w); }
-    DR_DEV static F521 inv(const F521& a) { return dr::inv(a); }                                  // 1 n
-    DR_DEV static void to_lds(const F521& a, uint32_t (&w)[L521]) { wave_limbs_to_words(a, w); }
-    DR_DEV static F521 from_lds(const uint32_t (&w)[L521]) { return wave_words_to_limbs<F521>(w); }
+    DR_DEV static F521 inv(const F521& a) { return dr::inv(a); }     // 1 n; stays here: Limb28Curve supplies no inv
     DR_DEV static P521Point identity() { return p521_identity(); }
     DR_DEV static P521Point from_affine(const F521& x, const F521& y) { return p521_from_affine(x, y); }
     DR_DEV static P521Point add(const P521Point& p, const P521Point& q) { return p521_add(p, q); }
@@ -116,6 +111,7 @@ __global__ __launch_bounds__(P521_BLOCK) void k_p521_map_to_curve(const uint32_t
 // x = bytes 1..66 of a 67-byte string (17 words, the last byte zero) read BIG-endian.  wave_curve.hip.h's sec1_x_words reads bytes
 // 1..4 W, a whole number of words; here the top word is the two bytes 1 and 2 and the sixteen below it are the byte swaps of the
 // (unaligned) words at bytes 63 - 4 q.
+// (in place, with the kernel below: through sec1_decode<P521Curve> over a 66-byte x k_p521_decode_points differs)
 DR_DEV void p521_sec1_x_words(const uint32_t (&w)[W521], uint32_t (&xb)[W521]) {
 #pragma unroll
     for (int q = 0; q < W521 - 1; q++) {
@@ -168,14 +164,9 @@ __global__ __launch_bounds__(64) void k_p521_field_selftest(const int32_t* __res
     if (i >= n) return;
     F521 a, b;
 #pragma unroll
-    for (int t = 0; t < L521; t++) { a.l[t] = a_limbs[(size_t)i * L521 + t]; b.l[t] = b_limbs[(size_t)i * L521 + t]; }
+    for (int t = 0; t < L521; t++) { a.l[t] = a_limbs[(size_t)i * L521 + t]; b.l[t] = b_limbs[(size_t)i * L521 + t]; }   // (in place: DESIGN.md section 8x)
     uint32_t* o = out + (size_t)i * P521_SELFTEST_RECORDS * W521;
-    auto put = [&](int r, const F521& v) {
-        uint32_t w[W521];
-        pack(v, w);
-#pragma unroll
-        for (int j = 0; j < W521; j++) o[r * W521 + j] = w[j];
-    };
+    auto put = [&](int r, const F521& v) { field_selftest_put(o, r, v); };
     put(0, mul(a, b));
     put(1, sqr(a));
     put(2, add(a, b));

@@ -21,14 +21,14 @@ struct P384Point {
     F384 x, y, z;
 };
 
-DR_F384_FN F384 p384_b() { return F384::constant<Fp384Consts::B>(); }
-DR_F384_FN P384Point p384_identity() { return {F384::zero(), F384::small(1), F384::zero()}; }
-DR_F384_FN P384Point p384_from_affine(const F384& x, const F384& y) { return {x, y, F384::small(1)}; }
-DR_F384_FN bool p384_is_identity(const P384Point& p) { return is_zero(p.z); }
-DR_F384_FN P384Point p384_cneg(const P384Point& p, bool negate) { return {p.x, cneg(p.y, negate), p.z}; }
+DR_L28_FN F384 p384_b() { return F384::constant<Fp384Consts::B>(); }
+DR_L28_FN P384Point p384_identity() { return {F384::zero(), F384::small(1), F384::zero()}; }
+DR_L28_FN P384Point p384_from_affine(const F384& x, const F384& y) { return {x, y, F384::small(1)}; }
+DR_L28_FN bool p384_is_identity(const P384Point& p) { return is_zero(p.z); }
+DR_L28_FN P384Point p384_cneg(const P384Point& p, bool negate) { return {p.x, cneg(p.y, negate), p.z}; }
 
 // algorithm 6, a = -3: 10 products (two by b), two of them fused into one pair, and 3 squarings; 12 reductions
-DR_F384_FN P384Point p384_dbl(const P384Point& p) {
+DR_L28_FN P384Point p384_dbl(const P384Point& p) {
     const F384 b = p384_b();
     const F384 t0 = sqr(p.x), t1 = sqr(p.y), t2 = sqr(p.z);                  // n
     const F384 xy = mul(p.x, p.y), xz = mul(p.x, p.z), yz = mul(p.y, p.z);   // 1 n x 1 n: n
@@ -49,7 +49,7 @@ DR_F384_FN P384Point p384_dbl(const P384Point& p) {
 }
 
 // algorithm 4, a = -3: 14 products (two by b), four of them fused into two pairs; 12 reductions
-DR_F384_FN P384Point p384_add(const P384Point& p, const P384Point& q) {
+DR_L28_FN P384Point p384_add(const P384Point& p, const P384Point& q) {
     const F384 b = p384_b();
     const F384 t0 = mul(p.x, q.x), t1 = mul(p.y, q.y), t2 = mul(p.z, q.z);   // n
     const F384 t3 = sub(mul(add(p.x, p.y), add(q.x, q.y)), add(t0, t1));     // X1 Y2 + X2 Y1 (2 n x 2 n): limbs in (-2 n, n): 2 n
@@ -70,25 +70,13 @@ DR_F384_FN P384Point p384_add(const P384Point& p, const P384Point& q) {
 }
 
 // The law as the host side of dr_wide_msm takes it (wide_combine.hpp): the operations of the window combination and the ABI's x || y
-// words <-> a point; zero words are the identity, which has Z = 0 and so stores them by 0^-1 = 0
-struct P384Law {
-    using Point = P384Point;
-    static constexpr int WORDS = W384, LIMBS = L384;
-    DR_F384_MEMBER static P384Point identity() { return p384_identity(); }
-    DR_F384_MEMBER static P384Point add(const P384Point& p, const P384Point& q) { return p384_add(p, q); }
-    DR_F384_MEMBER static P384Point dbl(const P384Point& p) { return p384_dbl(p); }
-    DR_F384_MEMBER static P384Point from_abi(const uint32_t (&w)[2 * W384]) {
-        uint32_t x[W384], y[W384], o = 0;
-        for (int j = 0; j < W384; j++) { x[j] = w[j]; y[j] = w[W384 + j]; o |= x[j] | y[j]; }
-        return o == 0 ? p384_identity() : p384_from_affine(unpack(x), unpack(y));
-    }
-    DR_F384_MEMBER static void to_abi(const P384Point& p, uint32_t (&w)[2 * W384]) {
-        const F384 zi = inv(p.z);
-        uint32_t x[W384], y[W384];
-        pack(mul(p.x, zi), x);
-        pack(mul(p.y, zi), y);
-        for (int j = 0; j < W384; j++) { w[j] = x[j]; w[W384 + j] = y[j]; }
-    }
+// words <-> a point; zero words are the identity, which has Z = 0 and so stores them by 0^-1 = 0.
+struct P384Law : Limb28Law<P384Law, P384Point> {
+    static constexpr bool ZERO_IS_IDENTITY = true;
+    DR_L28_MEMBER static P384Point identity() { return p384_identity(); }
+    DR_L28_MEMBER static P384Point from_affine(const F384& x, const F384& y) { return p384_from_affine(x, y); }
+    DR_L28_MEMBER static P384Point add(const P384Point& p, const P384Point& q) { return p384_add(p, q); }
+    DR_L28_MEMBER static P384Point dbl(const P384Point& p) { return p384_dbl(p); }
 };
 
 // sswu.hip.h's description of P-384: the simplified SWU map straight onto the curve (A = -3, B = b, Z = -12, no isogeny).  A and Z are
@@ -99,17 +87,17 @@ struct P384Sswu {
     using Fe = F384;
     using Point = P384Point;
     static constexpr bool ISOGENY = false;
-    DR_F384_MEMBER static F384 a() { return F384::small(-3); }
-    DR_F384_MEMBER static F384 z() { return F384::small(-12); }
-    DR_F384_MEMBER static F384 sqrt_neg_z() { return F384::constant<Fp384Consts::SQRT12>(); }
-    DR_F384_MEMBER static F384 one() { return F384::small(1); }
-    DR_F384_MEMBER static F384 mul_neg_z(const F384& x) { return mul_small(x, 12); }             // n
-    DR_F384_MEMBER static F384 mul_b(const F384& x) { return mul(p384_b(), x); }                  // n x (n or 2 n): n
-    DR_F384_MEMBER static F384 norm(const F384& x) { return carry(x); }
-    DR_F384_MEMBER static bool is_zero(const F384& x) { return dr::is_zero(x); }
-    DR_F384_MEMBER static bool equal(const F384& x, const F384& y) { return dr::equal(x, y); }
-    DR_F384_MEMBER static bool is_odd(const F384& x) { return dr::is_odd(x); }
-    DR_F384_MEMBER static F384 pow_p34(const F384& x) { return f384_pow_p34(x); }
+    DR_L28_MEMBER static F384 a() { return F384::small(-3); }
+    DR_L28_MEMBER static F384 z() { return F384::small(-12); }
+    DR_L28_MEMBER static F384 sqrt_neg_z() { return F384::constant<Fp384Consts::SQRT12>(); }
+    DR_L28_MEMBER static F384 one() { return F384::small(1); }
+    DR_L28_MEMBER static F384 mul_neg_z(const F384& x) { return mul_small(x, 12); }             // n
+    DR_L28_MEMBER static F384 mul_b(const F384& x) { return mul(p384_b(), x); }                  // n x (n or 2 n): n
+    DR_L28_MEMBER static F384 norm(const F384& x) { return carry(x); }
+    DR_L28_MEMBER static bool is_zero(const F384& x) { return dr::is_zero(x); }
+    DR_L28_MEMBER static bool equal(const F384& x, const F384& y) { return dr::equal(x, y); }
+    DR_L28_MEMBER static bool is_odd(const F384& x) { return dr::is_odd(x); }
+    DR_L28_MEMBER static F384 pow_p34(const F384& x) { return f384_pow_p34(x); }
 };
 
 // ---------------------------------------------------------------- the windows of the fixed schedule

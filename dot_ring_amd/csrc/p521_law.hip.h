@@ -25,19 +25,19 @@ struct P521Point {
     F521 x, y, z;
 };
 
-DR_F521_FN F521 p521_b() {
+DR_L28_FN F521 p521_b() {       // (not F521::constant<>: through it the compiler loads b from memory and the law's kernels change)
     F521 r;
 #pragma unroll
     for (int i = 0; i < L521; i++) r.l[i] = P521Consts::B[i];
     return r;
 }
-DR_F521_FN P521Point p521_identity() { return {F521::zero(), F521::small(1), F521::zero()}; }
-DR_F521_FN P521Point p521_from_affine(const F521& x, const F521& y) { return {x, y, F521::small(1)}; }
-DR_F521_FN bool p521_is_identity(const P521Point& p) { return is_zero(p.z); }
-DR_F521_FN P521Point p521_cneg(const P521Point& p, bool negate) { return {p.x, cneg(p.y, negate), p.z}; }
+DR_L28_FN P521Point p521_identity() { return {F521::zero(), F521::small(1), F521::zero()}; }
+DR_L28_FN P521Point p521_from_affine(const F521& x, const F521& y) { return {x, y, F521::small(1)}; }
+DR_L28_FN bool p521_is_identity(const P521Point& p) { return is_zero(p.z); }
+DR_L28_FN P521Point p521_cneg(const P521Point& p, bool negate) { return {p.x, cneg(p.y, negate), p.z}; }
 
 // algorithm 6, a = -3: 8 products (two by b) and 3 squarings
-DR_F521_FN P521Point p521_dbl(const P521Point& p) {
+DR_L28_FN P521Point p521_dbl(const P521Point& p) {
     const F521 b = p521_b();
     const F521 t0 = sqr(p.x), t1 = sqr(p.y), t2 = sqr(p.z);                  // n
     const F521 xy = mul(p.x, p.y), xz = mul(p.x, p.z), yz = mul(p.y, p.z);   // 1 n x 1 n: n
@@ -58,7 +58,7 @@ DR_F521_FN P521Point p521_dbl(const P521Point& p) {
 }
 
 // algorithm 4, a = -3: 14 products (two by b)
-DR_F521_FN P521Point p521_add(const P521Point& p, const P521Point& q) {
+DR_L28_FN P521Point p521_add(const P521Point& p, const P521Point& q) {
     const F521 b = p521_b();
     const F521 t0 = mul(p.x, q.x), t1 = mul(p.y, q.y), t2 = mul(p.z, q.z);   // n
     const F521 t3 = sub(mul(add(p.x, p.y), add(q.x, q.y)), add(t0, t1));     // X1 Y2 + X2 Y1 (2 n x 2 n): limbs in (-2 n, n): 2 n
@@ -80,24 +80,12 @@ DR_F521_FN P521Point p521_add(const P521Point& p, const P521Point& q) {
 
 // The law as the host side of dr_wide_msm takes it (wide_combine.hpp): the operations of the window combination and the ABI's x || y
 // words <-> a point; zero words are the identity, which has Z = 0 and so stores them by 0^-1 = 0
-struct P521Law {
-    using Point = P521Point;
-    static constexpr int WORDS = W521, LIMBS = L521;
-    DR_F521_MEMBER static P521Point identity() { return p521_identity(); }
-    DR_F521_MEMBER static P521Point add(const P521Point& p, const P521Point& q) { return p521_add(p, q); }
-    DR_F521_MEMBER static P521Point dbl(const P521Point& p) { return p521_dbl(p); }
-    DR_F521_MEMBER static P521Point from_abi(const uint32_t (&w)[2 * W521]) {
-        uint32_t x[W521], y[W521], o = 0;
-        for (int j = 0; j < W521; j++) { x[j] = w[j]; y[j] = w[W521 + j]; o |= x[j] | y[j]; }
-        return o == 0 ? p521_identity() : p521_from_affine(unpack(x), unpack(y));
-    }
-    DR_F521_MEMBER static void to_abi(const P521Point& p, uint32_t (&w)[2 * W521]) {
-        const F521 zi = inv(p.z);
-        uint32_t x[W521], y[W521];
-        pack(mul(p.x, zi), x);
-        pack(mul(p.y, zi), y);
-        for (int j = 0; j < W521; j++) { w[j] = x[j]; w[W521 + j] = y[j]; }
-    }
+struct P521Law : Limb28Law<P521Law, P521Point> {
+    static constexpr bool ZERO_IS_IDENTITY = true;
+    DR_L28_MEMBER static P521Point identity() { return p521_identity(); }
+    DR_L28_MEMBER static P521Point from_affine(const F521& x, const F521& y) { return p521_from_affine(x, y); }
+    DR_L28_MEMBER static P521Point add(const P521Point& p, const P521Point& q) { return p521_add(p, q); }
+    DR_L28_MEMBER static P521Point dbl(const P521Point& p) { return p521_dbl(p); }
 };
 
 // sswu.hip.h's description of P-521: the simplified SWU map straight onto the curve (A = -3, B = b, Z = -4, no isogeny).  The field is
@@ -107,17 +95,17 @@ struct P521Sswu {
     using Fe = F521;
     using Point = P521Point;
     static constexpr bool ISOGENY = false;
-    DR_F521_MEMBER static F521 a() { return F521::small(-3); }
-    DR_F521_MEMBER static F521 z() { return F521::small(-4); }
-    DR_F521_MEMBER static F521 sqrt_neg_z() { return F521::small(2); }
-    DR_F521_MEMBER static F521 one() { return F521::small(1); }
-    DR_F521_MEMBER static F521 mul_neg_z(const F521& x) { return mul_small(x, 4); }              // n
-    DR_F521_MEMBER static F521 mul_b(const F521& x) { return mul(p521_b(), x); }                  // n x (n or 2 n): n
-    DR_F521_MEMBER static F521 norm(const F521& x) { return carry(x); }
-    DR_F521_MEMBER static bool is_zero(const F521& x) { return dr::is_zero(x); }
-    DR_F521_MEMBER static bool equal(const F521& x, const F521& y) { return dr::equal(x, y); }
-    DR_F521_MEMBER static bool is_odd(const F521& x) { return dr::is_odd(x); }
-    DR_F521_MEMBER static F521 pow_p34(const F521& x) { return f521_pow_p34(x); }
+    DR_L28_MEMBER static F521 a() { return F521::small(-3); }
+    DR_L28_MEMBER static F521 z() { return F521::small(-4); }
+    DR_L28_MEMBER static F521 sqrt_neg_z() { return F521::small(2); }
+    DR_L28_MEMBER static F521 one() { return F521::small(1); }
+    DR_L28_MEMBER static F521 mul_neg_z(const F521& x) { return mul_small(x, 4); }              // n
+    DR_L28_MEMBER static F521 mul_b(const F521& x) { return mul(p521_b(), x); }                  // n x (n or 2 n): n
+    DR_L28_MEMBER static F521 norm(const F521& x) { return carry(x); }
+    DR_L28_MEMBER static bool is_zero(const F521& x) { return dr::is_zero(x); }
+    DR_L28_MEMBER static bool equal(const F521& x, const F521& y) { return dr::equal(x, y); }
+    DR_L28_MEMBER static bool is_odd(const F521& x) { return dr::is_odd(x); }
+    DR_L28_MEMBER static F521 pow_p34(const F521& x) { return f521_pow_p34(x); }
 };
 
 // ---------------------------------------------------------------- the windows of the fixed schedule

@@ -27,6 +27,8 @@
 // and, for sec1_decode:  below_p(w), y_of_x(x, y) (a root of the curve equation, false if none), is_odd(y) (of the canonical value),
 // and with CHECK in_subgroup(x, y).  Curve448Curve, whose points cross the ABI as Montgomery (u, v) with a flag word, gives the law and
 // the table forms only: its kernels (and kernels_curve25519.hip.h's over Ed25519Curve) call the core from bodies of their own.
+// The four descriptions over the signed 28-bit fields derive Fe, WORDS, LDS_WORDS, unpack, pack, to_lds and from_lds from limb28.hip.h's
+// Limb28Curve<F>.
 #pragma once
 #include "field.hip.h"
 #include "wave_recode.hip.h"
