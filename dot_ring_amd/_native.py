@@ -126,6 +126,7 @@ _PROTOTYPES.update({
                                                c_char_p]),
     "dr_blsg1_scalar_mul_batch": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_char_p]),
     "dr_blsg1_msm_groups": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_size_t, c_char_p]),
+    "dr_blsg1_msm": (c_int, [c_void_p, c_int, c_char_p, c_char_p, c_size_t, c_char_p]),
     "dr_blsg1_decode_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p, c_char_p]),
     "dr_blsg1_field_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p, c_void_p]),
     "dr_blsg2_hash_to_field_batch": (c_int, [c_int, c_char_p, POINTER(ctypes.c_uint64), c_size_t, c_char_p]),
@@ -381,6 +382,7 @@ _WIDE = {
 
 
 WIDE_PIP_FROM = 256            # csrc/msm_plan.hpp: the term count from which dr_wide_msm takes the bucket method
+NARROW_PIP_FROM = 257          # csrc/msm_plan.hpp: the same for dr_te_msm on the native 256-bit curves and for dr_blsg1_msm
 # the suites dr_wide_msm serves, by the curve id it takes (either variant: RO and NU are one group)
 _WIDE_MSM_CURVE = {"p384": CURVE_P384_RO, "p521": CURVE_P521_RO, "ed448": CURVE_ED448_RO, "curve448": CURVE_CURVE448_RO}
 
@@ -793,6 +795,16 @@ class Context:
         out = ctypes.create_string_buffer(w.point)
         _check(lib().dr_wide_msm(self.handle, _WIDE_MSM_CURVE[suite], pts_xy, scalars, n, out))
         return out.raw[: w.point]
+
+    def blsg1_msm(self, pts_xy: bytes, scalars: bytes) -> bytes:
+        """dr_blsg1_msm: ONE sum of n terms k_i P_i on BLS12-381's E(Fq), 96-byte points and 32-byte scalars used as they are; from
+        NARROW_PIP_FROM terms on by the bucket method (csrc/wave_msm.hip.h).  No terms give the identity."""
+        n = len(scalars) // 32
+        if len(scalars) != 32 * n or len(pts_xy) != 96 * n:
+            raise ValueError("Points and scalars must have same length")
+        out = ctypes.create_string_buffer(96)
+        _check(lib().dr_blsg1_msm(self.handle, CURVE_BLS12_381_G1, pts_xy, scalars, n, out))
+        return out.raw[:96]
 
     def _wide_flagged(self, suite: str, enc: bytes, check: bool = True):
         """dr_<suite>_decode_points: (x||y bytes, flags) for G1's 49-byte SEC1 encodings (check: also r P = O) and Ed448's 112-byte points

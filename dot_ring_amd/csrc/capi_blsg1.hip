@@ -6,7 +6,9 @@
 // threads and checks that inputs are canonical.  Scalars are 32 bytes used AS THEY ARE: E(Fq) has order h r, and its points need not lie
 // in G1.
 #include "capi_suite.hpp"
+#include "capi_wide_msm.hpp"
 #include "kernels_g1_h2c_entry.hip.h"
+#include "narrow_law.hpp"
 
 using namespace dri;
 
@@ -29,6 +31,12 @@ struct Blsg1Suite : SuiteDefaults {
     static constexpr bool decode_gives_points = true, decode_checks_canonical = false;
     static constexpr const char* no_image = "the map to the curve has no value for a message (an isogeny denominator vanishes)";
     static bool canonical(const uint8_t* p) { return fq_canonical(p); }
+    // dr_blsg1_msm (capi_wide_msm.hpp): the bucket method from NARROW_PIP_FROM terms on, over 257 tiled bits of scalars used as they are
+    using Law = dr::G1hLaw;
+    using WideCurve = dr::G1hCurve;
+    static constexpr int wide_bits = 257;
+    static constexpr size_t wide_from = dr::NARROW_PIP_FROM;
+    DR_WAVE_MSM_STAGES(blsg1);
     // RFC 9380 section 5: L = 64 bytes per element, the DST of the variant (the `dst` fields of the RFC's vector files)
     static void hash_to_field(int variant, const uint8_t* salt, size_t salt_len, const uint8_t* msg, size_t len, uint8_t* out) {
         const bool nu = variant == variant_nu;
@@ -63,6 +71,12 @@ int dr_blsg1_scalar_mul_batch(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t*
 int dr_blsg1_msm_groups(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy) {
     TRY(use_ctx(ctx));
     return msm_groups<Blsg1Suite>(ctx, pts_xy, scalars, groups, m, out_xy);
+}
+// ONE MSM of n terms: msm_groups in chunks of up to 64 folded on the host below NARROW_PIP_FROM terms, the bucket method from there on.
+// NOT a fixed schedule from there on: secret scalars go through dr_blsg1_scalar_mul_batch and dr_blsg1_msm_groups.
+int dr_blsg1_msm(dr_ctx* ctx, int curve, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy) {
+    TRY(check_variant<Blsg1Suite>(curve));
+    return wide_msm<Blsg1Suite>(ctx, pts_xy, scalars, n, out_xy);
 }
 int dr_blsg1_decode_points(dr_ctx* ctx, int check, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok) {
     return flagged_round<Blsg1Suite>(ctx, enc, n, out_xy, ok, [&] {

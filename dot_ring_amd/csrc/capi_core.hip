@@ -1,7 +1,9 @@
 // libdotring_hip.so — C ABI (include/dotring_hip.h), part 1 of 10: contexts, device memory, profiling, seam A (the
 // Bandersnatch / twisted Edwards kernels of kernels_bsn.hip.h) and hash-to-curve.  See capi_internal.hpp for the layout.
 #include "capi_suite.hpp"
+#include "capi_wide_msm.hpp"
 #include "hostsmall.hpp"
+#include "narrow_law.hpp"
 #include "kernels_sw.hip.h"
 #include "kernels_ed25519.hip.h"
 #include "kernels_curve25519.hip.h"
@@ -525,6 +527,11 @@ struct Ed25519Suite : Native256<Ed25519Suite> {
     static constexpr const char *name = "Ed25519", *k_scalar_mul = "k_ed_scalar_mul", *k_msm_groups = "k_ed_msm_groups", *k_decode = "k_ed_decode_points";
     static const drh::Mod256& field() { return drh::mod_p25519(); }
     static constexpr size_t identity_y = 1, enc_bytes = 32, rec_bytes = 32, tai_bytes = 32;   // identity (0, identity_y); encoding, decoder record, try-and-increment candidate
+    // the bucket method from NARROW_PIP_FROM terms on (native_msm): the host law, the device description, the tiled bits (the order's + 1)
+    using Law = dr::Ed25519Law;
+    using WideCurve = dr::Ed25519Curve;
+    static constexpr int wide_bits = 254;
+    DR_WAVE_MSM_STAGES(ed);
 };
 struct P256Suite : Native256<P256Suite> {
     static constexpr auto map = dr::k_p256_map_to_curve;
@@ -540,6 +547,10 @@ struct P256Suite : Native256<P256Suite> {
     static constexpr const char *name = "P-256", *k_scalar_mul = "k_p256_scalar_mul", *k_msm_groups = "k_p256_msm_groups", *k_decode = "k_p256_decode_points";
     static const drh::Mod256& field() { return drh::mod_p256(); }
     static constexpr size_t identity_y = 0, enc_bytes = 33, rec_bytes = 36, tai_bytes = 33;   // 64 zero bytes are the identity; candidates carry the flag byte
+    using Law = dr::P256Law;
+    using WideCurve = dr::P256Curve;
+    static constexpr int wide_bits = 257;
+    DR_WAVE_MSM_STAGES(p256);
 };
 // P256_RO / P256_NU (curves 8 and 9): P-256's kernels with the plain SEC1 modes of its decoder (the reference's generic short
 // Weierstrass encoding, not P256_TAI's; no string encodes the identity, so checking and codec-only decoding coincide and no entry point
@@ -567,6 +578,10 @@ struct Secp256k1Suite : Native256<Secp256k1Suite> {
                                 *k_decode = "k_secp256k1_decode_points";
     static const drh::Mod256& field() { return drh::mod_psecp256k1(); }
     static constexpr size_t identity_y = 0, enc_bytes = 33, rec_bytes = 36, tai_bytes = 33;   // 64 zero bytes are the identity; no candidates are made
+    using Law = dr::Secp256k1Law;
+    using WideCurve = dr::Secp256k1Curve;
+    static constexpr int wide_bits = 257;
+    DR_WAVE_MSM_STAGES(secp256k1);
 };
 // Baby JubJub's square-root tables (BjjConsts) are built on the host once per process and copied to the device the first time a context
 // decodes a point or runs the field selftest
@@ -650,6 +665,10 @@ struct BjjSuite : Native256<BjjSuite> {
     static const drh::Mod256& field() { return drh::mod_pbn254(); }
     static constexpr size_t identity_y = 1, enc_bytes = 32, rec_bytes = 32, tai_bytes = 32;
     static int consts_ready(dr_ctx* ctx) { return bjj_consts_ready(ctx); }
+    using Law = dr::BjjLaw;
+    using WideCurve = dr::BjjCurve;
+    static constexpr int wide_bits = 252;
+    DR_WAVE_MSM_STAGES(bjj);
 };
 // Curve25519_RO / Curve25519_NU (curves 13 and 14, kernels_curve25519.hip.h): Ed25519's group under Montgomery coordinates u || v, 64 bytes
 // encoded as they are.  The kernels take and give an identity flag word per point (`flagged`); between the launches, where a point is 64
@@ -665,6 +684,18 @@ struct Curve25519Suite : Native256<Curve25519Suite> {
                                 *k_decode = "k_c25519_decode_points";
     static const drh::Mod256& field() { return drh::mod_p25519(); }
     static constexpr size_t identity_y = 0, enc_bytes = 64, rec_bytes = 64, tai_bytes = 64;   // (identity_y does not apply: native_identity)
+    // the bucket method: a prepare of its own (the map, once per term), then Ed25519's stages; the host converts the one result
+    using Law = dr::C25519Law;
+    using WideCurve = dr::Ed25519Curve;
+    static constexpr int wide_bits = 254;
+    static constexpr bool wide_affine = true;
+    static constexpr auto wide_prepare = dr::k_c25519_msm_prepare;
+    static constexpr auto wide_sort = dr::k_ed_msm_sort;
+    static constexpr auto wide_accumulate = dr::k_ed_msm_accumulate;
+    static constexpr auto wide_accumulate_heavy = dr::k_ed_msm_accumulate_heavy;
+    static constexpr auto wide_reduce = dr::k_ed_msm_reduce;
+    static constexpr auto wide_fold = dr::k_ed_msm_fold;
+    static constexpr const char* wide_names[5] = {"k_c25519_msm_prepare", "k_ed_msm_sort", "k_ed_msm_accumulate", "k_ed_msm_reduce", "k_ed_msm_fold"};
     // Elligator 2, times the cofactor 8 unless `clear` is 0; every canonical input has a value, and the flag says that it is the identity
     static int map_launch(dr_ctx* ctx, size_t n, size_t, int per_item, int clear) {
         return launch(ctx, "k_curve25519_map_to_curve", [&] {
@@ -705,14 +736,33 @@ int native_fixed_base_groups(S, dr_ctx* ctx, const uint8_t* bases_xy, const uint
     return msm_groups<S>(ctx, pts.data(), scalars, groups, m, out_xy);
 }
 // one MSM: groups of 64 terms in one launch, then the partial sums with scalar 1, 64 at a time, until one is left.  The host copy of
-// the scalars is wiped after every launch, a failed one included.
+// the scalars is wiped after every launch, a failed one included.  From NARROW_PIP_FROM terms on: the bucket method
+// (capi_wide_msm.hpp), on scalars reduced mod the group order here as load_scalar reduces them in the kernels — the digits are read
+// from the words as they are, and on the curves with a cofactor sum (k_i mod n) P_i is what msm_groups returns for points with a
+// torsion component.  NOT a fixed schedule: the provers' secret scalars go through scalar_mul_batch and msm_groups.
 template <class S>
-int native_msm(S, dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t out_xy[64]) {
+int native_msm(S, dr_ctx* ctx, const drh::Mod256& order, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t out_xy[64]) {
     if (n == 0) {
         native_identity<S>(out_xy);
         return DR_OK;
     }
     if (!pts_xy || !scalars) return fail(DR_ERR_INVALID, "null buffer");
+    if (n >= dr::NARROW_PIP_FROM) {
+        if (n >= S::max_points) return fail(DR_ERR_INVALID, "batch too large");
+        std::vector<uint8_t> reduced(n * 32);
+        const auto one = [&](size_t i) {
+            uint64_t k[4];
+            drh::load_le32(scalars + 32 * i, k);
+            if (drh::Mod256::geq(k, order.m)) order.reduce_bytes(scalars + 32 * i, 32, false, k);
+            drh::store_le32(k, reduced.data() + 32 * i);
+            explicit_bzero(k, sizeof k);
+        };
+        if (n >= 4096) drh::parallel_for(n, one);
+        else for (size_t i = 0; i < n; i++) one(i);
+        const int rc = wide_msm_buckets<S>(ctx, pts_xy, reduced.data(), n, out_xy);
+        explicit_bzero(reduced.data(), reduced.size());
+        return rc;
+    }
     std::vector<uint8_t> pts(pts_xy, pts_xy + n * 64), sc(scalars, scalars + n * 32), part;
     for (;;) {
         const size_t parts = (n + 63) / 64, m = parts == 1 ? n : 64;          // the last level: one group of the n <= 64 left
@@ -912,7 +962,7 @@ int te_msm(dr_ctx* ctx, int cv, const uint8_t* pts_xy, const uint8_t* scalars, s
     TRY(use_ctx(ctx));
     TRY(check_curve(cv));
     if (!out_xy) return fail(DR_ERR_INVALID, "null buffer");
-    if (int rc; on_native(cv, rc, [&](auto S) { return native_msm(S, ctx, pts_xy, scalars, n, out_xy); })) return rc;
+    if (int rc; on_native(cv, rc, [&](auto S) { return native_msm(S, ctx, drh::te_curve(cv)->n, pts_xy, scalars, n, out_xy); })) return rc;
     if (n == 0) {
         std::memset(out_xy, 0, 64);
         out_xy[32] = 1;

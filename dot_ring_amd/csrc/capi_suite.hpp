@@ -36,6 +36,11 @@ struct SuiteDefaults {
     static int consts_ready(dr_ctx*) { return DR_OK; }
     static constexpr bool flagged = false;
     static constexpr bool checks_scalars = false;      // true: run_points asks S::scalars_ok(scalars, n) before anything is uploaded
+    // the bucket method (capi_wide_msm.hpp) as dr_wide_msm runs it: from WIDE_PIP_FROM terms, set sums out as records of limb images,
+    // and the profile names of prepare, sort, accumulate, reduce and fold (none: the fold is timed with the reduction)
+    static constexpr bool wide_affine = false;
+    static constexpr size_t wide_from = dr::WIDE_PIP_FROM;
+    static constexpr const char* wide_names[5] = {"k_wide_msm_prepare", "k_wide_msm_sort", "k_wide_msm_accumulate", "k_wide_msm_reduce", nullptr};
 };
 
 // BLS12-381's base field element (48 bytes little-endian) below p: shared by the G1 and G2 suites

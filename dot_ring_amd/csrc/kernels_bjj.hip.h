@@ -10,6 +10,7 @@
 #pragma once
 #include "fbn254.hip.h"
 #include "wave_curve.hip.h"
+#include "wave_msm.hip.h"
 
 namespace dr {
 
@@ -193,6 +194,8 @@ __global__ __launch_bounds__(BJJ_BLOCK) void k_bjj_msm_groups(const uint32_t* __
                                                               uint32_t* __restrict__ out, uint32_t groups, uint32_t m, uint32_t mpad) {
     wave_msm_groups<BjjCurve>(pts, ks, out, groups, m, mpad);
 }
+// the bucket method from NARROW_PIP_FROM terms on (wave_msm.hip.h): the stages over BjjCurve, set sums out as affine x || y
+DR_WAVE_MSM_KERNELS(bjj, BjjCurve)
 
 // Decoding (the reference's point.py:150-214 with te_affine_point.py:297-316), one lane per 32-byte encoding: the sign is bit 255,
 // y the low 255 bits, y >= p rejected (so is every encoding with bit 254 set: p < 2^254); x^2 = (1 - y^2) / (1 - d y^2) (a = 1; the

@@ -93,6 +93,17 @@ __global__ __launch_bounds__(ED_BLOCK) void k_c25519_msm_groups(const uint32_t* 
     if (g < groups && j == 0) c25519_store(out + (size_t)g * 16, id_out + g, acc);
 }
 
+// The bucket method from NARROW_PIP_FROM terms on (wave_msm.hip.h) runs Ed25519's stages (k_ed_msm_sort ... k_ed_msm_fold); only the
+// records are made here: the map and its two exceptional points are paid once per term.  The set sums leave as Edwards x || y and the
+// host converts the one result (narrow_law.hpp).
+__global__ __launch_bounds__(WMSM_BLOCK) void k_c25519_msm_prepare(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ id_in, uint32_t n,
+                                                                   uint32_t* __restrict__ table) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const F25 u = wave_load_fe<Ed25519Curve>(pts + (size_t)i * 16), v = wave_load_fe<Ed25519Curve>(pts + (size_t)i * 16 + 8);
+    wave_msm_put<Ed25519Curve>(table, i, c25519_to_edwards(u, v, id_in[i] != 0));
+}
+
 // Decoding (the reference's MGAffinePoint.string_to_point), one lane per 64-byte u || v: ok = u < p, v < p and v^2 = u^3 + 486662 u^2 + u
 // — all the reference checks; out = the 16 words, or zeros.  MODE:
 //   C25519_DEC_CODEC  the codec alone (small-order points and (0, 0) are accepted)

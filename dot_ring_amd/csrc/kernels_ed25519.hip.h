@@ -10,6 +10,7 @@
 #pragma once
 #include "fe25519.hip.h"
 #include "wave_curve.hip.h"
+#include "wave_msm.hip.h"
 
 namespace dr {
 
@@ -122,6 +123,8 @@ __global__ __launch_bounds__(ED_BLOCK) void k_ed_msm_groups(const uint32_t* __re
                                                             uint32_t* __restrict__ out, uint32_t groups, uint32_t m, uint32_t mpad) {
     wave_msm_groups<Ed25519Curve>(pts, ks, out, groups, m, mpad);
 }
+// the bucket method from NARROW_PIP_FROM terms on (wave_msm.hip.h): the stages over Ed25519Curve, set sums out as affine x || y
+DR_WAVE_MSM_KERNELS(ed, Ed25519Curve)
 
 // Decoding (the reference's point.py:150-214 with te_affine_point.py:297-316), one lane per 32-byte encoding: the sign is bit 255,
 // y the low 255 bits, y >= p rejected; x^2 = (y^2 - 1) / (d y^2 + 1) (= (1 - y^2) / (a - d y^2) with a = -1), no root rejected;

@@ -3,6 +3,7 @@
 // kernels_g1_h2c.hip.h itself is shared with the G2 unit.
 #pragma once
 #include "kernels_g1_h2c.hip.h"
+#include "wave_msm.hip.h"
 
 namespace dr {
 
@@ -44,6 +45,8 @@ __global__ __launch_bounds__(G1H_BLOCK) void k_blsg1_msm_groups(const uint32_t* 
                                                                 uint32_t* __restrict__ out, uint32_t groups, uint32_t m, uint32_t mpad) {
     wave_msm_groups<G1hCurve>(pts, ks, out, groups, m, mpad);
 }
+// the bucket method from NARROW_PIP_FROM terms on (wave_msm.hip.h): the stages over G1hCurve, set sums out as affine x || y (dr_blsg1_msm)
+DR_WAVE_MSM_KERNELS(blsg1, G1hCurve)
 // Decoding (the reference's SWAffinePoint.string_to_point for a compressed string), one lane per 49-byte SEC1 encoding padded to 13
 // words (bytes 49..51 zero): byte 0 is 0x02 or 0x03, x = bytes 1..48 BIG-endian, x < p, x^3 + 4 a square, y the root of byte 0's parity.
 // G1H_DEC_CODEC accepts every point of E(Fq), as the reference's codec does; G1H_DEC_CHECK also demands r P = O (valid_point).

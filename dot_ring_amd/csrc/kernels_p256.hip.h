@@ -12,6 +12,7 @@
 #include "fp256.hip.h"
 #include "sswu.hip.h"
 #include "wave_curve.hip.h"
+#include "wave_msm.hip.h"
 
 namespace dr {
 
@@ -139,6 +140,8 @@ __global__ __launch_bounds__(P256_BLOCK) void k_p256_msm_groups(const uint32_t* 
                                                                 uint32_t* __restrict__ out, uint32_t groups, uint32_t m, uint32_t mpad) {
     wave_msm_groups<P256Curve>(pts, ks, out, groups, m, mpad);
 }
+// the bucket method from NARROW_PIP_FROM terms on (wave_msm.hip.h): the stages over P256Curve, set sums out as affine x || y
+DR_WAVE_MSM_KERNELS(p256, P256Curve)
 
 // Decoding (the reference's P256Point.string_to_point / _string_to_canonical_point and, for strings that start with 0x02 or 0x03,
 // SWAffinePoint.string_to_point as the fallback), one lane per 33-byte encoding padded to 9 words (bytes 33..35 zero):

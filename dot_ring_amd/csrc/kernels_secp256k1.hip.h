@@ -12,6 +12,7 @@
 #include "fsecp256k1.hip.h"
 #include "sswu.hip.h"
 #include "wave_curve.hip.h"
+#include "wave_msm.hip.h"
 
 namespace dr {
 
@@ -121,6 +122,8 @@ __global__ __launch_bounds__(K1_BLOCK) void k_secp256k1_msm_groups(const uint32_
                                                                    uint32_t* __restrict__ out, uint32_t groups, uint32_t m, uint32_t mpad) {
     wave_msm_groups<Secp256k1Curve>(pts, ks, out, groups, m, mpad);
 }
+// the bucket method from NARROW_PIP_FROM terms on (wave_msm.hip.h): the stages over Secp256k1Curve, set sums out as affine x || y
+DR_WAVE_MSM_KERNELS(secp256k1, Secp256k1Curve)
 
 // Decoding (the reference's SWAffinePoint.string_to_point for a compressed string), one lane per 33-byte SEC1 encoding padded to 9
 // words (bytes 33..35 zero): byte 0 is 0x02 or 0x03, x = bytes 1..32 BIG-endian, x < p, x^3 + 7 a square, y the root of byte 0's

@@ -1,7 +1,8 @@
 // The plan of a G1 Pippenger call (msm_device, capi_msm.hip) and the kernel-geometry constants it depends on (kernels_g1.hip.h uses
 // them from here), and the plan of a twisted Edwards Pippenger call (te_msm_pippenger: plan_te_msm) and of the wide suites' bucket
-// method (dr_wide_msm: plan_wide_msm).  Plain host C++ (no HIP): g++ builds it for tests/native/msm_plan_check.cpp,
-// tests/native/te_msm_plan_check.cpp and tests/native/wide_msm_plan_check.cpp.
+// method (dr_wide_msm, and dr_te_msm / dr_blsg1_msm on the 256-bit suites and E(Fq): plan_wide_msm).  Plain host C++ (no HIP): g++ builds
+// it for tests/native/msm_plan_check.cpp, tests/native/te_msm_plan_check.cpp, tests/native/wide_msm_plan_check.cpp and
+// tests/native/narrow_msm_host_check.cpp.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -115,6 +116,11 @@ inline TeMsmPlan plan_te_msm(size_t n, int scalar_bits) {
 // P-384, Ed448, Curve448 or P-521.  From WIDE_PIP_FROM terms on; below it the call launches msm_groups in chunks of up to 64.
 constexpr size_t WIDE_PIP_FROM = 256;
 constexpr uint32_t WIDE_MAX_H = 512;                       // wave_msm_sort: bins of a set in LDS (window widths up to 10)
+// The same method under dr_te_msm for Ed25519, Baby JubJub, P-256, secp256k1 and Curve25519 and under dr_blsg1_msm for BLS12-381's
+// E(Fq), from this many terms on.  At least 257: a dr_te_msm of 256 terms is recorded as two msm_groups launches
+// (tests/golden/entry_surface_gpu.json).  The value is the smallest measured size at which the buckets beat msm_groups on all six
+// curves.
+constexpr size_t NARROW_PIP_FROM = 257;
 
 struct WideMsmPlan {
     int c = 0;                           // window width asked for; wide_cmax(wt) is the widest one of the tiling
@@ -124,7 +130,7 @@ struct WideMsmPlan {
 };
 
 // bits: what the tiling covers, one more than the scalars can have (wide_recode.hip.h): 385 on P-384, 449 on Ed448 and Curve448, 522 on
-// P-521.  Width by size, index groups and chunks are plan_te_msm's rules: the walk and the reduction have the same shape
+// P-521; 254 on Ed25519 and Curve25519 and 252 on Baby JubJub (scalars reduced below the order), 257 on P-256, secp256k1 and E(Fq).  Width by size, index groups and chunks are plan_te_msm's rules: the walk and the reduction have the same shape
 inline WideMsmPlan plan_wide_msm(size_t n, int bits) {
     WideMsmPlan p;
     p.c = n < 4096 ? 7 : n < 16384 ? 8 : n < 65536 ? 9 : 10;

@@ -1,25 +1,29 @@
-// The bucket method for ONE variable-base MSM of n >= WIDE_PIP_FROM terms on the wide suites — P-384, P-521, Ed448, Curve448 — as one
-// set of templates over wave_curve.hip.h's description C of the curve (Point, add, cneg, identity, to_lds / from_lds, LDS_WORDS) where
-// kernels_te_msm.hip.h is the same method over Bandersnatch's own field.  kernels_p384.hip.h, kernels_p521.hip.h, kernels_ed448.hip.h
-// and kernels_curve448.hip.h give one thin named __global__ per stage; the plan is msm_plan.hpp's plan_wide_msm, the digits are
-// wide_recode.hip.h's, the host side is capi_wide_msm.hpp:
-//   prepare      one lane per term: the ABI's point -> a projective RECORD of limb images (x, y, z: 3 x LDS_WORDS words as to_lds gives
-//                them, padded to whole uint4).  Walks read records, so Curve448's birational map and its exceptional points are paid
-//                once per term.  (The suites' kernels load the point; wave_msm_put stores it.)
+// The bucket method for ONE variable-base MSM as one set of templates over wave_curve.hip.h's description C of the curve (Point, add,
+// cneg, identity, to_lds / from_lds, LDS_WORDS, EXTENDED) where kernels_te_msm.hip.h is the same method over Bandersnatch's own field:
+//   the wide suites — P-384, P-521, Ed448, Curve448 — from WIDE_PIP_FROM terms (dr_wide_msm); kernels_p384.hip.h, kernels_p521.hip.h,
+//     kernels_ed448.hip.h and kernels_curve448.hip.h give one thin named __global__ per stage;
+//   the 256-bit suites — Ed25519, Baby JubJub, P-256, secp256k1, and Curve25519 on Ed25519's stages — and BLS12-381's E(Fq) from
+//     NARROW_PIP_FROM terms (dr_te_msm, dr_blsg1_msm); their kernel headers expand DR_WAVE_MSM_KERNELS below.
+// The plan is msm_plan.hpp's plan_wide_msm, the digits are wide_recode.hip.h's, the host side is capi_wide_msm.hpp:
+//   prepare      one lane per term: the ABI's point -> a projective RECORD of limb images (x, y, z and, where the description is
+//                EXTENDED, t: 3 or 4 x LDS_WORDS words as to_lds gives them, padded to whole uint4).  Walks read records, so the
+//                birational maps of Curve448 and Curve25519 and their exceptional points are paid once per term.  (The suites' kernels
+//                load the point; wave_msm_put stores it.)
 //   sort         one workgroup per bucket set (window, index group): histogram, scan and placement of the set's digits in LDS.  Entries
 //                are the term index with the digit's sign in bit 31.
 //   accumulate   one lane per bucket, in the order of a size-sorted permutation, walks its list with C::add, negating by C::cneg; lists
 //                longer than TE_HEAVY_BUCKET are left to accumulate_heavy, where a whole wave strides over the list and folds its 64 sums
-//                with wave_shfl_down.  All four laws are complete or unified: equal points, inverse pairs and identities in a list are
+//                with wave_shfl_down.  All the laws are complete or unified: equal points, inverse pairs and identities in a list are
 //                additions like any other.
 //   reduce       per (set, chunk of L buckets): running sums + the chunk's offset multiple (double-and-add over the bits of the offset)
-//   fold         one lane per set adds its chunk results; the W x G set sums leave the device as records
+//   fold         one lane per set adds its chunk results; the W x G set sums leave the device as records (the wide suites, whose laws
+//                compile for the host) or as the ABI's affine points (fold_affine: the suites whose host law runs over another form)
 // The host combines index groups and windows with the suite's own law (a chain of ~bits doublings: one CPU core is far faster at that
 // than one GPU lane).
 //
-// NOT a fixed schedule, exactly as dr_te_msm is not from 256 terms: which bucket a term goes to, how long a list is and which kernel
-// walks it all depend on the scalars.  The provers' secret scalars never come here (they go through scalar_mul_batch and msm_groups);
-// the verifiers' scalars are public.
+// NOT a fixed schedule, exactly as dr_te_msm on Bandersnatch is not from 256 terms: which bucket a term goes to, how long a list is and
+// which kernel walks it all depend on the scalars.  The provers' secret scalars never come here (they go through scalar_mul_batch and
+// msm_groups); the verifiers' scalars are public.
 #pragma once
 #include "msm_plan.hpp"
 #include "wave_curve.hip.h"
@@ -30,28 +34,36 @@ constexpr int WMSM_SORT_BLOCK = 256;
 constexpr int WMSM_BLOCK = 64;            // accumulate, reduce, fold: one wave per workgroup (the laws take 128 registers and more)
 
 template <class C>
-constexpr int wave_msm_record_words() { return (3 * C::LDS_WORDS + 3) & ~3; }
+constexpr int wave_msm_record_words() { return ((C::EXTENDED ? 4 : 3) * C::LDS_WORDS + 3) & ~3; }
 
 template <class C>
 DR_DEV void wave_msm_put(uint32_t* __restrict__ recs, size_t idx, const typename C::Point& p) {
-    constexpr int W = C::LDS_WORDS, R = wave_msm_record_words<C>();
-    uint32_t x[W], y[W], z[W], w[R];
+    constexpr int W = C::LDS_WORDS, N = C::EXTENDED ? 4 : 3, R = wave_msm_record_words<C>();
+    [[maybe_unused]] uint32_t x[W], y[W], z[W], t[W], w[R];
     C::to_lds(p.x, x); C::to_lds(p.y, y); C::to_lds(p.z, z);
+    if constexpr (C::EXTENDED) C::to_lds(p.t, t);
 #pragma unroll
-    for (int i = 0; i < W; i++) { w[i] = x[i]; w[W + i] = y[i]; w[2 * W + i] = z[i]; }
+    for (int i = 0; i < W; i++) {
+        w[i] = x[i]; w[W + i] = y[i]; w[2 * W + i] = z[i];
+        if constexpr (C::EXTENDED) w[3 * W + i] = t[i];
+    }
 #pragma unroll
-    for (int i = 3 * W; i < R; i++) w[i] = 0;
+    for (int i = N * W; i < R; i++) w[i] = 0;
     wave_store_words(recs + idx * R, w);
 }
 template <class C>
 DR_DEV typename C::Point wave_msm_get(const uint32_t* __restrict__ recs, size_t idx) {
     constexpr int W = C::LDS_WORDS, R = wave_msm_record_words<C>();
-    uint32_t x[W], y[W], z[W], w[R];
+    [[maybe_unused]] uint32_t x[W], y[W], z[W], t[W], w[R];
     wave_load_words(recs + idx * R, w);
 #pragma unroll
-    for (int i = 0; i < W; i++) { x[i] = w[i]; y[i] = w[W + i]; z[i] = w[2 * W + i]; }
+    for (int i = 0; i < W; i++) {
+        x[i] = w[i]; y[i] = w[W + i]; z[i] = w[2 * W + i];
+        if constexpr (C::EXTENDED) t[i] = w[3 * W + i];
+    }
     typename C::Point p;
     p.x = C::from_lds(x); p.y = C::from_lds(y); p.z = C::from_lds(z);
+    if constexpr (C::EXTENDED) p.t = C::from_lds(t);
     return p;
 }
 
@@ -201,13 +213,56 @@ DR_DEV void wave_msm_reduce(const uint32_t* __restrict__ buckets, size_t sets, u
     wave_msm_put<C>(partial, gid, sum);
 }
 template <class C>
-DR_DEV void wave_msm_fold(const uint32_t* __restrict__ partial, size_t sets, uint32_t T, uint32_t* __restrict__ setsum) {
-    const size_t set = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (set >= sets) return;
+DR_DEV typename C::Point wave_msm_fold_sum(const uint32_t* __restrict__ partial, size_t set, uint32_t T) {
     typename C::Point acc = wave_msm_get<C>(partial, set * T);
 #pragma unroll 1
     for (uint32_t t = 1; t < T; t++) acc = C::add(acc, wave_msm_get<C>(partial, set * T + t));
-    wave_msm_put<C>(setsum, set, acc);
+    return acc;
 }
+template <class C>
+DR_DEV void wave_msm_fold(const uint32_t* __restrict__ partial, size_t sets, uint32_t T, uint32_t* __restrict__ setsum) {
+    const size_t set = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (set >= sets) return;
+    wave_msm_put<C>(setsum, set, wave_msm_fold_sum<C>(partial, set, T));
+}
+// the same fold with the set sum stored as the ABI's affine point (2 WORDS canonical words: zero words for a Weierstrass identity, (0, 1)
+// on an Edwards curve), for the suites whose host law is not over the device's limb form
+template <class C>
+DR_DEV void wave_msm_fold_affine(const uint32_t* __restrict__ partial, size_t sets, uint32_t T, uint32_t* __restrict__ setsum) {
+    const size_t set = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (set >= sets) return;
+    wave_store_affine<C>(setsum + set * (2 * C::WORDS), wave_msm_fold_sum<C>(partial, set, T));
+}
+
+// The stages' kernels of a curve with 8-word scalars (NAME: ed, bjj, p256, secp256k1, blsg1) over its description C; each kernel header
+// expands this once.  The fold stores affine points.
+#define DR_WAVE_MSM_KERNELS(NAME, C)                                                                                                           \
+    __global__ __launch_bounds__(WMSM_BLOCK) void k_##NAME##_msm_prepare(const uint32_t* __restrict__ pts, uint32_t n, uint32_t* __restrict__ table) { \
+        wave_msm_prepare<C>(pts, n, table);                                                                                                    \
+    }                                                                                                                                          \
+    __global__ __launch_bounds__(WMSM_SORT_BLOCK) void k_##NAME##_msm_sort(const uint32_t* __restrict__ scalars, WideTiling wt, uint32_t n, uint32_t H, \
+                                                                           uint32_t groups, uint32_t capacity, uint32_t* __restrict__ counts,  \
+                                                                           uint32_t* __restrict__ offsets, uint32_t* __restrict__ sorted) {    \
+        wave_msm_sort<8>(scalars, wt, n, H, groups, capacity, counts, offsets, sorted);                                                        \
+    }                                                                                                                                          \
+    __global__ __launch_bounds__(WMSM_BLOCK) void k_##NAME##_msm_accumulate(const uint32_t* __restrict__ table, const uint32_t* __restrict__ sorted, \
+                                                                            const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts, \
+                                                                            const uint32_t* __restrict__ perm, uint32_t* __restrict__ buckets, \
+                                                                            size_t nbuckets) {                                                 \
+        wave_msm_accumulate<C>(table, sorted, offsets, counts, perm, buckets, nbuckets);                                                       \
+    }                                                                                                                                          \
+    __global__ __launch_bounds__(64) void k_##NAME##_msm_accumulate_heavy(const uint32_t* __restrict__ table, const uint32_t* __restrict__ sorted, \
+                                                                          const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts, \
+                                                                          uint32_t* __restrict__ buckets, size_t nbuckets) {                   \
+        wave_msm_accumulate_heavy<C>(table, sorted, offsets, counts, buckets, nbuckets);                                                       \
+    }                                                                                                                                          \
+    __global__ __launch_bounds__(WMSM_BLOCK) void k_##NAME##_msm_reduce(const uint32_t* __restrict__ buckets, size_t sets, uint32_t H, uint32_t L, \
+                                                                        uint32_t* __restrict__ partial) {                                      \
+        wave_msm_reduce<C>(buckets, sets, H, L, partial);                                                                                      \
+    }                                                                                                                                          \
+    __global__ __launch_bounds__(WMSM_BLOCK) void k_##NAME##_msm_fold(const uint32_t* __restrict__ partial, size_t sets, uint32_t T,           \
+                                                                      uint32_t* __restrict__ setsum) {                                         \
+        wave_msm_fold_affine<C>(partial, sets, T, setsum);                                                                                     \
+    }
 
 }  // namespace dr

@@ -2,7 +2,9 @@
 // limb images become points of the suite's own law (P384Law, P521Law, E448Law, M448Law: p384_law.hip.h, p521_law.hip.h, e448_law.hip.h,
 // c448_law.hip.h, which compile for the host), and index groups and windows are combined from the top window down — doublings by the
 // width of each window, then the additions of its groups.  A chain of ~bits doublings: one CPU core, not one GPU lane.
-// Plain host C++ over those headers: g++ builds it for tests/native/wide_msm_plan_check.cpp.
+// The suites whose set sums leave as affine ABI points (the 256-bit curves and E(Fq): narrow_law.hpp) use wide_combine alone, over laws
+// of the same shape.
+// Plain host C++ over those headers: g++ builds it for tests/native/wide_msm_plan_check.cpp and tests/native/narrow_msm_host_check.cpp.
 #pragma once
 #include <cstddef>
 #include <cstdint>

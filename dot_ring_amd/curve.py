@@ -826,12 +826,15 @@ class Bls12381G1Point(_WideRfc9380, _Sec1Codec, ShortWeierstrassA0Point):
 
     @classmethod
     def msm(cls, points, scalars):
-        """sum k_i P_i for any integers k_i: groups of up to 64 terms in one launch, then their partial sums the same way"""
+        """sum k_i P_i for any integers k_i: groups of up to 64 terms in one launch, then their partial sums the same way; from
+        NARROW_PIP_FROM terms on the bucket method of dr_blsg1_msm (not a fixed schedule: for public scalars)"""
         if len(points) != len(scalars):
             raise ValueError("Points and scalars must have same length")
         pts, ks = cls._terms(points, scalars)
         if not pts:
             return cls.identity()
+        if len(pts) >= _native.NARROW_PIP_FROM:      # dr_blsg1_msm: the bucket method
+            return cls._unpack(runtime.context().blsg1_msm(cls._pack(pts), b"".join(v.to_bytes(32, "little") for v in ks)))[0]
         while True:
             parts = -(-len(pts) // 64)
             m = len(pts) if parts == 1 else 64

@@ -177,7 +177,12 @@ enum { DR_CURVE_P256_RO = 8, DR_CURVE_P256_NU = 9, DR_CURVE_ED25519_RO = 10, DR_
  *     identity of these two curve ids as 64 bytes of 0xff: u = v = 2^256 - 1 is no field element, so it is no point.
  * A proof whose point would be the identity has no encoding (the reference's point_to_string raises): the provers return DR_ERR_INVALID.
  * The ring prover, the Ring-VRF calls, dr_ietf_verify_batch, the GLV and dr_bsn_* entry points refuse these ids, as they refuse 3 - 11.
- * Id 12 is not assigned (every entry point answers DR_ERR_INVALID to it). */
+ * Id 12 is not assigned (every entry point answers DR_ERR_INVALID to it).
+ *
+ * dr_te_msm on ids 3 - 11, 13 and 14 (the curves with kernels of their own): up to 256 terms it is dr_te_msm_groups' kernel over chunks of
+ * 64 and once more over the partial sums, a fixed schedule per term; from 257 terms on the bucket method (csrc/wave_msm.hip.h), which is
+ * NOT a fixed schedule — bucket choice and list lengths depend on the scalars, as on Bandersnatch from 256 terms.  The result is the same
+ * sum of (k_i mod n) P_i.  Secret scalars belong in dr_te_scalar_mul_batch and dr_te_msm_groups. */
 enum { DR_CURVE_CURVE25519_RO = 13, DR_CURVE_CURVE25519_NU = 14 };
 DR_API int dr_te_scalar_mul_batch(dr_ctx *ctx, int curve, const uint8_t *pts_xy, const uint8_t *scalars, size_t n, uint8_t *out_xy);
 DR_API int dr_te_msm(dr_ctx *ctx, int curve, const uint8_t *pts_xy, const uint8_t *scalars, size_t n, uint8_t out_xy[64]);
@@ -299,6 +304,10 @@ DR_API int dr_bjj_field_ops_selftest(dr_ctx *ctx, const int32_t *a_limbs /* n*9 
  *   dr_blsg1_encode_to_curve_batch  encode_to_curve(salt_i || msg_i) (salts nullable): hash_to_field on the worker threads and one map
  *                                   launch; DR_ERR_INVALID if a map has no value.
  *   dr_blsg1_scalar_mul_batch       out[i] = k[i] P[i];  dr_blsg1_msm_groups  out[g] = sum_{j<m} k[g m + j] P[g m + j], m <= 64
+ *   dr_blsg1_msm                    ONE sum of n terms k_i P_i, in the forms of dr_blsg1_msm_groups; `curve` is either id.  Below 257 terms
+ *                                   it launches dr_blsg1_msm_groups' kernel in chunks of up to 64 and folds them on the host; from there
+ *                                   on the bucket method (csrc/wave_msm.hip.h), which is NOT a fixed schedule: secret scalars go through
+ *                                   dr_blsg1_scalar_mul_batch and dr_blsg1_msm_groups.  n = 0 gives the identity.
  *   dr_blsg1_decode_points          49-byte SEC1 compressed strings (0x02 / 0x03 by the parity of y, then x BIG-endian, x < p, x^3 + 4 a
  *                                   square).  check = 0 accepts every point of E(Fq), as the reference's string_to_point; check = 1
  *                                   also demands r P = O (the reference's valid_point).  out_xy[i] = the point, or 96 zero bytes.
@@ -317,6 +326,7 @@ DR_API int dr_blsg1_scalar_mul_batch(dr_ctx *ctx, const uint8_t *pts_xy /* n*96 
                                      uint8_t *out_xy /* n*96 */);
 DR_API int dr_blsg1_msm_groups(dr_ctx *ctx, const uint8_t *pts_xy /* groups*m*96 */, const uint8_t *scalars /* groups*m*32 */, size_t groups,
                                size_t m, uint8_t *out_xy /* groups*96 */);
+DR_API int dr_blsg1_msm(dr_ctx *ctx, int curve, const uint8_t *pts_xy /* n*96 */, const uint8_t *scalars /* n*32 */, size_t n, uint8_t *out_xy /* 96 */);
 DR_API int dr_blsg1_decode_points(dr_ctx *ctx, int check, const uint8_t *enc /* n*49 */, size_t n, uint8_t *out_xy /* n*96 */, uint8_t *ok /* n */);
 DR_API int dr_blsg1_field_selftest(dr_ctx *ctx, const int32_t *a_limbs /* n*14 */, const int32_t *b_limbs /* n*14 */, size_t n,
                                    uint8_t *out /* n*240 */, uint8_t *flags /* n */);
