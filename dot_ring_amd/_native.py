@@ -71,6 +71,7 @@ _PROTOTYPES = {
     "dr_ring_prover_destroy": (None, [c_void_p]),
     "dr_ring_prover_root": (c_int, [c_void_p, c_void_p, POINTER(c_int)]),
     "dr_ring_prover_fixed_coeffs": (c_int, [c_void_p, c_void_p]),
+    "dr_ring_prover_peek": (c_int, [c_void_p, c_int, c_void_p, c_size_t]),
     "dr_ring_prove_witness": (c_int, [c_void_p, c_size_t, c_void_p, c_char_p, c_char_p, c_void_p, c_void_p, POINTER(c_int)]),
     "dr_ring_prove_quotient": (c_int, [c_void_p, c_size_t, c_char_p, c_void_p, POINTER(c_int)]),
     "dr_ring_prove_evals": (c_int, [c_void_p, c_size_t, c_char_p, c_void_p]),
@@ -556,6 +557,16 @@ class RingProver:
         out = ctypes.create_string_buffer(3 * self.n * 32)
         _check(lib().dr_ring_prover_fixed_coeffs(self.handle, out))
         return out.raw
+
+    PEEK_COLUMNS, PEEK_QUOTIENT, PEEK_LIN = 0, 1, 2
+
+    def peek(self, what: int, batch: int) -> bytes:
+        """Diagnostic read-back of the batch in flight: the four coefficient columns (after witness), q zero-padded to 3N + 1
+        coefficients (after quotient) or the linearisation polynomial (after evals); 32-byte LE standard form, proof-major."""
+        per = {self.PEEK_COLUMNS: 4 * self.n, self.PEEK_QUOTIENT: 3 * self.n + 1, self.PEEK_LIN: self.n}.get(what, 1)
+        out = ctypes.create_string_buffer(max(1, 32 * per * batch))
+        _check(lib().dr_ring_prover_peek(self.handle, what, out, 32 * per * batch))
+        return out.raw[: 32 * per * batch]
 
     def witness(self, producer_index: list, blinding: bytes, zk_rows: bytes | None):
         batch = len(producer_index)

@@ -114,6 +114,7 @@ struct dr_ring_prover {
     Scratch hid;                        // [B][4][4][8] std: rows N-3, N-2, N-1, 0 of the witness columns' evaluations (saved by the witness phase)
     bool fwd_pending = false;           // the witness phase has launched the coset transforms of this batch (they run beside the host's hashing)
     bool quot2_pending = false;         // the evaluation phase has launched the synthetic division of the linearisation polynomial
+    bool cols_ready = false, q_ready = false, lin_ready = false;    // which of dr_ring_prover_peek's buffers the current batch has filled
     uint8_t root[3 * 96];
     int root_inf[3];
     // per-batch state
@@ -314,6 +315,28 @@ int dr_ring_prover_fixed_coeffs(dr_ring_prover* p, uint8_t* out /* 3*N*32: px, p
     return DR_OK;
 }
 
+// Diagnostic: one of the current batch's polynomials, standard-form coefficients, as the phase that fills it left it.  Waits for the
+// context's stream and copies; no flag of the phase sequence (fwd_pending, quot2_pending) is read or written, nothing is launched.
+int dr_ring_prover_peek(dr_ring_prover* p, int what, uint8_t* out, size_t out_bytes) {
+    if (!p || !out) return fail(DR_ERR_INVALID, "null argument");
+    TRY(use_ctx(p->ctx));
+    const size_t n = p->rc.n;
+    const Scratch* src = nullptr;
+    size_t bytes = 0;
+    bool ready = false;
+    switch (what) {
+        case DR_RING_PEEK_COLUMNS: src = &p->cols; bytes = p->batch * 4 * n * 32; ready = p->cols_ready; break;
+        case DR_RING_PEEK_QUOTIENT: src = &p->q; bytes = p->batch * (3 * n + 1) * 32; ready = p->q_ready; break;
+        case DR_RING_PEEK_LIN: src = &p->lin; bytes = p->batch * n * 32; ready = p->lin_ready; break;
+        default: return fail(DR_ERR_INVALID, "unknown peek selector");
+    }
+    if (!ready || p->batch == 0) return fail(DR_ERR_INVALID, "the phase that fills this buffer has not run for the current batch");
+    if (out_bytes < bytes || src->cap < bytes) return fail(DR_ERR_INVALID, "peek buffer is too short");
+    HIP_TRY(hipMemcpyAsync(out, src->p, bytes, hipMemcpyDeviceToHost, p->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(p->ctx->stream));
+    return DR_OK;
+}
+
 // phase A: witness columns, interpolation, 4 commitments per proof (order b, accip, accx, accy)
 int dr_ring_prove_witness(dr_ring_prover* p, size_t batch, const uint32_t* producer_index, const uint8_t* blinding, const uint8_t* zk_rows,
                           uint8_t* out_relation_xy, uint8_t* out_commitments, int* is_inf) {
@@ -336,6 +359,7 @@ int dr_ring_prove_witness(dr_ring_prover* p, size_t batch, const uint32_t* produ
     if (zk_rows) TRY(check_fr_elems(zk_rows, batch * 12, "hidden row"));
     p->batch = batch;
     p->quot2_pending = false;
+    p->cols_ready = p->q_ready = p->lin_ready = false;
     hipStream_t st = ctx->stream;
     TRY(p->idx.reserve(batch * 4));
     TRY(p->blind.reserve(batch * 32));
@@ -391,6 +415,7 @@ int dr_ring_prove_witness(dr_ring_prover* p, size_t batch, const uint32_t* produ
                  p->coset_scale.as<uint32_t>()));
     HIP_TRY(hipGetLastError());
     p->fwd_pending = true;
+    p->cols_ready = true;
     return DR_OK;
 }
 
@@ -440,7 +465,9 @@ int dr_ring_prove_quotient(dr_ring_prover* p, size_t batch, const uint8_t* alpha
                            p->q.as<uint32_t>());
     }));
     MsmTable t = srs_table(p->srs, 0);
-    return msm_to_bytes(ctx, p->srs->d_bases, p->q.as<uint32_t>(), qn, batch, out_cq, is_inf, &t);
+    TRY(msm_to_bytes(ctx, p->srs->d_bases, p->q.as<uint32_t>(), qn, batch, out_cq, is_inf, &t));
+    p->q_ready = true;
+    return DR_OK;
 }
 
 // synthetic division of [batch] polynomials of len coefficients by (X - zeta) or (X - zeta*omega): chunk-local pass, link, write
@@ -511,6 +538,7 @@ int dr_ring_prove_evals(dr_ring_prover* p, size_t batch, const uint8_t* zetas, u
     TRY(ring_quot2(p, batch));
     HIP_TRY(hipGetLastError());
     p->quot2_pending = true;
+    p->lin_ready = true;
     return DR_OK;
 }
 
@@ -548,6 +576,7 @@ int dr_ring_prove_openings(dr_ring_prover* p, size_t batch, const uint8_t* nus, 
         if (is_inf) { is_inf[2 * b] = inf[b]; is_inf[2 * b + 1] = inf[batch + b]; }
     }
     // the last phase of a batch: its results are on the host, nothing of the witness has to outlive it
+    p->cols_ready = p->q_ready = p->lin_ready = false;
     return dr_ring_prover_wipe(p);
 }
 
@@ -584,6 +613,7 @@ int dr_ring_prover_wipe(dr_ring_prover* p) {
         std::fprintf(stderr, "\n");
     }
     p->fwd_pending = p->quot2_pending = false;
+    p->cols_ready = p->q_ready = p->lin_ready = false;
     TRY(ctx_wipe_enqueue_scratch(p->ctx, wst));
     return ctx_wipe_end(p->ctx, wst);
 }

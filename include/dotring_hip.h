@@ -730,6 +730,16 @@ DR_API int dr_ring_prover_create_te(dr_ctx *ctx, int curve, const dr_srs *srs, u
 DR_API void dr_ring_prover_destroy(dr_ring_prover *p);
 DR_API int dr_ring_prover_root(const dr_ring_prover *p, uint8_t out_commitments[3 * 96], int is_inf[3]);
 DR_API int dr_ring_prover_fixed_coeffs(dr_ring_prover *p, uint8_t *out /* 3*N*32: px, py, s coefficients */);
+/* Diagnostic (like the *_selftest entries; nothing on the proving path calls it): reads back one polynomial of the batch in flight,
+ * 32-byte LE standard-form coefficients, proof-major.  `what`:
+ *   DR_RING_PEEK_COLUMNS   B * 4 * N * 32 bytes: the coefficients of b, accip, accx, accy; valid after dr_ring_prove_witness
+ *   DR_RING_PEEK_QUOTIENT  B * (3N + 1) * 32 bytes: q, zero-padded; valid after dr_ring_prove_quotient
+ *   DR_RING_PEEK_LIN       B * N * 32 bytes: the linearisation polynomial; valid after dr_ring_prove_evals
+ * Waits for the context's stream and copies; the prover's state, the order of its phases included, is as before.  DR_ERR_INVALID for an
+ * unknown selector, for out_bytes below the size above, and when the phase that fills the buffer has not run for the current batch or
+ * the batch has been wiped (dr_ring_prove_openings ends with a wipe). */
+enum { DR_RING_PEEK_COLUMNS = 0, DR_RING_PEEK_QUOTIENT = 1, DR_RING_PEEK_LIN = 2 };
+DR_API int dr_ring_prover_peek(dr_ring_prover *p, int what, uint8_t *out, size_t out_bytes);
 DR_API int dr_ring_prove_witness(dr_ring_prover *p, size_t batch, const uint32_t *producer_index, const uint8_t *blinding,
                                  const uint8_t *zk_rows, uint8_t *out_relation_xy, uint8_t *out_commitments, int *is_inf);
 DR_API int dr_ring_prove_quotient(dr_ring_prover *p, size_t batch, const uint8_t *alphas, uint8_t *out_cq, int *is_inf);
