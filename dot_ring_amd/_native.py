@@ -54,6 +54,8 @@ _PROTOTYPES = {
     "dr_g2_mul": (c_int, [c_char_p, c_char_p, c_char_p]),
     "dr_srs_precompute": (c_int, [c_void_p, c_void_p, c_int]),
     "dr_srs_table_info": (c_int, [c_void_p, c_size_t, c_size_t, POINTER(c_int)]),
+    "dr_srs_precompute_multiples": (c_int, [c_void_p, c_void_p, c_int, c_int]),
+    "dr_srs_table_info_multiples": (c_int, [c_void_p, c_size_t, c_size_t, POINTER(c_int)]),
     "dr_srs_download": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]),
     "dr_srs_destroy": (None, [c_void_p]),
     "dr_srs_size": (c_size_t, [c_void_p]),
@@ -488,20 +490,24 @@ class Srs:
         self.count = len(g1_be_xy) // 96
         _check(lib().dr_srs_load(ctx.handle, g1_be_xy, self.count, byref(self.handle)))
 
-    def precompute(self, window_bits: int) -> "Srs":
-        """Build (or with 0 drop) the fixed-base window table in HBM."""
-        _check(lib().dr_srs_precompute(self.ctx.handle, self.handle, window_bits))
+    def precompute(self, window_bits: int, multiples: int = 1) -> "Srs":
+        """Build (or with 0 drop) the fixed-base window table in HBM.  multiples: blocks of rows of a bit-row table, one per small odd
+        multiple of the bases (2, 4, 8; 0 = the library's default count; dr_srs_precompute_multiples); 1 = the plain table."""
+        if multiples == 1:
+            _check(lib().dr_srs_precompute(self.ctx.handle, self.handle, window_bits))
+        else:
+            _check(lib().dr_srs_precompute_multiples(self.ctx.handle, self.handle, window_bits, multiples))
         return self
 
     def table_info(self, n: int = 0, batch: int = 0) -> dict:
         """Shape of the fixed-base table and the tiling `batch` MSMs of n points over it take (dr_srs_table_info): window_bits, rows,
         digit rows per scalar, the per-call tiling (window rows or the non-adjacent form over a bit-row table) with its width, and
         the expected non-zero digits per scalar (= bucket additions per pair)."""
-        info = (c_int * 6)()
-        _check(lib().dr_srs_table_info(self.handle, n, batch, info))
+        info = (c_int * 8)()
+        _check(lib().dr_srs_table_info_multiples(self.handle, n, batch, info))
         return {"window_bits": info[0], "rows": info[1], "batched_windows": info[2], "tiling_bits": info[3],
                 "tiling": ("window rows", "-", "non-adjacent form")[info[4]], "digits_per_scalar": info[5] / 1000.0,
-                "odd_buckets": bool(info[4])}
+                "odd_buckets": bool(info[4]), "multiples": info[6], "table_multiples": info[7]}
 
     def download(self, offset: int, count: int) -> bytes:
         out = ctypes.create_string_buffer(max(96 * count, 1))

@@ -136,6 +136,7 @@ struct dr_srs {
     // small SRS: the table has one row per BIT (table[s][i] = 2^s * base[i]), table_wt.row[w] = start[w]; batched MSMs then tile the
     // scalar in non-adjacent form with buckets for odd digit multiples only (tiling_for)
     bool table_bit_rows = false;
+    uint32_t table_multiples = 1;        // bit rows: blocks of 256 rows, block t = the rows of (2 t + 1) * base[i] (dr_srs_precompute_multiples)
     uint32_t table_pt_words = 24;        // words per table record: 24 (packed) or 32 (one point per 128-byte line)
     int table_naf_delta = -2;            // width of the non-adjacent form of batched MSMs: -2 = chosen per call (tiling_for), -1 = never, >= 0: window_bits + this
     // derived bases for summation-by-parts commitments, keyed by log2(domain size): PS_j = sum_{i<=j} L_i(tau) G
@@ -372,7 +373,7 @@ struct PhaseTrace {
 int msm_device(dr_ctx* ctx, const uint32_t* d_bases, const uint32_t* d_scalars, size_t n, size_t batch, std::vector<drh::G1>& results,
                const MsmTable* tbl = nullptr);
 MsmTable srs_table(const dr_srs* srs, size_t offset);
-int srs_precompute(dr_ctx* ctx, dr_srs* srs, int window_bits, bool allow_bit_rows);   // dr_srs_precompute with the table shape chosen
+int srs_precompute(dr_ctx* ctx, dr_srs* srs, int window_bits, bool allow_bit_rows, int multiples = 1);   // dr_srs_precompute with the table shape chosen
 void g1_result_to_bytes(const drh::G1& r, uint8_t* out96, int* is_inf);
 int msm_batch_results_to_bytes(dr_ctx* ctx, size_t batch, uint8_t* out_be_xy, int* is_inf);
 int msm_to_bytes(dr_ctx* ctx, const uint32_t* d_bases, const uint32_t* d_scalars, size_t n, size_t batch, uint8_t* out_be_xy, int* is_inf,

@@ -42,10 +42,15 @@ int msm_sort(dr_ctx* ctx, const MsmPlan& p, const uint32_t* d_scalars, const Msm
         sp.tbl_stride = p.single ? tbl->stride : 0; sp.tbl_offset = p.single ? tbl->offset : 0; sp.capacity = (uint32_t)p.per_set_digits;
         sp.short_from = p.single ? tbl->short_from : 0xffffffffu; sp.n_short = p.single ? std::min<uint32_t>(tbl->n_short, (uint32_t)p.n) : 0;
         sp.sets = (uint32_t)p.bsets; sp.fold = p.single && tbl->fold_sign ? 1 : 0; sp.n_pad = p.n_pad; sp.digits_per_set = p.digits_per_set;
+        sp.mult = p.multiples; sp.tbl_block = 256u * sp.tbl_stride;
         return launch(ctx, "k_g1_sort_sets", [&] {
             const auto staged = p.H <= dr::SORT2_SMALL_H ? dr::k_g1_sort_sets_staged<dr::SORT2_SMALL_H, dr::SORT2_CAP_SMALL_H>
                                                          : dr::k_g1_sort_sets_staged<dr::SORT_MAX_H, dr::SORT2_CAP_LARGE_H>;
-            if (p.sort == MsmSort::sets_staged)
+            if (p.sort == MsmSort::sets_staged && p.multiples > 1)      // (the non-adjacent form has at most 2^11 buckets per set)
+                hipLaunchKernelGGL((dr::k_g1_sort_sets_staged<dr::SORT2_SMALL_H, dr::SORT2_CAP_SMALL_H, uint32_t>), dim3((unsigned)p.bsets),
+                                   dim3(dr::SORT2_BLOCK), 0, st, d_scalars, p.wt, sp, ctx->digits.as<uint32_t>(), ctx->counts.as<uint32_t>(),
+                                   ctx->offsets.as<uint32_t>(), ctx->sorted.as<uint32_t>());
+            else if (p.sort == MsmSort::sets_staged)
                 hipLaunchKernelGGL(staged, dim3((unsigned)p.bsets), dim3(dr::SORT2_BLOCK), 0, st, d_scalars, p.wt, sp, ctx->digits.as<uint16_t>(),
                                    ctx->counts.as<uint32_t>(), ctx->offsets.as<uint32_t>(), ctx->sorted.as<uint32_t>());
             else
@@ -332,6 +337,7 @@ MsmTable srs_table(const dr_srs* srs, size_t offset) {
         t.pt_words = srs->table_pt_words;
         t.bit_rows = srs->table_bit_rows;
         t.naf_delta = srs->table_naf_delta;
+        t.multiples = srs->table_multiples;
         t.stride = (uint32_t)srs->count;
         t.offset = (uint32_t)offset;
     }
@@ -701,9 +707,20 @@ int dr_srs_download(dr_ctx* ctx, const dr_srs* srs, size_t offset, size_t count,
 
 int dr_srs_precompute(dr_ctx* ctx, dr_srs* srs, int window_bits) { return srs_precompute(ctx, srs, window_bits, true); }
 
+// ... and, where the table gets a row per bit, the rows of a few small odd multiples of every base beside them (k_g1_bit_table): batched
+// MSMs then write a digit as +-(2 t + 1) b and need fewer of them (msm_recode.hip.h: for_each_wnaf_multiple_digit).  multiples = 0: the
+// library's default count; DOTRING_SRS_MULTIPLES (1, 2, 4 or 8) overrides either.
+int dr_srs_precompute_multiples(dr_ctx* ctx, dr_srs* srs, int window_bits, int multiples) {
+    if (multiples != 0 && !multiples_ok((uint32_t)multiples)) return fail(DR_ERR_INVALID, "multiples must be 0 (default), 1, 2, 4 or 8");
+    if (multiples == 0) multiples = SRS_DEFAULT_MULTIPLES;
+    const char* env = std::getenv("DOTRING_SRS_MULTIPLES");          // read per call: a process may build tables of several shapes
+    if (env && multiples_ok((uint32_t)std::atoi(env))) multiples = std::atoi(env);
+    return srs_precompute(ctx, srs, window_bits, true, multiples);
+}
+
 // bit_rows = false: window rows only (the prover's summation-by-parts bases: a few hundred scalars per vector, most of them +-1 — short,
 // uneven lists that gain nothing from a window less and measured 0.7 ms per batch slower with odd-multiple buckets)
-int srs_precompute(dr_ctx* ctx, dr_srs* srs, int window_bits, bool allow_bit_rows) {
+int srs_precompute(dr_ctx* ctx, dr_srs* srs, int window_bits, bool allow_bit_rows, int multiples) {
     TRY(use_ctx(ctx));
     if (!srs) return fail(DR_ERR_INVALID, "null argument");
     if (srs->device != ctx->device) return fail(DR_ERR_INVALID, "SRS lives on another device");
@@ -718,6 +735,7 @@ int srs_precompute(dr_ctx* ctx, dr_srs* srs, int window_bits, bool allow_bit_row
     if (srs->d_table) (void)hipFree(srs->d_table);
     srs->d_table = nullptr;
     srs->table_bit_rows = false;
+    srs->table_multiples = 1;
     // A small SRS gets a row for every bit (32 KB per base: 201 MB for the 6145 points of a 2048-point domain) — the window rows are a
     // subset of it, and batched MSMs may then recode the scalars in non-adjacent form (tiling_for).
     // DOTRING_SRS_BIT_ROWS_MB (default 512, 0 = never) bounds the table; the width of that form is chosen per call (tiling_for).
@@ -727,7 +745,19 @@ int srs_precompute(dr_ctx* ctx, dr_srs* srs, int window_bits, bool allow_bit_row
     // a third larger (A/B on one box, three alternations: 40.50 - 40.63 against 40.85 - 41.17 ms per 1024 proofs).
     const uint32_t pt_words = 32;
     bool bit_rows = allow_bit_rows && window_bits <= 16 && (size_t)256 * srs->count * 4 * pt_words <= (bit_rows_mb << 20);
-    if (bit_rows && hipMalloc((void**)&srs->d_table, (size_t)256 * srs->count * 4 * pt_words) != hipSuccess) {
+    // Blocks of rows for the odd multiples 3 P_i, 5 P_i, ... behind the first: as many of the count asked for as fit DOTRING_SRS_MULTIPLES_MB
+    // (default 4096, the whole table), the 2^31 sorted entries and the device's memory — fewer, down to none, otherwise: never an error.
+    const char* mult_env = std::getenv("DOTRING_SRS_MULTIPLES_MB");
+    const size_t mult_mb = mult_env ? (size_t)std::atol(mult_env) : 4096;
+    uint32_t mult = bit_rows && multiples_ok((uint32_t)multiples) ? (uint32_t)multiples : 1u;
+    for (; mult > 1; mult /= 2) {
+        const size_t bytes = (size_t)mult * 256 * srs->count * 4 * pt_words;
+        if (bytes > (mult_mb << 20) || (uint64_t)mult * 256 * srs->count >= (1ull << 31)) continue;
+        if (hipMalloc((void**)&srs->d_table, bytes) == hipSuccess) break;
+        (void)hipGetLastError();
+        srs->d_table = nullptr;
+    }
+    if (bit_rows && mult == 1 && hipMalloc((void**)&srs->d_table, (size_t)256 * srs->count * 4 * pt_words) != hipSuccess) {
         (void)hipGetLastError();                   // a device short of memory keeps the window rows (W rows instead of 256)
         srs->d_table = nullptr;
         bit_rows = false;
@@ -736,9 +766,10 @@ int srs_precompute(dr_ctx* ctx, dr_srs* srs, int window_bits, bool allow_bit_row
     srs->table_pt_words = pt_words;
     if (bit_rows) {
         for (int w = 0; w < wt.W; w++) wt.row[w] = wt.start[w];
-        hipLaunchKernelGGL(dr::k_g1_bit_table, dim3(div_up(srs->count, 128)), dim3(128), 0, ctx->stream, srs->d_bases, (uint32_t)srs->count, 256u,
-                           pt_words, srs->d_table);
+        hipLaunchKernelGGL(dr::k_g1_bit_table, dim3(div_up(srs->count * mult, 128)), dim3(128), 0, ctx->stream, srs->d_bases, (uint32_t)srs->count, 256u,
+                           pt_words, mult, srs->d_table);
         srs->table_bit_rows = true;
+        srs->table_multiples = mult;
     } else {
         hipLaunchKernelGGL(dr::k_g1_window_table, dim3(div_up(srs->count, 128)), dim3(128), 0, ctx->stream, srs->d_bases, (uint32_t)srs->count, wt,
                            pt_words, srs->d_table);
@@ -747,6 +778,7 @@ int srs_precompute(dr_ctx* ctx, dr_srs* srs, int window_bits, bool allow_bit_row
     if (e != hipSuccess) {
         (void)hipFree(srs->d_table);
         srs->d_table = nullptr;
+        srs->table_multiples = 1;
         return fail(DR_ERR_DEVICE, std::string("window table: ") + hipGetErrorString(e));
     }
     srs->table_wt = wt;
@@ -777,6 +809,20 @@ int dr_srs_table_info(const dr_srs* srs, size_t n, size_t batch, int info[6]) {
     info[3] = tl.c;
     info[4] = tl.naf ? 2 : 0;
     info[5] = (int)std::lround(1000.0 * (tl.naf ? tl.digits : (double)srs->table_wt.W));
+    return DR_OK;
+}
+
+// dr_srs_table_info's six values, then info[6] = the multipliers a digit of this (n, batch) may take (1: none), info[7] = the blocks of
+// rows the table holds
+int dr_srs_table_info_multiples(const dr_srs* srs, size_t n, size_t batch, int info[8]) {
+    if (!srs || !info) return fail(DR_ERR_INVALID, "null argument");
+    TRY(dr_srs_table_info(srs, n, batch, info));
+    info[6] = info[7] = 0;
+    if (!srs->d_table) return DR_OK;
+    const MsmTable t = srs_table(srs, 0);
+    const MsmPlan p = plan_msm(n, batch, &t, msm_knobs());
+    info[6] = p.error ? 1 : (int)p.multiples;
+    info[7] = (int)srs->table_multiples;
     return DR_OK;
 }
 

@@ -421,15 +421,29 @@ __global__ __launch_bounds__(256) void k_g1_window_table(const uint32_t* __restr
     }
 }
 
-// fixed-base table with one row per bit: table[s][i] = 2^s * base[i], s < rows (affine, Montgomery), one lane per base
-__global__ __launch_bounds__(128) void k_g1_bit_table(const uint32_t* __restrict__ bases, uint32_t n, uint32_t rows, uint32_t pt_words, uint32_t* __restrict__ table) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+// fixed-base table with one row per bit: table[s][i] = 2^s * base[i], s < rows (affine, Montgomery), one lane per base — and, with
+// multiples > 1, one such block of rows per small odd multiple: table[t * rows + s][i] = 2^s * ((2 t + 1) * base[i]), t < multiples, one lane
+// per (multiple, base).  Block 0 is the table without multiples, word for word.
+__global__ __launch_bounds__(128) void k_g1_bit_table(const uint32_t* __restrict__ bases, uint32_t n, uint32_t rows, uint32_t pt_words, uint32_t multiples,
+                                                      uint32_t* __restrict__ table) {
+    const uint32_t lane = blockIdx.x * blockDim.x + threadIdx.x;
+    if (lane >= n * multiples) return;
+    const uint32_t t = lane / n, i = lane - t * n;
     G1Affine a = load_affine(bases, i);
+    if (t > 0 && !a.inf) {                           // (2 t + 1) P = 2 (t P) + P, t < 8
+        G1Xyzz acc = g1_inf();
+#pragma unroll 1
+        for (int bit = 31 - __clz(t); bit >= 0; bit--) {
+            acc = g1_dbl(acc);
+            if ((t >> bit) & 1) acc = g1_madd(acc, a);
+        }
+        a = g1_to_affine_dev(g1_madd(g1_dbl(acc), a));
+    }
 #pragma unroll 1
     for (uint32_t s = 0; s < rows; s++) {
         if (s > 0 && !a.inf) a = g1_to_affine_dev(g1_dbl_affine(a));
-        store_affine(table + ((size_t)s * n + i) * (pt_words - 24), (size_t)s * n + i, a);      // record of pt_words words
+        const size_t rec = ((size_t)t * rows + s) * n + i;
+        store_affine(table + rec * (pt_words - 24), rec, a);      // record of pt_words words
     }
 }
 
@@ -456,6 +470,8 @@ struct SortSetParams {
     uint32_t n_pad, digits_per_set;     // staged variant: row length (a multiple of 8) and u16 digits reserved per set
     uint32_t sets;
     int fold;                           // table mode: scalars above r / 2 are replaced by their negatives (scalar_fold_sign)
+    uint32_t mult;                      // non-adjacent form over a table with odd-multiple rows: its multiplier count (2, 4, 8), else 1
+    uint32_t tbl_block;                 // ... and the entries between two blocks of rows, 256 * tbl_stride
 };
 
 DR_DEV void load_scalar_mod_r(const uint32_t* __restrict__ scalars, size_t idx, uint32_t (&k)[9]) {
@@ -526,6 +542,10 @@ __global__ __launch_bounds__(SORT_BLOCK) void k_g1_sort_sets(const uint32_t* __r
         uint32_t k[9];
         load_scalar_mod_r(scalars, (size_t)b * sp.n + i, k);
         if (sp.fold) (void)scalar_fold_sign(k);
+        if (wt.odd == 2 && sp.mult > 1) {
+            for_each_wnaf_multiple_digit(sp.mult, k, wt, [&](int, uint32_t, uint32_t, int32_t d) { atomicAdd(&bins[((uint32_t)(d < 0 ? -d : d) - 1u) >> 1], 1u); });
+            continue;
+        }
         if (wt.odd == 2) {
             for_each_wnaf_digit(k, wt, [&](int, uint32_t, int32_t d) { atomicAdd(&bins[((uint32_t)(d < 0 ? -d : d) - 1u) >> 1], 1u); });
             continue;
@@ -559,6 +579,14 @@ __global__ __launch_bounds__(SORT_BLOCK) void k_g1_sort_sets(const uint32_t* __r
         uint32_t k[9];
         load_scalar_mod_r(scalars, (size_t)b * sp.n + i, k);
         const bool neg = sp.fold ? scalar_fold_sign(k) : false;
+        if (wt.odd == 2 && sp.mult > 1) {
+            for_each_wnaf_multiple_digit(sp.mult, k, wt, [&](int j, uint32_t o, uint32_t t, int32_t d) {
+                const uint32_t pos = atomicAdd(&bins[((uint32_t)(d < 0 ? -d : d) - 1u) >> 1], 1u);
+                const uint32_t entry = t * sp.tbl_block + ((uint32_t)wt.row[j] + o) * sp.tbl_stride + sp.tbl_offset + i;
+                sorted[base + pos] = entry | ((d < 0) != neg ? 0x80000000u : 0u);
+            });
+            continue;
+        }
         if (wt.odd == 2) {
             for_each_wnaf_digit(k, wt, [&](int j, uint32_t o, int32_t d) {
                 const uint32_t pos = atomicAdd(&bins[((uint32_t)(d < 0 ? -d : d) - 1u) >> 1], 1u);
@@ -588,9 +616,11 @@ __global__ __launch_bounds__(SORT_BLOCK) void k_g1_sort_sets(const uint32_t* __r
 // One workgroup of 1024 lanes per set (144 KB of LDS: one workgroup per CU, four waves per SIMD).
 // Two instances: up to 2048 buckets per set (the prover's 12-bit SRS windows: 8 KB of bins, 36864 staged entries — four
 // chunks for a dense 135 k-entry set) and up to 8192 (32 KB of bins, 28672 staged entries).
-template <uint32_t MAX_H, uint32_t SORT2_CAP>
+// DigT = uint32_t: the non-adjacent form over a table with odd-multiple rows (for_each_wnaf_multiple_digit), whose digits carry the
+// multiplier index as well — sign << 31 | t << 16 | offset << 11 | bucket, four to a 16-byte vector where the u16 rows have eight.
+template <uint32_t MAX_H, uint32_t SORT2_CAP, class DigT = uint16_t>
 __global__ __launch_bounds__(SORT2_BLOCK) void k_g1_sort_sets_staged(const uint32_t* __restrict__ scalars, WindowTable wt, SortSetParams sp,
-                                                                    uint16_t* __restrict__ digits16, uint32_t* __restrict__ counts,
+                                                                    DigT* __restrict__ digits16, uint32_t* __restrict__ counts,
                                                                     uint32_t* __restrict__ offsets, uint32_t* __restrict__ sorted) {
     constexpr uint32_t SORT2_CHUNK = SORT2_CAP - SORT2_SLACK;
     __shared__ uint32_t bins[MAX_H];
@@ -615,7 +645,9 @@ __global__ __launch_bounds__(SORT2_BLOCK) void k_g1_sort_sets_staged(const uint3
         i_hi = (uint32_t)(((uint64_t)(g + 1) * sp.n + sp.groups - 1) / sp.groups);
     }
     const uint32_t n_set = i_hi - i_lo, n_pad = (n_set + 7u) & ~7u, rows = (uint32_t)(w_hi - w_lo);
-    uint16_t* dg = digits16 + (size_t)set * sp.digits_per_set;
+    constexpr bool MULT = sizeof(DigT) == 4;
+    constexpr uint32_t PER = 16 / sizeof(DigT);                                      // digits per 16-byte vector
+    DigT* dg = digits16 + (size_t)set * sp.digits_per_set;
     for (uint32_t j = tid; j < H; j += SORT2_BLOCK) bins[j] = 0;
     for (uint32_t k = tid; k <= SORT2_MAX_CHUNKS; k += SORT2_BLOCK) { cs[k] = 0xffffffffu; jb[k] = H; }
     __syncthreads();
@@ -625,7 +657,17 @@ __global__ __launch_bounds__(SORT2_BLOCK) void k_g1_sort_sets_staged(const uint3
             uint32_t k[9];
             load_scalar_mod_r(scalars, (size_t)b * sp.n + i_lo + ii, k);
             const bool neg = sp.fold ? scalar_fold_sign(k) : false;
-            if (wt.odd == 2) {
+            if constexpr (MULT) {
+                for_each_wnaf_multiple_digit<true>(sp.mult, k, wt, [&](int j, uint32_t o, uint32_t t, int32_t d) {
+                    uint32_t enc = WNAF_EMPTY32;
+                    if (d != 0) {
+                        const uint32_t bin = ((uint32_t)(d < 0 ? -d : d) - 1u) >> 1;
+                        atomicAdd(&bins[bin], 1u);
+                        enc = bin | (o << 11) | (t << 16) | ((d < 0) != neg ? 0x80000000u : 0u);
+                    }
+                    dg[(size_t)j * n_pad + ii] = enc;
+                });
+            } else if (wt.odd == 2) {
                 for_each_wnaf_digit<true>(k, wt, [&](int j, uint32_t o, int32_t d) {
                     uint32_t enc = WNAF_EMPTY16;
                     if (d != 0) {
@@ -642,10 +684,10 @@ __global__ __launch_bounds__(SORT2_BLOCK) void k_g1_sort_sets_staged(const uint3
                 if (d != 0) {
                     atomicAdd(&bins[digit_bin(wt, w, mag, row)], 1u);
                 }
-                dg[(size_t)(w - w_lo) * n_pad + ii] = (uint16_t)(enc | ((d < 0) != neg && d != 0 ? 0x8000u : 0u));
+                dg[(size_t)(w - w_lo) * n_pad + ii] = (DigT)(enc | ((d < 0) != neg && d != 0 ? 0x8000u : 0u));
             });
         } else {
-            for (uint32_t r = 0; r < rows; r++) dg[(size_t)r * n_pad + ii] = wt.odd == 2 ? (uint16_t)WNAF_EMPTY16 : (uint16_t)0;
+            for (uint32_t r = 0; r < rows; r++) dg[(size_t)r * n_pad + ii] = MULT ? (DigT)WNAF_EMPTY32 : wt.odd == 2 ? (DigT)WNAF_EMPTY16 : (DigT)0;
         }
     }
     __syncthreads();
@@ -685,8 +727,8 @@ __global__ __launch_bounds__(SORT2_BLOCK) void k_g1_sort_sets_staged(const uint3
     for (uint32_t k = 0; k < K; k++) {
         const uint32_t j_lo = jb[k], j_hi = jb[k + 1], p_lo = cs[k], p_hi = cs[k + 1], c0 = k * SORT2_CHUNK;
         if (j_lo < j_hi) {
-            // the rows x (n_pad / 8) sixteen-byte vectors of the set as one index space (no idle lanes at row ends)
-            const uint32_t nv = n_pad / 8, nvec = rows * nv;
+            // the rows x (n_pad / PER) sixteen-byte vectors of the set as one index space (no idle lanes at row ends)
+            const uint32_t nv = n_pad / PER, nvec = rows * nv;
             const uint4* vecs = reinterpret_cast<const uint4*>(dg);
             uint32_t r = 0, v = tid;
             for (uint32_t idx = tid; idx < nvec; idx += SORT2_BLOCK, v += SORT2_BLOCK) {
@@ -696,7 +738,19 @@ __global__ __launch_bounds__(SORT2_BLOCK) void k_g1_sort_sets_staged(const uint3
                     const uint4 q = vecs[idx];
                     const uint32_t words[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
-                    for (int t = 0; t < 8; t++) {
+                    for (int t = 0; t < (int)PER; t++) {
+                        if constexpr (MULT) {
+                            const uint32_t dd = words[t], j = ((dd >> 11) & 15u) == 15u ? 0xffffffffu : (dd & 0x7ffu);
+                            if (j >= j_lo && j < j_hi) {
+                                const uint32_t up = ((dd >> 16) & 7u) * sp.tbl_block + ((dd >> 11) & 15u) * sp.tbl_stride;
+                                const uint32_t pos = atomicAdd(&bins[j], 1u);
+                                const uint32_t entry = (row_entry + up + v * PER + (uint32_t)t) | (dd & 0x80000000u);
+                                const uint32_t rel = pos - c0;
+                                if (rel < SORT2_CAP) stage[rel] = entry;
+                                else sorted[base + pos] = entry;
+                            }
+                            continue;
+                        }
                         const uint32_t dd = (words[t >> 1] >> (16 * (t & 1))) & 0xffffu;
                         // dd == 0 (windows) / offset field 15 (non-adjacent form) -> 0xffffffff: outside every range
                         const uint32_t j = wt.odd == 2 ? (((dd >> 11) & 15u) == 15u ? 0xffffffffu : (dd & 0x7ffu)) : (dd & 0x7fffu) - 1u;
@@ -706,7 +760,7 @@ __global__ __launch_bounds__(SORT2_BLOCK) void k_g1_sort_sets_staged(const uint3
                                 up = ((dd >> 11) & 15u) * sp.tbl_stride;      // the digit's offset in its slot: row[slot] + offset
                             }
                             const uint32_t pos = atomicAdd(&bins[j], 1u);
-                            const uint32_t entry = (row_entry + up + v * 8 + (uint32_t)t) | ((dd & 0x8000u) << 16);
+                            const uint32_t entry = (row_entry + up + v * PER + (uint32_t)t) | ((dd & 0x8000u) << 16);
                             const uint32_t rel = pos - c0;
                             if (rel < SORT2_CAP) stage[rel] = entry;
                             else sorted[base + pos] = entry;

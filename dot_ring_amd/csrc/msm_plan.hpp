@@ -151,6 +151,7 @@ struct MsmTable {
     uint32_t pt_words = 24;              // words per table record
     bool bit_rows = false;               // the table has a row per bit: a call may recode the scalars as it likes (non-adjacent form)
     int naf_delta = -2;                  // see dr_srs::table_naf_delta
+    uint32_t multiples = 1;              // bit rows only: blocks of 256 rows, block t = the rows of (2 t + 1) * base (1, 2, 4 or 8)
     uint32_t stride = 0, offset = 0;
     uint32_t short_from = 0xffffffffu, n_short = 0;   // batched MSM: vectors from this index on are zero beyond n_short (sort hint)
     bool fold_sign = false;              // scalars above r / 2 enter as their negatives (difference columns: r - 1 becomes -1, one digit)
@@ -168,7 +169,16 @@ constexpr size_t L4_BELOW = (size_t)1 << 15;
 
 // the tiling msm_device takes for `batch` MSMs of n points over this table: naf = width-c non-adjacent form (bit-row tables, hundreds of
 // MSMs), otherwise the table's window rows; slots = digit rows per scalar, digits = expected non-zero digits per scalar
-struct Tiling { bool naf; int c, slots; double digits; };
+struct Tiling { bool naf; int c, slots; double digits; uint32_t multiples = 1; };
+
+// Expected non-zero digits per uniformly random scalar of the non-adjacent form over a table with M = 2, 4, 8 odd multiples
+// (msm_recode.hip.h: for_each_wnaf_multiple_digit), widths 9 .. 13: measured over 20 000 scalars by tests/native/recode_multiples_check.cpp,
+// which prints this table
+constexpr double NAF_MULTIPLE_DIGITS[5][3] = {{24.65, 23.20, 21.83}, {22.59, 21.40, 20.21}, {20.85, 19.83, 18.84}, {19.36, 18.50, 17.64}, {18.06, 17.32, 16.60}};
+inline bool multiples_ok(uint32_t m) { return m == 1 || m == 2 || m == 4 || m == 8; }
+// the count dr_srs_precompute_multiples(.., 0) asks for (the walk gathers from 1.6 GB at 97 % of its rate over
+// 201 MB, so the largest count wins: 11.7 % fewer additions at 8 against 8.0 % at 4)
+constexpr int SRS_DEFAULT_MULTIPLES = 8;
 
 // A table with a row per bit and hundreds of MSMs (the batched prover): a digit may sit at ANY bit position, so every scalar is recoded
 // in width-w non-adjacent form (msm_recode.hip.h: for_each_wnaf_digit): 256 / (w + 1) + ~0.55 odd digits on average — 18.8 for w = 13
@@ -182,7 +192,8 @@ struct Tiling { bool naf; int c, slots; double digits; };
 // (measured: level 1 + set scan per bucket against the walk's time per entry): w = 13 for the 3N = 6144-point vectors of domain 2048
 // and the 12288 of domain 4096.
 inline Tiling tiling_for(const MsmTable& t, size_t n, size_t batch, bool naf_tiling) {
-    Tiling none{false, 0, 0, 0.0};
+    Tiling none{false, 0, 0, 0.0, 1};
+    const uint32_t M = multiples_ok(t.multiples) ? t.multiples : 1;
     if (!t.table || !t.bit_rows || t.naf_delta == -1 || batch < 256 || n == 0 || !naf_tiling) return none;
     const int cn = t.wt.cmax;
     const int lo = t.naf_delta >= 0 ? cn + t.naf_delta : cn - 1, hi = t.naf_delta >= 0 ? cn + t.naf_delta : cn + 2;
@@ -193,13 +204,14 @@ inline Tiling tiling_for(const MsmTable& t, size_t n, size_t batch, bool naf_til
         const size_t H = (size_t)1 << (w - 2), slots = (256 + w - 1) / w;
         if (batch * (H / 16) < L4_BELOW) continue;
         if ((n + 64) * slots > ((size_t)1 << 20) || batch * (n + 64) * slots >= (1ull << 32)) continue;
-        const double digits = 256.0 / (w + 1) + 0.55;        // (+ the evenly shared digits at the top and the end effects: 18.8 measured at w = 13)
+        // (+ the evenly shared digits at the top and the end effects: 18.8 measured at w = 13)
+        const double digits = M == 1 ? 256.0 / (w + 1) + 0.55 : NAF_MULTIPLE_DIGITS[w - 9][M == 2 ? 0 : M == 4 ? 1 : 2];
         if (t.naf_delta < 0 && (double)n * digits / (double)H > 160.0) continue;      // the fullest lists (~4x) stay near the one-lane limit
         // (1.5 addition-equivalents per bucket: with the widths 12 and 13 both admitted at ring 256 — 3N = 3072 terms, 1024 proofs — the
         //  narrower one saved 0.15 ms of reduction per step and cost 1.15 ms of walk; the 5.2 of the first fit priced the reduction at its
         //  issue rate, which launches of this size do not reach)
         const double cost = (double)n * digits + 1.5 * (double)H;
-        if (!best.naf || cost < best_cost) { best = Tiling{true, w, (int)slots, digits}; best_cost = cost; }
+        if (!best.naf || cost < best_cost) { best = Tiling{true, w, (int)slots, digits, M}; best_cost = cost; }
     }
     return best;
 }
@@ -215,6 +227,7 @@ struct MsmPlan {
     size_t n = 0, batch = 0;             // points per MSM, MSMs
     bool single = false;                 // over a fixed-base table: a bucket set per (MSM, index group) spans all windows
     dr::WindowTable wt{};                // the digit rows; wt.odd == 2: non-adjacent form with odd-multiple buckets
+    uint32_t multiples = 1;              // non-adjacent form over a table with odd-multiple rows: digits +-(2 t + 1) b, t < multiples (u32 digit rows)
     uint32_t H = 0, L = 0, T = 0, groups = 1;   // buckets per set, per first-level chunk, chunks per set, index groups per MSM
     size_t windows = 0, bsets = 0, nbuckets = 0, ndigits = 0, per_set_scalars = 0, per_set_digits = 0;
     MsmSort sort = MsmSort::global;
@@ -236,10 +249,10 @@ inline MsmPlan msm_shape(size_t n, size_t batch, const MsmTable* tbl, const MsmK
     MsmPlan p;
     p.n = n, p.batch = batch, p.single = tbl != nullptr && tbl->table != nullptr;
     if (p.single) {
-        const Tiling tl = allow_naf ? tiling_for(*tbl, n, batch, k.naf_tiling) : Tiling{false, 0, 0, 0.0};
+        const Tiling tl = allow_naf ? tiling_for(*tbl, n, batch, k.naf_tiling) : Tiling{false, 0, 0, 0.0, 1};
         if (tl.naf) {           // slots of the non-adjacent form: positions [c j, c j + c) of k << shift (msm_recode.hip.h: for_each_wnaf_digit)
             const int shift = tl.slots * tl.c - 256;
-            p.wt.W = tl.slots, p.wt.cmax = tl.c, p.wt.odd = 2;
+            p.wt.W = tl.slots, p.wt.cmax = tl.c, p.wt.odd = 2, p.multiples = tl.multiples;
             for (int j = 0; j < p.wt.W; j++)
                 p.wt.start[j] = (uint8_t)(tl.c * j), p.wt.row[j] = (uint8_t)(j ? tl.c * j - shift : 0), p.wt.width[j] = (uint8_t)tl.c;
         } else {
@@ -289,7 +302,8 @@ inline MsmPlan plan_msm(size_t n, size_t batch, const MsmTable* tbl, const MsmKn
     if (p.wt.odd && !(p.sort == MsmSort::sets && p.reduce == MsmReduce::set_scan)) p = msm_shape(n, batch, tbl, k, false);
     const uint32_t H = p.H, T = p.T, W = (uint32_t)p.wt.W;
     const size_t bsets = p.bsets;
-    if (p.single && ((uint64_t)p.wt.row[W - 1] + p.wt.cmax + 1) * tbl->stride >= (1ull << 31)) { p.error = "window table too large"; return p; }
+    // (a sorted entry is (t * 256 + row) * stride + i | sign << 31: the last block of a table with multiples counts from (multiples - 1) * 256)
+    if (p.single && ((uint64_t)(p.multiples - 1) * 256 + p.wt.row[W - 1] + p.wt.cmax + 1) * tbl->stride >= (1ull << 31)) { p.error = "window table too large"; return p; }
     p.nbuckets = bsets * (size_t)H, p.ndigits = p.windows * n;
     if (p.nbuckets >= (1ull << 32) || p.ndigits >= (1ull << 32)) { p.error = "MSM batch too large for one launch (split the batch)"; return p; }
 
@@ -358,7 +372,7 @@ inline MsmPlan plan_msm(size_t n, size_t batch, const MsmTable* tbl, const MsmKn
     // (a partition sort's room covers the global-atomic sort its second pass may fall back to; cursor: + fill counters, overflow flag)
     const bool global = p.sort == MsmSort::global, part = p.sort == MsmSort::partition;
     b.sorted = global ? p.ndigits * 4 : bsets * p.per_set_digits * 4;
-    b.digits = global ? p.ndigits * 4 : part ? p.nparts() * p.part_cap * 8 : bsets * (size_t)p.digits_per_set * 2;
+    b.digits = global ? p.ndigits * 4 : part ? p.nparts() * p.part_cap * 8 : bsets * (size_t)p.digits_per_set * (p.multiples > 1 ? 4 : 2);
     b.cursor = global ? p.nbuckets * 4 : part ? std::max(p.nparts() + 1, p.nbuckets) * 4 : 0;
     b.part_base = part ? p.nparts() * 4 : 0;
     b.result = batch > 1 ? batch * 192 : 0;

@@ -92,4 +92,89 @@ DR_RECODE_FN void for_each_wnaf_digit(const uint32_t (&k)[9], const WindowTable&
     }
 }
 
+// The same form over a table that also holds the rows of a few small odd multiples of every base (block t: 2^s ((2 t + 1) P_i), t < M):
+// a digit may be written d = +-m b with m = 2 t + 1 and b the odd bucket value, |b| < 2^(w-1), so the recoder is free to pick, among the
+// M multipliers, the one whose digit clears the most bits of what is left of the scalar — 17.3 digits per scalar at w = 13 with
+// {1, 3, 5, 7} where m = 1 alone has 18.8.  f(j, o, t, b): sum +-(2 t + 1) b 2^(row[j] + o) = k exactly.
+// With n = (K >> P) + c the value left at the position P of the next digit (n odd): for every m, b_m is the centred odd residue of
+// n / m mod 2^w, the remainder n - m b_m is a multiple of 2^w, and the m whose remainder has the most trailing zeros wins (counted over
+// the WNAF_LOOK bits after the w cleared ones, which is what the slot's 64-bit chunk always holds; ties go to the smaller m).  The scan
+// resumes w positions on with the carry c = (low w bits of n - m b_m) >> w, a small SIGNED value now (|c| <= M), so the first position
+// of a digit is found by adding the carry to the slot's bits rather than by complementing them.  Within WNAF_ZONE * w bits of the top the
+// rule is for_each_wnaf_digit's, m = 1 and the remaining bits shared evenly: its digit takes any carry in and leaves 0 or 1, so the sum
+// closes at the top as it does there, the top digits stay on rows <= 255 and the lowest buckets are no fuller.  As there: at most one
+// digit per slot (a digit clears at least w positions), and the words of K are indexed by the unrolled loop only.
+constexpr int WNAF_MAX_MULTIPLES = 8;
+constexpr uint32_t WNAF_LOOK = 8;
+constexpr uint32_t WNAF_EMPTY32 = 0x7fffffffu;            // u32 digit rows of tables with multiples: sign << 31 | t << 16 | offset << 11 | bucket
+template <int M, bool WITH_ZEROS = false, class F>
+DR_RECODE_FN void for_each_wnaf_multiple_digit(const uint32_t (&k)[9], const WindowTable& wt, F&& f) {
+    static_assert(M >= 1 && M <= WNAF_MAX_MULTIPLES, "multiplier count");
+    constexpr uint32_t MINV[WNAF_MAX_MULTIPLES] = {1u, 0xaaabu, 0xcccdu, 0x6db7u, 0x8e39u, 0x8ba3u, 0x4ec5u, 0xeeefu};   // (2 t + 1)^-1 mod 2^16
+    const uint32_t w = (uint32_t)wt.cmax, wmask = (1u << w) - 1u, L = (uint32_t)wt.W * w, shift = L - 256u;      // shift < w <= 13
+    uint32_t K[10];
+    K[0] = k[0] << shift;
+#pragma unroll
+    for (int i = 1; i < 9; i++) K[i] = shift ? (k[i] << shift) | (k[i - 1] >> (32u - shift)) : k[i];
+    K[9] = 0;
+    int32_t c = 0;                                        // signed carry
+    uint32_t r = 0;                                       // first offset of the slot at which a digit may start
+    int j = 0;
+#pragma unroll
+    for (int li = 0; li < 9; li++) {
+        const uint64_t two = (uint64_t)K[li] | ((uint64_t)K[li + 1] << 32);
+        while (j < wt.W && (wt.start[j] >> 5) == li) {
+            const uint64_t chunk = two >> (wt.start[j] & 31);                       // >= 33 valid bits; offset + width + look <= 2 w - 1 + 8 = 33 are used
+            const uint32_t rest = (uint32_t)(chunk >> r);
+            const uint32_t live = (rest + (uint32_t)c) & ((1u << (w - r)) - 1u);    // the slot's positions from r on, carry added
+            if (live) {
+                const uint32_t z = (uint32_t)__builtin_ctz(live), o = r + z;
+                const int32_t co = ((int32_t)(rest & ((1u << z) - 1u)) + c) >> z;   // carry into position o (exact: the bits below are zero)
+                const uint32_t R = L - ((uint32_t)wt.start[j] + o);                  // bits from this position to the top
+                const uint32_t at = (uint32_t)(chunk >> o);
+                if (R <= WNAF_ZONE * w) {
+                    const uint32_t q = (R + w - 1u) / w;                             // digits still to come (1 .. WNAF_ZONE)
+                    const uint32_t a = (R + q - 1u) / q;
+                    const int32_t n = (int32_t)(at & ((1u << a) - 1u)) + co;
+                    const uint32_t v = (uint32_t)n & ((1u << a) - 1u);               // odd
+                    const int32_t d = v > (1u << (a - 1)) ? (int32_t)v - (int32_t)(1u << a) : (int32_t)v;
+                    c = (n - d) >> a;
+                    f(j, j == 0 ? o - shift : o, 0u, d);
+                    r = o + a - w;
+                } else {
+                    const int32_t n = (int32_t)(at & wmask) + co;
+                    const uint32_t u = (uint32_t)n & wmask, above = (uint32_t)(chunk >> (o + w));
+                    uint32_t bt = 0, bz = 0;
+                    int32_t bb = 0, bc = 0;
+#pragma unroll
+                    for (int t = 0; t < M; t++) {
+                        const uint32_t bu = (u * MINV[t]) & wmask;                   // odd
+                        const int32_t b = bu > (1u << (w - 1)) ? (int32_t)bu - (int32_t)(1u << w) : (int32_t)bu;
+                        const int32_t cm = (n - (2 * t + 1) * b) >> w;
+                        const uint32_t y = (above + (uint32_t)cm) & ((1u << WNAF_LOOK) - 1u);
+                        const uint32_t tz = y ? (uint32_t)__builtin_ctz(y) : WNAF_LOOK;
+                        if (t == 0 || tz > bz) { bt = (uint32_t)t; bz = tz; bb = b; bc = cm; }
+                    }
+                    c = bc;
+                    f(j, j == 0 ? o - shift : o, bt, bb);
+                    r = o;
+                }
+            } else {
+                c = ((int32_t)(rest & ((1u << (w - r)) - 1u)) + c) >> (w - r);
+                if (WITH_ZEROS) f(j, 0u, 0u, 0);
+                r = 0;
+            }
+            j++;
+        }
+    }
+}
+
+// run-time multiplier count (2, 4 or 8) -> the instance
+template <bool WITH_ZEROS = false, class F>
+DR_RECODE_FN void for_each_wnaf_multiple_digit(uint32_t multiples, const uint32_t (&k)[9], const WindowTable& wt, F&& f) {
+    if (multiples == 2) for_each_wnaf_multiple_digit<2, WITH_ZEROS>(k, wt, f);
+    else if (multiples == 4) for_each_wnaf_multiple_digit<4, WITH_ZEROS>(k, wt, f);
+    else for_each_wnaf_multiple_digit<8, WITH_ZEROS>(k, wt, f);
+}
+
 }  // namespace dr
