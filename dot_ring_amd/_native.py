@@ -492,7 +492,8 @@ class Srs:
 
     def precompute(self, window_bits: int, multiples: int = 1) -> "Srs":
         """Build (or with 0 drop) the fixed-base window table in HBM.  multiples: blocks of rows of a bit-row table, one per small odd
-        multiple of the bases (2, 4, 8; 0 = the library's default count; dr_srs_precompute_multiples); 1 = the plain table."""
+        multiple of the bases (2, 4, 8, 16, 32; 0 = the library's default count, 8; -1 = the count it recommends for batched proving;
+        dr_srs_precompute_multiples); 1 = the plain table."""
         if multiples == 1:
             _check(lib().dr_srs_precompute(self.ctx.handle, self.handle, window_bits))
         else:

@@ -709,10 +709,13 @@ int dr_srs_precompute(dr_ctx* ctx, dr_srs* srs, int window_bits) { return srs_pr
 
 // ... and, where the table gets a row per bit, the rows of a few small odd multiples of every base beside them (k_g1_bit_table): batched
 // MSMs then write a digit as +-(2 t + 1) b and need fewer of them (msm_recode.hip.h: for_each_wnaf_multiple_digit).  multiples = 0: the
-// library's default count; DOTRING_SRS_MULTIPLES (1, 2, 4 or 8) overrides either.
+// library's default count, 8; -1: the count it recommends for batched proving (SRS_BATCH_MULTIPLES); DOTRING_SRS_MULTIPLES (1, 2, 4, 8,
+// 16 or 32) overrides any of them.
 int dr_srs_precompute_multiples(dr_ctx* ctx, dr_srs* srs, int window_bits, int multiples) {
-    if (multiples != 0 && !multiples_ok((uint32_t)multiples)) return fail(DR_ERR_INVALID, "multiples must be 0 (default), 1, 2, 4 or 8");
+    if (multiples != 0 && multiples != -1 && !multiples_ok((uint32_t)multiples))
+        return fail(DR_ERR_INVALID, "multiples must be 0 (default), -1 (recommended for batched proving), 1, 2, 4, 8, 16 or 32");
     if (multiples == 0) multiples = SRS_DEFAULT_MULTIPLES;
+    if (multiples == -1) multiples = SRS_BATCH_MULTIPLES;
     const char* env = std::getenv("DOTRING_SRS_MULTIPLES");          // read per call: a process may build tables of several shapes
     if (env && multiples_ok((uint32_t)std::atoi(env))) multiples = std::atoi(env);
     return srs_precompute(ctx, srs, window_bits, true, multiples);
@@ -746,9 +749,10 @@ int srs_precompute(dr_ctx* ctx, dr_srs* srs, int window_bits, bool allow_bit_row
     const uint32_t pt_words = 32;
     bool bit_rows = allow_bit_rows && window_bits <= 16 && (size_t)256 * srs->count * 4 * pt_words <= (bit_rows_mb << 20);
     // Blocks of rows for the odd multiples 3 P_i, 5 P_i, ... behind the first: as many of the count asked for as fit DOTRING_SRS_MULTIPLES_MB
-    // (default 4096, the whole table), the 2^31 sorted entries and the device's memory — fewer, down to none, otherwise: never an error.
+    // (default SRS_MULTIPLES_MB, the whole table), the 2^31 sorted entries and the device's memory — half as many, and half again down to
+    // none, otherwise: never an error.
     const char* mult_env = std::getenv("DOTRING_SRS_MULTIPLES_MB");
-    const size_t mult_mb = mult_env ? (size_t)std::atol(mult_env) : 4096;
+    const size_t mult_mb = mult_env ? (size_t)std::atol(mult_env) : SRS_MULTIPLES_MB;
     uint32_t mult = bit_rows && multiples_ok((uint32_t)multiples) ? (uint32_t)multiples : 1u;
     for (; mult > 1; mult /= 2) {
         const size_t bytes = (size_t)mult * 256 * srs->count * 4 * pt_words;

@@ -430,7 +430,7 @@ __global__ __launch_bounds__(128) void k_g1_bit_table(const uint32_t* __restrict
     if (lane >= n * multiples) return;
     const uint32_t t = lane / n, i = lane - t * n;
     G1Affine a = load_affine(bases, i);
-    if (t > 0 && !a.inf) {                           // (2 t + 1) P = 2 (t P) + P, t < 8
+    if (t > 0 && !a.inf) {                           // (2 t + 1) P = 2 (t P) + P, t < 32
         G1Xyzz acc = g1_inf();
 #pragma unroll 1
         for (int bit = 31 - __clz(t); bit >= 0; bit--) {
@@ -470,7 +470,7 @@ struct SortSetParams {
     uint32_t n_pad, digits_per_set;     // staged variant: row length (a multiple of 8) and u16 digits reserved per set
     uint32_t sets;
     int fold;                           // table mode: scalars above r / 2 are replaced by their negatives (scalar_fold_sign)
-    uint32_t mult;                      // non-adjacent form over a table with odd-multiple rows: its multiplier count (2, 4, 8), else 1
+    uint32_t mult;                      // non-adjacent form over a table with odd-multiple rows: its multiplier count (2, 4, 8, 16, 32), else 1
     uint32_t tbl_block;                 // ... and the entries between two blocks of rows, 256 * tbl_stride
 };
 
@@ -742,7 +742,7 @@ __global__ __launch_bounds__(SORT2_BLOCK) void k_g1_sort_sets_staged(const uint3
                         if constexpr (MULT) {
                             const uint32_t dd = words[t], j = ((dd >> 11) & 15u) == 15u ? 0xffffffffu : (dd & 0x7ffu);
                             if (j >= j_lo && j < j_hi) {
-                                const uint32_t up = ((dd >> 16) & 7u) * sp.tbl_block + ((dd >> 11) & 15u) * sp.tbl_stride;
+                                const uint32_t up = ((dd >> 16) & 31u) * sp.tbl_block + ((dd >> 11) & 15u) * sp.tbl_stride;
                                 const uint32_t pos = atomicAdd(&bins[j], 1u);
                                 const uint32_t entry = (row_entry + up + v * PER + (uint32_t)t) | (dd & 0x80000000u);
                                 const uint32_t rel = pos - c0;

@@ -151,7 +151,7 @@ struct MsmTable {
     uint32_t pt_words = 24;              // words per table record
     bool bit_rows = false;               // the table has a row per bit: a call may recode the scalars as it likes (non-adjacent form)
     int naf_delta = -2;                  // see dr_srs::table_naf_delta
-    uint32_t multiples = 1;              // bit rows only: blocks of 256 rows, block t = the rows of (2 t + 1) * base (1, 2, 4 or 8)
+    uint32_t multiples = 1;              // bit rows only: blocks of 256 rows, block t = the rows of (2 t + 1) * base (1, 2, 4, 8, 16 or 32)
     uint32_t stride = 0, offset = 0;
     uint32_t short_from = 0xffffffffu, n_short = 0;   // batched MSM: vectors from this index on are zero beyond n_short (sort hint)
     bool fold_sign = false;              // scalars above r / 2 enter as their negatives (difference columns: r - 1 becomes -1, one digit)
@@ -171,14 +171,20 @@ constexpr size_t L4_BELOW = (size_t)1 << 15;
 // MSMs), otherwise the table's window rows; slots = digit rows per scalar, digits = expected non-zero digits per scalar
 struct Tiling { bool naf; int c, slots; double digits; uint32_t multiples = 1; };
 
-// Expected non-zero digits per uniformly random scalar of the non-adjacent form over a table with M = 2, 4, 8 odd multiples
-// (msm_recode.hip.h: for_each_wnaf_multiple_digit), widths 9 .. 13: measured over 20 000 scalars by tests/native/recode_multiples_check.cpp,
-// which prints this table
-constexpr double NAF_MULTIPLE_DIGITS[5][3] = {{24.65, 23.20, 21.83}, {22.59, 21.40, 20.21}, {20.85, 19.83, 18.84}, {19.36, 18.50, 17.64}, {18.06, 17.32, 16.60}};
-inline bool multiples_ok(uint32_t m) { return m == 1 || m == 2 || m == 4 || m == 8; }
-// the count dr_srs_precompute_multiples(.., 0) asks for (the walk gathers from 1.6 GB at 97 % of its rate over
-// 201 MB, so the largest count wins: 11.7 % fewer additions at 8 against 8.0 % at 4)
+// Expected non-zero digits per uniformly random scalar of the non-adjacent form over a table with M = 2, 4, 8, 16, 32 odd multiples
+// (msm_recode.hip.h: for_each_wnaf_multiple_digit), widths 9 .. 13: measured over 20 000 scalars by tests/native/recode_multiples_check.cpp
+// (2, 4, 8) and tests/native/recode_multiples_wide_check.cpp (16, 32), which print this table
+constexpr double NAF_MULTIPLE_DIGITS[5][5] = {{24.65, 23.20, 21.83, 20.54, 19.44}, {22.59, 21.40, 20.21, 19.07, 18.12}, {20.85, 19.83, 18.84, 17.87, 17.00},
+                                              {19.36, 18.50, 17.64, 16.82, 16.02}, {18.06, 17.32, 16.60, 15.87, 15.15}};
+inline bool multiples_ok(uint32_t m) { return m == 1 || m == 2 || m == 4 || m == 8 || m == 16 || m == 32; }
+// the count dr_srs_precompute_multiples(.., 0) asks for
 constexpr int SRS_DEFAULT_MULTIPLES = 8;
+// the count dr_srs_precompute_multiples(.., -1) asks for, what the batched prover takes (the walk gathers
+// from 6.4 GB at 98 % of its rate over 1.6 GB and has 8.8 % fewer entries; the sort pays 0.6 ms of the 2.7 ms won; 16 gained less)
+constexpr int SRS_BATCH_MULTIPLES = 32;
+// default of DOTRING_SRS_MULTIPLES_MB: the 6145-point table of a 2048-point domain at 32 blocks is 6145 MiB; the 12289 points of a
+// 4096-point domain get 16 blocks under it (6145 MiB again; 32 would be 12289 MiB: raise the knob to take them)
+constexpr size_t SRS_MULTIPLES_MB = 8192;
 
 // A table with a row per bit and hundreds of MSMs (the batched prover): a digit may sit at ANY bit position, so every scalar is recoded
 // in width-w non-adjacent form (msm_recode.hip.h: for_each_wnaf_digit): 256 / (w + 1) + ~0.55 odd digits on average — 18.8 for w = 13
@@ -205,7 +211,7 @@ inline Tiling tiling_for(const MsmTable& t, size_t n, size_t batch, bool naf_til
         if (batch * (H / 16) < L4_BELOW) continue;
         if ((n + 64) * slots > ((size_t)1 << 20) || batch * (n + 64) * slots >= (1ull << 32)) continue;
         // (+ the evenly shared digits at the top and the end effects: 18.8 measured at w = 13)
-        const double digits = M == 1 ? 256.0 / (w + 1) + 0.55 : NAF_MULTIPLE_DIGITS[w - 9][M == 2 ? 0 : M == 4 ? 1 : 2];
+        const double digits = M == 1 ? 256.0 / (w + 1) + 0.55 : NAF_MULTIPLE_DIGITS[w - 9][M == 2 ? 0 : M == 4 ? 1 : M == 8 ? 2 : M == 16 ? 3 : 4];
         if (t.naf_delta < 0 && (double)n * digits / (double)H > 160.0) continue;      // the fullest lists (~4x) stay near the one-lane limit
         // (1.5 addition-equivalents per bucket: with the widths 12 and 13 both admitted at ring 256 — 3N = 3072 terms, 1024 proofs — the
         //  narrower one saved 0.15 ms of reduction per step and cost 1.15 ms of walk; the 5.2 of the first fit priced the reduction at its

@@ -104,13 +104,37 @@ DR_RECODE_FN void for_each_wnaf_digit(const uint32_t (&k)[9], const WindowTable&
 // rule is for_each_wnaf_digit's, m = 1 and the remaining bits shared evenly: its digit takes any carry in and leaves 0 or 1, so the sum
 // closes at the top as it does there, the top digits stay on rows <= 255 and the lowest buckets are no fuller.  As there: at most one
 // digit per slot (a digit clears at least w positions), and the words of K are indexed by the unrolled loop only.
-constexpr int WNAF_MAX_MULTIPLES = 8;
+// How a multiplier is tried: with N = n + 2^w (the WNAF_LOOK bits above), taken mod 2^(w + WNAF_LOOK), and q = N m^-1, b_m is the low w
+// bits of q, sign-extended, and (N - m b_m) / 2^w = m (q - b_m) / 2^w mod 2^WNAF_LOOK; m is odd and (q - b_m) / 2^w = (q + 2^(w-1)) >> w
+// (the half added carries into bit w exactly when b_m is negative), so the zeros won are the trailing zeros of q + 2^(w-1) from bit w
+// up.  N and the inverse (21 bits suffice: w + WNAF_LOOK <= 21) are below 2^24, so the product and the half are ONE full-rate 24-bit
+// multiply-add; masking the low w bits off with a stop bit at w + WNAF_LOOK, counting, and folding (zeros, 31 - t) into one key whose
+// maximum is the winner (more zeros first, then the smaller t) are four more instructions - against a dozen for the residue, the
+// centring, the product, the carry and the look-ahead sum of every candidate.  Only the winner's inverse (Newton, at run time), b and
+// carry are then worked out.
+// Bounds for M <= 32 (m <= 63): |n - m b| < 2^w + 32 + 63 2^(w-1), so |c| <= 32 = M and every value fits an int32_t by far; a carry
+// is ADDED to bits already taken from the chunk, so it uses none of the chunk's bits: the highest one read is that of the look-ahead,
+// offset + w + WNAF_LOOK <= (w - 1) + w + 8 = 33 for w = 13, and a 64-bit chunk shifted by at most 31 holds 33.  In the top zone a digit
+// has a >= 7 bits (w >= 9) and takes a carry in of -32 .. 32 > -2^(a-1): it leaves 0 or 1 as before.
+constexpr int WNAF_MAX_MULTIPLES = 32;
 constexpr uint32_t WNAF_LOOK = 8;
 constexpr uint32_t WNAF_EMPTY32 = 0x7fffffffu;            // u32 digit rows of tables with multiples: sign << 31 | t << 16 | offset << 11 | bucket
+// (2 t + 1)^-1 mod 2^32 by Newton's iteration: x = m is right to 3 bits (m m = 1 mod 8), every step doubles them
+constexpr uint32_t wnaf_multiplier_inverse(uint32_t t) {
+    const uint32_t m = 2u * t + 1u;
+    uint32_t x = m;
+    for (int i = 0; i < 4; i++) x *= 2u - m * x;
+    return x;
+}
+// a b + c for a, b < 2^24 (mod 2^32): v_mad_u32_u24 on the device, four times the rate of the 32-bit multiplication
+#if defined(__HIPCC__)
+#define DR_MAD24(a, b, c) (__umul24((a), (b)) + (c))
+#else
+#define DR_MAD24(a, b, c) ((a) * (b) + (c))
+#endif
 template <int M, bool WITH_ZEROS = false, class F>
 DR_RECODE_FN void for_each_wnaf_multiple_digit(const uint32_t (&k)[9], const WindowTable& wt, F&& f) {
-    static_assert(M >= 1 && M <= WNAF_MAX_MULTIPLES, "multiplier count");
-    constexpr uint32_t MINV[WNAF_MAX_MULTIPLES] = {1u, 0xaaabu, 0xcccdu, 0x6db7u, 0x8e39u, 0x8ba3u, 0x4ec5u, 0xeeefu};   // (2 t + 1)^-1 mod 2^16
+    static_assert(M >= 1 && M <= WNAF_MAX_MULTIPLES && WNAF_MAX_MULTIPLES <= 32, "multiplier count (the selection key has 5 bits for t)");
     const uint32_t w = (uint32_t)wt.cmax, wmask = (1u << w) - 1u, L = (uint32_t)wt.W * w, shift = L - 256u;      // shift < w <= 13
     uint32_t K[10];
     K[0] = k[0] << shift;
@@ -142,19 +166,20 @@ DR_RECODE_FN void for_each_wnaf_multiple_digit(const uint32_t (&k)[9], const Win
                     f(j, j == 0 ? o - shift : o, 0u, d);
                     r = o + a - w;
                 } else {
-                    const int32_t n = (int32_t)(at & wmask) + co;
-                    const uint32_t u = (uint32_t)n & wmask, above = (uint32_t)(chunk >> (o + w));
-                    uint32_t bt = 0, bz = 0;
-                    int32_t bb = 0, bc = 0;
+                    const uint32_t lmask = (1u << (w + WNAF_LOOK)) - 1u, half = 1u << (w - 1), stop = 1u << (w + WNAF_LOOK);
+                    const uint32_t N = ((at & lmask) + (uint32_t)co) & lmask;       // w + WNAF_LOOK <= 21 bits
+                    // key of multiplier t: (w + zeros won) << 5 | 31 - t
+                    uint32_t best = ((uint32_t)__builtin_ctz(((N + half) & ~wmask) | stop) << 5) | 31u;   // m = 1: q = N
 #pragma unroll
-                    for (int t = 0; t < M; t++) {
-                        const uint32_t bu = (u * MINV[t]) & wmask;                   // odd
-                        const int32_t b = bu > (1u << (w - 1)) ? (int32_t)bu - (int32_t)(1u << w) : (int32_t)bu;
-                        const int32_t cm = (n - (2 * t + 1) * b) >> w;
-                        const uint32_t y = (above + (uint32_t)cm) & ((1u << WNAF_LOOK) - 1u);
-                        const uint32_t tz = y ? (uint32_t)__builtin_ctz(y) : WNAF_LOOK;
-                        if (t == 0 || tz > bz) { bt = (uint32_t)t; bz = tz; bb = b; bc = cm; }
+                    for (int t = 1; t < M; t++) {
+                        const uint32_t qh = DR_MAD24(N, wnaf_multiplier_inverse((uint32_t)t) & 0x1fffffu, half);
+                        const uint32_t key = ((uint32_t)__builtin_ctz((qh & ~wmask) | stop) << 5) | (uint32_t)(31 - t);
+                        best = key > best ? key : best;
                     }
+                    const uint32_t bt = 31u - (best & 31u), bq = N * wnaf_multiplier_inverse(bt);
+                    const int32_t n = (int32_t)(at & wmask) + co;
+                    const int32_t bb = (int32_t)(bq << (32u - w)) >> (32u - w);     // odd, |bb| < 2^(w-1)
+                    const int32_t bc = (n - (2 * (int32_t)bt + 1) * bb) >> w;
                     c = bc;
                     f(j, j == 0 ? o - shift : o, bt, bb);
                     r = o;
@@ -169,11 +194,13 @@ DR_RECODE_FN void for_each_wnaf_multiple_digit(const uint32_t (&k)[9], const Win
     }
 }
 
-// run-time multiplier count (2, 4 or 8) -> the instance
+// run-time multiplier count (2, 4, 8, 16 or 32) -> the instance
 template <bool WITH_ZEROS = false, class F>
 DR_RECODE_FN void for_each_wnaf_multiple_digit(uint32_t multiples, const uint32_t (&k)[9], const WindowTable& wt, F&& f) {
     if (multiples == 2) for_each_wnaf_multiple_digit<2, WITH_ZEROS>(k, wt, f);
     else if (multiples == 4) for_each_wnaf_multiple_digit<4, WITH_ZEROS>(k, wt, f);
+    else if (multiples == 16) for_each_wnaf_multiple_digit<16, WITH_ZEROS>(k, wt, f);
+    else if (multiples == 32) for_each_wnaf_multiple_digit<32, WITH_ZEROS>(k, wt, f);
     else for_each_wnaf_multiple_digit<8, WITH_ZEROS>(k, wt, f);
 }
 

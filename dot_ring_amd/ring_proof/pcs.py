@@ -70,13 +70,13 @@ def _candidate_srs_files(min_g1_count: int):
 
 def _precompute_tables(dev) -> None:
     """Fixed-base tables of an SRS in HBM: 12-bit windows feeding the bucket pipeline — for an SRS of up to ~16 k points a row per bit,
-    over which batches of hundreds of MSMs recode their scalars in non-adjacent form (dr_srs_table_info), with the library's default
-    count of odd-multiple row blocks (dr_srs_precompute_multiples; DOTRING_SRS_MULTIPLES, DOTRING_SRS_MULTIPLES_MB).  DOTRING_SRS_WINDOW
-    overrides the width (0 = no table at all)."""
+    over which batches of hundreds of MSMs recode their scalars in non-adjacent form (dr_srs_table_info), with the count of
+    odd-multiple row blocks the library recommends for batched proving (dr_srs_precompute_multiples with -1; DOTRING_SRS_MULTIPLES,
+    DOTRING_SRS_MULTIPLES_MB).  DOTRING_SRS_WINDOW overrides the width (0 = no table at all)."""
     explicit = os.environ.get("DOTRING_SRS_WINDOW")
     bits = int(explicit) if explicit is not None else 12
     if bits:
-        dev.precompute(bits, multiples=0)
+        dev.precompute(bits, multiples=-1)
 
 
 class SRS:

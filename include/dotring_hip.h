@@ -601,13 +601,14 @@ DR_API int dr_srs_precompute(dr_ctx *ctx, dr_srs *srs, int window_bits);
  *   form, info[5] expected non-zero digits per scalar x 1000 */
 DR_API int dr_srs_table_info(const dr_srs *srs, size_t n, size_t batch, int info[6]);
 /* dr_srs_precompute, and where the table gets a row per bit it also gets the rows of the small odd multiples of every base:
- * `multiples` blocks of 256 rows, block t = 2^s * ((2 t + 1) * base[i]) (1, 2, 4 or 8; 0 = the library's default, 8; 1 = exactly
- * dr_srs_precompute's table).  Batches of hundreds of MSMs then write a digit as +-(2 t + 1) * b with b the odd bucket value and pick,
- * per digit, the multiplier that clears the most bits of the scalar: 18.1 / 17.3 / 16.6 bucket additions per (base, scalar) pair at
- * w = 13 with 2 / 4 / 8 multiples where the plain non-adjacent form has 18.8.  The table is `multiples` times as large (1.6 GB for 6145
- * points at 8); a table
- * beyond DOTRING_SRS_MULTIPLES_MB (default 4096) or the device's free memory gets fewer blocks, down to one — never an error.
- * DOTRING_SRS_MULTIPLES (1, 2, 4 or 8) overrides the count asked for.  Results are unchanged. */
+ * `multiples` blocks of 256 rows, block t = 2^s * ((2 t + 1) * base[i]) (1, 2, 4, 8, 16 or 32; 0 = the library's default, 8; -1 = the
+ * count the library recommends for batched proving, 32; 1 = exactly dr_srs_precompute's table).  Batches of hundreds of MSMs then write
+ * a digit as +-(2 t + 1) * b with b the odd bucket value and pick, per digit, the multiplier that clears the most bits of the scalar:
+ * 18.1 / 17.3 / 16.6 / 15.9 / 15.1 bucket additions per (base, scalar) pair at w = 13 with 2 / 4 / 8 / 16 / 32 multiples where the plain
+ * non-adjacent form has 18.8.  The table is `multiples` times as large (1.6 GB for 6145 points at 8, 6.4 GB at 32); a table beyond
+ * DOTRING_SRS_MULTIPLES_MB (default 8192: the 12289 points of a 4096-point domain get 16 blocks, 6.4 GB, where 32 would take 12.9 GB) or
+ * the device's free memory gets half the blocks, and half again down to one — never an error.
+ * DOTRING_SRS_MULTIPLES (1, 2, 4, 8, 16 or 32) overrides the count asked for.  Results are unchanged. */
 DR_API int dr_srs_precompute_multiples(dr_ctx *ctx, dr_srs *srs, int window_bits, int multiples);
 /* dr_srs_table_info's six values, then info[6] = multipliers a digit of this (n, batch) may take (1 = none), info[7] = blocks of rows
  * in the table */

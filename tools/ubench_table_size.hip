@@ -1,6 +1,6 @@
 // Micro-benchmark behind DESIGN "odd-multiple table rows": the inner loop of the bucket walk (g1_walk of kernels_g1.hip.h — a chain of
 // XYZZ mixed additions, one random 128-byte table record gathered per addition) over tables of growing size: the bit-row table of the
-// 6145-point SRS with 1, 2, 4 and 8 blocks of multiples is 201, 402, 804 and 1608 MB, against the 256 MB Infinity Cache.
+// 6145-point SRS with 1, 2, 4, 8, 16 and 32 blocks of multiples is 201, 402, 804, 1608, 3216 and 6432 MB, against the 256 MB Infinity Cache.
 // The records are 135190 distinct points repeated over the table (what is gathered does not matter to the memory system, only where).
 //   build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I dot_ring_amd/csrc tools/ubench_table_size.hip -o tools/ubench_table_size
 //   run:   tools/ubench_table_size [K [lanes]]
@@ -56,8 +56,8 @@ int main(int argc, char** argv) {
     hipLaunchKernelGGL(k_g1_bases_to_mont, dim3(1), dim3(256), 0, 0, d_seed, 1u);
     CK(hipMalloc(&d_small, (size_t)n_small * 96));
     hipLaunchKernelGGL(k_g1_synth_bases, dim3((n_small + 255) / 256), dim3(256), 0, 0, d_small, n_small, 1u, d_seed);
-    const uint32_t blocks[] = {1, 2, 4, 8};
-    const uint32_t max_records = 6145u * 256u * 8u;
+    const uint32_t blocks[] = {1, 2, 4, 8, 16, 32};
+    const uint32_t max_records = 6145u * 256u * 32u;             // 50.3 M records of 128 bytes: 6.4 GB (a record index stays below 2^31)
     const size_t count = (size_t)K * lanes;
     CK(hipMalloc(&d_table, (size_t)max_records * 128));
     CK(hipMalloc(&d_idx, count * 4));
