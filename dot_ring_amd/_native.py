@@ -218,6 +218,13 @@ LAW_SELFTEST_SHAPES = {"ed25519": (9, 4), "bjj": (9, 4), "p256": (9, 3), "secp25
                        "curve448": (16, 3), "p521": (19, 3), "p384": (14, 3)}
 LAW_SELFTEST_SLOTS = 13
 _PROTOTYPES.update({f"dr_{suite}_law_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p]) for suite in LAW_SELFTEST_SHAPES})
+# fr29.hip.h and curve.hip.h's law on raw limb images (kernels_bsn.hip.h: k_fr_raw_selftest, k_te_law_selftest)
+FR_RAW_IN_WORDS, FR_RAW_OUT_WORDS = 4 * 9, 13 * 9 + 4 * 8 + 1
+TE_LAW_REC_WORDS, TE_LAW_SLOTS, TE_LAW_PT_WORDS = 11 * 9, 17, 4 * 9
+_PROTOTYPES.update({
+    "dr_fr_raw_selftest": (c_int, [c_void_p, c_char_p, c_size_t, c_void_p]),
+    "dr_te_law_selftest": (c_int, [c_void_p, c_int, c_char_p, c_char_p, c_size_t, c_void_p]),
+})
 COMM_ID_BYTES = 128
 RINGVRF_AUX_BYTES = 960
 PEDERSEN_AUX_BYTES = 288
@@ -902,6 +909,26 @@ class Context:
     curve448_law_selftest = functools.partialmethod(_law_selftest, "curve448")
     p521_law_selftest = functools.partialmethod(_law_selftest, "p521")
     p384_law_selftest = functools.partialmethod(_law_selftest, "p384")
+
+    def fr_raw_selftest(self, images: bytes) -> bytes:
+        """dr_fr_raw_selftest: n x 150 little-endian words for n records of four raw images of nine int32 limbs (include/dotring_hip.h
+        lists the results)."""
+        n = len(images) // (4 * FR_RAW_IN_WORDS)
+        if len(images) != 4 * FR_RAW_IN_WORDS * n:
+            raise ValueError(f"a record is {4 * FR_RAW_IN_WORDS} bytes of limbs")
+        out = ctypes.create_string_buffer(max(1, n * 4 * FR_RAW_OUT_WORDS))
+        _check(lib().dr_fr_raw_selftest(self.handle, images, n, out))
+        return out.raw[: n * 4 * FR_RAW_OUT_WORDS]
+
+    def te_law_selftest(self, curve: int, records: bytes, controls: bytes) -> bytes:
+        """dr_te_law_selftest: n x 17 points of raw limbs for n records of P, Q and a table row (little-endian int32) and n little-endian
+        control words, on Bandersnatch (0) or JubJub (1) (include/dotring_hip.h lists the slots)."""
+        n = len(controls) // 4
+        if len(controls) != 4 * n or len(records) != 4 * TE_LAW_REC_WORDS * n:
+            raise ValueError(f"a record is {4 * TE_LAW_REC_WORDS} bytes of limbs and one 4-byte control word")
+        out = ctypes.create_string_buffer(max(1, n * TE_LAW_SLOTS * TE_LAW_PT_WORDS * 4))
+        _check(lib().dr_te_law_selftest(self.handle, curve, records, controls, n, out))
+        return out.raw[: n * TE_LAW_SLOTS * TE_LAW_PT_WORDS * 4]
 
     def blsg2_check_points(self, pts_xy: bytes, subgroup: bool = True) -> bytes:
         """dr_blsg2_check_points: one flag byte per 192-byte point: on the curve, and with `subgroup` also r P = O."""

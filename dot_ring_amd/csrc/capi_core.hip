@@ -1199,6 +1199,34 @@ int dr_fr_ops_selftest(dr_ctx* ctx, const uint8_t* a, const uint8_t* b, size_t n
     }, {out, &ctx->io_b, 0, n * 384}, n, is_square);
 }
 
+// fr29.hip.h on raw limb images (kernels_bsn.hip.h: k_fr_raw_selftest; include/dotring_hip.h describes the record); not profiled
+int dr_fr_raw_selftest(dr_ctx* ctx, const int32_t* images, size_t n, uint32_t* out) {
+    TRY(use_ctx(ctx));
+    if (n == 0) return DR_OK;
+    if (!images || !out) return fail(DR_ERR_INVALID, "null buffer");
+    if (n >= MAX_SELFTEST) return fail(DR_ERR_INVALID, "batch too large");
+    constexpr size_t in = 4 * dr::L29 * 4, res = (size_t)dr::FR_RAW_WORDS * 4;
+    return io_round(ctx, {n * in, n * res, 0}, {{&ctx->io_a, 0, images, n * in}}, nullptr, [&] {
+        hipLaunchKernelGGL(dr::k_fr_raw_selftest, dim3(div_up(n, 64)), dim3(64), 0, ctx->stream, ctx->io_a.as<int32_t>(), (uint32_t)n,
+                           ctx->io_b.as<uint32_t>());
+    }, {{out, &ctx->io_b, 0, n * res}});
+}
+
+// the law of curve.hip.h and te_madd on raw limb images (kernels_te.hip.h: te_law_selftest), Bandersnatch and JubJub; not profiled
+int dr_te_law_selftest(dr_ctx* ctx, int curve, const int32_t* records, const uint32_t* controls, size_t n, int32_t* out) {
+    TRY(use_ctx(ctx));
+    if (curve != DR_CURVE_BANDERSNATCH && curve != DR_CURVE_JUBJUB) return fail(DR_ERR_INVALID, "unknown curve id");
+    if (n == 0) return DR_OK;
+    if (!records || !controls || !out) return fail(DR_ERR_INVALID, "null buffer");
+    if (n >= MAX_SELFTEST) return fail(DR_ERR_INVALID, "batch too large");
+    constexpr size_t in = (size_t)dr::TE_LAW_REC * 4, res = (size_t)dr::TE_LAW_SLOTS * dr::TE_LAW_PT * 4;
+    return io_round(ctx, {n * (in + 4), n * res, 0}, {{&ctx->io_a, 0, records, n * in}, {&ctx->io_a, n * in, controls, n * 4}}, nullptr, [&] {
+        const auto k = curve == DR_CURVE_JUBJUB ? dr::k_te_law_selftest<dr::CV_JUBJUB> : dr::k_te_law_selftest<dr::CV_BANDERSNATCH>;
+        hipLaunchKernelGGL(k, dim3(div_up(n, dr::BSN_BLOCK)), dim3(dr::BSN_BLOCK), 0, ctx->stream, ctx->io_a.as<int32_t>(),
+                           (const uint32_t*)(ctx->io_a.as<uint8_t>() + n * in), (uint32_t)n, ctx->io_b.as<int32_t>());
+    }, {{out, &ctx->io_b, 0, n * res}});
+}
+
 int dr_fr_sqrt(const uint8_t in[32], uint8_t out[32]) {
     if (!in || !out) return fail(DR_ERR_INVALID, "null buffer");
     drh::Fr x, r;

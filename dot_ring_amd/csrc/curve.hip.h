@@ -48,7 +48,8 @@ DR_DEV Fs te_d_mont() {
     return CV == CV_BANDERSNATCH ? Fs::constant<TeCurveConsts::D_BANDERSNATCH>() : Fs::constant<TeCurveConsts::D_JUBJUB>();
 }
 
-// carry for a sum of NON-NEGATIVE low limbs (normal values added up to 7 times: below 2^32 as unsigned); top limb signed
+// carry for a sum of NON-NEGATIVE low limbs (normal values added up to 7 times: at most 7 (2^29 - 1); anything below 2^32 - 7 as
+// unsigned, since t = l[i] + c with c <= 7 must fit 32 bits); top limb signed
 DR_DEV Fs carry_u(const Fs& a) {
     Fs r;
     uint32_t c = 0;
@@ -84,6 +85,10 @@ template <int CV = CV_BANDERSNATCH>
 DR_DEV Fs te_mul_a(const Fs& v) { return te_aA<CV>(carry(v)); }
 
 // dbl-2008-hwcd.  WITH_T=false skips T3 (valid when the result is only doubled again).
+// Coordinates n (normal, fr29.hip.h; x and t possibly negated by te_cneg) in, n out; t the zero image without WITH_T.  The line bounds
+// are for operands in (-0.04 p, 1.04 p).  For ANY normal operand (|value| <= 1.5 p, what a law output fed back in may be): A, B < 1.04 p,
+// C < 2.07 p, |E| < 2.07 p, D in (-2.2 p, 3 p], |G| < 4.04 p, |F| < 4.23 p, |H| < 3.2 p, the products at most 17.1 p^2: every
+// coordinate out lies in (-0.25 p, 1.25 p), limbs 0..7 in [0, 2^29).
 template <bool WITH_T, int CV = CV_BANDERSNATCH>
 DR_DEV TePoint te_dbl(const TePoint& p) {
     const Fs A = sqr(p.x), B = sqr(p.y);             // (2^29, 1.04)
@@ -103,6 +108,9 @@ DR_DEV TePoint te_dbl(const TePoint& p) {
 }
 
 // add-2008-hwcd, unified (also correct for doubling and for the identity).  E = X1 Y2 + Y1 X2 as ONE fused product.
+// Coordinates n (x and t of either point possibly negated by te_cneg) in, n out.  For ANY normal operands (|value| <= 1.5 p): A, B, D
+// in (-0.04 p, 1.04 p), C in (-0.03 p, 1.03 p), |x1 y2 + y1 x2| <= 4.5 p^2 so E in (-0.07 p, 1.07 p), |F| < 1.06 p, G in (-0.06 p, 2.06 p),
+// |H| < 3.2 p, the products at most 6.6 p^2: every coordinate out lies in (-0.1 p, 1.1 p), limbs 0..7 in [0, 2^29).
 template <int CV = CV_BANDERSNATCH>
 DR_DEV TePoint te_add(const TePoint& p, const TePoint& q) {
     const Fs A = mul(p.x, q.x), B = mul(p.y, q.y);
@@ -119,6 +127,8 @@ DR_DEV TePoint te_add(const TePoint& p, const TePoint& q) {
     return r;
 }
 
+// Coordinates n in; out the very limbs, x and t negated limb-wise when asked: a negated normal (limbs within (-2^29, 2^29),
+// |value| <= 1.5 p), which te_add, te_dbl and te_madd take
 DR_DEV TePoint te_cneg(const TePoint& p, bool negate) {
     TePoint r = p;
     r.x = cneg(p.x, negate);

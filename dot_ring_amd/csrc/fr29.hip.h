@@ -11,8 +11,10 @@
 // room than Fq has (2^11), so the rules are tighter than fq28's:
 //   "normal" : limbs 0..7 in [0, 2^29), limb 8 small and signed — what mul() / sqr() / mul2() return; value in (-p/2, 1.5 p)
 //              (in (-0.04 p, 1.04 p) when the operands were normal)
-//   mul(a, b): 9 max|a_i| max|b_j| + 9 * 2^58 < 2^63, i.e. max|a_i| max|b_j| <= 2^59.3 (2^30 x 2^29, or 1.6 * 2^29 twice), and
-//              |a| |b| <= 35 p^2 for a normal result (beyond that the result is still correct, just wider by |a b| / (70.7 p))
+//   mul(a, b): 9 max|a_i| max|b_j| + 5.2 * 2^58 < 2^63 (a column holds nine products and the m_i p_j beside them: the limbs of p add
+//              up to 5.14 * 2^29), i.e. max|a_i| max|b_j| <= 2^59.5 (2^30 x 2^29, or 1.6 * 2^29 twice = 2^59.36), and
+//              |a| |b| <= 35 p^2 for a normal result (beyond that the result is still correct, just wider: limbs 0..7 in [0, 2^29)
+//              and value in (-|a b| / R, p + |a b| / R), R / p = 70.66)
 //   sqr(a)   : max|a_i| <= 1.6 * 2^29;   mul2(a, b, c, d): all limbs below 2^29 in magnitude, |a b + c d| <= 35 p^2
 //   carry()  : limbs back into [0, 2^29) (value unchanged) — needed after ~3 additions of normal values or before a product of
 //              two sums
@@ -89,7 +91,8 @@ DR_DEV Fs cneg(const Fs& a, bool negate) {
     for (int i = 0; i < L29; i++) r.l[i] = (a.l[i] ^ s) - s;
     return r;
 }
-// limbs 0..7 into [0, 2^29), the rest into the signed top limb.  Value unchanged.
+// limbs 0..7 into [0, 2^29), the rest into the signed top limb.  Value unchanged.  In: |limb| < 2^31 - 4 (t = l[i] + c with c in
+// [-4, 3] must fit 32 bits; every caller hands over sums and differences of a few normal or carried values, limbs below 2^31).
 DR_DEV Fs carry(const Fs& a) {
     Fs r;
     int32_t c = 0;
@@ -196,7 +199,7 @@ DR_DEV Fs from_arg(const FsArg& a) {
     for (int i = 0; i < L29; i++) r.l[i] = a.l[i];
     return r;
 }
-// Any lazy value with |value| < 30 p and limbs within int32 -> carried limbs (0..7 in [0, 2^29), signed top limb) and
+// Any lazy value with |value| < 30 p and |limb| < 2^31 - 4 (what carry() takes) -> carried limbs (0..7 in [0, 2^29), signed top limb) and
 // |value| < 0.51 p: q = round(value / p) from the top limb (p / 2^232 = 7597479.33; the low limbs add less than one unit of it),
 // then value - q p with 64-bit limb arithmetic (|q| P[i] does not fit 32 bits).  ~75 instructions: where a growing sum leaves a
 // kernel without passing through a product (the forward NTT's last stage).

@@ -516,4 +516,65 @@ __global__ __launch_bounds__(BSN_BLOCK) void k_te_decode_points(const uint32_t* 
     }
 }
 
+// Diagnostic (dr_fr_raw_selftest): fr29.hip.h and the addition chains of curve.hip.h on RAW limb images, one lane per record of four
+// images a, b, c, d (nine int32 limbs each, taken as they are: no packing and no conversion on the way in), so that a test can put every
+// operand at the bound its header documents and read the limbs of what comes back.  Every operation runs on every record; which results
+// a record's images are in contract for is the caller's knowledge.  out[i] = FR_RAW_WORDS words:
+//   thirteen raw 9-limb results   0 mul(a, b)   1 sqr(a)   2 mul2(a, b, c, d)   3 carry(a)   4 carry_u(a)   5 sub_3p(carry_u(a))
+//                                 6 reduce_small(a)   7 unpack(pack(a))   8 inv(a)   9 te_aA<Bandersnatch>(a)
+//                                 10 te_b_minus_aA<Bandersnatch>(a, b)   11 te_aA<JubJub>(a)   12 te_b_minus_aA<JubJub>(a, b)
+//   four 8-word results           canon29(a), canon29_small(a), fs_to_std(a), to_mont256(a)
+//   one flag word                 bit 0 is_zero(a), bit 1 equal(a, b)
+// Each result is stored as it is made.
+constexpr int FR_RAW_LIMB_SLOTS = 13, FR_RAW_WORD_SLOTS = 4, FR_RAW_WORDS = FR_RAW_LIMB_SLOTS * L29 + FR_RAW_WORD_SLOTS * 8 + 1;
+__global__ __launch_bounds__(64) void k_fr_raw_selftest(const int32_t* __restrict__ rec, uint32_t n, uint32_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t* r = rec + (size_t)i * (4 * L29);
+    const Fs a = te_law_load(r), b = te_law_load(r + L29), c = te_law_load(r + 2 * L29), d = te_law_load(r + 3 * L29);
+    uint32_t* o = out + (size_t)i * FR_RAW_WORDS;
+    fs_store9(o, mul(a, b));
+    fs_store9(o + 9, sqr(a));
+    fs_store9(o + 18, mul2(a, b, c, d));
+    fs_store9(o + 27, carry(a));
+    fs_store9(o + 36, carry_u(a));
+    fs_store9(o + 45, sub_3p(carry_u(a)));
+    fs_store9(o + 54, reduce_small(a));
+    fs_store9(o + 63, unpack(pack(a)));
+    fs_store9(o + 72, inv(a));
+    fs_store9(o + 81, te_aA<CV_BANDERSNATCH>(a));
+    fs_store9(o + 90, te_b_minus_aA<CV_BANDERSNATCH>(a, b));
+    fs_store9(o + 99, te_aA<CV_JUBJUB>(a));
+    fs_store9(o + 108, te_b_minus_aA<CV_JUBJUB>(a, b));
+    uint32_t* w = o + FR_RAW_LIMB_SLOTS * L29;
+    Fr v;
+    canon29(a, v.l);
+#pragma unroll
+    for (int j = 0; j < 8; j++) w[j] = v.l[j];
+    canon29_small(a, v.l);
+#pragma unroll
+    for (int j = 0; j < 8; j++) w[8 + j] = v.l[j];
+    v = fs_to_std(a);
+#pragma unroll
+    for (int j = 0; j < 8; j++) w[16 + j] = v.l[j];
+    v = to_mont256(a);
+#pragma unroll
+    for (int j = 0; j < 8; j++) w[24 + j] = v.l[j];
+    w[32] = (is_zero(a) ? 1u : 0u) | (equal(a, b) ? 2u : 0u);
+}
+
+// Diagnostic (dr_te_law_selftest): kernels_te.hip.h's te_law_selftest over the curve, and the endomorphism of the row's affine point
+template <int CV>
+__global__ __launch_bounds__(BSN_BLOCK) void k_te_law_selftest(const int32_t* __restrict__ recs, const uint32_t* __restrict__ ctl, uint32_t n,
+                                                               int32_t* __restrict__ out) {
+    __shared__ uint32_t tab[BSN_TABLE * BSN_PT_WORDS * BSN_BLOCK];
+    uint32_t i = blockIdx.x * BSN_BLOCK + threadIdx.x;
+    const bool live = i < n;
+    if (!live) i = n - 1;            // keep the wave converged; the duplicate results are not stored
+    const int32_t* rec = recs + (size_t)i * TE_LAW_REC;
+    int32_t* const o = out + (size_t)i * (TE_LAW_SLOTS * TE_LAW_PT);
+    te_law_selftest<CV>(tab, rec, ctl[i], live, o);
+    if constexpr (CV == CV_BANDERSNATCH) te_law_put(o, live, 16, bsn_endomorphism(te_law_load(rec + 8 * L29), te_law_load(rec + 9 * L29)));
+}
+
 }  // namespace dr

@@ -299,6 +299,9 @@ DR_DEV Fs fr_pow_limbs(const Fs& a, const uint32_t (&e)[8]) {
 
 
 // acc + (x2, y2, d*t2) with Z2 = 1  (add-2008-hwcd: D = Z1, C = T1 * d t2)
+// p: coordinates n (normal, fr29.hip.h); the row: unpack of canonical words, x2 and dt2 possibly negated limb-wise (te_msm_walk); n out.
+// For ANY normal p (|value| <= 1.5 p): A, B, C in (-0.03 p, 1.03 p), E in (-0.05 p, 1.05 p), D = Z1 itself, so |F| < 1.53 p and
+// G in (-0.53 p, 2.53 p), |H| < 3.2 p, the products at most 8.1 p^2: every coordinate out lies in (-0.12 p, 1.12 p).
 template <int CV>
 DR_DEV TePoint te_madd(const TePoint& p, const Fs& x2, const Fs& y2, const Fs& dt2) {
     const Fs A = mul(p.x, x2), B = mul(p.y, y2), C = mul(p.t, dt2);
@@ -310,6 +313,77 @@ DR_DEV TePoint te_madd(const TePoint& p, const Fs& x2, const Fs& y2, const Fs& d
     r.t = mul(E, H);
     r.z = mul(F, G);
     return r;
+}
+
+// ---------------------------------------------------------------- diagnostic of the law (dr_te_law_selftest)
+// curve.hip.h's law and te_madd on RAW limb images, one lane per record, as wave_curve.hip.h's wave_law_selftest does it for the wave
+// curves: no packing, no inversion and no conversion on either side.  rec: P then Q (x, y, z, t of nine int32 limbs each), then one table
+// row (x2, y2, d x2 y2) as te_msm_walk hands it to te_madd; ctl: n control words; out: n x TE_LAW_SLOTS points (x, y, z, t).  The slots:
+//   0  te_add(P, Q)             1  te_add(P, te_cneg(Q, true))    2  te_dbl<true>(P)      3  te_dbl<false>(P)
+//   4  te_cneg(P, true)         5  slot 0 after lds_store_point to entry TE_LAW_ENTRY and lds_load_point back      6  te_cneg(P, false)
+//   7 + w, w = 0..5             acc after window w of a chain run exactly as bsn_scalar_mul_core runs one: three te_dbl<false>, one
+//                               te_dbl<true>, then te_add of the table term loaded from LDS entry TE_LAW_ENTRY (slot 0's point, stored
+//                               once), negated when bit w of the control word is set and replaced by te_identity() when bit 8 + w is;
+//                               the chain starts at acc = P
+//   13 te_madd(P, row)          14 te_madd chained four times from te_identity() with the same row (the walk's own start)
+//                               bit 16 of the control word negates the row's x and dt limb-wise first, as te_msm_walk does
+//   15 te_add(slot 0, slot 2)   a law output on both sides, as k_te_msm_reduce and the shuffle sums have it
+//   16 (written by the kernel, kernels_bsn.hip.h; Bandersnatch only) bsn_endomorphism(x2, y2) of the row as loaded
+// The table is the scalar multiplication's own (BSN_TABLE entries).  A lane past n recomputes record n - 1 and stores nothing.
+constexpr int TE_LAW_SLOTS = 17, TE_LAW_WINDOWS = 6, TE_LAW_ENTRY = 3, TE_LAW_REC = 11 * L29, TE_LAW_PT = 4 * L29;
+DR_DEV Fs te_law_load(const int32_t* p) {
+    Fs r;
+#pragma unroll
+    for (int t = 0; t < L29; t++) r.l[t] = p[t];
+    return r;
+}
+DR_DEV void te_law_put(int32_t* o, bool live, int slot, const TePoint& r) {
+    if (!live) return;
+    int32_t* q = o + slot * TE_LAW_PT;
+#pragma unroll
+    for (int t = 0; t < L29; t++) {
+        q[t] = r.x.l[t]; q[L29 + t] = r.y.l[t]; q[2 * L29 + t] = r.z.l[t]; q[3 * L29 + t] = r.t.l[t];
+    }
+}
+template <int CV>
+DR_DEV void te_law_selftest(uint32_t* tab, const int32_t* __restrict__ rec, uint32_t cw, bool live, int32_t* __restrict__ o) {
+    const int lane = threadIdx.x;
+    TePoint P, Q;
+    P.x = te_law_load(rec); P.y = te_law_load(rec + L29); P.z = te_law_load(rec + 2 * L29); P.t = te_law_load(rec + 3 * L29);
+    Q.x = te_law_load(rec + 4 * L29); Q.y = te_law_load(rec + 5 * L29); Q.z = te_law_load(rec + 6 * L29); Q.t = te_law_load(rec + 7 * L29);
+    TePoint sum = te_identity();
+#pragma unroll 1
+    for (int s = 0; s < 2; s++) {
+        const TePoint R = te_add<CV>(P, te_cneg(Q, s != 0));
+        te_law_put(o, live, s, R);
+        if (s == 0) { lds_store_point(tab, TE_LAW_ENTRY, lane, R); sum = R; }
+    }
+    const TePoint twice = te_dbl<true, CV>(P);
+    te_law_put(o, live, 2, twice);
+    te_law_put(o, live, 3, te_dbl<false, CV>(P));
+    te_law_put(o, live, 15, te_add<CV>(sum, twice));
+#pragma unroll 1
+    for (int s = 0; s < 2; s++) te_law_put(o, live, s == 0 ? 4 : 6, te_cneg(P, s == 0));
+    te_law_put(o, live, 5, lds_load_point(tab, TE_LAW_ENTRY, lane));
+    TePoint acc = P;
+#pragma unroll 1
+    for (int w = 0; w < TE_LAW_WINDOWS; w++) {
+#pragma unroll 1
+        for (int j = 0; j < 3; j++) acc = te_dbl<false, CV>(acc);
+        acc = te_dbl<true, CV>(acc);
+        TePoint T = lds_load_point(tab, TE_LAW_ENTRY, lane);
+        T = te_cneg(T, ((cw >> w) & 1u) != 0);
+        if (((cw >> (8 + w)) & 1u) != 0) T = te_identity();
+        acc = te_add<CV>(acc, T);
+        te_law_put(o, live, 7 + w, acc);
+    }
+    const bool minus = ((cw >> 16) & 1u) != 0;
+    const Fs x2 = cneg(te_law_load(rec + 8 * L29), minus), y2 = te_law_load(rec + 9 * L29), dt2 = cneg(te_law_load(rec + 10 * L29), minus);
+    te_law_put(o, live, 13, te_madd<CV>(P, x2, y2, dt2));
+    acc = te_identity();
+#pragma unroll 1
+    for (int j = 0; j < 4; j++) acc = te_madd<CV>(acc, x2, y2, dt2);
+    te_law_put(o, live, 14, acc);
 }
 
 

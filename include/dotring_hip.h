@@ -206,6 +206,30 @@ DR_API int dr_te_fixed_base_msm_groups(dr_ctx *ctx, int curve, const uint8_t *ba
 DR_API int dr_fr_ops_selftest(dr_ctx *ctx, const uint8_t *a /* n*32 */, const uint8_t *b /* n*32 */, size_t n, uint8_t *out /* n*384 */,
                               uint8_t *is_square /* n */);
 
+/* Diagnostic: csrc/fr29.hip.h and the addition chains of csrc/curve.hip.h on RAW limb images: no packing and no conversion on the way
+ * in, so a test can put every operand at the bound its header documents and read the limbs of what comes back.  images[i] = four
+ * images a, b, c, d of nine signed 32-bit limbs each; every operation runs on every record.  out[i] = 150 words:
+ *   13 x 9 limbs   mul(a, b), sqr(a), mul2(a, b, c, d), carry(a), carry_u(a), sub_3p(carry_u(a)), reduce_small(a), unpack(pack(a)),
+ *                  inv(a), te_aA(a) and te_b_minus_aA(a, b) for Bandersnatch, the same two for JubJub
+ *   4 x 8 words    canon29(a), canon29_small(a), fs_to_std(a), to_mont256(a)
+ *   1 word         bit 0 is_zero(a), bit 1 equal(a, b)
+ * n = 0 returns at once; a null buffer and n >= 2^24 are refused.  The call launches under no profiled name. */
+DR_API int dr_fr_raw_selftest(dr_ctx *ctx, const int32_t *images /* n*4*9 */, size_t n, uint32_t *out /* n*150 */);
+
+/* Diagnostic: the twisted Edwards law of csrc/curve.hip.h (te_add, te_dbl, te_cneg) and te_madd on RAW limb images, for
+ * DR_CURVE_BANDERSNATCH and DR_CURVE_JUBJUB (any other id is refused), in the manner of the dr_*_law_selftest calls below.
+ * records[i] = P then Q (x, y, z, t of nine signed 32-bit limbs each), then one table row (x2, y2, d x2 y2) as the bucket walk hands it
+ * to te_madd: 11 x 9 limbs; controls[i] = one word; out[i] = 17 points (x, y, z, t):
+ *   0 te_add(P, Q)   1 te_add(P, -Q)   2 te_dbl<true>(P)   3 te_dbl<false>(P) (T = 0)   4 te_cneg(P, true)   6 te_cneg(P, false)
+ *   5 slot 0 through the LDS table of the scalar multiplication (lds_store_point, lds_load_point) and back
+ *   7 + w, w < 6: the accumulator after window w of the fixed schedule started at P: three te_dbl<false>, one te_dbl<true>, then the
+ *   table term (slot 0's point, from LDS) added, negated if bit w of the control word is set, the identity if bit 8 + w is
+ *   13 te_madd(P, row)   14 te_madd four times from the identity with the same row; bit 16 of the control word negates the row's x and
+ *   d x2 y2 limb-wise first   15 te_add(slot 0, slot 2)   16 the GLV endomorphism of (x2, y2) as given (Bandersnatch; not written otherwise)
+ * n = 0 returns at once; a null buffer and n >= 2^24 are refused.  The call launches under no profiled name. */
+DR_API int dr_te_law_selftest(dr_ctx *ctx, int curve, const int32_t *records /* n*11*9 */, const uint32_t *controls /* n */, size_t n,
+                              int32_t *out /* n*17*4*9 */);
+
 /* Ed25519 point decoding with the prime-order check (check = 1: as dr_te_decode_points for DR_CURVE_ED25519) or the codec alone
  * (check = 0: y < p and a root; (0, 1) and (0, p - 1) decode whatever the sign bit, as the reference's constructor takes them).
  * ok[i] = 1 when accepted; out_xy[i] is then x || y, otherwise 64 zero bytes. */

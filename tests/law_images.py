@@ -1,6 +1,9 @@
 """Lanes and a checker for the group laws of the nine wave curves on RAW limb images (csrc/wave_curve.hip.h, wave_law_selftest), shared
 by tests/test_gpu_wave_laws.py (the device), tests/test_law_images_cpu.py (the builder and the checker themselves) and the host builds
-of the laws under -fsanitize=undefined (tests/native/*_host_check.cpp, the `lane` line).
+of the laws under -fsanitize=undefined (tests/native/*_host_check.cpp, the `lane` line); for the law of Bandersnatch and JubJub over the
+9 x 29-bit Fr (csrc/curve.hip.h and te_madd, dr_te_law_selftest: the same thirteen slots and four more, tests/test_gpu_te_law.py); and,
+in the second half of the file, records and a checker for csrc/fr29.hip.h itself on raw limb images (dr_fr_raw_selftest,
+tests/test_gpu_fr_raw.py, proven by tests/test_fr_images_cpu.py).
 
 A lane is two real points P and Q of the curve, each coordinate a limb image at an edge of a class the law documents for it, and a
 control word.  The classes are TRANSCRIBED from the headers (the citation stands beside each); nothing here is a measured number.  The
@@ -28,6 +31,9 @@ import p521_ref as p521  # noqa: E402
 import secp256k1_ref as k1  # noqa: E402
 
 SLOTS = 13
+TE_SLOTS = 17                # dr_te_law_selftest: the thirteen, then te_madd, te_madd four times, add of two law outputs, the endomorphism
+SLOT_MADD, SLOT_MADD4, SLOT_ADD_OUT, SLOT_ENDO = 13, 14, 15, 16
+ROW_NEGATED = 1 << 16        # the control bit that negates the row's x and dt limb-wise, as te_msm_walk does
 SLOT_ADD, SLOT_SUB, SLOT_DBL, SLOT_DBL_NO_T, SLOT_NEG, SLOT_LDS, SLOT_KEEP, SLOT_CHAIN = 0, 1, 2, 3, 4, 5, 6, 7
 WINDOWS = 6
 CORNERS = ("hi", "lo", "alt0", "alt1")
@@ -113,10 +119,17 @@ class Curve:
       p_neg, q_neg     whether P / Q may be handed over once negated
       cls_out          {coordinate: class} of what add, dbl and dbl_no_t return
       cls_lds          None where the table keeps limb images (from_lds gives back the very image), otherwise the class from_lds documents
-      cneg_carries     cneg returns a carried coordinate (in cls_p's first class) instead of the limb-wise negation"""
+      cneg_carries     cneg returns a carried coordinate (in cls_p's first class) instead of the limb-wise negation
+      slots            how many slots a record returns; te_id: the curve id of dr_te_law_selftest, whose records carry a table row
+                       (x2, y2, d x2 y2) in cls_lds' class and return slots 13 .. 16; endo: the scalar the endomorphism of slot 16
+                       multiplies by (None: the slot is not written)
+      lds_canonical    the LDS table keeps the canonical representative: slot 5 is slot 0's very value mod p, digit by digit
+      no_t_zero        dbl_no_t returns the zero image as T"""
 
     def __init__(self, name, suite, limbs, bits, R, p, ref, kind, order, cls_p, cls_q, cls_out, one_image, specials, extended=False,
-                 p_neg=True, q_neg=True, to_ref=None, from_ref=None, cneg_carries=False, cls_lds=None):
+                 p_neg=True, q_neg=True, to_ref=None, from_ref=None, cneg_carries=False, cls_lds=None, slots=SLOTS, te_id=None, endo=None,
+                 lds_canonical=False, no_t_zero=False, d=None):
+        self.slots, self.te_id, self.endo, self.lds_canonical, self.no_t_zero, self.d = slots, te_id, endo, lds_canonical, no_t_zero, d
         self.name, self.suite, self.limbs, self.bits, self.R, self.p, self.ref = name, suite, limbs, bits, R % p, p, ref
         self.kind, self.order, self.extended = kind, order, extended
         self.cls_p, self.cls_q, self.cls_out, self.cls_lds = cls_p, cls_q, cls_out, cls_lds
@@ -312,9 +325,127 @@ def _bjj():
                  digits((1 << 261) % p, 9, 29), _torsion(bjj), extended=True, cls_lds={c: words for c in "xyzt"})
 
 
-_BUILDERS = {"ed25519": _ed25519, "bjj": _bjj, "p256": _p256, "secp256k1": _secp256k1, "blsg1": _blsg1, "ed448": _ed448,
+# ---- Bandersnatch and JubJub (fr29.hip.h, curve.hip.h, kernels_te.hip.h): extended coordinates over the 9 x 29-bit Fr
+class TeRef:
+    """oracle/pyref/bandersnatch.py in the add / neg / mul(k, pt) / G shape of the tests/*_ref.py modules, under using(suite).  mul is
+    plain double-and-add on the affine law and does not reduce k, so N R is a torsion point and not the identity by decree; a sum at
+    infinity (Bandersnatch: a = -5 is no square, two points of order 2 are not affine) raises ZeroDivisionError"""
+
+    def __init__(self, suite):
+        from oracle.pyref import bandersnatch as bsn
+
+        self.bsn, self.suite, self.P = bsn, suite, bsn.P
+        with bsn.using(suite):
+            self.G, self.N, self.A, self.D, self.COFACTOR = bsn.G, bsn.N, bsn.A, bsn.D, bsn.COFACTOR
+
+    def add(self, a, b):
+        with self.bsn.using(self.suite):
+            try:
+                return self.bsn.add(a, b)
+            except ValueError as exc:                            # pow(0, -1, p): a denominator of the affine law is zero
+                raise ZeroDivisionError(str(exc)) from exc
+
+    def neg(self, a):
+        return self.bsn.neg(a)
+
+    def mul(self, k, pt):
+        acc = (0, 1)
+        while k > 0:
+            if k & 1:
+                acc = self.add(acc, pt)
+            pt = self.add(pt, pt)
+            k >>= 1
+        return acc
+
+    def on_curve(self, pt):
+        with self.bsn.using(self.suite):
+            return self.bsn.on_curve(pt)
+
+    def sqrt(self, v):
+        return self.bsn.sqrt(v)
+
+
+def te_small_points(ref):
+    """(torsion, outside): the affine points of small order other than the identity, as multiples of N R for curve points R found on
+    the CPU by their x, and points outside the prime-order subgroup (one per kind: N R a torsion point; N R at infinity)"""
+    p, torsion, outside, at_infinity = ref.P, [], [], []
+    x = 1
+    while x < 60:
+        x += 1
+        y = ref.sqrt((1 - ref.A * x * x) * pow(1 - ref.D * x * x, -1, p) % p)
+        if y is None:
+            continue
+        R_ = (x, y)
+        assert ref.on_curve(R_)
+        try:
+            T = ref.mul(ref.N, R_)
+        except ZeroDivisionError:
+            if not at_infinity:
+                at_infinity.append(R_)
+            continue
+        if T == (0, 1):
+            continue
+        if not outside or (ref.mul(ref.COFACTOR // 2, T) != (0, 1) and ref.mul(ref.COFACTOR // 2, ref.mul(ref.N, outside[0])) == (0, 1)):
+            outside[:1] = [R_]                                   # prefer one whose torsion part has the full order
+        S = T
+        while S != (0, 1):                                       # every multiple of the torsion point
+            if S not in torsion:
+                torsion.append(S)
+            S = ref.add(S, T)
+    return sorted(torsion), outside + at_infinity
+
+
+def glv_lambda(order):
+    """the scalar the endomorphism multiplies by, from the lattice basis glv_decompose of csrc/hostproto.hpp uses: k = k1 + k2 lambda with
+    (a1, b1) and (a2, -a1) in the lattice x + y lambda = 0 mod n"""
+    import re
+
+    text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "dot_ring_amd", "csrc", "hostproto.hpp")).read()
+    text = text[text.index("inline bool glv_decompose"):]
+
+    def two(name):
+        m = re.search(r"static const uint64_t %s\[2\] = \{(0x[0-9a-fA-F]+)ULL, (0x[0-9a-fA-F]+)ULL\}" % name, text)
+        return int(m.group(1), 16) | int(m.group(2), 16) << 64
+
+    a1, b1, a2 = two("A1"), two("B1"), two("A2")
+    lam = -a1 * pow(b1, -1, order) % order
+    assert (a2 - a1 * lam) % order == 0
+    return lam
+
+
+def _te(name, suite_name, te_id, with_endo):
+    from oracle.pyref import bandersnatch as bsn
+
+    ref = TeRef(getattr(bsn, suite_name))
+    p, top = ref.P, 29 * 8
+    # fr29.hip.h:12 "normal": limbs 0..7 in [0, 2^29), limb 8 small and signed, value in (-p/2, 1.5 p); the top limb is what the value
+    # leaves it.  curve.hip.h:6-7: "coordinates come in normal (or negated normal: limbs within (-2^29, 2^29), |value| <= 1.5 p) and go
+    # out normal"; te_cneg negates x and t, so those two are the ones handed over negated
+    vlo, vhi = -(p // 2) - 1, 3 * p // 2 + 1
+    n = LimbClass("n", [0] * 8 + [(vlo >> top) - 1], [(1 << 29) - 1] * 8 + [vhi >> top], vlo=vlo, vhi=vhi)
+    # kernels_te.hip.h:20 "the table keeps canonical 8-word coordinates", fr29.hip.h:128 "canonical words (< p, < 2^255) reinterpreted in
+    # radix 2^29": lds_load_point and a table row (te_msm_walk: unpack(load_fr_std(...))) are unpack of canonical words
+    canon = LimbClass("canonical", [0] * 9, [(1 << 29) - 1] * 8 + [p >> top], vlo=-1, vhi=p)
+    torsion, outside = te_small_points(ref)
+    cv = Curve(name, "te", 9, 29, 1 << 261, p, ref, "ed", ref.N, _all(n, "xyzt"), _all(n, "xyzt"), {c: n for c in "xyzt"},
+               digits((1 << 261) % p, 9, 29), torsion + outside, extended=True, cls_lds={c: canon for c in "xyzt"}, slots=TE_SLOTS,
+               te_id=te_id, endo=glv_lambda(ref.N) if with_endo else None, lds_canonical=True, no_t_zero=True, d=ref.D)
+    cv.torsion, cv.outside = torsion, outside
+    return cv
+
+
+def _bandersnatch():
+    return _te("Bandersnatch", "SHA512", 0, True)
+
+
+def _jubjub():
+    return _te("JubJub", "JUBJUB", 1, False)
+
+
+CURVES = ("ed25519", "bjj", "p256", "secp256k1", "blsg1", "ed448", "curve448", "p521", "p384")       # the nine wave curves
+TE_CURVES = ("bandersnatch", "jubjub")                                                              # curve.hip.h over fr29
+_BUILDERS = {"bandersnatch": _bandersnatch, "jubjub": _jubjub, "ed25519": _ed25519, "bjj": _bjj, "p256": _p256, "secp256k1": _secp256k1, "blsg1": _blsg1, "ed448": _ed448,
              "curve448": _curve448, "p521": _p521, "p384": _p384}
-CURVES = tuple(_BUILDERS)
 _CACHE = {}
 
 
@@ -334,6 +465,7 @@ class Lane:
     def __init__(self, what, P, Q, images, control):
         self.what, self.P, self.Q, self.images, self.control = what, P, Q, images, control      # images: {"P": {c: image}, "Q": {...}}
         self._want = None
+        self.row = None          # dr_te_law_selftest: the affine point of the table row; its images are images["R"]: x, y, dt
 
 
 class Builder:
@@ -442,7 +574,33 @@ class Builder:
         while len(self.lanes) < 70:
             P, Q = rp(rng), rp(rng)
             self.lane(f"mixed {len(self.lanes)}", P, Q, self.point_images("P", P), self.point_images("Q", Q, negate=cv.q_neg and rng.random() < 0.3))
+        if cv.te_id is not None:
+            self.rows()
         return self
+
+    def rows(self):
+        """dr_te_law_selftest: a table row (x2, y2, d x2 y2) per lane, in the form te_msm_walk hands to te_madd: unpack of the canonical
+        words k_te_msm_prepare packed (one image per residue), negated limb-wise on the device where the control word says.  Rows are
+        prime-order points (what the endomorphism of slot 16 is defined on) or the identity; on a curve without the endomorphism also
+        the small-order points.  Some rows are the lane's own P or -P, so that te_madd doubles and cancels."""
+        cv, rng = self.cv, self.rng
+        for i, lane in enumerate(self.lanes):
+            what = lane.what.split()
+            if what[0] == "mixed" and int(what[1]) % 4 == 0:
+                row = lane.P
+            elif what[0] == "mixed" and int(what[1]) % 4 == 1:
+                row = cv.neg(lane.P)
+            elif what[0] == "corner" and what[2] == "kmin" and what[1] == "lo":
+                row = cv.identity()
+            elif cv.endo is None and lane.what.startswith("P special"):
+                row = lane.P
+            else:
+                row = cv.random_point(rng)
+            lane.row = row
+            dt = cv.d * row[0] * row[1] % cv.p
+            lane.images["R"] = {c: digits(v * cv.R % cv.p, cv.limbs, cv.bits) for c, v in (("x", row[0]), ("y", row[1]), ("dt", dt))}
+            if i % 3 == 1:
+                lane.control |= ROW_NEGATED
 
 
 _POOLS = {}
@@ -457,21 +615,25 @@ def pool(name):
 
 def pack_lanes(cv, lanes):
     """(points, controls) as the bytes dr_<suite>_law_selftest takes"""
-    words = [x for lane in lanes for who in ("P", "Q") for c in cv.coords for x in lane.images[who][c]]
+    words = []
+    for lane in lanes:
+        words += [x for who in ("P", "Q") for c in cv.coords for x in lane.images[who][c]]
+        if cv.te_id is not None:                                                       # dr_te_law_selftest: then the table row
+            words += [x for c in ("x", "y", "dt") for x in lane.images["R"][c]]
     return struct.pack(f"<{len(words)}i", *words), struct.pack(f"<{len(lanes)}I", *[lane.control for lane in lanes])
 
 
 def unpack_slots(cv, raw, count):
     """[{slot: {coordinate: image}}] of the device's output"""
     per = len(cv.coords) * cv.limbs
-    words = struct.unpack(f"<{count * SLOTS * per}i", raw)
+    words = struct.unpack(f"<{count * cv.slots * per}i", raw)
     out = []
     for i in range(count):
         slots = {}
-        for s in range(SLOTS):
-            if s == SLOT_DBL_NO_T and not cv.extended:
+        for s in range(cv.slots):
+            if (s == SLOT_DBL_NO_T and not cv.extended) or (s == SLOT_ENDO and cv.endo is None):
                 continue
-            at = (i * SLOTS + s) * per
+            at = (i * cv.slots + s) * per
             slots[s] = {c: list(words[at + j * cv.limbs : at + (j + 1) * cv.limbs]) for j, c in enumerate(cv.coords)}
         out.append(slots)
     return out
@@ -493,11 +655,20 @@ def expected(cv, lane):
             if not (lane.control >> (8 + w)) & 1:
                 acc = cv.add(acc, cv.neg(table) if (lane.control >> w) & 1 else table)
             want[SLOT_CHAIN + w] = acc
+        if lane.row is not None:
+            row = cv.neg(lane.row) if lane.control & ROW_NEGATED else lane.row
+            want[SLOT_MADD] = cv.add(P, row)
+            twice = cv.add(row, row)
+            want[SLOT_MADD4] = cv.add(twice, twice)
+            want[SLOT_ADD_OUT] = cv.add(want[SLOT_ADD], want[SLOT_DBL])
+            if cv.endo is not None:
+                want[SLOT_ENDO] = cv.from_ref(cv.ref.mul(cv.endo, cv.to_ref(lane.row)))            # of the row as given, not negated
         lane._want = want
     return lane._want
 
 
-SLOT_NAMES = {SLOT_ADD: "add", SLOT_SUB: "sub", SLOT_DBL: "dbl", SLOT_DBL_NO_T: "dbl_no_t", SLOT_NEG: "cneg", SLOT_LDS: "lds", SLOT_KEEP: "keep"}
+SLOT_NAMES = {SLOT_ADD: "add", SLOT_SUB: "sub", SLOT_DBL: "dbl", SLOT_DBL_NO_T: "dbl_no_t", SLOT_NEG: "cneg", SLOT_LDS: "lds", SLOT_KEEP: "keep",
+              SLOT_MADD: "madd", SLOT_MADD4: "madd4", SLOT_ADD_OUT: "add_out", SLOT_ENDO: "endo"}
 
 
 def out_classes(cv, slot, c):
@@ -522,10 +693,12 @@ def check_lane(cv, lane, slots, stats=None):
         xyz = {c: cv.residue(images[c]) for c in cv.coords}
         if not cv.same_point(xyz, want[slot], with_t=slot != SLOT_DBL_NO_T):
             bad.append(f"{lane.what}: slot {slot} ({op}) is not the reference's point")
+        if slot == SLOT_DBL_NO_T and cv.no_t_zero and any(images["t"]):
+            bad.append(f"{lane.what}: slot {slot} ({op}) t = {images['t']} is not the zero image")
         for c in cv.coords:
             classes = out_classes(cv, slot, c)
             if not any(cls.contains(images[c], cv.bits) for cls in classes):
-                bad.append(f"{lane.what}: slot {slot} ({op}) {c} = {images[c]} is outside its class {classes[0].name}")
+                bad.append(f"{lane.what}: slot {slot} ({op}) {c} = {images[c]} is outside its class {classes[0].name}{where_outside(classes[0], images[c], cv.bits)}")
             if stats is not None and slot not in (SLOT_NEG, SLOT_KEEP):
                 limb, val = max(abs(x) for x in images[c]), abs(value_of(images[c], cv.bits))
                 old = stats.get((op, c), (0, 0))
@@ -542,7 +715,20 @@ def check_lane(cv, lane, slots, stats=None):
         # the table keeps limb images: from_lds gives back exactly what to_lds took
         if slots[SLOT_LDS] != slots[SLOT_ADD]:
             bad.append(f"{lane.what}: the point read back from LDS is not the image that was stored")
+    if SLOT_LDS in slots and SLOT_ADD in slots and cv.lds_canonical:
+        # the table keeps the canonical representative of what was stored: the same residue, digit by digit
+        for c in cv.coords:
+            if slots[SLOT_LDS][c] != digits(value_of(slots[SLOT_ADD][c], cv.bits) % cv.p, cv.limbs, cv.bits):
+                bad.append(f"{lane.what}: slot {SLOT_LDS} (lds) {c} is not the canonical image of slot 0's {c}")
     return bad
+
+
+def where_outside(cls, image, bits):
+    """which limb of an image leaves the class, or that its value does"""
+    for j, (x, a, b) in enumerate(zip(image, cls.lo, cls.hi)):
+        if not a <= x <= b:
+            return f": limb {j} = {x} is not in [{a}, {b}]"
+    return f": the value {value_of(image, bits)} is not in ({cls.vlo}, {cls.vhi})"
 
 
 def check_all(cv, lanes, all_slots, stats=None):
@@ -578,6 +764,10 @@ def reimage(cv, lane, rng):
         slots[slot] = images
     if cv.cls_lds is None:
         slots[SLOT_LDS] = {c: list(v) for c, v in slots[SLOT_ADD].items()}
+    if cv.lds_canonical:
+        slots[SLOT_LDS] = {c: digits(value_of(v, cv.bits) % cv.p, cv.limbs, cv.bits) for c, v in slots[SLOT_ADD].items()}
+    if cv.no_t_zero:
+        slots[SLOT_DBL_NO_T]["t"] = [0] * cv.limbs
     if not cv.cneg_carries:
         slots[SLOT_KEEP] = {c: list(v) for c, v in lane.images["P"].items()}
         slots[SLOT_NEG] = {c: [-x if c in cv.neg_coords else x for x in v] for c, v in lane.images["P"].items()}
@@ -600,3 +790,396 @@ def parse_lane_line(cv, text):
     for k, s in enumerate(order):
         slots[s] = {c: words[k * per + j * cv.limbs : k * per + (j + 1) * cv.limbs] for j, c in enumerate(cv.coords)}
     return slots
+
+
+# ================================================================ fr29.hip.h itself on raw limb images (dr_fr_raw_selftest)
+# A record is four images a, b, c, d; the device runs every operation on every record, and a record names the operations whose contract
+# its images meet: only those are checked.  The reference is Python integers: the value of a result (sum l[i] 2^(29 i)) against the
+# value the header promises - a congruence mod p for the Montgomery products and the inverse, the very integer for carries, the
+# addition chains and the canonical words - and every returned limb and value against the class the header documents for that return.
+FR_P = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
+FR_R = 1 << 261
+FR_TOP = 29 * 8
+M29 = (1 << 29) - 1
+FR_LIMB_SLOTS = ("mul", "sqr", "mul2", "carry", "carry_u", "sub_3p", "reduce_small", "repack", "inv", "aA_b", "bmaA_b", "aA_j", "bmaA_j")
+FR_WORD_SLOTS = ("canon29", "canon29_small", "fs_to_std", "to_mont256")
+FR_FLAGS = ("is_zero", "equal")
+FR_IN_WORDS, FR_OUT_WORDS = 4 * 9, len(FR_LIMB_SLOTS) * 9 + len(FR_WORD_SLOTS) * 8 + 1
+# the bounds, each TRANSCRIBED from the header line beside it
+FR_MUL_WIDE, FR_MUL_NARROW = 1 << 30, 1 << 29            # fr29.hip.h:15 "max|a_i| max|b_j| <= 2^59.5 (2^30 x 2^29, ..."
+FR_MUL_BOTH = (16 << 29) // 10                           # fr29.hip.h:15 "... or 1.6 * 2^29 twice"; :18 "sqr(a): max|a_i| <= 1.6 * 2^29"
+FR_MUL_VALUE = 35 * FR_P * FR_P                          # fr29.hip.h:16 "|a| |b| <= 35 p^2 for a normal result"
+FR_MUL2_LIMB = M29                                       # fr29.hip.h:18 "mul2(a, b, c, d): all limbs below 2^29 in magnitude, |a b + c d| <= 35 p^2"
+FR_CARRY_LIMB = (1 << 31) - 5                            # fr29.hip.h, carry(): "|limb| < 2^31 - 4" (t = l[i] + c with c in [-4, 3] must fit)
+FR_CARRY_U_LIMB = (1 << 32) - 8                          # curve.hip.h, carry_u(): low limbs "below 2^32 - 7 as unsigned" (t = l[i] + c, c <= 7)
+FR_REDUCE_VALUE = 30 * FR_P                              # fr29.hip.h, reduce_small: "|value| < 30 p" in, "|value| < 0.51 p" out
+FR_CANON_VALUE = 8 * FR_P                                # fr29.hip.h, canon29: "any value with |value| < 8 p"
+FR_ZERO_VALUE = 4 * FR_P                                 # fr29.hip.h, is_zero / equal: "exact tests for |value| < 4 p"
+FR_PRODUCT_LO, FR_PRODUCT_HI = -(4 * FR_P // 100), 104 * FR_P // 100      # curve.hip.h:66 "products of normal operands (limbs in [0, 2^29),
+#                                                                           values in (-0.04 p, 1.04 p))": the ends te_aA / te_b_minus_aA take
+_VLO, _VHI = -(FR_P // 2) - 1, 3 * FR_P // 2 + 1
+FR_NORMAL = LimbClass("normal", [0] * 8 + [(_VLO >> FR_TOP) - 1], [M29] * 8 + [_VHI >> FR_TOP], vlo=_VLO, vhi=_VHI)       # fr29.hip.h:12
+FR_CARRIED = LimbClass("carried", [0] * 8 + [-(1 << 31)], [M29] * 8 + [(1 << 31) - 1])                                       # fr29.hip.h:19
+FR_SIGNED29 = LimbClass("within (-2^29, 2^29)", [-M29] * 9, [M29] * 9)                                                       # curve.hip.h:68, :76
+FR_LAZY = LimbClass("lazy", [-(1 << 30)] * 9, [1 << 30] * 9)                     # a form for exact values: limbs near +-2^30
+FR_BIG = LimbClass("big", [-FR_CARRY_LIMB] * 9, [FR_CARRY_LIMB] * 9)              # ... and near the bound of carry()
+
+
+def fr_value(image, unsigned_low=False):
+    """sum l[i] 2^(29 i); unsigned_low: limbs 0..7 read as the 32-bit unsigned words carry_u takes"""
+    return sum(((x & 0xFFFFFFFF) if unsigned_low and i < 8 else x) << (29 * i) for i, x in enumerate(image))
+
+
+def fr_digits(v):
+    """the carried image of any integer: limbs 0..7 in [0, 2^29), the signed top limb what is left"""
+    return digits(v, 9, 29)
+
+
+def fr_at(low, want):
+    """limbs 0..7 exactly as given, the top limb such that the value is the nearest to `want` that is not beyond it (seen from zero):
+    the low limbs sit AT their bound and the value within 2^232 = p / 7.6e6 of its bound"""
+    lv = fr_value(list(low) + [0])
+    top = (want - lv) >> FR_TOP if want >= 0 else -((lv - want) >> FR_TOP)
+    return list(low) + [top]
+
+
+def fr_exact(v, form):
+    """an image of the integer v: "digits" (carried), or written from a corner of FR_LAZY / FR_BIG ("lazy hi", "big alt0", ...)"""
+    if form == "digits":
+        return fr_digits(v)
+    cls, corner = form.split()
+    image = image_at({"lazy": FR_LAZY, "big": FR_BIG}[cls], corner, v, 29)
+    assert image is not None and fr_value(image) == v
+    return image
+
+
+def fr_pattern(which, m):
+    """eight low limbs of magnitude m: all positive, all negative, or alternating"""
+    return {"+": [m] * 8, "-": [-m] * 8, "+-": [m, -m] * 4, "-+": [-m, m] * 4}[which]
+
+
+class FrRecord:
+    def __init__(self, what, ops, a, b=None, c=None, d=None):
+        zero = [0] * 9
+        self.what, self.ops = what, frozenset(ops)
+        self.a, self.b, self.c, self.d = (list(x) if x is not None else list(zero) for x in (a, b, c, d))
+        assert self.ops <= set(FR_LIMB_SLOTS + FR_WORD_SLOTS + FR_FLAGS), self.ops
+        assert all(-(1 << 31) <= x < (1 << 32) for img in (self.a, self.b, self.c, self.d) for x in img)
+
+
+def _isqrt(n):
+    import math
+
+    return math.isqrt(n)
+
+
+def build_fr_records(seed=2025):
+    p, rng, out = FR_P, random.Random(f"fr29/{seed}"), []
+    forms = ["digits"] + [f"{cls} {corner}" for cls in ("lazy", "big") for corner in CORNERS]
+
+    def add(what, ops, a, b=None, c=None, d=None):
+        out.append(FrRecord(what, ops, a, b, c, d))
+
+    # ---- mul: the limb bound and the value bound together, every arrangement of signs; then the same pair swapped
+    for wide, narrow, va in ((FR_MUL_WIDE, FR_MUL_NARROW, 7 * p), (FR_MUL_BOTH, FR_MUL_BOTH, _isqrt(FR_MUL_VALUE))):
+        for pa in ("+", "-", "+-", "-+"):
+            for pb in ("+", "-", "+-"):
+                for sa, sb in ((1, 1), (1, -1), (-1, 1), (-1, -1)):
+                    a = fr_at(fr_pattern(pa, wide), sa * va)
+                    b = fr_at(fr_pattern(pb, narrow), sb * (FR_MUL_VALUE // abs(fr_value(a))))
+                    ops = {"mul"} | ({"sqr"} if wide == FR_MUL_BOTH else set())
+                    add(f"mul {wide}x{narrow} {pa} {pb} {sa} {sb}", ops, a, b)
+                    if pb != "+-" or pa == "+-":
+                        add(f"mul swapped {wide}x{narrow} {pa} {pb} {sa} {sb}", {"mul"}, b, a)
+    for s in (1, -1):                                    # the top limb at the bound too
+        a = [s * FR_MUL_WIDE] * 9
+        add(f"mul top limb {s}", {"mul"}, a, fr_at(fr_pattern("+", FR_MUL_NARROW), FR_MUL_VALUE // abs(fr_value(a))))
+    # ---- mul beyond 35 p^2: correct, and wider by |a b| / R (fr29.hip.h:16-17)
+    for sa, sb in ((1, 1), (1, -1), (-1, -1)):
+        add(f"mul beyond {sa} {sb}", {"mul"}, fr_at(fr_pattern("+", FR_MUL_WIDE), sa * 20 * p), fr_at(fr_pattern("-", FR_MUL_NARROW), sb * 10 * p))
+    # ---- sqr: limbs at 1.6 * 2^29, |a|^2 just under 35 p^2
+    for pa in ("+", "-", "+-", "-+"):
+        for s in (1, -1):
+            add(f"sqr {pa} {s}", {"sqr"}, fr_at(fr_pattern(pa, FR_MUL_BOTH), s * _isqrt(FR_MUL_VALUE)))
+    # ---- mul2: all four operands at +-(2^29 - 1); a b + c d at +-35 p^2 with the two products of the same and of opposite signs
+    root = _isqrt(FR_MUL_VALUE // 2)
+    for pats in ("++++", "----", "+-+-", "+--+", "-++-"):
+        pp = list(pats)
+        for total in (1, -1):
+            a = fr_at(fr_pattern(pp[0], FR_MUL2_LIMB), root)
+            b = fr_at(fr_pattern(pp[1], FR_MUL2_LIMB), total * (FR_MUL_VALUE // 2 // fr_value(a)))
+            c = fr_at(fr_pattern(pp[2], FR_MUL2_LIMB), -root)
+            d = fr_at(fr_pattern(pp[3], FR_MUL2_LIMB), -total * (FR_MUL_VALUE // 2 // abs(fr_value(c))))
+            add(f"mul2 same signs {pats} {total}", {"mul2"}, a, b, c, d)
+            # opposite: a b = +-100 p^2 and c d the other way, 35 p^2 apart
+            a = fr_at(fr_pattern(pp[0], FR_MUL2_LIMB), 10 * p)
+            b = fr_at(fr_pattern(pp[1], FR_MUL2_LIMB), total * 10 * p)
+            c = fr_at(fr_pattern(pp[2], FR_MUL2_LIMB), -10 * p)
+            need = abs(fr_value(a) * fr_value(b)) - FR_MUL_VALUE                    # |c d| must be at least this
+            d = fr_at(fr_pattern(pp[3], FR_MUL2_LIMB), total * (-(-need // abs(fr_value(c))) + (1 << FR_TOP)))
+            add(f"mul2 opposite signs {pats} {total}", {"mul2"}, a, b, c, d)
+    for pa in ("+-", "-+"):
+        a = fr_at(fr_pattern(pa, FR_MUL2_LIMB), root)
+        add(f"mul2 alternating {pa}", {"mul2"}, a, fr_at(fr_pattern(pa, FR_MUL2_LIMB), FR_MUL_VALUE // 2 // fr_value(a)), a,
+            fr_at(fr_pattern("-+" if pa == "+-" else "+-", FR_MUL2_LIMB), FR_MUL_VALUE // 2 // fr_value(a)))
+    # ---- carry: negative and mixed-sign limbs at the bound, and ordinary ones
+    for pa in ("+", "-", "+-", "-+"):
+        for top in (12345, -12345, (1 << 30), -(1 << 30)):
+            add(f"carry {pa} {top}", {"carry"}, fr_pattern(pa, FR_CARRY_LIMB) + [top])
+    for j in range(8):
+        add(f"carry mixed {j}", {"carry"}, [rng.randint(-FR_CARRY_LIMB, FR_CARRY_LIMB) for _ in range(9)])
+    # ---- carry_u and sub_3p: sums of normals, low limbs up to the unsigned bound
+    normal_top = FR_NORMAL.hi[8]
+    for k in range(1, 8):                                # k normals with every low limb at 2^29 - 1, at the top of their value range
+        ops = {"carry_u", "sub_3p"}
+        add(f"carry_u {k} normals", ops, [k * M29] * 8 + [k * normal_top])
+        add(f"carry_u {k} normals, low", ops, [k * M29] * 8 + [k * FR_NORMAL.lo[8]])
+    for top in (0, 5 * normal_top, -normal_top):
+        add(f"carry_u at the bound {top}", {"carry_u", "sub_3p"}, [FR_CARRY_U_LIMB] * 8 + [top])
+        add(f"carry_u alternating {top}", {"carry_u", "sub_3p"}, [FR_CARRY_U_LIMB, 0] * 4 + [top])
+    add("carry_u zero", {"carry_u", "sub_3p"}, [0] * 9)
+    for k in (1, 6):                                     # both ends of sub_3p's (0, 6 p), every low limb k (2^29 - 1)
+        add(f"sub_3p just under 6 p, {k}", {"carry_u", "sub_3p"}, fr_at([k * M29] * 8, 6 * p - 1))
+        add(f"sub_3p just above 0, {k}", {"carry_u", "sub_3p"}, fr_at([k * M29] * 8, 2 << FR_TOP))
+    for j in range(8):
+        add(f"carry_u mixed {j}", {"carry_u", "sub_3p"}, [rng.randint(0, FR_CARRY_U_LIMB) for _ in range(8)] + [rng.randint(-normal_top, 6 * normal_top)])
+    # ---- reduce_small: within one unit of +-30 p, and around every (q + 1/2) p, where the float rounding of the top limb picks q: the
+    # two integers beside the half, and eight units of the top limb to either side (the band the float's 24 bits can move q in)
+    for i, v in enumerate((FR_REDUCE_VALUE - 1, -(FR_REDUCE_VALUE - 1), FR_REDUCE_VALUE - (1 << FR_TOP), -(FR_REDUCE_VALUE - (1 << FR_TOP)))):
+        for form in ("digits", "lazy hi", "big lo", "big alt0"):
+            add(f"reduce_small edge {i} {form}", {"reduce_small"}, fr_exact(v, form))
+    for q in range(-30, 30):
+        half = (2 * q + 1) * p // 2                      # floor((q + 1/2) p); p is odd, so the half itself is no integer
+        for j, v in enumerate((half, half + 1, half - (8 << FR_TOP), half + 1 + (8 << FR_TOP))):
+            if abs(v) < FR_REDUCE_VALUE:
+                add(f"reduce_small half {q} {j}", {"reduce_small"}, fr_exact(v, forms[(q + 30 + j) % len(forms)]))
+    # ---- canon29 (k p + v, k = -8 .. 7), canon29_small (the same inside (-p, 3 p)), pack / unpack, inv, the conversions, is_zero
+    n = 0
+    for k in range(-8, 8):
+        for v in (0, 1, p - 1):
+            value = k * p + v
+            for form in ("digits", forms[1 + n % 8]):
+                n += 1
+                ops = {"canon29", "repack", "inv", "fs_to_std", "carry"}
+                if not form.startswith("big"):           # a product with K256 (limbs below 2^29) takes limbs up to 2^30
+                    ops.add("to_mont256")
+                if -p < value < 3 * p:
+                    ops.add("canon29_small")
+                if abs(value) <= FR_ZERO_VALUE and (v == 0 or abs(value) < FR_ZERO_VALUE):
+                    ops.add("is_zero")
+                add(f"canon {k} p + {v if v < 2 else 'p - 1'} {form}", ops, fr_exact(value, form))
+    for v in (-p + 1, 3 * p - 1):                        # the very ends of (-p, 3 p)
+        for form in ("digits", "lazy lo", "big alt1"):
+            add(f"canon29_small end {v // p} {form}", {"canon29_small", "canon29", "repack"}, fr_exact(v, form))
+    # ---- is_zero: every k p, |k| <= 4, from images that are not carried; and non-zero values that pass the limb-0 filter
+    for k in range(-4, 5):
+        for form in forms[1:]:
+            add(f"is_zero {k} p {form}", {"is_zero", "canon29"}, fr_exact(k * p, form))
+    for k in (-3, 0, 3):
+        for dd in list(range(0, 5)) + list(range((1 << 29) - 4, 1 << 29)):
+            v = (dd - k) % (1 << 29) + (rng.randrange(1, p >> 30) << 29)          # k p + v = dd mod 2^29 (p = 1 mod 2^29), 0 < v < p
+            if v % p == 0 or abs(k * p + v) >= FR_ZERO_VALUE:
+                continue
+            form = forms[(dd + k) % len(forms)]
+            image = fr_exact(k * p + v, form)
+            assert (image[0] & M29) == dd
+            add(f"is_zero passes the filter {k} {dd} {form}", {"is_zero", "canon29"}, image)
+    # ---- equal: a - b = k p, and one beside it
+    for k in range(-4, 5):
+        for off in (0, 1, -1):
+            if abs(k * p + off) >= FR_ZERO_VALUE and off:
+                continue
+            va = rng.randrange(-p // 2, 3 * p // 2)
+            form = forms[(k + 4) % len(forms)]
+            a, b = fr_exact(va, "digits" if form.startswith("big") else form), fr_exact(va - k * p - off, "lazy lo" if form.startswith("big") else "digits")
+            add(f"equal {k} p + {off}", {"equal"}, a, b)
+    # ---- te_aA / te_b_minus_aA: A and B at both ends of what a product of normal operands returns (a carried image: one per value),
+    # and with every low limb at 2^29 - 1
+    ends = (FR_PRODUCT_LO, FR_PRODUCT_HI, ((FR_PRODUCT_HI >> FR_TOP) << FR_TOP) - 1, ((FR_PRODUCT_LO >> FR_TOP) + 2 << FR_TOP) - 1, 0)
+    for i, va in enumerate(ends):
+        for j, vb in enumerate(ends):
+            add(f"aA end {i} ({va / p:.3f} p), end {j} ({vb / p:.3f} p)",{"aA_b", "bmaA_b", "aA_j", "bmaA_j"}, fr_digits(va), fr_digits(vb))
+    return out
+
+
+_FR_RECORDS = None
+
+
+def fr_records():
+    global _FR_RECORDS
+    if _FR_RECORDS is None:
+        _FR_RECORDS = build_fr_records()
+    return _FR_RECORDS
+
+
+def fr_spread(count=65):
+    """`count` records from across the pool with every operation among them (and already among the first: a call of one record is
+    still checked for something): the first record that names each operation, then every k-th of the rest"""
+    records = fr_records()
+    picked = []
+    for op in FR_LIMB_SLOTS + FR_WORD_SLOTS + FR_FLAGS:
+        first = next(r for r in records if op in r.ops)
+        if first not in picked:
+            picked.append(first)
+    rest = [r for r in records if r not in picked]
+    picked += rest[:: len(rest) // (count - len(picked))][: count - len(picked)]
+    assert len(picked) == count
+    return picked
+
+
+def pack_fr_records(records):
+    words = [x - (1 << 32) if x >= (1 << 31) else x for r in records for img in (r.a, r.b, r.c, r.d) for x in img]
+    return struct.pack(f"<{len(words)}i", *words)
+
+
+def unpack_fr_results(raw, count):
+    """[{name: nine limbs | an integer (the 8-word results) | a flag}] of the device's output"""
+    words = struct.unpack(f"<{count * FR_OUT_WORDS}I", raw)
+    out = []
+    for i in range(count):
+        w = words[i * FR_OUT_WORDS : (i + 1) * FR_OUT_WORDS]
+        res = {name: [x - (1 << 32) if x >= (1 << 31) else x for x in w[9 * s : 9 * s + 9]] for s, name in enumerate(FR_LIMB_SLOTS)}
+        at = 9 * len(FR_LIMB_SLOTS)
+        for s, name in enumerate(FR_WORD_SLOTS):
+            res[name] = sum(x << (32 * j) for j, x in enumerate(w[at + 8 * s : at + 8 * s + 8]))
+        res["is_zero"], res["equal"] = w[-1] & 1, (w[-1] >> 1) & 1
+        out.append(res)
+    return out
+
+
+# ---- the operations in Python integers, limb for limb where the header fixes the limbs (a carried image is unique, and so is the m of
+# a Montgomery product); the checker uses them to NAME the limb that differs, the CPU tests as the reference's own results
+_P_INV = pow(FR_P, -1, FR_R)
+
+
+def fr_montgomery(pairs):
+    """(sum a b + m p) / R with the one m in [0, R) that makes the division exact, carried"""
+    s = sum(fr_value(a) * fr_value(b) for a, b in pairs)
+    m = -s * _P_INV % FR_R
+    return fr_digits((s + m * FR_P) >> 261)
+
+
+def _limbwise(f, *images):
+    return [f(*xs) for xs in zip(*images)]
+
+
+def fr_model(r):
+    """what the header promises for a record, as {name: result}; reduce_small and inv as ONE admissible result"""
+    p, a, b = FR_P, r.a, r.b
+    va = fr_value(a)
+    u = fr_digits(fr_value(a, True))
+    p3 = fr_digits(3 * p)
+    five = fr_digits(fr_value([5 * x for x in a[:8]] + [5 * a[8]]))
+    fiveb = fr_digits(fr_value([5 * x + y for x, y in zip(a[:8], b[:8])] + [5 * a[8] + b[8]]))
+    inv = pow(va * pow(FR_R, -1, p) % p, -1, p) if va % p else 0
+    return {
+        "mul": fr_montgomery([(a, b)]), "sqr": fr_montgomery([(a, a)]), "mul2": fr_montgomery([(a, b), (r.c, r.d)]),
+        "carry": fr_digits(va), "carry_u": u, "sub_3p": _limbwise(lambda x, y: x - y, u, p3),
+        "reduce_small": fr_digits(va - (2 * va + p) // (2 * p) * p), "repack": fr_digits(va % p), "inv": fr_digits(inv * FR_R % p),
+        "aA_b": _limbwise(lambda x, y: y - x, five, p3), "bmaA_b": _limbwise(lambda x, y: x - y, fiveb, p3),
+        "aA_j": [-x for x in a], "bmaA_j": fr_digits(va + fr_value(b)),
+        "canon29": va % p, "canon29_small": va % p, "fs_to_std": va * pow(FR_R, -1, p) % p, "to_mont256": (va << 256) * pow(FR_R, -1, p) % p,
+        "is_zero": int(va % p == 0), "equal": int((va - fr_value(b)) % p == 0),
+    }
+
+
+def fr_model_words(r):
+    """fr_model as the device's output words"""
+    m = fr_model(r)
+    words = [x & 0xFFFFFFFF for name in FR_LIMB_SLOTS for x in m[name]]
+    words += [(m[name] >> (32 * j)) & 0xFFFFFFFF for name in FR_WORD_SLOTS for j in range(8)]
+    return struct.pack(f"<{FR_OUT_WORDS}I", *words, m["is_zero"] | m["equal"] << 1)
+
+
+def fr_mul_class(product):
+    """what fr29.hip.h:12-17 documents for a Montgomery product of the integer a b (+ c d): normal up to 35 p^2, beyond it "wider by
+    |a b| / (R / p) p": limbs 0..7 in [0, 2^29) either way"""
+    if abs(product) <= FR_MUL_VALUE:
+        return FR_NORMAL
+    wide = abs(product) // FR_R + 1
+    return LimbClass("wide product", [0] * 8 + [-(1 << 31)], [M29] * 8 + [(1 << 31) - 1], vlo=-wide, vhi=FR_P + wide)
+
+
+def check_fr_record(r, res, stats=None):
+    """the failures of one record's results (an empty list: all is well): the slot, what it should be, and the limb that differs"""
+    p, bad = FR_P, []
+    va, vb = fr_value(r.a), fr_value(r.b)
+    model = fr_model(r)
+
+    def differs(name):
+        got, want = res[name], model[name]
+        j = next((j for j in range(9) if got[j] != want[j]), None)
+        return "" if j is None else f"; limb {j} = {got[j]}, the header's arithmetic gives {want[j]}"
+
+    def limbs_in(name, cls):
+        if not cls.contains(res[name], 29):
+            bad.append(f"{r.what}: slot {name} = {res[name]} is outside its class {cls.name}{where_outside(cls, res[name], 29)}{differs(name)}")
+
+    def congruent(name, want_times_r):
+        """value(result) R^-1 = expected, i.e. value(result) = expected R (mod p)"""
+        if (fr_value(res[name]) - want_times_r) % p:
+            bad.append(f"{r.what}: slot {name} = {res[name]} is not congruent to what the reference computes{differs(name)}")
+
+    def exactly(name, want):
+        if fr_value(res[name]) != want:
+            bad.append(f"{r.what}: slot {name} = {res[name]} has the value {fr_value(res[name])}, not {want}{differs(name)}")
+
+    r_inv = pow(FR_R, -1, p)
+    for name in sorted(r.ops):
+        if name in ("mul", "sqr", "mul2"):
+            product = {"mul": va * vb, "sqr": va * va, "mul2": va * vb + fr_value(r.c) * fr_value(r.d)}[name]
+            congruent(name, product * r_inv)
+            limbs_in(name, fr_mul_class(product))
+        elif name == "carry":
+            exactly(name, va)
+            limbs_in(name, FR_CARRIED)
+        elif name == "carry_u":
+            exactly(name, fr_value(r.a, True))
+            limbs_in(name, FR_CARRIED)
+        elif name == "sub_3p":
+            v = fr_value(r.a, True)
+            exactly(name, v - 3 * p)
+            # fr29.hip.h, sub_3p: "limbs of a normal -> limbs in (-2^29, 2^29)"; the top limb too for "a value known to lie in (0, 6p)"
+            if 0 < v < 6 * p:
+                limbs_in(name, FR_SIGNED29)
+            elif any(abs(x) > M29 for x in res[name][:8]):
+                bad.append(f"{r.what}: slot {name} = {res[name]} has a low limb outside (-2^29, 2^29){differs(name)}")
+        elif name == "reduce_small":
+            congruent(name, va)
+            limbs_in(name, LimbClass("carried, |value| < 0.51 p", FR_CARRIED.lo, FR_CARRIED.hi, vmax=51 * p // 100 + 1))
+        elif name == "repack":
+            if res[name] != fr_digits(va % p):
+                bad.append(f"{r.what}: slot {name} = {res[name]} is not the canonical image{differs(name)}")
+        elif name == "inv":
+            congruent(name, (pow(va * r_inv % p, -1, p) if va % p else 0) * FR_R)
+            limbs_in(name, FR_NORMAL)
+        elif name == "aA_b":
+            exactly(name, 3 * p - 5 * va)                                             # curve.hip.h:76 "3p - 5A in (-2.2 p, 3.2 p)", limbs within (-2^29, 2^29)
+            limbs_in(name, LimbClass(FR_SIGNED29.name, FR_SIGNED29.lo, FR_SIGNED29.hi, vlo=-22 * p // 10, vhi=32 * p // 10 + 1))
+        elif name == "bmaA_b":
+            exactly(name, vb + 5 * va - 3 * p)                                        # curve.hip.h:67 "B + 5A - 3p in (-3.3 p, 3.3 p)"
+            limbs_in(name, LimbClass(FR_SIGNED29.name, FR_SIGNED29.lo, FR_SIGNED29.hi, vmax=33 * p // 10))
+        elif name == "aA_j":
+            if res[name] != [-x for x in r.a]:                                        # curve.hip.h:76 "JubJub -A"
+                bad.append(f"{r.what}: slot {name} = {res[name]} is not the limb-wise negation{differs(name)}")
+        elif name == "bmaA_j":
+            exactly(name, va + vb)                                                    # curve.hip.h:67 "kept as B + A (<= 2.1 p)"
+            limbs_in(name, LimbClass("carried, <= 2.1 p", FR_CARRIED.lo, FR_CARRIED.hi, vlo=-p, vhi=21 * p // 10 + 1))
+        elif name in FR_WORD_SLOTS or name in FR_FLAGS:
+            if res[name] != model[name]:
+                bad.append(f"{r.what}: {name} = {res[name]:#x}, the reference computes {model[name]:#x}")
+        if stats is not None and name in FR_LIMB_SLOTS:
+            old = stats.get(name, (0, 0))
+            stats[name] = (max(old[0], max(abs(x) for x in res[name])), max(old[1], abs(fr_value(res[name]))))
+    return bad
+
+
+def check_fr_records(records, results, stats=None):
+    assert len(records) == len(results)
+    return [b for r, res in zip(records, results) for b in check_fr_record(r, res, stats)]
+
+
+def format_fr_stats(stats):
+    import math
+
+    return "\n".join(f"fr29 {name:13s} max |limb| 2^{math.log2(limb) if limb else 0:.3f}  max |value| {val / FR_P:.4f} p" for name, (limb, val) in sorted(stats.items()))

@@ -2,7 +2,11 @@
 corner of every in-class is reached at the smallest and at the largest multiple of p, the checker accepts the reference's own results
 re-imaged and rejects a limb changed by one, a point replaced by its negative and an image one unit outside its out-class; and the
 host builds of the 384-, 521- and 448-bit laws under -fsanitize=undefined run the same lanes through the same checker (the `lane` line of
-tests/native/*_host_check.cpp), where a signed column overflow at the edge of a contract aborts."""
+tests/native/*_host_check.cpp), where a signed column overflow at the edge of a contract aborts.
+
+The same for the lanes of Bandersnatch and JubJub (dr_te_law_selftest): their table rows, the four further slots and the scalar of
+the endomorphism.  Their products are montmul9x29_asm, gfx950 assembly: there is no host build of this law to run under a sanitizer,
+and none is loaded into Python."""
 import os
 import random
 import subprocess
@@ -15,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "dot_ring_amd", "csrc")
 
 
-@pytest.mark.parametrize("name", L.CURVES)
+@pytest.mark.parametrize("name", L.CURVES + L.TE_CURVES)
 def test_every_image_is_in_its_class_and_every_corner_is_reached(name):
     cv, pool = L.curve(name), L.pool(name)
     assert len(pool.lanes) > 65
@@ -45,7 +49,7 @@ def test_every_image_is_in_its_class_and_every_corner_is_reached(name):
     assert any((k & 3) == 3 and not (k >> 8) & 3 for k in controls) and any((k & 3) == 0 and not (k >> 8) & 3 for k in controls)   # equal signs in a row
 
 
-@pytest.mark.parametrize("name", L.CURVES)
+@pytest.mark.parametrize("name", L.CURVES + L.TE_CURVES)
 def test_checker_accepts_the_reference_and_rejects_what_is_wrong(name):
     cv, pool = L.curve(name), L.pool(name)
     rng = random.Random(name)
@@ -89,7 +93,79 @@ def test_checker_accepts_the_reference_and_rejects_what_is_wrong(name):
         slots[L.SLOT_DBL]["t"][0] ^= 1
         slots[L.SLOT_DBL_NO_T]["t"][0] ^= 1
         bad = L.check_lane(cv, lane, slots)
-        assert any("slot 2" in b for b in bad) and not any("slot 3" in b for b in bad)
+        if cv.no_t_zero:                              # ... but where the law documents the zero image for it, that is asked
+            assert any("slot 2" in b for b in bad) and [b for b in bad if "slot 3" in b] == [b for b in bad if "not the zero image" in b] != []
+        else:
+            assert any("slot 2" in b for b in bad) and not any("slot 3" in b for b in bad)
+
+
+@pytest.mark.parametrize("name", L.TE_CURVES)
+def test_te_rows_small_points_and_the_four_further_slots(name):
+    cv, pool = L.curve(name), L.pool(name)
+    p, ref = cv.p, cv.ref
+    # the small-order points: Bandersnatch has the one affine point of order 2 (the other two are at infinity: a = -5 is no square) and
+    # points whose multiple by N is at infinity; JubJub all seven of its cyclic 8-torsion, orders 2, 4, 4, 8, 8, 8, 8
+    orders = sorted(next(k for k in (1, 2, 4, 8) if ref.mul(k, t) == (0, 1)) for t in cv.torsion)
+    assert orders == ([2] if name == "bandersnatch" else [2, 4, 4, 8, 8, 8, 8]) and (0, p - 1) in cv.torsion
+    assert len(cv.outside) == (2 if name == "bandersnatch" else 1)
+    for pt in cv.outside:
+        assert ref.on_curve(pt)
+        try:
+            assert ref.mul(ref.N, pt) != (0, 1)
+        except ZeroDivisionError:
+            assert name == "bandersnatch"
+    for s in cv.specials:
+        assert sum(1 for lane in pool.lanes if lane.P == s) >= 3 and sum(1 for lane in pool.lanes if lane.Q == s) >= 2
+    # the scalar of the endomorphism, from the lattice basis of glv_decompose: lambda^2 + 2 = 0 mod N
+    if cv.endo is not None:
+        assert (cv.endo * cv.endo + 2) % ref.N == 0
+    # every row is unpack of canonical words, of a point of the curve with dt = d x y; both signs; the identity; P and -P
+    canon = cv.cls_lds["x"]
+    for lane in pool.lanes:
+        x, y, dt = (cv.residue(lane.images["R"][c]) for c in ("x", "y", "dt"))
+        assert all(canon.contains(lane.images["R"][c], 29) for c in ("x", "y", "dt")) and (x, y) == lane.row and ref.on_curve(lane.row)
+        assert dt == ref.D * x * y % p
+        if cv.endo is not None and lane.row != (0, 1):
+            assert ref.mul(ref.N, lane.row) == (0, 1)                                                    # what the endomorphism is defined on
+    assert {bool(lane.control & L.ROW_NEGATED) for lane in pool.lanes} == {True, False}
+    assert any(lane.row == (0, 1) for lane in pool.lanes) and any(lane.row == lane.P != (0, 1) for lane in pool.lanes)
+    assert any(lane.row == cv.neg(lane.P) != lane.P for lane in pool.lanes)
+    if cv.endo is None:
+        assert {lane.row for lane in pool.lanes} >= set(cv.torsion)
+    # the checker sees the four further slots, T Z = X Y and the zero T of dbl_no_t, and the canonical LDS image
+    rng = random.Random(name)
+    lane = next(x for x in pool.lanes if x.what.startswith("mixed") and x.row not in ((0, 1), x.P, cv.neg(x.P)))
+    further = [L.SLOT_MADD, L.SLOT_MADD4, L.SLOT_ADD_OUT] + ([L.SLOT_ENDO] if cv.endo is not None else [])
+    assert sorted(L.reimage(cv, lane, rng)) == sorted(list(range(13)) + further)
+    for slot in further:
+        for c in cv.coords:
+            slots = L.reimage(cv, lane, rng)
+            slots[slot][c][rng.randrange(8)] ^= 1
+            assert any(f"slot {slot} " in b and "not the reference's point" in b for b in L.check_lane(cv, lane, slots)), (slot, c)
+        slots = L.reimage(cv, lane, rng)
+        for c in cv.neg_coords:
+            slots[slot][c] = [-v for v in slots[slot][c]]
+        assert any(f"slot {slot} " in b for b in L.check_lane(cv, lane, slots)), slot
+        slots = L.reimage(cv, lane, rng)
+        slots[slot]["y"][3] = 1 << 29
+        assert any(f"slot {slot} " in b and "limb 3 = 536870912 is not in" in b for b in L.check_lane(cv, lane, slots)), slot
+    slots = L.reimage(cv, lane, rng)
+    slots[L.SLOT_DBL_NO_T]["t"][0] = 1
+    assert any("not the zero image" in b for b in L.check_lane(cv, lane, slots))
+    slots = L.reimage(cv, lane, rng)
+    slots[L.SLOT_LDS]["y"] = [v + w for v, w in zip(slots[L.SLOT_LDS]["y"], L.digits(p, 9, 29))]        # the same residue, not canonical
+    assert any("slot 5" in b for b in L.check_lane(cv, lane, slots))
+    # the row's sign reaches the expectation: the other sign is rejected
+    lane.control ^= L.ROW_NEGATED
+    lane._want = None
+    other = L.reimage(cv, lane, rng)
+    lane.control ^= L.ROW_NEGATED
+    lane._want = None
+    assert any("slot 13" in b for b in L.check_lane(cv, lane, other)) and any("slot 14" in b for b in L.check_lane(cv, lane, other))
+    # the record as the device takes it: P, Q, the row, 11 x 9 limbs; 17 points back
+    records, controls = L.pack_lanes(cv, pool.lanes[:3])
+    assert len(records) == 3 * 11 * 9 * 4 and len(controls) == 12
+    assert L.unpack_slots(cv, bytes(3 * 17 * 36 * 4), 3)[0].keys() == set(range(13)) | set(further)
 
 
 HOST_CHECKS = {"p384": "p384_host_check.cpp", "p521": "p521_host_check.cpp", "curve448": "c448_law_host_check.cpp", "ed448": "e448_law_host_check.cpp"}
