@@ -137,6 +137,8 @@ _PROTOTYPES.update({
     "dr_blsg2_encode_to_curve_batch": (c_int, [c_void_p, c_int, c_char_p, POINTER(ctypes.c_uint64), c_char_p, POINTER(ctypes.c_uint64), c_size_t,
                                                c_char_p]),
     "dr_blsg2_scalar_mul_batch": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_char_p]),
+    "dr_blsg2_msm_groups": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_size_t, c_char_p]),
+    "dr_blsg2_msm": (c_int, [c_void_p, c_int, c_char_p, c_char_p, c_size_t, c_char_p]),
     "dr_blsg2_check_points": (c_int, [c_void_p, c_int, c_char_p, c_size_t, c_char_p]),
     "dr_blsg2_field_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p, c_void_p]),
     "dr_ed448_hash_to_field_batch": (c_int, [c_int, c_char_p, POINTER(ctypes.c_uint64), c_size_t, c_char_p]),
@@ -215,7 +217,8 @@ _PROTOTYPES.update({
 })
 # the group laws on raw limb images (csrc/wave_curve.hip.h, wave_law_selftest): suite -> (limbs of a coordinate, coordinates of a point)
 LAW_SELFTEST_SHAPES = {"ed25519": (9, 4), "bjj": (9, 4), "p256": (9, 3), "secp256k1": (9, 3), "blsg1": (14, 3), "ed448": (16, 3),
-                       "curve448": (16, 3), "p521": (19, 3), "p384": (14, 3)}
+                       "curve448": (16, 3), "p521": (19, 3), "p384": (14, 3),
+                       "blsg2": (28, 3)}   # E(Fq2), a coordinate c0 then c1: a kernel of its own with the same shape and slots (csrc/kernels_g2_msm.hip.h)
 LAW_SELFTEST_SLOTS = 13
 _PROTOTYPES.update({f"dr_{suite}_law_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_void_p]) for suite in LAW_SELFTEST_SHAPES})
 # fr29.hip.h and curve.hip.h's law on raw limb images (kernels_bsn.hip.h: k_fr_raw_selftest, k_te_law_selftest)
@@ -393,6 +396,7 @@ _WIDE = {
 
 WIDE_PIP_FROM = 256            # csrc/msm_plan.hpp: the term count from which dr_wide_msm takes the bucket method
 NARROW_PIP_FROM = 257          # csrc/msm_plan.hpp: the same for dr_te_msm on the native 256-bit curves and for dr_blsg1_msm
+BLSG2_PIP_FROM = 257           # csrc/msm_plan.hpp: the same for dr_blsg2_msm on BLS12-381's E(Fq2)
 # the suites dr_wide_msm serves, by the curve id it takes (either variant: RO and NU are one group)
 _WIDE_MSM_CURVE = {"p384": CURVE_P384_RO, "p521": CURVE_P521_RO, "ed448": CURVE_ED448_RO, "curve448": CURVE_CURVE448_RO}
 
@@ -831,6 +835,16 @@ class Context:
         _check(lib().dr_blsg1_msm(self.handle, CURVE_BLS12_381_G1, pts_xy, scalars, n, out))
         return out.raw[:96]
 
+    def blsg2_msm(self, pts_xy: bytes, scalars: bytes, curve: int = CURVE_BLS12_381_G2) -> bytes:
+        """dr_blsg2_msm: ONE sum of n terms k_i P_i on BLS12-381's E(Fq2), 192-byte points and 32-byte scalars used as they are; from
+        BLSG2_PIP_FROM terms on by the bucket method (csrc/wave_msm.hip.h over csrc/kernels_g2_msm.hip.h).  No terms give the identity."""
+        n = len(scalars) // 32
+        if len(scalars) != 32 * n or len(pts_xy) != 192 * n:
+            raise ValueError("Points and scalars must have same length")
+        out = ctypes.create_string_buffer(192)
+        _check(lib().dr_blsg2_msm(self.handle, curve, pts_xy, scalars, n, out))
+        return out.raw[:192]
+
     def _wide_flagged(self, suite: str, enc: bytes, check: bool = True):
         """dr_<suite>_decode_points: (x||y bytes, flags) for G1's 49-byte SEC1 encodings (check: also r P = O) and Ed448's 112-byte points
         (coordinates below p and on the curve; check: also not the identity and n P = O).  dr_blsg2_check_points: the flags alone, one per
@@ -863,6 +877,7 @@ class Context:
     blsg2_map_to_curve = functools.partialmethod(_wide_map_to_curve, "blsg2")
     blsg2_encode_to_curve_batch = functools.partialmethod(_wide_encode_to_curve_batch, "blsg2")
     blsg2_scalar_mul_batch = functools.partialmethod(_wide_scalar_mul_batch, "blsg2")
+    blsg2_msm_groups = functools.partialmethod(_wide_msm_groups, "blsg2")
     blsg2_field_selftest = functools.partialmethod(_wide_field_selftest, "blsg2")
     ed448_map_to_curve = functools.partialmethod(_wide_map_to_curve, "ed448")
     ed448_encode_to_curve_batch = functools.partialmethod(_wide_encode_to_curve_batch, "ed448")
@@ -909,6 +924,7 @@ class Context:
     curve448_law_selftest = functools.partialmethod(_law_selftest, "curve448")
     p521_law_selftest = functools.partialmethod(_law_selftest, "p521")
     p384_law_selftest = functools.partialmethod(_law_selftest, "p384")
+    blsg2_law_selftest = functools.partialmethod(_law_selftest, "blsg2")
 
     def fr_raw_selftest(self, images: bytes) -> bytes:
         """dr_fr_raw_selftest: n x 150 little-endian words for n records of four raw images of nine int32 limbs (include/dotring_hip.h

@@ -41,6 +41,9 @@ struct SuiteDefaults {
     static constexpr bool wide_affine = false;
     static constexpr size_t wide_from = dr::WIDE_PIP_FROM;
     static constexpr const char* wide_names[5] = {"k_wide_msm_prepare", "k_wide_msm_sort", "k_wide_msm_accumulate", "k_wide_msm_reduce", nullptr};
+    // the law diagnostic's scratch in io_c per LANE of its launch, handed to the kernel as a fifth operand (G2: one record of the bucket
+    // method, where the other curves' diagnostic goes through the LDS table)
+    static constexpr size_t law_lane_bytes = 0;
 };
 
 // BLS12-381's base field element (48 bytes little-endian) below p: shared by the G1 and G2 suites
@@ -232,7 +235,8 @@ int field_selftest(dr_ctx* ctx, const int32_t* a_limbs, const int32_t* b_limbs, 
 }
 
 // wave_curve.hip.h's wave_law_selftest over the suite's curve: n records of S::law_coords coordinates for P and as many for Q, raw limb
-// images of S::limb_bytes each, and n control words in; n x S::law_slots (wave_curve.hip.h's WAVE_LAW_SLOTS) points in the same form out; not profiled
+// images of S::limb_bytes each, and n control words in; n x S::law_slots (wave_curve.hip.h's WAVE_LAW_SLOTS) points in the same form out; not profiled.
+// A suite with law_lane_bytes gives a kernel of the same shape that takes its per-lane scratch (io_c) as a fifth operand.
 template <class S>
 int law_selftest(dr_ctx* ctx, const int32_t* points, const uint32_t* controls, size_t n, int32_t* out) {
     TRY(use_ctx(ctx));
@@ -241,10 +245,14 @@ int law_selftest(dr_ctx* ctx, const int32_t* points, const uint32_t* controls, s
     if (n >= MAX_SELFTEST) return fail(DR_ERR_INVALID, "batch too large");
     TRY(S::consts_ready(ctx));
     constexpr size_t pt = (size_t)S::law_coords * S::limb_bytes;
-    return io_round(ctx, {n * (2 * pt + 4), n * S::law_slots * pt, 0},
+    return io_round(ctx, {n * (2 * pt + 4), n * S::law_slots * pt, (size_t)div_up(n, 64) * 64 * S::law_lane_bytes},
                     {{&ctx->io_a, 0, points, n * 2 * pt}, {&ctx->io_a, n * 2 * pt, controls, n * 4}}, nullptr, [&] {
-        hipLaunchKernelGGL(S::law_selftest, dim3(div_up(n, 64)), dim3(64), 0, ctx->stream, ctx->io_a.as<int32_t>(),
-                           (const uint32_t*)(ctx->io_a.as<uint8_t>() + n * 2 * pt), (uint32_t)n, ctx->io_b.as<int32_t>());
+        if constexpr (S::law_lane_bytes != 0)
+            hipLaunchKernelGGL(S::law_selftest, dim3(div_up(n, 64)), dim3(64), 0, ctx->stream, ctx->io_a.as<int32_t>(),
+                               (const uint32_t*)(ctx->io_a.as<uint8_t>() + n * 2 * pt), (uint32_t)n, ctx->io_b.as<int32_t>(), ctx->io_c.as<uint32_t>());
+        else
+            hipLaunchKernelGGL(S::law_selftest, dim3(div_up(n, 64)), dim3(64), 0, ctx->stream, ctx->io_a.as<int32_t>(),
+                               (const uint32_t*)(ctx->io_a.as<uint8_t>() + n * 2 * pt), (uint32_t)n, ctx->io_b.as<int32_t>());
     }, {{out, &ctx->io_b, 0, n * S::law_slots * pt}});
 }
 

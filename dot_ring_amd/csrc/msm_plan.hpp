@@ -121,6 +121,8 @@ constexpr uint32_t WIDE_MAX_H = 512;                       // wave_msm_sort: bin
 // (tests/golden/entry_surface_gpu.json).  The value is the smallest measured size at which the buckets beat msm_groups on all six
 // curves.
 constexpr size_t NARROW_PIP_FROM = 257;
+// ... and under dr_blsg2_msm for BLS12-381's E(Fq2): the project's value for E(Fq); nothing else depends on it
+constexpr size_t BLSG2_PIP_FROM = NARROW_PIP_FROM;
 
 struct WideMsmPlan {
     int c = 0;                           // window width asked for; wide_cmax(wt) is the widest one of the tiling

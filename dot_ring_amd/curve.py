@@ -1011,9 +1011,10 @@ class Fp2:
 class Bls12381G2Point(_WideRfc9380, _AffinePoint):
     """Affine point of E(Fq2): y^2 = x^3 + 4 (1 + i) over BLS12-381's quadratic extension (dot_ring/curve/specs/bls12_381_G2.py), the
     identity is (None, None); coordinates are Fp2 values ((re, im) tuples are accepted).  E(Fq2) has order h2 r (762 bits): a point need
-    not lie in G2, so scalars are never reduced mod r.  Single additions are host big-integer code; scalar multiplications and hashing to
-    the curve (RFC 9380: simplified SWU, the 3-isogeny, the clearing by psi) run on the GPU (kernels_g2_h2c.hip.h, the dr_blsg2_* entry
-    points).  There is no point codec, as in the reference."""
+    not lie in G2, so scalars are never reduced mod r.  Single additions are host big-integer code; scalar multiplications, sums of
+    scalar multiples (msm, msm_groups: kernels_g2_msm.hip.h), the subgroup check and hashing to the curve (RFC 9380: simplified SWU, the
+    3-isogeny, the clearing by psi) run on the GPU (kernels_g2_h2c.hip.h, the dr_blsg2_* entry points).  Scalars on this curve are
+    public: none of it is a fixed schedule.  There is no point codec, as in the reference."""
     _P = 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB
     _N = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
     # h_eff of RFC 9380 8.8.2: the reference's `cofactor`, what clear_cofactor multiplies by (636 bits)
@@ -1110,6 +1111,93 @@ class Bls12381G2Point(_WideRfc9380, _AffinePoint):
         return self._unpack(runtime.context().blsg2_scalar_mul_batch(self._pack([self]), k.to_bytes(96, "little")))[0]
 
     __rmul__ = __mul__
+
+    @classmethod
+    def _wide_scalar(cls, k) -> int:
+        """a scalar as the 96-byte entry points take it: negative or 2^768 and more goes mod #E(Fq2) = h2 r, the exponent of every point"""
+        k = int(k)
+        return k if 0 <= k < 1 << 768 else k % (cls._COFACTOR * cls._N)
+
+    @classmethod
+    def _terms(cls, points, scalars):
+        """(points, scalars below 2^256) with the same sum of products: a scalar outside [0, 2^256) is reduced mod #E(Fq2) = h2 r (762
+        bits) and, if still 2^256 or more, split as k0 + 2^256 k1 + 2^512 k2 over P, 2^256 P and 2^512 P; the shifted points of all such
+        terms come from one scalar_mul_batch"""
+        pts, ks, wide = [], [], []
+        for pt, k in zip(points, scalars):
+            k = int(k)
+            if not 0 <= k < 1 << 256:
+                k %= cls._COFACTOR * cls._N
+            if k < 1 << 256:
+                pts.append(pt)
+                ks.append(k)
+            else:
+                wide.append((pt, k))
+        if wide:
+            shifts = [s for _, k in wide for s in ((256, 512) if k >> 512 else (256,))]
+            bases = [pt for pt, k in wide for _ in ((256, 512) if k >> 512 else (256,))]
+            shifted = iter(cls._unpack(runtime.context().blsg2_scalar_mul_batch(cls._pack(bases),
+                                                                                b"".join((1 << s).to_bytes(96, "little") for s in shifts))))
+            mask = (1 << 256) - 1
+            for pt, k in wide:
+                pts += [pt, next(shifted)]
+                ks += [k & mask, (k >> 256) & mask]
+                if k >> 512:
+                    pts.append(next(shifted))
+                    ks.append(k >> 512)
+        return pts, ks
+
+    @classmethod
+    def msm(cls, points, scalars):
+        """sum k_i P_i for any integers k_i and any points of E(Fq2): dr_blsg2_msm on terms with scalars below 2^256 — msm_groups' kernel
+        in chunks of 64 below BLSG2_PIP_FROM terms, the bucket method from there on.  For public scalars, as everything on this curve."""
+        if len(points) != len(scalars):
+            raise ValueError("Points and scalars must have same length")
+        pts, ks = cls._terms(points, scalars)
+        if not pts:
+            return cls.identity()
+        return cls._unpack(runtime.context().blsg2_msm(cls._pack(pts), b"".join(k.to_bytes(32, "little") for k in ks)))[0]
+
+    # -- the batch operations of this type, as classmethods of its own.  They are NOT hooked under the module-level helpers
+    # (scalar_mul_batch, msm_groups, valid_points, curve.valid_point): what those do on a point of this type is part of the recorded
+    # point surface (tests/golden/point_surface_*.json) and stays as it is.
+    @classmethod
+    def scalar_mul_batch(cls, points, scalars):
+        """[k_i P_i] in one launch; negative scalars and scalars of 2^768 or more as __mul__ treats them"""
+        if len(points) != len(scalars):
+            raise ValueError("Points and scalars must have same length")
+        if not points:
+            return []
+        ks = b"".join(cls._wide_scalar(k).to_bytes(96, "little") for k in scalars)
+        return cls._unpack(runtime.context().blsg2_scalar_mul_batch(cls._pack(points), ks))
+
+    @classmethod
+    def msm_groups(cls, points, scalars, m: int):
+        """[sum_{j<m} k_{g m + j} P_{g m + j}] for consecutive groups of m terms: one launch of dr_blsg2_msm_groups for m <= 64 (96-byte
+        scalars, reduced mod h2 r only where they are negative or 2^768 and more), one msm per group above that"""
+        if len(points) != len(scalars):
+            raise ValueError("Points and scalars must have same length")
+        if not points:
+            return []
+        if m > 64:
+            return [cls.msm(points[i : i + m], scalars[i : i + m]) for i in range(0, len(points), m)]
+        ks = b"".join(cls._wide_scalar(k).to_bytes(96, "little") for k in scalars)
+        return cls._unpack(runtime.context().blsg2_msm_groups(cls._pack(points), ks, m))
+
+    @classmethod
+    def valid_points(cls, points) -> list[bool]:
+        """the reference's valid_point for a batch: false for the identity and for what is off the curve, otherwise r P = O by the
+        subgroup mode of check_points.  The reference asks h_eff P != O and (h_eff^-1 mod r) h_eff P = P.  #E(Fq2) = h2 r with r prime and
+        not dividing h2, so a point of the curve is P = P_r + P_h in one way with r P_r = O and h2 P_h = O.  h_eff (_H) is a multiple of
+        h2 (_COFACTOR) and prime to r: h_eff P = h_eff P_r, and c = h_eff^-1 mod r gives c h_eff P = P_r.  So the two conditions say
+        P_r != O and P_r = P, which is P != O and r P = O."""
+        live = [i for i, pt in enumerate(points) if not pt.is_identity() and pt.is_on_curve()]
+        out = [False] * len(points)
+        if live:
+            ok = runtime.context().blsg2_check_points(cls._pack([points[i] for i in live]), subgroup=True)
+            for i, flag in zip(live, ok):
+                out[i] = bool(flag)
+        return out
 
     def clear_cofactor(self):
         return self * self._H

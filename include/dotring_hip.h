@@ -377,6 +377,14 @@ DR_API int dr_blsg1_field_selftest(dr_ctx *ctx, const int32_t *a_limbs /* n*14 *
  *   dr_blsg2_encode_to_curve_batch  encode_to_curve(salt_i || msg_i) (salts nullable): hash_to_field on the worker threads, then the map.
  *   dr_blsg2_scalar_mul_batch       out[i] = k[i] P[i]: a bit-by-bit walk from the top set bit of each wave's largest scalar.  Scalars
  *                                   are treated as PUBLIC (the walk's length and its skipped additions depend on them).
+ *   dr_blsg2_msm_groups             out[g] = sum_{j<m} k[g m + j] P[g m + j], m <= 64, 96-byte scalars: one lane per term on the same walk,
+ *                                   the lanes of a group folded by the complete addition.  m = 0 and m > 64 are refused; groups = 0
+ *                                   returns at once.
+ *   dr_blsg2_msm                    ONE sum of n terms k_i P_i with 32-byte scalars used AS THEY ARE (0 <= k < 2^256; wider scalars are
+ *                                   split by the caller); `curve` is either id.  Below 257 terms it launches dr_blsg2_msm_groups'
+ *                                   kernel (over 32-byte scalars) in chunks of up to 64 and folds them on the host; from there on the
+ *                                   bucket method (csrc/wave_msm.hip.h over csrc/kernels_g2_msm.hip.h).  Neither is a fixed schedule:
+ *                                   scalars on this curve are public.  n = 0 gives the identity.
  *   dr_blsg2_check_points           ok[i] = 1 iff point i satisfies the curve equation (the identity does); subgroup = 1 also demands
  *                                   r P = O.
  *   dr_blsg2_field_selftest         diagnostic of csrc/fq2_28.hip.h on RAW limb images (2 x 14 signed 32-bit limbs an element, c0 then c1,
@@ -392,6 +400,9 @@ DR_API int dr_blsg2_encode_to_curve_batch(dr_ctx *ctx, int variant, const uint8_
                                           const uint64_t *salt_off, size_t count, uint8_t *out_xy /* count*192 */);
 DR_API int dr_blsg2_scalar_mul_batch(dr_ctx *ctx, const uint8_t *pts_xy /* n*192 */, const uint8_t *scalars /* n*96 */, size_t n,
                                      uint8_t *out_xy /* n*192 */);
+DR_API int dr_blsg2_msm_groups(dr_ctx *ctx, const uint8_t *pts_xy /* groups*m*192 */, const uint8_t *scalars /* groups*m*96 */, size_t groups,
+                               size_t m, uint8_t *out_xy /* groups*192 */);
+DR_API int dr_blsg2_msm(dr_ctx *ctx, int curve, const uint8_t *pts_xy /* n*192 */, const uint8_t *scalars /* n*32 */, size_t n, uint8_t *out_xy /* 192 */);
 DR_API int dr_blsg2_check_points(dr_ctx *ctx, int subgroup, const uint8_t *pts_xy /* n*192 */, size_t n, uint8_t *ok /* n */);
 DR_API int dr_blsg2_field_selftest(dr_ctx *ctx, const int32_t *a_limbs /* n*28 */, const int32_t *b_limbs /* n*28 */, size_t n,
                                    uint8_t *out /* n*480 */, uint8_t *flags /* n */);
@@ -592,6 +603,15 @@ DR_API int dr_p521_law_selftest(dr_ctx *ctx, const int32_t *points /* n*2*3*19 *
                                 int32_t *out /* n*13*3*19 */);
 DR_API int dr_p384_law_selftest(dr_ctx *ctx, const int32_t *points /* n*2*3*14 */, const uint32_t *controls, size_t n,
                                 int32_t *out /* n*13*3*14 */);
+/* The same for BLS12-381's E(Fq2) (csrc/kernels_g2_msm.hip.h, a kernel of its own: the LDS table of the fixed schedule does not fit this
+ * curve): a coordinate is 28 limbs, c0's 14 then c1's, a point x, y, z.  The ABI shape and the slot numbers are the ones above, with the
+ * steps of the walks this curve has:
+ *   5 slot 0 through a record of the bucket method in device memory (wave_msm_put, wave_msm_get) and back
+ *   7 + w, w < 6: the accumulator after step w of the bit walk started at P: ONE doubling, then that record, loaded again, added, negated
+ *   if bit w of the control word is set, the identity if bit 8 + w is.
+ * Slot 3 is not written. */
+DR_API int dr_blsg2_law_selftest(dr_ctx *ctx, const int32_t *points /* n*2*3*28 */, const uint32_t *controls, size_t n,
+                                 int32_t *out /* n*13*3*28 */);
 
 /* square root in the Bandersnatch base field; DR_ERR_NOTSQUARE if none exists. Host-side, no ctx. */
 DR_API int dr_fr_sqrt(const uint8_t in[32], uint8_t out[32]);
