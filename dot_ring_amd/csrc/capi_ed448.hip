@@ -31,12 +31,7 @@ struct Ed448Suite : SuiteDefaults {
     // the bucket method of dr_wide_msm (capi_wide_msm.hpp): the law on the host, the bits the tiling covers, the stages' kernels
     using Law = dr::E448Law;
     static constexpr int wide_bits = 449;
-    static constexpr auto wide_prepare = dr::k_ed448_msm_prepare;
-    static constexpr auto wide_sort = dr::k_ed448_msm_sort;
-    static constexpr auto wide_accumulate = dr::k_ed448_msm_accumulate;
-    static constexpr auto wide_accumulate_heavy = dr::k_ed448_msm_accumulate_heavy;
-    static constexpr auto wide_reduce = dr::k_ed448_msm_reduce;
-    static constexpr auto wide_fold = dr::k_ed448_msm_fold;
+    DR_WAVE_MSM_STAGES_RECORDS(ed448);
     static constexpr size_t enc_bytes = pt_bytes, rec_bytes = pt_bytes;   // the decoder takes x || y as given: its kernel judges the range
     static constexpr bool decode_gives_points = true, decode_checks_canonical = false;
     // (a field element in {0, 1, p - 1}: kernels_ed448.hip.h, e448_ell2_map)

@@ -29,12 +29,7 @@ struct P384Suite : SuiteDefaults {
     // the bucket method of dr_wide_msm (capi_wide_msm.hpp): the law on the host, the bits the tiling covers, the stages' kernels
     using Law = dr::P384Law;
     static constexpr int wide_bits = 385;
-    static constexpr auto wide_prepare = dr::k_p384_msm_prepare;
-    static constexpr auto wide_sort = dr::k_p384_msm_sort;
-    static constexpr auto wide_accumulate = dr::k_p384_msm_accumulate;
-    static constexpr auto wide_accumulate_heavy = dr::k_p384_msm_accumulate_heavy;
-    static constexpr auto wide_reduce = dr::k_p384_msm_reduce;
-    static constexpr auto wide_fold = dr::k_p384_msm_fold;
+    DR_WAVE_MSM_STAGES_RECORDS(p384);
     // SEC1 compressed: 49 bytes, three zero bytes behind each on the device; the kernel judges the range of x, which is big-endian
     static constexpr size_t enc_bytes = 49, rec_bytes = 52;
     static constexpr bool decode_gives_points = true, decode_checks_canonical = false;

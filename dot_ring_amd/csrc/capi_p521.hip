@@ -29,12 +29,7 @@ struct P521Suite : SuiteDefaults {
     // the bucket method of dr_wide_msm (capi_wide_msm.hpp): the law on the host, the bits the tiling covers, the stages' kernels
     using Law = dr::P521Law;
     static constexpr int wide_bits = 522;
-    static constexpr auto wide_prepare = dr::k_p521_msm_prepare;
-    static constexpr auto wide_sort = dr::k_p521_msm_sort;
-    static constexpr auto wide_accumulate = dr::k_p521_msm_accumulate;
-    static constexpr auto wide_accumulate_heavy = dr::k_p521_msm_accumulate_heavy;
-    static constexpr auto wide_reduce = dr::k_p521_msm_reduce;
-    static constexpr auto wide_fold = dr::k_p521_msm_fold;
+    DR_WAVE_MSM_STAGES_RECORDS(p521);
     // SEC1 compressed: 67 bytes, a zero byte behind each on the device; the kernel judges the range of x, which is big-endian
     static constexpr size_t enc_bytes = 67, rec_bytes = 68;
     static constexpr bool decode_gives_points = true, decode_checks_canonical = false;

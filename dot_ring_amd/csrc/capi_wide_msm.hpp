@@ -19,15 +19,22 @@
 #include "wave_msm.hip.h"
 #include "wide_combine.hpp"
 
-// the members of a suite whose stages are wave_msm.hip.h's DR_WAVE_MSM_KERNELS(NAME, ...): affine set sums, each launch under its kernel's name
-#define DR_WAVE_MSM_STAGES(NAME)                                                                                                       \
-    static constexpr bool wide_affine = true;                                                                                          \
+// The stage members of a suite whose six kernels are one expansion of wave_msm.hip.h's macros under NAME.
+//   DR_WAVE_MSM_STAGES_RECORDS  after DR_WAVE_MSM_KERNELS_RECORDS (p384, p521, ed448): the six kernels; record set sums and the profile
+//                               names k_wide_msm_* with the fold unnamed stay SuiteDefaults'
+//   DR_WAVE_MSM_STAGES          after DR_WAVE_MSM_KERNELS (ed, bjj, p256, secp256k1, blsg1, blsg2): the same six, affine set sums, and
+//                               each launch under its kernel's name
+// (Curve448Suite and Curve25519Suite mix a prepare of their own with another suite's stages and list their members.)
+#define DR_WAVE_MSM_STAGES_RECORDS(NAME)                                                                                               \
     static constexpr auto wide_prepare = dr::k_##NAME##_msm_prepare;                                                                   \
     static constexpr auto wide_sort = dr::k_##NAME##_msm_sort;                                                                         \
     static constexpr auto wide_accumulate = dr::k_##NAME##_msm_accumulate;                                                             \
     static constexpr auto wide_accumulate_heavy = dr::k_##NAME##_msm_accumulate_heavy;                                                 \
     static constexpr auto wide_reduce = dr::k_##NAME##_msm_reduce;                                                                     \
-    static constexpr auto wide_fold = dr::k_##NAME##_msm_fold;                                                                         \
+    static constexpr auto wide_fold = dr::k_##NAME##_msm_fold
+#define DR_WAVE_MSM_STAGES(NAME)                                                                                                       \
+    DR_WAVE_MSM_STAGES_RECORDS(NAME);                                                                                                  \
+    static constexpr bool wide_affine = true;                                                                                          \
     static constexpr const char* wide_names[5] = {"k_" #NAME "_msm_prepare", "k_" #NAME "_msm_sort", "k_" #NAME "_msm_accumulate",      \
                                                   "k_" #NAME "_msm_reduce", "k_" #NAME "_msm_fold"}
 

@@ -60,32 +60,9 @@ __global__ __launch_bounds__(E448_BLOCK) void k_ed448_msm_groups(const uint32_t*
 
 
 // ---------------------------------------------------------------- the bucket method (dr_wide_msm): wave_msm.hip.h over Ed448Curve
-// One MSM of n >= WIDE_PIP_FROM terms; the stages, their operands and the plan are that header's.  W448 scalar words, as they are.
-__global__ __launch_bounds__(WMSM_BLOCK) void k_ed448_msm_prepare(const uint32_t* __restrict__ pts, uint32_t n, uint32_t* __restrict__ table) {
-    wave_msm_prepare<Ed448Curve>(pts, n, table);
-}
-__global__ __launch_bounds__(WMSM_SORT_BLOCK) void k_ed448_msm_sort(const uint32_t* __restrict__ scalars, WideTiling wt, uint32_t n, uint32_t H,
-                                                                   uint32_t groups, uint32_t capacity, uint32_t* __restrict__ counts,
-                                                                   uint32_t* __restrict__ offsets, uint32_t* __restrict__ sorted) {
-    wave_msm_sort<W448>(scalars, wt, n, H, groups, capacity, counts, offsets, sorted);
-}
-__global__ __launch_bounds__(WMSM_BLOCK) void k_ed448_msm_accumulate(const uint32_t* __restrict__ table, const uint32_t* __restrict__ sorted,
-                                                                    const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts,
-                                                                    const uint32_t* __restrict__ perm, uint32_t* __restrict__ buckets, size_t nbuckets) {
-    wave_msm_accumulate<Ed448Curve>(table, sorted, offsets, counts, perm, buckets, nbuckets);
-}
-__global__ __launch_bounds__(64) void k_ed448_msm_accumulate_heavy(const uint32_t* __restrict__ table, const uint32_t* __restrict__ sorted,
-                                                                  const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts,
-                                                                  uint32_t* __restrict__ buckets, size_t nbuckets) {
-    wave_msm_accumulate_heavy<Ed448Curve>(table, sorted, offsets, counts, buckets, nbuckets);
-}
-__global__ __launch_bounds__(WMSM_BLOCK) void k_ed448_msm_reduce(const uint32_t* __restrict__ buckets, size_t sets, uint32_t H, uint32_t L,
-                                                                uint32_t* __restrict__ partial) {
-    wave_msm_reduce<Ed448Curve>(buckets, sets, H, L, partial);
-}
-__global__ __launch_bounds__(WMSM_BLOCK) void k_ed448_msm_fold(const uint32_t* __restrict__ partial, size_t sets, uint32_t T, uint32_t* __restrict__ setsum) {
-    wave_msm_fold<Ed448Curve>(partial, sets, T, setsum);
-}
+// One MSM of n >= WIDE_PIP_FROM terms; the stages, their operands and the plan are that header's.  W448 scalar words, as they are; the
+// set sums leave as records of limb images (k_ed448_msm_prepare, _sort, _accumulate, _accumulate_heavy, _reduce, _fold).
+DR_WAVE_MSM_KERNELS_RECORDS(ed448, Ed448Curve)
 
 // ---------------------------------------------------------------- hashing to the curve (RFC 9380, edwards448_XOF:SHAKE256_ELL2_RO_ / _NU_)
 // Elligator 2 onto curve448 (v^2 = u^3 + A u^2 + u, A = 156326, Z = -1) as the reference's TECurve.map_to_curve_ell2 computes it, in the

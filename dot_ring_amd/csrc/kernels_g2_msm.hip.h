@@ -1,7 +1,7 @@
 // Sums of scalar multiples on BLS12-381's E(Fq2) (dr_blsg2_msm, dr_blsg2_msm_groups) and the diagnostic of its law on raw limb images
 // (dr_blsg2_law_selftest), over kernels_g2_h2c.hip.h's complete law — none of that header's kernels or device functions changes.
 //
-// G2hCurve is a description of the curve AS FAR AS wave_msm.hip.h ASKS FOR ONE (Fe, Point, WORDS, LDS_WORDS, EXTENDED, ZERO_IS_IDENTITY,
+// G2hCurve is a description of the curve AS FAR AS wave_msm.hip.h ASKS FOR ONE (Fe, Point, WORDS, SCALAR_WORDS, LDS_WORDS, EXTENDED, ZERO_IS_IDENTITY,
 // unpack / pack / inv, to_lds / from_lds, identity / from_affine / add / dbl / cneg), so that DR_WAVE_MSM_KERNELS expands over it with
 // wave_curve.hip.h and wave_msm.hip.h as they are.  Those templates read a coordinate as ONE array of limbs (wave_shfl_down) and multiply
 // coordinates by an unqualified mul (wave_store_affine); an Fq2 is two arrays.  So the description's Fe is the 28 limbs of c0 then c1 and
@@ -49,6 +49,7 @@ struct G2hCurve {
     using Fe = G2hFe;
     using Point = G2hWavePoint;
     static constexpr int WORDS = 24, BLOCK = G2H_BLOCK, LDS_WORDS = 2 * L28;
+    static constexpr int SCALAR_WORDS = 8;        // (for the stages' sort alone: there is no schedule over them, the head of the file)
     static constexpr bool EXTENDED = false, ZERO_IS_IDENTITY = true;
     DR_DEV static G2hFe unpack(const uint32_t (&w)[24]) {
         uint32_t w0[12], w1[12];

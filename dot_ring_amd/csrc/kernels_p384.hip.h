@@ -23,24 +23,18 @@ constexpr int P384_BLOCK = 64;        // one wave per workgroup
 constexpr int P384_PT_WORDS = 2 * W384;
 
 // wave_curve.hip.h's description of P-384: canonical words at the ABI (12 per coordinate; 96 zero bytes: the identity, which has Z = 0
-// and so stores them by 0^-1 = 0), the limb images (Montgomery form) in the LDS table, and 97 windows over the scalar AS IT IS
-struct P384Curve : Limb28Curve<Fp384Consts> {
-    using Point = P384Point;
+// and so stores them by 0^-1 = 0), the limb images (Montgomery form) in the LDS table, and 97 windows over the scalar AS IT IS.  The
+// law members are sw3_law.hip.h's Sw3Curve.
+struct P384Curve : Sw3Curve<P384Sw3> {
     static constexpr int SCALAR_WORDS = W384, BLOCK = P384_BLOCK, WINDOWS = P384_WINDOWS;
-    static constexpr bool EXTENDED = false, ZERO_IS_IDENTITY = true;
     DR_DEV static F384 inv(const F384& a) { return dr::inv(a); }     // n; stays here: Limb28Curve supplies no inv
-    DR_DEV static P384Point identity() { return p384_identity(); }
-    DR_DEV static P384Point from_affine(const F384& x, const F384& y) { return p384_from_affine(x, y); }
-    DR_DEV static P384Point add(const P384Point& p, const P384Point& q) { return p384_add(p, q); }
-    DR_DEV static P384Point dbl(const P384Point& p) { return p384_dbl(p); }
-    DR_DEV static P384Point cneg(const P384Point& p, bool negate) { return p384_cneg(p, negate); }
     DR_DEV static void load_scalar(const uint32_t* p, uint32_t (&k)[W384]) { wave_load_words(p, k); }    // no reduction
     // for sec1_decode: a root of x^3 - 3 x + b (n - 3 n + n, carried), the range of x and the parity of the canonical y
     DR_DEV static bool below_p(const uint32_t (&w)[W384]) { return dr::below_p(w); }
     DR_DEV static bool y_of_x(const F384& x, F384& y) {
         const F384 x3 = mul(sqr(x), x);
         const F384 x_3 = dr::add(x, dr::dbl(x));             // (dr::: the description's own add and dbl are the points')
-        return f384_sqrt(carry(dr::add(sub(x3, x_3), p384_b())), y);
+        return f384_sqrt(carry(dr::add(sub(x3, x_3), P384Sw3::b())), y);
     }
     DR_DEV static bool is_odd(const F384& y) { return dr::is_odd(y); }
 };
@@ -58,35 +52,13 @@ __global__ __launch_bounds__(P384_BLOCK) void k_p384_msm_groups(const uint32_t* 
 
 
 // ---------------------------------------------------------------- the bucket method (dr_wide_msm): wave_msm.hip.h over P384Curve
-// One MSM of n >= WIDE_PIP_FROM terms; the stages, their operands and the plan are that header's.  W384 scalar words, as they are.
-__global__ __launch_bounds__(WMSM_BLOCK) void k_p384_msm_prepare(const uint32_t* __restrict__ pts, uint32_t n, uint32_t* __restrict__ table) {
-    wave_msm_prepare<P384Curve>(pts, n, table);
-}
-__global__ __launch_bounds__(WMSM_SORT_BLOCK) void k_p384_msm_sort(const uint32_t* __restrict__ scalars, WideTiling wt, uint32_t n, uint32_t H,
-                                                                   uint32_t groups, uint32_t capacity, uint32_t* __restrict__ counts,
-                                                                   uint32_t* __restrict__ offsets, uint32_t* __restrict__ sorted) {
-    wave_msm_sort<W384>(scalars, wt, n, H, groups, capacity, counts, offsets, sorted);
-}
-__global__ __launch_bounds__(WMSM_BLOCK) void k_p384_msm_accumulate(const uint32_t* __restrict__ table, const uint32_t* __restrict__ sorted,
-                                                                    const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts,
-                                                                    const uint32_t* __restrict__ perm, uint32_t* __restrict__ buckets, size_t nbuckets) {
-    wave_msm_accumulate<P384Curve>(table, sorted, offsets, counts, perm, buckets, nbuckets);
-}
-__global__ __launch_bounds__(64) void k_p384_msm_accumulate_heavy(const uint32_t* __restrict__ table, const uint32_t* __restrict__ sorted,
-                                                                  const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts,
-                                                                  uint32_t* __restrict__ buckets, size_t nbuckets) {
-    wave_msm_accumulate_heavy<P384Curve>(table, sorted, offsets, counts, buckets, nbuckets);
-}
-__global__ __launch_bounds__(WMSM_BLOCK) void k_p384_msm_reduce(const uint32_t* __restrict__ buckets, size_t sets, uint32_t H, uint32_t L,
-                                                                uint32_t* __restrict__ partial) {
-    wave_msm_reduce<P384Curve>(buckets, sets, H, L, partial);
-}
-__global__ __launch_bounds__(WMSM_BLOCK) void k_p384_msm_fold(const uint32_t* __restrict__ partial, size_t sets, uint32_t T, uint32_t* __restrict__ setsum) {
-    wave_msm_fold<P384Curve>(partial, sets, T, setsum);
-}
+// One MSM of n >= WIDE_PIP_FROM terms; the stages, their operands and the plan are that header's.  W384 scalar words, as they are; the
+// set sums leave as records of limb images (k_p384_msm_prepare, _sort, _accumulate, _accumulate_heavy, _reduce, _fold).
+DR_WAVE_MSM_KERNELS_RECORDS(p384, P384Curve)
 
 // ---------------------------------------------------------------- hashing to the curve (RFC 9380, P384_XMD:SHA-384_SSWU_RO_ / _NU_)
-// (the map's description, P384Sswu, is p384_law.hip.h's)
+// (the map's description, P384Sswu, is p384_law.hip.h's.  The body below and k_p521_map_to_curve's are the same text and stay two: as
+// one template over the two descriptions both kernels change)
 // out[i] = the sum of the images of item i's `per_item` field elements (2: the uniform (RO) encoding, 1: the nonuniform one).  us: n x
 // per_item x 12 words (canonical, checked by the host), out: n x 24 words affine x || y (96 zero bytes if the two images cancel),
 // ok[i] = 1 always: the map has no isogeny and no denominator that can vanish (its exceptional branch, u in {0, s, p - s} with

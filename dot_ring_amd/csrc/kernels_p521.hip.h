@@ -21,17 +21,11 @@ constexpr int P521_BLOCK = 64;        // one wave per workgroup
 constexpr int P521_PT_WORDS = 2 * W521;
 
 // wave_curve.hip.h's description of P-521: canonical words at the ABI (17 per coordinate; 136 zero bytes: the identity, which has Z = 0
-// and so stores them by 0^-1 = 0), the limb images in the LDS table, and 131 windows over the scalar AS IT IS (k < 2^521)
-struct P521Curve : Limb28Curve<Fp521Consts> {
-    using Point = P521Point;
+// and so stores them by 0^-1 = 0), the limb images in the LDS table, and 131 windows over the scalar AS IT IS (k < 2^521).  The law
+// members are sw3_law.hip.h's Sw3Curve.
+struct P521Curve : Sw3Curve<P521Sw3> {
     static constexpr int SCALAR_WORDS = W521, BLOCK = P521_BLOCK, WINDOWS = P521_WINDOWS;
-    static constexpr bool EXTENDED = false, ZERO_IS_IDENTITY = true;
     DR_DEV static F521 inv(const F521& a) { return dr::inv(a); }     // 1 n; stays here: Limb28Curve supplies no inv
-    DR_DEV static P521Point identity() { return p521_identity(); }
-    DR_DEV static P521Point from_affine(const F521& x, const F521& y) { return p521_from_affine(x, y); }
-    DR_DEV static P521Point add(const P521Point& p, const P521Point& q) { return p521_add(p, q); }
-    DR_DEV static P521Point dbl(const P521Point& p) { return p521_dbl(p); }
-    DR_DEV static P521Point cneg(const P521Point& p, bool negate) { return p521_cneg(p, negate); }
     DR_DEV static void load_scalar(const uint32_t* p, uint32_t (&k)[W521]) { wave_load_words(p, k); }    // no reduction
 };
 
@@ -48,35 +42,13 @@ __global__ __launch_bounds__(P521_BLOCK) void k_p521_msm_groups(const uint32_t* 
 
 
 // ---------------------------------------------------------------- the bucket method (dr_wide_msm): wave_msm.hip.h over P521Curve
-// One MSM of n >= WIDE_PIP_FROM terms; the stages, their operands and the plan are that header's.  W521 scalar words, as they are.
-__global__ __launch_bounds__(WMSM_BLOCK) void k_p521_msm_prepare(const uint32_t* __restrict__ pts, uint32_t n, uint32_t* __restrict__ table) {
-    wave_msm_prepare<P521Curve>(pts, n, table);
-}
-__global__ __launch_bounds__(WMSM_SORT_BLOCK) void k_p521_msm_sort(const uint32_t* __restrict__ scalars, WideTiling wt, uint32_t n, uint32_t H,
-                                                                   uint32_t groups, uint32_t capacity, uint32_t* __restrict__ counts,
-                                                                   uint32_t* __restrict__ offsets, uint32_t* __restrict__ sorted) {
-    wave_msm_sort<W521>(scalars, wt, n, H, groups, capacity, counts, offsets, sorted);
-}
-__global__ __launch_bounds__(WMSM_BLOCK) void k_p521_msm_accumulate(const uint32_t* __restrict__ table, const uint32_t* __restrict__ sorted,
-                                                                    const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts,
-                                                                    const uint32_t* __restrict__ perm, uint32_t* __restrict__ buckets, size_t nbuckets) {
-    wave_msm_accumulate<P521Curve>(table, sorted, offsets, counts, perm, buckets, nbuckets);
-}
-__global__ __launch_bounds__(64) void k_p521_msm_accumulate_heavy(const uint32_t* __restrict__ table, const uint32_t* __restrict__ sorted,
-                                                                  const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts,
-                                                                  uint32_t* __restrict__ buckets, size_t nbuckets) {
-    wave_msm_accumulate_heavy<P521Curve>(table, sorted, offsets, counts, buckets, nbuckets);
-}
-__global__ __launch_bounds__(WMSM_BLOCK) void k_p521_msm_reduce(const uint32_t* __restrict__ buckets, size_t sets, uint32_t H, uint32_t L,
-                                                                uint32_t* __restrict__ partial) {
-    wave_msm_reduce<P521Curve>(buckets, sets, H, L, partial);
-}
-__global__ __launch_bounds__(WMSM_BLOCK) void k_p521_msm_fold(const uint32_t* __restrict__ partial, size_t sets, uint32_t T, uint32_t* __restrict__ setsum) {
-    wave_msm_fold<P521Curve>(partial, sets, T, setsum);
-}
+// One MSM of n >= WIDE_PIP_FROM terms; the stages, their operands and the plan are that header's.  W521 scalar words, as they are; the
+// set sums leave as records of limb images (k_p521_msm_prepare, _sort, _accumulate, _accumulate_heavy, _reduce, _fold).
+DR_WAVE_MSM_KERNELS_RECORDS(p521, P521Curve)
 
 // ---------------------------------------------------------------- hashing to the curve (RFC 9380, P521_XMD:SHA-512_SSWU_RO_ / _NU_)
-// (the map's description, P521Sswu, is p521_law.hip.h's)
+// (the map's description, P521Sswu, is p521_law.hip.h's.  The body below and k_p384_map_to_curve's are the same text and stay two: as
+// one template over the two descriptions both kernels change)
 // out[i] = the sum of the images of item i's `per_item` field elements (2: the uniform (RO) encoding, 1: the nonuniform one).  us: n x
 // per_item x 17 words (canonical, checked by the host), out: n x 34 words affine x || y (136 zero bytes if the two images cancel),
 // ok[i] = 1 always: the map has no isogeny and no denominator that can vanish (its exceptional branch, u in {0, 2^520, 2^520 - 1},
@@ -135,7 +107,7 @@ __global__ __launch_bounds__(P521_BLOCK) void k_p521_decode_points(const uint32_
     p521_sec1_x_words(w, xb);
     const F521 x = unpack(xb);                                               // 528 bits: 1 n
     const F521 x3 = mul(sqr(x), x);
-    const F521 rhs = carry(add(sub(x3, add(x, dbl(x))), p521_b()));          // x^3 - 3 x + b: n - 3 n + n, carried
+    const F521 rhs = carry(add(sub(x3, add(x, dbl(x))), P521Sw3::b()));          // x^3 - 3 x + b: n - 3 n + n, carried
     F521 y;
     const bool root = f521_sqrt(rhs, y);
     const bool valid = (first == 0x02u || first == 0x03u) && below_p(xb) && root;

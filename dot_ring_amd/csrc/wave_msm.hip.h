@@ -1,9 +1,10 @@
 // The bucket method for ONE variable-base MSM as one set of templates over wave_curve.hip.h's description C of the curve (Point, add,
 // cneg, identity, to_lds / from_lds, LDS_WORDS, EXTENDED) where kernels_te_msm.hip.h is the same method over Bandersnatch's own field:
-//   the wide suites — P-384, P-521, Ed448, Curve448 — from WIDE_PIP_FROM terms (dr_wide_msm); kernels_p384.hip.h, kernels_p521.hip.h,
-//     kernels_ed448.hip.h and kernels_curve448.hip.h give one thin named __global__ per stage;
-//   the 256-bit suites — Ed25519, Baby JubJub, P-256, secp256k1, and Curve25519 on Ed25519's stages — and BLS12-381's E(Fq) from
-//     NARROW_PIP_FROM terms (dr_te_msm, dr_blsg1_msm); their kernel headers expand DR_WAVE_MSM_KERNELS below.
+//   the wide suites — P-384, P-521, Ed448, Curve448 — from WIDE_PIP_FROM terms (dr_wide_msm);
+//   the 256-bit suites — Ed25519, Baby JubJub, P-256, secp256k1, and Curve25519 on Ed25519's stages — and BLS12-381's E(Fq) and E(Fq2)
+//     from NARROW_PIP_FROM / BLSG2_PIP_FROM terms (dr_te_msm, dr_blsg1_msm, dr_blsg2_msm).
+// Their kernel headers expand DR_WAVE_MSM_KERNELS or DR_WAVE_MSM_KERNELS_RECORDS below: one thin named __global__ per stage
+// (kernels_curve448.hip.h writes its own out).
 // The plan is msm_plan.hpp's plan_wide_msm, the digits are wide_recode.hip.h's, the host side is capi_wide_msm.hpp:
 //   prepare      one lane per term: the ABI's point -> a projective RECORD of limb images (x, y, z and, where the description is
 //                EXTENDED, t: 3 or 4 x LDS_WORDS words as to_lds gives them, padded to whole uint4).  Walks read records, so the
@@ -234,16 +235,21 @@ DR_DEV void wave_msm_fold_affine(const uint32_t* __restrict__ partial, size_t se
     wave_store_affine<C>(setsum + set * (2 * C::WORDS), wave_msm_fold_sum<C>(partial, set, T));
 }
 
-// The stages' kernels of a curve with 8-word scalars (NAME: ed, bjj, p256, secp256k1, blsg1) over its description C; each kernel header
-// expands this once.  The fold stores affine points.
-#define DR_WAVE_MSM_KERNELS(NAME, C)                                                                                                           \
+// The stages' kernels k_NAME_msm_prepare, _sort, _accumulate, _accumulate_heavy, _reduce and _fold of a curve over its description C
+// (scalars of C::SCALAR_WORDS words); each kernel header expands one of the two forms below once.
+//   DR_WAVE_MSM_KERNELS          the fold stores affine points (NAME: ed, bjj, p256, secp256k1, blsg1, blsg2)
+//   DR_WAVE_MSM_KERNELS_RECORDS  the fold stores records of limb images (NAME: p384, p521, ed448).  Curve448's stages stay written out in
+//                                kernels_curve448.hip.h: its prepare takes the flag words and its sort is Ed448's.
+#define DR_WAVE_MSM_KERNELS(NAME, C) DR_WAVE_MSM_KERNELS_FOLD(NAME, C, wave_msm_fold_affine)
+#define DR_WAVE_MSM_KERNELS_RECORDS(NAME, C) DR_WAVE_MSM_KERNELS_FOLD(NAME, C, wave_msm_fold)
+#define DR_WAVE_MSM_KERNELS_FOLD(NAME, C, FOLD)                                                                                                \
     __global__ __launch_bounds__(WMSM_BLOCK) void k_##NAME##_msm_prepare(const uint32_t* __restrict__ pts, uint32_t n, uint32_t* __restrict__ table) { \
         wave_msm_prepare<C>(pts, n, table);                                                                                                    \
     }                                                                                                                                          \
     __global__ __launch_bounds__(WMSM_SORT_BLOCK) void k_##NAME##_msm_sort(const uint32_t* __restrict__ scalars, WideTiling wt, uint32_t n, uint32_t H, \
                                                                            uint32_t groups, uint32_t capacity, uint32_t* __restrict__ counts,  \
                                                                            uint32_t* __restrict__ offsets, uint32_t* __restrict__ sorted) {    \
-        wave_msm_sort<8>(scalars, wt, n, H, groups, capacity, counts, offsets, sorted);                                                        \
+        wave_msm_sort<C::SCALAR_WORDS>(scalars, wt, n, H, groups, capacity, counts, offsets, sorted);                                          \
     }                                                                                                                                          \
     __global__ __launch_bounds__(WMSM_BLOCK) void k_##NAME##_msm_accumulate(const uint32_t* __restrict__ table, const uint32_t* __restrict__ sorted, \
                                                                             const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ counts, \
@@ -262,7 +268,7 @@ DR_DEV void wave_msm_fold_affine(const uint32_t* __restrict__ partial, size_t se
     }                                                                                                                                          \
     __global__ __launch_bounds__(WMSM_BLOCK) void k_##NAME##_msm_fold(const uint32_t* __restrict__ partial, size_t sets, uint32_t T,           \
                                                                       uint32_t* __restrict__ setsum) {                                         \
-        wave_msm_fold_affine<C>(partial, sets, T, setsum);                                                                                     \
+        FOLD<C>(partial, sets, T, setsum);                                                                                                     \
     }
 
 }  // namespace dr

@@ -483,7 +483,7 @@ DR_API int dr_curve448_decode_points(dr_ctx *ctx, int check, const uint8_t *enc 
 
 /* DR_CURVE_P521_RO (the reference's P521 = P521_RO) and DR_CURVE_P521_NU (P521_NU): P-521, y^2 = x^3 - 3 x + b over p = 2^521 - 1
  * (dot_ring/curve/specs/p521.py), prime order, cofactor 1, hashing by RFC 9380's P521_XMD:SHA-512_SSWU_RO_ (two field elements) or
- * ..._NU_ (one) — csrc/kernels_p521.hip.h on the complete law of csrc/p521_law.hip.h over csrc/fp521.hip.h.  Entry points of their own
+ * ..._NU_ (one) — csrc/kernels_p521.hip.h on the complete law of csrc/sw3_law.hip.h over csrc/fp521.hip.h.  Entry points of their own
  * (dr_p521_*); every 64-byte entry point refuses these two ids with DR_ERR_INVALID, and so do the dr_blsg1_* / dr_blsg2_* / dr_ed448_* /
  * dr_curve448_* calls as variants.  Formats: field elements and coordinates are 68 bytes little-endian, canonical (< p); points are
  * affine x || y, 136 bytes, and 136 ZERO BYTES ARE THE IDENTITY, in and out ((0, 0) is not on the curve); scalars are 68 bytes
@@ -522,7 +522,7 @@ DR_API int dr_p521_field_selftest(dr_ctx *ctx, const int32_t *a_limbs /* n*19 */
 
 /* DR_CURVE_P384_RO (the reference's P384 = P384_RO) and DR_CURVE_P384_NU (P384_NU): P-384, y^2 = x^3 - 3 x + b over
  * p = 2^384 - 2^128 - 2^96 + 2^32 - 1 (dot_ring/curve/specs/p384.py), prime order, cofactor 1, hashing by RFC 9380's
- * P384_XMD:SHA-384_SSWU_RO_ (two field elements) or ..._NU_ (one) — csrc/kernels_p384.hip.h on the complete law of csrc/p384_law.hip.h
+ * P384_XMD:SHA-384_SSWU_RO_ (two field elements) or ..._NU_ (one) — csrc/kernels_p384.hip.h on the complete law of csrc/sw3_law.hip.h
  * over csrc/fp384.hip.h (Montgomery form inside the kernels only).  Entry points of their own (dr_p384_*); every 64-byte entry point
  * refuses these two ids with DR_ERR_INVALID, and so do the dr_blsg1_* / dr_blsg2_* / dr_ed448_* / dr_curve448_* / dr_p521_* calls as
  * variants; the dr_p384_* calls refuse every other id.  Formats: field elements and coordinates are 48 bytes little-endian, canonical

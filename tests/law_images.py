@@ -196,14 +196,14 @@ def _small_one(limbs):
     return [1] + [0] * (limbs - 1)
 
 
-# ---- P-384 (fp384.hip.h, p384_law.hip.h)
+# ---- P-384 (fp384.hip.h, p384_law.hip.h over sw3_law.hip.h)
 def _p384():
     # fp384.hip.h, "normal": limbs 0..12 in [-2^22, 2^28 + 2^22), limb 13 in (-2^21, 2^21), |value| < 2^385
     n = LimbClass("n", [-(1 << 22)] * 13 + [-(1 << 21) + 1], [(1 << 28) + (1 << 22) - 1] * 13 + [(1 << 21) - 1], 1 << 385)
     # fp384.hip.h, "k n" with k = 1: |limb| <= 2^28 + 2^22 for limbs 0..12, |limb 13| <= 2^21, |value| < 2^385
     m, t = (1 << 28) + (1 << 22), 1 << 21
     n1 = LimbClass("1 n", [-m] * 13 + [-t], [m] * 13 + [t], 1 << 385)
-    # p384_law.hip.h: "A point's coordinates are x: 1 n, y: n (1 n once negated), z: n, in and out"
+    # sw3_law.hip.h: "A point's coordinates are x: 1 n, y: n (1 n once negated), z: n, in and out"
     cls = {"x": [n1], "y": [n], "z": [n]}
     # F384::small(1) = R mod p in signed limbs (fp384.hip.h): 2^8 - 2^12 B + 2^20 B^3 + 2^24 B^4
     one = [0] * 14
@@ -211,14 +211,14 @@ def _p384():
     return Curve("P-384", "p384", 14, 28, 1 << 392, p384.P, p384, "sw", p384.N, cls, cls, {"x": n1, "y": n, "z": n}, one, _x0_points(p384))
 
 
-# ---- P-521 (fp521.hip.h, p521_law.hip.h)
+# ---- P-521 (fp521.hip.h, p521_law.hip.h over sw3_law.hip.h)
 def _p521():
     # fp521.hip.h, "normal": limbs 0..17 in (-2^15, 2^28 + 2^15), limb 18 in [0, 2^17); the value has no bound of its own
     n = LimbClass("n", [-(1 << 15) + 1] * 18 + [0], [(1 << 28) + (1 << 15) - 1] * 18 + [(1 << 17) - 1])
     # fp521.hip.h, "k n" with k = 1: |limb| <= 2^28 + 2^15, EVERY limb
     m = (1 << 28) + (1 << 15)
     n1 = LimbClass("1 n", [-m] * 19, [m] * 19)
-    # p521_law.hip.h: "A point's coordinates are x: 1 n, y: n (1 n once negated), z: n, in and out"
+    # sw3_law.hip.h: "A point's coordinates are x: 1 n, y: n (1 n once negated), z: n, in and out"
     cls = {"x": [n1], "y": [n], "z": [n]}
     return Curve("P-521", "p521", 19, 28, 1, p521.P, p521, "sw", p521.N, cls, cls, {"x": n1, "y": n, "z": n}, _small_one(19), _x0_points(p521))
 
