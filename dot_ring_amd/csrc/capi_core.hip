@@ -1289,7 +1289,7 @@ int dr_host_random_expand(const uint8_t seed[32], uint8_t* out, size_t len) {
 int dr_ringvrf_aux_take_blindings(uint8_t* aux, size_t batch, uint8_t* out_blind) {
     if (batch && (!aux || !out_blind)) return fail(DR_ERR_INVALID, "null buffer");
     for (size_t i = 0; i < batch; i++) {
-        uint8_t* b = aux + (size_t)DR_RINGVRF_AUX_BYTES * i + 256;
+        uint8_t* b = aux + drh::ringfmt::AUX_BYTES * i + drh::ringfmt::AUX_BLIND;
         std::memcpy(out_blind + 32 * i, b, 32);
         explicit_bzero(b, 32);
     }
@@ -1407,8 +1407,7 @@ int dr_hash_to_field_batch(const dr_vrf_suite* suite, const uint8_t* msgs, const
     if (su.cv->native == drh::NativeSuite::p256 && !su.cv->sswu)
         return fail(DR_ERR_INVALID, "the P-256 suite hashes to the curve by try-and-increment: no hash_to_field");
     if (count && (!off || !out_u_pairs || (off[count] && !msgs))) return fail(DR_ERR_INVALID, "null buffer");
-    for (size_t i = 0; i < count; i++)
-        if (off[i + 1] < off[i]) return fail(DR_ERR_INVALID, "offsets must be non-decreasing");
+    TRY(offsets_ok(count, {off}));
     if (su.cv->sswu || su.cv->ell2_native) {   // two elements per message for the uniform (RO) variant (64 bytes), one for the nonuniform one (32)
         const unsigned per = su.cv->nu ? 1 : 2;
         drh::parallel_for(count, [&](size_t i) { drh::hash_to_field_rfc9380(su, msgs + off[i], off[i + 1] - off[i], per, out_u_pairs + 32 * per * i); });
@@ -1420,24 +1419,19 @@ int dr_hash_to_field_batch(const dr_vrf_suite* suite, const uint8_t* msgs, const
 
 int dr_encode_to_curve_batch(dr_ctx* ctx, const dr_vrf_suite* suite, const uint8_t* msgs, const uint64_t* off, const uint8_t* salts,
                              const uint64_t* salt_off, size_t count, uint8_t* out_xy) {
-    try {
+    return abi_guard("encode_to_curve", [&]() -> int {
         TRY(use_ctx(ctx));
         drh::VrfSuite su;
         TRY(load_suite(suite, su, true));
         if (count && (!off || !out_xy || (off[count] && !msgs))) return fail(DR_ERR_INVALID, "null buffer");
-        for (size_t i = 0; i < count; i++)
-            if (off[i + 1] < off[i] || (salt_off && salt_off[i + 1] < salt_off[i])) return fail(DR_ERR_INVALID, "offsets must be non-decreasing");
+        TRY(offsets_ok(count, {off, salt_off}));
         if (su.cv->sw) {              // the candidates decode to TE images (4P), which go back to SW in one launch
             std::vector<uint8_t> te(count * 64);
             TRY(encode_to_curve_msgs(ctx, su, count, msgs, off, salts, salt_off, te.data()));
             return sw_map_points(ctx, false, te.data(), count, out_xy, 1);
         }
         return encode_to_curve_msgs(ctx, su, count, msgs, off, salts, salt_off, out_xy);
-    } catch (const std::bad_alloc&) {
-        return fail(DR_ERR_NOMEM, "out of host memory");
-    } catch (const std::exception& e) {
-        return fail(DR_ERR_DEVICE, std::string("encode_to_curve: ") + e.what());
-    }
+    });
 }
 
 // I_i = encode_to_curve(salt_i || alpha_i) and O_i = x_i * I_i for an Elligator suite without a host round trip in between:

@@ -2,7 +2,8 @@
 //   capi_core.hip   contexts, device memory, profiling, seam A (Bandersnatch kernels), hash-to-curve
 //   capi_msm.hip    G1 Pippenger pipeline, seam B (SRS, MSM, G1 codecs), pairing entry points
 //   capi_ring.hip   seam C (NTT) and the batched ring prover's phases
-//   capi_batch.hip  native batch orchestration: Pedersen / IETF / Ring-VRF prove and verify
+//   capi_batch.hip  native batch orchestration: Pedersen / IETF / Ring-VRF prove and verify (proof layout and the ring proof's
+//                   Fiat-Shamir schedule: hostring.hpp; VRF transcripts: hostsigma.hpp)
 //   capi_comm.hip   RCCL communicator for the base-sharded MSM
 //   capi_blsg1.hip  the BLS12_381_G1 suites: 48-byte coordinates, hashing to G1 and the group of E(Fq)
 //   capi_blsg2.hip  the BLS12_381_G2 suites: Fq2 coordinates, hashing to G2 and the group of E(Fq2)
@@ -39,6 +40,7 @@
 #include "hostmath.hpp"
 #include "hostpairing.hpp"
 #include "hostproto.hpp"
+#include "hostring.hpp"
 #include "msm_plan.hpp"
 
 namespace dri {
@@ -205,6 +207,26 @@ int launch(dr_ctx* ctx, const char* name, F&& f) {
 
 inline unsigned div_up(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 
+// body of an entry point that allocates on the host or starts threads: C++ exceptions must not cross the C ABI (`who` opens the message)
+template <class F>
+int abi_guard(const char* who, F&& body) {
+    try {
+        return body();
+    } catch (const std::bad_alloc&) {
+        return fail(DR_ERR_NOMEM, "out of host memory");
+    } catch (const std::exception& e) {
+        return fail(DR_ERR_DEVICE, std::string(who) + ": " + e.what());
+    }
+}
+
+// the (n + 1)-entry offset arrays of n ragged items (a null array: that blob is absent) must not run backwards
+inline int offsets_ok(size_t n, std::initializer_list<const uint64_t*> offs) {
+    for (const uint64_t* off : offs)
+        for (size_t i = 0; off && i < n; i++)
+            if (off[i + 1] < off[i]) return fail(DR_ERR_INVALID, "offsets must be non-decreasing");
+    return DR_OK;
+}
+
 // One host round trip of a single-launch entry point, the only place that spells the sequence out: reserve io_a / io_b / io_c (`need`; 0:
 // not used), the uploads in order, the launch, the downloads in order (one without a destination is skipped), and with `sync` the wait
 // for the stream and the kernel timers.  Without `sync` the caller waits later (the prover's fixed-base commitments).  `go` is one kernel
@@ -315,6 +337,17 @@ void run_guarded(int& rc, std::string& err, F&& f) {
         err = e.what();
     }
 }
+
+// joins a helper thread when the scope (or the object it is a member of) ends, after `before` (what lets the thread go, if anything holds
+// it): declared behind everything the thread touches, so that it is joined before any of that goes away
+struct ThreadJoiner {
+    std::thread& t;
+    std::function<void()> before;
+    ~ThreadJoiner() {
+        if (before) before();
+        if (t.joinable()) t.join();
+    }
+};
 
 // ---- helpers shared between translation units (global scope, hidden visibility)
 bool ctx_alive(dr_ctx* c);

@@ -299,7 +299,7 @@ using Shake256 = Shake<136>;
 // four sponges in lockstep: every update gives each of them the same number of bytes
 template <int RATE>
 struct Shake4 {
-    u64x4 st[25];
+    alignas(32) u64x4 st[25];    // (32 on its own under hipcc; g++ without -mavx gives the vector type 16, and the AVX2 permutation loads aligned)
     uint8_t buf[4][RATE];    // the current block of each stream, XORed into the state when it is full
     size_t pos = 0;
 
@@ -327,7 +327,7 @@ struct Shake4 {
     }
     // digests of everything absorbed so far (n <= RATE bytes each); the absorbing state is left untouched
     void digest(uint8_t* const out[4], size_t n) const {
-        u64x4 s[25];
+        alignas(32) u64x4 s[25];
         std::memcpy(s, st, sizeof s);
         uint8_t b[4][RATE];                                    // the partial blocks, padded
         for (int k = 0; k < 4; k++) {

@@ -973,6 +973,37 @@ inline bool ring_verifier_terms(const TeCurveHost& cv, const RingVerifierDomain&
     return true;
 }
 
+// verifier randomness of the batched KZG check (kzg.py:84-108): coefficient k (0, 1) of proof i = SHAKE256(seed || LE64(2 i + k)), 48
+// bytes big-endian mod p, a zero replaced by 1
+inline void ring_verifier_randomness(const uint8_t seed32[32], uint64_t i, int k, uint64_t r[4]) {
+    const Mod256& f = mod_p();
+    Shake256 sh;
+    sh.update(seed32, 32);
+    uint8_t ctr[8];
+    for (int j = 0; j < 8; j++) ctr[j] = (uint8_t)((2 * i + (uint64_t)k) >> (8 * j));
+    sh.update(ctr, 8);
+    uint8_t raw[48];
+    sh.digest(raw, 48);
+    f.reduce_bytes(raw, 48, true, r);
+    if (f.is_zero(r)) f.set_u64(1, r);
+}
+// one proof's share of the folded pairing equation's lhs under its randomness (r1, r2): the scalars of its seven G1 points in the
+// verifier's gather order (C_b, C_accip, C_accx, C_accy, C_q, Phi_zeta, Phi_zeta_omega; 7 x 32 bytes little-endian) and its four
+// summands on the fixed points: r1 nu0, r1 nu1, r1 nu2 (C_px, C_py, C_s) and r1 agg + r2 l_zw (G1[0], subtracted by the caller)
+inline void ring_claim_fold(const RingClaimScalars& cl, const uint64_t r1[4], const uint64_t r2[4], uint8_t lhs[7 * 32], uint64_t fixed[16]) {
+    const Mod256& f = mod_p();
+    uint64_t v[4], w[4];
+    f.mul(r1, cl.nus[3], v); store_le32(v, lhs);                                                        // C_b
+    f.mul(r1, cl.nus[4], v); f.mul(r2, cl.k_ip, w); f.add(v, w, v); store_le32(v, lhs + 32);             // C_accip
+    f.mul(r1, cl.nus[5], v); f.mul(r2, cl.k_x, w); f.add(v, w, v); store_le32(v, lhs + 64);              // C_accx
+    f.mul(r1, cl.nus[6], v); f.mul(r2, cl.k_y, w); f.add(v, w, v); store_le32(v, lhs + 96);              // C_accy
+    f.mul(r1, cl.nus[7], v); store_le32(v, lhs + 128);                                                   // C_q
+    f.mul(r1, cl.zeta, v); store_le32(v, lhs + 160);                                                     // Phi_zeta
+    f.mul(r2, cl.zeta_omega, v); store_le32(v, lhs + 192);                                               // Phi_zeta_omega
+    for (int k = 0; k < 3; k++) f.mul(r1, cl.nus[k], fixed + 4 * k);
+    f.mul(r1, cl.agg_zeta, v); f.mul(r2, cl.l_zw, w); f.add(v, w, fixed + 12);
+}
+
 // 96-byte BE x||y record (or infinity) -> serialize() form: infinity = 0x40 || zeros  (kzg.py:133)
 inline void g1_serialized(const uint8_t rec[96], int is_inf, uint8_t out[96]) {
     if (is_inf) { std::memset(out, 0, 96); out[0] = 0x40; } else std::memcpy(out, rec, 96);

@@ -38,16 +38,17 @@ inline bool sigma_encode_to_curve(const VrfSuite& su, Span salt, Span msg, uint8
     return te_encode_to_curve_host(u, out_xy);
 }
 
-// transcript of the IETF schemes over the pairs (G, pk), (I, O), then the delinearisation scalar z (primitives.py:26-55,92-122)
-inline void ietf_transcript(const VrfSuite& su, bool thin, const uint8_t enc_g[32], const uint8_t enc_pk[32], const uint8_t enc_i[32],
-                            const uint8_t enc_o[32], Span ad, Bytes& t, uint64_t z[4]) {
+// transcript of the IETF schemes over the pairs (G, pk), (I, O), then the delinearisation scalar z (primitives.py:26-55,92-122);
+// pl: the suite's point length (32 here on the host route, 32 or 33 from the batch path)
+inline void ietf_transcript(const VrfSuite& su, bool thin, size_t pl, const uint8_t* enc_g, const uint8_t* enc_pk, const uint8_t* enc_i,
+                            const uint8_t* enc_o, Span ad, Bytes& t, uint64_t z[4]) {
     t = su.suite_id;
-    put8(t, thin ? 0x01 : 0x00);
+    put8(t, thin ? 0x01 : 0x00);                           // THIN_VRF / TINY_VRF
     put_le64(t, 2);
-    put(t, enc_g, 32);
-    put(t, enc_pk, 32);
-    put(t, enc_i, 32);
-    put(t, enc_o, 32);
+    put(t, enc_g, pl);
+    put(t, enc_pk, pl);
+    put(t, enc_i, pl);
+    put(t, enc_o, pl);
     put_le64(t, ad.n);
     if (ad.n) put(t, ad.p, ad.n);
     Bytes d = t;
@@ -76,7 +77,7 @@ inline int ietf_prove_one(const VrfSuite& su, const TeSuiteTables& tb, bool thin
     enc_te_point(in_xy, enc_i);
     enc_te_point(o_xy, enc_o);
     Bytes t;
-    ietf_transcript(su, thin, enc_g, enc_pk, enc_i, enc_o, ad, t, z);
+    ietf_transcript(su, thin, 32, enc_g, enc_pk, enc_i, enc_o, ad, t, z);
     int rc = 0;
     if (!vrf_nonce(su, t, x, k)) rc = 2;
     if (rc == 0) {
@@ -149,7 +150,7 @@ inline int ietf_verify_one(const VrfSuite& su, const TeSuiteTables& tb, bool thi
     enc_te_point(su.generator, enc_g);
     enc_te_point(in_xy, enc_i);
     Bytes t;
-    ietf_transcript(su, thin, enc_g, pk_enc, enc_i, proof, ad, t, z);      // (a validated encoding is the canonical one: enc(dec(e)) == e)
+    ietf_transcript(su, thin, 32, enc_g, pk_enc, enc_i, proof, ad, t, z);      // (a validated encoding is the canonical one: enc(dec(e)) == e)
     if (thin) vrf_challenge(su, t, proof + 32, 1, c);
     TeExt pts[3];
     uint64_t ks[3][4];
@@ -171,13 +172,13 @@ inline int ietf_verify_one(const VrfSuite& su, const TeSuiteTables& tb, bool thi
     return Mod256::eq(c, c2) ? SIGMA_OK : SIGMA_REJECT;
 }
 
-// transcript of the Pedersen scheme after the (I, O) pair (pedersen/vrf.py:86-104)
-inline void pedersen_transcript(const VrfSuite& su, const uint8_t enc_i[32], const uint8_t enc_o[32], Span ad, Bytes& t) {
+// transcript of the Pedersen scheme after the (I, O) pair (pedersen/vrf.py:86-104); pl: the suite's point length, as above
+inline void pedersen_transcript(const VrfSuite& su, size_t pl, const uint8_t* enc_i, const uint8_t* enc_o, Span ad, Bytes& t) {
     t = su.suite_id;
     put8(t, 0x02);                                         // PEDERSEN_VRF
-    put_le64(t, 1);
-    put(t, enc_i, 32);
-    put(t, enc_o, 32);
+    put_le64(t, 1);                                        // one (input, output) pair
+    put(t, enc_i, pl);
+    put(t, enc_o, pl);
     put_le64(t, ad.n);
     if (ad.n) put(t, ad.p, ad.n);
 }
@@ -198,7 +199,7 @@ inline int pedersen_prove_one(const VrfSuite& su, const TeSuiteTables& tb, Span 
     enc_te_point(in_xy, enc_i);
     enc_te_point(o_xy, out);
     Bytes t;
-    pedersen_transcript(su, enc_i, out, ad, t);
+    pedersen_transcript(su, 32, enc_i, out, ad, t);
     Bytes tbl = t;
     put8(tbl, 0x12);                                       // PEDERSEN_BLINDING
     int rc = 0;
@@ -255,7 +256,7 @@ inline int pedersen_verify_one(const VrfSuite& su, const TeSuiteTables& tb, cons
     uint8_t enc_i[32];
     enc_te_point(in_xy, enc_i);
     Bytes t;
-    pedersen_transcript(su, enc_i, proof, ad, t);
+    pedersen_transcript(su, 32, enc_i, proof, ad, t);
     put(t, proof + 32, 32);
     vrf_challenge(su, t, proof + 64, 2, c);
     TeExt O, Yb, R, Ok, I;

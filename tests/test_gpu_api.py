@@ -341,6 +341,57 @@ def test_tuning_knobs_do_not_change_the_bytes(ctx):
     assert len(set(digests)) == 1, list(zip(variants, digests))
 
 
+_GROUPS_SCRIPT = r"""
+import dot_ring_amd as d
+cv = d.Bandersnatch
+sks = [(7000 + i).to_bytes(32, "little") for i in range(9)]
+keys = [cv.public_key_from_secret(sk) for sk in sks]
+params = d.RingProofParams.from_ring_size(9, test_vectors=True)
+assert params.domain_size == 512
+ring = d.Ring(keys, params)
+root = d.RingRoot.from_ring(ring, params)
+vrf = d.RingVRF[cv]
+ENCODED = {}
+for n in (5, 9):
+    als, ads = [b"b%d" % i for i in range(n)], [b"ad%d" % (i % 3) for i in range(n)]
+    proofs = vrf.prove_batch(als, ads, sks[:n], keys[:n], ring, root)
+    assert vrf.batch_verify(proofs, als, ads, ring, root), n
+    assert not vrf.batch_verify(proofs, als[:-1] + [b"other"], ads, ring, root), n       # (the LAST proof: the one the spare slots repeat)
+    ENCODED[n] = [p.encode().hex() for p in proofs]
+    print("PROOFS", n, " ".join(ENCODED[n]))
+"""
+
+
+def test_ring_batches_of_5_and_9_equal_the_oracle_on_both_verifier_routes(ctx):
+    """Batches that are no multiple of the transcripts' group of four — five proofs (one full group and a group with three spare
+    slots) and nine (two full groups and a group of one; above the verifier's host cutover of 8) — on the smallest ring (domain 512):
+    every proof equals the oracle's bytes, the batch verifies and a wrong last input is refused.  Here with the default cutover (5:
+    decoding and folds on the host, 9: through the kernels), and in one child process with DOTRING_VERIFY_HOST_MAX=0 (both through
+    the kernels; the knob is read once per process)."""
+    import os
+    import subprocess
+    import sys
+
+    from oracle.pyref import bandersnatch as bsn
+    from oracle.pyref import ring as oring
+
+    sks = [(7000 + i).to_bytes(32, "little") for i in range(9)]
+    o_ring = oring.Ring([bsn.public_key_from_secret(sk) for sk in sks], oring.Params.from_ring_size(9, test_vectors=True))
+    o_root = oring.RingRoot(o_ring)
+    want = [oring.ring_vrf_prove(o_ring, o_root, b"b%d" % i, b"ad%d" % (i % 3), sks[i]).hex() for i in range(9)]
+    here = {}
+    exec(_GROUPS_SCRIPT, here)
+    root_dir = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if not k.startswith("DOTRING_")}
+    env.update({"DOTRING_VERIFY_HOST_MAX": "0", "PYTHONPATH": root_dir + os.pathsep + os.environ.get("PYTHONPATH", "")})
+    out = subprocess.run([sys.executable, "-c", _GROUPS_SCRIPT], cwd=root_dir, env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    child = {int(ln.split()[1]): ln.split()[2:] for ln in out.stdout.splitlines() if ln.startswith("PROOFS")}
+    for n in (5, 9):
+        assert here["ENCODED"][n] == want[:n], n
+        assert child[n] == want[:n], n
+
+
 def test_small_vrf_vectors_through_the_kernels_too(ctx):
     """Calls of up to DOTRING_SMALL_HOST_MAX proofs (default 64) run the Tiny / Thin / Pedersen protocols, and dec_point of a few points,
     on host cores (csrc/hostsigma.hpp) — so the vector tests above exercise that route.  The same vector tests (all Tiny, Thin and
