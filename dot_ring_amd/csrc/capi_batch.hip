@@ -1,4 +1,4 @@
-// libdotring_hip.so — C ABI, part 4 of 10: native batch orchestration.  Pedersen / IETF / Ring-VRF prove_batch and
+// libdotring_hip.so — C ABI, part 4 of 11: native batch orchestration.  Pedersen / IETF / Ring-VRF prove_batch and
 // batch_verify run the whole protocol in the library: GPU phases through the entry points of the other parts, the hashing
 // between them on worker threads (hosthash.hpp, hostproto.hpp).  The VRF transcripts are hostsigma.hpp's, the Ring-VRF proof's
 // layout and the ring proof's Fiat-Shamir schedule hostring.hpp's: prover and verifier share one copy of each.
@@ -289,6 +289,16 @@ int dr_ringvrf_prove_batch(dr_ring_prover* p, const dr_vrf_suite* suite, size_t 
         return ringvrf_prove_batch_impl(p, suite, batch, alphas, alpha_off, ads, ad_off, salts, salt_off, secret_scalars, producer_index, fs_prefix,
                                         fs_prefix_len, zk_random48, out_proofs, out_aux);
     });
+}
+
+int dr_ringvrf_aux_take_blindings(uint8_t* aux, size_t batch, uint8_t* out_blind) {
+    if (batch && (!aux || !out_blind)) return fail(DR_ERR_INVALID, "null buffer");
+    for (size_t i = 0; i < batch; i++) {
+        uint8_t* b = aux + rf::AUX_BYTES * i + rf::AUX_BLIND;
+        std::memcpy(out_blind + 32 * i, b, 32);
+        explicit_bzero(b, 32);
+    }
+    return DR_OK;
 }
 
 // Pedersen VRF batch verification core (pedersen/vrf.py:171-242) on decoded points: challenges, weights from one

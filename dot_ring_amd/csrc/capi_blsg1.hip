@@ -1,4 +1,4 @@
-// libdotring_hip.so — C ABI, part 6 of 10: the BLS12_381_G1 suites (DR_CURVE_BLS12_381_G1 / DR_CURVE_BLS12_381_G1_NU; the reference's
+// libdotring_hip.so — C ABI, part 6 of 11: the BLS12_381_G1 suites (DR_CURVE_BLS12_381_G1 / DR_CURVE_BLS12_381_G1_NU; the reference's
 // specs/bls12_381_G1.py).  The first curve here whose coordinates are 48 bytes: none of it goes through the 64-byte paths of
 // capi_core.hip but through capi_suite.hpp — points are affine x || y, 48 + 48 bytes little-endian, canonical standard form, 96 zero bytes
 // the identity.  The kernels are kernels_g1_h2c_entry.hip.h over kernels_g1_h2c.hip.h (the complete projective law over fq28.hip.h,

@@ -1,4 +1,4 @@
-// libdotring_hip.so — C ABI, part 7 of 10: the BLS12_381_G2 suites (DR_CURVE_BLS12_381_G2 / DR_CURVE_BLS12_381_G2_NU; the reference's
+// libdotring_hip.so — C ABI, part 7 of 11: the BLS12_381_G2 suites (DR_CURVE_BLS12_381_G2 / DR_CURVE_BLS12_381_G2_NU; the reference's
 // specs/bls12_381_G2.py).  Coordinates are elements of Fq2, c0 || c1, 48 + 48 bytes little-endian, canonical standard form; points are
 // affine x || y, 192 bytes, 192 zero bytes the identity.  None of it goes through the 64-byte paths of capi_core.hip but through
 // capi_suite.hpp.  The kernels are kernels_g2_h2c.hip.h (the complete projective law over fq2_28.hip.h); the host does hash_to_field

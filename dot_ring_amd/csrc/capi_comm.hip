@@ -1,4 +1,4 @@
-// libdotring_hip.so — C ABI, part 5 of 10: the RCCL communicator of the base-sharded MSM (second mode).
+// libdotring_hip.so — C ABI, part 5 of 11: the RCCL communicator of the base-sharded MSM (second mode).
 //
 // One process per GPU.  A large MSM shards by bases: rank g reduces its (base, scalar) pairs to ONE G1 point, the points
 // are exchanged with ncclAllGather (96 bytes per rank: latency-bound on xGMI, the per-link bandwidth is irrelevant) and

@@ -1,4 +1,4 @@
-// libdotring_hip.so — C ABI, part 8 of 10: the suites over p = 2^448 - 2^224 - 1.  Ed448 (DR_CURVE_ED448_RO / DR_CURVE_ED448_NU; the
+// libdotring_hip.so — C ABI, part 8 of 11: the suites over p = 2^448 - 2^224 - 1.  Ed448 (DR_CURVE_ED448_RO / DR_CURVE_ED448_NU; the
 // reference's specs/ed448.py) and Curve448 (DR_CURVE_CURVE448_RO / DR_CURVE_CURVE448_NU; specs/curve448.py).
 // Field elements and coordinates are 56 bytes little-endian, canonical; points are affine, 112 bytes: Ed448's x || y with the identity
 // (0, 1) as itself, Curve448's Montgomery u || v with the identity as 112 bytes of 0xff, in and out, at every dr_curve448_* entry point

@@ -1,19 +1,23 @@
 // Internal declarations shared by the translation units of libdotring_hip.so (not part of the C ABI):
-//   capi_core.hip   contexts, device memory, profiling, seam A (Bandersnatch kernels), hash-to-curve
-//   capi_msm.hip    G1 Pippenger pipeline, seam B (SRS, MSM, G1 codecs), pairing entry points
-//   capi_ring.hip   seam C (NTT) and the batched ring prover's phases
-//   capi_batch.hip  native batch orchestration: Pedersen / IETF / Ring-VRF prove and verify (proof layout and the ring proof's
-//                   Fiat-Shamir schedule: hostring.hpp; VRF transcripts: hostsigma.hpp)
-//   capi_comm.hip   RCCL communicator for the base-sharded MSM
-//   capi_blsg1.hip  the BLS12_381_G1 suites: 48-byte coordinates, hashing to G1 and the group of E(Fq)
-//   capi_blsg2.hip  the BLS12_381_G2 suites: Fq2 coordinates, hashing to G2 and the group of E(Fq2)
-//   capi_ed448.hip  the Ed448 suites: 56-byte coordinates and scalars, hashing to the curve and the group of E(F_p)
-// (wave_msm.hip.h defines none either: the wide suites' units instantiate its templates in their own named kernels)
-// The last three are one description of their suite each (widths, limits, kernels, hashing parameters) and their entry points as calls
-// of capi_suite.hpp's templates, the one host path they share with the five 256-bit suites described in capi_core.hip; every host
-// round trip of a single-launch entry point is io_round below.
+//   capi_core.hip       contexts, device memory, profiling and wiping, seam A (Bandersnatch / JubJub / Bandersnatch_SW kernels),
+//                       load_suite, hash-to-curve, host hashing
+//   capi_msm.hip        G1 Pippenger pipeline, seam B (SRS, MSM, G1 codecs), pairing entry points
+//   capi_ring.hip       seam C (NTT) and the batched ring prover's phases
+//   capi_batch.hip      native batch orchestration: Pedersen / IETF / Ring-VRF prove and verify (proof layout and the ring proof's
+//                       Fiat-Shamir schedule: hostring.hpp; VRF transcripts: hostsigma.hpp)
+//   capi_comm.hip       RCCL communicator for the base-sharded MSM
+//   capi_blsg1.hip      the BLS12_381_G1 suites: 48-byte coordinates, hashing to G1 and the group of E(Fq)
+//   capi_blsg2.hip      the BLS12_381_G2 suites: Fq2 coordinates, hashing to G2 and the group of E(Fq2)
+//   capi_ed448.hip      the Ed448 and Curve448 suites: 56-byte coordinates and scalars, hashing to the curve and the group of E(F_p)
+//   capi_p521.hip       the P-521 suites: 68-byte coordinates and scalars
+//   capi_p384.hip       the P-384 suites: 48-byte coordinates and scalars
+//   capi_native256.hip  the five native 256-bit suites (Ed25519, P-256, Baby JubJub, secp256k1, Curve25519): their descriptions, their own
+//                       entry points, and the native_* calls below through which capi_core.hip's dr_te_* paths reach them
+// The last six are one description per suite (widths, limits, kernels, hashing parameters) and their entry points as calls of
+// capi_suite.hpp's templates, the one host path they share; every host round trip of a single-launch entry point is io_round below.
 // Each header that defines kernels is included by exactly one of them; the others reach its kernels through the launch wrappers below.
-// (kernels_g1_h2c.hip.h defines none: the two BLS12-381 hashing units share its device functions.)
+// (kernels_g1_h2c.hip.h defines none: the two BLS12-381 hashing units share its device functions.  wave_msm.hip.h defines none either:
+// the suites' units instantiate its templates in their own named kernels.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -114,7 +118,7 @@ struct dr_ctx {
     hipStream_t wipe_stream = nullptr;
     hipEvent_t wipe_from = nullptr, wipe_done = nullptr;
     bool wipe_pending = false;
-    bool bjj_ready = false;                  // the Baby JubJub square-root tables are on this context's device (capi_core.hip)
+    bool bjj_ready = false;                  // the Baby JubJub square-root tables are on this context's device (capi_native256.hip)
     dr_ctx* aux = nullptr;                   // second stream for the latency-bound Bandersnatch side of the batch verifier
     dr_ctx* aux2 = nullptr;                  // third stream: the verifier's two G1 MSMs run side by side
     std::vector<dr_ctx*> helpers;            // further streams working for this context (a prover's Pedersen stream): profiling only
@@ -206,6 +210,8 @@ int launch(dr_ctx* ctx, const char* name, F&& f) {
     } while (0)
 
 inline unsigned div_up(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
+
+constexpr size_t MAX_SELFTEST = 1ull << 24;            // the field and law selftests' batch limit (capi_suite.hpp's and capi_core.hip's)
 
 // body of an entry point that allocates on the host or starts threads: C++ exceptions must not cross the C ABI (`who` opens the message)
 template <class F>
@@ -379,6 +385,21 @@ int encode_to_curve_msgs(dr_ctx* ctx, const drh::VrfSuite& su, size_t B, const u
 int encode_and_mul(dr_ctx* ctx, const drh::VrfSuite& su, size_t B, const uint8_t* data, const uint64_t* off, const uint8_t* salts,
                    const uint64_t* salt_off, const uint8_t* xs, uint8_t* inputs_xy, uint8_t* outs_xy,
                    const std::function<void()>* while_waiting = nullptr);
+
+// ---- capi_native256.hip: what the dr_te_* paths and load_suite of capi_core.hip ask of the five native 256-bit suites.  Each call returns
+// false and does nothing when cv is not a native suite's; otherwise rc is the call's result.  The caller has made the context current, except for the decoder, which does that itself.
+bool native_scalar_mul_batch(int cv, int& rc, dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy);
+bool native_msm_groups(int cv, int& rc, dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy);
+bool native_fixed_base_groups(int cv, int& rc, dr_ctx* ctx, const uint8_t* bases_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_xy);
+bool native_msm(int cv, int& rc, dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t out_xy[64]);   // the order: te_curve(cv)->n
+bool native_decode_points(int cv, int& rc, dr_ctx* ctx, bool tai, const uint8_t* enc, size_t n, uint8_t* out_xy, uint8_t* ok);
+// what load_suite reads from a native suite's description; null for a curve that is not native
+struct NativeSuiteInfo {
+    size_t enc_bytes, tai_bytes, identity_y;
+    bool flagged;
+    const char* name;
+};
+const NativeSuiteInfo* native_suite_info(int cv);
 
 // DOTRING_TRACE=1: wall-clock phase breakdown of the native batch calls on stderr
 struct PhaseTrace {

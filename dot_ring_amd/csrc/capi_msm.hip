@@ -1,4 +1,4 @@
-// libdotring_hip.so — C ABI, part 2 of 10: the G1 Pippenger pipeline over kernels_g1.hip.h, seam B (SRS handles, MSM entry
+// libdotring_hip.so — C ABI, part 2 of 11: the G1 Pippenger pipeline over kernels_g1.hip.h, seam B (SRS handles, MSM entry
 // points, G1 codecs) and the pairing entry points.
 #include "capi_internal.hpp"
 #include "kernels_g1.hip.h"

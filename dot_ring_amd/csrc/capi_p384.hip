@@ -1,4 +1,4 @@
-// libdotring_hip.so — C ABI, part 10 of 10: the P-384 suites (DR_CURVE_P384_RO / DR_CURVE_P384_NU; the reference's specs/p384.py).
+// libdotring_hip.so — C ABI, part 10 of 11: the P-384 suites (DR_CURVE_P384_RO / DR_CURVE_P384_NU; the reference's specs/p384.py).
 // Field elements and coordinates are 48 bytes little-endian, canonical; points are affine x || y, 96 bytes, and 96 zero bytes are the
 // identity, in and out ((0, 0) is not on the curve).  Scalars are 48 bytes used AS THEY ARE: the 97 windows of the schedule take every
 // 384-bit value, so none is refused.  None of it goes through the 64-byte paths of capi_core.hip but through capi_suite.hpp.  The

@@ -1,4 +1,4 @@
-// libdotring_hip.so — C ABI, part 9 of 10: the P-521 suites (DR_CURVE_P521_RO / DR_CURVE_P521_NU; the reference's specs/p521.py).
+// libdotring_hip.so — C ABI, part 9 of 11: the P-521 suites (DR_CURVE_P521_RO / DR_CURVE_P521_NU; the reference's specs/p521.py).
 // Field elements and coordinates are 68 bytes little-endian, canonical; points are affine x || y, 136 bytes, and 136 zero bytes are the
 // identity, in and out ((0, 0) is not on the curve).  Scalars are 68 bytes below 2^521 used AS THEY ARE: the 131 windows of the schedule
 // cover no more, so a larger one is refused here, on the host, before anything is uploaded.  None of it goes through the 64-byte paths of

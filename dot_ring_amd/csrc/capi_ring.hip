@@ -1,4 +1,4 @@
-// libdotring_hip.so — C ABI, part 3 of 10: seam C (the Fr NTT of kernels_ntt.hip.h) and the phases of the batched ring
+// libdotring_hip.so — C ABI, part 3 of 11: seam C (the Fr NTT of kernels_ntt.hip.h) and the phases of the batched ring
 // prover (kernels_ring.hip.h): everything between two Fiat-Shamir hashes stays in HBM.
 #include "capi_internal.hpp"
 #include "kernels_ntt.hip.h"

@@ -1,4 +1,4 @@
-// The one host path of every suite's single-launch entry points: the five 256-bit suites of capi_core.hip (Ed25519, P-256, Baby JubJub,
+// The one host path of every suite's single-launch entry points: the five 256-bit suites of capi_native256.hip (Ed25519, P-256, Baby JubJub,
 // secp256k1, Curve25519) and the wide ones (capi_blsg1.hip, capi_blsg2.hip, capi_ed448.hip, capi_p521.hip, capi_p384.hip), whose coordinates do not fit 64-byte points.
 // No kernel is defined here.  A unit describes its suite in one struct S and its entry points are calls of the templates below; every one
 // of them is one io_round (capi_internal.hpp).  S has
@@ -29,8 +29,6 @@
 #include "hostrecords.hpp"
 
 namespace dri {
-
-constexpr size_t MAX_SELFTEST = 1ull << 24;            // the field selftests' batch limit
 
 struct SuiteDefaults {
     static int consts_ready(dr_ctx*) { return DR_OK; }

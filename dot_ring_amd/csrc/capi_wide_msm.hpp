@@ -4,7 +4,7 @@
 //                        dr_blsg1_msm (capi_blsg1.hip): below S::wide_from terms it launches msm_groups in chunks of up to 64 and folds the
 //                        partial sums with the suite's law on the host; from there on wide_msm_buckets
 //   wide_msm_buckets<S>  the bucket method by msm_plan.hpp's plan_wide_msm, the set sums combined on the host (wide_combine.hpp); also
-//                        what native_msm (capi_core.hip) calls from NARROW_PIP_FROM terms for the five 256-bit suites
+//                        what native_msm (capi_native256.hip) calls from NARROW_PIP_FROM terms for the five 256-bit suites
 // No kernel is defined here.  Beyond capi_suite.hpp's members a suite S gives
 //   Law                                        the law as the host runs it, with the ABI's words <-> a point (P384Law, ...; narrow_law.hpp)
 //   wide_bits                                  what the tiling covers: one bit more than a scalar can have (wide_recode.hip.h)

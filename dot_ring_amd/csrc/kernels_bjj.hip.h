@@ -21,7 +21,7 @@ constexpr int BJJ_BLOCK = 64;         // one wave per workgroup; 64 KiB of LDS t
 // (kernels_bsn.hip.h) does in 8-bit windows for the BLS12-381 scalar field: t^(2^21) is one of the 128 elements of <c^(2^21)>, a
 // perfect-hash table gives e mod 2^7, t c^(-e0) raised to 2^14 the next window, and so on — 42 squarings, 7 products and 4 look-ups
 // after the exponentiation, the same in every lane.  x is a square iff e is even, and then sqrt(x) = R c^(-e/2).  The tables are
-// built on the host once per process and copied to the device once per context (capi_core.hip: bjj_consts_ready).  Entries are in
+// built on the host once per process and copied to the device once per context (capi_native256.hip: bjj_consts_ready).  Entries are in
 // Montgomery form (bn_unpack_raw reads them); the hash is over the low word of the standard (packed) value.
 constexpr int BJJ_DL_SLOTS = 4096;
 struct BjjConsts {

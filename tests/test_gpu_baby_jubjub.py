@@ -189,6 +189,29 @@ def test_decode_points_with_and_without_check(ctx):
     assert list(ok) == [int(r.decode(enc) is not None) for enc in cases]
 
 
+def test_decode_is_first_call_of_two_fresh_contexts():
+    """The square-root tables are built on the host once per process and copied to the device once per context, by the first call that
+    needs them and not by context creation: two contexts one after the other, each one's first call of any kind a checked decode of
+    three valid encodings and one that is not on the curve."""
+    from dot_ring_amd import _native
+
+    off_curve = next(y.to_bytes(32, "little") for y in range(2, 100) if r.decode(y.to_bytes(32, "little"), check=False) is None)
+    cases = [r.encode(r.mul(k, r.G)) for k in (1, 2, r.N - 1)]
+    cases.insert(2, off_curve)
+    want = [r.decode(enc) for enc in cases]
+    assert [w is not None for w in want] == [True, True, False, True]
+    for _ in range(2):
+        c = _native.Context(0)
+        try:
+            out, ok = c.bjj_decode_points(b"".join(cases), True)
+        finally:
+            c.close()
+        assert list(ok) == [1, 1, 0, 1]
+        for i, w in enumerate(want):
+            if w is not None:
+                assert out[64 * i : 64 * i + 64] == r.raw(w)
+
+
 def test_encode_to_curve_1000(ctx):
     import dot_ring_amd as d
 
