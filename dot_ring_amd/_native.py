@@ -196,6 +196,13 @@ _PROTOTYPES.update({
     "dr_ringvrf_verify_batch_multi": (c_int, [POINTER(c_void_p), c_size_t, POINTER(VrfSuiteStruct), POINTER(RingVerifierKeyStruct), c_size_t,
                                               c_char_p, c_char_p, POINTER(ctypes.c_uint64), c_char_p, POINTER(ctypes.c_uint64), c_char_p,
                                               POINTER(ctypes.c_uint64), c_char_p, POINTER(c_int)]),
+    "dr_ringvrf_verify_each": (c_int, [c_void_p, POINTER(VrfSuiteStruct), POINTER(RingVerifierKeyStruct), c_size_t, c_char_p, c_char_p,
+                                       POINTER(ctypes.c_uint64), c_char_p, POINTER(ctypes.c_uint64), c_char_p, POINTER(ctypes.c_uint64),
+                                       c_char_p, c_char_p, POINTER(ctypes.c_uint32)]),
+    "dr_ringvrf_verify_each_multi": (c_int, [POINTER(c_void_p), c_size_t, POINTER(VrfSuiteStruct), POINTER(RingVerifierKeyStruct), c_size_t,
+                                             c_char_p, c_char_p, POINTER(ctypes.c_uint64), c_char_p, POINTER(ctypes.c_uint64), c_char_p,
+                                             POINTER(ctypes.c_uint64), c_char_p, c_char_p, POINTER(ctypes.c_uint32)]),
+    "dr_g1_claim_tree_selftest": (c_int, [c_void_p, c_char_p, c_char_p, c_size_t, c_size_t, c_char_p, c_char_p]),
     "dr_host_hash": (c_int, [c_int, c_char_p, c_size_t, c_char_p, c_size_t]),
     "dr_hash_to_field_batch": (c_int, [POINTER(VrfSuiteStruct), c_char_p, POINTER(ctypes.c_uint64), c_size_t, c_char_p]),
     "dr_ringvrf_prove_batch": (c_int, [c_void_p, POINTER(VrfSuiteStruct), c_size_t, c_char_p, POINTER(ctypes.c_uint64), c_char_p,
@@ -667,6 +674,22 @@ def ringvrf_verify_batch_multi(contexts: list, suite: "VrfSuiteStruct", vk: "Rin
     return bool(ok.value)
 
 
+def ringvrf_verify_each_multi(contexts: list, suite: "VrfSuiteStruct", vk: "RingVerifierKeyStruct", proofs: bytes, inputs, ads, salts,
+                              seed32: bytes):
+    """dr_ringvrf_verify_each_multi: a verdict per 784-byte proof over the devices of `contexts` -> (list of bool, the four stats words)."""
+    batch = len(inputs)
+    if len(proofs) != 784 * batch:
+        raise ValueError("proofs must be 784 bytes each")
+    i_blob, i_off = _ragged(inputs)
+    d_blob, d_off = _ragged(ads)
+    s_blob, s_off = (None, None) if not salts or not any(salts) else _ragged(salts)
+    handles = (c_void_p * len(contexts))(*[c.handle for c in contexts])
+    verdicts, stats = ctypes.create_string_buffer(max(1, batch)), (ctypes.c_uint32 * 4)()
+    _check(lib().dr_ringvrf_verify_each_multi(handles, len(contexts), byref(suite), byref(vk), batch, proofs, i_blob, i_off, d_blob, d_off,
+                                              s_blob, s_off, seed32, verdicts, stats))
+    return [b != 0 for b in verdicts.raw[:batch]], tuple(stats)
+
+
 class Context:
     """One GPU + one HIP stream.  Not thread-safe; create one per thread / per rank."""
 
@@ -1111,6 +1134,33 @@ class Context:
         _check(lib().dr_ringvrf_verify_batch(self.handle, byref(suite), byref(vk), batch, proofs, i_blob, i_off, d_blob, d_off, s_blob, s_off,
                                              seed32, byref(ok)))
         return bool(ok.value)
+
+    def ringvrf_verify_each(self, suite: "VrfSuiteStruct", vk: "RingVerifierKeyStruct", proofs: bytes, inputs, ads, salts, seed32: bytes):
+        """dr_ringvrf_verify_each over 784-byte encoded proofs (<= 4096 per call) -> (list of bool, (pairing equations evaluated,
+        proofs excluded before the fold, tree depth, 0))."""
+        batch = len(inputs)
+        if len(proofs) != 784 * batch:
+            raise ValueError("proofs must be 784 bytes each")
+        i_blob, i_off = _ragged(inputs)
+        d_blob, d_off = _ragged(ads)
+        s_blob, s_off = (None, None) if not salts or not any(salts) else _ragged(salts)
+        verdicts, stats = ctypes.create_string_buffer(max(1, batch)), (ctypes.c_uint32 * 4)()
+        _check(lib().dr_ringvrf_verify_each(self.handle, byref(suite), byref(vk), batch, proofs, i_blob, i_off, d_blob, d_off, s_blob, s_off,
+                                            seed32, verdicts, stats))
+        return [b != 0 for b in verdicts.raw[:batch]], tuple(stats)
+
+    def g1_claim_tree_selftest(self, pts_le_xy: bytes, scalars: bytes, groups: int, m: int):
+        """dr_g1_claim_tree_selftest: `groups` groups of m terms (96-byte affine LE points, 32-byte LE scalars) -> (nodes, flags): the
+        2 * Bp - 1 nodes of the sum tree in heap order as 96-byte affine LE records, and one byte per node, 1 for the identity."""
+        if len(pts_le_xy) != 96 * groups * m or len(scalars) != 32 * groups * m:
+            raise ValueError("groups * m points of 96 bytes and scalars of 32 bytes")
+        padded = 1
+        while padded < groups:
+            padded *= 2
+        nodes = 2 * padded - 1
+        out, inf = ctypes.create_string_buffer(96 * nodes), ctypes.create_string_buffer(nodes)
+        _check(lib().dr_g1_claim_tree_selftest(self.handle, pts_le_xy, scalars, groups, m, out, inf))
+        return out.raw[: 96 * nodes], inf.raw[:nodes]
 
     def g1_decompress_batch(self, enc: bytes):
         """KZG.decompress_g1 for len(enc)/48 encodings on the GPU -> (list of 96-byte records or None for infinity, flags)."""

@@ -6,6 +6,7 @@
 #include <atomic>
 #include <condition_variable>
 #include "hostsigma.hpp"
+#include "verify_tree.hpp"
 
 using namespace dri;
 namespace rf = drh::ringfmt;
@@ -306,7 +307,7 @@ int dr_ringvrf_aux_take_blindings(uint8_t* aux, size_t batch, uint8_t* out_blind
 // `stride`; te_xy: the four decoded points of each proof (O, Y_bar, R, O_k affine); in_pts: encode_to_curve of the inputs.
 int pedersen_verify_core(dr_ctx* actx, const drh::VrfSuite& su, size_t B, const uint8_t* proofs, size_t stride,
                                 const std::vector<uint8_t>& te_xy, const std::vector<uint8_t>& in_pts, const uint8_t* ads,
-                                const uint64_t* ad_off, int& ped_ok) {
+                                const uint64_t* ad_off, int& ped_ok, const uint8_t* excluded = nullptr, uint8_t* each_ok = nullptr) {
     const drh::Mod256& mn = su.cv->n;
     const size_t pl = su.point_len;
     std::vector<uint8_t> in_store;
@@ -314,6 +315,7 @@ int pedersen_verify_core(dr_ctx* actx, const drh::VrfSuite& su, size_t B, const 
     TRY(suite_coords(actx, su, in_pts.data(), B, 1, in_store, &in_c));
     std::vector<uint8_t> cs(B * 32);
     drh::parallel_for(B, [&](size_t i) {
+        if (excluded && excluded[i]) return;
         const uint8_t* pr = proofs + stride * i;
         uint8_t enc[drh::POINT_MAX];
         drh::enc_point(su, in_c + 64 * i, enc);
@@ -324,6 +326,31 @@ int pedersen_verify_core(dr_ctx* actx, const drh::VrfSuite& su, size_t B, const 
         drh::vrf_challenge(su, t, pr + 2 * pl, 2, c);          // R, O_k
         drh::store_le32(c, cs.data() + 32 * i);
     });
+    if (each_ok) {
+        // a verdict per proof: the two equations of each proof as they stand, O_k = s*I - c*O and R = s*G + s_b*B - c*Y_bar — 2B groups of
+        // three terms in ONE launch of the group kernel, compared on the host (an excluded proof rides along as 0 * G and is not compared)
+        std::vector<uint8_t> pts(6 * B * 64), sc(6 * B * 32, 0), sums(2 * B * 64);
+        drh::parallel_for(B, [&](size_t i) {
+            uint8_t* p = pts.data() + 384 * i;
+            if (excluded && excluded[i]) { for (int k = 0; k < 6; k++) std::memcpy(p + 64 * k, su.generator, 64); return; }
+            const uint8_t* pr = proofs + stride * i;
+            uint64_t c[4];
+            drh::load_le32(cs.data() + 32 * i, c);
+            mn.neg(c, c);
+            uint8_t* k = sc.data() + 192 * i;
+            std::memcpy(p, in_pts.data() + 64 * i, 64);                  std::memcpy(k, pr + 4 * pl, 32);            // s * I
+            std::memcpy(p + 64, te_xy.data() + 64 * (4 * i), 64);        drh::store_le32(c, k + 32);                 // - c * O
+            std::memcpy(p + 128, su.generator, 64);                                                                  // (0 * G: groups are of one size)
+            std::memcpy(p + 192, su.generator, 64);                      std::memcpy(k + 96, pr + 4 * pl, 32);       // s * G
+            std::memcpy(p + 256, su.blinding_base, 64);                  std::memcpy(k + 128, pr + 4 * pl + 32, 32); // s_b * B
+            std::memcpy(p + 320, te_xy.data() + 64 * (4 * i + 1), 64);   drh::store_le32(c, k + 160);                // - c * Y_bar
+        });
+        TRY(te_msm_groups(actx, su.cv->id, pts.data(), sc.data(), 2 * B, 3, sums.data()));
+        for (size_t i = 0; i < B; i++)
+            each_ok[i] = !(excluded && excluded[i]) && std::memcmp(sums.data() + 128 * i, te_xy.data() + 64 * (4 * i + 3), 64) == 0 &&
+                         std::memcmp(sums.data() + 128 * i + 64, te_xy.data() + 64 * (4 * i + 2), 64) == 0;
+        return DR_OK;
+    }
     {
         drh::Bytes absorbed = su.suite_id;
         drh::put8(absorbed, 0x50);                             // BATCH_VERIFY
@@ -390,6 +417,9 @@ static size_t verify_host_max() {
 // Bandersnatch MSM (5B+2 points, must be the identity) and two G1 MSMs + one pairing equation.  One call = one object; run() is the
 // timeline, the phases are the methods below it in the order they run.  A phase that finds the batch malformed (a non-canonical
 // scalar, a point that does not decode, a zeta inside the domain) sets `rejected`: the verdict is then 0 with DR_OK.
+// run_each() (dr_ringvrf_verify_each, `each` set) goes through the same phases for a verdict PER PROOF: there such a phase marks the
+// proof in `excluded` instead — verdict 0, its scalars zero, its undecodable points the identity — and the others are judged as if
+// it were absent; the two G1 MSMs give way to the per-proof claim points and their sum tree, the pairing to the descent over it.
 // The members are declared in the order the phases create them and each helper thread's joiner behind everything its thread
 // touches, so that on ANY exit path a thread is joined before what it works on goes away.
 struct RingVerifyBatch {
@@ -404,7 +434,13 @@ struct RingVerifyBatch {
     const size_t n_te, n_g1;                         // Bandersnatch points of the proofs; G1 points of both folds
     const bool small;
     bool rejected = false;
-    PhaseTrace tr_{"verify_batch"};
+    // dr_ringvrf_verify_each: a malformed proof is excluded (verdict 0, scalars zero, undecodable points the identity) instead of
+    // rejecting the call; ring and Pedersen verdicts per proof
+    uint8_t* const verdicts;
+    uint32_t* const stats;
+    const bool each;
+    std::vector<uint8_t> excluded, ped_each, ring_each, nodes_le;
+    PhaseTrace tr_{verdicts ? "verify_each" : "verify_batch"};
     // gather
     std::vector<uint8_t> te_enc, g1_enc;
     // verifier randomness: two non-zero coefficients per proof (kzg.py:84-108) — they depend on the seed alone, and they are the only scalars of
@@ -438,9 +474,11 @@ struct RingVerifyBatch {
     std::vector<uint64_t> fixed_part;                   // per proof: r1*nu0, r1*nu1, r1*nu2, r1*agg + r2*l_zw
 
     RingVerifyBatch(dr_ctx* c, const drh::VrfSuite& s, const dr_ring_verifier_key* k, size_t batch, const uint8_t* pr, const uint8_t* in,
-                    const uint64_t* ino, const uint8_t* ad, const uint64_t* ado, const uint8_t* sa, const uint64_t* sao, const uint8_t* seed)
+                    const uint64_t* ino, const uint8_t* ad, const uint64_t* ado, const uint8_t* sa, const uint64_t* sao, const uint8_t* seed, uint8_t* verdicts_out = nullptr,
+                    uint32_t* stats_out = nullptr)
         : ctx(c), su(s), vk(k), B(batch), proofs(pr), inputs(in), ads(ad), salts(sa), seed32(seed), in_off(ino), ad_off(ado), salt_off(sao),
-          st(c->stream), n_te(4 * batch), n_g1(rf::G_PER_PROOF * batch + rf::G_FIXED), small(batch <= verify_host_max()), g1_bases(c->vfy_bases) {}
+          st(c->stream), n_te(4 * batch), n_g1(rf::G_PER_PROOF * batch + rf::G_FIXED), small(batch <= verify_host_max()), verdicts(verdicts_out),
+          stats(stats_out), each(verdicts_out != nullptr), excluded(each ? batch : 0, 0), g1_bases(c->vfy_bases) {}
 
     int run(int* ok) {
         gather();
@@ -493,7 +531,7 @@ struct RingVerifyBatch {
             for (int k = 0; k < 2; k++) { drh::load_le32(pr + rf::PED_SCALARS + 32 * k, v); if (drh::Mod256::geq(v, mn.m)) ok_i = false; }      // dec_scalar
             for (int k = 0; k < 7; k++) { drh::load_le32(pr + rf::EVALS + 32 * k, v); if (drh::Mod256::geq(v, mp.m)) ok_i = false; }
             drh::load_le32(pr + rf::L_ZW, v); if (drh::Mod256::geq(v, mp.m)) ok_i = false;
-            if (!ok_i) canonical.store(false, std::memory_order_relaxed);
+            if (!ok_i) { if (each) excluded[i] = 1; else canonical.store(false, std::memory_order_relaxed); }
             uint8_t* g = g1_enc.data() + rf::G_PER_PROOF * 48 * i;
             std::memcpy(g + 48 * rf::G_COMMITS, pr + rf::COMMITS, rf::COMMITS_BYTES);      // C_b, C_accip, C_accx, C_accy
             std::memcpy(g + 48 * rf::G_CQ, pr + rf::CQ, 48);                               // C_q
@@ -520,7 +558,9 @@ struct RingVerifyBatch {
                     gate_cv.wait(lk, [&] { return gate >= 0; });
                     if (gate == 0) return DR_OK;
                 }
-                return pedersen_verify_core(actx, su, B, proofs, rf::PROOF_BYTES, te_xy, in_pts, ads, ad_off, ped_ok);
+                if (each) ped_each.assign(B, 0);
+                return pedersen_verify_core(actx, su, B, proofs, rf::PROOF_BYTES, te_xy, in_pts, ads, ad_off, ped_ok, each ? excluded.data() : nullptr,
+                                            each ? ped_each.data() : nullptr);
             });
         });
         return DR_OK;
@@ -548,14 +588,22 @@ struct RingVerifyBatch {
         // 4B + 7B decodings of 35 - 80 us each, one per item of the worker pool (its threads are already there: starting seven of our
         // own cost more than a decoding)
         drh::parallel_for(n_te + n_dec, decode_one, 1);
-        for (int g : good) if (!g) { rejected = true; return DR_OK; }      // malformed / invalid point: ok = 0
+        for (size_t j = 0; j < good.size(); j++)
+            if (!good[j]) {                                                  // malformed / invalid point: ok = 0
+                if (!each) { rejected = true; return DR_OK; }
+                excluded[j < n_te ? j / 4 : (j - n_te) / rf::G_PER_PROOF] = 1;      // (an undecoded G1 record stays zero: the identity)
+            }
         host_bases.resize(n_g1);
         for (size_t k = 0; k < n_dec; k++) {
             const uint8_t* le = g1_le.data() + 96 * k;
             bool inf = true;
             for (int q = 0; q < 96; q++) if (le[q]) { inf = false; break; }
             host_bases[k].inf = inf;
-            if (!inf && (!drh::Fq::load_le(host_bases[k].x, le) || !drh::Fq::load_le(host_bases[k].y, le + 48))) { rejected = true; return DR_OK; }
+            if (!inf && (!drh::Fq::load_le(host_bases[k].x, le) || !drh::Fq::load_le(host_bases[k].y, le + 48))) {
+                if (!each) { rejected = true; return DR_OK; }
+                excluded[k / rf::G_PER_PROOF] = 1;
+                host_bases[k].inf = true;
+            }
         }
         for (size_t k = 0; k < rf::G_FIXED; k++) {
             const uint8_t* be = k < 3 ? vk->fixed_commitments + 96 * k : vk->g1_generator;
@@ -632,7 +680,11 @@ struct RingVerifyBatch {
         HIP_TRY(hipMemcpyAsync(g1_le.data(), g1_std.p, n_dec * 96, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(flags.data(), d_ok, (n_te + n_dec) * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        for (size_t i = 0; i < n_te + n_dec; i++) if (!flags[i]) { rejected = true; return DR_OK; }      // malformed / invalid point: ok = 0
+        for (size_t i = 0; i < n_te + n_dec; i++)
+            if (!flags[i]) {                                                 // malformed / invalid point: ok = 0
+                if (!each) { rejected = true; return DR_OK; }
+                excluded[i < n_te ? i / 4 : (i - n_te) / rf::G_PER_PROOF] = 1;      // (k_g1_decompress wrote the identity in its place)
+            }
         return DR_OK;
     }
 
@@ -718,6 +770,7 @@ struct RingVerifyBatch {
             uint64_t den[2 * VS][4];
             for (size_t i = lo; i < hi; i++) {
                 const size_t k = i - lo;
+                if (each && excluded[i]) { bad[i] = 1; std::memset(den[2 * k], 0, 64); continue; }
                 drh::te_add_affine_prep(*su.cv, vk->seed_xy, te_xy.data() + 64 * (4 * i + 1), ta[k]);
                 std::memcpy(den[2 * k], ta[k].den, 32);
                 if (drh::ring_verifier_terms_prep(dm, zeta_all.data() + 32 * i, rt[k])) std::memcpy(den[2 * k + 1], rt[k].prod, 32);
@@ -738,7 +791,8 @@ struct RingVerifyBatch {
                 drh::ring_claim_fold(cl, r[0], r[1], lhs_sc.data() + 32 * rf::G_PER_PROOF * i, &fixed_part[16 * i]);
             }
         }, 1);
-        for (size_t i = 0; i < B; i++) if (bad[i]) rejected = true;
+        for (size_t i = 0; i < B; i++)
+            if (bad[i]) { if (each) excluded[i] = 1; else rejected = true; }
     }
 
     // two MSMs over the decompressed bases (already resident): lhs over all 7B+4 points here, rhs (started above) over the 2B opening
@@ -781,6 +835,131 @@ struct RingVerifyBatch {
         if (side_rc != DR_OK) return fail(side_rc, side_err.empty() ? "Pedersen part failed" : side_err);
         return DR_OK;
     }
+
+    // ---- dr_ringvrf_verify_each: the same phases, the proofs kept apart.  The coefficients r1, r2 are drawn per proof, so the sum of
+    // (L_i, R_i) over ANY subset of proofs is a sound combination of its own: the tree of these sums is built once (kernels_g1_claims.hip.h,
+    // or on the host for the small route) and pairings are spent only where a subtree fails (verify_tree.hpp).
+    int run_each() {
+        gather();
+        tr_.mark("gather");
+        TRY(start_pedersen_side());
+        TRY(small ? decode_host() : decode_kernels());
+        tr_.mark("decode");
+        replay();
+        tr_.mark("replay");
+        claim_scalars();
+        size_t n_excluded = 0;
+        for (size_t i = 0; i < B; i++) n_excluded += excluded[i];
+        open_gate(1);                // (`excluded` is final from here on: the Pedersen helper reads it)
+        tr_.mark("transcripts");
+        const drh::VerifyTreeShape shape(B);
+        TRY(small ? claim_nodes_host(shape) : claim_nodes_device(shape));
+        tr_.mark("claim tree");
+        size_t tested = 0;
+        TRY(descend(shape, tested));
+        tr_.mark("pairings");
+        TRY(join());
+        for (size_t i = 0; i < B; i++) verdicts[i] = (!excluded[i] && ring_each[i] && ped_each[i]) ? 1 : 0;
+        if (stats) { stats[0] = (uint32_t)tested; stats[1] = (uint32_t)n_excluded; stats[2] = (uint32_t)shape.depth; stats[3] = 0; }
+        return DR_OK;
+    }
+
+    // the 13 terms of proof i: its seven claim scalars on its own points, f_{i,0..3} on C_px, C_py, C_s, G1[0] (the last negated), then
+    // r1, r2 on its opening proofs; all zero for an excluded proof
+    static constexpr size_t CLAIM_TERMS = rf::G_PER_PROOF + rf::G_FIXED + 2, CLAIM_L = rf::G_PER_PROOF + rf::G_FIXED;
+    void claim_terms(std::vector<uint32_t>& idx, std::vector<uint8_t>& sc) const {
+        idx.resize(B * CLAIM_TERMS);
+        sc.assign(B * CLAIM_TERMS * 32, 0);
+        for (size_t i = 0; i < B; i++) {
+            uint32_t* ix = &idx[CLAIM_TERMS * i];
+            uint8_t* k = sc.data() + 32 * CLAIM_TERMS * i;
+            for (size_t j = 0; j < rf::G_PER_PROOF; j++) ix[j] = (uint32_t)(rf::G_PER_PROOF * i + j);
+            for (size_t j = 0; j < rf::G_FIXED; j++) ix[rf::G_PER_PROOF + j] = (uint32_t)(rf::G_PER_PROOF * B + j);
+            ix[CLAIM_L] = (uint32_t)(rf::G_PER_PROOF * i + rf::G_OPENS);
+            ix[CLAIM_L + 1] = ix[CLAIM_L] + 1;
+            if (excluded[i]) continue;
+            std::memcpy(k, lhs_sc.data() + 32 * rf::G_PER_PROOF * i, 32 * rf::G_PER_PROOF);
+            for (size_t j = 0; j < rf::G_FIXED; j++) {
+                uint64_t f[4];
+                std::memcpy(f, &fixed_part[16 * i + 4 * j], 32);
+                if (j == 3) mp.neg(f, f);
+                drh::store_le32(f, k + 32 * (rf::G_PER_PROOF + j));
+            }
+            std::memcpy(k + 32 * CLAIM_L, rhs_sc.data() + 64 * i, 64);
+        }
+    }
+
+    // nodes_le: the L tree then the R tree, 2 * Bp - 1 nodes each in heap order, affine standard-form little-endian x || y (zeros: identity)
+    int claim_nodes_device(const drh::VerifyTreeShape& shape) {
+        std::vector<uint32_t> idx;
+        std::vector<uint8_t> sc;
+        claim_terms(idx, sc);
+        nodes_le.resize(2 * shape.nodes() * 96);
+        TRY(use_ctx(ctx));           // from here on the context's scratch is used: behind a pending wipe of it
+        const uint32_t off[2] = {0, (uint32_t)CLAIM_L}, m[2] = {(uint32_t)CLAIM_L, 2};
+        return g1_claim_tree(ctx, g1_bases.as<uint32_t>(), idx.data(), sc.data(), B, CLAIM_TERMS, 2, off, m, nodes_le.data());
+    }
+
+    int claim_nodes_host(const drh::VerifyTreeShape& shape) {
+        std::vector<uint32_t> idx;
+        std::vector<uint8_t> sc;
+        claim_terms(idx, sc);
+        const size_t N = shape.nodes();
+        std::vector<drh::G1> tree(2 * N, drh::G1::inf());
+        drh::parallel_for(2 * B, [&](size_t job) {
+            const size_t i = job >> 1, c = job & 1, first = CLAIM_TERMS * i + (c ? CLAIM_L : 0), m = c ? 2 : CLAIM_L;
+            drh::G1AffineHost pts[CLAIM_L];
+            for (size_t j = 0; j < m; j++) pts[j] = host_bases[idx[first + j]];
+            tree[c * N + shape.padded - 1 + i] = drh::g1_msm_small(pts, sc.data() + 32 * first, m, 1);
+        }, 1);
+        for (size_t c = 0; c < 2; c++)
+            for (size_t k = shape.padded - 1; k-- > 0;) tree[c * N + k] = drh::g1_add(tree[c * N + 2 * k + 1], tree[c * N + 2 * k + 2]);
+        nodes_le.assign(2 * N * 96, 0);
+        drh::parallel_for(2 * N, [&](size_t k) {
+            drh::Fq ax, ay;
+            if (!drh::g1_to_affine(tree[k], ax, ay)) return;
+            ax.store_le(nodes_le.data() + 96 * k);
+            ay.store_le(nodes_le.data() + 96 * k + 48);
+        }, 4);
+        return DR_OK;
+    }
+
+    // e(L, G2[0]) * e(-R, G2[1]) == 1 at the nodes the descent asks for, the tests of one request side by side on the worker pool
+    int descend(const drh::VerifyTreeShape& shape, size_t& tested) {
+        const size_t N = shape.nodes();
+        std::atomic<int> rc{DR_OK};
+        std::mutex err_m;
+        std::string err;
+        auto operand = [&](size_t node, bool negate, uint8_t out[96]) {
+            const uint8_t* le = nodes_le.data() + 96 * node;
+            std::memset(out, 0, 96);
+            drh::Fq x, y;
+            bool inf = true;
+            for (int q = 0; q < 96; q++) if (le[q]) { inf = false; break; }
+            if (inf || !drh::Fq::load_le(x, le) || !drh::Fq::load_le(y, le + 48)) return;
+            x.store_be(out);
+            (negate ? y.neg() : y).store_be(out + 48);
+        };
+        auto test = [&](const std::vector<size_t>& ask, std::vector<uint8_t>& pass) {
+            drh::parallel_for(ask.size(), [&](size_t j) {
+                uint8_t pair[2 * 96];
+                operand(ask[j], false, pair);
+                operand(N + ask[j], true, pair + 96);
+                drh::Fq12 f;
+                const int r = pairing_miller(pair, vk->g2, 2, f);
+                if (r != DR_OK) {
+                    std::lock_guard<std::mutex> lk(err_m);
+                    if (rc.exchange(r) == DR_OK) err = dr_last_error();
+                    return;
+                }
+                pass[j] = pairing_product_is_one(f) ? 1 : 0;
+            }, 1);
+        };
+        ring_each.assign(B, 0);
+        tested = drh::verify_tree_descend(shape, test, ring_each.data());
+        if (rc.load() != DR_OK) return fail(rc.load(), err.empty() ? "pairing failed" : err);
+        return DR_OK;
+    }
 };
 
 int ringvrf_verify_batch_impl(dr_ctx* ctx, const dr_vrf_suite* suite, const dr_ring_verifier_key* vk, size_t batch, const uint8_t* proofs,
@@ -800,6 +979,33 @@ int ringvrf_verify_batch_impl(dr_ctx* ctx, const dr_vrf_suite* suite, const dr_r
     TRY(offsets_ok(batch, {in_off, ad_off, salt_off}));
     RingVerifyBatch v(ctx, su, vk, batch, proofs, inputs, in_off, ads, ad_off, salts, salt_off, seed32);
     return v.run(ok);
+}
+
+// ... with a verdict per proof: the same refusals, the same phases (RingVerifyBatch::run_each)
+int ringvrf_verify_each_impl(dr_ctx* ctx, const dr_vrf_suite* suite, const dr_ring_verifier_key* vk, size_t batch, const uint8_t* proofs,
+                             const uint8_t* inputs, const uint64_t* in_off, const uint8_t* ads, const uint64_t* ad_off, const uint8_t* salts,
+                             const uint64_t* salt_off, const uint8_t seed32[32], uint8_t* verdicts, uint32_t* stats) {
+    if (!ctx) return fail(DR_ERR_INVALID, "null context");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!vk || !proofs || !in_off || !ad_off || !seed32 || !vk->fs_prefix || (batch && !verdicts)) return fail(DR_ERR_INVALID, "null argument");
+    if (stats) std::memset(stats, 0, 4 * sizeof(uint32_t));
+    if (batch == 0) return DR_OK;
+    if (batch > 4096) return fail(DR_ERR_INVALID, "batch must be at most 4096 per call");
+    std::memset(verdicts, 0, batch);
+    if (vk->log2n < 9 || vk->log2n > 16) return fail(DR_ERR_INVALID, "bad domain size");
+    drh::VrfSuite su;
+    TRY(load_suite(suite, su));
+    TRY(offsets_ok(batch, {in_off, ad_off, salt_off}));
+    RingVerifyBatch v(ctx, su, vk, batch, proofs, inputs, in_off, ads, ad_off, salts, salt_off, seed32, verdicts, stats);
+    return v.run_each();
+}
+
+int dr_ringvrf_verify_each(dr_ctx* ctx, const dr_vrf_suite* suite, const dr_ring_verifier_key* vk, size_t batch, const uint8_t* proofs,
+                           const uint8_t* inputs, const uint64_t* in_off, const uint8_t* ads, const uint64_t* ad_off, const uint8_t* salts,
+                           const uint64_t* salt_off, const uint8_t seed32[32], uint8_t* verdicts, uint32_t* stats) {
+    return abi_guard("native verifier", [&] {
+        return ringvrf_verify_each_impl(ctx, suite, vk, batch, proofs, inputs, in_off, ads, ad_off, salts, salt_off, seed32, verdicts, stats);
+    });
 }
 
 int dr_ringvrf_verify_batch(dr_ctx* ctx, const dr_vrf_suite* suite, const dr_ring_verifier_key* vk, size_t batch, const uint8_t* proofs,
@@ -1143,6 +1349,48 @@ int dr_ringvrf_verify_batch_multi(dr_ctx* const* ctxs, size_t n_ctxs, const dr_v
         int all = 1;
         for (size_t g = 0; g < n_ctxs; g++) all &= verdict[g];
         *ok = all;
+        return DR_OK;
+    });
+}
+
+// every shard writes its slice of `verdicts`; the statistics are summed, the depth is the deepest tree's
+int dr_ringvrf_verify_each_multi(dr_ctx* const* ctxs, size_t n_ctxs, const dr_vrf_suite* suite, const dr_ring_verifier_key* vk, size_t batch,
+                                 const uint8_t* proofs, const uint8_t* inputs, const uint64_t* in_off, const uint8_t* ads, const uint64_t* ad_off,
+                                 const uint8_t* salts, const uint64_t* salt_off, const uint8_t seed32[32], uint8_t* verdicts, uint32_t* stats) {
+    return abi_guard("native verifier", [&]() -> int {
+        if (!ctxs || n_ctxs == 0 || n_ctxs > 64) return fail(DR_ERR_INVALID, "1..64 contexts");
+        if (!vk || !proofs || !in_off || !ad_off || !seed32 || (batch && !verdicts)) return fail(DR_ERR_INVALID, "null argument");
+        for (size_t g = 0; g < n_ctxs; g++) {
+            if (!ctxs[g]) return fail(DR_ERR_INVALID, "null context");
+            for (size_t h = 0; h < g; h++)
+                if (ctxs[h] == ctxs[g]) return fail(DR_ERR_INVALID, "every shard needs a context of its own");
+        }
+        if (stats) std::memset(stats, 0, 4 * sizeof(uint32_t));
+        if (batch == 0) return DR_OK;
+        std::vector<uint32_t> shard_stats(4 * n_ctxs, 0);
+        TRY(run_shards(n_ctxs, [&](size_t g) -> int {
+            const Shard sh = shard_of(batch, g, n_ctxs);
+            for (size_t lo = sh.lo; lo < sh.hi; lo += 4096) {
+                const size_t n = std::min<size_t>(4096, sh.hi - lo);
+                // every shard (and chunk) folds its claims with randomness of its own: SHAKE256(seed || LE64(first proof))
+                uint8_t mix[40], sub[32];
+                std::memcpy(mix, seed32, 32);
+                for (int k = 0; k < 8; k++) mix[32 + k] = (uint8_t)((uint64_t)lo >> (8 * k));
+                drh::Shake256 sh256;
+                sh256.update(mix, 40);
+                sh256.digest(sub, 32);
+                uint32_t one[4] = {0, 0, 0, 0};
+                TRY(ringvrf_verify_each_impl(ctxs[g], suite, vk, n, proofs + rf::PROOF_BYTES * lo, inputs, in_off + lo, ads, ad_off + lo, salts,
+                                             salt_off ? salt_off + lo : nullptr, sub, verdicts + lo, one));
+                uint32_t* s = &shard_stats[4 * g];
+                s[0] += one[0]; s[1] += one[1]; s[2] = std::max(s[2], one[2]);
+            }
+            return DR_OK;
+        }));
+        if (stats)
+            for (size_t g = 0; g < n_ctxs; g++) {
+                stats[0] += shard_stats[4 * g]; stats[1] += shard_stats[4 * g + 1]; stats[2] = std::max(stats[2], shard_stats[4 * g + 2]);
+            }
         return DR_OK;
     });
 }

@@ -442,6 +442,10 @@ int bucket_size_order(dr_ctx* ctx, size_t nbuckets);
 void g1_launch_decompress(hipStream_t st, const uint8_t* d_enc, uint32_t* d_bases, uint32_t* d_ok, size_t n);
 void g1_launch_bases_to_mont(hipStream_t st, uint32_t* d_bases, size_t n);
 void g1_launch_bases_from_mont(hipStream_t st, const uint32_t* d_bases, uint32_t* d_out, size_t n);
+// kernels_g1_claims.hip.h: per-group sums of scalar multiples of resident bases and the heap-ordered tree of their subset sums
+size_t g1_claim_tree_padded(size_t groups);
+int g1_claim_tree(dr_ctx* ctx, const uint32_t* d_bases, const uint32_t* h_idx, const uint8_t* h_scalars, size_t groups, size_t stride, size_t comps,
+                  const uint32_t off[2], const uint32_t m[2], uint8_t* out_le);
 
 // ---- capi_p384.hip, capi_p521.hip, capi_ed448.hip: dr_wide_msm of their suites (capi_wide_msm.hpp); the dispatcher is capi_msm.hip's
 int p384_wide_msm(dr_ctx* ctx, const uint8_t* pts_xy, const uint8_t* scalars, size_t n, uint8_t* out_xy);

@@ -2,6 +2,7 @@
 // points, G1 codecs) and the pairing entry points.
 #include "capi_internal.hpp"
 #include "kernels_g1.hip.h"
+#include "kernels_g1_claims.hip.h"
 #include "kernels_te_msm.hip.h"
 
 using namespace dri;
@@ -563,6 +564,85 @@ void g1_launch_bases_to_mont(hipStream_t st, uint32_t* d_bases, size_t n) {
 }
 void g1_launch_bases_from_mont(hipStream_t st, const uint32_t* d_bases, uint32_t* d_out, size_t n) {
     hipLaunchKernelGGL(dr::k_g1_bases_from_mont, dim3(div_up(n, 256)), dim3(256), 0, st, d_bases, d_out, (uint32_t)n);
+}
+
+// Claim points and their sum tree (kernels_g1_claims.hip.h) over bases already on the device: `terms` = groups * stride terms, term t is
+// scalars[t] on base h_idx[t] (null: base t); leaf g of component c sums terms [g * stride + off[c], + m[c]).  out_le: comps trees of
+// 2 * Bp - 1 nodes each (heap order), affine standard-form little-endian x || y, zeros for the identity.  Works in io_a (indices),
+// scalars, io_b (terms), io_c (nodes) and result (affine nodes) on the context's stream; the caller has made the context current.
+size_t g1_claim_tree_padded(size_t groups) {
+    size_t bp = 1;
+    while (bp < groups) bp <<= 1;
+    return bp;
+}
+int g1_claim_tree(dr_ctx* ctx, const uint32_t* d_bases, const uint32_t* h_idx, const uint8_t* h_scalars, size_t groups, size_t stride, size_t comps,
+                  const uint32_t off[2], const uint32_t m[2], uint8_t* out_le) {
+    if (groups == 0 || groups > 4096 || stride == 0 || stride > 64 || comps < 1 || comps > 2) return fail(DR_ERR_INVALID, "claim tree: 1..4096 groups of 1..64 terms");
+    for (size_t c = 0; c < comps; c++)
+        if ((size_t)off[c] + m[c] > stride) return fail(DR_ERR_INVALID, "claim tree: component outside its group");
+    const size_t n = groups * stride, bp = g1_claim_tree_padded(groups), nodes = comps * (2 * bp - 1);
+    hipStream_t st = ctx->stream;
+    TRY(ctx->scalars.reserve(n * 32));
+    TRY(ctx->io_b.reserve(n * 192));
+    TRY(ctx->io_c.reserve(nodes * 192));
+    TRY(ctx->result.reserve(nodes * 96));
+    HIP_TRY(hipMemcpyAsync(ctx->scalars.p, h_scalars, n * 32, hipMemcpyHostToDevice, st));
+    if (h_idx) {
+        TRY(ctx->io_a.reserve(n * 4));
+        HIP_TRY(hipMemcpyAsync(ctx->io_a.p, h_idx, n * 4, hipMemcpyHostToDevice, st));
+    }
+    dr::ClaimTreeShape sh{};
+    sh.groups = (uint32_t)groups; sh.padded = (uint32_t)bp; sh.stride = (uint32_t)stride; sh.comps = (uint32_t)comps;
+    for (size_t c = 0; c < comps; c++) { sh.off[c] = off[c]; sh.m[c] = m[c]; }
+    TRY(launch(ctx, "k_g1_claim_terms", [&] {
+        hipLaunchKernelGGL(dr::k_g1_claim_terms, dim3(div_up(n, 64)), dim3(64), 0, st, d_bases, h_idx ? ctx->io_a.as<uint32_t>() : nullptr,
+                           ctx->scalars.as<uint32_t>(), (uint32_t)n, ctx->io_b.as<uint32_t>());
+    }));
+    const unsigned wgs = (unsigned)std::max<size_t>(1, bp / dr::CLAIM_TREE_WG);
+    TRY(launch(ctx, "k_g1_claim_tree", [&] {
+        hipLaunchKernelGGL(dr::k_g1_claim_tree, dim3(wgs, (unsigned)comps), dim3(dr::CLAIM_TREE_WG), 0, st, ctx->io_b.as<uint32_t>(), sh,
+                           ctx->io_c.as<uint32_t>(), 0);
+    }));
+    if (wgs > 1)
+        TRY(launch(ctx, "k_g1_claim_tree", [&] {
+            hipLaunchKernelGGL(dr::k_g1_claim_tree, dim3(1, (unsigned)comps), dim3(dr::CLAIM_TREE_WG), 0, st, ctx->io_b.as<uint32_t>(), sh,
+                               ctx->io_c.as<uint32_t>(), 1);
+        }));
+    TRY(launch(ctx, "k_g1_results_affine", [&] {
+        hipLaunchKernelGGL(dr::k_g1_results_affine, dim3(div_up(nodes, 64)), dim3(64), 0, st, ctx->io_c.as<uint32_t>(), (uint32_t)nodes,
+                           ctx->result.as<uint32_t>());
+    }));
+    HIP_TRY(hipMemcpyAsync(out_le, ctx->result.p, nodes * 96, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (ctx->prof) TRY(prof_collect(ctx));
+    return DR_OK;
+}
+
+int dr_g1_claim_tree_selftest(dr_ctx* ctx, const uint8_t* pts_le_xy, const uint8_t* scalars, size_t groups, size_t m, uint8_t* out_nodes_le_xy,
+                              uint8_t* out_inf) {
+    return abi_guard("claim tree selftest", [&]() -> int {
+        TRY(use_ctx(ctx));
+        if (!pts_le_xy || !scalars || !out_nodes_le_xy || !out_inf) return fail(DR_ERR_INVALID, "null buffer");
+        if (groups == 0 || groups > 4096 || m == 0 || m > 64) return fail(DR_ERR_INVALID, "1..4096 groups of 1..64 terms");
+        const size_t n = groups * m;
+        for (size_t i = 0; i < 2 * n; i++) {                                // coordinates below p: the device brings them to Montgomery form
+            drh::Fq v;
+            if (!drh::Fq::load_le(v, pts_le_xy + 48 * i)) return fail(DR_ERR_INVALID, "coordinate out of range");
+        }
+        TRY(ctx->buckets.reserve(n * 96));
+        HIP_TRY(hipMemcpyAsync(ctx->buckets.p, pts_le_xy, n * 96, hipMemcpyHostToDevice, ctx->stream));
+        g1_launch_bases_to_mont(ctx->stream, ctx->buckets.as<uint32_t>(), n);
+        HIP_TRY(hipGetLastError());
+        const uint32_t off[2] = {0, 0}, mm[2] = {(uint32_t)m, 0};
+        TRY(g1_claim_tree(ctx, ctx->buckets.as<uint32_t>(), nullptr, scalars, groups, m, 1, off, mm, out_nodes_le_xy));
+        const size_t nodes = 2 * g1_claim_tree_padded(groups) - 1;
+        for (size_t k = 0; k < nodes; k++) {
+            bool inf = true;
+            for (int q = 0; q < 96; q++) if (out_nodes_le_xy[96 * k + q]) { inf = false; break; }
+            out_inf[k] = inf ? 1 : 0;
+        }
+        return DR_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------- seam B

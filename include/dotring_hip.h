@@ -962,6 +962,36 @@ DR_API int dr_ringvrf_verify_batch_multi(dr_ctx *const *ctxs, size_t n_ctxs, con
                                          const uint8_t *ads, const uint64_t *ad_off, const uint8_t *salts, const uint64_t *salt_off,
                                          const uint8_t seed32[32], int *ok);
 
+/* ---- RingVRF.verify_each: a verdict PER PROOF from one batch pass -----
+ * dr_ringvrf_verify_batch answers with one bit; this call says which proofs fail.  Same arguments, refusals and phases; then
+ *  - a malformed proof (non-canonical scalar, a point that does not decode, zeta inside the domain) no longer rejects the call:
+ *    its verdict is 0 and it leaves the combination (scalars zero, undecodable points the identity);
+ *  - ring part: per proof the claim points L_i (seven claim scalars on its own points, four on C_px, C_py, C_s, G1[0]) and
+ *    R_i (r1, r2 on its opening proofs) and the tree of their subset sums are computed on the GPU (csrc/kernels_g1_claims.hip.h) and
+ *    downloaded in one copy; e(L, G2[0]) e(-R, G2[1]) == 1 is tested at the root — if it holds, every proof left in passes with ONE
+ *    equation, as in batch_verify — and otherwise down the tree, only below nodes that fail (csrc/verify_tree.hpp);
+ *  - Pedersen part: per proof exactly, O_k = s I - c O and R = s G + s_b B - c Y_bar, 2 * batch groups of three terms in one launch.
+ * verdicts[i] = 1 iff proof i verifies.  stats (nullable, 4 words): [0] pairing equations evaluated, [1] proofs excluded before
+ * the fold, [2] depth of the tree (ceil(log2 batch)), [3] reserved, 0.  Up to DOTRING_VERIFY_HOST_MAX proofs the points and
+ * the tree come from the host route of dr_ringvrf_verify_batch.  The _multi form shards as dr_ringvrf_verify_batch_multi does: every
+ * shard writes its slice of `verdicts`; stats are summed, the depth is the largest. */
+DR_API int dr_ringvrf_verify_each(dr_ctx *ctx, const dr_vrf_suite *suite, const dr_ring_verifier_key *vk, size_t batch,
+                                  const uint8_t *proofs, const uint8_t *inputs, const uint64_t *in_off, const uint8_t *ads,
+                                  const uint64_t *ad_off, const uint8_t *salts, const uint64_t *salt_off,
+                                  const uint8_t seed32[32], uint8_t *verdicts /* batch */, uint32_t *stats /* nullable, 4 words */);
+DR_API int dr_ringvrf_verify_each_multi(dr_ctx *const *ctxs, size_t n_ctxs, const dr_vrf_suite *suite, const dr_ring_verifier_key *vk,
+                                        size_t batch, const uint8_t *proofs, const uint8_t *inputs, const uint64_t *in_off,
+                                        const uint8_t *ads, const uint64_t *ad_off, const uint8_t *salts, const uint64_t *salt_off,
+                                        const uint8_t seed32[32], uint8_t *verdicts, uint32_t *stats);
+
+/* Diagnostic: the claim-point and tree kernels on caller-supplied groups.  `groups` (1..4096) groups of m (1..64) terms: points
+ * affine standard-form little-endian x || y (96 bytes, coordinates below p, all zero = infinity), scalars 32 bytes little-endian,
+ * any value below 2^256.  Leaf g is the sum of its group's m terms.  Node array: 2 * Bp - 1 nodes, Bp = groups rounded up to a power
+ * of two (the padding leaves are the identity), in heap order — node 0 is the root, the children of node k are 2k + 1 and 2k + 2,
+ * leaf g is node Bp - 1 + g.  out_nodes_le_xy: 96 bytes per node as the input points; out_inf: one byte per node, 1 for the identity. */
+DR_API int dr_g1_claim_tree_selftest(dr_ctx *ctx, const uint8_t *pts_le_xy /* groups*m*96 */, const uint8_t *scalars /* groups*m*32 */,
+                                     size_t groups, size_t m, uint8_t *out_nodes_le_xy /* (2*Bp-1)*96 */, uint8_t *out_inf /* 2*Bp-1 */);
+
 #ifdef __cplusplus
 }
 #endif
